@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the graph-Laplacian image filter hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One step = one whole pass of the approximate path (affinity/degree -> L_A ->
 inverse subspace iteration -> Nystroem contraction -> spectral filter) over one
@@ -11,7 +11,9 @@ SAME image is split by pixel rows over the N ranks (strong scaling); the driver
 launches one rank per GPU through torch.distributed.run and the all-reduces
 (degree vector, Phi^T y) go over RCCL.
 
-Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings).
+Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings). A plain run sets up, warms up, times the
+K steps and prints the headline line; --full adds the other legs (other paths and workloads, host-to-host timing), the CPU
+baseline and the parity checks against the fp64 oracle.
 """
 import argparse
 import json
@@ -99,7 +101,46 @@ def parse_args():
                          "loopback backend (host-staged collectives); prints per-rank stage times and the collectives per step")
     ap.add_argument("--no-direct-leg", action="store_true",
                     help="skip the direct_contraction leg (one step with the entry-by-entry Nystroem kernel, ~0.5 s)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline steps, run the other legs (host_to_host, exact_grid_form, rank_form, exact_zero_skipping, "
+                         "direct_contraction, nlm, throughput_mode) and the CPU baseline with its parity checks; the --no-* options "
+                         "leave out single ones")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them returned as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:   # a plain run does what the headline line needs and nothing else
+        for leg in ("cpu_baseline", "skip_leg", "parity", "nlm_leg", "batch_leg", "exact_leg", "host_leg", "direct_leg"):
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+DUMP_PIXELS = 1 << 23   # pixels of the filtered image in out_sample.npy: 32 MiB as float32 (a whole 4096^2 image would be 64 MiB)
+
+
+def dump_outputs(path, d_out, info, world):
+    """--dump-outputs: what a caller of the timed path received from its last step, so that two builds can be compared output
+    for output (the inputs are fixed by the arguments):
+      out_sample.npy  float32  the filtered 8-bit image at DUMP_PIXELS pixels drawn with seed 0, in raster order
+      eigvals.npy     float64  the m eigenvalues
+      alpha.npy       float64  [alpha], the normalisation of L_A
+    With N > 1 ranks each rank fills only its own image rows of d_out (the rest stays zero), so the sample is summed over the
+    ranks. Call on every rank; rank 0 writes."""
+    n = d_out.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_PIXELS), replace=False))
+    sample = d_out.view(-1)[torch.from_numpy(idx).to(d_out.device)].float()
+    if world > 1:
+        dist.all_reduce(sample)
+    if int(os.environ.get("RANK", "0")) != 0:
+        return
+    if not os.path.isdir(path):
+        os.makedirs(path)
+        with open(os.path.join(path, ".gitignore"), "w") as f:   # a dump inside a checkout leaves `git status` clean
+            f.write("*\n")
+    np.save(os.path.join(path, "out_sample.npy"), sample.cpu().numpy())
+    np.save(os.path.join(path, "eigvals.npy"), np.asarray(info["eigvals"], dtype=np.float64))
+    np.save(os.path.join(path, "alpha.npy"), np.array([info["alpha"]], dtype=np.float64))
 
 
 def cpu_baseline(img, info, args):
@@ -392,6 +433,8 @@ def main():
     if world > 1 or args.force_comm:
         ctx.comm_counters(reset=True)
     sec_per_step, info, avg_ms, stage_ms = run_leg(opt)
+    if args.dump_outputs:   # before any other leg writes d_out
+        dump_outputs(args.dump_outputs, d_out, info, world)
     ms_per_step = sec_per_step * 1e3
     value = N / sec_per_step * 1e-6
     # what the communicator reports, the collectives of a step, every rank's stage times

@@ -5,7 +5,7 @@ set -e
 tag=${1:-r01}
 cd /tmp; export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out
-python3 bench.py --steps 3 --warmup 1 > $out/bench_plain.json 2> $out/bench_plain.err
+python3 bench.py --steps 3 --warmup 1 --full > $out/bench_plain.json 2> $out/bench_plain.err
 # the profiled run holds the headline steps only (no skipping / throughput / direct-contraction legs, which launch the same kernels on
 # other workloads): its per-kernel averages are the ones bench.py's roofline block reports
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-parity --no-skip-leg --no-direct-leg --no-batch-leg --no-exact-leg --no-host-leg --no-nlm-leg > $out/bench_under_rocprof.json 2> $out/stats.err
