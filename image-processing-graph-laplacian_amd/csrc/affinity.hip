@@ -380,6 +380,15 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 #include "grid_common.inc"
 #include "affinity_grid.inc"
 
+// U_s[(a,b)] = sum over the image rows [row0, row1) of K(sample, px) s[px] for a float plane s (joint filtering): the grid-factored
+// degree with s as the histogram weight. GLF_ERR_UNSUPPORTED where the grid-factored degree does not apply.
+int weighted_sums_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
+                       const unsigned *h_idx, KernelCoef coef, int window, const float *d_plane, double wabs, double *d_out)
+{
+    if (coef.kernel == GLF_KERNEL_NLM) return GLF_ERR_UNSUPPORTED;
+    return degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_out, window, nullptr, nullptr, d_plane, wabs);
+}
+
 // D_A over the image rows [row0, row1): the grid-factored form when the samples are a tensor grid, else the
 // direct sweep (windowed when exact zeros may be skipped). *evaluated = kernel entries represented.
 int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples,

@@ -24,13 +24,18 @@
 // Wt[rl][v][b] for one image row. Ec(c - C_b) comes from an LDS copy of the factor table (index clamped to `ne - 1`,
 // where the factor is exactly 0 or the table ends) -- reading the (W x nc) table row of every pixel instead cost 20 GB
 // of L2 traffic per image (3.7 ms vs 1 ms at cfg4).
+// WEIGHTED: every pixel's Ec term is multiplied by its value in the float plane `wplane` (rows from the shard's first row):
+// Wt_s[r][v][b] = sum_{c : img[r][c] = v} s[r][c] Ec(c - C_b), the histogram of the value-weighted sums Phi^T s (joint filtering)
 constexpr int DGRID_NE_MAX = 8192;
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_dgrid_hist(const float *__restrict__ etab, int ne, const int *__restrict__ gcol, int nc,
                                                      int ncp, const unsigned short *__restrict__ scol,
-                                                     const unsigned *__restrict__ goff, int width, float *__restrict__ Wt)
+                                                     const unsigned *__restrict__ goff, int width, float *__restrict__ Wt,
+                                                     const float *__restrict__ wplane)
 {
-    extern __shared__ float etab_s[]; // [ne], then the row's value-sorted columns u16 [width]
+    extern __shared__ float etab_s[]; // [ne], then the row's value-sorted columns u16 [width] (WEIGHTED: then the row's weights)
     unsigned short *sc_s = reinterpret_cast<unsigned short *>(etab_s + ne);
+    float *w_s = reinterpret_cast<float *>(etab_s + ne + (width + 1) / 2);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int rl = blockIdx.x;
     const unsigned short *sc = scol + (size_t)rl * width;
@@ -39,6 +44,8 @@ __global__ __launch_bounds__(256) void k_dgrid_hist(const float *__restrict__ et
     // (the loop below walks a value's pixels one after the other: a global load of the column per pixel put its latency on
     // every step; from LDS, and with eight pixels' gathers in flight at a time, 1.25 -> 0.94 ms at cfg4)
     for (int i = threadIdx.x; i < width; i += 256) sc_s[i] = sc[i];
+    if (WEIGHTED)
+        for (int i = threadIdx.x; i < width; i += 256) w_s[i] = wplane[(size_t)rl * width + i];
     __syncthreads();
     constexpr int NB = 10; // ncp <= 640
     int gc[NB];
@@ -71,6 +78,13 @@ __global__ __launch_bounds__(256) void k_dgrid_hist(const float *__restrict__ et
                     if (in == 0ull) continue;
                     const int k0 = kb + __builtin_ctzll(in), k1 = k0 + __builtin_popcountll(in);
                     int k = k0;
+                    if (WEIGHTED) {
+                        for (; k < k1; ++k) {
+                            const int c0 = (int)sc_s[k];
+                            acc[i] = fmaf(w_s[c0], etab_s[min(abs(c0 - gc[i]), ne - 1)], acc[i]);
+                        }
+                        continue;
+                    }
                     for (; k + 4 <= k1; k += 4) { // (the additions stay in pixel order: only the gathers are hoisted)
                         const int c0 = (int)sc_s[k], c1 = (int)sc_s[k + 1], c2 = (int)sc_s[k + 2], c3 = (int)sc_s[k + 3]; // wave-uniform
                         const float e0 = etab_s[min(abs(c0 - gc[i]), ne - 1)], e1 = etab_s[min(abs(c1 - gc[i]), ne - 1)];
@@ -275,8 +289,10 @@ __global__ __launch_bounds__(256) void k_dgrid_final_parts(const float *__restri
         const float *z = Zpart + (size_t)a * ncols + b;
         // chunks of DGZ_CHUNK image rows all farther than the table's radius (its first exact zero) from this grid row hold
         // exact zeros (every Er fragment of theirs is zero): not read -- adding +0 leaves the sum as it is
-        const int ra = grow[a] - row0;
-        const int c_lo = max(0, (ra - radius + 1) / DGZ_CHUNK), c_hi = min(nchunks - 1, max(0, ra + radius - 1) / DGZ_CHUNK);
+        // A grid row out of reach above the shard (ra + radius - 1 < 0) has an empty range: its m-tile may lie below the first
+        // one k_dgrid_zmfma stored for chunk 0 in window shape, so chunk 0 must not be read for it.
+        const int ra = grow[a] - row0, hi = ra + radius - 1;
+        const int c_lo = max(0, (ra - radius + 1) / DGZ_CHUNK), c_hi = hi < 0 ? -1 : min(nchunks - 1, hi / DGZ_CHUNK);
         for (int v = vl; v < 256; v += 8) {
             double zs = 0.0;
             for (int c = c_lo; c <= c_hi; ++c) zs += (double)z[(size_t)c * cstride + (size_t)v * ncp];
@@ -301,9 +317,11 @@ __global__ __launch_bounds__(256) void k_dgrid_final_parts(const float *__restri
 }
 
 // GLF_ERR_UNSUPPORTED = not a grid (or too wide): the caller runs the direct sweep.
+// d_wplane (joint filtering): d_degree receives U_s[(a,b)] = sum over the shard's pixels of K(sample, px) s[px] instead, with
+// s = the float plane d_wplane [height][width] (absolute rows) and wabs >= max |s| (the f16 operand scale); d_ysum must be null.
 static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1,
                             const float4 *d_samples, unsigned p, const unsigned *h_idx, KernelCoef coef, double *d_degree,
-                            int window, double *evaluated, double *d_ysum)
+                            int window, double *evaluated, double *d_ysum, const float *d_wplane = nullptr, double wabs = 1.0)
 {
     if (!grid_path_wanted(ctx->tune.deg_path, width) || width > GRID_MAX_W || p < 4 || row0 >= row1 || coef.kernel == GLF_KERNEL_NLM)
         return GLF_ERR_UNSUPPORTED;
@@ -319,8 +337,12 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
     // entries of the factor table the histogram needs: up to the first exact zero (kept as the clamp target)
     const int ne = std::min(gt.maxdim, gt.radius + 1);
     if (ne > DGRID_NE_MAX) return GLF_ERR_UNSUPPORTED; // (a kernel this wide on an image this large: the direct sweep runs)
-    hipLaunchKernelGGL(k_dgrid_hist, dim3(nrows), dim3(256), (size_t)ne * sizeof(float) + (size_t)width * 2, st, gt.etab(), ne, gt.gcol(), gt.nc, gt.ncp,
-                       gt.scol.p, gt.goff.p, width, Wt.p);
+    if (d_wplane)
+        hipLaunchKernelGGL(k_dgrid_hist<true>, dim3(nrows), dim3(256), (size_t)ne * sizeof(float) + (size_t)((width + 1) / 2) * 4 + (size_t)width * 4,
+                           st, gt.etab(), ne, gt.gcol(), gt.nc, gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, d_wplane + (size_t)row0 * width);
+    else
+        hipLaunchKernelGGL(k_dgrid_hist<false>, dim3(nrows), dim3(256), (size_t)ne * sizeof(float) + (size_t)width * 2, st, gt.etab(), ne, gt.gcol(), gt.nc,
+                           gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, (const float *)nullptr);
     const bool skip = window && gt.can_skip(coef);
     // row contraction on the matrix pipe (k_dgrid_zmfma): Wt entries are sums of Ec over a row's pixels of one value, bounded by
     // the whole factor table's mass -> one power-of-two scale keeps 2^wsh Wt below the f16 range
@@ -329,6 +351,7 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
         const double s_loc = (double)coef.s_loc;
         for (int d = 1; d < width; ++d) wmax += std::exp2(-s_loc * (double)d * (double)d);
         wmax = 1.0 + 2.0 * wmax;
+        if (d_wplane) wmax *= wabs > 0.0 ? wabs : 1.0; // signed weights: |Wt_s| <= max |s| x the table's mass
     }
     int wexp = 0;
     (void)std::frexp(wmax, &wexp);       // wmax < 2^wexp

@@ -394,8 +394,26 @@ const char *glf_multi_last_error(const glf_multi *w) { return w ? w->last_error 
 
 // One rank thread per GPU: replicate the image (hpc/image_processing.c:45-76 broadcasts it to every rank), run the sharded
 // path, copy this rank's pixel rows of the result back (hpc/utils.c:502-527 gathers to rank 0).
+// nsig > 0: signal planes h_sig [nsig][N] replicated on every rank, each rank's pixel rows of the results into h_sig_out
+static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out, float *h_zf,
+                     double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out);
+
 int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out,
                                float *h_zf, double *eigvals_out, glf_stats *stats)
+{
+    return multi_run(w, opt, h_img, width, height, h_out, h_zf, eigvals_out, stats, 0, nullptr, nullptr);
+}
+
+int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, int nsig,
+                                       const float *h_sig, float *h_sig_out, uint8_t *h_out, float *h_zf, double *eigvals_out,
+                                       glf_stats *stats)
+{
+    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
+    return multi_run(w, opt, h_img, width, height, h_out, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
+}
+
+static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out, float *h_zf,
+                     double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out)
 {
     if (!w || !h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     if (w->broken) {
@@ -431,12 +449,28 @@ int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8
             step(hipStreamSynchronize(ctx->stream));
         }
         glf_stats st{};
-        if (rc == GLF_OK) rc = glf_image_processing(ctx, opt, b.d_img, width, height, b.d_out, h_zf ? b.d_zf : nullptr,
-                                                    r == 0 ? eigvals_out : nullptr, &st);
+        DevBuf<float> sig_in, sig_out; // (from the context's pool: the planes are not kept between calls)
+        float *d_sig = nullptr, *d_sig_out = nullptr;
+        if (rc == GLF_OK && nsig > 0) {
+            rc = sig_in.alloc(ctx, (size_t)nsig * N);
+            if (rc == GLF_OK) rc = sig_out.alloc(ctx, (size_t)nsig * N);
+            d_sig = sig_in.p;
+            d_sig_out = sig_out.p;
+            if (rc == GLF_OK) step(hipMemcpyAsync(d_sig, h_sig, (size_t)nsig * N * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            step(hipStreamSynchronize(ctx->stream));
+        }
+        if (rc == GLF_OK)
+            rc = nsig > 0 ? glf_image_processing_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out,
+                                                         h_zf ? b.d_zf : nullptr, r == 0 ? eigvals_out : nullptr, &st)
+                          : glf_image_processing(ctx, opt, b.d_img, width, height, b.d_out, h_zf ? b.d_zf : nullptr,
+                                                 r == 0 ? eigvals_out : nullptr, &st);
         if (rc == GLF_OK) {
             const size_t o = (size_t)st.row0 * width, len = (size_t)(st.row1 - st.row0) * width;
             if (len) step(hipMemcpyAsync(h_out + o, b.d_out + o, len, hipMemcpyDeviceToHost, ctx->stream));
             if (len && h_zf) step(hipMemcpyAsync(h_zf + o, b.d_zf + o, len * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            for (int k = 0; k < nsig && len; ++k)
+                step(hipMemcpyAsync(h_sig_out + (size_t)k * N + o, d_sig_out + (size_t)k * N + o, len * sizeof(float), hipMemcpyDeviceToHost,
+                                    ctx->stream));
             step(hipStreamSynchronize(ctx->stream));
             if (stats) stats[r] = st;
         }

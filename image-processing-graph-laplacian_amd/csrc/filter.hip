@@ -6,6 +6,7 @@
 #include "glf_internal.hpp"
 
 #include <algorithm>
+#include <cstring>
 
 namespace glf {
 
@@ -80,7 +81,7 @@ int phi_t_y(glf_ctx *ctx, const float *d_phi, const uint8_t *d_img, int64_t pix0
 __global__ __launch_bounds__(256) void k_c_from_ysum(const float *__restrict__ psi, const float *__restrict__ phiA,
                                                       const double *__restrict__ ysum, const float *__restrict__ t, unsigned t_ld,
                                                       const float4 *__restrict__ samples, unsigned p, unsigned ld,
-                                                      double *__restrict__ partial)
+                                                      double *__restrict__ partial, const float *__restrict__ sval)
 {
     __shared__ double sh[256];
     const int col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld;
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void k_c_from_ysum(const float *__restrict__ p
         if (s >= p) break;
         const double u = ysum[s] - (double)t[(size_t)s * t_ld];
         acc = fma((double)psi[(size_t)s * ld + col], u, acc);
-        acc = fma((double)phiA[(size_t)s * ld + col], (double)samples[s].z, acc);
+        acc = fma((double)phiA[(size_t)s * ld + col], sval ? (double)sval[(size_t)s * t_ld] : (double)samples[s].z, acc);
     }
     sh[threadIdx.x] = acc;
     __syncthreads();
@@ -103,13 +104,13 @@ __global__ __launch_bounds__(256) void k_c_from_ysum(const float *__restrict__ p
 }
 
 int c_from_ysum(glf_ctx *ctx, const float *d_psi, const float *d_phiA, const double *d_ysum, const float *d_t, unsigned t_ld,
-                const float4 *d_samples, unsigned p, unsigned ld, double *d_c)
+                const float4 *d_samples, unsigned p, unsigned ld, double *d_c, const float *d_sval)
 {
     if (!valid_ld(ld)) return set_error(ctx, GLF_ERR_INVALID, "c_from_ysum: ld=%u", ld);
     const int nblk = (int)ceil_div(p, 128u);
     DevBuf<double> part;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ld));
-    hipLaunchKernelGGL(k_c_from_ysum, dim3(nblk), dim3(256), 0, ctx->stream, d_psi, d_phiA, d_ysum, d_t, t_ld, d_samples, p, ld, part.p);
+    hipLaunchKernelGGL(k_c_from_ysum, dim3(nblk), dim3(256), 0, ctx->stream, d_psi, d_phiA, d_ysum, d_t, t_ld, d_samples, p, ld, part.p, d_sval);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld), dim3(256), 0, ctx->stream, part.p, nblk, ld, d_c);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (part goes out of scope)
@@ -257,6 +258,173 @@ int apply_filter(glf_ctx *ctx, const uint8_t *d_img, const float *d_phi, int64_t
     case 64: hipLaunchKernelGGL(k_apply_filter<64>, grid, block, 0, ctx->stream, d_img, d_phi, pix0, pix1, d_w, gain, ysub, d_out, d_zf, d_corr); break;
     case 128: hipLaunchKernelGGL(k_apply_filter<128>, grid, block, 0, ctx->stream, d_img, d_phi, pix0, pix1, d_w, gain, ysub, d_out, d_zf, d_corr); break;
     case 256: hipLaunchKernelGGL(k_apply_filter<256>, grid, block, 0, ctx->stream, d_img, d_phi, pix0, pix1, d_w, gain, ysub, d_out, d_zf, d_corr); break;
+    }
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+// ---- extra signal planes through the guide's operator (glf_image_processing_signals) ------------------------------------
+// Each plane s_k (float [N], replicated) goes through z_k = (1 - ysub) s_k + gain Phi w_k with w_k = f(Pi) Phi^T s_k. Every
+// signal is its own accumulator chain in the same order whatever nsig is, so a plane's result does not depend on the others.
+
+// partial[blk][k][j] = sum_{pix in blk} Phi[pix][j] * s_k[pix]: one read of Phi for all planes. The products are exact in
+// f64 and summed in f64: a signed, zero-mean plane (chroma, a noise field) makes Phi^T s a sum with heavy cancellation, where
+// k_phi_t_y's bounded f32 chains would lose ~1e-7 x sqrt(N) of it
+__global__ __launch_bounds__(256) void k_phi_t_signals(const float *__restrict__ phi, const float *__restrict__ sig, int64_t N, int nsig,
+                                                        int64_t pix0, int64_t pix1, unsigned ld, double *__restrict__ partial)
+{
+    __shared__ double sh[GLF_MAX_SIGNALS][256];
+    const int col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld;
+    const int64_t base = pix0 + (int64_t)blockIdx.x * 1024;
+    double s[GLF_MAX_SIGNALS];
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k) s[k] = 0.0;
+    for (int64_t r = rl; r < 1024; r += nrl) {
+        const int64_t px = base + r;
+        if (px >= pix1) break;
+        const double f = (double)phi[(size_t)px * ld + col];
+#pragma unroll
+        for (int k = 0; k < GLF_MAX_SIGNALS; ++k)
+            if (k < nsig) s[k] = fma(f, (double)sig[(size_t)k * N + px], s[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k) sh[k][threadIdx.x] = s[k];
+    __syncthreads();
+    if (threadIdx.x < ld)
+        for (int k = 0; k < nsig; ++k) {
+            double t = 0.0;
+            for (int r = 0; r < nrl; ++r) t += sh[k][r * ld + col];
+            partial[((size_t)blockIdx.x * nsig + k) * ld + col] = t;
+        }
+}
+
+int phi_t_signals(glf_ctx *ctx, const float *d_phi, const float *d_sig, int64_t N, int nsig, int64_t pix0, int64_t pix1, unsigned ld,
+                  double *d_c)
+{
+    if (!valid_ld(ld) || pix0 > pix1 || nsig < 1 || nsig > GLF_MAX_SIGNALS)
+        return set_error(ctx, GLF_ERR_INVALID, "phi_t_signals: ld=%u nsig=%d", ld, nsig);
+    if (pix0 == pix1) {
+        GLF_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof(double) * ld * nsig, ctx->stream));
+        return GLF_OK;
+    }
+    const int nblk = (int)ceil_div(pix1 - pix0, 1024);
+    DevBuf<double> part;
+    GLF_TRY(part.alloc(ctx, (size_t)nblk * nsig * ld));
+    hipLaunchKernelGGL(k_phi_t_signals, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_sig, N, nsig, pix0, pix1, ld, part.p);
+    hipLaunchKernelGGL(k_cols_sum, dim3(ld * nsig), dim3(256), 0, ctx->stream, part.p, nblk, ld * nsig, d_c);
+    GLF_LAUNCH_CHECK(ctx);
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GLF_OK;
+}
+
+// out_k[pix] = s_k + (gain * sum_j Phi[pix][j] w_k[j] - ysub * s_k): k_apply_filter's per-pixel arithmetic with the plane's
+// value in place of y, unclamped; each Phi row read once for all planes
+template <int LD>
+__global__ __launch_bounds__(256) void k_apply_filter_signals(const float *__restrict__ phi, int64_t pix0, int64_t pix1, int nsig,
+                                                               const float *__restrict__ w, float gain, float ysub,
+                                                               const float *__restrict__ sig, float *__restrict__ out, int64_t N)
+{
+    constexpr int LPP = LD / 4, PPB = 256 / LPP;
+    const int q = threadIdx.x % LPP, pl = threadIdx.x / LPP;
+    float4 wq[GLF_MAX_SIGNALS];
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k)
+        wq[k] = k < nsig ? reinterpret_cast<const float4 *>(w + (size_t)k * LD)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t px = pix0 + (int64_t)blockIdx.x * PPB + pl; px < pix1; px += (int64_t)gridDim.x * PPB) {
+        const float4 f = reinterpret_cast<const float4 *>(phi + (size_t)px * LD)[q];
+#pragma unroll
+        for (int k = 0; k < GLF_MAX_SIGNALS; ++k) {
+            if (k >= nsig) break;
+            float s = f.x * wq[k].x + f.y * wq[k].y + f.z * wq[k].z + f.w * wq[k].w;
+#pragma unroll
+            for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (q == 0) {
+                const float v = sig[(size_t)k * N + px];
+                const float c = gain * s - ysub * v;
+                out[(size_t)k * N + px] = v + c;
+            }
+        }
+    }
+}
+
+// max |s| over n floats (the f16 operand scale of the weighted histogram): non-negative floats order as their bit patterns
+__global__ __launch_bounds__(256) void k_plane_absmax(const float *__restrict__ s, int64_t n, unsigned *__restrict__ out)
+{
+    float m = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = fmaxf(m, fabsf(s[i]));
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+}
+
+int plane_absmax(glf_ctx *ctx, const float *d_s, int64_t n, float *h_max)
+{
+    *h_max = 0.f;
+    if (n <= 0) return GLF_OK;
+    DevBuf<unsigned> m;
+    GLF_TRY(m.alloc(ctx, 1));
+    GLF_HIP(ctx, hipMemsetAsync(m.p, 0, sizeof(unsigned), ctx->stream));
+    hipLaunchKernelGGL(k_plane_absmax, dim3((unsigned)std::min<int64_t>(1024, ceil_div(n, 256))), dim3(256), 0, ctx->stream, d_s, n, m.p);
+    GLF_LAUNCH_CHECK(ctx);
+    unsigned bits = 0;
+    GLF_HIP(ctx, hipMemcpyAsync(&bits, m.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::memcpy(h_max, &bits, sizeof(float));
+    return GLF_OK;
+}
+
+// the planes at n sample pixels px = idx[i], each from its row of Phi_A (k_filter_sample_rows' arithmetic per plane)
+template <int LD>
+__global__ __launch_bounds__(256) void k_filter_sample_rows_signals(const float *__restrict__ phiA, unsigned n, const uint32_t *__restrict__ idx,
+                                                                     int nsig, const float *__restrict__ w, float gain, float ysub,
+                                                                     const float *__restrict__ sig, float *__restrict__ out, int64_t N)
+{
+    constexpr int LPP = LD / 4, PPB = 256 / LPP;
+    const int q = threadIdx.x % LPP, pl = threadIdx.x / LPP;
+    const unsigned i = blockIdx.x * PPB + pl;
+    const bool live = i < n;
+    const float4 f = live ? reinterpret_cast<const float4 *>(phiA + (size_t)i * LD)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < nsig; ++k) {
+        const float4 wq = reinterpret_cast<const float4 *>(w + (size_t)k * LD)[q];
+        float s = f.x * wq.x + f.y * wq.y + f.z * wq.z + f.w * wq.w;
+#pragma unroll
+        for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (q == 0 && live) {
+            const int64_t px = (int64_t)idx[i];
+            const float v = sig[(size_t)k * N + px];
+            out[(size_t)k * N + px] = v + (gain * s - ysub * v);
+        }
+    }
+}
+
+int filter_sample_rows_signals(glf_ctx *ctx, const float *d_phiA, unsigned n, unsigned ld, const uint32_t *d_idx, int nsig, const float *d_w,
+                               float gain, float ysub, const float *d_sig, float *d_out, int64_t N)
+{
+    if (n == 0) return GLF_OK;
+    if ((ld != 32 && ld != 64) || nsig < 1 || nsig > GLF_MAX_SIGNALS)
+        return set_error(ctx, GLF_ERR_INVALID, "filter_sample_rows_signals: ld=%u nsig=%d", ld, nsig);
+    const unsigned ppb = 256 / (ld / 4);
+    const dim3 grid((unsigned)ceil_div(n, ppb)), block(256);
+    if (ld == 32) hipLaunchKernelGGL(k_filter_sample_rows_signals<32>, grid, block, 0, ctx->stream, d_phiA, n, d_idx, nsig, d_w, gain, ysub, d_sig, d_out, N);
+    else hipLaunchKernelGGL(k_filter_sample_rows_signals<64>, grid, block, 0, ctx->stream, d_phiA, n, d_idx, nsig, d_w, gain, ysub, d_sig, d_out, N);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w, float gain,
+                         float ysub, const float *d_sig, float *d_out, int64_t N)
+{
+    if (!valid_ld(ld) || pix0 > pix1 || nsig < 1 || nsig > GLF_MAX_SIGNALS)
+        return set_error(ctx, GLF_ERR_INVALID, "apply_filter_signals: ld=%u nsig=%d", ld, nsig);
+    if (pix0 == pix1) return GLF_OK;
+    const int ppb = 256 / (ld / 4);
+    int64_t nblk = ceil_div(pix1 - pix0, ppb);
+    if (nblk > 8192) nblk = 8192; // grid-stride the rest
+    dim3 grid((unsigned)nblk), block(256);
+    switch (ld) {
+    case 32: hipLaunchKernelGGL(k_apply_filter_signals<32>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
+    case 64: hipLaunchKernelGGL(k_apply_filter_signals<64>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
+    case 128: hipLaunchKernelGGL(k_apply_filter_signals<128>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
+    case 256: hipLaunchKernelGGL(k_apply_filter_signals<256>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
     }
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;

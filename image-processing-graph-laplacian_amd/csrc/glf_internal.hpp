@@ -285,6 +285,8 @@ int start_block_cached(glf_ctx *ctx, unsigned p, unsigned m, unsigned ld, unsign
 int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples,
                      unsigned p, const unsigned *h_idx, KernelCoef coef, double *d_degree, int window, double *evaluated,
                      const uint32_t *d_idx = nullptr, double *d_ysum = nullptr, bool *have_ysum = nullptr);
+int weighted_sums_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
+                       const unsigned *h_idx, KernelCoef coef, int window, const float *d_plane, double wabs, double *d_out);
 int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1,
                          const float4 *d_samples, unsigned p, const unsigned *h_idx, KernelCoef coef,
                          double *d_degree, double *evaluated);
@@ -334,7 +336,16 @@ unsigned grid_op_rows_per_rank(const GridOp *op, int size); // all-gather block:
 void band_cache_free(glf_ctx *ctx);
 // Filter applied in the epilogue of the band-form Nystroem kernel: z = y + gain Phi[px] . w - ysub y straight from the
 // accumulators, Phi itself never written (hpc/display.c:60-78 fused into hpc/nystroem.c:41-42)
+// joint filtering in k_band's epilogue: nsig float planes through the guide's filter (weights [nsig][ld], planes [nsig][N])
+struct BandSignals {
+    int nsig = 0;
+    const float *w = nullptr;
+    const float *s = nullptr;
+    float *out = nullptr;
+    int64_t N = 0;
+};
 struct BandFilter {
+    BandSignals sig;
     const float *w = nullptr; // [ld] filter weights x c (device)
     float gain = 0.f, ysub = 0.f;
     uint8_t *out = nullptr;   // [N] (absolute pixel index)
@@ -349,7 +360,7 @@ int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 // c = Psi^T (ysum - t) + Phi_A^T y_A  (ysum: the degree stage's value-weighted sums over all pixels; t = K_A y_A takes the
 // sample pixels out again): Phi^T y without Phi. d_c [ld] f64.
 int c_from_ysum(glf_ctx *ctx, const float *d_psi, const float *d_phiA, const double *d_ysum, const float *d_t, unsigned t_ld,
-                const float4 *d_samples, unsigned p, unsigned ld, double *d_c);
+                const float4 *d_samples, unsigned p, unsigned ld, double *d_c, const float *d_sval = nullptr); // d_sval: s_A [p][t_ld] in place of y_A
 // the sample pixels' outputs from their rows of Phi_A (the band kernel filters every pixel with its extended row)
 int filter_sample_rows(glf_ctx *ctx, const float *d_phiA, unsigned n, unsigned ld, const uint32_t *d_idx, const uint8_t *d_img,
                        const float *d_w, float gain, float ysub, uint8_t *d_out, float *d_zf, float *d_corr, int64_t pix0);
@@ -420,6 +431,15 @@ int phi_gram(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsig
 int apply_filter(glf_ctx *ctx, const uint8_t *d_img, const float *d_phi, int64_t pix0, int64_t pix1,
                  unsigned m, unsigned ld, const float *d_w, float gain, float ysub, uint8_t *d_out, float *d_zf,
                  float *d_corr = nullptr);
+// extra signal planes (glf_image_processing_signals): d_sig / d_out [nsig][N] float, rows [pix0, pix1) only;
+// d_c [nsig][ld] (f64) = Phi^T s_k over this rank's pixels; d_w [nsig][ld]
+int phi_t_signals(glf_ctx *ctx, const float *d_phi, const float *d_sig, int64_t N, int nsig, int64_t pix0, int64_t pix1, unsigned ld,
+                  double *d_c);
+int plane_absmax(glf_ctx *ctx, const float *d_s, int64_t n, float *h_max); // max |s| of a device float array
+int filter_sample_rows_signals(glf_ctx *ctx, const float *d_phiA, unsigned n, unsigned ld, const uint32_t *d_idx, int nsig, const float *d_w,
+                               float gain, float ysub, const float *d_sig, float *d_out, int64_t N);
+int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w, float gain,
+                         float ysub, const float *d_sig, float *d_out, int64_t N);
 // the same filter panel by panel (m > 256): acc[px - pix0] (+)= sum_j Phi[px][j] w[j], then z = (1 - ysub) y + gain * acc
 int filter_accumulate(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float *d_acc,
                       bool first);

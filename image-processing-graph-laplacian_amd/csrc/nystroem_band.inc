@@ -142,7 +142,8 @@ __device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
 // SAMPLES = false: targets = the pixels of image rows [row_begin, row_begin + gridDim.y): out = Phi (+ column offset), epilogue
 //   as k_nystroem_f16s (sample pixels skipped unless raster; c += Phi^T y per workgroup).
 // SAMPLES = true: targets = the samples of grid rows [row_begin, ..): out = Y = alpha (D X - K_A X).
-template <int MB, int PB, int NW, bool SAMPLES>
+// NS > 0 (joint filtering): NS float planes through the same filter in the epilogue, fsig.w [NS][LD] their weights
+template <int MB, int PB, int NW, bool SAMPLES, int NS = 0>
 __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tval, int width, int row_begin, const int *__restrict__ grow,
                                                    const int *__restrict__ gcol, int nr, int nc, int ksc, const float *__restrict__ btab,
                                                    const float *__restrict__ pexp, int rad, const unsigned *__restrict__ rowband, const unsigned *__restrict__ win,
@@ -152,7 +153,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                                                    const float *__restrict__ X, int x_ld, const double *__restrict__ degree, float alpha,
                                                    unsigned long long *__restrict__ evaluated, int row_end, const float *__restrict__ fw,
                                                    float fgain, float fysub, uint8_t *__restrict__ fout, float *__restrict__ fzf,
-                                                   float *__restrict__ fcorr, int64_t fpix0)
+                                                   float *__restrict__ fcorr, int64_t fpix0, BandSignals fsig)
 {
     static_assert(!SAMPLES || PB == 1, "sample targets: one tile of 32 per wave");
     constexpr int LD = 32 * MB, CHB = band_chunk_bytes(MB), NPIECE = MB * 2 + 1; // (the last piece is the 256-byte tail)
@@ -528,6 +529,32 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                     }
                 }
             }
+            if constexpr (NS > 0) { // the planes: one more dot product and 32-lane reduction each per pixel, accumulators still live
+#pragma unroll
+                for (int k = 0; k < NS; ++k) {
+                    float sv[MB];
+#pragma unroll
+                    for (int j = 0; j < MB; ++j) sv[j] = fsig.w[k * LD + 32 * j + l31] * iv[j];
+#pragma unroll
+                    for (int b = 0; b < PB; ++b) {
+#pragma unroll
+                        for (int q = 0; q < 16; ++q) {
+                            float sdot = 0.f;
+#pragma unroll
+                            for (int j = 0; j < MB; ++j) sdot = fmaf(acc[b][j][q], sv[j], sdot);
+#pragma unroll
+                            for (int o = 16; o > 0; o >>= 1) sdot += __shfl_xor(sdot, o, 64);
+                            const int col = (tile * PB + b) * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
+                            if (l31 == 0 && col < width) {
+                                const int64_t px = (int64_t)trow * width + col;
+                                if (mask[px]) continue; // (filter_sample_rows_signals)
+                                const float v = fsig.s[(size_t)k * fsig.N + px];
+                                fsig.out[(size_t)k * fsig.N + px] = v + (fgain * sdot - fysub * v);
+                            }
+                        }
+                    }
+                }
+            }
         }
         return;
     }
@@ -784,12 +811,22 @@ constexpr int BAND_PB = BAND_PB_X, BAND_NW = BAND_NW_X;     // pixel targets: 64
 #endif
 constexpr int BAND_NW_S = BAND_NW_S_X;                // sample targets: 32 per wave, 8 grid rows per workgroup
 
-template <int MB>
+template <int MB, int NS = 0>
 static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int row0, int nrows, const unsigned char *chunks,
                           const float *inv, float *phi, int phi_ld, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, int raster,
                           double *cpartial, unsigned long long *evaluated, const BandFilter *flt = nullptr, int64_t pix0 = 0)
 {
-    auto kern = k_band<MB, BAND_PB, BAND_NW, false>;
+    if constexpr (NS == 0) // the planes ride in the filter's epilogue: one instantiation per plane count
+        if (flt && flt->sig.nsig > 0) {
+            switch (flt->sig.nsig) {
+            case 1: return launch_band_px<MB, 1>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
+            case 2: return launch_band_px<MB, 2>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
+            case 3: return launch_band_px<MB, 3>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
+            case 4: return launch_band_px<MB, 4>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
+            default: return set_error(ctx, GLF_ERR_INVALID, "k_band: %d signal planes", flt->sig.nsig);
+            }
+        }
+    auto kern = k_band<MB, BAND_PB, BAND_NW, false, NS>;
     const unsigned lds = band_lds_bytes(MB, BAND_NW, bt.rad, bt.ksc, false);
     GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
@@ -797,7 +834,7 @@ static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_i
                        bt.ksc, bt.tab(), bt.pexp(), bt.rad, bt.rowband_px(), bt.win_px(), bt.ntiles_px, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster,
                        cpartial, (const float *)nullptr, 0, (const double *)nullptr, 0.f, evaluated, row0 + nrows, flt ? flt->w : (const float *)nullptr,
                        flt ? flt->gain : 0.f, flt ? flt->ysub : 0.f, flt ? flt->out : (uint8_t *)nullptr, flt ? flt->zf : (float *)nullptr,
-                       flt ? flt->corr : (float *)nullptr, pix0);
+                       flt ? flt->corr : (float *)nullptr, pix0, flt ? flt->sig : BandSignals{});
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -815,7 +852,7 @@ static int launch_band_samples(glf_ctx *ctx, const BandTables &bt, const uint8_t
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW_S * 64), lds, ctx->stream, svals, bt.nc, a0, bt.grow(), bt.gcol(), bt.nr, bt.nc, bt.ksc,
                        bt.tab(), bt.pexp(), bt.rad, bt.rowband_s(), bt.win_s(), bt.ntiles_s, chunks, inv, Y, y_ld, (const uint8_t *)nullptr,
                        (const uint32_t *)nullptr, 0u, 1, (double *)nullptr, X, x_ld, degree, alpha, evaluated, a0 + nrows, (const float *)nullptr, 0.f,
-                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0);
+                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0, BandSignals{});
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

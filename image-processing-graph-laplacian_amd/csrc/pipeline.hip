@@ -40,6 +40,15 @@ __global__ void k_ka_from_la(const float4 *__restrict__ samples, const double *_
     if (s < p) T[(size_t)s * ld] = (float)(degree[s] * (double)samples[s].z - (double)T[(size_t)s * ld] * inv_alpha);
 }
 
+// X[s][k] = s_k at sample s (block of `ld` columns, the others stay zero): the planes' sample values for t_s = K_A s_A
+__global__ void k_sample_signal_columns(const uint32_t *__restrict__ idx, const float *__restrict__ sig, int64_t N, int nsig, unsigned p,
+                                        unsigned ld, float *__restrict__ X)
+{
+    const unsigned s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < p)
+        for (int k = 0; k < nsig; ++k) X[(size_t)s * ld + k] = sig[(size_t)k * N + idx[s]];
+}
+
 __global__ void k_make_psi(const float *__restrict__ phiA, const float *__restrict__ pinv, unsigned p, unsigned ld, unsigned m,
                            float scale, float *__restrict__ psi)
 {
@@ -471,8 +480,33 @@ int glf_image_processing(glf_ctx *ctx, const glf_options *opt_in, const uint8_t 
     return glf_image_processing_capture(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
 }
 
+// extra signal planes of glf_image_processing_signals (nullptr: the guide alone)
+struct SignalPlanes {
+    int nsig;
+    const float *d_sig;
+    float *d_out;
+};
+
+static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
+                                float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
+
 int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height,
                                  uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
+{
+    return image_processing_run(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, nullptr);
+}
+
+int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, int nsig,
+                                 const float *d_sig, float *d_sig_out, uint8_t *d_out, float *d_zf, double *eigvals_out,
+                                 glf_stats *stats)
+{
+    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
+    const SignalPlanes sig{nsig, d_sig, d_sig_out};
+    return image_processing_run(ctx, opt, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, &sig);
+}
+
+static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
+                                float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
     if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     if (cap && cap->struct_size != sizeof(glf_capture))
@@ -534,6 +568,7 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
     if (wide && opt.filter_mode == GLF_FILTER_SHARPEN) // (its Gram matrix Phi^T Phi would couple the panels)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "the sharpening filter takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
     if (wide && cap) return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_capture with more than 256 eigenpairs");
+    if (wide && sig) return set_error(ctx, GLF_ERR_UNSUPPORTED, "signal planes with more than 256 eigenpairs (%u asked for)", m);
     const unsigned ld = wide ? PANEL_COLS : ld_for(m);
     const unsigned p32 = (unsigned)round_up(p, VEC_PAD);
     const KernelCoef coef = make_coef(opt.kernel, opt.h_loc, opt.h_val);
@@ -770,6 +805,63 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
     while (si1 < p && (int64_t)h_idx[si1] < pix1) ++si1;
     // ---- band form with the filter in the kernel's epilogue: Phi is never written -----------------------------------------
     // c = Phi^T y is needed before the extension then: it follows from the degree stage's value-weighted sums (c_from_ysum).
+    // ---- joint filtering on the band form: the planes ride in k_band's epilogue, Phi is never written for them either --------
+    // c_s = Phi^T s the way c is formed for y: U_s from the grid-factored degree with s as the histogram weight (all-reduced in
+    // a collective of its own), t_s = K_A s_A from one more operator application (the guide's own application is untouched),
+    // then c_from_ysum with s_A in place of y_A. The route is voted on every rank (have_ysum is decided per rank).
+    const int nsig = sig ? sig->nsig : 0;
+    bool sig_fused = false, sig_done = false;
+    DevBuf<float> sig_w; // [nsig][ld] the planes' filter weights once c_s is known
+    if (sig) {
+        const bool elig = gop.op && ld <= 64 && opt.filter_mode != GLF_FILTER_SHARPEN && ctx->contraction == GLF_CONTRACT_F16_SPLIT &&
+                          (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) && !ctx->tune.no_fused_filter && (have_ysum || pix0 == pix1);
+        DevBuf<double> vote;
+        GLF_TRY(vote.alloc(ctx, 1));
+        double hv = elig ? 1.0 : 0.0;
+        GLF_HIP(ctx, hipMemcpyAsync(vote.p, &hv, sizeof(double), hipMemcpyHostToDevice, st));
+        GLF_TRY(allreduce_f64(ctx, vote.p, 1));
+        GLF_HIP(ctx, hipMemcpyAsync(&hv, vote.p, sizeof(double), hipMemcpyDeviceToHost, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+        sig_fused = hv == (double)(ctx->has_comm ? ctx->comm.size : 1);
+    }
+    if (sig_fused) {
+        DevBuf<double> us, cs, zdeg;
+        DevBuf<float> xs, ts;
+        GLF_TRY(us.alloc(ctx, (size_t)nsig * p));
+        for (int k = 0; k < nsig; ++k) {
+            if (pix1 == pix0) {
+                GLF_HIP(ctx, hipMemsetAsync(us.p + (size_t)k * p, 0, sizeof(double) * p, st));
+                continue;
+            }
+            float smax = 0.f;
+            GLF_TRY(plane_absmax(ctx, sig->d_sig + (size_t)k * N + pix0, pix1 - pix0, &smax));
+            const int rc = weighted_sums_grid(ctx, d_img, width, height, row0, row1, tb.samples.p, p, h_idx, coef, opt.skip_exact_zeros,
+                                              sig->d_sig + (size_t)k * N, (double)smax, us.p + (size_t)k * p);
+            if (rc != GLF_OK) return rc == GLF_ERR_UNSUPPORTED ? set_error(ctx, GLF_ERR_INVALID, "weighted sums: no grid-factored degree") : rc;
+        }
+        GLF_TRY(allreduce_f64(ctx, us.p, (size_t)nsig * p));
+        GLF_TRY(xs.alloc(ctx, (size_t)p32 * 32));
+        GLF_TRY(ts.alloc(ctx, (size_t)p32 * 32));
+        GLF_TRY(zdeg.alloc(ctx, p));
+        GLF_TRY(cs.alloc(ctx, (size_t)nsig * ld));
+        GLF_HIP(ctx, hipMemsetAsync(xs.p, 0, sizeof(float) * (size_t)p32 * 32, st));
+        GLF_HIP(ctx, hipMemsetAsync(ts.p, 0, sizeof(float) * (size_t)p32 * 32, st));
+        GLF_HIP(ctx, hipMemsetAsync(zdeg.p, 0, sizeof(double) * p, st));
+        hipLaunchKernelGGL(k_sample_signal_columns, dim3((p + 255) / 256), dim3(256), 0, st, tb.idx.p, sig->d_sig, (int64_t)N, nsig, p, 32u, xs.p);
+        GLF_LAUNCH_CHECK(ctx);
+        GLF_TRY(grid_op_apply(ctx, gop.op, xs.p, ts.p, 32, -1.0, zdeg.p, 0, p, 0)); // K_A s_A for every plane's column
+        for (int k = 0; k < nsig; ++k)
+            GLF_TRY(c_from_ysum(ctx, psi.p, phiA.p, us.p + (size_t)k * p, ts.p + k, 32, tb.samples.p, p, ld, cs.p + (size_t)k * ld, xs.p + k));
+        std::vector<double> hcs((size_t)nsig * ld);
+        GLF_HIP(ctx, hipMemcpyAsync(hcs.data(), cs.p, sizeof(double) * nsig * ld, hipMemcpyDeviceToHost, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+        std::vector<float> hws((size_t)nsig * ld, 0.f);
+        for (int k = 0; k < nsig; ++k)
+            for (unsigned j = 0; j < m; ++j) hws[(size_t)k * ld + j] = (float)(filter_weight(lam[j]) * hcs[(size_t)k * ld + j]);
+        GLF_TRY(sig_w.alloc(ctx, (size_t)nsig * ld));
+        GLF_HIP(ctx, hipMemcpyAsync(sig_w.p, hws.data(), sizeof(float) * nsig * ld, hipMemcpyHostToDevice, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+    }
     bool fused = false;
     if (have_ysum && (gop.op || LA.p) && ld <= 64 && opt.filter_mode != GLF_FILTER_SHARPEN && !(cap && cap->d_phi) &&
         ctx->contraction == GLF_CONTRACT_F16_SPLIT && (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) && !ctx->tune.no_fused_filter) {
@@ -806,6 +898,11 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
         flt.out = d_out;
         flt.zf = d_zf;
         flt.corr = cap ? cap->d_corr : nullptr;
+        if (sig_fused) {
+            flt.sig = BandSignals{nsig, sig_w.p, sig->d_sig, sig->d_out, (int64_t)N};
+            GLF_TRY(filter_sample_rows_signals(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, nsig, sig_w.p, filter_gain, filter_ysub,
+                                               sig->d_sig, sig->d_out, N));
+        }
         // the sample pixels from their rows of Phi_A first (k_band leaves them alone: the host work between the two launches --
         // grid detection, cached tables -- then overlaps a kernel instead of following the long one)
         GLF_TRY(filter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, d_img, w.p, filter_gain, filter_ysub, d_out, d_zf,
@@ -817,9 +914,29 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
             S.filter_fused = 1;
             GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
             fused = true;
+            sig_done = sig_fused;
         } else if (rc != GLF_ERR_UNSUPPORTED) return rc;
     }
     LA.release();
+    // sharpening: (1 + beta) W^2 y - beta W^3 y with W = Phi L Phi^T applied factor by factor as the PoC does
+    // (python/image_processing.py:231-235): the extended eigenvectors are not orthonormal, so G = Phi^T Phi sits
+    // between the factors -- z = Phi w, w = (1 + beta) L G L c - beta L G L G L c, L = 1 - mu, c = Phi^T y
+    std::vector<double> hG; // G (f64 [ld][ld], all ranks' pixels): filled on the unfused path for the sharpening filter
+    auto sharpen_weights = [&](const double *hc, float *hw) {
+        std::vector<double> t(m), u(m), v(m);
+        const double beta = (double)opt.filter_beta;
+        auto LG = [&](const std::vector<double> &x, std::vector<double> &y) { // y = L (G x)
+            for (unsigned i = 0; i < m; ++i) {
+                double a = 0.0;
+                for (unsigned j = 0; j < m; ++j) a += hG[(size_t)i * ld + j] * x[j];
+                y[i] = (1.0 - lam[i]) * a;
+            }
+        };
+        for (unsigned j = 0; j < m; ++j) t[j] = (1.0 - lam[j]) * hc[j];
+        LG(t, u);
+        LG(u, v);
+        for (unsigned j = 0; j < m; ++j) hw[j] = (float)((1.0 + beta) * u[j] - beta * v[j]);
+    };
     if (!fused) {
     GLF_TRY(phi.alloc(ctx, (size_t)npix * ld));
     float *phi_base = phi.p - (size_t)pix0 * ld; // rows addressed by absolute pixel index
@@ -843,28 +960,14 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
         std::vector<float> hw(ld, 0.f);
         for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
         if (opt.filter_mode == GLF_FILTER_SHARPEN) {
-            // (1 + beta) W^2 y - beta W^3 y with W = Phi L Phi^T applied factor by factor as the PoC does
-            // (python/image_processing.py:231-235): the extended eigenvectors are not orthonormal, so G = Phi^T Phi sits
-            // between the factors -- z = Phi w, w = (1 + beta) L G L c - beta L G L G L c, L = 1 - mu, c = Phi^T y
             DevBuf<double> G;
             GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
             GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
             GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
-            std::vector<double> hG((size_t)ld * ld), t(m), u(m), v(m);
+            hG.resize((size_t)ld * ld);
             GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
             GLF_HIP(ctx, hipStreamSynchronize(st));
-            const double beta = (double)opt.filter_beta;
-            auto LG = [&](const std::vector<double> &x, std::vector<double> &y) { // y = L (G x)
-                for (unsigned i = 0; i < m; ++i) {
-                    double a = 0.0;
-                    for (unsigned j = 0; j < m; ++j) a += hG[(size_t)i * ld + j] * x[j];
-                    y[i] = (1.0 - lam[i]) * a;
-                }
-            };
-            for (unsigned j = 0; j < m; ++j) t[j] = (1.0 - lam[j]) * hc[j];
-            LG(t, u);
-            LG(u, v);
-            for (unsigned j = 0; j < m; ++j) hw[j] = (float)((1.0 + beta) * u[j] - beta * v[j]);
+            sharpen_weights(hc.data(), hw.data());
         }
         GLF_HIP(ctx, hipMemcpyAsync(w.p, hw.data(), sizeof(float) * ld, hipMemcpyHostToDevice, st));
         GLF_HIP(ctx, hipStreamSynchronize(st));
@@ -880,6 +983,48 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const 
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
     if (stats) *stats = S;
+    // ---- signal planes through the guide's operator (after the guide is complete: its outputs, stats and collectives are
+    // those of the plain call). Phi is written for them on every path: the fused guide filter never writes it, so it is
+    // extended here with the guide's own Psi and contraction. Every rank takes this branch, so the collectives match.
+    if (sig && !sig_done) {
+        DevBuf<float> phis;
+        float *phi_rows = nullptr; // rows addressed by absolute pixel index
+        if (!fused) phi_rows = phi.p - (size_t)pix0 * ld;
+        else {
+            GLF_TRY(phis.alloc(ctx, (size_t)npix * ld));
+            phi_rows = phis.p - (size_t)pix0 * ld;
+            GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha),
+                                      psi.p, m, ld, phi_rows, 1, nullptr, nullptr, opt.skip_exact_zeros));
+            if (si1 > si0)
+                GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
+        }
+        const int ns = sig->nsig;
+        if (sig_fused) { // (the band launch fell back after c_s was formed: its weights stand, c_s's collective is not repeated)
+            GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
+            GLF_HIP(ctx, hipStreamSynchronize(st));
+            return GLF_OK;
+        }
+        DevBuf<double> cs;
+        DevBuf<float> ws;
+        GLF_TRY(cs.alloc(ctx, (size_t)ns * ld));
+        GLF_TRY(ws.alloc(ctx, (size_t)ns * ld));
+        GLF_TRY(phi_t_signals(ctx, phi_rows, sig->d_sig, N, ns, pix0, pix1, ld, cs.p));
+        GLF_TRY(allreduce_f64(ctx, cs.p, (size_t)ns * ld)); // c_k = Phi^T s_k over all ranks' pixels (a collective of its own)
+        std::vector<double> hcs((size_t)ns * ld);
+        GLF_HIP(ctx, hipMemcpyAsync(hcs.data(), cs.p, sizeof(double) * ns * ld, hipMemcpyDeviceToHost, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+        std::vector<float> hws((size_t)ns * ld, 0.f);
+        for (int k = 0; k < ns; ++k) {
+            const double *hc = hcs.data() + (size_t)k * ld;
+            float *hw = hws.data() + (size_t)k * ld;
+            if (opt.filter_mode == GLF_FILTER_SHARPEN) sharpen_weights(hc, hw);
+            else
+                for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
+        }
+        GLF_HIP(ctx, hipMemcpyAsync(ws.p, hws.data(), sizeof(float) * ns * ld, hipMemcpyHostToDevice, st));
+        GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+    }
     return GLF_OK;
 }
 

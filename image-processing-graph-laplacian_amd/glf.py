@@ -49,7 +49,9 @@ EXPORTS = [
     "glf_ComputeLaplacianMatrix", "glf_InversePowerIteration", "glf_OrthonormaliseVecs", "glf_NormaliseVecs",
     "glf_InverseDiagMat", "glf_Nystroem", "glf_Permutation", "glf_ComputeResultFromLaplacian", "glf_Sinkhorn", "glf_SinkhornRows", "glf_Orthogonalisation",
     "glf_options_default", "glf_image_processing", "glf_image_processing_capture", "glf_ctx_debug_violations", "glf_ctx_cached_bytes", "glf_image_processing_batch", "glf_EntireComputation", "glf_read_png", "glf_write_png", "glf_read_png_rgb", "glf_write_png_rgb",
+    "glf_image_processing_signals", "glf_multi_image_processing_signals",
 ]
+MAX_SIGNALS = 4
 
 
 class Mat(C.Structure):
@@ -317,6 +319,32 @@ class Multi:
                       matvecs=s.eig.matvecs, nystroem_path=s.nystroem_path,
                       matvec_path=s.matvec_path, filter_fused=s.filter_fused, eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
         return out, zf, infos
+
+    def image_processing_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_signals: the host image plus float planes [nsig, H, W] (numpy, replicated on every
+        rank) filtered through the image's graph. Returns (out u8 [H, W], zf f32 [H, W], sig_out f32 [nsig, H, W], infos)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        h, w = img.shape
+        sig = np.ascontiguousarray(signals, dtype=np.float32)
+        if sig.ndim != 3 or sig.shape[1:] != (h, w):
+            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, sig.shape))
+        opt = opt or default_options()
+        out = np.zeros((h, w), dtype=np.uint8)
+        zf = np.zeros((h, w), dtype=np.float32)
+        sig_out = np.zeros(sig.shape, dtype=np.float32)
+        lam = np.zeros(max(1, int(Sampling(w, h, int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)).size)),
+                       dtype=np.float64)
+        stats = (Stats * self.n)()
+        rc = _lib.glf_multi_image_processing_signals(
+            self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h), C.c_int(sig.shape[0]),
+            sig.ctypes.data_as(C.c_void_p), sig_out.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+            zf.ctypes.data_as(C.c_void_p), lam.ctypes.data_as(C.c_void_p), stats)
+        if rc != OK:
+            raise GlfError(rc, "glf_multi_image_processing_signals: " + _lib.glf_multi_last_error(self._w).decode())
+        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
+                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
+                      eigvals=lam[:s.m].copy()) for s in stats]
+        return out, zf, sig_out, infos
 
     def comm_counters(self, rank=0, reset=True):
         """Collectives rank `rank` issued since the last reset: dict(allreduce_calls, allreduce_bytes, allgather_calls, allgather_bytes)."""
@@ -726,6 +754,39 @@ class Context:
             info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], c=keep[2][:st.m].copy(), degree=keep[3][:st.p].copy(),
                                    corr=keep[4], ld=int(cap.ld))
         return out, zf, info
+
+
+    def image_processing_signals(self, d_img, signals, opt=None, want_float=False):
+        """Joint filtering (glf_image_processing_signals): the guide d_img (device uint8 [H, W]) defines the graph, the
+        eigenpairs and the filter; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same operator.
+        Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing."""
+        torch = self.torch
+        assert d_img.dtype == torch.uint8 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
+        assert signals.dtype == torch.float32 and signals.is_cuda and signals.dim() == 3 and signals.is_contiguous()
+        h, w = d_img.shape
+        if tuple(signals.shape[1:]) != (h, w):
+            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, tuple(signals.shape)))
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the planes are complete before the library reads them
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w), dtype=torch.uint8, device=self.device)
+            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
+            sig_out = torch.zeros(tuple(signals.shape), dtype=torch.float32, device=self.device)
+        st = Stats()
+        req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
+        p_real = int(Sampling(w, h, req).size) if not getattr(opt, "sampling", 0) else max(req, 1) * 2 + 64
+        lam = np.zeros(max(p_real, 1), dtype=np.float64)
+        rc = _lib.glf_image_processing_signals(self._ctx, C.byref(opt), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
+                                               C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()),
+                                               C.c_void_p(sig_out.data_ptr()), C.c_void_p(out.data_ptr()),
+                                               C.c_void_p(zf.data_ptr()) if want_float else None,
+                                               lam.ctypes.data_as(C.c_void_p), C.byref(st))
+        self._check(rc, "image_processing_signals")
+        self.stream.synchronize()
+        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, row0=st.row0, row1=st.row1,
+                    ms_total=st.ms_total, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
+                    filter_fused=st.filter_fused, eigvals=lam[:st.m].copy())
+        return out, zf, sig_out, info
 
 
 def image_processing_batch(contexts, d_imgs, opt=None):

@@ -8,13 +8,15 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma]]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
  * (python/image_processing.py:197-241, B = 1.5) with W = Phi diag(1 - mu) Phi^T from the eigenpairs this program computes.
  * -color keeps the colours of an RGB(A) input the way the PoC does (python/image_processing.py:410-432):
  * RGB -> YUV (python/utils.py:33-44), the luma plane is filtered, the chroma planes pass through, YUV -> RGB; the luma is
  * rounded to 8 bits first because every kernel here works on u8 pixel values (the PoC filters the unrounded floats).
+ * -chroma (with -color) filters the two chroma planes too: the unrounded U and V go through the luma's graph with the same
+ * -filter (glf_image_processing_signals), so chroma noise is smoothed along the luma's edges.
  * -dump_residual writes results/residuals.png = |input - output| stretched to the full grey range, the PoC's residual image
  * (python/image_processing.py:378-380: plt.imsave of np.abs(y - z) with cmap 'gray' autoscales min..max).
  * -no_approx runs the full-matrix mode (hpc/image_processing.c:155-181); -use_slepc is accepted and refused.
@@ -330,12 +332,14 @@ static png_bytep *ColorComputation(const char *filename, unsigned *width_out, un
                 inv[i][j] = (a[r0][c0] * a[r1][c1] - a[r0][c1] * a[r1][c0]) / det;
             }
     }
+    const int chroma = opt_has("-chroma");
     double *yuv = (double *)malloc(sizeof(double) * 3 * n);
     uint8_t *luma = (uint8_t *)malloc(n);
     float *zf = (float *)malloc(sizeof(float) * n);
+    float *uv = chroma ? (float *)malloc(sizeof(float) * 2 * n) : NULL; /* U, V as float; filtered in place */
     glf_ctx *ctx = glf_world();
-    void *d_img = NULL, *d_out = NULL, *d_zf = NULL;
-    if (!yuv || !luma || !zf) goto out;
+    void *d_img = NULL, *d_out = NULL, *d_zf = NULL, *d_uv = NULL, *d_uv_out = NULL;
+    if (!yuv || !luma || !zf || (chroma && !uv)) goto out;
     for (int r = 0; r < h; ++r)
         for (int c = 0; c < w; ++c) {
             const double R = rgb[r][3 * c], G = rgb[r][3 * c + 1], B = rgb[r][3 * c + 2];
@@ -346,24 +350,38 @@ static png_bytep *ColorComputation(const char *filename, unsigned *width_out, un
         }
     if (glf_malloc(ctx, &d_img, n) != GLF_OK || glf_malloc(ctx, &d_out, n) != GLF_OK || glf_malloc(ctx, &d_zf, sizeof(float) * n) != GLF_OK) goto out;
     if (glf_memcpy_h2d(ctx, d_img, luma, n) != GLF_OK) goto out;
+    if (chroma) {
+        for (size_t i = 0; i < 2 * n; ++i) uv[i] = (float)yuv[n + i];
+        if (glf_malloc(ctx, &d_uv, sizeof(float) * 2 * n) != GLF_OK || glf_malloc(ctx, &d_uv_out, sizeof(float) * 2 * n) != GLF_OK) goto out;
+        if (glf_memcpy_h2d(ctx, d_uv, uv, sizeof(float) * 2 * n) != GLF_OK) goto out;
+    }
     glf_options opt;
     fill_options(&opt, (unsigned)w, (unsigned)h);
     glf_stats st;
     {
-        const int rc = glf_image_processing(ctx, &opt, (const uint8_t *)d_img, w, h, (uint8_t *)d_out, (float *)d_zf, NULL, &st);
+        const int rc = chroma ? glf_image_processing_signals(ctx, &opt, (const uint8_t *)d_img, w, h, 2, (const float *)d_uv, (float *)d_uv_out,
+                                                             (uint8_t *)d_out, (float *)d_zf, NULL, &st)
+                              : glf_image_processing(ctx, &opt, (const uint8_t *)d_img, w, h, (uint8_t *)d_out, (float *)d_zf, NULL, &st);
         if (rc != GLF_OK) {
-            fprintf(stderr, "glf_image_processing: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(ctx));
+            fprintf(stderr, "%s: %s (%s)\n", chroma ? "glf_image_processing_signals" : "glf_image_processing", glf_strerror(rc),
+                    glf_ctx_last_error(ctx));
             goto out;
         }
     }
     print_stage_times(&st, opt.epsilon);
     if (glf_memcpy_d2h(ctx, zf, d_zf, sizeof(float) * n) != GLF_OK) goto out;
+    if (chroma) {
+        if (glf_memcpy_d2h(ctx, uv, d_uv_out, sizeof(float) * 2 * n) != GLF_OK) goto out;
+        printf("Chroma: the U and V planes were filtered through the luma's graph (filter %s)\n",
+               opt_value("-filter") ? opt_value("-filter") : "reference");
+    }
     rows = (png_bytep *)malloc(sizeof(png_bytep) * (size_t)h);
     for (int r = 0; rows && r < h; ++r) {
         rows[r] = (png_bytep)malloc(3 * (size_t)w);
         for (int c = 0; rows[r] && c < w; ++c) {
             const size_t i = (size_t)r * w + c;
-            const double zy = (double)zf[i], u = yuv[n + i], v = yuv[2 * n + i]; /* z[:, :, 0] = z_ycc; chroma unchanged */
+            const double zy = (double)zf[i];                                       /* z[:, :, 0] = z_ycc; chroma unchanged */
+            const double u = chroma ? (double)uv[i] : yuv[n + i], v = chroma ? (double)uv[n + i] : yuv[2 * n + i]; /* (or filtered) */
             for (int k = 0; k < 3; ++k) {                                          /* ycc2rgb, then astype(uint8) made safe */
                 double x = zy * inv[k][0] + u * inv[k][1] + v * inv[k][2];
                 x = x < 0.0 ? 0.0 : (x > 255.0 ? 255.0 : x);
@@ -375,6 +393,9 @@ out:
     free(yuv);
     free(luma);
     free(zf);
+    free(uv);
+    if (d_uv) glf_free(ctx, d_uv);
+    if (d_uv_out) glf_free(ctx, d_uv_out);
     if (d_img) glf_free(ctx, d_img);
     if (d_out) glf_free(ctx, d_out);
     if (d_zf) glf_free(ctx, d_zf);
@@ -464,6 +485,11 @@ int main(int argc, char **argv)
 
     int width = 0, height = 0;
     png_bytep *img_bytes = NULL, *output_img = NULL;
+    if (opt_has("-chroma") && !opt_has("-color")) {
+        fprintf(stderr, "-chroma filters the chroma planes of a colour image: it needs -color\n");
+        FinalizeProgram();
+        return 1;
+    }
     if (opt_has("-color")) { /* python/image_processing.py:410-432 */
         unsigned cw = 0, ch = 0;
         png_bytep *in_rgb = NULL;

@@ -386,6 +386,20 @@ int glf_image_processing(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_
                          int height, uint8_t *d_out, float *d_zf, double *eigvals_out,
                          glf_stats *stats);
 
+/* Joint filtering: the guide image's graph filter applied to extra signal planes. The graph, the eigenpairs, the filter mode
+ * and its weights are those of glf_image_processing on d_img, and d_out / d_zf / eigvals_out / stats are bit-identical to
+ * that call's (stats describe the guide). Each plane s_k goes through the same linear operator:
+ *   z_k = (1 - ysub) s_k + gain Phi (f(Pi) Phi^T s_k)
+ * (reference: s + gain Phi Pi^k Phi^T s; PoC: s - Phi diag(mu + 5) Phi^T s; smooth / sharpen: the same factors as for y).
+ * d_sig: device float [nsig][height*width], replicated on every rank like d_img (a depth map, an alpha matte, the chroma of
+ * a colour image, ...); d_sig_out: device float [nsig][height*width], not clamped; with a comm rank g writes its own pixel
+ * rows only. A plane's result does not depend on the other planes. 1 <= nsig <= GLF_MAX_SIGNALS, else GLF_ERR_INVALID;
+ * more than 256 eigenpairs: GLF_ERR_UNSUPPORTED. */
+#define GLF_MAX_SIGNALS 4
+int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, int nsig,
+                                 const float *d_sig, float *d_sig_out, uint8_t *d_out, float *d_zf, double *eigvals_out,
+                                 glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -421,6 +435,13 @@ int glf_image_processing_batch(glf_ctx *const *ctxs, int nctx, const glf_options
  * or NULL; eigvals_out: HOST double[m] or NULL (rank 0's, identical on every rank). */
 int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height,
                                uint8_t *h_out, float *h_zf, double *eigvals_out, glf_stats *stats);
+
+/* glf_multi_image_processing with signal planes (glf_image_processing_signals): h_sig HOST float [nsig][height*width] goes
+ * to every rank whole; each rank's pixel rows of the filtered planes are gathered into h_sig_out (HOST float
+ * [nsig][height*width]). */
+int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height,
+                                       int nsig, const float *h_sig, float *h_sig_out, uint8_t *h_out, float *h_zf,
+                                       double *eigvals_out, glf_stats *stats);
 
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
