@@ -28,8 +28,21 @@ __global__ void k_sample_tables(const uint8_t *__restrict__ img, int width, int6
     mask[px] = 1;
 }
 
+__global__ void k_sample_tables_rgb(const uint8_t *__restrict__ rgb, int width, int64_t N, unsigned p, const uint32_t *__restrict__ idx,
+                                    float4 *__restrict__ samples, uint8_t *__restrict__ mask)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p) return;
+    const uint32_t px = idx[i];
+    if ((int64_t)px >= N) return;
+    const uint8_t *c = rgb + (size_t)px * 3;
+    samples[i] = make_float4((float)(px / (uint32_t)width), (float)(px % (uint32_t)width), 0.f,
+                             (float)((unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16)));
+    mask[px] = 1;
+}
+
 int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int height, unsigned p,
-                        const unsigned *h_idx, SampleTables &out)
+                        const unsigned *h_idx, SampleTables &out, int kernel)
 {
     const int64_t N = (int64_t)width * height;
     if (p == 0 || !h_idx) return set_error(ctx, GLF_ERR_INVALID, "empty sample set");
@@ -44,8 +57,12 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     GLF_TRY(out.idx.alloc(ctx, p));
     GLF_HIP(ctx, hipMemcpyAsync(out.idx.p, h_idx, sizeof(uint32_t) * p, hipMemcpyHostToDevice, ctx->stream));
     GLF_HIP(ctx, hipMemsetAsync(out.mask.p, 0, (size_t)N, ctx->stream));
-    hipLaunchKernelGGL(k_sample_tables, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p,
-                       out.idx.p, out.samples.p, out.mask.p);
+    if (kernel == GLF_KERNEL_BILATERAL_RGB)
+        hipLaunchKernelGGL(k_sample_tables_rgb, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p,
+                           out.mask.p);
+    else
+        hipLaunchKernelGGL(k_sample_tables, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p,
+                           out.idx.p, out.samples.p, out.mask.p);
     GLF_LAUNCH_CHECK(ctx);
     // h_idx is pageable host memory: make sure the async copy has consumed it
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -385,7 +402,7 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 int weighted_sums_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
                        const unsigned *h_idx, KernelCoef coef, int window, const float *d_plane, double wabs, double *d_out)
 {
-    if (coef.kernel == GLF_KERNEL_NLM) return GLF_ERR_UNSUPPORTED;
+    if (coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB) return GLF_ERR_UNSUPPORTED;
     return degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_out, window, nullptr, nullptr, d_plane, wabs);
 }
 
@@ -401,6 +418,8 @@ int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, 
         if (evaluated) *evaluated = (double)p * (double)(row1 - row0) * (double)width;
         return nlm_degree_rows(ctx, d_img, width, height, row0, row1, d_idx, p, coef, d_degree);
     }
+    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) // no factored form over 2^24 colours: its own windowed sweep (rgb.hip)
+        return rgb_degree_rows(ctx, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
     const int rc = degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_degree, window, evaluated, d_ysum);
     if (rc != GLF_ERR_UNSUPPORTED) {
         if (have_ysum) *have_ysum = rc == GLF_OK && d_ysum != nullptr; // (only the grid-factored degree has the value-weighted sums)
@@ -534,6 +553,7 @@ int build_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, Kerne
         if (!d_img || !d_idx) return set_error(ctx, GLF_ERR_INVALID, "NLM sample matrix needs the image and the device sample indices");
         return nlm_sample_matrix(ctx, d_img, width, height, d_idx, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
     }
+    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) return rgb_sample_matrix(ctx, d_samples, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
     if (ncols == 0) {
         col0 = 0;
         ncols = p;

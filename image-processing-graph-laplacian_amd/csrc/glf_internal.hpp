@@ -225,6 +225,9 @@ __device__ __forceinline__ float kernel_eval(float dr, float dc, float dv, float
     return __builtin_amdgcn_exp2f(-t);
 }
 
+// byte k of a packed colour R + 256 G + 65536 B as f32 (v_cvt_f32_ubyte<k>)
+__device__ __forceinline__ float ubyte_f32(unsigned v, int k) { return (float)((v >> (8 * k)) & 0xffu); }
+
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
 // VGPRs. Issued from inline asm on purpose: with the builtin, hipcc (ROCm 7.2) cannot prove that the DMA
@@ -269,8 +272,9 @@ struct SampleTables {
     DevBuf<uint8_t> mask;
     DevBuf<uint32_t> idx;
 };
+// kernel GLF_KERNEL_BILATERAL_RGB: d_img is interleaved RGB and a record is {row, col, 0, R + 256 G + 65536 B}
 int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int height, unsigned p,
-                        const unsigned *h_idx, SampleTables &out);
+                        const unsigned *h_idx, SampleTables &out, int kernel = GLF_KERNEL_BILATERAL);
 
 // Partial degree D[i] = sum over pixels in rows [row0,row1) of K(sample i, pixel).
 int degree_rows(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1,
@@ -309,6 +313,13 @@ int nlm_sample_matrix(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
 int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const uint8_t *d_mask,
                  const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld, float *d_phi, int raster,
                  double *d_c, float *kernel_ms);
+// colour bilateral kernel (rgb.hip, GLF_KERNEL_BILATERAL_RGB): image interleaved uint8 [height][width][3]; same contracts as
+// degree_rows / build_sample_matrix (nystroem_contract runs k_nystroem with the colour generator)
+int rgb_degree_rows(glf_ctx *ctx, const uint8_t *d_rgb, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
+                    KernelCoef coef, double *d_degree, double *evaluated);
+int rgb_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, KernelCoef coef, float *d_out, int64_t ld, bool laplacian,
+                      double alpha, const double *d_degree, unsigned col0, unsigned ncols);
+int rgb_planes(glf_ctx *ctx, const uint8_t *d_rgb, int64_t N, float *d_planes); // [3][N] float channel planes
 int laplacian_from_KA(glf_ctx *ctx, const float *d_KA, int64_t ldk, unsigned p, float *d_LA, int64_t ld,
                       double alpha, const double *d_degree);
 
@@ -440,6 +451,9 @@ int filter_sample_rows_signals(glf_ctx *ctx, const float *d_phiA, unsigned n, un
                                float gain, float ysub, const float *d_sig, float *d_out, int64_t N);
 int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w, float gain,
                          float ysub, const float *d_sig, float *d_out, int64_t N);
+// colour output: d_w [3][ld]; d_rgb / d_out interleaved uint8 [N][3], rows [pix0, pix1) only; d_zf optional [3][N]
+int apply_filter_rgb(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain, float ysub,
+                     const uint8_t *d_rgb, uint8_t *d_out, float *d_zf, int64_t N);
 // the same filter panel by panel (m > 256): acc[px - pix0] (+)= sum_j Phi[px][j] w[j], then z = (1 - ysub) y + gain * acc
 int filter_accumulate(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float *d_acc,
                       bool first);

@@ -102,7 +102,9 @@ __device__ __forceinline__ int build_chunk_list(const int4 *__restrict__ box, in
     return scratch[256];
 }
 
-template <int MB, int PB, bool SKIP> // MB = ld / 32 column blocks; PB = 32-pixel blocks per wave; SKIP: chunk list
+// RGB: the colour generator (GLF_KERNEL_BILATERAL_RGB, rgb.hip): img is interleaved RGB, a sample record carries its packed colour
+// in w, and the epilogue has no grey y (cpartial must be null)
+template <int MB, int PB, bool SKIP, bool RGB = false> // MB = ld / 32 column blocks; PB = 32-pixel blocks per wave; SKIP: chunk list
 __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ img, int width, int64_t pix0, int64_t pix1,
                                                    const float4 *__restrict__ samples, unsigned p, float s_loc,
                                                    float s_val, const float *__restrict__ psi,
@@ -124,14 +126,20 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
     const int64_t wbase = pix0 + ((int64_t)blockIdx.x * 4 + wave) * (32 * PB);
 
     // this lane's pixels (one per 32-pixel block): exact integer coordinates in f32
-    float pr[PB], pc[PB], pv[PB];
+    float pr[PB], pc[PB], pv[PB], pg[RGB ? PB : 1], pb[RGB ? PB : 1];
 #pragma unroll
     for (int b = 0; b < PB; ++b) {
         int64_t px = wbase + 32 * b + l31;
         if (px >= pix1) px = pix1 - 1; // clamp loads; stores are guarded
         pr[b] = (float)(px / width);
         pc[b] = (float)(px % width);
-        pv[b] = (float)img[px];
+        if constexpr (RGB) {
+            pv[b] = (float)img[3 * px];
+            pg[b] = (float)img[3 * px + 1];
+            pb[b] = (float)img[3 * px + 2];
+        } else {
+            pv[b] = (float)img[px];
+        }
     }
 
     f32x16 acc[PB][MB];
@@ -172,8 +180,20 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
         for (int kk = 0; kk < KC / 2; ++kk) {
             const float4 s = stb[kk]; // two addresses per wave: broadcast within each half
             float a[PB];
+            if constexpr (RGB) {
+                const unsigned sc = (unsigned)s.w;
+                const float sr = ubyte_f32(sc, 0), sg = ubyte_f32(sc, 1),
+                            sb = ubyte_f32(sc, 2);
 #pragma unroll
-            for (int b = 0; b < PB; ++b) a[b] = kernel_eval(pr[b] - s.x, pc[b] - s.y, pv[b] - s.z, s_loc, s_val);
+                for (int b = 0; b < PB; ++b) {
+                    const float dr = pr[b] - s.x, dc = pc[b] - s.y, d0 = pv[b] - sr, d1 = pg[b] - sg, d2 = pb[b] - sb;
+                    const float u = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
+                    a[b] = __builtin_amdgcn_exp2f(-fmaf(u, s_val, fmaf(dc, dc, dr * dr) * s_loc));
+                }
+            } else {
+#pragma unroll
+                for (int b = 0; b < PB; ++b) a[b] = kernel_eval(pr[b] - s.x, pc[b] - s.y, pv[b] - s.z, s_loc, s_val);
+            }
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
                 const float bf = psb[kk * LD + 32 * j];
@@ -203,7 +223,7 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
                 if (is_sample) continue; // sample rows come from Phi_A (hpc/nystroem.c:25-34)
                 dst = (int64_t)p + px - (int64_t)samples_before(idx, p, (uint32_t)px);
             }
-            const float y = is_sample ? 0.f : (float)img[px];
+            const float y = (RGB || is_sample) ? 0.f : (float)img[px];
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
                 const float v = acc[b][j][r];
@@ -310,7 +330,7 @@ struct NysWindow {
     }
 };
 
-template <int MB, int PB>
+template <int MB, int PB, bool RGB = false>
 static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
                            const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
                            KernelCoef coef, const float *d_psi, float *d_phi, int raster, double *d_c, float *kernel_ms,
@@ -326,11 +346,11 @@ static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_
     GLF_TRY(win.init(ctx, d_samples, p, coef, window, 151.0, nwg));
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (win.radius >= 0)
-        hipLaunchKernelGGL((k_nystroem<MB, PB, true>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, true, RGB>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
                            d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     else
-        hipLaunchKernelGGL((k_nystroem<MB, PB, false>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, false, RGB>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
                            d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     GLF_LAUNCH_CHECK(ctx);
@@ -813,6 +833,19 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
         if (mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
         return nlm_nystroem(ctx, d_img, width, height, pix0, pix1, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c, kernel_ms);
     }
+    int rc = GLF_ERR_UNSUPPORTED;
+    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) { // the colour generator: entry by entry, f32 MFMA (no factored or split-f16 form)
+        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour kernel has no grey y for Phi^T y");
+        window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
+        switch (ld) {
+        case 32: rc = launch_nystroem<1, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
+        case 64: rc = launch_nystroem<2, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
+        case 128: rc = launch_nystroem<4, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
+        case 256: rc = launch_nystroem<8, 1, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
+        }
+        if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
+        return rc;
+    }
     {
         // a tensor-grid sample set (hpc/sampling.c always yields one) takes the factored contraction
         const int rc = nystroem_contract_grid(ctx, d_img, width, height, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld,
@@ -820,7 +853,6 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
         if (rc != GLF_ERR_UNSUPPORTED) return rc;
         if (path) *path = 0;
     }
-    int rc = GLF_ERR_UNSUPPORTED;
     if (ctx->contraction == GLF_CONTRACT_F16_SPLIT) {
         switch (ld) {
         case 32: rc = launch_nystroem_f16s<1, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;

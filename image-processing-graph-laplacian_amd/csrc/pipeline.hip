@@ -176,13 +176,13 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
                                 float h_val)
 {
     if (!ctx || !K_B || !d_img || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_NLM) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
+    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_RGB) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
     if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3)) // (nlm.hip reflects an out-of-image patch index once: valid from 3 pixels on)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     GLF_ENTER(ctx);
     const unsigned p = sample_size;
     SampleTables tb;
-    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb));
+    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3])
     const KernelCoef coef = make_coef(kernel, h_loc, h_val);
     DevBuf<double> deg;
     GLF_TRY(deg.alloc(ctx, p));
@@ -480,11 +480,13 @@ int glf_image_processing(glf_ctx *ctx, const glf_options *opt_in, const uint8_t 
     return glf_image_processing_capture(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
 }
 
-// extra signal planes of glf_image_processing_signals (nullptr: the guide alone)
+// extra signal planes of glf_image_processing_signals (nullptr: the guide alone); rgb_out set: glf_image_processing_rgb, the guide is
+// the colour image and its three channels are the planes (formed inside from the image)
 struct SignalPlanes {
     int nsig;
     const float *d_sig;
     float *d_out;
+    uint8_t *rgb_out = nullptr;
 };
 
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
@@ -505,6 +507,22 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
     return image_processing_run(ctx, opt, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, &sig);
 }
 
+int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
+                             float *d_zf, double *eigvals_out, glf_stats *stats)
+{
+    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    const SignalPlanes sig{3, nullptr, nullptr, d_out_rgb};
+    return image_processing_run(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr, &sig);
+}
+
+int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
+                                     float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
+{
+    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    const SignalPlanes sig{3, nullptr, nullptr, d_out_rgb};
+    return image_processing_run(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, cap, &sig);
+}
+
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
                                 float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
@@ -520,7 +538,15 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
             return set_error(ctx, GLF_ERR_INVALID, "glf_options.struct_size %u != %zu", opt_in->struct_size, sizeof(glf_options));
         opt = *opt_in;
     }
-    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_NLM) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
+    // the colour kernel reads the image as RGB: only the colour entry point takes it, and there it is the only kernel
+    const bool rgb = sig && sig->rgb_out;
+    if (rgb) {
+        if (opt.kernel != GLF_KERNEL_BILATERAL && opt.kernel != GLF_KERNEL_BILATERAL_RGB)
+            return set_error(ctx, GLF_ERR_UNSUPPORTED, "colour filtering: kernel %d (the colour bilateral kernel only)", opt.kernel);
+        opt.kernel = GLF_KERNEL_BILATERAL_RGB;
+    } else if (opt.kernel == GLF_KERNEL_BILATERAL_RGB)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the colour kernel takes an RGB image: glf_image_processing_rgb");
+    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_RGB) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     if (opt.filter_mode < GLF_FILTER_REFERENCE || opt.filter_mode > GLF_FILTER_SHARPEN) return set_error(ctx, GLF_ERR_INVALID, "filter_mode %d", opt.filter_mode);
@@ -545,6 +571,14 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
     hipStream_t st = ctx->stream;
     glf_stats S{};
+    DevBuf<float> rgb_planes_buf; // colour: the channels as float planes [3][N] (Phi^T x_c)
+    SignalPlanes rgb_sig{};
+    if (rgb) {
+        GLF_TRY(rgb_planes_buf.alloc(ctx, (size_t)3 * N));
+        GLF_TRY(rgb_planes(ctx, d_img, N, rgb_planes_buf.p));
+        rgb_sig = SignalPlanes{3, rgb_planes_buf.p, nullptr, sig->rgb_out};
+        sig = &rgb_sig;
+    }
 
     // p = width*height*0.01 (truncating), hpc/image_processing.c:187; Sampling rewrites it, :191-193
     unsigned p = opt.num_samples ? opt.num_samples : (unsigned)((double)N * opt.sample_frac);
@@ -583,7 +617,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     GLF_HIP(ctx, hipEventRecord(ctx->ev[0], st));
     // ---- affinity: sample tables + degree (K_B generated on the fly) -------------------------
     SampleTables tb;
-    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, h_idx, tb));
+    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, h_idx, tb, opt.kernel));
     DevBuf<double> deg; // D_A [p], then (grid-factored degree only) the value-weighted sums U[s] = sum_px K(s, px) y[px] [p]
     GLF_TRY(deg.alloc(ctx, 2 * (size_t)p));
     bool have_ysum = false;
@@ -942,15 +976,28 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     float *phi_base = phi.p - (size_t)pix0 * ld; // rows addressed by absolute pixel index
     GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * ld, st));
     GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha),
-                              psi.p, m, ld, phi_base, 1, c.p, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
+                              psi.p, m, ld, phi_base, 1, rgb ? nullptr : c.p, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
                               &S.nystroem_path, &rps));
     nystroem_stats();
     // sample rows of this shard <- Phi_A, and their share of c
     if (si1 > si0)
-        GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, c.p, m));
-    GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
+        GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, rgb ? nullptr : c.p, m));
+    if (!rgb) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
     GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
     // ---- filter ------------------------------------------------------------------------------
+    if (rgb) { // (no grey y: the channels are filtered below, as planes; the sharpening weights need G)
+        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour generator has no split-f16 form)
+        if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
+        if (opt.filter_mode == GLF_FILTER_SHARPEN) {
+            DevBuf<double> G;
+            GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
+            GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
+            GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
+            hG.resize((size_t)ld * ld);
+            GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
+            GLF_HIP(ctx, hipStreamSynchronize(st));
+        }
+    } else {
     {
         std::vector<double> hc(ld);
         GLF_HIP(ctx, hipMemcpyAsync(hc.data(), c.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
@@ -973,6 +1020,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
         GLF_HIP(ctx, hipStreamSynchronize(st));
     }
     GLF_TRY(apply_filter(ctx, d_img, phi_base, pix0, pix1, m, ld, w.p, filter_gain, filter_ysub, d_out, d_zf, cap ? cap->d_corr : nullptr));
+    } // (!rgb)
     } // (!fused)
     GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
     GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
@@ -982,7 +1030,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_nystroem, ctx->ev[3], ctx->ev[4]));
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-    if (stats) *stats = S;
+    if (stats && !rgb) *stats = S;
     // ---- signal planes through the guide's operator (after the guide is complete: its outputs, stats and collectives are
     // those of the plain call). Phi is written for them on every path: the fused guide filter never writes it, so it is
     // extended here with the guide's own Psi and contraction. Every rank takes this branch, so the collectives match.
@@ -1022,6 +1070,15 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
                 for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
         }
         GLF_HIP(ctx, hipMemcpyAsync(ws.p, hws.data(), sizeof(float) * ns * ld, hipMemcpyHostToDevice, st));
+        if (rgb) { // the channels' outputs, clamped and cast as the grey d_out; the filter stage ends here
+            GLF_TRY(apply_filter_rgb(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, sig->rgb_out, d_zf, N));
+            GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
+            GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
+            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
+            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
+            if (stats) *stats = S;
+            return GLF_OK;
+        }
         GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
         GLF_HIP(ctx, hipStreamSynchronize(st));
     }

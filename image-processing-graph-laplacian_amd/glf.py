@@ -32,7 +32,7 @@ OK = 0
 ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_NODEVICE, ERR_COMM, ERR_NOCONV, ERR_IO, ERR_UNSUPPORTED = range(-1, -9, -1)
 MAT_DENSE, MAT_DIAG, MAT_KERNEL_B = 0, 1, 2
 ROWS_NA, ROWS_SAMPLE_FIRST, ROWS_RASTER = 0, 1, 2
-KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM = 0, 1, 2, 3
+KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM, KERNEL_BILATERAL_RGB = 0, 1, 2, 3, 4
 CONTRACT_F32_MFMA, CONTRACT_F16_SPLIT = 1, 2
 FILTER_REFERENCE, FILTER_POC, FILTER_SMOOTH, FILTER_SHARPEN = 0, 1, 2, 3
 SAMPLING_UNIFORM, SAMPLING_RANDOM = 0, 1
@@ -50,6 +50,7 @@ EXPORTS = [
     "glf_InverseDiagMat", "glf_Nystroem", "glf_Permutation", "glf_ComputeResultFromLaplacian", "glf_Sinkhorn", "glf_SinkhornRows", "glf_Orthogonalisation",
     "glf_options_default", "glf_image_processing", "glf_image_processing_capture", "glf_ctx_debug_violations", "glf_ctx_cached_bytes", "glf_image_processing_batch", "glf_EntireComputation", "glf_read_png", "glf_write_png", "glf_read_png_rgb", "glf_write_png_rgb",
     "glf_image_processing_signals", "glf_multi_image_processing_signals",
+    "glf_image_processing_rgb", "glf_multi_image_processing_rgb", "glf_image_processing_rgb_capture",
 ]
 MAX_SIGNALS = 4
 
@@ -346,6 +347,27 @@ class Multi:
                       eigvals=lam[:s.m].copy()) for s in stats]
         return out, zf, sig_out, infos
 
+    def image_processing_rgb(self, img, opt=None, want_float=False):
+        """glf_multi_image_processing_rgb: host uint8 [H, W, 3] in, (out u8 [H, W, 3], zf f32 [3, H, W] or None, per-rank infos)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
+        h, w = img.shape[:2]
+        opt = opt or default_options()
+        out = np.zeros((h, w, 3), dtype=np.uint8)
+        zf = np.zeros((3, h, w), dtype=np.float32) if want_float else None
+        lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
+        stats = (Stats * self.n)()
+        rc = _lib.glf_multi_image_processing_rgb(self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h),
+                                                 out.ctypes.data_as(C.c_void_p), zf.ctypes.data_as(C.c_void_p) if want_float else None,
+                                                 lam.ctypes.data_as(C.c_void_p), stats)
+        if rc != OK:
+            raise GlfError(rc, "glf_multi_image_processing_rgb: " + _lib.glf_multi_last_error(self._w).decode())
+        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
+                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
+                      eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
+        return out, zf, infos
+
     def comm_counters(self, rank=0, reset=True):
         """Collectives rank `rank` issued since the last reset: dict(allreduce_calls, allreduce_bytes, allgather_calls, allgather_bytes)."""
         return _comm_counters(C.c_void_p(_lib.glf_multi_ctx(self._w, C.c_int(rank))), reset)
@@ -596,8 +618,10 @@ class Context:
     # -- stages (names as in hpc/*.h) -------------------------------------------------------
     def ComputeAffinityMatrices(self, d_img, sample_indices, want_KA=True, kernel=KERNEL_BILATERAL,
                                 h_loc=40.0, h_val=30.0):
-        assert d_img.dtype == self.torch.uint8 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
+        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3])
+        assert d_img.dtype == self.torch.uint8 and d_img.is_cuda and d_img.is_contiguous()
+        assert d_img.dim() == (3 if kernel == KERNEL_BILATERAL_RGB else 2) and (kernel != KERNEL_BILATERAL_RGB or d_img.shape[2] == 3)
+        h, w = d_img.shape[:2]
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)
         K_A, K_B = Mat(), Mat()
         self._check(_lib.glf_ComputeAffinityMatrices(
@@ -787,6 +811,58 @@ class Context:
                     ms_total=st.ms_total, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
                     filter_fused=st.filter_fused, eigvals=lam[:st.m].copy())
         return out, zf, sig_out, info
+
+    def image_processing_rgb(self, d_rgb, opt=None, want_float=False, capture=False):
+        """Colour-guided filtering (glf_image_processing_rgb): d_rgb (device uint8 [H, W, 3]) defines the graph through its RGB
+        differences, and each channel goes through the graph's filter. Returns (out uint8 [H, W, 3], zf float32 [3, H, W] or None,
+        info). capture=True (glf_image_processing_rgb_capture) adds info["capture"]: phi_A [p, ld] and phi [rows of this rank *
+        width, ld] as device tensors, the degree vector as a numpy array."""
+        torch = self.torch
+        assert d_rgb.dtype == torch.uint8 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
+        h, w = d_rgb.shape[:2]
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w, 3), dtype=torch.uint8, device=self.device)
+            zf = torch.zeros((3, h, w), dtype=torch.float32, device=self.device) if want_float else None
+        st = Stats()
+        p_real = _realised_samples(w, h, opt)
+        lam = np.zeros(max(1, p_real), dtype=np.float64)
+        cap, keep = None, None
+        if capture:
+            m_req = int(opt.num_eigvals) if 0 < opt.num_eigvals < p_real else max(1, p_real - 1)
+            ld = 32
+            while ld < min(m_req, 256):
+                ld *= 2
+            rows = shard_rows(h, *self._native_rank) if getattr(self, "_native_rank", None) else (0, h)
+            with torch.cuda.stream(self.stream):
+                phi_A = torch.zeros(((p_real + 63) // 64 * 64, ld), dtype=torch.float32, device=self.device)
+                phi = torch.zeros(((rows[1] - rows[0]) * w, ld), dtype=torch.float32, device=self.device)
+            deg_host = np.zeros(p_real, dtype=np.float64)
+            cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(), None,
+                          deg_host.ctypes.data, None, 0)
+            keep = (phi_A, phi, deg_host)
+        rc = _lib.glf_image_processing_rgb_capture(self._ctx, C.byref(opt), C.c_void_p(d_rgb.data_ptr()), C.c_int(w), C.c_int(h),
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if want_float else None,
+                                                   lam.ctypes.data_as(C.c_void_p), C.byref(st), C.byref(cap) if cap else None)
+        self._check(rc, "image_processing_rgb")
+        self.stream.synchronize()
+        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, inner_its_total=st.eig.inner_its_total,
+                    residual=st.eig.residual, row0=st.row0, row1=st.row1, ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian,
+                    ms_eigen=st.ms_eigen, ms_nystroem=st.ms_nystroem, ms_filter=st.ms_filter, ms_total=st.ms_total,
+                    nystroem_kernel_ms=st.nystroem_kernel_ms, contraction=st.contraction, nystroem_evaluated=st.nystroem_evaluated,
+                    degree_evaluated=st.degree_evaluated, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
+                    filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded, eigvals=lam[:st.m].copy())
+        if capture:
+            assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
+            info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], degree=keep[2][:st.p].copy(), ld=int(cap.ld))
+        return out, zf, info
+
+
+def _realised_samples(w, h, opt):
+    """An upper bound of the sample count a call realises (the size of its eigenvalue array)."""
+    req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
+    return int(Sampling(w, h, req).size) if not getattr(opt, "sampling", 0) else max(req, 1) * 2 + 64
 
 
 def image_processing_batch(contexts, d_imgs, opt=None):

@@ -8,7 +8,7 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma]]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
  * (python/image_processing.py:197-241, B = 1.5) with W = Phi diag(1 - mu) Phi^T from the eigenpairs this program computes.
@@ -17,6 +17,8 @@
  * rounded to 8 bits first because every kernel here works on u8 pixel values (the PoC filters the unrounded floats).
  * -chroma (with -color) filters the two chroma planes too: the unrounded U and V go through the luma's graph with the same
  * -filter (glf_image_processing_signals), so chroma noise is smoothed along the luma's edges.
+ * -rgb_graph (with -color) builds the graph from the RGB differences instead of the luma (glf_image_processing_rgb: the colour
+ * bilateral kernel, which sees edges between colours of equal luma) and filters R, G and B through it with the same -filter.
  * -dump_residual writes results/residuals.png = |input - output| stretched to the full grey range, the PoC's residual image
  * (python/image_processing.py:378-380: plt.imsave of np.abs(y - z) with cmap 'gray' autoscales min..max).
  * -no_approx runs the full-matrix mode (hpc/image_processing.c:155-181); -use_slepc is accepted and refused.
@@ -318,8 +320,37 @@ static png_bytep *ColorComputation(const char *filename, unsigned *width_out, un
     *width_out = (unsigned)w;
     *height_out = (unsigned)h;
     *input_rgb = rgb;
-    printf("Read image %s of size %dx%d => %d pixels (colour: the luma plane is filtered)\n", filename, w, h, w * h);
     const size_t n = (size_t)w * h;
+    if (opt_has("-rgb_graph")) { /* the colour graph: R, G, B through the operator built from the RGB differences */
+        printf("Read image %s of size %dx%d => %d pixels (colour: graph from the RGB differences, R, G, B filtered)\n", filename, w, h, w * h);
+        glf_ctx *cctx = glf_world();
+        uint8_t *flat = (uint8_t *)malloc(3 * n);
+        void *d_rgb = NULL, *d_rgb_out = NULL;
+        glf_options copt;
+        glf_stats cst;
+        fill_options(&copt, (unsigned)w, (unsigned)h);
+        int ok = flat && glf_malloc(cctx, &d_rgb, 3 * n) == GLF_OK && glf_malloc(cctx, &d_rgb_out, 3 * n) == GLF_OK;
+        for (int r = 0; ok && r < h; ++r) memcpy(flat + (size_t)r * 3 * w, rgb[r], 3 * (size_t)w);
+        ok = ok && glf_memcpy_h2d(cctx, d_rgb, flat, 3 * n) == GLF_OK;
+        if (ok) {
+            const int rc = glf_image_processing_rgb(cctx, &copt, (const uint8_t *)d_rgb, w, h, (uint8_t *)d_rgb_out, NULL, NULL, &cst);
+            if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_rgb: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(cctx));
+            ok = rc == GLF_OK && glf_memcpy_d2h(cctx, flat, d_rgb_out, 3 * n) == GLF_OK;
+        }
+        if (ok) {
+            print_stage_times(&cst, copt.epsilon);
+            rows = (png_bytep *)malloc(sizeof(png_bytep) * (size_t)h);
+            for (int r = 0; rows && r < h; ++r) {
+                rows[r] = (png_bytep)malloc(3 * (size_t)w);
+                if (rows[r]) memcpy(rows[r], flat + (size_t)r * 3 * w, 3 * (size_t)w);
+            }
+        }
+        free(flat);
+        if (d_rgb) glf_free(cctx, d_rgb);
+        if (d_rgb_out) glf_free(cctx, d_rgb_out);
+        return rows;
+    }
+    printf("Read image %s of size %dx%d => %d pixels (colour: the luma plane is filtered)\n", filename, w, h, w * h);
     /* rgb_from_yuv = inv(yuv_from_rgb), python/utils.py:38 */
     double inv[3][3];
     {
@@ -487,6 +518,12 @@ int main(int argc, char **argv)
     png_bytep *img_bytes = NULL, *output_img = NULL;
     if (opt_has("-chroma") && !opt_has("-color")) {
         fprintf(stderr, "-chroma filters the chroma planes of a colour image: it needs -color\n");
+        FinalizeProgram();
+        return 1;
+    }
+    if (opt_has("-rgb_graph") && (!opt_has("-color") || opt_has("-chroma"))) {
+        fprintf(stderr, opt_has("-color") ? "-rgb_graph filters R, G and B through the colour graph: it cannot be combined with -chroma\n"
+                                          : "-rgb_graph builds the graph of a colour image: it needs -color\n");
         FinalizeProgram();
         return 1;
     }

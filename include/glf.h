@@ -159,7 +159,12 @@ enum { GLF_MAT_DENSE = 0, GLF_MAT_DIAG = 1, GLF_MAT_KERNEL_B = 2 };
 enum { GLF_ROWS_NA = 0, GLF_ROWS_SAMPLE_FIRST = 1, GLF_ROWS_RASTER = 2 };
 /* NLM: non-local means, 7 x 7 Gaussian-weighted patches of the symmetrically padded image, K = exp(-|| G o (P_i - P_j) ||^2 / h_val^2)
  * (python/affinity_methods/NLM.py:9-34, where h = 3; the C reference has bilateral / photometric / spatial only, hpc/affinity.c:8-121) */
-enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3 };
+/* BILATERAL_RGB: the colour bilateral kernel K = exp(-(dr^2 + dc^2) / h_loc^2) exp(-(dR^2 + dG^2 + dB^2) / h_val^2), i.e. the
+ * photometric factor once per channel. With it the stage entry points (glf_ComputeAffinityMatrices and every consumer of its
+ * KERNEL_B descriptor) read d_img as interleaved uint8 [height][width][3], the layout of glf_read_png_rgb. h_loc and h_val keep
+ * their per-channel meaning: a grey image replicated into three channels gives the grey graph at h_val * sqrt(3). It has no
+ * grid-factored, rank or band form: the entry-by-entry kernels run (f32 MFMA contraction whatever glf_ctx_set_contraction says). */
+enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3, GLF_KERNEL_BILATERAL_RGB = 4 };
 
 /* Replaces PETSc Mat (MATMPIDENSE / MATMPIAIJ diagonal). */
 typedef struct glf_mat {
@@ -400,6 +405,17 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
                                  const float *d_sig, float *d_sig_out, uint8_t *d_out, float *d_zf, double *eigvals_out,
                                  glf_stats *stats);
 
+/* Colour-guided filtering: the graph is built from the RGB differences (GLF_KERNEL_BILATERAL_RGB; opt->kernel must be
+ * GLF_KERNEL_BILATERAL or GLF_KERNEL_BILATERAL_RGB, both mean the colour kernel here, any other gives GLF_ERR_UNSUPPORTED) on
+ * the sampler of opt->sampling, and each channel x_c of R, G, B goes through the one operator with the filter of
+ * opt->filter_mode: z_c = (1 - ysub) x_c + gain Phi f(Pi) Phi^T x_c, then clamped and cast as glf_image_processing's d_out.
+ * d_rgb / d_out_rgb: device uint8 [height][width][3] interleaved, d_rgb replicated on every rank; with a comm rank g writes its
+ * own pixel rows only. d_zf optional: device float [3][height*width] (planes R, G, B of z before the clamp). eigvals_out: HOST
+ * double[m] or NULL. More than 256 eigenpairs: GLF_ERR_UNSUPPORTED. The colour kernel has no band, grid or rank form (yet): the
+ * entry-by-entry kernels run and L_A is stored (stats.nystroem_path = matvec_path = 0, filter_fused = 0). */
+int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
+                             float *d_zf, double *eigvals_out, glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -418,6 +434,10 @@ typedef struct glf_capture {
 } glf_capture;
 int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height,
                                  uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap);
+/* The same by-products of one glf_image_processing_rgb call: d_phi_A, d_phi and h_degree as above; h_c and d_corr are not
+ * written (there is one c = Phi^T x_c and one correction per channel: the float z gives them). */
+int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height,
+                                     uint8_t *d_out_rgb, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
@@ -442,6 +462,11 @@ int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8
 int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height,
                                        int nsig, const float *h_sig, float *h_sig_out, uint8_t *h_out, float *h_zf,
                                        double *eigvals_out, glf_stats *stats);
+
+/* glf_multi_image_processing for colour (glf_image_processing_rgb): h_rgb / h_out_rgb HOST uint8 [height][width][3]; each rank's
+ * pixel rows are gathered into h_out_rgb (h_zf optional HOST float [3][height*width]). */
+int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height,
+                                   uint8_t *h_out_rgb, float *h_zf, double *eigvals_out, glf_stats *stats);
 
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
