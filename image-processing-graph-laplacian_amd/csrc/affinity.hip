@@ -41,6 +41,18 @@ __global__ void k_sample_tables_rgb(const uint8_t *__restrict__ rgb, int width, 
     mask[px] = 1;
 }
 
+// 16-bit grey: the grey record {row, col, v, 0} with v in 0..65535 (exact in f32)
+__global__ void k_sample_tables_u16(const uint16_t *__restrict__ img, int width, int64_t N, unsigned p, const uint32_t *__restrict__ idx,
+                                    float4 *__restrict__ samples, uint8_t *__restrict__ mask)
+{
+    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p) return;
+    const uint32_t px = idx[i];
+    if ((int64_t)px >= N) return;
+    samples[i] = make_float4((float)(px / (uint32_t)width), (float)(px % (uint32_t)width), (float)img[px], 0.f);
+    mask[px] = 1;
+}
+
 int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int height, unsigned p,
                         const unsigned *h_idx, SampleTables &out, int kernel)
 {
@@ -60,6 +72,9 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     if (kernel == GLF_KERNEL_BILATERAL_RGB)
         hipLaunchKernelGGL(k_sample_tables_rgb, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p,
                            out.mask.p);
+    else if (kernel == GLF_KERNEL_BILATERAL_U16)
+        hipLaunchKernelGGL(k_sample_tables_u16, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const uint16_t *>(d_img), width,
+                           N, p, out.idx.p, out.samples.p, out.mask.p);
     else
         hipLaunchKernelGGL(k_sample_tables, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p,
                            out.idx.p, out.samples.p, out.mask.p);
@@ -402,7 +417,8 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 int weighted_sums_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
                        const unsigned *h_idx, KernelCoef coef, int window, const float *d_plane, double wabs, double *d_out)
 {
-    if (coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB) return GLF_ERR_UNSUPPORTED;
+    if (coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB || coef.kernel == GLF_KERNEL_BILATERAL_U16)
+        return GLF_ERR_UNSUPPORTED;
     return degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_out, window, nullptr, nullptr, d_plane, wabs);
 }
 
@@ -420,6 +436,8 @@ int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, 
     }
     if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) // no factored form over 2^24 colours: its own windowed sweep (rgb.hip)
         return rgb_degree_rows(ctx, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
+    if (coef.kernel == GLF_KERNEL_BILATERAL_U16) // no factored form over 65 536 levels, no 256-entry table: its own windowed sweep (u16.hip)
+        return u16_degree_rows(ctx, reinterpret_cast<const uint16_t *>(d_img), width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
     const int rc = degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_degree, window, evaluated, d_ysum);
     if (rc != GLF_ERR_UNSUPPORTED) {
         if (have_ysum) *have_ysum = rc == GLF_OK && d_ysum != nullptr; // (only the grid-factored degree has the value-weighted sums)
@@ -554,6 +572,7 @@ int build_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, Kerne
         return nlm_sample_matrix(ctx, d_img, width, height, d_idx, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
     }
     if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) return rgb_sample_matrix(ctx, d_samples, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
+    // (GLF_KERNEL_BILATERAL_U16 takes k_sample_matrix as it is: it reads the values from the grey records, with no level table)
     if (ncols == 0) {
         col0 = 0;
         ncols = p;

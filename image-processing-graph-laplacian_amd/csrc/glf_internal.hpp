@@ -228,6 +228,11 @@ __device__ __forceinline__ float kernel_eval(float dr, float dc, float dv, float
 // byte k of a packed colour R + 256 G + 65536 B as f32 (v_cvt_f32_ubyte<k>)
 __device__ __forceinline__ float ubyte_f32(unsigned v, int k) { return (float)((v >> (8 * k)) & 0xffu); }
 
+// The pixel generators of the entry-by-entry kernels (k_nystroem and, later, a band form): how a pixel's value is read from the
+// image and compared with a sample record. Grey: uint8 [N], record {row, col, v, 0}; Rgb: interleaved uint8 [N][3], record
+// {row, col, 0, R + 256 G + 65536 B}; U16: uint16 [N] (the same byte pointer, read as 16-bit), record {row, col, v, 0}.
+enum class PixGen { Grey, Rgb, U16 };
+
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
 // VGPRs. Issued from inline asm on purpose: with the builtin, hipcc (ROCm 7.2) cannot prove that the DMA
@@ -272,7 +277,8 @@ struct SampleTables {
     DevBuf<uint8_t> mask;
     DevBuf<uint32_t> idx;
 };
-// kernel GLF_KERNEL_BILATERAL_RGB: d_img is interleaved RGB and a record is {row, col, 0, R + 256 G + 65536 B}
+// kernel GLF_KERNEL_BILATERAL_RGB: d_img is interleaved RGB and a record is {row, col, 0, R + 256 G + 65536 B};
+// GLF_KERNEL_BILATERAL_U16: d_img is uint16_t [height][width] and a record is {row, col, v, 0} as for grey
 int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int height, unsigned p,
                         const unsigned *h_idx, SampleTables &out, int kernel = GLF_KERNEL_BILATERAL);
 
@@ -320,6 +326,14 @@ int rgb_degree_rows(glf_ctx *ctx, const uint8_t *d_rgb, int width, int height, i
 int rgb_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, KernelCoef coef, float *d_out, int64_t ld, bool laplacian,
                       double alpha, const double *d_degree, unsigned col0, unsigned ncols);
 int rgb_planes(glf_ctx *ctx, const uint8_t *d_rgb, int64_t N, float *d_planes); // [3][N] float channel planes
+// 16-bit grey bilateral kernel (u16.hip, GLF_KERNEL_BILATERAL_U16): image uint16_t [height][width]; the same contract as
+// degree_rows (K_A / L_A come from k_sample_matrix on the grey records; nystroem_contract runs k_nystroem with the 16-bit read)
+int u16_degree_rows(glf_ctx *ctx, const uint16_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
+                    KernelCoef coef, double *d_degree, double *evaluated);
+int u16_plane(glf_ctx *ctx, const uint16_t *d_img, int64_t N, float *d_plane); // the image as one float plane [N]
+// 16-bit output: d_w [ld]; d_img / d_out uint16_t [N], rows [pix0, pix1) only; d_zf optional [N]
+int apply_filter_u16(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain, float ysub,
+                     const uint16_t *d_img, uint16_t *d_out, float *d_zf);
 int laplacian_from_KA(glf_ctx *ctx, const float *d_KA, int64_t ldk, unsigned p, float *d_LA, int64_t ld,
                       double alpha, const double *d_degree);
 

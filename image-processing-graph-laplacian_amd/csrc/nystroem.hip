@@ -102,9 +102,10 @@ __device__ __forceinline__ int build_chunk_list(const int4 *__restrict__ box, in
     return scratch[256];
 }
 
-// RGB: the colour generator (GLF_KERNEL_BILATERAL_RGB, rgb.hip): img is interleaved RGB, a sample record carries its packed colour
-// in w, and the epilogue has no grey y (cpartial must be null)
-template <int MB, int PB, bool SKIP, bool RGB = false> // MB = ld / 32 column blocks; PB = 32-pixel blocks per wave; SKIP: chunk list
+// GEN: the pixel generator (PixGen, glf_internal.hpp). Rgb: the colour generator (GLF_KERNEL_BILATERAL_RGB, rgb.hip): img is
+// interleaved RGB and a sample record carries its packed colour in w. U16 (GLF_KERNEL_BILATERAL_U16, u16.hip): img is uint16_t
+// and the grey record and exponent apply. Only the grey generator has the epilogue's y (cpartial must be null for the others).
+template <int MB, int PB, bool SKIP, PixGen GEN = PixGen::Grey> // MB = ld / 32 column blocks; PB = 32-pixel blocks per wave; SKIP: chunk list
 __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ img, int width, int64_t pix0, int64_t pix1,
                                                    const float4 *__restrict__ samples, unsigned p, float s_loc,
                                                    float s_val, const float *__restrict__ psi,
@@ -115,6 +116,7 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
 {
     constexpr int LD = MB * 32;
     constexpr int KC = NYS_KC;
+    constexpr bool RGB = GEN == PixGen::Rgb;
     __shared__ unsigned short clist[SKIP ? NYS_MAXCH : 1];
     __shared__ int cscratch[SKIP ? 257 : 1];
     // one array for everything (guide: a second __shared__ object can de-pipeline LDS staging)
@@ -137,6 +139,8 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
             pv[b] = (float)img[3 * px];
             pg[b] = (float)img[3 * px + 1];
             pb[b] = (float)img[3 * px + 2];
+        } else if constexpr (GEN == PixGen::U16) {
+            pv[b] = (float)reinterpret_cast<const uint16_t *>(img)[px];
         } else {
             pv[b] = (float)img[px];
         }
@@ -223,7 +227,7 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
                 if (is_sample) continue; // sample rows come from Phi_A (hpc/nystroem.c:25-34)
                 dst = (int64_t)p + px - (int64_t)samples_before(idx, p, (uint32_t)px);
             }
-            const float y = (RGB || is_sample) ? 0.f : (float)img[px];
+            const float y = (GEN != PixGen::Grey || is_sample) ? 0.f : (float)img[px];
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
                 const float v = acc[b][j][r];
@@ -330,7 +334,7 @@ struct NysWindow {
     }
 };
 
-template <int MB, int PB, bool RGB = false>
+template <int MB, int PB, PixGen GEN = PixGen::Grey>
 static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
                            const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
                            KernelCoef coef, const float *d_psi, float *d_phi, int raster, double *d_c, float *kernel_ms,
@@ -346,11 +350,11 @@ static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_
     GLF_TRY(win.init(ctx, d_samples, p, coef, window, 151.0, nwg));
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (win.radius >= 0)
-        hipLaunchKernelGGL((k_nystroem<MB, PB, true, RGB>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, true, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
                            d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     else
-        hipLaunchKernelGGL((k_nystroem<MB, PB, false, RGB>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, false, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
                            d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     GLF_LAUNCH_CHECK(ctx);
@@ -813,6 +817,21 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
 #include "grid_common.inc"
 #include "nystroem_grid.inc"
 
+// the f32-MFMA k_nystroem with a non-grey pixel generator (no c = Phi^T y in its epilogue)
+template <PixGen GEN>
+static int nystroem_entrywise(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
+                              const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
+                              float *d_phi, int raster, float *kernel_ms, int window, uint64_t *entries_evaluated)
+{
+    switch (ld) {
+    case 32: return launch_nystroem<1, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
+    case 64: return launch_nystroem<2, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
+    case 128: return launch_nystroem<4, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
+    case 256: return launch_nystroem<8, 1, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
+    }
+    return GLF_ERR_UNSUPPORTED;
+}
+
 int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
                       const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
                       KernelCoef coef, float /*scale folded into psi*/, const float *d_psi, unsigned m, unsigned ld,
@@ -834,15 +853,13 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
         return nlm_nystroem(ctx, d_img, width, height, pix0, pix1, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c, kernel_ms);
     }
     int rc = GLF_ERR_UNSUPPORTED;
-    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) { // the colour generator: entry by entry, f32 MFMA (no factored or split-f16 form)
-        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour kernel has no grey y for Phi^T y");
+    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB || coef.kernel == GLF_KERNEL_BILATERAL_U16) {
+        // the colour and 16-bit generators: entry by entry, f32 MFMA (no factored or split-f16 form)
+        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour and 16-bit kernels have no 8-bit y for Phi^T y");
         window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
-        switch (ld) {
-        case 32: rc = launch_nystroem<1, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
-        case 64: rc = launch_nystroem<2, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
-        case 128: rc = launch_nystroem<4, 2, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
-        case 256: rc = launch_nystroem<8, 1, true>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated); break;
-        }
+        rc = coef.kernel == GLF_KERNEL_BILATERAL_RGB
+                 ? nystroem_entrywise<PixGen::Rgb>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated)
+                 : nystroem_entrywise<PixGen::U16>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated);
         if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
         return rc;
     }

@@ -176,13 +176,13 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
                                 float h_val)
 {
     if (!ctx || !K_B || !d_img || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_RGB) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
+    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_U16) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
     if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3)) // (nlm.hip reflects an out-of-image patch index once: valid from 3 pixels on)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     GLF_ENTER(ctx);
     const unsigned p = sample_size;
     SampleTables tb;
-    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3])
+    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3]; U16: uint16_t)
     const KernelCoef coef = make_coef(kernel, h_loc, h_val);
     DevBuf<double> deg;
     GLF_TRY(deg.alloc(ctx, p));
@@ -481,12 +481,14 @@ int glf_image_processing(glf_ctx *ctx, const glf_options *opt_in, const uint8_t 
 }
 
 // extra signal planes of glf_image_processing_signals (nullptr: the guide alone); rgb_out set: glf_image_processing_rgb, the guide is
-// the colour image and its three channels are the planes (formed inside from the image)
+// the colour image and its three channels are the planes (formed inside from the image); u16_out set: glf_image_processing_u16, the
+// guide is the 16-bit image and it is the one plane
 struct SignalPlanes {
     int nsig;
     const float *d_sig;
     float *d_out;
     uint8_t *rgb_out = nullptr;
+    uint16_t *u16_out = nullptr;
 };
 
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
@@ -523,6 +525,21 @@ int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const
     return image_processing_run(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, cap, &sig);
 }
 
+int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
+                             float *d_zf, double *eigvals_out, glf_stats *stats)
+{
+    return glf_image_processing_u16_capture(ctx, opt, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
+}
+
+int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
+                                     float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
+{
+    if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    const SignalPlanes sig{1, nullptr, nullptr, nullptr, d_out};
+    return image_processing_run(ctx, opt, reinterpret_cast<const uint8_t *>(d_img), width, height, reinterpret_cast<uint8_t *>(d_out), d_zf,
+                                eigvals_out, stats, cap, &sig);
+}
+
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
                                 float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
@@ -538,15 +555,22 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
             return set_error(ctx, GLF_ERR_INVALID, "glf_options.struct_size %u != %zu", opt_in->struct_size, sizeof(glf_options));
         opt = *opt_in;
     }
-    // the colour kernel reads the image as RGB: only the colour entry point takes it, and there it is the only kernel
-    const bool rgb = sig && sig->rgb_out;
+    // the colour kernel reads the image as RGB: only the colour entry point takes it, and there it is the only kernel; the same for
+    // the 16-bit kernel and the 16-bit entry point. Both guides have no 8-bit y: their values are filtered as planes (u8_guide false)
+    const bool rgb = sig && sig->rgb_out, u16 = sig && sig->u16_out, u8_guide = !rgb && !u16;
     if (rgb) {
         if (opt.kernel != GLF_KERNEL_BILATERAL && opt.kernel != GLF_KERNEL_BILATERAL_RGB)
             return set_error(ctx, GLF_ERR_UNSUPPORTED, "colour filtering: kernel %d (the colour bilateral kernel only)", opt.kernel);
         opt.kernel = GLF_KERNEL_BILATERAL_RGB;
+    } else if (u16) {
+        if (opt.kernel != GLF_KERNEL_BILATERAL && opt.kernel != GLF_KERNEL_BILATERAL_U16)
+            return set_error(ctx, GLF_ERR_UNSUPPORTED, "16-bit filtering: kernel %d (the 16-bit bilateral kernel only)", opt.kernel);
+        opt.kernel = GLF_KERNEL_BILATERAL_U16;
     } else if (opt.kernel == GLF_KERNEL_BILATERAL_RGB)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "the colour kernel takes an RGB image: glf_image_processing_rgb");
-    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_RGB) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
+    else if (opt.kernel == GLF_KERNEL_BILATERAL_U16)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
+    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_U16) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     if (opt.filter_mode < GLF_FILTER_REFERENCE || opt.filter_mode > GLF_FILTER_SHARPEN) return set_error(ctx, GLF_ERR_INVALID, "filter_mode %d", opt.filter_mode);
@@ -571,12 +595,17 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
     hipStream_t st = ctx->stream;
     glf_stats S{};
-    DevBuf<float> rgb_planes_buf; // colour: the channels as float planes [3][N] (Phi^T x_c)
+    DevBuf<float> rgb_planes_buf; // colour: the channels as float planes [3][N] (Phi^T x_c); 16-bit: the image as one plane
     SignalPlanes rgb_sig{};
     if (rgb) {
         GLF_TRY(rgb_planes_buf.alloc(ctx, (size_t)3 * N));
         GLF_TRY(rgb_planes(ctx, d_img, N, rgb_planes_buf.p));
         rgb_sig = SignalPlanes{3, rgb_planes_buf.p, nullptr, sig->rgb_out};
+        sig = &rgb_sig;
+    } else if (u16) { // 16-bit: the image as one float plane [N] (Phi^T y with f64 sums)
+        GLF_TRY(rgb_planes_buf.alloc(ctx, (size_t)N));
+        GLF_TRY(u16_plane(ctx, reinterpret_cast<const uint16_t *>(d_img), N, rgb_planes_buf.p));
+        rgb_sig = SignalPlanes{1, rgb_planes_buf.p, nullptr, nullptr, sig->u16_out};
         sig = &rgb_sig;
     }
 
@@ -976,17 +1005,17 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     float *phi_base = phi.p - (size_t)pix0 * ld; // rows addressed by absolute pixel index
     GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * ld, st));
     GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha),
-                              psi.p, m, ld, phi_base, 1, rgb ? nullptr : c.p, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
+                              psi.p, m, ld, phi_base, 1, u8_guide ? c.p : nullptr, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
                               &S.nystroem_path, &rps));
     nystroem_stats();
     // sample rows of this shard <- Phi_A, and their share of c
     if (si1 > si0)
-        GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, rgb ? nullptr : c.p, m));
-    if (!rgb) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
+        GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, u8_guide ? c.p : nullptr, m));
+    if (u8_guide) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
     GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
     // ---- filter ------------------------------------------------------------------------------
-    if (rgb) { // (no grey y: the channels are filtered below, as planes; the sharpening weights need G)
-        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour generator has no split-f16 form)
+    if (!u8_guide) { // (no 8-bit y: the channels / the 16-bit image are filtered below, as planes; the sharpening weights need G)
+        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour and 16-bit generators have no split-f16 form)
         if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
         if (opt.filter_mode == GLF_FILTER_SHARPEN) {
             DevBuf<double> G;
@@ -1020,7 +1049,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
         GLF_HIP(ctx, hipStreamSynchronize(st));
     }
     GLF_TRY(apply_filter(ctx, d_img, phi_base, pix0, pix1, m, ld, w.p, filter_gain, filter_ysub, d_out, d_zf, cap ? cap->d_corr : nullptr));
-    } // (!rgb)
+    } // (u8_guide)
     } // (!fused)
     GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
     GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
@@ -1030,7 +1059,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_nystroem, ctx->ev[3], ctx->ev[4]));
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
     GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-    if (stats && !rgb) *stats = S;
+    if (stats && u8_guide) *stats = S;
     // ---- signal planes through the guide's operator (after the guide is complete: its outputs, stats and collectives are
     // those of the plain call). Phi is written for them on every path: the fused guide filter never writes it, so it is
     // extended here with the guide's own Psi and contraction. Every rank takes this branch, so the collectives match.
@@ -1070,8 +1099,11 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
                 for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
         }
         GLF_HIP(ctx, hipMemcpyAsync(ws.p, hws.data(), sizeof(float) * ns * ld, hipMemcpyHostToDevice, st));
-        if (rgb) { // the channels' outputs, clamped and cast as the grey d_out; the filter stage ends here
-            GLF_TRY(apply_filter_rgb(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, sig->rgb_out, d_zf, N));
+        if (!u8_guide) { // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
+            if (rgb) GLF_TRY(apply_filter_rgb(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, sig->rgb_out, d_zf, N));
+            else
+                GLF_TRY(apply_filter_u16(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, reinterpret_cast<const uint16_t *>(d_img),
+                                         sig->u16_out, d_zf));
             GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
             GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
             GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));

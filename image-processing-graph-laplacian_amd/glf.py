@@ -32,7 +32,7 @@ OK = 0
 ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_NODEVICE, ERR_COMM, ERR_NOCONV, ERR_IO, ERR_UNSUPPORTED = range(-1, -9, -1)
 MAT_DENSE, MAT_DIAG, MAT_KERNEL_B = 0, 1, 2
 ROWS_NA, ROWS_SAMPLE_FIRST, ROWS_RASTER = 0, 1, 2
-KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM, KERNEL_BILATERAL_RGB = 0, 1, 2, 3, 4
+KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM, KERNEL_BILATERAL_RGB, KERNEL_BILATERAL_U16 = 0, 1, 2, 3, 4, 5
 CONTRACT_F32_MFMA, CONTRACT_F16_SPLIT = 1, 2
 FILTER_REFERENCE, FILTER_POC, FILTER_SMOOTH, FILTER_SHARPEN = 0, 1, 2, 3
 SAMPLING_UNIFORM, SAMPLING_RANDOM = 0, 1
@@ -51,6 +51,7 @@ EXPORTS = [
     "glf_options_default", "glf_image_processing", "glf_image_processing_capture", "glf_ctx_debug_violations", "glf_ctx_cached_bytes", "glf_image_processing_batch", "glf_EntireComputation", "glf_read_png", "glf_write_png", "glf_read_png_rgb", "glf_write_png_rgb",
     "glf_image_processing_signals", "glf_multi_image_processing_signals",
     "glf_image_processing_rgb", "glf_multi_image_processing_rgb", "glf_image_processing_rgb_capture",
+    "glf_image_processing_u16", "glf_multi_image_processing_u16", "glf_image_processing_u16_capture", "glf_read_png16", "glf_write_png16",
 ]
 MAX_SIGNALS = 4
 
@@ -224,6 +225,33 @@ def write_png(path, img):
         raise GlfError(ERR_IO, path)
 
 
+def read_png16(path):
+    """A 16-bit greyscale PNG (colour type 0, bit depth 16) as uint16 [H, W]; any other format raises GlfError."""
+    rows = C.POINTER(C.POINTER(C.c_uint16))()
+    w, h = C.c_int(), C.c_int()
+    rc = _lib.glf_read_png16(path.encode(), C.byref(rows), C.byref(w), C.byref(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+    img = np.empty((h.value, w.value), dtype=np.uint16)
+    for r in range(h.value):
+        img[r] = np.ctypeslib.as_array(rows[r], shape=(w.value,))
+        _lib.glf_host_free(rows[r])
+    _lib.glf_host_free(rows)
+    return img
+
+
+def write_png16(path, img):
+    """Writes uint16 [H, W] as a 16-bit greyscale PNG."""
+    img = np.ascontiguousarray(img, dtype=np.uint16)
+    h, w = img.shape
+    rowptr = (C.POINTER(C.c_uint16) * h)()
+    for r in range(h):
+        rowptr[r] = C.cast(img.ctypes.data + r * w * 2, C.POINTER(C.c_uint16))
+    rc = _lib.glf_write_png16(path.encode(), rowptr, C.c_uint(w), C.c_uint(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+
+
 def shard_rows(height, rank, size):
     """Pixel rows [row0, row1) owned by `rank` (glf_shard_rows; used by glf_image_processing)."""
     r0, r1 = C.c_int(), C.c_int()
@@ -363,6 +391,27 @@ class Multi:
                                                  lam.ctypes.data_as(C.c_void_p), stats)
         if rc != OK:
             raise GlfError(rc, "glf_multi_image_processing_rgb: " + _lib.glf_multi_last_error(self._w).decode())
+        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
+                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
+                      eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
+        return out, zf, infos
+
+    def image_processing_u16(self, img, opt=None, want_float=False):
+        """glf_multi_image_processing_u16: host uint16 [H, W] in, (out uint16 [H, W], zf f32 [H, W] or None, per-rank infos)."""
+        img = np.ascontiguousarray(img, dtype=np.uint16)
+        if img.ndim != 2:
+            raise ValueError("image must be [H, W], got %s" % (img.shape,))
+        h, w = img.shape
+        opt = opt or default_options()
+        out = np.zeros((h, w), dtype=np.uint16)
+        zf = np.zeros((h, w), dtype=np.float32) if want_float else None
+        lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
+        stats = (Stats * self.n)()
+        rc = _lib.glf_multi_image_processing_u16(self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h),
+                                                 out.ctypes.data_as(C.c_void_p), zf.ctypes.data_as(C.c_void_p) if want_float else None,
+                                                 lam.ctypes.data_as(C.c_void_p), stats)
+        if rc != OK:
+            raise GlfError(rc, "glf_multi_image_processing_u16: " + _lib.glf_multi_last_error(self._w).decode())
         infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
                       nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
                       eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
@@ -618,8 +667,8 @@ class Context:
     # -- stages (names as in hpc/*.h) -------------------------------------------------------
     def ComputeAffinityMatrices(self, d_img, sample_indices, want_KA=True, kernel=KERNEL_BILATERAL,
                                 h_loc=40.0, h_val=30.0):
-        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3])
-        assert d_img.dtype == self.torch.uint8 and d_img.is_cuda and d_img.is_contiguous()
+        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3]; KERNEL_BILATERAL_U16: uint16 [H, W])
+        assert d_img.dtype == (self.torch.uint16 if kernel == KERNEL_BILATERAL_U16 else self.torch.uint8) and d_img.is_cuda and d_img.is_contiguous()
         assert d_img.dim() == (3 if kernel == KERNEL_BILATERAL_RGB else 2) and (kernel != KERNEL_BILATERAL_RGB or d_img.shape[2] == 3)
         h, w = d_img.shape[:2]
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)
@@ -857,6 +906,56 @@ class Context:
             assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
             info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], degree=keep[2][:st.p].copy(), ld=int(cap.ld))
         return out, zf, info
+
+    def image_processing_u16(self, d_img, opt=None, want_float=False, capture=False):
+        """16-bit greyscale filtering (glf_image_processing_u16): d_img (device uint16 [H, W]) defines the graph through its 16-bit
+        values (opt.h_val in 16-bit units) and goes through the graph's filter. Returns (out uint16 [H, W], zf float32 [H, W] or None,
+        info). capture=True (glf_image_processing_u16_capture) adds info["capture"] as image_processing_rgb does."""
+        torch = self.torch
+        assert d_img.dtype == torch.uint16 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
+        h, w = d_img.shape
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
+            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
+        st = Stats()
+        p_real = _realised_samples(w, h, opt)
+        lam = np.zeros(max(1, p_real), dtype=np.float64)
+        cap, keep = None, None
+        if capture:
+            cap, keep = self._capture_buffers(w, h, opt, p_real)
+        rc = _lib.glf_image_processing_u16_capture(self._ctx, C.byref(opt), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
+                                                   C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if want_float else None,
+                                                   lam.ctypes.data_as(C.c_void_p), C.byref(st), C.byref(cap) if cap else None)
+        self._check(rc, "image_processing_u16")
+        self.stream.synchronize()
+        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, inner_its_total=st.eig.inner_its_total,
+                    residual=st.eig.residual, row0=st.row0, row1=st.row1, ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian,
+                    ms_eigen=st.ms_eigen, ms_nystroem=st.ms_nystroem, ms_filter=st.ms_filter, ms_total=st.ms_total,
+                    nystroem_kernel_ms=st.nystroem_kernel_ms, contraction=st.contraction, nystroem_evaluated=st.nystroem_evaluated,
+                    degree_evaluated=st.degree_evaluated, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
+                    filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded, eigvals=lam[:st.m].copy())
+        if capture:
+            assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
+            info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], degree=keep[2][:st.p].copy(), ld=int(cap.ld))
+        return out, zf, info
+
+    def _capture_buffers(self, w, h, opt, p_real):
+        """glf_capture with phi_A, phi (this rank's rows) and the degree vector, and the buffers it points to."""
+        torch = self.torch
+        m_req = int(opt.num_eigvals) if 0 < opt.num_eigvals < p_real else max(1, p_real - 1)
+        ld = 32
+        while ld < min(m_req, 256):
+            ld *= 2
+        rows = shard_rows(h, *self._native_rank) if getattr(self, "_native_rank", None) else (0, h)
+        with torch.cuda.stream(self.stream):
+            phi_A = torch.zeros(((p_real + 63) // 64 * 64, ld), dtype=torch.float32, device=self.device)
+            phi = torch.zeros(((rows[1] - rows[0]) * w, ld), dtype=torch.float32, device=self.device)
+        deg_host = np.zeros(p_real, dtype=np.float64)
+        cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(), None,
+                      deg_host.ctypes.data, None, 0)
+        return cap, (phi_A, phi, deg_host)
 
 
 def _realised_samples(w, h, opt):

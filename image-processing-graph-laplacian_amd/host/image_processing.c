@@ -8,7 +8,7 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
  * (python/image_processing.py:197-241, B = 1.5) with W = Phi diag(1 - mu) Phi^T from the eigenpairs this program computes.
@@ -19,6 +19,9 @@
  * -filter (glf_image_processing_signals), so chroma noise is smoothed along the luma's edges.
  * -rgb_graph (with -color) builds the graph from the RGB differences instead of the luma (glf_image_processing_rgb: the colour
  * bilateral kernel, which sees edges between colours of equal luma) and filters R, G and B through it with the same -filter.
+ * -depth16 reads a 16-bit grey PNG and filters it on its 16-bit values (glf_image_processing_u16: the bilateral kernel with
+ * v in 0..65535, -h_val in 16-bit units, 30 x 257 by default -- the 8-bit default graph on the same content) with the same
+ * -filter, and writes results/input.png and results/output.png as 16-bit grey PNGs; -ngpu N works as for 8 bits.
  * -dump_residual writes results/residuals.png = |input - output| stretched to the full grey range, the PoC's residual image
  * (python/image_processing.py:378-380: plt.imsave of np.abs(y - z) with cmap 'gray' autoscales min..max).
  * -no_approx runs the full-matrix mode (hpc/image_processing.c:155-181); -use_slepc is accepted and refused.
@@ -307,6 +310,75 @@ out:
     return rows;
 }
 
+/* -depth16: img (rows of `width` uint16_t) through glf_image_processing_u16 on one context, or glf_multi_image_processing_u16 on
+ * ngpu ranks; returns the output rows (NULL on failure, the message printed). */
+static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned height, int ngpu, int backend)
+{
+    const size_t n = (size_t)width * height;
+    uint16_t *flat = (uint16_t *)malloc(sizeof(uint16_t) * n), *flat_out = (uint16_t *)calloc(n, sizeof(uint16_t));
+    uint16_t **rows = NULL;
+    glf_options opt;
+    fill_options(&opt, width, height);
+    int ok = flat && flat_out;
+    for (unsigned r = 0; ok && r < height; ++r) memcpy(flat + (size_t)r * width, img[r], sizeof(uint16_t) * width);
+    if (ok && ngpu > 0) {
+        glf_multi *world = NULL;
+        int *devices = NULL;
+        if (backend == GLF_MULTI_LOOPBACK) { /* every rank on the device of -device (default 0) */
+            const char *dev = opt_value("-device");
+            devices = (int *)malloc(sizeof(int) * (size_t)ngpu);
+            for (int r = 0; devices && r < ngpu; ++r) devices[r] = dev ? atoi(dev) : 0;
+        }
+        int rc = glf_multi_create(&world, ngpu, devices, backend);
+        free(devices);
+        glf_stats *st = (glf_stats *)calloc((size_t)ngpu, sizeof(glf_stats));
+        if (rc != GLF_OK) fprintf(stderr, "glf_multi_create(%d GPUs, %s): %s\n", ngpu, backend == GLF_MULTI_RCCL ? "rccl" : "loopback", glf_strerror(rc));
+        else if (st) {
+            rc = glf_multi_image_processing_u16(world, &opt, flat, (int)width, (int)height, flat_out, NULL, NULL, st);
+            if (rc != GLF_OK) fprintf(stderr, "glf_multi_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_multi_last_error(world));
+            else {
+                print_stage_times(&st[0], opt.epsilon);
+                for (int r = 0; r < ngpu; ++r)
+                    printf("rank %d: pixel rows [%d, %d), %.3f ms on the device\n", r, st[r].row0, st[r].row1, st[r].ms_total);
+            }
+        }
+        ok = rc == GLF_OK && st;
+        free(st);
+        if (world) glf_multi_destroy(world);
+    } else if (ok) {
+        glf_ctx *ctx = glf_world();
+        void *d_img = NULL, *d_out = NULL;
+        glf_stats st;
+        ok = glf_malloc(ctx, &d_img, sizeof(uint16_t) * n) == GLF_OK && glf_malloc(ctx, &d_out, sizeof(uint16_t) * n) == GLF_OK &&
+             glf_memcpy_h2d(ctx, d_img, flat, sizeof(uint16_t) * n) == GLF_OK;
+        if (ok) {
+            const int rc = glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
+            if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(ctx));
+            ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, sizeof(uint16_t) * n) == GLF_OK;
+            if (ok) print_stage_times(&st, opt.epsilon);
+        }
+        if (d_img) glf_free(ctx, d_img);
+        if (d_out) glf_free(ctx, d_out);
+    }
+    if (ok) {
+        rows = (uint16_t **)calloc(height, sizeof(uint16_t *));
+        for (unsigned r = 0; rows && r < height; ++r) {
+            rows[r] = (uint16_t *)malloc(sizeof(uint16_t) * width);
+            if (rows[r]) memcpy(rows[r], flat_out + (size_t)r * width, sizeof(uint16_t) * width);
+        }
+    }
+    free(flat);
+    free(flat_out);
+    return rows;
+}
+
+static void free_rows16(uint16_t **rows, int height)
+{
+    if (!rows) return;
+    for (int r = 0; r < height; ++r) free(rows[r]);
+    free(rows);
+}
+
 /* -color (python/image_processing.py:410-432): filter the luma of an RGB image, keep its chroma. Returns rows of 3 * width
  * bytes for glf_write_png_rgb; *input_rgb receives the input as read (for results/input.png). */
 static const double yuv_from_rgb[3][3] = {{0.299, 0.587, 0.114},                 /* python/utils.py:33-36 (the BT.601 YUV matrix) */
@@ -516,6 +588,15 @@ int main(int argc, char **argv)
 
     int width = 0, height = 0;
     png_bytep *img_bytes = NULL, *output_img = NULL;
+    if (opt_has("-depth16")) {
+        const char *other = opt_has("-color") ? "-color" : opt_has("-chroma") ? "-chroma" : opt_has("-rgb_graph") ? "-rgb_graph"
+                          : opt_has("-no_approx") ? "-no_approx" : NULL;
+        if (other) {
+            fprintf(stderr, "-depth16 filters a 16-bit grey image: it cannot be combined with %s\n", other);
+            FinalizeProgram();
+            return 1;
+        }
+    }
     if (opt_has("-chroma") && !opt_has("-color")) {
         fprintf(stderr, "-chroma filters the chroma planes of a colour image: it needs -color\n");
         FinalizeProgram();
@@ -526,6 +607,32 @@ int main(int argc, char **argv)
                                           : "-rgb_graph builds the graph of a colour image: it needs -color\n");
         FinalizeProgram();
         return 1;
+    }
+    if (opt_has("-depth16")) { /* 16-bit grey: its own reader, route and writer */
+        uint16_t **in16 = NULL, **out16 = NULL;
+        if (glf_read_png16(filename, &in16, &width, &height) != 0) {
+            uint8_t **in8 = NULL;
+            int w8 = 0, h8 = 0;
+            if (read_png(filename, &in8, &w8, &h8) == 0) {
+                fprintf(stderr, "-depth16 needs a 16-bit grey PNG: %s is an 8-bit image\n", filename);
+                free_rows(in8, h8);
+            } else
+                fprintf(stderr, "Could not read %s as a 16-bit gray PNG\n", filename);
+            FinalizeProgram();
+            return 1;
+        }
+        if (!opt_value("-h_val")) stage_h_val = 30.0f * 257.0f; /* the 8-bit default graph on the same content */
+        printf("Read image %s of size %dx%d => %d pixels (16-bit gray)\n", filename, width, height, width * height);
+        out16 = Depth16Computation(in16, (unsigned)width, (unsigned)height, ngpu,
+                                   nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL);
+        int dstatus = out16 ? 0 : 5;
+        if (glf_write_png16("results/input.png", in16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
+        if (out16 && glf_write_png16("results/output.png", out16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
+        printf("Total computation time: %fs\n", wtime() - start_time);
+        free_rows16(in16, height);
+        free_rows16(out16, height);
+        FinalizeProgram();
+        return dstatus;
     }
     if (opt_has("-color")) { /* python/image_processing.py:410-432 */
         unsigned cw = 0, ch = 0;

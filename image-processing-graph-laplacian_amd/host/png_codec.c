@@ -12,6 +12,8 @@
  *        Anything else (gray+alpha, 16-bit, palette, interlaced) is rejected with -1
  *        instead of being silently misread (survey quirk Q13).
  * write: 8-bit gray, non-interlaced (hpc/write_img.c:38-45).
+ * 16-bit gray (glf_read_png16 / glf_write_png16): colour type 0 at bit depth 16 only, big-endian samples, the five scanline
+ *        filters with a 2-byte pixel; every other format is rejected, as read_png rejects 16-bit input.
  */
 #include <math.h>
 #include <stdint.h>
@@ -38,26 +40,28 @@ static int paeth(int a, int b, int c)
     return (pb <= pc) ? b : c;
 }
 
-/* want_rgb: rows of 3 * width bytes (R, G, B interleaved; a gray file replicates its value) instead of the gray conversion */
-static int read_png_impl(const char *filename, uint8_t ***row_pointers, int *width, int *height, int want_rgb)
+/* What the chunk walk of a PNG file yields: the IHDR fields, the concatenated IDAT stream (malloc'd) and the gamma chunks. */
+typedef struct png_chunks {
+    uint32_t w, h;
+    int bit_depth, color_type, interlace;
+    uint8_t *zdata;
+    size_t zlen;
+    long file_gamma; /* libpng fixed point (x 100000); 0 = unknown */
+    int have_srgb;
+} png_chunks;
+
+/* Reads the whole file and walks its chunks (CRCs checked, unknown critical chunks rejected). 0 / -1; pc->zdata is the caller's. */
+static int read_png_chunks(FILE *f, png_chunks *pc)
 {
-    if (!filename || !row_pointers || !width || !height) return -1;
-    *row_pointers = NULL;
-    FILE *f = fopen(filename, "rb");
-    if (!f) {
-        fprintf(stderr, "Could not open file %s\n", filename); /* hpc/read_img.c:16 */
-        return -1;
-    }
     int rc = -1;
-    uint8_t *file = NULL, *zdata = NULL, *raw = NULL;
-    uint8_t **rows = NULL;
+    uint8_t *file = NULL, *zdata = NULL;
     long fsize = 0;
     uint32_t w = 0, h = 0;
-    int bit_depth = 0, color_type = -1, interlace = 0, seen_ihdr = 0, seen_iend = 0, channels = 0;
-    size_t zlen = 0, zcap = 0, pos = 8, stride = 0, rawlen = 0;
-    uLongf outlen = 0;
-    long file_gamma = 0; /* libpng fixed point (x 100000); 0 = unknown */
+    int bit_depth = 0, color_type = -1, interlace = 0, seen_ihdr = 0, seen_iend = 0;
+    size_t zlen = 0, zcap = 0, pos = 8;
+    long file_gamma = 0;
     int have_srgb = 0;
+    memset(pc, 0, sizeof(*pc));
     if (fseek(f, 0, SEEK_END) != 0 || (fsize = ftell(f)) < 8 + 25 || fseek(f, 0, SEEK_SET) != 0) goto done;
     file = (uint8_t *)malloc((size_t)fsize);
     if (!file || fread(file, 1, (size_t)fsize, f) != (size_t)fsize) goto done;
@@ -99,6 +103,77 @@ static int read_png_impl(const char *filename, uint8_t ***row_pointers, int *wid
         pos += 12 + (size_t)len;
     }
     if (!seen_ihdr || !seen_iend || w == 0 || h == 0 || w > 65535u || h > 65535u) goto done;
+    pc->w = w;
+    pc->h = h;
+    pc->bit_depth = bit_depth;
+    pc->color_type = color_type;
+    pc->interlace = interlace;
+    pc->zdata = zdata;
+    pc->zlen = zlen;
+    pc->file_gamma = file_gamma;
+    pc->have_srgb = have_srgb;
+    zdata = NULL;
+    rc = 0;
+done:
+    free(zdata);
+    free(file);
+    return rc;
+}
+
+/* Undoes the scanline filters of h rows of `stride` bytes (each after its filter-type byte) in place; bpp = bytes per pixel. */
+static int unfilter_rows(uint8_t *raw, size_t stride, uint32_t h, size_t bpp)
+{
+    for (uint32_t y = 0; y < h; ++y) {
+        uint8_t *cur = raw + (stride + 1) * y + 1;
+        const uint8_t *prev = y ? cur - (stride + 1) : NULL;
+        const int ft = cur[-1];
+        for (size_t x = 0; x < stride; ++x) {
+            const int a = x >= bpp ? cur[x - bpp] : 0;
+            const int b = prev ? prev[x] : 0;
+            const int c = (prev && x >= bpp) ? prev[x - bpp] : 0;
+            int v = cur[x];
+            switch (ft) {
+            case 0: break;
+            case 1: v += a; break;
+            case 2: v += b; break;
+            case 3: v += (a + b) >> 1; break;
+            case 4: v += paeth(a, b, c); break;
+            default: return -1;
+            }
+            cur[x] = (uint8_t)v;
+        }
+    }
+    return 0;
+}
+
+/* want_rgb: rows of 3 * width bytes (R, G, B interleaved; a gray file replicates its value) instead of the gray conversion */
+static int read_png_impl(const char *filename, uint8_t ***row_pointers, int *width, int *height, int want_rgb)
+{
+    if (!filename || !row_pointers || !width || !height) return -1;
+    *row_pointers = NULL;
+    FILE *f = fopen(filename, "rb");
+    if (!f) {
+        fprintf(stderr, "Could not open file %s\n", filename); /* hpc/read_img.c:16 */
+        return -1;
+    }
+    int rc = -1;
+    uint8_t *zdata = NULL, *raw = NULL;
+    uint8_t **rows = NULL;
+    uint32_t w = 0, h = 0;
+    int bit_depth = 0, color_type = -1, interlace = 0, channels = 0;
+    size_t zlen = 0, stride = 0, rawlen = 0;
+    uLongf outlen = 0;
+    long file_gamma = 0; /* libpng fixed point (x 100000); 0 = unknown */
+    png_chunks pc;
+    if (read_png_chunks(f, &pc) != 0) goto done;
+    w = pc.w;
+    h = pc.h;
+    bit_depth = pc.bit_depth;
+    color_type = pc.color_type;
+    interlace = pc.interlace;
+    zdata = pc.zdata;
+    zlen = pc.zlen;
+    file_gamma = pc.file_gamma;
     if (bit_depth != 8 || interlace != 0) goto done;
     switch (color_type) {
     case 0: channels = 1; break; /* gray */
@@ -114,26 +189,7 @@ static int read_png_impl(const char *filename, uint8_t ***row_pointers, int *wid
     if (uncompress(raw, &outlen, zdata, (uLong)zlen) != Z_OK || outlen != rawlen) goto done;
 
     /* undo the scanline filters in place */
-    for (uint32_t y = 0; y < h; ++y) {
-        uint8_t *cur = raw + (stride + 1) * y + 1;
-        const uint8_t *prev = y ? cur - (stride + 1) : NULL;
-        const int ft = cur[-1];
-        for (size_t x = 0; x < stride; ++x) {
-            const int a = x >= (size_t)channels ? cur[x - channels] : 0;
-            const int b = prev ? prev[x] : 0;
-            const int c = (prev && x >= (size_t)channels) ? prev[x - channels] : 0;
-            int v = cur[x];
-            switch (ft) {
-            case 0: break;
-            case 1: v += a; break;
-            case 2: v += b; break;
-            case 3: v += (a + b) >> 1; break;
-            case 4: v += paeth(a, b, c); break;
-            default: goto done;
-            }
-            cur[x] = (uint8_t)v;
-        }
-    }
+    if (unfilter_rows(raw, stride, h, (size_t)channels) != 0) goto done;
 
     /* libpng's 8-bit gamma tables for rgb_to_gray (png_build_8bit_table /
      * png_gamma_8bit_correct): only when the gamma is known and significant */
@@ -181,7 +237,6 @@ done:
     }
     free(raw);
     free(zdata);
-    free(file);
     fclose(f);
     return rc;
 }
@@ -189,6 +244,53 @@ done:
 int glf_read_png(const char *filename, uint8_t ***row_pointers, int *width, int *height)
 {
     return read_png_impl(filename, row_pointers, width, height, 0);
+}
+
+int glf_read_png16(const char *filename, uint16_t ***row_pointers, int *width, int *height)
+{
+    if (!filename || !row_pointers || !width || !height) return -1;
+    *row_pointers = NULL;
+    FILE *f = fopen(filename, "rb");
+    if (!f) {
+        fprintf(stderr, "Could not open file %s\n", filename);
+        return -1;
+    }
+    int rc = -1;
+    uint8_t *raw = NULL;
+    uint16_t **rows = NULL;
+    png_chunks pc;
+    pc.zdata = NULL;
+    pc.h = 0;
+    if (read_png_chunks(f, &pc) != 0) goto done;
+    if (pc.bit_depth != 16 || pc.color_type != 0 || pc.interlace != 0) goto done; /* 16-bit gray only */
+    const size_t stride = 2 * (size_t)pc.w, rawlen = (stride + 1) * (size_t)pc.h;
+    raw = (uint8_t *)malloc(rawlen);
+    if (!raw) goto done;
+    uLongf outlen = (uLongf)rawlen;
+    if (uncompress(raw, &outlen, pc.zdata, (uLong)pc.zlen) != Z_OK || outlen != rawlen) goto done;
+    if (unfilter_rows(raw, stride, pc.h, 2) != 0) goto done;
+    rows = (uint16_t **)calloc(pc.h, sizeof(uint16_t *));
+    if (!rows) goto done;
+    for (uint32_t y = 0; y < pc.h; ++y) {
+        rows[y] = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)pc.w);
+        if (!rows[y]) goto done;
+        const uint8_t *src = raw + (stride + 1) * y + 1;
+        for (uint32_t x = 0; x < pc.w; ++x) rows[y][x] = (uint16_t)(((unsigned)src[2 * x] << 8) | src[2 * x + 1]);
+    }
+    *row_pointers = rows;
+    *width = (int)pc.w;
+    *height = (int)pc.h;
+    rows = NULL;
+    rc = 0;
+done:
+    if (rows) {
+        for (uint32_t y = 0; y < pc.h; ++y) free(rows[y]);
+        free(rows);
+    }
+    free(raw);
+    free(pc.zdata);
+    fclose(f);
+    return rc;
 }
 
 int glf_read_png_rgb(const char *filename, uint8_t ***row_pointers, int *width, int *height)
@@ -210,43 +312,56 @@ static int write_chunk(FILE *f, const char *type, const uint8_t *data, uint32_t 
     return 0;
 }
 
-static int write_png_impl(const char *filename, uint8_t **img_bytes, unsigned width, unsigned height, int rgb);
+/* kind 0: 8-bit gray, 1: 8-bit RGB (rows of bytes); 2: 16-bit gray (rows of uint16_t, written big-endian) */
+static int write_png_impl(const char *filename, void *const *rows, unsigned width, unsigned height, int kind);
 
 int glf_write_png(const char *filename, uint8_t **img_bytes, unsigned width, unsigned height)
 {
-    return write_png_impl(filename, img_bytes, width, height, 0);
+    return write_png_impl(filename, (void *const *)img_bytes, width, height, 0);
 }
 
 int glf_write_png_rgb(const char *filename, uint8_t **img_bytes, unsigned width, unsigned height)
 {
-    return write_png_impl(filename, img_bytes, width, height, 1);
+    return write_png_impl(filename, (void *const *)img_bytes, width, height, 1);
 }
 
-static int write_png_impl(const char *filename, uint8_t **img_bytes, unsigned width, unsigned height, int rgb)
+int glf_write_png16(const char *filename, uint16_t **rows, unsigned width, unsigned height)
 {
-    if (!filename || !img_bytes || width == 0 || height == 0) return -1;
+    return write_png_impl(filename, (void *const *)rows, width, height, 2);
+}
+
+static int write_png_impl(const char *filename, void *const *rows, unsigned width, unsigned height, int kind)
+{
+    if (!filename || !rows || width == 0 || height == 0) return -1;
     FILE *f = fopen(filename, "wb");
     if (!f) {
         fprintf(stderr, "Could not open file %s\n", filename); /* hpc/write_img.c:10 */
         return -1;
     }
     int rc = -1;
-    const size_t rowbytes = (size_t)width * (rgb ? 3 : 1);
+    const size_t rowbytes = (size_t)width * (kind == 1 ? 3 : kind == 2 ? 2 : 1);
     const size_t rawlen = (rowbytes + 1) * height;
     uint8_t *raw = (uint8_t *)malloc(rawlen), *z = NULL;
     uLongf zlen = compressBound((uLong)rawlen);
     uint8_t ihdr[13];
     if (!raw) goto done;
     for (unsigned y = 0; y < height; ++y) {
-        raw[(rowbytes + 1) * y] = 0; /* filter type None */
-        memcpy(raw + (rowbytes + 1) * y + 1, img_bytes[y], rowbytes);
+        uint8_t *dst = raw + (rowbytes + 1) * y;
+        dst[0] = 0; /* filter type None */
+        if (kind == 2) {
+            const uint16_t *src = (const uint16_t *)rows[y];
+            for (unsigned x = 0; x < width; ++x) {
+                dst[1 + 2 * x] = (uint8_t)(src[x] >> 8);
+                dst[2 + 2 * x] = (uint8_t)src[x];
+            }
+        } else memcpy(dst + 1, rows[y], rowbytes);
     }
     z = (uint8_t *)malloc(zlen);
     if (!z || compress2(z, &zlen, raw, (uLong)rawlen, 6) != Z_OK) goto done;
     put_be32(ihdr, width);
     put_be32(ihdr + 4, height);
-    ihdr[8] = 8;  /* bit depth,  hpc/write_img.c:39 */
-    ihdr[9] = rgb ? 2 : 0; /* PNG_COLOR_TYPE_GRAY, :38 (2 = RGB for the colour path) */
+    ihdr[8] = kind == 2 ? 16 : 8;  /* bit depth,  hpc/write_img.c:39 (16 for the 16-bit gray path) */
+    ihdr[9] = kind == 1 ? 2 : 0; /* PNG_COLOR_TYPE_GRAY, :38 (2 = RGB for the colour path) */
     ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0; /* base compression/filter, no interlace, :42-44 */
     if (fwrite(PNG_SIG, 1, 8, f) != 8) goto done;
     if (write_chunk(f, "IHDR", ihdr, 13) != 0) goto done;

@@ -164,7 +164,14 @@ enum { GLF_ROWS_NA = 0, GLF_ROWS_SAMPLE_FIRST = 1, GLF_ROWS_RASTER = 2 };
  * KERNEL_B descriptor) read d_img as interleaved uint8 [height][width][3], the layout of glf_read_png_rgb. h_loc and h_val keep
  * their per-channel meaning: a grey image replicated into three channels gives the grey graph at h_val * sqrt(3). It has no
  * grid-factored, rank or band form: the entry-by-entry kernels run (f32 MFMA contraction whatever glf_ctx_set_contraction says). */
-enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3, GLF_KERNEL_BILATERAL_RGB = 4 };
+/* BILATERAL_U16: the bilateral kernel on 16-bit grey values, K = exp(-(dr^2 + dc^2) / h_loc^2) exp(-(v_i - v_j)^2 / h_val^2) with
+ * v in 0..65535. With it the stage entry points (glf_ComputeAffinityMatrices and every consumer of its KERNEL_B descriptor) read
+ * d_img as uint16_t [height][width] (glf_mat.img stays a byte pointer: the kernel id says how it is read). h_val is in the units
+ * of the image's values on every entry point: an image 257 g (g an 8-bit image) at h_val * 257 has the graph of g at h_val. Like
+ * the colour kernel it has no grid-factored, rank or band form (those factor over 256 grey levels): the entry-by-entry kernels run
+ * with the f32 MFMA contraction whatever glf_ctx_set_contraction says. */
+enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3, GLF_KERNEL_BILATERAL_RGB = 4,
+       GLF_KERNEL_BILATERAL_U16 = 5 };
 
 /* Replaces PETSc Mat (MATMPIDENSE / MATMPIAIJ diagonal). */
 typedef struct glf_mat {
@@ -416,6 +423,17 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
 int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                              float *d_zf, double *eigvals_out, glf_stats *stats);
 
+/* 16-bit greyscale filtering: the graph is built from the 16-bit values (GLF_KERNEL_BILATERAL_U16; opt->kernel must be
+ * GLF_KERNEL_BILATERAL or GLF_KERNEL_BILATERAL_U16, both mean the 16-bit kernel here, any other gives GLF_ERR_UNSUPPORTED; opt->h_val
+ * is in 16-bit units) on the sampler of opt->sampling, and the image x goes through its filter in the mode of opt->filter_mode:
+ * z = (1 - ysub) x + gain Phi f(Pi) Phi^T x, d_out = clamp(x + floor(z - x), 0, 65535) (glf_image_processing's rule at 16 bits).
+ * d_img / d_out: device uint16_t [height][width], d_img replicated on every rank; with a comm rank g writes its own pixel rows only.
+ * d_zf optional: device float [height*width], z before the clamp. eigvals_out: HOST double[m] or NULL. More than 256 eigenpairs:
+ * GLF_ERR_UNSUPPORTED. As for colour the entry-by-entry kernels run and L_A is stored (stats.nystroem_path = matvec_path = 0,
+ * filter_fused = 0). */
+int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
+                             float *d_zf, double *eigvals_out, glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -438,6 +456,10 @@ int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt, const uin
  * written (there is one c = Phi^T x_c and one correction per channel: the float z gives them). */
 int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height,
                                      uint8_t *d_out_rgb, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap);
+/* The same by-products of one glf_image_processing_u16 call: d_phi_A, d_phi and h_degree; h_c and d_corr are not written (the
+ * float z gives the correction). */
+int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height,
+                                     uint16_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
@@ -468,6 +490,11 @@ int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, con
 int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height,
                                    uint8_t *h_out_rgb, float *h_zf, double *eigvals_out, glf_stats *stats);
 
+/* glf_multi_image_processing for 16-bit grey (glf_image_processing_u16): h_img / h_out HOST uint16_t [height][width]; each rank's
+ * pixel rows are gathered into h_out (h_zf optional HOST float [height*width]). */
+int glf_multi_image_processing_u16(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height,
+                                   uint16_t *h_out, float *h_zf, double *eigvals_out, glf_stats *stats);
+
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
  * (hpc/affinity.c:264-336, hpc/laplacian.c:44-65, hpc/display.c:128-149). The matrices are never stored
@@ -487,6 +514,11 @@ int glf_write_png(const char *filename, uint8_t **img_bytes, unsigned width, uns
  * converts to gray on read): the same codec with rows of 3 * width bytes, R G B interleaved. */
 int glf_read_png_rgb(const char *filename, uint8_t ***row_pointers, int *width, int *height);
 int glf_write_png_rgb(const char *filename, uint8_t **img_bytes, unsigned width, unsigned height);
+/* 16-bit greyscale (colour type 0, bit depth 16, non-interlaced): rows of `width` uint16_t values (host byte order; the file holds
+ * them big-endian). glf_read_png16 rejects every other format (8-bit, RGB(A), palette, grey+alpha, interlaced) with -1, as
+ * glf_read_png rejects 16-bit input. */
+int glf_read_png16(const char *filename, uint16_t ***row_pointers, int *width, int *height);
+int glf_write_png16(const char *filename, uint16_t **rows, unsigned width, unsigned height);
 
 #ifdef __cplusplus
 }
