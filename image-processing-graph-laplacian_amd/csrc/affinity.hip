@@ -15,6 +15,7 @@ namespace glf {
 
 // ---- sample tables ------------------------------------------------------------------
 
+template <PixGen G>
 __global__ void k_sample_tables(const uint8_t *__restrict__ img, int width, int64_t N, unsigned p,
                                 const uint32_t *__restrict__ idx, float4 *__restrict__ samples,
                                 uint8_t *__restrict__ mask)
@@ -24,32 +25,7 @@ __global__ void k_sample_tables(const uint8_t *__restrict__ img, int width, int6
     const uint32_t px = idx[i];
     if ((int64_t)px >= N) return; // validated on the host as well
     // num2x / num2y, hpc/utils.c:11-19: x = row, y = column
-    samples[i] = make_float4((float)(px / (uint32_t)width), (float)(px % (uint32_t)width), (float)img[px], 0.f);
-    mask[px] = 1;
-}
-
-__global__ void k_sample_tables_rgb(const uint8_t *__restrict__ rgb, int width, int64_t N, unsigned p, const uint32_t *__restrict__ idx,
-                                    float4 *__restrict__ samples, uint8_t *__restrict__ mask)
-{
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p) return;
-    const uint32_t px = idx[i];
-    if ((int64_t)px >= N) return;
-    const uint8_t *c = rgb + (size_t)px * 3;
-    samples[i] = make_float4((float)(px / (uint32_t)width), (float)(px % (uint32_t)width), 0.f,
-                             (float)((unsigned)c[0] | ((unsigned)c[1] << 8) | ((unsigned)c[2] << 16)));
-    mask[px] = 1;
-}
-
-// 16-bit grey: the grey record {row, col, v, 0} with v in 0..65535 (exact in f32)
-__global__ void k_sample_tables_u16(const uint16_t *__restrict__ img, int width, int64_t N, unsigned p, const uint32_t *__restrict__ idx,
-                                    float4 *__restrict__ samples, uint8_t *__restrict__ mask)
-{
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p) return;
-    const uint32_t px = idx[i];
-    if ((int64_t)px >= N) return;
-    samples[i] = make_float4((float)(px / (uint32_t)width), (float)(px % (uint32_t)width), (float)img[px], 0.f);
+    samples[i] = Pix<G>::record(reinterpret_cast<const typename Pix<G>::In *>(img), px, (uint32_t)width);
     mask[px] = 1;
 }
 
@@ -69,15 +45,12 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     GLF_TRY(out.idx.alloc(ctx, p));
     GLF_HIP(ctx, hipMemcpyAsync(out.idx.p, h_idx, sizeof(uint32_t) * p, hipMemcpyHostToDevice, ctx->stream));
     GLF_HIP(ctx, hipMemsetAsync(out.mask.p, 0, (size_t)N, ctx->stream));
-    if (kernel == GLF_KERNEL_BILATERAL_RGB)
-        hipLaunchKernelGGL(k_sample_tables_rgb, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p,
-                           out.mask.p);
-    else if (kernel == GLF_KERNEL_BILATERAL_U16)
-        hipLaunchKernelGGL(k_sample_tables_u16, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const uint16_t *>(d_img), width,
-                           N, p, out.idx.p, out.samples.p, out.mask.p);
-    else
-        hipLaunchKernelGGL(k_sample_tables, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_img, width, N, p,
-                           out.idx.p, out.samples.p, out.mask.p);
+    const dim3 grid((p + 255) / 256);
+    switch (pixgen_of(kernel)) {
+    case PixGen::Grey: hipLaunchKernelGGL(k_sample_tables<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
+    case PixGen::Rgb: hipLaunchKernelGGL(k_sample_tables<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
+    case PixGen::U16: hipLaunchKernelGGL(k_sample_tables<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
+    }
     GLF_LAUNCH_CHECK(ctx);
     // h_idx is pageable host memory: make sure the async copy has consumed it
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -417,8 +390,7 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 int weighted_sums_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
                        const unsigned *h_idx, KernelCoef coef, int window, const float *d_plane, double wabs, double *d_out)
 {
-    if (coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB || coef.kernel == GLF_KERNEL_BILATERAL_U16)
-        return GLF_ERR_UNSUPPORTED;
+    if (!grey_levels_factor(coef.kernel)) return GLF_ERR_UNSUPPORTED;
     return degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_out, window, nullptr, nullptr, d_plane, wabs);
 }
 
@@ -434,10 +406,9 @@ int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, 
         if (evaluated) *evaluated = (double)p * (double)(row1 - row0) * (double)width;
         return nlm_degree_rows(ctx, d_img, width, height, row0, row1, d_idx, p, coef, d_degree);
     }
-    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) // no factored form over 2^24 colours: its own windowed sweep (rgb.hip)
-        return rgb_degree_rows(ctx, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
-    if (coef.kernel == GLF_KERNEL_BILATERAL_U16) // no factored form over 65 536 levels, no 256-entry table: its own windowed sweep (u16.hip)
-        return u16_degree_rows(ctx, reinterpret_cast<const uint16_t *>(d_img), width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
+    const PixGen gen = pixgen_of(coef.kernel);
+    if (gen != PixGen::Grey) // no factored form over 2^24 colours or 65 536 levels, no 256-entry table: the windowed sweep (entrywise.hip)
+        return degree_rows_entrywise(ctx, gen, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
     const int rc = degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_degree, window, evaluated, d_ysum);
     if (rc != GLF_ERR_UNSUPPORTED) {
         if (have_ysum) *have_ysum = rc == GLF_OK && d_ysum != nullptr; // (only the grid-factored degree has the value-weighted sums)
@@ -535,6 +506,8 @@ int entire_computation(glf_ctx *ctx, const uint8_t *d_img, int width, int height
 // L_A = alpha * (diag(D) - K_A)  => off-diagonal -alpha*K, diagonal alpha*(D_i - K_ii).
 // Write-bound: 4 p^2 bytes (29 GB at p = 85 264).
 
+// G: the format of the sample records (the photometric distance); U16 takes the Grey instantiation: the same records, no level table
+template <PixGen G>
 __global__ __launch_bounds__(256) void k_sample_matrix(const float4 *__restrict__ samples, unsigned p, float s_loc,
                                                         float s_val, float *__restrict__ out, int64_t ld,
                                                         int laplacian, double alpha,
@@ -550,16 +523,21 @@ __global__ __launch_bounds__(256) void k_sample_matrix(const float4 *__restrict_
     }
     const unsigned j = col0 + jl;
     const float4 sj = samples[j];
+    const typename Pix<G>::Val vj = Pix<G>::value(sj);
     const float fscale = laplacian ? (float)(-alpha) : 1.0f;
-#pragma unroll 4
-    for (unsigned ii = 0; ii < 16; ++ii) {
-        const unsigned i = i0 + ii;
-        if (i >= p) break;
+    auto entry = [&](unsigned i) {
         const float4 si = samples[i]; // wave-uniform -> scalar load
-        float k = kernel_eval(si.x - sj.x, si.y - sj.y, si.z - sj.z, s_loc, s_val);
+        const float dr = si.x - sj.x, dc = si.y - sj.y;
+        const float k = __builtin_amdgcn_exp2f(-fmaf(Pix<G>::dist2(Pix<G>::value(si), vj), s_val, fmaf(dc, dc, dr * dr) * s_loc));
         float v = fscale * k;
         if (laplacian && i == j) v = (float)(alpha * (degree[i] - (double)k));
         out[(size_t)i * ld + jl] = v;
+    };
+    if constexpr (G == PixGen::Grey) {
+#pragma unroll 4
+        for (unsigned ii = 0; ii < 16 && i0 + ii < p; ++ii) entry(i0 + ii);
+    } else { // (the compiler's own unrolling: the colour distance makes the body three times longer)
+        for (unsigned ii = 0; ii < 16 && i0 + ii < p; ++ii) entry(i0 + ii);
     }
 }
 
@@ -571,16 +549,18 @@ int build_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, Kerne
         if (!d_img || !d_idx) return set_error(ctx, GLF_ERR_INVALID, "NLM sample matrix needs the image and the device sample indices");
         return nlm_sample_matrix(ctx, d_img, width, height, d_idx, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
     }
-    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB) return rgb_sample_matrix(ctx, d_samples, p, coef, d_out, ld, laplacian, alpha, d_degree, col0, ncols);
-    // (GLF_KERNEL_BILATERAL_U16 takes k_sample_matrix as it is: it reads the values from the grey records, with no level table)
     if (ncols == 0) {
         col0 = 0;
         ncols = p;
     }
     if (col0 + ncols > p) return set_error(ctx, GLF_ERR_INVALID, "build_sample_matrix: column range");
     dim3 grid((unsigned)((ld + 63) / 64), (p + 63) / 64); // covers the padding columns too
-    hipLaunchKernelGGL(k_sample_matrix, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
-                       ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
+    if (pixgen_of(coef.kernel) == PixGen::Rgb)
+        hipLaunchKernelGGL(k_sample_matrix<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
+                           ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
+    else
+        hipLaunchKernelGGL(k_sample_matrix<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
+                           ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

@@ -323,8 +323,7 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
                             const float4 *d_samples, unsigned p, const unsigned *h_idx, KernelCoef coef, double *d_degree,
                             int window, double *evaluated, double *d_ysum, const float *d_wplane = nullptr, double wabs = 1.0)
 {
-    if (!grid_path_wanted(ctx->tune.deg_path, width) || width > GRID_MAX_W || p < 4 || row0 >= row1 || coef.kernel == GLF_KERNEL_NLM ||
-        coef.kernel == GLF_KERNEL_BILATERAL_RGB || coef.kernel == GLF_KERNEL_BILATERAL_U16)
+    if (!grid_path_wanted(ctx->tune.deg_path, width) || width > GRID_MAX_W || p < 4 || row0 >= row1 || !grey_levels_factor(coef.kernel))
         return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> idx(h_idx, h_idx + p);
     GridInfo g;

@@ -240,10 +240,9 @@ struct glf_multi {
     std::unique_ptr<Loopback> loop;
     // per-rank device buffers of glf_multi_image_processing, kept between calls (one image size at a time)
     struct Buffers {
-        uint8_t *d_img = nullptr, *d_out = nullptr;
-        float *d_zf = nullptr;
-        size_t npix = 0;
-        bool has_zf = false;
+        uint8_t *d_img = nullptr, *d_out = nullptr; // [bytes] each
+        float *d_zf = nullptr;                      // [zf_floats]
+        size_t bytes = 0, zf_floats = 0;
     };
     std::vector<Buffers> buf;
     bool broken = false; // RCCL backend: a rank failed and the communicators were aborted -- the world cannot be used again
@@ -395,16 +394,15 @@ const char *glf_multi_last_error(const glf_multi *w) { return w ? w->last_error 
 // One rank thread per GPU: replicate the image (hpc/image_processing.c:45-76 broadcasts it to every rank), run the sharded
 // path, copy this rank's pixel rows of the result back (hpc/utils.c:502-527 gathers to rank 0).
 // nsig > 0: signal planes h_sig [nsig][N] replicated on every rank, each rank's pixel rows of the results into h_sig_out
-// guide: the 8-bit grey image (glf_image_processing / _signals), the colour image (glf_image_processing_rgb: [N][3] bytes in and
-// out, [3][N] floats) or the 16-bit image (glf_image_processing_u16: [N] uint16_t in and out, [N] floats)
-enum class MultiGuide { U8, Rgb, U16 };
-static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out, float *h_zf,
-                     double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out, MultiGuide guide = MultiGuide::U8);
+// gen: the guide's pixel format (glf_image_processing / _signals, _rgb, _u16): h_img and h_out are [N] pixels of it, h_zf the
+// format's [NCH][N] floats
+static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
+                     float *h_zf, double *eigvals_out, glf_stats *stats, int nsig = 0, const float *h_sig = nullptr, float *h_sig_out = nullptr);
 
 int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out,
                                float *h_zf, double *eigvals_out, glf_stats *stats)
 {
-    return multi_run(w, opt, h_img, width, height, h_out, h_zf, eigvals_out, stats, 0, nullptr, nullptr);
+    return multi_run(w, opt, PixGen::Grey, h_img, width, height, h_out, h_zf, eigvals_out, stats);
 }
 
 int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, int nsig,
@@ -412,28 +410,27 @@ int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, con
                                        glf_stats *stats)
 {
     if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run(w, opt, h_img, width, height, h_out, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
+    return multi_run(w, opt, PixGen::Grey, h_img, width, height, h_out, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
 }
 
 int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height, uint8_t *h_out_rgb,
                                    float *h_zf, double *eigvals_out, glf_stats *stats)
 {
-    return multi_run(w, opt, h_rgb, width, height, h_out_rgb, h_zf, eigvals_out, stats, 0, nullptr, nullptr, MultiGuide::Rgb);
+    return multi_run(w, opt, PixGen::Rgb, h_rgb, width, height, h_out_rgb, h_zf, eigvals_out, stats);
 }
 
 int glf_multi_image_processing_u16(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height, uint16_t *h_out,
                                    float *h_zf, double *eigvals_out, glf_stats *stats)
 {
-    return multi_run(w, opt, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), h_zf, eigvals_out,
-                     stats, 0, nullptr, nullptr, MultiGuide::U16);
+    return multi_run(w, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), h_zf,
+                     eigvals_out, stats);
 }
 
-static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out, float *h_zf,
-                     double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out, MultiGuide guide)
+static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
+                     float *h_zf, double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out)
 {
-    const bool u8 = guide == MultiGuide::U8; // (the colour and 16-bit guides take their own buffers, from the context's pool)
-    const size_t pxb = guide == MultiGuide::Rgb ? 3 : guide == MultiGuide::U16 ? 2 : 1; // bytes per pixel in and out
-    const int nzf = guide == MultiGuide::Rgb ? 3 : 1;                                  // float z planes
+    const size_t pxb = pix_bytes(gen); // bytes per pixel in and out
+    const int nzf = pix_channels(gen); // float z planes
     if (!w || !h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     if (w->broken) {
         std::snprintf(w->last_error, sizeof(w->last_error), "the communicators of this world were aborted after a rank failed; create a new one");
@@ -450,47 +447,21 @@ static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img,
             if (e != hipSuccess && rc == GLF_OK) rc = set_error(ctx, GLF_ERR_HIP, "glf_multi rank %d: %s", r, hipGetErrorString(e));
         };
         step(hipSetDevice(ctx->device));
-        if (!u8) { // colour: [N][3] bytes in and out, [3][N] floats; 16-bit: [N] uint16_t in and out, [N] floats (from the context's pool,
-                   // not kept between calls)
-            DevBuf<uint8_t> img3, out3;
-            DevBuf<float> zf3;
-            glf_stats st{};
-            if (rc == GLF_OK) rc = img3.alloc(ctx, pxb * N);
-            if (rc == GLF_OK) rc = out3.alloc(ctx, pxb * N);
-            if (rc == GLF_OK && h_zf) rc = zf3.alloc(ctx, nzf * N);
-            if (rc == GLF_OK) {
-                step(hipMemcpyAsync(img3.p, h_img, pxb * N, hipMemcpyHostToDevice, ctx->stream));
-                step(hipStreamSynchronize(ctx->stream));
-            }
-            if (rc == GLF_OK)
-                rc = guide == MultiGuide::Rgb
-                         ? glf_image_processing_rgb(ctx, opt, img3.p, width, height, out3.p, h_zf ? zf3.p : nullptr, r == 0 ? eigvals_out : nullptr, &st)
-                         : glf_image_processing_u16(ctx, opt, reinterpret_cast<const uint16_t *>(img3.p), width, height,
-                                                    reinterpret_cast<uint16_t *>(out3.p), h_zf ? zf3.p : nullptr, r == 0 ? eigvals_out : nullptr, &st);
-            if (rc == GLF_OK) {
-                const size_t o = (size_t)st.row0 * width, len = (size_t)(st.row1 - st.row0) * width;
-                if (len) step(hipMemcpyAsync(h_out + pxb * o, out3.p + pxb * o, pxb * len, hipMemcpyDeviceToHost, ctx->stream));
-                for (int k = 0; k < nzf && len && h_zf; ++k)
-                    step(hipMemcpyAsync(h_zf + k * N + o, zf3.p + k * N + o, len * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-                step(hipStreamSynchronize(ctx->stream));
-                if (stats) stats[r] = st;
-            }
-        }
-        if (u8 && rc == GLF_OK && (b.npix != N || (h_zf && !b.has_zf))) {
+        if (rc == GLF_OK && (b.bytes != pxb * N || (h_zf && b.zf_floats < nzf * N))) {
             if (b.d_img) (void)hipFree(b.d_img);
             if (b.d_out) (void)hipFree(b.d_out);
             if (b.d_zf) (void)hipFree(b.d_zf);
             b = glf_multi::Buffers{};
-            step(hipMalloc(reinterpret_cast<void **>(&b.d_img), N));
-            step(hipMalloc(reinterpret_cast<void **>(&b.d_out), N));
-            if (h_zf) step(hipMalloc(reinterpret_cast<void **>(&b.d_zf), N * sizeof(float)));
+            step(hipMalloc(reinterpret_cast<void **>(&b.d_img), pxb * N));
+            step(hipMalloc(reinterpret_cast<void **>(&b.d_out), pxb * N));
+            if (h_zf) step(hipMalloc(reinterpret_cast<void **>(&b.d_zf), nzf * N * sizeof(float)));
             if (rc == GLF_OK) {
-                b.npix = N;
-                b.has_zf = h_zf != nullptr;
+                b.bytes = pxb * N;
+                b.zf_floats = h_zf ? nzf * N : 0;
             }
         }
-        if (u8 && rc == GLF_OK) {
-            step(hipMemcpyAsync(b.d_img, h_img, N, hipMemcpyHostToDevice, ctx->stream));
+        if (rc == GLF_OK) {
+            step(hipMemcpyAsync(b.d_img, h_img, pxb * N, hipMemcpyHostToDevice, ctx->stream));
             step(hipStreamSynchronize(ctx->stream));
         }
         glf_stats st{};
@@ -504,15 +475,21 @@ static int multi_run(glf_multi *w, const glf_options *opt, const uint8_t *h_img,
             if (rc == GLF_OK) step(hipMemcpyAsync(d_sig, h_sig, (size_t)nsig * N * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             step(hipStreamSynchronize(ctx->stream));
         }
-        if (u8 && rc == GLF_OK)
-            rc = nsig > 0 ? glf_image_processing_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out,
-                                                         h_zf ? b.d_zf : nullptr, r == 0 ? eigvals_out : nullptr, &st)
-                          : glf_image_processing(ctx, opt, b.d_img, width, height, b.d_out, h_zf ? b.d_zf : nullptr,
-                                                 r == 0 ? eigvals_out : nullptr, &st);
-        if (u8 && rc == GLF_OK) {
+        if (rc == GLF_OK) {
+            float *zf = h_zf ? b.d_zf : nullptr;
+            double *ev = r == 0 ? eigvals_out : nullptr;
+            if (gen == PixGen::Rgb) rc = glf_image_processing_rgb(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
+            else if (gen == PixGen::U16)
+                rc = glf_image_processing_u16(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height,
+                                              reinterpret_cast<uint16_t *>(b.d_out), zf, ev, &st);
+            else if (nsig > 0) rc = glf_image_processing_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out, zf, ev, &st);
+            else rc = glf_image_processing(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
+        }
+        if (rc == GLF_OK) {
             const size_t o = (size_t)st.row0 * width, len = (size_t)(st.row1 - st.row0) * width;
-            if (len) step(hipMemcpyAsync(h_out + o, b.d_out + o, len, hipMemcpyDeviceToHost, ctx->stream));
-            if (len && h_zf) step(hipMemcpyAsync(h_zf + o, b.d_zf + o, len * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            if (len) step(hipMemcpyAsync(h_out + pxb * o, b.d_out + pxb * o, pxb * len, hipMemcpyDeviceToHost, ctx->stream));
+            for (int k = 0; k < nzf && len && h_zf; ++k)
+                step(hipMemcpyAsync(h_zf + k * N + o, b.d_zf + k * N + o, len * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
             for (int k = 0; k < nsig && len; ++k)
                 step(hipMemcpyAsync(h_sig_out + (size_t)k * N + o, d_sig_out + (size_t)k * N + o, len * sizeof(float), hipMemcpyDeviceToHost,
                                     ctx->stream));

@@ -1,0 +1,224 @@
+// entrywise.hip -- the pixel formats without a factored form behind the same stage API as the grey kernels: the colour bilateral
+// affinity (glf_options.kernel = GLF_KERNEL_BILATERAL_RGB, image interleaved uint8 [height][width][3]) and the bilateral affinity
+// on 16-bit grey values (GLF_KERNEL_BILATERAL_U16, image uint16_t [height][width]):
+//
+//   K(i, j) = Es(dr) Es(dc) P(v_i - v_j) = exp2(-(s_loc (dr^2 + dc^2) + s_val |v_i - v_j|^2))
+//
+// with v the pixel's colour or 16-bit value, read and compared through the format's policy Pix<G> (glf_internal.hpp). The
+// photometric factor is at most 1, so every spatial bound of the grey kernels (the f32 underflow radius, the chunk boxes of the
+// Nystroem window) holds unchanged. A colour guide has 2^24 values and a 16-bit guide 65 536, so the forms that factor the sums over
+// the 256 grey levels (grid, rank, band) and the grey direct degree (a 256-entry table per sample) do not extend: those routes
+// decline the kernel and the entry-by-entry kernels run --
+//   k_degree_entrywise<G>               D[i] = sum over the rank's pixel rows of K(sample i, pixel)   lane = sample, pixel tiles in LDS
+//   k_sample_matrix<G> (affinity.hip)   K_A / L_A from the sample records (U16 takes the grey instantiation: the same records)
+//   k_nystroem<.., G> (nystroem.hip)    Phi = K_B^T Psi, f32 MFMA with the format's pixel read
+//   k_apply_filter_pix<LD, G>           the outputs and z, dot products in f64
+//
+// Arithmetic at 16 bits. dv = v_i - v_j is exact in f32 (|dv| < 2^16), dv^2 is not (up to 32 bits): it is rounded once (relative
+// error <= 2^-24), and so is the exponent t = s_val dv^2 + s_loc q (q = dr^2 + dc^2 exact) in its fma, so t carries a relative error
+// of at most ~2^-23 -- the same order as the f32 rounding of s_val itself, which the 8-bit kernels have too. exp2(-t) then moves by
+// |dK| <= K t ln2 2^-23 <= (1/e) 2^-23 ~ 4.4e-8 absolute (the maximum of x e^-x at x = 1), and v_exp_f32 adds its own ~1 ulp: every
+// entry of K_A and K_B is within ~1e-7 of the fp64 kernel, well inside 1e-6 of max|K| = 1. The colour distance is exact (integers
+// below 2^18).
+#include "glf_internal.hpp"
+
+#include <cmath>
+
+namespace glf {
+
+// ---- degree -------------------------------------------------------------------------------------------------------------
+// A workgroup of 256 consecutive samples (ascending raster order: a band of sample rows) sweeps a chunk of EW_ROWS image rows in
+// tiles of EW_ROWS x EW_COLS pixels staged in LDS as the format's {value, col} and read back as wave-wide broadcasts. Chunks beyond
+// the f32 underflow radius of the block's sample rows, tiles beyond it from the block's sample columns (not even loaded) and from a
+// wave's sample columns hold only entries that are exactly 0 (t > 150) and are not visited. Accumulation: f32 over one tile row,
+// f64 across rows, chunks and the final reduction, in a fixed order. *evaluated += the (sample, pixel) entries the waves computed.
+constexpr int EW_ROWS = 16, EW_COLS = 64;
+
+template <PixGen G>
+__global__ __launch_bounds__(256) void k_degree_entrywise(const uint8_t *__restrict__ img_bytes, int width, int row0, int row1,
+                                                           const float4 *__restrict__ samples, unsigned p, float s_loc, float s_val,
+                                                           int radius, double *__restrict__ partial, unsigned long long *__restrict__ evaluated)
+{
+    using P = Pix<G>;
+    const typename P::In *img = reinterpret_cast<const typename P::In *>(img_bytes);
+    __shared__ typename P::Tile tile[EW_ROWS * EW_COLS];
+    __shared__ int wcols[2][4];
+    const unsigned b0 = blockIdx.x * 256, i = b0 + threadIdx.x;
+    const bool live = i < p;
+    const float4 s = samples[live ? i : p - 1];
+    const typename P::Val sv = P::value(s);
+    const int r_begin = row0 + (int)blockIdx.y * EW_ROWS, r_end = min(r_begin + EW_ROWS, row1);
+    // rows of the block's samples: the first and last sample (ascending indices)
+    const int brmin = (int)samples[b0].x, brmax = (int)samples[min(b0 + 255u, p - 1)].x;
+    double total = 0.0;
+    if (r_end > brmin - radius && r_begin <= brmax + radius) { // workgroup-uniform
+        // columns of the wave's samples
+        int wcmin = (int)s.y, wcmax = (int)s.y;
+        for (int o = 32; o; o >>= 1) {
+            wcmin = min(wcmin, __shfl_xor(wcmin, o, 64));
+            wcmax = max(wcmax, __shfl_xor(wcmax, o, 64));
+        }
+        // columns of the block's samples: tiles out of their reach are not loaded at all
+        if ((threadIdx.x & 63) == 0) {
+            wcols[0][threadIdx.x >> 6] = wcmin;
+            wcols[1][threadIdx.x >> 6] = wcmax;
+        }
+        __syncthreads();
+        const int bcmin = min(min(wcols[0][0], wcols[0][1]), min(wcols[0][2], wcols[0][3]));
+        const int bcmax = max(max(wcols[1][0], wcols[1][1]), max(wcols[1][2], wcols[1][3]));
+        const int live_lanes = __popcll(__ballot(live));
+        unsigned long long wave_entries = 0;
+        for (int c0 = max(0, bcmin - radius) / EW_COLS * EW_COLS; c0 < width && c0 <= bcmax + radius; c0 += EW_COLS) {
+            __syncthreads();
+            for (int e = threadIdx.x; e < EW_ROWS * EW_COLS; e += 256) {
+                const int rr = e / EW_COLS, cc = e % EW_COLS, r = r_begin + rr, c = c0 + cc;
+                typename P::Tile v = P::outside();
+                if (r < r_end && c < width) v = P::tile(img, (size_t)r * width + c, c);
+                tile[e] = v;
+            }
+            __syncthreads();
+            if (c0 + EW_COLS <= wcmin - radius || c0 > wcmax + radius) continue; // wave-uniform: only exact zeros here
+            wave_entries += (unsigned long long)live_lanes * (unsigned long long)((r_end - r_begin) * min(EW_COLS, width - c0));
+            for (int rr = 0; rr < r_end - r_begin; ++rr) {
+                const float dr = s.x - (float)(r_begin + rr);
+                const float qr = dr * dr;
+                float acc = 0.f;
+                const typename P::Tile *trow = tile + rr * EW_COLS;
+#pragma unroll 8
+                for (int cc = 0; cc < EW_COLS; ++cc) {
+                    const typename P::Tile v = trow[cc];
+                    const float dc = s.y - P::tile_col(v);
+                    const float u = P::dist2(sv, P::tile_value(v));
+                    acc += __builtin_amdgcn_exp2f(-fmaf(u, s_val, fmaf(dc, dc, qr) * s_loc));
+                }
+                total += (double)acc;
+            }
+        }
+        if ((threadIdx.x & 63) == 0 && wave_entries) atomicAdd(evaluated, wave_entries);
+    }
+    if (live) partial[(size_t)blockIdx.y * p + i] = total;
+}
+
+int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height, int row0, int row1,
+                          const float4 *d_samples, unsigned p, KernelCoef coef, double *d_degree, double *evaluated)
+{
+    if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "degree_rows_entrywise: the 8-bit grey format has kernels of its own");
+    if (row0 < 0 || row1 > height || row0 > row1) return set_error(ctx, GLF_ERR_INVALID, "bad row range");
+    if (evaluated) *evaluated = 0.0;
+    if (row0 == row1) {
+        GLF_HIP(ctx, hipMemsetAsync(d_degree, 0, sizeof(double) * p, ctx->stream));
+        return GLF_OK;
+    }
+    // t > 150 => exp2(-t) == 0 in f32 (the photometric term only adds to t); s_loc == 0 (never for these kernels): no window
+    const int radius = coef.s_loc > 0.f ? (int)std::floor(std::sqrt(151.0 / (double)coef.s_loc)) + 1 : (width + height) * 2;
+    const int nchunks = (int)ceil_div(row1 - row0, EW_ROWS);
+    if (nchunks > 65535)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too tall for one %s degree launch", gen == PixGen::Rgb ? "colour" : "16-bit");
+    DevBuf<double> partial;
+    DevBuf<unsigned long long> count;
+    GLF_TRY(partial.alloc(ctx, (size_t)nchunks * p));
+    GLF_TRY(count.alloc(ctx, 1));
+    GLF_HIP(ctx, hipMemsetAsync(count.p, 0, sizeof(unsigned long long), ctx->stream));
+    const dim3 grid((unsigned)ceil_div(p, 256), nchunks);
+    if (gen == PixGen::Rgb)
+        hipLaunchKernelGGL(k_degree_entrywise<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p,
+                           coef.s_loc, coef.s_val, radius, partial.p, count.p);
+    else
+        hipLaunchKernelGGL(k_degree_entrywise<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p,
+                           coef.s_loc, coef.s_val, radius, partial.p, count.p);
+    GLF_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
+    GLF_LAUNCH_CHECK(ctx);
+    unsigned long long h_count = 0;
+    GLF_HIP(ctx, hipMemcpyAsync(&h_count, count.p, sizeof(h_count), hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // partial is released at scope exit
+    if (evaluated) *evaluated = (double)h_count;
+    return GLF_OK;
+}
+
+// ---- whole path: the guide's channels as float planes [NCH][N] (c = Phi^T x_k with f64 sums, k_phi_t_signals) -------------
+template <PixGen G>
+__global__ void k_planes(const uint8_t *__restrict__ img_bytes, int64_t N, float *__restrict__ planes)
+{
+    using P = Pix<G>;
+    const typename P::In *img = reinterpret_cast<const typename P::In *>(img_bytes);
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+#pragma unroll
+    for (int k = 0; k < P::NCH; ++k) planes[k * N + i] = (float)img[P::NCH * i + k];
+}
+
+int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float *d_planes)
+{
+    if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "pix_planes: the 8-bit grey format has kernels of its own");
+    const dim3 grid((unsigned)ceil_div(N, 256));
+    if (gen == PixGen::Rgb) hipLaunchKernelGGL(k_planes<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    else hipLaunchKernelGGL(k_planes<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+// ---- filter ---------------------------------------------------------------------------------------------------------------------
+// Channel k of pixel px is x = img[NCH px + k], its correction c = gain * Phi[px] . w_k - ysub * x, the output P::output(x, c)
+// (clamped and cast as the grey d_out, at the format's depth) and zf (optional) [NCH][N] = x + c. The dot product and c are formed in
+// f64: with the smoothing filters (z = Phi w, no y term) the terms of Phi[px] . w cancel to ~1 % of their size, and an f32 sum
+// leaves ~1.5e-5 of relative error in z where f64 leaves the f32 rounding of Phi and w alone.
+template <int LD, PixGen G>
+__global__ __launch_bounds__(256) void k_apply_filter_pix(const float *__restrict__ phi, int64_t pix0, int64_t pix1, const float *__restrict__ w,
+                                                           float gain, float ysub, const uint8_t *__restrict__ img_bytes,
+                                                           uint8_t *__restrict__ out_bytes, float *__restrict__ zf, int64_t N)
+{
+    using P = Pix<G>;
+    constexpr int NCH = P::NCH, LPP = LD / 4, PPB = 256 / LPP;
+    const typename P::In *img = reinterpret_cast<const typename P::In *>(img_bytes);
+    typename P::Out *out = reinterpret_cast<typename P::Out *>(out_bytes);
+    const int q = threadIdx.x % LPP, pl = threadIdx.x / LPP;
+    float4 wq[NCH];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) wq[k] = reinterpret_cast<const float4 *>(w + (size_t)k * LD)[q];
+    for (int64_t px = pix0 + (int64_t)blockIdx.x * PPB + pl; px < pix1; px += (int64_t)gridDim.x * PPB) {
+        const float4 f = reinterpret_cast<const float4 *>(phi + (size_t)px * LD)[q];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            double s = (double)f.x * wq[k].x + (double)f.y * wq[k].y + (double)f.z * wq[k].z + (double)f.w * wq[k].w;
+#pragma unroll
+            for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (q == 0) {
+                const int x = (int)img[NCH * px + k];
+                const double c = (double)gain * s - (double)ysub * (double)x;
+                if (zf) zf[(size_t)k * N + px] = (float)((double)x + c);
+                out[NCH * px + k] = P::output(x, c);
+            }
+        }
+    }
+}
+
+template <PixGen G>
+static void launch_apply_filter_pix(unsigned ld, dim3 grid, hipStream_t st, const float *d_phi, int64_t pix0, int64_t pix1, const float *d_w,
+                                    float gain, float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, int64_t N)
+{
+    switch (ld) {
+    case 32: hipLaunchKernelGGL((k_apply_filter_pix<32, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); break;
+    case 64: hipLaunchKernelGGL((k_apply_filter_pix<64, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); break;
+    case 128: hipLaunchKernelGGL((k_apply_filter_pix<128, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); break;
+    case 256: hipLaunchKernelGGL((k_apply_filter_pix<256, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); break;
+    }
+}
+
+int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain,
+                     float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, int64_t N)
+{
+    if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "apply_filter_pix: the 8-bit grey format has kernels of its own");
+    if (!valid_ld(ld) || pix0 > pix1) return set_error(ctx, GLF_ERR_INVALID, "apply_filter_pix: ld=%u", ld);
+    if (pix0 == pix1) return GLF_OK;
+    const int ppb = 256 / (ld / 4);
+    int64_t nblk = ceil_div(pix1 - pix0, ppb);
+    if (nblk > 8192) nblk = 8192; // grid-stride the rest
+    const dim3 grid((unsigned)nblk);
+    if (gen == PixGen::Rgb) launch_apply_filter_pix<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    else launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+} // namespace glf

@@ -166,18 +166,6 @@ int phi_gram(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsig
     return GLF_OK;
 }
 
-// AboveXSetY(z, 255, 255) (hpc/display.c:76), negative -> 0 (survey quirk Q4) and the truncating (png_byte) cast
-// (hpc/utils.c:525) of the reference's fp64 z = y + c, evaluated WITHOUT rounding the sum to f32 first: y is an integer, so
-// trunc(y + c) = y + floor(c) wherever y + c >= 0. At 4096^2 |c| ~ 1e-3 grey levels: the f32 sum rounds y - 2e-6 up to y
-// and 4 % of the pixels then miss the reference's y - 1.
-__device__ __forceinline__ uint8_t filter_output(int y, float c)
-{
-    int zi = y + (int)floorf(fminf(fmaxf(c, -1.0e6f), 1.0e6f));
-    zi = zi > 255 ? 255 : zi;
-    zi = (zi < 0 || !(c == c)) ? 0 : zi; // (NaN -> 0)
-    return (uint8_t)zi;
-}
-
 // z[pix] = y + gain * sum_j Phi[pix][j] w[j]; LD/4 lanes per pixel, float4 each.
 template <int LD>
 __global__ __launch_bounds__(256) void k_apply_filter(const uint8_t *__restrict__ img, const float *__restrict__ phi,
@@ -425,56 +413,6 @@ int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t
     case 64: hipLaunchKernelGGL(k_apply_filter_signals<64>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
     case 128: hipLaunchKernelGGL(k_apply_filter_signals<128>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
     case 256: hipLaunchKernelGGL(k_apply_filter_signals<256>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
-    }
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
-// colour output (glf_image_processing_rgb): channel c of pixel px is x = rgb[3 px + c], its correction c = gain * Phi[px] . w_c -
-// ysub * x, and the output filter_output(x, c) as the grey d_out; zf (optional) [3][N] = x + c. The dot product and c are formed in
-// f64: with the smoothing filters (z = Phi w, no y term) the terms of Phi[px] . w cancel to ~1 % of their size, and an f32 sum
-// leaves ~1.5e-5 of relative error in z where f64 leaves the f32 rounding of Phi and w alone
-template <int LD>
-__global__ __launch_bounds__(256) void k_apply_filter_rgb(const float *__restrict__ phi, int64_t pix0, int64_t pix1, const float *__restrict__ w,
-                                                           float gain, float ysub, const uint8_t *__restrict__ rgb, uint8_t *__restrict__ out,
-                                                           float *__restrict__ zf, int64_t N)
-{
-    constexpr int LPP = LD / 4, PPB = 256 / LPP;
-    const int q = threadIdx.x % LPP, pl = threadIdx.x / LPP;
-    float4 wq[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) wq[k] = reinterpret_cast<const float4 *>(w + (size_t)k * LD)[q];
-    for (int64_t px = pix0 + (int64_t)blockIdx.x * PPB + pl; px < pix1; px += (int64_t)gridDim.x * PPB) {
-        const float4 f = reinterpret_cast<const float4 *>(phi + (size_t)px * LD)[q];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            double s = (double)f.x * wq[k].x + (double)f.y * wq[k].y + (double)f.z * wq[k].z + (double)f.w * wq[k].w;
-#pragma unroll
-            for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-            if (q == 0) {
-                const int x = (int)rgb[3 * px + k];
-                const double c = (double)gain * s - (double)ysub * (double)x;
-                if (zf) zf[(size_t)k * N + px] = (float)((double)x + c);
-                out[3 * px + k] = filter_output(x, (float)c);
-            }
-        }
-    }
-}
-
-int apply_filter_rgb(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain, float ysub,
-                     const uint8_t *d_rgb, uint8_t *d_out, float *d_zf, int64_t N)
-{
-    if (!valid_ld(ld) || pix0 > pix1) return set_error(ctx, GLF_ERR_INVALID, "apply_filter_rgb: ld=%u", ld);
-    if (pix0 == pix1) return GLF_OK;
-    const int ppb = 256 / (ld / 4);
-    int64_t nblk = ceil_div(pix1 - pix0, ppb);
-    if (nblk > 8192) nblk = 8192; // grid-stride the rest
-    dim3 grid((unsigned)nblk), block(256);
-    switch (ld) {
-    case 32: hipLaunchKernelGGL(k_apply_filter_rgb<32>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_rgb, d_out, d_zf, N); break;
-    case 64: hipLaunchKernelGGL(k_apply_filter_rgb<64>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_rgb, d_out, d_zf, N); break;
-    case 128: hipLaunchKernelGGL(k_apply_filter_rgb<128>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_rgb, d_out, d_zf, N); break;
-    case 256: hipLaunchKernelGGL(k_apply_filter_rgb<256>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_rgb, d_out, d_zf, N); break;
     }
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;

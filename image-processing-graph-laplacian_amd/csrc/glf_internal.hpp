@@ -228,10 +228,117 @@ __device__ __forceinline__ float kernel_eval(float dr, float dc, float dv, float
 // byte k of a packed colour R + 256 G + 65536 B as f32 (v_cvt_f32_ubyte<k>)
 __device__ __forceinline__ float ubyte_f32(unsigned v, int k) { return (float)((v >> (8 * k)) & 0xffu); }
 
-// The pixel generators of the entry-by-entry kernels (k_nystroem and, later, a band form): how a pixel's value is read from the
-// image and compared with a sample record. Grey: uint8 [N], record {row, col, v, 0}; Rgb: interleaved uint8 [N][3], record
-// {row, col, 0, R + 256 G + 65536 B}; U16: uint16 [N] (the same byte pointer, read as 16-bit), record {row, col, v, 0}.
+// AboveXSetY(z, 255, 255) (hpc/display.c:76), negative -> 0 (survey quirk Q4) and the truncating (png_byte) cast
+// (hpc/utils.c:525) of the reference's fp64 z = y + c, evaluated WITHOUT rounding the sum to f32 first: y is an integer, so
+// trunc(y + c) = y + floor(c) wherever y + c >= 0. At 4096^2 |c| ~ 1e-3 grey levels: the f32 sum rounds y - 2e-6 up to y
+// and 4 % of the pixels then miss the reference's y - 1.
+__device__ __forceinline__ uint8_t filter_output(int y, float c)
+{
+    int zi = y + (int)floorf(fminf(fmaxf(c, -1.0e6f), 1.0e6f));
+    zi = zi > 255 ? 255 : zi;
+    zi = (zi < 0 || !(c == c)) ? 0 : zi; // (NaN -> 0)
+    return (uint8_t)zi;
+}
+// the same rule at 16 bits, in f64: clamp(x + floor(c), 0, 65535), NaN -> 0
+__device__ __forceinline__ uint16_t filter_output_u16(int x, double c)
+{
+    const double fc = floor(fmin(fmax(c, -1.0e6), 1.0e6));
+    int zi = x + (int)fc;
+    zi = zi > 65535 ? 65535 : zi;
+    zi = (zi < 0 || !(c == c)) ? 0 : zi;
+    return (uint16_t)zi;
+}
+
+// The pixel formats. Grey: uint8 [N] (GLF_KERNEL_BILATERAL and the other 8-bit kernels); Rgb: interleaved uint8 [N][3]
+// (GLF_KERNEL_BILATERAL_RGB); U16: uint16 [N] (GLF_KERNEL_BILATERAL_U16). The image travels as a byte pointer; the entry-by-entry
+// kernels read it through the format's policy Pix<G>, which holds all that differs between the formats:
+//   In, NCH        the image element and the channels per pixel: channel k of pixel px is img[NCH px + k]
+//   Val, read      a pixel's value as the kernels compare it (its channels in f32, exact)
+//   record, value  the sample record of pixel px and the value it carries. Grey, U16: {row, col, v, 0};
+//                  Rgb: {row, col, 0, R + 256 G + 65536 B} (the packed colour as an exact integer in f32)
+//   dist2          the squared photometric distance |a - b|^2 in a fixed operation order; the kernels take
+//                  K = exp2(-fmaf(dist2, s_val, (dr^2 + dc^2) s_loc))
+//   Tile, tile     the degree sweep's LDS element {value, col}; outside() lies in a column no sample reaches (K = 0)
+//   Out, output    the output element of the apply kernel and its rule for channel x with its f64 correction c: the grey
+//                  d_out's rule, through f32 at 8 bits, in f64 at 16 bits
+// The factored forms over the 256 grey levels (grid, rank, band, the level-table degree) exist for Grey alone.
 enum class PixGen { Grey, Rgb, U16 };
+template <PixGen G> struct Pix;
+// one grey value per pixel, stored as T (Grey: uint8_t, U16: uint16_t): the record {row, col, v, 0}
+template <typename T> struct PixGreyValue {
+    using In = T;
+    using Val = float;
+    static constexpr int NCH = 1;
+    __device__ __forceinline__ static Val read(const In *img, int64_t px) { return (float)img[px]; }
+    __device__ __forceinline__ static float4 record(const In *img, uint32_t px, uint32_t width)
+    {
+        return make_float4((float)(px / width), (float)(px % width), (float)img[px], 0.f);
+    }
+    __device__ __forceinline__ static Val value(float4 s) { return s.z; }
+    __device__ __forceinline__ static float dist2(Val a, Val b) { const float d = a - b; return d * d; }
+};
+template <> struct Pix<PixGen::Grey> : PixGreyValue<uint8_t> {};
+template <> struct Pix<PixGen::U16> : PixGreyValue<uint16_t> {
+    using Tile = float2; // {v, col}
+    using Out = uint16_t;
+    __device__ __forceinline__ static Tile tile(const In *img, int64_t px, int c) { return make_float2(read(img, px), (float)c); }
+    __device__ __forceinline__ static Tile outside() { return make_float2(0.f, -1e30f); }
+    __device__ __forceinline__ static Val tile_value(Tile t) { return t.x; }
+    __device__ __forceinline__ static float tile_col(Tile t) { return t.y; }
+    __device__ __forceinline__ static Out output(int x, double c) { return filter_output_u16(x, c); }
+};
+template <> struct Pix<PixGen::Rgb> {
+    using In = uint8_t;
+    using Val = float3;
+    using Tile = float4; // {R, G, B, col}
+    using Out = uint8_t;
+    static constexpr int NCH = 3;
+    __device__ __forceinline__ static Val read(const In *img, int64_t px)
+    {
+        return make_float3((float)img[3 * px], (float)img[3 * px + 1], (float)img[3 * px + 2]);
+    }
+    __device__ __forceinline__ static float4 record(const In *img, uint32_t px, uint32_t width)
+    {
+        const In *q = img + (size_t)px * 3;
+        return make_float4((float)(px / width), (float)(px % width), 0.f, (float)((unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16)));
+    }
+    __device__ __forceinline__ static Val value(float4 s)
+    {
+        const unsigned v = (unsigned)s.w;
+        return make_float3(ubyte_f32(v, 0), ubyte_f32(v, 1), ubyte_f32(v, 2));
+    }
+    __device__ __forceinline__ static float dist2(Val a, Val b)
+    {
+        const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z;
+        return fmaf(d2, d2, fmaf(d1, d1, d0 * d0)); // exact: integers below 2^18
+    }
+    __device__ __forceinline__ static Tile tile(const In *img, int64_t px, int c)
+    {
+        const Val v = read(img, px);
+        return make_float4(v.x, v.y, v.z, (float)c);
+    }
+    __device__ __forceinline__ static Tile outside() { return make_float4(0.f, 0.f, 0.f, -1e30f); }
+    __device__ __forceinline__ static Val tile_value(Tile t) { return make_float3(t.x, t.y, t.z); }
+    __device__ __forceinline__ static float tile_col(Tile t) { return t.w; }
+    __device__ __forceinline__ static Out output(int x, double c) { return filter_output(x, (float)c); }
+};
+// host side: the format a kernel reads (and the bilateral kernel on a format), whether the factored forms over the 256 grey
+// levels apply to a kernel, bytes and channels per pixel
+inline PixGen pixgen_of(int kernel)
+{
+    return kernel == GLF_KERNEL_BILATERAL_RGB ? PixGen::Rgb : kernel == GLF_KERNEL_BILATERAL_U16 ? PixGen::U16 : PixGen::Grey;
+}
+inline int bilateral_kernel_of(PixGen g)
+{
+    return g == PixGen::Rgb ? GLF_KERNEL_BILATERAL_RGB : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16 : GLF_KERNEL_BILATERAL;
+}
+inline bool grey_levels_factor(int kernel) { return kernel != GLF_KERNEL_NLM && pixgen_of(kernel) == PixGen::Grey; }
+template <PixGen G> constexpr size_t pix_bytes_of = sizeof(typename Pix<G>::In) * Pix<G>::NCH;
+inline size_t pix_bytes(PixGen g)
+{
+    return g == PixGen::Rgb ? pix_bytes_of<PixGen::Rgb> : g == PixGen::U16 ? pix_bytes_of<PixGen::U16> : pix_bytes_of<PixGen::Grey>;
+}
+inline int pix_channels(PixGen g) { return g == PixGen::Rgb ? Pix<PixGen::Rgb>::NCH : g == PixGen::U16 ? Pix<PixGen::U16>::NCH : Pix<PixGen::Grey>::NCH; }
 
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
@@ -277,8 +384,7 @@ struct SampleTables {
     DevBuf<uint8_t> mask;
     DevBuf<uint32_t> idx;
 };
-// kernel GLF_KERNEL_BILATERAL_RGB: d_img is interleaved RGB and a record is {row, col, 0, R + 256 G + 65536 B};
-// GLF_KERNEL_BILATERAL_U16: d_img is uint16_t [height][width] and a record is {row, col, v, 0} as for grey
+// d_img and the records in the format of `kernel` (Pix<pixgen_of(kernel)>)
 int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int height, unsigned p,
                         const unsigned *h_idx, SampleTables &out, int kernel = GLF_KERNEL_BILATERAL);
 
@@ -319,21 +425,16 @@ int nlm_sample_matrix(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
 int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const uint8_t *d_mask,
                  const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld, float *d_phi, int raster,
                  double *d_c, float *kernel_ms);
-// colour bilateral kernel (rgb.hip, GLF_KERNEL_BILATERAL_RGB): image interleaved uint8 [height][width][3]; same contracts as
-// degree_rows / build_sample_matrix (nystroem_contract runs k_nystroem with the colour generator)
-int rgb_degree_rows(glf_ctx *ctx, const uint8_t *d_rgb, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
-                    KernelCoef coef, double *d_degree, double *evaluated);
-int rgb_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, KernelCoef coef, float *d_out, int64_t ld, bool laplacian,
-                      double alpha, const double *d_degree, unsigned col0, unsigned ncols);
-int rgb_planes(glf_ctx *ctx, const uint8_t *d_rgb, int64_t N, float *d_planes); // [3][N] float channel planes
-// 16-bit grey bilateral kernel (u16.hip, GLF_KERNEL_BILATERAL_U16): image uint16_t [height][width]; the same contract as
-// degree_rows (K_A / L_A come from k_sample_matrix on the grey records; nystroem_contract runs k_nystroem with the 16-bit read)
-int u16_degree_rows(glf_ctx *ctx, const uint16_t *d_img, int width, int height, int row0, int row1, const float4 *d_samples, unsigned p,
-                    KernelCoef coef, double *d_degree, double *evaluated);
-int u16_plane(glf_ctx *ctx, const uint16_t *d_img, int64_t N, float *d_plane); // the image as one float plane [N]
-// 16-bit output: d_w [ld]; d_img / d_out uint16_t [N], rows [pix0, pix1) only; d_zf optional [N]
-int apply_filter_u16(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain, float ysub,
-                     const uint16_t *d_img, uint16_t *d_out, float *d_zf);
+// out[i] = sum over the chunks k of partial[k][i], k ascending (affinity.hip)
+__global__ void k_reduce_partials(const double *__restrict__ partial, unsigned p, int nchunks, double *__restrict__ out);
+// the formats without a factored form (entrywise.hip, gen Rgb or U16; d_img in the format): the contract of degree_rows, the
+// windowed entry-by-entry sweep (*evaluated = entries computed); the image's channels as float planes [NCH][N]; the outputs
+// (d_w [NCH][ld]; d_img / d_out [N] pixels, rows [pix0, pix1) only; d_zf optional [NCH][N])
+int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height, int row0, int row1,
+                          const float4 *d_samples, unsigned p, KernelCoef coef, double *d_degree, double *evaluated);
+int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float *d_planes);
+int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain,
+                     float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, int64_t N);
 int laplacian_from_KA(glf_ctx *ctx, const float *d_KA, int64_t ldk, unsigned p, float *d_LA, int64_t ld,
                       double alpha, const double *d_degree);
 
@@ -465,9 +566,6 @@ int filter_sample_rows_signals(glf_ctx *ctx, const float *d_phiA, unsigned n, un
                                float gain, float ysub, const float *d_sig, float *d_out, int64_t N);
 int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w, float gain,
                          float ysub, const float *d_sig, float *d_out, int64_t N);
-// colour output: d_w [3][ld]; d_rgb / d_out interleaved uint8 [N][3], rows [pix0, pix1) only; d_zf optional [3][N]
-int apply_filter_rgb(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain, float ysub,
-                     const uint8_t *d_rgb, uint8_t *d_out, float *d_zf, int64_t N);
 // the same filter panel by panel (m > 256): acc[px - pix0] (+)= sum_j Phi[px][j] w[j], then z = (1 - ysub) y + gain * acc
 int filter_accumulate(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float *d_acc,
                       bool first);

@@ -142,15 +142,6 @@ __global__ __launch_bounds__(256) void k_nlm_degree(const uint8_t *__restrict__ 
     if (live) partial[(size_t)blockIdx.y * p + i] = total;
 }
 
-__global__ void k_nlm_reduce(const double *__restrict__ partial, unsigned p, int nchunks, double *__restrict__ out)
-{
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= p) return;
-    double s = 0.0;
-    for (int k = 0; k < nchunks; ++k) s += partial[(size_t)k * p + i];
-    out[i] = s;
-}
-
 int nlm_degree_rows(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int row0, int row1, const uint32_t *d_idx, unsigned p,
                     KernelCoef coef, double *d_degree)
 {
@@ -166,7 +157,7 @@ int nlm_degree_rows(glf_ctx *ctx, const uint8_t *d_img, int width, int height, i
     GLF_TRY(partial.alloc(ctx, (size_t)nchunks * p));
     hipLaunchKernelGGL(k_nlm_degree, dim3((unsigned)ceil_div(p, 256), nchunks), dim3(256), 0, ctx->stream, d_img, width, height, pix0, pix1,
                        d_idx, p, coef.s_val, nlm_mask(), partial.p);
-    hipLaunchKernelGGL(k_nlm_reduce, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
+    hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // partial is released at scope exit
     return GLF_OK;

@@ -102,9 +102,8 @@ __device__ __forceinline__ int build_chunk_list(const int4 *__restrict__ box, in
     return scratch[256];
 }
 
-// GEN: the pixel generator (PixGen, glf_internal.hpp). Rgb: the colour generator (GLF_KERNEL_BILATERAL_RGB, rgb.hip): img is
-// interleaved RGB and a sample record carries its packed colour in w. U16 (GLF_KERNEL_BILATERAL_U16, u16.hip): img is uint16_t
-// and the grey record and exponent apply. Only the grey generator has the epilogue's y (cpartial must be null for the others).
+// GEN: the pixel format (Pix<GEN>, glf_internal.hpp): how img is read and a pixel compared with a sample record. Only the grey
+// format has the epilogue's y (cpartial must be null for the others).
 template <int MB, int PB, bool SKIP, PixGen GEN = PixGen::Grey> // MB = ld / 32 column blocks; PB = 32-pixel blocks per wave; SKIP: chunk list
 __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ img, int width, int64_t pix0, int64_t pix1,
                                                    const float4 *__restrict__ samples, unsigned p, float s_loc,
@@ -116,7 +115,7 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
 {
     constexpr int LD = MB * 32;
     constexpr int KC = NYS_KC;
-    constexpr bool RGB = GEN == PixGen::Rgb;
+    using P = Pix<GEN>;
     __shared__ unsigned short clist[SKIP ? NYS_MAXCH : 1];
     __shared__ int cscratch[SKIP ? 257 : 1];
     // one array for everything (guide: a second __shared__ object can de-pipeline LDS staging)
@@ -128,22 +127,15 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
     const int64_t wbase = pix0 + ((int64_t)blockIdx.x * 4 + wave) * (32 * PB);
 
     // this lane's pixels (one per 32-pixel block): exact integer coordinates in f32
-    float pr[PB], pc[PB], pv[PB], pg[RGB ? PB : 1], pb[RGB ? PB : 1];
+    float pr[PB], pc[PB];
+    typename P::Val pv[PB];
 #pragma unroll
     for (int b = 0; b < PB; ++b) {
         int64_t px = wbase + 32 * b + l31;
         if (px >= pix1) px = pix1 - 1; // clamp loads; stores are guarded
         pr[b] = (float)(px / width);
         pc[b] = (float)(px % width);
-        if constexpr (RGB) {
-            pv[b] = (float)img[3 * px];
-            pg[b] = (float)img[3 * px + 1];
-            pb[b] = (float)img[3 * px + 2];
-        } else if constexpr (GEN == PixGen::U16) {
-            pv[b] = (float)reinterpret_cast<const uint16_t *>(img)[px];
-        } else {
-            pv[b] = (float)img[px];
-        }
+        pv[b] = P::read(reinterpret_cast<const typename P::In *>(img), px);
     }
 
     f32x16 acc[PB][MB];
@@ -183,20 +175,13 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
 #pragma unroll 4
         for (int kk = 0; kk < KC / 2; ++kk) {
             const float4 s = stb[kk]; // two addresses per wave: broadcast within each half
+            const typename P::Val sv = P::value(s);
             float a[PB];
-            if constexpr (RGB) {
-                const unsigned sc = (unsigned)s.w;
-                const float sr = ubyte_f32(sc, 0), sg = ubyte_f32(sc, 1),
-                            sb = ubyte_f32(sc, 2);
 #pragma unroll
-                for (int b = 0; b < PB; ++b) {
-                    const float dr = pr[b] - s.x, dc = pc[b] - s.y, d0 = pv[b] - sr, d1 = pg[b] - sg, d2 = pb[b] - sb;
-                    const float u = fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
-                    a[b] = __builtin_amdgcn_exp2f(-fmaf(u, s_val, fmaf(dc, dc, dr * dr) * s_loc));
-                }
-            } else {
-#pragma unroll
-                for (int b = 0; b < PB; ++b) a[b] = kernel_eval(pr[b] - s.x, pc[b] - s.y, pv[b] - s.z, s_loc, s_val);
+            for (int b = 0; b < PB; ++b) {
+                const float dr = pr[b] - s.x, dc = pc[b] - s.y;
+                const float q = fmaf(dc, dc, dr * dr);
+                a[b] = __builtin_amdgcn_exp2f(-fmaf(P::dist2(pv[b], sv), s_val, q * s_loc));
             }
 #pragma unroll
             for (int j = 0; j < MB; ++j) {
@@ -817,7 +802,7 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
 #include "grid_common.inc"
 #include "nystroem_grid.inc"
 
-// the f32-MFMA k_nystroem with a non-grey pixel generator (no c = Phi^T y in its epilogue)
+// the f32-MFMA k_nystroem with a non-grey pixel format (no c = Phi^T y in its epilogue)
 template <PixGen GEN>
 static int nystroem_entrywise(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
                               const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
@@ -853,11 +838,12 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
         return nlm_nystroem(ctx, d_img, width, height, pix0, pix1, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c, kernel_ms);
     }
     int rc = GLF_ERR_UNSUPPORTED;
-    if (coef.kernel == GLF_KERNEL_BILATERAL_RGB || coef.kernel == GLF_KERNEL_BILATERAL_U16) {
-        // the colour and 16-bit generators: entry by entry, f32 MFMA (no factored or split-f16 form)
+    const PixGen gen = pixgen_of(coef.kernel);
+    if (gen != PixGen::Grey) {
+        // the colour and 16-bit formats: entry by entry, f32 MFMA (no factored or split-f16 form)
         if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour and 16-bit kernels have no 8-bit y for Phi^T y");
         window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
-        rc = coef.kernel == GLF_KERNEL_BILATERAL_RGB
+        rc = gen == PixGen::Rgb
                  ? nystroem_entrywise<PixGen::Rgb>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated)
                  : nystroem_entrywise<PixGen::U16>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated);
         if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;

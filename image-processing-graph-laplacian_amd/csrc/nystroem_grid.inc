@@ -1229,8 +1229,7 @@ static int nystroem_contract_grid(glf_ctx *ctx, const uint8_t *d_img, int width,
                                   int window, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *rowpass_stats,
                                   int *path)
 {
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(ctx->tune.nys_path, width) || coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB ||
-        coef.kernel == GLF_KERNEL_BILATERAL_U16)
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(ctx->tune.nys_path, width) || !grey_levels_factor(coef.kernel))
         return GLF_ERR_UNSUPPORTED;
     if (pix0 % width || pix1 % width || width > GRID_MAX_W || p < 4) return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> hidx(p);
@@ -1267,8 +1266,8 @@ int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
                          const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, int *path,
                          RowpassStats *stats, const unsigned *h_idx)
 {
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !(ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) || coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB ||
-        coef.kernel == GLF_KERNEL_BILATERAL_U16 || !grid_path_wanted(ctx->tune.nys_path, width) || ld > 64)
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !(ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) || !grey_levels_factor(coef.kernel) ||
+        !grid_path_wanted(ctx->tune.nys_path, width) || ld > 64)
         return GLF_ERR_UNSUPPORTED;
     if (pix0 % width || pix1 % width || width > GRID_MAX_W || p < 4 || pix0 >= pix1) return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> hidx(p);
@@ -1384,9 +1383,7 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
                    KernelCoef coef, GridOp **out)
 {
     *out = nullptr;
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || p < 4 || coef.kernel == GLF_KERNEL_NLM || coef.kernel == GLF_KERNEL_BILATERAL_RGB ||
-        coef.kernel == GLF_KERNEL_BILATERAL_U16)
-        return GLF_ERR_UNSUPPORTED;
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || p < 4 || !grey_levels_factor(coef.kernel)) return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> idx(h_idx, h_idx + p);
     GridInfo g;
     if (!detect_grid(idx, width, g) || ceil_div(g.nr, 16) > GRID_MAX_KS || g.nc > GRID_MAX_W) return GLF_ERR_UNSUPPORTED;

@@ -480,24 +480,22 @@ int glf_image_processing(glf_ctx *ctx, const glf_options *opt_in, const uint8_t 
     return glf_image_processing_capture(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
 }
 
-// extra signal planes of glf_image_processing_signals (nullptr: the guide alone); rgb_out set: glf_image_processing_rgb, the guide is
-// the colour image and its three channels are the planes (formed inside from the image); u16_out set: glf_image_processing_u16, the
-// guide is the 16-bit image and it is the one plane
+// extra signal planes of glf_image_processing_signals (nullptr: the guide alone)
 struct SignalPlanes {
     int nsig;
     const float *d_sig;
     float *d_out;
-    uint8_t *rgb_out = nullptr;
-    uint16_t *u16_out = nullptr;
 };
 
-static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
-                                float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
+// gen: the guide's pixel format; d_img and d_out are [N] pixels of it. A colour or 16-bit guide has no 8-bit y: its channels are
+// filtered as planes (formed inside from the image) and written to d_out.
+static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
+                                uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
 
 int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height,
                                  uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    return image_processing_run(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, nullptr);
+    return image_processing_run(ctx, opt_in, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, int nsig,
@@ -506,23 +504,20 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
 {
     if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
-    return image_processing_run(ctx, opt, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, &sig);
+    return image_processing_run(ctx, opt, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, &sig);
 }
 
 int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                              float *d_zf, double *eigvals_out, glf_stats *stats)
 {
-    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    const SignalPlanes sig{3, nullptr, nullptr, d_out_rgb};
-    return image_processing_run(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr, &sig);
+    return glf_image_processing_rgb_capture(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr);
 }
 
 int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                                      float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
     if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    const SignalPlanes sig{3, nullptr, nullptr, d_out_rgb};
-    return image_processing_run(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, cap, &sig);
+    return image_processing_run(ctx, opt, PixGen::Rgb, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
@@ -535,13 +530,12 @@ int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const
                                      float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
     if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    const SignalPlanes sig{1, nullptr, nullptr, nullptr, d_out};
-    return image_processing_run(ctx, opt, reinterpret_cast<const uint8_t *>(d_img), width, height, reinterpret_cast<uint8_t *>(d_out), d_zf,
-                                eigvals_out, stats, cap, &sig);
+    return image_processing_run(ctx, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(d_img), width, height,
+                                reinterpret_cast<uint8_t *>(d_out), d_zf, eigvals_out, stats, cap, nullptr);
 }
 
-static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height, uint8_t *d_out,
-                                float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
+static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
+                                uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
     if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     if (cap && cap->struct_size != sizeof(glf_capture))
@@ -555,21 +549,20 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
             return set_error(ctx, GLF_ERR_INVALID, "glf_options.struct_size %u != %zu", opt_in->struct_size, sizeof(glf_options));
         opt = *opt_in;
     }
-    // the colour kernel reads the image as RGB: only the colour entry point takes it, and there it is the only kernel; the same for
-    // the 16-bit kernel and the 16-bit entry point. Both guides have no 8-bit y: their values are filtered as planes (u8_guide false)
-    const bool rgb = sig && sig->rgb_out, u16 = sig && sig->u16_out, u8_guide = !rgb && !u16;
-    if (rgb) {
-        if (opt.kernel != GLF_KERNEL_BILATERAL && opt.kernel != GLF_KERNEL_BILATERAL_RGB)
-            return set_error(ctx, GLF_ERR_UNSUPPORTED, "colour filtering: kernel %d (the colour bilateral kernel only)", opt.kernel);
-        opt.kernel = GLF_KERNEL_BILATERAL_RGB;
-    } else if (u16) {
-        if (opt.kernel != GLF_KERNEL_BILATERAL && opt.kernel != GLF_KERNEL_BILATERAL_U16)
-            return set_error(ctx, GLF_ERR_UNSUPPORTED, "16-bit filtering: kernel %d (the 16-bit bilateral kernel only)", opt.kernel);
-        opt.kernel = GLF_KERNEL_BILATERAL_U16;
-    } else if (opt.kernel == GLF_KERNEL_BILATERAL_RGB)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the colour kernel takes an RGB image: glf_image_processing_rgb");
-    else if (opt.kernel == GLF_KERNEL_BILATERAL_U16)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
+    // a kernel reads one pixel format: the colour and 16-bit entry points take their format's bilateral kernel only (for which
+    // GLF_KERNEL_BILATERAL stands there), the 8-bit entry points no kernel of another format. The colour and 16-bit guides have no
+    // 8-bit y: their values are filtered as planes (u8_guide false)
+    const bool u8_guide = gen == PixGen::Grey;
+    if (!u8_guide && opt.kernel == GLF_KERNEL_BILATERAL) opt.kernel = bilateral_kernel_of(gen);
+    if (pixgen_of(opt.kernel) != gen) {
+        if (!u8_guide) {
+            const char *what = gen == PixGen::Rgb ? "colour" : "16-bit";
+            return set_error(ctx, GLF_ERR_UNSUPPORTED, "%s filtering: kernel %d (the %s bilateral kernel only)", what, opt.kernel, what);
+        }
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, pixgen_of(opt.kernel) == PixGen::Rgb
+                                                       ? "the colour kernel takes an RGB image: glf_image_processing_rgb"
+                                                       : "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
+    }
     if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_U16) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
@@ -595,18 +588,14 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
     hipStream_t st = ctx->stream;
     glf_stats S{};
-    DevBuf<float> rgb_planes_buf; // colour: the channels as float planes [3][N] (Phi^T x_c); 16-bit: the image as one plane
-    SignalPlanes rgb_sig{};
-    if (rgb) {
-        GLF_TRY(rgb_planes_buf.alloc(ctx, (size_t)3 * N));
-        GLF_TRY(rgb_planes(ctx, d_img, N, rgb_planes_buf.p));
-        rgb_sig = SignalPlanes{3, rgb_planes_buf.p, nullptr, sig->rgb_out};
-        sig = &rgb_sig;
-    } else if (u16) { // 16-bit: the image as one float plane [N] (Phi^T y with f64 sums)
-        GLF_TRY(rgb_planes_buf.alloc(ctx, (size_t)N));
-        GLF_TRY(u16_plane(ctx, reinterpret_cast<const uint16_t *>(d_img), N, rgb_planes_buf.p));
-        rgb_sig = SignalPlanes{1, rgb_planes_buf.p, nullptr, nullptr, sig->u16_out};
-        sig = &rgb_sig;
+    DevBuf<float> guide_planes; // colour: the channels as float planes [3][N] (Phi^T x_c); 16-bit: the image as one plane
+    SignalPlanes guide_sig{};
+    if (!u8_guide) {
+        const int nch = pix_channels(gen);
+        GLF_TRY(guide_planes.alloc(ctx, (size_t)nch * N));
+        GLF_TRY(pix_planes(ctx, gen, d_img, N, guide_planes.p));
+        guide_sig = SignalPlanes{nch, guide_planes.p, nullptr};
+        sig = &guide_sig;
     }
 
     // p = width*height*0.01 (truncating), hpc/image_processing.c:187; Sampling rewrites it, :191-193
@@ -1014,18 +1003,20 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
     if (u8_guide) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
     GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
     // ---- filter ------------------------------------------------------------------------------
+    auto gram_to_host = [&]() -> int { // hG = Phi^T Phi over all ranks' pixels (the sharpening weights)
+        DevBuf<double> G;
+        GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
+        GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
+        GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
+        hG.resize((size_t)ld * ld);
+        GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+        return GLF_OK;
+    };
     if (!u8_guide) { // (no 8-bit y: the channels / the 16-bit image are filtered below, as planes; the sharpening weights need G)
-        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour and 16-bit generators have no split-f16 form)
+        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour and 16-bit formats have no split-f16 form)
         if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
-        if (opt.filter_mode == GLF_FILTER_SHARPEN) {
-            DevBuf<double> G;
-            GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
-            GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
-            GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
-            hG.resize((size_t)ld * ld);
-            GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-        }
+        if (opt.filter_mode == GLF_FILTER_SHARPEN) GLF_TRY(gram_to_host());
     } else {
     {
         std::vector<double> hc(ld);
@@ -1036,13 +1027,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
         std::vector<float> hw(ld, 0.f);
         for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
         if (opt.filter_mode == GLF_FILTER_SHARPEN) {
-            DevBuf<double> G;
-            GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
-            GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
-            GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
-            hG.resize((size_t)ld * ld);
-            GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
+            GLF_TRY(gram_to_host());
             sharpen_weights(hc.data(), hw.data());
         }
         GLF_HIP(ctx, hipMemcpyAsync(w.p, hw.data(), sizeof(float) * ld, hipMemcpyHostToDevice, st));
@@ -1100,10 +1085,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, const u
         }
         GLF_HIP(ctx, hipMemcpyAsync(ws.p, hws.data(), sizeof(float) * ns * ld, hipMemcpyHostToDevice, st));
         if (!u8_guide) { // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
-            if (rgb) GLF_TRY(apply_filter_rgb(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, sig->rgb_out, d_zf, N));
-            else
-                GLF_TRY(apply_filter_u16(ctx, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, reinterpret_cast<const uint16_t *>(d_img),
-                                         sig->u16_out, d_zf));
+            GLF_TRY(apply_filter_pix(ctx, gen, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, d_out, d_zf, N));
             GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
             GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
             GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));

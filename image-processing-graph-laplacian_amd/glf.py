@@ -11,6 +11,7 @@ InversePowerIteration, OrthonormaliseVecs, Nystroem, Permutation,
 ComputeResultFromLaplacian, plus image_processing for the whole path.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -334,20 +335,17 @@ class Multi:
         opt = opt or default_options()
         out = np.zeros((h, w), dtype=np.uint8)
         zf = np.zeros((h, w), dtype=np.float32) if want_float else None
-        lam = np.zeros(max(1, int(Sampling(w, h, int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)).size)),
-                       dtype=np.float64)
+        return out, zf, self._run("glf_multi_image_processing", opt, img, out, zf)
+
+    def _run(self, fn, opt, img, out, zf, sig=()):
+        """glf_multi_<...>(world, opt, img, width, height, [nsig, planes, planes out,] out, zf, eigvals, stats): per-rank infos."""
+        h, w = img.shape[:2]
+        lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
         stats = (Stats * self.n)()
-        rc = _lib.glf_multi_image_processing(self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h),
-                                             out.ctypes.data_as(C.c_void_p), zf.ctypes.data_as(C.c_void_p) if want_float else None,
-                                             lam.ctypes.data_as(C.c_void_p), stats)
+        rc = getattr(_lib, fn)(self._w, C.byref(opt), _ptr(img), C.c_int(w), C.c_int(h), *sig, _ptr(out), _ptr(zf), _ptr(lam), stats)
         if rc != OK:
-            raise GlfError(rc, "glf_multi_image_processing: " + _lib.glf_multi_last_error(self._w).decode())
-        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, inner_its_total=s.eig.inner_its_total,
-                      residual=s.eig.residual, row0=s.row0, row1=s.row1, ms_total=s.ms_total, ms_eigen=s.ms_eigen,
-                      ms_nystroem=s.ms_nystroem, ms_affinity=s.ms_affinity, ms_laplacian=s.ms_laplacian, ms_filter=s.ms_filter,
-                      matvecs=s.eig.matvecs, nystroem_path=s.nystroem_path,
-                      matvec_path=s.matvec_path, filter_fused=s.filter_fused, eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
-        return out, zf, infos
+            raise GlfError(rc, fn + ": " + _lib.glf_multi_last_error(self._w).decode())
+        return [_info(s, lam) for s in stats]
 
     def image_processing_signals(self, img, signals, opt=None):
         """glf_multi_image_processing_signals: the host image plus float planes [nsig, H, W] (numpy, replicated on every
@@ -361,18 +359,7 @@ class Multi:
         out = np.zeros((h, w), dtype=np.uint8)
         zf = np.zeros((h, w), dtype=np.float32)
         sig_out = np.zeros(sig.shape, dtype=np.float32)
-        lam = np.zeros(max(1, int(Sampling(w, h, int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)).size)),
-                       dtype=np.float64)
-        stats = (Stats * self.n)()
-        rc = _lib.glf_multi_image_processing_signals(
-            self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h), C.c_int(sig.shape[0]),
-            sig.ctypes.data_as(C.c_void_p), sig_out.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
-            zf.ctypes.data_as(C.c_void_p), lam.ctypes.data_as(C.c_void_p), stats)
-        if rc != OK:
-            raise GlfError(rc, "glf_multi_image_processing_signals: " + _lib.glf_multi_last_error(self._w).decode())
-        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
-                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
-                      eigvals=lam[:s.m].copy()) for s in stats]
+        infos = self._run("glf_multi_image_processing_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
         return out, zf, sig_out, infos
 
     def image_processing_rgb(self, img, opt=None, want_float=False):
@@ -384,17 +371,7 @@ class Multi:
         opt = opt or default_options()
         out = np.zeros((h, w, 3), dtype=np.uint8)
         zf = np.zeros((3, h, w), dtype=np.float32) if want_float else None
-        lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
-        stats = (Stats * self.n)()
-        rc = _lib.glf_multi_image_processing_rgb(self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h),
-                                                 out.ctypes.data_as(C.c_void_p), zf.ctypes.data_as(C.c_void_p) if want_float else None,
-                                                 lam.ctypes.data_as(C.c_void_p), stats)
-        if rc != OK:
-            raise GlfError(rc, "glf_multi_image_processing_rgb: " + _lib.glf_multi_last_error(self._w).decode())
-        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
-                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
-                      eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
-        return out, zf, infos
+        return out, zf, self._run("glf_multi_image_processing_rgb", opt, img, out, zf)
 
     def image_processing_u16(self, img, opt=None, want_float=False):
         """glf_multi_image_processing_u16: host uint16 [H, W] in, (out uint16 [H, W], zf f32 [H, W] or None, per-rank infos)."""
@@ -405,17 +382,7 @@ class Multi:
         opt = opt or default_options()
         out = np.zeros((h, w), dtype=np.uint16)
         zf = np.zeros((h, w), dtype=np.float32) if want_float else None
-        lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
-        stats = (Stats * self.n)()
-        rc = _lib.glf_multi_image_processing_u16(self._w, C.byref(opt), img.ctypes.data_as(C.c_void_p), C.c_int(w), C.c_int(h),
-                                                 out.ctypes.data_as(C.c_void_p), zf.ctypes.data_as(C.c_void_p) if want_float else None,
-                                                 lam.ctypes.data_as(C.c_void_p), stats)
-        if rc != OK:
-            raise GlfError(rc, "glf_multi_image_processing_u16: " + _lib.glf_multi_last_error(self._w).decode())
-        infos = [dict(p=s.p, m=s.m, alpha=s.alpha, outer_its=s.eig.outer_its, row0=s.row0, row1=s.row1, ms_total=s.ms_total,
-                      nystroem_path=s.nystroem_path, matvec_path=s.matvec_path, filter_fused=s.filter_fused,
-                      eigen_sharded=s.eigen_sharded, eigvals=lam[:s.m].copy()) for s in stats]
-        return out, zf, infos
+        return out, zf, self._run("glf_multi_image_processing_u16", opt, img, out, zf)
 
     def comm_counters(self, rank=0, reset=True):
         """Collectives rank `rank` issued since the last reset: dict(allreduce_calls, allreduce_bytes, allgather_calls, allgather_bytes)."""
@@ -771,62 +738,31 @@ class Context:
             if out is None:
                 out = torch.zeros((h, w), dtype=torch.uint8, device=self.device)
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-        st = Stats()
-        # (the realised sample count sizes the eigenvalue array; hpc/sampling.c's rule, cached per image size and request)
-        req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
-        key = (w, h, req, int(getattr(opt, "sampling", 0)), int(getattr(opt, "sampling_seed", 0)))
-        cache = self.__dict__.setdefault("_p_real_cache", {})
-        if key not in cache:
-            cache[key] = int(Sampling(w, h, req).size) if not getattr(opt, "sampling", 0) else max(req, 1) * 2 + 64
-        p_real = cache[key]
+        return out, zf, self._run("glf_image_processing_capture", "image_processing", opt, d_img, out, zf, capture, grey=True)
+
+    def _run(self, fn, what, opt, d_img, out, zf, capture=False, grey=False, sig=()):
+        """fn(ctx, opt, img, width, height, [*sig,] out, zf, eigvals, stats[, capture]) on the context's stream (sig: nsig, the
+        planes and the planes out of the signals entry point, which takes no capture): the call's info dict, with info["capture"]
+        when asked for (grey: also c = Phi^T y and the correction). Errors are reported as `what`."""
+        h, w = d_img.shape[:2]
+        p_real = _realised_samples(w, h, opt)
         lam = np.zeros(max(p_real, 1), dtype=np.float64)       # m <= p - 1 eigenvalues come back
-        cap, keep = None, None
-        if capture:
-            # the realised sample count (hpc/sampling.c rewrites the request) and the row stride, known before the call
-            p_max = p_real
-            m_req = int(opt.num_eigvals) if 0 < opt.num_eigvals < p_max else max(1, p_max - 1)
-            ld = 32
-            while ld < min(m_req, 256):
-                ld *= 2
-            if self._comm_keepalive:
-                rows = shard_rows(h, self._comm_keepalive.rank, self._comm_keepalive.size)
-            elif getattr(self, "_native_rank", None):
-                rows = shard_rows(h, *self._native_rank)
-            else:
-                rows = (0, h)
-            npix = (rows[1] - rows[0]) * w
-            with torch.cuda.stream(self.stream):
-                phi_A = torch.zeros(((p_max + 63) // 64 * 64, ld), dtype=torch.float32, device=self.device)
-                phi = torch.zeros((npix, ld), dtype=torch.float32, device=self.device)
-                corr = torch.zeros(npix, dtype=torch.float32, device=self.device)
-            c_host, deg_host = np.zeros(ld, dtype=np.float64), np.zeros(p_max, dtype=np.float64)
-            cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(),
-                          c_host.ctypes.data, deg_host.ctypes.data, corr.data_ptr(), corr.numel())
-            keep = (phi_A, phi, c_host, deg_host, corr)
-        rc = _lib.glf_image_processing_capture(self._ctx, C.byref(opt), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
-                                               C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if want_float else None,
-                                               lam.ctypes.data_as(C.c_void_p), C.byref(st), C.byref(cap) if cap else None)
-        self._check(rc, "image_processing")
+        cap, keep = self._capture_buffers(w, h, opt, p_real, grey) if capture else (None, None)
+        st = Stats()
+        args = (C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h)) + sig + (
+            C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if zf is not None else None, _ptr(lam), C.byref(st))
+        if not sig:
+            args += (C.byref(cap) if cap else None,)
+        self._check(getattr(_lib, fn)(self._ctx, C.byref(opt), *args), what)
         self.stream.synchronize()
-        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its,
-                    inner_its_total=st.eig.inner_its_total, residual=st.eig.residual,
-                    ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian, ms_eigen=st.ms_eigen,
-                    ms_nystroem=st.ms_nystroem, ms_filter=st.ms_filter, ms_total=st.ms_total,
-                    nystroem_kernel_ms=st.nystroem_kernel_ms, nystroem_launches=st.nystroem_launches,
-                    row0=st.row0, row1=st.row1, contraction=st.contraction, skip_exact_zeros=st.skip_exact_zeros,
-                    nystroem_evaluated=st.nystroem_evaluated, degree_evaluated=st.degree_evaluated,
-                    nystroem_mfma_flops=st.nystroem_mfma_flops, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
-                    nystroem_rowpass_launches=st.nystroem_rowpass_launches, nystroem_rowpass_ms=st.nystroem_rowpass_ms,
-                    nystroem_rowpass_flops=st.nystroem_rowpass_flops, nystroem_colpass_launches=st.nystroem_colpass_launches,
-                    nystroem_colpass_ms=st.nystroem_colpass_ms, nystroem_colpass_flops=st.nystroem_colpass_flops, rank_terms=st.rank_terms, filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded,
-                    matvecs=st.eig.matvecs, matvec_ms=st.eig.matvec_ms, matvec_bytes=st.eig.matvec_bytes,
-                    narrow_sweeps=st.eig.narrow_sweeps,
-                    eigvals=lam[:st.m].copy())
+        info = _info(st, lam)
         if capture:
-            assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
-            info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], c=keep[2][:st.m].copy(), degree=keep[3][:st.p].copy(),
-                                   corr=keep[4], ld=int(cap.ld))
-        return out, zf, info
+            phi_A, phi, deg_host, c_host, corr = keep
+            assert cap.ld == phi_A.shape[1], (cap.ld, phi_A.shape)
+            info["capture"] = dict(phi_A=phi_A[:st.p], phi=phi, degree=deg_host[:st.p].copy(), ld=int(cap.ld))
+            if grey:
+                info["capture"].update(c=c_host[:st.m].copy(), corr=corr)
+        return info
 
 
     def image_processing_signals(self, d_img, signals, opt=None, want_float=False):
@@ -845,20 +781,8 @@ class Context:
             out = torch.zeros((h, w), dtype=torch.uint8, device=self.device)
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
             sig_out = torch.zeros(tuple(signals.shape), dtype=torch.float32, device=self.device)
-        st = Stats()
-        req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
-        p_real = int(Sampling(w, h, req).size) if not getattr(opt, "sampling", 0) else max(req, 1) * 2 + 64
-        lam = np.zeros(max(p_real, 1), dtype=np.float64)
-        rc = _lib.glf_image_processing_signals(self._ctx, C.byref(opt), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
-                                               C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()),
-                                               C.c_void_p(sig_out.data_ptr()), C.c_void_p(out.data_ptr()),
-                                               C.c_void_p(zf.data_ptr()) if want_float else None,
-                                               lam.ctypes.data_as(C.c_void_p), C.byref(st))
-        self._check(rc, "image_processing_signals")
-        self.stream.synchronize()
-        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, row0=st.row0, row1=st.row1,
-                    ms_total=st.ms_total, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
-                    filter_fused=st.filter_fused, eigvals=lam[:st.m].copy())
+        info = self._run("glf_image_processing_signals", "image_processing_signals", opt, d_img, out, zf,
+                         sig=(C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()), C.c_void_p(sig_out.data_ptr())))
         return out, zf, sig_out, info
 
     def image_processing_rgb(self, d_rgb, opt=None, want_float=False, capture=False):
@@ -874,38 +798,7 @@ class Context:
         with torch.cuda.stream(self.stream):
             out = torch.zeros((h, w, 3), dtype=torch.uint8, device=self.device)
             zf = torch.zeros((3, h, w), dtype=torch.float32, device=self.device) if want_float else None
-        st = Stats()
-        p_real = _realised_samples(w, h, opt)
-        lam = np.zeros(max(1, p_real), dtype=np.float64)
-        cap, keep = None, None
-        if capture:
-            m_req = int(opt.num_eigvals) if 0 < opt.num_eigvals < p_real else max(1, p_real - 1)
-            ld = 32
-            while ld < min(m_req, 256):
-                ld *= 2
-            rows = shard_rows(h, *self._native_rank) if getattr(self, "_native_rank", None) else (0, h)
-            with torch.cuda.stream(self.stream):
-                phi_A = torch.zeros(((p_real + 63) // 64 * 64, ld), dtype=torch.float32, device=self.device)
-                phi = torch.zeros(((rows[1] - rows[0]) * w, ld), dtype=torch.float32, device=self.device)
-            deg_host = np.zeros(p_real, dtype=np.float64)
-            cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(), None,
-                          deg_host.ctypes.data, None, 0)
-            keep = (phi_A, phi, deg_host)
-        rc = _lib.glf_image_processing_rgb_capture(self._ctx, C.byref(opt), C.c_void_p(d_rgb.data_ptr()), C.c_int(w), C.c_int(h),
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if want_float else None,
-                                                   lam.ctypes.data_as(C.c_void_p), C.byref(st), C.byref(cap) if cap else None)
-        self._check(rc, "image_processing_rgb")
-        self.stream.synchronize()
-        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, inner_its_total=st.eig.inner_its_total,
-                    residual=st.eig.residual, row0=st.row0, row1=st.row1, ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian,
-                    ms_eigen=st.ms_eigen, ms_nystroem=st.ms_nystroem, ms_filter=st.ms_filter, ms_total=st.ms_total,
-                    nystroem_kernel_ms=st.nystroem_kernel_ms, contraction=st.contraction, nystroem_evaluated=st.nystroem_evaluated,
-                    degree_evaluated=st.degree_evaluated, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
-                    filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded, eigvals=lam[:st.m].copy())
-        if capture:
-            assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
-            info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], degree=keep[2][:st.p].copy(), ld=int(cap.ld))
-        return out, zf, info
+        return out, zf, self._run("glf_image_processing_rgb_capture", "image_processing_rgb", opt, d_rgb, out, zf, capture)
 
     def image_processing_u16(self, d_img, opt=None, want_float=False, capture=False):
         """16-bit greyscale filtering (glf_image_processing_u16): d_img (device uint16 [H, W]) defines the graph through its 16-bit
@@ -919,49 +812,65 @@ class Context:
         with torch.cuda.stream(self.stream):
             out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-        st = Stats()
-        p_real = _realised_samples(w, h, opt)
-        lam = np.zeros(max(1, p_real), dtype=np.float64)
-        cap, keep = None, None
-        if capture:
-            cap, keep = self._capture_buffers(w, h, opt, p_real)
-        rc = _lib.glf_image_processing_u16_capture(self._ctx, C.byref(opt), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
-                                                   C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if want_float else None,
-                                                   lam.ctypes.data_as(C.c_void_p), C.byref(st), C.byref(cap) if cap else None)
-        self._check(rc, "image_processing_u16")
-        self.stream.synchronize()
-        info = dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=st.eig.outer_its, inner_its_total=st.eig.inner_its_total,
-                    residual=st.eig.residual, row0=st.row0, row1=st.row1, ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian,
-                    ms_eigen=st.ms_eigen, ms_nystroem=st.ms_nystroem, ms_filter=st.ms_filter, ms_total=st.ms_total,
-                    nystroem_kernel_ms=st.nystroem_kernel_ms, contraction=st.contraction, nystroem_evaluated=st.nystroem_evaluated,
-                    degree_evaluated=st.degree_evaluated, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
-                    filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded, eigvals=lam[:st.m].copy())
-        if capture:
-            assert cap.ld == keep[0].shape[1], (cap.ld, keep[0].shape)
-            info["capture"] = dict(phi_A=keep[0][:st.p], phi=keep[1], degree=keep[2][:st.p].copy(), ld=int(cap.ld))
-        return out, zf, info
+        return out, zf, self._run("glf_image_processing_u16_capture", "image_processing_u16", opt, d_img, out, zf, capture)
 
-    def _capture_buffers(self, w, h, opt, p_real):
-        """glf_capture with phi_A, phi (this rank's rows) and the degree vector, and the buffers it points to."""
+    def _capture_buffers(self, w, h, opt, p_real, grey=False):
+        """glf_capture with phi_A, phi (this rank's rows) and the degree vector -- grey: also c = Phi^T y and the correction -- and
+        the buffers it points to. The realised sample count and the row stride are known before the call."""
         torch = self.torch
         m_req = int(opt.num_eigvals) if 0 < opt.num_eigvals < p_real else max(1, p_real - 1)
         ld = 32
         while ld < min(m_req, 256):
             ld *= 2
-        rows = shard_rows(h, *self._native_rank) if getattr(self, "_native_rank", None) else (0, h)
+        if self._comm_keepalive:
+            rows = shard_rows(h, self._comm_keepalive.rank, self._comm_keepalive.size)
+        elif getattr(self, "_native_rank", None):
+            rows = shard_rows(h, *self._native_rank)
+        else:
+            rows = (0, h)
+        npix = (rows[1] - rows[0]) * w
         with torch.cuda.stream(self.stream):
             phi_A = torch.zeros(((p_real + 63) // 64 * 64, ld), dtype=torch.float32, device=self.device)
-            phi = torch.zeros(((rows[1] - rows[0]) * w, ld), dtype=torch.float32, device=self.device)
+            phi = torch.zeros((npix, ld), dtype=torch.float32, device=self.device)
+            corr = torch.zeros(npix, dtype=torch.float32, device=self.device) if grey else None
         deg_host = np.zeros(p_real, dtype=np.float64)
-        cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(), None,
-                      deg_host.ctypes.data, None, 0)
-        return cap, (phi_A, phi, deg_host)
+        c_host = np.zeros(ld, dtype=np.float64) if grey else None
+        cap = Capture(C.sizeof(Capture), 0, phi_A.data_ptr(), phi_A.numel(), phi.data_ptr(), phi.numel(),
+                      c_host.ctypes.data if grey else None, deg_host.ctypes.data, corr.data_ptr() if grey else None,
+                      corr.numel() if grey else 0)
+        return cap, (phi_A, phi, deg_host, c_host, corr)
+
+
+@functools.lru_cache(maxsize=256)
+def _realised(w, h, req, random):
+    return max(req, 1) * 2 + 64 if random else int(Sampling(w, h, req).size)
 
 
 def _realised_samples(w, h, opt):
-    """An upper bound of the sample count a call realises (the size of its eigenvalue array)."""
+    """An upper bound of the sample count a call realises (the size of its eigenvalue array): hpc/sampling.c's rule for the
+    uniform sampler (which rewrites the request), the request with margin for the random one; cached per image size and request."""
     req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
-    return int(Sampling(w, h, req).size) if not getattr(opt, "sampling", 0) else max(req, 1) * 2 + 64
+    return _realised(w, h, req, bool(getattr(opt, "sampling", 0)))
+
+
+def _info(st, lam):
+    """The info dict of one call (one rank) from its glf_stats and the eigenvalue array."""
+    e = st.eig
+    return dict(p=st.p, m=st.m, alpha=st.alpha, outer_its=e.outer_its, inner_its_total=e.inner_its_total, residual=e.residual,
+                ms_affinity=st.ms_affinity, ms_laplacian=st.ms_laplacian, ms_eigen=st.ms_eigen, ms_nystroem=st.ms_nystroem,
+                ms_filter=st.ms_filter, ms_total=st.ms_total, nystroem_kernel_ms=st.nystroem_kernel_ms,
+                nystroem_launches=st.nystroem_launches, row0=st.row0, row1=st.row1, contraction=st.contraction,
+                skip_exact_zeros=st.skip_exact_zeros, nystroem_evaluated=st.nystroem_evaluated, degree_evaluated=st.degree_evaluated,
+                nystroem_mfma_flops=st.nystroem_mfma_flops, nystroem_path=st.nystroem_path, matvec_path=st.matvec_path,
+                nystroem_rowpass_launches=st.nystroem_rowpass_launches, nystroem_rowpass_ms=st.nystroem_rowpass_ms,
+                nystroem_rowpass_flops=st.nystroem_rowpass_flops, nystroem_colpass_launches=st.nystroem_colpass_launches,
+                nystroem_colpass_ms=st.nystroem_colpass_ms, nystroem_colpass_flops=st.nystroem_colpass_flops, rank_terms=st.rank_terms,
+                filter_fused=st.filter_fused, eigen_sharded=st.eigen_sharded, matvecs=e.matvecs, matvec_ms=e.matvec_ms,
+                matvec_bytes=e.matvec_bytes, narrow_sweeps=e.narrow_sweeps, eigvals=lam[:st.m].copy())
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
 
 
 def image_processing_batch(contexts, d_imgs, opt=None):

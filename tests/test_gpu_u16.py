@@ -6,7 +6,7 @@ path in every filter mode on both samplers, the 8-bit equivalence (257 g at h_va
 than one 8-bit level that only the 16-bit route keeps, 2048^2 sampled rows, the context's bookkeeping and the declines.
 
 Tolerances. The only arithmetic the 16-bit kernel adds to the 8-bit one is the f32 rounding of dv^2 (up to 32 bits): the exponent's
-relative error is ~2^-23 and every kernel entry stays within ~1e-7 of the fp64 value (u16.hip), so K_A and D_A are held to 1e-6 of
+relative error is ~2^-23 and every kernel entry stays within ~1e-7 of the fp64 value (entrywise.hip), so K_A and D_A are held to 1e-6 of
 their maxima like the 8-bit and colour kernels, and Phi and the corrections to the 1e-5 relative L2 the colour tests use."""
 import numpy as np
 import pytest
