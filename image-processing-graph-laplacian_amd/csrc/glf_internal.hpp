@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/glf.h"
+#include "band_plan.hpp"
 
 // Workspace pool of a context: device blocks released by DevBuf are kept and handed out again
 // (same stream => ordering is safe). hipMalloc / hipFree of the multi-GB buffers on every call cost
@@ -41,6 +42,7 @@ struct glf_tuning {
     bool zmfma_groups = false;   // ZMFMA_GROUPS: degree row contraction in groups of five m-tiles (two n-tiles per wave) even when ten fit one wave
     int eig_shard = 0;           // EIG_SHARD: 0 auto (row-sharded eigen-solve unless the operator is in band form), 1 sharded, 2 replicated
     bool no_fused_filter = false; // NO_FUSED_FILTER: band form writes Phi and the filter runs as its own stage (k_apply_filter)
+    bool band_noskip = false;    // BAND_NOSKIP: band-form Nystroem kernel executes every (row pair, half-block) of its workgroup's range, the exact zeros outside a wave's window included (same bits, more work: the check that the schedule loses no unit)
     bool no_narrow = false;      // NO_NARROW: block PCG applies the operator to all columns of the block even when few still iterate
     bool verbose = false;        // VERBOSE: log every outer iteration on stderr (the reference does, hpc/inverse_power_it.c:164-181)
 };
@@ -354,6 +356,17 @@ __device__ __forceinline__ void lds_dma_16B(const void *gptr, unsigned lds_byte_
                  "global_load_lds_dwordx4 %0, off"
                  :
                  : "v"(gptr), "s"(lds_byte_offset)
+                 : "memory");
+}
+// the same with the global address as a wave-uniform base (scalar registers) + a 32-bit byte offset per lane: no 64-bit vector
+// address arithmetic per instruction when only the base changes between calls
+__device__ __forceinline__ void lds_dma_16B_base(const void *gbase_uniform, unsigned lane_byte_offset, unsigned lds_byte_offset)
+{
+    asm volatile("s_mov_b32 m0, %2\n\t"
+                 "s_nop 0\n\t"
+                 "global_load_lds_dwordx4 %0, %1"
+                 :
+                 : "v"(lane_byte_offset), "s"(gbase_uniform), "s"(lds_byte_offset)
                  : "memory");
 }
 __device__ __forceinline__ void lds_dma_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }

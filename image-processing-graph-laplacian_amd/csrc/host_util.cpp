@@ -1,5 +1,5 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
-// synthetic benchmark images. No device code.
+// synthetic benchmark images, the geometry and schedule of the band form. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/glf.h"
+#include "band_plan.hpp"
 
 namespace {
 
@@ -145,6 +146,61 @@ int glf_synth_image(uint8_t *out, int width, int height, uint64_t seed)
     return GLF_OK;
 }
 
+// The schedule of k_band's pixel-target instantiations, restated on the host from the same windows and the same pairing helpers
+// (band_plan.hpp): what every wave executes, so that coverage can be checked without relying on the parity of outputs whose
+// edge entries are below 2^-40 of the largest term.
+int glf_band_plan(const int *rows, int nr, const int *cols, int nc, float h_loc, int width, int height, int row_begin, int row_end,
+                  int pair_stride, int *rad, int *tile_px, int *ntiles, int *first_row, unsigned *units, uint64_t *ksteps)
+{
+    if (!rows || !cols || nr <= 0 || nc <= 0 || width <= 0 || height <= 0 || row_begin < 0 || row_end > height || row_begin > row_end ||
+        !(h_loc > 0.f))
+        return GLF_ERR_INVALID;
+    const float s_loc = (float)(1.4426950408889634 / ((double)h_loc * (double)h_loc)); // (kernel_coef's)
+    glf::BandGeom geom;
+    if (!geom.init(rows, nr, cols, nc, (double)s_loc)) return GLF_ERR_UNSUPPORTED;
+    static_assert(glf::BAND_NW == GLF_BAND_WG_ROWS, "glf.h documents the rows of a workgroup");
+    const int tpx = 32 * glf::BAND_PB, nt = (width + tpx - 1) / tpx, NW = glf::BAND_NW;
+    if (rad) *rad = geom.rad;
+    if (tile_px) *tile_px = tpx;
+    if (ntiles) *ntiles = nt;
+    std::vector<unsigned> win((size_t)geom.rad * nt);
+    for (int dr = 0; dr < geom.rad; ++dr)
+        for (int t = 0; t < nt; ++t) win[(size_t)dr * nt + t] = geom.window(t * tpx, std::min(width, (t + 1) * tpx) - 1, dr, glf::BAND_HALF_SHIFT);
+    uint64_t steps = 0;
+    for (int trow0 = row_begin; trow0 < row_end; trow0 += NW) {
+        const int ntw = std::min(NW, row_end - trow0);
+        int alo = 0xFFFF, ahi = -1;
+        for (int w = 0; w < ntw; ++w) {
+            const unsigned rb = geom.band_of(trow0 + w);
+            if (glf::band_win_live(rb)) {
+                alo = std::min(alo, (int)(rb & 0xFFFFu));
+                ahi = std::max(ahi, (int)(rb >> 16));
+            }
+        }
+        const int nb = std::min(glf::BAND_MAXROWS, std::max(0, ahi - alo + 1)), npairs = (nb + glf::BAND_PAIR - 1) / glf::BAND_PAIR;
+        if (units && npairs > pair_stride) return GLF_ERR_INVALID;
+        for (int w = 0; w < ntw; ++w) {
+            const size_t ro = (size_t)(trow0 + w - row_begin);
+            if (first_row) first_row[ro] = nb > 0 ? alo : -1;
+            for (int t = 0; t < nt; ++t) {
+                unsigned *u = units ? units + (ro * nt + t) * (size_t)pair_stride : nullptr;
+                for (int j = 0; u && j < pair_stride; ++j) u[j] = glf::BAND_EMPTY;
+                for (int j = 0; j < npairs; ++j) {
+                    unsigned h = glf::BAND_EMPTY;
+                    for (int i = glf::BAND_PAIR * j; i < std::min(nb, glf::BAND_PAIR * (j + 1)); ++i) {
+                        const int dr = std::abs(trow0 + w - geom.rows[alo + i]);
+                        h = glf::band_win_hull(h, dr < geom.rad ? win[(size_t)dr * nt + t] : glf::BAND_EMPTY);
+                    }
+                    if (u) u[j] = h;
+                    if (glf::band_win_live(h)) steps += (h >> 16) - (h & 0xFFFFu) + 1;
+                }
+            }
+        }
+    }
+    if (ksteps) *ksteps = steps;
+    return GLF_OK;
+}
+
 } // extern "C"
 
 // ---- low-rank factor of the photometric table -----------------------------------------------------------------
@@ -258,6 +314,44 @@ double photometric_factor_error(double s_val, const std::vector<double> &F, int 
             worst = std::max(worst, std::fabs(x - std::exp2(-s_val * (double)(v - w) * (double)(v - w))));
         }
     return worst;
+}
+
+// ---- band form: radius and windows -----------------------------------------------------------------------------
+bool BandGeom::init(const int *grows, int nr, const int *gcols, int nc, double s_loc)
+{
+    if (!(s_loc > 0.0)) return false;
+    D2 = 40.5 / s_loc; // 2^15 E(dr) E(dc) <= 2^-25.5: a zero f16 (hi, lo) pair whatever P is
+    const double rr = std::floor(std::sqrt(D2)) + 1.0;
+    if (rr > BAND_RMAX) return false;
+    rad = (int)rr; // first integer distance with d^2 >= D2
+    rows.assign(grows, grows + nr);
+    cols.assign(gcols, gcols + nc);
+    // largest |dc| inside the circle at row distance dr: dc^2 < D2 - dr^2
+    dcmax.assign(rad, -1);
+    for (int dr = 0; dr < rad; ++dr) {
+        const double rem = D2 - (double)dr * dr;
+        int d = (int)std::floor(std::sqrt(std::max(0.0, rem)));
+        while (d > 0 && (double)d * d >= rem) --d;
+        dcmax[dr] = rem > 0.0 ? d : -1;
+    }
+    return true;
+}
+
+unsigned BandGeom::band_of(int r) const
+{
+    const int lo = (int)(std::lower_bound(rows.begin(), rows.end(), r - rad + 1) - rows.begin());
+    const int hi = (int)(std::upper_bound(rows.begin(), rows.end(), r + rad - 1) - rows.begin()) - 1;
+    if (hi < lo) return 1u;
+    return (unsigned)lo | ((unsigned)hi << 16);
+}
+
+unsigned BandGeom::window(int cmin, int cmax, int dr, int shift) const
+{
+    if (dcmax[dr] < 0) return BAND_EMPTY;
+    const int lo = (int)(std::lower_bound(cols.begin(), cols.end(), cmin - dcmax[dr]) - cols.begin());
+    const int hi = (int)(std::upper_bound(cols.begin(), cols.end(), cmax + dcmax[dr]) - cols.begin()) - 1;
+    if (hi < lo) return BAND_EMPTY;
+    return (unsigned)(lo >> shift) | ((unsigned)(hi >> shift) << 16);
 }
 
 } // namespace glf

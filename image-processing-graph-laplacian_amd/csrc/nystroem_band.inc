@@ -14,9 +14,11 @@
 //   over the grid rows: it depends on the target and the sample column only), split into f16 hi + lo, and contracted
 //   with the (hi, lo) fragments of Psi -- staged once per workgroup by LDS-DMA -- on v_mfma_f32_32x32x16_f16.
 // No intermediate reaches HBM; the operand is 21.8 MB per 64 columns.
+// With the pixels as targets the unit is finer: a half-block of 8 sample columns in two consecutive band rows per k-step (the two
+// lane-halves of the MFMA's k), which covers the circle with 0.835 of the k-steps (see k_band and band_plan.hpp).
 //
-// Tables (host-built, BandTables): win[dr][tile] = the blocks of sample columns whose entries can be non-zero for a tile
-// of targets at row distance dr (the circle narrows with dr); rowband[r] = the grid rows within the radius of target row r.
+// Tables (host-built, BandTables): win[dr][tile] = the blocks (sample targets) or half-blocks (pixel targets) of sample columns whose
+// entries can be non-zero for a tile of targets at row distance dr (the circle narrows with dr); rowband[r] = the grid rows within the radius of target row r.
 
 #ifndef BAND_SETPRIO
 #define BAND_SETPRIO 1
@@ -32,12 +34,7 @@ constexpr unsigned BAND_PSTRIDE = 4u * BAND_PCOPY; // bytes between consecutive 
 #define BAND_GROWS 4
 #endif
 constexpr int BAND_G = BAND_GROWS;         // grid rows staged together (one barrier per stage)
-#ifndef BAND_MAXROWS_X
-#define BAND_MAXROWS_X 128
-#endif
-constexpr int BAND_MAXROWS = BAND_MAXROWS_X; // grid rows within the radius of one target row
-constexpr int BAND_RMAX = 1023;   // largest radius (the Ec table sits in LDS)
-constexpr unsigned BAND_EMPTY = 0x0000FFFFu; // lo = 0xFFFF, hi = 0: no block
+// (BAND_MAXROWS, BAND_RMAX, BAND_EMPTY, BAND_PB, BAND_NW and the window helpers: band_plan.hpp, shared with the host-side plan)
 __host__ __device__ constexpr inline int band_chunk_bytes(int mb) { return mb * 2048 + 256; }
 constexpr int BAND_WB = 6; // sample targets: blocks of a grid row staged together (row-major stage order)
 __host__ __device__ constexpr inline int band_stage_chunks(bool samples)
@@ -153,10 +150,16 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                                                    const float *__restrict__ X, int x_ld, const double *__restrict__ degree, float alpha,
                                                    unsigned long long *__restrict__ evaluated, int row_end, const float *__restrict__ fw,
                                                    float fgain, float fysub, uint8_t *__restrict__ fout, float *__restrict__ fzf,
-                                                   float *__restrict__ fcorr, int64_t fpix0, BandSignals fsig)
+                                                   float *__restrict__ fcorr, int64_t fpix0, BandSignals fsig, int noskip)
 {
     static_assert(!SAMPLES || PB == 1, "sample targets: one tile of 32 per wave");
     constexpr int LD = 32 * MB, CHB = band_chunk_bytes(MB), NPIECE = MB * 2 + 1; // (the last piece is the 256-byte tail)
+    // Pixel targets: a unit of work is (pair of consecutive band rows, half-block of 8 sample columns): lanes 0 - 31 of the MFMA's
+    // k hold the 8 columns in the pair's first row, lanes 32 - 63 the same columns in its second row. The pairs are aligned to the
+    // workgroup's first band row, so every wave shares a stage; windows and positions `blk` are in half-blocks. The circle is covered
+    // at 8 columns x 1 row instead of 16 x 1: 0.835 of the k-steps. A half outside its own window generates exact zeros.
+    // Sample targets: (one band row, block of 16 columns) as before.
+    constexpr int RP = SAMPLES ? 1 : BAND_PAIR;
     extern __shared__ __attribute__((aligned(16))) unsigned char bdyn[];
     float *plut = reinterpret_cast<float *>(bdyn); // [256][32]: the photometric table, one copy per bank
     unsigned char *stage = bdyn + 256 * BAND_PSTRIDE; // [BAND_NBUF][BAND_G][CHB]
@@ -190,29 +193,29 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     }
     for (int i = tid; i <= rad; i += NW * 64) elut[i] = btab[256 + i];
     for (int i = tid; i < 16 * ksc; i += NW * 64) gcs[i] = i < nc ? gcol[i] : -(1 << 28);
-    for (int i = tid; i < nb; i += NW * 64) {
-        const int ra = grow[alo + i];
-        unsigned lo = 0xFFFFu, hi = 0u;
+    // per unit of RP band rows (entry RP u of the arrays): what each wave needs of it -- the hull of its rows' windows -- and what any does
+    for (int i0 = RP * tid; i0 < nb; i0 += RP * NW * 64) {
+        unsigned g = BAND_EMPTY;
         for (int w = 0; w < NW; ++w) {
             const int rw = w < ntw ? (SAMPLES ? grow[trow0 + w] : trow0 + w) : (1 << 28);
-            const int dr = abs(rw - ra);
-            const unsigned u = dr < rad ? win[(size_t)dr * ntiles + tile] : BAND_EMPTY;
-            er_s[w * BAND_MAXROWS + i] = dr < rad ? btab[256 + rad + 1 + dr] : 0.f;
-            wwin[w * BAND_MAXROWS + i] = u;
-            if ((u & 0xFFFFu) <= (u >> 16)) {
-                lo = min(lo, u & 0xFFFFu);
-                hi = max(hi, u >> 16);
+            unsigned u = BAND_EMPTY;
+            for (int i = i0; i < min(i0 + RP, nb); ++i) {
+                const int dr = abs(rw - grow[alo + i]);
+                er_s[w * BAND_MAXROWS + i] = dr < rad ? btab[256 + rad + 1 + dr] : 0.f;
+                u = band_win_hull(u, dr < rad ? win[(size_t)dr * ntiles + tile] : BAND_EMPTY);
             }
+            wwin[w * BAND_MAXROWS + i0] = u;
+            g = band_win_hull(g, u);
         }
-        gwin[i] = lo | (hi << 16);
+        gwin[i0] = g;
     }
     lds_dma_drain(); // (this wave's pieces of the photometric table)
     __syncthreads();
     if (tid == 0) {
         int blo = 0xFFFF, bhi = -1;
-        for (int i = 0; i < nb; ++i) {
+        for (int i = 0; i < nb; i += RP) {
             const unsigned u = gwin[i];
-            if ((u & 0xFFFFu) <= (u >> 16)) {
+            if (band_win_live(u)) {
                 blo = min(blo, (int)(u & 0xFFFFu));
                 bhi = max(bhi, (int)(u >> 16));
             }
@@ -249,18 +252,16 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[b][j][q] = 0.f;
 
-    // stages: (block, group of BAND_G band rows) in block-major order; a stage no wave needs anything of is passed over
+    // stages: ((half-)block, group of BAND_G units of RP band rows) in block-major order; a stage no wave needs anything of is passed
+    // over (noskip: none is, and every wave executes every unit of the workgroup's range -- the skipped ones add exact zeros)
     auto stage_live = [&](int blk, int g0) -> bool {
-        bool any = false;
-        for (int i = g0; i < min(g0 + BAND_G, nb); ++i) {
-            const unsigned u = gwin[i];
-            any = any || (blk >= (int)(u & 0xFFFFu) && blk <= (int)(u >> 16));
-        }
+        bool any = noskip != 0;
+        for (int i = g0; i < min(g0 + RP * BAND_G, nb); i += RP) any = any || band_win_has(gwin[i], blk);
         return any;
     };
     auto advance = [&](int &blk, int &g0) { // to the next live stage (blk > Bhi: none)
         for (;;) {
-            g0 += BAND_G;
+            g0 += RP * BAND_G;
             if (g0 >= nb) {
                 g0 = 0;
                 ++blk;
@@ -268,16 +269,30 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
             if (blk > Bhi || stage_live(blk, g0)) return;
         }
     };
+    // pixel targets: byte offsets of a lane's 16 bytes within a DMA instruction, from the chunk of the pair's first row: the piece's
+    // half for lanes 0 - 31 and the same of the next band row (ksc chunks on) for lanes 32 - 63; of the tail, lanes 0 - 1 and 2 - 3
+    const unsigned dma_off_row = 16u * (unsigned)l31, dma_off = dma_off_row + (half ? (unsigned)ksc * CHB : 0u);
+    const unsigned dma_toff_row = 16u * (unsigned)(lane & 1), dma_toff = dma_toff_row + ((lane >> 1) & 1 ? (unsigned)ksc * CHB : 0u);
     auto issue = [&](int blk, int g0, int buf) -> int { // returns the DMA instructions this wave issued
         int n = 0;
         for (int q = wave; q < BAND_G * NPIECE; q += NW) { // (wave-uniform)
-            const int slot = q / NPIECE, k = q % NPIECE, i = g0 + slot;
+            const int slot = q / NPIECE, k = q % NPIECE, i = g0 + RP * slot;
             if (i >= nb) break;
-            const unsigned u = gwin[i];
-            if (blk < (int)(u & 0xFFFFu) || blk > (int)(u >> 16)) continue;
-            const unsigned char *src = chunks + ((size_t)(alo + i) * ksc + blk) * CHB + k * 1024 + lane * 16;
+            if (!noskip && !band_win_has(gwin[i], blk)) continue;
             const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset_of(stage + (size_t)(buf * BAND_G + slot) * CHB + k * 1024));
-            if (k < NPIECE - 1 || lane < 16) lds_dma_16B(src, dst);
+            if constexpr (SAMPLES) {
+                const unsigned char *src = chunks + ((size_t)(alo + i) * ksc + blk) * CHB + k * 1024 + lane * 16;
+                if (k < NPIECE - 1 || lane < 16) lds_dma_16B(src, dst);
+            } else {
+                // the slot is assembled by the DMA itself (it writes dst + 16 lane from per-lane addresses): lanes 0 - 31 bring half
+                // (blk & 1) of block blk >> 1 of band row i, lanes 32 - 63 the same half of row i + 1; of the tail, 32 bytes
+                // of sample values each. A row past the end of the band: row i again (its Er is 0).
+                // (wave-uniform base + per-lane 32-bit offsets fixed for the launch: one vector instruction per DMA)
+                const unsigned char *ch = chunks + ((size_t)(alo + i) * ksc + (blk >> 1)) * CHB + k * 1024;
+                const bool both = i + 1 < nb;
+                if (k < NPIECE - 1) lds_dma_16B_base(ch + 512 * (blk & 1), both ? dma_off : dma_off_row, dst);
+                else if (lane < 4) lds_dma_16B_base(ch + 32 * (blk & 1), both ? dma_toff : dma_toff_row, dst);
+            }
             ++n;
         }
         return n;
@@ -461,20 +476,22 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                 cur_blk = blk;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const int cb = gcs[16 * blk + 8 * half + e];
+                    const int cb = SAMPLES ? gcs[16 * blk + 8 * half + e] : gcs[8 * blk + e]; // (pixel targets: the same 8 columns in both lane-halves)
 #pragma unroll
                     for (int b = 0; b < PB; ++b) ec[b][e >> 1][e & 1] = elut[min(abs(tc[b] - cb), rad)];
                 }
             }
 #pragma unroll 1
             for (int slot = 0; slot < BAND_G; ++slot) {
-                const int i = g0 + slot;
+                const int i = g0 + RP * slot;
                 if (i >= nb) break;
                 const unsigned u = (unsigned)__builtin_amdgcn_readfirstlane((int)wwin[wave * BAND_MAXROWS + i]);
-                if (blk < (int)(u & 0xFFFFu) || blk > (int)(u >> 16)) continue;
+                if (!noskip && !band_win_has(u, blk)) continue;
                 ++nsteps;
                 const unsigned char *sl = stage + (size_t)(buf * BAND_G + slot) * CHB;
-                const float era = er_s[wave * BAND_MAXROWS + i];
+                // (pixel targets: each lane-half its own row of the pair; 0 past the end of the band)
+                const int ie = SAMPLES ? i : i + half;
+                const float era = ie < nb ? er_s[wave * BAND_MAXROWS + ie] : 0.f;
                 kstep(sl, era, ec);
             }
         }
@@ -612,7 +629,8 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
 }
 
 // Host-built geometry of the band for one sample grid and kernel: which grid rows lie within the radius of a target row, and
-// which blocks of 16 sample columns can reach a tile of targets at a given row distance.
+// which blocks of sample columns can reach a tile of targets at a given row distance (BandGeom, band_plan.hpp) -- half-blocks
+// of 8 columns for the pixel targets (win_px), blocks of 16 for the sample targets (win_s).
 struct BandTables {
     int rad = 0, nr = 0, nc = 0, ksc = 0, width = 0;
     int tile_px = 0, ntiles_px = 0, ntiles_s = 0; // pixels per wave tile (32 PB); wave tiles per image row / per grid row
@@ -631,13 +649,8 @@ struct BandTables {
     std::vector<double> pairs_dr;   // per row distance: (target column, sample column) pairs inside the circle, pixels as targets
     std::vector<double> pairs_dr_s; // ... the samples as targets
     std::vector<int> hrows;
-    unsigned band_of(int r) const // grid rows with |r - R_a| < rad (the rows ascend): lo | hi << 16 (lo > hi: none)
-    {
-        const int lo = (int)(std::lower_bound(hrows.begin(), hrows.end(), r - rad + 1) - hrows.begin());
-        const int hi = (int)(std::upper_bound(hrows.begin(), hrows.end(), r + rad - 1) - hrows.begin()) - 1;
-        if (hi < lo) return 1u;
-        return (unsigned)lo | ((unsigned)hi << 16);
-    }
+    BandGeom geom;
+    unsigned band_of(int r) const { return geom.band_of(r); }
     double pairs_rows(const std::vector<double> &per_dr, int r) const
     {
         const unsigned rb = band_of(r);
@@ -667,11 +680,8 @@ struct BandTables {
     int build(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, int width_, int height, int tile_px_, bool want_px, bool want_s)
     {
         ok = false;
-        if (!(coef.s_loc > 0.f)) return GLF_ERR_UNSUPPORTED;
-        const double D2 = 40.5 / (double)coef.s_loc; // 2^15 E(dr) E(dc) <= 2^-25.5: a zero f16 (hi, lo) pair whatever P is
-        const double rr = std::floor(std::sqrt(D2)) + 1.0;
-        if (rr > BAND_RMAX) return GLF_ERR_UNSUPPORTED;
-        rad = (int)rr; // first integer distance with d^2 >= D2
+        if (!geom.init(g.rows.data(), g.nr, g.cols.data(), g.nc, (double)coef.s_loc)) return GLF_ERR_UNSUPPORTED;
+        rad = geom.rad;
         nr = g.nr;
         nc = g.nc;
         ksc = (int)ceil_div(nc, 16);
@@ -699,21 +709,7 @@ struct BandTables {
         for (int i = 0; i < 256 * BAND_PCOPY; ++i) reinterpret_cast<float *>(h.data())[o_pexp + i] = htab[i / BAND_PCOPY];
         for (int a = 0; a < nr; ++a) h[o_grid + a] = (unsigned)g.rows[a];
         for (int b = 0; b < nc; ++b) h[o_grid + nr + b] = (unsigned)g.cols[b];
-        // largest |dc| inside the circle at row distance dr: dc^2 < D2 - dr^2
-        std::vector<int> dcmax(rad);
-        for (int dr = 0; dr < rad; ++dr) {
-            const double rem = D2 - (double)dr * dr;
-            int d = (int)std::floor(std::sqrt(std::max(0.0, rem)));
-            while (d > 0 && (double)d * d >= rem) --d;
-            dcmax[dr] = rem > 0.0 ? d : -1;
-        }
-        auto window = [&](int cmin, int cmax, int dr) -> unsigned {
-            if (dcmax[dr] < 0) return BAND_EMPTY;
-            const int lo = (int)(std::lower_bound(g.cols.begin(), g.cols.end(), cmin - dcmax[dr]) - g.cols.begin());
-            const int hi = (int)(std::upper_bound(g.cols.begin(), g.cols.end(), cmax + dcmax[dr]) - g.cols.begin()) - 1;
-            if (hi < lo) return BAND_EMPTY;
-            return (unsigned)(lo >> 4) | ((unsigned)(hi >> 4) << 16);
-        };
+        const std::vector<int> &dcmax = geom.dcmax;
         int maxband = 0;
         if (want_px) {
             for (int r = 0; r < height; ++r) {
@@ -722,7 +718,7 @@ struct BandTables {
                 maxband = std::max(maxband, (int)(rb >> 16) - (int)(rb & 0xFFFF) + 1);
             }
             for (int dr = 0; dr < rad; ++dr)
-                for (int t = 0; t < ntiles_px; ++t) h[o_win_px + (size_t)dr * ntiles_px + t] = window(t * tile_px, std::min(width, (t + 1) * tile_px) - 1, dr);
+                for (int t = 0; t < ntiles_px; ++t) h[o_win_px + (size_t)dr * ntiles_px + t] = geom.window(t * tile_px, std::min(width, (t + 1) * tile_px) - 1, dr, BAND_HALF_SHIFT);
             pairs_dr.assign(rad, 0.0);
             for (int dr = 0; dr < rad; ++dr) {
                 if (dcmax[dr] < 0) continue;
@@ -738,7 +734,7 @@ struct BandTables {
                 maxband = std::max(maxband, (int)(rb >> 16) - (int)(rb & 0xFFFF) + 1);
             }
             for (int dr = 0; dr < rad; ++dr)
-                for (int t = 0; t < ntiles_s; ++t) h[o_win_s + (size_t)dr * ntiles_s + t] = window(g.cols[t * 32], g.cols[std::min(nc, (t + 1) * 32) - 1], dr);
+                for (int t = 0; t < ntiles_s; ++t) h[o_win_s + (size_t)dr * ntiles_s + t] = geom.window(g.cols[t * 32], g.cols[std::min(nc, (t + 1) * 32) - 1], dr, BAND_BLOCK_SHIFT);
             pairs_dr_s.assign(rad, 0.0);
             for (int dr = 0; dr < rad; ++dr) {
                 if (dcmax[dr] < 0) continue;
@@ -799,13 +795,6 @@ static int band_tables_cached(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, 
     return GLF_OK;
 }
 
-#ifndef BAND_PB_X
-#define BAND_PB_X 2
-#endif
-#ifndef BAND_NW_X
-#define BAND_NW_X 8
-#endif
-constexpr int BAND_PB = BAND_PB_X, BAND_NW = BAND_NW_X;     // pixel targets: 64 columns per wave, 8 image rows per workgroup
 #ifndef BAND_NW_S_X
 #define BAND_NW_S_X 8
 #endif
@@ -834,7 +823,7 @@ static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_i
                        bt.ksc, bt.tab(), bt.pexp(), bt.rad, bt.rowband_px(), bt.win_px(), bt.ntiles_px, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster,
                        cpartial, (const float *)nullptr, 0, (const double *)nullptr, 0.f, evaluated, row0 + nrows, flt ? flt->w : (const float *)nullptr,
                        flt ? flt->gain : 0.f, flt ? flt->ysub : 0.f, flt ? flt->out : (uint8_t *)nullptr, flt ? flt->zf : (float *)nullptr,
-                       flt ? flt->corr : (float *)nullptr, pix0, flt ? flt->sig : BandSignals{});
+                       flt ? flt->corr : (float *)nullptr, pix0, flt ? flt->sig : BandSignals{}, ctx->tune.band_noskip ? 1 : 0);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -852,7 +841,7 @@ static int launch_band_samples(glf_ctx *ctx, const BandTables &bt, const uint8_t
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW_S * 64), lds, ctx->stream, svals, bt.nc, a0, bt.grow(), bt.gcol(), bt.nr, bt.nc, bt.ksc,
                        bt.tab(), bt.pexp(), bt.rad, bt.rowband_s(), bt.win_s(), bt.ntiles_s, chunks, inv, Y, y_ld, (const uint8_t *)nullptr,
                        (const uint32_t *)nullptr, 0u, 1, (double *)nullptr, X, x_ld, degree, alpha, evaluated, a0 + nrows, (const float *)nullptr, 0.f,
-                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0, BandSignals{});
+                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0, BandSignals{}, 0);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

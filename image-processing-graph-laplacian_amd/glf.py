@@ -44,7 +44,7 @@ RCCL_ID_BYTES = 128
 EXPORTS = [
     "glf_strerror", "glf_ctx_create", "glf_ctx_destroy", "glf_ctx_synchronize", "glf_ctx_last_error",
     "glf_ctx_device_info", "glf_ctx_set_tuning", "glf_ctx_set_comm", "glf_rccl_unique_id", "glf_ctx_set_comm_rccl", "glf_ctx_comm_info", "glf_ctx_comm_counters", "glf_multi_create", "glf_multi_destroy",
-    "glf_multi_size", "glf_multi_ctx", "glf_multi_last_error", "glf_multi_image_processing", "glf_shard_rows", "glf_ctx_set_contraction", "glf_malloc", "glf_free", "glf_memcpy_h2d", "glf_memcpy_d2h",
+    "glf_multi_size", "glf_multi_ctx", "glf_multi_last_error", "glf_multi_image_processing", "glf_shard_rows", "glf_band_plan", "glf_ctx_set_contraction", "glf_malloc", "glf_free", "glf_memcpy_h2d", "glf_memcpy_d2h",
     "glf_memset", "glf_mat_create_dense", "glf_mat_create_diag", "glf_mat_destroy", "glf_mat_get_column", "glf_Sampling",
     "glf_host_free", "glf_random_vectors", "glf_synth_image", "glf_RandomSampling", "glf_ComputeAffinityMatrices",
     "glf_ComputeLaplacianMatrix", "glf_InversePowerIteration", "glf_OrthonormaliseVecs", "glf_NormaliseVecs",
@@ -262,6 +262,34 @@ def shard_rows(height, rank, size):
     return r0.value, r1.value
 
 
+BAND_WG_ROWS = 8
+
+
+def band_plan(rows, cols, width, height, h_loc=40.0, row_begin=0, row_end=None, pair_stride=64):
+    """glf_band_plan: the schedule of the band-form Nystroem kernel for the image rows [row_begin, row_end) and the sample
+    grid rows x cols. Returns a dict: rad, tile_px, ntiles, first_row [rows], units [rows][ntiles][pair_stride] (lo | hi << 16
+    in half-blocks of 8 sample columns; lo > hi: none) and ksteps. Host only."""
+    rows = np.ascontiguousarray(rows, dtype=np.int32)
+    cols = np.ascontiguousarray(cols, dtype=np.int32)
+    row_end = height if row_end is None else row_end
+    rad, tile_px, ntiles, ksteps = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+    ip, up = C.POINTER(C.c_int), C.POINTER(C.c_uint)
+
+    def call(first_row, units):
+        rc = _lib.glf_band_plan(rows.ctypes.data_as(ip), C.c_int(rows.size), cols.ctypes.data_as(ip), C.c_int(cols.size), C.c_float(h_loc),
+                                C.c_int(width), C.c_int(height), C.c_int(row_begin), C.c_int(row_end), C.c_int(pair_stride),
+                                C.byref(rad), C.byref(tile_px), C.byref(ntiles), first_row, units, C.byref(ksteps))
+        if rc != OK:
+            raise GlfError(rc, "band_plan(%d x %d, grid %d x %d)" % (width, height, rows.size, cols.size))
+    call(None, None)   # (the sizes)
+    n = max(row_end - row_begin, 0)
+    first_row = np.empty(n, dtype=np.int32)
+    units = np.empty((n, ntiles.value, pair_stride), dtype=np.uint32)
+    call(first_row.ctypes.data_as(ip), units.ctypes.data_as(up))
+    return {"rad": rad.value, "tile_px": tile_px.value, "ntiles": ntiles.value, "first_row": first_row, "units": units,
+            "ksteps": int(ksteps.value)}
+
+
 def device_tensor_from_ptr(ptr, count, dtype, device):
     """Zero-copy torch view of `count` elements at device address `ptr`."""
     iface = {"shape": (count,), "typestr": "<f8" if dtype == torch.float64 else "<f4",
@@ -459,7 +487,7 @@ class Context:
     def synchronize(self):
         self._check(_lib.glf_ctx_synchronize(self._ctx))
 
-    TUNING_KEYS = ("NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "VERBOSE")
+    TUNING_KEYS = ("NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "BAND_NOSKIP", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "VERBOSE")
 
     def set_tuning(self, **kw):
         """glf_ctx_set_tuning: e.g. set_tuning(NYS_PATH="grid", MV_PATH="dense"); None / "" / "auto" = the default choice."""

@@ -66,7 +66,7 @@ int glf_ctx_device_info(const glf_ctx *ctx, char *name, size_t name_len, int *nu
  * row-pass shapes, ...); the default picks by problem size. key / value (value NULL, "" or "auto" = default):
  *   NYS_PATH  band | rank | grid | direct     DEG_PATH  grid | direct     MV_PATH  band | rank | grid | dense
  *   ROWPASS, ROWPASS_OP  rt | v1     COLPASS  ws | v1     SWEEP_COLPASS  segments | samples
- *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
+ *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, BAND_NOSKIP, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
  * At context creation each key is initialised from the environment variable GLF_<KEY> (read once; nothing reads the
  * environment per call). No reference counterpart (PETSc's -ksp_type / -pc_type options database is the nearest thing). */
 int glf_ctx_set_tuning(glf_ctx *ctx, const char *key, const char *value);
@@ -146,6 +146,20 @@ int glf_ctx_set_contraction(glf_ctx *ctx, int mode);
 /* The pixel-row shard of rank `rank` of `size`: rows [*row0, *row1) = [rank*height/size, (rank+1)*height/size).
  * Host only (replaces PETSc's PETSC_DECIDE row ownership, hpc/utils.c:463-475). */
 int glf_shard_rows(int height, int rank, int size, int *row0, int *row1);
+/* Band form of the Nystroem extension (NYS_PATH band), host only: the schedule its kernel runs for the image rows
+ * [row_begin, row_end) of a width x height image whose samples are the tensor grid rows[nr] x cols[nc] (ascending), with the
+ * spatial scale h_loc. Workgroups take GLF_BAND_WG_ROWS consecutive target rows from row_begin on, one wave per row and tile of
+ * *tile_px target columns; a workgroup pairs the grid rows within the radius of its target rows from the first one on, and a
+ * wave executes, per pair, an interval of half-blocks (8 consecutive sample columns: column index >> 3). Outputs, each may be NULL:
+ *   *rad the radius in pixels, *tile_px, *ntiles = ceil(width / *tile_px)
+ *   first_row[r - row_begin]                                 first grid row of the band of r's workgroup (-1: no band)
+ *   units[((r - row_begin) * ntiles + t) * pair_stride + j]  lo | hi << 16: the half-blocks the wave of (r, t) executes of grid
+ *                                                            rows first_row + 2 j and + 2 j + 1; lo > hi: none
+ *   *ksteps  the MFMA k-steps of the launch: the sum of the intervals' lengths (x 16 x *tile_px = nystroem_evaluated)
+ * GLF_ERR_UNSUPPORTED: radius beyond what the kernel's tables hold; GLF_ERR_INVALID: a band of more than pair_stride pairs. */
+enum { GLF_BAND_WG_ROWS = 8 };
+int glf_band_plan(const int *rows, int nr, const int *cols, int nc, float h_loc, int width, int height, int row_begin, int row_end,
+                  int pair_stride, int *rad, int *tile_px, int *ntiles, int *first_row, unsigned *units, uint64_t *ksteps);
 
 /* Flat device buffers (replace MatCreate/VecCreate + MatDestroy/VecDestroy). */
 int glf_malloc(glf_ctx *ctx, void **dptr, size_t bytes);
