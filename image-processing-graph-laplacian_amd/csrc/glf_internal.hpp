@@ -43,6 +43,7 @@ struct glf_tuning {
     int eig_shard = 0;           // EIG_SHARD: 0 auto (row-sharded eigen-solve unless the operator is in band form), 1 sharded, 2 replicated
     bool no_fused_filter = false; // NO_FUSED_FILTER: band form writes Phi and the filter runs as its own stage (k_apply_filter)
     bool band_noskip = false;    // BAND_NOSKIP: band-form Nystroem kernel executes every (row pair, half-block) of its workgroup's range, the exact zeros outside a wave's window included (same bits, more work: the check that the schedule loses no unit)
+    bool pix_band = false;       // PIX_BAND: the colour and 16-bit bilateral kernels take the band form (Nystroem stage and operator) where the grey kernel would; off: entry by entry, L_A stored
     bool no_narrow = false;      // NO_NARROW: block PCG applies the operator to all columns of the block even when few still iterate
     bool verbose = false;        // VERBOSE: log every outer iteration on stderr (the reference does, hpc/inverse_power_it.c:164-181)
 };
@@ -263,7 +264,8 @@ __device__ __forceinline__ uint16_t filter_output_u16(int x, double c)
 //   Tile, tile     the degree sweep's LDS element {value, col}; outside() lies in a column no sample reaches (K = 0)
 //   Out, output    the output element of the apply kernel and its rule for channel x with its f64 correction c: the grey
 //                  d_out's rule, through f32 at 8 bits, in f64 at 16 bits
-// The factored forms over the 256 grey levels (grid, rank, band, the level-table degree) exist for Grey alone.
+// The factored forms over the 256 grey levels (grid, rank, the level-table degree) exist for Grey alone. The band form takes
+// the other two as well (k_band<.., G>: the photometric factor from dist2 and one v_exp_f32 per entry), behind the PIX_BAND key.
 enum class PixGen { Grey, Rgb, U16 };
 template <PixGen G> struct Pix;
 // one grey value per pixel, stored as T (Grey: uint8_t, U16: uint16_t): the record {row, col, v, 0}
@@ -335,6 +337,8 @@ inline int bilateral_kernel_of(PixGen g)
     return g == PixGen::Rgb ? GLF_KERNEL_BILATERAL_RGB : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16 : GLF_KERNEL_BILATERAL;
 }
 inline bool grey_levels_factor(int kernel) { return kernel != GLF_KERNEL_NLM && pixgen_of(kernel) == PixGen::Grey; }
+// the band form applies to a kernel: it factors over grey levels, or it is a colour / 16-bit bilateral kernel and PIX_BAND is set
+inline bool band_form_applies(const glf_ctx *ctx, int kernel) { return grey_levels_factor(kernel) || (ctx->tune.pix_band && pixgen_of(kernel) != PixGen::Grey); }
 template <PixGen G> constexpr size_t pix_bytes_of = sizeof(typename Pix<G>::In) * Pix<G>::NCH;
 inline size_t pix_bytes(PixGen g)
 {

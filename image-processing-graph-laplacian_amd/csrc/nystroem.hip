@@ -840,7 +840,14 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
     int rc = GLF_ERR_UNSUPPORTED;
     const PixGen gen = pixgen_of(coef.kernel);
     if (gen != PixGen::Grey) {
-        // the colour and 16-bit formats: entry by entry, f32 MFMA (no factored or split-f16 form)
+        // the colour and 16-bit formats: the band form where PIX_BAND asks for it and it applies (split f16, *path = 4), otherwise
+        // entry by entry, f32 MFMA (no grid or rank form)
+        if (ctx->tune.pix_band && !d_c) {
+            rc = nystroem_contract_grid(ctx, d_img, width, height, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, nullptr,
+                                        kernel_ms, window, entries_evaluated, mfma_flops, rowpass, path);
+            if (rc != GLF_ERR_UNSUPPORTED) return rc;
+            if (path) *path = 0;
+        }
         if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour and 16-bit kernels have no 8-bit y for Phi^T y");
         window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
         rc = gen == PixGen::Rgb

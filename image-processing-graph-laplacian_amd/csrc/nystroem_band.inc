@@ -17,6 +17,10 @@
 // With the pixels as targets the unit is finer: a half-block of 8 sample columns in two consecutive band rows per k-step (the two
 // lane-halves of the MFMA's k), which covers the circle with 0.835 of the k-steps (see k_band and band_plan.hpp).
 //
+// The colour and 16-bit bilateral kernels take the same form (k_band<.., PixGen::Rgb | U16>, behind the PIX_BAND tuning key): the
+// spatial factor, the windows and the contraction are the grey ones, and P is generated from the raw values -- dist2 of the pixel
+// policy and one v_exp_f32 per entry -- instead of gathered from the 256-level table.
+//
 // Tables (host-built, BandTables): win[dr][tile] = the blocks (sample targets) or half-blocks (pixel targets) of sample columns whose
 // entries can be non-zero for a tile of targets at row distance dr (the circle narrows with dr); rowband[r] = the grid rows within the radius of target row r.
 
@@ -41,18 +45,23 @@ __host__ __device__ constexpr inline int band_stage_chunks(bool samples)
 {
     return samples && 2 * BAND_WB > BAND_NBUF * BAND_G ? 2 * BAND_WB : BAND_NBUF * BAND_G;
 }
-__host__ __device__ inline unsigned band_lds_bytes(int mb, int nw, int rad, int ksc, bool samples)
+// (plut: the replicated photometric table -- the grey instantiations; the colour and 16-bit ones generate the factor instead)
+__host__ __device__ inline unsigned band_lds_bytes(int mb, int nw, int rad, int ksc, bool samples, bool plut = true)
 {
-    return 256u * BAND_PSTRIDE + (unsigned)band_stage_chunks(samples) * (unsigned)band_chunk_bytes(mb) + 4u * (unsigned)(rad + 1) + 64u * (unsigned)ksc + 4u * BAND_MAXROWS * (unsigned)(1 + 2 * nw) + 16u;
+    return (plut ? 256u * BAND_PSTRIDE : 0u) + (unsigned)band_stage_chunks(samples) * (unsigned)band_chunk_bytes(mb) + 4u * (unsigned)(rad + 1) + 64u * (unsigned)ksc + 4u * BAND_MAXROWS * (unsigned)(1 + 2 * nw) + 16u;
 }
 
 // operand chunks: per (grid row a, block of 16 sample columns): the MFMA B fragments of X[(a, b)][c0 .. c0 + 32 MB) colscale,
 // [n-tile j][hi | lo][lane = 32 (k / 8) + n][k % 8] f16 (1 KiB each), then 128 v of the 16 samples as u32 (the row
 // stride of the replicated photometric table) and padding to 256 B. Sample columns past nc: zeros.
+// RAW (the colour and 16-bit formats): svals is the u32 image of the sample values (the 16-bit value, or the packed colour
+// R + 256 G + 65536 B) and the tail carries it as it is.
+template <bool RAW>
 __global__ __launch_bounds__(256) void k_band_prep(const float *__restrict__ X, unsigned x_ld, const float *__restrict__ colscale,
-                                                    const uint8_t *__restrict__ svals, int nr, int nc, int ksc, int mb,
+                                                    const void *__restrict__ svals_, int nr, int nc, int ksc, int mb,
                                                     unsigned char *__restrict__ chunks)
 {
+    const std::conditional_t<RAW, unsigned, uint8_t> *__restrict__ svals = static_cast<const std::conditional_t<RAW, unsigned, uint8_t> *>(svals_);
     // one thread per 16-byte fragment piece pair (hi, lo): (grid row a, block, n-tile jb, half h, column rr) -> the 8 samples
     // 16 blk + 8 h + j of column 32 jb + rr: 32 lanes read 128 contiguous bytes of a sample's row, and write 512 contiguous bytes
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -79,7 +88,7 @@ __global__ __launch_bounds__(256) void k_band_prep(const float *__restrict__ X, 
     f[(size_t)(jb * 2 + 1) * 64 + h * 32 + rr] = lo;
     if (jb == 0 && rr < 8) {
         const int k = 8 * (int)h + (int)rr, bcol = 16 * blk + k;
-        reinterpret_cast<unsigned *>(ch + mb * 2048)[k] = bcol < nc ? BAND_PSTRIDE * (unsigned)svals[(size_t)a * nc + bcol] : 0u;
+        reinterpret_cast<unsigned *>(ch + mb * 2048)[k] = bcol < nc ? (RAW ? 1u : BAND_PSTRIDE) * (unsigned)svals[(size_t)a * nc + bcol] : 0u;
     }
 }
 
@@ -140,7 +149,17 @@ __device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
 //   as k_nystroem_f16s (sample pixels skipped unless raster; c += Phi^T y per workgroup).
 // SAMPLES = true: targets = the samples of grid rows [row_begin, ..): out = Y = alpha (D X - K_A X).
 // NS > 0 (joint filtering): NS float planes through the same filter in the epilogue, fsig.w [NS][LD] their weights
-template <int MB, int PB, int NW, bool SAMPLES, int NS = 0>
+// G: the pixel format. Grey: the photometric factor is one LDS gather per entry from the 256-level table. Rgb, U16: tval is the
+//   image in the format (pixel targets) or the u32 image of the sample values (sample targets), the chunk tails carry the raw u32
+//   values, and the factor is P = exp2(pix_nsval dist2) with Pix<G>::dist2 and one v_exp_f32 per entry (pix_nsval = -s_val); no
+//   table in LDS. Er Ec stays a separate factor, so an entry outside the radius is still an exact zero pair. These
+//   instantiations write Phi (or Y): no filter in the epilogue, no c.
+template <PixGen G> __device__ __forceinline__ typename Pix<G>::Val band_pix_value(unsigned v)
+{
+    if constexpr (G == PixGen::Rgb) return make_float3(ubyte_f32(v, 0), ubyte_f32(v, 1), ubyte_f32(v, 2));
+    else return (float)v;
+}
+template <int MB, int PB, int NW, bool SAMPLES, int NS = 0, PixGen G = PixGen::Grey>
 __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tval, int width, int row_begin, const int *__restrict__ grow,
                                                    const int *__restrict__ gcol, int nr, int nc, int ksc, const float *__restrict__ btab,
                                                    const float *__restrict__ pexp, int rad, const unsigned *__restrict__ rowband, const unsigned *__restrict__ win,
@@ -150,9 +169,12 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                                                    const float *__restrict__ X, int x_ld, const double *__restrict__ degree, float alpha,
                                                    unsigned long long *__restrict__ evaluated, int row_end, const float *__restrict__ fw,
                                                    float fgain, float fysub, uint8_t *__restrict__ fout, float *__restrict__ fzf,
-                                                   float *__restrict__ fcorr, int64_t fpix0, BandSignals fsig, int noskip)
+                                                   float *__restrict__ fcorr, int64_t fpix0, BandSignals fsig, int noskip, float pix_nsval)
 {
     static_assert(!SAMPLES || PB == 1, "sample targets: one tile of 32 per wave");
+    static_assert(G == PixGen::Grey || NS == 0, "the colour and 16-bit instantiations have no filter epilogue");
+    constexpr bool GREY = G == PixGen::Grey;
+    constexpr unsigned PLUT_BYTES = GREY ? 256 * BAND_PSTRIDE : 0u;
     constexpr int LD = 32 * MB, CHB = band_chunk_bytes(MB), NPIECE = MB * 2 + 1; // (the last piece is the 256-byte tail)
     // Pixel targets: a unit of work is (pair of consecutive band rows, half-block of 8 sample columns): lanes 0 - 31 of the MFMA's
     // k hold the 8 columns in the pair's first row, lanes 32 - 63 the same columns in its second row. The pairs are aligned to the
@@ -161,8 +183,8 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     // Sample targets: (one band row, block of 16 columns) as before.
     constexpr int RP = SAMPLES ? 1 : BAND_PAIR;
     extern __shared__ __attribute__((aligned(16))) unsigned char bdyn[];
-    float *plut = reinterpret_cast<float *>(bdyn); // [256][32]: the photometric table, one copy per bank
-    unsigned char *stage = bdyn + 256 * BAND_PSTRIDE; // [BAND_NBUF][BAND_G][CHB]
+    float *plut = reinterpret_cast<float *>(bdyn); // [256][32]: the photometric table, one copy per bank (Grey only)
+    unsigned char *stage = bdyn + PLUT_BYTES; // [BAND_NBUF][BAND_G][CHB]
     float *elut = reinterpret_cast<float *>(stage + band_stage_chunks(SAMPLES) * CHB); // [rad + 1]: Ec(d), 0 at d = rad
     int *gcs = reinterpret_cast<int *>(elut + (rad + 1));              // [16 ksc]: the sample columns (far away past nc)
     float *er_s = reinterpret_cast<float *>(gcs + 16 * ksc);           // [NW][BAND_MAXROWS]: 2^15 Er of the band rows, per wave
@@ -185,7 +207,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
 
     // the replicated photometric table arrives by LDS-DMA from its expanded image in the tables blob (256 BAND_PCOPY floats, after
     // the grid coordinates), 1 KiB per instruction: 21 load + store rounds per thread otherwise
-    {
+    if constexpr (GREY) {
         constexpr int PIECES = 256 * BAND_PCOPY * 4 / 1024;
         const unsigned char *src = reinterpret_cast<const unsigned char *>(pexp);
         const unsigned dst0 = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_offset_of(plut));
@@ -209,7 +231,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
         }
         gwin[i0] = g;
     }
-    lds_dma_drain(); // (this wave's pieces of the photometric table)
+    if constexpr (GREY) lds_dma_drain(); // (this wave's pieces of the photometric table)
     __syncthreads();
     if (tid == 0) {
         int blo = 0xFFFF, bhi = -1;
@@ -231,16 +253,19 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     const int trow = min(trow0 + wave, row_end - 1);
     int tc[PB];
     unsigned pv128[PB];
+    typename Pix<G>::Val pvv[PB]; // (Rgb, U16: the target's value as the policy compares it)
 #pragma unroll
     for (int b = 0; b < PB; ++b) {
         if (SAMPLES) {
             const int bb = min(tile * 32 + l31, nc - 1);
             tc[b] = gcol[bb];
-            pv128[b] = BAND_PSTRIDE * (unsigned)tval[(size_t)trow * nc + bb];
+            if constexpr (GREY) pv128[b] = BAND_PSTRIDE * (unsigned)tval[(size_t)trow * nc + bb];
+            else pvv[b] = band_pix_value<G>(reinterpret_cast<const unsigned *>(tval)[(size_t)trow * nc + bb]);
         } else {
             const int cc = min((tile * PB + b) * 32 + l31, width - 1);
             tc[b] = cc;
-            pv128[b] = BAND_PSTRIDE * (unsigned)tval[(size_t)trow * width + cc];
+            if constexpr (GREY) pv128[b] = BAND_PSTRIDE * (unsigned)tval[(size_t)trow * width + cc];
+            else pvv[b] = Pix<G>::read(reinterpret_cast<const typename Pix<G>::In *>(tval), (int64_t)trow * width + cc);
         }
     }
     const unsigned pbase = lds_offset_of(plut) + 4u * (unsigned)(lane % BAND_PCOPY);
@@ -322,10 +347,21 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
         // tile's MFMAs between the vector instructions of the next tile's generation inside a step costs no registers and
         // measured 2 % slower; tiles of 32 or 128 columns per wave (PB = 1, 4): 11.6 / 11.1 ms against 9.2.)
         float pp[PB][8];
+        if constexpr (GREY) {
 #pragma unroll
-        for (int b = 0; b < PB; ++b)
+            for (int b = 0; b < PB; ++b)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) pp[b][e] = lds_f32(sad_u32(pv128[b], sv128[e], pbase));
+                for (int e = 0; e < 8; ++e) pp[b][e] = lds_f32(sad_u32(pv128[b], sv128[e], pbase));
+        } else {
+            // the policy's squared distance (exact integer terms, the sum rounded once) and one v_exp_f32 per entry; a sample's
+            // value is unpacked once for the PB targets
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const typename Pix<G>::Val sv = band_pix_value<G>(sv128[e]);
+#pragma unroll
+                for (int b = 0; b < PB; ++b) pp[b][e] = __builtin_amdgcn_exp2f(Pix<G>::dist2(pvv[b], sv) * pix_nsval);
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
         f16x8 ah[PB], al[PB];
 #if defined(BAND_EXP) && BAND_EXP == 2 // (profiling build: no generation -- the gathers stay, their values go unused)
@@ -518,7 +554,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
         iv[j] = inv[32 * j + l31];
         csum[j] = 0.f;
     }
-    if (!SAMPLES && fw) {
+    if (GREY && !SAMPLES && fw) {
         // filter in the epilogue: s = Phi[px] . w summed over the 32 lanes that hold the pixel's columns, then hpc/display.c:64-78
         // as k_apply_filter has it; Phi is not written (the sample pixels are filter_sample_rows' from Phi_A)
         if (wvalid) {
@@ -600,7 +636,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                         if (is_sample) continue;
                         dst = (int64_t)p + px - (int64_t)samples_before(idx, p, (uint32_t)px);
                     }
-                    const float yv = is_sample ? 0.f : (float)tval[px];
+                    const float yv = (!GREY || is_sample) ? 0.f : (float)tval[px]; // (Rgb, U16: no 8-bit y, no c)
 #pragma unroll
                     for (int j = 0; j < MB; ++j) {
                         const float v = acc[b][j][q] * iv[j];
@@ -611,7 +647,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
             }
         }
     }
-    if (!SAMPLES && cpartial) {
+    if (GREY && !SAMPLES && cpartial) {
         __syncthreads();
         float *red = reinterpret_cast<float *>(stage); // [NW][LD]
 #pragma unroll
@@ -800,12 +836,15 @@ static int band_tables_cached(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, 
 #endif
 constexpr int BAND_NW_S = BAND_NW_S_X;                // sample targets: 32 per wave, 8 grid rows per workgroup
 
-template <int MB, int NS = 0>
+// G: the pixel format of d_img (Rgb, U16: Phi is written; no filter, no c; nsval = -s_val of the kernel)
+template <int MB, int NS = 0, PixGen G = PixGen::Grey>
 static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int row0, int nrows, const unsigned char *chunks,
                           const float *inv, float *phi, int phi_ld, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, int raster,
-                          double *cpartial, unsigned long long *evaluated, const BandFilter *flt = nullptr, int64_t pix0 = 0)
+                          double *cpartial, unsigned long long *evaluated, const BandFilter *flt = nullptr, int64_t pix0 = 0, float nsval = 0.f)
 {
-    if constexpr (NS == 0) // the planes ride in the filter's epilogue: one instantiation per plane count
+    if constexpr (G != PixGen::Grey)
+        if (flt || cpartial) return set_error(ctx, GLF_ERR_INVALID, "k_band: the colour and 16-bit formats have no filter epilogue");
+    if constexpr (NS == 0 && G == PixGen::Grey) // the planes ride in the filter's epilogue: one instantiation per plane count
         if (flt && flt->sig.nsig > 0) {
             switch (flt->sig.nsig) {
             case 1: return launch_band_px<MB, 1>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
@@ -815,43 +854,45 @@ static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_i
             default: return set_error(ctx, GLF_ERR_INVALID, "k_band: %d signal planes", flt->sig.nsig);
             }
         }
-    auto kern = k_band<MB, BAND_PB, BAND_NW, false, NS>;
-    const unsigned lds = band_lds_bytes(MB, BAND_NW, bt.rad, bt.ksc, false);
+    auto kern = k_band<MB, BAND_PB, BAND_NW, false, NS, G>;
+    const unsigned lds = band_lds_bytes(MB, BAND_NW, bt.rad, bt.ksc, false, G == PixGen::Grey);
     GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW * 64), lds, ctx->stream, d_img, bt.width, row0, bt.grow(), bt.gcol(), bt.nr, bt.nc,
                        bt.ksc, bt.tab(), bt.pexp(), bt.rad, bt.rowband_px(), bt.win_px(), bt.ntiles_px, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster,
                        cpartial, (const float *)nullptr, 0, (const double *)nullptr, 0.f, evaluated, row0 + nrows, flt ? flt->w : (const float *)nullptr,
                        flt ? flt->gain : 0.f, flt ? flt->ysub : 0.f, flt ? flt->out : (uint8_t *)nullptr, flt ? flt->zf : (float *)nullptr,
-                       flt ? flt->corr : (float *)nullptr, pix0, flt ? flt->sig : BandSignals{}, ctx->tune.band_noskip ? 1 : 0);
+                       flt ? flt->corr : (float *)nullptr, pix0, flt ? flt->sig : BandSignals{}, ctx->tune.band_noskip ? 1 : 0, nsval);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
 inline size_t band_px_wgs(const BandTables &bt, int nrows) { return (size_t)bt.ntiles_px * (size_t)ceil_div(nrows, BAND_NW); }
 
-template <int MB>
+// (Rgb, U16: svals is the u32 image of the sample values, passed as bytes)
+template <int MB, PixGen G = PixGen::Grey>
 static int launch_band_samples(glf_ctx *ctx, const BandTables &bt, const uint8_t *svals, int a0, int nrows, const unsigned char *chunks,
                                const float *inv, float *Y, int y_ld, const float *X, int x_ld, const double *degree, float alpha,
-                               unsigned long long *evaluated)
+                               unsigned long long *evaluated, float nsval = 0.f)
 {
-    auto kern = k_band<MB, 1, BAND_NW_S, true>;
-    const unsigned lds = band_lds_bytes(MB, BAND_NW_S, bt.rad, bt.ksc, true);
+    auto kern = k_band<MB, 1, BAND_NW_S, true, 0, G>;
+    const unsigned lds = band_lds_bytes(MB, BAND_NW_S, bt.rad, bt.ksc, true, G == PixGen::Grey);
     GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((unsigned)bt.ntiles_s, (unsigned)ceil_div(nrows, BAND_NW_S));
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW_S * 64), lds, ctx->stream, svals, bt.nc, a0, bt.grow(), bt.gcol(), bt.nr, bt.nc, bt.ksc,
                        bt.tab(), bt.pexp(), bt.rad, bt.rowband_s(), bt.win_s(), bt.ntiles_s, chunks, inv, Y, y_ld, (const uint8_t *)nullptr,
                        (const uint32_t *)nullptr, 0u, 1, (double *)nullptr, X, x_ld, degree, alpha, evaluated, a0 + nrows, (const float *)nullptr, 0.f,
-                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0, BandSignals{}, 0);
+                       0.f, (uint8_t *)nullptr, (float *)nullptr, (float *)nullptr, (int64_t)0, BandSignals{}, 0, nsval);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
 
-static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *colscale, const uint8_t *svals, int nr, int nc, int ksc, int mb,
+// svals: uint8 [nr][nc] (raw = false) or u32 [nr][nc] (raw: the colour and 16-bit formats)
+static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *colscale, const void *svals, bool raw, int nr, int nc, int ksc, int mb,
                      unsigned char *chunks)
 {
     const size_t total = (size_t)nr * ksc * mb * 64;
-    hipLaunchKernelGGL(k_band_prep, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, ctx->stream, X, x_ld, colscale, svals, nr, nc, ksc,
-                       mb, chunks);
+    hipLaunchKernelGGL(raw ? k_band_prep<true> : k_band_prep<false>, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, ctx->stream, X, x_ld,
+                       colscale, svals, nr, nc, ksc, mb, chunks);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -872,13 +913,18 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     const int mb = (int)LD / 32;
     DevBuf<float> colscale, inv, camx;
     DevBuf<uint8_t> svals;
+    DevBuf<unsigned> svals32; // (Rgb, U16: the sample values as u32)
     DevBuf<unsigned char> chunks;
     DevBuf<double> cpart;
+    const PixGen gen = pixgen_of(coef.kernel);
+    const bool raw = gen != PixGen::Grey;
+    if (raw && (flt || d_c)) return GLF_ERR_UNSUPPORTED; // (no 8-bit y: the filter stays a stage of its own)
     DevBuf<unsigned long long> dev_eval;
     GLF_TRY(colscale.alloc(ctx, ld_total));
     GLF_TRY(inv.alloc(ctx, ld_total));
     GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    GLF_TRY(svals.alloc(ctx, p));
+    if (raw) GLF_TRY(svals32.alloc(ctx, p));
+    else GLF_TRY(svals.alloc(ctx, p));
     GLF_TRY(chunks.alloc(ctx, (size_t)bt.nr * bt.ksc * band_chunk_bytes(mb)));
     GLF_TRY(dev_eval.alloc(ctx, 1));
     const size_t wgs = band_px_wgs(bt, nrows);
@@ -887,20 +933,28 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     if (d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
     GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), st));
     band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);
-    hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
+    if (raw) hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, gen == PixGen::Rgb ? 1 : 0, svals32.p);
+    else hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
     GLF_LAUNCH_CHECK(ctx);
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     float band_ms = 0.f;
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
-        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, svals.p, bt.nr, bt.nc, bt.ksc, mb, chunks.p));
+        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p));
         const bool timed = stats && (int)cb < glf_ctx::CP_RING;
         if (timed)
             for (int q = 0; q < 2; ++q)
                 if (!ctx->cp_ev[q][cb]) GLF_HIP(ctx, hipEventCreate(&ctx->cp_ev[q][cb]));
         hipEvent_t e0 = timed ? ctx->cp_ev[0][cb] : nullptr, e1 = timed ? ctx->cp_ev[1][cb] : nullptr;
         if (timed) GLF_HIP(ctx, hipEventRecord(e0, st));
-        if (mb == 2)
+        if (raw) {
+            float *po = d_phi + c0;
+            const float nsval = -coef.s_val;
+#define GLF_BAND_PX(MB_, G_) launch_band_px<MB_, 0, G_>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster, nullptr, dev_eval.p, nullptr, pix0, nsval)
+            if (gen == PixGen::Rgb) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::Rgb) : GLF_BAND_PX(1, PixGen::Rgb));
+            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::U16) : GLF_BAND_PX(1, PixGen::U16));
+#undef GLF_BAND_PX
+        } else if (mb == 2)
             GLF_TRY(launch_band_px<2>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,
                                       raster, d_c ? cpart.p : nullptr, dev_eval.p, flt, pix0));
         else

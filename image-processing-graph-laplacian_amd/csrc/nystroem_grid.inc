@@ -1229,8 +1229,11 @@ static int nystroem_contract_grid(glf_ctx *ctx, const uint8_t *d_img, int width,
                                   int window, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *rowpass_stats,
                                   int *path)
 {
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(ctx->tune.nys_path, width) || !grey_levels_factor(coef.kernel))
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(ctx->tune.nys_path, width) || !band_form_applies(ctx, coef.kernel))
         return GLF_ERR_UNSUPPORTED;
+    // the colour and 16-bit kernels (PIX_BAND): the band form or nothing, one block of at most 64 columns, no c = Phi^T y
+    const bool band_only = !grey_levels_factor(coef.kernel);
+    if (band_only && (!(ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) || ld > 64 || d_c)) return GLF_ERR_UNSUPPORTED;
     if (pix0 % width || pix1 % width || width > GRID_MAX_W || p < 4) return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> hidx(p);
     GLF_HIP(ctx, hipMemcpyAsync(hidx.data(), d_idx, sizeof(uint32_t) * p, hipMemcpyDeviceToHost, ctx->stream));
@@ -1246,6 +1249,7 @@ static int nystroem_contract_grid(glf_ctx *ctx, const uint8_t *d_img, int width,
             return rc;
         }
     }
+    if (band_only) return GLF_ERR_UNSUPPORTED;
     if (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 3) { // auto | rank: the rank form when the photometric table allows it
         const int rc = launch_nystroem_rank(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster,
                                             d_c, kernel_ms, window, entries_evaluated, mfma_flops, g, height, rowpass_stats);
@@ -1339,6 +1343,13 @@ __global__ __launch_bounds__(256) void k_gridop_svals(const float4 *__restrict__
     if (s < p) svals[s] = (uint8_t)samples[s].z;
 }
 
+// the colour and 16-bit formats' sample values as u32 [nr][nc]: the 16-bit value (record's z), or the packed colour (its w)
+__global__ __launch_bounds__(256) void k_gridop_svals32(const float4 *__restrict__ samples, unsigned p, int rgb, unsigned *__restrict__ svals)
+{
+    const unsigned s = blockIdx.x * 256 + threadIdx.x;
+    if (s < p) svals[s] = (unsigned)(rgb ? samples[s].w : samples[s].z);
+}
+
 #include "nystroem_rank.inc"
 #include "nystroem_band.inc"
 
@@ -1356,6 +1367,9 @@ struct glf::GridOp {
     glf::DevBuf<unsigned short> scol;
     glf::DevBuf<unsigned> goff, pmask;
     glf::DevBuf<uint8_t> svals;
+    glf::DevBuf<unsigned> svals32; // the colour and 16-bit formats (band form only): the sample values as u32, in place of svals
+    glf::PixGen gen = glf::PixGen::Grey;
+    float nsval = 0.f;             // -s_val (the generated photometric factor of those formats)
     glf::RowTiles rtl; // row-tile form of the row pass: the grid rows [rtl_a0, rtl_a0 + rtl_rows) as target rows
     int rtl_a0 = -1, rtl_rows = 0;
     // rank form (nystroem_rank.inc): R terms of the photometric expansion (0: exact form), the context's tables, the
@@ -1383,7 +1397,9 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
                    KernelCoef coef, GridOp **out)
 {
     *out = nullptr;
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || p < 4 || !grey_levels_factor(coef.kernel)) return GLF_ERR_UNSUPPORTED;
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || p < 4 || !band_form_applies(ctx, coef.kernel)) return GLF_ERR_UNSUPPORTED;
+    const bool band_only = !grey_levels_factor(coef.kernel); // the colour and 16-bit kernels (PIX_BAND): the band form or nothing
+    if (band_only && !(ctx->tune.mv_path == 0 || ctx->tune.mv_path == 4)) return GLF_ERR_UNSUPPORTED;
     std::vector<uint32_t> idx(h_idx, h_idx + p);
     GridInfo g;
     if (!detect_grid(idx, width, g) || ceil_div(g.nr, 16) > GRID_MAX_KS || g.nc > GRID_MAX_W) return GLF_ERR_UNSUPPORTED;
@@ -1414,14 +1430,25 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
     GLF_HIP(ctx, hipMemcpyAsync(op->grid.p + nr, g.cols.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st));
     const float *ptab = op->tab.p, *etab = op->tab.p + 256;
     const int *grow = op->grid.p, *gcol = op->grid.p + nr;
-    GLF_TRY(op->svals.alloc(ctx, p));
-    hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, op->svals.p);
+    op->gen = pixgen_of(coef.kernel);
+    op->nsval = -coef.s_val;
+    if (band_only) {
+        GLF_TRY(op->svals32.alloc(ctx, p));
+        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, op->gen == PixGen::Rgb ? 1 : 0, op->svals32.p);
+    } else {
+        GLF_TRY(op->svals.alloc(ctx, p));
+        hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, op->svals.p);
+    }
     GLF_LAUNCH_CHECK(ctx);
     if (ctx->tune.mv_path == 0 || ctx->tune.mv_path == 4) { // auto | band
         const int rc = band_tables_cached(ctx, g, coef, width, height, 32 * BAND_PB, false, &op->band);
         if (rc != GLF_OK && rc != GLF_ERR_UNSUPPORTED) return rc;
         op->use_band = rc == GLF_OK && (ctx->tune.mv_path == 4 || op->band->narrow(height));
         if (ctx->tune.mv_path == 4 && !op->use_band) return GLF_ERR_UNSUPPORTED;
+    }
+    if (band_only && !op->use_band) {
+        GLF_HIP(ctx, hipStreamSynchronize(st)); // htab is pageable host memory
+        return GLF_ERR_UNSUPPORTED;
     }
     if (op->use_band) {
         op->d_samples = d_samples;
@@ -1491,9 +1518,13 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         }
         band_scales(st, X, op->p, ld_total, op->camx.p, op->colscale.p, op->band_inv.p);
         for (unsigned c0 = 0; c0 < ld_total; c0 += LD) {
-            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->colscale.p + c0, op->svals.p, nr, nc, ksc, NT, op->band_chunks.p));
-            GLF_TRY((launch_band_samples<NT>(ctx, *op->band, op->svals.p, a0, nrows, op->band_chunks.p, op->band_inv.p + c0, Y + c0, (int)ld_total,
-                                             X + c0, (int)ld_total, d_degree, (float)alpha, nullptr)));
+            const bool raw = op->gen != PixGen::Grey;
+            const uint8_t *sv = raw ? reinterpret_cast<const uint8_t *>(op->svals32.p) : op->svals.p;
+            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->colscale.p + c0, sv, raw, nr, nc, ksc, NT, op->band_chunks.p));
+#define GLF_BAND_SAMPLES(G_) launch_band_samples<NT, G_>(ctx, *op->band, sv, a0, nrows, op->band_chunks.p, op->band_inv.p + c0, Y + c0, (int)ld_total, \
+                                                         X + c0, (int)ld_total, d_degree, (float)alpha, nullptr, op->nsval)
+            GLF_TRY(op->gen == PixGen::Rgb ? GLF_BAND_SAMPLES(PixGen::Rgb) : op->gen == PixGen::U16 ? GLF_BAND_SAMPLES(PixGen::U16) : GLF_BAND_SAMPLES(PixGen::Grey));
+#undef GLF_BAND_SAMPLES
         }
         return GLF_OK;
     }

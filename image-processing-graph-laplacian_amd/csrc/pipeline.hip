@@ -671,7 +671,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     } gop;
     {
         const bool want = (ctx->tune.mv_path == 1 || ctx->tune.mv_path == 3 || ctx->tune.mv_path == 4) ? true : ctx->tune.mv_path == 2 ? false : p >= 16384;
-        if (want && opt.kernel != GLF_KERNEL_NLM) {
+        if (want && opt.kernel != GLF_KERNEL_NLM && (u8_guide || ld <= 64)) { // (the colour and 16-bit band form: one block of 64 columns)
             const int rc = grid_op_create(ctx, tb.samples.p, h_idx, p, width, height, coef, &gop.op);
             if (rc != GLF_OK && rc != GLF_ERR_UNSUPPORTED) return rc;
         }
@@ -865,7 +865,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     bool sig_fused = false, sig_done = false;
     DevBuf<float> sig_w; // [nsig][ld] the planes' filter weights once c_s is known
     if (sig) {
-        const bool elig = gop.op && ld <= 64 && opt.filter_mode != GLF_FILTER_SHARPEN && ctx->contraction == GLF_CONTRACT_F16_SPLIT &&
+        const bool elig = u8_guide && gop.op && ld <= 64 && opt.filter_mode != GLF_FILTER_SHARPEN && ctx->contraction == GLF_CONTRACT_F16_SPLIT &&
                           (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) && !ctx->tune.no_fused_filter && (have_ysum || pix0 == pix1);
         DevBuf<double> vote;
         GLF_TRY(vote.alloc(ctx, 1));
@@ -1014,7 +1014,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
         return GLF_OK;
     };
     if (!u8_guide) { // (no 8-bit y: the channels / the 16-bit image are filtered below, as planes; the sharpening weights need G)
-        S.contraction = GLF_CONTRACT_F32_MFMA; // (the colour and 16-bit formats have no split-f16 form)
+        if (S.nystroem_path != 4) S.contraction = GLF_CONTRACT_F32_MFMA; // (those formats' entry-by-entry kernel; their band form (PIX_BAND) is split f16)
         if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
         if (opt.filter_mode == GLF_FILTER_SHARPEN) GLF_TRY(gram_to_host());
     } else {

@@ -8,7 +8,7 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16] [-pix_band]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
  * (python/image_processing.py:197-241, B = 1.5) with W = Phi diag(1 - mu) Phi^T from the eigenpairs this program computes.
@@ -22,6 +22,9 @@
  * -depth16 reads a 16-bit grey PNG and filters it on its 16-bit values (glf_image_processing_u16: the bilateral kernel with
  * v in 0..65535, -h_val in 16-bit units, 30 x 257 by default -- the 8-bit default graph on the same content) with the same
  * -filter, and writes results/input.png and results/output.png as 16-bit grey PNGs; -ngpu N works as for 8 bits.
+ * -pix_band (with -depth16 or -color -rgb_graph) sets the PIX_BAND tuning key: the 16-bit / colour kernel takes the band form
+ * of the Nystroem stage and of the operator wherever the grey kernel would (GLF_PIX_BAND=1 in the environment does the same), and
+ * one more line names the routes taken ("band form: nystroem_path 4, matvec_path 4", or the fallback's numbers).
  * -dump_residual writes results/residuals.png = |input - output| stretched to the full grey range, the PoC's residual image
  * (python/image_processing.py:378-380: plt.imsave of np.abs(y - z) with cmap 'gray' autoscales min..max).
  * -no_approx runs the full-matrix mode (hpc/image_processing.c:155-181); -use_slepc is accepted and refused.
@@ -310,6 +313,17 @@ out:
     return rows;
 }
 
+/* -pix_band (with -depth16 or -color -rgb_graph): the band form of the 16-bit and colour kernels (the PIX_BAND tuning key) on a
+ * context, and the line that names the routes the call took */
+static void pix_band_set(glf_ctx *ctx)
+{
+    if (opt_has("-pix_band") && glf_ctx_set_tuning(ctx, "PIX_BAND", "1") != GLF_OK) fprintf(stderr, "-pix_band: could not set PIX_BAND\n");
+}
+static void pix_band_report(const glf_stats *st)
+{
+    if (opt_has("-pix_band")) printf("band form: nystroem_path %d, matvec_path %d\n", (int)st->nystroem_path, (int)st->matvec_path);
+}
+
 /* -depth16: img (rows of `width` uint16_t) through glf_image_processing_u16 on one context, or glf_multi_image_processing_u16 on
  * ngpu ranks; returns the output rows (NULL on failure, the message printed). */
 static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned height, int ngpu, int backend)
@@ -334,10 +348,12 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         glf_stats *st = (glf_stats *)calloc((size_t)ngpu, sizeof(glf_stats));
         if (rc != GLF_OK) fprintf(stderr, "glf_multi_create(%d GPUs, %s): %s\n", ngpu, backend == GLF_MULTI_RCCL ? "rccl" : "loopback", glf_strerror(rc));
         else if (st) {
+            for (int r = 0; r < ngpu; ++r) pix_band_set(glf_multi_ctx(world, r));
             rc = glf_multi_image_processing_u16(world, &opt, flat, (int)width, (int)height, flat_out, NULL, NULL, st);
             if (rc != GLF_OK) fprintf(stderr, "glf_multi_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_multi_last_error(world));
             else {
                 print_stage_times(&st[0], opt.epsilon);
+                pix_band_report(&st[0]);
                 for (int r = 0; r < ngpu; ++r)
                     printf("rank %d: pixel rows [%d, %d), %.3f ms on the device\n", r, st[r].row0, st[r].row1, st[r].ms_total);
             }
@@ -352,10 +368,14 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         ok = glf_malloc(ctx, &d_img, sizeof(uint16_t) * n) == GLF_OK && glf_malloc(ctx, &d_out, sizeof(uint16_t) * n) == GLF_OK &&
              glf_memcpy_h2d(ctx, d_img, flat, sizeof(uint16_t) * n) == GLF_OK;
         if (ok) {
+            pix_band_set(ctx);
             const int rc = glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
             if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(ctx));
             ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, sizeof(uint16_t) * n) == GLF_OK;
-            if (ok) print_stage_times(&st, opt.epsilon);
+            if (ok) {
+                print_stage_times(&st, opt.epsilon);
+                pix_band_report(&st);
+            }
         }
         if (d_img) glf_free(ctx, d_img);
         if (d_out) glf_free(ctx, d_out);
@@ -405,12 +425,14 @@ static png_bytep *ColorComputation(const char *filename, unsigned *width_out, un
         for (int r = 0; ok && r < h; ++r) memcpy(flat + (size_t)r * 3 * w, rgb[r], 3 * (size_t)w);
         ok = ok && glf_memcpy_h2d(cctx, d_rgb, flat, 3 * n) == GLF_OK;
         if (ok) {
+            pix_band_set(cctx);
             const int rc = glf_image_processing_rgb(cctx, &copt, (const uint8_t *)d_rgb, w, h, (uint8_t *)d_rgb_out, NULL, NULL, &cst);
             if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_rgb: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(cctx));
             ok = rc == GLF_OK && glf_memcpy_d2h(cctx, flat, d_rgb_out, 3 * n) == GLF_OK;
         }
         if (ok) {
             print_stage_times(&cst, copt.epsilon);
+            pix_band_report(&cst);
             rows = (png_bytep *)malloc(sizeof(png_bytep) * (size_t)h);
             for (int r = 0; rows && r < h; ++r) {
                 rows[r] = (png_bytep)malloc(3 * (size_t)w);
@@ -605,6 +627,11 @@ int main(int argc, char **argv)
     if (opt_has("-rgb_graph") && (!opt_has("-color") || opt_has("-chroma"))) {
         fprintf(stderr, opt_has("-color") ? "-rgb_graph filters R, G and B through the colour graph: it cannot be combined with -chroma\n"
                                           : "-rgb_graph builds the graph of a colour image: it needs -color\n");
+        FinalizeProgram();
+        return 1;
+    }
+    if (opt_has("-pix_band") && !opt_has("-depth16") && !opt_has("-rgb_graph")) {
+        fprintf(stderr, "-pix_band selects the band form of the 16-bit and colour kernels: it needs -depth16 or -color -rgb_graph\n");
         FinalizeProgram();
         return 1;
     }

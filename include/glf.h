@@ -67,6 +67,13 @@ int glf_ctx_device_info(const glf_ctx *ctx, char *name, size_t name_len, int *nu
  *   NYS_PATH  band | rank | grid | direct     DEG_PATH  grid | direct     MV_PATH  band | rank | grid | dense
  *   ROWPASS, ROWPASS_OP  rt | v1     COLPASS  ws | v1     SWEEP_COLPASS  segments | samples
  *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, BAND_NOSKIP, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
+ *   PIX_BAND  1 | 0 (default 0): the colour and 16-bit bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16) take the band form of
+ *     the Nystroem stage and of the L_A operator under exactly the conditions under which the grey kernel takes it -- split-f16
+ *     contraction, a tensor-grid sample set, at most 64 eigenpairs, the radius and band-row limits, NYS_PATH auto (width >= 1024)
+ *     or band, MV_PATH auto (p >= 16 384) or band -- with the photometric factor generated per entry (one v_exp_f32) instead of
+ *     gathered from the 256-level table. L_A is then neither built nor stored. The degree stage and the filter stage are
+ *     unchanged (entry by entry; Phi is written, filter_fused = 0). Wherever the form does not apply, and with the key off, the
+ *     entry-by-entry route runs, bit for bit as before. The grey kernels never read the key.
  * At context creation each key is initialised from the environment variable GLF_<KEY> (read once; nothing reads the
  * environment per call). No reference counterpart (PETSc's -ksp_type / -pc_type options database is the nearest thing). */
 int glf_ctx_set_tuning(glf_ctx *ctx, const char *key, const char *value);
@@ -378,9 +385,10 @@ typedef struct glf_stats {
                                3 grid-factored in rank form (photometric table as a rank-R expansion),
                                4 band form (entry by entry over the samples within the kernel's radius; then nystroem_evaluated
                                counts the entries the kernel evaluated and nystroem_colpass_* describe its launches, with
-                               nystroem_colpass_flops = 2 ld x the (pixel, sample) pairs inside the radius) */
+                               nystroem_colpass_flops = 2 ld x the (pixel, sample) pairs inside the radius). The colour and 16-bit
+                               kernels report 0, or 4 with the PIX_BAND tuning key (contraction is then GLF_CONTRACT_F16_SPLIT) */
     int32_t matvec_path;    /* 0 stored L_A streamed per sweep, 1 L_A applied in grid-factored form (never stored), 3 the same in rank form,
-                               4 L_A applied in band form (never stored) */
+                               4 L_A applied in band form (never stored). The colour and 16-bit kernels: 0, or 4 with PIX_BAND */
     /* grid-factored Nystroem: the row-pass kernel (k_grid_rowpass) alone -- launches, summed device ms (HIP events around
      * each launch) and its algorithmic flops 2 rows 256 nc nr ld (one product per multiply-add) */
     int32_t nystroem_rowpass_launches;
@@ -432,8 +440,10 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
  * opt->filter_mode: z_c = (1 - ysub) x_c + gain Phi f(Pi) Phi^T x_c, then clamped and cast as glf_image_processing's d_out.
  * d_rgb / d_out_rgb: device uint8 [height][width][3] interleaved, d_rgb replicated on every rank; with a comm rank g writes its
  * own pixel rows only. d_zf optional: device float [3][height*width] (planes R, G, B of z before the clamp). eigvals_out: HOST
- * double[m] or NULL. More than 256 eigenpairs: GLF_ERR_UNSUPPORTED. The colour kernel has no band, grid or rank form (yet): the
- * entry-by-entry kernels run and L_A is stored (stats.nystroem_path = matvec_path = 0, filter_fused = 0). */
+ * double[m] or NULL. More than 256 eigenpairs: GLF_ERR_UNSUPPORTED. The colour kernel has no grid or rank form: by default the
+ * entry-by-entry kernels run and L_A is stored (stats.nystroem_path = matvec_path = 0, filter_fused = 0). With the PIX_BAND tuning
+ * key (glf_ctx_set_tuning) the Nystroem stage and the operator take the band form where it applies (nystroem_path / matvec_path 4,
+ * L_A not stored, contraction GLF_CONTRACT_F16_SPLIT); the degree and the filter stay entry by entry and unfused. */
 int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                              float *d_zf, double *eigvals_out, glf_stats *stats);
 
@@ -443,8 +453,8 @@ int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t
  * z = (1 - ysub) x + gain Phi f(Pi) Phi^T x, d_out = clamp(x + floor(z - x), 0, 65535) (glf_image_processing's rule at 16 bits).
  * d_img / d_out: device uint16_t [height][width], d_img replicated on every rank; with a comm rank g writes its own pixel rows only.
  * d_zf optional: device float [height*width], z before the clamp. eigvals_out: HOST double[m] or NULL. More than 256 eigenpairs:
- * GLF_ERR_UNSUPPORTED. As for colour the entry-by-entry kernels run and L_A is stored (stats.nystroem_path = matvec_path = 0,
- * filter_fused = 0). */
+ * GLF_ERR_UNSUPPORTED. As for colour the entry-by-entry kernels run and L_A is stored by default (stats.nystroem_path = matvec_path =
+ * 0, filter_fused = 0), and the PIX_BAND tuning key selects the band form of the Nystroem stage and the operator. */
 int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
                              float *d_zf, double *eigvals_out, glf_stats *stats);
 
