@@ -426,6 +426,23 @@ int glf_multi_image_processing_u16(glf_multi *w, const glf_options *opt, const u
                      eigvals_out, stats);
 }
 
+int glf_multi_image_processing_rgb_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height, int nsig,
+                                           const float *h_sig, float *h_sig_out, uint8_t *h_out_rgb, float *h_zf, double *eigvals_out,
+                                           glf_stats *stats)
+{
+    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
+    return multi_run(w, opt, PixGen::Rgb, h_rgb, width, height, h_out_rgb, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
+}
+
+int glf_multi_image_processing_u16_signals(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height, int nsig,
+                                           const float *h_sig, float *h_sig_out, uint16_t *h_out, float *h_zf, double *eigvals_out,
+                                           glf_stats *stats)
+{
+    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
+    return multi_run(w, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), h_zf,
+                     eigvals_out, stats, nsig, h_sig, h_sig_out);
+}
+
 static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
                      float *h_zf, double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out)
 {
@@ -478,7 +495,12 @@ static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uin
         if (rc == GLF_OK) {
             float *zf = h_zf ? b.d_zf : nullptr;
             double *ev = r == 0 ? eigvals_out : nullptr;
-            if (gen == PixGen::Rgb) rc = glf_image_processing_rgb(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
+            if (gen == PixGen::Rgb && nsig > 0)
+                rc = glf_image_processing_rgb_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out, zf, ev, &st);
+            else if (gen == PixGen::U16 && nsig > 0)
+                rc = glf_image_processing_u16_signals(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height, nsig, d_sig,
+                                                      d_sig_out, reinterpret_cast<uint16_t *>(b.d_out), zf, ev, &st);
+            else if (gen == PixGen::Rgb) rc = glf_image_processing_rgb(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
             else if (gen == PixGen::U16)
                 rc = glf_image_processing_u16(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height,
                                               reinterpret_cast<uint16_t *>(b.d_out), zf, ev, &st);

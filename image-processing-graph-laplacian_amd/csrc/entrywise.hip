@@ -13,6 +13,7 @@
 //   k_sample_matrix<G> (affinity.hip)   K_A / L_A from the sample records (U16 takes the grey instantiation: the same records)
 //   k_nystroem<.., G> (nystroem.hip)    Phi = K_B^T Psi, f32 MFMA with the format's pixel read
 //   k_apply_filter_pix<LD, G>           the outputs and z, dot products in f64
+//   k_phi_t_pix_signals<G>, k_apply_filter_pix_signals<LD, G>   the same filter stage with 1-4 float planes riding along
 //
 // Arithmetic at 16 bits. dv = v_i - v_j is exact in f32 (|dv| < 2^16), dv^2 is not (up to 32 bits): it is rounded once (relative
 // error <= 2^-24), and so is the exponent t = s_val dv^2 + s_loc q (q = dr^2 + dc^2 exact) in its fma, so t carries a relative error
@@ -217,6 +218,168 @@ int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0,
     const dim3 grid((unsigned)nblk);
     if (gen == PixGen::Rgb) launch_apply_filter_pix<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
     else launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+// ---- joint filtering: float planes through the guide's filter (glf_image_processing_rgb_signals / _u16_signals) --------------------
+// The filter stage with planes makes the two passes over Phi that it makes without them: one forms c for the guide's channels and
+// the planes together, one forms every output. Each channel and each plane is an accumulator chain of its own, in the order it has
+// when it runs alone: the guide's results keep the bits of the plain call, a plane's do not depend on the planes beside it.
+
+// part_g[blk][k][j] = sum_{px in blk} Phi[px][j] * x_k[px] for the guide's NCH channels, part_s[blk][k][j] the same for the nsig
+// planes: k_phi_t_signals' block partition (1024 pixels), f64 fma chains and LDS order per plane, one read of Phi for all of them.
+// The guide's values are read from the image: (double)x is what the plain call's float plane holds.
+template <PixGen G>
+__global__ __launch_bounds__(256) void k_phi_t_pix_signals(const float *__restrict__ phi, const uint8_t *__restrict__ img_bytes,
+                                                            const float *__restrict__ sig, int64_t N, int nsig, int64_t pix0, int64_t pix1,
+                                                            unsigned ld, double *__restrict__ part_g, double *__restrict__ part_s)
+{
+    using P = Pix<G>;
+    constexpr int NCH = P::NCH;
+    const typename P::In *img = reinterpret_cast<const typename P::In *>(img_bytes);
+    __shared__ double sh[NCH + GLF_MAX_SIGNALS][256];
+    const int col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld;
+    const int64_t base = pix0 + (int64_t)blockIdx.x * 1024;
+    double g[NCH], s[GLF_MAX_SIGNALS];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) g[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k) s[k] = 0.0;
+    for (int64_t r = rl; r < 1024; r += nrl) {
+        const int64_t px = base + r;
+        if (px >= pix1) break;
+        const double f = (double)phi[(size_t)px * ld + col];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) g[k] = fma(f, (double)img[NCH * px + k], g[k]);
+#pragma unroll
+        for (int k = 0; k < GLF_MAX_SIGNALS; ++k)
+            if (k < nsig) s[k] = fma(f, (double)sig[(size_t)k * N + px], s[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) sh[k][threadIdx.x] = g[k];
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k) sh[NCH + k][threadIdx.x] = s[k];
+    __syncthreads();
+    if (threadIdx.x < ld)
+        for (int k = 0; k < NCH + nsig; ++k) {
+            double t = 0.0;
+            for (int r = 0; r < nrl; ++r) t += sh[k][r * ld + col];
+            if (k < NCH) part_g[((size_t)blockIdx.x * NCH + k) * ld + col] = t;
+            else part_s[((size_t)blockIdx.x * nsig + (k - NCH)) * ld + col] = t;
+        }
+}
+
+int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_t *d_img, const float *d_sig, int64_t N, int nsig,
+                      int64_t pix0, int64_t pix1, unsigned ld, double *d_c, double *d_cs)
+{
+    if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "phi_t_pix_signals: the 8-bit grey format has kernels of its own");
+    if (!valid_ld(ld) || pix0 > pix1 || nsig < 1 || nsig > GLF_MAX_SIGNALS)
+        return set_error(ctx, GLF_ERR_INVALID, "phi_t_pix_signals: ld=%u nsig=%d", ld, nsig);
+    const int nch = pix_channels(gen);
+    if (pix0 == pix1) {
+        GLF_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof(double) * ld * nch, ctx->stream));
+        GLF_HIP(ctx, hipMemsetAsync(d_cs, 0, sizeof(double) * ld * nsig, ctx->stream));
+        return GLF_OK;
+    }
+    const int nblk = (int)ceil_div(pix1 - pix0, 1024);
+    DevBuf<double> part_g, part_s;
+    GLF_TRY(part_g.alloc(ctx, (size_t)nblk * nch * ld));
+    GLF_TRY(part_s.alloc(ctx, (size_t)nblk * nsig * ld));
+    if (gen == PixGen::Rgb)
+        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::Rgb>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
+                           part_g.p, part_s.p);
+    else
+        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::U16>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
+                           part_g.p, part_s.p);
+    GLF_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(k_cols_sum, dim3(ld * nch), dim3(256), 0, ctx->stream, part_g.p, nblk, ld * nch, d_c);
+    hipLaunchKernelGGL(k_cols_sum, dim3(ld * nsig), dim3(256), 0, ctx->stream, part_s.p, nblk, ld * nsig, d_cs);
+    GLF_LAUNCH_CHECK(ctx);
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // the partials are released at scope exit
+    return GLF_OK;
+}
+
+// Each Phi row loaded once for the guide's channels and the planes. The channels: k_apply_filter_pix's arithmetic, statement for
+// statement. Plane k of pixel px: out = (float)(s + (gain * Phi[px] . w_k - ysub * s)) in f64 (the dot product for the reason given
+// above k_apply_filter_pix), not clamped. w [NCH + nsig][LD], the channels' weights first.
+template <int LD, PixGen G>
+__global__ __launch_bounds__(256) void k_apply_filter_pix_signals(const float *__restrict__ phi, int64_t pix0, int64_t pix1, int nsig,
+                                                                   const float *__restrict__ w, float gain, float ysub,
+                                                                   const uint8_t *__restrict__ img_bytes, uint8_t *__restrict__ out_bytes,
+                                                                   float *__restrict__ zf, const float *__restrict__ sig,
+                                                                   float *__restrict__ sig_out, int64_t N)
+{
+    using P = Pix<G>;
+    constexpr int NCH = P::NCH, LPP = LD / 4, PPB = 256 / LPP;
+    const typename P::In *img = reinterpret_cast<const typename P::In *>(img_bytes);
+    typename P::Out *out = reinterpret_cast<typename P::Out *>(out_bytes);
+    const int q = threadIdx.x % LPP, pl = threadIdx.x / LPP;
+    float4 wq[NCH], ws[GLF_MAX_SIGNALS];
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) wq[k] = reinterpret_cast<const float4 *>(w + (size_t)k * LD)[q];
+#pragma unroll
+    for (int k = 0; k < GLF_MAX_SIGNALS; ++k)
+        ws[k] = k < nsig ? reinterpret_cast<const float4 *>(w + (size_t)(NCH + k) * LD)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int64_t px = pix0 + (int64_t)blockIdx.x * PPB + pl; px < pix1; px += (int64_t)gridDim.x * PPB) {
+        const float4 f = reinterpret_cast<const float4 *>(phi + (size_t)px * LD)[q];
+#pragma unroll
+        for (int k = 0; k < NCH; ++k) {
+            double s = (double)f.x * wq[k].x + (double)f.y * wq[k].y + (double)f.z * wq[k].z + (double)f.w * wq[k].w;
+#pragma unroll
+            for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (q == 0) {
+                const int x = (int)img[NCH * px + k];
+                const double c = (double)gain * s - (double)ysub * (double)x;
+                if (zf) zf[(size_t)k * N + px] = (float)((double)x + c);
+                out[NCH * px + k] = P::output(x, c);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < GLF_MAX_SIGNALS; ++k) {
+            if (k >= nsig) break;
+            double s = (double)f.x * ws[k].x + (double)f.y * ws[k].y + (double)f.z * ws[k].z + (double)f.w * ws[k].w;
+#pragma unroll
+            for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (q == 0) {
+                const double v = (double)sig[(size_t)k * N + px];
+                sig_out[(size_t)k * N + px] = (float)(v + ((double)gain * s - (double)ysub * v));
+            }
+        }
+    }
+}
+
+template <PixGen G>
+static void launch_apply_filter_pix_signals(unsigned ld, dim3 grid, hipStream_t st, const float *d_phi, int64_t pix0, int64_t pix1, int nsig,
+                                            const float *d_w, float gain, float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf,
+                                            const float *d_sig, float *d_sig_out, int64_t N)
+{
+    switch (ld) {
+    case 32: hipLaunchKernelGGL((k_apply_filter_pix_signals<32, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N); break;
+    case 64: hipLaunchKernelGGL((k_apply_filter_pix_signals<64, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N); break;
+    case 128: hipLaunchKernelGGL((k_apply_filter_pix_signals<128, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N); break;
+    case 256: hipLaunchKernelGGL((k_apply_filter_pix_signals<256, G>), grid, dim3(256), 0, st, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N); break;
+    }
+}
+
+int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w,
+                             float gain, float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, const float *d_sig, float *d_sig_out,
+                             int64_t N)
+{
+    if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "apply_filter_pix_signals: the 8-bit grey format has kernels of its own");
+    if (!valid_ld(ld) || pix0 > pix1 || nsig < 1 || nsig > GLF_MAX_SIGNALS)
+        return set_error(ctx, GLF_ERR_INVALID, "apply_filter_pix_signals: ld=%u nsig=%d", ld, nsig);
+    if (pix0 == pix1) return GLF_OK;
+    const int ppb = 256 / (ld / 4);
+    int64_t nblk = ceil_div(pix1 - pix0, ppb);
+    if (nblk > 8192) nblk = 8192; // grid-stride the rest
+    const dim3 grid((unsigned)nblk);
+    if (gen == PixGen::Rgb)
+        launch_apply_filter_pix_signals<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
+                                                     d_sig_out, N);
+    else
+        launch_apply_filter_pix_signals<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
+                                                     d_sig_out, N);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

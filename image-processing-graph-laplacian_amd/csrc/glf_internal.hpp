@@ -452,6 +452,15 @@ int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int wi
 int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float *d_planes);
 int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, const float *d_w, float gain,
                      float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, int64_t N);
+// joint filtering under a colour or 16-bit guide (glf_image_processing_rgb_signals / _u16_signals): the guide's channels and nsig
+// float planes (d_sig / d_sig_out [nsig][N]) in two passes over Phi. phi_t_pix_signals: d_c [NCH][ld] and d_cs [nsig][ld] (f64) =
+// Phi^T x over this rank's pixels, the guide's with the bits phi_t_signals gives on its float planes. apply_filter_pix_signals:
+// d_w [NCH + nsig][ld], the guide's weights first; the guide's outputs are those of apply_filter_pix
+int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_t *d_img, const float *d_sig, int64_t N, int nsig,
+                      int64_t pix0, int64_t pix1, unsigned ld, double *d_c, double *d_cs);
+int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w,
+                             float gain, float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, const float *d_sig, float *d_sig_out,
+                             int64_t N);
 int laplacian_from_KA(glf_ctx *ctx, const float *d_KA, int64_t ldk, unsigned p, float *d_LA, int64_t ld,
                       double alpha, const double *d_degree);
 
@@ -568,6 +577,8 @@ int permute_rows(glf_ctx *ctx, const float *d_in, float *d_out, int64_t N, unsig
                  const uint32_t *d_idx, unsigned p);
 
 // filter.hip
+// out[c] = sum over the rows r of in[r][c], one workgroup per column, in an order that depends on nrows alone
+__global__ void k_cols_sum(const double *__restrict__ in, int nrows, unsigned ld, double *__restrict__ out);
 int phi_t_y(glf_ctx *ctx, const float *d_phi, const uint8_t *d_img, int64_t pix0, int64_t pix1, unsigned m,
             unsigned ld, double *d_c);
 int phi_gram(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, double *d_G); // Phi^T Phi (f64 [ld][ld])

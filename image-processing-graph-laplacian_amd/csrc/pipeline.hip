@@ -488,7 +488,8 @@ struct SignalPlanes {
 };
 
 // gen: the guide's pixel format; d_img and d_out are [N] pixels of it. A colour or 16-bit guide has no 8-bit y: its channels are
-// filtered as planes (formed inside from the image) and written to d_out.
+// filtered as planes (formed inside from the image) and written to d_out; sig there: float planes that ride along in the same two
+// passes over Phi (glf_image_processing_rgb_signals / _u16_signals).
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
                                 uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
 
@@ -532,6 +533,25 @@ int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const
     if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     return image_processing_run(ctx, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(d_img), width, height,
                                 reinterpret_cast<uint8_t *>(d_out), d_zf, eigvals_out, stats, cap, nullptr);
+}
+
+int glf_image_processing_rgb_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, int nsig,
+                                     const float *d_sig, float *d_sig_out, uint8_t *d_out_rgb, float *d_zf, double *eigvals_out,
+                                     glf_stats *stats)
+{
+    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
+    const SignalPlanes sig{nsig, d_sig, d_sig_out};
+    return image_processing_run(ctx, opt, PixGen::Rgb, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr, &sig);
+}
+
+int glf_image_processing_u16_signals(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, int nsig,
+                                     const float *d_sig, float *d_sig_out, uint16_t *d_out, float *d_zf, double *eigvals_out,
+                                     glf_stats *stats)
+{
+    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
+    const SignalPlanes sig{nsig, d_sig, d_sig_out};
+    return image_processing_run(ctx, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(d_img), width, height,
+                                reinterpret_cast<uint8_t *>(d_out), d_zf, eigvals_out, stats, nullptr, &sig);
 }
 
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
@@ -590,10 +610,14 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     glf_stats S{};
     DevBuf<float> guide_planes; // colour: the channels as float planes [3][N] (Phi^T x_c); 16-bit: the image as one plane
     SignalPlanes guide_sig{};
+    const SignalPlanes *planes = nullptr; // a colour or 16-bit guide's extra planes (its own kernels read the channels from the image)
     if (!u8_guide) {
         const int nch = pix_channels(gen);
-        GLF_TRY(guide_planes.alloc(ctx, (size_t)nch * N));
-        GLF_TRY(pix_planes(ctx, gen, d_img, N, guide_planes.p));
+        planes = sig;
+        if (!planes) {
+            GLF_TRY(guide_planes.alloc(ctx, (size_t)nch * N));
+            GLF_TRY(pix_planes(ctx, gen, d_img, N, guide_planes.p));
+        }
         guide_sig = SignalPlanes{nch, guide_planes.p, nullptr};
         sig = &guide_sig;
     }
@@ -1061,6 +1085,38 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
                 GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
         }
         const int ns = sig->nsig;
+        if (planes) { // colour or 16-bit guide with planes: c for the channels and the planes in one pass over Phi, the outputs in one more
+            const int np = planes->nsig;
+            DevBuf<double> cg, cp;
+            DevBuf<float> wa;
+            GLF_TRY(cg.alloc(ctx, (size_t)ns * ld));
+            GLF_TRY(cp.alloc(ctx, (size_t)np * ld));
+            GLF_TRY(wa.alloc(ctx, (size_t)(ns + np) * ld));
+            GLF_TRY(phi_t_pix_signals(ctx, gen, phi_rows, d_img, planes->d_sig, N, np, pix0, pix1, ld, cg.p, cp.p));
+            GLF_TRY(allreduce_f64(ctx, cg.p, (size_t)ns * ld)); // the guide's collective, with the shape it has in the plain call
+            GLF_TRY(allreduce_f64(ctx, cp.p, (size_t)np * ld)); // the planes' in one of their own (a ring's summation order may follow the layout)
+            std::vector<double> hca((size_t)(ns + np) * ld);
+            GLF_HIP(ctx, hipMemcpyAsync(hca.data(), cg.p, sizeof(double) * ns * ld, hipMemcpyDeviceToHost, st));
+            GLF_HIP(ctx, hipMemcpyAsync(hca.data() + (size_t)ns * ld, cp.p, sizeof(double) * np * ld, hipMemcpyDeviceToHost, st));
+            GLF_HIP(ctx, hipStreamSynchronize(st));
+            std::vector<float> hwa((size_t)(ns + np) * ld, 0.f);
+            for (int k = 0; k < ns + np; ++k) {
+                const double *hc = hca.data() + (size_t)k * ld;
+                float *hw = hwa.data() + (size_t)k * ld;
+                if (opt.filter_mode == GLF_FILTER_SHARPEN) sharpen_weights(hc, hw);
+                else
+                    for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
+            }
+            GLF_HIP(ctx, hipMemcpyAsync(wa.p, hwa.data(), sizeof(float) * (ns + np) * ld, hipMemcpyHostToDevice, st));
+            GLF_TRY(apply_filter_pix_signals(ctx, gen, phi_rows, pix0, pix1, ld, np, wa.p, filter_gain, filter_ysub, d_img, d_out, d_zf,
+                                             planes->d_sig, planes->d_out, N));
+            GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
+            GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
+            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
+            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
+            if (stats) *stats = S;
+            return GLF_OK;
+        }
         if (sig_fused) { // (the band launch fell back after c_s was formed: its weights stand, c_s's collective is not repeated)
             GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
             GLF_HIP(ctx, hipStreamSynchronize(st));

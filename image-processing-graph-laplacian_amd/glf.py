@@ -53,6 +53,8 @@ EXPORTS = [
     "glf_image_processing_signals", "glf_multi_image_processing_signals",
     "glf_image_processing_rgb", "glf_multi_image_processing_rgb", "glf_image_processing_rgb_capture",
     "glf_image_processing_u16", "glf_multi_image_processing_u16", "glf_image_processing_u16_capture", "glf_read_png16", "glf_write_png16",
+    "glf_image_processing_rgb_signals", "glf_image_processing_u16_signals",
+    "glf_multi_image_processing_rgb_signals", "glf_multi_image_processing_u16_signals",
 ]
 MAX_SIGNALS = 4
 
@@ -411,6 +413,41 @@ class Multi:
         out = np.zeros((h, w), dtype=np.uint16)
         zf = np.zeros((h, w), dtype=np.float32) if want_float else None
         return out, zf, self._run("glf_multi_image_processing_u16", opt, img, out, zf)
+
+    def image_processing_rgb_signals(self, img, signals, opt=None, want_float=False):
+        """glf_multi_image_processing_rgb_signals: host uint8 [H, W, 3] plus float planes [nsig, H, W] filtered through the colour
+        graph. Returns (out u8 [H, W, 3], zf f32 [3, H, W] or None, sig_out f32 [nsig, H, W], infos)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
+        h, w = img.shape[:2]
+        sig, sig_out = self._planes(signals, h, w)
+        opt = opt or default_options()
+        out = np.zeros((h, w, 3), dtype=np.uint8)
+        zf = np.zeros((3, h, w), dtype=np.float32) if want_float else None
+        infos = self._run("glf_multi_image_processing_rgb_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
+        return out, zf, sig_out, infos
+
+    def image_processing_u16_signals(self, img, signals, opt=None, want_float=False):
+        """glf_multi_image_processing_u16_signals: host uint16 [H, W] plus float planes [nsig, H, W] filtered through the 16-bit
+        graph. Returns (out uint16 [H, W], zf f32 [H, W] or None, sig_out f32 [nsig, H, W], infos)."""
+        img = np.ascontiguousarray(img, dtype=np.uint16)
+        if img.ndim != 2:
+            raise ValueError("image must be [H, W], got %s" % (img.shape,))
+        h, w = img.shape
+        sig, sig_out = self._planes(signals, h, w)
+        opt = opt or default_options()
+        out = np.zeros((h, w), dtype=np.uint16)
+        zf = np.zeros((h, w), dtype=np.float32) if want_float else None
+        infos = self._run("glf_multi_image_processing_u16_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
+        return out, zf, sig_out, infos
+
+    @staticmethod
+    def _planes(signals, h, w):
+        sig = np.ascontiguousarray(signals, dtype=np.float32)
+        if sig.ndim != 3 or sig.shape[1:] != (h, w):
+            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, sig.shape))
+        return sig, np.zeros(sig.shape, dtype=np.float32)
 
     def comm_counters(self, rank=0, reset=True):
         """Collectives rank `rank` issued since the last reset: dict(allreduce_calls, allreduce_bytes, allgather_calls, allgather_bytes)."""
@@ -841,6 +878,46 @@ class Context:
             out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
         return out, zf, self._run("glf_image_processing_u16_capture", "image_processing_u16", opt, d_img, out, zf, capture)
+
+    def image_processing_rgb_signals(self, d_rgb, signals, opt=None, want_float=False):
+        """Joint filtering under a colour guide (glf_image_processing_rgb_signals): d_rgb (device uint8 [H, W, 3]) defines the graph
+        and is filtered as by image_processing_rgb; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same
+        operator. Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing_rgb."""
+        torch = self.torch
+        assert d_rgb.dtype == torch.uint8 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
+        h, w = d_rgb.shape[:2]
+        opt = opt or default_options()
+        sig_out, sig = self._signal_planes(signals, h, w)
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w, 3), dtype=torch.uint8, device=self.device)
+            zf = torch.zeros((3, h, w), dtype=torch.float32, device=self.device) if want_float else None
+        info = self._run("glf_image_processing_rgb_signals", "image_processing_rgb_signals", opt, d_rgb, out, zf, sig=sig)
+        return out, zf, sig_out, info
+
+    def image_processing_u16_signals(self, d_img, signals, opt=None, want_float=False):
+        """Joint filtering under a 16-bit guide (glf_image_processing_u16_signals): as image_processing_rgb_signals with the graph
+        and the outputs of image_processing_u16 (d_img device uint16 [H, W])."""
+        torch = self.torch
+        assert d_img.dtype == torch.uint16 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
+        h, w = d_img.shape
+        opt = opt or default_options()
+        sig_out, sig = self._signal_planes(signals, h, w)
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
+            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
+        info = self._run("glf_image_processing_u16_signals", "image_processing_u16_signals", opt, d_img, out, zf, sig=sig)
+        return out, zf, sig_out, info
+
+    def _signal_planes(self, signals, h, w):
+        """The zero-filled result planes and the (nsig, planes, planes out) arguments of a signals entry point."""
+        torch = self.torch
+        assert signals.dtype == torch.float32 and signals.is_cuda and signals.dim() == 3 and signals.is_contiguous()
+        if tuple(signals.shape[1:]) != (h, w):
+            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, tuple(signals.shape)))
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image and the planes are complete before the library reads them
+        with torch.cuda.stream(self.stream):
+            sig_out = torch.zeros(tuple(signals.shape), dtype=torch.float32, device=self.device)
+        return sig_out, (C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()), C.c_void_p(sig_out.data_ptr()))
 
     def _capture_buffers(self, w, h, opt, p_real, grey=False):
         """glf_capture with phi_A, phi (this rank's rows) and the degree vector -- grey: also c = Phi^T y and the correction -- and

@@ -9,6 +9,7 @@
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
  *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16] [-pix_band]
+ *                    [-planes F1[,F2[,F3[,F4]]]]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
  * (python/image_processing.py:197-241, B = 1.5) with W = Phi diag(1 - mu) Phi^T from the eigenpairs this program computes.
@@ -25,6 +26,11 @@
  * -pix_band (with -depth16 or -color -rgb_graph) sets the PIX_BAND tuning key: the 16-bit / colour kernel takes the band form
  * of the Nystroem stage and of the operator wherever the grey kernel would (GLF_PIX_BAND=1 in the environment does the same), and
  * one more line names the routes taken ("band form: nystroem_path 4, matvec_path 4", or the fallback's numbers).
+ * -planes F1[,F2[,F3[,F4]]] (with -depth16 or -color -rgb_graph) is joint filtering: each file is a grey PNG of the image's size (16
+ * or 8 bits; a depth map, an alpha matte, ...) whose pixel values go as a float plane through the 16-bit / colour image's graph with
+ * the same -filter (glf_image_processing_u16_signals / glf_image_processing_rgb_signals; with -depth16 -ngpu N the glf_multi_ call).
+ * Plane k (from 0) is written to results/plane_<k>.png at its input's bit depth as clamp(floor(z + 0.5)); results/output.png is the
+ * one of the run without -planes. One more line says how many planes went through which graph.
  * -dump_residual writes results/residuals.png = |input - output| stretched to the full grey range, the PoC's residual image
  * (python/image_processing.py:378-380: plt.imsave of np.abs(y - z) with cmap 'gray' autoscales min..max).
  * -no_approx runs the full-matrix mode (hpc/image_processing.c:155-181); -use_slepc is accepted and refused.
@@ -37,6 +43,7 @@
  * The approximate path runs the tail the reference left commented out
  * (hpc/image_processing.c:240-275) as its specification (survey quirk Q1).
  */
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -324,6 +331,93 @@ static void pix_band_report(const glf_stats *st)
     if (opt_has("-pix_band")) printf("band form: nystroem_path %d, matvec_path %d\n", (int)st->nystroem_path, (int)st->matvec_path);
 }
 
+/* -planes: up to GLF_MAX_SIGNALS grey PNGs of the image's size as float planes [nsig][height*width]. A file that cannot be read or
+ * has another size ends the program with status 1. */
+static int g_nplanes;
+static int g_plane_bits[GLF_MAX_SIGNALS];
+static float *g_planes, *g_planes_out;
+
+static void planes_fail(void)
+{
+    FinalizeProgram();
+    exit(1);
+}
+
+static void planes_load(unsigned width, unsigned height)
+{
+    const char *v = opt_value("-planes");
+    if (!v) return;
+    const size_t n = (size_t)width * height;
+    char *list = strdup(v);
+    g_planes = (float *)malloc(sizeof(float) * GLF_MAX_SIGNALS * n);
+    g_planes_out = (float *)calloc(GLF_MAX_SIGNALS * n, sizeof(float));
+    if (!list || !g_planes || !g_planes_out) {
+        fprintf(stderr, "-planes: out of memory\n");
+        planes_fail();
+    }
+    for (char *name = strtok(list, ","); name; name = strtok(NULL, ",")) {
+        if (g_nplanes == GLF_MAX_SIGNALS) {
+            fprintf(stderr, "-planes takes at most %d files\n", GLF_MAX_SIGNALS);
+            planes_fail();
+        }
+        float *dst = g_planes + (size_t)g_nplanes * n;
+        uint16_t **r16 = NULL;
+        uint8_t **r8 = NULL;
+        int w = 0, h = 0;
+        if (glf_read_png16(name, &r16, &w, &h) == 0) g_plane_bits[g_nplanes] = 16;
+        else if (glf_read_png(name, &r8, &w, &h) == 0) g_plane_bits[g_nplanes] = 8;
+        else {
+            fprintf(stderr, "-planes: could not read %s as a grey PNG\n", name);
+            planes_fail();
+        }
+        if (w != (int)width || h != (int)height) {
+            fprintf(stderr, "-planes: %s is %dx%d, the image %ux%u\n", name, w, h, width, height);
+            planes_fail();
+        }
+        for (unsigned r = 0; r < height; ++r)
+            for (unsigned c = 0; c < width; ++c) dst[(size_t)r * width + c] = r16 ? (float)r16[r][c] : (float)r8[r][c];
+        for (int r = 0; r < h; ++r) free(r16 ? (void *)r16[r] : (void *)r8[r]);
+        free(r16 ? (void *)r16 : (void *)r8);
+        ++g_nplanes;
+    }
+    free(list);
+    if (g_nplanes == 0) {
+        fprintf(stderr, "-planes needs at least one file\n");
+        planes_fail();
+    }
+}
+
+/* results/plane_<k>.png = clamp(floor(z_k + 0.5)) at the input plane's bit depth; returns 0, or 4 when a file could not be written */
+static int planes_write(unsigned width, unsigned height, const char *graph)
+{
+    const size_t n = (size_t)width * height;
+    int status = 0;
+    for (int k = 0; k < g_nplanes; ++k) {
+        const float *z = g_planes_out + (size_t)k * n;
+        const double vmax = g_plane_bits[k] == 16 ? 65535.0 : 255.0;
+        char name[64];
+        snprintf(name, sizeof(name), "results/plane_%d.png", k);
+        void **rows = (void **)calloc(height, sizeof(void *));
+        for (unsigned r = 0; rows && r < height; ++r) {
+            rows[r] = malloc((size_t)width * (g_plane_bits[k] == 16 ? 2 : 1));
+            for (unsigned c = 0; rows[r] && c < width; ++c) {
+                double x = floor((double)z[(size_t)r * width + c] + 0.5);
+                x = x >= 0.0 ? (x > vmax ? vmax : x) : 0.0;
+                if (g_plane_bits[k] == 16) ((uint16_t *)rows[r])[c] = (uint16_t)x;
+                else ((uint8_t *)rows[r])[c] = (uint8_t)x;
+            }
+        }
+        if (!rows || (g_plane_bits[k] == 16 ? glf_write_png16(name, (uint16_t **)rows, width, height)
+                                            : glf_write_png(name, (uint8_t **)rows, width, height)) != 0)
+            status = 4;
+        for (unsigned r = 0; rows && r < height; ++r) free(rows[r]);
+        free(rows);
+    }
+    printf("Planes: %d plane%s filtered through the %s graph (filter %s)\n", g_nplanes, g_nplanes == 1 ? "" : "s", graph,
+           opt_value("-filter") ? opt_value("-filter") : "reference");
+    return status;
+}
+
 /* -depth16: img (rows of `width` uint16_t) through glf_image_processing_u16 on one context, or glf_multi_image_processing_u16 on
  * ngpu ranks; returns the output rows (NULL on failure, the message printed). */
 static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned height, int ngpu, int backend)
@@ -349,7 +443,9 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         if (rc != GLF_OK) fprintf(stderr, "glf_multi_create(%d GPUs, %s): %s\n", ngpu, backend == GLF_MULTI_RCCL ? "rccl" : "loopback", glf_strerror(rc));
         else if (st) {
             for (int r = 0; r < ngpu; ++r) pix_band_set(glf_multi_ctx(world, r));
-            rc = glf_multi_image_processing_u16(world, &opt, flat, (int)width, (int)height, flat_out, NULL, NULL, st);
+            rc = g_nplanes ? glf_multi_image_processing_u16_signals(world, &opt, flat, (int)width, (int)height, g_nplanes, g_planes, g_planes_out,
+                                                                    flat_out, NULL, NULL, st)
+                           : glf_multi_image_processing_u16(world, &opt, flat, (int)width, (int)height, flat_out, NULL, NULL, st);
             if (rc != GLF_OK) fprintf(stderr, "glf_multi_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_multi_last_error(world));
             else {
                 print_stage_times(&st[0], opt.epsilon);
@@ -363,15 +459,22 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         if (world) glf_multi_destroy(world);
     } else if (ok) {
         glf_ctx *ctx = glf_world();
-        void *d_img = NULL, *d_out = NULL;
+        void *d_img = NULL, *d_out = NULL, *d_sig = NULL, *d_sig_out = NULL;
+        const size_t sig_bytes = sizeof(float) * n * (size_t)g_nplanes;
         glf_stats st;
         ok = glf_malloc(ctx, &d_img, sizeof(uint16_t) * n) == GLF_OK && glf_malloc(ctx, &d_out, sizeof(uint16_t) * n) == GLF_OK &&
              glf_memcpy_h2d(ctx, d_img, flat, sizeof(uint16_t) * n) == GLF_OK;
+        if (ok && g_nplanes)
+            ok = glf_malloc(ctx, &d_sig, sig_bytes) == GLF_OK && glf_malloc(ctx, &d_sig_out, sig_bytes) == GLF_OK &&
+                 glf_memcpy_h2d(ctx, d_sig, g_planes, sig_bytes) == GLF_OK;
         if (ok) {
             pix_band_set(ctx);
-            const int rc = glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
+            const int rc = g_nplanes ? glf_image_processing_u16_signals(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, g_nplanes,
+                                                                        (const float *)d_sig, (float *)d_sig_out, (uint16_t *)d_out, NULL, NULL, &st)
+                                     : glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
             if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(ctx));
-            ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, sizeof(uint16_t) * n) == GLF_OK;
+            ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, sizeof(uint16_t) * n) == GLF_OK &&
+                 (!g_nplanes || glf_memcpy_d2h(ctx, g_planes_out, d_sig_out, sig_bytes) == GLF_OK);
             if (ok) {
                 print_stage_times(&st, opt.epsilon);
                 pix_band_report(&st);
@@ -379,6 +482,8 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         }
         if (d_img) glf_free(ctx, d_img);
         if (d_out) glf_free(ctx, d_out);
+        if (d_sig) glf_free(ctx, d_sig);
+        if (d_sig_out) glf_free(ctx, d_sig_out);
     }
     if (ok) {
         rows = (uint16_t **)calloc(height, sizeof(uint16_t *));
@@ -417,19 +522,29 @@ static png_bytep *ColorComputation(const char *filename, unsigned *width_out, un
         printf("Read image %s of size %dx%d => %d pixels (colour: graph from the RGB differences, R, G, B filtered)\n", filename, w, h, w * h);
         glf_ctx *cctx = glf_world();
         uint8_t *flat = (uint8_t *)malloc(3 * n);
-        void *d_rgb = NULL, *d_rgb_out = NULL;
+        void *d_rgb = NULL, *d_rgb_out = NULL, *d_sig = NULL, *d_sig_out = NULL;
         glf_options copt;
         glf_stats cst;
         fill_options(&copt, (unsigned)w, (unsigned)h);
+        planes_load((unsigned)w, (unsigned)h);
+        const size_t sig_bytes = sizeof(float) * n * (size_t)g_nplanes;
         int ok = flat && glf_malloc(cctx, &d_rgb, 3 * n) == GLF_OK && glf_malloc(cctx, &d_rgb_out, 3 * n) == GLF_OK;
         for (int r = 0; ok && r < h; ++r) memcpy(flat + (size_t)r * 3 * w, rgb[r], 3 * (size_t)w);
         ok = ok && glf_memcpy_h2d(cctx, d_rgb, flat, 3 * n) == GLF_OK;
+        if (ok && g_nplanes)
+            ok = glf_malloc(cctx, &d_sig, sig_bytes) == GLF_OK && glf_malloc(cctx, &d_sig_out, sig_bytes) == GLF_OK &&
+                 glf_memcpy_h2d(cctx, d_sig, g_planes, sig_bytes) == GLF_OK;
         if (ok) {
             pix_band_set(cctx);
-            const int rc = glf_image_processing_rgb(cctx, &copt, (const uint8_t *)d_rgb, w, h, (uint8_t *)d_rgb_out, NULL, NULL, &cst);
+            const int rc = g_nplanes ? glf_image_processing_rgb_signals(cctx, &copt, (const uint8_t *)d_rgb, w, h, g_nplanes, (const float *)d_sig,
+                                                                        (float *)d_sig_out, (uint8_t *)d_rgb_out, NULL, NULL, &cst)
+                                     : glf_image_processing_rgb(cctx, &copt, (const uint8_t *)d_rgb, w, h, (uint8_t *)d_rgb_out, NULL, NULL, &cst);
             if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_rgb: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(cctx));
-            ok = rc == GLF_OK && glf_memcpy_d2h(cctx, flat, d_rgb_out, 3 * n) == GLF_OK;
+            ok = rc == GLF_OK && glf_memcpy_d2h(cctx, flat, d_rgb_out, 3 * n) == GLF_OK &&
+                 (!g_nplanes || glf_memcpy_d2h(cctx, g_planes_out, d_sig_out, sig_bytes) == GLF_OK);
         }
+        if (d_sig) glf_free(cctx, d_sig);
+        if (d_sig_out) glf_free(cctx, d_sig_out);
         if (ok) {
             print_stage_times(&cst, copt.epsilon);
             pix_band_report(&cst);
@@ -635,6 +750,11 @@ int main(int argc, char **argv)
         FinalizeProgram();
         return 1;
     }
+    if (opt_has("-planes") && !opt_has("-depth16") && !(opt_has("-color") && opt_has("-rgb_graph"))) {
+        fprintf(stderr, "-planes filters extra planes through the 16-bit or the colour graph: it needs -depth16 or -color -rgb_graph\n");
+        FinalizeProgram();
+        return 1;
+    }
     if (opt_has("-depth16")) { /* 16-bit grey: its own reader, route and writer */
         uint16_t **in16 = NULL, **out16 = NULL;
         if (glf_read_png16(filename, &in16, &width, &height) != 0) {
@@ -650,11 +770,13 @@ int main(int argc, char **argv)
         }
         if (!opt_value("-h_val")) stage_h_val = 30.0f * 257.0f; /* the 8-bit default graph on the same content */
         printf("Read image %s of size %dx%d => %d pixels (16-bit gray)\n", filename, width, height, width * height);
+        planes_load((unsigned)width, (unsigned)height);
         out16 = Depth16Computation(in16, (unsigned)width, (unsigned)height, ngpu,
                                    nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL);
         int dstatus = out16 ? 0 : 5;
         if (glf_write_png16("results/input.png", in16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
         if (out16 && glf_write_png16("results/output.png", out16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
+        if (out16 && g_nplanes && planes_write((unsigned)width, (unsigned)height, "16-bit") != 0) dstatus = dstatus ? dstatus : 4;
         printf("Total computation time: %fs\n", wtime() - start_time);
         free_rows16(in16, height);
         free_rows16(out16, height);
@@ -668,6 +790,7 @@ int main(int argc, char **argv)
         int cstatus = out_rgb ? 0 : 5;
         if (in_rgb && glf_write_png_rgb("results/input.png", in_rgb, cw, ch) != 0) cstatus = cstatus ? cstatus : 4;
         if (out_rgb && glf_write_png_rgb("results/output.png", out_rgb, cw, ch) != 0) cstatus = cstatus ? cstatus : 4;
+        if (out_rgb && g_nplanes && planes_write(cw, ch, "colour") != 0) cstatus = cstatus ? cstatus : 4;
         if (!in_rgb) {
             fprintf(stderr, "Could not read %s as an 8-bit gray / RGB / RGBA PNG\n", filename);
             cstatus = 1;

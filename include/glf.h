@@ -458,6 +458,21 @@ int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t
 int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
                              float *d_zf, double *eigvals_out, glf_stats *stats);
 
+/* Joint filtering under a colour or a 16-bit guide: glf_image_processing_signals with the graph of glf_image_processing_rgb /
+ * glf_image_processing_u16 (a depth map through a colour image's graph, ...). d_out*, d_zf, eigvals_out and every non-timing field
+ * of stats are bit-identical to the plain _rgb / _u16 call's, with or without the PIX_BAND tuning key. d_sig / d_sig_out: device
+ * float [nsig][height*width], d_sig replicated on every rank; plane k comes out as z_k = (1 - ysub) s_k + gain Phi (f(Pi) Phi^T s_k),
+ * not clamped (sharpening: the Gram-matrix weights, as for the channels); with a comm rank g writes its own pixel rows only. A
+ * plane's result does not depend on the other planes. The filter stage reads Phi twice whatever nsig is: once for Phi^T of the
+ * channels and the planes together, once for all the outputs. 1 <= nsig <= GLF_MAX_SIGNALS and non-null planes, else
+ * GLF_ERR_INVALID; a kernel other than the format's bilateral one, or more than 256 eigenpairs: GLF_ERR_UNSUPPORTED. */
+int glf_image_processing_rgb_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, int nsig,
+                                     const float *d_sig, float *d_sig_out, uint8_t *d_out_rgb, float *d_zf, double *eigvals_out,
+                                     glf_stats *stats);
+int glf_image_processing_u16_signals(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, int nsig,
+                                     const float *d_sig, float *d_sig_out, uint16_t *d_out, float *d_zf, double *eigvals_out,
+                                     glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -518,6 +533,15 @@ int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const u
  * pixel rows are gathered into h_out (h_zf optional HOST float [height*width]). */
 int glf_multi_image_processing_u16(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height,
                                    uint16_t *h_out, float *h_zf, double *eigvals_out, glf_stats *stats);
+
+/* glf_multi_image_processing_rgb / _u16 with signal planes (glf_image_processing_rgb_signals / _u16_signals): h_sig and h_sig_out
+ * HOST float [nsig][height*width] as for glf_multi_image_processing_signals. */
+int glf_multi_image_processing_rgb_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height,
+                                           int nsig, const float *h_sig, float *h_sig_out, uint8_t *h_out_rgb, float *h_zf,
+                                           double *eigvals_out, glf_stats *stats);
+int glf_multi_image_processing_u16_signals(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height,
+                                           int nsig, const float *h_sig, float *h_sig_out, uint16_t *h_out, float *h_zf,
+                                           double *eigvals_out, glf_stats *stats);
 
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
