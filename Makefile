@@ -14,7 +14,7 @@ HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystr
             $(CSRC)/entrywise.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
-C_OBJS   := $(HOST)/png_codec.o
+C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
 
 all: $(PKG)/libglf.so $(PKG)/image_processing oracle
 
@@ -36,8 +36,13 @@ $(PKG)/image_processing: $(HOST)/image_processing.o $(HOST)/stages.o $(PKG)/libg
 oracle:
 	$(MAKE) -C oracle
 
+# the PFM reader under the address and undefined-behaviour sanitizers, as a stand-alone program (CPU only)
+pfm_check: tools/pfm_fuzz_main.c $(HOST)/pfm_codec.c include/glf.h
+	gcc -O1 -g -std=gnu11 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -o tools/pfm_fuzz $(filter %.c,$^) -lm
+	tools/pfm_fuzz
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean
+.PHONY: all oracle clean pfm_check

@@ -50,6 +50,7 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     case PixGen::Grey: hipLaunchKernelGGL(k_sample_tables<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     case PixGen::Rgb: hipLaunchKernelGGL(k_sample_tables<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     case PixGen::U16: hipLaunchKernelGGL(k_sample_tables<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
+    case PixGen::F32: hipLaunchKernelGGL(k_sample_tables<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     }
     GLF_LAUNCH_CHECK(ctx);
     // h_idx is pageable host memory: make sure the async copy has consumed it

@@ -1,10 +1,11 @@
 // entrywise.hip -- the pixel formats without a factored form behind the same stage API as the grey kernels: the colour bilateral
 // affinity (glf_options.kernel = GLF_KERNEL_BILATERAL_RGB, image interleaved uint8 [height][width][3]) and the bilateral affinity
-// on 16-bit grey values (GLF_KERNEL_BILATERAL_U16, image uint16_t [height][width]):
+// on 16-bit grey values (GLF_KERNEL_BILATERAL_U16, image uint16_t [height][width]) and on float values (GLF_KERNEL_BILATERAL_F32, image
+// float [height][width], any finite value):
 //
 //   K(i, j) = Es(dr) Es(dc) P(v_i - v_j) = exp2(-(s_loc (dr^2 + dc^2) + s_val |v_i - v_j|^2))
 //
-// with v the pixel's colour or 16-bit value, read and compared through the format's policy Pix<G> (glf_internal.hpp). The
+// with v the pixel's colour, 16-bit or float value, read and compared through the format's policy Pix<G> (glf_internal.hpp). The
 // photometric factor is at most 1, so every spatial bound of the grey kernels (the f32 underflow radius, the chunk boxes of the
 // Nystroem window) holds unchanged. A colour guide has 2^24 values and a 16-bit guide 65 536, so the forms that factor the sums over
 // the 256 grey levels (grid, rank, band) and the grey direct degree (a 256-entry table per sample) do not extend: those routes
@@ -21,6 +22,9 @@
 // |dK| <= K t ln2 2^-23 <= (1/e) 2^-23 ~ 4.4e-8 absolute (the maximum of x e^-x at x = 1), and v_exp_f32 adds its own ~1 ulp: every
 // entry of K_A and K_B is within ~1e-7 of the fp64 kernel, well inside 1e-6 of max|K| = 1. The colour distance is exact (integers
 // below 2^18).
+// Arithmetic on floats. dv is rounded once (2^-24 relative, exact when the two values are within a factor of two), dv^2 once more, the
+// exponent's fma once: ~3 x 2^-24 on t, |dK| <= K t ln2 x 1.8e-7 <= 7e-8, inside the same 1e-7 per entry. Inputs are finite (the entry
+// points check): P <= 1 and never NaN; a dv^2 that overflows gives exp2(-inf) = 0.
 #include "glf_internal.hpp"
 
 #include <cmath>
@@ -114,19 +118,19 @@ int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int wi
     const int radius = coef.s_loc > 0.f ? (int)std::floor(std::sqrt(151.0 / (double)coef.s_loc)) + 1 : (width + height) * 2;
     const int nchunks = (int)ceil_div(row1 - row0, EW_ROWS);
     if (nchunks > 65535)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too tall for one %s degree launch", gen == PixGen::Rgb ? "colour" : "16-bit");
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too tall for one %s degree launch", pix_name(gen));
     DevBuf<double> partial;
     DevBuf<unsigned long long> count;
     GLF_TRY(partial.alloc(ctx, (size_t)nchunks * p));
     GLF_TRY(count.alloc(ctx, 1));
     GLF_HIP(ctx, hipMemsetAsync(count.p, 0, sizeof(unsigned long long), ctx->stream));
     const dim3 grid((unsigned)ceil_div(p, 256), nchunks);
-    if (gen == PixGen::Rgb)
-        hipLaunchKernelGGL(k_degree_entrywise<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p,
-                           coef.s_loc, coef.s_val, radius, partial.p, count.p);
-    else
-        hipLaunchKernelGGL(k_degree_entrywise<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p,
-                           coef.s_loc, coef.s_val, radius, partial.p, count.p);
+#define GLF_DEGREE_EW(G_) hipLaunchKernelGGL(k_degree_entrywise<G_>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p, \
+                                             coef.s_loc, coef.s_val, radius, partial.p, count.p)
+    if (gen == PixGen::Rgb) GLF_DEGREE_EW(PixGen::Rgb);
+    else if (gen == PixGen::U16) GLF_DEGREE_EW(PixGen::U16);
+    else GLF_DEGREE_EW(PixGen::F32);
+#undef GLF_DEGREE_EW
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
     GLF_LAUNCH_CHECK(ctx);
@@ -154,7 +158,8 @@ int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float 
     if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "pix_planes: the 8-bit grey format has kernels of its own");
     const dim3 grid((unsigned)ceil_div(N, 256));
     if (gen == PixGen::Rgb) hipLaunchKernelGGL(k_planes<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
-    else hipLaunchKernelGGL(k_planes<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    else if (gen == PixGen::U16) hipLaunchKernelGGL(k_planes<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    else hipLaunchKernelGGL(k_planes<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -185,9 +190,9 @@ __global__ __launch_bounds__(256) void k_apply_filter_pix(const float *__restric
 #pragma unroll
             for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
             if (q == 0) {
-                const int x = (int)img[NCH * px + k];
-                const double c = (double)gain * s - (double)ysub * (double)x;
-                if (zf) zf[(size_t)k * N + px] = (float)((double)x + c);
+                const double x = (double)img[NCH * px + k];
+                const double c = (double)gain * s - (double)ysub * x;
+                if (zf) zf[(size_t)k * N + px] = (float)(x + c);
                 out[NCH * px + k] = P::output(x, c);
             }
         }
@@ -217,7 +222,8 @@ int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0,
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     const dim3 grid((unsigned)nblk);
     if (gen == PixGen::Rgb) launch_apply_filter_pix<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
-    else launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    else if (gen == PixGen::U16) launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    else launch_apply_filter_pix<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -289,8 +295,11 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
     if (gen == PixGen::Rgb)
         hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::Rgb>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
                            part_g.p, part_s.p);
-    else
+    else if (gen == PixGen::U16)
         hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::U16>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
+                           part_g.p, part_s.p);
+    else
+        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::F32>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
                            part_g.p, part_s.p);
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * nch), dim3(256), 0, ctx->stream, part_g.p, nblk, ld * nch, d_c);
@@ -329,9 +338,9 @@ __global__ __launch_bounds__(256) void k_apply_filter_pix_signals(const float *_
 #pragma unroll
             for (int o = LPP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
             if (q == 0) {
-                const int x = (int)img[NCH * px + k];
-                const double c = (double)gain * s - (double)ysub * (double)x;
-                if (zf) zf[(size_t)k * N + px] = (float)((double)x + c);
+                const double x = (double)img[NCH * px + k];
+                const double c = (double)gain * s - (double)ysub * x;
+                if (zf) zf[(size_t)k * N + px] = (float)(x + c);
                 out[NCH * px + k] = P::output(x, c);
             }
         }
@@ -377,10 +386,39 @@ int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64
     if (gen == PixGen::Rgb)
         launch_apply_filter_pix_signals<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
                                                      d_sig_out, N);
-    else
+    else if (gen == PixGen::U16)
         launch_apply_filter_pix_signals<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
                                                      d_sig_out, N);
+    else
+        launch_apply_filter_pix_signals<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
+                                                     d_sig_out, N);
     GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+// ---- the float format's admission check -------------------------------------------------------------------------------------
+// *bad |= 1 where a value is NaN or Inf: exponent bits all ones. Grid-strided, one flag write per wave that saw one.
+__global__ __launch_bounds__(256) void k_f32_nonfinite(const float *__restrict__ img, int64_t N, unsigned *__restrict__ bad)
+{
+    bool seen = false;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256)
+        seen |= (__float_as_uint(img[i]) & 0x7f800000u) == 0x7f800000u;
+    if (__ballot(seen) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
+}
+
+int f32_all_finite(glf_ctx *ctx, const float *d_img, int64_t N, bool *finite)
+{
+    DevBuf<unsigned> bad;
+    GLF_TRY(bad.alloc(ctx, 1));
+    GLF_HIP(ctx, hipMemsetAsync(bad.p, 0, sizeof(unsigned), ctx->stream));
+    int64_t nblk = ceil_div(N, 256);
+    if (nblk > 4096) nblk = 4096;
+    hipLaunchKernelGGL(k_f32_nonfinite, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_img, N, bad.p);
+    GLF_LAUNCH_CHECK(ctx);
+    unsigned h_bad = 0;
+    GLF_HIP(ctx, hipMemcpyAsync(&h_bad, bad.p, sizeof(h_bad), hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *finite = h_bad == 0;
     return GLF_OK;
 }
 

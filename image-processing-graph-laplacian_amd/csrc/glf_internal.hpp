@@ -253,22 +253,24 @@ __device__ __forceinline__ uint16_t filter_output_u16(int x, double c)
 }
 
 // The pixel formats. Grey: uint8 [N] (GLF_KERNEL_BILATERAL and the other 8-bit kernels); Rgb: interleaved uint8 [N][3]
-// (GLF_KERNEL_BILATERAL_RGB); U16: uint16 [N] (GLF_KERNEL_BILATERAL_U16). The image travels as a byte pointer; the entry-by-entry
+// (GLF_KERNEL_BILATERAL_RGB); U16: uint16 [N] (GLF_KERNEL_BILATERAL_U16); F32: float [N] (GLF_KERNEL_BILATERAL_F32, any finite
+// value, h_val in the image's units). The image travels as a byte pointer; the entry-by-entry
 // kernels read it through the format's policy Pix<G>, which holds all that differs between the formats:
 //   In, NCH        the image element and the channels per pixel: channel k of pixel px is img[NCH px + k]
 //   Val, read      a pixel's value as the kernels compare it (its channels in f32, exact)
-//   record, value  the sample record of pixel px and the value it carries. Grey, U16: {row, col, v, 0};
+//   record, value  the sample record of pixel px and the value it carries. Grey, U16, F32: {row, col, v, 0};
 //                  Rgb: {row, col, 0, R + 256 G + 65536 B} (the packed colour as an exact integer in f32)
 //   dist2          the squared photometric distance |a - b|^2 in a fixed operation order; the kernels take
 //                  K = exp2(-fmaf(dist2, s_val, (dr^2 + dc^2) s_loc))
 //   Tile, tile     the degree sweep's LDS element {value, col}; outside() lies in a column no sample reaches (K = 0)
-//   Out, output    the output element of the apply kernel and its rule for channel x with its f64 correction c: the grey
-//                  d_out's rule, through f32 at 8 bits, in f64 at 16 bits
+//   Out, output    the output element of the apply kernel and its rule for channel x (passed exactly, as a double) with its
+//                  f64 correction c: the grey d_out's rule, through f32 at 8 bits, in f64 at 16 bits; F32: (float)(x + c), the
+//                  float z itself, no clamp and no floor
 // The factored forms over the 256 grey levels (grid, rank, the level-table degree) exist for Grey alone. The band form takes
-// the other two as well (k_band<.., G>: the photometric factor from dist2 and one v_exp_f32 per entry), behind the PIX_BAND key.
-enum class PixGen { Grey, Rgb, U16 };
+// the others as well (k_band<.., G>: the photometric factor from dist2 and one v_exp_f32 per entry), behind the PIX_BAND key.
+enum class PixGen { Grey, Rgb, U16, F32 };
 template <PixGen G> struct Pix;
-// one grey value per pixel, stored as T (Grey: uint8_t, U16: uint16_t): the record {row, col, v, 0}
+// one grey value per pixel, stored as T (Grey: uint8_t, U16: uint16_t, F32: float): the record {row, col, v, 0}
 template <typename T> struct PixGreyValue {
     using In = T;
     using Val = float;
@@ -289,7 +291,17 @@ template <> struct Pix<PixGen::U16> : PixGreyValue<uint16_t> {
     __device__ __forceinline__ static Tile outside() { return make_float2(0.f, -1e30f); }
     __device__ __forceinline__ static Val tile_value(Tile t) { return t.x; }
     __device__ __forceinline__ static float tile_col(Tile t) { return t.y; }
-    __device__ __forceinline__ static Out output(int x, double c) { return filter_output_u16(x, c); }
+    __device__ __forceinline__ static Out output(double x, double c) { return filter_output_u16((int)x, c); }
+};
+// (the differences of two floats are rounded once, their squares once more; a dist2 that overflows gives exp2(-inf) = 0)
+template <> struct Pix<PixGen::F32> : PixGreyValue<float> {
+    using Tile = float2; // {v, col}
+    using Out = float;
+    __device__ __forceinline__ static Tile tile(const In *img, int64_t px, int c) { return make_float2(read(img, px), (float)c); }
+    __device__ __forceinline__ static Tile outside() { return make_float2(0.f, -1e30f); }
+    __device__ __forceinline__ static Val tile_value(Tile t) { return t.x; }
+    __device__ __forceinline__ static float tile_col(Tile t) { return t.y; }
+    __device__ __forceinline__ static Out output(double x, double c) { return (float)(x + c); }
 };
 template <> struct Pix<PixGen::Rgb> {
     using In = uint8_t;
@@ -324,17 +336,23 @@ template <> struct Pix<PixGen::Rgb> {
     __device__ __forceinline__ static Tile outside() { return make_float4(0.f, 0.f, 0.f, -1e30f); }
     __device__ __forceinline__ static Val tile_value(Tile t) { return make_float3(t.x, t.y, t.z); }
     __device__ __forceinline__ static float tile_col(Tile t) { return t.w; }
-    __device__ __forceinline__ static Out output(int x, double c) { return filter_output(x, (float)c); }
+    __device__ __forceinline__ static Out output(double x, double c) { return filter_output((int)x, (float)c); }
 };
 // host side: the format a kernel reads (and the bilateral kernel on a format), whether the factored forms over the 256 grey
 // levels apply to a kernel, bytes and channels per pixel
 inline PixGen pixgen_of(int kernel)
 {
-    return kernel == GLF_KERNEL_BILATERAL_RGB ? PixGen::Rgb : kernel == GLF_KERNEL_BILATERAL_U16 ? PixGen::U16 : PixGen::Grey;
+    return kernel == GLF_KERNEL_BILATERAL_RGB   ? PixGen::Rgb
+           : kernel == GLF_KERNEL_BILATERAL_U16 ? PixGen::U16
+           : kernel == GLF_KERNEL_BILATERAL_F32 ? PixGen::F32
+                                                : PixGen::Grey;
 }
 inline int bilateral_kernel_of(PixGen g)
 {
-    return g == PixGen::Rgb ? GLF_KERNEL_BILATERAL_RGB : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16 : GLF_KERNEL_BILATERAL;
+    return g == PixGen::Rgb   ? GLF_KERNEL_BILATERAL_RGB
+           : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16
+           : g == PixGen::F32 ? GLF_KERNEL_BILATERAL_F32
+                              : GLF_KERNEL_BILATERAL;
 }
 inline bool grey_levels_factor(int kernel) { return kernel != GLF_KERNEL_NLM && pixgen_of(kernel) == PixGen::Grey; }
 // the band form applies to a kernel: it factors over grey levels, or it is a colour / 16-bit bilateral kernel and PIX_BAND is set
@@ -342,9 +360,17 @@ inline bool band_form_applies(const glf_ctx *ctx, int kernel) { return grey_leve
 template <PixGen G> constexpr size_t pix_bytes_of = sizeof(typename Pix<G>::In) * Pix<G>::NCH;
 inline size_t pix_bytes(PixGen g)
 {
-    return g == PixGen::Rgb ? pix_bytes_of<PixGen::Rgb> : g == PixGen::U16 ? pix_bytes_of<PixGen::U16> : pix_bytes_of<PixGen::Grey>;
+    return g == PixGen::Rgb   ? pix_bytes_of<PixGen::Rgb>
+           : g == PixGen::U16 ? pix_bytes_of<PixGen::U16>
+           : g == PixGen::F32 ? pix_bytes_of<PixGen::F32>
+                              : pix_bytes_of<PixGen::Grey>;
 }
-inline int pix_channels(PixGen g) { return g == PixGen::Rgb ? Pix<PixGen::Rgb>::NCH : g == PixGen::U16 ? Pix<PixGen::U16>::NCH : Pix<PixGen::Grey>::NCH; }
+inline int pix_channels(PixGen g)
+{
+    return g == PixGen::Rgb ? Pix<PixGen::Rgb>::NCH : g == PixGen::U16 ? Pix<PixGen::U16>::NCH : g == PixGen::F32 ? Pix<PixGen::F32>::NCH : Pix<PixGen::Grey>::NCH;
+}
+// the name of a format in messages
+inline const char *pix_name(PixGen g) { return g == PixGen::Rgb ? "colour" : g == PixGen::U16 ? "16-bit" : g == PixGen::F32 ? "float" : "8-bit"; }
 
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
@@ -444,7 +470,7 @@ int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int6
                  double *d_c, float *kernel_ms);
 // out[i] = sum over the chunks k of partial[k][i], k ascending (affinity.hip)
 __global__ void k_reduce_partials(const double *__restrict__ partial, unsigned p, int nchunks, double *__restrict__ out);
-// the formats without a factored form (entrywise.hip, gen Rgb or U16; d_img in the format): the contract of degree_rows, the
+// the formats without a factored form (entrywise.hip, gen Rgb, U16 or F32; d_img in the format): the contract of degree_rows, the
 // windowed entry-by-entry sweep (*evaluated = entries computed); the image's channels as float planes [NCH][N]; the outputs
 // (d_w [NCH][ld]; d_img / d_out [N] pixels, rows [pix0, pix1) only; d_zf optional [NCH][N])
 int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height, int row0, int row1,
@@ -461,6 +487,8 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
 int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, int nsig, const float *d_w,
                              float gain, float ysub, const uint8_t *d_img, uint8_t *d_out, float *d_zf, const float *d_sig, float *d_sig_out,
                              int64_t N);
+// the float format admits finite values only: *finite = every one of the N floats is (one pass, synchronises)
+int f32_all_finite(glf_ctx *ctx, const float *d_img, int64_t N, bool *finite);
 int laplacian_from_KA(glf_ctx *ctx, const float *d_KA, int64_t ldk, unsigned p, float *d_LA, int64_t ld,
                       double alpha, const double *d_degree);
 

@@ -149,14 +149,15 @@ __device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
 //   as k_nystroem_f16s (sample pixels skipped unless raster; c += Phi^T y per workgroup).
 // SAMPLES = true: targets = the samples of grid rows [row_begin, ..): out = Y = alpha (D X - K_A X).
 // NS > 0 (joint filtering): NS float planes through the same filter in the epilogue, fsig.w [NS][LD] their weights
-// G: the pixel format. Grey: the photometric factor is one LDS gather per entry from the 256-level table. Rgb, U16: tval is the
+// G: the pixel format. Grey: the photometric factor is one LDS gather per entry from the 256-level table. Rgb, U16, F32: tval is the
 //   image in the format (pixel targets) or the u32 image of the sample values (sample targets), the chunk tails carry the raw u32
-//   values, and the factor is P = exp2(pix_nsval dist2) with Pix<G>::dist2 and one v_exp_f32 per entry (pix_nsval = -s_val); no
+//   values (F32: the float's bit pattern), and the factor is P = exp2(pix_nsval dist2) with Pix<G>::dist2 and one v_exp_f32 per entry (pix_nsval = -s_val); no
 //   table in LDS. Er Ec stays a separate factor, so an entry outside the radius is still an exact zero pair. These
 //   instantiations write Phi (or Y): no filter in the epilogue, no c.
 template <PixGen G> __device__ __forceinline__ typename Pix<G>::Val band_pix_value(unsigned v)
 {
     if constexpr (G == PixGen::Rgb) return make_float3(ubyte_f32(v, 0), ubyte_f32(v, 1), ubyte_f32(v, 2));
+    else if constexpr (G == PixGen::F32) return __uint_as_float(v); // (the float's bit pattern)
     else return (float)v;
 }
 template <int MB, int PB, int NW, bool SAMPLES, int NS = 0, PixGen G = PixGen::Grey>
@@ -933,7 +934,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     if (d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
     GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), st));
     band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);
-    if (raw) hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, gen == PixGen::Rgb ? 1 : 0, svals32.p);
+    if (raw) hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals32_what(gen), svals32.p);
     else hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
     GLF_LAUNCH_CHECK(ctx);
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
@@ -952,7 +953,8 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
             const float nsval = -coef.s_val;
 #define GLF_BAND_PX(MB_, G_) launch_band_px<MB_, 0, G_>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster, nullptr, dev_eval.p, nullptr, pix0, nsval)
             if (gen == PixGen::Rgb) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::Rgb) : GLF_BAND_PX(1, PixGen::Rgb));
-            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::U16) : GLF_BAND_PX(1, PixGen::U16));
+            else if (gen == PixGen::U16) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::U16) : GLF_BAND_PX(1, PixGen::U16));
+            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::F32) : GLF_BAND_PX(1, PixGen::F32));
 #undef GLF_BAND_PX
         } else if (mb == 2)
             GLF_TRY(launch_band_px<2>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,

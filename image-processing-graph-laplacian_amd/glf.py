@@ -34,6 +34,7 @@ ERR_INVALID, ERR_NOMEM, ERR_HIP, ERR_NODEVICE, ERR_COMM, ERR_NOCONV, ERR_IO, ERR
 MAT_DENSE, MAT_DIAG, MAT_KERNEL_B = 0, 1, 2
 ROWS_NA, ROWS_SAMPLE_FIRST, ROWS_RASTER = 0, 1, 2
 KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM, KERNEL_BILATERAL_RGB, KERNEL_BILATERAL_U16 = 0, 1, 2, 3, 4, 5
+KERNEL_BILATERAL_F32 = 6
 CONTRACT_F32_MFMA, CONTRACT_F16_SPLIT = 1, 2
 FILTER_REFERENCE, FILTER_POC, FILTER_SMOOTH, FILTER_SHARPEN = 0, 1, 2, 3
 SAMPLING_UNIFORM, SAMPLING_RANDOM = 0, 1
@@ -55,6 +56,8 @@ EXPORTS = [
     "glf_image_processing_u16", "glf_multi_image_processing_u16", "glf_image_processing_u16_capture", "glf_read_png16", "glf_write_png16",
     "glf_image_processing_rgb_signals", "glf_image_processing_u16_signals",
     "glf_multi_image_processing_rgb_signals", "glf_multi_image_processing_u16_signals",
+    "glf_image_processing_f32", "glf_image_processing_f32_capture", "glf_image_processing_f32_signals",
+    "glf_multi_image_processing_f32", "glf_multi_image_processing_f32_signals", "glf_read_pfm", "glf_write_pfm",
 ]
 MAX_SIGNALS = 4
 
@@ -255,6 +258,33 @@ def write_png16(path, img):
         raise GlfError(ERR_IO, path)
 
 
+def read_pfm(path):
+    """A greyscale Portable Float Map ("Pf", either byte order) as float32 [H, W], rows top first; anything else raises GlfError."""
+    rows = C.POINTER(C.POINTER(C.c_float))()
+    w, h = C.c_int(), C.c_int()
+    rc = _lib.glf_read_pfm(path.encode(), C.byref(rows), C.byref(w), C.byref(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+    img = np.empty((h.value, w.value), dtype=np.float32)
+    for r in range(h.value):
+        img[r] = np.ctypeslib.as_array(rows[r], shape=(w.value,))
+        _lib.glf_host_free(rows[r])
+    _lib.glf_host_free(rows)
+    return img
+
+
+def write_pfm(path, img):
+    """Writes float32 [H, W] as a little-endian greyscale Portable Float Map (scale -1.0)."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    h, w = img.shape
+    rowptr = (C.POINTER(C.c_float) * h)()
+    for r in range(h):
+        rowptr[r] = C.cast(img.ctypes.data + r * w * 4, C.POINTER(C.c_float))
+    rc = _lib.glf_write_pfm(path.encode(), rowptr, C.c_uint(w), C.c_uint(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+
+
 def shard_rows(height, rank, size):
     """Pixel rows [row0, row1) owned by `rank` (glf_shard_rows; used by glf_image_processing)."""
     r0, r1 = C.c_int(), C.c_int()
@@ -367,12 +397,14 @@ class Multi:
         zf = np.zeros((h, w), dtype=np.float32) if want_float else None
         return out, zf, self._run("glf_multi_image_processing", opt, img, out, zf)
 
-    def _run(self, fn, opt, img, out, zf, sig=()):
-        """glf_multi_<...>(world, opt, img, width, height, [nsig, planes, planes out,] out, zf, eigvals, stats): per-rank infos."""
+    def _run(self, fn, opt, img, out, zf, sig=(), no_zf=False):
+        """glf_multi_<...>(world, opt, img, width, height, [nsig, planes, planes out,] out, zf, eigvals, stats): per-rank infos.
+        no_zf: the float entry points, whose out is the float z (no zf argument)."""
         h, w = img.shape[:2]
         lam = np.zeros(max(1, _realised_samples(w, h, opt)), dtype=np.float64)
         stats = (Stats * self.n)()
-        rc = getattr(_lib, fn)(self._w, C.byref(opt), _ptr(img), C.c_int(w), C.c_int(h), *sig, _ptr(out), _ptr(zf), _ptr(lam), stats)
+        outs = (_ptr(out),) if no_zf else (_ptr(out), _ptr(zf))
+        rc = getattr(_lib, fn)(self._w, C.byref(opt), _ptr(img), C.c_int(w), C.c_int(h), *sig, *outs, _ptr(lam), stats)
         if rc != OK:
             raise GlfError(rc, fn + ": " + _lib.glf_multi_last_error(self._w).decode())
         return [_info(s, lam) for s in stats]
@@ -441,6 +473,29 @@ class Multi:
         zf = np.zeros((h, w), dtype=np.float32) if want_float else None
         infos = self._run("glf_multi_image_processing_u16_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
         return out, zf, sig_out, infos
+
+    def image_processing_f32(self, img, opt=None):
+        """glf_multi_image_processing_f32: host float32 [H, W] in (finite values), (z float32 [H, W], per-rank infos)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 2:
+            raise ValueError("image must be [H, W], got %s" % (img.shape,))
+        opt = opt or default_options()
+        out = np.zeros(img.shape, dtype=np.float32)
+        return out, self._run("glf_multi_image_processing_f32", opt, img, out, None, no_zf=True)
+
+    def image_processing_f32_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_f32_signals: host float32 [H, W] plus float planes [nsig, H, W] filtered through the float
+        image's graph. Returns (z float32 [H, W], sig_out f32 [nsig, H, W], infos)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 2:
+            raise ValueError("image must be [H, W], got %s" % (img.shape,))
+        h, w = img.shape
+        sig, sig_out = self._planes(signals, h, w)
+        opt = opt or default_options()
+        out = np.zeros((h, w), dtype=np.float32)
+        infos = self._run("glf_multi_image_processing_f32_signals", opt, img, out, None,
+                          sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)), no_zf=True)
+        return out, sig_out, infos
 
     @staticmethod
     def _planes(signals, h, w):
@@ -699,8 +754,9 @@ class Context:
     # -- stages (names as in hpc/*.h) -------------------------------------------------------
     def ComputeAffinityMatrices(self, d_img, sample_indices, want_KA=True, kernel=KERNEL_BILATERAL,
                                 h_loc=40.0, h_val=30.0):
-        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3]; KERNEL_BILATERAL_U16: uint16 [H, W])
-        assert d_img.dtype == (self.torch.uint16 if kernel == KERNEL_BILATERAL_U16 else self.torch.uint8) and d_img.is_cuda and d_img.is_contiguous()
+        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3]; KERNEL_BILATERAL_U16: uint16 [H, W]; KERNEL_BILATERAL_F32: float32 [H, W])
+        dtype = {KERNEL_BILATERAL_U16: self.torch.uint16, KERNEL_BILATERAL_F32: self.torch.float32}.get(kernel, self.torch.uint8)
+        assert d_img.dtype == dtype and d_img.is_cuda and d_img.is_contiguous()
         assert d_img.dim() == (3 if kernel == KERNEL_BILATERAL_RGB else 2) and (kernel != KERNEL_BILATERAL_RGB or d_img.shape[2] == 3)
         h, w = d_img.shape[:2]
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)
@@ -805,17 +861,18 @@ class Context:
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
         return out, zf, self._run("glf_image_processing_capture", "image_processing", opt, d_img, out, zf, capture, grey=True)
 
-    def _run(self, fn, what, opt, d_img, out, zf, capture=False, grey=False, sig=()):
+    def _run(self, fn, what, opt, d_img, out, zf, capture=False, grey=False, sig=(), no_zf=False):
         """fn(ctx, opt, img, width, height, [*sig,] out, zf, eigvals, stats[, capture]) on the context's stream (sig: nsig, the
         planes and the planes out of the signals entry point, which takes no capture): the call's info dict, with info["capture"]
-        when asked for (grey: also c = Phi^T y and the correction). Errors are reported as `what`."""
+        when asked for (grey: also c = Phi^T y and the correction). Errors are reported as `what`. no_zf: the float entry points,
+        whose out is the float z (no zf argument)."""
         h, w = d_img.shape[:2]
         p_real = _realised_samples(w, h, opt)
         lam = np.zeros(max(p_real, 1), dtype=np.float64)       # m <= p - 1 eigenvalues come back
         cap, keep = self._capture_buffers(w, h, opt, p_real, grey) if capture else (None, None)
         st = Stats()
-        args = (C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h)) + sig + (
-            C.c_void_p(out.data_ptr()), C.c_void_p(zf.data_ptr()) if zf is not None else None, _ptr(lam), C.byref(st))
+        zfs = () if no_zf else (C.c_void_p(zf.data_ptr()) if zf is not None else None,)
+        args = (C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h)) + sig + (C.c_void_p(out.data_ptr()),) + zfs + (_ptr(lam), C.byref(st))
         if not sig:
             args += (C.byref(cap) if cap else None,)
         self._check(getattr(_lib, fn)(self._ctx, C.byref(opt), *args), what)
@@ -878,6 +935,35 @@ class Context:
             out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
             zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
         return out, zf, self._run("glf_image_processing_u16_capture", "image_processing_u16", opt, d_img, out, zf, capture)
+
+    def image_processing_f32(self, d_img, opt=None, capture=False, out=None):
+        """32-bit float greyscale filtering (glf_image_processing_f32): d_img (device float32 [H, W], finite values) defines the graph
+        through its values (opt.h_val in the image's units) and goes through the graph's filter. Returns (z float32 [H, W], info):
+        the output is the float z itself, not clamped. A NaN or an Inf in d_img raises GlfError(ERR_INVALID) and `out` (optional: a
+        device float32 [H, W] to write into) is left as it was. capture=True adds info["capture"] as image_processing_u16 does."""
+        torch = self.torch
+        assert d_img.dtype == torch.float32 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
+        h, w = d_img.shape
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
+        with torch.cuda.stream(self.stream):
+            if out is None:
+                out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_cuda and tuple(out.shape) == (h, w) and out.is_contiguous()
+        return out, self._run("glf_image_processing_f32_capture", "image_processing_f32", opt, d_img, out, None, capture, no_zf=True)
+
+    def image_processing_f32_signals(self, d_img, signals, opt=None):
+        """Joint filtering under a float guide (glf_image_processing_f32_signals): as image_processing_u16_signals with the graph
+        and the output of image_processing_f32. Returns (z float32 [H, W], sig_out float32 [nsig, H, W], info)."""
+        torch = self.torch
+        assert d_img.dtype == torch.float32 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
+        h, w = d_img.shape
+        opt = opt or default_options()
+        sig_out, sig = self._signal_planes(signals, h, w)
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
+        info = self._run("glf_image_processing_f32_signals", "image_processing_f32_signals", opt, d_img, out, None, sig=sig, no_zf=True)
+        return out, sig_out, info
 
     def image_processing_rgb_signals(self, d_rgb, signals, opt=None, want_float=False):
         """Joint filtering under a colour guide (glf_image_processing_rgb_signals): d_rgb (device uint8 [H, W, 3]) defines the graph

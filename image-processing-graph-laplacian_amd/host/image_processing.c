@@ -8,7 +8,7 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16] [-pix_band]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16 | -float32] [-pix_band]
  *                    [-planes F1[,F2[,F3[,F4]]]]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
@@ -23,10 +23,15 @@
  * -depth16 reads a 16-bit grey PNG and filters it on its 16-bit values (glf_image_processing_u16: the bilateral kernel with
  * v in 0..65535, -h_val in 16-bit units, 30 x 257 by default -- the 8-bit default graph on the same content) with the same
  * -filter, and writes results/input.png and results/output.png as 16-bit grey PNGs; -ngpu N works as for 8 bits.
- * -pix_band (with -depth16 or -color -rgb_graph) sets the PIX_BAND tuning key: the 16-bit / colour kernel takes the band form
+ * -float32 reads a greyscale Portable Float Map ("Pf", either byte order) and filters it on its float values
+ * (glf_image_processing_f32: the bilateral kernel on any finite value, -h_val in the image's own units, default 30) with the same
+ * -filter, and writes results/input.pfm and results/output.pfm (the float z, not clamped); a NaN or an Inf in the file is refused.
+ * It combines with -pix_band, -planes (the planes stay PNGs) and -ngpu N like -depth16, and with neither -depth16, -color, -no_approx
+ * nor a -kernel other than bilateral.
+ * -pix_band (with -depth16, -float32 or -color -rgb_graph) sets the PIX_BAND tuning key: the 16-bit / colour kernel takes the band form
  * of the Nystroem stage and of the operator wherever the grey kernel would (GLF_PIX_BAND=1 in the environment does the same), and
  * one more line names the routes taken ("band form: nystroem_path 4, matvec_path 4", or the fallback's numbers).
- * -planes F1[,F2[,F3[,F4]]] (with -depth16 or -color -rgb_graph) is joint filtering: each file is a grey PNG of the image's size (16
+ * -planes F1[,F2[,F3[,F4]]] (with -depth16, -float32 or -color -rgb_graph) is joint filtering: each file is a grey PNG of the image's size (16
  * or 8 bits; a depth map, an alpha matte, ...) whose pixel values go as a float plane through the 16-bit / colour image's graph with
  * the same -filter (glf_image_processing_u16_signals / glf_image_processing_rgb_signals; with -depth16 -ngpu N the glf_multi_ call).
  * Plane k (from 0) is written to results/plane_<k>.png at its input's bit depth as clamp(floor(z + 0.5)); results/output.png is the
@@ -418,17 +423,18 @@ static int planes_write(unsigned width, unsigned height, const char *graph)
     return status;
 }
 
-/* -depth16: img (rows of `width` uint16_t) through glf_image_processing_u16 on one context, or glf_multi_image_processing_u16 on
- * ngpu ranks; returns the output rows (NULL on failure, the message printed). */
-static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned height, int ngpu, int backend)
+/* -depth16 / -float32: img (rows of `width` uint16_t, or float with f32 set) through glf_image_processing_u16 / _f32 on one context, or
+ * the glf_multi_ call on ngpu ranks; returns the output rows in the input's format (NULL on failure, the message printed). */
+static void **DeepComputation(void **img, unsigned width, unsigned height, int ngpu, int backend, int f32)
 {
-    const size_t n = (size_t)width * height;
-    uint16_t *flat = (uint16_t *)malloc(sizeof(uint16_t) * n), *flat_out = (uint16_t *)calloc(n, sizeof(uint16_t));
-    uint16_t **rows = NULL;
+    const size_t n = (size_t)width * height, esz = f32 ? sizeof(float) : sizeof(uint16_t);
+    const char *fn = f32 ? "glf_image_processing_f32" : "glf_image_processing_u16";
+    void *flat = malloc(esz * n), *flat_out = calloc(n, esz);
+    void **rows = NULL;
     glf_options opt;
     fill_options(&opt, width, height);
     int ok = flat && flat_out;
-    for (unsigned r = 0; ok && r < height; ++r) memcpy(flat + (size_t)r * width, img[r], sizeof(uint16_t) * width);
+    for (unsigned r = 0; ok && r < height; ++r) memcpy((char *)flat + esz * r * width, img[r], esz * width);
     if (ok && ngpu > 0) {
         glf_multi *world = NULL;
         int *devices = NULL;
@@ -443,10 +449,16 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         if (rc != GLF_OK) fprintf(stderr, "glf_multi_create(%d GPUs, %s): %s\n", ngpu, backend == GLF_MULTI_RCCL ? "rccl" : "loopback", glf_strerror(rc));
         else if (st) {
             for (int r = 0; r < ngpu; ++r) pix_band_set(glf_multi_ctx(world, r));
-            rc = g_nplanes ? glf_multi_image_processing_u16_signals(world, &opt, flat, (int)width, (int)height, g_nplanes, g_planes, g_planes_out,
-                                                                    flat_out, NULL, NULL, st)
-                           : glf_multi_image_processing_u16(world, &opt, flat, (int)width, (int)height, flat_out, NULL, NULL, st);
-            if (rc != GLF_OK) fprintf(stderr, "glf_multi_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_multi_last_error(world));
+            if (f32)
+                rc = g_nplanes ? glf_multi_image_processing_f32_signals(world, &opt, (const float *)flat, (int)width, (int)height, g_nplanes, g_planes,
+                                                                        g_planes_out, (float *)flat_out, NULL, st)
+                               : glf_multi_image_processing_f32(world, &opt, (const float *)flat, (int)width, (int)height, (float *)flat_out, NULL, st);
+            else
+                rc = g_nplanes ? glf_multi_image_processing_u16_signals(world, &opt, (const uint16_t *)flat, (int)width, (int)height, g_nplanes, g_planes,
+                                                                        g_planes_out, (uint16_t *)flat_out, NULL, NULL, st)
+                               : glf_multi_image_processing_u16(world, &opt, (const uint16_t *)flat, (int)width, (int)height, (uint16_t *)flat_out, NULL,
+                                                                NULL, st);
+            if (rc != GLF_OK) fprintf(stderr, "%s: %s (%s)\n", f32 ? "glf_multi_image_processing_f32" : "glf_multi_image_processing_u16", glf_strerror(rc), glf_multi_last_error(world));
             else {
                 print_stage_times(&st[0], opt.epsilon);
                 pix_band_report(&st[0]);
@@ -462,18 +474,24 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         void *d_img = NULL, *d_out = NULL, *d_sig = NULL, *d_sig_out = NULL;
         const size_t sig_bytes = sizeof(float) * n * (size_t)g_nplanes;
         glf_stats st;
-        ok = glf_malloc(ctx, &d_img, sizeof(uint16_t) * n) == GLF_OK && glf_malloc(ctx, &d_out, sizeof(uint16_t) * n) == GLF_OK &&
-             glf_memcpy_h2d(ctx, d_img, flat, sizeof(uint16_t) * n) == GLF_OK;
+        ok = glf_malloc(ctx, &d_img, esz * n) == GLF_OK && glf_malloc(ctx, &d_out, esz * n) == GLF_OK &&
+             glf_memcpy_h2d(ctx, d_img, flat, esz * n) == GLF_OK;
         if (ok && g_nplanes)
             ok = glf_malloc(ctx, &d_sig, sig_bytes) == GLF_OK && glf_malloc(ctx, &d_sig_out, sig_bytes) == GLF_OK &&
                  glf_memcpy_h2d(ctx, d_sig, g_planes, sig_bytes) == GLF_OK;
         if (ok) {
             pix_band_set(ctx);
-            const int rc = g_nplanes ? glf_image_processing_u16_signals(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, g_nplanes,
-                                                                        (const float *)d_sig, (float *)d_sig_out, (uint16_t *)d_out, NULL, NULL, &st)
-                                     : glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
-            if (rc != GLF_OK) fprintf(stderr, "glf_image_processing_u16: %s (%s)\n", glf_strerror(rc), glf_ctx_last_error(ctx));
-            ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, sizeof(uint16_t) * n) == GLF_OK &&
+            int rc;
+            if (f32)
+                rc = g_nplanes ? glf_image_processing_f32_signals(ctx, &opt, (const float *)d_img, (int)width, (int)height, g_nplanes, (const float *)d_sig,
+                                                                  (float *)d_sig_out, (float *)d_out, NULL, &st)
+                               : glf_image_processing_f32(ctx, &opt, (const float *)d_img, (int)width, (int)height, (float *)d_out, NULL, &st);
+            else
+                rc = g_nplanes ? glf_image_processing_u16_signals(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, g_nplanes,
+                                                                  (const float *)d_sig, (float *)d_sig_out, (uint16_t *)d_out, NULL, NULL, &st)
+                               : glf_image_processing_u16(ctx, &opt, (const uint16_t *)d_img, (int)width, (int)height, (uint16_t *)d_out, NULL, NULL, &st);
+            if (rc != GLF_OK) fprintf(stderr, "%s: %s (%s)\n", fn, glf_strerror(rc), glf_ctx_last_error(ctx));
+            ok = rc == GLF_OK && glf_memcpy_d2h(ctx, flat_out, d_out, esz * n) == GLF_OK &&
                  (!g_nplanes || glf_memcpy_d2h(ctx, g_planes_out, d_sig_out, sig_bytes) == GLF_OK);
             if (ok) {
                 print_stage_times(&st, opt.epsilon);
@@ -486,10 +504,10 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
         if (d_sig_out) glf_free(ctx, d_sig_out);
     }
     if (ok) {
-        rows = (uint16_t **)calloc(height, sizeof(uint16_t *));
+        rows = (void **)calloc(height, sizeof(void *));
         for (unsigned r = 0; rows && r < height; ++r) {
-            rows[r] = (uint16_t *)malloc(sizeof(uint16_t) * width);
-            if (rows[r]) memcpy(rows[r], flat_out + (size_t)r * width, sizeof(uint16_t) * width);
+            rows[r] = malloc(esz * width);
+            if (rows[r]) memcpy(rows[r], (char *)flat_out + esz * r * width, esz * width);
         }
     }
     free(flat);
@@ -497,8 +515,9 @@ static uint16_t **Depth16Computation(uint16_t **img, unsigned width, unsigned he
     return rows;
 }
 
-static void free_rows16(uint16_t **rows, int height)
+static void free_rows16(void *rows_, int height) /* (rows of any element type) */
 {
+    void **rows = (void **)rows_;
     if (!rows) return;
     for (int r = 0; r < height; ++r) free(rows[r]);
     free(rows);
@@ -734,6 +753,19 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (opt_has("-float32")) {
+        const char *kv = opt_value("-kernel");
+        const char *other = opt_has("-color") ? "-color" : opt_has("-chroma") ? "-chroma" : opt_has("-rgb_graph") ? "-rgb_graph"
+                          : opt_has("-no_approx") ? "-no_approx" : opt_has("-depth16") ? "-depth16"
+                          : (kv && strcmp(kv, "bilateral") != 0) ? "-kernel" : NULL;
+        if (other) {
+            fprintf(stderr, strcmp(other, "-kernel") == 0 ? "-float32 filters a float grey image with the bilateral kernel: it cannot be combined with %s %s\n"
+                                                          : "-float32 filters a float grey image: it cannot be combined with %s%s\n",
+                    other, strcmp(other, "-kernel") == 0 ? kv : "");
+            FinalizeProgram();
+            return 1;
+        }
+    }
     if (opt_has("-chroma") && !opt_has("-color")) {
         fprintf(stderr, "-chroma filters the chroma planes of a colour image: it needs -color\n");
         FinalizeProgram();
@@ -745,13 +777,13 @@ int main(int argc, char **argv)
         FinalizeProgram();
         return 1;
     }
-    if (opt_has("-pix_band") && !opt_has("-depth16") && !opt_has("-rgb_graph")) {
-        fprintf(stderr, "-pix_band selects the band form of the 16-bit and colour kernels: it needs -depth16 or -color -rgb_graph\n");
+    if (opt_has("-pix_band") && !opt_has("-depth16") && !opt_has("-float32") && !opt_has("-rgb_graph")) {
+        fprintf(stderr, "-pix_band selects the band form of the 16-bit, float and colour kernels: it needs -depth16 or -color -rgb_graph (or -float32)\n");
         FinalizeProgram();
         return 1;
     }
-    if (opt_has("-planes") && !opt_has("-depth16") && !(opt_has("-color") && opt_has("-rgb_graph"))) {
-        fprintf(stderr, "-planes filters extra planes through the 16-bit or the colour graph: it needs -depth16 or -color -rgb_graph\n");
+    if (opt_has("-planes") && !opt_has("-depth16") && !opt_has("-float32") && !(opt_has("-color") && opt_has("-rgb_graph"))) {
+        fprintf(stderr, "-planes filters extra planes through the 16-bit, the float or the colour graph: it needs -depth16 or -color -rgb_graph (or -float32)\n");
         FinalizeProgram();
         return 1;
     }
@@ -771,8 +803,8 @@ int main(int argc, char **argv)
         if (!opt_value("-h_val")) stage_h_val = 30.0f * 257.0f; /* the 8-bit default graph on the same content */
         printf("Read image %s of size %dx%d => %d pixels (16-bit gray)\n", filename, width, height, width * height);
         planes_load((unsigned)width, (unsigned)height);
-        out16 = Depth16Computation(in16, (unsigned)width, (unsigned)height, ngpu,
-                                   nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL);
+        out16 = (uint16_t **)DeepComputation((void **)in16, (unsigned)width, (unsigned)height, ngpu,
+                                             nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL, 0);
         int dstatus = out16 ? 0 : 5;
         if (glf_write_png16("results/input.png", in16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
         if (out16 && glf_write_png16("results/output.png", out16, (unsigned)width, (unsigned)height) != 0) dstatus = dstatus ? dstatus : 4;
@@ -782,6 +814,27 @@ int main(int argc, char **argv)
         free_rows16(out16, height);
         FinalizeProgram();
         return dstatus;
+    }
+    if (opt_has("-float32")) { /* float grey: a PFM in, a PFM out */
+        float **in32 = NULL, **out32 = NULL;
+        if (glf_read_pfm(filename, &in32, &width, &height) != 0) {
+            fprintf(stderr, "-float32 needs a greyscale Portable Float Map (Pf): could not read %s as one\n", filename);
+            FinalizeProgram();
+            return 1;
+        }
+        printf("Read image %s of size %dx%d => %d pixels (32-bit float gray)\n", filename, width, height, width * height);
+        planes_load((unsigned)width, (unsigned)height);
+        out32 = (float **)DeepComputation((void **)in32, (unsigned)width, (unsigned)height, ngpu,
+                                          nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL, 1);
+        int fstatus = out32 ? 0 : 5;
+        if (glf_write_pfm("results/input.pfm", in32, (unsigned)width, (unsigned)height) != 0) fstatus = fstatus ? fstatus : 4;
+        if (out32 && glf_write_pfm("results/output.pfm", out32, (unsigned)width, (unsigned)height) != 0) fstatus = fstatus ? fstatus : 4;
+        if (out32 && g_nplanes && planes_write((unsigned)width, (unsigned)height, "float") != 0) fstatus = fstatus ? fstatus : 4;
+        printf("Total computation time: %fs\n", wtime() - start_time);
+        free_rows16(in32, height);
+        free_rows16(out32, height);
+        FinalizeProgram();
+        return fstatus;
     }
     if (opt_has("-color")) { /* python/image_processing.py:410-432 */
         unsigned cw = 0, ch = 0;

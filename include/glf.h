@@ -67,7 +67,7 @@ int glf_ctx_device_info(const glf_ctx *ctx, char *name, size_t name_len, int *nu
  *   NYS_PATH  band | rank | grid | direct     DEG_PATH  grid | direct     MV_PATH  band | rank | grid | dense
  *   ROWPASS, ROWPASS_OP  rt | v1     COLPASS  ws | v1     SWEEP_COLPASS  segments | samples
  *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, BAND_NOSKIP, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
- *   PIX_BAND  1 | 0 (default 0): the colour and 16-bit bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16) take the band form of
+ *   PIX_BAND  1 | 0 (default 0): the colour, 16-bit and float bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16 / _F32) take the band form of
  *     the Nystroem stage and of the L_A operator under exactly the conditions under which the grey kernel takes it -- split-f16
  *     contraction, a tensor-grid sample set, at most 64 eigenpairs, the radius and band-row limits, NYS_PATH auto (width >= 1024)
  *     or band, MV_PATH auto (p >= 16 384) or band -- with the photometric factor generated per entry (one v_exp_f32) instead of
@@ -191,8 +191,11 @@ enum { GLF_ROWS_NA = 0, GLF_ROWS_SAMPLE_FIRST = 1, GLF_ROWS_RASTER = 2 };
  * of the image's values on every entry point: an image 257 g (g an 8-bit image) at h_val * 257 has the graph of g at h_val. Like
  * the colour kernel it has no grid-factored, rank or band form (those factor over 256 grey levels): the entry-by-entry kernels run
  * with the f32 MFMA contraction whatever glf_ctx_set_contraction says. */
+/* BILATERAL_F32: the same kernel on 32-bit float values, K = exp(-(dr^2 + dc^2) / h_loc^2) exp(-(v_i - v_j)^2 / h_val^2) with v any
+ * finite float (negative and fractional included) and h_val in the image's own units. With it the stage entry points read d_img as
+ * float [height][width]; an image with a NaN or an Inf is refused (GLF_ERR_INVALID). Routes and contraction as for BILATERAL_U16. */
 enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3, GLF_KERNEL_BILATERAL_RGB = 4,
-       GLF_KERNEL_BILATERAL_U16 = 5 };
+       GLF_KERNEL_BILATERAL_U16 = 5, GLF_KERNEL_BILATERAL_F32 = 6 };
 
 /* Replaces PETSc Mat (MATMPIDENSE / MATMPIAIJ diagonal). */
 typedef struct glf_mat {
@@ -473,6 +476,20 @@ int glf_image_processing_u16_signals(glf_ctx *ctx, const glf_options *opt, const
                                      const float *d_sig, float *d_sig_out, uint16_t *d_out, float *d_zf, double *eigvals_out,
                                      glf_stats *stats);
 
+/* 32-bit float greyscale filtering: glf_image_processing_u16 on float values (GLF_KERNEL_BILATERAL_F32; opt->kernel must be
+ * GLF_KERNEL_BILATERAL or GLF_KERNEL_BILATERAL_F32, both mean the float kernel here, any other gives GLF_ERR_UNSUPPORTED; opt->h_val
+ * is in the image's units). d_img / d_out: device float [height][width]; d_out is z = (float)(x + c) with c the f64 correction
+ * gain Phi f(Pi) Phi^T x - ysub x: no clamp, no floor, and so no separate float z. The image is checked first, in one pass: a NaN
+ * or an Inf anywhere gives GLF_ERR_INVALID (the message names it) and d_out is not written. Routes, tuning keys, declines (more
+ * than 256 eigenpairs: GLF_ERR_UNSUPPORTED) and stats as for glf_image_processing_u16. On integer values 0..65535 the graph,
+ * the eigenvalues and z have the bits of the 16-bit call's (z: of its d_zf). The _signals call is
+ * glf_image_processing_u16_signals under a float guide (the planes are not checked for NaN / Inf); the _capture call writes
+ * d_phi_A, d_phi and h_degree. */
+int glf_image_processing_f32(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, float *d_out,
+                             double *eigvals_out, glf_stats *stats);
+int glf_image_processing_f32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, int nsig,
+                                     const float *d_sig, float *d_sig_out, float *d_out, double *eigvals_out, glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -499,6 +516,10 @@ int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const
  * float z gives the correction). */
 int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height,
                                      uint16_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap);
+
+/* The same by-products of one glf_image_processing_f32 call, as for 16 bits. */
+int glf_image_processing_f32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, float *d_out,
+                                     double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
@@ -543,6 +564,13 @@ int glf_multi_image_processing_u16_signals(glf_multi *w, const glf_options *opt,
                                            int nsig, const float *h_sig, float *h_sig_out, uint16_t *h_out, float *h_zf,
                                            double *eigvals_out, glf_stats *stats);
 
+/* glf_multi_image_processing for float grey (glf_image_processing_f32 / _f32_signals): h_img / h_out HOST float [height][width]. The
+ * NaN / Inf check runs on the host image before any rank starts: a refused image leaves the world usable. */
+int glf_multi_image_processing_f32(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, float *h_out,
+                                   double *eigvals_out, glf_stats *stats);
+int glf_multi_image_processing_f32_signals(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, int nsig,
+                                           const float *h_sig, float *h_sig_out, float *h_out, double *eigvals_out, glf_stats *stats);
+
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
  * (hpc/affinity.c:264-336, hpc/laplacian.c:44-65, hpc/display.c:128-149). The matrices are never stored
@@ -567,6 +595,12 @@ int glf_write_png_rgb(const char *filename, uint8_t **img_bytes, unsigned width,
  * glf_read_png rejects 16-bit input. */
 int glf_read_png16(const char *filename, uint16_t ***row_pointers, int *width, int *height);
 int glf_write_png16(const char *filename, uint16_t **rows, unsigned width, unsigned height);
+/* Greyscale Portable Float Map: the header "Pf\n<width> <height>\n<scale>\n" (any whitespace between the tokens, one whitespace
+ * byte after the scale), then width * height raw floats, bottom row first; scale < 0: little-endian, > 0: big-endian. The reader takes
+ * both byte orders and returns malloc'd rows top first; -1 for colour ("PF"), a short file, a zero or overflowing size or a malformed
+ * header. The writer writes little-endian, scale -1.0. */
+int glf_read_pfm(const char *filename, float ***rows, int *width, int *height);
+int glf_write_pfm(const char *filename, float **rows, unsigned width, unsigned height);
 
 #ifdef __cplusplus
 }
