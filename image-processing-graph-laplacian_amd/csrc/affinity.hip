@@ -26,6 +26,8 @@ __global__ void k_sample_tables(const uint8_t *__restrict__ img, int width, int6
     if ((int64_t)px >= N) return; // validated on the host as well
     // num2x / num2y, hpc/utils.c:11-19: x = row, y = column
     samples[i] = Pix<G>::record(reinterpret_cast<const typename Pix<G>::In *>(img), px, (uint32_t)width);
+    if constexpr (Pix<G>::HAS_VALUE_BLOCK) // the value block behind the padded records
+        samples[(size_t)round_up_dev(p, NYS_PAD) + i] = Pix<G>::block_entry(reinterpret_cast<const typename Pix<G>::In *>(img), px);
     mask[px] = 1;
 }
 
@@ -38,7 +40,8 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
         if ((int64_t)h_idx[i] >= N || (i && h_idx[i] <= h_idx[i - 1]))
             return set_error(ctx, GLF_ERR_INVALID, "sample_indices must be ascending and < width*height (i=%u)", i);
     }
-    const size_t p_pad = (size_t)round_up(p, NYS_PAD); // zero records past p (Nystroem LDS staging)
+    // zero records past p (Nystroem LDS staging); float colour: as many value-block entries behind them
+    const size_t p_pad = sample_table_records(pixgen_of(kernel), p);
     GLF_TRY(out.samples.alloc(ctx, p_pad));
     GLF_HIP(ctx, hipMemsetAsync(out.samples.p, 0, sizeof(float4) * p_pad, ctx->stream));
     GLF_TRY(out.mask.alloc(ctx, (size_t)N));
@@ -51,6 +54,7 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     case PixGen::Rgb: hipLaunchKernelGGL(k_sample_tables<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     case PixGen::U16: hipLaunchKernelGGL(k_sample_tables<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     case PixGen::F32: hipLaunchKernelGGL(k_sample_tables<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
+    case PixGen::RgbF32: hipLaunchKernelGGL(k_sample_tables<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
     }
     GLF_LAUNCH_CHECK(ctx);
     // h_idx is pageable host memory: make sure the async copy has consumed it
@@ -507,7 +511,8 @@ int entire_computation(glf_ctx *ctx, const uint8_t *d_img, int width, int height
 // L_A = alpha * (diag(D) - K_A)  => off-diagonal -alpha*K, diagonal alpha*(D_i - K_ii).
 // Write-bound: 4 p^2 bytes (29 GB at p = 85 264).
 
-// G: the format of the sample records (the photometric distance); U16 takes the Grey instantiation: the same records, no level table
+// G: the format of the sample records (the photometric distance); U16 and F32 take the Grey instantiation: the same records, no level
+// table. RgbF32 reads the two samples' channels from the value block behind the records (one more 16-byte load each)
 template <PixGen G>
 __global__ __launch_bounds__(256) void k_sample_matrix(const float4 *__restrict__ samples, unsigned p, float s_loc,
                                                         float s_val, float *__restrict__ out, int64_t ld,
@@ -524,12 +529,13 @@ __global__ __launch_bounds__(256) void k_sample_matrix(const float4 *__restrict_
     }
     const unsigned j = col0 + jl;
     const float4 sj = samples[j];
-    const typename Pix<G>::Val vj = Pix<G>::value(sj);
+    const unsigned p_pad = round_up_dev(p, NYS_PAD);
+    const typename Pix<G>::Val vj = sample_value<G>(samples, p_pad, j, sj);
     const float fscale = laplacian ? (float)(-alpha) : 1.0f;
     auto entry = [&](unsigned i) {
         const float4 si = samples[i]; // wave-uniform -> scalar load
         const float dr = si.x - sj.x, dc = si.y - sj.y;
-        const float k = __builtin_amdgcn_exp2f(-fmaf(Pix<G>::dist2(Pix<G>::value(si), vj), s_val, fmaf(dc, dc, dr * dr) * s_loc));
+        const float k = __builtin_amdgcn_exp2f(-fmaf(Pix<G>::dist2(sample_value<G>(samples, p_pad, i, si), vj), s_val, fmaf(dc, dc, dr * dr) * s_loc));
         float v = fscale * k;
         if (laplacian && i == j) v = (float)(alpha * (degree[i] - (double)k));
         out[(size_t)i * ld + jl] = v;
@@ -558,6 +564,9 @@ int build_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, Kerne
     dim3 grid((unsigned)((ld + 63) / 64), (p + 63) / 64); // covers the padding columns too
     if (pixgen_of(coef.kernel) == PixGen::Rgb)
         hipLaunchKernelGGL(k_sample_matrix<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
+                           ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
+    else if (pixgen_of(coef.kernel) == PixGen::RgbF32)
+        hipLaunchKernelGGL(k_sample_matrix<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
                            ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
     else
         hipLaunchKernelGGL(k_sample_matrix<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,

@@ -394,7 +394,7 @@ const char *glf_multi_last_error(const glf_multi *w) { return w ? w->last_error 
 // One rank thread per GPU: replicate the image (hpc/image_processing.c:45-76 broadcasts it to every rank), run the sharded
 // path, copy this rank's pixel rows of the result back (hpc/utils.c:502-527 gathers to rank 0).
 // nsig > 0: signal planes h_sig [nsig][N] replicated on every rank, each rank's pixel rows of the results into h_sig_out
-// gen: the guide's pixel format (glf_image_processing / _signals, _rgb, _u16, _f32): h_img and h_out are [N] pixels of it, h_zf the
+// gen: the guide's pixel format (glf_image_processing / _signals, _rgb, _u16, _f32, _rgbf32): h_img and h_out are [N] pixels of it, h_zf the
 // format's [NCH][N] floats
 static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
                      float *h_zf, double *eigvals_out, glf_stats *stats, int nsig = 0, const float *h_sig = nullptr, float *h_sig_out = nullptr);
@@ -446,19 +446,19 @@ int glf_multi_image_processing_u16_signals(glf_multi *w, const glf_options *opt,
 // float grey: the finite check runs here on the host image, once for all ranks and before any of them starts (a rank that failed
 // alone would cost the world its communicators)
 static int multi_run_f32(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, float *h_out, double *eigvals_out,
-                         glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out)
+                         glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out, PixGen gen = PixGen::F32)
 {
     if (!w || !h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    const size_t N = (size_t)width * height;
+    const size_t nch = (size_t)pix_channels(gen), N = (size_t)width * height * nch;
     for (size_t i = 0; i < N; ++i) {
         uint32_t bits;
         std::memcpy(&bits, h_img + i, sizeof(bits));
         if ((bits & 0x7f800000u) == 0x7f800000u) {
-            std::snprintf(w->last_error, sizeof(w->last_error), "the float image holds a NaN or an Inf (pixel %zu): finite values only", i);
+            std::snprintf(w->last_error, sizeof(w->last_error), "the %s image holds a NaN or an Inf (pixel %zu): finite values only", pix_name(gen), i / nch);
             return GLF_ERR_INVALID;
         }
     }
-    return multi_run(w, opt, PixGen::F32, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), nullptr,
+    return multi_run(w, opt, gen, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), nullptr,
                      eigvals_out, stats, nsig, h_sig, h_sig_out);
 }
 
@@ -473,6 +473,19 @@ int glf_multi_image_processing_f32_signals(glf_multi *w, const glf_options *opt,
 {
     if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
     return multi_run_f32(w, opt, h_img, width, height, h_out, eigvals_out, stats, nsig, h_sig, h_sig_out);
+}
+
+int glf_multi_image_processing_rgbf32(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, float *h_out_rgb,
+                                      double *eigvals_out, glf_stats *stats)
+{
+    return multi_run_f32(w, opt, h_rgb, width, height, h_out_rgb, eigvals_out, stats, 0, nullptr, nullptr, PixGen::RgbF32);
+}
+
+int glf_multi_image_processing_rgbf32_signals(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, int nsig,
+                                              const float *h_sig, float *h_sig_out, float *h_out_rgb, double *eigvals_out, glf_stats *stats)
+{
+    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
+    return multi_run_f32(w, opt, h_rgb, width, height, h_out_rgb, eigvals_out, stats, nsig, h_sig, h_sig_out, PixGen::RgbF32);
 }
 
 static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
@@ -538,6 +551,12 @@ static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uin
             else if (gen == PixGen::F32)
                 rc = glf_image_processing_f32(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height,
                                               reinterpret_cast<float *>(b.d_out), ev, &st);
+            else if (gen == PixGen::RgbF32 && nsig > 0)
+                rc = glf_image_processing_rgbf32_signals(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height, nsig, d_sig, d_sig_out,
+                                                         reinterpret_cast<float *>(b.d_out), ev, &st);
+            else if (gen == PixGen::RgbF32)
+                rc = glf_image_processing_rgbf32(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height,
+                                                 reinterpret_cast<float *>(b.d_out), ev, &st);
             else if (gen == PixGen::Rgb) rc = glf_image_processing_rgb(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
             else if (gen == PixGen::U16)
                 rc = glf_image_processing_u16(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height,

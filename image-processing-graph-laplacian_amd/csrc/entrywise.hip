@@ -1,7 +1,8 @@
 // entrywise.hip -- the pixel formats without a factored form behind the same stage API as the grey kernels: the colour bilateral
 // affinity (glf_options.kernel = GLF_KERNEL_BILATERAL_RGB, image interleaved uint8 [height][width][3]) and the bilateral affinity
 // on 16-bit grey values (GLF_KERNEL_BILATERAL_U16, image uint16_t [height][width]) and on float values (GLF_KERNEL_BILATERAL_F32, image
-// float [height][width], any finite value):
+// float [height][width], any finite value), and the colour affinity on float channels (GLF_KERNEL_BILATERAL_RGBF32, image interleaved
+// float [height][width][3]):
 //
 //   K(i, j) = Es(dr) Es(dc) P(v_i - v_j) = exp2(-(s_loc (dr^2 + dc^2) + s_val |v_i - v_j|^2))
 //
@@ -25,6 +26,9 @@
 // Arithmetic on floats. dv is rounded once (2^-24 relative, exact when the two values are within a factor of two), dv^2 once more, the
 // exponent's fma once: ~3 x 2^-24 on t, |dK| <= K t ln2 x 1.8e-7 <= 7e-8, inside the same 1e-7 per entry. Inputs are finite (the entry
 // points check): P <= 1 and never NaN; a dv^2 that overflows gives exp2(-inf) = 0.
+// Float colour. Each of the three differences is rounded once, its square once, the two fmas once each; all terms are positive, so
+// dist2 carries at most ~5 x 2^-24 and an entry moves by at most K t ln2 x 3e-7 <= 1.1e-7. A sample's three channels do not fit its
+// record: they sit in the value block behind the records (Pix<G>::HAS_VALUE_BLOCK, sample_value<G>).
 #include "glf_internal.hpp"
 
 #include <cmath>
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void k_degree_entrywise(const uint8_t *__restr
     const unsigned b0 = blockIdx.x * 256, i = b0 + threadIdx.x;
     const bool live = i < p;
     const float4 s = samples[live ? i : p - 1];
-    const typename P::Val sv = P::value(s);
+    const typename P::Val sv = sample_value<G>(samples, round_up_dev(p, NYS_PAD), live ? i : p - 1, s); // (a value block: one more 16-byte load)
     const int r_begin = row0 + (int)blockIdx.y * EW_ROWS, r_end = min(r_begin + EW_ROWS, row1);
     // rows of the block's samples: the first and last sample (ascending indices)
     const int brmin = (int)samples[b0].x, brmax = (int)samples[min(b0 + 255u, p - 1)].x;
@@ -129,7 +133,8 @@ int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int wi
                                              coef.s_loc, coef.s_val, radius, partial.p, count.p)
     if (gen == PixGen::Rgb) GLF_DEGREE_EW(PixGen::Rgb);
     else if (gen == PixGen::U16) GLF_DEGREE_EW(PixGen::U16);
-    else GLF_DEGREE_EW(PixGen::F32);
+    else if (gen == PixGen::F32) GLF_DEGREE_EW(PixGen::F32);
+    else GLF_DEGREE_EW(PixGen::RgbF32);
 #undef GLF_DEGREE_EW
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
@@ -159,7 +164,8 @@ int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float 
     const dim3 grid((unsigned)ceil_div(N, 256));
     if (gen == PixGen::Rgb) hipLaunchKernelGGL(k_planes<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
     else if (gen == PixGen::U16) hipLaunchKernelGGL(k_planes<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
-    else hipLaunchKernelGGL(k_planes<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    else if (gen == PixGen::F32) hipLaunchKernelGGL(k_planes<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    else hipLaunchKernelGGL(k_planes<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -223,7 +229,8 @@ int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0,
     const dim3 grid((unsigned)nblk);
     if (gen == PixGen::Rgb) launch_apply_filter_pix<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
     else if (gen == PixGen::U16) launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
-    else launch_apply_filter_pix<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    else if (gen == PixGen::F32) launch_apply_filter_pix<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    else launch_apply_filter_pix<PixGen::RgbF32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -298,8 +305,11 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
     else if (gen == PixGen::U16)
         hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::U16>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
                            part_g.p, part_s.p);
-    else
+    else if (gen == PixGen::F32)
         hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::F32>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
+                           part_g.p, part_s.p);
+    else
+        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::RgbF32>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
                            part_g.p, part_s.p);
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * nch), dim3(256), 0, ctx->stream, part_g.p, nblk, ld * nch, d_c);
@@ -389,14 +399,17 @@ int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64
     else if (gen == PixGen::U16)
         launch_apply_filter_pix_signals<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
                                                      d_sig_out, N);
-    else
+    else if (gen == PixGen::F32)
         launch_apply_filter_pix_signals<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
                                                      d_sig_out, N);
+    else
+        launch_apply_filter_pix_signals<PixGen::RgbF32>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
+                                                        d_sig_out, N);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
 
-// ---- the float format's admission check -------------------------------------------------------------------------------------
+// ---- the float formats' admission check (float colour: N = its 3 x pixels floats) -------------------------------------------------------------------------------------
 // *bad |= 1 where a value is NaN or Inf: exponent bits all ones. Grid-strided, one flag write per wave that saw one.
 __global__ __launch_bounds__(256) void k_f32_nonfinite(const float *__restrict__ img, int64_t N, unsigned *__restrict__ bad)
 {

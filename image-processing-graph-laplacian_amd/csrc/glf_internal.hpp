@@ -254,33 +254,40 @@ __device__ __forceinline__ uint16_t filter_output_u16(int x, double c)
 
 // The pixel formats. Grey: uint8 [N] (GLF_KERNEL_BILATERAL and the other 8-bit kernels); Rgb: interleaved uint8 [N][3]
 // (GLF_KERNEL_BILATERAL_RGB); U16: uint16 [N] (GLF_KERNEL_BILATERAL_U16); F32: float [N] (GLF_KERNEL_BILATERAL_F32, any finite
-// value, h_val in the image's units). The image travels as a byte pointer; the entry-by-entry
+// value, h_val in the image's units); RgbF32: interleaved float [N][3] (GLF_KERNEL_BILATERAL_RGBF32, any finite values). The image
+// travels as a byte pointer; the entry-by-entry
 // kernels read it through the format's policy Pix<G>, which holds all that differs between the formats:
 //   In, NCH        the image element and the channels per pixel: channel k of pixel px is img[NCH px + k]
 //   Val, read      a pixel's value as the kernels compare it (its channels in f32, exact)
 //   record, value  the sample record of pixel px and the value it carries. Grey, U16, F32: {row, col, v, 0};
-//                  Rgb: {row, col, 0, R + 256 G + 65536 B} (the packed colour as an exact integer in f32)
+//                  Rgb: {row, col, 0, R + 256 G + 65536 B} (the packed colour as an exact integer in f32);
+//                  RgbF32: {row, col, 0, 0}: three floats do not fit the record, so HAS_VALUE_BLOCK is set and the sample table
+//                  carries a value block of float4 {R, G, B, 0}, one per sample, behind its padded records (samples + p_pad, p_pad =
+//                  round_up(p, NYS_PAD): one pointer, one allocation). value(record, entry) takes both; the formats without a
+//                  block ignore the entry, and sample_value<G> does not load it for them
 //   dist2          the squared photometric distance |a - b|^2 in a fixed operation order; the kernels take
 //                  K = exp2(-fmaf(dist2, s_val, (dr^2 + dc^2) s_loc))
 //   Tile, tile     the degree sweep's LDS element {value, col}; outside() lies in a column no sample reaches (K = 0)
 //   Out, output    the output element of the apply kernel and its rule for channel x (passed exactly, as a double) with its
 //                  f64 correction c: the grey d_out's rule, through f32 at 8 bits, in f64 at 16 bits; F32: (float)(x + c), the
-//                  float z itself, no clamp and no floor
+//                  float z itself, no clamp and no floor (RgbF32 too)
 // The factored forms over the 256 grey levels (grid, rank, the level-table degree) exist for Grey alone. The band form takes
-// the others as well (k_band<.., G>: the photometric factor from dist2 and one v_exp_f32 per entry), behind the PIX_BAND key.
-enum class PixGen { Grey, Rgb, U16, F32 };
+// the others as well (k_band<.., G>: the photometric factor from dist2 and one v_exp_f32 per entry; RgbF32 with three u32 per sample in
+// the chunk tails), behind the PIX_BAND key.
+enum class PixGen { Grey, Rgb, U16, F32, RgbF32 };
 template <PixGen G> struct Pix;
 // one grey value per pixel, stored as T (Grey: uint8_t, U16: uint16_t, F32: float): the record {row, col, v, 0}
 template <typename T> struct PixGreyValue {
     using In = T;
     using Val = float;
     static constexpr int NCH = 1;
+    static constexpr bool HAS_VALUE_BLOCK = false;
     __device__ __forceinline__ static Val read(const In *img, int64_t px) { return (float)img[px]; }
     __device__ __forceinline__ static float4 record(const In *img, uint32_t px, uint32_t width)
     {
         return make_float4((float)(px / width), (float)(px % width), (float)img[px], 0.f);
     }
-    __device__ __forceinline__ static Val value(float4 s) { return s.z; }
+    __device__ __forceinline__ static Val value(float4 s, float4) { return s.z; }
     __device__ __forceinline__ static float dist2(Val a, Val b) { const float d = a - b; return d * d; }
 };
 template <> struct Pix<PixGen::Grey> : PixGreyValue<uint8_t> {};
@@ -309,6 +316,7 @@ template <> struct Pix<PixGen::Rgb> {
     using Tile = float4; // {R, G, B, col}
     using Out = uint8_t;
     static constexpr int NCH = 3;
+    static constexpr bool HAS_VALUE_BLOCK = false;
     __device__ __forceinline__ static Val read(const In *img, int64_t px)
     {
         return make_float3((float)img[3 * px], (float)img[3 * px + 1], (float)img[3 * px + 2]);
@@ -318,7 +326,7 @@ template <> struct Pix<PixGen::Rgb> {
         const In *q = img + (size_t)px * 3;
         return make_float4((float)(px / width), (float)(px % width), 0.f, (float)((unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16)));
     }
-    __device__ __forceinline__ static Val value(float4 s)
+    __device__ __forceinline__ static Val value(float4 s, float4)
     {
         const unsigned v = (unsigned)s.w;
         return make_float3(ubyte_f32(v, 0), ubyte_f32(v, 1), ubyte_f32(v, 2));
@@ -338,6 +346,55 @@ template <> struct Pix<PixGen::Rgb> {
     __device__ __forceinline__ static float tile_col(Tile t) { return t.w; }
     __device__ __forceinline__ static Out output(double x, double c) { return filter_output((int)x, (float)c); }
 };
+// three float channels per pixel: Rgb's tile and dist2 (its operation order) on float reads, F32's output rule; the sample's channels
+// come from the value block. Each difference is rounded once, its square once, the two fmas once each: all terms positive, so dist2
+// carries at most ~5 x 2^-24 of relative error; a dist2 that overflows gives exp2(-inf) = 0
+template <> struct Pix<PixGen::RgbF32> {
+    using In = float;
+    using Val = float3;
+    using Tile = float4; // {R, G, B, col}
+    using Out = float;
+    static constexpr int NCH = 3;
+    static constexpr bool HAS_VALUE_BLOCK = true;
+    __device__ __forceinline__ static Val read(const In *img, int64_t px) { return make_float3(img[3 * px], img[3 * px + 1], img[3 * px + 2]); }
+    __device__ __forceinline__ static float4 record(const In *, uint32_t px, uint32_t width)
+    {
+        return make_float4((float)(px / width), (float)(px % width), 0.f, 0.f);
+    }
+    __device__ __forceinline__ static float4 block_entry(const In *img, uint32_t px)
+    {
+        const In *q = img + (size_t)px * 3;
+        return make_float4(q[0], q[1], q[2], 0.f);
+    }
+    __device__ __forceinline__ static Val value(float4, float4 e) { return make_float3(e.x, e.y, e.z); }
+    __device__ __forceinline__ static float dist2(Val a, Val b)
+    {
+        const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z;
+        return fmaf(d2, d2, fmaf(d1, d1, d0 * d0));
+    }
+    __device__ __forceinline__ static Tile tile(const In *img, int64_t px, int c)
+    {
+        const Val v = read(img, px);
+        return make_float4(v.x, v.y, v.z, (float)c);
+    }
+    __device__ __forceinline__ static Tile outside() { return make_float4(0.f, 0.f, 0.f, -1e30f); }
+    __device__ __forceinline__ static Val tile_value(Tile t) { return make_float3(t.x, t.y, t.z); }
+    __device__ __forceinline__ static float tile_col(Tile t) { return t.w; }
+    __device__ __forceinline__ static Out output(double x, double c) { return (float)(x + c); }
+};
+__device__ __forceinline__ unsigned round_up_dev(unsigned x, unsigned q) { return (x + q - 1) / q * q; }
+// the value sample i carries: from its record s alone, or (HAS_VALUE_BLOCK) from entry i of the value block behind the p_pad records
+template <PixGen G> __device__ __forceinline__ typename Pix<G>::Val sample_value(const float4 *__restrict__ samples, unsigned p_pad, unsigned i, float4 s)
+{
+    if constexpr (Pix<G>::HAS_VALUE_BLOCK) return Pix<G>::value(s, samples[(size_t)p_pad + i]);
+    else return Pix<G>::value(s, s);
+}
+// records the sample table allocates for p samples in the format: the padded records, and the value block behind them
+inline size_t sample_table_records(PixGen g, unsigned p)
+{
+    const size_t p_pad = (size_t)round_up(p, NYS_PAD);
+    return g == PixGen::RgbF32 ? 2 * p_pad : p_pad;
+}
 // host side: the format a kernel reads (and the bilateral kernel on a format), whether the factored forms over the 256 grey
 // levels apply to a kernel, bytes and channels per pixel
 inline PixGen pixgen_of(int kernel)
@@ -345,6 +402,7 @@ inline PixGen pixgen_of(int kernel)
     return kernel == GLF_KERNEL_BILATERAL_RGB   ? PixGen::Rgb
            : kernel == GLF_KERNEL_BILATERAL_U16 ? PixGen::U16
            : kernel == GLF_KERNEL_BILATERAL_F32 ? PixGen::F32
+           : kernel == GLF_KERNEL_BILATERAL_RGBF32 ? PixGen::RgbF32
                                                 : PixGen::Grey;
 }
 inline int bilateral_kernel_of(PixGen g)
@@ -352,10 +410,11 @@ inline int bilateral_kernel_of(PixGen g)
     return g == PixGen::Rgb   ? GLF_KERNEL_BILATERAL_RGB
            : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16
            : g == PixGen::F32 ? GLF_KERNEL_BILATERAL_F32
+           : g == PixGen::RgbF32 ? GLF_KERNEL_BILATERAL_RGBF32
                               : GLF_KERNEL_BILATERAL;
 }
 inline bool grey_levels_factor(int kernel) { return kernel != GLF_KERNEL_NLM && pixgen_of(kernel) == PixGen::Grey; }
-// the band form applies to a kernel: it factors over grey levels, or it is a colour / 16-bit bilateral kernel and PIX_BAND is set
+// the band form applies to a kernel: it factors over grey levels, or it is a colour / 16-bit / float bilateral kernel and PIX_BAND is set
 inline bool band_form_applies(const glf_ctx *ctx, int kernel) { return grey_levels_factor(kernel) || (ctx->tune.pix_band && pixgen_of(kernel) != PixGen::Grey); }
 template <PixGen G> constexpr size_t pix_bytes_of = sizeof(typename Pix<G>::In) * Pix<G>::NCH;
 inline size_t pix_bytes(PixGen g)
@@ -363,14 +422,24 @@ inline size_t pix_bytes(PixGen g)
     return g == PixGen::Rgb   ? pix_bytes_of<PixGen::Rgb>
            : g == PixGen::U16 ? pix_bytes_of<PixGen::U16>
            : g == PixGen::F32 ? pix_bytes_of<PixGen::F32>
+           : g == PixGen::RgbF32 ? pix_bytes_of<PixGen::RgbF32>
                               : pix_bytes_of<PixGen::Grey>;
 }
 inline int pix_channels(PixGen g)
 {
-    return g == PixGen::Rgb ? Pix<PixGen::Rgb>::NCH : g == PixGen::U16 ? Pix<PixGen::U16>::NCH : g == PixGen::F32 ? Pix<PixGen::F32>::NCH : Pix<PixGen::Grey>::NCH;
+    return g == PixGen::Rgb      ? Pix<PixGen::Rgb>::NCH
+           : g == PixGen::U16    ? Pix<PixGen::U16>::NCH
+           : g == PixGen::F32    ? Pix<PixGen::F32>::NCH
+           : g == PixGen::RgbF32 ? Pix<PixGen::RgbF32>::NCH
+                                 : Pix<PixGen::Grey>::NCH;
 }
 // the name of a format in messages
-inline const char *pix_name(PixGen g) { return g == PixGen::Rgb ? "colour" : g == PixGen::U16 ? "16-bit" : g == PixGen::F32 ? "float" : "8-bit"; }
+inline const char *pix_name(PixGen g)
+{
+    return g == PixGen::Rgb ? "colour" : g == PixGen::U16 ? "16-bit" : g == PixGen::F32 ? "float" : g == PixGen::RgbF32 ? "float colour" : "8-bit";
+}
+// the float formats (admitted after the finite check only) and the floats per pixel the check runs over
+inline bool pix_is_float(PixGen g) { return g == PixGen::F32 || g == PixGen::RgbF32; }
 
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
@@ -421,7 +490,7 @@ __device__ __forceinline__ void lds_dma_copy(const void *gsrc, void *ldst, int p
 
 // ---- stage implementations (device pointers, all on ctx->stream) -----------------
 
-// Sample table: float4 {row, col, value, 0} per sample + mask + device idx.
+// Sample table: float4 {row, col, value, 0} per sample (float colour: and the value block behind the padded records) + mask + device idx.
 struct SampleTables {
     DevBuf<float4> samples;
     DevBuf<uint8_t> mask;
@@ -470,7 +539,7 @@ int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int6
                  double *d_c, float *kernel_ms);
 // out[i] = sum over the chunks k of partial[k][i], k ascending (affinity.hip)
 __global__ void k_reduce_partials(const double *__restrict__ partial, unsigned p, int nchunks, double *__restrict__ out);
-// the formats without a factored form (entrywise.hip, gen Rgb, U16 or F32; d_img in the format): the contract of degree_rows, the
+// the formats without a factored form (entrywise.hip, gen Rgb, U16, F32 or RgbF32; d_img in the format): the contract of degree_rows, the
 // windowed entry-by-entry sweep (*evaluated = entries computed); the image's channels as float planes [NCH][N]; the outputs
 // (d_w [NCH][ld]; d_img / d_out [N] pixels, rows [pix0, pix1) only; d_zf optional [NCH][N])
 int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height, int row0, int row1,

@@ -119,8 +119,10 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
     __shared__ unsigned short clist[SKIP ? NYS_MAXCH : 1];
     __shared__ int cscratch[SKIP ? 257 : 1];
     // one array for everything (guide: a second __shared__ object can de-pipeline LDS staging)
-    __shared__ __attribute__((aligned(16))) float lds[2 * (NYS_KC * 4 + NYS_KC * MB * 32)];
-    constexpr int BUF = KC * 4 + KC * LD; // floats per buffer: sample table then Psi tile
+    // a format with a value block stages the chunk's KC value entries too, behind the Psi tile: the other formats' buffers do not move
+    constexpr int VB = P::HAS_VALUE_BLOCK ? NYS_KC * 4 : 0;
+    __shared__ __attribute__((aligned(16))) float lds[2 * (NYS_KC * 4 + NYS_KC * MB * 32 + VB)];
+    constexpr int BUF = KC * 4 + KC * LD + VB; // floats per buffer: sample table, then Psi tile (then the value entries)
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int half = lane >> 5, l31 = lane & 31;
@@ -158,6 +160,13 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
             const unsigned s = s0 + threadIdx.x;
             reinterpret_cast<float4 *>(lds + buf * BUF)[threadIdx.x] = (s < p) ? samples[s] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
+        if constexpr (P::HAS_VALUE_BLOCK) {
+            if (threadIdx.x >= 64 && threadIdx.x < 64 + KC) { // (the second wave: the first loads the records)
+                const unsigned k = threadIdx.x - 64, s = s0 + k;
+                reinterpret_cast<float4 *>(lds + buf * BUF + KC * 4 + KC * LD)[k] =
+                    (s < p) ? samples[(size_t)round_up_dev(p, NYS_PAD) + s] : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
         for (int e = threadIdx.x * 4; e < KC * LD; e += 256 * 4) {
             const unsigned s = s0 + e / LD;
             const float4 v = (s < p) ? *reinterpret_cast<const float4 *>(&psi[(size_t)s0 * LD + e])
@@ -171,11 +180,14 @@ __global__ __launch_bounds__(256) void k_nystroem(const uint8_t *__restrict__ im
         const int buf = ch & 1;
         if (ch + 1 < nlist) stage(chunk_at(ch + 1), buf ^ 1);
         const float4 *stb = reinterpret_cast<const float4 *>(lds + buf * BUF) + half * (KC / 2);
+        [[maybe_unused]] const float4 *svb = stb + (KC * 4 + KC * LD) / 4; // (the staged value entries of this half, where the format has them)
         const float *psb = lds + buf * BUF + KC * 4 + (half * (KC / 2)) * LD + l31;
 #pragma unroll 4
         for (int kk = 0; kk < KC / 2; ++kk) {
             const float4 s = stb[kk]; // two addresses per wave: broadcast within each half
-            const typename P::Val sv = P::value(s);
+            typename P::Val sv;
+            if constexpr (P::HAS_VALUE_BLOCK) sv = P::value(s, svb[kk]);
+            else sv = P::value(s, s);
             float a[PB];
 #pragma unroll
             for (int b = 0; b < PB; ++b) {
@@ -848,10 +860,13 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
             if (rc != GLF_ERR_UNSUPPORTED) return rc;
             if (path) *path = 0;
         }
-        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour, 16-bit and float kernels have no 8-bit y for Phi^T y");
+        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour, 16-bit, float and float colour kernels have no 8-bit y for Phi^T y");
         window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
 #define GLF_NYS_EW(G_) nystroem_entrywise<G_>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated)
-        rc = gen == PixGen::Rgb ? GLF_NYS_EW(PixGen::Rgb) : gen == PixGen::U16 ? GLF_NYS_EW(PixGen::U16) : GLF_NYS_EW(PixGen::F32);
+        rc = gen == PixGen::Rgb   ? GLF_NYS_EW(PixGen::Rgb)
+             : gen == PixGen::U16 ? GLF_NYS_EW(PixGen::U16)
+             : gen == PixGen::F32 ? GLF_NYS_EW(PixGen::F32)
+                                  : GLF_NYS_EW(PixGen::RgbF32);
 #undef GLF_NYS_EW
         if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
         return rc;

@@ -55,8 +55,9 @@ __host__ __device__ inline unsigned band_lds_bytes(int mb, int nw, int rad, int 
 // [n-tile j][hi | lo][lane = 32 (k / 8) + n][k % 8] f16 (1 KiB each), then 128 v of the 16 samples as u32 (the row
 // stride of the replicated photometric table) and padding to 256 B. Sample columns past nc: zeros.
 // RAW (the colour and 16-bit formats): svals is the u32 image of the sample values (the 16-bit value, or the packed colour
-// R + 256 G + 65536 B) and the tail carries it as it is.
-template <bool RAW>
+// R + 256 G + 65536 B) and the tail carries it as it is. NCH = 3 (float colour): svals is three such planes [3][nr][nc], the bit
+// patterns of R, G and B, and the tail carries R at +0, G at +64 and B at +128.
+template <bool RAW, int NCH = 1>
 __global__ __launch_bounds__(256) void k_band_prep(const float *__restrict__ X, unsigned x_ld, const float *__restrict__ colscale,
                                                     const void *__restrict__ svals_, int nr, int nc, int ksc, int mb,
                                                     unsigned char *__restrict__ chunks)
@@ -88,7 +89,13 @@ __global__ __launch_bounds__(256) void k_band_prep(const float *__restrict__ X, 
     f[(size_t)(jb * 2 + 1) * 64 + h * 32 + rr] = lo;
     if (jb == 0 && rr < 8) {
         const int k = 8 * (int)h + (int)rr, bcol = 16 * blk + k;
-        reinterpret_cast<unsigned *>(ch + mb * 2048)[k] = bcol < nc ? (RAW ? 1u : BAND_PSTRIDE) * (unsigned)svals[(size_t)a * nc + bcol] : 0u;
+        if constexpr (NCH == 1)
+            reinterpret_cast<unsigned *>(ch + mb * 2048)[k] = bcol < nc ? (RAW ? 1u : BAND_PSTRIDE) * (unsigned)svals[(size_t)a * nc + bcol] : 0u;
+        else {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+                reinterpret_cast<unsigned *>(ch + mb * 2048)[16 * c + k] = bcol < nc ? (unsigned)svals[((size_t)c * nr + a) * nc + bcol] : 0u;
+        }
     }
 }
 
@@ -154,11 +161,19 @@ __device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
 //   values (F32: the float's bit pattern), and the factor is P = exp2(pix_nsval dist2) with Pix<G>::dist2 and one v_exp_f32 per entry (pix_nsval = -s_val); no
 //   table in LDS. Er Ec stays a separate factor, so an entry outside the radius is still an exact zero pair. These
 //   instantiations write Phi (or Y): no filter in the epilogue, no c.
+//   RgbF32: three u32 per sample (the bit patterns of R, G, B): tval for the sample targets is three planes [3][nr][nc], and the tail
+//   carries R at +0, G at +64, B at +128 -- a k-step reads its 8 samples' channels as three pairs of uint4. With the pixels as targets
+//   the tail piece of a slot is assembled by lanes 0 - 11 of its one DMA instruction (four lanes per channel) in the same layout.
 template <PixGen G> __device__ __forceinline__ typename Pix<G>::Val band_pix_value(unsigned v)
 {
     if constexpr (G == PixGen::Rgb) return make_float3(ubyte_f32(v, 0), ubyte_f32(v, 1), ubyte_f32(v, 2));
     else if constexpr (G == PixGen::F32) return __uint_as_float(v); // (the float's bit pattern)
     else return (float)v;
+}
+// (float colour: the three bit patterns of a value)
+__device__ __forceinline__ float3 band_pix_value3(unsigned r, unsigned g, unsigned b)
+{
+    return make_float3(__uint_as_float(r), __uint_as_float(g), __uint_as_float(b));
 }
 template <int MB, int PB, int NW, bool SAMPLES, int NS = 0, PixGen G = PixGen::Grey>
 __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tval, int width, int row_begin, const int *__restrict__ grow,
@@ -174,7 +189,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
 {
     static_assert(!SAMPLES || PB == 1, "sample targets: one tile of 32 per wave");
     static_assert(G == PixGen::Grey || NS == 0, "the colour and 16-bit instantiations have no filter epilogue");
-    constexpr bool GREY = G == PixGen::Grey;
+    constexpr bool GREY = G == PixGen::Grey, TRI = G == PixGen::RgbF32; // (TRI: three u32 per sample value)
     constexpr unsigned PLUT_BYTES = GREY ? 256 * BAND_PSTRIDE : 0u;
     constexpr int LD = 32 * MB, CHB = band_chunk_bytes(MB), NPIECE = MB * 2 + 1; // (the last piece is the 256-byte tail)
     // Pixel targets: a unit of work is (pair of consecutive band rows, half-block of 8 sample columns): lanes 0 - 31 of the MFMA's
@@ -261,7 +276,11 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
             const int bb = min(tile * 32 + l31, nc - 1);
             tc[b] = gcol[bb];
             if constexpr (GREY) pv128[b] = BAND_PSTRIDE * (unsigned)tval[(size_t)trow * nc + bb];
-            else pvv[b] = band_pix_value<G>(reinterpret_cast<const unsigned *>(tval)[(size_t)trow * nc + bb]);
+            else if constexpr (TRI) {
+                const unsigned *tv = reinterpret_cast<const unsigned *>(tval) + (size_t)trow * nc + bb;
+                const size_t plane = (size_t)nr * nc;
+                pvv[b] = band_pix_value3(tv[0], tv[plane], tv[2 * plane]);
+            } else pvv[b] = band_pix_value<G>(reinterpret_cast<const unsigned *>(tval)[(size_t)trow * nc + bb]);
         } else {
             const int cc = min((tile * PB + b) * 32 + l31, width - 1);
             tc[b] = cc;
@@ -298,7 +317,10 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     // pixel targets: byte offsets of a lane's 16 bytes within a DMA instruction, from the chunk of the pair's first row: the piece's
     // half for lanes 0 - 31 and the same of the next band row (ksc chunks on) for lanes 32 - 63; of the tail, lanes 0 - 1 and 2 - 3
     const unsigned dma_off_row = 16u * (unsigned)l31, dma_off = dma_off_row + (half ? (unsigned)ksc * CHB : 0u);
-    const unsigned dma_toff_row = 16u * (unsigned)(lane & 1), dma_toff = dma_toff_row + ((lane >> 1) & 1 ? (unsigned)ksc * CHB : 0u);
+    // (TRI: lanes 4 c .. 4 c + 3 the same of channel c, 64 c bytes on in the tail and in the slot)
+    constexpr int TAIL_LANES = TRI ? 12 : 4;
+    const unsigned dma_toff_row = 16u * (unsigned)(lane & 1) + (TRI ? 64u * (unsigned)(lane >> 2) : 0u),
+                   dma_toff = dma_toff_row + ((lane >> 1) & 1 ? (unsigned)ksc * CHB : 0u);
     auto issue = [&](int blk, int g0, int buf) -> int { // returns the DMA instructions this wave issued
         int n = 0;
         for (int q = wave; q < BAND_G * NPIECE; q += NW) { // (wave-uniform)
@@ -317,7 +339,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
                 const unsigned char *ch = chunks + ((size_t)(alo + i) * ksc + (blk >> 1)) * CHB + k * 1024;
                 const bool both = i + 1 < nb;
                 if (k < NPIECE - 1) lds_dma_16B_base(ch + 512 * (blk & 1), both ? dma_off : dma_off_row, dst);
-                else if (lane < 4) lds_dma_16B_base(ch + 32 * (blk & 1), both ? dma_toff : dma_toff_row, dst);
+                else if (lane < TAIL_LANES) lds_dma_16B_base(ch + 32 * (blk & 1), both ? dma_toff : dma_toff_row, dst);
             }
             ++n;
         }
@@ -348,7 +370,47 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
         // tile's MFMAs between the vector instructions of the next tile's generation inside a step costs no registers and
         // measured 2 % slower; tiles of 32 or 128 columns per wave (PB = 1, 4): 11.6 / 11.1 ms against 9.2.)
         float pp[PB][8];
-        if constexpr (GREY) {
+        if constexpr (TRI) {
+            // the sample's three channels from the tail (G 64 bytes, B 128 bytes behind R): Pix<G>::dist2 in its own operation order,
+            // fmaf(dB, dB, fmaf(dG, dG, dR dR)), taken channel by channel over the step's entries so that one channel's 8 values are live
+            // at a time (all 24 at once cost the kernel a wave per SIMD), then one v_exp_f32 per entry
+            const unsigned char *tl = sl + MB * 2048 + 32 * half;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float sr = __uint_as_float(sv128[e]);
+#pragma unroll
+                for (int b = 0; b < PB; ++b) {
+                    const float d = pvv[b].x - sr;
+                    pp[b][e] = d * d;
+                }
+            }
+            {
+                const uint4 g0 = *reinterpret_cast<const uint4 *>(tl + 64), g1 = *reinterpret_cast<const uint4 *>(tl + 80);
+                const unsigned sg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v = __uint_as_float(sg[e]);
+#pragma unroll
+                    for (int b = 0; b < PB; ++b) {
+                        const float d = pvv[b].y - v;
+                        pp[b][e] = fmaf(d, d, pp[b][e]);
+                    }
+                }
+            }
+            {
+                const uint4 b0 = *reinterpret_cast<const uint4 *>(tl + 128), b1 = *reinterpret_cast<const uint4 *>(tl + 144);
+                const unsigned sb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float v = __uint_as_float(sb[e]);
+#pragma unroll
+                    for (int b = 0; b < PB; ++b) {
+                        const float d = pvv[b].z - v;
+                        pp[b][e] = __builtin_amdgcn_exp2f(fmaf(d, d, pp[b][e]) * pix_nsval);
+                    }
+                }
+            }
+        } else if constexpr (GREY) {
 #pragma unroll
             for (int b = 0; b < PB; ++b)
 #pragma unroll
@@ -888,12 +950,13 @@ static int launch_band_samples(glf_ctx *ctx, const BandTables &bt, const uint8_t
 }
 
 // svals: uint8 [nr][nc] (raw = false) or u32 [nr][nc] (raw: the colour and 16-bit formats)
+// (nch = 3: float colour, three planes)
 static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *colscale, const void *svals, bool raw, int nr, int nc, int ksc, int mb,
-                     unsigned char *chunks)
+                     unsigned char *chunks, int nch = 1)
 {
     const size_t total = (size_t)nr * ksc * mb * 64;
-    hipLaunchKernelGGL(raw ? k_band_prep<true> : k_band_prep<false>, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, ctx->stream, X, x_ld,
-                       colscale, svals, nr, nc, ksc, mb, chunks);
+    auto kern = raw && nch == 3 ? k_band_prep<true, 3> : raw ? k_band_prep<true> : k_band_prep<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, ctx->stream, X, x_ld, colscale, svals, nr, nc, ksc, mb, chunks);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -914,7 +977,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     const int mb = (int)LD / 32;
     DevBuf<float> colscale, inv, camx;
     DevBuf<uint8_t> svals;
-    DevBuf<unsigned> svals32; // (Rgb, U16: the sample values as u32)
+    DevBuf<unsigned> svals32; // (Rgb, U16, F32: the sample values as u32; float colour: three planes)
     DevBuf<unsigned char> chunks;
     DevBuf<double> cpart;
     const PixGen gen = pixgen_of(coef.kernel);
@@ -924,7 +987,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(colscale.alloc(ctx, ld_total));
     GLF_TRY(inv.alloc(ctx, ld_total));
     GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    if (raw) GLF_TRY(svals32.alloc(ctx, p));
+    if (raw) GLF_TRY(svals32.alloc(ctx, svals32_planes(gen) * p));
     else GLF_TRY(svals.alloc(ctx, p));
     GLF_TRY(chunks.alloc(ctx, (size_t)bt.nr * bt.ksc * band_chunk_bytes(mb)));
     GLF_TRY(dev_eval.alloc(ctx, 1));
@@ -941,7 +1004,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     float band_ms = 0.f;
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
-        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p));
+        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p, (int)svals32_planes(gen)));
         const bool timed = stats && (int)cb < glf_ctx::CP_RING;
         if (timed)
             for (int q = 0; q < 2; ++q)
@@ -954,7 +1017,8 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
 #define GLF_BAND_PX(MB_, G_) launch_band_px<MB_, 0, G_>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster, nullptr, dev_eval.p, nullptr, pix0, nsval)
             if (gen == PixGen::Rgb) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::Rgb) : GLF_BAND_PX(1, PixGen::Rgb));
             else if (gen == PixGen::U16) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::U16) : GLF_BAND_PX(1, PixGen::U16));
-            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::F32) : GLF_BAND_PX(1, PixGen::F32));
+            else if (gen == PixGen::F32) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::F32) : GLF_BAND_PX(1, PixGen::F32));
+            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::RgbF32) : GLF_BAND_PX(1, PixGen::RgbF32));
 #undef GLF_BAND_PX
         } else if (mb == 2)
             GLF_TRY(launch_band_px<2>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,

@@ -171,12 +171,14 @@ int glf_image_processing_batch(glf_ctx *const *ctxs, int nctx, const glf_options
 
 // ------------------------------------------------------------------------------------------
 
-// the float format admits finite values only: one pass over the image before anything else
-static int f32_admit(glf_ctx *ctx, const float *d_img, int width, int height)
+// the float formats admit finite values only: one pass over the image's floats (nch per pixel) before anything else
+static int f32_admit(glf_ctx *ctx, const float *d_img, int width, int height, int nch = 1)
 {
     bool finite = true;
-    GLF_TRY(f32_all_finite(ctx, d_img, (int64_t)width * height, &finite));
-    if (!finite) return set_error(ctx, GLF_ERR_INVALID, "the float image holds a NaN or an Inf: finite values only");
+    GLF_TRY(f32_all_finite(ctx, d_img, (int64_t)width * height * nch, &finite));
+    if (!finite)
+        return set_error(ctx, GLF_ERR_INVALID, nch == 1 ? "the float image holds a NaN or an Inf: finite values only"
+                                                        : "the float colour image holds a NaN or an Inf: finite values only");
     return GLF_OK;
 }
 
@@ -185,14 +187,15 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
                                 float h_val)
 {
     if (!ctx || !K_B || !d_img || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_F32) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
+    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", kernel);
     if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3)) // (nlm.hip reflects an out-of-image patch index once: valid from 3 pixels on)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     GLF_ENTER(ctx);
-    if (kernel == GLF_KERNEL_BILATERAL_F32) GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height));
+    if (pix_is_float(pixgen_of(kernel)))
+        GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height, pix_channels(pixgen_of(kernel))));
     const unsigned p = sample_size;
     SampleTables tb;
-    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3]; U16: uint16_t; F32: float)
+    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3]; U16: uint16_t; F32: float; RGBF32: float [height][width][3])
     const KernelCoef coef = make_coef(kernel, h_loc, h_val);
     DevBuf<double> deg;
     GLF_TRY(deg.alloc(ctx, p));
@@ -588,6 +591,30 @@ int glf_image_processing_f32_signals(glf_ctx *ctx, const glf_options *opt, const
                                 reinterpret_cast<uint8_t *>(d_out), nullptr, eigvals_out, stats, nullptr, &sig);
 }
 
+int glf_image_processing_rgbf32(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, float *d_out_rgb,
+                                double *eigvals_out, glf_stats *stats)
+{
+    return glf_image_processing_rgbf32_capture(ctx, opt, d_rgb, width, height, d_out_rgb, eigvals_out, stats, nullptr);
+}
+
+// (the float output is z itself, interleaved as the image: no d_zf)
+int glf_image_processing_rgbf32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height,
+                                        float *d_out_rgb, double *eigvals_out, glf_stats *stats, glf_capture *cap)
+{
+    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    return image_processing_run(ctx, opt, PixGen::RgbF32, reinterpret_cast<const uint8_t *>(d_rgb), width, height,
+                                reinterpret_cast<uint8_t *>(d_out_rgb), nullptr, eigvals_out, stats, cap, nullptr);
+}
+
+int glf_image_processing_rgbf32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, int nsig,
+                                        const float *d_sig, float *d_sig_out, float *d_out_rgb, double *eigvals_out, glf_stats *stats)
+{
+    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
+    const SignalPlanes sig{nsig, d_sig, d_sig_out};
+    return image_processing_run(ctx, opt, PixGen::RgbF32, reinterpret_cast<const uint8_t *>(d_rgb), width, height,
+                                reinterpret_cast<uint8_t *>(d_out_rgb), nullptr, eigvals_out, stats, nullptr, &sig);
+}
+
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
                                 uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
@@ -595,7 +622,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     if (cap && cap->struct_size != sizeof(glf_capture))
         return set_error(ctx, GLF_ERR_INVALID, "glf_capture.struct_size %u != %zu", cap->struct_size, sizeof(glf_capture));
     GLF_ENTER(ctx);
-    if (gen == PixGen::F32) GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height)); // (before anything else)
+    if (pix_is_float(gen)) GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height, pix_channels(gen))); // (before anything else)
     pool_age(ctx);
     glf_options opt;
     glf_options_default(&opt);
@@ -614,11 +641,13 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
             const char *what = pix_name(gen);
             return set_error(ctx, GLF_ERR_UNSUPPORTED, "%s filtering: kernel %d (the %s bilateral kernel only)", what, opt.kernel, what);
         }
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, pixgen_of(opt.kernel) == PixGen::Rgb   ? "the colour kernel takes an RGB image: glf_image_processing_rgb"
-                                                   : pixgen_of(opt.kernel) == PixGen::F32 ? "the float kernel takes a float image: glf_image_processing_f32"
-                                                                                          : "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
+        return set_error(ctx, GLF_ERR_UNSUPPORTED,
+                         pixgen_of(opt.kernel) == PixGen::Rgb      ? "the colour kernel takes an RGB image: glf_image_processing_rgb"
+                         : pixgen_of(opt.kernel) == PixGen::F32    ? "the float kernel takes a float image: glf_image_processing_f32"
+                         : pixgen_of(opt.kernel) == PixGen::RgbF32 ? "the float colour kernel takes a float RGB image: glf_image_processing_rgbf32"
+                                                                   : "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
     }
-    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_F32) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
+    if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     if (opt.filter_mode < GLF_FILTER_REFERENCE || opt.filter_mode > GLF_FILTER_SHARPEN) return set_error(ctx, GLF_ERR_INVALID, "filter_mode %d", opt.filter_mode);

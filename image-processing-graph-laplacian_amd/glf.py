@@ -35,6 +35,7 @@ MAT_DENSE, MAT_DIAG, MAT_KERNEL_B = 0, 1, 2
 ROWS_NA, ROWS_SAMPLE_FIRST, ROWS_RASTER = 0, 1, 2
 KERNEL_BILATERAL, KERNEL_PHOTOMETRIC, KERNEL_SPATIAL, KERNEL_NLM, KERNEL_BILATERAL_RGB, KERNEL_BILATERAL_U16 = 0, 1, 2, 3, 4, 5
 KERNEL_BILATERAL_F32 = 6
+KERNEL_BILATERAL_RGBF32 = 7
 CONTRACT_F32_MFMA, CONTRACT_F16_SPLIT = 1, 2
 FILTER_REFERENCE, FILTER_POC, FILTER_SMOOTH, FILTER_SHARPEN = 0, 1, 2, 3
 SAMPLING_UNIFORM, SAMPLING_RANDOM = 0, 1
@@ -58,6 +59,8 @@ EXPORTS = [
     "glf_multi_image_processing_rgb_signals", "glf_multi_image_processing_u16_signals",
     "glf_image_processing_f32", "glf_image_processing_f32_capture", "glf_image_processing_f32_signals",
     "glf_multi_image_processing_f32", "glf_multi_image_processing_f32_signals", "glf_read_pfm", "glf_write_pfm",
+    "glf_image_processing_rgbf32", "glf_image_processing_rgbf32_capture", "glf_image_processing_rgbf32_signals",
+    "glf_multi_image_processing_rgbf32", "glf_multi_image_processing_rgbf32_signals", "glf_read_pfm_rgb", "glf_write_pfm_rgb",
 ]
 MAX_SIGNALS = 4
 
@@ -285,6 +288,35 @@ def write_pfm(path, img):
         raise GlfError(ERR_IO, path)
 
 
+def read_pfm_rgb(path):
+    """A colour Portable Float Map ("PF", either byte order) as float32 [H, W, 3], rows top first; anything else raises GlfError."""
+    rows = C.POINTER(C.POINTER(C.c_float))()
+    w, h = C.c_int(), C.c_int()
+    rc = _lib.glf_read_pfm_rgb(path.encode(), C.byref(rows), C.byref(w), C.byref(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+    img = np.empty((h.value, w.value, 3), dtype=np.float32)
+    for r in range(h.value):
+        img[r] = np.ctypeslib.as_array(rows[r], shape=(w.value, 3))
+        _lib.glf_host_free(rows[r])
+    _lib.glf_host_free(rows)
+    return img
+
+
+def write_pfm_rgb(path, img):
+    """Writes float32 [H, W, 3] as a little-endian colour Portable Float Map (scale -1.0)."""
+    img = np.ascontiguousarray(img, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 3:
+        raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
+    h, w = img.shape[:2]
+    rowptr = (C.POINTER(C.c_float) * h)()
+    for r in range(h):
+        rowptr[r] = C.cast(img.ctypes.data + r * w * 12, C.POINTER(C.c_float))
+    rc = _lib.glf_write_pfm_rgb(path.encode(), rowptr, C.c_uint(w), C.c_uint(h))
+    if rc != 0:
+        raise GlfError(ERR_IO, path)
+
+
 def shard_rows(height, rank, size):
     """Pixel rows [row0, row1) owned by `rank` (glf_shard_rows; used by glf_image_processing)."""
     r0, r1 = C.c_int(), C.c_int()
@@ -494,6 +526,29 @@ class Multi:
         opt = opt or default_options()
         out = np.zeros((h, w), dtype=np.float32)
         infos = self._run("glf_multi_image_processing_f32_signals", opt, img, out, None,
+                          sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)), no_zf=True)
+        return out, sig_out, infos
+
+    def image_processing_rgbf32(self, img, opt=None):
+        """glf_multi_image_processing_rgbf32: host float32 [H, W, 3] in (finite values), (z float32 [H, W, 3], per-rank infos)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
+        opt = opt or default_options()
+        out = np.zeros(img.shape, dtype=np.float32)
+        return out, self._run("glf_multi_image_processing_rgbf32", opt, img, out, None, no_zf=True)
+
+    def image_processing_rgbf32_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_rgbf32_signals: host float32 [H, W, 3] plus float planes [nsig, H, W] filtered through the
+        float colour graph. Returns (z float32 [H, W, 3], sig_out f32 [nsig, H, W], infos)."""
+        img = np.ascontiguousarray(img, dtype=np.float32)
+        if img.ndim != 3 or img.shape[2] != 3:
+            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
+        h, w = img.shape[:2]
+        sig, sig_out = self._planes(signals, h, w)
+        opt = opt or default_options()
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        infos = self._run("glf_multi_image_processing_rgbf32_signals", opt, img, out, None,
                           sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)), no_zf=True)
         return out, sig_out, infos
 
@@ -754,10 +809,13 @@ class Context:
     # -- stages (names as in hpc/*.h) -------------------------------------------------------
     def ComputeAffinityMatrices(self, d_img, sample_indices, want_KA=True, kernel=KERNEL_BILATERAL,
                                 h_loc=40.0, h_val=30.0):
-        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3]; KERNEL_BILATERAL_U16: uint16 [H, W]; KERNEL_BILATERAL_F32: float32 [H, W])
-        dtype = {KERNEL_BILATERAL_U16: self.torch.uint16, KERNEL_BILATERAL_F32: self.torch.float32}.get(kernel, self.torch.uint8)
+        # (KERNEL_BILATERAL_RGB: d_img is [H, W, 3]; KERNEL_BILATERAL_U16: uint16 [H, W]; KERNEL_BILATERAL_F32: float32 [H, W];
+        # KERNEL_BILATERAL_RGBF32: float32 [H, W, 3])
+        dtype = {KERNEL_BILATERAL_U16: self.torch.uint16, KERNEL_BILATERAL_F32: self.torch.float32,
+                 KERNEL_BILATERAL_RGBF32: self.torch.float32}.get(kernel, self.torch.uint8)
+        colour = kernel in (KERNEL_BILATERAL_RGB, KERNEL_BILATERAL_RGBF32)
         assert d_img.dtype == dtype and d_img.is_cuda and d_img.is_contiguous()
-        assert d_img.dim() == (3 if kernel == KERNEL_BILATERAL_RGB else 2) and (kernel != KERNEL_BILATERAL_RGB or d_img.shape[2] == 3)
+        assert d_img.dim() == (3 if colour else 2) and (not colour or d_img.shape[2] == 3)
         h, w = d_img.shape[:2]
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)
         K_A, K_B = Mat(), Mat()
@@ -963,6 +1021,36 @@ class Context:
         with torch.cuda.stream(self.stream):
             out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
         info = self._run("glf_image_processing_f32_signals", "image_processing_f32_signals", opt, d_img, out, None, sig=sig, no_zf=True)
+        return out, sig_out, info
+
+    def image_processing_rgbf32(self, d_rgb, opt=None, capture=False, out=None):
+        """Float colour filtering (glf_image_processing_rgbf32): d_rgb (device float32 [H, W, 3], finite values: HDR, [0, 1] RGB,
+        Lab / YUV, a network's output) defines the graph through the differences of its three channels (opt.h_val in the image's units)
+        and each channel goes through the graph's filter. Returns (z float32 [H, W, 3], info): the output is the float z itself,
+        interleaved as the image, not clamped. A NaN or an Inf in d_rgb raises GlfError(ERR_INVALID) and `out` (optional: a device
+        float32 [H, W, 3] to write into) is left as it was. capture=True adds info["capture"] as image_processing_rgb does."""
+        torch = self.torch
+        assert d_rgb.dtype == torch.float32 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
+        h, w = d_rgb.shape[:2]
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
+        with torch.cuda.stream(self.stream):
+            if out is None:
+                out = torch.zeros((h, w, 3), dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.is_cuda and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
+        return out, self._run("glf_image_processing_rgbf32_capture", "image_processing_rgbf32", opt, d_rgb, out, None, capture, no_zf=True)
+
+    def image_processing_rgbf32_signals(self, d_rgb, signals, opt=None):
+        """Joint filtering under a float colour guide (glf_image_processing_rgbf32_signals): as image_processing_rgb_signals with the
+        graph and the output of image_processing_rgbf32. Returns (z float32 [H, W, 3], sig_out float32 [nsig, H, W], info)."""
+        torch = self.torch
+        assert d_rgb.dtype == torch.float32 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
+        h, w = d_rgb.shape[:2]
+        opt = opt or default_options()
+        sig_out, sig = self._signal_planes(signals, h, w)
+        with torch.cuda.stream(self.stream):
+            out = torch.zeros((h, w, 3), dtype=torch.float32, device=self.device)
+        info = self._run("glf_image_processing_rgbf32_signals", "image_processing_rgbf32_signals", opt, d_rgb, out, None, sig=sig, no_zf=True)
         return out, sig_out, info
 
     def image_processing_rgb_signals(self, d_rgb, signals, opt=None, want_float=False):

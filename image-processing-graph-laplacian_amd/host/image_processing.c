@@ -8,7 +8,7 @@
  *                    [-num_samples P | -sample_frac F] [-sampling uniform|random] [-sampling_seed S] [-fused] [-device D] [-no_approx] [-use_slepc]
  *                    [-dump_eigvecs] [-ngpu N [-ngpu_backend rccl|loopback]] [-filter_pow K]
  *                    [-kernel bilateral|photometric|spatial|nlm] [-h_loc X] [-h_val X] [-gain X] [-dump_residual]
- *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16 | -float32] [-pix_band]
+ *                    [-filter reference|poc|smooth|sharpen [-sharpen_beta B]] [-color [-chroma | -rgb_graph]] [-depth16 | -float32 | -float_rgb] [-pix_band]
  *                    [-planes F1[,F2[,F3[,F4]]]]
  * -filter poc applies the Python PoC's active filter z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305) instead
  * of hpc/display.c:58-83; -filter smooth / sharpen the PoC's `smoothing` z = W y and `sharpening` z = (1 + B) W^2 y - B W^3 y
@@ -28,6 +28,10 @@
  * -filter, and writes results/input.pfm and results/output.pfm (the float z, not clamped); a NaN or an Inf in the file is refused.
  * It combines with -pix_band, -planes (the planes stay PNGs) and -ngpu N like -depth16, and with neither -depth16, -color, -no_approx
  * nor a -kernel other than bilateral.
+ * -float_rgb reads a colour Portable Float Map ("PF", either byte order) and filters it on its three float channels
+ * (glf_image_processing_rgbf32: the colour bilateral kernel on any finite values, -h_val in the image's own units, default 30) with the
+ * same -filter, and writes results/input.pfm and results/output.pfm (both "PF"; the float z, not clamped); a NaN or an Inf in the file
+ * is refused. It combines with -pix_band, -planes (grey PNGs) and -ngpu N like -float32, and with neither -color, -chroma, -rgb_graph, -depth16, -float32, -no_approx nor a -kernel option.
  * -pix_band (with -depth16, -float32 or -color -rgb_graph) sets the PIX_BAND tuning key: the 16-bit / colour kernel takes the band form
  * of the Nystroem stage and of the operator wherever the grey kernel would (GLF_PIX_BAND=1 in the environment does the same), and
  * one more line names the routes taken ("band form: nystroem_path 4, matvec_path 4", or the fallback's numbers).
@@ -423,12 +427,13 @@ static int planes_write(unsigned width, unsigned height, const char *graph)
     return status;
 }
 
-/* -depth16 / -float32: img (rows of `width` uint16_t, or float with f32 set) through glf_image_processing_u16 / _f32 on one context, or
- * the glf_multi_ call on ngpu ranks; returns the output rows in the input's format (NULL on failure, the message printed). */
+/* -depth16 / -float32 / -float_rgb: img (rows of `width` uint16_t; float with f32 = 1; 3 interleaved floats with f32 = 2) through
+ * glf_image_processing_u16 / _f32 / _rgbf32 on one context, or the glf_multi_ call on ngpu ranks; returns the output rows in the
+ * input's format (NULL on failure, the message printed). */
 static void **DeepComputation(void **img, unsigned width, unsigned height, int ngpu, int backend, int f32)
 {
-    const size_t n = (size_t)width * height, esz = f32 ? sizeof(float) : sizeof(uint16_t);
-    const char *fn = f32 ? "glf_image_processing_f32" : "glf_image_processing_u16";
+    const size_t n = (size_t)width * height, esz = f32 == 2 ? 3 * sizeof(float) : f32 ? sizeof(float) : sizeof(uint16_t); /* bytes per pixel */
+    const char *fn = f32 == 2 ? "glf_image_processing_rgbf32" : f32 ? "glf_image_processing_f32" : "glf_image_processing_u16";
     void *flat = malloc(esz * n), *flat_out = calloc(n, esz);
     void **rows = NULL;
     glf_options opt;
@@ -449,7 +454,11 @@ static void **DeepComputation(void **img, unsigned width, unsigned height, int n
         if (rc != GLF_OK) fprintf(stderr, "glf_multi_create(%d GPUs, %s): %s\n", ngpu, backend == GLF_MULTI_RCCL ? "rccl" : "loopback", glf_strerror(rc));
         else if (st) {
             for (int r = 0; r < ngpu; ++r) pix_band_set(glf_multi_ctx(world, r));
-            if (f32)
+            if (f32 == 2)
+                rc = g_nplanes ? glf_multi_image_processing_rgbf32_signals(world, &opt, (const float *)flat, (int)width, (int)height, g_nplanes,
+                                                                           g_planes, g_planes_out, (float *)flat_out, NULL, st)
+                               : glf_multi_image_processing_rgbf32(world, &opt, (const float *)flat, (int)width, (int)height, (float *)flat_out, NULL, st);
+            else if (f32)
                 rc = g_nplanes ? glf_multi_image_processing_f32_signals(world, &opt, (const float *)flat, (int)width, (int)height, g_nplanes, g_planes,
                                                                         g_planes_out, (float *)flat_out, NULL, st)
                                : glf_multi_image_processing_f32(world, &opt, (const float *)flat, (int)width, (int)height, (float *)flat_out, NULL, st);
@@ -458,7 +467,9 @@ static void **DeepComputation(void **img, unsigned width, unsigned height, int n
                                                                         g_planes_out, (uint16_t *)flat_out, NULL, NULL, st)
                                : glf_multi_image_processing_u16(world, &opt, (const uint16_t *)flat, (int)width, (int)height, (uint16_t *)flat_out, NULL,
                                                                 NULL, st);
-            if (rc != GLF_OK) fprintf(stderr, "%s: %s (%s)\n", f32 ? "glf_multi_image_processing_f32" : "glf_multi_image_processing_u16", glf_strerror(rc), glf_multi_last_error(world));
+            if (rc != GLF_OK)
+                fprintf(stderr, "%s: %s (%s)\n", f32 == 2 ? "glf_multi_image_processing_rgbf32" : f32 ? "glf_multi_image_processing_f32" : "glf_multi_image_processing_u16",
+                        glf_strerror(rc), glf_multi_last_error(world));
             else {
                 print_stage_times(&st[0], opt.epsilon);
                 pix_band_report(&st[0]);
@@ -482,7 +493,11 @@ static void **DeepComputation(void **img, unsigned width, unsigned height, int n
         if (ok) {
             pix_band_set(ctx);
             int rc;
-            if (f32)
+            if (f32 == 2)
+                rc = g_nplanes ? glf_image_processing_rgbf32_signals(ctx, &opt, (const float *)d_img, (int)width, (int)height, g_nplanes,
+                                                                     (const float *)d_sig, (float *)d_sig_out, (float *)d_out, NULL, &st)
+                               : glf_image_processing_rgbf32(ctx, &opt, (const float *)d_img, (int)width, (int)height, (float *)d_out, NULL, &st);
+            else if (f32)
                 rc = g_nplanes ? glf_image_processing_f32_signals(ctx, &opt, (const float *)d_img, (int)width, (int)height, g_nplanes, (const float *)d_sig,
                                                                   (float *)d_sig_out, (float *)d_out, NULL, &st)
                                : glf_image_processing_f32(ctx, &opt, (const float *)d_img, (int)width, (int)height, (float *)d_out, NULL, &st);
@@ -766,6 +781,19 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (opt_has("-float_rgb")) {
+        const char *kv = opt_value("-kernel");
+        const char *other = opt_has("-color") ? "-color" : opt_has("-chroma") ? "-chroma" : opt_has("-rgb_graph") ? "-rgb_graph"
+                          : opt_has("-depth16") ? "-depth16" : opt_has("-float32") ? "-float32" : opt_has("-no_approx") ? "-no_approx"
+                          : opt_has("-kernel") ? "-kernel" : NULL;
+        if (other) {
+            fprintf(stderr, strcmp(other, "-kernel") == 0 ? "-float_rgb filters a float colour image with its own bilateral kernel: it cannot be combined with %s %s\n"
+                                                          : "-float_rgb filters a float colour image: it cannot be combined with %s%s\n",
+                    other, strcmp(other, "-kernel") == 0 ? (kv ? kv : "") : "");
+            FinalizeProgram();
+            return 1;
+        }
+    }
     if (opt_has("-chroma") && !opt_has("-color")) {
         fprintf(stderr, "-chroma filters the chroma planes of a colour image: it needs -color\n");
         FinalizeProgram();
@@ -777,13 +805,13 @@ int main(int argc, char **argv)
         FinalizeProgram();
         return 1;
     }
-    if (opt_has("-pix_band") && !opt_has("-depth16") && !opt_has("-float32") && !opt_has("-rgb_graph")) {
-        fprintf(stderr, "-pix_band selects the band form of the 16-bit, float and colour kernels: it needs -depth16 or -color -rgb_graph (or -float32)\n");
+    if (opt_has("-pix_band") && !opt_has("-depth16") && !opt_has("-float32") && !opt_has("-float_rgb") && !opt_has("-rgb_graph")) {
+        fprintf(stderr, "-pix_band selects the band form of the 16-bit, float and colour kernels: it needs -depth16 or -color -rgb_graph (or -float32), or -float_rgb\n");
         FinalizeProgram();
         return 1;
     }
-    if (opt_has("-planes") && !opt_has("-depth16") && !opt_has("-float32") && !(opt_has("-color") && opt_has("-rgb_graph"))) {
-        fprintf(stderr, "-planes filters extra planes through the 16-bit, the float or the colour graph: it needs -depth16 or -color -rgb_graph (or -float32)\n");
+    if (opt_has("-planes") && !opt_has("-depth16") && !opt_has("-float32") && !opt_has("-float_rgb") && !(opt_has("-color") && opt_has("-rgb_graph"))) {
+        fprintf(stderr, "-planes filters extra planes through the 16-bit, the float or the colour graph: it needs -depth16 or -color -rgb_graph (or -float32), or -float_rgb\n");
         FinalizeProgram();
         return 1;
     }
@@ -833,6 +861,27 @@ int main(int argc, char **argv)
         printf("Total computation time: %fs\n", wtime() - start_time);
         free_rows16(in32, height);
         free_rows16(out32, height);
+        FinalizeProgram();
+        return fstatus;
+    }
+    if (opt_has("-float_rgb")) { /* float colour: a "PF" PFM in, a "PF" PFM out */
+        float **in96 = NULL, **out96 = NULL;
+        if (glf_read_pfm_rgb(filename, &in96, &width, &height) != 0) {
+            fprintf(stderr, "-float_rgb needs a colour Portable Float Map (PF): could not read %s as one\n", filename);
+            FinalizeProgram();
+            return 1;
+        }
+        printf("Read image %s of size %dx%d => %d pixels (32-bit float colour)\n", filename, width, height, width * height);
+        planes_load((unsigned)width, (unsigned)height);
+        out96 = (float **)DeepComputation((void **)in96, (unsigned)width, (unsigned)height, ngpu,
+                                          nb && strcmp(nb, "loopback") == 0 ? GLF_MULTI_LOOPBACK : GLF_MULTI_RCCL, 2);
+        int fstatus = out96 ? 0 : 5;
+        if (glf_write_pfm_rgb("results/input.pfm", in96, (unsigned)width, (unsigned)height) != 0) fstatus = fstatus ? fstatus : 4;
+        if (out96 && glf_write_pfm_rgb("results/output.pfm", out96, (unsigned)width, (unsigned)height) != 0) fstatus = fstatus ? fstatus : 4;
+        if (out96 && g_nplanes && planes_write((unsigned)width, (unsigned)height, "float colour") != 0) fstatus = fstatus ? fstatus : 4;
+        printf("Total computation time: %fs\n", wtime() - start_time);
+        free_rows16(in96, height);
+        free_rows16(out96, height);
         FinalizeProgram();
         return fstatus;
     }

@@ -67,7 +67,7 @@ int glf_ctx_device_info(const glf_ctx *ctx, char *name, size_t name_len, int *nu
  *   NYS_PATH  band | rank | grid | direct     DEG_PATH  grid | direct     MV_PATH  band | rank | grid | dense
  *   ROWPASS, ROWPASS_OP  rt | v1     COLPASS  ws | v1     SWEEP_COLPASS  segments | samples
  *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, BAND_NOSKIP, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
- *   PIX_BAND  1 | 0 (default 0): the colour, 16-bit and float bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16 / _F32) take the band form of
+ *   PIX_BAND  1 | 0 (default 0): the colour, 16-bit, float and float colour bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16 / _F32 / _RGBF32) take the band form of
  *     the Nystroem stage and of the L_A operator under exactly the conditions under which the grey kernel takes it -- split-f16
  *     contraction, a tensor-grid sample set, at most 64 eigenpairs, the radius and band-row limits, NYS_PATH auto (width >= 1024)
  *     or band, MV_PATH auto (p >= 16 384) or band -- with the photometric factor generated per entry (one v_exp_f32) instead of
@@ -194,8 +194,14 @@ enum { GLF_ROWS_NA = 0, GLF_ROWS_SAMPLE_FIRST = 1, GLF_ROWS_RASTER = 2 };
 /* BILATERAL_F32: the same kernel on 32-bit float values, K = exp(-(dr^2 + dc^2) / h_loc^2) exp(-(v_i - v_j)^2 / h_val^2) with v any
  * finite float (negative and fractional included) and h_val in the image's own units. With it the stage entry points read d_img as
  * float [height][width]; an image with a NaN or an Inf is refused (GLF_ERR_INVALID). Routes and contraction as for BILATERAL_U16. */
+/* BILATERAL_RGBF32: the colour kernel on float channels, K = exp(-(dr^2 + dc^2) / h_loc^2) exp(-((dR)^2 + (dG)^2 + (dB)^2) / h_val^2)
+ * on an interleaved float [height][width][3] image of any finite values (HDR, [0, 1]-normalised RGB, Lab / YUV with negative chroma),
+ * h_val in the image's units; a grey image replicated into three channels gives the grey graph at h_val * sqrt(3). With it the stage
+ * entry points read d_img as float [height][width][3], and the sample descriptor (glf_mat.samples) carries one float4 {R, G, B, 0} per
+ * sample behind its padded records. An image with a NaN or an Inf is refused (GLF_ERR_INVALID). Routes and contraction as for
+ * BILATERAL_RGB: the entry-by-entry kernels (f32 MFMA contraction), and the band form behind PIX_BAND. */
 enum { GLF_KERNEL_BILATERAL = 0, GLF_KERNEL_PHOTOMETRIC = 1, GLF_KERNEL_SPATIAL = 2, GLF_KERNEL_NLM = 3, GLF_KERNEL_BILATERAL_RGB = 4,
-       GLF_KERNEL_BILATERAL_U16 = 5, GLF_KERNEL_BILATERAL_F32 = 6 };
+       GLF_KERNEL_BILATERAL_U16 = 5, GLF_KERNEL_BILATERAL_F32 = 6, GLF_KERNEL_BILATERAL_RGBF32 = 7 };
 
 /* Replaces PETSc Mat (MATMPIDENSE / MATMPIAIJ diagonal). */
 typedef struct glf_mat {
@@ -490,6 +496,21 @@ int glf_image_processing_f32(glf_ctx *ctx, const glf_options *opt, const float *
 int glf_image_processing_f32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, int nsig,
                                      const float *d_sig, float *d_sig_out, float *d_out, double *eigvals_out, glf_stats *stats);
 
+/* Float colour filtering: glf_image_processing_rgb on float channels (GLF_KERNEL_BILATERAL_RGBF32; opt->kernel must be
+ * GLF_KERNEL_BILATERAL or GLF_KERNEL_BILATERAL_RGBF32, both mean the float colour kernel here, any other gives GLF_ERR_UNSUPPORTED;
+ * opt->h_val is in the image's units). d_rgb / d_out_rgb: device float [height][width][3], interleaved; d_out_rgb is z = (float)(x + c)
+ * per channel with c the f64 correction: no clamp, no floor, no separate float z. The image's 3 N floats are checked first, in one
+ * pass: a NaN or an Inf anywhere gives GLF_ERR_INVALID (the message names it) and d_out_rgb is not written. Routes, tuning keys
+ * (PIX_BAND: the band form with three u32 per sample in the chunk tails), declines (the grid / rank / level-table forms, the split-f16
+ * direct kernel, the fused filter; more than 256 eigenpairs: GLF_ERR_UNSUPPORTED), stats and eigvals_out as for
+ * glf_image_processing_rgb. On integer values 0..255 the graph, the eigenvalues and z
+ * have the bits of the 8-bit colour call's (z: of its d_zf, channel by channel). The _signals call is glf_image_processing_rgb_signals
+ * under a float colour guide (the planes are not checked for NaN / Inf). */
+int glf_image_processing_rgbf32(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, float *d_out_rgb,
+                                double *eigvals_out, glf_stats *stats);
+int glf_image_processing_rgbf32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, int nsig,
+                                        const float *d_sig, float *d_sig_out, float *d_out_rgb, double *eigvals_out, glf_stats *stats);
+
 /* By-products of one glf_image_processing call, for parity checks at sizes where the CPU oracle cannot run the whole
  * path (tests/test_gpu_large.py, bench.py's parity leg): the caller checks sampled rows of Phi / z against
  * hpc/nystroem.c:41-57 and hpc/display.c:58-83 evaluated on the CPU from these. Every pointer is optional. */
@@ -520,6 +541,10 @@ int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const
 /* The same by-products of one glf_image_processing_f32 call, as for 16 bits. */
 int glf_image_processing_f32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, float *d_out,
                                      double *eigvals_out, glf_stats *stats, glf_capture *cap);
+
+/* The same by-products of one glf_image_processing_rgbf32 call (d_phi_A, d_phi and h_degree), as for 8-bit colour. */
+int glf_image_processing_rgbf32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height,
+                                        float *d_out_rgb, double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
@@ -571,6 +596,14 @@ int glf_multi_image_processing_f32(glf_multi *w, const glf_options *opt, const f
 int glf_multi_image_processing_f32_signals(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, int nsig,
                                            const float *h_sig, float *h_sig_out, float *h_out, double *eigvals_out, glf_stats *stats);
 
+/* glf_multi_image_processing for float colour (glf_image_processing_rgbf32 / _rgbf32_signals): h_rgb / h_out_rgb HOST float
+ * [height][width][3]. The NaN / Inf check runs on the host image before any rank starts: a refused image leaves the world usable. */
+int glf_multi_image_processing_rgbf32(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, float *h_out_rgb,
+                                      double *eigvals_out, glf_stats *stats);
+int glf_multi_image_processing_rgbf32_signals(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, int nsig,
+                                              const float *h_sig, float *h_sig_out, float *h_out_rgb, double *eigvals_out,
+                                              glf_stats *stats);
+
 /* EntireComputation, hpc/image_processing.c:155-181 (-no_approx): z = clamp(y - L y) with the full N x N
  * Laplacian of ComputeEntireAffinityMatrix / ComputeEntireLaplacianMatrix / ComputeResultFromEntireLaplacian
  * (hpc/affinity.c:264-336, hpc/laplacian.c:44-65, hpc/display.c:128-149). The matrices are never stored
@@ -601,6 +634,11 @@ int glf_write_png16(const char *filename, uint16_t **rows, unsigned width, unsig
  * header. The writer writes little-endian, scale -1.0. */
 int glf_read_pfm(const char *filename, float ***rows, int *width, int *height);
 int glf_write_pfm(const char *filename, float **rows, unsigned width, unsigned height);
+/* Colour Portable Float Map: the header "PF", then 3 * width * height floats, rows of 3 * width interleaved R G B, bottom row first.
+ * The reader takes both byte orders and returns malloc'd rows (3 * width floats each) top first; -1 for greyscale ("Pf"), a short file,
+ * a zero or overflowing size or a malformed header. The writer writes little-endian, scale -1.0. */
+int glf_read_pfm_rgb(const char *filename, float ***rows, int *width, int *height);
+int glf_write_pfm_rgb(const char *filename, float **rows, unsigned width, unsigned height);
 
 #ifdef __cplusplus
 }
