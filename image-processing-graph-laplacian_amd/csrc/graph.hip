@@ -1,0 +1,392 @@
+// graph.hip -- the graph handle (glf_graph_*): the eigenbasis of one image built once, then any number of projections
+// c = Phi^T s and syntheses out = ident s + Phi a on it. The build is the format's capture call with the handle's Phi as the
+// capture target; Phi^T s and Phi^T Phi are filter.hip's phi_t_signals / phi_gram; the synthesis is the one new kernel.
+#include "glf_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <new>
+
+struct glf_graph {
+    glf_ctx *ctx = nullptr;
+    int pix = 0, width = 0, height = 0;
+    unsigned p = 0, m = 0, ld = 0;
+    float *phi = nullptr;      // device [N][ld], raster rows (glf_malloc: not a block of the workspace pool)
+    std::vector<double> lam;   // [m]
+    std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
+    int synth_blocks_per_cu = 0; // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
+};
+
+namespace glf {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// the per-call operand block of k_graph_synthesize (device): the coefficients as the MFMA's A operand, then the identity terms
+//   [LD][32] float  (float)a_j[k] at [k][j], zero for j >= nout and k >= m
+//   [32] float      ident[j]
+//   [32] int        plane[j] (-1: no identity term)
+constexpr int GS_OUT = GLF_GRAPH_MAX_OUTPUTS;
+inline size_t gs_operand_floats(unsigned ld) { return (size_t)ld * GS_OUT + 2 * GS_OUT; }
+
+// Out[j][px] = ident[j] s_plane[j][px] + sum_k Phi[px][k] a_j[k] for all outputs j < nout in one pass over Phi.
+// One wave per tile of 32 pixels, v_mfma_f32_32x32x2_f32 with the outputs as the M index (A: the coefficients, read from LDS)
+// and the pixels as the N index (B: Phi), so that register g of the accumulator holds, in the 32 lanes of half h, 32 consecutive
+// pixels of output (g & 3) + 8 (g >> 2) + 4 h. The tile's rows are loaded as whole 16-byte pieces in address order (each row's
+// CW * 4 bytes contiguous), written to the wave's own LDS image with the row pitch padded by 4 floats, and read back one pixel
+// per lane as float4s (pitch CW + 4: the 16 lanes of a ds_read_b128 group hit 64 different banks). The contraction index is
+// visited in a fixed order that does not depend on nout -- chunk by chunk of CW columns, half-wave h taking columns
+// h CW / 2 + t of the chunk at step t -- and every output is its own k-ordered fma chain: its bits do not depend on the
+// outputs beside it. Rows past N are staged as zeros and neither read nor stored.
+template <int LD>
+__global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restrict__ phi, int64_t N, int nout, const float *__restrict__ operand,
+                                                           const float *__restrict__ planes, float *__restrict__ out)
+{
+    constexpr int CW = LD < 64 ? LD : 64; // columns staged per pass
+    constexpr int PITCH = CW + 4;
+    constexpr int FPR = CW / 4;           // float4 pieces per staged row
+    constexpr int NLOAD = CW / 8;         // pieces per lane: 32 rows x FPR / 64 lanes
+    __shared__ __attribute__((aligned(16))) float a_sh[LD * GS_OUT];
+    __shared__ __attribute__((aligned(16))) float tile_sh[4][32 * PITCH];
+    __shared__ float ident_sh[GS_OUT];
+    __shared__ int plane_sh[GS_OUT];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int e = threadIdx.x; e < LD * GS_OUT; e += 256) a_sh[e] = operand[e];
+    if (threadIdx.x < GS_OUT) {
+        ident_sh[threadIdx.x] = operand[LD * GS_OUT + threadIdx.x];
+        plane_sh[threadIdx.x] = reinterpret_cast<const int *>(operand + LD * GS_OUT + GS_OUT)[threadIdx.x];
+    }
+    __syncthreads();
+    const int r = lane & 31, h = lane >> 5;
+    float *tw = tile_sh[wave];
+    const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
+    // the pieces this lane stages of chunk ch of a tile: rows past N as zeros
+    float4 v[NLOAD];
+    auto load_chunk = [&](int64_t tile, int ch) {
+        const int64_t base = tile * 32;
+#pragma unroll
+        for (int q = 0; q < NLOAD; ++q) {
+            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + ch * CW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+    if (tile < ntiles) load_chunk(tile, 0);
+    for (; tile < ntiles; tile += tstride) {
+        f32x16 acc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+#pragma unroll 1
+        for (int ch = 0; ch < LD / CW; ++ch) {
+            __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
+#pragma unroll
+            for (int q = 0; q < NLOAD; ++q) {
+                const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+                *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
+            }
+            __builtin_amdgcn_wave_barrier();
+            // the next chunk's loads fly under this chunk's MFMAs
+            if (ch + 1 < LD / CW) load_chunk(tile, ch + 1);
+            else if (tile + tstride < ntiles) load_chunk(tile + tstride, 0);
+#pragma unroll
+            for (int u = 0; u < CW / 8; ++u) {
+                const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
+                const float *ak = a_sh + (size_t)(ch * CW + h * (CW / 2) + 4 * u) * GS_OUT + r;
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GS_OUT], b.x, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GS_OUT], b.y, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GS_OUT], b.z, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GS_OUT], b.w, acc, 0, 0, 0);
+            }
+        }
+        const int64_t px = tile * 32 + r;
+        if (px < N) {
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
+                if (j < nout) {
+                    float z = acc[g];
+                    const int pl = plane_sh[j];
+                    if (pl >= 0) z = fmaf(ident_sh[j], planes[(size_t)pl * N + px], z);
+                    out[(size_t)j * N + px] = z;
+                }
+            }
+        }
+    }
+}
+
+template <int LD>
+static int launch_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, int nout, const float *d_operand, const float *d_planes,
+                             float *d_out)
+{
+    if (*per_cu <= 0) {
+        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_graph_synthesize<LD>, 256, 0));
+        *per_cu = std::max(1, *per_cu);
+    }
+    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
+    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident); // (the rest of the tiles by the grid stride)
+    hipLaunchKernelGGL(k_graph_synthesize<LD>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, nout, d_operand, d_planes, d_out);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+static int graph_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, int nout, const float *d_operand,
+                            const float *d_planes, float *d_out)
+{
+    switch (ld) {
+    case 32: return launch_synthesize<32>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
+    case 64: return launch_synthesize<64>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
+    case 128: return launch_synthesize<128>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
+    case 256: return launch_synthesize<256>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
+    }
+    return set_error(ctx, GLF_ERR_INVALID, "graph_synthesize: ld=%u", ld);
+}
+
+} // namespace glf
+
+using namespace glf;
+
+extern "C" {
+
+int glf_graph_destroy(glf_graph *g)
+{
+    if (!g) return GLF_OK;
+    int rc = GLF_OK;
+    if (g->phi) rc = glf_free(g->ctx, g->phi);
+    delete g;
+    return rc;
+}
+
+int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void *d_img, int width, int height, glf_graph **graph,
+                    glf_stats *stats)
+{
+    if (graph) *graph = nullptr;
+    if (!ctx || !graph || !d_img || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    if (pix < GLF_PIX_U8 || pix > GLF_PIX_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: pixel format %d", pix);
+    glf_options opt;
+    glf_options_default(&opt);
+    if (opt_in) {
+        if (opt_in->struct_size != sizeof(glf_options))
+            return set_error(ctx, GLF_ERR_INVALID, "glf_options.struct_size %u != %zu", opt_in->struct_size, sizeof(glf_options));
+        opt = *opt_in;
+    }
+    if (ctx->has_comm || ctx->native)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: the context carries a communicator (row-sharded graph handles are not supported)");
+    const int64_t N = (int64_t)width * height;
+    if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
+    // the sample count and the eigenpairs the capture call will realise: they size Phi. This restates image_processing_run's rules
+    // (pipeline.hip, "p = width*height*0.01 ..." and "GetNumberEigenvalues": keep the two in step); the call's own answer is checked
+    // against it below (S.m, cap.ld), and capture's phi_floats guard refuses a Phi that would not fit
+    unsigned p = opt.num_samples ? opt.num_samples : (unsigned)((double)N * opt.sample_frac);
+    {
+        unsigned *h_idx = nullptr;
+        const int rc = opt.sampling == GLF_SAMPLING_RANDOM ? glf_RandomSampling(width, height, &p, &h_idx, opt.sampling_seed)
+                                                           : glf_Sampling(width, height, &p, &h_idx);
+        std::free(h_idx);
+        if (rc != GLF_OK || p < 2) return set_error(ctx, GLF_ERR_INVALID, "sampling failed (requested %u samples on %dx%d)", p, width, height);
+    }
+    unsigned m = opt.num_eigvals;
+    if (m == 0 || m >= p) m = p - 1;
+    if (m > PANEL_COLS)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: a graph handle takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
+    const unsigned ld = ld_for(m);
+    const PixGen gen = pix == GLF_PIX_RGB8 ? PixGen::Rgb : pix == GLF_PIX_U16 ? PixGen::U16 : pix == GLF_PIX_F32 ? PixGen::F32
+                       : pix == GLF_PIX_RGBF32 ? PixGen::RgbF32 : PixGen::Grey;
+    glf_graph *g = new (std::nothrow) glf_graph;
+    if (!g) return set_error(ctx, GLF_ERR_NOMEM, "glf_graph_build: host allocation");
+    g->ctx = ctx;
+    g->pix = pix;
+    g->width = width;
+    g->height = height;
+    g->lam.assign(m, 0.0);
+    glf_stats S{};
+    int rc;
+    {
+        void *d = nullptr;
+        rc = glf_malloc(ctx, &d, sizeof(float) * (size_t)N * ld);
+        g->phi = static_cast<float *>(d);
+    }
+    if (rc == GLF_OK) {
+        DevBuf<uint8_t> img_out; // the call's filtered image: not kept
+        rc = img_out.alloc(ctx, (size_t)N * pix_bytes(gen));
+        glf_capture cap{};
+        cap.struct_size = sizeof(glf_capture);
+        cap.d_phi = g->phi;
+        cap.phi_floats = (size_t)N * ld;
+        if (rc == GLF_OK) switch (gen) {
+            case PixGen::Grey:
+                rc = glf_image_processing_capture(ctx, &opt, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap);
+                break;
+            case PixGen::Rgb:
+                rc = glf_image_processing_rgb_capture(ctx, &opt, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap);
+                break;
+            case PixGen::U16:
+                rc = glf_image_processing_u16_capture(ctx, &opt, static_cast<const uint16_t *>(d_img), width, height,
+                                                      reinterpret_cast<uint16_t *>(img_out.p), nullptr, g->lam.data(), &S, &cap);
+                break;
+            case PixGen::F32:
+                rc = glf_image_processing_f32_capture(ctx, &opt, static_cast<const float *>(d_img), width, height, reinterpret_cast<float *>(img_out.p),
+                                                      g->lam.data(), &S, &cap);
+                break;
+            case PixGen::RgbF32:
+                rc = glf_image_processing_rgbf32_capture(ctx, &opt, static_cast<const float *>(d_img), width, height,
+                                                         reinterpret_cast<float *>(img_out.p), g->lam.data(), &S, &cap);
+                break;
+            }
+        if (rc == GLF_OK && (S.m != m || cap.ld != ld))
+            rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised m=%u ld=%u, %u / %u expected", S.m, cap.ld, m, ld);
+        if (rc == GLF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GLF_ERR_HIP, "glf_graph_build: synchronize");
+    }
+    if (rc != GLF_OK) {
+        if (g->phi) (void)hipFree(g->phi); // (not glf_free: the failing call's message stays in last_error)
+        delete g;
+        return rc;
+    }
+    g->p = S.p;
+    g->m = m;
+    g->ld = ld;
+    if (stats) *stats = S;
+    *graph = g;
+    return GLF_OK;
+}
+
+int glf_graph_get_info(const glf_graph *g, glf_graph_info *info)
+{
+    if (!g || !info || info->struct_size != sizeof(glf_graph_info)) return GLF_ERR_INVALID;
+    info->pix = g->pix;
+    info->width = g->width;
+    info->height = g->height;
+    info->p = g->p;
+    info->m = g->m;
+    info->ld = g->ld;
+    info->d_phi = g->phi;
+    info->phi_bytes = sizeof(float) * (size_t)g->width * g->height * g->ld;
+    return GLF_OK;
+}
+
+int glf_graph_eigenvalues(const glf_graph *g, double *lam)
+{
+    if (!g || !lam) return GLF_ERR_INVALID;
+    std::memcpy(lam, g->lam.data(), sizeof(double) * g->m);
+    return GLF_OK;
+}
+
+int glf_graph_gram(glf_graph *g, double *G)
+{
+    if (!g || !G) return GLF_ERR_INVALID;
+    const unsigned m = g->m, ld = g->ld;
+    if (g->gram.empty()) {
+        glf_ctx *ctx = g->ctx;
+        GLF_ENTER(ctx);
+        DevBuf<double> dG;
+        GLF_TRY(dG.alloc(ctx, (size_t)ld * ld));
+        GLF_TRY(phi_gram(ctx, g->phi, 0, (int64_t)g->width * g->height, ld, dG.p));
+        std::vector<double> hG((size_t)ld * ld);
+        GLF_HIP(ctx, hipMemcpyAsync(hG.data(), dG.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, ctx->stream));
+        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        g->gram.resize((size_t)m * m);
+        for (unsigned i = 0; i < m; ++i)
+            for (unsigned j = 0; j < m; ++j) g->gram[(size_t)i * m + j] = hG[(size_t)i * ld + j];
+    }
+    std::memcpy(G, g->gram.data(), sizeof(double) * m * m);
+    return GLF_OK;
+}
+
+int glf_graph_project(glf_graph *g, int nplanes, const float *d_planes, double *h_c)
+{
+    if (!g || nplanes < 1 || nplanes > GLF_MAX_SIGNALS || !d_planes || !h_c) return GLF_ERR_INVALID;
+    glf_ctx *ctx = g->ctx;
+    const unsigned m = g->m, ld = g->ld;
+    const int64_t N = (int64_t)g->width * g->height;
+    GLF_ENTER(ctx);
+    DevBuf<double> c;
+    GLF_TRY(c.alloc(ctx, (size_t)nplanes * ld));
+    GLF_TRY(phi_t_signals(ctx, g->phi, d_planes, N, nplanes, 0, N, ld, c.p));
+    std::vector<double> hc((size_t)nplanes * ld);
+    GLF_HIP(ctx, hipMemcpyAsync(hc.data(), c.p, sizeof(double) * nplanes * ld, hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < nplanes; ++k)
+        for (unsigned j = 0; j < m; ++j) h_c[(size_t)k * m + j] = hc[(size_t)k * ld + j];
+    return GLF_OK;
+}
+
+int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float *ident, const int *plane, int nplanes, const float *d_planes,
+                         float *d_out)
+{
+    if (!g || nout < 1 || nout > GLF_GRAPH_MAX_OUTPUTS || !h_a || !plane || !d_out || nplanes < 0) return GLF_ERR_INVALID;
+    bool any_plane = false;
+    for (int j = 0; j < nout; ++j) {
+        if (plane[j] < -1 || plane[j] >= nplanes) return GLF_ERR_INVALID;
+        any_plane = any_plane || plane[j] >= 0;
+    }
+    if (any_plane && (!ident || !d_planes)) return GLF_ERR_INVALID;
+    glf_ctx *ctx = g->ctx;
+    const unsigned m = g->m, ld = g->ld;
+    const int64_t N = (int64_t)g->width * g->height;
+    GLF_ENTER(ctx);
+    std::vector<float> h_op(gs_operand_floats(ld), 0.f);
+    int h_plane[GS_OUT];
+    for (int j = 0; j < GS_OUT; ++j) h_plane[j] = -1;
+    for (int j = 0; j < nout; ++j) {
+        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GS_OUT + j] = (float)h_a[(size_t)j * m + k];
+        if (plane[j] >= 0) {
+            h_op[(size_t)ld * GS_OUT + j] = ident[j];
+            h_plane[j] = plane[j];
+        }
+    }
+    std::memcpy(h_op.data() + (size_t)ld * GS_OUT + GS_OUT, h_plane, sizeof(h_plane));
+    DevBuf<float> op;
+    GLF_TRY(op.alloc(ctx, h_op.size()));
+    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    GLF_TRY(graph_synthesize(ctx, &g->synth_blocks_per_cu, g->phi, N, ld, nout, op.p, d_planes, d_out));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)
+    return GLF_OK;
+}
+
+int glf_filter_coeffs(const glf_options *opt_in, unsigned m, const double *lam, const double *gram, const double *c, double *a, float *ident)
+{
+    if (!lam || !c || !a || !ident) return GLF_ERR_INVALID;
+    glf_options opt;
+    glf_options_default(&opt);
+    if (opt_in) {
+        if (opt_in->struct_size != sizeof(glf_options)) return GLF_ERR_INVALID;
+        opt = *opt_in;
+    }
+    switch (opt.filter_mode) {
+    case GLF_FILTER_REFERENCE: {
+        const double gain = (double)opt.gain, k = (double)(opt.filter_pow > 0 ? opt.filter_pow : 1);
+        for (unsigned j = 0; j < m; ++j) a[j] = gain * std::pow(lam[j], k) * c[j];
+        *ident = 1.f;
+        return GLF_OK;
+    }
+    case GLF_FILTER_POC:
+        for (unsigned j = 0; j < m; ++j) a[j] = -(lam[j] + 5.0) * c[j];
+        *ident = 1.f;
+        return GLF_OK;
+    case GLF_FILTER_SMOOTH:
+        for (unsigned j = 0; j < m; ++j) a[j] = (1.0 - lam[j]) * c[j];
+        *ident = 0.f;
+        return GLF_OK;
+    case GLF_FILTER_SHARPEN: {
+        if (!gram) return GLF_ERR_INVALID;
+        // (1 + beta) L G L c - beta L G L G L c, factor by factor as the whole path forms it
+        const double beta = (double)opt.filter_beta;
+        std::vector<double> t(m), u(m), v(m);
+        auto LG = [&](const std::vector<double> &x, std::vector<double> &y) {
+            for (unsigned i = 0; i < m; ++i) {
+                double s = 0.0;
+                for (unsigned j = 0; j < m; ++j) s += gram[(size_t)i * m + j] * x[j];
+                y[i] = (1.0 - lam[i]) * s;
+            }
+        };
+        for (unsigned j = 0; j < m; ++j) t[j] = (1.0 - lam[j]) * c[j];
+        LG(t, u);
+        LG(u, v);
+        for (unsigned j = 0; j < m; ++j) a[j] = (1.0 + beta) * u[j] - beta * v[j];
+        *ident = 0.f;
+        return GLF_OK;
+    }
+    }
+    return GLF_ERR_INVALID;
+}
+
+} // extern "C"

@@ -61,8 +61,12 @@ EXPORTS = [
     "glf_multi_image_processing_f32", "glf_multi_image_processing_f32_signals", "glf_read_pfm", "glf_write_pfm",
     "glf_image_processing_rgbf32", "glf_image_processing_rgbf32_capture", "glf_image_processing_rgbf32_signals",
     "glf_multi_image_processing_rgbf32", "glf_multi_image_processing_rgbf32_signals", "glf_read_pfm_rgb", "glf_write_pfm_rgb",
+    "glf_graph_build", "glf_graph_destroy", "glf_graph_get_info", "glf_graph_eigenvalues", "glf_graph_gram", "glf_graph_project",
+    "glf_graph_synthesize", "glf_filter_coeffs",
 ]
 MAX_SIGNALS = 4
+PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
+GRAPH_MAX_OUTPUTS = 32
 
 
 class Mat(C.Structure):
@@ -114,6 +118,11 @@ class Capture(C.Structure):
                 ("d_corr", C.c_void_p), ("corr_floats", C.c_size_t)]
 
 
+class GraphInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pix", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("p", C.c_uint32),
+                ("m", C.c_uint32), ("ld", C.c_uint32), ("d_phi", C.c_void_p), ("phi_bytes", C.c_size_t)]
+
+
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHER_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -134,6 +143,14 @@ _lib.glf_multi_last_error.argtypes = [C.c_void_p]
 _lib.glf_options_default.restype = None
 _lib.glf_ctx_cached_bytes.restype = C.c_size_t
 _lib.glf_ctx_cached_bytes.argtypes = [C.c_void_p]
+_lib.glf_graph_build.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+_lib.glf_graph_destroy.argtypes = [C.c_void_p]
+_lib.glf_graph_get_info.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_eigenvalues.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_gram.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_project.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+_lib.glf_graph_synthesize.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+_lib.glf_filter_coeffs.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -315,6 +332,27 @@ def write_pfm_rgb(path, img):
     rc = _lib.glf_write_pfm_rgb(path.encode(), rowptr, C.c_uint(w), C.c_uint(h))
     if rc != 0:
         raise GlfError(ERR_IO, path)
+
+
+def filter_coeffs(opt, lam, c, gram=None):
+    """glf_filter_coeffs (host only): (a, ident) such that ident * s + Phi a is the library's own filter of opt.filter_mode on a plane
+    whose projection is c. lam [m], c [m] or [k, m] (one row per plane: a comes back in c's shape); gram [m, m] for sharpening."""
+    opt = opt or default_options()
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    c2 = np.ascontiguousarray(np.atleast_2d(np.asarray(c, dtype=np.float64)))
+    if lam.ndim != 1 or c2.shape[1] != lam.size:
+        raise ValueError("filter_coeffs: lam %s, c %s" % (lam.shape, np.shape(c)))
+    if gram is not None:
+        gram = np.ascontiguousarray(gram, dtype=np.float64)
+        if gram.shape != (lam.size, lam.size):
+            raise ValueError("filter_coeffs: gram must be [%d, %d]" % (lam.size, lam.size))
+    a = np.zeros_like(c2)
+    ident = C.c_float()
+    for k in range(c2.shape[0]):
+        rc = _lib.glf_filter_coeffs(C.byref(opt), C.c_uint(lam.size), _ptr(lam), _ptr(gram), _ptr(c2[k]), _ptr(a[k]), C.byref(ident))
+        if rc != OK:
+            raise GlfError(rc, "glf_filter_coeffs(filter_mode=%d)" % opt.filter_mode)
+    return a.reshape(np.shape(c)), float(ident.value)
 
 
 def shard_rows(height, rank, size):
@@ -1093,6 +1131,25 @@ class Context:
             sig_out = torch.zeros(tuple(signals.shape), dtype=torch.float32, device=self.device)
         return sig_out, (C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()), C.c_void_p(sig_out.data_ptr()))
 
+    def graph(self, d_img, opt=None):
+        """glf_graph_build: the graph handle of a device image -- uint8 [H, W], uint8 [H, W, 3], uint16 [H, W], float32 [H, W] or
+        float32 [H, W, 3] -- as a Graph: the eigenbasis is built once (the format's capture call), then Graph.project /
+        Graph.synthesize / Graph.apply run any number of spectral responses on any planes in two passes over Phi each."""
+        torch = self.torch
+        assert d_img.is_cuda and d_img.is_contiguous()
+        key = (d_img.dtype, d_img.dim(), d_img.shape[2] if d_img.dim() == 3 else 1)
+        pix = {(torch.uint8, 2, 1): PIX_U8, (torch.uint8, 3, 3): PIX_RGB8, (torch.uint16, 2, 1): PIX_U16,
+               (torch.float32, 2, 1): PIX_F32, (torch.float32, 3, 3): PIX_RGBF32}.get(key)
+        if pix is None:
+            raise ValueError("graph: no pixel format for dtype %s, shape %s" % (d_img.dtype, tuple(d_img.shape)))
+        h, w = d_img.shape[:2]
+        opt = opt or default_options()
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
+        handle, st = C.c_void_p(), Stats()
+        self._check(_lib.glf_graph_build(self._ctx, C.byref(opt), C.c_int(pix), C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h),
+                                         C.byref(handle), C.byref(st)), "graph")
+        return Graph(self, handle, st)
+
     def _capture_buffers(self, w, h, opt, p_real, grey=False):
         """glf_capture with phi_A, phi (this rank's rows) and the degree vector -- grey: also c = Phi^T y and the correction -- and
         the buffers it points to. The realised sample count and the row stride are known before the call."""
@@ -1118,6 +1175,102 @@ class Context:
                       c_host.ctypes.data if grey else None, deg_host.ctypes.data, corr.data_ptr() if grey else None,
                       corr.numel() if grey else 0)
         return cap, (phi_A, phi, deg_host, c_host, corr)
+
+
+class Graph:
+    """One glf_graph: Phi [N, ld] and the eigenvalues of one image, kept on the device until close(). It belongs to its Context and
+    must be closed before it. Outputs are float planes, not clamped."""
+
+    def __init__(self, ctx, handle, st):
+        self.ctx, self._g = ctx, handle
+        gi = GraphInfo(struct_size=C.sizeof(GraphInfo))
+        ctx._check(_lib.glf_graph_get_info(handle, C.byref(gi)), "graph info")
+        self.info = dict(pix=gi.pix, width=gi.width, height=gi.height, p=gi.p, m=gi.m, ld=gi.ld, phi_bytes=int(gi.phi_bytes))
+        lam = np.zeros(gi.m, dtype=np.float64)
+        ctx._check(_lib.glf_graph_eigenvalues(handle, _ptr(lam)), "graph eigenvalues")
+        self.eigenvalues = lam
+        self.stats = _info(st, lam)
+        n = gi.width * gi.height
+        self.phi = device_tensor_from_ptr(gi.d_phi, n * gi.ld, torch.float32, ctx.device).view(n, gi.ld)   # a view: dies with the handle
+
+    def close(self):
+        if self._g:
+            self.phi = None
+            handle, self._g = self._g, C.c_void_p()
+            self.ctx._check(_lib.glf_graph_destroy(handle), "graph destroy")
+
+    def __del__(self):
+        # a Graph dropped without close() gives its Phi back, as long as its context is still alive (a graph is destroyed before it)
+        if getattr(self, "_g", None) and self.ctx._ctx:
+            _lib.glf_graph_destroy(self._g)
+            self._g = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def gram(self):
+        """Phi^T Phi as a numpy array [m, m] (glf_graph_gram: computed on first use, cached in the handle)."""
+        m = self.info["m"]
+        G = np.zeros((m, m), dtype=np.float64)
+        self.ctx._check(_lib.glf_graph_gram(self._g, _ptr(G)), "graph gram")
+        return G
+
+    def _planes(self, planes):
+        t = self.ctx.torch
+        h, w = self.info["height"], self.info["width"]
+        assert planes.dtype == t.float32 and planes.is_cuda and planes.dim() == 3 and planes.is_contiguous()
+        if tuple(planes.shape[1:]) != (h, w):
+            raise ValueError("planes must be [nplanes, %d, %d], got %s" % (h, w, tuple(planes.shape)))
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the planes are complete before the library reads them
+        return planes
+
+    def project(self, planes):
+        """c_k = Phi^T s_k in f64 (glf_graph_project): planes device float32 [nplanes, H, W], 1 <= nplanes <= 4 -> numpy [nplanes, m]."""
+        planes = self._planes(planes)
+        c = np.zeros((planes.shape[0], self.info["m"]), dtype=np.float64)
+        self.ctx._check(_lib.glf_graph_project(self._g, C.c_int(planes.shape[0]), C.c_void_p(planes.data_ptr()), _ptr(c)), "graph project")
+        return c
+
+    def synthesize(self, coeffs, ident=None, plane=None, planes=None):
+        """out_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (glf_graph_synthesize), one pass over Phi for all outputs: coeffs
+        [nout, m] (nout <= 32), ident [nout] floats, plane [nout] ints in [-1, nplanes) (-1 / None: no identity term), planes device
+        float32 [nplanes, H, W] or None -> device float32 [nout, H, W]."""
+        t = self.ctx.torch
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        nout, h, w = a.shape[0], self.info["height"], self.info["width"]
+        if a.shape[1] != self.info["m"]:
+            raise ValueError("coeffs must be [nout, %d], got %s" % (self.info["m"], a.shape))
+        pl = np.full(nout, -1, dtype=np.int32) if plane is None else np.ascontiguousarray(plane, dtype=np.int32)
+        idn = np.zeros(nout, dtype=np.float32) if ident is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ident, dtype=np.float32), (nout,)))
+        if pl.shape != (nout,):
+            raise ValueError("plane must be [%d]" % nout)
+        nplanes = 0
+        if planes is not None:
+            planes = self._planes(planes)
+            nplanes = planes.shape[0]
+        with t.cuda.stream(self.ctx.stream):
+            out = t.empty((nout, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        self.ctx._check(_lib.glf_graph_synthesize(self._g, C.c_int(nout), _ptr(a), _ptr(idn), _ptr(pl), C.c_int(nplanes),
+                                                  C.c_void_p(planes.data_ptr()) if planes is not None else None,
+                                                  C.c_void_p(out.data_ptr())), "graph synthesize")   # (returns with the stream drained)
+        return out
+
+    def apply(self, planes, weights, ident=1.0):
+        """Diagonal responses: out[r, k] = ident[r] * s_k + Phi diag(weights[r]) Phi^T s_k for every response r and plane k -- one
+        project, the scaling on the host, one synthesize of nresp * nplanes <= 32 outputs. weights [nresp, m] (e.g. gain * lam for
+        the reference filter, 1 - lam for smoothing, any band-pass), ident a float or [nresp] -> device float32 [nresp, nplanes, H, W]."""
+        wts = np.atleast_2d(np.asarray(weights, dtype=np.float64))
+        nresp, nplanes = wts.shape[0], planes.shape[0]
+        if nresp * nplanes > GRAPH_MAX_OUTPUTS:
+            raise ValueError("apply: %d responses x %d planes exceed %d outputs" % (nresp, nplanes, GRAPH_MAX_OUTPUTS))
+        c = self.project(planes)
+        a = (wts[:, None, :] * c[None, :, :]).reshape(nresp * nplanes, -1)
+        idn = np.repeat(np.broadcast_to(np.asarray(ident, dtype=np.float32), (nresp,)), nplanes)
+        out = self.synthesize(a, idn, np.tile(np.arange(nplanes, dtype=np.int32), nresp), planes)
+        return out.view(nresp, nplanes, self.info["height"], self.info["width"])
 
 
 @functools.lru_cache(maxsize=256)

@@ -546,6 +546,53 @@ int glf_image_processing_f32_capture(glf_ctx *ctx, const glf_options *opt, const
 int glf_image_processing_rgbf32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height,
                                         float *d_out_rgb, double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
+/* ---- graph handle: build the eigenbasis once, project and synthesize many ------------------------------------------------------
+ * Every entry point above builds the graph, solves for the eigenpairs, extends them to every pixel, applies one spectral response
+ * and discards everything. The operator is z = ident s + Phi diag(g(mu)) Phi^T s: once Phi exists, any response on any plane is
+ * two passes over Phi. A glf_graph keeps Phi (device float [N][ld], raster rows) and the eigenvalues of one image; glf_graph_project
+ * forms c = Phi^T s, the caller turns c into coefficients a on the host (glf_filter_coeffs for the library's own four filters, or
+ * any response of its own: a band-pass, per-band gains, ...), and glf_graph_synthesize forms ident s + Phi a for up to
+ * GLF_GRAPH_MAX_OUTPUTS outputs in one pass over Phi. No reference counterpart (hpc/image_processing.c runs its stages once).
+ * Out of scope: contexts that carry a communicator and glf_multi_* (a row-sharded handle: GLF_ERR_UNSUPPORTED); more than 256
+ * eigenpairs (GLF_ERR_UNSUPPORTED, the capture calls' own limit); integer or clamped outputs (the outputs are float planes, the
+ * caller clamps); a flag of the image_processing host program (it keeps the reference's one-image-in, one-image-out command
+ * line); the band-form Nystroem kernel, which is untouched. A graph belongs to its context and is destroyed before it. */
+typedef struct glf_graph glf_graph; /* opaque; owns Phi and the eigenvalues */
+enum { GLF_PIX_U8 = 0, GLF_PIX_RGB8 = 1, GLF_PIX_U16 = 2, GLF_PIX_F32 = 3, GLF_PIX_RGBF32 = 4 };
+#define GLF_GRAPH_MAX_OUTPUTS 32
+/* Runs the glf_image_processing*_capture entry point of the pixel format `pix` (d_img in that format, as that entry point takes
+ * it) with the handle's Phi as the capture target, allocated as by glf_malloc (not a block of the workspace pool): the graph, the
+ * eigenvalues and Phi are bit for bit what that call gives with the same options on the same context, with its routes (PIX_BAND,
+ * NYS_PATH, ...), its declines and its refusal of NaN / Inf. opt's filter_mode, gain, filter_pow and filter_beta do not enter the
+ * graph. stats: that call's. On any failure *graph is NULL and nothing stays allocated. */
+int glf_graph_build(glf_ctx *ctx, const glf_options *opt, int pix, const void *d_img, int width, int height, glf_graph **graph,
+                    glf_stats *stats);
+int glf_graph_destroy(glf_graph *g); /* NULL: GLF_OK */
+typedef struct glf_graph_info {
+    uint32_t struct_size;   /* sizeof(glf_graph_info), set by the caller */
+    int32_t pix, width, height;
+    uint32_t p, m, ld;      /* samples, eigenpairs, row stride of Phi (m rounded up to 32, 64, 128 or 256; columns >= m are zero) */
+    const float *d_phi;     /* device [width * height][ld], owned by the handle */
+    size_t phi_bytes;
+} glf_graph_info;
+int glf_graph_get_info(const glf_graph *g, glf_graph_info *info);
+int glf_graph_eigenvalues(const glf_graph *g, double *lam /* HOST [m] */);
+/* G = Phi^T Phi (the extended eigenvectors are not orthonormal: the sharpening filter needs it); computed on first use, cached */
+int glf_graph_gram(glf_graph *g, double *G /* HOST [m][m] */);
+/* c_k = Phi^T s_k with f64 sums: one pass over Phi for all planes. 1 <= nplanes <= GLF_MAX_SIGNALS */
+int glf_graph_project(glf_graph *g, int nplanes, const float *d_planes /* device [nplanes][N] */, double *h_c /* HOST [nplanes][m] */);
+/* out_j = ident[j] * s_{plane[j]} + Phi a_j: one pass over Phi for all outputs (v_mfma_f32_32x32x2_f32: operands (float)a and Phi
+ * exactly f32, f32 accumulation in a fixed order; an output's bits do not depend on the outputs beside it). 1 <= nout <=
+ * GLF_GRAPH_MAX_OUTPUTS; plane[j] in [0, nplanes) or -1 (no identity term; ident[j] ignored); nplanes may be 0, and ident and
+ * d_planes NULL, when every plane[j] is -1. Not clamped. */
+int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a /* HOST [nout][m] */, const float *ident, const int *plane,
+                         int nplanes, const float *d_planes /* device [nplanes][N] */, float *d_out /* device [nout][N] */);
+/* Host only: coefficients a and identity term such that ident * s + Phi a is the library's own filter of opt->filter_mode (opt NULL:
+ * the defaults) on a plane whose projection is c. reference: a = gain lam^filter_pow c, ident 1; PoC: a = -(lam + 5) c, ident 1;
+ * smooth: a = (1 - lam) c, ident 0; sharpen: a = (1 + beta) L G L c - beta L G L G L c, L = diag(1 - lam), G = gram [m][m], ident 0
+ * (gram NULL: GLF_ERR_INVALID). */
+int glf_filter_coeffs(const glf_options *opt, unsigned m, const double *lam, const double *gram, const double *c, double *a, float *ident);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
