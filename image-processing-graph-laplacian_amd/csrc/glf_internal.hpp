@@ -697,4 +697,9 @@ int filter_accumulate(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pi
 int filter_finish(glf_ctx *ctx, const uint8_t *d_img, const float *d_acc, int64_t pix0, int64_t pix1, float gain, float ysub,
                   uint8_t *d_out, float *d_zf);
 
+// graph_fit.hip: h_G [m][m] = Phi^T diag(w) Phi (exactly symmetric) and h_b [nplanes][m] = Phi^T diag(w) s_k of Phi [N][ld] in one pass
+// (d_w NULL: w = 1; nplanes 0: no planes); returns with the stream drained
+int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
+                           const float *d_planes, double *h_G, double *h_b);
+
 } // namespace glf

@@ -342,6 +342,14 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float 
     return GLF_OK;
 }
 
+int glf_graph_normal_equations(glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_G, double *h_b)
+{
+    if (!g || !h_G || nplanes < 0 || nplanes > GLF_MAX_SIGNALS || (nplanes > 0 && (!d_planes || !h_b))) return GLF_ERR_INVALID;
+    glf_ctx *ctx = g->ctx;
+    GLF_ENTER(ctx);
+    return graph_normal_equations(ctx, g->phi, (int64_t)g->width * g->height, g->m, g->ld, d_w, nplanes, d_planes, h_G, h_b);
+}
+
 int glf_filter_coeffs(const glf_options *opt_in, unsigned m, const double *lam, const double *gram, const double *c, double *a, float *ident)
 {
     if (!lam || !c || !a || !ident) return GLF_ERR_INVALID;

@@ -62,11 +62,12 @@ EXPORTS = [
     "glf_image_processing_rgbf32", "glf_image_processing_rgbf32_capture", "glf_image_processing_rgbf32_signals",
     "glf_multi_image_processing_rgbf32", "glf_multi_image_processing_rgbf32_signals", "glf_read_pfm_rgb", "glf_write_pfm_rgb",
     "glf_graph_build", "glf_graph_destroy", "glf_graph_get_info", "glf_graph_eigenvalues", "glf_graph_gram", "glf_graph_project",
-    "glf_graph_synthesize", "glf_filter_coeffs",
+    "glf_graph_synthesize", "glf_filter_coeffs", "glf_graph_normal_equations", "glf_fit_coeffs",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
 GRAPH_MAX_OUTPUTS = 32
+GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 
 
 class Mat(C.Structure):
@@ -353,6 +354,28 @@ def filter_coeffs(opt, lam, c, gram=None):
         if rc != OK:
             raise GlfError(rc, "glf_filter_coeffs(filter_mode=%d)" % opt.filter_mode)
     return a.reshape(np.shape(c)), float(ident.value)
+
+
+def fit_coeffs(G, b, penalty=None):
+    """glf_fit_coeffs (host only): a_k = (G + diag(penalty))^-1 b_k by an f64 Cholesky factorisation. G [m, m] symmetric, b [m] or
+    [k, m] (one row per plane: a comes back in b's shape), penalty [m] >= 0 or None. A matrix that is not positive definite (NaN
+    included) raises GlfError(ERR_INVALID)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    b2 = np.ascontiguousarray(np.atleast_2d(np.asarray(b, dtype=np.float64)))
+    m = G.shape[0] if G.ndim == 2 else -1
+    if G.ndim != 2 or G.shape != (m, m) or b2.ndim != 2 or b2.shape[1] != m:
+        raise ValueError("fit_coeffs: G %s, b %s" % (G.shape, np.shape(b)))
+    if penalty is not None:
+        penalty = np.ascontiguousarray(penalty, dtype=np.float64)
+        if penalty.shape != (m,):
+            raise ValueError("fit_coeffs: penalty must be [%d]" % m)
+    a = np.zeros_like(b2)
+    if b2.shape[0] == 0:
+        return a.reshape(np.shape(b))
+    rc = _lib.glf_fit_coeffs(C.c_uint(m), _ptr(G), _ptr(penalty), C.c_int(b2.shape[0]), _ptr(b2), _ptr(a))
+    if rc != OK:
+        raise GlfError(rc, "glf_fit_coeffs(m=%d): not positive definite, or an empty system" % m)
+    return a.reshape(np.shape(b))
 
 
 def shard_rows(height, rank, size):
@@ -1233,6 +1256,45 @@ class Graph:
         c = np.zeros((planes.shape[0], self.info["m"]), dtype=np.float64)
         self.ctx._check(_lib.glf_graph_project(self._g, C.c_int(planes.shape[0]), C.c_void_p(planes.data_ptr()), _ptr(c)), "graph project")
         return c
+
+    def _weight(self, weight):
+        t = self.ctx.torch
+        h, w = self.info["height"], self.info["width"]
+        assert weight.dtype == t.float32 and weight.is_cuda and weight.is_contiguous()
+        if tuple(weight.shape) != (h, w):
+            raise ValueError("weight must be [%d, %d], got %s" % (h, w, tuple(weight.shape)))
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the weights are complete before the library reads them
+        return weight
+
+    def normal_equations(self, weight, planes=None):
+        """G = Phi^T diag(w) Phi [m, m] (exactly symmetric) and b_k = Phi^T diag(w) s_k [nplanes, m] in f64, one pass over Phi
+        (glf_graph_normal_equations). weight: device float32 [H, W], or None for w = 1; planes: device float32 [nplanes, H, W],
+        nplanes <= 4, or None (b is then [0, m]). Neither is checked for NaN / Inf or sign."""
+        m = self.info["m"]
+        nplanes = 0
+        if weight is not None:
+            weight = self._weight(weight)
+        if planes is not None:
+            planes = self._planes(planes)
+            nplanes = planes.shape[0]
+        G, b = np.zeros((m, m), dtype=np.float64), np.zeros((nplanes, m), dtype=np.float64)
+        self.ctx._check(_lib.glf_graph_normal_equations(self._g, C.c_void_p(weight.data_ptr()) if weight is not None else None, C.c_int(nplanes),
+                                                        C.c_void_p(planes.data_ptr()) if nplanes else None, _ptr(G), _ptr(b) if nplanes else None),
+                        "graph normal equations")
+        return G, b
+
+    def fit(self, planes, weight=None, smooth=0.0, ridge=0.0, penalty=None):
+        """The weighted least-squares fit of every plane in the span of Phi: z_k = Phi a_k with a_k minimising
+        sum_px w (s_k - Phi a)^2 + sum_j penalty_j a_j^2 -- hole filling (w a 0/1 mask), confidences, scribble propagation. One
+        normal_equations, fit_coeffs on the host, one synthesize with no identity term -> device float32 [nplanes, H, W].
+        penalty_j = (ridge + smooth * lam_j) * trace(G) / m: relative to the mean diagonal of G, so that smooth and ridge depend on
+        neither the scale of w nor Phi's normalisation; penalty [m] (absolute units) overrides both. smooth * lam is the Laplacian
+        energy of Phi a only to the extent that Phi is orthonormal (the extended eigenvectors are not, exactly). With every
+        penalty 0 and w = 0 on a set that leaves Phi rank deficient the system is refused (GlfError)."""
+        G, b = self.normal_equations(weight, planes)
+        if penalty is None:
+            penalty = (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / self.info["m"])
+        return self.synthesize(fit_coeffs(G, b, penalty))
 
     def synthesize(self, coeffs, ident=None, plane=None, planes=None):
         """out_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (glf_graph_synthesize), one pass over Phi for all outputs: coeffs

@@ -593,6 +593,25 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a /* HOST [nout
  * (gram NULL: GLF_ERR_INVALID). */
 int glf_filter_coeffs(const glf_options *opt, unsigned m, const double *lam, const double *gram, const double *c, double *a, float *ident);
 
+/* ---- weighted least-squares fit on a graph handle ----------------------------------------------------------------------------------
+ * min_a sum_px w (s - Phi a)^2 + a^T diag(penalty) a has the normal equations (Phi^T diag(w) Phi + diag(penalty)) a = Phi^T diag(w) s:
+ * hole filling under a mask, per-pixel confidences, scribble propagation; with w = 1 and no penalty, the orthogonal projection onto
+ * the (non-orthonormal) Phi. glf_graph_normal_equations forms both sides in one pass over Phi (k_graph_normal: G on
+ * v_mfma_f32_32x32x2_f32 with the pixels as the contraction index, A = fl32(w Phi), B = Phi, f32 chains of at most
+ * GLF_GRAPH_NORMAL_CHAIN pixel terms added into f64; b as exact f64 products summed in f64), glf_fit_coeffs solves on the host, and
+ * glf_graph_synthesize with no identity term forms the fit Phi a. Summation order and pixel partition depend on (N, ld) alone:
+ * two calls give the same bits, G does not depend on nplanes, a plane's b does not depend on the planes beside it. Out of scope:
+ * contexts with a communicator (handles refuse them), m > 256, iterative or non-quadratic data terms. */
+#define GLF_GRAPH_NORMAL_CHAIN 128
+/* G = Phi^T diag(w) Phi (HOST [m][m], exactly symmetric) and b_k = Phi^T diag(w) s_k (HOST [nplanes][m]) in one call.
+ * d_w: device float [N] or NULL (w = 1). 0 <= nplanes <= GLF_MAX_SIGNALS; with nplanes 0, d_planes and h_b may be NULL.
+ * w and the planes are not checked for NaN / Inf or sign. */
+int glf_graph_normal_equations(glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_G, double *h_b);
+/* Host only: a_k = (G + diag(penalty))^-1 b_k by an f64 Cholesky factorisation, k < nrhs (G's lower triangle is read). penalty NULL = 0.
+ * GLF_ERR_INVALID for NULL G / b / a, m = 0, nrhs < 1, or a matrix that is not positive definite
+ * (a pivot p with !(p > 0), so NaN is refused too; so is any entry of G or penalty that is not finite); a is then untouched. */
+int glf_fit_coeffs(unsigned m, const double *G, const double *penalty, int nrhs, const double *b, double *a);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
