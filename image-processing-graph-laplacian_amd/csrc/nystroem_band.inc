@@ -734,9 +734,9 @@ struct BandTables {
     int rad = 0, nr = 0, nc = 0, ksc = 0, width = 0;
     int tile_px = 0, ntiles_px = 0, ntiles_s = 0; // pixels per wave tile (32 PB); wave tiles per image row / per grid row
     bool ok = false;
-    // one device blob (one upload): P[256] Ec[rad + 1] Er15[rad + 1] | P replicated as in LDS | grow[nr] gcol[nc] | rowband_px win_px | rowband_s win_s
+    // one device blob (one upload): P[256] Ec[rad + 1] Er15[rad + 1] | P replicated as in LDS | grow[nr] gcol[nc] | rowband_px win_px | rowband_s win_s | dcmax[rad]
     DevBuf<unsigned> blob;
-    size_t o_pexp = 0, o_grid = 0, o_rb_px = 0, o_win_px = 0, o_rb_s = 0, o_win_s = 0;
+    size_t o_pexp = 0, o_grid = 0, o_rb_px = 0, o_win_px = 0, o_rb_s = 0, o_win_s = 0, o_dcmax = 0;
     const float *tab() const { return reinterpret_cast<const float *>(blob.p); }
     const float *pexp() const { return reinterpret_cast<const float *>(blob.p + o_pexp); } // P replicated BAND_PCOPY-fold, as it sits in LDS
     const int *grow() const { return reinterpret_cast<const int *>(blob.p + o_grid); }
@@ -745,6 +745,7 @@ struct BandTables {
     const unsigned *win_px() const { return blob.p + o_win_px; }
     const unsigned *rowband_s() const { return blob.p + o_rb_s; }
     const unsigned *win_s() const { return blob.p + o_win_s; }
+    const int *dcmax() const { return reinterpret_cast<const int *>(blob.p + o_dcmax); } // geom.dcmax (k_band_vec's support)
     std::vector<double> pairs_dr;   // per row distance: (target column, sample column) pairs inside the circle, pixels as targets
     std::vector<double> pairs_dr_s; // ... the samples as targets
     std::vector<int> hrows;
@@ -797,7 +798,8 @@ struct BandTables {
         o_win_px = o_rb_px + (want_px ? (size_t)height : 0);
         o_rb_s = o_win_px + (size_t)rad * ntiles_px;
         o_win_s = o_rb_s + (want_s ? (size_t)nr : 0);
-        std::vector<unsigned> h(o_win_s + (size_t)rad * ntiles_s);
+        o_dcmax = o_win_s + (size_t)rad * ntiles_s;
+        std::vector<unsigned> h(o_dcmax + (size_t)rad);
         float *htab = reinterpret_cast<float *>(h.data());
         for (int e = 0; e < 256; ++e) htab[e] = (float)std::exp2(-(double)coef.s_val * e * e);
         for (int d = 0; d <= rad; ++d) {
@@ -809,6 +811,7 @@ struct BandTables {
         for (int a = 0; a < nr; ++a) h[o_grid + a] = (unsigned)g.rows[a];
         for (int b = 0; b < nc; ++b) h[o_grid + nr + b] = (unsigned)g.cols[b];
         const std::vector<int> &dcmax = geom.dcmax;
+        for (int dr = 0; dr < rad; ++dr) h[o_dcmax + dr] = (unsigned)dcmax[dr];
         int maxband = 0;
         if (want_px) {
             for (int r = 0; r < height; ++r) {
@@ -961,6 +964,11 @@ static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *c
     return GLF_OK;
 }
 
+// (nystroem_band_vec.inc: the fused filter contracted with q = Psi w, one column per plane)
+static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
+                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, const float *d_psi, unsigned ld, const BandFilter &flt,
+                                    float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats);
+
 // Nystroem extension of the image rows [pix0 / width, pix1 / width) in band form (see the head of this file)
 static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
                                 const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi,
@@ -983,6 +991,12 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     const PixGen gen = pixgen_of(coef.kernel);
     const bool raw = gen != PixGen::Grey;
     if (raw && (flt || d_c)) return GLF_ERR_UNSUPPORTED; // (no 8-bit y: the filter stays a stage of its own)
+    if (flt && ld_total > 64) return GLF_ERR_UNSUPPORTED; // (the filter's dot product with w runs over one block of at most 64 columns)
+    if (flt && !ctx->tune.filter_form_phi) { // FILTER_FORM=vec: one column per plane instead of Phi's; its LDS window too large: k_band's epilogue
+        const int rc = launch_nystroem_band_vec(ctx, bt, d_img, width, pix0, pix1, d_samples, d_mask, p, d_psi, ld_total, *flt, kernel_ms,
+                                                entries_evaluated, mfma_flops, stats);
+        if (rc != GLF_ERR_UNSUPPORTED) return rc;
+    }
     DevBuf<unsigned long long> dev_eval;
     GLF_TRY(colscale.alloc(ctx, ld_total));
     GLF_TRY(inv.alloc(ctx, ld_total));
@@ -993,7 +1007,6 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(dev_eval.alloc(ctx, 1));
     const size_t wgs = band_px_wgs(bt, nrows);
     if (flt) d_c = nullptr; // (c was needed before this launch: c_from_ysum)
-    if (flt && nblocks != 1) return GLF_ERR_UNSUPPORTED; // (the dot product with w runs over one 32 MB-column block)
     if (d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
     GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), st));
     band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);

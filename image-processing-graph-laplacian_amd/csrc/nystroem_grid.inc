@@ -1364,6 +1364,7 @@ inline size_t svals32_planes(glf::PixGen g) { return g == glf::PixGen::RgbF32 ? 
 
 #include "nystroem_rank.inc"
 #include "nystroem_band.inc"
+#include "nystroem_band_vec.inc"
 
 } // namespace glf (GridOp is declared at global scope in glf_internal.hpp)
 
