@@ -11,7 +11,8 @@ CFLAGS   ?= -O2 -std=gnu11 -Wall -Wextra -fPIC
 
 HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystroem.hip \
             $(CSRC)/filter.hip $(CSRC)/pipeline.hip $(CSRC)/comm.hip $(CSRC)/nlm.hip $(CSRC)/balance.hip \
-            $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip
+            $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip \
+            $(CSRC)/graph_cluster.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
 C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
@@ -41,8 +42,13 @@ pfm_check: tools/pfm_fuzz_main.c $(HOST)/pfm_codec.c include/glf.h
 	gcc -O1 -g -std=gnu11 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -o tools/pfm_fuzz $(filter %.c,$^) -lm
 	tools/pfm_fuzz
 
+# the host-only centroid update and k-means++ seeding under the address and undefined-behaviour sanitizers (CPU only)
+cluster_check: tools/cluster_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp include/glf.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/cluster_host_check $(filter %.cpp,$^)
+	tools/cluster_host_check
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean pfm_check
+.PHONY: all oracle clean pfm_check cluster_check

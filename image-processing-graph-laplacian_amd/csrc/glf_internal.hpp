@@ -100,6 +100,18 @@ struct glf_ctx {
     glf_tuning tune;
 };
 
+// the graph handle of graph.hip (graph_cluster.hip reads it too)
+struct glf_graph {
+    glf_ctx *ctx = nullptr;
+    int pix = 0, width = 0, height = 0;
+    unsigned p = 0, m = 0, ld = 0;
+    float *phi = nullptr;      // device [N][ld], raster rows (glf_malloc: not a block of the workspace pool)
+    std::vector<double> lam;   // [m]
+    std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
+    int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
+    int cluster_blocks_per_cu = 0; // k_graph_cluster<CW>'s, asked at the first cluster step
+};
+
 namespace glf {
 
 constexpr int WAVE = 64;

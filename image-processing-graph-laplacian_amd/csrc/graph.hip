@@ -8,16 +8,6 @@
 #include <cstdlib>
 #include <new>
 
-struct glf_graph {
-    glf_ctx *ctx = nullptr;
-    int pix = 0, width = 0, height = 0;
-    unsigned p = 0, m = 0, ld = 0;
-    float *phi = nullptr;      // device [N][ld], raster rows (glf_malloc: not a block of the workspace pool)
-    std::vector<double> lam;   // [m]
-    std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
-    int synth_blocks_per_cu = 0; // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
-};
-
 namespace glf {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

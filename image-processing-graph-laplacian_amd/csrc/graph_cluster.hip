@@ -1,0 +1,358 @@
+// graph_cluster.hip -- spectral segmentation on a graph handle: k-means over the rows of Phi. One Lloyd iteration is one pass over
+// Phi (k_graph_cluster: the assignment on k_graph_synthesize's MFMA shape, the per-label sums on k_graph_normal's), driven by
+// glf_graph_cluster_step and glf_graph_segment; the host-only centroid update and k-means++ seeding are in host_util.cpp.
+// Out of scope: row-normalised (Ng-Jordan-Weiss) embeddings, per-pixel weights, more than 64 embedding columns, k > 32, contexts
+// with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
+// k_graph_synthesize and k_graph_normal.
+#include "glf_internal.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace glf {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int GC_K = GLF_CLUSTER_MAX;                       // centroids = the M index of one 32 x 32 accumulator
+constexpr int GC_CHAIN_TILES = GLF_GRAPH_NORMAL_CHAIN / 32; // 32-pixel tiles in one f32 chain of the sums
+constexpr int GC_TAIL = 64;                                 // doubles after a partial's sum tiles: counts [32], changed, zero padding
+static_assert(GC_K == 32, "the centroids fill exactly one MFMA tile");
+static_assert(GLF_GRAPH_NORMAL_CHAIN % 32 == 0 && GLF_GRAPH_NORMAL_CHAIN >= 32, "a chain is a whole number of 32-pixel tiles");
+
+// the per-call operand block of k_graph_cluster (device):
+//   [CW][32] float  fl32(scale_c cent_j[c]) at [c][j], zero for j >= k and c >= dim
+//   [32] float      fl32(|cent_j|^2), zero for j >= k
+inline int gc_cw(unsigned ld) { return ld < 64 ? 32 : 64; }
+inline size_t gc_operand_floats(int cw) { return (size_t)cw * GC_K + GC_K; }
+// one workgroup's partial: [CW / 32][32 labels][32 columns] sums, then the tail
+inline size_t gc_part_cols(int cw) { return (size_t)(cw / 32) * 1024 + GC_TAIL; }
+
+// One Lloyd iteration in one pass over the first CW columns of Phi (row pitch ld floats). One wave per tile of 32 pixels, tiles
+// strided over a resident grid. The tile's rows are loaded as whole 16-byte pieces in address order and written to the wave's own
+// LDS image with the row pitch padded by 4 floats (k_graph_synthesize's image).
+// Assignment: v_mfma_f32_32x32x2_f32 with the centroids as the M index (A: the operand block, from LDS) and the pixels as the N
+// index (B: Phi, one pixel per lane as float4s; pitch CW + 4: the 16 lanes of a ds_read_b128 group hit 64 different banks), half-wave
+// h taking columns h CW / 2 + t at step t: k_graph_synthesize's contraction order, every score its own fma chain. Register g of
+// lane (r, h) then holds the dot product of pixel r with centroid j = (g & 3) + 8 (g >> 2) + 4 h; score = fmaf(-2, dot, |c_j|^2)
+// (|e|^2 is the same for every j and is not formed). Each lane takes the argmin of its 16 registers in ascending j with a strict <
+// (j >= k carries a bias of +inf and never wins), one exchange with the other half-wave decides between the two, the lower index
+// winning a tie.
+// Update: the wave's 32 labels go to LDS (-1 for rows past N), then the same MFMA with the pixels as the contraction index: at step
+// u lane (r, h) gives A = (label[2u + h] == r) and B = Phi[2u + h][r] (and [32 + r]) from the same image -- the 32 lanes of a
+// ds_read_b32 group read 32 consecutive floats of one row, no conflict at any pitch; the label is one address per group, a
+// broadcast. The products are exact; each accumulator tile is an f32 chain over at most GLF_GRAPH_NORMAL_CHAIN pixels, then added
+// into its f64 image and cleared (k_graph_normal's rule). Lane (r, h) counts its own hits: the members of label r among the pixels
+// of parity h, an exact integer; the lanes of half 0 count the labels that differ from prev.
+// No atomics: the workgroup's four waves are added in a fixed order, the workgroups by k_cols_sum. Rows past N are staged as
+// zeros and are neither labelled nor counted. prev may be labels itself: a lane reads prev[px] before it writes labels[px], and
+// no other lane touches that pixel.
+template <int CW>
+__global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
+                                                          const int32_t *prev, int32_t *labels, double *__restrict__ part)
+{
+    constexpr int PITCH = CW + 4;
+    constexpr int FPR = CW / 4;   // float4 pieces per staged row
+    constexpr int NLOAD = CW / 8; // pieces per lane: 32 rows x FPR / 64 lanes
+    constexpr int NT = CW / 32;   // accumulator tiles of the sums
+    constexpr int RW = 32 * PITCH > 2048 ? 32 * PITCH : 2048; // floats of a wave's region (>= one f64 tile for the epilogue)
+    __shared__ __attribute__((aligned(16))) float a_sh[CW * GC_K];
+    __shared__ __attribute__((aligned(16))) float region[4][RW];
+    __shared__ int lab_sh[4][32];
+    __shared__ unsigned cnt_sh[4][64], chg_sh[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    for (int e = threadIdx.x; e < CW * GC_K; e += 256) a_sh[e] = operand[e];
+    float bias[16];
+#pragma unroll
+    for (int g = 0; g < 16; ++g) {
+        const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
+        bias[g] = j < k ? operand[CW * GC_K + j] : INFINITY;
+    }
+    __syncthreads();
+    float *tw = region[wave];
+    const int *lab = lab_sh[wave];
+    const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
+
+    f32x16 acc[NT];
+    double dacc[NT][16];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            acc[t][g] = 0.f;
+            dacc[t][g] = 0.0;
+        }
+    unsigned cnt = 0, chg = 0;
+
+    // what this lane stages of a tile: rows past N as zeros
+    float4 v[NLOAD];
+    int pv = 0;
+    auto load_tile = [&](int64_t tile) {
+        const int64_t base = tile * 32;
+#pragma unroll
+        for (int q = 0; q < NLOAD; ++q) {
+            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (prev && h == 0 && base + r < N) pv = prev[base + r];
+    };
+    auto flush = [&]() {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                dacc[t][g] += (double)acc[t][g];
+                acc[t][g] = 0.f;
+            }
+    };
+
+    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+    if (tile < ntiles) load_tile(tile);
+    int chained = 0; // tiles in the running f32 chains
+    for (; tile < ntiles; tile += tstride) {
+        __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
+#pragma unroll
+        for (int q = 0; q < NLOAD; ++q) {
+            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+            *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
+        }
+        const int pv_cur = pv;
+        __builtin_amdgcn_wave_barrier();
+        // the next tile's loads fly under this tile's MFMAs
+        if (tile + tstride < ntiles) load_tile(tile + tstride);
+
+        f32x16 sc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) sc[g] = 0.f;
+#pragma unroll
+        for (int u = 0; u < CW / 8; ++u) {
+            const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
+            const float *ak = a_sh + (h * (CW / 2) + 4 * u) * GC_K + r;
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GC_K], b.x, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GC_K], b.y, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GC_K], b.z, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GC_K], b.w, sc, 0, 0, 0);
+        }
+        // half 0 always holds centroid 0 < k, so a label is in [0, k) even if no comparison holds
+        float best = INFINITY;
+        int bj = h ? 0x7fffffff : 0;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const float s = fmaf(-2.f, sc[g], bias[g]);
+            if (s < best) {
+                best = s;
+                bj = (g & 3) + 8 * (g >> 2) + 4 * h;
+            }
+        }
+        const float ob = __shfl_xor(best, 32);
+        const int oj = __shfl_xor(bj, 32);
+        if (ob < best || (ob == best && oj < bj)) bj = oj;
+        const int64_t px = tile * 32 + r;
+        if (h == 0) {
+            const bool live = px < N;
+            lab_sh[wave][r] = live ? bj : -1;
+            if (live) {
+                if (prev) chg += pv_cur != bj;
+                labels[px] = bj;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int p = 2 * u + h;
+            const bool hit = lab[p] == r;
+            const float a = hit ? 1.f : 0.f;
+            cnt += hit;
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + r], acc[0], 0, 0, 0);
+            if constexpr (NT == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + 32 + r], acc[1], 0, 0, 0);
+        }
+        if (++chained == GC_CHAIN_TILES) {
+            flush();
+            chained = 0;
+        }
+    }
+    flush();
+
+    // the workgroup's four waves, wave 0 first, tile by tile through the waves' regions (one f64 tile each)
+    double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + GC_TAIL);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        __syncthreads();
+        double *mine = reinterpret_cast<double *>(region[wave]);
+#pragma unroll
+        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[t][g];
+        __syncthreads();
+        for (int e = threadIdx.x; e < 1024; e += 256) {
+            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
+                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
+            pout[(size_t)t * 1024 + e] = s;
+        }
+    }
+    cnt_sh[wave][lane] = cnt;
+    chg_sh[wave][lane] = chg;
+    __syncthreads();
+    if (threadIdx.x < GC_TAIL) {
+        const int t = threadIdx.x;
+        unsigned s = 0;
+        if (t < 32) {
+            for (int w = 0; w < 4; ++w) s += cnt_sh[w][t] + cnt_sh[w][t + 32];
+        } else if (t == 32) {
+            for (int w = 0; w < 4; ++w)
+                for (int l = 0; l < 32; ++l) s += chg_sh[w][l];
+        }
+        pout[NT * 1024 + t] = (double)s;
+    }
+}
+
+// out[i][c] = Phi[floor(i N / ns)][c], c < dim: the sample of rows the seeding draws from
+__global__ void k_cluster_sample(const float *__restrict__ phi, int64_t N, int ld, int64_t ns, int dim, float *__restrict__ out)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * dim) return;
+    const int64_t i = e / dim;
+    const int c = (int)(e % dim);
+    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
+    out[e] = phi[(size_t)px * ld + c];
+}
+
+template <int CW>
+static int launch_cluster(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, unsigned k, const float *d_operand,
+                          const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, unsigned *nblk_out)
+{
+    if (*per_cu <= 0) {
+        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_graph_cluster<CW>, 256, 0));
+        *per_cu = std::max(1, *per_cu);
+    }
+    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
+    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident); // (the rest of the tiles by the grid stride)
+    GLF_TRY(part.alloc(ctx, (size_t)nblk * gc_part_cols(CW)));
+    hipLaunchKernelGGL(k_graph_cluster<CW>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)ld, (int)k, d_operand, d_prev, d_labels,
+                       part.p);
+    GLF_LAUNCH_CHECK(ctx);
+    *nblk_out = (unsigned)nblk;
+    return GLF_OK;
+}
+
+static bool all_finite(const double *x, size_t n)
+{
+    for (size_t e = 0; e < n; ++e)
+        if (!std::isfinite(x[e])) return false;
+    return true;
+}
+
+// what glf_graph_cluster_step and glf_graph_segment refuse alike, before any device work
+static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
+{
+    if (!g || k == 0 || k > (unsigned)GC_K || dim == 0 || dim > std::min(g->m, 64u)) return false;
+    return !scale || all_finite(scale, dim);
+}
+
+// one Lloyd iteration on checked arguments (returns with the stream drained)
+static int cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev, int32_t *d_labels,
+                        double *h_sums, uint64_t *h_counts, uint64_t *changed)
+{
+    glf_ctx *ctx = g->ctx;
+    const unsigned ld = g->ld;
+    const int cw = gc_cw(ld);
+    const int64_t N = (int64_t)g->width * g->height;
+    std::vector<float> h_op(gc_operand_floats(cw), 0.f);
+    for (unsigned j = 0; j < k; ++j) {
+        double n2 = 0.0;
+        for (unsigned c = 0; c < dim; ++c) {
+            const double x = h_cent[(size_t)j * dim + c];
+            h_op[(size_t)c * GC_K + j] = (float)((scale ? scale[c] : 1.0) * x);
+            n2 += x * x;
+        }
+        h_op[(size_t)cw * GC_K + j] = (float)n2;
+    }
+    DevBuf<float> op;
+    DevBuf<double> part, tot;
+    GLF_TRY(op.alloc(ctx, h_op.size()));
+    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    unsigned nblk = 0;
+    if (cw == 32) GLF_TRY(launch_cluster<32>(ctx, &g->cluster_blocks_per_cu, g->phi, N, ld, k, op.p, d_prev, d_labels, part, &nblk));
+    else GLF_TRY(launch_cluster<64>(ctx, &g->cluster_blocks_per_cu, g->phi, N, ld, k, op.p, d_prev, d_labels, part, &nblk));
+    const size_t ncols = gc_part_cols(cw);
+    GLF_TRY(tot.alloc(ctx, ncols));
+    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
+    GLF_LAUNCH_CHECK(ctx);
+    std::vector<double> h_tot(ncols);
+    GLF_HIP(ctx, hipMemcpyAsync(h_tot.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
+    const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
+    for (unsigned j = 0; j < k; ++j) {
+        for (unsigned c = 0; c < dim; ++c) h_sums[(size_t)j * dim + c] = h_tot[(size_t)(c / 32) * 1024 + j * 32 + c % 32];
+        h_counts[j] = (uint64_t)tail[j];
+    }
+    *changed = d_prev ? (uint64_t)tail[32] : 0;
+    return GLF_OK;
+}
+
+} // namespace glf
+
+using namespace glf;
+
+extern "C" {
+
+int glf_graph_cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev,
+                           int32_t *d_labels, double *h_sums, uint64_t *h_counts, uint64_t *changed)
+{
+    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !changed) return GLF_ERR_INVALID;
+    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k, dim,
+                         g->m);
+    GLF_ENTER(g->ctx);
+    return cluster_step(g, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, changed);
+}
+
+int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_labels, double *h_cent, glf_segment_stats *stats)
+{
+    if (!g || !opt || !d_labels || !h_cent || opt->struct_size != sizeof(glf_segment_options)) return GLF_ERR_INVALID;
+    glf_ctx *ctx = g->ctx;
+    const unsigned k = opt->k, dim = opt->dim;
+    const double *scale = opt->scale;
+    if (!cluster_shape_ok(g, k, dim, scale) || (opt->init != 0 && opt->init != 1) || (opt->init == 1 && !all_finite(h_cent, (size_t)k * dim)))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment: k=%u dim=%u (m=%u) init=%d, or a centroid or scale entry that is not finite", k, dim,
+                         g->m, opt->init);
+    const unsigned max_iter = opt->max_iter ? opt->max_iter : 50;
+    const int64_t N = (int64_t)g->width * g->height;
+    GLF_ENTER(ctx);
+    std::vector<double> cent((size_t)k * dim);
+    if (opt->init == 0) {
+        const int64_t ns = std::min<int64_t>(opt->sample_rows ? opt->sample_rows : 4096, N);
+        const size_t cnt = (size_t)ns * dim;
+        DevBuf<float> d_rows;
+        GLF_TRY(d_rows.alloc(ctx, cnt));
+        hipLaunchKernelGGL(k_cluster_sample, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, ns, (int)dim,
+                           d_rows.p);
+        GLF_LAUNCH_CHECK(ctx);
+        std::vector<float> h_rows(cnt);
+        GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
+        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<double> rows(cnt);
+        for (size_t e = 0; e < cnt; ++e) rows[e] = (scale ? scale[e % dim] : 1.0) * (double)h_rows[e];
+        if (glf_cluster_seed(rows.data(), (size_t)ns, dim, k, opt->seed, cent.data()) != GLF_OK)
+            return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment: the sample of %lld rows holds fewer than %u distinct rows", (long long)ns, k);
+    } else
+        std::copy(h_cent, h_cent + (size_t)k * dim, cent.begin());
+    std::vector<double> sums((size_t)k * dim);
+    uint64_t counts[GC_K] = {0}, changed = 0;
+    unsigned it = 0;
+    int converged = 0;
+    while (it < max_iter && !converged) {
+        GLF_TRY(cluster_step(g, k, dim, cent.data(), scale, it ? d_labels : nullptr, d_labels, sums.data(), counts, &changed));
+        converged = it > 0 && changed == 0;
+        ++it;
+        GLF_TRY(glf_cluster_update(k, dim, scale, sums.data(), counts, cent.data(), cent.data()));
+    }
+    std::copy(cent.begin(), cent.end(), h_cent);
+    if (stats) {
+        stats->iterations = it;
+        stats->converged = converged;
+        stats->changed_last = changed;
+        for (int j = 0; j < GC_K; ++j) stats->counts[j] = j < (int)k ? counts[j] : 0;
+    }
+    return GLF_OK;
+}
+
+} // extern "C"

@@ -1,5 +1,6 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
-// synthetic benchmark images, the geometry and schedule of the band form. No device code.
+// synthetic benchmark images, the geometry and schedule of the band form, the centroid update and
+// the seeding of the spectral segmentation. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -198,6 +199,58 @@ int glf_band_plan(const int *rows, int nr, const int *cols, int nc, float h_loc,
         }
     }
     if (ksteps) *ksteps = steps;
+    return GLF_OK;
+}
+
+// The centroid update of one Lloyd iteration: the mean of a label's raw rows of Phi, moved into the embedding by scale.
+int glf_cluster_update(unsigned k, unsigned dim, const double *scale, const double *sums, const uint64_t *counts, const double *cent_prev,
+                       double *cent)
+{
+    if (!sums || !counts || !cent || k == 0 || dim == 0) return GLF_ERR_INVALID;
+    if (!cent_prev)
+        for (unsigned j = 0; j < k; ++j)
+            if (counts[j] == 0) return GLF_ERR_INVALID;
+    for (unsigned j = 0; j < k; ++j)
+        for (unsigned c = 0; c < dim; ++c) {
+            const size_t e = (size_t)j * dim + c;
+            cent[e] = counts[j] ? (scale ? scale[c] : 1.0) * sums[e] / (double)counts[j] : cent_prev[e];
+        }
+    return GLF_OK;
+}
+
+// k-means++ (Arthur & Vassilvitskii 2007) on the library's own uniform stream, so that a seed names one set of centres.
+int glf_cluster_seed(const double *rows, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
+{
+    if (!rows || !cent || n == 0 || dim == 0 || k == 0 || k > n) return GLF_ERR_INVALID;
+    Xoshiro256ss rng(seed);
+    std::vector<size_t> chosen(k);
+    std::vector<double> d2(n);
+    chosen[0] = std::min(n - 1, (size_t)(rng.uniform() * (double)n));
+    for (unsigned t = 1; t < k; ++t) {
+        const double *c = rows + chosen[t - 1] * dim;
+        double total = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            double d = 0.0;
+            for (unsigned q = 0; q < dim; ++q) {
+                const double x = rows[i * dim + q] - c[q];
+                d += x * x;
+            }
+            d2[i] = t == 1 ? d : std::min(d2[i], d);
+            total += d2[i];
+        }
+        if (!(total > 0.0) || !std::isfinite(total)) return GLF_ERR_INVALID; // fewer than k distinct rows (or a NaN / Inf)
+        const double target = rng.uniform() * total;
+        size_t pick = n;
+        double run = 0.0;
+        for (size_t i = 0; i < n && pick == n; ++i) {
+            run += d2[i];
+            if (run > target) pick = i;
+        }
+        if (pick == n) // (run ends at total > target; unreachable, kept so that no index leaves the rows)
+            for (pick = n - 1; pick > 0 && !(d2[pick] > 0.0);) --pick;
+        chosen[t] = pick;
+    }
+    for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
     return GLF_OK;
 }
 

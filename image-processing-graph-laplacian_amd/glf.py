@@ -63,11 +63,13 @@ EXPORTS = [
     "glf_multi_image_processing_rgbf32", "glf_multi_image_processing_rgbf32_signals", "glf_read_pfm_rgb", "glf_write_pfm_rgb",
     "glf_graph_build", "glf_graph_destroy", "glf_graph_get_info", "glf_graph_eigenvalues", "glf_graph_gram", "glf_graph_project",
     "glf_graph_synthesize", "glf_filter_coeffs", "glf_graph_normal_equations", "glf_fit_coeffs",
+    "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
 GRAPH_MAX_OUTPUTS = 32
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
+CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 
 
 class Mat(C.Structure):
@@ -124,6 +126,15 @@ class GraphInfo(C.Structure):
                 ("m", C.c_uint32), ("ld", C.c_uint32), ("d_phi", C.c_void_p), ("phi_bytes", C.c_size_t)]
 
 
+class SegmentOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("dim", C.c_uint32), ("max_iter", C.c_uint32), ("sample_rows", C.c_uint32),
+                ("init", C.c_int32), ("seed", C.c_uint64), ("scale", C.c_void_p)]
+
+
+class SegmentStats(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("converged", C.c_int32), ("changed_last", C.c_uint64), ("counts", C.c_uint64 * CLUSTER_MAX)]
+
+
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHER_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -152,6 +163,11 @@ _lib.glf_graph_gram.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_graph_project.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 _lib.glf_graph_synthesize.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 _lib.glf_filter_coeffs.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_cluster_step.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]
+_lib.glf_cluster_update.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_cluster_seed.argtypes = [C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
+_lib.glf_graph_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -376,6 +392,50 @@ def fit_coeffs(G, b, penalty=None):
     if rc != OK:
         raise GlfError(rc, "glf_fit_coeffs(m=%d): not positive definite, or an empty system" % m)
     return a.reshape(np.shape(b))
+
+
+def _scale(scale, dim):
+    if scale is None:
+        return None
+    scale = np.ascontiguousarray(scale, dtype=np.float64)
+    if scale.shape != (dim,):
+        raise ValueError("scale must be [%d], got %s" % (dim, scale.shape))
+    return scale
+
+
+def cluster_update(sums, counts, scale=None, cent_prev=None):
+    """glf_cluster_update (host only): cent_j = scale o sums_j / counts_j of one Lloyd iteration; an empty cluster keeps cent_prev_j.
+    sums [k, dim] (the sums of the raw rows of Phi per label), counts [k], scale [dim] or None (= 1), cent_prev [k, dim] (may be
+    None when no cluster is empty) -> cent [k, dim]."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    if sums.ndim != 2 or counts.shape != (sums.shape[0],):
+        raise ValueError("cluster_update: sums %s, counts %s" % (sums.shape, counts.shape))
+    k, dim = sums.shape
+    scale = _scale(scale, dim)
+    if cent_prev is not None:
+        cent_prev = np.ascontiguousarray(cent_prev, dtype=np.float64)
+        if cent_prev.shape != (k, dim):
+            raise ValueError("cluster_update: cent_prev must be [%d, %d]" % (k, dim))
+    cent = np.zeros((k, dim), dtype=np.float64)
+    rc = _lib.glf_cluster_update(C.c_uint(k), C.c_uint(dim), _ptr(scale), _ptr(sums), _ptr(counts), _ptr(cent_prev), _ptr(cent))
+    if rc != OK:
+        raise GlfError(rc, "glf_cluster_update(k=%d, dim=%d): an empty cluster without cent_prev, or an empty shape" % (k, dim))
+    return cent
+
+
+def cluster_seed(rows, k, seed=1):
+    """glf_cluster_seed (host only): k-means++ seeding of k centres among rows [n, dim] on the uniforms random_vectors(k, 1, seed)
+    exposes -> cent [k, dim]. Fewer than k distinct rows raise GlfError(ERR_INVALID)."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2:
+        raise ValueError("cluster_seed: rows must be [n, dim], got %s" % (rows.shape,))
+    n, dim = rows.shape
+    cent = np.zeros((max(int(k), 0), dim), dtype=np.float64)
+    rc = _lib.glf_cluster_seed(_ptr(rows), C.c_size_t(n), C.c_uint(dim), C.c_uint(k), C.c_uint64(seed), _ptr(cent))
+    if rc != OK:
+        raise GlfError(rc, "glf_cluster_seed(n=%d, dim=%d, k=%d): fewer than k distinct rows, or an empty shape" % (n, dim, k))
+    return cent
 
 
 def shard_rows(height, rank, size):
@@ -1319,6 +1379,60 @@ class Graph:
                                                   C.c_void_p(planes.data_ptr()) if planes is not None else None,
                                                   C.c_void_p(out.data_ptr())), "graph synthesize")   # (returns with the stream drained)
         return out
+
+    def _labels(self, labels, what):
+        t = self.ctx.torch
+        h, w = self.info["height"], self.info["width"]
+        assert labels.dtype == t.int32 and labels.is_cuda and labels.is_contiguous()
+        if tuple(labels.shape) != (h, w):
+            raise ValueError("%s must be [%d, %d], got %s" % (what, h, w, tuple(labels.shape)))
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the labels are complete before the library touches them
+        return labels
+
+    def _new_labels(self):
+        t = self.ctx.torch
+        with t.cuda.stream(self.ctx.stream):
+            return t.empty((self.info["height"], self.info["width"]), dtype=t.int32, device=self.ctx.device)   # (every element is written)
+
+    def cluster_step(self, cent, scale=None, prev=None, labels=None):
+        """One Lloyd iteration of k-means over the embedded rows e(px) = scale o Phi[px][:dim] in one pass over Phi
+        (glf_graph_cluster_step): every pixel takes the nearest of the centroids cent [k, dim] (embedding space; k <= 32,
+        dim <= min(m, 64); the lowest index wins a tie). scale [dim] or None (= 1); prev: device int32 [H, W] labels to count the
+        changes against, or None; labels: the device int32 [H, W] tensor to write (it may be prev itself), or None for a new one.
+        -> (labels, sums [k, dim] of the raw rows of Phi per label, counts uint64 [k], changed)."""
+        cent = np.ascontiguousarray(np.atleast_2d(np.asarray(cent, dtype=np.float64)))
+        k, dim = cent.shape
+        scale = _scale(scale, dim)
+        if prev is not None:
+            prev = self._labels(prev, "prev")
+        labels = self._new_labels() if labels is None else self._labels(labels, "labels")
+        sums, counts, changed = np.zeros((k, dim), dtype=np.float64), np.zeros(k, dtype=np.uint64), C.c_uint64(0)
+        self.ctx._check(_lib.glf_graph_cluster_step(self._g, C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale),
+                                                    C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(labels.data_ptr()),
+                                                    _ptr(sums), _ptr(counts), C.byref(changed)), "graph cluster step")   # (returns with the stream drained)
+        return labels, sums, counts, int(changed.value)
+
+    def segment(self, k, dim=None, scale=None, init=None, seed=1, max_iter=50, sample_rows=4096):
+        """Spectral segmentation (glf_graph_segment): Lloyd's k-means over the embedded rows, cluster_step + cluster_update until a
+        step moves no label or max_iter steps ran. dim defaults to min(m, 64, max(k, 2)): the usual k vectors for k segments. init:
+        centroids [k, dim] in embedding space, or None for k-means++ seeding (cluster_seed with `seed`) among the sample_rows rows
+        floor(i N / n_s) of Phi. -> (labels device int32 [H, W], cent [k, dim], dict(iterations, converged, changed_last, counts))."""
+        if dim is None:
+            dim = min(self.info["m"], 64, max(int(k), 2))
+        cent = np.zeros((max(int(k), 0), max(int(dim), 0)), dtype=np.float64)
+        if init is not None:
+            init = np.asarray(init, dtype=np.float64)
+            if init.shape != cent.shape:
+                raise ValueError("init must be [%d, %d], got %s" % (cent.shape + (init.shape,)))
+            cent[...] = init
+        scale = _scale(scale, int(dim))
+        labels = self._new_labels()
+        opt = SegmentOptions(C.sizeof(SegmentOptions), k, dim, max_iter, sample_rows, 0 if init is None else 1, seed,
+                             scale.ctypes.data if scale is not None else None)
+        st = SegmentStats()
+        self.ctx._check(_lib.glf_graph_segment(self._g, C.byref(opt), C.c_void_p(labels.data_ptr()), _ptr(cent), C.byref(st)), "graph segment")
+        return labels, cent, dict(iterations=int(st.iterations), converged=int(st.converged), changed_last=int(st.changed_last),
+                                  counts=np.array(st.counts[:int(k)], dtype=np.uint64))
 
     def apply(self, planes, weights, ident=1.0):
         """Diagonal responses: out[r, k] = ident[r] * s_k + Phi diag(weights[r]) Phi^T s_k for every response r and plane k -- one

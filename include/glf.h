@@ -615,6 +615,60 @@ int glf_graph_normal_equations(glf_graph *g, const float *d_w, int nplanes, cons
  * (a pivot p with !(p > 0), so NaN is refused too; so is any entry of G or penalty that is not finite); a is then untouched. */
 int glf_fit_coeffs(unsigned m, const double *G, const double *penalty, int nrhs, const double *b, double *a);
 
+/* ---- spectral segmentation on a graph handle: k-means over the rows of Phi ---------------------------------------------------------
+ * The third classic use of the extended eigenvectors: embed every pixel as e(px) = scale o Phi[px][0..dim) (columns in the handle's
+ * own order, that of glf_graph_eigenvalues; a 0 in scale drops a column) and cluster the rows (Lloyd's k-means). One iteration is
+ * one pass over Phi (k_graph_cluster): the score |c_j|^2 - 2 e . c_j of every pixel against k centroids on v_mfma_f32_32x32x2_f32
+ * (operands fl32(scale c_j) and Phi, the fixed contraction order of glf_graph_synthesize: a score's bits do not depend on the
+ * centroids beside it), the argmin with the lowest index winning a tie, and in the same pass the per-label sums of the raw rows of
+ * Phi (MFMA with the pixels as the contraction index and an exact 0/1 indicator operand, f32 chains of at most GLF_GRAPH_NORMAL_CHAIN
+ * pixel terms added into f64), the member counts and the number of labels that moved (exact integers). No atomics; the pixel
+ * partition depends on (N, ld) and the device alone: two calls give the same bits. Only the first 32 (ld 32) or 64 (ld >= 64) columns
+ * of a row are read, whatever ld is. Out of scope: row-normalised (Ng-Jordan-Weiss) embeddings; per-pixel weights; more than 64
+ * embedding columns; k > GLF_CLUSTER_MAX; contexts with a communicator and glf_multi_* (handles refuse them); a flag of the
+ * image_processing host program; k_band, k_graph_synthesize and k_graph_normal, which are untouched. */
+#define GLF_CLUSTER_MAX 32
+/* One Lloyd iteration. h_cent HOST [k][dim] (embedding space), scale HOST [dim] or NULL (= 1). d_labels device int32 [N], written;
+ * d_prev device int32 [N] or NULL, may be d_labels itself (in place). h_sums HOST [k][dim] = the sum of the raw rows of Phi per label
+ * (the caller applies scale: glf_cluster_update), h_counts HOST uint64 [k], *changed = the pixels whose label differs from d_prev's
+ * (0 without d_prev). GLF_ERR_INVALID before any device work, d_labels untouched: a NULL handle or NULL h_cent / d_labels / h_sums /
+ * h_counts / changed, k = 0 or k > GLF_CLUSTER_MAX, dim = 0 or dim > min(m, 64), a centroid or scale entry that is not finite.
+ * Returns with the stream drained. */
+int glf_graph_cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev,
+                           int32_t *d_labels, double *h_sums, uint64_t *h_counts, uint64_t *changed);
+/* Host only: cent_j = scale o sums_j / counts_j (scale NULL = 1); an empty cluster keeps cent_prev_j. cent may be cent_prev.
+ * GLF_ERR_INVALID, cent untouched: NULL sums / counts / cent, k = 0, dim = 0, an empty cluster without cent_prev. */
+int glf_cluster_update(unsigned k, unsigned dim, const double *scale, const double *sums, const uint64_t *counts, const double *cent_prev,
+                       double *cent);
+/* Host only: k-means++ seeding of k centres among the n rows [n][dim]. It consumes the uniforms u_0 .. u_{k-1} of the stream
+ * glf_random_vectors(.., seed) exposes: the first centre is row floor(u_0 n); centre t is the first row, in row order, whose running
+ * sum of D^2 exceeds u_t times the total, D^2 the squared distance to the nearest centre chosen so far. GLF_ERR_INVALID, cent
+ * untouched: NULL rows / cent, n = 0, dim = 0, k = 0, k > n, or a total that is not positive (fewer than k distinct rows; a NaN). */
+int glf_cluster_seed(const double *rows, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent);
+/* The driver. init 0: the rows px_i = floor(i N / n_s), i < n_s = min(sample_rows, N), first dim columns, are gathered to the host,
+ * scaled and seeded (glf_cluster_seed with opt->seed); init 1: the caller's h_cent. Then glf_graph_cluster_step + glf_cluster_update
+ * with the labels in place, the first step without d_prev, until a step changes no label (converged = 1) or max_iter steps ran. The
+ * labels returned are those of the last step, h_cent its update: the usual Lloyd state. max_iter 0 means 50, sample_rows 0 means
+ * 4096. One read-back per iteration is the loop's only host poll. Refusals as for glf_graph_cluster_step, and a struct_size that is
+ * not sizeof(glf_segment_options), an init other than 0 / 1, or a sample without k distinct rows. */
+typedef struct glf_segment_options {
+    uint32_t struct_size;  /* sizeof(glf_segment_options), set by the caller */
+    uint32_t k, dim;
+    uint32_t max_iter;     /* 0: 50 */
+    uint32_t sample_rows;  /* 0: 4096 */
+    int32_t init;          /* 0: seed from a sample of the rows, 1: the caller's h_cent */
+    uint64_t seed;
+    const double *scale;   /* HOST [dim] or NULL (= 1) */
+} glf_segment_options;
+typedef struct glf_segment_stats {
+    uint32_t iterations;   /* steps run */
+    int32_t converged;
+    uint64_t changed_last; /* labels the last step moved (0 when only one step ran) */
+    uint64_t counts[GLF_CLUSTER_MAX];
+} glf_segment_stats;
+int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_labels, double *h_cent /* HOST [k][dim]: in (init 1) / out */,
+                      glf_segment_stats *stats /* or NULL */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
