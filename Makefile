@@ -42,7 +42,7 @@ pfm_check: tools/pfm_fuzz_main.c $(HOST)/pfm_codec.c include/glf.h
 	gcc -O1 -g -std=gnu11 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -o tools/pfm_fuzz $(filter %.c,$^) -lm
 	tools/pfm_fuzz
 
-# the host-only centroid update and k-means++ seeding under the address and undefined-behaviour sanitizers (CPU only)
+# the host-only centroid updates and k-means++ seedings (plain and weighted) under the address and undefined-behaviour sanitizers (CPU only)
 cluster_check: tools/cluster_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp include/glf.h
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/cluster_host_check $(filter %.cpp,$^)
 	tools/cluster_host_check

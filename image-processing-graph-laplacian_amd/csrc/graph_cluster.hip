@@ -1,8 +1,10 @@
 // graph_cluster.hip -- spectral segmentation on a graph handle: k-means over the rows of Phi. One Lloyd iteration is one pass over
 // Phi (k_graph_cluster: the assignment on k_graph_synthesize's MFMA shape, the per-label sums on k_graph_normal's), driven by
 // glf_graph_cluster_step and glf_graph_segment; the host-only centroid update and k-means++ seeding are in host_util.cpp.
-// Out of scope: row-normalised (Ng-Jordan-Weiss) embeddings, per-pixel weights, more than 64 embedding columns, k > 32, contexts
-// with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
+// Unit-length rows (the row-normalised embedding of Ng, Jordan and Weiss) and per-pixel weights are a kernel of their own,
+// k_graph_cluster_nw, behind glf_graph_cluster_step_ex and glf_graph_segment_ex; k_graph_cluster is what a plain embedding runs.
+// Out of scope: spherical k-means (renormalised centroids), a margin or confidence output, more than 64 embedding columns, k > 32,
+// contexts with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
 // k_graph_synthesize and k_graph_normal.
 #include "glf_internal.hpp"
 
@@ -288,6 +290,293 @@ static int cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_
     return GLF_OK;
 }
 
+// ---- unit-length rows and per-pixel weights ------------------------------------------------------------------------------------------
+// k_graph_cluster_nw: k_graph_cluster with the embedding e(px) = rinv(px) scale o Phi[px] and a weight plane in the update. The
+// staging, the MFMA shapes and the contraction order are k_graph_cluster's; what it adds:
+//   the per-call operand block grows by [CW] float fl32(scale_c), zero for c >= dim (gc_nw_operand_floats), kept in LDS;
+//   the 16 biases of a lane are read from LDS at every tile (bias_sh, +inf for j >= k; registers 4 q .. 4 q + 3 hold 16 consecutive
+//   bytes) instead of living in registers: with them in registers as in k_graph_cluster, CW 64 spilled 5 registers (24 bytes of scratch;
+//   profiles/graph_cluster_nw_kernel_resources.txt). The values, and so every score's bits, are the same;
+//   with `normalize`, lane (r, h) forms the squared length of its half row of pixel r from the float4s it reads anyway,
+//   n2 = fmaf(x, x, n2), x = fl32(scale_c) phi_c, in ascending column order; the halves are added through one __shfl_xor(.., 32) (a
+//   commutative sum: both half-waves hold the same bits) and rinv = n2 > 0 ? 1 / sqrtf(n2) : 0; without it rinv = 1 and none of this runs
+//   (NORM is a template argument: a run-time branch inside the unrolled contraction cuts it into one basic block per four MFMAs, and
+//   the LDS reads of the next step are then no longer issued under the MFMAs of this one);
+//   score = fmaf(-2 rinv, dot, |c_j|^2): with rinv = 1 the plain kernel's bits;
+//   t(px) = fl32(w(px) rinv(px)) and w(px) go to LDS beside the tile's 32 labels (w is loaded with the prefetch of the next tile, as
+//   prev is; NULL is w = 1), and the update's A operand is hit ? t[p] : 0: sums_j = sum w rinv Phi[px][c] over the members of j;
+//   lane (r, h) adds (double) w[p] over its hits: the mass of label r among the pixels of parity h. Counts and changed stay integers.
+// The partial's tail is GC_TAIL_NW doubles: counts [32], changed, zero padding up to 64, then the mass [32].
+constexpr int GC_TAIL_NW = 96;
+inline size_t gc_nw_operand_floats(int cw) { return gc_operand_floats(cw) + (size_t)cw; }
+inline size_t gc_nw_part_cols(int cw) { return (size_t)(cw / 32) * 1024 + GC_TAIL_NW; }
+
+template <int CW, bool NORM>
+__global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
+                                                             const float *__restrict__ weight, const int32_t *prev, int32_t *labels,
+                                                             double *__restrict__ part)
+{
+    constexpr int PITCH = CW + 4;
+    constexpr int FPR = CW / 4;
+    constexpr int NLOAD = CW / 8;
+    constexpr int NT = CW / 32;
+    constexpr int RW = 32 * PITCH > 2048 ? 32 * PITCH : 2048;
+    __shared__ __attribute__((aligned(16))) float a_sh[CW * GC_K];
+    __shared__ __attribute__((aligned(16))) float region[4][RW];
+    __shared__ __attribute__((aligned(16))) float s_sh[CW];
+    __shared__ __attribute__((aligned(16))) float bias_sh[GC_K];
+    __shared__ int lab_sh[4][32];
+    __shared__ float t_sh[4][32], w_sh[4][32];
+    __shared__ unsigned cnt_sh[4][64], chg_sh[4][64];
+    __shared__ double mass_sh[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    for (int e = threadIdx.x; e < CW * GC_K; e += 256) a_sh[e] = operand[e];
+    if (threadIdx.x < GC_K) bias_sh[threadIdx.x] = (int)threadIdx.x < k ? operand[CW * GC_K + threadIdx.x] : INFINITY;
+    if (threadIdx.x < CW) s_sh[threadIdx.x] = operand[CW * GC_K + GC_K + threadIdx.x];
+    __syncthreads();
+    float *tw = region[wave];
+    const int *lab = lab_sh[wave];
+    const float *tsh = t_sh[wave], *wsh = w_sh[wave];
+    const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
+
+    f32x16 acc[NT];
+    double dacc[NT][16];
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            acc[t][g] = 0.f;
+            dacc[t][g] = 0.0;
+        }
+    unsigned cnt = 0, chg = 0;
+    double mass = 0.0;
+
+    float4 v[NLOAD];
+    int pv = 0;
+    float wv = 1.f;
+    auto load_tile = [&](int64_t tile) {
+        const int64_t base = tile * 32;
+#pragma unroll
+        for (int q = 0; q < NLOAD; ++q) {
+            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        if (h == 0 && base + r < N) {
+            if (prev) pv = prev[base + r];
+            if (weight) wv = weight[base + r];
+        }
+    };
+    auto flush = [&]() {
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                dacc[t][g] += (double)acc[t][g];
+                acc[t][g] = 0.f;
+            }
+    };
+
+    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+    if (tile < ntiles) load_tile(tile);
+    int chained = 0;
+    for (; tile < ntiles; tile += tstride) {
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int q = 0; q < NLOAD; ++q) {
+            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
+            *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
+        }
+        const int pv_cur = pv;
+        const float wv_cur = wv;
+        __builtin_amdgcn_wave_barrier();
+        if (tile + tstride < ntiles) load_tile(tile + tstride);
+
+        f32x16 sc;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) sc[g] = 0.f;
+        float n2 = 0.f;
+#pragma unroll
+        for (int u = 0; u < CW / 8; ++u) {
+            const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
+            const float *ak = a_sh + (h * (CW / 2) + 4 * u) * GC_K + r;
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GC_K], b.x, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GC_K], b.y, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GC_K], b.z, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GC_K], b.w, sc, 0, 0, 0);
+            if constexpr (NORM) {
+                const float4 s = *reinterpret_cast<const float4 *>(s_sh + h * (CW / 2) + 4 * u);
+                const float x0 = s.x * b.x, x1 = s.y * b.y, x2 = s.z * b.z, x3 = s.w * b.w;
+                n2 = fmaf(x0, x0, n2);
+                n2 = fmaf(x1, x1, n2);
+                n2 = fmaf(x2, x2, n2);
+                n2 = fmaf(x3, x3, n2);
+            }
+        }
+        float rinv = 1.f;
+        if constexpr (NORM) {
+            n2 += __shfl_xor(n2, 32);
+            rinv = n2 > 0.f ? 1.f / sqrtf(n2) : 0.f;
+        }
+        const float m2 = -2.f * rinv;
+        float best = INFINITY;
+        int bj = h ? 0x7fffffff : 0;
+#pragma unroll
+        for (int g = 0; g < 16; ++g) {
+            const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
+            const float s = fmaf(m2, sc[g], bias_sh[j]);
+            if (s < best) {
+                best = s;
+                bj = j;
+            }
+        }
+        const float ob = __shfl_xor(best, 32);
+        const int oj = __shfl_xor(bj, 32);
+        if (ob < best || (ob == best && oj < bj)) bj = oj;
+        const int64_t px = tile * 32 + r;
+        if (h == 0) {
+            const bool live = px < N;
+            lab_sh[wave][r] = live ? bj : -1;
+            t_sh[wave][r] = wv_cur * rinv;
+            w_sh[wave][r] = wv_cur;
+            if (live) {
+                if (prev) chg += pv_cur != bj;
+                labels[px] = bj;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int p = 2 * u + h;
+            const bool hit = lab[p] == r;
+            const float tp = tsh[p], wp = wsh[p]; // (read whatever hit is: a branch here would cut the MFMA chain into blocks of two)
+            const float a = hit ? tp : 0.f;
+            cnt += hit;
+            mass += (double)(hit ? wp : 0.f);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + r], acc[0], 0, 0, 0);
+            if constexpr (NT == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + 32 + r], acc[1], 0, 0, 0);
+        }
+        if (++chained == GC_CHAIN_TILES) {
+            flush();
+            chained = 0;
+        }
+    }
+    flush();
+
+    double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + GC_TAIL_NW);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        __syncthreads();
+        double *mine = reinterpret_cast<double *>(region[wave]);
+#pragma unroll
+        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[t][g];
+        __syncthreads();
+        for (int e = threadIdx.x; e < 1024; e += 256) {
+            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
+                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
+            pout[(size_t)t * 1024 + e] = s;
+        }
+    }
+    cnt_sh[wave][lane] = cnt;
+    chg_sh[wave][lane] = chg;
+    mass_sh[wave][lane] = mass;
+    __syncthreads();
+    if (threadIdx.x < GC_TAIL_NW) {
+        const int t = threadIdx.x;
+        double out = 0.0;
+        if (t < 32) {
+            unsigned s = 0;
+            for (int w = 0; w < 4; ++w) s += cnt_sh[w][t] + cnt_sh[w][t + 32];
+            out = (double)s;
+        } else if (t == 32) {
+            unsigned s = 0;
+            for (int w = 0; w < 4; ++w)
+                for (int l = 0; l < 32; ++l) s += chg_sh[w][l];
+            out = (double)s;
+        } else if (t >= 64) {
+            for (int w = 0; w < 4; ++w) out += mass_sh[w][t - 64] + mass_sh[w][t - 32]; // wave 0 first, parity 0 before parity 1
+        }
+        pout[NT * 1024 + t] = out;
+    }
+}
+
+// out[i] = w[floor(i N / ns)]: the weights of the rows k_cluster_sample gathers
+__global__ void k_cluster_sample_w(const float *__restrict__ w, int64_t N, int64_t ns, float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < ns) out[i] = w[i * N / ns];
+}
+
+template <int CW, bool NORM>
+static int launch_cluster_nw(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, unsigned k, const float *d_operand,
+                             const float *d_weight, const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, unsigned *nblk_out)
+{
+    if (*per_cu <= 0) {
+        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (k_graph_cluster_nw<CW, NORM>), 256, 0));
+        *per_cu = std::max(1, *per_cu);
+    }
+    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
+    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident);
+    GLF_TRY(part.alloc(ctx, (size_t)nblk * gc_nw_part_cols(CW)));
+    hipLaunchKernelGGL((k_graph_cluster_nw<CW, NORM>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)ld, (int)k, d_operand, d_weight,
+                       d_prev, d_labels, part.p);
+    GLF_LAUNCH_CHECK(ctx);
+    *nblk_out = (unsigned)nblk;
+    return GLF_OK;
+}
+
+static bool embed_plain(const glf_cluster_embed *emb) { return !emb || (emb->normalize == 0 && !emb->d_weight); }
+static bool embed_ok(const glf_cluster_embed *emb)
+{
+    return !emb || (emb->struct_size == sizeof(glf_cluster_embed) && (emb->normalize == 0 || emb->normalize == 1));
+}
+
+// one Lloyd iteration with unit-length rows and / or a weight plane, on checked arguments (returns with the stream drained)
+static int cluster_step_nw(glf_graph *g, int normalize, const float *d_weight, unsigned k, unsigned dim, const double *h_cent, const double *scale,
+                           const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
+{
+    glf_ctx *ctx = g->ctx;
+    const unsigned ld = g->ld;
+    const int cw = gc_cw(ld);
+    const int64_t N = (int64_t)g->width * g->height;
+    std::vector<float> h_op(gc_nw_operand_floats(cw), 0.f);
+    for (unsigned j = 0; j < k; ++j) {
+        double n2 = 0.0;
+        for (unsigned c = 0; c < dim; ++c) {
+            const double x = h_cent[(size_t)j * dim + c];
+            h_op[(size_t)c * GC_K + j] = (float)((scale ? scale[c] : 1.0) * x);
+            n2 += x * x;
+        }
+        h_op[(size_t)cw * GC_K + j] = (float)n2;
+    }
+    for (unsigned c = 0; c < dim; ++c) h_op[gc_operand_floats(cw) + c] = (float)(scale ? scale[c] : 1.0);
+    DevBuf<float> op;
+    DevBuf<double> part, tot;
+    GLF_TRY(op.alloc(ctx, h_op.size()));
+    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    unsigned nblk = 0;
+    int *per_cu = &g->cluster_nw_blocks_per_cu[normalize ? 1 : 0];
+    if (cw == 32 && normalize) GLF_TRY((launch_cluster_nw<32, true>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
+    else if (cw == 32) GLF_TRY((launch_cluster_nw<32, false>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
+    else if (normalize) GLF_TRY((launch_cluster_nw<64, true>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
+    else GLF_TRY((launch_cluster_nw<64, false>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
+    const size_t ncols = gc_nw_part_cols(cw);
+    GLF_TRY(tot.alloc(ctx, ncols));
+    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
+    GLF_LAUNCH_CHECK(ctx);
+    std::vector<double> h_tot(ncols);
+    GLF_HIP(ctx, hipMemcpyAsync(h_tot.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration)
+    const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
+    for (unsigned j = 0; j < k; ++j) {
+        for (unsigned c = 0; c < dim; ++c) h_sums[(size_t)j * dim + c] = h_tot[(size_t)(c / 32) * 1024 + j * 32 + c % 32];
+        h_counts[j] = (uint64_t)tail[j];
+        h_mass[j] = tail[64 + j];
+    }
+    *changed = d_prev ? (uint64_t)tail[32] : 0;
+    return GLF_OK;
+}
+
 } // namespace glf
 
 using namespace glf;
@@ -352,6 +641,111 @@ int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_l
         stats->changed_last = changed;
         for (int j = 0; j < GC_K; ++j) stats->counts[j] = j < (int)k ? counts[j] : 0;
     }
+    return GLF_OK;
+}
+
+int glf_graph_cluster_step_ex(glf_graph *g, const glf_cluster_embed *emb, unsigned k, unsigned dim, const double *h_cent, const double *scale,
+                              const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
+{
+    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !h_mass || !changed) return GLF_ERR_INVALID;
+    if (!embed_ok(emb))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: struct_size=%u (want %zu) normalize=%d", emb->struct_size,
+                         sizeof(glf_cluster_embed), emb->normalize);
+    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k,
+                         dim, g->m);
+    GLF_ENTER(g->ctx);
+    if (embed_plain(emb)) {
+        GLF_TRY(cluster_step(g, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, changed));
+        for (unsigned j = 0; j < k; ++j) h_mass[j] = (double)h_counts[j];
+        return GLF_OK;
+    }
+    return cluster_step_nw(g, emb->normalize, emb->d_weight, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, h_mass, changed);
+}
+
+int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels, double *h_cent,
+                         glf_segment_stats *stats, double *h_mass)
+{
+    if (!g || !opt || !d_labels || !h_cent || opt->struct_size != sizeof(glf_segment_options)) return GLF_ERR_INVALID;
+    glf_ctx *ctx = g->ctx;
+    if (!embed_ok(emb))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment_ex: struct_size=%u (want %zu) normalize=%d", emb->struct_size, sizeof(glf_cluster_embed),
+                         emb->normalize);
+    if (embed_plain(emb)) {
+        glf_segment_stats st;
+        const int rc = glf_graph_segment(g, opt, d_labels, h_cent, &st);
+        if (rc != GLF_OK) return rc;
+        if (stats) *stats = st;
+        for (unsigned j = 0; h_mass && j < opt->k; ++j) h_mass[j] = (double)st.counts[j];
+        return GLF_OK;
+    }
+    const unsigned k = opt->k, dim = opt->dim;
+    const double *scale = opt->scale;
+    const int normalize = emb->normalize;
+    const float *d_weight = emb->d_weight;
+    if (!cluster_shape_ok(g, k, dim, scale) || (opt->init != 0 && opt->init != 1) || (opt->init == 1 && !all_finite(h_cent, (size_t)k * dim)))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment_ex: k=%u dim=%u (m=%u) init=%d, or a centroid or scale entry that is not finite", k,
+                         dim, g->m, opt->init);
+    const unsigned max_iter = opt->max_iter ? opt->max_iter : 50;
+    const int64_t N = (int64_t)g->width * g->height;
+    GLF_ENTER(ctx);
+    std::vector<double> cent((size_t)k * dim);
+    if (opt->init == 0) {
+        const int64_t ns = std::min<int64_t>(opt->sample_rows ? opt->sample_rows : 4096, N);
+        const size_t cnt = (size_t)ns * dim;
+        DevBuf<float> d_rows, d_ws;
+        GLF_TRY(d_rows.alloc(ctx, cnt));
+        hipLaunchKernelGGL(k_cluster_sample, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, ns, (int)dim,
+                           d_rows.p);
+        GLF_LAUNCH_CHECK(ctx);
+        std::vector<float> h_rows(cnt), h_ws;
+        GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
+        if (d_weight) {
+            GLF_TRY(d_ws.alloc(ctx, (size_t)ns));
+            hipLaunchKernelGGL(k_cluster_sample_w, dim3((unsigned)ceil_div(ns, 256)), dim3(256), 0, ctx->stream, d_weight, N, ns, d_ws.p);
+            GLF_LAUNCH_CHECK(ctx);
+            h_ws.resize((size_t)ns);
+            GLF_HIP(ctx, hipMemcpyAsync(h_ws.data(), d_ws.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        std::vector<double> rows(cnt), ws(h_ws.begin(), h_ws.end());
+        for (int64_t i = 0; i < ns; ++i) {
+            double *row = rows.data() + (size_t)i * dim;
+            double n2 = 0.0;
+            for (unsigned c = 0; c < dim; ++c) {
+                row[c] = (scale ? scale[c] : 1.0) * (double)h_rows[(size_t)i * dim + c];
+                n2 += row[c] * row[c];
+            }
+            const double rinv = !normalize ? 1.0 : n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
+            for (unsigned c = 0; normalize && c < dim; ++c) row[c] *= rinv;
+        }
+        if (glf_cluster_seed_w(rows.data(), d_weight ? ws.data() : nullptr, (size_t)ns, dim, k, opt->seed, cent.data()) != GLF_OK)
+            return set_error(ctx, GLF_ERR_INVALID,
+                             "glf_graph_segment_ex: the sample of %lld rows holds fewer than %u distinct rows of positive weight, or a weight that is "
+                             "negative or not finite",
+                             (long long)ns, k);
+    } else
+        std::copy(h_cent, h_cent + (size_t)k * dim, cent.begin());
+    std::vector<double> sums((size_t)k * dim);
+    uint64_t counts[GC_K] = {0}, changed = 0;
+    double mass[GC_K] = {0.0};
+    unsigned it = 0;
+    int converged = 0;
+    while (it < max_iter && !converged) {
+        GLF_TRY(cluster_step_nw(g, normalize, d_weight, k, dim, cent.data(), scale, it ? d_labels : nullptr, d_labels, sums.data(), counts, mass,
+                                &changed));
+        converged = it > 0 && changed == 0;
+        ++it;
+        GLF_TRY(glf_cluster_update_w(k, dim, scale, sums.data(), mass, cent.data(), cent.data()));
+    }
+    std::copy(cent.begin(), cent.end(), h_cent);
+    if (stats) {
+        stats->iterations = it;
+        stats->converged = converged;
+        stats->changed_last = changed;
+        for (int j = 0; j < GC_K; ++j) stats->counts[j] = j < (int)k ? counts[j] : 0;
+    }
+    if (h_mass) std::copy(mass, mass + k, h_mass);
     return GLF_OK;
 }
 

@@ -1,6 +1,6 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
-// synthetic benchmark images, the geometry and schedule of the band form, the centroid update and
-// the seeding of the spectral segmentation. No device code.
+// synthetic benchmark images, the geometry and schedule of the band form, the centroid updates and
+// the seedings (plain and weighted) of the spectral segmentation. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -249,6 +249,69 @@ int glf_cluster_seed(const double *rows, size_t n, unsigned dim, unsigned k, uin
         if (pick == n) // (run ends at total > target; unreachable, kept so that no index leaves the rows)
             for (pick = n - 1; pick > 0 && !(d2[pick] > 0.0);) --pick;
         chosen[t] = pick;
+    }
+    for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
+    return GLF_OK;
+}
+
+// glf_cluster_update with a mass in place of the count: the weighted mean of a label's rows.
+int glf_cluster_update_w(unsigned k, unsigned dim, const double *scale, const double *sums, const double *mass, const double *cent_prev,
+                         double *cent)
+{
+    if (!sums || !mass || !cent || k == 0 || dim == 0) return GLF_ERR_INVALID;
+    if (!cent_prev)
+        for (unsigned j = 0; j < k; ++j)
+            if (!(mass[j] > 0.0)) return GLF_ERR_INVALID;
+    for (unsigned j = 0; j < k; ++j)
+        for (unsigned c = 0; c < dim; ++c) {
+            const size_t e = (size_t)j * dim + c;
+            cent[e] = mass[j] > 0.0 ? (scale ? scale[c] : 1.0) * sums[e] / mass[j] : cent_prev[e];
+        }
+    return GLF_OK;
+}
+
+// glf_cluster_seed with every row's chance multiplied by its weight.
+int glf_cluster_seed_w(const double *rows, const double *w, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
+{
+    if (!w) return glf_cluster_seed(rows, n, dim, k, seed, cent);
+    if (!rows || !cent || n == 0 || dim == 0 || k == 0 || k > n) return GLF_ERR_INVALID;
+    double wtotal = 0.0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return GLF_ERR_INVALID;
+        wtotal += w[i];
+    }
+    if (!(wtotal > 0.0) || !std::isfinite(wtotal)) return GLF_ERR_INVALID;
+    Xoshiro256ss rng(seed);
+    std::vector<size_t> chosen(k);
+    std::vector<double> d2(n);
+    // the first row, in row order, whose running sum of wd exceeds u times total (total > 0: some wd[i] > 0)
+    auto draw = [&](auto wd, double total) {
+        const double target = rng.uniform() * total;
+        size_t pick = n;
+        double run = 0.0;
+        for (size_t i = 0; i < n && pick == n; ++i) {
+            run += wd(i);
+            if (run > target) pick = i;
+        }
+        if (pick == n) // (run ends at total > target; unreachable, kept so that no index leaves the rows)
+            for (pick = n - 1; pick > 0 && !(wd(pick) > 0.0);) --pick;
+        return pick;
+    };
+    chosen[0] = draw([&](size_t i) { return w[i]; }, wtotal);
+    for (unsigned t = 1; t < k; ++t) {
+        const double *c = rows + chosen[t - 1] * dim;
+        double total = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            double d = 0.0;
+            for (unsigned q = 0; q < dim; ++q) {
+                const double x = rows[i * dim + q] - c[q];
+                d += x * x;
+            }
+            d2[i] = t == 1 ? d : std::min(d2[i], d);
+            total += w[i] * d2[i];
+        }
+        if (!(total > 0.0) || !std::isfinite(total)) return GLF_ERR_INVALID; // fewer than k distinct rows of positive weight (or a NaN / Inf)
+        chosen[t] = draw([&](size_t i) { return w[i] * d2[i]; }, total);
     }
     for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
     return GLF_OK;

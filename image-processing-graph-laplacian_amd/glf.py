@@ -64,6 +64,7 @@ EXPORTS = [
     "glf_graph_build", "glf_graph_destroy", "glf_graph_get_info", "glf_graph_eigenvalues", "glf_graph_gram", "glf_graph_project",
     "glf_graph_synthesize", "glf_filter_coeffs", "glf_graph_normal_equations", "glf_fit_coeffs",
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
+    "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
@@ -135,6 +136,10 @@ class SegmentStats(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("converged", C.c_int32), ("changed_last", C.c_uint64), ("counts", C.c_uint64 * CLUSTER_MAX)]
 
 
+class ClusterEmbed(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("normalize", C.c_int32), ("d_weight", C.c_void_p)]
+
+
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHER_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -168,6 +173,11 @@ _lib.glf_graph_cluster_step.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void
 _lib.glf_cluster_update.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_cluster_seed.argtypes = [C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
 _lib.glf_graph_segment.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_cluster_step_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_cluster_update_w.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_cluster_seed_w.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
+_lib.glf_graph_segment_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -421,6 +431,47 @@ def cluster_update(sums, counts, scale=None, cent_prev=None):
     rc = _lib.glf_cluster_update(C.c_uint(k), C.c_uint(dim), _ptr(scale), _ptr(sums), _ptr(counts), _ptr(cent_prev), _ptr(cent))
     if rc != OK:
         raise GlfError(rc, "glf_cluster_update(k=%d, dim=%d): an empty cluster without cent_prev, or an empty shape" % (k, dim))
+    return cent
+
+
+def cluster_update_w(sums, mass, scale=None, cent_prev=None):
+    """glf_cluster_update_w (host only): cent_j = scale o sums_j / mass_j, the weighted mean of one Lloyd iteration under a weight
+    plane; a cluster with !(mass_j > 0) keeps cent_prev_j. sums [k, dim], mass [k] floats, scale [dim] or None (= 1), cent_prev
+    [k, dim] (may be None when every mass is positive) -> cent [k, dim]."""
+    sums = np.ascontiguousarray(sums, dtype=np.float64)
+    mass = np.ascontiguousarray(mass, dtype=np.float64)
+    if sums.ndim != 2 or mass.shape != (sums.shape[0],):
+        raise ValueError("cluster_update_w: sums %s, mass %s" % (sums.shape, mass.shape))
+    k, dim = sums.shape
+    scale = _scale(scale, dim)
+    if cent_prev is not None:
+        cent_prev = np.ascontiguousarray(cent_prev, dtype=np.float64)
+        if cent_prev.shape != (k, dim):
+            raise ValueError("cluster_update_w: cent_prev must be [%d, %d]" % (k, dim))
+    cent = np.zeros((k, dim), dtype=np.float64)
+    rc = _lib.glf_cluster_update_w(C.c_uint(k), C.c_uint(dim), _ptr(scale), _ptr(sums), _ptr(mass), _ptr(cent_prev), _ptr(cent))
+    if rc != OK:
+        raise GlfError(rc, "glf_cluster_update_w(k=%d, dim=%d): a cluster of mass 0 without cent_prev, or an empty shape" % (k, dim))
+    return cent
+
+
+def cluster_seed_w(rows, weight, k, seed=1):
+    """glf_cluster_seed_w (host only): k-means++ among rows [n, dim] with probability proportional to weight * D^2, on the uniforms of
+    cluster_seed; the first centre is the first row whose running sum of the weights exceeds u_0 times their total. weight [n]
+    (>= 0, finite), or None for cluster_seed itself -> cent [k, dim]."""
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.ndim != 2:
+        raise ValueError("cluster_seed_w: rows must be [n, dim], got %s" % (rows.shape,))
+    n, dim = rows.shape
+    if weight is not None:
+        weight = np.ascontiguousarray(weight, dtype=np.float64)
+        if weight.shape != (n,):
+            raise ValueError("cluster_seed_w: weight must be [%d], got %s" % (n, weight.shape))
+    cent = np.zeros((max(int(k), 0), dim), dtype=np.float64)
+    rc = _lib.glf_cluster_seed_w(_ptr(rows), _ptr(weight), C.c_size_t(n), C.c_uint(dim), C.c_uint(k), C.c_uint64(seed), _ptr(cent))
+    if rc != OK:
+        raise GlfError(rc, "glf_cluster_seed_w(n=%d, dim=%d, k=%d): fewer than k distinct rows of positive weight, a weight that is negative "
+                           "or not finite, or an empty shape" % (n, dim, k))
     return cent
 
 
@@ -1412,11 +1463,37 @@ class Graph:
                                                     _ptr(sums), _ptr(counts), C.byref(changed)), "graph cluster step")   # (returns with the stream drained)
         return labels, sums, counts, int(changed.value)
 
-    def segment(self, k, dim=None, scale=None, init=None, seed=1, max_iter=50, sample_rows=4096):
+    def _embed(self, normalize, weight):
+        if weight is not None:
+            weight = self._weight(weight)
+        return ClusterEmbed(C.sizeof(ClusterEmbed), int(bool(normalize)), weight.data_ptr() if weight is not None else None)
+
+    def cluster_step_ex(self, cent, scale=None, prev=None, labels=None, normalize=False, weight=None):
+        """cluster_step under an embedding (glf_graph_cluster_step_ex). normalize: unit-length rows, e(px) = scale o Phi[px][:dim]
+        divided by its length (a row of length 0 stays at the origin); cent is then in that embedding. weight: device float32 [H, W]
+        or None (= 1), not checked for sign, NaN or Inf; it enters the update only, every pixel is labelled.
+        -> (labels, sums [k, dim] = sum of weight / length times the raw rows of Phi per label, counts uint64 [k] (pixels),
+        mass [k] = sum of the weights per label, changed (pixels)). With neither set every output has cluster_step's bits."""
+        cent = np.ascontiguousarray(np.atleast_2d(np.asarray(cent, dtype=np.float64)))
+        k, dim = cent.shape
+        scale = _scale(scale, dim)
+        emb = self._embed(normalize, weight)
+        if prev is not None:
+            prev = self._labels(prev, "prev")
+        labels = self._new_labels() if labels is None else self._labels(labels, "labels")
+        sums, counts, mass, changed = np.zeros((k, dim), dtype=np.float64), np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.float64), C.c_uint64(0)
+        self.ctx._check(_lib.glf_graph_cluster_step_ex(self._g, C.byref(emb), C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale),
+                                                       C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(labels.data_ptr()),
+                                                       _ptr(sums), _ptr(counts), _ptr(mass), C.byref(changed)), "graph cluster step")
+        return labels, sums, counts, mass, int(changed.value)
+
+    def segment(self, k, dim=None, scale=None, init=None, seed=1, max_iter=50, sample_rows=4096, normalize=False, weight=None):
         """Spectral segmentation (glf_graph_segment): Lloyd's k-means over the embedded rows, cluster_step + cluster_update until a
         step moves no label or max_iter steps ran. dim defaults to min(m, 64, max(k, 2)): the usual k vectors for k segments. init:
         centroids [k, dim] in embedding space, or None for k-means++ seeding (cluster_seed with `seed`) among the sample_rows rows
-        floor(i N / n_s) of Phi. -> (labels device int32 [H, W], cent [k, dim], dict(iterations, converged, changed_last, counts))."""
+        floor(i N / n_s) of Phi. -> (labels device int32 [H, W], cent [k, dim], dict(iterations, converged, changed_last, counts)).
+        With normalize (unit-length rows: use dim = m with it) or weight (device float32 [H, W]) set, glf_graph_segment_ex:
+        cluster_step_ex + cluster_update_w, seeding by cluster_seed_w on the normalised sample; the dict then also holds mass [k]."""
         if dim is None:
             dim = min(self.info["m"], 64, max(int(k), 2))
         cent = np.zeros((max(int(k), 0), max(int(dim), 0)), dtype=np.float64)
@@ -1430,6 +1507,13 @@ class Graph:
         opt = SegmentOptions(C.sizeof(SegmentOptions), k, dim, max_iter, sample_rows, 0 if init is None else 1, seed,
                              scale.ctypes.data if scale is not None else None)
         st = SegmentStats()
+        if normalize or weight is not None:
+            emb = self._embed(normalize, weight)
+            mass = np.zeros(max(int(k), 0), dtype=np.float64)
+            self.ctx._check(_lib.glf_graph_segment_ex(self._g, C.byref(opt), C.byref(emb), C.c_void_p(labels.data_ptr()), _ptr(cent), C.byref(st),
+                                                      _ptr(mass)), "graph segment")
+            return labels, cent, dict(iterations=int(st.iterations), converged=int(st.converged), changed_last=int(st.changed_last),
+                                      counts=np.array(st.counts[:int(k)], dtype=np.uint64), mass=mass)
         self.ctx._check(_lib.glf_graph_segment(self._g, C.byref(opt), C.c_void_p(labels.data_ptr()), _ptr(cent), C.byref(st)), "graph segment")
         return labels, cent, dict(iterations=int(st.iterations), converged=int(st.converged), changed_last=int(st.changed_last),
                                   counts=np.array(st.counts[:int(k)], dtype=np.uint64))

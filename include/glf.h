@@ -624,9 +624,17 @@ int glf_fit_coeffs(unsigned m, const double *G, const double *penalty, int nrhs,
  * Phi (MFMA with the pixels as the contraction index and an exact 0/1 indicator operand, f32 chains of at most GLF_GRAPH_NORMAL_CHAIN
  * pixel terms added into f64), the member counts and the number of labels that moved (exact integers). No atomics; the pixel
  * partition depends on (N, ld) and the device alone: two calls give the same bits. Only the first 32 (ld 32) or 64 (ld >= 64) columns
- * of a row are read, whatever ld is. Out of scope: row-normalised (Ng-Jordan-Weiss) embeddings; per-pixel weights; more than 64
- * embedding columns; k > GLF_CLUSTER_MAX; contexts with a communicator and glf_multi_* (handles refuse them); a flag of the
- * image_processing host program; k_band, k_graph_synthesize and k_graph_normal, which are untouched. */
+ * of a row are read, whatever ld is.
+ * Unit-length rows and per-pixel weights (the _ex / _w entry points below, k_graph_cluster_nw): with glf_cluster_embed.normalize the
+ * embedding is e(px) = rinv(px) scale o Phi[px][0..dim), rinv = 1 / |scale o Phi[px][0..dim)| formed in f32 in a fixed order (a row
+ * of length 0 keeps rinv = 0 and embeds at the origin) -- the row-normalised embedding of Ng, Jordan and Weiss, which is what the
+ * Nystroem segmentation paper clusters; without it rinv = 1. A weight plane w (device float [N], NULL = 1; not checked for sign, NaN
+ * or Inf: glf_graph_normal_equations' rule) enters the update only: every pixel is labelled, a pixel of weight 0 included, sums_j =
+ * sum over the members of j of w rinv Phi[px][c] (raw columns; the caller applies scale), mass_j = sum of w in f64, counts_j and
+ * changed count pixels, and the centroid is scale o sums_j / mass_j, a cluster of mass 0 keeping its previous centroid.
+ * Out of scope: spherical k-means (renormalised centroids); a margin or confidence output; more than 64 embedding columns;
+ * k > GLF_CLUSTER_MAX; contexts with a communicator and glf_multi_* (handles refuse them); a flag of the image_processing host
+ * program; k_band, k_graph_synthesize and k_graph_normal, which are untouched. */
 #define GLF_CLUSTER_MAX 32
 /* One Lloyd iteration. h_cent HOST [k][dim] (embedding space), scale HOST [dim] or NULL (= 1). d_labels device int32 [N], written;
  * d_prev device int32 [N] or NULL, may be d_labels itself (in place). h_sums HOST [k][dim] = the sum of the raw rows of Phi per label
@@ -668,6 +676,36 @@ typedef struct glf_segment_stats {
 } glf_segment_stats;
 int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_labels, double *h_cent /* HOST [k][dim]: in (init 1) / out */,
                       glf_segment_stats *stats /* or NULL */);
+/* The embedding of the _ex calls. NULL, or {normalize 0, d_weight NULL}, is the plain embedding: the call then runs k_graph_cluster
+ * itself and every output has the bits of the plain call's. */
+typedef struct glf_cluster_embed {
+    uint32_t struct_size;   /* sizeof(glf_cluster_embed), set by the caller */
+    int32_t normalize;      /* 0 | 1: unit-length rows */
+    const float *d_weight;  /* device float [N] or NULL (w = 1) */
+} glf_cluster_embed;
+/* glf_graph_cluster_step under an embedding. h_sums = sum of w rinv Phi[px][c] per label, h_mass HOST double [k] = sum of w per label
+ * (with a plain emb, (double) h_counts), h_counts and *changed count pixels. Refusals as for glf_graph_cluster_step, and an
+ * emb->struct_size that is not sizeof(glf_cluster_embed), a normalize other than 0 / 1, a NULL h_mass: all before any device work,
+ * d_labels untouched. Two calls give the same bits. */
+int glf_graph_cluster_step_ex(glf_graph *g, const glf_cluster_embed *emb, unsigned k, unsigned dim, const double *h_cent, const double *scale,
+                              const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass /* HOST [k] */,
+                              uint64_t *changed);
+/* Host only: cent_j = scale o sums_j / mass_j; a cluster that is empty, !(mass_j > 0), keeps cent_prev_j. Refusals as for
+ * glf_cluster_update (NULL sums / mass / cent, k = 0, dim = 0, an empty cluster without cent_prev), cent untouched. */
+int glf_cluster_update_w(unsigned k, unsigned dim, const double *scale, const double *sums, const double *mass, const double *cent_prev,
+                         double *cent);
+/* Host only: k-means++ with probability proportional to w D^2, on the same uniforms as glf_cluster_seed. The first centre is the first
+ * row whose running sum of w exceeds u_0 times the total of w; centre t the first row whose running sum of w D^2 exceeds u_t times its
+ * total. w HOST [n], or NULL: glf_cluster_seed itself, bit for bit. Refusals as for glf_cluster_seed, and a w that is negative or not
+ * finite, or a total (of w, or of w D^2) that is not positive; cent is then untouched. */
+int glf_cluster_seed_w(const double *rows, const double *w /* [n] or NULL */, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent);
+/* glf_graph_segment under an embedding; with a plain emb it is glf_graph_segment. Otherwise init 0 gathers the sample rows (and the
+ * sample's weights when a plane is given), scales them, normalises them on the host in f64 when asked and seeds with
+ * glf_cluster_seed_w; init 1 takes h_cent as it is (embedding space: unit rows when normalize is set). Then glf_graph_cluster_step_ex +
+ * glf_cluster_update_w under glf_graph_segment's convergence rule, one read-back per iteration. h_mass: the last step's, or NULL.
+ * Refusals as for glf_graph_segment and glf_graph_cluster_step_ex. */
+int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels, double *h_cent,
+                         glf_segment_stats *stats /* or NULL */, double *h_mass /* HOST [k] or NULL */);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
