@@ -12,7 +12,7 @@ CFLAGS   ?= -O2 -std=gnu11 -Wall -Wextra -fPIC
 HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystroem.hip \
             $(CSRC)/filter.hip $(CSRC)/pipeline.hip $(CSRC)/comm.hip $(CSRC)/nlm.hip $(CSRC)/balance.hip \
             $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip \
-            $(CSRC)/graph_cluster.hip
+            $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
 C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
@@ -47,8 +47,14 @@ cluster_check: tools/cluster_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_pl
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/cluster_host_check $(filter %.cpp,$^)
 	tools/cluster_host_check
 
+# the host-only change of basis (Cholesky and Ritz modes, the refusals) under the address and undefined-behaviour sanitizers (CPU only)
+BASIS_CHECK_BIN ?= tools/basis_host_check
+basis_check: tools/basis_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp include/glf.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o $(BASIS_CHECK_BIN) $(filter %.cpp,$^)
+	$(BASIS_CHECK_BIN)
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean pfm_check cluster_check
+.PHONY: all oracle clean pfm_check cluster_check basis_check

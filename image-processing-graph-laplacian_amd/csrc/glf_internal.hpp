@@ -111,6 +111,7 @@ struct glf_graph {
     int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
     int cluster_blocks_per_cu = 0; // k_graph_cluster<CW>'s, asked at the first cluster step
     int cluster_nw_blocks_per_cu[2] = {0, 0}; // k_graph_cluster_nw<CW, NORM>'s at [NORM], asked at the first such step
+    int transform_blocks_per_cu = 0; // k_graph_transform<ld>'s, asked at the first transform
 };
 
 namespace glf {

@@ -1,6 +1,7 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
 // synthetic benchmark images, the geometry and schedule of the band form, the centroid updates and
-// the seedings (plain and weighted) of the spectral segmentation. No device code.
+// the seedings (plain and weighted) of the spectral segmentation, the orthonormal change of basis of a
+// graph handle from its Gram matrix. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -314,6 +315,115 @@ int glf_cluster_seed_w(const double *rows, const double *w, size_t n, unsigned d
         chosen[t] = draw([&](size_t i) { return w[i] * d2[i]; }, total);
     }
     for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
+    return GLF_OK;
+}
+
+// The change of basis that makes Phi orthonormal, from its Gram matrix alone (the one-shot orthogonalisation of Fowlkes, Belongie,
+// Chung and Malik, restated on Phi): G = L L^T, Q = Phi L^-T has orthonormal columns, and Phi diag(1 - lam) Phi^T = Q S Q^T with
+// S = L^T diag(1 - lam) L. With S = U Theta U^T (cyclic Jacobi), Phi T with T = L^-T U is an orthonormal eigenbasis of the same
+// operator with the eigenvalues 1 - theta. Everything is sequential f64 in a fixed order: two calls give the same bits.
+int glf_basis_orthonormal(unsigned m, const double *G, const double *lam, double *T, double *lam_new)
+{
+    if (!G || !T || m == 0 || (lam && !lam_new)) return GLF_ERR_INVALID;
+    const size_t n = m;
+    for (size_t e = 0; e < n * n; ++e)
+        if (!std::isfinite(G[e])) return GLF_ERR_INVALID;
+    for (size_t i = 0; lam && i < n; ++i)
+        if (!std::isfinite(lam[i])) return GLF_ERR_INVALID;
+    // L L^T = G, row by row from G's lower triangle (glf_fit_coeffs' factorisation)
+    std::vector<double> L(n * n, 0.0), Li(n * n, 0.0);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = 0; j <= i; ++j) {
+            double s = G[i * n + j];
+            for (size_t k = 0; k < j; ++k) s -= L[i * n + k] * L[j * n + k];
+            if (i == j) {
+                if (!(s > 0.0)) return GLF_ERR_INVALID;
+                L[i * n + i] = std::sqrt(s);
+            } else
+                L[i * n + j] = s / L[j * n + j];
+        }
+    // Li = L^-1 (lower triangular), column by column: L Li = I
+    for (size_t c = 0; c < n; ++c)
+        for (size_t i = c; i < n; ++i) {
+            double s = i == c ? 1.0 : 0.0;
+            for (size_t k = c; k < i; ++k) s -= L[i * n + k] * Li[k * n + c];
+            Li[i * n + c] = s / L[i * n + i];
+        }
+    std::vector<double> out(n * n, 0.0);
+    if (!lam) {
+        for (size_t k = 0; k < n; ++k)
+            for (size_t j = k; j < n; ++j) out[k * n + j] = Li[j * n + k]; // L^-T
+        std::copy(out.begin(), out.end(), T);
+        return GLF_OK;
+    }
+    // S = L^T diag(1 - lam) L: the upper triangle, mirrored. Ut is U^T: a rotation then works on two rows of each matrix
+    std::vector<double> S(n * n, 0.0), Ut(n * n, 0.0);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t j = i; j < n; ++j) {
+            double s = 0.0;
+            for (size_t k = j; k < n; ++k) s += L[k * n + i] * (1.0 - lam[k]) * L[k * n + j];
+            S[i * n + j] = S[j * n + i] = s;
+        }
+    for (size_t i = 0; i < n; ++i) Ut[i * n + i] = 1.0;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double off = 0.0, diag = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            diag += S[i * n + i] * S[i * n + i];
+            for (size_t j = i + 1; j < n; ++j) off += S[i * n + j] * S[i * n + j];
+        }
+        if (off <= 1e-32 * diag) break;
+        for (size_t p = 0; p + 1 < n; ++p)
+            for (size_t q = p + 1; q < n; ++q) {
+                const double apq = S[p * n + q];
+                if (apq == 0.0) continue;
+                const double app = S[p * n + p], aqq = S[q * n + q];
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double c = 1.0 / std::sqrt(t * t + 1.0), s = t * c;
+                // S <- J^T S J: rows p and q (contiguous), the columns as their mirror, the 2 x 2 block in closed form
+                double *sp = S.data() + p * n, *sq = S.data() + q * n;
+                for (size_t k = 0; k < n; ++k) {
+                    const double spk = sp[k], sqk = sq[k];
+                    sp[k] = c * spk - s * sqk;
+                    sq[k] = s * spk + c * sqk;
+                }
+                for (size_t k = 0; k < n; ++k) {
+                    S[k * n + p] = sp[k];
+                    S[k * n + q] = sq[k];
+                }
+                sp[p] = app - t * apq;
+                sq[q] = aqq + t * apq;
+                sp[q] = sq[p] = 0.0;
+                double *up = Ut.data() + p * n, *uq = Ut.data() + q * n;
+                for (size_t k = 0; k < n; ++k) {
+                    const double upk = up[k], uqk = uq[k];
+                    up[k] = c * upk - s * uqk;
+                    uq[k] = s * upk + c * uqk;
+                }
+            }
+    }
+    // theta descending, the lower original index first on a tie
+    std::vector<size_t> order(n);
+    for (size_t i = 0; i < n; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return S[a * n + a] > S[b * n + b]; });
+    for (size_t j = 0; j < n; ++j) {
+        const size_t col = order[j];
+        // sign: the entry of largest magnitude of the column of U is positive, the lowest index on a tie
+        double big = 0.0;
+        const double *u = Ut.data() + col * n;
+        for (size_t i = 0; i < n; ++i)
+            if (std::fabs(u[i]) > std::fabs(big)) big = u[i];
+        const double sign = big < 0.0 ? -1.0 : 1.0;
+        for (size_t k = 0; k < n; ++k) { // T = L^-T U
+            double s = 0.0;
+            for (size_t i = k; i < n; ++i) s += Li[i * n + k] * u[i];
+            out[k * n + j] = sign * s;
+        }
+    }
+    for (size_t e = 0; e < n * n; ++e)
+        if (!std::isfinite(out[e])) return GLF_ERR_INVALID; // (a lam near the f64 range: nothing was written)
+    std::copy(out.begin(), out.end(), T);
+    for (size_t j = 0; j < n; ++j) lam_new[j] = 1.0 - S[order[j] * n + order[j]];
     return GLF_OK;
 }
 

@@ -65,12 +65,14 @@ EXPORTS = [
     "glf_graph_synthesize", "glf_filter_coeffs", "glf_graph_normal_equations", "glf_fit_coeffs",
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
+    "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
 GRAPH_MAX_OUTPUTS = 32
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
+BASIS_CHOLESKY, BASIS_RITZ = 0, 1
 
 
 class Mat(C.Structure):
@@ -140,6 +142,10 @@ class ClusterEmbed(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("normalize", C.c_int32), ("d_weight", C.c_void_p)]
 
 
+class BasisStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("defect_in", C.c_double), ("defect_out", C.c_double)]
+
+
 ALLREDUCE_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLREDUCE_F64 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 ALLGATHER_F32 = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -178,6 +184,9 @@ _lib.glf_graph_cluster_step_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c
 _lib.glf_cluster_update_w.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_cluster_seed_w.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
 _lib.glf_graph_segment_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_transform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+_lib.glf_basis_orthonormal.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_orthonormalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -402,6 +411,28 @@ def fit_coeffs(G, b, penalty=None):
     if rc != OK:
         raise GlfError(rc, "glf_fit_coeffs(m=%d): not positive definite, or an empty system" % m)
     return a.reshape(np.shape(b))
+
+
+def basis_orthonormal(G, lam=None):
+    """glf_basis_orthonormal (host only): the change of basis T [m, m] that makes a basis with the Gram matrix G [m, m] orthonormal,
+    T^T G T = I. lam None: T = L^-T of the Cholesky factor G = L L^T (upper triangular: Gram-Schmidt in column order) -> T.
+    lam [m]: the Ritz basis of Phi diag(1 - lam) Phi^T, T = L^-T U with L^T diag(1 - lam) L = U Theta U^T -> (T, lam_new),
+    lam_new = 1 - theta ascending, T diag(1 - lam_new) T^T = diag(1 - lam). Two calls give the same bits."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    if G.ndim != 2 or G.shape[0] != G.shape[1]:
+        raise ValueError("G must be [m, m], got %s" % (G.shape,))
+    m = G.shape[0]
+    T = np.zeros((m, m), dtype=np.float64)
+    lam_new = None
+    if lam is not None:
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        if lam.shape != (m,):
+            raise ValueError("lam must be [%d], got %s" % (m, lam.shape))
+        lam_new = np.zeros(m, dtype=np.float64)
+    rc = _lib.glf_basis_orthonormal(C.c_uint(m), _ptr(G), _ptr(lam), _ptr(T), _ptr(lam_new))
+    if rc != OK:
+        raise GlfError(rc, "glf_basis_orthonormal(m=%d): not positive definite, not finite, or empty" % m)
+    return T if lam is None else (T, lam_new)
 
 
 def _scale(scale, dim):
@@ -1317,15 +1348,20 @@ class Graph:
 
     def __init__(self, ctx, handle, st):
         self.ctx, self._g = ctx, handle
-        gi = GraphInfo(struct_size=C.sizeof(GraphInfo))
-        ctx._check(_lib.glf_graph_get_info(handle, C.byref(gi)), "graph info")
-        self.info = dict(pix=gi.pix, width=gi.width, height=gi.height, p=gi.p, m=gi.m, ld=gi.ld, phi_bytes=int(gi.phi_bytes))
-        lam = np.zeros(gi.m, dtype=np.float64)
-        ctx._check(_lib.glf_graph_eigenvalues(handle, _ptr(lam)), "graph eigenvalues")
-        self.eigenvalues = lam
-        self.stats = _info(st, lam)
+        gi = self._refresh()
+        self.stats = _info(st, self.eigenvalues)   # the build call's: a later transform does not rewrite them
         n = gi.width * gi.height
         self.phi = device_tensor_from_ptr(gi.d_phi, n * gi.ld, torch.float32, ctx.device).view(n, gi.ld)   # a view: dies with the handle
+
+    def _refresh(self):
+        """info and eigenvalues from the handle: what the object caches of it (at build time and after every transform)."""
+        gi = GraphInfo(struct_size=C.sizeof(GraphInfo))
+        self.ctx._check(_lib.glf_graph_get_info(self._g, C.byref(gi)), "graph info")
+        self.info = dict(pix=gi.pix, width=gi.width, height=gi.height, p=gi.p, m=gi.m, ld=gi.ld, phi_bytes=int(gi.phi_bytes))
+        lam = np.zeros(gi.m, dtype=np.float64)
+        self.ctx._check(_lib.glf_graph_eigenvalues(self._g, _ptr(lam)), "graph eigenvalues")
+        self.eigenvalues = lam
+        return gi
 
     def close(self):
         if self._g:
@@ -1400,7 +1436,8 @@ class Graph:
         normal_equations, fit_coeffs on the host, one synthesize with no identity term -> device float32 [nplanes, H, W].
         penalty_j = (ridge + smooth * lam_j) * trace(G) / m: relative to the mean diagonal of G, so that smooth and ridge depend on
         neither the scale of w nor Phi's normalisation; penalty [m] (absolute units) overrides both. smooth * lam is the Laplacian
-        energy of Phi a only to the extent that Phi is orthonormal (the extended eigenvectors are not, exactly). With every
+        energy of Phi a only to the extent that Phi is orthonormal (the extended eigenvectors are not, exactly; after orthonormalize()
+        they are, to f32 rounding). With every
         penalty 0 and w = 0 on a set that leaves Phi rank deficient the system is refused (GlfError)."""
         G, b = self.normal_equations(weight, planes)
         if penalty is None:
@@ -1517,6 +1554,36 @@ class Graph:
         self.ctx._check(_lib.glf_graph_segment(self._g, C.byref(opt), C.c_void_p(labels.data_ptr()), _ptr(cent), C.byref(st)), "graph segment")
         return labels, cent, dict(iterations=int(st.iterations), converged=int(st.converged), changed_last=int(st.changed_last),
                                   counts=np.array(st.counts[:int(k)], dtype=np.uint64))
+
+    def transform(self, T, lam):
+        """Phi <- Phi T in place on the device (glf_graph_transform): T [m, m_new], 1 <= m_new <= m, lam [m_new] the eigenvalues of
+        the new columns. The handle's m becomes m_new, columns m_new .. ld of Phi exact zeros, the cached Gram matrix is dropped;
+        info and eigenvalues are refreshed (phi stays the same view; stats stay the build call's). Truncation (T = I[:, :k]), column
+        reordering and rescaling, any rotation."""
+        T = np.ascontiguousarray(np.asarray(T, dtype=np.float64))
+        lam = np.ascontiguousarray(np.asarray(lam, dtype=np.float64))
+        if T.ndim != 2 or T.shape[0] != self.info["m"] or lam.shape != (T.shape[1],):
+            raise ValueError("T must be [%d, m_new] and lam [m_new], got %s and %s" % (self.info["m"], T.shape, lam.shape))
+        t = self.ctx.torch
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the caller's own reads of phi precede the rewrite
+        try:
+            self.ctx._check(_lib.glf_graph_transform(self._g, C.c_uint(T.shape[1]), _ptr(T), _ptr(lam)), "graph transform")   # (drained)
+        finally:
+            self._refresh()
+
+    def orthonormalize(self, mode="ritz", passes=1, verify=False):
+        """glf_graph_orthonormalize: make Phi orthonormal in place. mode "ritz": Phi becomes the orthonormal eigenbasis of the same
+        smoothing operator Phi diag(1 - lam) Phi^T, eigenvalues ascending; "cholesky": Gram-Schmidt in column order, eigenvalues
+        kept. Per pass one normal_equations(None), basis_orthonormal on the host, one transform; a second pass runs in Cholesky
+        mode. -> dict(passes, defect_in = max |Phi^T Phi - I| before, defect_out = the same after when verify, else NaN)."""
+        modes = {"cholesky": BASIS_CHOLESKY, "ritz": BASIS_RITZ}
+        st = BasisStats(struct_size=C.sizeof(BasisStats))
+        try:
+            self.ctx._check(_lib.glf_graph_orthonormalize(self._g, C.c_int(modes.get(mode, -1) if isinstance(mode, str) else int(mode)),
+                                                          C.c_int(passes), C.c_int(bool(verify)), C.byref(st)), "graph orthonormalize")
+        finally:
+            self._refresh()
+        return dict(passes=int(st.passes), defect_in=float(st.defect_in), defect_out=float(st.defect_out))
 
     def apply(self, planes, weights, ident=1.0):
         """Diagonal responses: out[r, k] = ident[r] * s_k + Phi diag(weights[r]) Phi^T s_k for every response r and plane k -- one

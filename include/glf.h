@@ -707,6 +707,50 @@ int glf_cluster_seed_w(const double *rows, const double *w /* [n] or NULL */, si
 int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels, double *h_cent,
                          glf_segment_stats *stats /* or NULL */, double *h_mass /* HOST [k] or NULL */);
 
+/* ---- change of basis on a graph handle: Phi <- Phi T in place, orthonormal Ritz basis -----------------------------------------------
+ * The extended eigenvectors are not orthonormal, and the handle's eigenvalues are not sorted. The handle's own data hold the cure,
+ * the one-shot orthogonalisation of the Nystroem literature (Fowlkes, Belongie, Chung, Malik) restated on Phi alone: with
+ * G = Phi^T Phi = L L^T, Q = Phi L^-T has orthonormal columns and the approximated smoothing operator is W = Phi diag(1 - lam) Phi^T
+ * = Q S Q^T, S = L^T diag(1 - lam) L (m x m). With S = U Theta U^T, Phi' = Phi T, T = L^-T U, is an orthonormal eigenbasis of the
+ * same W with the eigenvalues lam' = 1 - theta, ascending; W itself does not change. On such a handle Phi^T Phi = I (sharpening
+ * needs no Gram matrix), project + synthesize is an orthogonal projector, Graph.fit's smooth penalty is the true energy and "the
+ * leading k columns" are the k smoothest.
+ * The primitive underneath is glf_graph_transform, Phi <- Phi T for any [m][m_new] matrix (k_graph_transform:
+ * v_mfma_f32_32x32x2_f32 with the pixels as the M index, operands Phi and fl32(T) exactly f32, f32 accumulation in
+ * glf_graph_synthesize's contraction order, which depends on ld alone; a column's bits depend neither on m_new nor on the other
+ * columns of T; a wave reads all ld columns of its 32 rows before it stores the first). It also gives truncation to the leading
+ * columns, column reordering and rescaling, and a caller's own rotation (say, the Ritz vectors of a weighted G_w from
+ * glf_graph_normal_equations). Out of scope: contexts with a communicator and glf_multi_* (handles refuse them), m > 256, changing
+ * ld, a flag of the image_processing host program, Rayleigh-Ritz against the true Laplacian (it needs L Phi over all pixels), a
+ * faster glf_graph_gram; k_band, k_graph_synthesize, k_graph_normal and k_graph_cluster* are untouched. A handle that is never
+ * transformed gives the bits it gave before. */
+/* Phi <- Phi T in place; the handle's m becomes m_new (1 <= m_new <= m), its eigenvalues lam_new, its cached Gram matrix is dropped.
+ * h_T HOST [m][m_new] row-major, h_lam_new HOST [m_new]. ld does not change; columns m_new .. ld of Phi become exact zeros. Every
+ * later call sees m_new: glf_graph_get_info, _eigenvalues, _project, _synthesize, _normal_equations, _gram (recomputed) and the
+ * dim <= min(m, 64) rule of the cluster calls. GLF_ERR_INVALID before any device work, the handle untouched: a NULL argument,
+ * m_new = 0 or m_new > m, an entry of T or lam_new that is not finite (or a T entry that does not fit a float). Returns with the
+ * stream drained. After a HIP failure inside the call (GLF_ERR_HIP / GLF_ERR_NOMEM) the handle's Phi is unspecified: destroy it. */
+int glf_graph_transform(glf_graph *g, unsigned m_new, const double *h_T, const double *h_lam_new);
+/* Host only. G [m][m] (lower triangle read). lam NULL: T = L^-T (upper triangular: Gram-Schmidt in column order), lam_new not written.
+ * lam [m]: the Ritz basis of Phi diag(1 - lam) Phi^T: T = L^-T U, lam_new = 1 - theta ascending. T [m][m]. f64 Cholesky, then cyclic
+ * Jacobi on S; theta descending, the lower original index first on a tie; each column of U signed so that its entry of largest
+ * magnitude is positive (the lowest index on a tie). Two calls give the same bits. GLF_ERR_INVALID, T and lam_new untouched: NULL
+ * G / T (or lam without lam_new), m = 0, an entry of G or lam that is not finite, a pivot p with !(p > 0). */
+int glf_basis_orthonormal(unsigned m, const double *G, const double *lam, double *T, double *lam_new);
+enum { GLF_BASIS_CHOLESKY = 0, GLF_BASIS_RITZ = 1 };
+typedef struct glf_basis_stats {
+    uint32_t struct_size;  /* sizeof(glf_basis_stats), set by the caller */
+    uint32_t passes;
+    double defect_in;      /* max |Phi^T Phi - I| before the first pass */
+    double defect_out;     /* the same after the last pass when verify is set (one more normal-equations pass), else NaN */
+} glf_basis_stats;
+/* The driver: per pass, G = glf_graph_normal_equations(w NULL, no planes), T = glf_basis_orthonormal (mode RITZ: with the handle's
+ * eigenvalues, which become lam_new; mode CHOLESKY: lam NULL, the eigenvalues stay), then glf_graph_transform. A second pass runs in
+ * Cholesky mode whatever mode is, so that the Ritz order of the first survives. GLF_ERR_INVALID, the handle untouched: a NULL
+ * handle, an unknown mode, passes outside 1..2, a stats->struct_size that is not sizeof(glf_basis_stats), a G that is not positive
+ * definite (a later pass that fails leaves the handle as the pass before left it). */
+int glf_graph_orthonormalize(glf_graph *g, int mode, int passes /* 1 | 2 */, int verify, glf_basis_stats *stats /* or NULL */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
