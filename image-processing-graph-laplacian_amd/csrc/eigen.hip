@@ -350,6 +350,22 @@ __global__ __launch_bounds__(256) void k_mv_sum_splits(const float *__restrict__
     Y[e] = s * scales[ld + (unsigned)(e % ld)];
 }
 
+int mv_ksplit(const glf_ctx *ctx, unsigned p, unsigned row0, unsigned row1)
+{
+    const int nrb = (int)ceil_div(row1 > row0 ? row1 - row0 : 1u, 128);
+    const int slots = 2 * ctx->prop.multiProcessorCount;
+    int ksplit = 1;
+    double best = 0.0;
+    const int ntiles = (int)(round_up(p, VEC_PAD) / 64);
+    for (int ks = 1; ks <= 8 && ks <= ntiles; ++ks) {
+        const double wgs = (double)nrb * ks;
+        const double eff = wgs / (std::ceil(wgs / slots) * slots);
+        if (eff > best + 0.02) { best = eff; ksplit = ks; }
+    }
+    return ksplit;
+}
+bool mv_can_skip(unsigned p) { return round_up(p, VEC_PAD) / 64 <= MV_MAXTILES; }
+
 static int block_matvec_f16s(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const float *X, float *Y, unsigned ld,
                              const MatShard *shard)
 {
@@ -359,23 +375,13 @@ static int block_matvec_f16s(glf_ctx *ctx, const float *A, int64_t lda, unsigned
     // element (k, row) of the symmetric operator sits at A[k * lda + (row - row0)]
     const float *A_eff = A - row0;
     const int4 *kbox = shard ? shard->kbox : nullptr;
-    const int radius = (kbox && shard->radius >= 0 && p_pad / 64 <= (unsigned)MV_MAXTILES) ? shard->radius : -1;
+    const int radius = (kbox && shard->radius >= 0 && mv_can_skip(p)) ? shard->radius : -1;
     hipStream_t st = ctx->stream;
     // scratch lives in the context (reused by every mat-vec of a solve; no allocation in the loop)
     // K split so that the grid fills the 2-workgroups-per-CU residency evenly (the kernel keeps
     // 64 VGPRs of A tile in flight: 2 waves per SIMD)
     const int nrb = (int)ceil_div(row1 > row0 ? row1 - row0 : 1u, 128);
-    const int slots = 2 * ctx->prop.multiProcessorCount;
-    int ksplit = 1;
-    {
-        double best = 0.0;
-        const int ntiles = (int)(p_pad / 64);
-        for (int ks = 1; ks <= 8 && ks <= ntiles; ++ks) {
-            const double wgs = (double)nrb * ks;
-            const double eff = wgs / (std::ceil(wgs / slots) * slots);
-            if (eff > best + 0.02) { best = eff; ksplit = ks; }
-        }
-    }
+    const int ksplit = mv_ksplit(ctx, p, row0, row1);
     const size_t part_bytes = ksplit > 1 ? (size_t)ksplit * p_pad * ld * sizeof(float) : 0;
     const size_t frag_bytes = (size_t)p_pad * ld * 2 * sizeof(_Float16);
     const size_t need = 256 + 2 * ld * sizeof(float) + frag_bytes + part_bytes;

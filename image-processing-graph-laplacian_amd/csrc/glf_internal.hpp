@@ -629,6 +629,8 @@ int c_from_ysum(glf_ctx *ctx, const float *d_psi, const float *d_phiA, const dou
 int filter_sample_rows(glf_ctx *ctx, const float *d_phiA, unsigned n, unsigned ld, const uint32_t *d_idx, const uint8_t *d_img,
                        const float *d_w, float gain, float ysub, uint8_t *d_out, float *d_zf, float *d_corr, int64_t pix0);
 int grid_op_path(const GridOp *op);                          // glf_stats.matvec_path: 1 exact grid form, 3 rank form
+int grid_op_row_len(const GridOp *op);                       // samples per grid row (a row range of the operator is whole grid rows)
+bool grid_op_can_skip(const GridOp *op);                     // the grid and rank forms' exact-zero skipping has something to skip (window != 0 turns it on)
 int grid_op_apply(glf_ctx *ctx, GridOp *op, const float *X, float *Y, unsigned ld, double alpha, const double *d_degree,
                   unsigned row0, unsigned row1, int window);
 
@@ -656,6 +658,10 @@ inline unsigned vec_rows(unsigned p, const MatShard *sh, int size)
 }
 int block_matvec(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const float *X, float *Y,
                  unsigned mld, const MatShard *shard = nullptr);
+// the stored split-f16 sweep's K slabs for the rows [row0, row1) (fills the 2-workgroups-per-CU residency evenly), and whether its
+// tile list can hold p samples (exact-zero tile skipping)
+int mv_ksplit(const glf_ctx *ctx, unsigned p, unsigned row0, unsigned row1);
+bool mv_can_skip(unsigned p);
 int orthonormalise(glf_ctx *ctx, float *X, unsigned n, unsigned m, unsigned ld, double *h_norms);
 int normalise(glf_ctx *ctx, float *X, unsigned n, unsigned m, unsigned ld, double *h_norms);
 int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, unsigned m, unsigned ld,

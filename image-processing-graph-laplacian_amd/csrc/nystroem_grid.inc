@@ -1509,6 +1509,8 @@ void band_cache_free(glf_ctx *ctx)
 
 unsigned grid_op_rows_per_rank(const GridOp *op, int size) { return (unsigned)(ceil_div(op->g.nr, size) * op->g.nc); }
 int grid_op_path(const GridOp *op) { return op->use_band ? 4 : op->rank_R ? 3 : 1; }
+int grid_op_row_len(const GridOp *op) { return op->g.nc; }
+bool grid_op_can_skip(const GridOp *op) { return !op->use_band && op->can_skip; }
 
 // Y[s][:] = alpha (D_s X[s][:] - (K_A X)[s][:]) for the samples s in [row0, row1) (whole grid rows); X holds all p rows.
 template <int NT>

@@ -615,6 +615,196 @@ int glf_image_processing_rgbf32_signals(glf_ctx *ctx, const glf_options *opt, co
                                 reinterpret_cast<uint8_t *>(d_out_rgb), nullptr, eigvals_out, stats, nullptr, &sig);
 }
 
+// ------------------------------------------------------------------------------------------
+// The form L_A takes in the eigen-solve: decided here for the whole-path driver and for glf_operator_create alike
+// ------------------------------------------------------------------------------------------
+// For a tensor-grid sample set L_A is applied in grid-factored form and never stored (GLF_MV_PATH = grid | rank | band | dense |
+// auto; auto: from 16 384 samples on -- below, streaming a small stored L_A is cheaper than the factored sweep's fixed cost).
+// *out stays null where L_A is to be stored: not asked for, the NLM kernel, a colour / 16-bit / float guide wider than its band
+// form's one block of 64 columns, or a form that does not apply (grid_op_create's GLF_ERR_UNSUPPORTED)
+static int operator_factored(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx, unsigned p, int width, int height, KernelCoef coef,
+                             int kernel, unsigned ld, GridOp **out)
+{
+    *out = nullptr;
+    const bool want = (ctx->tune.mv_path == 1 || ctx->tune.mv_path == 3 || ctx->tune.mv_path == 4) ? true : ctx->tune.mv_path == 2 ? false : p >= 16384;
+    if (want && kernel != GLF_KERNEL_NLM && (pixgen_of(kernel) == PixGen::Grey || ld <= 64)) {
+        const int rc = grid_op_create(ctx, d_samples, h_idx, p, width, height, coef, out);
+        if (rc != GLF_OK && rc != GLF_ERR_UNSUPPORTED) return rc;
+    }
+    return GLF_OK;
+}
+
+struct OperatorStore {
+    DevBuf<int4> kbox; // bounding boxes of the 64-sample chunks (exact-zero tile skipping of the stored split-f16 form)
+    DevBuf<float> LA;  // the stored L_A: [p][lda], whole or (sharded) the column block [:, row0:row1)
+    int64_t lda = 0;
+};
+// Completes the solve's MatShard (sharded: row0, row1 and rows_per_rank are the caller's) and builds what a stored L_A needs.
+// Factored: alpha, the degree and the skipping window of the operator. Stored: the boxes and the radius of exact-zero tile
+// skipping (|2^10 L_A[i][j]| = 2^10 alpha K < 2^-25 once t > 35 + log2(alpha)), lda and the matrix
+static int operator_store(glf_ctx *ctx, GridOp *gop, const float4 *d_samples, const uint32_t *d_idx, unsigned p, KernelCoef coef, int kernel,
+                          double alpha, const double *d_degree, int skip_exact_zeros, bool sharded, const uint8_t *d_img, int width, int height,
+                          MatShard &shard, OperatorStore &st)
+{
+    if (gop) {
+        shard.grid = gop;
+        shard.grid_alpha = alpha;
+        shard.grid_degree = d_degree;
+        shard.grid_window = skip_exact_zeros;
+    }
+    if (!gop && skip_exact_zeros && coef.s_loc > 0.f && kernel != GLF_KERNEL_NLM && ctx->contraction == GLF_CONTRACT_F16_SPLIT) {
+        const double t_zero = 35.5 + std::log2(alpha);
+        GLF_TRY(st.kbox.alloc(ctx, (size_t)ceil_div(p, 64)));
+        GLF_TRY(chunk_boxes(ctx, d_samples, p, st.kbox.p));
+        shard.kbox = st.kbox.p;
+        shard.radius = t_zero > 0.0 ? (int)std::floor(std::sqrt(t_zero / (double)coef.s_loc)) + 1 : 0;
+    }
+    const unsigned la_cols = sharded ? shard.row1 - shard.row0 : p;
+    st.lda = sharded ? round_up(la_cols ? la_cols : 1, VEC_PAD) : round_up(p, VEC_PAD);
+    if (!gop) {
+        GLF_TRY(st.LA.alloc(ctx, (size_t)p * st.lda));
+        if (la_cols) // writes every element of the p x lda block, padding columns included
+            GLF_TRY(build_sample_matrix(ctx, d_samples, p, coef, st.LA.p, st.lda, true, alpha, d_degree, sharded ? shard.row0 : 0u, la_cols, d_img,
+                                        width, height, d_idx));
+    }
+    return GLF_OK;
+}
+// what the solve hands to block_matvec: the shard where it says anything (rows, skipping boxes or a factored operator)
+static inline const MatShard *shard_arg(const MatShard &shard) { return (shard.rows_per_rank || shard.kbox || shard.grid) ? &shard : nullptr; }
+
+// ------------------------------------------------------------------------------------------
+// One sweep of that operator on its own (glf_operator_*)
+// ------------------------------------------------------------------------------------------
+struct glf_operator {
+    glf_ctx *ctx = nullptr;
+    unsigned p = 0;
+    PixGen gen = PixGen::Grey;
+    GridOp *gop = nullptr;
+    OperatorStore store;
+    MatShard shard;
+    unsigned row0 = 0, row1 = 0;
+    int contraction = 0, mv_path = 0; // what the form was chosen (and a factored operator's tables built) under
+    bool sweep_samples = false;
+    ~glf_operator() { grid_op_destroy(gop); }
+};
+
+int glf_operator_create(glf_ctx *ctx, const glf_mat *L_B, int skip_exact_zeros, unsigned row0, unsigned row1, unsigned ld_hint, glf_operator **out)
+{
+    if (!ctx || !out) return GLF_ERR_INVALID;
+    *out = nullptr;
+    if (!L_B || L_B->kind != GLF_MAT_KERNEL_B || !L_B->degree || !L_B->samples || !L_B->idx || !L_B->img)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: L_B must be a KERNEL_B descriptor with its cached degree (glf_ComputeLaplacianMatrix's L_B)");
+    GLF_ENTER(ctx);
+    const unsigned p = L_B->p;
+    const int kernel = L_B->kernel, width = L_B->width, height = L_B->height;
+    if (p < 2 || kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_RGBF32)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: p = %u, kernel %d", p, kernel);
+    const bool ranged = !(row0 == 0 && row1 == p);
+    if (ranged && !(row0 < row1 && row1 <= p)) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: rows [%u, %u) of p = %u", row0, row1, p);
+    const bool forced = ctx->tune.mv_path == 1 || ctx->tune.mv_path == 3 || ctx->tune.mv_path == 4;
+    if (forced && kernel == GLF_KERNEL_NLM)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_operator_create: the non-local-means kernel has no factored form (MV_PATH forces one)");
+    if (ld_hint % 32 || ld_hint < 32 || ld_hint > 256)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: ld_hint %u (a multiple of 32 up to 256)", ld_hint);
+    const KernelCoef coef = make_coef(kernel, L_B->h_loc, L_B->h_val);
+    const float4 *samples = reinterpret_cast<const float4 *>(L_B->samples);
+    std::vector<unsigned> h_idx(p);
+    GLF_HIP(ctx, hipMemcpyAsync(h_idx.data(), L_B->idx, sizeof(unsigned) * p, hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    // alpha = 1 / VecMean(D_A), as glf_ComputeLaplacianMatrix and the whole path compute it (L_B->scale holds it rounded to f32)
+    double dsum = 0.0;
+    GLF_TRY(sum_host(ctx, L_B->degree, p, &dsum));
+    const double alpha = 1.0 / (dsum / (double)p);
+    std::unique_ptr<glf_operator> op(new glf_operator);
+    op->ctx = ctx;
+    op->p = p;
+    op->gen = pixgen_of(kernel);
+    op->row0 = ranged ? row0 : 0u;
+    op->row1 = ranged ? row1 : p;
+    op->contraction = ctx->contraction;
+    op->mv_path = ctx->tune.mv_path;
+    op->sweep_samples = ctx->tune.sweep_samples;
+    GLF_TRY(operator_factored(ctx, samples, h_idx.data(), p, width, height, coef, kernel, ld_hint, &op->gop));
+    if (forced && !op->gop)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED,
+                         "glf_operator_create: the forced MV_PATH does not apply (it needs a tensor grid of samples, the split-f16 contraction and, for a "
+                         "colour, 16-bit or float guide, PIX_BAND with MV_PATH=band and ld_hint <= 64)");
+    if (ranged) {
+        if (op->gop) {
+            const unsigned nc = (unsigned)grid_op_row_len(op->gop);
+            if (row0 % nc || (row1 % nc && row1 != p))
+                return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: rows [%u, %u) are not whole grid rows (%u samples each)", row0, row1, nc);
+        } else {
+            if (ctx->contraction != GLF_CONTRACT_F16_SPLIT)
+                return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_operator_create: a row range of the stored L_A needs the split-f16 contraction");
+            if (row0 % VEC_PAD) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_create: row0 = %u of a stored L_A must be a multiple of %d", row0, VEC_PAD);
+        }
+        op->shard.row0 = row0;
+        op->shard.row1 = row1;
+        op->shard.rows_per_rank = (unsigned)round_up(row1 - row0, VEC_PAD); // (the all-gather block of a rank that owns these rows)
+    }
+    GLF_TRY(operator_store(ctx, op->gop, samples, L_B->idx, p, coef, kernel, alpha, L_B->degree, skip_exact_zeros, ranged, L_B->img, width, height,
+                           op->shard, op->store));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *out = op.release();
+    return GLF_OK;
+}
+
+int glf_operator_apply(glf_operator *op, const glf_mat *X, glf_mat *Y, glf_operator_info *info)
+{
+    if (!op || !op->ctx) return GLF_ERR_INVALID;
+    glf_ctx *ctx = op->ctx;
+    if (!X || !Y || X->kind != GLF_MAT_DENSE || Y->kind != GLF_MAT_DENSE || !X->data || !Y->data || X->data == Y->data)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: X and Y must be two dense matrices");
+    GLF_ENTER(ctx);
+    const unsigned p = op->p;
+    if (ctx->contraction != op->contraction || ctx->tune.mv_path != op->mv_path || ctx->tune.sweep_samples != op->sweep_samples)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the contraction mode, MV_PATH or SWEEP_COLPASS changed since glf_operator_create");
+    if (X->rows < (int64_t)p || Y->rows < (int64_t)p)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: X has %lld rows and Y %lld, fewer than p = %u", (long long)X->rows, (long long)Y->rows, p);
+    if (X->ld != Y->ld || X->ld <= 0 || X->ld > 256)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: X has ld %lld, Y ld %lld (equal, at most 256)", (long long)X->ld, (long long)Y->ld);
+    const unsigned ld = (unsigned)X->ld;
+    if (!op->gop && !valid_ld(ld)) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the stored L_A takes ld 32, 64, 128 or 256 (ld = %u)", ld);
+    if (op->gop && op->gen != PixGen::Grey && ld != 32 && ld != 64)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the %s band form takes ld 32 or 64 (ld = %u)", pix_name(op->gen), ld);
+    if (op->gop && ld != 32 && ld % 64) // (grid_op_apply walks the block 64 columns at a time from ld 64 on)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: a factored form takes ld 32, 64, 128, 192 or 256 (ld = %u)", ld);
+    GLF_TRY(block_matvec(ctx, op->store.LA.p, op->store.lda, p, X->data, Y->data, ld, shard_arg(op->shard)));
+    GLF_TRY(mv_collect(ctx));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (info) {
+        info->path = op->gop ? grid_op_path(op->gop) : 0;
+        const bool f16s = !op->gop && ctx->contraction == GLF_CONTRACT_F16_SPLIT;
+        info->ksplit = f16s ? mv_ksplit(ctx, p, op->row0, op->row1) : 0;
+        info->skipping = op->gop ? (op->shard.grid_window && grid_op_can_skip(op->gop)) : (f16s && op->shard.kbox && op->shard.radius >= 0 && mv_can_skip(p));
+        info->row0 = (int32_t)op->row0;
+        info->row1 = (int32_t)op->row1;
+    }
+    return GLF_OK;
+}
+
+int glf_operator_stored(const glf_operator *op, glf_mat *view)
+{
+    if (!op || !op->ctx || !view) return GLF_ERR_INVALID;
+    if (op->gop) return set_error(op->ctx, GLF_ERR_UNSUPPORTED, "glf_operator_stored: a factored form stores no matrix");
+    std::memset(view, 0, sizeof(*view));
+    view->kind = GLF_MAT_DENSE;
+    view->rows = op->p;
+    view->cols = op->row1 - op->row0;
+    view->ld = op->store.lda;
+    view->data = op->store.LA.p;
+    return GLF_OK;
+}
+
+int glf_operator_destroy(glf_operator *op)
+{
+    if (!op) return GLF_OK;
+    if (op->ctx && hipSetDevice(op->ctx->device) != hipSuccess) return GLF_ERR_HIP;
+    delete op;
+    return GLF_OK;
+}
+
 static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
                                 uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
@@ -757,13 +947,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
         GridOp *op = nullptr;
         ~GridOpGuard() { grid_op_destroy(op); }
     } gop;
-    {
-        const bool want = (ctx->tune.mv_path == 1 || ctx->tune.mv_path == 3 || ctx->tune.mv_path == 4) ? true : ctx->tune.mv_path == 2 ? false : p >= 16384;
-        if (want && opt.kernel != GLF_KERNEL_NLM && (u8_guide || ld <= 64)) { // (the colour and 16-bit band form: one block of 64 columns)
-            const int rc = grid_op_create(ctx, tb.samples.p, h_idx, p, width, height, coef, &gop.op);
-            if (rc != GLF_OK && rc != GLF_ERR_UNSUPPORTED) return rc;
-        }
-    }
+    GLF_TRY(operator_factored(ctx, tb.samples.p, h_idx, p, width, height, coef, opt.kernel, ld, &gop.op));
     S.matvec_path = gop.op ? grid_op_path(gop.op) : 0;
     // With the band form a sweep costs less (0.19 ms at cfg4) than the all-gather of its 21.8 MB operand block over xGMI
     // (~0.2-0.4 ms), and the whole eigen-solve (4.8 ms) less than the sharded one's 12 all-gathers + ~46 small all-reduces:
@@ -771,36 +955,18 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     // -- degree, extension, filter -- are sharded. EIG_SHARD=1 forces the row-sharded solve, 0 the replicated one.
     if (shard_eig && ((S.matvec_path == 4 && ctx->tune.eig_shard != 1) || ctx->tune.eig_shard == 2)) shard_eig = false;
     S.eigen_sharded = shard_eig ? 1 : 0;
-    if (gop.op) {
-        shard.grid = gop.op;
-        shard.grid_alpha = alpha;
-        shard.grid_degree = deg.p;
-        shard.grid_window = opt.skip_exact_zeros;
-    }
     if (shard_eig) {
         shard.rows_per_rank = gop.op ? grid_op_rows_per_rank(gop.op, ctx->comm.size) : shard_rows_per_rank(p, ctx->comm.size);
         const uint64_t b = (uint64_t)shard.rows_per_rank * (unsigned)ctx->comm.rank;
         shard.row0 = (unsigned)(b < p ? b : p);
         shard.row1 = (unsigned)(b + shard.rows_per_rank < p ? b + shard.rows_per_rank : p);
     }
-    // Exact-zero tile skipping of the mat-vec: |2^10 L_A[i][j]| = 2^10 alpha K < 2^-25 once t > 35 + log2(alpha)
-    DevBuf<int4> kbox;
-    if (!gop.op && opt.skip_exact_zeros && coef.s_loc > 0.f && opt.kernel != GLF_KERNEL_NLM && ctx->contraction == GLF_CONTRACT_F16_SPLIT) {
-        const double t_zero = 35.5 + std::log2(alpha);
-        GLF_TRY(kbox.alloc(ctx, (size_t)ceil_div(p, 64)));
-        GLF_TRY(chunk_boxes(ctx, tb.samples.p, p, kbox.p));
-        shard.kbox = kbox.p;
-        shard.radius = t_zero > 0.0 ? (int)std::floor(std::sqrt(t_zero / (double)coef.s_loc)) + 1 : 0;
-    }
-    const unsigned la_cols = shard_eig ? shard.row1 - shard.row0 : p;
-    const int64_t lda = shard_eig ? round_up(la_cols ? la_cols : 1, VEC_PAD) : (int64_t)p32;
-    DevBuf<float> LA, dinv;
-    if (!gop.op) {
-        GLF_TRY(LA.alloc(ctx, (size_t)p * lda));
-        if (la_cols) // writes every element of the p x lda block, padding columns included
-            GLF_TRY(build_sample_matrix(ctx, tb.samples.p, p, coef, LA.p, lda, true, alpha, deg.p, shard_eig ? shard.row0 : 0u, la_cols, d_img,
-                                        width, height, tb.idx.p));
-    }
+    OperatorStore store; // the skipping boxes and the stored L_A (neither with a factored operator)
+    GLF_TRY(operator_store(ctx, gop.op, tb.samples.p, tb.idx.p, p, coef, opt.kernel, alpha, deg.p, opt.skip_exact_zeros, shard_eig, d_img, width,
+                           height, shard, store));
+    DevBuf<float> &LA = store.LA;
+    DevBuf<float> dinv;
+    const int64_t lda = store.lda;
     GLF_TRY(dinv.alloc(ctx, p));
     hipLaunchKernelGGL(k_dinv_from_degree, dim3((p + 255) / 256), dim3(256), 0, st, deg.p, p, alpha, dinv.p);
     GLF_LAUNCH_CHECK(ctx);
@@ -896,7 +1062,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
         GLF_TRY(start_block_cached(ctx, p, m, ld, opt.seed, &d_x0));
         int rc = inverse_power_iteration(ctx, LA.p, lda, p, m, ld, nullptr, opt.opti_gs, opt.epsilon, opt.inner_rtol,
                                          opt.max_outer > 0 ? opt.max_outer : 100000, phiA.p, lam.data(), &S.eig,
-                                         (shard_eig || shard.kbox || shard.grid) ? &shard : nullptr, dinv.p, d_x0);
+                                         shard_arg(shard), dinv.p, d_x0);
         if (rc != GLF_OK) return rc;
     }
     if (shard_eig || gop.op) LA.release(); // (a whole stored L_A is used once more below: K_A y_A for the fused filter)

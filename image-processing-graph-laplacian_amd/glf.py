@@ -66,6 +66,7 @@ EXPORTS = [
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize",
+    "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
@@ -142,6 +143,10 @@ class ClusterEmbed(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("normalize", C.c_int32), ("d_weight", C.c_void_p)]
 
 
+class OperatorInfo(C.Structure):
+    _fields_ = [("path", C.c_int32), ("ksplit", C.c_int32), ("skipping", C.c_int32), ("row0", C.c_int32), ("row1", C.c_int32)]
+
+
 class BasisStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("defect_in", C.c_double), ("defect_out", C.c_double)]
 
@@ -187,6 +192,10 @@ _lib.glf_graph_segment_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_vo
 _lib.glf_graph_transform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_basis_orthonormal.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_orthonormalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+_lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
+_lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_operator_destroy.argtypes = [C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -1063,6 +1072,17 @@ class Context:
         self._check(_lib.glf_NormaliseVecs(self._ctx, C.byref(X), norms.ctypes.data_as(C.c_void_p)))
         return norms
 
+    def operator(self, L_B, skip_exact_zeros=0, rows=None, ld_hint=256):
+        """glf_operator_create: the eigen-solve's L_A = alpha (D - K_A) of the descriptor L_B (ComputeLaplacianMatrix's) in the form the
+        whole path would take under the context's contraction mode and tuning. rows = (row0, row1): the rows one rank of the
+        sharded solve owns (None: all). Returns an Operator (apply, apply_numpy, stored, info, close); L_B must outlive it."""
+        p = int(L_B.p)
+        row0, row1 = (0, p) if rows is None else rows
+        h = C.c_void_p()
+        self._check(_lib.glf_operator_create(self._ctx, C.byref(L_B), C.c_int(skip_exact_zeros), C.c_uint(row0), C.c_uint(row1),
+                                             C.c_uint(ld_hint), C.byref(h)), "operator")
+        return Operator(self, h, p, L_B)
+
     def InverseDiagMat(self, x):
         inv = Mat()
         self._check(_lib.glf_InverseDiagMat(self._ctx, C.byref(x), C.byref(inv)))
@@ -1340,6 +1360,67 @@ class Context:
                       c_host.ctypes.data if grey else None, deg_host.ctypes.data, corr.data_ptr() if grey else None,
                       corr.numel() if grey else 0)
         return cap, (phi_A, phi, deg_host, c_host, corr)
+
+
+class Operator:
+    """One glf_operator: a sweep Y = L_A X through the function the eigen-solve calls (Context.operator)."""
+
+    def __init__(self, ctx, handle, p, desc):
+        self.ctx, self._h, self.p, self._desc = ctx, handle, p, desc
+        self.info = None          # dict of the last apply: path, ksplit, skipping, row0, row1
+
+    def close(self):
+        if self._h:
+            _lib.glf_operator_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def apply(self, X, Y):
+        """glf_operator_apply on two dense Mats of one ld -> the info dict (also kept in self.info)."""
+        info = OperatorInfo()
+        self.ctx._check(_lib.glf_operator_apply(self._h, C.byref(X), C.byref(Y), C.byref(info)), "operator.apply")
+        self.info = {k: int(getattr(info, k)) for k, _ in OperatorInfo._fields_}
+        return self.info
+
+    def apply_numpy(self, X, fill=None):
+        """X: float32 [rows >= p, ld] (the whole block, padding columns included) -> Y float32 [round_up(p, 64), ld]. The device
+        blocks hold round_up(p, 64) rows, X zero from its last row on; Y starts as zeros, or as the float32 array `fill`
+        [round_up(p, 64), ld] (a sentinel: rows the operator does not own, and every row after a refusal, keep it)."""
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        rows, ld = (self.p + 63) // 64 * 64, X.shape[1]
+        if X.shape[0] > rows:
+            raise ValueError("X has %d rows, more than round_up(p, 64) = %d" % (X.shape[0], rows))
+        ctx = self.ctx
+        full = np.zeros((rows, ld), dtype=np.float32)
+        full[:X.shape[0]] = X
+        y0 = np.zeros((rows, ld), dtype=np.float32) if fill is None else np.ascontiguousarray(fill, dtype=np.float32)
+        assert y0.shape == (rows, ld)
+        dX, dY = ctx.dense_from_numpy(full, ld=ld), ctx.dense_from_numpy(y0, ld=ld)
+        dX.rows = dY.rows = max(X.shape[0], 1) if X.shape[0] < self.p else self.p
+        out = np.empty((rows, ld), dtype=np.float32)
+        try:
+            try:
+                self.apply(dX, dY)
+            finally:
+                ctx._check(_lib.glf_memcpy_d2h(ctx._ctx, _ptr(out), C.c_void_p(dY.data), C.c_size_t(out.nbytes)))
+                self.last_Y = out
+        finally:
+            ctx.destroy(dX, dY)
+        return out
+
+    def stored(self):
+        """The stored form's matrix as downloaded, float32 [p, row1 - row0] (element (k, row - row0) of the symmetric L_A);
+        GlfError(ERR_UNSUPPORTED) for a factored form."""
+        view = Mat()
+        self.ctx._check(_lib.glf_operator_stored(self._h, C.byref(view)), "operator.stored")
+        full = np.empty((view.rows, view.ld), dtype=np.float32)
+        self.ctx._check(_lib.glf_memcpy_d2h(self.ctx._ctx, _ptr(full), C.c_void_p(view.data), C.c_size_t(full.nbytes)))
+        return full[:, :view.cols].copy()
 
 
 class Graph:

@@ -301,6 +301,37 @@ int glf_NormaliseVecs(glf_ctx *ctx, glf_mat *X, double *norms);
 /* Mat InverseDiagMat(Mat x)  hpc/utils.h (hpc/utils.c:559-586) */
 int glf_InverseDiagMat(glf_ctx *ctx, const glf_mat *x, glf_mat *inv);
 
+/* ---- the eigen-solve's operator on its own: one sweep Y = L_A X ---------------------------------------------------------------
+ * L_A = alpha (D - K_A) of a KERNEL_B descriptor (L_B of glf_ComputeLaplacianMatrix: scale = -alpha, degree cached), in the form
+ * the eigen-solve of the whole path would take under the context's contraction mode and the MV_PATH / PIX_BAND tuning at creation:
+ * stored (f32-input MFMA or split-f16 with K slabs, with exact-zero tile skipping when skip_exact_zeros is set and the kernel has a
+ * spatial factor), grid-factored, rank form or band form. glf_operator_apply calls the function the block PCG calls, with the same
+ * arguments; the decisions of glf_operator_create are the whole-path driver's own (one code). [row0, row1): the rows this operator
+ * produces -- 0, p: all of them; otherwise what one rank of the row-sharded solve owns: for a stored L_A (split-f16 contraction
+ * only) row0 a multiple of 64 and the column block L_A[:, row0:row1) is what is built; for a factored form whole grid rows (row1 =
+ * p closes the last one). ld_hint: the widest ld the caller will apply (the colour, 16-bit and float formats take a factored form
+ * only up to ld 64). The descriptor (its image, tables and degree) must outlive the operator.
+ * glf_operator_apply: X, Y dense with the same ld, at least p logical rows and round_up(p, 64) rows of storage (what
+ * glf_mat_create_dense(round_up(p, 64), ...) gives; the rows from p on of X zero); rows [row0, row1) of Y are written, all ld
+ * columns. ld: stored 32, 64, 128 or 256; factored, 8-bit grey: 32 or a multiple of 64 up to 256 (192 included: the widths the
+ * block PCG's packed sweeps ask for); factored, other formats: 32 or 64.
+ * info (optional) describes the sweep. GLF_ERR_INVALID / GLF_ERR_UNSUPPORTED (a forced MV_PATH that does not apply: not a tensor
+ * grid, not the split-f16 contraction, the NLM kernel) name their reason in glf_ctx_last_error and leave Y untouched. */
+typedef struct glf_operator glf_operator;
+typedef struct glf_operator_info {
+    int32_t path;       /* as glf_stats.matvec_path: 0 stored, 1 grid, 3 rank, 4 band */
+    int32_t ksplit;     /* stored split-f16 form: K slabs of the last apply; else 0 */
+    int32_t skipping;   /* exact-zero skipping in effect */
+    int32_t row0, row1;
+} glf_operator_info;
+int glf_operator_create(glf_ctx *ctx, const glf_mat *L_B, int skip_exact_zeros, unsigned row0, unsigned row1, unsigned ld_hint,
+                        glf_operator **op);
+int glf_operator_apply(glf_operator *op, const glf_mat *X, glf_mat *Y, glf_operator_info *info);
+/* the stored form's matrix as a dense view (not owned: p rows, row1 - row0 columns, element (k, row) of the symmetric L_A at
+ * data[k * ld + row - row0]); GLF_ERR_UNSUPPORTED for a factored form, which stores none */
+int glf_operator_stored(const glf_operator *op, glf_mat *view);
+int glf_operator_destroy(glf_operator *op); /* NULL: GLF_OK */
+
 /* ---- the PoC's balancing steps of the approximated affinity (inactive experiments in the PoC) ----------
  * sinkhorn(phi, Pi)  python/image_processing.py:90-98: the alternating scalings of K = phi diag(Pi) phi^T, K never formed
  * (200 products K x = phi (Pi o (phi^T x)) for the PoC's 100 iterations). phi: dense N x m in any row order, Pi: diagonal m;
