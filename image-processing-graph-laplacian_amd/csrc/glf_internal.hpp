@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -109,8 +110,7 @@ struct glf_graph {
     std::vector<double> lam;   // [m]
     std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
     int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
-    int cluster_blocks_per_cu = 0; // k_graph_cluster<CW>'s, asked at the first cluster step
-    int cluster_nw_blocks_per_cu[2] = {0, 0}; // k_graph_cluster_nw<CW, NORM>'s at [NORM], asked at the first such step
+    int cluster_blocks_per_cu[3] = {0, 0, 0}; // k_graph_cluster<CW, MODE>'s at [MODE], asked at the first cluster step in that mode
     int transform_blocks_per_cu = 0; // k_graph_transform<ld>'s, asked at the first transform
 };
 
@@ -165,6 +165,26 @@ inline int set_error(glf_ctx *ctx, int status, const char *fmt, ...)
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 inline int64_t ceil_div(int64_t x, int64_t q) { return (x + q - 1) / q; }
+// The grid of the graph-handle kernels that take one tile of 32 pixels per wave, four waves per workgroup, the tiles strided over
+// a resident grid: min(ceil(ceil(N / 32) / 4), what fits the device at once), the rest of the tiles by the grid stride. *per_cu
+// caches the kernel's resident workgroups per CU, asked of the runtime at the first launch.
+template <class Kernel>
+inline int resident_tile_grid(glf_ctx *ctx, int *per_cu, Kernel kernel, int64_t N, int64_t *nblk)
+{
+    if (*per_cu <= 0) {
+        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, 256, 0));
+        *per_cu = *per_cu > 1 ? *per_cu : 1;
+    }
+    const int64_t cus = ctx->prop.multiProcessorCount > 1 ? ctx->prop.multiProcessorCount : 1, tiles4 = ceil_div(ceil_div(N, 32), 4);
+    *nblk = tiles4 < *per_cu * cus ? tiles4 : *per_cu * cus;
+    return GLF_OK;
+}
+inline bool all_finite(const double *x, size_t n)
+{
+    for (size_t e = 0; e < n; ++e)
+        if (!std::isfinite(x[e])) return false;
+    return true;
+}
 // Leading dimension of vector blocks: m rounded up to a power of two in {32,64,128,256}
 // (the column-reduction kernels map 256 threads onto 256/ld row lanes x ld columns).
 inline unsigned ld_for(unsigned m) { unsigned ld = 32; while (ld < m) ld <<= 1; return ld; }

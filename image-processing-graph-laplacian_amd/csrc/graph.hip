@@ -108,12 +108,8 @@ template <int LD>
 static int launch_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, int nout, const float *d_operand, const float *d_planes,
                              float *d_out)
 {
-    if (*per_cu <= 0) {
-        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_graph_synthesize<LD>, 256, 0));
-        *per_cu = std::max(1, *per_cu);
-    }
-    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
-    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident); // (the rest of the tiles by the grid stride)
+    int64_t nblk = 0;
+    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_synthesize<LD>, N, &nblk));
     hipLaunchKernelGGL(k_graph_synthesize<LD>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, nout, d_operand, d_planes, d_out);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;

@@ -179,22 +179,11 @@ __global__ __launch_bounds__(256) void k_graph_transform(float *phi, int64_t N, 
 template <int LD>
 static int launch_transform(glf_ctx *ctx, int *per_cu, float *d_phi, int64_t N, unsigned m_new, const float *d_operand)
 {
-    if (*per_cu <= 0) {
-        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_graph_transform<LD>, 256, 0));
-        *per_cu = std::max(1, *per_cu);
-    }
-    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
-    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident); // (the rest of the tiles by the grid stride)
+    int64_t nblk = 0;
+    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_transform<LD>, N, &nblk));
     hipLaunchKernelGGL(k_graph_transform<LD>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)m_new, d_operand);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
-}
-
-static bool all_finite(const double *x, size_t n)
-{
-    for (size_t e = 0; e < n; ++e)
-        if (!std::isfinite(x[e])) return false;
-    return true;
 }
 
 // max |G - I| of an [m][m] matrix

@@ -1,8 +1,8 @@
 // graph_cluster.hip -- spectral segmentation on a graph handle: k-means over the rows of Phi. One Lloyd iteration is one pass over
 // Phi (k_graph_cluster: the assignment on k_graph_synthesize's MFMA shape, the per-label sums on k_graph_normal's), driven by
-// glf_graph_cluster_step and glf_graph_segment; the host-only centroid update and k-means++ seeding are in host_util.cpp.
-// Unit-length rows (the row-normalised embedding of Ng, Jordan and Weiss) and per-pixel weights are a kernel of their own,
-// k_graph_cluster_nw, behind glf_graph_cluster_step_ex and glf_graph_segment_ex; k_graph_cluster is what a plain embedding runs.
+// glf_graph_cluster_step[_ex] and glf_graph_segment[_ex]; the host-only centroid update and k-means++ seeding are in host_util.cpp.
+// Unit-length rows (the row-normalised embedding of Ng, Jordan and Weiss) and per-pixel weights are compile-time modes of that one
+// kernel, chosen from the embedding the _ex entry points take; a plain embedding runs the plain mode.
 // Out of scope: spherical k-means (renormalised centroids), a margin or confidence output, more than 64 embedding columns, k > 32,
 // contexts with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
 // k_graph_synthesize and k_graph_normal.
@@ -17,17 +17,26 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GC_K = GLF_CLUSTER_MAX;                       // centroids = the M index of one 32 x 32 accumulator
 constexpr int GC_CHAIN_TILES = GLF_GRAPH_NORMAL_CHAIN / 32; // 32-pixel tiles in one f32 chain of the sums
-constexpr int GC_TAIL = 64;                                 // doubles after a partial's sum tiles: counts [32], changed, zero padding
 static_assert(GC_K == 32, "the centroids fill exactly one MFMA tile");
 static_assert(GLF_GRAPH_NORMAL_CHAIN % 32 == 0 && GLF_GRAPH_NORMAL_CHAIN >= 32, "a chain is a whole number of 32-pixel tiles");
+
+// The modes of k_graph_cluster: the embedding is e(px) = rinv(px) scale o Phi[px], and pixel px enters the update with weight w(px).
+//   GC_PLAIN   rinv = 1, w = 1
+//   GC_WEIGHT  rinv = 1, w = the weight plane
+//   GC_NORM    rinv = 1 / |scale o Phi[px]| (unit-length rows), w = the weight plane, or 1 where there is none (a run-time NULL check)
+enum { GC_PLAIN = 0, GC_WEIGHT = 1, GC_NORM = 2, GC_MODES = 3 };
+static_assert(GC_MODES == sizeof(glf_graph::cluster_blocks_per_cu) / sizeof(int), "one cached occupancy per mode");
 
 // the per-call operand block of k_graph_cluster (device):
 //   [CW][32] float  fl32(scale_c cent_j[c]) at [c][j], zero for j >= k and c >= dim
 //   [32] float      fl32(|cent_j|^2), zero for j >= k
+//   [CW] float      fl32(scale_c), zero for c >= dim (GC_NORM only)
 inline int gc_cw(unsigned ld) { return ld < 64 ? 32 : 64; }
-inline size_t gc_operand_floats(int cw) { return (size_t)cw * GC_K + GC_K; }
-// one workgroup's partial: [CW / 32][32 labels][32 columns] sums, then the tail
-inline size_t gc_part_cols(int cw) { return (size_t)(cw / 32) * 1024 + GC_TAIL; }
+inline size_t gc_operand_floats(int cw, int mode) { return (size_t)cw * GC_K + GC_K + (mode == GC_NORM ? cw : 0); }
+// one workgroup's partial: [CW / 32][32 labels][32 columns] sums, then the tail of doubles: counts [32], changed, zero padding up to
+// 64, and outside GC_PLAIN the mass [32]
+constexpr int gc_tail(int mode) { return mode == GC_PLAIN ? 64 : 96; }
+inline size_t gc_part_cols(int cw, int mode) { return (size_t)(cw / 32) * 1024 + gc_tail(mode); }
 
 // One Lloyd iteration in one pass over the first CW columns of Phi (row pitch ld floats). One wave per tile of 32 pixels, tiles
 // strided over a resident grid. The tile's rows are loaded as whole 16-byte pieces in address order and written to the wave's own
@@ -35,42 +44,72 @@ inline size_t gc_part_cols(int cw) { return (size_t)(cw / 32) * 1024 + GC_TAIL; 
 // Assignment: v_mfma_f32_32x32x2_f32 with the centroids as the M index (A: the operand block, from LDS) and the pixels as the N
 // index (B: Phi, one pixel per lane as float4s; pitch CW + 4: the 16 lanes of a ds_read_b128 group hit 64 different banks), half-wave
 // h taking columns h CW / 2 + t at step t: k_graph_synthesize's contraction order, every score its own fma chain. Register g of
-// lane (r, h) then holds the dot product of pixel r with centroid j = (g & 3) + 8 (g >> 2) + 4 h; score = fmaf(-2, dot, |c_j|^2)
+// lane (r, h) then holds the dot product of pixel r with centroid j = (g & 3) + 8 (g >> 2) + 4 h; score = fmaf(-2 rinv, dot, |c_j|^2)
 // (|e|^2 is the same for every j and is not formed). Each lane takes the argmin of its 16 registers in ascending j with a strict <
 // (j >= k carries a bias of +inf and never wins), one exchange with the other half-wave decides between the two, the lower index
 // winning a tie.
 // Update: the wave's 32 labels go to LDS (-1 for rows past N), then the same MFMA with the pixels as the contraction index: at step
-// u lane (r, h) gives A = (label[2u + h] == r) and B = Phi[2u + h][r] (and [32 + r]) from the same image -- the 32 lanes of a
-// ds_read_b32 group read 32 consecutive floats of one row, no conflict at any pitch; the label is one address per group, a
-// broadcast. The products are exact; each accumulator tile is an f32 chain over at most GLF_GRAPH_NORMAL_CHAIN pixels, then added
-// into its f64 image and cleared (k_graph_normal's rule). Lane (r, h) counts its own hits: the members of label r among the pixels
-// of parity h, an exact integer; the lanes of half 0 count the labels that differ from prev.
+// u lane (r, h) gives A = (label[2u + h] == r ? t[2u + h] : 0), t(px) = fl32(w(px) rinv(px)), and B = Phi[2u + h][r] (and [32 + r])
+// from the same image -- the 32 lanes of a ds_read_b32 group read 32 consecutive floats of one row, no conflict at any pitch; the
+// label is one address per group, a broadcast. sums_j = sum w rinv Phi[px][c] over the members of j: each accumulator tile is an f32
+// chain over at most GLF_GRAPH_NORMAL_CHAIN pixels, then added into its f64 image and cleared (k_graph_normal's rule). Lane (r, h)
+// counts its own hits: the members of label r among the pixels of parity h, an exact integer; the lanes of half 0 count the labels
+// that differ from prev.
 // No atomics: the workgroup's four waves are added in a fixed order, the workgroups by k_cols_sum. Rows past N are staged as
 // zeros and are neither labelled nor counted. prev may be labels itself: a lane reads prev[px] before it writes labels[px], and
 // no other lane touches that pixel.
-template <int CW>
+// What the modes change (MODE is a template argument, nothing of another mode is left in an instance):
+//   GC_PLAIN keeps the 16 biases |c_j|^2 of a lane in registers; t = 1, so A is 1 or 0 and the products are exact. In the other modes
+//   the biases are read from LDS at every tile (bias_sh, +inf for j >= k; registers 4 q .. 4 q + 3 hold 16 consecutive bytes): with
+//   them in registers, GC_NORM at CW 64 spilled 5 registers (profiles/graph_cluster_nw_kernel_resources.txt). The values, and so
+//   every score's bits, are the same;
+//   GC_NORM: lane (r, h) forms the squared length of its half row of pixel r from the float4s it reads anyway,
+//   n2 = fmaf(x, x, n2), x = fl32(scale_c) phi_c (the scales in LDS, s_sh), in ascending column order; the halves are added through one
+//   __shfl_xor(.., 32) (a commutative sum: both half-waves hold the same bits) and rinv = n2 > 0 ? 1 / sqrtf(n2) : 0 (a run-time
+//   branch inside the unrolled contraction would cut it into one basic block per four MFMAs, and the LDS reads of the next step
+//   would no longer be issued under the MFMAs of this one);
+//   GC_WEIGHT and GC_NORM: t(px) and w(px) go to LDS beside the tile's 32 labels (w is loaded with the prefetch of the next tile,
+//   as prev is), and lane (r, h) adds (double) w[p] over its hits: the mass of label r among the pixels of parity h. Counts and
+//   changed stay integers.
+template <int CW, int MODE>
 __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
-                                                          const int32_t *prev, int32_t *labels, double *__restrict__ part)
+                                                          const float *__restrict__ weight, const int32_t *prev, int32_t *labels,
+                                                          double *__restrict__ part)
 {
     constexpr int PITCH = CW + 4;
     constexpr int FPR = CW / 4;   // float4 pieces per staged row
     constexpr int NLOAD = CW / 8; // pieces per lane: 32 rows x FPR / 64 lanes
     constexpr int NT = CW / 32;   // accumulator tiles of the sums
     constexpr int RW = 32 * PITCH > 2048 ? 32 * PITCH : 2048; // floats of a wave's region (>= one f64 tile for the epilogue)
+    constexpr int TAIL = gc_tail(MODE);
     __shared__ __attribute__((aligned(16))) float a_sh[CW * GC_K];
     __shared__ __attribute__((aligned(16))) float region[4][RW];
+    __shared__ __attribute__((aligned(16))) float s_sh[CW];      // GC_NORM
+    __shared__ __attribute__((aligned(16))) float bias_sh[GC_K]; // not GC_PLAIN, as are t_sh, w_sh and mass_sh
     __shared__ int lab_sh[4][32];
+    __shared__ float t_sh[4][32], w_sh[4][32];
     __shared__ unsigned cnt_sh[4][64], chg_sh[4][64];
+    __shared__ double mass_sh[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     for (int e = threadIdx.x; e < CW * GC_K; e += 256) a_sh[e] = operand[e];
+    auto centroid_of = [&](int g) { return (g & 3) + 8 * (g >> 2) + 4 * h; }; // the centroid of accumulator register g of this lane
     float bias[16];
+    if constexpr (MODE == GC_PLAIN) {
 #pragma unroll
-    for (int g = 0; g < 16; ++g) {
-        const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
-        bias[g] = j < k ? operand[CW * GC_K + j] : INFINITY;
-    }
+        for (int g = 0; g < 16; ++g) {
+            const int j = centroid_of(g);
+            bias[g] = j < k ? operand[CW * GC_K + j] : INFINITY;
+        }
+    } else if (threadIdx.x < GC_K)
+        bias_sh[threadIdx.x] = (int)threadIdx.x < k ? operand[CW * GC_K + threadIdx.x] : INFINITY;
+    if constexpr (MODE == GC_NORM)
+        if (threadIdx.x < CW) s_sh[threadIdx.x] = operand[CW * GC_K + GC_K + threadIdx.x];
     __syncthreads();
+    auto bias_of = [&](int g) {
+        if constexpr (MODE == GC_PLAIN) return bias[g];
+        else return bias_sh[centroid_of(g)];
+    };
     float *tw = region[wave];
     const int *lab = lab_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
@@ -85,10 +124,12 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
             dacc[t][g] = 0.0;
         }
     unsigned cnt = 0, chg = 0;
+    double mass = 0.0;
 
     // what this lane stages of a tile: rows past N as zeros
     float4 v[NLOAD];
     int pv = 0;
+    float wv = 1.f;
     auto load_tile = [&](int64_t tile) {
         const int64_t base = tile * 32;
 #pragma unroll
@@ -96,7 +137,12 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
             const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
             v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        if (prev && h == 0 && base + r < N) pv = prev[base + r];
+        if constexpr (MODE == GC_PLAIN) { // (prev first: with the other order the plain tile loop gains scalar work per tile)
+            if (prev && h == 0 && base + r < N) pv = prev[base + r];
+        } else if (h == 0 && base + r < N) {
+            if (prev) pv = prev[base + r];
+            if (weight) wv = weight[base + r];
+        }
     };
     auto flush = [&]() {
 #pragma unroll
@@ -119,277 +165,9 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
             *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
         }
         const int pv_cur = pv;
-        __builtin_amdgcn_wave_barrier();
-        // the next tile's loads fly under this tile's MFMAs
-        if (tile + tstride < ntiles) load_tile(tile + tstride);
-
-        f32x16 sc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) sc[g] = 0.f;
-#pragma unroll
-        for (int u = 0; u < CW / 8; ++u) {
-            const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
-            const float *ak = a_sh + (h * (CW / 2) + 4 * u) * GC_K + r;
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GC_K], b.x, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GC_K], b.y, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GC_K], b.z, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GC_K], b.w, sc, 0, 0, 0);
-        }
-        // half 0 always holds centroid 0 < k, so a label is in [0, k) even if no comparison holds
-        float best = INFINITY;
-        int bj = h ? 0x7fffffff : 0;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            const float s = fmaf(-2.f, sc[g], bias[g]);
-            if (s < best) {
-                best = s;
-                bj = (g & 3) + 8 * (g >> 2) + 4 * h;
-            }
-        }
-        const float ob = __shfl_xor(best, 32);
-        const int oj = __shfl_xor(bj, 32);
-        if (ob < best || (ob == best && oj < bj)) bj = oj;
-        const int64_t px = tile * 32 + r;
-        if (h == 0) {
-            const bool live = px < N;
-            lab_sh[wave][r] = live ? bj : -1;
-            if (live) {
-                if (prev) chg += pv_cur != bj;
-                labels[px] = bj;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int p = 2 * u + h;
-            const bool hit = lab[p] == r;
-            const float a = hit ? 1.f : 0.f;
-            cnt += hit;
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + r], acc[0], 0, 0, 0);
-            if constexpr (NT == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + 32 + r], acc[1], 0, 0, 0);
-        }
-        if (++chained == GC_CHAIN_TILES) {
-            flush();
-            chained = 0;
-        }
-    }
-    flush();
-
-    // the workgroup's four waves, wave 0 first, tile by tile through the waves' regions (one f64 tile each)
-    double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + GC_TAIL);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        __syncthreads();
-        double *mine = reinterpret_cast<double *>(region[wave]);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[t][g];
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 256) {
-            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
-                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
-            pout[(size_t)t * 1024 + e] = s;
-        }
-    }
-    cnt_sh[wave][lane] = cnt;
-    chg_sh[wave][lane] = chg;
-    __syncthreads();
-    if (threadIdx.x < GC_TAIL) {
-        const int t = threadIdx.x;
-        unsigned s = 0;
-        if (t < 32) {
-            for (int w = 0; w < 4; ++w) s += cnt_sh[w][t] + cnt_sh[w][t + 32];
-        } else if (t == 32) {
-            for (int w = 0; w < 4; ++w)
-                for (int l = 0; l < 32; ++l) s += chg_sh[w][l];
-        }
-        pout[NT * 1024 + t] = (double)s;
-    }
-}
-
-// out[i][c] = Phi[floor(i N / ns)][c], c < dim: the sample of rows the seeding draws from
-__global__ void k_cluster_sample(const float *__restrict__ phi, int64_t N, int ld, int64_t ns, int dim, float *__restrict__ out)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ns * dim) return;
-    const int64_t i = e / dim;
-    const int c = (int)(e % dim);
-    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
-    out[e] = phi[(size_t)px * ld + c];
-}
-
-template <int CW>
-static int launch_cluster(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, unsigned k, const float *d_operand,
-                          const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, unsigned *nblk_out)
-{
-    if (*per_cu <= 0) {
-        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, k_graph_cluster<CW>, 256, 0));
-        *per_cu = std::max(1, *per_cu);
-    }
-    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
-    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident); // (the rest of the tiles by the grid stride)
-    GLF_TRY(part.alloc(ctx, (size_t)nblk * gc_part_cols(CW)));
-    hipLaunchKernelGGL(k_graph_cluster<CW>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)ld, (int)k, d_operand, d_prev, d_labels,
-                       part.p);
-    GLF_LAUNCH_CHECK(ctx);
-    *nblk_out = (unsigned)nblk;
-    return GLF_OK;
-}
-
-static bool all_finite(const double *x, size_t n)
-{
-    for (size_t e = 0; e < n; ++e)
-        if (!std::isfinite(x[e])) return false;
-    return true;
-}
-
-// what glf_graph_cluster_step and glf_graph_segment refuse alike, before any device work
-static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
-{
-    if (!g || k == 0 || k > (unsigned)GC_K || dim == 0 || dim > std::min(g->m, 64u)) return false;
-    return !scale || all_finite(scale, dim);
-}
-
-// one Lloyd iteration on checked arguments (returns with the stream drained)
-static int cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev, int32_t *d_labels,
-                        double *h_sums, uint64_t *h_counts, uint64_t *changed)
-{
-    glf_ctx *ctx = g->ctx;
-    const unsigned ld = g->ld;
-    const int cw = gc_cw(ld);
-    const int64_t N = (int64_t)g->width * g->height;
-    std::vector<float> h_op(gc_operand_floats(cw), 0.f);
-    for (unsigned j = 0; j < k; ++j) {
-        double n2 = 0.0;
-        for (unsigned c = 0; c < dim; ++c) {
-            const double x = h_cent[(size_t)j * dim + c];
-            h_op[(size_t)c * GC_K + j] = (float)((scale ? scale[c] : 1.0) * x);
-            n2 += x * x;
-        }
-        h_op[(size_t)cw * GC_K + j] = (float)n2;
-    }
-    DevBuf<float> op;
-    DevBuf<double> part, tot;
-    GLF_TRY(op.alloc(ctx, h_op.size()));
-    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
-    unsigned nblk = 0;
-    if (cw == 32) GLF_TRY(launch_cluster<32>(ctx, &g->cluster_blocks_per_cu, g->phi, N, ld, k, op.p, d_prev, d_labels, part, &nblk));
-    else GLF_TRY(launch_cluster<64>(ctx, &g->cluster_blocks_per_cu, g->phi, N, ld, k, op.p, d_prev, d_labels, part, &nblk));
-    const size_t ncols = gc_part_cols(cw);
-    GLF_TRY(tot.alloc(ctx, ncols));
-    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
-    GLF_LAUNCH_CHECK(ctx);
-    std::vector<double> h_tot(ncols);
-    GLF_HIP(ctx, hipMemcpyAsync(h_tot.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
-    const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
-    for (unsigned j = 0; j < k; ++j) {
-        for (unsigned c = 0; c < dim; ++c) h_sums[(size_t)j * dim + c] = h_tot[(size_t)(c / 32) * 1024 + j * 32 + c % 32];
-        h_counts[j] = (uint64_t)tail[j];
-    }
-    *changed = d_prev ? (uint64_t)tail[32] : 0;
-    return GLF_OK;
-}
-
-// ---- unit-length rows and per-pixel weights ------------------------------------------------------------------------------------------
-// k_graph_cluster_nw: k_graph_cluster with the embedding e(px) = rinv(px) scale o Phi[px] and a weight plane in the update. The
-// staging, the MFMA shapes and the contraction order are k_graph_cluster's; what it adds:
-//   the per-call operand block grows by [CW] float fl32(scale_c), zero for c >= dim (gc_nw_operand_floats), kept in LDS;
-//   the 16 biases of a lane are read from LDS at every tile (bias_sh, +inf for j >= k; registers 4 q .. 4 q + 3 hold 16 consecutive
-//   bytes) instead of living in registers: with them in registers as in k_graph_cluster, CW 64 spilled 5 registers (24 bytes of scratch;
-//   profiles/graph_cluster_nw_kernel_resources.txt). The values, and so every score's bits, are the same;
-//   with `normalize`, lane (r, h) forms the squared length of its half row of pixel r from the float4s it reads anyway,
-//   n2 = fmaf(x, x, n2), x = fl32(scale_c) phi_c, in ascending column order; the halves are added through one __shfl_xor(.., 32) (a
-//   commutative sum: both half-waves hold the same bits) and rinv = n2 > 0 ? 1 / sqrtf(n2) : 0; without it rinv = 1 and none of this runs
-//   (NORM is a template argument: a run-time branch inside the unrolled contraction cuts it into one basic block per four MFMAs, and
-//   the LDS reads of the next step are then no longer issued under the MFMAs of this one);
-//   score = fmaf(-2 rinv, dot, |c_j|^2): with rinv = 1 the plain kernel's bits;
-//   t(px) = fl32(w(px) rinv(px)) and w(px) go to LDS beside the tile's 32 labels (w is loaded with the prefetch of the next tile, as
-//   prev is; NULL is w = 1), and the update's A operand is hit ? t[p] : 0: sums_j = sum w rinv Phi[px][c] over the members of j;
-//   lane (r, h) adds (double) w[p] over its hits: the mass of label r among the pixels of parity h. Counts and changed stay integers.
-// The partial's tail is GC_TAIL_NW doubles: counts [32], changed, zero padding up to 64, then the mass [32].
-constexpr int GC_TAIL_NW = 96;
-inline size_t gc_nw_operand_floats(int cw) { return gc_operand_floats(cw) + (size_t)cw; }
-inline size_t gc_nw_part_cols(int cw) { return (size_t)(cw / 32) * 1024 + GC_TAIL_NW; }
-
-template <int CW, bool NORM>
-__global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
-                                                             const float *__restrict__ weight, const int32_t *prev, int32_t *labels,
-                                                             double *__restrict__ part)
-{
-    constexpr int PITCH = CW + 4;
-    constexpr int FPR = CW / 4;
-    constexpr int NLOAD = CW / 8;
-    constexpr int NT = CW / 32;
-    constexpr int RW = 32 * PITCH > 2048 ? 32 * PITCH : 2048;
-    __shared__ __attribute__((aligned(16))) float a_sh[CW * GC_K];
-    __shared__ __attribute__((aligned(16))) float region[4][RW];
-    __shared__ __attribute__((aligned(16))) float s_sh[CW];
-    __shared__ __attribute__((aligned(16))) float bias_sh[GC_K];
-    __shared__ int lab_sh[4][32];
-    __shared__ float t_sh[4][32], w_sh[4][32];
-    __shared__ unsigned cnt_sh[4][64], chg_sh[4][64];
-    __shared__ double mass_sh[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int r = lane & 31, h = lane >> 5;
-    for (int e = threadIdx.x; e < CW * GC_K; e += 256) a_sh[e] = operand[e];
-    if (threadIdx.x < GC_K) bias_sh[threadIdx.x] = (int)threadIdx.x < k ? operand[CW * GC_K + threadIdx.x] : INFINITY;
-    if (threadIdx.x < CW) s_sh[threadIdx.x] = operand[CW * GC_K + GC_K + threadIdx.x];
-    __syncthreads();
-    float *tw = region[wave];
-    const int *lab = lab_sh[wave];
-    const float *tsh = t_sh[wave], *wsh = w_sh[wave];
-    const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
-
-    f32x16 acc[NT];
-    double dacc[NT][16];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-        for (int g = 0; g < 16; ++g) {
-            acc[t][g] = 0.f;
-            dacc[t][g] = 0.0;
-        }
-    unsigned cnt = 0, chg = 0;
-    double mass = 0.0;
-
-    float4 v[NLOAD];
-    int pv = 0;
-    float wv = 1.f;
-    auto load_tile = [&](int64_t tile) {
-        const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        if (h == 0 && base + r < N) {
-            if (prev) pv = prev[base + r];
-            if (weight) wv = weight[base + r];
-        }
-    };
-    auto flush = [&]() {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                dacc[t][g] += (double)acc[t][g];
-                acc[t][g] = 0.f;
-            }
-    };
-
-    int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntiles) load_tile(tile);
-    int chained = 0;
-    for (; tile < ntiles; tile += tstride) {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
-        }
-        const int pv_cur = pv;
         const float wv_cur = wv;
         __builtin_amdgcn_wave_barrier();
+        // the next tile's loads fly under this tile's MFMAs
         if (tile + tstride < ntiles) load_tile(tile + tstride);
 
         f32x16 sc;
@@ -404,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
             sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GC_K], b.y, sc, 0, 0, 0);
             sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GC_K], b.z, sc, 0, 0, 0);
             sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GC_K], b.w, sc, 0, 0, 0);
-            if constexpr (NORM) {
+            if constexpr (MODE == GC_NORM) {
                 const float4 s = *reinterpret_cast<const float4 *>(s_sh + h * (CW / 2) + 4 * u);
                 const float x0 = s.x * b.x, x1 = s.y * b.y, x2 = s.z * b.z, x3 = s.w * b.w;
                 n2 = fmaf(x0, x0, n2);
@@ -414,20 +192,20 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
             }
         }
         float rinv = 1.f;
-        if constexpr (NORM) {
+        if constexpr (MODE == GC_NORM) {
             n2 += __shfl_xor(n2, 32);
             rinv = n2 > 0.f ? 1.f / sqrtf(n2) : 0.f;
         }
         const float m2 = -2.f * rinv;
+        // half 0 always holds centroid 0 < k, so a label is in [0, k) even if no comparison holds
         float best = INFINITY;
         int bj = h ? 0x7fffffff : 0;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-            const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
-            const float s = fmaf(m2, sc[g], bias_sh[j]);
+            const float s = fmaf(m2, sc[g], bias_of(g));
             if (s < best) {
                 best = s;
-                bj = j;
+                bj = centroid_of(g);
             }
         }
         const float ob = __shfl_xor(best, 32);
@@ -437,8 +215,10 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
         if (h == 0) {
             const bool live = px < N;
             lab_sh[wave][r] = live ? bj : -1;
-            t_sh[wave][r] = wv_cur * rinv;
-            w_sh[wave][r] = wv_cur;
+            if constexpr (MODE != GC_PLAIN) {
+                t_sh[wave][r] = wv_cur * rinv;
+                w_sh[wave][r] = wv_cur;
+            }
             if (live) {
                 if (prev) chg += pv_cur != bj;
                 labels[px] = bj;
@@ -449,10 +229,11 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
         for (int u = 0; u < 16; ++u) {
             const int p = 2 * u + h;
             const bool hit = lab[p] == r;
-            const float tp = tsh[p], wp = wsh[p]; // (read whatever hit is: a branch here would cut the MFMA chain into blocks of two)
+            float tp = 1.f, wp = 0.f;
+            if constexpr (MODE != GC_PLAIN) tp = t_sh[wave][p], wp = w_sh[wave][p]; // (read whatever hit is: a branch here would cut the MFMA chain into blocks of two)
             const float a = hit ? tp : 0.f;
             cnt += hit;
-            mass += (double)(hit ? wp : 0.f);
+            if constexpr (MODE != GC_PLAIN) mass += (double)(hit ? wp : 0.f);
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + r], acc[0], 0, 0, 0);
             if constexpr (NT == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + 32 + r], acc[1], 0, 0, 0);
         }
@@ -463,7 +244,8 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
     }
     flush();
 
-    double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + GC_TAIL_NW);
+    // the workgroup's four waves, wave 0 first, tile by tile through the waves' regions (one f64 tile each)
+    double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + TAIL);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         __syncthreads();
@@ -479,9 +261,9 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
     }
     cnt_sh[wave][lane] = cnt;
     chg_sh[wave][lane] = chg;
-    mass_sh[wave][lane] = mass;
+    if constexpr (MODE != GC_PLAIN) mass_sh[wave][lane] = mass;
     __syncthreads();
-    if (threadIdx.x < GC_TAIL_NW) {
+    if (threadIdx.x < TAIL) {
         const int t = threadIdx.x;
         double out = 0.0;
         if (t < 32) {
@@ -493,11 +275,28 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster_nw(const float *__rest
             for (int w = 0; w < 4; ++w)
                 for (int l = 0; l < 32; ++l) s += chg_sh[w][l];
             out = (double)s;
-        } else if (t >= 64) {
-            for (int w = 0; w < 4; ++w) out += mass_sh[w][t - 64] + mass_sh[w][t - 32]; // wave 0 first, parity 0 before parity 1
+        } else if (t >= 64) { // (TAIL is 64 in GC_PLAIN: never taken there)
+            if constexpr (MODE != GC_PLAIN)
+                for (int w = 0; w < 4; ++w) out += mass_sh[w][t - 64] + mass_sh[w][t - 32]; // wave 0 first, parity 0 before parity 1
         }
         pout[NT * 1024 + t] = out;
     }
+}
+
+// the six instances, at [CW == 64][mode]
+using cluster_kernel = decltype(&k_graph_cluster<32, GC_PLAIN>);
+static const cluster_kernel GC_KERNELS[2][GC_MODES] = {{k_graph_cluster<32, GC_PLAIN>, k_graph_cluster<32, GC_WEIGHT>, k_graph_cluster<32, GC_NORM>},
+                                                       {k_graph_cluster<64, GC_PLAIN>, k_graph_cluster<64, GC_WEIGHT>, k_graph_cluster<64, GC_NORM>}};
+
+// out[i][c] = Phi[floor(i N / ns)][c], c < dim: the sample of rows the seeding draws from
+__global__ void k_cluster_sample(const float *__restrict__ phi, int64_t N, int ld, int64_t ns, int dim, float *__restrict__ out)
+{
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * dim) return;
+    const int64_t i = e / dim;
+    const int c = (int)(e % dim);
+    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
+    out[e] = phi[(size_t)px * ld + c];
 }
 
 // out[i] = w[floor(i N / ns)]: the weights of the rows k_cluster_sample gathers
@@ -507,39 +306,29 @@ __global__ void k_cluster_sample_w(const float *__restrict__ w, int64_t N, int64
     if (i < ns) out[i] = w[i * N / ns];
 }
 
-template <int CW, bool NORM>
-static int launch_cluster_nw(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, unsigned k, const float *d_operand,
-                             const float *d_weight, const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, unsigned *nblk_out)
+// what the steps and the drivers refuse alike, before any device work
+static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
 {
-    if (*per_cu <= 0) {
-        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, (k_graph_cluster_nw<CW, NORM>), 256, 0));
-        *per_cu = std::max(1, *per_cu);
-    }
-    const int64_t resident = (int64_t)*per_cu * std::max(1, ctx->prop.multiProcessorCount);
-    const int64_t nblk = std::min<int64_t>(ceil_div(ceil_div(N, 32), 4), resident);
-    GLF_TRY(part.alloc(ctx, (size_t)nblk * gc_nw_part_cols(CW)));
-    hipLaunchKernelGGL((k_graph_cluster_nw<CW, NORM>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)ld, (int)k, d_operand, d_weight,
-                       d_prev, d_labels, part.p);
-    GLF_LAUNCH_CHECK(ctx);
-    *nblk_out = (unsigned)nblk;
-    return GLF_OK;
+    if (!g || k == 0 || k > (unsigned)GC_K || dim == 0 || dim > std::min(g->m, 64u)) return false;
+    return !scale || all_finite(scale, dim);
 }
 
-static bool embed_plain(const glf_cluster_embed *emb) { return !emb || (emb->normalize == 0 && !emb->d_weight); }
 static bool embed_ok(const glf_cluster_embed *emb)
 {
     return !emb || (emb->struct_size == sizeof(glf_cluster_embed) && (emb->normalize == 0 || emb->normalize == 1));
 }
+static int embed_mode(const glf_cluster_embed *emb) { return !emb ? GC_PLAIN : emb->normalize ? GC_NORM : emb->d_weight ? GC_WEIGHT : GC_PLAIN; }
 
-// one Lloyd iteration with unit-length rows and / or a weight plane, on checked arguments (returns with the stream drained)
-static int cluster_step_nw(glf_graph *g, int normalize, const float *d_weight, unsigned k, unsigned dim, const double *h_cent, const double *scale,
-                           const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
+// one Lloyd iteration on checked arguments (returns with the stream drained). d_weight: NULL in GC_PLAIN, may be NULL in GC_NORM;
+// h_mass may be NULL; GC_PLAIN reports mass = (double) counts.
+static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned k, unsigned dim, const double *h_cent, const double *scale,
+                        const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
 {
     glf_ctx *ctx = g->ctx;
     const unsigned ld = g->ld;
     const int cw = gc_cw(ld);
     const int64_t N = (int64_t)g->width * g->height;
-    std::vector<float> h_op(gc_nw_operand_floats(cw), 0.f);
+    std::vector<float> h_op(gc_operand_floats(cw, mode), 0.f);
     for (unsigned j = 0; j < k; ++j) {
         double n2 = 0.0;
         for (unsigned c = 0; c < dim; ++c) {
@@ -549,143 +338,54 @@ static int cluster_step_nw(glf_graph *g, int normalize, const float *d_weight, u
         }
         h_op[(size_t)cw * GC_K + j] = (float)n2;
     }
-    for (unsigned c = 0; c < dim; ++c) h_op[gc_operand_floats(cw) + c] = (float)(scale ? scale[c] : 1.0);
+    for (unsigned c = 0; mode == GC_NORM && c < dim; ++c) h_op[(size_t)cw * GC_K + GC_K + c] = (float)(scale ? scale[c] : 1.0);
     DevBuf<float> op;
     DevBuf<double> part, tot;
     GLF_TRY(op.alloc(ctx, h_op.size()));
     GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
-    unsigned nblk = 0;
-    int *per_cu = &g->cluster_nw_blocks_per_cu[normalize ? 1 : 0];
-    if (cw == 32 && normalize) GLF_TRY((launch_cluster_nw<32, true>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
-    else if (cw == 32) GLF_TRY((launch_cluster_nw<32, false>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
-    else if (normalize) GLF_TRY((launch_cluster_nw<64, true>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
-    else GLF_TRY((launch_cluster_nw<64, false>(ctx, per_cu, g->phi, N, ld, k, op.p, d_weight, d_prev, d_labels, part, &nblk)));
-    const size_t ncols = gc_nw_part_cols(cw);
+    const cluster_kernel kernel = GC_KERNELS[cw == 64][mode];
+    const size_t ncols = gc_part_cols(cw, mode);
+    int64_t nblk = 0;
+    GLF_TRY(resident_tile_grid(ctx, &g->cluster_blocks_per_cu[mode], kernel, N, &nblk));
+    GLF_TRY(part.alloc(ctx, (size_t)nblk * ncols));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)k, op.p, d_weight, d_prev, d_labels, part.p);
+    GLF_LAUNCH_CHECK(ctx);
     GLF_TRY(tot.alloc(ctx, ncols));
     hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
     GLF_LAUNCH_CHECK(ctx);
     std::vector<double> h_tot(ncols);
     GLF_HIP(ctx, hipMemcpyAsync(h_tot.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration)
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
     const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
     for (unsigned j = 0; j < k; ++j) {
         for (unsigned c = 0; c < dim; ++c) h_sums[(size_t)j * dim + c] = h_tot[(size_t)(c / 32) * 1024 + j * 32 + c % 32];
         h_counts[j] = (uint64_t)tail[j];
-        h_mass[j] = tail[64 + j];
+        if (h_mass) h_mass[j] = mode == GC_PLAIN ? (double)h_counts[j] : tail[64 + j];
     }
     *changed = d_prev ? (uint64_t)tail[32] : 0;
     return GLF_OK;
 }
 
-} // namespace glf
-
-using namespace glf;
-
-extern "C" {
-
-int glf_graph_cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev,
-                           int32_t *d_labels, double *h_sums, uint64_t *h_counts, uint64_t *changed)
-{
-    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !changed) return GLF_ERR_INVALID;
-    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
-        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k, dim,
-                         g->m);
-    GLF_ENTER(g->ctx);
-    return cluster_step(g, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, changed);
-}
-
-int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_labels, double *h_cent, glf_segment_stats *stats)
-{
-    if (!g || !opt || !d_labels || !h_cent || opt->struct_size != sizeof(glf_segment_options)) return GLF_ERR_INVALID;
-    glf_ctx *ctx = g->ctx;
-    const unsigned k = opt->k, dim = opt->dim;
-    const double *scale = opt->scale;
-    if (!cluster_shape_ok(g, k, dim, scale) || (opt->init != 0 && opt->init != 1) || (opt->init == 1 && !all_finite(h_cent, (size_t)k * dim)))
-        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment: k=%u dim=%u (m=%u) init=%d, or a centroid or scale entry that is not finite", k, dim,
-                         g->m, opt->init);
-    const unsigned max_iter = opt->max_iter ? opt->max_iter : 50;
-    const int64_t N = (int64_t)g->width * g->height;
-    GLF_ENTER(ctx);
-    std::vector<double> cent((size_t)k * dim);
-    if (opt->init == 0) {
-        const int64_t ns = std::min<int64_t>(opt->sample_rows ? opt->sample_rows : 4096, N);
-        const size_t cnt = (size_t)ns * dim;
-        DevBuf<float> d_rows;
-        GLF_TRY(d_rows.alloc(ctx, cnt));
-        hipLaunchKernelGGL(k_cluster_sample, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, ns, (int)dim,
-                           d_rows.p);
-        GLF_LAUNCH_CHECK(ctx);
-        std::vector<float> h_rows(cnt);
-        GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
-        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<double> rows(cnt);
-        for (size_t e = 0; e < cnt; ++e) rows[e] = (scale ? scale[e % dim] : 1.0) * (double)h_rows[e];
-        if (glf_cluster_seed(rows.data(), (size_t)ns, dim, k, opt->seed, cent.data()) != GLF_OK)
-            return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment: the sample of %lld rows holds fewer than %u distinct rows", (long long)ns, k);
-    } else
-        std::copy(h_cent, h_cent + (size_t)k * dim, cent.begin());
-    std::vector<double> sums((size_t)k * dim);
-    uint64_t counts[GC_K] = {0}, changed = 0;
-    unsigned it = 0;
-    int converged = 0;
-    while (it < max_iter && !converged) {
-        GLF_TRY(cluster_step(g, k, dim, cent.data(), scale, it ? d_labels : nullptr, d_labels, sums.data(), counts, &changed));
-        converged = it > 0 && changed == 0;
-        ++it;
-        GLF_TRY(glf_cluster_update(k, dim, scale, sums.data(), counts, cent.data(), cent.data()));
-    }
-    std::copy(cent.begin(), cent.end(), h_cent);
-    if (stats) {
-        stats->iterations = it;
-        stats->converged = converged;
-        stats->changed_last = changed;
-        for (int j = 0; j < GC_K; ++j) stats->counts[j] = j < (int)k ? counts[j] : 0;
-    }
-    return GLF_OK;
-}
-
-int glf_graph_cluster_step_ex(glf_graph *g, const glf_cluster_embed *emb, unsigned k, unsigned dim, const double *h_cent, const double *scale,
-                              const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
-{
-    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !h_mass || !changed) return GLF_ERR_INVALID;
-    if (!embed_ok(emb))
-        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: struct_size=%u (want %zu) normalize=%d", emb->struct_size,
-                         sizeof(glf_cluster_embed), emb->normalize);
-    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
-        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k,
-                         dim, g->m);
-    GLF_ENTER(g->ctx);
-    if (embed_plain(emb)) {
-        GLF_TRY(cluster_step(g, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, changed));
-        for (unsigned j = 0; j < k; ++j) h_mass[j] = (double)h_counts[j];
-        return GLF_OK;
-    }
-    return cluster_step_nw(g, emb->normalize, emb->d_weight, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, h_mass, changed);
-}
-
-int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels, double *h_cent,
-                         glf_segment_stats *stats, double *h_mass)
+// The driver behind glf_graph_segment (emb and h_mass NULL) and glf_graph_segment_ex, errors reported under `name`: the seeding on
+// a sample of rows (embedded in f64 as the kernel embeds them, with the sample's weights), then cluster_step + glf_cluster_update_w
+// until a step moves no label. Without a weight plane the mass is the count, an integer below 2^53, and glf_cluster_update_w and
+// glf_cluster_seed_w(w = NULL) are glf_cluster_update and glf_cluster_seed bit for bit.
+static int segment_run(const char *name, glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels,
+                       double *h_cent, glf_segment_stats *stats, double *h_mass)
 {
     if (!g || !opt || !d_labels || !h_cent || opt->struct_size != sizeof(glf_segment_options)) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
     if (!embed_ok(emb))
-        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment_ex: struct_size=%u (want %zu) normalize=%d", emb->struct_size, sizeof(glf_cluster_embed),
+        return set_error(ctx, GLF_ERR_INVALID, "%s: struct_size=%u (want %zu) normalize=%d", name, emb->struct_size, sizeof(glf_cluster_embed),
                          emb->normalize);
-    if (embed_plain(emb)) {
-        glf_segment_stats st;
-        const int rc = glf_graph_segment(g, opt, d_labels, h_cent, &st);
-        if (rc != GLF_OK) return rc;
-        if (stats) *stats = st;
-        for (unsigned j = 0; h_mass && j < opt->k; ++j) h_mass[j] = (double)st.counts[j];
-        return GLF_OK;
-    }
     const unsigned k = opt->k, dim = opt->dim;
     const double *scale = opt->scale;
-    const int normalize = emb->normalize;
-    const float *d_weight = emb->d_weight;
+    const int mode = embed_mode(emb);
+    const bool normalize = mode == GC_NORM;
+    const float *d_weight = emb ? emb->d_weight : nullptr;
     if (!cluster_shape_ok(g, k, dim, scale) || (opt->init != 0 && opt->init != 1) || (opt->init == 1 && !all_finite(h_cent, (size_t)k * dim)))
-        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_segment_ex: k=%u dim=%u (m=%u) init=%d, or a centroid or scale entry that is not finite", k,
-                         dim, g->m, opt->init);
+        return set_error(ctx, GLF_ERR_INVALID, "%s: k=%u dim=%u (m=%u) init=%d, or a centroid or scale entry that is not finite", name, k, dim, g->m,
+                         opt->init);
     const unsigned max_iter = opt->max_iter ? opt->max_iter : 50;
     const int64_t N = (int64_t)g->width * g->height;
     GLF_ENTER(ctx);
@@ -716,14 +416,12 @@ int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf
                 row[c] = (scale ? scale[c] : 1.0) * (double)h_rows[(size_t)i * dim + c];
                 n2 += row[c] * row[c];
             }
-            const double rinv = !normalize ? 1.0 : n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
+            const double rinv = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
             for (unsigned c = 0; normalize && c < dim; ++c) row[c] *= rinv;
         }
         if (glf_cluster_seed_w(rows.data(), d_weight ? ws.data() : nullptr, (size_t)ns, dim, k, opt->seed, cent.data()) != GLF_OK)
-            return set_error(ctx, GLF_ERR_INVALID,
-                             "glf_graph_segment_ex: the sample of %lld rows holds fewer than %u distinct rows of positive weight, or a weight that is "
-                             "negative or not finite",
-                             (long long)ns, k);
+            return set_error(ctx, GLF_ERR_INVALID, "%s: the sample of %lld rows holds fewer than %u distinct rows%s", name, (long long)ns, k,
+                             d_weight ? " of positive weight, or a weight that is negative or not finite" : "");
     } else
         std::copy(h_cent, h_cent + (size_t)k * dim, cent.begin());
     std::vector<double> sums((size_t)k * dim);
@@ -732,8 +430,7 @@ int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf
     unsigned it = 0;
     int converged = 0;
     while (it < max_iter && !converged) {
-        GLF_TRY(cluster_step_nw(g, normalize, d_weight, k, dim, cent.data(), scale, it ? d_labels : nullptr, d_labels, sums.data(), counts, mass,
-                                &changed));
+        GLF_TRY(cluster_step(g, mode, d_weight, k, dim, cent.data(), scale, it ? d_labels : nullptr, d_labels, sums.data(), counts, mass, &changed));
         converged = it > 0 && changed == 0;
         ++it;
         GLF_TRY(glf_cluster_update_w(k, dim, scale, sums.data(), mass, cent.data(), cent.data()));
@@ -747,6 +444,48 @@ int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf
     }
     if (h_mass) std::copy(mass, mass + k, h_mass);
     return GLF_OK;
+}
+
+} // namespace glf
+
+using namespace glf;
+
+extern "C" {
+
+int glf_graph_cluster_step(glf_graph *g, unsigned k, unsigned dim, const double *h_cent, const double *scale, const int32_t *d_prev,
+                           int32_t *d_labels, double *h_sums, uint64_t *h_counts, uint64_t *changed)
+{
+    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !changed) return GLF_ERR_INVALID;
+    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k, dim,
+                         g->m);
+    GLF_ENTER(g->ctx);
+    return cluster_step(g, GC_PLAIN, nullptr, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, nullptr, changed);
+}
+
+int glf_graph_cluster_step_ex(glf_graph *g, const glf_cluster_embed *emb, unsigned k, unsigned dim, const double *h_cent, const double *scale,
+                              const int32_t *d_prev, int32_t *d_labels, double *h_sums, uint64_t *h_counts, double *h_mass, uint64_t *changed)
+{
+    if (!g || !h_cent || !d_labels || !h_sums || !h_counts || !h_mass || !changed) return GLF_ERR_INVALID;
+    if (!embed_ok(emb))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: struct_size=%u (want %zu) normalize=%d", emb->struct_size,
+                         sizeof(glf_cluster_embed), emb->normalize);
+    if (!cluster_shape_ok(g, k, dim, scale) || !all_finite(h_cent, (size_t)k * dim))
+        return set_error(g->ctx, GLF_ERR_INVALID, "glf_graph_cluster_step_ex: k=%u dim=%u (m=%u), or a centroid or scale entry that is not finite", k,
+                         dim, g->m);
+    GLF_ENTER(g->ctx);
+    return cluster_step(g, embed_mode(emb), emb ? emb->d_weight : nullptr, k, dim, h_cent, scale, d_prev, d_labels, h_sums, h_counts, h_mass, changed);
+}
+
+int glf_graph_segment(glf_graph *g, const glf_segment_options *opt, int32_t *d_labels, double *h_cent, glf_segment_stats *stats)
+{
+    return segment_run("glf_graph_segment", g, opt, nullptr, d_labels, h_cent, stats, nullptr);
+}
+
+int glf_graph_segment_ex(glf_graph *g, const glf_segment_options *opt, const glf_cluster_embed *emb, int32_t *d_labels, double *h_cent,
+                         glf_segment_stats *stats, double *h_mass)
+{
+    return segment_run("glf_graph_segment_ex", g, opt, emb, d_labels, h_cent, stats, h_mass);
 }
 
 } // extern "C"

@@ -42,6 +42,69 @@ struct Xoshiro256ss {
     double uniform() { return (double)(next() >> 11) * (1.0 / 9007199254740992.0); } // [0,1)
 };
 
+// The centroid update of one Lloyd iteration: the mean of a label's raw rows of Phi, moved into the embedding by scale. div is the
+// label's count (glf_cluster_update) or its mass (glf_cluster_update_w: the weighted mean); a label with !(div_j > 0) keeps cent_prev_j.
+template <class T>
+int cluster_update(unsigned k, unsigned dim, const double *scale, const double *sums, const T *div, const double *cent_prev, double *cent)
+{
+    if (!sums || !div || !cent || k == 0 || dim == 0) return GLF_ERR_INVALID;
+    if (!cent_prev)
+        for (unsigned j = 0; j < k; ++j)
+            if (!(div[j] > 0)) return GLF_ERR_INVALID;
+    for (unsigned j = 0; j < k; ++j)
+        for (unsigned c = 0; c < dim; ++c) {
+            const size_t e = (size_t)j * dim + c;
+            cent[e] = div[j] > 0 ? (scale ? scale[c] : 1.0) * sums[e] / (double)div[j] : cent_prev[e];
+        }
+    return GLF_OK;
+}
+
+// k-means++ (Arthur & Vassilvitskii 2007) on the library's own uniform stream, so that a seed names one set of centres. Every row's
+// chance is multiplied by its weight w[i] (checked by the caller: >= 0 and finite), NULL meaning 1. A draw takes the first row, in
+// row order, whose running sum of the chances exceeds u times their total; with all weights 1 the first centre is then row
+// min(n - 1, floor(u n)), and 1.0 * D^2 is exact.
+int cluster_seed(const double *rows, const double *w, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
+{
+    if (!rows || !cent || n == 0 || dim == 0 || k == 0 || k > n) return GLF_ERR_INVALID;
+    auto wt = [&](size_t i) { return w ? w[i] : 1.0; };
+    double wtotal = 0.0;
+    for (size_t i = 0; i < n; ++i) wtotal += wt(i);
+    if (!(wtotal > 0.0) || !std::isfinite(wtotal)) return GLF_ERR_INVALID;
+    Xoshiro256ss rng(seed);
+    std::vector<size_t> chosen(k);
+    std::vector<double> d2(n);
+    auto draw = [&](auto wd, double total) { // (total > 0: some wd[i] > 0)
+        const double target = rng.uniform() * total;
+        size_t pick = n;
+        double run = 0.0;
+        for (size_t i = 0; i < n && pick == n; ++i) {
+            run += wd(i);
+            if (run > target) pick = i;
+        }
+        if (pick == n) // (run ends at total; reached only where u total rounds up to total: the last row with a chance)
+            for (pick = n - 1; pick > 0 && !(wd(pick) > 0.0);) --pick;
+        return pick;
+    };
+    chosen[0] = draw(wt, wtotal);
+    for (unsigned t = 1; t < k; ++t) {
+        const double *c = rows + chosen[t - 1] * dim;
+        double total = 0.0;
+        for (size_t i = 0; i < n; ++i) {
+            double d = 0.0;
+            for (unsigned q = 0; q < dim; ++q) {
+                const double x = rows[i * dim + q] - c[q];
+                d += x * x;
+            }
+            d2[i] = t == 1 ? d : std::min(d2[i], d);
+            total += wt(i) * d2[i];
+        }
+        if (!(total > 0.0) || !std::isfinite(total)) return GLF_ERR_INVALID; // fewer than k distinct rows of positive weight (or a NaN / Inf)
+        chosen[t] = draw([&](size_t i) { return wt(i) * d2[i]; }, total);
+    }
+    for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
+    return GLF_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -203,119 +266,28 @@ int glf_band_plan(const int *rows, int nr, const int *cols, int nc, float h_loc,
     return GLF_OK;
 }
 
-// The centroid update of one Lloyd iteration: the mean of a label's raw rows of Phi, moved into the embedding by scale.
 int glf_cluster_update(unsigned k, unsigned dim, const double *scale, const double *sums, const uint64_t *counts, const double *cent_prev,
                        double *cent)
 {
-    if (!sums || !counts || !cent || k == 0 || dim == 0) return GLF_ERR_INVALID;
-    if (!cent_prev)
-        for (unsigned j = 0; j < k; ++j)
-            if (counts[j] == 0) return GLF_ERR_INVALID;
-    for (unsigned j = 0; j < k; ++j)
-        for (unsigned c = 0; c < dim; ++c) {
-            const size_t e = (size_t)j * dim + c;
-            cent[e] = counts[j] ? (scale ? scale[c] : 1.0) * sums[e] / (double)counts[j] : cent_prev[e];
-        }
-    return GLF_OK;
+    return cluster_update(k, dim, scale, sums, counts, cent_prev, cent);
 }
 
-// k-means++ (Arthur & Vassilvitskii 2007) on the library's own uniform stream, so that a seed names one set of centres.
-int glf_cluster_seed(const double *rows, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
-{
-    if (!rows || !cent || n == 0 || dim == 0 || k == 0 || k > n) return GLF_ERR_INVALID;
-    Xoshiro256ss rng(seed);
-    std::vector<size_t> chosen(k);
-    std::vector<double> d2(n);
-    chosen[0] = std::min(n - 1, (size_t)(rng.uniform() * (double)n));
-    for (unsigned t = 1; t < k; ++t) {
-        const double *c = rows + chosen[t - 1] * dim;
-        double total = 0.0;
-        for (size_t i = 0; i < n; ++i) {
-            double d = 0.0;
-            for (unsigned q = 0; q < dim; ++q) {
-                const double x = rows[i * dim + q] - c[q];
-                d += x * x;
-            }
-            d2[i] = t == 1 ? d : std::min(d2[i], d);
-            total += d2[i];
-        }
-        if (!(total > 0.0) || !std::isfinite(total)) return GLF_ERR_INVALID; // fewer than k distinct rows (or a NaN / Inf)
-        const double target = rng.uniform() * total;
-        size_t pick = n;
-        double run = 0.0;
-        for (size_t i = 0; i < n && pick == n; ++i) {
-            run += d2[i];
-            if (run > target) pick = i;
-        }
-        if (pick == n) // (run ends at total > target; unreachable, kept so that no index leaves the rows)
-            for (pick = n - 1; pick > 0 && !(d2[pick] > 0.0);) --pick;
-        chosen[t] = pick;
-    }
-    for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
-    return GLF_OK;
-}
-
-// glf_cluster_update with a mass in place of the count: the weighted mean of a label's rows.
 int glf_cluster_update_w(unsigned k, unsigned dim, const double *scale, const double *sums, const double *mass, const double *cent_prev,
                          double *cent)
 {
-    if (!sums || !mass || !cent || k == 0 || dim == 0) return GLF_ERR_INVALID;
-    if (!cent_prev)
-        for (unsigned j = 0; j < k; ++j)
-            if (!(mass[j] > 0.0)) return GLF_ERR_INVALID;
-    for (unsigned j = 0; j < k; ++j)
-        for (unsigned c = 0; c < dim; ++c) {
-            const size_t e = (size_t)j * dim + c;
-            cent[e] = mass[j] > 0.0 ? (scale ? scale[c] : 1.0) * sums[e] / mass[j] : cent_prev[e];
-        }
-    return GLF_OK;
+    return cluster_update(k, dim, scale, sums, mass, cent_prev, cent);
 }
 
-// glf_cluster_seed with every row's chance multiplied by its weight.
+int glf_cluster_seed(const double *rows, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
+{
+    return cluster_seed(rows, nullptr, n, dim, k, seed, cent);
+}
+
 int glf_cluster_seed_w(const double *rows, const double *w, size_t n, unsigned dim, unsigned k, uint64_t seed, double *cent)
 {
-    if (!w) return glf_cluster_seed(rows, n, dim, k, seed, cent);
-    if (!rows || !cent || n == 0 || dim == 0 || k == 0 || k > n) return GLF_ERR_INVALID;
-    double wtotal = 0.0;
-    for (size_t i = 0; i < n; ++i) {
+    for (size_t i = 0; w && i < n; ++i)
         if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return GLF_ERR_INVALID;
-        wtotal += w[i];
-    }
-    if (!(wtotal > 0.0) || !std::isfinite(wtotal)) return GLF_ERR_INVALID;
-    Xoshiro256ss rng(seed);
-    std::vector<size_t> chosen(k);
-    std::vector<double> d2(n);
-    // the first row, in row order, whose running sum of wd exceeds u times total (total > 0: some wd[i] > 0)
-    auto draw = [&](auto wd, double total) {
-        const double target = rng.uniform() * total;
-        size_t pick = n;
-        double run = 0.0;
-        for (size_t i = 0; i < n && pick == n; ++i) {
-            run += wd(i);
-            if (run > target) pick = i;
-        }
-        if (pick == n) // (run ends at total > target; unreachable, kept so that no index leaves the rows)
-            for (pick = n - 1; pick > 0 && !(wd(pick) > 0.0);) --pick;
-        return pick;
-    };
-    chosen[0] = draw([&](size_t i) { return w[i]; }, wtotal);
-    for (unsigned t = 1; t < k; ++t) {
-        const double *c = rows + chosen[t - 1] * dim;
-        double total = 0.0;
-        for (size_t i = 0; i < n; ++i) {
-            double d = 0.0;
-            for (unsigned q = 0; q < dim; ++q) {
-                const double x = rows[i * dim + q] - c[q];
-                d += x * x;
-            }
-            d2[i] = t == 1 ? d : std::min(d2[i], d);
-            total += w[i] * d2[i];
-        }
-        if (!(total > 0.0) || !std::isfinite(total)) return GLF_ERR_INVALID; // fewer than k distinct rows of positive weight (or a NaN / Inf)
-        chosen[t] = draw([&](size_t i) { return w[i] * d2[i]; }, total);
-    }
-    for (unsigned t = 0; t < k; ++t) std::copy(rows + chosen[t] * dim, rows + (chosen[t] + 1) * dim, cent + (size_t)t * dim);
-    return GLF_OK;
+    return cluster_seed(rows, w, n, dim, k, seed, cent);
 }
 
 // The change of basis that makes Phi orthonormal, from its Gram matrix alone (the one-shot orthogonalisation of Fowlkes, Belongie,

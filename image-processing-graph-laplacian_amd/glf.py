@@ -453,21 +453,26 @@ def _scale(scale, dim):
     return scale
 
 
-def cluster_update(sums, counts, scale=None, cent_prev=None):
-    """glf_cluster_update (host only): cent_j = scale o sums_j / counts_j of one Lloyd iteration; an empty cluster keeps cent_prev_j.
-    sums [k, dim] (the sums of the raw rows of Phi per label), counts [k], scale [dim] or None (= 1), cent_prev [k, dim] (may be
-    None when no cluster is empty) -> cent [k, dim]."""
+def _update_args(name, sums, div, div_name, div_dtype, scale, cent_prev):
+    """What cluster_update and cluster_update_w check and make contiguous alike -> (k, dim, scale, sums, div, cent_prev, the cent to fill)."""
     sums = np.ascontiguousarray(sums, dtype=np.float64)
-    counts = np.ascontiguousarray(counts, dtype=np.uint64)
-    if sums.ndim != 2 or counts.shape != (sums.shape[0],):
-        raise ValueError("cluster_update: sums %s, counts %s" % (sums.shape, counts.shape))
+    div = np.ascontiguousarray(div, dtype=div_dtype)
+    if sums.ndim != 2 or div.shape != (sums.shape[0],):
+        raise ValueError("%s: sums %s, %s %s" % (name, sums.shape, div_name, div.shape))
     k, dim = sums.shape
     scale = _scale(scale, dim)
     if cent_prev is not None:
         cent_prev = np.ascontiguousarray(cent_prev, dtype=np.float64)
         if cent_prev.shape != (k, dim):
-            raise ValueError("cluster_update: cent_prev must be [%d, %d]" % (k, dim))
-    cent = np.zeros((k, dim), dtype=np.float64)
+            raise ValueError("%s: cent_prev must be [%d, %d]" % (name, k, dim))
+    return k, dim, scale, sums, div, cent_prev, np.zeros((k, dim), dtype=np.float64)
+
+
+def cluster_update(sums, counts, scale=None, cent_prev=None):
+    """glf_cluster_update (host only): cent_j = scale o sums_j / counts_j of one Lloyd iteration; an empty cluster keeps cent_prev_j.
+    sums [k, dim] (the sums of the raw rows of Phi per label), counts [k], scale [dim] or None (= 1), cent_prev [k, dim] (may be
+    None when no cluster is empty) -> cent [k, dim]."""
+    k, dim, scale, sums, counts, cent_prev, cent = _update_args("cluster_update", sums, counts, "counts", np.uint64, scale, cent_prev)
     rc = _lib.glf_cluster_update(C.c_uint(k), C.c_uint(dim), _ptr(scale), _ptr(sums), _ptr(counts), _ptr(cent_prev), _ptr(cent))
     if rc != OK:
         raise GlfError(rc, "glf_cluster_update(k=%d, dim=%d): an empty cluster without cent_prev, or an empty shape" % (k, dim))
@@ -478,36 +483,31 @@ def cluster_update_w(sums, mass, scale=None, cent_prev=None):
     """glf_cluster_update_w (host only): cent_j = scale o sums_j / mass_j, the weighted mean of one Lloyd iteration under a weight
     plane; a cluster with !(mass_j > 0) keeps cent_prev_j. sums [k, dim], mass [k] floats, scale [dim] or None (= 1), cent_prev
     [k, dim] (may be None when every mass is positive) -> cent [k, dim]."""
-    sums = np.ascontiguousarray(sums, dtype=np.float64)
-    mass = np.ascontiguousarray(mass, dtype=np.float64)
-    if sums.ndim != 2 or mass.shape != (sums.shape[0],):
-        raise ValueError("cluster_update_w: sums %s, mass %s" % (sums.shape, mass.shape))
-    k, dim = sums.shape
-    scale = _scale(scale, dim)
-    if cent_prev is not None:
-        cent_prev = np.ascontiguousarray(cent_prev, dtype=np.float64)
-        if cent_prev.shape != (k, dim):
-            raise ValueError("cluster_update_w: cent_prev must be [%d, %d]" % (k, dim))
-    cent = np.zeros((k, dim), dtype=np.float64)
+    k, dim, scale, sums, mass, cent_prev, cent = _update_args("cluster_update_w", sums, mass, "mass", np.float64, scale, cent_prev)
     rc = _lib.glf_cluster_update_w(C.c_uint(k), C.c_uint(dim), _ptr(scale), _ptr(sums), _ptr(mass), _ptr(cent_prev), _ptr(cent))
     if rc != OK:
         raise GlfError(rc, "glf_cluster_update_w(k=%d, dim=%d): a cluster of mass 0 without cent_prev, or an empty shape" % (k, dim))
     return cent
 
 
-def cluster_seed_w(rows, weight, k, seed=1):
-    """glf_cluster_seed_w (host only): k-means++ among rows [n, dim] with probability proportional to weight * D^2, on the uniforms of
-    cluster_seed; the first centre is the first row whose running sum of the weights exceeds u_0 times their total. weight [n]
-    (>= 0, finite), or None for cluster_seed itself -> cent [k, dim]."""
+def _seed_args(name, rows, k, weight=None):
+    """What cluster_seed and cluster_seed_w check and make contiguous alike -> (rows, weight, n, dim, the cent [k, dim] to fill)."""
     rows = np.ascontiguousarray(rows, dtype=np.float64)
     if rows.ndim != 2:
-        raise ValueError("cluster_seed_w: rows must be [n, dim], got %s" % (rows.shape,))
+        raise ValueError("%s: rows must be [n, dim], got %s" % (name, rows.shape))
     n, dim = rows.shape
     if weight is not None:
         weight = np.ascontiguousarray(weight, dtype=np.float64)
         if weight.shape != (n,):
-            raise ValueError("cluster_seed_w: weight must be [%d], got %s" % (n, weight.shape))
-    cent = np.zeros((max(int(k), 0), dim), dtype=np.float64)
+            raise ValueError("%s: weight must be [%d], got %s" % (name, n, weight.shape))
+    return rows, weight, n, dim, np.zeros((max(int(k), 0), dim), dtype=np.float64)
+
+
+def cluster_seed_w(rows, weight, k, seed=1):
+    """glf_cluster_seed_w (host only): k-means++ among rows [n, dim] with probability proportional to weight * D^2, on the uniforms of
+    cluster_seed; the first centre is the first row whose running sum of the weights exceeds u_0 times their total. weight [n]
+    (>= 0, finite), or None for cluster_seed itself -> cent [k, dim]."""
+    rows, weight, n, dim, cent = _seed_args("cluster_seed_w", rows, k, weight)
     rc = _lib.glf_cluster_seed_w(_ptr(rows), _ptr(weight), C.c_size_t(n), C.c_uint(dim), C.c_uint(k), C.c_uint64(seed), _ptr(cent))
     if rc != OK:
         raise GlfError(rc, "glf_cluster_seed_w(n=%d, dim=%d, k=%d): fewer than k distinct rows of positive weight, a weight that is negative "
@@ -518,11 +518,7 @@ def cluster_seed_w(rows, weight, k, seed=1):
 def cluster_seed(rows, k, seed=1):
     """glf_cluster_seed (host only): k-means++ seeding of k centres among rows [n, dim] on the uniforms random_vectors(k, 1, seed)
     exposes -> cent [k, dim]. Fewer than k distinct rows raise GlfError(ERR_INVALID)."""
-    rows = np.ascontiguousarray(rows, dtype=np.float64)
-    if rows.ndim != 2:
-        raise ValueError("cluster_seed: rows must be [n, dim], got %s" % (rows.shape,))
-    n, dim = rows.shape
-    cent = np.zeros((max(int(k), 0), dim), dtype=np.float64)
+    rows, _, n, dim, cent = _seed_args("cluster_seed", rows, k)
     rc = _lib.glf_cluster_seed(_ptr(rows), C.c_size_t(n), C.c_uint(dim), C.c_uint(k), C.c_uint64(seed), _ptr(cent))
     if rc != OK:
         raise GlfError(rc, "glf_cluster_seed(n=%d, dim=%d, k=%d): fewer than k distinct rows, or an empty shape" % (n, dim, k))
@@ -1563,21 +1559,25 @@ class Graph:
         with t.cuda.stream(self.ctx.stream):
             return t.empty((self.info["height"], self.info["width"]), dtype=t.int32, device=self.ctx.device)   # (every element is written)
 
-    def cluster_step(self, cent, scale=None, prev=None, labels=None):
-        """One Lloyd iteration of k-means over the embedded rows e(px) = scale o Phi[px][:dim] in one pass over Phi
-        (glf_graph_cluster_step): every pixel takes the nearest of the centroids cent [k, dim] (embedding space; k <= 32,
-        dim <= min(m, 64); the lowest index wins a tie). scale [dim] or None (= 1); prev: device int32 [H, W] labels to count the
-        changes against, or None; labels: the device int32 [H, W] tensor to write (it may be prev itself), or None for a new one.
-        -> (labels, sums [k, dim] of the raw rows of Phi per label, counts uint64 [k], changed)."""
+    def _step_args(self, cent, scale, prev, labels):
+        """What cluster_step and cluster_step_ex prepare alike -> (k, dim, cent, scale, prev's pointer or None, labels, sums, counts, changed)."""
         cent = np.ascontiguousarray(np.atleast_2d(np.asarray(cent, dtype=np.float64)))
         k, dim = cent.shape
         scale = _scale(scale, dim)
         if prev is not None:
             prev = self._labels(prev, "prev")
         labels = self._new_labels() if labels is None else self._labels(labels, "labels")
-        sums, counts, changed = np.zeros((k, dim), dtype=np.float64), np.zeros(k, dtype=np.uint64), C.c_uint64(0)
-        self.ctx._check(_lib.glf_graph_cluster_step(self._g, C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale),
-                                                    C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(labels.data_ptr()),
+        return (k, dim, cent, scale, C.c_void_p(prev.data_ptr()) if prev is not None else None, labels, np.zeros((k, dim), dtype=np.float64),
+                np.zeros(k, dtype=np.uint64), C.c_uint64(0))
+
+    def cluster_step(self, cent, scale=None, prev=None, labels=None):
+        """One Lloyd iteration of k-means over the embedded rows e(px) = scale o Phi[px][:dim] in one pass over Phi
+        (glf_graph_cluster_step): every pixel takes the nearest of the centroids cent [k, dim] (embedding space; k <= 32,
+        dim <= min(m, 64); the lowest index wins a tie). scale [dim] or None (= 1); prev: device int32 [H, W] labels to count the
+        changes against, or None; labels: the device int32 [H, W] tensor to write (it may be prev itself), or None for a new one.
+        -> (labels, sums [k, dim] of the raw rows of Phi per label, counts uint64 [k], changed)."""
+        k, dim, cent, scale, prev, labels, sums, counts, changed = self._step_args(cent, scale, prev, labels)
+        self.ctx._check(_lib.glf_graph_cluster_step(self._g, C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale), prev, C.c_void_p(labels.data_ptr()),
                                                     _ptr(sums), _ptr(counts), C.byref(changed)), "graph cluster step")   # (returns with the stream drained)
         return labels, sums, counts, int(changed.value)
 
@@ -1592,17 +1592,12 @@ class Graph:
         or None (= 1), not checked for sign, NaN or Inf; it enters the update only, every pixel is labelled.
         -> (labels, sums [k, dim] = sum of weight / length times the raw rows of Phi per label, counts uint64 [k] (pixels),
         mass [k] = sum of the weights per label, changed (pixels)). With neither set every output has cluster_step's bits."""
-        cent = np.ascontiguousarray(np.atleast_2d(np.asarray(cent, dtype=np.float64)))
-        k, dim = cent.shape
-        scale = _scale(scale, dim)
         emb = self._embed(normalize, weight)
-        if prev is not None:
-            prev = self._labels(prev, "prev")
-        labels = self._new_labels() if labels is None else self._labels(labels, "labels")
-        sums, counts, mass, changed = np.zeros((k, dim), dtype=np.float64), np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.float64), C.c_uint64(0)
-        self.ctx._check(_lib.glf_graph_cluster_step_ex(self._g, C.byref(emb), C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale),
-                                                       C.c_void_p(prev.data_ptr()) if prev is not None else None, C.c_void_p(labels.data_ptr()),
-                                                       _ptr(sums), _ptr(counts), _ptr(mass), C.byref(changed)), "graph cluster step")
+        k, dim, cent, scale, prev, labels, sums, counts, changed = self._step_args(cent, scale, prev, labels)
+        mass = np.zeros(k, dtype=np.float64)
+        self.ctx._check(_lib.glf_graph_cluster_step_ex(self._g, C.byref(emb), C.c_uint(k), C.c_uint(dim), _ptr(cent), _ptr(scale), prev,
+                                                       C.c_void_p(labels.data_ptr()), _ptr(sums), _ptr(counts), _ptr(mass), C.byref(changed)),
+                        "graph cluster step")
         return labels, sums, counts, mass, int(changed.value)
 
     def segment(self, k, dim=None, scale=None, init=None, seed=1, max_iter=50, sample_rows=4096, normalize=False, weight=None):

@@ -656,7 +656,8 @@ int glf_fit_coeffs(unsigned m, const double *G, const double *penalty, int nrhs,
  * pixel terms added into f64), the member counts and the number of labels that moved (exact integers). No atomics; the pixel
  * partition depends on (N, ld) and the device alone: two calls give the same bits. Only the first 32 (ld 32) or 64 (ld >= 64) columns
  * of a row are read, whatever ld is.
- * Unit-length rows and per-pixel weights (the _ex / _w entry points below, k_graph_cluster_nw): with glf_cluster_embed.normalize the
+ * Unit-length rows and per-pixel weights (the _ex / _w entry points below, the weight and normalise modes of k_graph_cluster):
+ * with glf_cluster_embed.normalize the
  * embedding is e(px) = rinv(px) scale o Phi[px][0..dim), rinv = 1 / |scale o Phi[px][0..dim)| formed in f32 in a fixed order (a row
  * of length 0 keeps rinv = 0 and embeds at the origin) -- the row-normalised embedding of Ng, Jordan and Weiss, which is what the
  * Nystroem segmentation paper clusters; without it rinv = 1. A weight plane w (device float [N], NULL = 1; not checked for sign, NaN

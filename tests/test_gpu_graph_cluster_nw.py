@@ -1,5 +1,5 @@
-"""Spectral segmentation under unit-length rows and per-pixel weights: glf_graph_cluster_step_ex (k_graph_cluster_nw: k_graph_cluster
-with the embedding e(px) = rinv(px) scale o Phi[px][:dim], rinv = 1 / |scale o Phi[px][:dim]| formed in f32, and a weight plane in the
+"""Spectral segmentation under unit-length rows and per-pixel weights: glf_graph_cluster_step_ex (k_graph_cluster's weight and normalise modes:
+the embedding e(px) = rinv(px) scale o Phi[px][:dim], rinv = 1 / |scale o Phi[px][:dim]| formed in f32, and a weight plane in the
 update), the driver glf_graph_segment_ex and Graph.cluster_step_ex / Graph.segment(normalize=, weight=) on top.
 
 Shapes: those of tests/test_gpu_graph.py, as in tests/test_gpu_graph_cluster.py, whose decided / undecided scheme and helpers are used.
@@ -241,7 +241,7 @@ def test_exact_properties(shape):
                 np.testing.assert_array_equal(_bits(s), _bits(s0))
                 np.testing.assert_array_equal(c, c0)
                 np.testing.assert_array_equal(ms, c0.astype(np.float64))
-            # weight = 1 without normalize: the other kernel, the plain step's labels (and, the operand being 1 and both kernels
+            # weight = 1 without normalize: the weight mode, the plain step's labels (and, the operand being 1 and both instances
             # running one tile per wave at this size, its sums)
             l3, s3, c3, m3, ch3 = g.cluster_step_ex(cent, scale, prev=prev, weight=ones)
             assert torch.equal(l3, l0) and ch3 == ch0
@@ -563,4 +563,38 @@ def test_segment_driver_finds_the_quadrants():
         assert torch.equal(buf, lp) and st2.iterations == sp["iterations"]
         np.testing.assert_array_equal(hc, cp)
         np.testing.assert_array_equal(hm, sp["counts"].astype(np.float64))
+        g.close()
+
+
+# ---- 7. one driver behind both entry points ---------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("shape", ["tiny", "ld64"])
+def test_plain_embedding_through_segment_ex_is_segment(shape):
+    """glf_graph_segment is the reference; glf_graph_segment_ex with emb NULL, and with an embed struct of normalize = 0 and no weight,
+    gives the same labels, the same centroid bits, the same stats, and mass == counts -- seeded (the sample of rows and k-means++ are
+    shared too) and from given centroids."""
+    width, h, _, _, m, ld = SHAPES[shape]
+    n, k, dim = width * h, min(m, 5), min(m, 64)
+    size = C.sizeof(glf.ClusterEmbed)
+    with glf.Context(0) as ctx:
+        g = _grey_graph(ctx, shape)[0]
+        given = _centroids(_phi(g, "cpu"), k, dim, None, 0, np.random.default_rng(17))
+        for init, sample_rows in ((0, 4096), (0, 100), (1, 4096)):
+            o = glf.SegmentOptions(C.sizeof(glf.SegmentOptions), k, dim, 50, sample_rows, init, 7, None)
+
+            def run(entry, *emb):
+                labels = torch.full((h, width), SENTINEL, dtype=torch.int32, device=ctx.device)
+                cent, st, mass = given.copy(), glf.SegmentStats(), np.full(k, -1.0)
+                torch.cuda.synchronize()
+                rc = entry(g._g, C.byref(o), *emb, C.c_void_p(labels.data_ptr()), glf._ptr(cent), C.byref(st), *((glf._ptr(mass),) if emb else ()))
+                assert rc == glf.OK, (shape, init, sample_rows)
+                return labels, cent, (int(st.iterations), int(st.converged), int(st.changed_last), list(st.counts)), mass
+
+            l0, c0, s0, _ = run(glf._lib.glf_graph_segment)
+            assert s0[0] >= 1 and sum(s0[3]) == n and int(l0.min()) >= 0 and int(l0.max()) < k
+            for emb in (None, C.byref(glf.ClusterEmbed(size, 0, None))):
+                l1, c1, s1, m1 = run(glf._lib.glf_graph_segment_ex, emb)
+                assert torch.equal(l1, l0) and s1 == s0, (shape, init, sample_rows)
+                np.testing.assert_array_equal(_bits(c1), _bits(c0))
+                np.testing.assert_array_equal(m1, np.asarray(s0[3][:k], dtype=np.float64))
         g.close()

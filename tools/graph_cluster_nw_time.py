@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Cost of one Lloyd iteration with unit-length rows and a weight plane (glf_graph_cluster_step_ex, k_graph_cluster_nw) against the plain
-step (glf_graph_cluster_step, k_graph_cluster) of the same build, on the benchmark workload.
+"""Cost of one Lloyd iteration with unit-length rows and a weight plane (glf_graph_cluster_step_ex, the weight and normalise modes of k_graph_cluster)
+against the plain step (glf_graph_cluster_step, its plain mode) of the same build, on the benchmark workload.
 
   python tools/graph_cluster_nw_time.py [--size 4096] [--steps 3] [--warmup 1] [--timeout 600]
                                         [--out profiles/graph_cluster_nw_time_cfg4.json]
