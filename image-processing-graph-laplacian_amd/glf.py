@@ -964,8 +964,8 @@ class Context:
         self.stream.synchronize()
         return t
 
-    def mat_to_numpy(self, mat):
-        """Dense / diagonal glf_mat -> numpy (rows x cols), padding stripped."""
+    def mat_to_numpy(self, mat, padded=False):
+        """Dense / diagonal glf_mat -> numpy (rows x cols), padding stripped; padded: a dense one as stored (rows x ld)."""
         if mat.kind == MAT_DIAG:
             out = np.empty(mat.rows, dtype=np.float32)
             self._check(_lib.glf_memcpy_d2h(self._ctx, out.ctypes.data_as(C.c_void_p), C.c_void_p(mat.data),
@@ -975,7 +975,7 @@ class Context:
         full = np.empty((mat.rows, mat.ld), dtype=np.float32)
         self._check(_lib.glf_memcpy_d2h(self._ctx, full.ctypes.data_as(C.c_void_p), C.c_void_p(mat.data),
                                         C.c_size_t(full.nbytes)))
-        return full[:, :mat.cols].copy()
+        return full if padded else full[:, :mat.cols].copy()
 
     def degree_of(self, K_B):
         out = np.empty(K_B.p, dtype=np.float64)
