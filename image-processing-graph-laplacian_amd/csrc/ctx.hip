@@ -74,7 +74,7 @@ int glf_ctx_create(glf_ctx **out, int device, void *hip_stream)
         else fprintf(stderr, "glf: ignoring GLF_CONTRACTION=%s (expected f32 or f16s)\n", mode);
     }
     if (const char *dbg = std::getenv("GLF_POOL_DEBUG")) ctx->pool_debug = dbg[0] && dbg[0] != '0';
-    for (const char *key : {"NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "FILTER_FORM", "BAND_NOSKIP", "PIX_BAND", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "VERBOSE"}) {
+    for (const char *key : {"NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "FILTER_FORM", "BAND_NOSKIP", "PIX_BAND", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "OPERAND_MAXIMA", "VERBOSE"}) {
         char name[32];
         std::snprintf(name, sizeof(name), "GLF_%s", key);
         if (const char *v = std::getenv(name))
@@ -127,6 +127,9 @@ int glf_ctx_set_tuning(glf_ctx *ctx, const char *key, const char *value)
     } else if (!std::strcmp(key, "RESIDUAL")) {
         if (!unset && !is("sweep") && !is("derived")) return GLF_ERR_INVALID;
         t.residual_sweep = is("sweep");
+    } else if (!std::strcmp(key, "OPERAND_MAXIMA")) {
+        if (!unset && !is("sweep") && !is("carried")) return GLF_ERR_INVALID;
+        t.operand_maxima_sweep = is("sweep");
     } else if (!std::strcmp(key, "VERBOSE")) t.verbose = flag();
     else return GLF_ERR_INVALID;
     return GLF_OK;

@@ -508,7 +508,7 @@ static int allgather_rows(glf_ctx *ctx, float *V, const MatShard *sh, unsigned l
 
 // Y[rows of this rank] = A X; X must hold all p rows (sharded callers all-gather it first)
 int block_matvec(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const float *X, float *Y, unsigned ld,
-                 const MatShard *shard)
+                 const MatShard *shard, const ColMaxima *maxima)
 {
     const unsigned p32 = (unsigned)round_up(p, VEC_PAD);
     const bool sharded = shard && shard->rows_per_rank;
@@ -516,7 +516,7 @@ int block_matvec(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const fl
         const unsigned row0 = sharded ? shard->row0 : 0u, row1 = sharded ? shard->row1 : p;
         if (ctx->mv_pending == glf_ctx::MV_RING) GLF_TRY(mv_collect(ctx));
         GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[0][ctx->mv_pending], ctx->stream));
-        GLF_TRY(grid_op_apply(ctx, shard->grid, X, Y, ld, shard->grid_alpha, shard->grid_degree, row0, row1, shard->grid_window));
+        GLF_TRY(grid_op_apply(ctx, shard->grid, X, Y, ld, shard->grid_alpha, shard->grid_degree, row0, row1, shard->grid_window, maxima));
         GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[1][ctx->mv_pending], ctx->stream));
         ++ctx->mv_pending;
         return GLF_OK;
@@ -547,72 +547,30 @@ int block_matvec(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const fl
 
 constexpr int RED_ROWS = 128; // rows per reduction workgroup (667 workgroups at p = 85 264: every CU busy)
 
-// out[c] = sum_blk partial[blk][c], c < ncols
-// Second level of the column reductions, one 256-thread workgroup: out[v] (valid for t < ld) = sum over the nblk
-// blocks of partial[(b * NV + v) * ld + t % ld]. The 256 / ld thread rows take interleaved blocks and are combined
-// through LDS -- all in a fixed order.
-// NTHR: threads of the workgroup (256, or 1024 where the reduction sits between two sweeps of the solver: four times the
-// thread rows, a quarter of the dependent load batches).
-template <int NV, int NTHR = 256>
-__device__ __forceinline__ void wg_sum_partials(const double *__restrict__ partial, int nblk, unsigned ld, double (&out)[NV],
-                                                double *sh /* [NV][NTHR] */)
-{
-    const int t = threadIdx.x, col = t % ld, part = t / ld, nparts = NTHR / ld;
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    // eight blocks' loads in flight at a time, added in the same order as one by one (667 dependent round trips to L2
-    // made each of these single-workgroup reductions 43 us at p = 85 264)
-    int b = part;
-    for (; b + 7 * nparts < nblk; b += 8 * nparts) {
-        double x[8][NV];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) x[u][v] = partial[((size_t)(b + u * nparts) * NV + v) * ld + col];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int v = 0; v < NV; ++v) acc[v] += x[u][v];
-    }
-    for (; b < nblk; b += nparts)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) acc[v] += partial[((size_t)b * NV + v) * ld + col];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) sh[v * NTHR + t] = acc[v];
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-        double s = 0.0;
-        if (t < (int)ld)
-            for (int r = 0; r < nparts; ++r) s += sh[v * NTHR + r * ld + col];
-        out[v] = s;
-    }
-    __syncthreads();
-}
+// Second levels: wg_reduce_partials (glf_internal.hpp), red2_grid(ld) workgroups of RED2_THREADS threads, RED2_COLS columns each.
 
-// out[c] = sum_blk partial[blk][c], c < ld (one workgroup of 256 threads)
-__global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__ partial, int nblk, int ncols,
-                                                       double *__restrict__ out)
+// out[c] = sum_blk partial[blk][c], c < ld
+__global__ __launch_bounds__(RED2_THREADS) void k_sum_partials(const double *__restrict__ partial, int nblk, unsigned ld,
+                                                                double *__restrict__ out)
 {
-    __shared__ double sh[256];
+    __shared__ double sh[RED2_THREADS];
     double s[1];
-    wg_sum_partials<1>(partial, nblk, (unsigned)ncols, s, sh);
-    if ((int)threadIdx.x < ncols) out[threadIdx.x] = s[0];
+    wg_reduce_partials<double, 1, false>(partial, nblk, ld, s, sh);
+    if (threadIdx.x < RED2_COLS) out[blockIdx.x * RED2_COLS + threadIdx.x] = s[0];
 }
 
 // sums[v * ld + c] = sum_blk partial[(blk * NV + v) * ld + c]: the local sums of a row-sharded reduction, all-reduced by the
 // host before the second-level kernel consumes them as ONE block (nblk = 1)
 template <int NV>
-__global__ __launch_bounds__(256) void k_sum_partials_nv(const double *__restrict__ partial, int nblk, unsigned ld,
-                                                          double *__restrict__ sums)
+__global__ __launch_bounds__(RED2_THREADS) void k_sum_partials_nv(const double *__restrict__ partial, int nblk, unsigned ld,
+                                                                   double *__restrict__ sums)
 {
-    __shared__ double sh[NV * 256];
+    __shared__ double sh[NV * RED2_THREADS];
     double s[NV];
-    wg_sum_partials<NV>(partial, nblk, ld, s, sh);
-    if (threadIdx.x < ld)
+    wg_reduce_partials<double, NV, false>(partial, nblk, ld, s, sh);
+    if (threadIdx.x < RED2_COLS)
 #pragma unroll
-        for (int v = 0; v < NV; ++v) sums[v * ld + threadIdx.x] = s[v];
+        for (int v = 0; v < NV; ++v) sums[v * ld + blockIdx.x * RED2_COLS + threadIdx.x] = s[v];
 }
 
 // Block-level column reduction helper: 256 threads, column = t % ld, row lane = t / ld.
@@ -637,6 +595,20 @@ __device__ __forceinline__ void block_col_reduce(double (&val)[NV], unsigned ld,
     }
 }
 
+// The same for a maximum of values >= 0 over `w`-wide rows of threads (w <= 256; threads t >= (256 / w) w hold 0):
+// pmax[blockIdx.x * w + col]. These are the block maxima of |operand| that the operator's scales need (ColMaxima); the
+// kernel that writes an operand of the PCG has every element in a register, so the sweep need not read the block again.
+__device__ __forceinline__ void block_col_max(float m, unsigned w, float *__restrict__ pmax, float *sh /* [256] */)
+{
+    const unsigned t = threadIdx.x;
+    sh[t] = m;
+    __syncthreads();
+    if (t < w) {
+        for (unsigned r = 1; r < 256 / w; ++r) m = fmaxf(m, sh[r * w + t]);
+        pmax[(size_t)blockIdx.x * w + t] = m;
+    }
+}
+
 // =====================================================================================
 // Jacobi-PCG on all columns at once (stands in for KSPSolve x m, hpc/inverse_power_it.c:165-168)
 // =====================================================================================
@@ -650,15 +622,17 @@ struct CgScalars {    // device, per column (ld entries each)
     int *nactive;     // single int
 };
 
-// init: R = B (B lives in XB), X = 0 (XB is overwritten at the end), P = dinv .* R
+// init: R = B (B lives in XB), X = 0 (XB is overwritten at the end), P = dinv .* R; pmax: this block's column maxima of |P|
 __global__ __launch_bounds__(256) void k_cg_init(const float *__restrict__ B, const float *__restrict__ dinv,
                                                   float *__restrict__ R, float *__restrict__ P,
                                                   float *__restrict__ Xs, unsigned p, unsigned ld,
-                                                  double *__restrict__ partial)
+                                                  double *__restrict__ partial, float *__restrict__ pmax)
 {
     __shared__ double sh[2 * 256];
+    __shared__ float shm[256];
     const int col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld;
     double v[2] = {0.0, 0.0};
+    float mx = 0.f;
     const unsigned base = blockIdx.x * RED_ROWS;
     for (unsigned r = rl; r < RED_ROWS; r += nrl) {
         const unsigned i = base + r;
@@ -671,18 +645,20 @@ __global__ __launch_bounds__(256) void k_cg_init(const float *__restrict__ B, co
         Xs[o] = 0.f;
         v[0] += (double)b * (double)z; // r.z
         v[1] += (double)b * (double)b; // ||b||^2
+        mx = fmaxf(mx, fabsf(z));
     }
     block_col_reduce<2>(v, ld, partial, sh);
+    block_col_max(mx, ld, pmax, shm);
 }
 
-__global__ __launch_bounds__(256) void k_cg_init_scalars(const double *__restrict__ partial, int nblk, unsigned ld, unsigned m,
-                                                          CgScalars s)
+__global__ __launch_bounds__(RED2_THREADS) void k_cg_init_scalars(const double *__restrict__ partial, int nblk, unsigned ld, unsigned m,
+                                                                   CgScalars s)
 {
-    __shared__ double sh[2 * 256];
-    const int c = threadIdx.x;
+    __shared__ double sh[2 * RED2_THREADS];
     double tot[2];
-    wg_sum_partials<2>(partial, nblk, ld, tot, sh);
-    if (c < (int)ld) {
+    wg_reduce_partials<double, 2, false>(partial, nblk, ld, tot, sh);
+    if (threadIdx.x < RED2_COLS) {
+        const int c = blockIdx.x * RED2_COLS + threadIdx.x;
         const double rz = tot[0], bn2 = tot[1];
         s.rz[c] = rz;
         s.bn2[c] = bn2;
@@ -690,12 +666,15 @@ __global__ __launch_bounds__(256) void k_cg_init_scalars(const double *__restric
         s.alpha[c] = 0.0;
         s.beta[c] = 0.0;
     }
-    __syncthreads();
-    if (c == 0) {
-        int n = 0;
-        for (unsigned k = 0; k < ld; ++k) n += s.active[k];
-        *s.nactive = n;
-    }
+}
+
+// The number of columns still iterating, into the pinned counter the host reads after its synchronise. The second levels
+// above and below are split over workgroups, so the flags are counted by ONE workgroup of the launch that follows them
+// (256 threads, ld <= 256): k_cg_pupdate, or k_cg_count after k_cg_init_scalars.
+__global__ __launch_bounds__(256) void k_cg_count(CgScalars s, unsigned ld)
+{
+    const int n = __syncthreads_count(threadIdx.x < ld && s.active[threadIdx.x] != 0);
+    if (threadIdx.x == 0) *s.nactive = n;
 }
 
 // partial p.Ap
@@ -715,13 +694,16 @@ __global__ __launch_bounds__(256) void k_cg_dot(const float *__restrict__ P, con
     block_col_reduce<1>(v, ld, partial, sh);
 }
 
-__global__ __launch_bounds__(1024) void k_cg_alpha(const double *__restrict__ partial, int nblk, unsigned ld, CgScalars s)
+__global__ __launch_bounds__(RED2_THREADS) void k_cg_alpha(const double *__restrict__ partial, int nblk, unsigned ld, CgScalars s)
 {
-    __shared__ double sh[1024];
-    const int c = threadIdx.x;
+    __shared__ double sh[RED2_THREADS];
+    const int c = blockIdx.x * RED2_COLS + threadIdx.x;
+    const bool own = threadIdx.x < RED2_COLS;
+    const int act = own ? s.active[c] : 0; // (read before the reduction, not in a chain behind it)
+    const double rz = own ? s.rz[c] : 0.0;
     double pap[1];
-    wg_sum_partials<1, 1024>(partial, nblk, ld, pap, sh);
-    if (c < (int)ld) s.alpha[c] = s.active[c] ? s.rz[c] / pap[0] : 0.0;
+    wg_reduce_partials<double, 1, false>(partial, nblk, ld, pap, sh);
+    if (own) s.alpha[c] = act ? rz / pap[0] : 0.0;
 }
 
 // x += alpha p ; r -= alpha Ap ; partial ||r||^2 and r.(dinv r)
@@ -751,38 +733,70 @@ __global__ __launch_bounds__(256) void k_cg_update(float *__restrict__ Xs, float
     block_col_reduce<2>(v, ld, partial, sh);
 }
 
-__global__ __launch_bounds__(1024) void k_cg_beta(const double *__restrict__ partial, int nblk, unsigned ld, double rtol2,
-                                                   CgScalars s)
+// (the columns still active are counted by k_cg_pupdate, the next launch: cg_count_active)
+__global__ __launch_bounds__(RED2_THREADS) void k_cg_beta(const double *__restrict__ partial, int nblk, unsigned ld, double rtol2,
+                                                           CgScalars s)
 {
-    __shared__ double sh[2 * 1024];
-    const int c = threadIdx.x;
+    __shared__ double sh[2 * RED2_THREADS];
+    const int c = blockIdx.x * RED2_COLS + threadIdx.x;
+    const bool own = threadIdx.x < RED2_COLS;
+    const int act = own ? s.active[c] : 0; // (read before the reduction, not in a chain behind it)
+    const double bn2 = own ? s.bn2[c] : 0.0, rz_old = own ? s.rz[c] : 0.0;
     double tot[2];
-    wg_sum_partials<2, 1024>(partial, nblk, ld, tot, sh);
-    int still = 0; // this thread's column keeps iterating
-    if (c < (int)ld && s.active[c]) {
+    wg_reduce_partials<double, 2, false>(partial, nblk, ld, tot, sh);
+    if (act) {
         const double rr = tot[0], rz = tot[1];
-        if (rr <= rtol2 * s.bn2[c]) { // ||r|| <= rtol ||b||
+        if (rr <= rtol2 * bn2) { // ||r|| <= rtol ||b||
             s.active[c] = 0;
             s.beta[c] = 0.0;
         } else {
-            s.beta[c] = rz / s.rz[c];
+            s.beta[c] = rz / rz_old;
             s.rz[c] = rz;
-            still = 1;
         }
     }
-    const int n = __syncthreads_count(still); // (one thread re-reading the ld flags from memory took a third of the kernel)
-    if (c == 0) *s.nactive = n;
 }
 
-// p = dinv r + beta p
+// p = dinv r + beta p on the columns still active, RED_ROWS rows per workgroup. pmax (optional): this block's column
+// maxima of |P|, the inactive columns included -- read, not written: a wide sweep scales all ld columns. Every workgroup
+// counts the active columns (none left: nothing to do), block 0 writes the count for the host.
 __global__ __launch_bounds__(256) void k_cg_pupdate(float *__restrict__ P, const float *__restrict__ R,
                                                      const float *__restrict__ dinv, unsigned p, unsigned ld,
-                                                     CgScalars s)
+                                                     CgScalars s, float *__restrict__ pmax)
 {
-    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const unsigned i = (unsigned)(e / ld), col = (unsigned)(e % ld);
-    if (i >= p || !s.active[col]) return;
-    P[e] = fmaf((float)s.beta[col], P[e], dinv[i] * R[e]);
+    __shared__ float shm[256];
+    const int nact = __syncthreads_count(threadIdx.x < ld && s.active[threadIdx.x] != 0);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *s.nactive = nact;
+    if (nact == 0) return; // the solve is over: neither P nor its maxima are used again
+    const int col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld;
+    const bool act = s.active[col] != 0;
+    const float beta = (float)s.beta[col];
+    float mx = 0.f;
+    const unsigned base = blockIdx.x * RED_ROWS;
+    if (base < p && (act || pmax)) {
+        for (unsigned r = rl; r < RED_ROWS; r += 8 * nrl) { // eight rows' loads in flight (RED_ROWS / nrl is a multiple of 8)
+            float pv[8], rv[8], dv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { // (a row past the end re-reads the last one)
+                const unsigned i = min(base + r + u * nrl, p - 1);
+                const size_t o = (size_t)i * ld + col;
+                pv[u] = P[o];
+                rv[u] = act ? R[o] : 0.f;
+                dv[u] = act ? dinv[i] : 0.f;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const unsigned i = base + r + u * nrl;
+                if (i >= p) continue;
+                float v = pv[u];
+                if (act) {
+                    v = fmaf(beta, v, dv[u] * rv[u]);
+                    P[(size_t)i * ld + col] = v;
+                }
+                mx = fmaxf(mx, fabsf(v));
+            }
+        }
+    }
+    if (pmax) block_col_max(mx, ld, pmax, shm);
 }
 
 __global__ void k_diag_inv(const float *__restrict__ A, int64_t lda, unsigned p, float *__restrict__ dinv)
@@ -809,16 +823,26 @@ __device__ __forceinline__ int cg_active_map(const int *__restrict__ active, uns
 }
 
 __global__ __launch_bounds__(256) void k_cg_pack(const float *__restrict__ P, const int *__restrict__ active, unsigned p, unsigned ld,
-                                                  unsigned wn, float *__restrict__ Pc)
+                                                  unsigned wn, float *__restrict__ Pc, float *__restrict__ pcmax)
 {
     __shared__ int map[256], count;
+    __shared__ float shm[256];
     const int nact = cg_active_map(active, ld, map, &count);
+    // a thread keeps one packed column r (so that it can carry the column's maximum: pcmax, the block maxima of |Pc|);
+    // 256 / wn rows at a time (wn = 192: one row, 64 threads idle)
+    const unsigned r = threadIdx.x % wn, rl = threadIdx.x / wn, nrl = 256 / wn;
     const unsigned base = blockIdx.x * RED_ROWS;
-    for (unsigned e = threadIdx.x; e < RED_ROWS * wn; e += 256) {
-        const unsigned i = base + e / wn, r = e % wn;
-        if (i >= p) break;
-        Pc[(size_t)i * wn + r] = (int)r < nact ? P[(size_t)i * ld + map[r]] : 0.f;
+    float mx = 0.f;
+    if (rl < nrl) {
+        for (unsigned q = rl; q < RED_ROWS; q += nrl) {
+            const unsigned i = base + q;
+            if (i >= p) break;
+            const float v = (int)r < nact ? P[(size_t)i * ld + map[r]] : 0.f;
+            Pc[(size_t)i * wn + r] = v;
+            mx = fmaxf(mx, fabsf(v));
+        }
     }
+    block_col_max(mx, wn, pcmax, shm);
 }
 
 // rows [r0, r0 + n) of the packed result back into the active columns of AP
@@ -839,6 +863,10 @@ struct CgWork {
     DevBuf<float> R, P, AP, Xs, dinv, Pc, APc;
     DevBuf<double> partial, scal, sums;
     DevBuf<int> flags;
+    DevBuf<float> pmax, pcmax; // block maxima of |P| (k_cg_init, k_cg_pupdate) and of the packed |Pc| (k_cg_pack)
+    // The sweeps take the operand's maxima from its writer (ColMaxima). Only where that writer covers all p rows: not in
+    // a sharded solve, whose k_cg_pupdate sees this rank's rows only. Set by the caller (the panels path leaves it off).
+    bool carry_maxima = false;
     CgScalars s{};
     int nblk = 0;
     Rows rows;                // the rows of the vector blocks this rank updates (all of them unless the solve is sharded)
@@ -856,6 +884,7 @@ struct CgWork {
         GLF_TRY(dinv.alloc(ctx, p));
         nblk = (int)ceil_div(rows.n(), RED_ROWS);
         GLF_TRY(partial.alloc(ctx, (size_t)std::max(1, nblk) * 2 * ld));
+        GLF_TRY(pmax.alloc(ctx, (size_t)std::max(1, nblk) * ld));
         GLF_TRY(sums.alloc(ctx, (size_t)2 * ld));
         GLF_TRY(scal.alloc(ctx, (size_t)4 * ld));
         GLF_TRY(flags.alloc(ctx, ld + 1));
@@ -875,21 +904,25 @@ struct CgWork {
 };
 
 static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, unsigned p, float *XB, unsigned m,
-                          unsigned ld, double rtol, int max_it, int *iters)
+                          unsigned ld, double rtol, int max_it, int *iters, bool solution_to_XB = true)
 {
+    // XB: the right-hand side B in, the solution out -- unless solution_to_XB is off: then XB is only read and the solution
+    // stays in w.Xs (the caller swaps buffers instead of copying a block)
     const int nblk = w.nblk;
     const Rows rows = w.rows;
     const unsigned nloc = rows.n();
     const size_t off = (size_t)rows.r0 * ld; // first element of this rank's rows in every vector block
-    const unsigned nelem_blocks = (unsigned)ceil_div((int64_t)nloc * ld, 256);
     hipStream_t st = ctx->stream;
+    const dim3 red2(red2_grid(ld)), red2_threads(RED2_THREADS);
+    const bool carry = w.carry_maxima && !rows.dist;
+    const ColMaxima pmax{w.pmax.p, nblk}; // |P| as k_cg_init / k_cg_pupdate left it
     // second-level reductions: the per-block partial sums of this rank, or (sharded) their all-reduced totals as one block
     auto reduce2 = [&](int nv, const double **src, int *src_blk) -> int {
         *src = w.partial.p;
         *src_blk = nblk;
         if (!rows.dist) return GLF_OK;
-        if (nv == 1) hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(1), dim3(256), 0, st, w.partial.p, nblk, ld, w.sums.p);
-        else hipLaunchKernelGGL(k_sum_partials_nv<2>, dim3(1), dim3(256), 0, st, w.partial.p, nblk, ld, w.sums.p);
+        if (nv == 1) hipLaunchKernelGGL(k_sum_partials_nv<1>, red2, red2_threads, 0, st, w.partial.p, nblk, ld, w.sums.p);
+        else hipLaunchKernelGGL(k_sum_partials_nv<2>, red2, red2_threads, 0, st, w.partial.p, nblk, ld, w.sums.p);
         GLF_LAUNCH_CHECK(ctx);
         GLF_TRY(allreduce_d(ctx, w.sums.p, (size_t)nv * ld));
         *src = w.sums.p;
@@ -900,9 +933,10 @@ static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, 
     int src_blk = 0;
     if (nblk > 0)
         hipLaunchKernelGGL(k_cg_init, dim3(nblk), dim3(256), 0, st, XB + off, w.dinv.p + rows.r0, w.R.p + off, w.P.p + off, w.Xs.p + off,
-                           nloc, ld, w.partial.p);
+                           nloc, ld, w.partial.p, w.pmax.p);
     GLF_TRY(reduce2(2, &src, &src_blk));
-    hipLaunchKernelGGL(k_cg_init_scalars, dim3(1), dim3(256), 0, st, src, src_blk, ld, m, w.s);
+    hipLaunchKernelGGL(k_cg_init_scalars, red2, red2_threads, 0, st, src, src_blk, ld, m, w.s);
+    hipLaunchKernelGGL(k_cg_count, dim3(1), dim3(256), 0, st, w.s, ld);
     GLF_LAUNCH_CHECK(ctx);
     int it = 0;
     GLF_HIP(ctx, hipStreamSynchronize(st));
@@ -920,32 +954,36 @@ static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, 
                 const size_t n = (size_t)vec_rows(p, w.shard, ctx->comm.size) * ld;
                 GLF_TRY(w.Pc.alloc(ctx, n));
                 GLF_TRY(w.APc.alloc(ctx, n));
+                GLF_TRY(w.pcmax.alloc(ctx, (size_t)ceil_div(p, RED_ROWS) * ld));
                 GLF_HIP(ctx, hipMemsetAsync(w.Pc.p, 0, n * sizeof(float), st)); // (rows beyond p stay zero)
             }
-            hipLaunchKernelGGL(k_cg_pack, dim3((unsigned)ceil_div(p, RED_ROWS)), dim3(256), 0, st, w.P.p, w.s.active, p, ld, wn, w.Pc.p);
-            GLF_TRY(block_matvec(ctx, A, lda, p, w.Pc.p, w.APc.p, wn, w.shard));
+            const ColMaxima pcmax{w.pcmax.p, (int)ceil_div(p, RED_ROWS)};
+            hipLaunchKernelGGL(k_cg_pack, dim3((unsigned)pcmax.nblk), dim3(256), 0, st, w.P.p, w.s.active, p, ld, wn, w.Pc.p, w.pcmax.p);
+            GLF_TRY(block_matvec(ctx, A, lda, p, w.Pc.p, w.APc.p, wn, w.shard, carry ? &pcmax : nullptr));
             if (nblk > 0)
                 hipLaunchKernelGGL(k_cg_unpack, dim3(nblk), dim3(256), 0, st, w.APc.p, w.s.active, rows.r0, nloc, ld, wn, w.AP.p);
             ++ctx->narrow_sweeps;
             if (ctx->tune.verbose) fprintf(stderr, "[glf] block PCG step %d: operator applied to %u packed columns\n", it, wn);
         } else {
-            GLF_TRY(block_matvec(ctx, A, lda, p, w.P.p, w.AP.p, ld, w.shard));
+            GLF_TRY(block_matvec(ctx, A, lda, p, w.P.p, w.AP.p, ld, w.shard, carry ? &pmax : nullptr));
         }
         if (nblk > 0) hipLaunchKernelGGL(k_cg_dot, dim3(nblk), dim3(256), 0, st, w.P.p + off, w.AP.p + off, nloc, ld, w.partial.p);
         GLF_TRY(reduce2(1, &src, &src_blk));
-        hipLaunchKernelGGL(k_cg_alpha, dim3(1), dim3(1024), 0, st, src, src_blk, ld, w.s);
+        hipLaunchKernelGGL(k_cg_alpha, red2, red2_threads, 0, st, src, src_blk, ld, w.s);
         if (nblk > 0)
             hipLaunchKernelGGL(k_cg_update, dim3(nblk), dim3(256), 0, st, w.Xs.p + off, w.R.p + off, w.P.p + off, w.AP.p + off,
                                w.dinv.p + rows.r0, nloc, ld, w.s, w.partial.p);
         GLF_TRY(reduce2(2, &src, &src_blk));
-        hipLaunchKernelGGL(k_cg_beta, dim3(1), dim3(1024), 0, st, src, src_blk, ld, rtol * rtol, w.s);
-        if (nelem_blocks > 0)
-            hipLaunchKernelGGL(k_cg_pupdate, dim3(nelem_blocks), dim3(256), 0, st, w.P.p + off, w.R.p + off, w.dinv.p + rows.r0, nloc, ld, w.s);
+        hipLaunchKernelGGL(k_cg_beta, red2, red2_threads, 0, st, src, src_blk, ld, rtol * rtol, w.s);
+        // (at least one workgroup: block 0 counts the active columns for the synchronise below)
+        hipLaunchKernelGGL(k_cg_pupdate, dim3((unsigned)std::max(1, nblk)), dim3(256), 0, st, w.P.p + off, w.R.p + off, w.dinv.p + rows.r0, nloc, ld,
+                           w.s, carry ? w.pmax.p : nullptr);
         GLF_LAUNCH_CHECK(ctx);
         GLF_HIP(ctx, hipStreamSynchronize(st));
         if (ctx->tune.verbose) fprintf(stderr, "[glf] block PCG step %d: %d of %u columns active\n", it, *w.h_nactive, m);
     }
-    if (nloc > 0) GLF_HIP(ctx, hipMemcpyAsync(XB + off, w.Xs.p + off, sizeof(float) * (size_t)nloc * ld, hipMemcpyDeviceToDevice, st));
+    if (nloc > 0 && solution_to_XB)
+        GLF_HIP(ctx, hipMemcpyAsync(XB + off, w.Xs.p + off, sizeof(float) * (size_t)nloc * ld, hipMemcpyDeviceToDevice, st));
     if (iters) *iters = it;
     return (*w.h_nactive > 0) ? set_error(ctx, GLF_ERR_NOCONV, "block PCG: %d columns unconverged after %d iterations",
                                           *w.h_nactive, it)
@@ -1084,13 +1122,13 @@ __global__ __launch_bounds__(256) void k_col_sumsq(const float *__restrict__ X, 
     block_col_reduce<1>(v, ld, partial, sh);
 }
 
-__global__ __launch_bounds__(256) void k_norms_from_partials(const double *__restrict__ partial, int nblk, unsigned ld,
-                                                              double *__restrict__ norms)
+__global__ __launch_bounds__(RED2_THREADS) void k_norms_from_partials(const double *__restrict__ partial, int nblk, unsigned ld,
+                                                                       double *__restrict__ norms)
 {
-    __shared__ double sh[256];
+    __shared__ double sh[RED2_THREADS];
     double s[1];
-    wg_sum_partials<1>(partial, nblk, ld, s, sh);
-    if (threadIdx.x < ld) norms[threadIdx.x] = sqrt(s[0]);
+    wg_reduce_partials<double, 1, false>(partial, nblk, ld, s, sh);
+    if (threadIdx.x < RED2_COLS) norms[blockIdx.x * RED2_COLS + threadIdx.x] = sqrt(s[0]);
 }
 
 __global__ void k_scale_all(float *__restrict__ X, unsigned n, unsigned ld, unsigned m, const double *__restrict__ norms)
@@ -1412,13 +1450,14 @@ __global__ __launch_bounds__(256) void k_gsf_recur_global(unsigned ld, unsigned 
     gsf_recur_body<false>(S, ld, m, G, Tn, norms, flag, flag_host);
 }
 
-// X[i][k] <- sum_{j<=k} X[i][j] Tn[j][k] (f64 accumulation), in place; GSF_APPLY_TILE / ld rows per workgroup (32 at ld = 64:
-// with 128 the 42 workgroups of a 5329-sample block left most of the chip idle), thread = column.
+// Out[i][k] <- sum_{j<=k} V[i][j] Tn[j][k] (f64 accumulation) with V = X, or V = X - S rounded to f32 where S is given (the
+// solver's A Y = B - R); Out may be X (in place: a workgroup has read its rows before it stores them). GSF_APPLY_TILE / ld rows per
+// workgroup (32 at ld = 64: with 128 the 42 workgroups of a 5329-sample block left most of the chip idle), thread = column.
 constexpr unsigned GSF_APPLY_TILE = 2048;
-__global__ __launch_bounds__(256) void k_gsf_apply(float *__restrict__ X, unsigned n, unsigned ld, unsigned m,
-                                                    const double *__restrict__ Tn, const int *__restrict__ flag)
+__global__ __launch_bounds__(256) void k_gsf_apply(const float *X, const float *__restrict__ S, float *Out, unsigned n, unsigned ld,
+                                                    unsigned m, const double *__restrict__ Tn, const int *__restrict__ flag)
 {
-    if (*flag) return; // ill-conditioned: the caller runs the sequential sweep on the untouched X
+    if (*flag) return; // ill-conditioned: the caller runs the sequential sweep on the untouched block
     __shared__ float xs[GSF_APPLY_TILE];
     __shared__ double ts[4096];
     const unsigned rows = GSF_APPLY_TILE / ld, jb = min(4096u / ld, ld); // rows per workgroup; T rows per staged block (Tn has ld rows)
@@ -1426,7 +1465,8 @@ __global__ __launch_bounds__(256) void k_gsf_apply(float *__restrict__ X, unsign
     const unsigned col = threadIdx.x % ld, rl = threadIdx.x / ld, nrl = 256 / ld, rpt = rows / nrl; // rpt = 8
     for (unsigned e = threadIdx.x; e < rows * ld; e += 256) {
         const unsigned i = r0 + e / ld;
-        xs[e] = i < n ? X[(size_t)i * ld + e % ld] : 0.f;
+        const size_t o = (size_t)i * ld + e % ld;
+        xs[e] = i >= n ? 0.f : S ? X[o] - S[o] : X[o];
     }
     double acc[8];
 #pragma unroll
@@ -1447,7 +1487,7 @@ __global__ __launch_bounds__(256) void k_gsf_apply(float *__restrict__ X, unsign
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const unsigned i = r0 + rl + q * nrl;
-            if (i < n) X[(size_t)i * ld + col] = (float)acc[q];
+            if (i < n) Out[(size_t)i * ld + col] = (float)acc[q];
         }
 }
 
@@ -1457,10 +1497,10 @@ __global__ __launch_bounds__(256) void k_gsf_apply(float *__restrict__ X, unsign
 // LDS with rows of LD + 4 doubles (the two j rows a half-wave reads are 4 apart: 32 banks apart with that stride).
 // `tiles` row tiles per wave (1 .. 4: enough workgroups for every CU before a workgroup's copy of Tn is shared by more rows).
 template <int LD>
-__global__ __launch_bounds__(256) void k_gsf_apply_mfma(float *__restrict__ X, unsigned n, unsigned m, const double *__restrict__ Tn,
-                                                         const int *__restrict__ flag, int tiles)
+__global__ __launch_bounds__(256) void k_gsf_apply_mfma(const float *X, const float *__restrict__ S, float *Out, unsigned n, unsigned m,
+                                                         const double *__restrict__ Tn, const int *__restrict__ flag, int tiles)
 {
-    if (*flag) return; // ill-conditioned: the caller runs the sequential sweep on the untouched X
+    if (*flag) return; // ill-conditioned: the caller runs the sequential sweep on the untouched block
     constexpr int NTL = LD / 16, TS = LD + 4;
     __shared__ double ts[LD * TS];
     for (unsigned e = threadIdx.x; e < LD * LD; e += 256) ts[(e / LD) * TS + e % LD] = Tn[e];
@@ -1474,6 +1514,12 @@ __global__ __launch_bounds__(256) void k_gsf_apply_mfma(float *__restrict__ X, u
         float4 xa[NTL];
 #pragma unroll
         for (int jb = 0; jb < NTL; ++jb) xa[jb] = *reinterpret_cast<const float4 *>(X + (size_t)ra * LD + 16 * jb + 4 * lq);
+        if (S)
+#pragma unroll
+            for (int jb = 0; jb < NTL; ++jb) {
+                const float4 s4 = *reinterpret_cast<const float4 *>(S + (size_t)ra * LD + 16 * jb + 4 * lq);
+                xa[jb] = make_float4(xa[jb].x - s4.x, xa[jb].y - s4.y, xa[jb].z - s4.z, xa[jb].w - s4.w);
+            }
         f64x4 acc[NTL];
 #pragma unroll
         for (int t = 0; t < NTL; ++t)
@@ -1494,7 +1540,7 @@ __global__ __launch_bounds__(256) void k_gsf_apply_mfma(float *__restrict__ X, u
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const unsigned i = row0 + lq + 4 * r;
-                if (i < n && 16 * t + l15 < (int)m) X[(size_t)i * LD + 16 * t + l15] = (float)acc[t][r];
+                if (i < n && 16 * t + l15 < (int)m) Out[(size_t)i * LD + 16 * t + l15] = (float)acc[t][r];
             }
     }
 }
@@ -1535,16 +1581,18 @@ __global__ __launch_bounds__(256) void k_gsf_sub(float *__restrict__ Y, const fl
     }
 }
 
-static void launch_gsf_apply(hipStream_t st, float *X, unsigned n, unsigned ld, unsigned m, const double *Tn, const int *flag)
+// out = (X - S) Tn (S optional); out == X: in place
+static void launch_gsf_apply(hipStream_t st, const float *X, const float *S, float *out, unsigned n, unsigned ld, unsigned m, const double *Tn,
+                             const int *flag)
 {
     const int tiles = (int)std::max<int64_t>(1, std::min<int64_t>(4, ceil_div(n, 16 * 4 * 256)));
     const unsigned rows_wg = 16 * 4 * (unsigned)tiles;
     if (ld == 64)
-        hipLaunchKernelGGL(k_gsf_apply_mfma<64>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, n, m, Tn, flag, tiles);
+        hipLaunchKernelGGL(k_gsf_apply_mfma<64>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, n, m, Tn, flag, tiles);
     else if (ld == 32)
-        hipLaunchKernelGGL(k_gsf_apply_mfma<32>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, n, m, Tn, flag, tiles);
+        hipLaunchKernelGGL(k_gsf_apply_mfma<32>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, n, m, Tn, flag, tiles);
     else
-        hipLaunchKernelGGL(k_gsf_apply, dim3((unsigned)ceil_div(n, GSF_APPLY_TILE / ld)), dim3(256), 0, st, X, n, ld, m, Tn, flag);
+        hipLaunchKernelGGL(k_gsf_apply, dim3((unsigned)ceil_div(n, GSF_APPLY_TILE / ld)), dim3(256), 0, st, X, S, out, n, ld, m, Tn, flag);
 }
 
 struct GsFusedWork {
@@ -1592,14 +1640,24 @@ struct GsWork {
     }
 };
 
-// returns GLF_OK with *fell_back = 1 when the device found V too ill-conditioned (X untouched)
+// The solver's outer step without its block copies (inverse_power_iteration): the block to orthonormalise is Y (the PCG's
+// solution, left where the PCG built it) while X still holds the right-hand side B, and A X_new = (B - R) Tn is formed from
+// X before X_new = Y Tn overwrites it.
+struct GsDerive {
+    const float *Y; // in: the block to orthonormalise (X receives the result)
+    const float *R; // in: the PCG's residual B - A Y
+    float *AX;      // out: (B - R) Tn, B read from X
+};
+
+// returns GLF_OK with *fell_back = 1 when the device found V too ill-conditioned (X untouched; der: AX too)
 // rows: this rank's rows of X (X points at row 0 of the whole block); dist: the Gram block is all-reduced
 static int orthonormalise_fused_dev(glf_ctx *ctx, GsFusedWork &f, float *X, Rows rows, unsigned m, unsigned ld,
-                                    double *d_norms, int *fell_back)
+                                    double *d_norms, int *fell_back, const GsDerive *der = nullptr)
 {
     hipStream_t st = ctx->stream;
     const unsigned n = rows.n();
-    float *Xl = X + (size_t)rows.r0 * ld;
+    float *Xout = X + (size_t)rows.r0 * ld;
+    const float *Xl = der ? der->Y + (size_t)rows.r0 * ld : Xout;
     GLF_TRY(f.init(ctx, n, ld));
     const int tile = ld >= 64 ? 64 : 32, mb = (int)ld / tile;
     if (f.nchunks > 0) {
@@ -1615,8 +1673,10 @@ static int orthonormalise_fused_dev(glf_ctx *ctx, GsFusedWork &f, float *X, Rows
         hipLaunchKernelGGL(k_gsf_recur_lds, dim3(1), dim3(256), 0, st, ld, m, f.G.p, f.Tn.p, d_norms, f.flag.p, f.h_flag);
     else
         hipLaunchKernelGGL(k_gsf_recur_global, dim3(1), dim3(256), 0, st, ld, m, f.G.p, f.S.p, f.Tn.p, d_norms, f.flag.p, f.h_flag);
+    if (n > 0 && der) // (B - R) rounded to f32, then the f64 product with Tn
+        launch_gsf_apply(st, Xout, der->R + (size_t)rows.r0 * ld, der->AX + (size_t)rows.r0 * ld, n, ld, m, f.Tn.p, f.flag.p);
     if (n > 0)
-        launch_gsf_apply(st, Xl, n, ld, m, f.Tn.p, f.flag.p);
+        launch_gsf_apply(st, Xl, nullptr, Xout, n, ld, m, f.Tn.p, f.flag.p);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(st));
     *fell_back = *(volatile int *)f.h_flag;
@@ -1690,12 +1750,12 @@ static int normalise_dev(glf_ctx *ctx, float *X, unsigned n, unsigned m, unsigne
     hipStream_t st = ctx->stream;
     if (nblk > 0) hipLaunchKernelGGL(k_col_sumsq, dim3(nblk), dim3(256), 0, st, Xl, nloc, ld, d_partial);
     if (rows.dist) {
-        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(1), dim3(256), 0, st, d_partial, nblk, ld, d_sums);
+        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, d_partial, nblk, ld, d_sums);
         GLF_LAUNCH_CHECK(ctx);
         GLF_TRY(allreduce_d(ctx, d_sums, ld));
-        hipLaunchKernelGGL(k_norms_from_partials, dim3(1), dim3(256), 0, st, d_sums, 1, ld, d_norms);
+        hipLaunchKernelGGL(k_norms_from_partials, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, d_sums, 1, ld, d_norms);
     } else {
-        hipLaunchKernelGGL(k_norms_from_partials, dim3(1), dim3(256), 0, st, d_partial, nblk, ld, d_norms);
+        hipLaunchKernelGGL(k_norms_from_partials, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, d_partial, nblk, ld, d_norms);
     }
     if (nloc > 0)
         hipLaunchKernelGGL(k_scale_all, dim3((unsigned)ceil_div((int64_t)nloc * ld, 256)), dim3(256), 0, st, Xl, nloc, ld, m, d_norms);
@@ -1923,12 +1983,12 @@ static int residual_dev(glf_ctx *ctx, ResWork &w, const float *A, int64_t lda, u
     else if (nblk > 0)
         hipLaunchKernelGGL(k_resid, dim3(nblk), dim3(256), 0, st, X + off, w.AX.p + off, w.G.p, nloc, ld, m, w.partial.p);
     if (rows.dist) {
-        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(1), dim3(256), 0, st, w.partial.p, nblk, ld, w.sums.p);
+        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, w.partial.p, nblk, ld, w.sums.p);
         GLF_LAUNCH_CHECK(ctx);
         GLF_TRY(allreduce_d(ctx, w.sums.p, ld));
         GLF_HIP(ctx, hipMemcpyAsync(w.h_sums, w.sums.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
     } else {
-        hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, st, w.partial.p, nblk, (int)ld, w.h_sums);
+        hipLaunchKernelGGL(k_sum_partials, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, w.partial.p, nblk, ld, w.h_sums);
     }
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(st));
@@ -1991,6 +2051,7 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
     GLF_TRY(gs.init(ctx, p, ld));
     CgWork cg;
     GLF_TRY(cg.init(ctx, p, ld, shard));
+    cg.carry_maxima = true;
     ResWork rs;
     GLF_TRY(rs.init(ctx, p, ld, shard));
     // Sharded solve (see Rows above): every vector kernel below touches this rank's rows [rows.r0, rows.r1) only.
@@ -2018,6 +2079,9 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
     if (verbose) fprintf(stderr, "[glf rank %d] initial residual %.9g\n", ctx->comm.rank, r_norm);
     int it = 0, inner_total = 0, rc = GLF_OK;
     const bool derive_ax = !ctx->tune.residual_sweep;
+    // The default route (derived residual, Gram-matrix form every iteration, one rank) runs without its four block passes
+    // per outer iteration -- B into rs.AX, the solution into X, X into Xb, AX -= R: see the loop. Every other route keeps them.
+    const bool swap_blocks = derive_ax && !ctx->tune.gs_seq && opti_gs == 1 && !rows.dist;
     while (r_norm > epsilon) { // :161
         if (it >= max_outer) {
             rc = set_error(ctx, GLF_ERR_NOCONV, "inverse iteration: residual %g > %g after %d outer iterations", r_norm,
@@ -2026,19 +2090,37 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
         }
         ++it;
         int inner = 0;
-        if (derive_ax && nloc) GLF_HIP(ctx, hipMemcpyAsync(rs.AX.p + off, X.p + off, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st)); // B
-        GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner)); // :165-168
-        inner_total += inner;
-        if (nloc) GLF_HIP(ctx, hipMemcpyAsync(Xb.p + off, X.p + off, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st)); // CopyVecs :171
         bool ax_ready = derive_ax;
-        if (derive_ax && nloc) // A Y = B - R
-            hipLaunchKernelGGL(k_sub_inplace, dim3((unsigned)ceil_div((int64_t)nloc_ld, 256)), dim3(256), 0, st, rs.AX.p + off, cg.R.p + off, nloc_ld);
-        if (it % opti_gs == 0) {
-            GLF_TRY(orthonormalise_dev(ctx, gs, X.p, p, m, ld, rows, shard, &replicated)); // :174-177
-            if (ax_ready && gs.last_fused) { // A X_new = (A Y) Tn
-                if (nloc) launch_gsf_apply(st, rs.AX.p + off, nloc, ld, m, gs.fused.Tn.p, gs.fused.flag.p);
-            } else {
-                ax_ready = false; // column-by-column sweep: no triangular map at hand
+        if (swap_blocks) {
+            // X holds B and is only read by the PCG, which leaves Y in cg.Xs; A X_new = (B - R) Tn and X_new = Y Tn are
+            // written out of place, and cg.Xs becomes X_k_before_orth (CopyVecs :171) by a swap of pointers
+            GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner, false)); // :165-168
+            inner_total += inner;
+            const GsDerive der{cg.Xs.p, cg.R.p, rs.AX.p};
+            int fell_back = 0;
+            GLF_TRY(orthonormalise_fused_dev(ctx, gs.fused, X.p, rows, m, ld, gs.norms.p, &fell_back, &der)); // :174-177
+            gs.last_fused = !fell_back;
+            if (fell_back) { // ill-conditioned block: X = Y, the column-by-column sweep in place, the residual from an explicit sweep
+                if (verbose) fprintf(stderr, "[glf] Gram-Schmidt: ill-conditioned block, column-by-column sweep\n");
+                GLF_HIP(ctx, hipMemcpyAsync(X.p, cg.Xs.p, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st));
+                GLF_TRY(orthonormalise_seq_dev(ctx, gs, X.p, p, m, ld));
+                ax_ready = false;
+            }
+            std::swap(cg.Xs.p, Xb.p);
+        } else {
+            if (derive_ax && nloc) GLF_HIP(ctx, hipMemcpyAsync(rs.AX.p + off, X.p + off, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st)); // B
+            GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner)); // :165-168
+            inner_total += inner;
+            if (nloc) GLF_HIP(ctx, hipMemcpyAsync(Xb.p + off, X.p + off, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st)); // CopyVecs :171
+            if (derive_ax && nloc) // A Y = B - R
+                hipLaunchKernelGGL(k_sub_inplace, dim3((unsigned)ceil_div((int64_t)nloc_ld, 256)), dim3(256), 0, st, rs.AX.p + off, cg.R.p + off, nloc_ld);
+            if (it % opti_gs == 0) {
+                GLF_TRY(orthonormalise_dev(ctx, gs, X.p, p, m, ld, rows, shard, &replicated)); // :174-177
+                if (ax_ready && gs.last_fused) { // A X_new = (A Y) Tn
+                    if (nloc) launch_gsf_apply(st, rs.AX.p + off, nullptr, rs.AX.p + off, nloc, ld, m, gs.fused.Tn.p, gs.fused.flag.p);
+                } else {
+                    ax_ready = false; // column-by-column sweep: no triangular map at hand
+                }
             }
         }
         GLF_LAUNCH_CHECK(ctx);
@@ -2154,7 +2236,7 @@ static int panels_residual(glf_ctx *ctx, PanelWork &w, const float *A, int64_t l
                                PANEL, panel_cols(m, i), w.C.p);
         }
         hipLaunchKernelGGL(k_col_sumsq, dim3(nblk), dim3(256), 0, st, w.R.p, p, PANEL, w.partial.p);
-        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(1), dim3(256), 0, st, w.partial.p, nblk, PANEL, w.sums.p);
+        hipLaunchKernelGGL(k_sum_partials_nv<1>, dim3(red2_grid(PANEL)), dim3(RED2_THREADS), 0, st, w.partial.p, nblk, PANEL, w.sums.p);
         GLF_LAUNCH_CHECK(ctx);
         GLF_HIP(ctx, hipMemcpyAsync(h.data(), w.sums.p, sizeof(double) * PANEL, hipMemcpyDeviceToHost, st));
         GLF_HIP(ctx, hipStreamSynchronize(st));

@@ -47,6 +47,7 @@ struct glf_tuning {
     bool band_noskip = false;    // BAND_NOSKIP: band-form Nystroem kernel executes every (row pair, half-block) of its workgroup's range, the exact zeros outside a wave's window included (same bits, more work: the check that the schedule loses no unit)
     bool pix_band = false;       // PIX_BAND: the colour and 16-bit bilateral kernels take the band form (Nystroem stage and operator) where the grey kernel would; off: entry by entry, L_A stored
     bool no_narrow = false;      // NO_NARROW: block PCG applies the operator to all columns of the block even when few still iterate
+    bool operand_maxima_sweep = false; // OPERAND_MAXIMA=sweep: the operator finds its operand's column maxima itself (a pass over the block) even where block PCG carries them (ColMaxima); same bits either way: a max does not depend on the order
     bool verbose = false;        // VERBOSE: log every outer iteration on stderr (the reference does, hpc/inverse_power_it.c:164-181)
 };
 
@@ -651,8 +652,76 @@ int filter_sample_rows(glf_ctx *ctx, const float *d_phiA, unsigned n, unsigned l
 int grid_op_path(const GridOp *op);                          // glf_stats.matvec_path: 1 exact grid form, 3 rank form
 int grid_op_row_len(const GridOp *op);                       // samples per grid row (a row range of the operator is whole grid rows)
 bool grid_op_can_skip(const GridOp *op);                     // the grid and rank forms' exact-zero skipping has something to skip (window != 0 turns it on)
+// Column maxima of |X| that the kernel which wrote the operand X left behind, per block of its rows: part[b * ld + c], b < nblk,
+// over ALL p rows (any partition of the rows gives the same max). With it a sweep skips its own pass over X for the scales.
+struct ColMaxima {
+    const float *part;
+    int nblk;
+};
+// maxima: optional (band, grid and rank forms; ignored under OPERAND_MAXIMA=sweep)
 int grid_op_apply(glf_ctx *ctx, GridOp *op, const float *X, float *Y, unsigned ld, double alpha, const double *d_degree,
-                  unsigned row0, unsigned row1, int window);
+                  unsigned row0, unsigned row1, int window, const ColMaxima *maxima = nullptr);
+
+// Second level of the column reductions: out[v] = the sum (MAX: the maximum, of values >= 0) over b < nblk of
+// part[(b * NV + v) * ld + col], in a fixed order. The kernel is launched with red2_grid(ld) workgroups of RED2_THREADS
+// threads; a workgroup takes RED2_COLS columns, so at p = 85 264 (667 blocks of 128 rows) each of its 128 thread rows
+// loads 6 blocks, all of them independent loads of one batch (a single workgroup over all the columns walked 6 - 21
+// dependent batches: 8 - 16 us of L2 round trips between two sweeps of the solver). The thread rows are combined through
+// LDS, 128 -> 16 -> 1. out[] is valid in threads t < RED2_COLS, for column blockIdx.x * RED2_COLS + t.
+constexpr int RED2_COLS = 8, RED2_THREADS = 1024, RED2_BATCH = 8;
+inline unsigned red2_grid(unsigned ld) { return ld / RED2_COLS; } // (ld is a multiple of 32)
+template <typename T, int NV, bool MAX>
+__device__ __forceinline__ void wg_reduce_partials(const T *__restrict__ part, int nblk, unsigned ld, T (&out)[NV],
+                                                   T *sh /* LDS [NV][RED2_THREADS] */)
+{
+    constexpr int NP = RED2_THREADS / RED2_COLS, G = 16;
+    const int t = threadIdx.x, c = t % RED2_COLS, row = t / RED2_COLS;
+    const unsigned col = blockIdx.x * RED2_COLS + c;
+    auto comb = [](T a, T b) {
+        if constexpr (MAX) return a > b ? a : b;
+        else return a + b;
+    };
+    T acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = T(0);
+    for (int b0 = row; b0 < nblk; b0 += RED2_BATCH * NP) {
+        T x[RED2_BATCH][NV]; // every load is issued (a block past the end re-reads the last one), then the valid ones are combined in order
+#pragma unroll
+        for (int u = 0; u < RED2_BATCH; ++u)
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const int b = b0 + u * NP < nblk ? b0 + u * NP : nblk - 1;
+                x[u][v] = part[((size_t)b * NV + v) * ld + col];
+            }
+#pragma unroll
+        for (int u = 0; u < RED2_BATCH; ++u)
+#pragma unroll
+            for (int v = 0; v < NV; ++v)
+                if (b0 + u * NP < nblk) acc[v] = comb(acc[v], x[u][v]);
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v) sh[v * RED2_THREADS + t] = acc[v];
+    __syncthreads();
+    if (t < RED2_COLS * G) // thread row g < G: rows g, g + G, ...
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            acc[v] = T(0);
+            for (int r = row; r < NP; r += G) acc[v] = comb(acc[v], sh[v * RED2_THREADS + r * RED2_COLS + c]);
+        }
+    __syncthreads();
+    if (t < RED2_COLS * G)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) sh[v * RED2_THREADS + t] = acc[v];
+    __syncthreads();
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        T s = T(0);
+        if (t < RED2_COLS)
+            for (int g = 0; g < G; ++g) s = comb(s, sh[v * RED2_THREADS + g * RED2_COLS + c]);
+        out[v] = s;
+    }
+    __syncthreads();
+}
 
 struct MatShard {
     unsigned row0 = 0, row1 = 0, rows_per_rank = 0;
@@ -677,7 +746,7 @@ inline unsigned vec_rows(unsigned p, const MatShard *sh, int size)
     return g > base ? g : base;
 }
 int block_matvec(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, const float *X, float *Y,
-                 unsigned mld, const MatShard *shard = nullptr);
+                 unsigned mld, const MatShard *shard = nullptr, const ColMaxima *maxima = nullptr); // maxima: see ColMaxima (the stored forms ignore it)
 // the stored split-f16 sweep's K slabs for the rows [row0, row1) (fills the 2-workgroups-per-CU residency evenly), and whether its
 // tile list can hold p samples (exact-zero tile skipping)
 int mv_ksplit(const glf_ctx *ctx, unsigned p, unsigned row0, unsigned row1);

@@ -460,9 +460,14 @@ __global__ __launch_bounds__(256) void k_col_absmax_fin(const float *__restrict_
         out[col] = m;
     }
 }
-// scratch: ceil(p / CAM_ROWS) * ld floats
-static void col_absmax(hipStream_t st, const float *psi, unsigned p, unsigned ld, float *scratch, float *out)
+// scratch: ceil(p / CAM_ROWS) * ld floats; carried: the block maxima are at hand already (ColMaxima), only the second level runs
+static void col_absmax(hipStream_t st, const float *psi, unsigned p, unsigned ld, float *scratch, float *out,
+                       const ColMaxima *carried = nullptr)
 {
+    if (carried) {
+        hipLaunchKernelGGL(k_col_absmax_fin, dim3(1), dim3(256), 0, st, carried->part, carried->nblk, ld, out);
+        return;
+    }
     const int nblk = (int)ceil_div(p, CAM_ROWS);
     hipLaunchKernelGGL(k_col_absmax_part, dim3(nblk), dim3(256), 0, st, psi, p, ld, scratch);
     hipLaunchKernelGGL(k_col_absmax_fin, dim3(1), dim3(256), 0, st, scratch, nblk, ld, out);

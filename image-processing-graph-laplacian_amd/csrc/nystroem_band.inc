@@ -101,25 +101,16 @@ __global__ __launch_bounds__(256) void k_band_prep(const float *__restrict__ X, 
 
 // second level of the column maxima (k_col_absmax_part's block maxima) and the scales in one launch:
 // colscale[j] = 2^e with |X[:, j]| 2^e in [2^13, 2^14); inv[j] = 2^(-e - 15) takes it and the 2^15 of the kernel out again
-__global__ __launch_bounds__(256) void k_band_absmax_scales(const float *__restrict__ part, int nblk, unsigned ld, float *__restrict__ colscale,
-                                                             float *__restrict__ inv)
+// (red2_grid(ld) workgroups of RED2_THREADS threads: wg_reduce_partials)
+__global__ __launch_bounds__(RED2_THREADS) void k_band_absmax_scales(const float *__restrict__ part, int nblk, unsigned ld,
+                                                                      float *__restrict__ colscale, float *__restrict__ inv)
 {
-    __shared__ float sh[256];
-    const unsigned npt = 256 / ld, col = threadIdx.x % ld, r0 = threadIdx.x / ld; // (ld <= 256, a power of two)
-    float m = 0.f;
-    int b = (int)r0;
-    for (; b + 7 * (int)npt < nblk; b += 8 * (int)npt) { // eight loads in flight at a time
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = part[(size_t)(b + u * (int)npt) * ld + col];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) m = fmaxf(m, x[u]);
-    }
-    for (; b < nblk; b += (int)npt) m = fmaxf(m, part[(size_t)b * ld + col]);
-    sh[threadIdx.x] = m;
-    __syncthreads();
-    if (threadIdx.x < ld) {
-        for (unsigned r = 1; r < npt; ++r) m = fmaxf(m, sh[r * ld + col]);
+    __shared__ float sh[RED2_THREADS];
+    float mx[1];
+    wg_reduce_partials<float, 1, true>(part, nblk, ld, mx, sh);
+    if (threadIdx.x < RED2_COLS) {
+        const unsigned col = blockIdx.x * RED2_COLS + threadIdx.x;
+        const float m = mx[0];
         int e = 0;
         if (m > 0.f && isfinite(m)) {
             int ex;
@@ -131,12 +122,19 @@ __global__ __launch_bounds__(256) void k_band_absmax_scales(const float *__restr
         inv[col] = ldexpf(1.0f, -e - (int)NYS_F16_KSCALE_LOG2);
     }
 }
-// the column maxima of X, then colscale / inv (two launches)
-static void band_scales(hipStream_t st, const float *X, unsigned p, unsigned ld, float *scratch, float *colscale, float *inv)
+// the column maxima of X, then colscale / inv (two launches; one where the writer of X carried the block maxima along)
+static void band_scales(hipStream_t st, const float *X, unsigned p, unsigned ld, float *scratch, float *colscale, float *inv,
+                        const ColMaxima *carried = nullptr)
 {
-    const int nblk = (int)ceil_div(p, CAM_ROWS);
-    hipLaunchKernelGGL(k_col_absmax_part, dim3(nblk), dim3(256), 0, st, X, p, ld, scratch);
-    hipLaunchKernelGGL(k_band_absmax_scales, dim3(1), dim3(256), 0, st, scratch, nblk, ld, colscale, inv);
+    const float *part = scratch;
+    int nblk = (int)ceil_div(p, CAM_ROWS);
+    if (carried) {
+        part = carried->part;
+        nblk = carried->nblk;
+    } else {
+        hipLaunchKernelGGL(k_col_absmax_part, dim3(nblk), dim3(256), 0, st, X, p, ld, scratch);
+    }
+    hipLaunchKernelGGL(k_band_absmax_scales, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, part, nblk, ld, colscale, inv);
 }
 
 // (filter.hip's filter_output: trunc(y + c) = y + floor(c) wherever y + c >= 0, clamped, NaN -> 0)

@@ -1515,8 +1515,9 @@ bool grid_op_can_skip(const GridOp *op) { return !op->use_band && op->can_skip; 
 // Y[s][:] = alpha (D_s X[s][:] - (K_A X)[s][:]) for the samples s in [row0, row1) (whole grid rows); X holds all p rows.
 template <int NT>
 static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, unsigned ld_total, double alpha,
-                            const double *d_degree, unsigned row0, unsigned row1, int window)
+                            const double *d_degree, unsigned row0, unsigned row1, int window, const ColMaxima *maxima)
 {
+    if (ctx->tune.operand_maxima_sweep) maxima = nullptr;
     constexpr unsigned LD = 32 * NT;
     hipStream_t st = ctx->stream;
     const int nr = op->g.nr, nc = op->g.nc, ks = op->ks, ksc = op->ksc;
@@ -1531,7 +1532,7 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
             GLF_TRY(op->band_chunks.alloc(ctx, (size_t)nr * ksc * band_chunk_bytes(2)));
             op->work_ld = ld_total;
         }
-        band_scales(st, X, op->p, ld_total, op->camx.p, op->colscale.p, op->band_inv.p);
+        band_scales(st, X, op->p, ld_total, op->camx.p, op->colscale.p, op->band_inv.p, maxima);
         for (unsigned c0 = 0; c0 < ld_total; c0 += LD) {
             const bool raw = op->gen != PixGen::Grey;
             const uint8_t *sv = raw ? reinterpret_cast<const uint8_t *>(op->svals32.p) : op->svals.p;
@@ -1558,7 +1559,7 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         op->work_ld = ld_total;
     }
     // per-column power-of-two scales from max |X[:, n]| (device side: no host round trip inside the PCG loop)
-    col_absmax(st, X, op->p, ld_total, op->camx.p, op->colmax.p);
+    col_absmax(st, X, op->p, ld_total, op->camx.p, op->colmax.p, maxima);
     hipLaunchKernelGGL(k_gridop_scales, dim3(1), dim3(256), 0, st, op->colmax.p, ld_total, nr, op->colscale.p, op->tscale.p,
                        op->tinv.p);
     constexpr int MT = GRID_MT;
@@ -1629,10 +1630,10 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
 }
 
 int grid_op_apply(glf_ctx *ctx, GridOp *op, const float *X, float *Y, unsigned ld, double alpha, const double *d_degree,
-                  unsigned row0, unsigned row1, int window)
+                  unsigned row0, unsigned row1, int window, const ColMaxima *maxima)
 {
     if (row0 % op->g.nc || (row1 % op->g.nc && row1 != op->p))
         return set_error(ctx, GLF_ERR_INVALID, "grid_op_apply: rows [%u, %u) are not whole grid rows", row0, row1);
-    if (ld >= 64) return grid_op_apply_nt<2>(ctx, op, X, Y, ld, alpha, d_degree, row0, row1, window);
-    return grid_op_apply_nt<1>(ctx, op, X, Y, ld, alpha, d_degree, row0, row1, window);
+    if (ld >= 64) return grid_op_apply_nt<2>(ctx, op, X, Y, ld, alpha, d_degree, row0, row1, window, maxima);
+    return grid_op_apply_nt<1>(ctx, op, X, Y, ld, alpha, d_degree, row0, row1, window, maxima);
 }

@@ -842,7 +842,7 @@ class Context:
     def synchronize(self):
         self._check(_lib.glf_ctx_synchronize(self._ctx))
 
-    TUNING_KEYS = ("NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "FILTER_FORM", "BAND_NOSKIP", "PIX_BAND", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "VERBOSE")
+    TUNING_KEYS = ("NYS_PATH", "DEG_PATH", "MV_PATH", "ROWPASS", "ROWPASS_OP", "SWEEP_COLPASS", "COLPASS", "NYS_NO_LUT", "NO_ECR", "NO_NARROW", "NO_FUSED_FILTER", "FILTER_FORM", "BAND_NOSKIP", "PIX_BAND", "EIG_SHARD", "ZMFMA_GROUPS", "GS", "RESIDUAL", "OPERAND_MAXIMA", "VERBOSE")
 
     def set_tuning(self, **kw):
         """glf_ctx_set_tuning: e.g. set_tuning(NYS_PATH="grid", MV_PATH="dense"); None / "" / "auto" = the default choice."""
