@@ -114,9 +114,9 @@ int glf_ctx_set_tuning(glf_ctx *ctx, const char *key, const char *value)
     else if (!std::strcmp(key, "NO_ECR")) t.no_ecr = flag();
     else if (!std::strcmp(key, "NO_NARROW")) t.no_narrow = flag();
     else if (!std::strcmp(key, "NO_FUSED_FILTER")) t.no_fused_filter = flag();
-    else if (!std::strcmp(key, "FILTER_FORM")) { // the fused filter: contracted with q = Psi w (k_band_vec) | k_band's epilogue over Phi's columns
-        if (!unset && !is("vec") && !is("phi")) return GLF_ERR_INVALID;
-        t.filter_form_phi = is("phi");
+    else if (!std::strcmp(key, "FILTER_FORM")) { // the fused filter: separable rank-R form (k_band_sep_*) | contracted with q = Psi w (k_band_vec) | k_band's epilogue over Phi's columns
+        if (!unset && !is("sep") && !is("vec") && !is("phi")) return GLF_ERR_INVALID;
+        t.filter_form = is("sep") ? 1 : is("vec") ? 2 : is("phi") ? 3 : 0;
     } else if (!std::strcmp(key, "BAND_NOSKIP")) t.band_noskip = flag();
     else if (!std::strcmp(key, "PIX_BAND")) t.pix_band = flag();
     else if (!std::strcmp(key, "ZMFMA_GROUPS")) t.zmfma_groups = flag();

@@ -43,7 +43,7 @@ struct glf_tuning {
     bool zmfma_groups = false;   // ZMFMA_GROUPS: degree row contraction in groups of five m-tiles (two n-tiles per wave) even when ten fit one wave
     int eig_shard = 0;           // EIG_SHARD: 0 auto (row-sharded eigen-solve unless the operator is in band form), 1 sharded, 2 replicated
     bool no_fused_filter = false; // NO_FUSED_FILTER: band form writes Phi and the filter runs as its own stage (k_apply_filter)
-    bool filter_form_phi = false; // FILTER_FORM: the fused filter of the band form: false / vec = contracted with q = Psi w, one column per plane (k_band_vec); true / phi = k_band's epilogue over the 64 columns of Phi
+    int filter_form = 0;         // FILTER_FORM: the fused filter of the band form: 0 auto (sep where supported, else vec, else phi), 1 / sep = separable rank-R form (k_band_sep_*), 2 / vec = contracted with q = Psi w pair by pair, one column per plane (k_band_vec), 3 / phi = k_band's epilogue over the 64 columns of Phi
     bool band_noskip = false;    // BAND_NOSKIP: band-form Nystroem kernel executes every (row pair, half-block) of its workgroup's range, the exact zeros outside a wave's window included (same bits, more work: the check that the schedule loses no unit)
     bool pix_band = false;       // PIX_BAND: the colour and 16-bit bilateral kernels take the band form (Nystroem stage and operator) where the grey kernel would; off: entry by entry, L_A stored
     bool no_narrow = false;      // NO_NARROW: block PCG applies the operator to all columns of the block even when few still iterate

@@ -966,6 +966,10 @@ static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *c
 static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
                                     const float4 *d_samples, const uint8_t *d_mask, unsigned p, const float *d_psi, unsigned ld, const BandFilter &flt,
                                     float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats);
+// (nystroem_band_sep.inc: the same sum in separable form, the photometric table as its rank-R expansion)
+static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
+                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
+                                    const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats);
 
 // Nystroem extension of the image rows [pix0 / width, pix1 / width) in band form (see the head of this file)
 static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
@@ -990,7 +994,14 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     const bool raw = gen != PixGen::Grey;
     if (raw && (flt || d_c)) return GLF_ERR_UNSUPPORTED; // (no 8-bit y: the filter stays a stage of its own)
     if (flt && ld_total > 64) return GLF_ERR_UNSUPPORTED; // (the filter's dot product with w runs over one block of at most 64 columns)
-    if (flt && !ctx->tune.filter_form_phi) { // FILTER_FORM=vec: one column per plane instead of Phi's; its LDS window too large: k_band's epilogue
+    // FILTER_FORM: sep (separable rank-R form) where the photometric table has an expansion, else vec (pair by pair, one column per
+    // plane instead of Phi's), else -- its LDS window too large -- k_band's epilogue
+    if (flt && ctx->tune.filter_form <= 1) {
+        const int rc = launch_nystroem_band_sep(ctx, bt, d_img, width, pix0, pix1, d_samples, d_mask, p, coef, d_psi, ld_total, *flt, kernel_ms,
+                                                entries_evaluated, mfma_flops, stats);
+        if (rc != GLF_ERR_UNSUPPORTED) return rc;
+    }
+    if (flt && ctx->tune.filter_form <= 2) {
         const int rc = launch_nystroem_band_vec(ctx, bt, d_img, width, pix0, pix1, d_samples, d_mask, p, d_psi, ld_total, *flt, kernel_ms,
                                                 entries_evaluated, mfma_flops, stats);
         if (rc != GLF_ERR_UNSUPPORTED) return rc;

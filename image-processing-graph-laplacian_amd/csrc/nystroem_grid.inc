@@ -1365,6 +1365,7 @@ inline size_t svals32_planes(glf::PixGen g) { return g == glf::PixGen::RgbF32 ? 
 #include "nystroem_rank.inc"
 #include "nystroem_band.inc"
 #include "nystroem_band_vec.inc"
+#include "nystroem_band_sep.inc"
 
 } // namespace glf (GridOp is declared at global scope in glf_internal.hpp)
 

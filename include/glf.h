@@ -67,9 +67,12 @@ int glf_ctx_device_info(const glf_ctx *ctx, char *name, size_t name_len, int *nu
  *   NYS_PATH  band | rank | grid | direct     DEG_PATH  grid | direct     MV_PATH  band | rank | grid | dense
  *   ROWPASS, ROWPASS_OP  rt | v1     COLPASS  ws | v1     SWEEP_COLPASS  segments | samples
  *   NYS_NO_LUT, NO_ECR, NO_NARROW, NO_FUSED_FILTER, BAND_NOSKIP, ZMFMA_GROUPS, VERBOSE  1 | 0     EIG_SHARD  1 | 0       GS        seq | gram          RESIDUAL  sweep | derived
- *   FILTER_FORM  vec | phi (default vec): the filter fused into the band-form Nystroem launch is contracted with q = Psi w, one
- *     column per plane (k_band_vec), or taken from the 64 columns of Phi in k_band's epilogue (also where the window of samples of
- *     the vec form does not fit the LDS). Same conditions for fusing, same stats keys; nystroem_mfma_flops = 0 under vec.
+ *   FILTER_FORM  sep | vec | phi (default: sep where it applies, else vec, else phi): the filter fused into the band-form Nystroem
+ *     launch is contracted with q = Psi w, one column per plane, in separable form with the photometric table as a rank-R expansion
+ *     (k_band_sep_*: a row pass and a column pass; needs an expansion of at most 48 terms, stats rank_terms = R), pair by pair
+ *     with the exact table (k_band_vec; rank_terms = 0), or taken from the 64 columns of Phi in k_band's epilogue (also where the
+ *     window of samples of the vec form does not fit the LDS). Same conditions for fusing, same stats keys; nystroem_mfma_flops = 0
+ *     under sep and vec.
  *   PIX_BAND  1 | 0 (default 0): the colour, 16-bit, float and float colour bilateral kernels (GLF_KERNEL_BILATERAL_RGB / _U16 / _F32 / _RGBF32) take the band form of
  *     the Nystroem stage and of the L_A operator under exactly the conditions under which the grey kernel takes it -- split-f16
  *     contraction, a tensor-grid sample set, at most 64 eigenpairs, the radius and band-row limits, NYS_PATH auto (width >= 1024)
