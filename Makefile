@@ -53,8 +53,13 @@ basis_check: tools/basis_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.h
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o $(BASIS_CHECK_BIN) $(filter %.cpp,$^)
 	$(BASIS_CHECK_BIN)
 
+# the window plan of the fused band filter (band_rows_hull, band_cols_range, BandGeom::window) under the address and undefined-behaviour sanitizers (CPU only)
+band_plan_check: tools/band_plan_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp include/glf.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/band_plan_host_check $(filter %.cpp,$^)
+	tools/band_plan_host_check
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean pfm_check cluster_check basis_check
+.PHONY: all oracle clean pfm_check cluster_check basis_check band_plan_check

@@ -43,6 +43,38 @@ GLF_BAND_HD inline unsigned band_win_hull(unsigned u, unsigned v)
     const unsigned hi = (u >> 16) > (v >> 16) ? (u >> 16) : (v >> 16);
     return lo | (hi << 16);
 }
+// hull of the bands (rowband[r] = BandGeom::band_of(r)) of the n target rows from r0; *alo = 0xFFFF > *ahi = -1: none of them has one
+GLF_BAND_HD inline void band_rows_hull(const unsigned *rowband, int r0, int n, int *alo, int *ahi)
+{
+    int lo = 0xFFFF, hi = -1;
+    for (int w = 0; w < n; ++w) {
+        const unsigned rb = rowband[r0 + w];
+        if (!band_win_live(rb)) continue;
+        lo = (int)(rb & 0xFFFFu) < lo ? (int)(rb & 0xFFFFu) : lo;
+        hi = (int)(rb >> 16) > hi ? (int)(rb >> 16) : hi;
+    }
+    *alo = lo;
+    *ahi = hi;
+}
+// the ascending sample columns gcol[0 .. nc) inside [cmin, cmax]: *lo = the first one >= cmin, *count of them (0 where cmax < cmin)
+GLF_BAND_HD inline void band_cols_range(const int *gcol, int nc, int cmin, int cmax, int *lo, int *count)
+{
+    int l = 0, h = nc; // first column >= cmin
+    while (l < h) {
+        const int mid = (l + h) >> 1;
+        if (gcol[mid] < cmin) l = mid + 1;
+        else h = mid;
+    }
+    const int first = l;
+    h = nc; // first column > cmax, from there on
+    while (l < h) {
+        const int mid = (l + h) >> 1;
+        if (gcol[mid] <= cmax) l = mid + 1;
+        else h = mid;
+    }
+    *lo = first;
+    *count = l - first;
+}
 
 // radius and windows of one (sample grid, spatial coefficient)
 struct BandGeom {

@@ -629,13 +629,14 @@ struct BandSignals {
     float *out = nullptr;
     int64_t N = 0;
 };
+// (the fused kernels take it by value: what only k_band_q / k_band_sep_g read -- w and sig.w -- sits behind what every lane stores with)
 struct BandFilter {
-    BandSignals sig;
-    const float *w = nullptr; // [ld] filter weights x c (device)
     float gain = 0.f, ysub = 0.f;
     uint8_t *out = nullptr;   // [N] (absolute pixel index)
     float *zf = nullptr;      // [N] or null
     float *corr = nullptr;    // [pix1 - pix0] or null
+    BandSignals sig;
+    const float *w = nullptr; // [ld] filter weights x c (device)
 };
 // GLF_ERR_UNSUPPORTED: the band form does not apply (not a tensor grid, radius too large, or auto mode prefers a factored form)
 int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const float4 *d_samples,

@@ -546,10 +546,10 @@ unsigned BandGeom::band_of(int r) const
 unsigned BandGeom::window(int cmin, int cmax, int dr, int shift) const
 {
     if (dcmax[dr] < 0) return BAND_EMPTY;
-    const int lo = (int)(std::lower_bound(cols.begin(), cols.end(), cmin - dcmax[dr]) - cols.begin());
-    const int hi = (int)(std::upper_bound(cols.begin(), cols.end(), cmax + dcmax[dr]) - cols.begin()) - 1;
-    if (hi < lo) return BAND_EMPTY;
-    return (unsigned)(lo >> shift) | ((unsigned)(hi >> shift) << 16);
+    int lo = 0, n = 0;
+    band_cols_range(cols.data(), (int)cols.size(), cmin - dcmax[dr], cmax + dcmax[dr], &lo, &n);
+    if (n <= 0) return BAND_EMPTY;
+    return (unsigned)(lo >> shift) | ((unsigned)((lo + n - 1) >> shift) << 16);
 }
 
 } // namespace glf

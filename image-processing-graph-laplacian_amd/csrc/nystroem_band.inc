@@ -137,13 +137,40 @@ static void band_scales(hipStream_t st, const float *X, unsigned p, unsigned ld,
     hipLaunchKernelGGL(k_band_absmax_scales, dim3(red2_grid(ld)), dim3(RED2_THREADS), 0, st, part, nblk, ld, colscale, inv);
 }
 
-// (filter.hip's filter_output: trunc(y + c) = y + floor(c) wherever y + c >= 0, clamped, NaN -> 0)
-__device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
+// The filter of one pixel px that is no sample, from sdot[k] = Phi[px] . w_k (k = 0: the guide, then the planes of joint filtering):
+// hpc/display.c:64-78 as k_apply_filter has it, Phi never written. The one store of every form of the fused filter -- k_band's
+// epilogue, k_band_vec, k_band_sep_cols; y: the guide's value at px.
+template <int NC>
+__device__ __forceinline__ void band_filter_store(const BandFilter &f, int64_t pix0, int64_t px, int y, const float (&sdot)[NC])
 {
-    int zi = y + (int)floorf(fminf(fmaxf(c, -1.0e6f), 1.0e6f));
-    zi = zi > 255 ? 255 : zi;
-    zi = (zi < 0 || !(c == c)) ? 0 : zi;
-    return (uint8_t)zi;
+    const float cc = f.gain * sdot[0] - f.ysub * (float)y;
+    if (f.zf) f.zf[px] = (float)y + cc;
+    if (f.corr) f.corr[px - pix0] = cc;
+    f.out[px] = filter_output(y, cc);
+#pragma unroll
+    for (int k = 1; k < NC; ++k) {
+        const float v = f.sig.s[(size_t)(k - 1) * f.sig.N + px];
+        f.sig.out[(size_t)(k - 1) * f.sig.N + px] = v + (f.gain * sdot[k] - f.ysub * v);
+    }
+}
+// k_band_vec and k_band_sep_cols sum with the Er15 table, which carries k_band's 2^15 (k_band's inv[] takes it out); their f64
+// totals lose it here
+constexpr double BAND_UNSCALE = 1.0 / 32768.0;
+static_assert(NYS_F16_KSCALE_LOG2 == 15.0f, "BAND_UNSCALE takes the scale of the Er15 table out again");
+
+// the fused filter's columns: the guide and up to GLF_MAX_SIGNALS planes, one instantiation of its kernels per count
+constexpr int BANDV_MAXNC = 1 + GLF_MAX_SIGNALS;
+template <class F> static int band_dispatch_planes(int n, F &&f)
+{
+    static_assert(BANDV_MAXNC == 5, "one instantiation per column count");
+    switch (n) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    default: return GLF_ERR_UNSUPPORTED;
+    }
 }
 
 // MB: n-tiles of 32 columns; PB: tiles of 32 targets per wave; NW: waves per workgroup. The waves of a workgroup take the
@@ -153,7 +180,8 @@ __device__ __forceinline__ uint8_t filter_output_u8(int y, float c)
 // SAMPLES = false: targets = the pixels of image rows [row_begin, row_begin + gridDim.y): out = Phi (+ column offset), epilogue
 //   as k_nystroem_f16s (sample pixels skipped unless raster; c += Phi^T y per workgroup).
 // SAMPLES = true: targets = the samples of grid rows [row_begin, ..): out = Y = alpha (D X - K_A X).
-// NS > 0 (joint filtering): NS float planes through the same filter in the epilogue, fsig.w [NS][LD] their weights
+// fw set: the filter in the epilogue (band_filter_store) instead of Phi. NS > 0 (joint filtering): NS float planes through the
+//   same filter, fsig.w [NS][LD] their weights
 // G: the pixel format. Grey: the photometric factor is one LDS gather per entry from the 256-level table. Rgb, U16, F32: tval is the
 //   image in the format (pixel targets) or the u32 image of the sample values (sample targets), the chunk tails carry the raw u32
 //   values (F32: the float's bit pattern), and the factor is P = exp2(pix_nsval dist2) with Pix<G>::dist2 and one v_exp_f32 per entry (pix_nsval = -s_val); no
@@ -209,14 +237,8 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     const int trow0 = row_begin + blockIdx.y * NW; // target row of wave 0 (image row / grid row)
     const int tile = blockIdx.x, ntw = min(NW, row_end - trow0); // waves with a target row
     // band of the workgroup: the grid rows within the radius of any of its target rows
-    int alo = 0xFFFF, ahi = -1;
-    for (int w = 0; w < ntw; ++w) {
-        const unsigned rb = rowband[trow0 + w];
-        if ((rb & 0xFFFFu) <= (rb >> 16)) {
-            alo = min(alo, (int)(rb & 0xFFFFu));
-            ahi = max(ahi, (int)(rb >> 16));
-        }
-    }
+    int alo, ahi;
+    band_rows_hull(rowband, trow0, ntw, &alo, &ahi);
     const int nb = min(BAND_MAXROWS, max(0, ahi - alo + 1));
 
     // the replicated photometric table arrives by LDS-DMA from its expanded image in the tables blob (256 BAND_PCOPY floats, after
@@ -568,7 +590,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     while (blk <= Bhi) {
         int issued = 0;
         if (qblk[BAND_NBUF - 1] <= Bhi) issued = issue(qblk[BAND_NBUF - 1], qg0[BAND_NBUF - 1], (buf + BAND_NBUF - 1) % BAND_NBUF);
-        if (wvalid) {
+        if (wvalid || noskip) { // (noskip: a wave without a target row walks too, as in k_band_vec and k_band_sep_cols -- its Er15 is 0 and it writes nothing)
             if (blk != cur_blk) {
                 cur_blk = blk;
 #pragma unroll
@@ -616,56 +638,41 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
         csum[j] = 0.f;
     }
     if (GREY && !SAMPLES && fw) {
-        // filter in the epilogue: s = Phi[px] . w summed over the 32 lanes that hold the pixel's columns, then hpc/display.c:64-78
-        // as k_apply_filter has it; Phi is not written (the sample pixels are filter_sample_rows' from Phi_A)
+        // filter in the epilogue: s_k = Phi[px] . w_k (the guide's w, then the planes' fsig.w [NS][LD]), each summed over the 32 lanes
+        // that hold the pixel's columns, then band_filter_store; Phi is not written. (The filter arrives as loose scalars and becomes a
+        // BandFilter here: taken by value it moved the registers of the instantiations that write Phi or Y.)
         if (wvalid) {
-            float wv[MB];
+            BandFilter flt;
+            flt.sig = fsig;
+            flt.w = fw;
+            flt.gain = fgain;
+            flt.ysub = fysub;
+            flt.out = fout;
+            flt.zf = fzf;
+            flt.corr = fcorr;
+            float wv[1 + NS][MB];
 #pragma unroll
-            for (int j = 0; j < MB; ++j) wv[j] = fw[32 * j + l31] * iv[j];
+            for (int k = 0; k <= NS; ++k)
+#pragma unroll
+                for (int j = 0; j < MB; ++j) wv[k][j] = (k == 0 ? flt.w[32 * j + l31] : flt.sig.w[(k - 1) * LD + 32 * j + l31]) * iv[j];
 #pragma unroll
             for (int b = 0; b < PB; ++b) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
-                    float sdot = 0.f;
+                    float sdot[1 + NS];
 #pragma unroll
-                    for (int j = 0; j < MB; ++j) sdot = fmaf(acc[b][j][q], wv[j], sdot);
+                    for (int k = 0; k <= NS; ++k) {
+                        sdot[k] = 0.f;
 #pragma unroll
-                    for (int o = 16; o > 0; o >>= 1) sdot += __shfl_xor(sdot, o, 64);
+                        for (int j = 0; j < MB; ++j) sdot[k] = fmaf(acc[b][j][q], wv[k][j], sdot[k]);
+#pragma unroll
+                        for (int o = 16; o > 0; o >>= 1) sdot[k] += __shfl_xor(sdot[k], o, 64);
+                    }
                     const int col = (tile * PB + b) * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
                     if (l31 == 0 && col < width) {
                         const int64_t px = (int64_t)trow * width + col;
-                        if (mask[px]) continue; // (a sample: filter_sample_rows writes it from Phi_A)
-                        const int y = (int)tval[px];
-                        const float cc = fgain * sdot - fysub * (float)y;
-                        if (fzf) fzf[px] = (float)y + cc;
-                        if (fcorr) fcorr[px - fpix0] = cc;
-                        fout[px] = filter_output_u8(y, cc);
-                    }
-                }
-            }
-            if constexpr (NS > 0) { // the planes: one more dot product and 32-lane reduction each per pixel, accumulators still live
-#pragma unroll
-                for (int k = 0; k < NS; ++k) {
-                    float sv[MB];
-#pragma unroll
-                    for (int j = 0; j < MB; ++j) sv[j] = fsig.w[k * LD + 32 * j + l31] * iv[j];
-#pragma unroll
-                    for (int b = 0; b < PB; ++b) {
-#pragma unroll
-                        for (int q = 0; q < 16; ++q) {
-                            float sdot = 0.f;
-#pragma unroll
-                            for (int j = 0; j < MB; ++j) sdot = fmaf(acc[b][j][q], sv[j], sdot);
-#pragma unroll
-                            for (int o = 16; o > 0; o >>= 1) sdot += __shfl_xor(sdot, o, 64);
-                            const int col = (tile * PB + b) * 32 + (q & 3) + 8 * (q >> 2) + 4 * half;
-                            if (l31 == 0 && col < width) {
-                                const int64_t px = (int64_t)trow * width + col;
-                                if (mask[px]) continue; // (filter_sample_rows_signals)
-                                const float v = fsig.s[(size_t)k * fsig.N + px];
-                                fsig.out[(size_t)k * fsig.N + px] = v + (fgain * sdot - fysub * v);
-                            }
-                        }
+                        if (mask[px]) continue; // (a sample: filter_sample_rows and filter_sample_rows_signals write it from Phi_A)
+                        band_filter_store<1 + NS>(flt, fpix0, px, (int)tval[px], sdot);
                     }
                 }
             }
@@ -744,6 +751,14 @@ struct BandTables {
     const unsigned *rowband_s() const { return blob.p + o_rb_s; }
     const unsigned *win_s() const { return blob.p + o_win_s; }
     const int *dcmax() const { return reinterpret_cast<const int *>(blob.p + o_dcmax); } // geom.dcmax (k_band_vec's support)
+    std::vector<unsigned> h_rowband_px; // host copy of rowband_px (the launchers' window plans)
+    int dc0() const { return geom.dcmax.empty() ? -1 : geom.dcmax[0]; } // the circle's half-width in a sample's own row (-1: none)
+    int cols_near_tile(int t) const // sample columns within dc0 of pixel tile t: what k_band_vec and k_band_sep_cols walk at most
+    {
+        int lo = 0, n = 0;
+        if (dc0() >= 0) band_cols_range(geom.cols.data(), nc, t * tile_px - dc0(), std::min(width, (t + 1) * tile_px) - 1 + dc0(), &lo, &n);
+        return n;
+    }
     std::vector<double> pairs_dr;   // per row distance: (target column, sample column) pairs inside the circle, pixels as targets
     std::vector<double> pairs_dr_s; // ... the samples as targets
     std::vector<int> hrows;
@@ -817,6 +832,7 @@ struct BandTables {
                 h[o_rb_px + r] = rb;
                 maxband = std::max(maxband, (int)(rb >> 16) - (int)(rb & 0xFFFF) + 1);
             }
+            h_rowband_px.assign(h.begin() + o_rb_px, h.begin() + o_win_px);
             for (int dr = 0; dr < rad; ++dr)
                 for (int t = 0; t < ntiles_px; ++t) h[o_win_px + (size_t)dr * ntiles_px + t] = geom.window(t * tile_px, std::min(width, (t + 1) * tile_px) - 1, dr, BAND_HALF_SHIFT);
             pairs_dr.assign(rad, 0.0);
@@ -910,13 +926,11 @@ static int launch_band_px(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_i
         if (flt || cpartial) return set_error(ctx, GLF_ERR_INVALID, "k_band: the colour and 16-bit formats have no filter epilogue");
     if constexpr (NS == 0 && G == PixGen::Grey) // the planes ride in the filter's epilogue: one instantiation per plane count
         if (flt && flt->sig.nsig > 0) {
-            switch (flt->sig.nsig) {
-            case 1: return launch_band_px<MB, 1>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
-            case 2: return launch_band_px<MB, 2>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
-            case 3: return launch_band_px<MB, 3>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
-            case 4: return launch_band_px<MB, 4>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster, cpartial, evaluated, flt, pix0);
-            default: return set_error(ctx, GLF_ERR_INVALID, "k_band: %d signal planes", flt->sig.nsig);
-            }
+            if (flt->sig.nsig >= BANDV_MAXNC) return set_error(ctx, GLF_ERR_INVALID, "k_band: %d signal planes", flt->sig.nsig);
+            return band_dispatch_planes(1 + flt->sig.nsig, [&](auto nc) -> int {
+                return launch_band_px<MB, decltype(nc)::value - 1>(ctx, bt, d_img, row0, nrows, chunks, inv, phi, phi_ld, d_mask, d_idx, p, raster,
+                                                                   cpartial, evaluated, flt, pix0);
+            });
         }
     auto kern = k_band<MB, BAND_PB, BAND_NW, false, NS, G>;
     const unsigned lds = band_lds_bytes(MB, BAND_NW, bt.rad, bt.ksc, false, G == PixGen::Grey);
@@ -960,6 +974,39 @@ static int band_prep(glf_ctx *ctx, const float *X, unsigned x_ld, const float *c
     hipLaunchKernelGGL(kern, dim3((unsigned)ceil_div((int64_t)total, 256)), dim3(256), 0, ctx->stream, X, x_ld, colscale, svals, nr, nc, ksc, mb, chunks);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
+}
+
+// What the launchers of the three forms share. The sample values as bytes [p]:
+static int band_svals(glf_ctx *ctx, const float4 *d_samples, unsigned p, DevBuf<uint8_t> &svals)
+{
+    GLF_TRY(svals.alloc(ctx, p));
+    hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, d_samples, p, svals.p);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+// the kernels' counter of evaluated entries: zeroed on the stream; read back (through the pinned block) with the stream synchronised
+static int band_eval_zero(glf_ctx *ctx, DevBuf<unsigned long long> &dev_eval)
+{
+    GLF_TRY(dev_eval.alloc(ctx, 1));
+    GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), ctx->stream));
+    return GLF_OK;
+}
+static int band_eval_read(glf_ctx *ctx, const DevBuf<unsigned long long> &dev_eval, unsigned long long *h_eval)
+{
+    unsigned long long *pin_eval = ctx_pinned(ctx) ? reinterpret_cast<unsigned long long *>(ctx_pinned(ctx) + PINNED_BANDEVAL) : nullptr;
+    GLF_HIP(ctx, hipMemcpyAsync(pin_eval ? pin_eval : h_eval, dev_eval.p, sizeof(*h_eval), hipMemcpyDeviceToHost, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (pin_eval) *h_eval = *pin_eval;
+    return GLF_OK;
+}
+// the launch as the statistics report it: `launches` launches of ms in all over `cols` columns (Phi's, or one per plane), R expansion terms
+static void band_stats(RowpassStats *stats, const BandTables &bt, int row0, int row1, int launches, float ms, unsigned cols, int R)
+{
+    if (!stats) return;
+    stats->col_launches = launches;
+    stats->col_ms = ms;
+    stats->col_flops = 2.0 * bt.pairs_px(row0, row1) * cols; // algorithmic: the (pixel, sample) pairs inside the radius (memoised), one multiply-add per column
+    stats->rank_R = R;
 }
 
 // (nystroem_band_vec.inc: the fused filter contracted with q = Psi w, one column per plane)
@@ -1011,17 +1058,16 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(inv.alloc(ctx, ld_total));
     GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
     if (raw) GLF_TRY(svals32.alloc(ctx, svals32_planes(gen) * p));
-    else GLF_TRY(svals.alloc(ctx, p));
     GLF_TRY(chunks.alloc(ctx, (size_t)bt.nr * bt.ksc * band_chunk_bytes(mb)));
-    GLF_TRY(dev_eval.alloc(ctx, 1));
     const size_t wgs = band_px_wgs(bt, nrows);
     if (flt) d_c = nullptr; // (c was needed before this launch: c_from_ysum)
     if (d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
-    GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), st));
+    GLF_TRY(band_eval_zero(ctx, dev_eval));
     band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);
-    if (raw) hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals32_what(gen), svals32.p);
-    else hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
-    GLF_LAUNCH_CHECK(ctx);
+    if (raw) {
+        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals32_what(gen), svals32.p);
+        GLF_LAUNCH_CHECK(ctx);
+    } else GLF_TRY(band_svals(ctx, d_samples, p, svals));
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     float band_ms = 0.f;
     for (unsigned cb = 0; cb < nblocks; ++cb) {
@@ -1059,19 +1105,11 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     }
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     unsigned long long h_eval = 0;
-    unsigned long long *pin_eval = ctx_pinned(ctx) ? reinterpret_cast<unsigned long long *>(ctx_pinned(ctx) + PINNED_BANDEVAL) : nullptr;
-    GLF_HIP(ctx, hipMemcpyAsync(pin_eval ? pin_eval : &h_eval, dev_eval.p, sizeof(h_eval), hipMemcpyDeviceToHost, st));
-    GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (pin_eval) h_eval = *pin_eval;
+    GLF_TRY(band_eval_read(ctx, dev_eval, &h_eval));
     if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
     // (every column block evaluates the same entries: per block, h_eval / nblocks)
     if (entries_evaluated) *entries_evaluated = (uint64_t)(h_eval / std::max(1u, nblocks));
     if (mfma_flops) *mfma_flops = 6.0 * (double)h_eval * LD; // three split products per entry and column
-    if (stats) {
-        stats->col_launches = (int)nblocks;
-        stats->col_ms = band_ms;
-        stats->col_flops = 2.0 * bt.pairs_px(row0, row1) * ld_total; // algorithmic: the (pixel, sample) pairs inside the radius (memoised)
-        stats->rank_R = 0;
-    }
+    band_stats(stats, bt, row0, row1, (int)nblocks, band_ms, ld_total, 0);
     return GLF_OK;
 }

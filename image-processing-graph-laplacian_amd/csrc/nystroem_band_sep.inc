@@ -7,7 +7,7 @@
 //   G[a][b][k] = f_k(v_ab) q_ab                         k_band_sep_g     p R values per plane
 //   S[r][b][k] = sum_a Er15(|r - R_a|) G[a][b][k]       k_band_sep_rows  one fmaf chain per element, a ascending
 //   U_k[px]    = sum_b Ec(|c - C_b|) S[r][b][k]         k_band_sep_cols  one gather of Ec + R FMAs per (pixel, sample column)
-//   s[px]      = sum_k f_k(v_px) U_k[px]                                 folded in f64, then k_band_vec's filter epilogue
+//   s[px]      = sum_k f_k(v_px) U_k[px]                                 folded in f64, then band_filter_store
 // In the column pass a wave is 64 pixels of one image row, so S[r][b][.] is wave-uniform: it is fetched by scalar loads and enters the
 // FMAs as their scalar operand. No gather of P, no support test, no select: the support is the square |dr|, |dc| < rad (Er15 and
 // Ec are exact zeros from rad on) instead of k_band_vec's circle -- the corners add terms below 2^-40 of the largest one.
@@ -20,8 +20,7 @@ constexpr size_t BSEP_S_BYTES = 256u << 20; // S of one chunk of image rows: the
 static_assert(BSEP_RB == BAND_NW, "a block of the row pass is the rows of one workgroup of the column pass");
 static_assert(BSEP_ATILE >= BAND_MAXROWS, "without BAND_NOSKIP one tile holds the band of a block of rows");
 
-// q as k_band_q (f64, rounded once; a zero weight skips its column, so the padded columns of Psi never enter), then
-// G[k][s][t] = ftab[t][v_s] q_k[s]. One thread per sample.
+// q_k[s] = (float)(Psi[s] . w_k) as k_band_q has it (band_q_row), then G[k][s][t] = ftab[t][v_s] q_k[s]. One thread per sample.
 template <int NC>
 __global__ __launch_bounds__(256) void k_band_sep_g(const float *__restrict__ psi, unsigned p, unsigned ld, const float *__restrict__ w,
                                                     const float *__restrict__ sig_w, const uint8_t *__restrict__ svals,
@@ -30,20 +29,7 @@ __global__ __launch_bounds__(256) void k_band_sep_g(const float *__restrict__ ps
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
     if (s >= p) return;
     double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    const float4 *row = reinterpret_cast<const float4 *>(psi + (size_t)s * ld);
-    for (unsigned n = 0; n < ld; n += 4) {
-        const float4 x4 = row[n / 4];
-        const float x[4] = {x4.x, x4.y, x4.z, x4.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int k = 0; k < NC; ++k) {
-                const float wv = k == 0 ? w[n + u] : sig_w[(size_t)(k - 1) * ld + n + u];
-                if (wv != 0.f) acc[k] = fma((double)x[u], (double)wv, acc[k]);
-            }
-    }
+    band_q_row<NC>(psi + (size_t)s * ld, ld, w, sig_w, acc);
     const int v = (int)svals[s];
     for (int t = 0; t < R; t += 4) {
         const float f0 = ftab[(t + 0) * 256 + v], f1 = ftab[(t + 1) * 256 + v], f2 = ftab[(t + 2) * 256 + v], f3 = ftab[(t + 3) * 256 + v];
@@ -65,14 +51,8 @@ __global__ __launch_bounds__(256) void k_band_sep_rows(const float *__restrict__
 {
     __shared__ __attribute__((aligned(16))) float er_l[BSEP_ATILE][BSEP_RB];
     const int r0 = row_begin + blockIdx.y * BSEP_RB, nrb = min(BSEP_RB, row_end - r0);
-    int alo = 0xFFFF, ahi = -1;
-    for (int j = 0; j < nrb; ++j) {
-        const unsigned rb = rowband[r0 + j];
-        if ((rb & 0xFFFFu) <= (rb >> 16)) {
-            alo = min(alo, (int)(rb & 0xFFFFu));
-            ahi = max(ahi, (int)(rb >> 16));
-        }
-    }
+    int alo, ahi;
+    band_rows_hull(rowband, r0, nrb, &alo, &ahi);
     if (noskip) {
         alo = 0;
         ahi = nr - 1;
@@ -118,9 +98,7 @@ template <int NC, int KB>
 __global__ __launch_bounds__(BAND_NW * 64) void k_band_sep_cols(const uint8_t *__restrict__ img, int width, int row_begin, int row_end, int srow0,
                                                                 const int *__restrict__ gcol, int nc, const float *__restrict__ btab, int rad,
                                                                 int dc0, const float *__restrict__ S, int R, const float *__restrict__ ftab,
-                                                                const uint8_t *__restrict__ mask, float fgain, float fysub,
-                                                                uint8_t *__restrict__ fout, float *__restrict__ fzf, float *__restrict__ fcorr,
-                                                                int64_t fpix0, BandSignals fsig, int noskip)
+                                                                const uint8_t *__restrict__ mask, BandFilter flt, int64_t fpix0, int noskip)
 {
     constexpr int NW = BAND_NW;
     extern __shared__ __attribute__((aligned(16))) unsigned char bsdyn[];
@@ -133,22 +111,7 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_sep_cols(const uint8_t *_
     for (int i = tid; i <= rad; i += NW * 64) elut[i] = btab[256 + i];
     // the tile's range of sample columns: within dc0 of it
     int Clo = 0, W = 0;
-    if (dc0 >= 0) {
-        int lo = 0, hi = nc; // first column >= tc0 - dc0
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (gcol[mid] < tc0 - dc0) lo = mid + 1;
-            else hi = mid;
-        }
-        Clo = lo;
-        hi = nc; // first column > tc1 + dc0
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (gcol[mid] <= tc1 + dc0) lo = mid + 1;
-            else hi = mid;
-        }
-        W = lo - Clo;
-    }
+    if (dc0 >= 0) band_cols_range(gcol, nc, tc0 - dc0, tc1 + dc0, &Clo, &W);
     __syncthreads();
     if (wave >= ntw && !noskip) return;
     const int trow = min(trow0 + wave, row_end - 1), tcol = min(tc0 + lane, width - 1);
@@ -175,26 +138,14 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_sep_cols(const uint8_t *_
         }
     }
 
-    // k_band_vec's filter epilogue
+    // the filter, one lane per pixel (the sample pixels are filter_sample_rows' from Phi_A)
     if (wave >= ntw || tc0 + lane >= width) return;
     const int64_t px = (int64_t)trow * width + tcol;
     if (mask[px]) return;
-    constexpr double UNSCALE = 1.0 / 32768.0; // (Er15 carries k_band's 2^15)
-    static_assert(NYS_F16_KSCALE_LOG2 == 15.0f, "UNSCALE takes the scale of the Er15 table out again");
-    {
-        const float sdot = (float)(tot[0] * UNSCALE);
-        const int y = pv;
-        const float cc = fgain * sdot - fysub * (float)y;
-        if (fzf) fzf[px] = (float)y + cc;
-        if (fcorr) fcorr[px - fpix0] = cc;
-        fout[px] = filter_output_u8(y, cc);
-    }
+    float sdot[NC];
 #pragma unroll
-    for (int k = 1; k < NC; ++k) {
-        const float sdot = (float)(tot[k] * UNSCALE);
-        const float v = fsig.s[(size_t)(k - 1) * fsig.N + px];
-        fsig.out[(size_t)(k - 1) * fsig.N + px] = v + (fgain * sdot - fysub * v);
-    }
+    for (int k = 0; k < NC; ++k) sdot[k] = (float)(tot[k] * BAND_UNSCALE);
+    band_filter_store<NC>(flt, fpix0, px, pv, sdot);
 }
 
 template <int NC, int KB>
@@ -205,37 +156,14 @@ static int band_sep_cols_launch(glf_ctx *ctx, const BandTables &bt, const uint8_
     if (lds > 48u * 1024u) GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW * 64), lds, ctx->stream, d_img, bt.width, row0, row0 + nrows, srow0, bt.gcol(), bt.nc, bt.tab(), bt.rad,
-                       bt.geom.dcmax.empty() ? -1 : bt.geom.dcmax[0], S, R, ftab, d_mask, flt.gain, flt.ysub, flt.out, flt.zf, flt.corr, pix0, flt.sig,
-                       ctx->tune.band_noskip ? 1 : 0);
+                       bt.dc0(), S, R, ftab, d_mask, flt, pix0, ctx->tune.band_noskip ? 1 : 0);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
 
-// G, then per chunk of image rows the row pass and the column pass
-template <int NC>
-static int band_sep_launch(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int row0, int nrows, int chunk, const uint8_t *svals,
-                           const float *d_psi, unsigned p, unsigned ld, int R, const float *ftab, float *G, float *S, unsigned lds,
-                           const uint8_t *d_mask, const BandFilter &flt, int64_t pix0, hipEvent_t e0, hipEvent_t e1)
-{
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_band_sep_g<NC>, dim3((p + 255) / 256), dim3(256), 0, st, d_psi, p, ld, flt.w, flt.sig.w, svals, ftab, R, G);
-    GLF_LAUNCH_CHECK(ctx);
-    const unsigned ncR = (unsigned)bt.nc * (unsigned)R, E = ncR * NC;
-    GLF_HIP(ctx, hipEventRecord(e0, st));
-    for (int c0 = 0; c0 < nrows; c0 += chunk) {
-        const int r0 = row0 + c0, n = std::min(chunk, nrows - c0);
-        hipLaunchKernelGGL(k_band_sep_rows, dim3((E + 255) / 256, (unsigned)ceil_div(n, BSEP_RB)), dim3(256), 0, st, G, E, ncR, bt.nr, r0, r0 + n, r0,
-                           bt.grow(), bt.tab(), bt.rad, bt.rowband_px(), ctx->tune.band_noskip ? 1 : 0, S);
-        GLF_LAUNCH_CHECK(ctx);
-        if (R % 32 == 0) GLF_TRY((band_sep_cols_launch<NC, 32>(ctx, bt, d_img, r0, n, r0, S, R, ftab, lds, d_mask, flt, pix0)));
-        else GLF_TRY((band_sep_cols_launch<NC, 16>(ctx, bt, d_img, r0, n, r0, S, R, ftab, lds, d_mask, flt, pix0)));
-    }
-    GLF_HIP(ctx, hipEventRecord(e1, st));
-    return GLF_OK;
-}
-
-// The fused filter of the image rows [pix0 / width, pix1 / width) in separable rank-R form. GLF_ERR_UNSUPPORTED: the photometric
-// table has no expansion of at most RANK_MAX_R terms (R = 0: sharp kernels), or more planes than instantiated -- k_band_vec runs then.
+// The fused filter of the image rows [pix0 / width, pix1 / width) in separable rank-R form: G, then per chunk of image rows the row
+// pass and the column pass. GLF_ERR_UNSUPPORTED: the photometric table has no expansion of at most RANK_MAX_R terms (R = 0: sharp
+// kernels), or more planes than instantiated -- k_band_vec runs then.
 static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
                                     const float4 *d_samples, const uint8_t *d_mask, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
                                     const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats)
@@ -255,54 +183,50 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     int chunk = (int)std::min<size_t>((size_t)round_up(nrows, BAND_NW), std::max<size_t>(BAND_NW, BSEP_S_BYTES / row_bytes / BAND_NW * BAND_NW));
     DevBuf<uint8_t> svals;
     DevBuf<float> G, S;
-    GLF_TRY(svals.alloc(ctx, p));
     GLF_TRY(G.alloc(ctx, (size_t)ncol * p * R));
     while (S.alloc(ctx, (size_t)chunk * bt.nc * R * ncol) != GLF_OK) {
         if (chunk <= BAND_NW) return GLF_ERR_NOMEM;
         chunk = (int)round_up(chunk / 2, BAND_NW);
     }
+    GLF_TRY(band_svals(ctx, d_samples, p, svals));
     hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
-    GLF_LAUNCH_CHECK(ctx);
     hipEvent_t e0 = ctx->ev[6], e1 = ctx->ev[7];
-#define GLF_BAND_SEP(NC_) band_sep_launch<NC_>(ctx, bt, d_img, row0, nrows, chunk, svals.p, d_psi, p, ld, R, ftab, G.p, S.p, lds, d_mask, flt, pix0, e0, e1)
-    switch (ncol) {
-    case 1: GLF_TRY(GLF_BAND_SEP(1)); break;
-    case 2: GLF_TRY(GLF_BAND_SEP(2)); break;
-    case 3: GLF_TRY(GLF_BAND_SEP(3)); break;
-    case 4: GLF_TRY(GLF_BAND_SEP(4)); break;
-    default: GLF_TRY(GLF_BAND_SEP(5)); break;
-    }
-#undef GLF_BAND_SEP
-    static_assert(BANDV_MAXNC == 5, "one instantiation per column count");
+    const bool noskip = ctx->tune.band_noskip;
+    GLF_TRY(band_dispatch_planes(ncol, [&](auto nc_) -> int {
+        constexpr int NC = decltype(nc_)::value;
+        hipLaunchKernelGGL(k_band_sep_g<NC>, dim3((p + 255) / 256), dim3(256), 0, st, d_psi, p, ld, flt.w, flt.sig.w, svals.p, ftab, R, G.p);
+        GLF_LAUNCH_CHECK(ctx);
+        const unsigned ncR = (unsigned)bt.nc * (unsigned)R, E = ncR * NC;
+        GLF_HIP(ctx, hipEventRecord(e0, st));
+        for (int c0 = 0; c0 < nrows; c0 += chunk) {
+            const int r0 = row0 + c0, n = std::min(chunk, nrows - c0);
+            hipLaunchKernelGGL(k_band_sep_rows, dim3((E + 255) / 256, (unsigned)ceil_div(n, BSEP_RB)), dim3(256), 0, st, G.p, E, ncR, bt.nr, r0, r0 + n, r0,
+                               bt.grow(), bt.tab(), bt.rad, bt.rowband_px(), noskip ? 1 : 0, S.p);
+            GLF_LAUNCH_CHECK(ctx);
+            if (R % 32 == 0) GLF_TRY((band_sep_cols_launch<NC, 32>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, lds, d_mask, flt, pix0)));
+            else GLF_TRY((band_sep_cols_launch<NC, 16>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, lds, d_mask, flt, pix0)));
+        }
+        GLF_HIP(ctx, hipEventRecord(e1, st));
+        return GLF_OK;
+    }));
     GLF_HIP(ctx, hipStreamSynchronize(st));
     float ms = 0.f;
     GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (kernel_ms) *kernel_ms = ms;
     if (entries_evaluated) {
         // lane-entries covered by the windows, from the plan: 64 x sum over the walking waves of (columns walked x band rows feeding them)
-        const bool noskip = ctx->tune.band_noskip;
         uint64_t cols = 0, rows = 0;
-        const int d0 = bt.geom.dcmax.empty() ? -1 : bt.geom.dcmax[0];
-        const std::vector<int> &gc = bt.geom.cols;
-        for (int t = 0; t < bt.ntiles_px && d0 >= 0; ++t) {
-            const int c0 = t * bt.tile_px, c1 = std::min(bt.width, c0 + bt.tile_px) - 1;
-            cols += (uint64_t)(std::upper_bound(gc.begin(), gc.end(), c1 + d0) - std::lower_bound(gc.begin(), gc.end(), c0 - d0));
-        }
+        for (int t = 0; t < bt.ntiles_px; ++t) cols += (uint64_t)bt.cols_near_tile(t);
         if (noskip) rows = (uint64_t)ceil_div(nrows, BAND_NW) * BAND_NW * (uint64_t)bt.nr; // every wave, every band row
         else
             for (int r = row0; r < row1; ++r) {
-                const unsigned rb = bt.band_of(r);
-                if ((rb & 0xFFFFu) <= (rb >> 16)) rows += (rb >> 16) - (rb & 0xFFFFu) + 1;
+                int alo, ahi;
+                band_rows_hull(bt.h_rowband_px.data(), r, 1, &alo, &ahi);
+                rows += (uint64_t)std::max(0, ahi - alo + 1);
             }
         *entries_evaluated = 64ull * cols * rows;
     }
     if (mfma_flops) *mfma_flops = 0.0;
-    if (stats) {
-        stats->col_launches = 1;
-        stats->col_ms = ms;
-        stats->col_flops = 2.0 * bt.pairs_px(row0, row1) * ncol; // algorithmic: the pairs inside the radius, one multiply-add per column
-        stats->rank_R = R;
-    }
+    band_stats(stats, bt, row0, row1, 1, ms, (unsigned)ncol, R);
     return GLF_OK;
 }

@@ -23,7 +23,6 @@ constexpr int BANDV_CHUNK = 16, BANDV_GROUP = 8;          // band rows per set o
 static_assert(BANDV_GROUP % 4 == 0 && BANDV_CHUNK % BANDV_GROUP == 0, "a group's samples are read 16 bytes at a time");
 static_assert(32 * BAND_PB == 64, "k_band_vec: one lane per pixel of a 64-column tile (BandTables' tile_px)");
 constexpr unsigned BANDV_LDS_MAX = 64u * 1024u;           // what a workgroup may take
-constexpr int BANDV_MAXNC = 1 + GLF_MAX_SIGNALS;
 
 // [wcap][nbcap] samples of 1 + nc dwords | Ec[rad + 1] | columns[wcap] | Er15[NW][nbcap] | dcmax[NW][nbcap] | rows per column [NW][wcap] | misc
 __host__ __device__ inline unsigned band_vec_lds_bytes(int ncol, int rad, int wcap, int nbcap)
@@ -32,31 +31,40 @@ __host__ __device__ inline unsigned band_vec_lds_bytes(int ncol, int rad, int wc
                                        2u * BAND_NW * (unsigned)nbcap + BAND_NW * (unsigned)wcap + 4u);
 }
 
-// q[k][s] = sum_n Psi[s][n] w_k[n] (f64, rounded once), [NC][p32] zero-padded. w_0 = w, w_k = sig_w[k - 1]; a zero weight skips
-// its column, so the padded columns of Psi never enter.
+// out[k] = sum_n row[n] w_k[n] over one sample's row of Psi, in f64 (the callers round once). w_0 = w, w_k = sig_w[k - 1]; a zero
+// weight skips its column, so the padded columns of Psi never enter. (Summed in locals and copied out: accumulating through the
+// reference costs both callers 4 - 8 VGPRs, and their NC = 5 a wave per SIMD.)
+template <int NC>
+__device__ __forceinline__ void band_q_row(const float *psi_row, unsigned ld, const float *w, const float *sig_w, double (&out)[NC])
+{
+    double acc[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
+    const float4 *row = reinterpret_cast<const float4 *>(psi_row);
+    for (unsigned n = 0; n < ld; n += 4) {
+        const float4 x4 = row[n / 4];
+        const float x[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int k = 0; k < NC; ++k) {
+                const float wv = k == 0 ? w[n + u] : sig_w[(size_t)(k - 1) * ld + n + u];
+                if (wv != 0.f) acc[k] = fma((double)x[u], (double)wv, acc[k]);
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < NC; ++k) out[k] = acc[k];
+}
+
+// q[k][s] = (float)(Psi[s] . w_k), [NC][p32] zero-padded
 template <int NC>
 __global__ __launch_bounds__(256) void k_band_q(const float *__restrict__ psi, unsigned p, unsigned p32, unsigned ld, const float *__restrict__ w,
                                                 const float *__restrict__ sig_w, float *__restrict__ q)
 {
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
     if (s >= p32) return;
-    double acc[NC];
-#pragma unroll
-    for (int k = 0; k < NC; ++k) acc[k] = 0.0;
-    if (s < p) {
-        const float4 *row = reinterpret_cast<const float4 *>(psi + (size_t)s * ld);
-        for (unsigned n = 0; n < ld; n += 4) {
-            const float4 x4 = row[n / 4];
-            const float x[4] = {x4.x, x4.y, x4.z, x4.w};
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int k = 0; k < NC; ++k) {
-                    const float wv = k == 0 ? w[n + u] : sig_w[(size_t)(k - 1) * ld + n + u];
-                    if (wv != 0.f) acc[k] = fma((double)x[u], (double)wv, acc[k]);
-                }
-        }
-    }
+    double acc[NC] = {};
+    if (s < p) band_q_row<NC>(psi + (size_t)s * ld, ld, w, sig_w, acc);
 #pragma unroll
     for (int k = 0; k < NC; ++k) q[(size_t)k * p32 + s] = (float)acc[k];
 }
@@ -70,9 +78,8 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_vec(const uint8_t *__rest
                                                            const float *__restrict__ btab, const float *__restrict__ pexp, int rad,
                                                            const unsigned *__restrict__ rowband, const int *__restrict__ dcmax,
                                                            const uint8_t *__restrict__ svals, const float *__restrict__ q, unsigned q_ld, int wcap,
-                                                           int nbcap, const uint8_t *__restrict__ mask, float fgain, float fysub,
-                                                           uint8_t *__restrict__ fout, float *__restrict__ fzf, float *__restrict__ fcorr,
-                                                           int64_t fpix0, BandSignals fsig, int noskip, unsigned long long *__restrict__ evaluated)
+                                                           int nbcap, const uint8_t *__restrict__ mask, BandFilter flt, int64_t fpix0, int noskip,
+                                                           unsigned long long *__restrict__ evaluated)
 {
     constexpr int NW = BAND_NW, EW = 1 + NC;
     constexpr unsigned PLUT_BYTES = 256 * BAND_PSTRIDE;
@@ -88,14 +95,8 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_vec(const uint8_t *__rest
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int trow0 = row_begin + blockIdx.y * NW, ntw = min(NW, row_end - trow0);
     const int tc0 = blockIdx.x * 64, tc1 = min(width, tc0 + 64) - 1;
-    int alo = 0xFFFF, ahi = -1;
-    for (int w = 0; w < ntw; ++w) {
-        const unsigned rb = rowband[trow0 + w];
-        if ((rb & 0xFFFFu) <= (rb >> 16)) {
-            alo = min(alo, (int)(rb & 0xFFFFu));
-            ahi = max(ahi, (int)(rb >> 16));
-        }
-    }
+    int alo, ahi;
+    band_rows_hull(rowband, trow0, ntw, &alo, &ahi);
     const int nb = min(nbcap, max(0, ahi - alo + 1)), nbp = (nb + BANDV_GROUP - 1) / BANDV_GROUP * BANDV_GROUP; // (nbcap is a multiple of the group)
     { // (the replicated table as it sits in the tables blob, 1 KiB per instruction)
         constexpr int PIECES = 256 * BAND_PCOPY * 4 / 1024;
@@ -123,20 +124,8 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_vec(const uint8_t *__rest
     const int dmx = __builtin_amdgcn_readfirstlane(misc[0]);
     int Clo = 0, W = 0;
     if (dmx >= 0) {
-        int lo = 0, hi = nc; // first column >= tc0 - dmx
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (gcol[mid] < tc0 - dmx) lo = mid + 1;
-            else hi = mid;
-        }
-        Clo = lo;
-        hi = nc; // first column > tc1 + dmx
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (gcol[mid] <= tc1 + dmx) lo = mid + 1;
-            else hi = mid;
-        }
-        W = min(wcap, lo - Clo);
+        band_cols_range(gcol, nc, tc0 - dmx, tc1 + dmx, &Clo, &W);
+        W = min(wcap, W);
     }
     // the samples, once: column-major so that the band rows of a column are contiguous; rows nb .. nbp - 1 are zeros
     for (int e = tid; e < W * nbp; e += NW * 64) {
@@ -228,26 +217,14 @@ __global__ __launch_bounds__(BAND_NW * 64) void k_band_vec(const uint8_t *__rest
     }
     if (evaluated && lane == 0 && nsteps) atomicAdd(evaluated, nsteps * 64ull);
 
-    // k_band's filter epilogue, one lane per pixel (the sample pixels are filter_sample_rows' from Phi_A)
+    // the filter, one lane per pixel (the sample pixels are filter_sample_rows' from Phi_A)
     if (wave >= ntw || tc0 + lane >= width) return;
     const int64_t px = (int64_t)trow * width + tcol;
     if (mask[px]) return;
-    constexpr double UNSCALE = 1.0 / 32768.0; // (Er15 carries k_band's 2^15)
-    static_assert(NYS_F16_KSCALE_LOG2 == 15.0f, "UNSCALE takes the scale of the Er15 table out again");
-    {
-        const float sdot = (float)(tot[0] * UNSCALE);
-        const int y = (int)img[px];
-        const float cc = fgain * sdot - fysub * (float)y;
-        if (fzf) fzf[px] = (float)y + cc;
-        if (fcorr) fcorr[px - fpix0] = cc;
-        fout[px] = filter_output_u8(y, cc);
-    }
+    float sdot[NC];
 #pragma unroll
-    for (int k = 1; k < NC; ++k) {
-        const float sdot = (float)(tot[k] * UNSCALE);
-        const float v = fsig.s[(size_t)(k - 1) * fsig.N + px];
-        fsig.out[(size_t)(k - 1) * fsig.N + px] = v + (fgain * sdot - fysub * v);
-    }
+    for (int k = 0; k < NC; ++k) sdot[k] = (float)(tot[k] * BAND_UNSCALE);
+    band_filter_store<NC>(flt, fpix0, px, (int)img[px], sdot);
 }
 
 // the LDS window of a launch over the image rows [row0, row1): the most band rows of a workgroup (rounded up to the group) and the
@@ -256,42 +233,13 @@ static void band_vec_caps(const BandTables &bt, int row0, int row1, int *wcap, i
 {
     int nbmax = 0, wmax = 0;
     for (int r = row0; r < row1; r += BAND_NW) {
-        int alo = 0xFFFF, ahi = -1;
-        for (int w = 0; w < std::min(BAND_NW, row1 - r); ++w) {
-            const unsigned rb = bt.band_of(r + w);
-            if ((rb & 0xFFFFu) <= (rb >> 16)) {
-                alo = std::min(alo, (int)(rb & 0xFFFFu));
-                ahi = std::max(ahi, (int)(rb >> 16));
-            }
-        }
+        int alo, ahi;
+        band_rows_hull(bt.h_rowband_px.data(), r, std::min(BAND_NW, row1 - r), &alo, &ahi);
         nbmax = std::max(nbmax, ahi - alo + 1);
     }
-    const int d0 = bt.geom.dcmax.empty() ? -1 : bt.geom.dcmax[0];
-    const std::vector<int> &cols = bt.geom.cols;
-    for (int t = 0; t < bt.ntiles_px && d0 >= 0; ++t) {
-        const int c0 = t * bt.tile_px, c1 = std::min(bt.width, c0 + bt.tile_px) - 1;
-        const int lo = (int)(std::lower_bound(cols.begin(), cols.end(), c0 - d0) - cols.begin());
-        const int hi = (int)(std::upper_bound(cols.begin(), cols.end(), c1 + d0) - cols.begin());
-        wmax = std::max(wmax, hi - lo);
-    }
+    for (int t = 0; t < bt.ntiles_px; ++t) wmax = std::max(wmax, bt.cols_near_tile(t));
     *wcap = std::max(1, wmax);
     *nbcap = std::max(BANDV_GROUP, (std::min(nbmax, BAND_MAXROWS) + BANDV_GROUP - 1) / BANDV_GROUP * BANDV_GROUP);
-}
-
-template <int NC>
-static void band_vec_launch(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int row0, int nrows, const uint8_t *svals, const float *d_psi,
-                            unsigned p, unsigned p32, unsigned ld, float *q, int wcap, int nbcap, unsigned lds, const uint8_t *d_mask,
-                            const BandFilter &flt, int64_t pix0, unsigned long long *evaluated, hipEvent_t e0, hipEvent_t e1)
-{
-    hipStream_t st = ctx->stream;
-    hipLaunchKernelGGL(k_band_q<NC>, dim3((p32 + 255) / 256), dim3(256), 0, st, d_psi, p, p32, ld, flt.w, flt.sig.w, q);
-    auto kern = k_band_vec<NC>;
-    const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
-    if (e0) (void)hipEventRecord(e0, st);
-    hipLaunchKernelGGL(kern, grid, dim3(BAND_NW * 64), lds, st, d_img, bt.width, row0, row0 + nrows, bt.grow(), bt.gcol(), bt.nc, bt.tab(), bt.pexp(),
-                       bt.rad, bt.rowband_px(), bt.dcmax(), svals, q, p32, wcap, nbcap, d_mask, flt.gain, flt.ysub, flt.out, flt.zf, flt.corr, pix0,
-                       flt.sig, ctx->tune.band_noskip ? 1 : 0, evaluated);
-    if (e1) (void)hipEventRecord(e1, st);
 }
 
 // The fused filter of the image rows [pix0 / width, pix1 / width) through k_band_vec: the sample values, q = Psi w (and the planes'),
@@ -312,39 +260,28 @@ static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const ui
     DevBuf<uint8_t> svals;
     DevBuf<float> q;
     DevBuf<unsigned long long> dev_eval;
-    GLF_TRY(svals.alloc(ctx, p));
     GLF_TRY(q.alloc(ctx, (size_t)ncol * p32));
-    GLF_TRY(dev_eval.alloc(ctx, 1));
-    GLF_HIP(ctx, hipMemsetAsync(dev_eval.p, 0, sizeof(unsigned long long), st));
-    hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals.p);
-    GLF_LAUNCH_CHECK(ctx);
+    GLF_TRY(band_eval_zero(ctx, dev_eval));
+    GLF_TRY(band_svals(ctx, d_samples, p, svals));
     hipEvent_t e0 = ctx->ev[6], e1 = ctx->ev[7];
-#define GLF_BAND_VEC(NC_) band_vec_launch<NC_>(ctx, bt, d_img, row0, nrows, svals.p, d_psi, p, p32, ld, q.p, wcap, nbcap, lds, d_mask, flt, pix0, dev_eval.p, e0, e1)
-    switch (ncol) {
-    case 1: GLF_BAND_VEC(1); break;
-    case 2: GLF_BAND_VEC(2); break;
-    case 3: GLF_BAND_VEC(3); break;
-    case 4: GLF_BAND_VEC(4); break;
-    default: GLF_BAND_VEC(5); break;
-    }
-#undef GLF_BAND_VEC
-    static_assert(BANDV_MAXNC == 5, "one instantiation per column count");
+    GLF_TRY(band_dispatch_planes(ncol, [&](auto nc_) -> int {
+        constexpr int NC = decltype(nc_)::value;
+        hipLaunchKernelGGL(k_band_q<NC>, dim3((p32 + 255) / 256), dim3(256), 0, st, d_psi, p, p32, ld, flt.w, flt.sig.w, q.p);
+        const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
+        (void)hipEventRecord(e0, st);
+        hipLaunchKernelGGL(k_band_vec<NC>, grid, dim3(BAND_NW * 64), lds, st, d_img, bt.width, row0, row1, bt.grow(), bt.gcol(), bt.nc, bt.tab(), bt.pexp(),
+                           bt.rad, bt.rowband_px(), bt.dcmax(), svals.p, q.p, p32, wcap, nbcap, d_mask, flt, pix0, ctx->tune.band_noskip ? 1 : 0, dev_eval.p);
+        (void)hipEventRecord(e1, st);
+        return GLF_OK;
+    }));
     GLF_LAUNCH_CHECK(ctx);
     unsigned long long h_eval = 0;
-    unsigned long long *pin_eval = ctx_pinned(ctx) ? reinterpret_cast<unsigned long long *>(ctx_pinned(ctx) + PINNED_BANDEVAL) : nullptr;
-    GLF_HIP(ctx, hipMemcpyAsync(pin_eval ? pin_eval : &h_eval, dev_eval.p, sizeof(h_eval), hipMemcpyDeviceToHost, st));
-    GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (pin_eval) h_eval = *pin_eval;
+    GLF_TRY(band_eval_read(ctx, dev_eval, &h_eval));
     float ms = 0.f;
     GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (kernel_ms) *kernel_ms = ms;
     if (entries_evaluated) *entries_evaluated = (uint64_t)h_eval; // wave-level entry steps x 64 lanes
     if (mfma_flops) *mfma_flops = 0.0;
-    if (stats) {
-        stats->col_launches = 1;
-        stats->col_ms = ms;
-        stats->col_flops = 2.0 * bt.pairs_px(row0, row1) * ncol; // algorithmic: the pairs inside the radius, one multiply-add per column
-        stats->rank_R = 0;
-    }
+    band_stats(stats, bt, row0, row1, 1, ms, (unsigned)ncol, 0);
     return GLF_OK;
 }

@@ -49,6 +49,7 @@ def _assert_rule(what, got, want, z):
 def _assert_stats(info):
     assert info["filter_fused"] == 1 and info["nystroem_path"] == 4
     assert info["nystroem_mfma_flops"] == 0 and info["nystroem_evaluated"] > 0
+    assert info["rank_terms"] == 0, info["rank_terms"]   # k_band_vec ran, not the separable form (the default)
 
 
 def _oracle_phi(img, ns, opt, cinfo):
@@ -159,26 +160,41 @@ def test_planes(nsig):
     assert d.max() <= 1 and (d > 0).mean() <= 1e-4
 
 
-def test_noskip_is_bit_identical():
-    """BAND_NOSKIP: every wave walks every sample of its workgroup's range; the per-lane support still applies, so not a bit moves."""
+def _noskip_pair(form):
+    """CLIPPED at m = 20 (a last workgroup whose waves have no row) under FILTER_FORM=form with BAND_NOSKIP unset and set: out and zf
+    bit for bit the same, and more entries evaluated without the skips. Returns the two runs' infos."""
     img, ns = _image(**CLIPPED)
     opt = glf.default_options(num_samples=ns, num_eigvals=20, epsilon=0.1)
     res = {}
     with glf.Context(0) as ctx:
         d_img = ctx.to_device(img)
         for noskip in (0, 1):
-            ctx.set_tuning(BAND_NOSKIP="1" if noskip else None, **BAND)
+            ctx.set_tuning(FILTER_FORM=form, BAND_NOSKIP="1" if noskip else None, **BAND)
             out, zf, info = ctx.image_processing(d_img, opt, want_float=True)
             res[noskip] = (out.clone(), zf.clone(), info)
     (o0, z0, i0), (o1, z1, i1) = res[0], res[1]
-    _assert_stats(i0)
-    _assert_stats(i1)
     print("nystroem_evaluated: %.4e with the skips, %.4e without" % (i0["nystroem_evaluated"], i1["nystroem_evaluated"]))
     assert torch.equal(z0.view(torch.int32), z1.view(torch.int32))      # bit for bit
     assert torch.equal(o0, o1)
     np.testing.assert_array_equal(i0["eigvals"], i1["eigvals"])
     assert i0["alpha"] == i1["alpha"]
     assert i1["nystroem_evaluated"] > i0["nystroem_evaluated"]
+    return i0, i1
+
+
+def test_noskip_is_bit_identical():
+    """BAND_NOSKIP: every wave walks every sample of its workgroup's range; the per-lane support still applies, so not a bit moves."""
+    for info in _noskip_pair("vec"):
+        _assert_stats(info)
+
+
+def test_phi_noskip_is_bit_identical():
+    """k_band's epilogue (FILTER_FORM=phi) under BAND_NOSKIP: every wave executes every unit of the workgroup's range. On this shape
+    the radius exceeds the image, so no wave with an image row skips anything: what grows the count are the three waves of the last
+    workgroup that have no row, which walk with Er15 = 0 and must store nothing (10 665 984 -> 11 010 048 entries)."""
+    for info in _noskip_pair("phi"):
+        assert info["filter_fused"] == 1 and info["nystroem_path"] == 4 and info["rank_terms"] == 0
+        assert info["nystroem_mfma_flops"] > 0 and info["nystroem_evaluated"] > 0
 
 
 def test_three_ranks_uneven_rows(monkeypatch):
@@ -186,6 +202,7 @@ def test_three_ranks_uneven_rows(monkeypatch):
     monkeypatch.setenv("GLF_NYS_PATH", "band")
     monkeypatch.setenv("GLF_DEG_PATH", "grid")
     monkeypatch.setenv("GLF_MV_PATH", "band")
+    monkeypatch.setenv("GLF_FILTER_FORM", "vec")
     img, ns = _image(**CLIPPED)
     opt = glf.default_options(num_samples=ns, num_eigvals=20, epsilon=0.1)
     with glf.Context(0) as ctx:
