@@ -113,6 +113,7 @@ struct glf_graph {
     int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
     int cluster_blocks_per_cu[3] = {0, 0, 0}; // k_graph_cluster<CW, MODE>'s at [MODE], asked at the first cluster step in that mode
     int transform_blocks_per_cu = 0; // k_graph_transform<ld>'s, asked at the first transform
+    int robust_blocks_per_cu = 0;    // k_graph_residual_weight<ld>'s, asked at the first robust step
 };
 
 namespace glf {

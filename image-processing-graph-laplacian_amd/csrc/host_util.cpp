@@ -1,7 +1,7 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
 // synthetic benchmark images, the geometry and schedule of the band form, the centroid updates and
 // the seedings (plain and weighted) of the spectral segmentation, the orthonormal change of basis of a
-// graph handle from its Gram matrix. No device code.
+// graph handle from its Gram matrix, the loss table and the scale estimate of the robust fit. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -10,6 +10,7 @@
 
 #include "../../include/glf.h"
 #include "band_plan.hpp"
+#include "robust_loss.hpp"
 
 namespace {
 
@@ -288,6 +289,35 @@ int glf_cluster_seed_w(const double *rows, const double *w, size_t n, unsigned d
     for (size_t i = 0; w && i < n; ++i)
         if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return GLF_ERR_INVALID;
     return cluster_seed(rows, w, n, dim, k, seed, cent);
+}
+
+static_assert((int)GLF_ROBUST_HUBER == (int)glf::ROBUST_HUBER && (int)GLF_ROBUST_CAUCHY == (int)glf::ROBUST_CAUCHY && (int)GLF_ROBUST_TUKEY == (int)glf::ROBUST_TUKEY,
+              "robust_loss.hpp restates the header's kinds");
+
+int glf_robust_weight(int kind, double c, double q, double *u, double *rho)
+{
+    if (kind < 0 || kind >= glf::ROBUST_KINDS || !std::isfinite(c) || c < 0.0 || !(q >= 0.0)) return GLF_ERR_INVALID;
+    if (c == 0.0) c = glf::robust_default_c(kind);
+    if (u) *u = glf::robust_u(kind, c, q);
+    if (rho) *rho = glf::robust_rho(kind, c, q);
+    return GLF_OK;
+}
+
+int glf_robust_scale(const double *res, const double *w, size_t n, double *sigma)
+{
+    if (!res || !sigma || n == 0) return GLF_ERR_INVALID;
+    std::vector<double> mag;
+    mag.reserve(n);
+    for (size_t i = 0; i < n; ++i) {
+        if (!std::isfinite(res[i]) || (w && !std::isfinite(w[i]))) return GLF_ERR_INVALID;
+        if (!w || w[i] > 0.0) mag.push_back(std::fabs(res[i]));
+    }
+    if (mag.empty()) return GLF_ERR_INVALID;
+    const size_t mid = (mag.size() - 1) / 2;
+    std::nth_element(mag.begin(), mag.begin() + (std::ptrdiff_t)mid, mag.end());
+    if (!(mag[mid] > 0.0)) return GLF_ERR_INVALID;
+    *sigma = 1.4826 * mag[mid];
+    return GLF_OK;
 }
 
 // The change of basis that makes Phi orthonormal, from its Gram matrix alone (the one-shot orthogonalisation of Fowlkes, Belongie,

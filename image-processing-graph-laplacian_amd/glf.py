@@ -63,6 +63,7 @@ EXPORTS = [
     "glf_multi_image_processing_rgbf32", "glf_multi_image_processing_rgbf32_signals", "glf_read_pfm_rgb", "glf_write_pfm_rgb",
     "glf_graph_build", "glf_graph_destroy", "glf_graph_get_info", "glf_graph_eigenvalues", "glf_graph_gram", "glf_graph_project",
     "glf_graph_synthesize", "glf_filter_coeffs", "glf_graph_normal_equations", "glf_fit_coeffs",
+    "glf_robust_weight", "glf_robust_scale", "glf_graph_robust_step", "glf_graph_fit_robust",
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize",
@@ -74,6 +75,10 @@ GRAPH_MAX_OUTPUTS = 32
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
+ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2
+ROBUST_LOSSES = {"huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
+ROBUST_DEFAULT_C = {ROBUST_HUBER: 1.345, ROBUST_CAUCHY: 2.385, ROBUST_TUKEY: 4.685}   # c = 0: 95 % efficiency under Gaussian noise
+ROBUST_OBJECTIVES = 32     # GLF_ROBUST_OBJECTIVES: the iterations whose objective glf_graph_fit_robust reports
 
 
 class Mat(C.Structure):
@@ -143,6 +148,20 @@ class ClusterEmbed(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("normalize", C.c_int32), ("d_weight", C.c_void_p)]
 
 
+class RobustLoss(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("c", C.c_double), ("sigma", C.c_double * MAX_SIGNALS)]
+
+
+class RobustOptions(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("loss", RobustLoss), ("penalty", C.c_void_p), ("max_iter", C.c_uint32), ("tol", C.c_double),
+                ("sample_rows", C.c_uint32), ("estimate_sigma", C.c_int32)]
+
+
+class RobustStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_uint32), ("converged", C.c_int32), ("sigma", C.c_double * MAX_SIGNALS),
+                ("mass", C.c_double), ("objective", C.c_double * ROBUST_OBJECTIVES)]
+
+
 class OperatorInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("ksplit", C.c_int32), ("skipping", C.c_int32), ("row0", C.c_int32), ("row1", C.c_int32)]
 
@@ -189,6 +208,11 @@ _lib.glf_graph_cluster_step_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c
 _lib.glf_cluster_update_w.argtypes = [C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_cluster_seed_w.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_uint, C.c_uint64, C.c_void_p]
 _lib.glf_graph_segment_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_robust_weight.argtypes = [C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+_lib.glf_robust_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+_lib.glf_graph_robust_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_fit_robust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_transform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_basis_orthonormal.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_orthonormalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
@@ -420,6 +444,47 @@ def fit_coeffs(G, b, penalty=None):
     if rc != OK:
         raise GlfError(rc, "glf_fit_coeffs(m=%d): not positive definite, or an empty system" % m)
     return a.reshape(np.shape(b))
+
+
+def _robust_kind(loss):
+    if isinstance(loss, str):
+        if loss not in ROBUST_LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (sorted(ROBUST_LOSSES), loss))
+        return ROBUST_LOSSES[loss]
+    return int(loss)
+
+
+def robust_weight(loss, q, c=None):
+    """glf_robust_weight (host only): the f64 statement of the robust losses at q = r^2 >= 0 -> (u, rho), u = psi(r) / r the IRLS
+    multiplier and rho the loss, in q's shape (a scalar gives two floats). loss: "huber" | "cauchy" | "tukey" (or a ROBUST_*
+    constant); c: the tuning constant, None or 0 for the kind's 95 % efficiency default (1.345 / 2.385 / 4.685). An unknown kind, a c
+    that is negative or not finite, a q that is negative or NaN raise GlfError(ERR_INVALID)."""
+    kind, cc = _robust_kind(loss), 0.0 if c is None else float(c)
+    qa = np.asarray(q, dtype=np.float64)
+    u, rho = np.zeros(qa.shape), np.zeros(qa.shape)
+    uo, ro = C.c_double(0.0), C.c_double(0.0)
+    for i, qi in enumerate(qa.ravel()):
+        rc = _lib.glf_robust_weight(C.c_int(kind), C.c_double(cc), C.c_double(qi), C.byref(uo), C.byref(ro))
+        if rc != OK:
+            raise GlfError(rc, "glf_robust_weight(kind=%d, c=%g, q=%g)" % (kind, cc, qi))
+        u.flat[i], rho.flat[i] = uo.value, ro.value
+    return (float(u), float(rho)) if qa.ndim == 0 else (u, rho)
+
+
+def robust_scale(res, weight=None):
+    """glf_robust_scale (host only): 1.4826 x the median of |res_i| over the entries with weight_i > 0 (None: all), the median being
+    element floor((cnt - 1) / 2) of the ascending order. No entry of positive weight, an entry that is not finite or a median of 0
+    raise GlfError(ERR_INVALID)."""
+    res = np.ascontiguousarray(np.ravel(np.asarray(res, dtype=np.float64)))
+    if weight is not None:
+        weight = np.ascontiguousarray(np.ravel(np.asarray(weight, dtype=np.float64)))
+        if weight.shape != res.shape:
+            raise ValueError("robust_scale: weight must have res's %d entries, got %d" % (res.size, weight.size))
+    sigma = C.c_double(0.0)
+    rc = _lib.glf_robust_scale(_ptr(res), _ptr(weight), C.c_size_t(res.size), C.byref(sigma))
+    if rc != OK:
+        raise GlfError(rc, "glf_robust_scale(n=%d): no entry of positive weight, an entry that is not finite, or a median of 0" % res.size)
+    return float(sigma.value)
 
 
 def basis_orthonormal(G, lam=None):
@@ -1520,6 +1585,85 @@ class Graph:
         if penalty is None:
             penalty = (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / self.info["m"])
         return self.synthesize(fit_coeffs(G, b, penalty))
+
+    def _robust_loss(self, loss, c, sigma, nplanes):
+        rl = RobustLoss(struct_size=C.sizeof(RobustLoss), kind=_robust_kind(loss), c=0.0 if c is None else float(c))
+        if sigma is not None:
+            sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (nplanes,))
+            for k in range(nplanes):
+                rl.sigma[k] = float(sg[k])
+        return rl
+
+    def robust_step(self, planes, coeffs, loss, c=None, sigma=1.0, weight=None, want_weights=False, want_residuals=False):
+        """One IRLS iteration's device work at the iterate coeffs [nplanes, m] (glf_graph_robust_step): the per-pixel weight
+        w_eff = weight * u(q), q = sum_k ((s_k - Phi a_k) / sigma_k)^2, of the loss "huber" | "cauchy" | "tukey" with the tuning constant
+        c (None: the kind's default), then G = Phi^T diag(w_eff) Phi and b_k = Phi^T diag(w_eff) s_k. planes: device float32
+        [nplanes, H, W], nplanes <= 4; sigma: a float or [nplanes], > 0; weight: device float32 [H, W] or None (= 1).
+        -> (G [m, m], b [nplanes, m], loss = sum w rho(q), mass = sum w_eff, w_eff device float32 [H, W] or None, the residual planes
+        device float32 [nplanes, H, W] or None). Asking for the last two changes no bit of the rest."""
+        t = self.ctx.torch
+        planes = self._planes(planes)
+        nplanes, h, w = planes.shape
+        m = self.info["m"]
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        if a.shape != (nplanes, m):
+            raise ValueError("coeffs must be [%d, %d], got %s" % (nplanes, m, a.shape))
+        if weight is not None:
+            weight = self._weight(weight)
+        rl = self._robust_loss(loss, c, sigma, nplanes)
+        with t.cuda.stream(self.ctx.stream):
+            wout = t.empty((h, w), dtype=t.float32, device=self.ctx.device) if want_weights else None   # (every element is written)
+            rout = t.empty((nplanes, h, w), dtype=t.float32, device=self.ctx.device) if want_residuals else None
+        G, b = np.zeros((m, m), dtype=np.float64), np.zeros((nplanes, m), dtype=np.float64)
+        lo, ma = C.c_double(0.0), C.c_double(0.0)
+        self.ctx._check(_lib.glf_graph_robust_step(self._g, C.byref(rl), C.c_void_p(weight.data_ptr()) if weight is not None else None,
+                                                   C.c_int(nplanes), C.c_void_p(planes.data_ptr()), _ptr(a), _ptr(G), _ptr(b), C.byref(lo), C.byref(ma),
+                                                   C.c_void_p(wout.data_ptr()) if want_weights else None,
+                                                   C.c_void_p(rout.data_ptr()) if want_residuals else None),
+                        "graph robust step")   # (returns with the stream drained)
+        return G, b, float(lo.value), float(ma.value), wout, rout
+
+    def fit_robust(self, planes, weight=None, loss="huber", c=None, sigma=None, smooth=0.0, ridge=0.0, penalty=None, max_iter=20, tol=1e-6,
+                   sample_rows=4096, return_info=False):
+        """The outlier-tolerant fit of the planes in the span of Phi (glf_graph_fit_robust): z_k = Phi a_k with a minimising
+        sum_px w rho(q) + sum_k sum_j penalty_j a_kj^2 / (2 sigma_k^2), q = sum_k ((s_k - Phi a_k) / sigma_k)^2, by iteratively
+        reweighted least squares from the plain weighted fit: robust_step + fit_coeffs(G, b, penalty) until
+        max |a - a_prev| <= tol max |a| or max_iter steps ran, then one synthesize -> device float32 [nplanes, H, W]. loss, c,
+        weight: as for robust_step. sigma: a float or [nplanes], or None to estimate it (robust_scale of the plain fit's residuals
+        on sample_rows rows). smooth, ridge, penalty: as for fit and in its units (where every u = 1 the result is fit's), scaled by
+        trace(G_0) / m of the plain system, so the penalty is fixed over the iterations. Tukey's loss is not convex: the plain fit is
+        the start, nothing cleverer. return_info: -> (fit, dict(coeffs [nplanes, m], weights device float32 [H, W] = the last step's
+        w_eff, the outlier map, iterations, converged, sigma [nplanes], mass, objective [min(iterations, 32)]))."""
+        t = self.ctx.torch
+        planes = self._planes(planes)
+        nplanes, h, w = planes.shape
+        m = self.info["m"]
+        if weight is not None:
+            weight = self._weight(weight)
+        if penalty is None and (smooth or ridge):
+            G0, _ = self.normal_equations(weight)
+            penalty = (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G0) / m)
+        if penalty is not None:
+            penalty = np.ascontiguousarray(penalty, dtype=np.float64)
+            if penalty.shape != (m,):
+                raise ValueError("penalty must be [%d], got %s" % (m, penalty.shape))
+        opt = RobustOptions(struct_size=C.sizeof(RobustOptions), loss=self._robust_loss(loss, c, sigma, nplanes),
+                            penalty=penalty.ctypes.data if penalty is not None else None, max_iter=max_iter, tol=tol, sample_rows=sample_rows,
+                            estimate_sigma=1 if sigma is None else 0)
+        st = RobustStats(struct_size=C.sizeof(RobustStats))
+        a = np.zeros((nplanes, m), dtype=np.float64)
+        with t.cuda.stream(self.ctx.stream):
+            fit = t.empty((nplanes, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written)
+            wout = t.empty((h, w), dtype=t.float32, device=self.ctx.device) if return_info else None
+        self.ctx._check(_lib.glf_graph_fit_robust(self._g, C.byref(opt), C.c_void_p(weight.data_ptr()) if weight is not None else None,
+                                                  C.c_int(nplanes), C.c_void_p(planes.data_ptr()), _ptr(a), C.c_void_p(fit.data_ptr()),
+                                                  C.c_void_p(wout.data_ptr()) if return_info else None, C.byref(st)),
+                        "graph fit robust")   # (returns with the stream drained)
+        if not return_info:
+            return fit
+        its = int(st.iterations)
+        return fit, dict(coeffs=a, weights=wout, iterations=its, converged=int(st.converged), sigma=np.array(st.sigma[:nplanes]),
+                         mass=float(st.mass), objective=np.array(st.objective[:min(its, ROBUST_OBJECTIVES)]))
 
     def synthesize(self, coeffs, ident=None, plane=None, planes=None):
         """out_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (glf_graph_synthesize), one pass over Phi for all outputs: coeffs

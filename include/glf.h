@@ -638,7 +638,7 @@ int glf_filter_coeffs(const glf_options *opt, unsigned m, const double *lam, con
  * GLF_GRAPH_NORMAL_CHAIN pixel terms added into f64; b as exact f64 products summed in f64), glf_fit_coeffs solves on the host, and
  * glf_graph_synthesize with no identity term forms the fit Phi a. Summation order and pixel partition depend on (N, ld) alone:
  * two calls give the same bits, G does not depend on nplanes, a plane's b does not depend on the planes beside it. Out of scope:
- * contexts with a communicator (handles refuse them), m > 256, iterative or non-quadratic data terms. */
+ * contexts with a communicator (handles refuse them), m > 256. Robust (non-quadratic) data terms: the next section. */
 #define GLF_GRAPH_NORMAL_CHAIN 128
 /* G = Phi^T diag(w) Phi (HOST [m][m], exactly symmetric) and b_k = Phi^T diag(w) s_k (HOST [nplanes][m]) in one call.
  * d_w: device float [N] or NULL (w = 1). 0 <= nplanes <= GLF_MAX_SIGNALS; with nplanes 0, d_planes and h_b may be NULL.
@@ -648,6 +648,91 @@ int glf_graph_normal_equations(glf_graph *g, const float *d_w, int nplanes, cons
  * GLF_ERR_INVALID for NULL G / b / a, m = 0, nrhs < 1, or a matrix that is not positive definite
  * (a pivot p with !(p > 0), so NaN is refused too; so is any entry of G or penalty that is not finite); a is then untouched. */
 int glf_fit_coeffs(unsigned m, const double *G, const double *penalty, int nrhs, const double *b, double *a);
+
+/* ---- robust fit on a graph handle: iteratively reweighted least squares under Huber, Cauchy and Tukey losses ------------------------
+ * The weighted fit is quadratic: the caller has to know which pixels are bad. A robust loss does not ask for that mask:
+ * min_a sum_px w rho(q) + the penalty, with q(px) = sum_k ((s_k - Phi a_k)(px) / sigma_k)^2, one weight shared by the 1..4
+ * planes (a joint, vector-valued residual: chroma, normals; independent per-plane fits are separate calls). It is solved by IRLS: at
+ * the iterate a_prev every pixel gets the weight w_eff = w u(q), u = psi(r) / r, and the next iterate is the weighted fit under w_eff,
+ * (G + diag(penalty)) a_k = b_k. The penalty is in the weighted fit's units (with every u = 1 the step is that fit); rho counts a
+ * residual in units of sigma_k and halves its square, so the function the iteration decreases (rho is concave in q, d rho / d q =
+ * u / 2: majorise-minimise) is F(a) = sum_px w rho(q) + sum_k a_k^T diag(penalty) a_k / (2 sigma_k^2).
+ *
+ *   loss     u(q)                                      rho(q)
+ *   Huber    1 if q <= c^2, else c / sqrt(q)           q / 2 if q <= c^2, else c sqrt(q) - c^2 / 2
+ *   Cauchy   1 / (1 + q / c^2)                         (c^2 / 2) log1p(q / c^2)
+ *   Tukey    (1 - q / c^2)^2 if q < c^2, else 0        (c^2 / 6) (1 - (1 - min(q / c^2, 1))^3)
+ *
+ * One iteration's device work (glf_graph_robust_step) is two passes over Phi: k_graph_residual_weight forms d_k = Phi fl32(a_k) on
+ * v_mfma_f32_32x32x2_f32 in glf_graph_synthesize's contraction order (d_k has the bits of glf_graph_synthesize's output for the
+ * coefficients a_k with no identity term), then in f32 res_k = s_k - d_k, x_k = res_k fl32(1 / sigma_k), q = fmaf(x_k, x_k, q) in
+ * ascending k, u by the table with the constants fl32(c), fl32(c^2), fl32(1 / c^2) (Huber: q <= c2 ? 1 : cf / sqrtf(q); Cauchy:
+ * 1 / fmaf(q, ic2, 1); Tukey: t = q ic2, t < 1 ? (1 - t)(1 - t) : 0) and w_eff = w u; rho is formed in f64 from (double) q, and loss
+ * and mass are per-lane f64 sums added in a fixed order. Then glf_graph_normal_equations' own pass with d_w = w_eff forms G and b: they
+ * have the bits of glf_graph_normal_equations(d_weight_out, planes). Two calls give the same bits; a plane's residual plane does not
+ * depend on the planes beside it. sigma is the caller's, or the driver's estimate (glf_robust_scale of the plain fit's residuals on a
+ * sample of rows); the step never estimates it. Tukey's loss is not convex: the driver starts every loss at the plain weighted fit
+ * and does nothing cleverer.
+ * Out of scope: per-plane independent weights in one call, a device-side median, L1 / total-variation terms, m > 256, contexts with
+ * a communicator and glf_multi_* (handles refuse them), a flag of the image_processing host program; k_graph_normal,
+ * k_graph_synthesize, k_graph_cluster and k_graph_transform are untouched. */
+enum { GLF_ROBUST_HUBER = 0, GLF_ROBUST_CAUCHY = 1, GLF_ROBUST_TUKEY = 2 };
+typedef struct glf_robust_loss {
+    uint32_t struct_size;              /* sizeof(glf_robust_loss) */
+    int32_t kind;                      /* GLF_ROBUST_* */
+    double c;                          /* tuning constant, > 0 and finite; 0 = the 95 % efficiency default: 1.345 / 2.385 / 4.685 */
+    double sigma[GLF_MAX_SIGNALS];     /* scale of plane k's residual, > 0 and finite (the step never estimates it) */
+} glf_robust_loss;
+/* Host only: the f64 statement of the table at q = r^2 >= 0 (c = 0: the default of the kind). u and rho may each be NULL.
+ * GLF_ERR_INVALID, u and rho untouched: an unknown kind, a c that is negative or not finite, a q that is negative or NaN. */
+int glf_robust_weight(int kind, double c, double q, double *u, double *rho);
+/* Host only: sigma = 1.4826 x the median of |res_i| over the entries with w_i > 0 (w NULL: all entries), the median being element
+ * floor((cnt - 1) / 2) of the ascending order. GLF_ERR_INVALID, sigma untouched: NULL res / sigma, n = 0, no entry with w > 0, an
+ * entry of res or w that is not finite, a median of 0. */
+int glf_robust_scale(const double *res, const double *w /* [n] or NULL */, size_t n, double *sigma);
+/* One IRLS iteration's device work at the iterate h_a (HOST [nplanes][m]): w_eff = w u(q) of the residuals s_k - Phi a_k,
+ * G = Phi^T diag(w_eff) Phi (HOST [m][m]), b_k = Phi^T diag(w_eff) s_k (HOST [nplanes][m]), *h_loss = sum w rho(q) and *h_mass =
+ * sum w_eff in f64 (either may be NULL). d_weight_out (device float [N]) receives w_eff and d_res_out (device float [nplanes][N])
+ * the residual planes; either may be NULL, and asking for them changes no bit of the rest. 1 <= nplanes <= GLF_MAX_SIGNALS; d_w
+ * device float [N] or NULL (w = 1); the planes and w are not checked for NaN / Inf or sign (glf_graph_normal_equations' rule).
+ * GLF_ERR_INVALID before any device work, nothing written: a NULL handle / loss / planes / h_a / h_G / h_b, a wrong struct_size, an
+ * unknown kind, a c or sigma_k (k < nplanes) that is not finite and positive (c = 0 excepted), an h_a entry that is not finite.
+ * Returns with the stream drained. */
+int glf_graph_robust_step(glf_graph *g, const glf_robust_loss *loss, const float *d_w, int nplanes, const float *d_planes,
+                          const double *h_a, double *h_G, double *h_b, double *h_loss, double *h_mass, float *d_weight_out,
+                          float *d_res_out);
+typedef struct glf_robust_options {
+    uint32_t struct_size;      /* sizeof(glf_robust_options) */
+    glf_robust_loss loss;      /* with estimate_sigma set, loss.sigma is not read */
+    const double *penalty;     /* HOST [m] or NULL (= 0): fixed over the iterations */
+    uint32_t max_iter;         /* 0: 20 */
+    double tol;                /* 0: 1e-6 */
+    uint32_t sample_rows;      /* rows the scale estimate reads; 0: 4096 */
+    int32_t estimate_sigma;    /* 0 | 1 */
+} glf_robust_options;
+#define GLF_ROBUST_OBJECTIVES 32
+typedef struct glf_robust_stats {
+    uint32_t struct_size;      /* sizeof(glf_robust_stats), set by the caller */
+    uint32_t iterations;       /* steps run */
+    int32_t converged;
+    double sigma[GLF_MAX_SIGNALS]; /* the scales used (estimated or given); 0 for k >= nplanes */
+    double mass;               /* sum w_eff of the last step */
+    double objective[GLF_ROBUST_OBJECTIVES]; /* objective[i] = F(a_i) = loss_i + sum_k a_ik^T diag(penalty) a_ik / (2 sigma_k^2) of the
+                                                first 32 steps, loss_i the data term the step at its input a_i reports (a_0: the plain
+                                                weighted fit); non-increasing up to rounding; the rest 0 */
+} glf_robust_stats;
+/* The driver. a_0 is the plain weighted fit (glf_graph_normal_equations + glf_fit_coeffs) for every loss. With estimate_sigma: the
+ * rows px_i = floor(i N / n_s), n_s = min(sample_rows, N), of Phi, the planes and the weight are gathered, the residuals of a_0
+ * formed in f64 on the host and sigma_k = glf_robust_scale of them (a scale of 0, or no sampled pixel of positive weight:
+ * GLF_ERR_INVALID, the message says to pass sigma). Then glf_graph_robust_step(a_prev) + glf_fit_coeffs(G, penalty, b) until
+ * max |a - a_prev| <= tol max |a| or max_iter steps ran, and optionally one glf_graph_synthesize of the result. h_a HOST
+ * [nplanes][m], written; d_fit_out device float [nplanes][N] or NULL; d_weight_out device float [N] or NULL: the last step's
+ * weights (those of the last but one iterate); stats or NULL. Refusals before any device work as for glf_graph_robust_step, and
+ * a NULL opt, a wrong struct_size (opt's, stats'), an estimate_sigma other than 0 | 1, a tol or penalty entry that is negative or
+ * not finite. A system glf_fit_coeffs refuses returns GLF_ERR_INVALID: at a_0 with nothing written, later with h_a, d_fit_out and
+ * stats holding the last good iterate. */
+int glf_graph_fit_robust(glf_graph *g, const glf_robust_options *opt, const float *d_w, int nplanes, const float *d_planes, double *h_a,
+                         float *d_fit_out, float *d_weight_out, glf_robust_stats *stats);
 
 /* ---- spectral segmentation on a graph handle: k-means over the rows of Phi ---------------------------------------------------------
  * The third classic use of the extended eigenvectors: embed every pixel as e(px) = scale o Phi[px][0..dim) (columns in the handle's
