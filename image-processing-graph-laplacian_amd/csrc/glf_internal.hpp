@@ -84,6 +84,9 @@ struct glf_ctx {
     unsigned x0_p = 0, x0_m = 0, x0_ld = 0;
     unsigned long long x0_seed = 0;
     int contraction = GLF_CONTRACT_F16_SPLIT; // how glf_Nystroem / glf_image_processing contract K_B^T Psi
+    // what the last nystroem_contract launch ran with (glf_Nystroem_ex reports it): an exact-zero window (a SKIP instantiation, the
+    // grid and rank forms' skipping passes, the band form's schedule), the table-driven generation of k_nystroem_f16s
+    struct { int skipping = 0, lut = 0; } nys_note;
     // one page of pinned, device-visible host memory the eigensolver's kernels write their flags and norms into (read
     // after a stream synchronise; no D2H copy launches, and no hipHostMalloc per image): see glf::ctx_pinned()
     void *pinned = nullptr;

@@ -345,6 +345,7 @@ static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_
     // f32 operands: K underflows to exactly 0 below 2^-149 (t > 150)
     NysWindow win;
     GLF_TRY(win.init(ctx, d_samples, p, coef, window, 151.0, nwg));
+    ctx->nys_note.skipping = win.radius >= 0;
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (win.radius >= 0)
         hipLaunchKernelGGL((k_nystroem<MB, PB, true, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
@@ -788,6 +789,8 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
     // K' = 2^15 K rounds to zero in f16 (hi and lo) below 2^-25: t > 40; 40.5 covers the f32 rounding of t
     NysWindow win;
     GLF_TRY(win.init(ctx, d_samples, p, coef, window, 40.5, nwg, use_lut ? NYS_MAXCH_LUT : NYS_MAXCH));
+    ctx->nys_note.skipping = win.radius >= 0;
+    ctx->nys_note.lut = use_lut;
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
 #define GLF_NYS_LAUNCH(SKIP_, LUT_, NW_)                                                                                     \
     hipLaunchKernelGGL((k_nystroem_f16s<MB, PB, SKIP_, LUT_, NW_>), dim3((unsigned)nwg), dim3(NW_ * 64), 0, st, d_img, width, \
@@ -844,6 +847,7 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
     if (!entries_evaluated) entries_evaluated = &entries_local;
     if (path) *path = 0;
     if (mfma_flops) *mfma_flops = 0.0;
+    ctx->nys_note.skipping = ctx->nys_note.lut = 0;
     const int64_t N = (int64_t)width * height;
     if (pix0 < 0 || pix1 > N || pix0 > pix1 || !valid_ld(ld) || m > ld)
         return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: bad range or ld=%u", ld);

@@ -1054,6 +1054,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
         if (rc != GLF_ERR_UNSUPPORTED) return rc;
     }
     DevBuf<unsigned long long> dev_eval;
+    ctx->nys_note.skipping = ctx->tune.band_noskip ? 0 : 1; // (the band is a window by construction; BAND_NOSKIP executes all of it)
     GLF_TRY(colscale.alloc(ctx, ld_total));
     GLF_TRY(inv.alloc(ctx, ld_total));
     GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));

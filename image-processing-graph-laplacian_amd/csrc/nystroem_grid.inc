@@ -1128,6 +1128,7 @@ static int launch_nystroem_grid(glf_ctx *ctx, const uint8_t *d_img, int width, i
     const bool blds = ks <= GRID_KS_BLDS && GRID_MT <= 2;
     const size_t lds_row = (size_t)ks * 2048 * MT + (blds ? (size_t)ks * NT * 2048 + GRID_NW * 2 * ER_PIECE * sizeof(float) : 0);
     const bool skip = window && gt.can_skip(coef);
+    ctx->nys_note.skipping = skip;
     auto rowpass = blds ? (skip ? k_grid_rowpass<NT, true, MT, true, false> : k_grid_rowpass<NT, false, MT, true, false>)
                         : (skip ? k_grid_rowpass<NT, true, MT, false, false> : k_grid_rowpass<NT, false, MT, false, false>);
     auto colpass = ecr_dist > 0 ? (skip ? k_grid_colpass<NT, true, false, true> : k_grid_colpass<NT, false, false, true>)

@@ -1372,6 +1372,7 @@ static int launch_nystroem_rank(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(rank_zero_pad(ctx, S.p, (int)round_up(rows_pass, 64), (int)ntt, nc, ncs, R));
     if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nrows * sg.nseg_max * LD));
     const bool skip = window && gt.can_skip(coef);
+    ctx->nys_note.skipping = skip;
     if (rowpass_stats) GLF_TRY(mv_collect(ctx));
     const double ring_ms0 = ctx->mv_ms;
     const int ring_count0 = ctx->mv_count;

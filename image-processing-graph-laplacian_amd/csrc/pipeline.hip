@@ -344,7 +344,8 @@ int glf_InverseDiagMat(glf_ctx *ctx, const glf_mat *x, glf_mat *inv)
     return GLF_OK;
 }
 
-int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf_mat *Pi_A_Inv, glf_mat *phi)
+int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf_mat *Pi_A_Inv, int skip_exact_zeros, unsigned row0,
+                    unsigned row1, glf_mat *phi, glf_nystroem_info *info)
 {
     if (!ctx || !B || !phi_A || !Pi_A_Inv || !phi) return GLF_ERR_INVALID;
     GLF_ENTER(ctx);
@@ -355,6 +356,29 @@ int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf
         return set_error(ctx, GLF_ERR_INVALID, "Nystroem: shape mismatch (p=%u, phi_A %lld x %u ld %u)", p,
                          (long long)phi_A->rows, m, ld);
     const int64_t N = (int64_t)B->width * B->height;
+    const bool all_rows = row0 == 0 && row1 == 0, given = phi->data != nullptr;
+    if (!all_rows && (row0 >= row1 || row1 > (unsigned)B->height))
+        return set_error(ctx, GLF_ERR_INVALID, "Nystroem: image rows [%u, %u) are not a range of the %d rows", row0, row1, B->height);
+    if (given && (phi->kind != GLF_MAT_DENSE || phi->rows != N || phi->cols != m || phi->ld != ld || phi->row_order != GLF_ROWS_SAMPLE_FIRST))
+        return set_error(ctx, GLF_ERR_INVALID, "Nystroem: the given phi (%lld x %lld, ld %lld) is not a dense sample-first %lld x %u matrix of ld %u",
+                         (long long)phi->rows, (long long)phi->cols, (long long)phi->ld, (long long)N, m, ld);
+    if (wide_ld(ld) && (!all_rows || given))
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "Nystroem: more than 256 eigenpairs take all image rows and a phi allocated by the call");
+    const int64_t pix0 = all_rows ? 0 : (int64_t)row0 * B->width, pix1 = all_rows ? N : (int64_t)row1 * B->width;
+    const int window = skip_exact_zeros ? 1 : 0;
+    int path = 0;
+    uint64_t evaluated = 0;
+    auto report = [&]() {
+        if (!info) return;
+        info->path = path;
+        // (the colour, 16-bit and float formats' entry-by-entry kernels contract in f32 whatever the context's mode: glf_stats.contraction)
+        info->contraction = (pixgen_of(B->kernel) != PixGen::Grey && path != 4) ? GLF_CONTRACT_F32_MFMA : ctx->contraction;
+        info->skipping = ctx->nys_note.skipping;
+        info->lut = ctx->nys_note.lut;
+        info->row0 = all_rows ? 0u : row0;
+        info->row1 = all_rows ? (unsigned)B->height : row1;
+        info->entries_evaluated = (double)evaluated;
+    };
     if (wide_ld(ld)) { // more than 256 eigenvectors: one 256-column panel of Phi at a time (columns are independent)
         const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS), p64 = (unsigned)round_up(p, NYS_PAD);
         DevBuf<float> pa, psiw, phip;
@@ -372,12 +396,15 @@ int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf
             hipLaunchKernelGGL(k_make_psi, dim3((unsigned)ceil_div((int64_t)p * PANEL_COLS, 256)), dim3(256), 0, ctx->stream, pa.p,
                                Pi_A_Inv->data + (size_t)q * PANEL_COLS, p, PANEL_COLS, mq, B->scale, psiw.p);
             GLF_LAUNCH_CHECK(ctx);
+            uint64_t ev = 0;
             GLF_TRY(nystroem_contract(ctx, B->img, B->width, B->height, 0, N, reinterpret_cast<const float4 *>(B->samples), B->mask, B->idx, p,
-                                      coefw, B->scale, psiw.p, mq, PANEL_COLS, phip.p, 0, nullptr, nullptr));
+                                      coefw, B->scale, psiw.p, mq, PANEL_COLS, phip.p, 0, nullptr, nullptr, window, &ev, nullptr, &path));
+            evaluated += ev; // (every panel evaluates K_B again)
             GLF_TRY(scatter_sample_rows(ctx, pa.p, p, PANEL_COLS, B->idx, phip.p, 0, B->img, nullptr, mq));
             GLF_TRY(unpack_panel(ctx, phip.p, ld, N, q, phi->data));
         }
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        report();
         return GLF_OK;
     }
     DevBuf<float> psi;
@@ -386,14 +413,27 @@ int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf
     hipLaunchKernelGGL(k_make_psi, dim3((unsigned)ceil_div((int64_t)p * ld, 256)), dim3(256), 0, ctx->stream, phi_A->data,
                        Pi_A_Inv->data, p, ld, m, B->scale, psi.p);
     GLF_LAUNCH_CHECK(ctx);
-    GLF_TRY(glf_mat_create_dense(ctx, phi, N, m, ld));
-    phi->row_order = GLF_ROWS_SAMPLE_FIRST;
+    if (!given) {
+        GLF_TRY(glf_mat_create_dense(ctx, phi, N, m, ld));
+        phi->row_order = GLF_ROWS_SAMPLE_FIRST;
+    }
     const KernelCoef coef = make_coef(B->kernel, B->h_loc, B->h_val);
-    GLF_TRY(nystroem_contract(ctx, B->img, B->width, B->height, 0, N, reinterpret_cast<const float4 *>(B->samples), B->mask,
-                              B->idx, p, coef, B->scale, psi.p, m, ld, phi->data, 0, nullptr, nullptr));
+    GLF_TRY(nystroem_contract(ctx, B->img, B->width, B->height, pix0, pix1, reinterpret_cast<const float4 *>(B->samples), B->mask,
+                              B->idx, p, coef, B->scale, psi.p, m, ld, phi->data, 0, nullptr, nullptr, window, &evaluated, nullptr, &path));
     GLF_TRY(scatter_sample_rows(ctx, phi_A->data, p, ld, B->idx, phi->data, 0, B->img, nullptr, m));
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    report();
     return GLF_OK;
+}
+
+int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf_mat *Pi_A_Inv, glf_mat *phi)
+{
+    if (!phi) return GLF_ERR_INVALID;
+    glf_mat out; // (phi is an output here, allocated by the call whatever the struct held; a refusal leaves it as it was)
+    std::memset(&out, 0, sizeof(out));
+    const int rc = glf_Nystroem_ex(ctx, B, phi_A, Pi_A_Inv, 0, 0, 0, &out, nullptr);
+    if (out.data) *phi = out;
+    return rc;
 }
 
 int glf_Permutation(glf_ctx *ctx, const glf_mat *in, const unsigned *sample_indices, unsigned num, glf_mat *out)

@@ -68,6 +68,7 @@ EXPORTS = [
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize",
     "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
+    "glf_Nystroem_ex",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
@@ -166,6 +167,11 @@ class OperatorInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("ksplit", C.c_int32), ("skipping", C.c_int32), ("row0", C.c_int32), ("row1", C.c_int32)]
 
 
+class NystroemInfo(C.Structure):
+    _fields_ = [("path", C.c_int32), ("contraction", C.c_int32), ("skipping", C.c_int32), ("lut", C.c_int32), ("row0", C.c_uint32),
+                ("row1", C.c_uint32), ("entries_evaluated", C.c_double)]
+
+
 class BasisStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("defect_in", C.c_double), ("defect_out", C.c_double)]
 
@@ -220,6 +226,7 @@ _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, 
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_operator_destroy.argtypes = [C.c_void_p]
+_lib.glf_Nystroem_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -1153,6 +1160,16 @@ class Context:
         phi = Mat()
         self._check(_lib.glf_Nystroem(self._ctx, C.byref(B), C.byref(phi_A), C.byref(Pi_A_Inv), C.byref(phi)), "Nystroem")
         return phi
+
+    def Nystroem_ex(self, B, phi_A, Pi_A_Inv, skip_exact_zeros=0, rows=None, phi=None):
+        """glf_Nystroem_ex: the Nystroem stage with the contraction's window, a range of image rows (rows = (row0, row1); None: all)
+        and, with phi, an existing sample-first N x m matrix written in place. Returns (phi, info), info a dict of glf_nystroem_info."""
+        row0, row1 = (0, 0) if rows is None else rows
+        out = Mat() if phi is None else phi
+        info = NystroemInfo()
+        self._check(_lib.glf_Nystroem_ex(self._ctx, C.byref(B), C.byref(phi_A), C.byref(Pi_A_Inv), C.c_int(skip_exact_zeros), C.c_uint(row0),
+                                         C.c_uint(row1), C.byref(out), C.byref(info)), "Nystroem_ex")
+        return out, {k: getattr(info, k) for k, _ in NystroemInfo._fields_}
 
     def Permutation(self, mat, sample_indices):
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)

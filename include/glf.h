@@ -355,6 +355,31 @@ int glf_Orthogonalisation(glf_ctx *ctx, const double *d_A, int n, const double *
 int glf_Nystroem(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf_mat *Pi_A_Inv,
                  glf_mat *phi);
 
+/* The same stage with the knobs and the report the whole path has: glf_Nystroem is this call with (0, 0, 0, NULL).
+ * skip_exact_zeros: the window of the contraction (glf_options.skip_exact_zeros): the direct kernels pass over the 64-sample chunks,
+ *   the grid and rank forms over the k-steps, whose entries are exact zeros of the contraction's arithmetic; same bits, less work.
+ *   The colour, 16-bit and float formats' entry-by-entry kernels always run with it.
+ * row0 == row1 == 0: all image rows. Otherwise only the image rows [row0, row1) are extended (pixels [row0 width, row1 width): the
+ *   geometry one rank of the sharded whole path has); row0 < row1 <= height.
+ * phi->data == NULL: phi is allocated here, zero-filled, as glf_Nystroem does. Otherwise phi must be an existing dense N x m
+ *   SAMPLE-FIRST matrix of phi_A's ld: the call writes its first p rows (the sample rows, phi_A's bits) and the rows of the
+ *   non-sample pixels in the range; every other row keeps its bits.
+ * More than 256 eigenpairs (ld a multiple of 256 above 256): all image rows and a phi allocated by the call only; a row range or a
+ *   given phi is refused with GLF_ERR_UNSUPPORTED. info then reports the last panel's launch and the entries of all panels.
+ * A refusal (bad range, mismatching phi, m > ld) names its reason in glf_ctx_last_error and leaves phi untouched. */
+typedef struct glf_nystroem_info {
+    int32_t  path;             /* as glf_stats.nystroem_path: 0 direct, 1 grid, 3 rank, 4 band */
+    int32_t  contraction;      /* GLF_CONTRACT_* of the kernel that ran */
+    int32_t  skipping;         /* 1: the launch ran with a window (SKIP instantiation / skipping passes / band) */
+    int32_t  lut;              /* 1: table-driven generation in k_nystroem_f16s */
+    uint32_t row0, row1;       /* image rows written */
+    double   entries_evaluated;
+} glf_nystroem_info;
+
+int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const glf_mat *Pi_A_Inv,
+                    int skip_exact_zeros, unsigned row0, unsigned row1,
+                    glf_mat *phi, glf_nystroem_info *info);
+
 /* Mat Permutation(Mat m, const unsigned* idx, unsigned p)  hpc/utils.h:18, hpc/utils.c:134-173
  * sample-first rows -> raster rows. sample_indices: HOST. */
 int glf_Permutation(glf_ctx *ctx, const glf_mat *in, const unsigned *sample_indices,
