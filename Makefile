@@ -12,7 +12,7 @@ CFLAGS   ?= -O2 -std=gnu11 -Wall -Wextra -fPIC
 HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystroem.hip \
             $(CSRC)/filter.hip $(CSRC)/pipeline.hip $(CSRC)/comm.hip $(CSRC)/nlm.hip $(CSRC)/balance.hip \
             $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip \
-            $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip $(CSRC)/graph_robust.hip
+            $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip $(CSRC)/graph_robust.hip $(CSRC)/graph_project.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
 C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o

@@ -66,13 +66,14 @@ EXPORTS = [
     "glf_robust_weight", "glf_robust_scale", "glf_graph_robust_step", "glf_graph_fit_robust",
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
-    "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize",
+    "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize", "glf_graph_project_wide",
     "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
 GRAPH_MAX_OUTPUTS = 32
+GRAPH_MAX_PLANES = 32      # GLF_GRAPH_MAX_PLANES: the most planes of one glf_graph_project_wide call
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -222,6 +223,7 @@ _lib.glf_graph_fit_robust.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_in
 _lib.glf_graph_transform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_basis_orthonormal.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_orthonormalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+_lib.glf_graph_project_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
@@ -1563,6 +1565,37 @@ class Graph:
         self.ctx._check(_lib.glf_graph_project(self._g, C.c_int(planes.shape[0]), C.c_void_p(planes.data_ptr()), _ptr(c)), "graph project")
         return c
 
+    def project_wide(self, planes, weight=None):
+        """c_k = Phi^T diag(w) s_k on the matrix pipe (glf_graph_project_wide: f32 chains of at most GRAPH_NORMAL_CHAIN pixel terms
+        added into f64), one pass over Phi per 32 planes: planes device float32 [nplanes, H, W], any nplanes >= 1; weight device
+        float32 [H, W] or None (w = 1) -> numpy [nplanes, m]. A plane's row depends neither on the planes beside it nor on its slot,
+        so the grouping by 32 does not show in the bits. Neither argument is checked for NaN / Inf or sign."""
+        planes = self._planes(planes)
+        if planes.shape[0] < 1:
+            raise ValueError("project_wide: no planes")
+        if weight is not None:
+            weight = self._weight(weight)
+        n = self.info["height"] * self.info["width"]
+        c = np.zeros((planes.shape[0], self.info["m"]), dtype=np.float64)
+        for k0 in range(0, planes.shape[0], GRAPH_MAX_PLANES):
+            k1 = min(k0 + GRAPH_MAX_PLANES, planes.shape[0])
+            self.ctx._check(_lib.glf_graph_project_wide(self._g, C.c_void_p(weight.data_ptr()) if weight is not None else None, C.c_int(k1 - k0),
+                                                        C.c_void_p(planes.data_ptr() + 4 * n * k0), _ptr(c[k0:k1])), "graph project wide")
+        return c
+
+    def _synthesize_groups(self, a, ident=None, plane=None, planes=None):
+        """synthesize for any number of outputs: calls of at most GRAPH_MAX_OUTPUTS outputs, each into its rows of one tensor."""
+        t = self.ctx.torch
+        nout = a.shape[0]
+        if nout <= GRAPH_MAX_OUTPUTS:
+            return self.synthesize(a, ident, plane, planes)
+        with t.cuda.stream(self.ctx.stream):
+            out = t.empty((nout, self.info["height"], self.info["width"]), dtype=t.float32, device=self.ctx.device)
+        for o in range(0, nout, GRAPH_MAX_OUTPUTS):
+            rows = slice(o, min(o + GRAPH_MAX_OUTPUTS, nout))
+            self.synthesize(a[rows], None if ident is None else ident[rows], None if plane is None else plane[rows], planes, out=out[rows])
+        return out
+
     def _weight(self, weight):
         t = self.ctx.torch
         h, w = self.info["height"], self.info["width"]
@@ -1597,11 +1630,17 @@ class Graph:
         neither the scale of w nor Phi's normalisation; penalty [m] (absolute units) overrides both. smooth * lam is the Laplacian
         energy of Phi a only to the extent that Phi is orthonormal (the extended eigenvectors are not, exactly; after orthonormalize()
         they are, to f32 rounding). With every
-        penalty 0 and w = 0 on a set that leaves Phi rank deficient the system is refused (GlfError)."""
-        G, b = self.normal_equations(weight, planes)
+        penalty 0 and w = 0 on a set that leaves Phi rank deficient the system is refused (GlfError). More than 4 planes: two passes
+        over Phi, normal_equations(weight) for G and project_wide(planes, weight) for b (f32 chains added into f64 instead of f64
+        sums), and the synthesis in groups of 32 outputs; up to 4 planes the route and its bits are the one-pass route above."""
+        if planes.shape[0] > MAX_SIGNALS:
+            G = self.normal_equations(weight)[0]
+            b = self.project_wide(planes, weight)
+        else:
+            G, b = self.normal_equations(weight, planes)
         if penalty is None:
             penalty = (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / self.info["m"])
-        return self.synthesize(fit_coeffs(G, b, penalty))
+        return self._synthesize_groups(fit_coeffs(G, b, penalty))
 
     def _robust_loss(self, loss, c, sigma, nplanes):
         rl = RobustLoss(struct_size=C.sizeof(RobustLoss), kind=_robust_kind(loss), c=0.0 if c is None else float(c))
@@ -1682,10 +1721,10 @@ class Graph:
         return fit, dict(coeffs=a, weights=wout, iterations=its, converged=int(st.converged), sigma=np.array(st.sigma[:nplanes]),
                          mass=float(st.mass), objective=np.array(st.objective[:min(its, ROBUST_OBJECTIVES)]))
 
-    def synthesize(self, coeffs, ident=None, plane=None, planes=None):
+    def synthesize(self, coeffs, ident=None, plane=None, planes=None, out=None):
         """out_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (glf_graph_synthesize), one pass over Phi for all outputs: coeffs
         [nout, m] (nout <= 32), ident [nout] floats, plane [nout] ints in [-1, nplanes) (-1 / None: no identity term), planes device
-        float32 [nplanes, H, W] or None -> device float32 [nout, H, W]."""
+        float32 [nplanes, H, W] or None -> device float32 [nout, H, W] (out: a contiguous tensor of that shape to write into)."""
         t = self.ctx.torch
         a = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
         nout, h, w = a.shape[0], self.info["height"], self.info["width"]
@@ -1699,8 +1738,13 @@ class Graph:
         if planes is not None:
             planes = self._planes(planes)
             nplanes = planes.shape[0]
-        with t.cuda.stream(self.ctx.stream):
-            out = t.empty((nout, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        if out is None:
+            with t.cuda.stream(self.ctx.stream):
+                out = t.empty((nout, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        else:
+            assert out.dtype == t.float32 and out.is_cuda and out.is_contiguous()
+            if tuple(out.shape) != (nout, h, w):
+                raise ValueError("out must be [%d, %d, %d], got %s" % (nout, h, w, tuple(out.shape)))
         self.ctx._check(_lib.glf_graph_synthesize(self._g, C.c_int(nout), _ptr(a), _ptr(idn), _ptr(pl), C.c_int(nplanes),
                                                   C.c_void_p(planes.data_ptr()) if planes is not None else None,
                                                   C.c_void_p(out.data_ptr())), "graph synthesize")   # (returns with the stream drained)
@@ -1822,18 +1866,20 @@ class Graph:
             self._refresh()
         return dict(passes=int(st.passes), defect_in=float(st.defect_in), defect_out=float(st.defect_out))
 
-    def apply(self, planes, weights, ident=1.0):
+    def apply(self, planes, weights, ident=1.0, wide=None):
         """Diagonal responses: out[r, k] = ident[r] * s_k + Phi diag(weights[r]) Phi^T s_k for every response r and plane k -- one
-        project, the scaling on the host, one synthesize of nresp * nplanes <= 32 outputs. weights [nresp, m] (e.g. gain * lam for
-        the reference filter, 1 - lam for smoothing, any band-pass), ident a float or [nresp] -> device float32 [nresp, nplanes, H, W]."""
+        projection, the scaling on the host, the synthesis. weights [nresp, m] (e.g. gain * lam for the reference filter, 1 - lam
+        for smoothing, any band-pass), ident a float or [nresp] -> device float32 [nresp, nplanes, H, W]. wide None: up to 4 planes
+        and nresp * nplanes <= 32 outputs take project and one synthesize; anything larger takes project_wide (one pass over Phi
+        per 32 planes) and synthesize in groups of at most 32 outputs. wide True: project_wide for any nplanes."""
         wts = np.atleast_2d(np.asarray(weights, dtype=np.float64))
         nresp, nplanes = wts.shape[0], planes.shape[0]
-        if nresp * nplanes > GRAPH_MAX_OUTPUTS:
-            raise ValueError("apply: %d responses x %d planes exceed %d outputs" % (nresp, nplanes, GRAPH_MAX_OUTPUTS))
-        c = self.project(planes)
+        if wide is None:
+            wide = nplanes > MAX_SIGNALS or nresp * nplanes > GRAPH_MAX_OUTPUTS
+        c = self.project_wide(planes) if wide else self.project(planes)
         a = (wts[:, None, :] * c[None, :, :]).reshape(nresp * nplanes, -1)
         idn = np.repeat(np.broadcast_to(np.asarray(ident, dtype=np.float32), (nresp,)), nplanes)
-        out = self.synthesize(a, idn, np.tile(np.arange(nplanes, dtype=np.int32), nresp), planes)
+        out = self._synthesize_groups(a, idn, np.tile(np.arange(nplanes, dtype=np.int32), nresp), planes)
         return out.view(nresp, nplanes, self.info["height"], self.info["width"])
 
 

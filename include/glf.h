@@ -896,6 +896,30 @@ typedef struct glf_basis_stats {
  * definite (a later pass that fails leaves the handle as the pass before left it). */
 int glf_graph_orthonormalize(glf_graph *g, int mode, int passes /* 1 | 2 */, int verify, glf_basis_stats *stats /* or NULL */);
 
+/* ---- graph handle: project up to 32 planes in one pass over Phi ------------------------------------------------------------------------
+ * glf_graph_synthesize writes 32 outputs in one pass over Phi; glf_graph_project and glf_graph_normal_equations take 4 planes, on
+ * f64 fma chains that, not the memory, set their time. glf_graph_project_wide is the projection on the matrix pipe
+ * (k_graph_project_wide): a 32-channel feature map, the bands of a multispectral cube, a stack of depth hypotheses or the frames of
+ * a burst cost one pass instead of ceil(k / 4). Operation by operation: t_k = fl32(w s_k), one f32 multiplication per pixel and
+ * plane (d_w NULL: t_k = s_k itself, so NULL and a plane of ones give the same bits); v_mfma_f32_32x32x2_f32 with the pixels as
+ * the contraction index, operands t (the 32 plane slots) and Phi exactly as stored (32 columns), every (plane, column) its own f32
+ * fma chain over at most GLF_GRAPH_NORMAL_CHAIN pixel terms in ascending pixel order, then added into an f64 image and cleared
+ * (k_graph_normal's rule for G); the per-wave and per-workgroup f64 partials are added in a fixed order, no atomics. The pixel
+ * partition comes from a fixed per-ld table, so it and the summation order depend on (N, ld) alone: two calls give the same bits; a
+ * plane's c depends neither on nplanes, nor on the planes beside it, nor on the slot it sits in; w = 0 gives exact zeros. Against
+ * exact arithmetic |c - c*| <= ((GLF_GRAPH_NORMAL_CHAIN + 3) 2^-24 + N 2^-51) sum_px |w s Phi| per entry. Phi is read
+ * once at every ld, the planes once (twice at ld 256: the columns are cut into groups of 128). Out of scope: rerouting
+ * glf_graph_project, glf_graph_normal_equations or glf_graph_gram through this kernel (their bits stay), contexts with a
+ * communicator and glf_multi_* (handles refuse them), m > 256, a flag of the image_processing host program. */
+#define GLF_GRAPH_MAX_PLANES 32
+/* c_k = Phi^T diag(w) s_k for 1 <= nplanes <= GLF_GRAPH_MAX_PLANES planes in one pass over Phi.
+ * d_w: device float [N] or NULL (w = 1); d_planes: device float [nplanes][N]; h_c: HOST double [nplanes][m], m the handle's current
+ * m (after glf_graph_transform: m_new). GLF_ERR_INVALID before any device work for a NULL handle, d_planes or h_c, or nplanes
+ * outside 1 .. GLF_GRAPH_MAX_PLANES; h_c is untouched on every refusal and every failure. w and the planes are not checked for
+ * NaN / Inf or sign (glf_graph_normal_equations' rule): a NaN or Inf in plane k (or in w) reaches c_k (or every c) and no other
+ * plane's. Returns with the stream drained. */
+int glf_graph_project_wide(glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_c);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
