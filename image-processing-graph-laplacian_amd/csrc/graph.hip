@@ -1,7 +1,7 @@
 // graph.hip -- the graph handle (glf_graph_*): the eigenbasis of one image built once, then any number of projections
 // c = Phi^T s and syntheses out = ident s + Phi a on it. The build is the format's capture call with the handle's Phi as the
 // capture target; Phi^T s and Phi^T Phi are filter.hip's phi_t_signals / phi_gram; the synthesis is the one new kernel.
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -9,8 +9,6 @@
 #include <new>
 
 namespace glf {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // the per-call operand block of k_graph_synthesize (device): the coefficients as the MFMA's A operand, then the identity terms
 //   [LD][32] float  (float)a_j[k] at [k][j], zero for j >= nout and k >= m
@@ -20,22 +18,16 @@ constexpr int GS_OUT = GLF_GRAPH_MAX_OUTPUTS;
 inline size_t gs_operand_floats(unsigned ld) { return (size_t)ld * GS_OUT + 2 * GS_OUT; }
 
 // Out[j][px] = ident[j] s_plane[j][px] + sum_k Phi[px][k] a_j[k] for all outputs j < nout in one pass over Phi.
-// One wave per tile of 32 pixels, v_mfma_f32_32x32x2_f32 with the outputs as the M index (A: the coefficients, read from LDS)
-// and the pixels as the N index (B: Phi), so that register g of the accumulator holds, in the 32 lanes of half h, 32 consecutive
-// pixels of output (g & 3) + 8 (g >> 2) + 4 h. The tile's rows are loaded as whole 16-byte pieces in address order (each row's
-// CW * 4 bytes contiguous), written to the wave's own LDS image with the row pitch padded by 4 floats, and read back one pixel
-// per lane as float4s (pitch CW + 4: the 16 lanes of a ds_read_b128 group hit 64 different banks). The contraction index is
-// visited in a fixed order that does not depend on nout -- chunk by chunk of CW columns, half-wave h taking columns
-// h CW / 2 + t of the chunk at step t -- and every output is its own k-ordered fma chain: its bits do not depend on the
-// outputs beside it. Rows past N are staged as zeros and neither read nor stored.
+// The outputs are the M index (A: the coefficients, from LDS), the pixels the N index (B: Phi, the padded image of phi_tile.hpp):
+// register g of the accumulator holds, in the 32 lanes of half h, 32 consecutive pixels of output acc_row(g, h). The contraction index
+// is visited chunk by chunk of CW columns in chunk_contract's order, which does not depend on nout, and every output is its own
+// k-ordered fma chain: its bits do not depend on the outputs beside it. Rows past N are neither read nor stored.
 template <int LD>
 __global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restrict__ phi, int64_t N, int nout, const float *__restrict__ operand,
                                                            const float *__restrict__ planes, float *__restrict__ out)
 {
     constexpr int CW = LD < 64 ? LD : 64; // columns staged per pass
     constexpr int PITCH = CW + 4;
-    constexpr int FPR = CW / 4;           // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8;         // pieces per lane: 32 rows x FPR / 64 lanes
     __shared__ __attribute__((aligned(16))) float a_sh[LD * GS_OUT];
     __shared__ __attribute__((aligned(16))) float tile_sh[4][32 * PITCH];
     __shared__ float ident_sh[GS_OUT];
@@ -50,49 +42,25 @@ __global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restric
     const int r = lane & 31, h = lane >> 5;
     float *tw = tile_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
-    // the pieces this lane stages of chunk ch of a tile: rows past N as zeros
-    float4 v[NLOAD];
-    auto load_chunk = [&](int64_t tile, int ch) {
-        const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + ch * CW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
+    float4 v[CW / 8];
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntiles) load_chunk(tile, 0);
+    if (tile < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile, lane);
     for (; tile < ntiles; tile += tstride) {
         f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+        acc_clear(acc);
 #pragma unroll 1
         for (int ch = 0; ch < LD / CW; ++ch) {
-            __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
-#pragma unroll
-            for (int q = 0; q < NLOAD; ++q) {
-                const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-                *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
-            }
-            __builtin_amdgcn_wave_barrier();
+            tile_store<CW, PITCH>(tw, v, lane);
             // the next chunk's loads fly under this chunk's MFMAs
-            if (ch + 1 < LD / CW) load_chunk(tile, ch + 1);
-            else if (tile + tstride < ntiles) load_chunk(tile + tstride, 0);
-#pragma unroll
-            for (int u = 0; u < CW / 8; ++u) {
-                const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
-                const float *ak = a_sh + (size_t)(ch * CW + h * (CW / 2) + 4 * u) * GS_OUT + r;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GS_OUT], b.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GS_OUT], b.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GS_OUT], b.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GS_OUT], b.w, acc, 0, 0, 0);
-            }
+            if (ch + 1 < LD / CW) tile_load<CW>(v, phi, LD, (ch + 1) * CW, N, tile, lane);
+            else if (tile + tstride < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile + tstride, lane);
+            chunk_contract<CW, GS_OUT>(acc, tw, a_sh + (size_t)(ch * CW) * GS_OUT, r, h);
         }
         const int64_t px = tile * 32 + r;
         if (px < N) {
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const int j = (g & 3) + 8 * (g >> 2) + 4 * h;
+                const int j = acc_row(g, h);
                 if (j < nout) {
                     float z = acc[g];
                     const int pl = plane_sh[j];
@@ -118,13 +86,22 @@ static int launch_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int6
 static int graph_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, int nout, const float *d_operand,
                             const float *d_planes, float *d_out)
 {
-    switch (ld) {
-    case 32: return launch_synthesize<32>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
-    case 64: return launch_synthesize<64>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
-    case 128: return launch_synthesize<128>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
-    case 256: return launch_synthesize<256>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out);
-    }
-    return set_error(ctx, GLF_ERR_INVALID, "graph_synthesize: ld=%u", ld);
+    int rc = GLF_OK;
+    if (!dispatch_ld(ld, [&](auto LD) { rc = launch_synthesize<LD.value>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out); }))
+        return set_error(ctx, GLF_ERR_INVALID, "graph_synthesize: ld=%u", ld);
+    return rc;
+}
+
+__global__ void k_sample_rows(const float *__restrict__ phi, int64_t N, int ld, int dim, int nplanes, const float *__restrict__ planes,
+                              const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out)
+{
+    const int cols = dim + nplanes + wcol;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= ns * cols) return;
+    const int64_t i = e / cols;
+    const int c = (int)(e % cols);
+    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
+    out[e] = c < dim ? phi[(size_t)px * ld + c] : c < dim + nplanes ? planes[(size_t)(c - dim) * N + px] : w ? w[px] : 1.f;
 }
 
 } // namespace glf
@@ -321,8 +298,7 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float 
     }
     std::memcpy(h_op.data() + (size_t)ld * GS_OUT + GS_OUT, h_plane, sizeof(h_plane));
     DevBuf<float> op;
-    GLF_TRY(op.alloc(ctx, h_op.size()));
-    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    GLF_TRY(upload_operand(ctx, op, h_op));
     GLF_TRY(graph_synthesize(ctx, &g->synth_blocks_per_cu, g->phi, N, ld, nout, op.p, d_planes, d_out));
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)
     return GLF_OK;

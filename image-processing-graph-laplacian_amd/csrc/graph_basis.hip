@@ -4,7 +4,7 @@
 // Out of scope: contexts with a communicator and glf_multi_* (handles refuse them), m > 256, changing ld, a flag of the host
 // program, Rayleigh-Ritz against the true Laplacian (it needs L Phi over all pixels), a faster glf_graph_gram, and anything inside
 // k_band, k_graph_synthesize, k_graph_normal and k_graph_cluster*.
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -12,7 +12,6 @@
 
 namespace glf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // the per-call operand of k_graph_transform (device): [LD][LD] float, fl32(T[k][j]) at [k][j], zero for k >= m and j >= m_new
@@ -20,11 +19,10 @@ inline size_t gt_operand_floats(unsigned ld) { return (size_t)ld * ld; }
 
 // Phi'[px][j] = sum_k Phi[px][k] fl32(T[k][j]) for j < m_new, exact zeros for m_new <= j < LD, written over Phi.
 // One wave per tile of 32 pixels, tiles strided over a resident grid in groups of four (one per wave of the workgroup).
-// v_mfma_f32_32x32x2_f32 with the pixels as the M index (A: Phi, one pixel per lane as float4s from the wave's LDS image, which is
-// k_graph_synthesize's: whole 16-byte pieces loaded in address order, row pitch CW + 4) and 32 output columns as the N index (B:
-// T[k][32 t + r], 32 consecutive floats of one LDS row per half-wave: no conflict). A wave keeps all LD / 32 accumulator tiles, so
-// a float4 of Phi feeds 4 LD / 32 MFMAs. Register g of tile t holds, in the 32 lanes of half h, columns 32 t .. 32 t + 31 of pixel
-// (g & 3) + 8 (g >> 2) + 4 h: a store instruction writes two 128-byte row segments. The other shape -- k_graph_synthesize's, the
+// The pixels are the M index (A: Phi, one pixel per lane as float4s from the padded image of phi_tile.hpp) and 32 output columns
+// the N index (B: T[k][32 t + r], 32 consecutive floats of one LDS row per half-wave: no conflict). A wave keeps all LD / 32
+// accumulator tiles, so a float4 of Phi feeds 4 LD / 32 MFMAs. Register g of tile t holds, in the 32 lanes of half h, columns
+// 32 t .. 32 t + 31 of pixel acc_row(g, h): a store instruction writes two 128-byte row segments. The other shape -- k_graph_synthesize's, the
 // outputs as the M index -- leaves one column of 32 pixels per register and needs a transpose through LDS before any row segment
 // can be stored; this one stores from the accumulator as it is.
 // The contraction index is visited in k_graph_synthesize's order, which depends on LD alone -- chunk by chunk of CW columns,
@@ -73,8 +71,6 @@ __global__ __launch_bounds__(256) void k_graph_transform(float *phi, int64_t N, 
     constexpr int CW = LD < 64 ? LD : 64; // columns staged per pass
     constexpr int NCH = LD / CW;
     constexpr int PITCH = CW + 4;
-    constexpr int FPR = CW / 4;           // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8;         // pieces per lane: 32 rows x FPR / 64 lanes
     constexpr int NT = LD / 32;           // accumulator tiles
     constexpr bool RESIDENT = LD <= 128;  // all of T in LDS
     constexpr int TROWS = RESIDENT ? LD : CW; // (streamed: two buffers of CW / 2 rows)
@@ -108,38 +104,21 @@ __global__ __launch_bounds__(256) void k_graph_transform(float *phi, int64_t N, 
     __syncthreads();
     float *tw = tile_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
-    // the pieces this lane stages of chunk ch of a tile: rows past N as zeros
-    float4 v[NLOAD];
-    auto load_chunk = [&](int64_t tile, int ch) {
-        const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + ch * CW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    if ((int64_t)blockIdx.x * 4 + wave < ntiles) load_chunk((int64_t)blockIdx.x * 4 + wave, 0);
+    float4 v[CW / 8];
+    if ((int64_t)blockIdx.x * 4 + wave < ntiles) tile_load<CW>(v, phi, LD, 0, N, (int64_t)blockIdx.x * 4 + wave, lane);
     for (int64_t group = (int64_t)blockIdx.x * 4; group < ntiles; group += tstride) {
         const int64_t tile = group + wave;
         const bool live = tile < ntiles; // (wave-uniform)
         f32x16 acc[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) acc[t][g] = 0.f;
+        for (int t = 0; t < NT; ++t) acc_clear(acc[t]);
 #pragma unroll 1
         for (int ch = 0; ch < NCH; ++ch) {
             if (live) {
-                __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
-#pragma unroll
-                for (int q = 0; q < NLOAD; ++q) {
-                    const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-                    *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
-                }
-                __builtin_amdgcn_wave_barrier();
+                tile_store<CW, PITCH>(tw, v, lane);
                 // the next chunk's loads fly under this chunk's MFMAs
-                if (ch + 1 < NCH) load_chunk(tile, ch + 1);
-                else if (tile + tstride < ntiles) load_chunk(tile + tstride, 0);
+                if (ch + 1 < NCH) tile_load<CW>(v, phi, LD, (ch + 1) * CW, N, tile, lane);
+                else if (tile + tstride < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile + tstride, lane);
             }
             if constexpr (RESIDENT) {
                 if (live) gt_steps<LD, NT, CW / 8>(acc, tw + r * PITCH + h * (CW / 2), t_sh + (size_t)(ch * CW + h * (CW / 2)) * LD + r);
@@ -162,7 +141,7 @@ __global__ __launch_bounds__(256) void k_graph_transform(float *phi, int64_t N, 
             // every column of the tile's rows has been read by now: the stores may begin
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
-                const int64_t px = tile * 32 + (g & 3) + 8 * (g >> 2) + 4 * h;
+                const int64_t px = tile * 32 + acc_row(g, h);
                 if (px < N) {
                     float *row = phi + (size_t)px * LD + r;
 #pragma unroll
@@ -220,17 +199,13 @@ int glf_graph_transform(glf_graph *g, unsigned m_new, const double *h_T, const d
     const int64_t N = (int64_t)g->width * g->height;
     GLF_ENTER(ctx);
     DevBuf<float> op;
-    GLF_TRY(op.alloc(ctx, h_op.size()));
-    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    GLF_TRY(upload_operand(ctx, op, h_op));
     // from here on a failure leaves Phi unspecified: the handle's cached Gram matrix goes first
     g->gram.clear();
-    switch (ld) {
-    case 32: GLF_TRY(launch_transform<32>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p)); break;
-    case 64: GLF_TRY(launch_transform<64>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p)); break;
-    case 128: GLF_TRY(launch_transform<128>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p)); break;
-    case 256: GLF_TRY(launch_transform<256>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p)); break;
-    default: return set_error(ctx, GLF_ERR_INVALID, "glf_graph_transform: ld=%u", ld);
-    }
+    int rc = GLF_OK;
+    if (!dispatch_ld(ld, [&](auto LD) { rc = launch_transform<LD.value>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p); }))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_transform: ld=%u", ld);
+    GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)
     g->m = m_new;
     g->lam.assign(h_lam_new, h_lam_new + m_new);

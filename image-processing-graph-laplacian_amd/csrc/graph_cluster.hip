@@ -6,19 +6,15 @@
 // Out of scope: spherical k-means (renormalised centroids), a margin or confidence output, more than 64 embedding columns, k > 32,
 // contexts with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
 // k_graph_synthesize and k_graph_normal.
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace glf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int GC_K = GLF_CLUSTER_MAX;                       // centroids = the M index of one 32 x 32 accumulator
-constexpr int GC_CHAIN_TILES = GLF_GRAPH_NORMAL_CHAIN / 32; // 32-pixel tiles in one f32 chain of the sums
+constexpr int GC_K = GLF_CLUSTER_MAX; // centroids = the M index of one 32 x 32 accumulator
 static_assert(GC_K == 32, "the centroids fill exactly one MFMA tile");
-static_assert(GLF_GRAPH_NORMAL_CHAIN % 32 == 0 && GLF_GRAPH_NORMAL_CHAIN >= 32, "a chain is a whole number of 32-pixel tiles");
 
 // The modes of k_graph_cluster: the embedding is e(px) = rinv(px) scale o Phi[px], and pixel px enters the update with weight w(px).
 //   GC_PLAIN   rinv = 1, w = 1
@@ -38,26 +34,19 @@ inline size_t gc_operand_floats(int cw, int mode) { return (size_t)cw * GC_K + G
 constexpr int gc_tail(int mode) { return mode == GC_PLAIN ? 64 : 96; }
 inline size_t gc_part_cols(int cw, int mode) { return (size_t)(cw / 32) * 1024 + gc_tail(mode); }
 
-// One Lloyd iteration in one pass over the first CW columns of Phi (row pitch ld floats). One wave per tile of 32 pixels, tiles
-// strided over a resident grid. The tile's rows are loaded as whole 16-byte pieces in address order and written to the wave's own
-// LDS image with the row pitch padded by 4 floats (k_graph_synthesize's image).
-// Assignment: v_mfma_f32_32x32x2_f32 with the centroids as the M index (A: the operand block, from LDS) and the pixels as the N
-// index (B: Phi, one pixel per lane as float4s; pitch CW + 4: the 16 lanes of a ds_read_b128 group hit 64 different banks), half-wave
-// h taking columns h CW / 2 + t at step t: k_graph_synthesize's contraction order, every score its own fma chain. Register g of
-// lane (r, h) then holds the dot product of pixel r with centroid j = (g & 3) + 8 (g >> 2) + 4 h; score = fmaf(-2 rinv, dot, |c_j|^2)
-// (|e|^2 is the same for every j and is not formed). Each lane takes the argmin of its 16 registers in ascending j with a strict <
-// (j >= k carries a bias of +inf and never wins), one exchange with the other half-wave decides between the two, the lower index
-// winning a tie.
+// One Lloyd iteration in one pass over the first CW columns of Phi (row pitch ld floats), on the padded image of phi_tile.hpp.
+// Assignment: chunk_contract with the centroids as the M index (A: the operand block, from LDS) and the pixels as the N index:
+// k_graph_synthesize's contraction order, every score its own fma chain. Register g of lane (r, h) then holds the dot product of pixel
+// r with centroid j = acc_row(g, h); score = fmaf(-2 rinv, dot, |c_j|^2) (|e|^2 is the same for every j and is not formed). Each lane
+// takes the argmin of its 16 registers in ascending j with a strict < (j >= k carries a bias of +inf and never wins), one exchange
+// with the other half-wave decides between the two, the lower index winning a tie.
 // Update: the wave's 32 labels go to LDS (-1 for rows past N), then the same MFMA with the pixels as the contraction index: at step
 // u lane (r, h) gives A = (label[2u + h] == r ? t[2u + h] : 0), t(px) = fl32(w(px) rinv(px)), and B = Phi[2u + h][r] (and [32 + r])
-// from the same image -- the 32 lanes of a ds_read_b32 group read 32 consecutive floats of one row, no conflict at any pitch; the
-// label is one address per group, a broadcast. sums_j = sum w rinv Phi[px][c] over the members of j: each accumulator tile is an f32
-// chain over at most GLF_GRAPH_NORMAL_CHAIN pixels, then added into its f64 image and cleared (k_graph_normal's rule). Lane (r, h)
-// counts its own hits: the members of label r among the pixels of parity h, an exact integer; the lanes of half 0 count the labels
-// that differ from prev.
-// No atomics: the workgroup's four waves are added in a fixed order, the workgroups by k_cols_sum. Rows past N are staged as
-// zeros and are neither labelled nor counted. prev may be labels itself: a lane reads prev[px] before it writes labels[px], and
-// no other lane touches that pixel.
+// from the same image; the label is one address per group, a broadcast. sums_j = sum w rinv Phi[px][c] over the members of j, under
+// the chain rule and the four-wave reduction of phi_tile.hpp. Lane (r, h) counts its own hits: the members of label r among the
+// pixels of parity h, an exact integer; the lanes of half 0 count the labels that differ from prev.
+// Rows past N are neither labelled nor counted. prev may be labels itself: a lane reads prev[px] before it writes labels[px], and no
+// other lane touches that pixel.
 // What the modes change (MODE is a template argument, nothing of another mode is left in an instance):
 //   GC_PLAIN keeps the 16 biases |c_j|^2 of a lane in registers; t = 1, so A is 1 or 0 and the products are exact. In the other modes
 //   the biases are read from LDS at every tile (bias_sh, +inf for j >= k; registers 4 q .. 4 q + 3 hold 16 consecutive bytes): with
@@ -77,8 +66,6 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
                                                           double *__restrict__ part)
 {
     constexpr int PITCH = CW + 4;
-    constexpr int FPR = CW / 4;   // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8; // pieces per lane: 32 rows x FPR / 64 lanes
     constexpr int NT = CW / 32;   // accumulator tiles of the sums
     constexpr int RW = 32 * PITCH > 2048 ? 32 * PITCH : 2048; // floats of a wave's region (>= one f64 tile for the epilogue)
     constexpr int TAIL = gc_tail(MODE);
@@ -93,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = lane & 31, h = lane >> 5;
     for (int e = threadIdx.x; e < CW * GC_K; e += 256) a_sh[e] = operand[e];
-    auto centroid_of = [&](int g) { return (g & 3) + 8 * (g >> 2) + 4 * h; }; // the centroid of accumulator register g of this lane
+    auto centroid_of = [&](int g) { return acc_row(g, h); }; // the centroid of accumulator register g of this lane
     float bias[16];
     if constexpr (MODE == GC_PLAIN) {
 #pragma unroll
@@ -127,16 +114,12 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
     double mass = 0.0;
 
     // what this lane stages of a tile: rows past N as zeros
-    float4 v[NLOAD];
+    float4 v[CW / 8];
     int pv = 0;
     float wv = 1.f;
     auto load_tile = [&](int64_t tile) {
         const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * ld + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        tile_load<CW>(v, phi, ld, 0, N, tile, lane);
         if constexpr (MODE == GC_PLAIN) { // (prev first: with the other order the plain tile loop gains scalar work per tile)
             if (prev && h == 0 && base + r < N) pv = prev[base + r];
         } else if (h == 0 && base + r < N) {
@@ -144,53 +127,31 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
             if (weight) wv = weight[base + r];
         }
     };
-    auto flush = [&]() {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                dacc[t][g] += (double)acc[t][g];
-                acc[t][g] = 0.f;
-            }
-    };
 
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     if (tile < ntiles) load_tile(tile);
     int chained = 0; // tiles in the running f32 chains
     for (; tile < ntiles; tile += tstride) {
-        __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
-        }
+        tile_store<CW, PITCH>(tw, v, lane);
         const int pv_cur = pv;
         const float wv_cur = wv;
-        __builtin_amdgcn_wave_barrier();
         // the next tile's loads fly under this tile's MFMAs
         if (tile + tstride < ntiles) load_tile(tile + tstride);
 
         f32x16 sc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) sc[g] = 0.f;
+        acc_clear(sc);
         float n2 = 0.f;
-#pragma unroll
-        for (int u = 0; u < CW / 8; ++u) {
-            const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
-            const float *ak = a_sh + (h * (CW / 2) + 4 * u) * GC_K + r;
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[0 * GC_K], b.x, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[1 * GC_K], b.y, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[2 * GC_K], b.z, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x2f32(ak[3 * GC_K], b.w, sc, 0, 0, 0);
-            if constexpr (MODE == GC_NORM) {
+        if constexpr (MODE == GC_NORM)
+            chunk_contract<CW, GC_K>(sc, tw, a_sh, r, h, [&](int u, const float4 &b) {
                 const float4 s = *reinterpret_cast<const float4 *>(s_sh + h * (CW / 2) + 4 * u);
                 const float x0 = s.x * b.x, x1 = s.y * b.y, x2 = s.z * b.z, x3 = s.w * b.w;
                 n2 = fmaf(x0, x0, n2);
                 n2 = fmaf(x1, x1, n2);
                 n2 = fmaf(x2, x2, n2);
                 n2 = fmaf(x3, x3, n2);
-            }
-        }
+            });
+        else
+            chunk_contract<CW, GC_K>(sc, tw, a_sh, r, h);
         float rinv = 1.f;
         if constexpr (MODE == GC_NORM) {
             n2 += __shfl_xor(n2, 32);
@@ -237,28 +198,15 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + r], acc[0], 0, 0, 0);
             if constexpr (NT == 2) acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[p * PITCH + 32 + r], acc[1], 0, 0, 0);
         }
-        if (++chained == GC_CHAIN_TILES) {
-            flush();
+        if (++chained == CHAIN_TILES) {
+            chain_flush(acc, dacc);
             chained = 0;
         }
     }
-    flush();
+    chain_flush(acc, dacc);
 
-    // the workgroup's four waves, wave 0 first, tile by tile through the waves' regions (one f64 tile each)
     double *const pout = part + (size_t)blockIdx.x * (NT * 1024 + TAIL);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        __syncthreads();
-        double *mine = reinterpret_cast<double *>(region[wave]);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[t][g];
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 256) {
-            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
-                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
-            pout[(size_t)t * 1024 + e] = s;
-        }
-    }
+    wave_tiles_reduce(region, dacc, wave, r, h, [&](int t, int e, double s) { pout[(size_t)t * 1024 + e] = s; });
     cnt_sh[wave][lane] = cnt;
     chg_sh[wave][lane] = chg;
     if constexpr (MODE != GC_PLAIN) mass_sh[wave][lane] = mass;
@@ -287,24 +235,6 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
 using cluster_kernel = decltype(&k_graph_cluster<32, GC_PLAIN>);
 static const cluster_kernel GC_KERNELS[2][GC_MODES] = {{k_graph_cluster<32, GC_PLAIN>, k_graph_cluster<32, GC_WEIGHT>, k_graph_cluster<32, GC_NORM>},
                                                        {k_graph_cluster<64, GC_PLAIN>, k_graph_cluster<64, GC_WEIGHT>, k_graph_cluster<64, GC_NORM>}};
-
-// out[i][c] = Phi[floor(i N / ns)][c], c < dim: the sample of rows the seeding draws from
-__global__ void k_cluster_sample(const float *__restrict__ phi, int64_t N, int ld, int64_t ns, int dim, float *__restrict__ out)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ns * dim) return;
-    const int64_t i = e / dim;
-    const int c = (int)(e % dim);
-    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
-    out[e] = phi[(size_t)px * ld + c];
-}
-
-// out[i] = w[floor(i N / ns)]: the weights of the rows k_cluster_sample gathers
-__global__ void k_cluster_sample_w(const float *__restrict__ w, int64_t N, int64_t ns, float *__restrict__ out)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < ns) out[i] = w[i * N / ns];
-}
 
 // what the steps and the drivers refuse alike, before any device work
 static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
@@ -341,8 +271,7 @@ static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned 
     for (unsigned c = 0; mode == GC_NORM && c < dim; ++c) h_op[(size_t)cw * GC_K + GC_K + c] = (float)(scale ? scale[c] : 1.0);
     DevBuf<float> op;
     DevBuf<double> part, tot;
-    GLF_TRY(op.alloc(ctx, h_op.size()));
-    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    GLF_TRY(upload_operand(ctx, op, h_op));
     const cluster_kernel kernel = GC_KERNELS[cw == 64][mode];
     const size_t ncols = gc_part_cols(cw, mode);
     int64_t nblk = 0;
@@ -350,12 +279,8 @@ static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned 
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ncols));
     hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)k, op.p, d_weight, d_prev, d_labels, part.p);
     GLF_LAUNCH_CHECK(ctx);
-    GLF_TRY(tot.alloc(ctx, ncols));
-    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
-    GLF_LAUNCH_CHECK(ctx);
-    std::vector<double> h_tot(ncols);
-    GLF_HIP(ctx, hipMemcpyAsync(h_tot.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
+    std::vector<double> h_tot;
+    GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, ncols, tot, h_tot)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
     const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
     for (unsigned j = 0; j < k; ++j) {
         for (unsigned c = 0; c < dim; ++c) h_sums[(size_t)j * dim + c] = h_tot[(size_t)(c / 32) * 1024 + j * 32 + c % 32];
@@ -392,30 +317,25 @@ static int segment_run(const char *name, glf_graph *g, const glf_segment_options
     std::vector<double> cent((size_t)k * dim);
     if (opt->init == 0) {
         const int64_t ns = std::min<int64_t>(opt->sample_rows ? opt->sample_rows : 4096, N);
-        const size_t cnt = (size_t)ns * dim;
-        DevBuf<float> d_rows, d_ws;
+        const unsigned cols = dim + (d_weight ? 1 : 0); // a sampled row: its dim columns of Phi, then its weight
+        const size_t cnt = (size_t)ns * cols;
+        DevBuf<float> d_rows;
         GLF_TRY(d_rows.alloc(ctx, cnt));
-        hipLaunchKernelGGL(k_cluster_sample, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, ns, (int)dim,
-                           d_rows.p);
+        hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, (int)dim, 0,
+                           (const float *)nullptr, d_weight, (int)(cols - dim), ns, d_rows.p);
         GLF_LAUNCH_CHECK(ctx);
-        std::vector<float> h_rows(cnt), h_ws;
+        std::vector<float> h_rows(cnt);
         GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
-        if (d_weight) {
-            GLF_TRY(d_ws.alloc(ctx, (size_t)ns));
-            hipLaunchKernelGGL(k_cluster_sample_w, dim3((unsigned)ceil_div(ns, 256)), dim3(256), 0, ctx->stream, d_weight, N, ns, d_ws.p);
-            GLF_LAUNCH_CHECK(ctx);
-            h_ws.resize((size_t)ns);
-            GLF_HIP(ctx, hipMemcpyAsync(h_ws.data(), d_ws.p, sizeof(float) * (size_t)ns, hipMemcpyDeviceToHost, ctx->stream));
-        }
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        std::vector<double> rows(cnt), ws(h_ws.begin(), h_ws.end());
+        std::vector<double> rows((size_t)ns * dim), ws(d_weight ? (size_t)ns : 0);
         for (int64_t i = 0; i < ns; ++i) {
             double *row = rows.data() + (size_t)i * dim;
             double n2 = 0.0;
             for (unsigned c = 0; c < dim; ++c) {
-                row[c] = (scale ? scale[c] : 1.0) * (double)h_rows[(size_t)i * dim + c];
+                row[c] = (scale ? scale[c] : 1.0) * (double)h_rows[(size_t)i * cols + c];
                 n2 += row[c] * row[c];
             }
+            if (d_weight) ws[(size_t)i] = (double)h_rows[(size_t)i * cols + dim];
             const double rinv = n2 > 0.0 ? 1.0 / std::sqrt(n2) : 0.0;
             for (unsigned c = 0; normalize && c < dim; ++c) row[c] *= rinv;
         }

@@ -1,16 +1,11 @@
 // graph_fit.hip -- the weighted normal equations of a least-squares fit on a graph handle: G = Phi^T diag(w) Phi and
 // b_k = Phi^T diag(w) s_k in one pass over Phi (k_graph_normal), and the host-side Cholesky solve (glf_fit_coeffs).
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace glf {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int GN_CHAIN = GLF_GRAPH_NORMAL_CHAIN; // f32 accumulation runs over at most this many pixel terms
-static_assert(GN_CHAIN % 32 == 0 && GN_CHAIN >= 32 && GN_CHAIN <= 256, "a chain is a whole number of 32-pixel tiles");
 
 // How the [ld][ld] matrix is cut. Tiles are 32 x 32 (one MFMA accumulator); only tiles (ti <= tj) are computed. The columns
 // are grouped into superblocks of CW (64; 32 at ld 32) and blockIdx.y runs over the superblock pairs I <= J: a diagonal pair
@@ -58,16 +53,12 @@ inline bool gn_slot_tile(unsigned ld, int I, int J, int s, int &ti, int &tj)
 
 // partG[blockIdx.x][pair y][slot][32][32] (f64) = sum over the workgroup's pixels of fl32(w Phi[px][i]) Phi[px][j];
 // partB[(blockIdx.x * 4 + wave) * 2 + half][k][LD] (f64) = sum over the wave's pixels of parity `half` of Phi[px][j] (w s_k)[px].
-// One wave per tile of 32 pixels, tiles strided over the grid. The tile's rows are loaded as whole 16-byte pieces in address order
-// and written to the wave's own LDS image [pixel][column] unpadded: v_mfma_f32_32x32x2_f32 takes the pixels as the contraction
-// index, so at step u lane (r, h) reads column r (and 32 + r) of pixel 2u + h for both operands -- consecutive lanes,
-// consecutive floats (ds_read_b32 banks per 32-lane group: no conflict). A = fl32(w phi), B = phi; w = 1 (no weight plane)
-// leaves A = phi exactly. Each accumulator tile is an f32 fma chain over at most GN_CHAIN pixels, then added into its f64 image
-// and cleared. b: t = (double)w (double)s is exact, then fma((double)phi, t, acc) on the values the MFMAs read, one chain per
-// (plane, column, pixel parity): it depends on no other plane, and G on no plane. Rows past N are staged as zeros (w and t
-// too) and never read from memory. No atomics: the partials are summed by k_cols_sum in a fixed order. ld <= 64 keeps two
-// workgroups per CU (the k-steps of a diagonal pair are unrolled by 4, which holds the registers under 256); ld >= 128 carries four
-// accumulator tiles and their f64 images and runs one wave per SIMD.
+// The pixels are the contraction index (phi_tile.hpp: the unpadded image, the chain rule, the four-wave reduction): at step u lane
+// (r, h) reads column r (and 32 + r) of pixel 2u + h for both operands. A = fl32(w phi), B = phi; w = 1 (no weight plane) leaves
+// A = phi exactly. b: t = (double)w (double)s is exact, then fma((double)phi, t, acc) on the values the MFMAs read, one chain per
+// (plane, column, pixel parity): it depends on no other plane, and G on no plane. Rows past N are staged as zeros (w and t too).
+// ld <= 64 keeps two workgroups per CU (the k-steps of a diagonal pair are unrolled by 4, which holds the registers under 256);
+// ld >= 128 carries four accumulator tiles and their f64 images and runs one wave per SIMD.
 template <int LD>
 __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const float *__restrict__ phi, int64_t N, const float *__restrict__ w,
                                                                          int nplanes, const float *__restrict__ planes,
@@ -78,8 +69,6 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
     constexpr int NY = SB * (SB + 1) / 2;
     constexpr int NP = LD >= 128 ? 4 : LD == 64 ? 3 : 1; // accumulator tiles of a workgroup
     constexpr int NIMG = LD >= 128 ? 2 : 1;               // staged images: superblock I, and J when it differs
-    constexpr int FPR = CW / 4;                           // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8;                         // pieces per lane and image: 32 rows x FPR / 64 lanes
     constexpr int RW = NIMG * 32 * CW > 2048 ? NIMG * 32 * CW : 2048; // floats of a wave's region (>= one f64 tile for the epilogue)
     __shared__ __attribute__((aligned(16))) float region[4][RW];
     __shared__ float w_sh[4][32];
@@ -110,50 +99,27 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
     for (int k = 0; k < GLF_MAX_SIGNALS; ++k) bacc[k][0] = bacc[k][1] = 0.0;
 
     // what this lane stages of a tile
-    float4 v[NIMG][NLOAD];
+    float4 v[NIMG][CW / 8];
     float wv = 0.f, sv0 = 0.f, sv1 = 0.f;
     auto load_tile = [&](int64_t tile) {
-        const int64_t base = tile * 32;
 #pragma unroll
         for (int img = 0; img < NIMG; ++img)
-            if (img == 0 || offd) {
-#pragma unroll
-                for (int q = 0; q < NLOAD; ++q) {
-                    const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-                    v[img][q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + (img ? cJ : cI) + c4 * 4)
-                                               : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            }
-        const int64_t px = base + r;
+            if (img == 0 || offd) tile_load<CW>(v[img], phi, LD, img ? cJ : cI, N, tile, lane);
+        const int64_t px = tile * 32 + r;
         const bool live = px < N;
         wv = live ? (w ? w[px] : 1.f) : 0.f;
         sv0 = do_b && live && h < nplanes ? planes[(size_t)h * N + px] : 0.f;
         sv1 = do_b && live && h + 2 < nplanes ? planes[(size_t)(h + 2) * N + px] : 0.f;
-    };
-    auto flush = [&]() {
-#pragma unroll
-        for (int p = 0; p < NP; ++p)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                dacc[p][g] += (double)acc[p][g];
-                acc[p][g] = 0.f;
-            }
     };
 
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     if (tile < ntiles) load_tile(tile);
     int chained = 0; // tiles in the running f32 chains
     for (; tile < ntiles; tile += tstride) {
-        __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
+        __builtin_amdgcn_wave_barrier();
 #pragma unroll
         for (int img = 0; img < NIMG; ++img)
-            if (img == 0 || offd) {
-#pragma unroll
-                for (int q = 0; q < NLOAD; ++q) {
-                    const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-                    *reinterpret_cast<float4 *>(tw + img * 32 * CW + row * CW + c4 * 4) = v[img][q];
-                }
-            }
+            if (img == 0 || offd) tile_put<CW, CW>(tw + img * 32 * CW, v[img], lane);
         if (h == 0) w_sh[wave][r] = wv;
         if (do_b) {
             if (h < nplanes) t_sh[wave][h][r] = (double)wv * (double)sv0;
@@ -202,28 +168,15 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
                 }
             }
         }
-        if (++chained == GN_CHAIN / 32) {
-            flush();
+        if (++chained == CHAIN_TILES) {
+            chain_flush(acc, dacc);
             chained = 0;
         }
     }
-    flush();
+    chain_flush(acc, dacc);
 
-    // the workgroup's four waves, wave 0 first, slot by slot through the waves' regions (one f64 tile each)
     double *const gout = partG + ((size_t)blockIdx.x * NY + blockIdx.y) * NP * 1024;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        __syncthreads();
-        double *mine = reinterpret_cast<double *>(region[wave]);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[p][g];
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 256) {
-            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
-                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
-            gout[(size_t)p * 1024 + e] = s;
-        }
-    }
+    wave_tiles_reduce(region, dacc, wave, r, h, [&](int p, int e, double s) { gout[(size_t)p * 1024 + e] = s; });
     if (do_b) {
         double *bout = partB + ((size_t)(blockIdx.x * 4 + wave) * 2 + h) * nplanes * LD;
 #pragma unroll
@@ -233,15 +186,6 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
                 if constexpr (CW == 64) bout[(size_t)k * LD + cI + 32 + r] = bacc[k][1];
             }
     }
-}
-
-template <int LD>
-static void launch_normal(glf_ctx *ctx, unsigned nblk, const float *d_phi, int64_t N, const float *d_w, int nplanes, const float *d_planes,
-                          double *d_partG, double *d_partB)
-{
-    const GnGeom gm = gn_geom(LD);
-    hipLaunchKernelGGL(k_graph_normal<LD>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes, d_partG,
-                       d_partB);
 }
 
 // h_G [m][m] and h_b [nplanes][m] of Phi [N][ld] (returns with the stream drained)
@@ -255,19 +199,14 @@ int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned
     const size_t gcols = (size_t)gm.ny * gm.slots * 1024, bcols = (size_t)nplanes * ld;
     DevBuf<double> partG, partB, dG, dB;
     GLF_TRY(partG.alloc(ctx, (size_t)nblk * gcols));
-    GLF_TRY(dG.alloc(ctx, gcols));
     GLF_TRY(partB.alloc(ctx, (size_t)nblk * 8 * bcols));
-    GLF_TRY(dB.alloc(ctx, bcols));
-    switch (ld) {
-    case 32: launch_normal<32>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, partG.p, partB.p); break;
-    case 64: launch_normal<64>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, partG.p, partB.p); break;
-    case 128: launch_normal<128>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, partG.p, partB.p); break;
-    case 256: launch_normal<256>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, partG.p, partB.p); break;
-    }
+    dispatch_ld(ld, [&](auto LD) { // (ld is valid)
+        hipLaunchKernelGGL(k_graph_normal<LD.value>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes, partG.p,
+                           partB.p);
+    });
     GLF_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)gcols), dim3(256), 0, ctx->stream, partG.p, (int)nblk, (unsigned)gcols, dG.p);
-    if (nplanes > 0) hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)bcols), dim3(256), 0, ctx->stream, partB.p, (int)nblk * 8, (unsigned)bcols, dB.p);
-    GLF_LAUNCH_CHECK(ctx);
+    GLF_TRY(sum_partials(ctx, partG, (int)nblk, gcols, dG));
+    if (nplanes > 0) GLF_TRY(sum_partials(ctx, partB, (int)nblk * 8, bcols, dB));
     std::vector<double> hG(gcols), hB(bcols);
     GLF_HIP(ctx, hipMemcpyAsync(hG.data(), dG.p, sizeof(double) * gcols, hipMemcpyDeviceToHost, ctx->stream));
     if (nplanes > 0) GLF_HIP(ctx, hipMemcpyAsync(hB.data(), dB.p, sizeof(double) * bcols, hipMemcpyDeviceToHost, ctx->stream));

@@ -1,18 +1,14 @@
 // graph_project.hip -- the wide projection of a graph handle: c_k = Phi^T diag(w) s_k for up to GLF_GRAPH_MAX_PLANES planes in one
 // pass over Phi on the matrix pipe (k_graph_project_wide), the counterpart of k_graph_synthesize's 32 outputs. glf_graph_project and
 // glf_graph_normal_equations keep their own f64 kernels and their bits.
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 
 #include <algorithm>
 
 namespace glf {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int GPW_CHAIN = GLF_GRAPH_NORMAL_CHAIN; // f32 accumulation runs over at most this many pixel terms (k_graph_normal's rule)
 constexpr int GPW_SLOTS = GLF_GRAPH_MAX_PLANES;   // plane slots of one call: one index of the 32 x 32 accumulator tile
 constexpr int GPW_PITCH = 33;                     // floats between two planes of the staged plane image
-static_assert(GPW_CHAIN % 32 == 0 && GPW_CHAIN >= 32, "a chain is a whole number of 32-pixel tiles");
 static_assert(GPW_SLOTS == 32, "the plane slots are the M index of v_mfma_f32_32x32x2_f32");
 
 // How the columns are cut and how many workgroups run along the pixels: fixed per ld, so that the pixel partition and with it the
@@ -33,10 +29,10 @@ inline GpwGeom gpw_geom(unsigned ld)
 // part[blockIdx.x][k][LD] (f64) = sum over the workgroup's pixels of t_k[px] Phi[px][j], t_k = fl32(w s_k) (w NULL: s_k itself), for the
 // columns j of the workgroup's group and every plane k < nplanes.
 //
-// Arithmetic. v_mfma_f32_32x32x2_f32 with the pixels as the contraction index: A = t (M index: the 32 plane slots), B = Phi as
-// stored (N index: 32 columns), so the accumulator of lane (r, h) holds column r of the tile for the planes (g & 3) + 8 (g >> 2) + 4 h,
-// g < 16. Every element is its own f32 fma chain over the wave's pixels in ascending order: it depends on no other plane and on no
-// other column. A chain runs over at most GPW_CHAIN pixel terms (GPW_CHAIN / 32 tiles), is then added into its f64 image and cleared.
+// Arithmetic. The pixels are the contraction index (phi_tile.hpp: the unpadded image, the chain rule, the four-wave reduction):
+// A = t (M index: the 32 plane slots), B = Phi as stored (N index: 32 columns), so the accumulator of lane (r, h) holds column r of the
+// tile for the planes acc_row(g, h), g < 16. Every element is its own f32 fma chain over the wave's pixels in ascending order: it
+// depends on no other plane and on no other column.
 // Plane slots >= nplanes are staged as zeros and never read from memory; rows past N are staged as zeros (Phi, w and the planes).
 //
 // The split and the traffic. An accumulator tile and its f64 image are 48 registers per (32 columns x 32 planes): a wave holds at
@@ -44,17 +40,14 @@ inline GpwGeom gpw_geom(unsigned ld)
 // A group reads its own columns of Phi only, and the planes and w once per group: Phi is read once at every ld, the planes once at
 // ld <= 128 and twice at ld 256 (per pixel 4 LD + 128 (LD / CW) + 4 (LD / CW) bytes with all 32 planes and a weight plane).
 //
-// Staging. One wave per tile of 32 pixels, tiles strided over the grid; the next tile's loads are issued under the current tile's
-// MFMAs. Phi: whole 16-byte pieces in address order into the wave's own LDS image [pixel][column], unpadded, read at step u by lane
-// (r, h) as column 32 c + r of pixel 2 u + h -- consecutive lanes, consecutive floats. The planes: a tile is 32 runs of 128 contiguous
-// bytes, one per plane; lane (r, h) loads pixel r of the planes 2 q + h (a half-wave reads one run; dword loads, since a plane's start
-// is only 4-byte aligned when N is odd) and writes t to img[plane * 33 + r]. The operand read is img[r * 33 + px], plane r of one pixel
-// per half-wave. The bank of a ds_read_b32 / ds_write_b32 is the dword address mod 32 and only the 32 lanes of a half-wave conflict
-// with one another: at a pitch of 32 the 32 planes of one pixel would sit on one bank (32-way); at 33 the bank is (r + px) mod 32,
-// one lane per bank, and the writes (consecutive r at a fixed plane) are consecutive dwords. So both directions are conflict-free.
+// Staging the planes. A tile is 32 runs of 128 contiguous bytes, one per plane; lane (r, h) loads pixel r of the planes 2 q + h (a
+// half-wave reads one run; dword loads, since a plane's start is only 4-byte aligned when N is odd) and writes t to
+// img[plane * 33 + r]. The operand read is img[r * 33 + px], plane r of one pixel per half-wave. The bank of a ds_read_b32 /
+// ds_write_b32 is the dword address mod 32 and only the 32 lanes of a half-wave conflict with one another: at a pitch of 32 the 32
+// planes of one pixel would sit on one bank (32-way); at 33 the bank is (r + px) mod 32, one lane per bank, and the writes
+// (consecutive r at a fixed plane) are consecutive dwords. So both directions are conflict-free.
 //
-// Reduction. No atomics: the four waves' f64 images are added in a fixed order through LDS, the workgroups by k_cols_sum. ld <= 64
-// runs two workgroups per CU; ld >= 128 carries four tiles and their images and runs one wave per SIMD.
+// ld <= 64 runs two workgroups per CU; ld >= 128 carries four tiles and their images and runs one wave per SIMD.
 template <int LD>
 __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(const float *__restrict__ phi, int64_t N, const float *__restrict__ w,
                                                                                 int nplanes, const float *__restrict__ planes,
@@ -62,8 +55,6 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
 {
     constexpr int CW = LD < 128 ? LD : 128;
     constexpr int NT = CW / 32;   // accumulator tiles of a wave
-    constexpr int FPR = CW / 4;   // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8; // pieces per lane: 32 rows x FPR / 64 lanes
     constexpr int NPL = GPW_SLOTS / 2; // planes per lane: 32 slots / 2 half-waves
     constexpr int RW = 32 * CW + 32 * GPW_PITCH; // floats of a wave's region: the Phi image, then the plane image
     static_assert(RW >= 2048 && RW % 4 == 0, "a region holds one f64 tile for the epilogue and keeps the next one 16-byte aligned");
@@ -86,17 +77,12 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
         }
 
     // what this lane stages of a tile
-    float4 v[NLOAD];
+    float4 v[CW / 8];
     float sv[NPL];
     float wv = 0.f;
     auto load_tile = [&](int64_t tile) {
-        const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + c0 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        const int64_t px = base + r;
+        tile_load<CW>(v, phi, LD, c0, N, tile, lane);
+        const int64_t px = tile * 32 + r;
         const bool live = px < N;
         wv = live && w ? w[px] : 0.f;
 #pragma unroll
@@ -105,26 +91,13 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
             sv[q] = live && k < nplanes ? planes[(size_t)k * N + px] : 0.f;
         }
     };
-    auto flush = [&]() {
-#pragma unroll
-        for (int c = 0; c < NT; ++c)
-#pragma unroll
-            for (int g = 0; g < 16; ++g) {
-                dacc[c][g] += (double)acc[c][g];
-                acc[c][g] = 0.f;
-            }
-    };
 
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     if (tile < ntiles) load_tile(tile);
     int chained = 0; // tiles in the running f32 chains
     for (; tile < ntiles; tile += tstride) {
-        __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            *reinterpret_cast<float4 *>(tw + row * CW + c4 * 4) = v[q];
-        }
+        __builtin_amdgcn_wave_barrier();
+        tile_put<CW, CW>(tw, v, lane);
 #pragma unroll
         for (int q = 0; q < NPL; ++q) img[(2 * q + h) * GPW_PITCH + r] = w ? wv * sv[q] : sv[q];
         __builtin_amdgcn_wave_barrier();
@@ -137,37 +110,19 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
 #pragma unroll
             for (int c = 0; c < NT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, tw[px * CW + c * 32 + r], acc[c], 0, 0, 0);
         }
-        if (++chained == GPW_CHAIN / 32) {
-            flush();
+        if (++chained == CHAIN_TILES) {
+            chain_flush(acc, dacc);
             chained = 0;
         }
     }
-    flush();
+    chain_flush(acc, dacc);
 
-    // the workgroup's four waves, wave 0 first, tile by tile through the waves' regions (one f64 tile [plane][column] each)
+    // one f64 tile [plane][column] per 32 columns
     double *const pout = part + (size_t)blockIdx.x * nplanes * LD + c0;
-#pragma unroll
-    for (int c = 0; c < NT; ++c) {
-        __syncthreads();
-        double *mine = reinterpret_cast<double *>(region[wave]);
-#pragma unroll
-        for (int g = 0; g < 16; ++g) mine[((g & 3) + 8 * (g >> 2) + 4 * h) * 32 + r] = dacc[c][g];
-        __syncthreads();
-        for (int e = threadIdx.x; e < 1024; e += 256) {
-            const double s = ((reinterpret_cast<const double *>(region[0])[e] + reinterpret_cast<const double *>(region[1])[e]) +
-                              reinterpret_cast<const double *>(region[2])[e]) + reinterpret_cast<const double *>(region[3])[e];
-            const int k = e >> 5, j = e & 31;
-            if (k < nplanes) pout[(size_t)k * LD + c * 32 + j] = s;
-        }
-    }
-}
-
-template <int LD>
-static void launch_project_wide(glf_ctx *ctx, unsigned nblk, const float *d_phi, int64_t N, const float *d_w, int nplanes, const float *d_planes,
-                                double *d_part)
-{
-    const GpwGeom gm = gpw_geom(LD);
-    hipLaunchKernelGGL(k_graph_project_wide<LD>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes, d_part);
+    wave_tiles_reduce(region, dacc, wave, r, h, [&](int c, int e, double s) {
+        const int k = e >> 5, j = e & 31;
+        if (k < nplanes) pout[(size_t)k * LD + c * 32 + j] = s;
+    });
 }
 
 // h_c [nplanes][m] of Phi [N][ld] (returns with the stream drained; h_c is written only on success)
@@ -181,19 +136,13 @@ static int graph_project_wide(glf_ctx *ctx, const float *d_phi, int64_t N, unsig
     const size_t ncols = (size_t)nplanes * ld;
     DevBuf<double> part, tot;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ncols));
-    GLF_TRY(tot.alloc(ctx, ncols));
-    switch (ld) {
-    case 32: launch_project_wide<32>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, part.p); break;
-    case 64: launch_project_wide<64>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, part.p); break;
-    case 128: launch_project_wide<128>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, part.p); break;
-    case 256: launch_project_wide<256>(ctx, nblk, d_phi, N, d_w, nplanes, d_planes, part.p); break;
-    }
+    dispatch_ld(ld, [&](auto LD) { // (ld is valid)
+        hipLaunchKernelGGL(k_graph_project_wide<LD.value>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes,
+                           part.p);
+    });
     GLF_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(k_cols_sum, dim3((unsigned)ncols), dim3(256), 0, ctx->stream, part.p, (int)nblk, (unsigned)ncols, tot.p);
-    GLF_LAUNCH_CHECK(ctx);
-    std::vector<double> hc(ncols);
-    GLF_HIP(ctx, hipMemcpyAsync(hc.data(), tot.p, sizeof(double) * ncols, hipMemcpyDeviceToHost, ctx->stream));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<double> hc;
+    GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, ncols, tot, hc));
     for (int k = 0; k < nplanes; ++k)
         for (unsigned j = 0; j < m; ++j) h_c[(size_t)k * m + j] = hc[(size_t)k * ld + j];
     return GLF_OK;

@@ -7,7 +7,7 @@
 // Out of scope: per-plane independent weights in one call, a device-side median, L1 / total-variation terms, m > 256, contexts with a
 // communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_graph_normal,
 // k_graph_synthesize, k_graph_cluster and k_graph_transform.
-#include "glf_internal.hpp"
+#include "phi_tile.hpp"
 #include "robust_loss.hpp"
 
 #include <algorithm>
@@ -18,8 +18,6 @@
 #pragma clang fp contract(off)
 
 namespace glf {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GR_OUT = GLF_MAX_SIGNALS; // residual planes = the first rows of the M index
 static_assert(GR_OUT == 4, "accumulator registers 0..3 of half-wave 0 hold the planes");
@@ -43,14 +41,12 @@ __device__ inline float robust_u32(int kind, float q, float cf, float c2, float 
 }
 
 // res_k[px] = s_k[px] - sum_c Phi[px][c] fl32(a_k[c]) for the planes k < nplanes, and from them the IRLS weight of the pixel, in one
-// pass over Phi. The contraction is k_graph_synthesize's, instruction for instruction: one wave per tile of 32 pixels,
-// v_mfma_f32_32x32x2_f32 with the planes as the M index (A: the coefficients, operand [LD][4] float with fl32(a_k[c]) at [c][k], read
-// from LDS by the lanes r < 4, zero in the others) and the pixels as the N index (B: Phi, the wave's LDS image with the row pitch
-// padded by 4 floats, one pixel per lane as float4s), chunk by chunk of CW columns, half-wave h taking columns h CW / 2 + t of the
-// chunk at step t. Register k of lane (r, 0) then holds d_k of pixel r with the bits glf_graph_synthesize gives for a_k with no
+// pass over Phi. The contraction is k_graph_synthesize's, the same chunk_contract (phi_tile.hpp): the planes are the M index (A: the
+// coefficients, operand [LD][4] float with fl32(a_k[c]) at [c][k], read from LDS by the lanes r < 4, zero in the others), the pixels
+// the N index. Register k of lane (r, 0) then holds d_k of pixel r with the bits glf_graph_synthesize gives for a_k with no
 // identity term. Epilogue, lanes of half 0, in f32: res_k = s_k - d_k, x_k = res_k isig_k, q = fmaf(x_k, x_k, q) in ascending k,
 // u = robust_u32(q), w_eff = w u; rho in f64 from (double) q (robust_rho, the host table's own statement), loss += (double) w rho and
-// mass += (double) w_eff per lane. Rows past N are staged as zeros, and neither read nor stored nor summed.
+// mass += (double) w_eff per lane. Rows past N are neither read nor stored nor summed.
 // part[blockIdx.x][2] = (loss, mass) of the workgroup: the lanes of wave 0 first, in ascending lane order; no atomics, the
 // workgroups are added by k_cols_sum.
 template <int LD>
@@ -61,8 +57,6 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__re
 {
     constexpr int CW = LD < 64 ? LD : 64; // columns staged per pass
     constexpr int PITCH = CW + 4;
-    constexpr int FPR = CW / 4;           // float4 pieces per staged row
-    constexpr int NLOAD = CW / 8;         // pieces per lane: 32 rows x FPR / 64 lanes
     __shared__ __attribute__((aligned(16))) float a_sh[LD * GR_OUT];
     __shared__ __attribute__((aligned(16))) float tile_sh[4][32 * PITCH];
     __shared__ double red_sh[2][4][32];
@@ -70,22 +64,12 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__re
     for (int e = threadIdx.x; e < LD * GR_OUT; e += 256) a_sh[e] = operand[e];
     __syncthreads();
     const int r = lane & 31, h = lane >> 5;
-    const bool arow = r < GR_OUT; // this lane's row of A is a plane
     float *tw = tile_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
     double loss = 0.0, mass = 0.0;
-    // the pieces this lane stages of chunk ch of a tile: rows past N as zeros
-    float4 v[NLOAD];
-    auto load_chunk = [&](int64_t tile, int ch) {
-        const int64_t base = tile * 32;
-#pragma unroll
-        for (int q = 0; q < NLOAD; ++q) {
-            const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-            v[q] = base + row < N ? *reinterpret_cast<const float4 *>(phi + (size_t)(base + row) * LD + ch * CW + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
+    float4 v[CW / 8];
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile < ntiles) load_chunk(tile, 0);
+    if (tile < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile, lane);
     for (; tile < ntiles; tile += tstride) {
         // the pixel's planes and weight fly under the tile's MFMAs
         const int64_t px = tile * 32 + r;
@@ -95,31 +79,14 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__re
         for (int k = 0; k < GR_OUT; ++k) sv[k] = live && k < nplanes ? planes[(size_t)k * N + px] : 0.f;
         if (live && w) wv = w[px];
         f32x16 acc;
-#pragma unroll
-        for (int g = 0; g < 16; ++g) acc[g] = 0.f;
+        acc_clear(acc);
 #pragma unroll 1
         for (int ch = 0; ch < LD / CW; ++ch) {
-            __builtin_amdgcn_wave_barrier(); // (the wave's reads of the previous image precede these writes: LDS runs in order per wave)
-#pragma unroll
-            for (int q = 0; q < NLOAD; ++q) {
-                const int e = q * 64 + lane, row = e / FPR, c4 = e % FPR;
-                *reinterpret_cast<float4 *>(tw + row * PITCH + c4 * 4) = v[q];
-            }
-            __builtin_amdgcn_wave_barrier();
+            tile_store<CW, PITCH>(tw, v, lane);
             // the next chunk's loads fly under this chunk's MFMAs
-            if (ch + 1 < LD / CW) load_chunk(tile, ch + 1);
-            else if (tile + tstride < ntiles) load_chunk(tile + tstride, 0);
-#pragma unroll
-            for (int u = 0; u < CW / 8; ++u) {
-                const float4 b = *reinterpret_cast<const float4 *>(tw + r * PITCH + h * (CW / 2) + 4 * u);
-                const float *ak = a_sh + (size_t)(ch * CW + h * (CW / 2) + 4 * u) * GR_OUT + (r & (GR_OUT - 1));
-                const float a0 = arow ? ak[0 * GR_OUT] : 0.f, a1 = arow ? ak[1 * GR_OUT] : 0.f;
-                const float a2 = arow ? ak[2 * GR_OUT] : 0.f, a3 = arow ? ak[3 * GR_OUT] : 0.f;
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b.y, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b.z, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a3, b.w, acc, 0, 0, 0);
-            }
+            if (ch + 1 < LD / CW) tile_load<CW>(v, phi, LD, (ch + 1) * CW, N, tile, lane);
+            else if (tile + tstride < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile + tstride, lane);
+            chunk_contract<CW, GR_OUT>(acc, tw, a_sh + (size_t)(ch * CW) * GR_OUT, r, h);
         }
         if (live) {
             float q = 0.f;
@@ -164,20 +131,6 @@ static int launch_residual_weight(glf_ctx *ctx, int *per_cu, int64_t *nblk, DevB
     return GLF_OK;
 }
 
-// out[i][0 .. m) = Phi[px_i][0 .. m), out[i][m + k] = s_k[px_i], out[i][m + nplanes] = w[px_i] (1 without a weight plane),
-// px_i = floor(i N / ns): the sample of rows the scale estimate reads
-__global__ void k_robust_sample(const float *__restrict__ phi, int64_t N, int ld, int m, int nplanes, const float *__restrict__ planes,
-                                const float *__restrict__ w, int64_t ns, float *__restrict__ out)
-{
-    const int cols = m + nplanes + 1;
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= ns * cols) return;
-    const int64_t i = e / cols;
-    const int c = (int)(e % cols);
-    const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
-    out[e] = c < m ? phi[(size_t)px * ld + c] : c < m + nplanes ? planes[(size_t)(c - m) * N + px] : w ? w[px] : 1.f;
-}
-
 // what the step and the driver refuse alike, before any device work
 static bool loss_shape_ok(const glf_robust_loss *loss, int nplanes, bool with_sigma)
 {
@@ -212,26 +165,20 @@ static int robust_step(glf_graph *g, const RobustConst &rc, const float *d_w, in
         for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GR_OUT + j] = (float)h_a[(size_t)j * m + k];
     DevBuf<float> op, weff;
     DevBuf<double> part, tot;
-    GLF_TRY(op.alloc(ctx, h_op.size()));
-    GLF_HIP(ctx, hipMemcpyAsync(op.p, h_op.data(), sizeof(float) * h_op.size(), hipMemcpyHostToDevice, ctx->stream));
+    GLF_TRY(upload_operand(ctx, op, h_op));
     if (!d_weight_out) {
         GLF_TRY(weff.alloc(ctx, (size_t)N));
         d_weight_out = weff.p;
     }
     int64_t nblk = 0;
     int rc_launch = GLF_ERR_INVALID;
-    switch (ld) {
-    case 32: rc_launch = launch_residual_weight<32>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes, d_weight_out, d_res_out); break;
-    case 64: rc_launch = launch_residual_weight<64>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes, d_weight_out, d_res_out); break;
-    case 128: rc_launch = launch_residual_weight<128>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes, d_weight_out, d_res_out); break;
-    case 256: rc_launch = launch_residual_weight<256>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes, d_weight_out, d_res_out); break;
-    }
+    dispatch_ld(ld, [&](auto LD) {
+        rc_launch = launch_residual_weight<LD.value>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes,
+                                                     d_weight_out, d_res_out);
+    });
     GLF_TRY(rc_launch);
-    GLF_TRY(tot.alloc(ctx, 2));
-    hipLaunchKernelGGL(k_cols_sum, dim3(2), dim3(256), 0, ctx->stream, part.p, (int)nblk, 2u, tot.p);
-    GLF_LAUNCH_CHECK(ctx);
-    double h_tot[2] = {0.0, 0.0};
-    GLF_HIP(ctx, hipMemcpyAsync(h_tot, tot.p, sizeof(h_tot), hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> h_tot;
+    GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, 2, tot, h_tot, false));
     // the second pass: G and b under w_eff, by the weighted fit's own kernel (it drains the stream; h_op and h_tot are then settled)
     GLF_TRY(graph_normal_equations(ctx, g->phi, N, m, ld, d_weight_out, nplanes, d_planes, h_G, h_b));
     if (h_loss) *h_loss = h_tot[0];
@@ -306,8 +253,8 @@ int glf_graph_fit_robust(glf_graph *g, const glf_robust_options *opt, const floa
         const size_t cnt = (size_t)ns * cols;
         DevBuf<float> d_rows;
         GLF_TRY(d_rows.alloc(ctx, cnt));
-        hipLaunchKernelGGL(k_robust_sample, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)m, nplanes,
-                           d_planes, d_w, ns, d_rows.p);
+        hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)m, nplanes,
+                           d_planes, d_w, 1, ns, d_rows.p);
         GLF_LAUNCH_CHECK(ctx);
         std::vector<float> h_rows(cnt);
         GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
