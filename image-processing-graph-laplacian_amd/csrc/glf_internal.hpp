@@ -110,7 +110,11 @@ struct glf_graph {
     glf_ctx *ctx = nullptr;
     int pix = 0, width = 0, height = 0;
     unsigned p = 0, m = 0, ld = 0;
-    float *phi = nullptr;      // device [N][ld], raster rows (glf_malloc: not a block of the workspace pool)
+    float *phi = nullptr;      // device [N][ld], raster rows (glf_malloc: not a block of the workspace pool); NULL once compact
+    int storage = GLF_PHI_F32; // GLF_PHI_F16 after glf_graph_compact (graph_compact.hip): phi16, expo and d_expo then hold the handle's Phi
+    void *phi16 = nullptr;     // device __half [N][ld], raster rows (glf_malloc)
+    std::vector<int32_t> expo; // [ld] the column exponents e_c: the handle stands for Q[px][c] = 2^e_c phi16[px][c]
+    int32_t *d_expo = nullptr; // device [ld], the same (glf_malloc): the row gathers of the drivers read it
     std::vector<double> lam;   // [m]
     std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
     int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
@@ -816,5 +820,8 @@ int filter_finish(glf_ctx *ctx, const uint8_t *d_img, const float *d_acc, int64_
 // (d_w NULL: w = 1; nplanes 0: no planes); returns with the stream drained
 int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
                            const float *d_planes, double *h_G, double *h_b);
+// ... of a handle of either storage: on a compact one the f16 instance forms them on the stored halves, and the column scales are
+// folded into the read-back in f64 (G[i][j] 2^(e_i + e_j), b_k[c] 2^e_c: the bits of the f32 pass over Q)
+int graph_normal_equations(const glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_G, double *h_b);
 
 } // namespace glf

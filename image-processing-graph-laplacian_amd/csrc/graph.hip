@@ -2,6 +2,7 @@
 // c = Phi^T s and syntheses out = ident s + Phi a on it. The build is the format's capture call with the handle's Phi as the
 // capture target; Phi^T s and Phi^T Phi are filter.hip's phi_t_signals / phi_gram; the synthesis is the one new kernel.
 #include "phi_tile.hpp"
+#include "phi_compact.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -22,8 +23,9 @@ inline size_t gs_operand_floats(unsigned ld) { return (size_t)ld * GS_OUT + 2 * 
 // register g of the accumulator holds, in the 32 lanes of half h, 32 consecutive pixels of output acc_row(g, h). The contraction index
 // is visited chunk by chunk of CW columns in chunk_contract's order, which does not depend on nout, and every output is its own
 // k-ordered fma chain: its bits do not depend on the outputs beside it. Rows past N are neither read nor stored.
-template <int LD>
-__global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restrict__ phi, int64_t N, int nout, const float *__restrict__ operand,
+// T: the element type of Phi (float, or __half on a compact handle: phi_tile.hpp's second loader, the same image).
+template <int LD, class T = float>
+__global__ __launch_bounds__(256) void k_graph_synthesize(const T *__restrict__ phi, int64_t N, int nout, const float *__restrict__ operand,
                                                            const float *__restrict__ planes, float *__restrict__ out)
 {
     constexpr int CW = LD < 64 ? LD : 64; // columns staged per pass
@@ -42,7 +44,7 @@ __global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restric
     const int r = lane & 31, h = lane >> 5;
     float *tw = tile_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
-    float4 v[CW / 8];
+    tile_regs<T, CW> v;
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     if (tile < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile, lane);
     for (; tile < ntiles; tile += tstride) {
@@ -72,18 +74,19 @@ __global__ __launch_bounds__(256) void k_graph_synthesize(const float *__restric
     }
 }
 
-template <int LD>
-static int launch_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, int nout, const float *d_operand, const float *d_planes,
+template <int LD, class T>
+static int launch_synthesize(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, int nout, const float *d_operand, const float *d_planes,
                              float *d_out)
 {
     int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_synthesize<LD>, N, &nblk));
-    hipLaunchKernelGGL(k_graph_synthesize<LD>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, nout, d_operand, d_planes, d_out);
+    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_synthesize<LD, T>, N, &nblk));
+    hipLaunchKernelGGL((k_graph_synthesize<LD, T>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, nout, d_operand, d_planes, d_out);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
 
-static int graph_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64_t N, unsigned ld, int nout, const float *d_operand,
+template <class T>
+static int graph_synthesize(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, unsigned ld, int nout, const float *d_operand,
                             const float *d_planes, float *d_out)
 {
     int rc = GLF_OK;
@@ -92,8 +95,9 @@ static int graph_synthesize(glf_ctx *ctx, int *per_cu, const float *d_phi, int64
     return rc;
 }
 
-__global__ void k_sample_rows(const float *__restrict__ phi, int64_t N, int ld, int dim, int nplanes, const float *__restrict__ planes,
-                              const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out)
+template <class T>
+__global__ void k_sample_rows(const T *__restrict__ phi, const int *__restrict__ expo, int64_t N, int ld, int dim, int nplanes,
+                              const float *__restrict__ planes, const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out)
 {
     const int cols = dim + nplanes + wcol;
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -101,7 +105,25 @@ __global__ void k_sample_rows(const float *__restrict__ phi, int64_t N, int ld, 
     const int64_t i = e / cols;
     const int c = (int)(e % cols);
     const int64_t px = i * N / ns; // (i < ns <= N < 2^31)
-    out[e] = c < dim ? phi[(size_t)px * ld + c] : c < dim + nplanes ? planes[(size_t)(c - dim) * N + px] : w ? w[px] : 1.f;
+    float x = 0.f;
+    if (c < dim) {
+        if constexpr (std::is_same<T, float>::value) x = phi[(size_t)px * ld + c];
+        else x = ldexpf(__half2float(phi[(size_t)px * ld + c]), expo[c]); // Q, exact
+    }
+    out[e] = c < dim ? x : c < dim + nplanes ? planes[(size_t)(c - dim) * N + px] : w ? w[px] : 1.f;
+}
+
+int graph_sample_rows(glf_graph *g, int dim, int nplanes, const float *d_planes, const float *d_w, int wcol, int64_t ns, float *d_out)
+{
+    glf_ctx *ctx = g->ctx;
+    const int64_t N = (int64_t)g->width * g->height, cnt = ns * (dim + nplanes + wcol);
+    dispatch_phi(g, [&](auto *phi) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>;
+        hipLaunchKernelGGL(k_sample_rows<T>, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, ctx->stream, phi, (const int *)g->d_expo, N, (int)g->ld, dim,
+                           nplanes, d_planes, d_w, wcol, ns, d_out);
+    });
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
 }
 
 } // namespace glf
@@ -115,6 +137,14 @@ int glf_graph_destroy(glf_graph *g)
     if (!g) return GLF_OK;
     int rc = GLF_OK;
     if (g->phi) rc = glf_free(g->ctx, g->phi);
+    if (g->phi16) {
+        const int rc16 = glf_free(g->ctx, g->phi16);
+        rc = rc != GLF_OK ? rc : rc16;
+    }
+    if (g->d_expo) {
+        const int rce = glf_free(g->ctx, g->d_expo);
+        rc = rc != GLF_OK ? rc : rce;
+    }
     delete g;
     return rc;
 }
@@ -222,7 +252,7 @@ int glf_graph_get_info(const glf_graph *g, glf_graph_info *info)
     info->m = g->m;
     info->ld = g->ld;
     info->d_phi = g->phi;
-    info->phi_bytes = sizeof(float) * (size_t)g->width * g->height * g->ld;
+    info->phi_bytes = (g->storage == GLF_PHI_F16 ? sizeof(__half) : sizeof(float)) * (size_t)g->width * g->height * g->ld;
     return GLF_OK;
 }
 
@@ -237,6 +267,13 @@ int glf_graph_gram(glf_graph *g, double *G)
 {
     if (!g || !G) return GLF_ERR_INVALID;
     const unsigned m = g->m, ld = g->ld;
+    if (g->gram.empty() && g->storage == GLF_PHI_F16) {
+        // a compact handle: the normal-equations pass with w = NULL (no earlier bits to keep)
+        GLF_ENTER(g->ctx);
+        std::vector<double> hG((size_t)m * m);
+        GLF_TRY(graph_normal_equations(g, nullptr, 0, nullptr, hG.data(), nullptr));
+        g->gram.swap(hG);
+    }
     if (g->gram.empty()) {
         glf_ctx *ctx = g->ctx;
         GLF_ENTER(ctx);
@@ -260,6 +297,8 @@ int glf_graph_project(glf_graph *g, int nplanes, const float *d_planes, double *
     glf_ctx *ctx = g->ctx;
     const unsigned m = g->m, ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
+    if (g->storage != GLF_PHI_F32)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_project: the handle is compact (its f64-chain kernel reads an f32 Phi): use glf_graph_project_wide");
     GLF_ENTER(ctx);
     DevBuf<double> c;
     GLF_TRY(c.alloc(ctx, (size_t)nplanes * ld));
@@ -286,11 +325,14 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float 
     const unsigned m = g->m, ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
     GLF_ENTER(ctx);
+    // (a compact handle: the column scales folded into the coefficients in f64, before their fl32)
+    std::vector<double> a(h_a, h_a + (size_t)nout * m);
+    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)nout, m, g->expo.data());
     std::vector<float> h_op(gs_operand_floats(ld), 0.f);
     int h_plane[GS_OUT];
     for (int j = 0; j < GS_OUT; ++j) h_plane[j] = -1;
     for (int j = 0; j < nout; ++j) {
-        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GS_OUT + j] = (float)h_a[(size_t)j * m + k];
+        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GS_OUT + j] = (float)a[(size_t)j * m + k];
         if (plane[j] >= 0) {
             h_op[(size_t)ld * GS_OUT + j] = ident[j];
             h_plane[j] = plane[j];
@@ -299,7 +341,9 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float 
     std::memcpy(h_op.data() + (size_t)ld * GS_OUT + GS_OUT, h_plane, sizeof(h_plane));
     DevBuf<float> op;
     GLF_TRY(upload_operand(ctx, op, h_op));
-    GLF_TRY(graph_synthesize(ctx, &g->synth_blocks_per_cu, g->phi, N, ld, nout, op.p, d_planes, d_out));
+    int rc = GLF_OK;
+    dispatch_phi(g, [&](auto *phi) { rc = graph_synthesize(ctx, &g->synth_blocks_per_cu, phi, N, ld, nout, op.p, d_planes, d_out); });
+    GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)
     return GLF_OK;
 }
@@ -309,7 +353,7 @@ int glf_graph_normal_equations(glf_graph *g, const float *d_w, int nplanes, cons
     if (!g || !h_G || nplanes < 0 || nplanes > GLF_MAX_SIGNALS || (nplanes > 0 && (!d_planes || !h_b))) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
     GLF_ENTER(ctx);
-    return graph_normal_equations(ctx, g->phi, (int64_t)g->width * g->height, g->m, g->ld, d_w, nplanes, d_planes, h_G, h_b);
+    return graph_normal_equations(g, d_w, nplanes, d_planes, h_G, h_b);
 }
 
 int glf_filter_coeffs(const glf_options *opt_in, unsigned m, const double *lam, const double *gram, const double *c, double *a, float *ident)

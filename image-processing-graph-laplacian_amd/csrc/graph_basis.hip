@@ -185,6 +185,8 @@ int glf_graph_transform(glf_graph *g, unsigned m_new, const double *h_T, const d
     if (!g || !h_T || !h_lam_new) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
     const unsigned m = g->m, ld = g->ld;
+    if (g->storage != GLF_PHI_F32)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_transform: the handle is compact (compaction is the last step of preparing a handle: transform first)");
     if (m_new == 0 || m_new > m) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_transform: m_new=%u (m=%u)", m_new, m);
     if (!all_finite(h_T, (size_t)m * m_new) || !all_finite(h_lam_new, m_new))
         return set_error(ctx, GLF_ERR_INVALID, "glf_graph_transform: an entry of T or lam_new that is not finite");
@@ -216,6 +218,9 @@ int glf_graph_orthonormalize(glf_graph *g, int mode, int passes, int verify, glf
 {
     if (!g) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
+    if (g->storage != GLF_PHI_F32)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED,
+                         "glf_graph_orthonormalize: the handle is compact (compaction is the last step of preparing a handle: orthonormalize first)");
     if ((mode != GLF_BASIS_CHOLESKY && mode != GLF_BASIS_RITZ) || passes < 1 || passes > 2 || (stats && stats->struct_size != sizeof(glf_basis_stats)))
         return set_error(ctx, GLF_ERR_INVALID, "glf_graph_orthonormalize: mode=%d passes=%d struct_size=%u (want %zu)", mode, passes,
                          stats ? stats->struct_size : 0u, sizeof(glf_basis_stats));

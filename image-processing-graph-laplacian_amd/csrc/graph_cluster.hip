@@ -7,6 +7,7 @@
 // contexts with a communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_band,
 // k_graph_synthesize and k_graph_normal.
 #include "phi_tile.hpp"
+#include "phi_compact.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -60,8 +61,9 @@ inline size_t gc_part_cols(int cw, int mode) { return (size_t)(cw / 32) * 1024 +
 //   GC_WEIGHT and GC_NORM: t(px) and w(px) go to LDS beside the tile's 32 labels (w is loaded with the prefetch of the next tile,
 //   as prev is), and lane (r, h) adds (double) w[p] over its hits: the mass of label r among the pixels of parity h. Counts and
 //   changed stay integers.
-template <int CW, int MODE>
-__global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
+// T: the element type of Phi (float, or __half on a compact handle: phi_tile.hpp's second loader, the same image).
+template <int CW, int MODE, class T = float>
+__global__ __launch_bounds__(256, 2) void k_graph_cluster(const T *__restrict__ phi, int64_t N, int ld, int k, const float *__restrict__ operand,
                                                           const float *__restrict__ weight, const int32_t *prev, int32_t *labels,
                                                           double *__restrict__ part)
 {
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
     double mass = 0.0;
 
     // what this lane stages of a tile: rows past N as zeros
-    float4 v[CW / 8];
+    tile_regs<T, CW> v;
     int pv = 0;
     float wv = 1.f;
     auto load_tile = [&](int64_t tile) {
@@ -231,10 +233,31 @@ __global__ __launch_bounds__(256, 2) void k_graph_cluster(const float *__restric
     }
 }
 
-// the six instances, at [CW == 64][mode]
-using cluster_kernel = decltype(&k_graph_cluster<32, GC_PLAIN>);
-static const cluster_kernel GC_KERNELS[2][GC_MODES] = {{k_graph_cluster<32, GC_PLAIN>, k_graph_cluster<32, GC_WEIGHT>, k_graph_cluster<32, GC_NORM>},
-                                                       {k_graph_cluster<64, GC_PLAIN>, k_graph_cluster<64, GC_WEIGHT>, k_graph_cluster<64, GC_NORM>}};
+// the six instances of a storage, at [CW == 64][mode]
+template <class T>
+using cluster_kernel = decltype(&k_graph_cluster<32, GC_PLAIN, T>);
+template <class T>
+static cluster_kernel<T> gc_kernel(int cw, int mode)
+{
+    static const cluster_kernel<T> kernels[2][GC_MODES] = {
+        {k_graph_cluster<32, GC_PLAIN, T>, k_graph_cluster<32, GC_WEIGHT, T>, k_graph_cluster<32, GC_NORM, T>},
+        {k_graph_cluster<64, GC_PLAIN, T>, k_graph_cluster<64, GC_WEIGHT, T>, k_graph_cluster<64, GC_NORM, T>}};
+    return kernels[cw == 64][mode];
+}
+
+// the launch of one Lloyd iteration on Phi as stored (queued)
+template <class T>
+static int launch_cluster(glf_graph *g, const T *d_phi, int cw, int mode, int64_t N, unsigned k, const float *d_op, const float *d_weight,
+                          const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, int64_t *nblk)
+{
+    glf_ctx *ctx = g->ctx;
+    const cluster_kernel<T> kernel = gc_kernel<T>(cw, mode);
+    GLF_TRY(resident_tile_grid(ctx, &g->cluster_blocks_per_cu[mode], kernel, N, nblk));
+    GLF_TRY(part.alloc(ctx, (size_t)*nblk * gc_part_cols(cw, mode)));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)*nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)g->ld, (int)k, d_op, d_weight, d_prev, d_labels, part.p);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
 
 // what the steps and the drivers refuse alike, before any device work
 static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
@@ -258,27 +281,31 @@ static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned 
     const unsigned ld = g->ld;
     const int cw = gc_cw(ld);
     const int64_t N = (int64_t)g->width * g->height;
+    // the scale operand as the kernel takes it: on a compact handle scale_c 2^e_c, the column scale folded in f64 before any fl32
+    const bool compact = g->storage == GLF_PHI_F16;
+    double sc[64];
+    for (unsigned c = 0; c < dim; ++c) sc[c] = scale ? scale[c] : 1.0;
+    if (compact) compact_fold_cols(sc, 1, dim, g->expo.data());
+    if (!all_finite(sc, dim)) return set_error(ctx, GLF_ERR_INVALID, "cluster step: a scale entry folded with its column's 2^e_c is not finite");
     std::vector<float> h_op(gc_operand_floats(cw, mode), 0.f);
     for (unsigned j = 0; j < k; ++j) {
         double n2 = 0.0;
         for (unsigned c = 0; c < dim; ++c) {
             const double x = h_cent[(size_t)j * dim + c];
-            h_op[(size_t)c * GC_K + j] = (float)((scale ? scale[c] : 1.0) * x);
+            h_op[(size_t)c * GC_K + j] = (float)(sc[c] * x);
             n2 += x * x;
         }
         h_op[(size_t)cw * GC_K + j] = (float)n2;
     }
-    for (unsigned c = 0; mode == GC_NORM && c < dim; ++c) h_op[(size_t)cw * GC_K + GC_K + c] = (float)(scale ? scale[c] : 1.0);
+    for (unsigned c = 0; mode == GC_NORM && c < dim; ++c) h_op[(size_t)cw * GC_K + GC_K + c] = (float)sc[c];
     DevBuf<float> op;
     DevBuf<double> part, tot;
     GLF_TRY(upload_operand(ctx, op, h_op));
-    const cluster_kernel kernel = GC_KERNELS[cw == 64][mode];
     const size_t ncols = gc_part_cols(cw, mode);
     int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, &g->cluster_blocks_per_cu[mode], kernel, N, &nblk));
-    GLF_TRY(part.alloc(ctx, (size_t)nblk * ncols));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)k, op.p, d_weight, d_prev, d_labels, part.p);
-    GLF_LAUNCH_CHECK(ctx);
+    int rc = GLF_OK;
+    dispatch_phi(g, [&](auto *phi) { rc = launch_cluster(g, phi, cw, mode, N, k, op.p, d_weight, d_prev, d_labels, part, &nblk); });
+    GLF_TRY(rc);
     std::vector<double> h_tot;
     GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, ncols, tot, h_tot)); // (the one read-back of an iteration; h_op and the buffers go out of scope)
     const double *tail = h_tot.data() + (size_t)(cw / 32) * 1024;
@@ -287,6 +314,7 @@ static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned 
         h_counts[j] = (uint64_t)tail[j];
         if (h_mass) h_mass[j] = mode == GC_PLAIN ? (double)h_counts[j] : tail[64 + j];
     }
+    if (compact) compact_fold_cols(h_sums, k, dim, g->expo.data()); // (the raw-row sums of the halves times 2^e_c)
     *changed = d_prev ? (uint64_t)tail[32] : 0;
     return GLF_OK;
 }
@@ -321,9 +349,7 @@ static int segment_run(const char *name, glf_graph *g, const glf_segment_options
         const size_t cnt = (size_t)ns * cols;
         DevBuf<float> d_rows;
         GLF_TRY(d_rows.alloc(ctx, cnt));
-        hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)g->ld, (int)dim, 0,
-                           (const float *)nullptr, d_weight, (int)(cols - dim), ns, d_rows.p);
-        GLF_LAUNCH_CHECK(ctx);
+        GLF_TRY(graph_sample_rows(g, (int)dim, 0, nullptr, d_weight, (int)(cols - dim), ns, d_rows.p));
         std::vector<float> h_rows(cnt);
         GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));

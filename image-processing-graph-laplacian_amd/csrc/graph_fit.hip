@@ -1,6 +1,7 @@
 // graph_fit.hip -- the weighted normal equations of a least-squares fit on a graph handle: G = Phi^T diag(w) Phi and
 // b_k = Phi^T diag(w) s_k in one pass over Phi (k_graph_normal), and the host-side Cholesky solve (glf_fit_coeffs).
 #include "phi_tile.hpp"
+#include "phi_compact.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -59,8 +60,9 @@ inline bool gn_slot_tile(unsigned ld, int I, int J, int s, int &ti, int &tj)
 // (plane, column, pixel parity): it depends on no other plane, and G on no plane. Rows past N are staged as zeros (w and t too).
 // ld <= 64 keeps two workgroups per CU (the k-steps of a diagonal pair are unrolled by 4, which holds the registers under 256);
 // ld >= 128 carries four accumulator tiles and their f64 images and runs one wave per SIMD.
-template <int LD>
-__global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const float *__restrict__ phi, int64_t N, const float *__restrict__ w,
+// T: the element type of Phi (float, or __half on a compact handle: phi_tile.hpp's second loader, the same image).
+template <int LD, class T = float>
+__global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const T *__restrict__ phi, int64_t N, const float *__restrict__ w,
                                                                          int nplanes, const float *__restrict__ planes,
                                                                          double *__restrict__ partG, double *__restrict__ partB)
 {
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
     for (int k = 0; k < GLF_MAX_SIGNALS; ++k) bacc[k][0] = bacc[k][1] = 0.0;
 
     // what this lane stages of a tile
-    float4 v[NIMG][CW / 8];
+    tile_regs<T, CW> v[NIMG];
     float wv = 0.f, sv0 = 0.f, sv1 = 0.f;
     auto load_tile = [&](int64_t tile) {
 #pragma unroll
@@ -189,7 +191,8 @@ __global__ __launch_bounds__(256, LD <= 64 ? 2 : 1) void k_graph_normal(const fl
 }
 
 // h_G [m][m] and h_b [nplanes][m] of Phi [N][ld] (returns with the stream drained)
-int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
+template <class T>
+static int normal_equations(glf_ctx *ctx, const T *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
                            const float *d_planes, double *h_G, double *h_b)
 {
     if (!valid_ld(ld) || N < 1 || m < 1 || m > ld || nplanes < 0 || nplanes > GLF_MAX_SIGNALS)
@@ -201,7 +204,7 @@ int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned
     GLF_TRY(partG.alloc(ctx, (size_t)nblk * gcols));
     GLF_TRY(partB.alloc(ctx, (size_t)nblk * 8 * bcols));
     dispatch_ld(ld, [&](auto LD) { // (ld is valid)
-        hipLaunchKernelGGL(k_graph_normal<LD.value>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes, partG.p,
+        hipLaunchKernelGGL((k_graph_normal<LD.value, T>), dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes, partG.p,
                            partB.p);
     });
     GLF_LAUNCH_CHECK(ctx);
@@ -228,6 +231,22 @@ int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned
     }
     for (int k = 0; k < nplanes; ++k)
         for (unsigned j = 0; j < m; ++j) h_b[(size_t)k * m + j] = hB[(size_t)k * ld + j];
+    return GLF_OK;
+}
+
+int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
+                           const float *d_planes, double *h_G, double *h_b)
+{
+    return normal_equations(ctx, d_phi, N, m, ld, d_w, nplanes, d_planes, h_G, h_b);
+}
+
+int graph_normal_equations(const glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_G, double *h_b)
+{
+    const int64_t N = (int64_t)g->width * g->height;
+    if (g->storage != GLF_PHI_F16) return normal_equations(g->ctx, g->phi, N, g->m, g->ld, d_w, nplanes, d_planes, h_G, h_b);
+    GLF_TRY(normal_equations(g->ctx, static_cast<const __half *>(g->phi16), N, g->m, g->ld, d_w, nplanes, d_planes, h_G, h_b));
+    compact_fold_gram(h_G, g->m, g->expo.data());
+    if (nplanes > 0) compact_fold_cols(h_b, (size_t)nplanes, g->m, g->expo.data());
     return GLF_OK;
 }
 

@@ -2,6 +2,7 @@
 // pass over Phi on the matrix pipe (k_graph_project_wide), the counterpart of k_graph_synthesize's 32 outputs. glf_graph_project and
 // glf_graph_normal_equations keep their own f64 kernels and their bits.
 #include "phi_tile.hpp"
+#include "phi_compact.hpp"
 
 #include <algorithm>
 
@@ -48,8 +49,9 @@ inline GpwGeom gpw_geom(unsigned ld)
 // (consecutive r at a fixed plane) are consecutive dwords. So both directions are conflict-free.
 //
 // ld <= 64 runs two workgroups per CU; ld >= 128 carries four tiles and their images and runs one wave per SIMD.
-template <int LD>
-__global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(const float *__restrict__ phi, int64_t N, const float *__restrict__ w,
+// T: the element type of Phi (float, or __half on a compact handle: phi_tile.hpp's second loader, the same image).
+template <int LD, class T = float>
+__global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(const T *__restrict__ phi, int64_t N, const float *__restrict__ w,
                                                                                 int nplanes, const float *__restrict__ planes,
                                                                                 double *__restrict__ part)
 {
@@ -77,7 +79,7 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
         }
 
     // what this lane stages of a tile
-    float4 v[CW / 8];
+    tile_regs<T, CW> v;
     float sv[NPL];
     float wv = 0.f;
     auto load_tile = [&](int64_t tile) {
@@ -126,7 +128,8 @@ __global__ __launch_bounds__(256, LD < 128 ? 2 : 1) void k_graph_project_wide(co
 }
 
 // h_c [nplanes][m] of Phi [N][ld] (returns with the stream drained; h_c is written only on success)
-static int graph_project_wide(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
+template <class T>
+static int graph_project_wide(glf_ctx *ctx, const T *d_phi, int64_t N, unsigned m, unsigned ld, const float *d_w, int nplanes,
                               const float *d_planes, double *h_c)
 {
     if (!valid_ld(ld) || N < 1 || m < 1 || m > ld || nplanes < 1 || nplanes > GPW_SLOTS)
@@ -137,7 +140,7 @@ static int graph_project_wide(glf_ctx *ctx, const float *d_phi, int64_t N, unsig
     DevBuf<double> part, tot;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ncols));
     dispatch_ld(ld, [&](auto LD) { // (ld is valid)
-        hipLaunchKernelGGL(k_graph_project_wide<LD.value>, dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes,
+        hipLaunchKernelGGL((k_graph_project_wide<LD.value, T>), dim3(nblk, (unsigned)gm.ny), dim3(256), 0, ctx->stream, d_phi, N, d_w, nplanes, d_planes,
                            part.p);
     });
     GLF_LAUNCH_CHECK(ctx);
@@ -157,5 +160,9 @@ extern "C" int glf_graph_project_wide(glf_graph *g, const float *d_w, int nplane
     if (!g || nplanes < 1 || nplanes > GLF_GRAPH_MAX_PLANES || !d_planes || !h_c) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
     GLF_ENTER(ctx);
-    return graph_project_wide(ctx, g->phi, (int64_t)g->width * g->height, g->m, g->ld, d_w, nplanes, d_planes, h_c);
+    int rc = GLF_OK;
+    dispatch_phi(g, [&](auto *phi) { rc = graph_project_wide(ctx, phi, (int64_t)g->width * g->height, g->m, g->ld, d_w, nplanes, d_planes, h_c); });
+    // (a compact handle: c_k[c] 2^e_c, the column scale folded into the read-back in f64)
+    if (rc == GLF_OK && g->storage == GLF_PHI_F16) compact_fold_cols(h_c, (size_t)nplanes, g->m, g->expo.data());
+    return rc;
 }

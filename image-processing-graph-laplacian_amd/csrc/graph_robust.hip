@@ -8,6 +8,7 @@
 // communicator and glf_multi_* (handles refuse them), a flag of the host program, and anything inside k_graph_normal,
 // k_graph_synthesize, k_graph_cluster and k_graph_transform.
 #include "phi_tile.hpp"
+#include "phi_compact.hpp"
 #include "robust_loss.hpp"
 
 #include <algorithm>
@@ -49,8 +50,9 @@ __device__ inline float robust_u32(int kind, float q, float cf, float c2, float 
 // mass += (double) w_eff per lane. Rows past N are neither read nor stored nor summed.
 // part[blockIdx.x][2] = (loss, mass) of the workgroup: the lanes of wave 0 first, in ascending lane order; no atomics, the
 // workgroups are added by k_cols_sum.
-template <int LD>
-__global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__restrict__ phi, int64_t N, int nplanes, const float *__restrict__ operand,
+// T: the element type of Phi (float, or __half on a compact handle: phi_tile.hpp's second loader, the same image).
+template <int LD, class T = float>
+__global__ __launch_bounds__(256) void k_graph_residual_weight(const T *__restrict__ phi, int64_t N, int nplanes, const float *__restrict__ operand,
                                                                 RobustConst rc, const float *__restrict__ w, const float *__restrict__ planes,
                                                                 float *__restrict__ weight_out, float *__restrict__ res_out,
                                                                 double *__restrict__ part)
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__re
     float *tw = tile_sh[wave];
     const int64_t ntiles = (N + 31) / 32, tstride = (int64_t)gridDim.x * 4;
     double loss = 0.0, mass = 0.0;
-    float4 v[CW / 8];
+    tile_regs<T, CW> v;
     int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     if (tile < ntiles) tile_load<CW>(v, phi, LD, 0, N, tile, lane);
     for (; tile < ntiles; tile += tstride) {
@@ -118,14 +120,14 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const float *__re
     }
 }
 
-template <int LD>
-static int launch_residual_weight(glf_ctx *ctx, int *per_cu, int64_t *nblk, DevBuf<double> &part, const float *d_phi, int64_t N, int nplanes,
+template <int LD, class T>
+static int launch_residual_weight(glf_ctx *ctx, int *per_cu, int64_t *nblk, DevBuf<double> &part, const T *d_phi, int64_t N, int nplanes,
                                   const float *d_operand, const RobustConst &rc, const float *d_w, const float *d_planes, float *d_weight_out,
                                   float *d_res_out)
 {
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_residual_weight<LD>, N, nblk));
+    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_residual_weight<LD, T>, N, nblk));
     GLF_TRY(part.alloc(ctx, (size_t)*nblk * 2));
-    hipLaunchKernelGGL(k_graph_residual_weight<LD>, dim3((unsigned)*nblk), dim3(256), 0, ctx->stream, d_phi, N, nplanes, d_operand, rc, d_w, d_planes,
+    hipLaunchKernelGGL((k_graph_residual_weight<LD, T>), dim3((unsigned)*nblk), dim3(256), 0, ctx->stream, d_phi, N, nplanes, d_operand, rc, d_w, d_planes,
                        d_weight_out, d_res_out, part.p);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
@@ -160,9 +162,14 @@ static int robust_step(glf_graph *g, const RobustConst &rc, const float *d_w, in
     glf_ctx *ctx = g->ctx;
     const unsigned m = g->m, ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
+    // (a compact handle: the column scales folded into the coefficients in f64 before their fl32, glf_graph_synthesize's rule; the
+    // refusal of a coefficient that is not finite then applies to the folded values)
+    std::vector<double> a(h_a, h_a + (size_t)nplanes * m);
+    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)nplanes, m, g->expo.data());
+    if (!all_finite(a.data(), a.size())) return set_error(ctx, GLF_ERR_INVALID, "robust step: a coefficient folded with its column's 2^e_c is not finite");
     std::vector<float> h_op((size_t)ld * GR_OUT, 0.f);
     for (int j = 0; j < nplanes; ++j)
-        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GR_OUT + j] = (float)h_a[(size_t)j * m + k];
+        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GR_OUT + j] = (float)a[(size_t)j * m + k];
     DevBuf<float> op, weff;
     DevBuf<double> part, tot;
     GLF_TRY(upload_operand(ctx, op, h_op));
@@ -172,15 +179,17 @@ static int robust_step(glf_graph *g, const RobustConst &rc, const float *d_w, in
     }
     int64_t nblk = 0;
     int rc_launch = GLF_ERR_INVALID;
-    dispatch_ld(ld, [&](auto LD) {
-        rc_launch = launch_residual_weight<LD.value>(ctx, &g->robust_blocks_per_cu, &nblk, part, g->phi, N, nplanes, op.p, rc, d_w, d_planes,
-                                                     d_weight_out, d_res_out);
+    dispatch_phi(g, [&](auto *phi) {
+        dispatch_ld(ld, [&](auto LD) {
+            rc_launch = launch_residual_weight<LD.value>(ctx, &g->robust_blocks_per_cu, &nblk, part, phi, N, nplanes, op.p, rc, d_w, d_planes,
+                                                         d_weight_out, d_res_out);
+        });
     });
     GLF_TRY(rc_launch);
     std::vector<double> h_tot;
     GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, 2, tot, h_tot, false));
     // the second pass: G and b under w_eff, by the weighted fit's own kernel (it drains the stream; h_op and h_tot are then settled)
-    GLF_TRY(graph_normal_equations(ctx, g->phi, N, m, ld, d_weight_out, nplanes, d_planes, h_G, h_b));
+    GLF_TRY(graph_normal_equations(g, d_weight_out, nplanes, d_planes, h_G, h_b));
     if (h_loss) *h_loss = h_tot[0];
     if (h_mass) *h_mass = h_tot[1];
     return GLF_OK;
@@ -226,7 +235,7 @@ int glf_graph_fit_robust(glf_graph *g, const glf_robust_options *opt, const floa
 {
     if (!g || !opt || !d_planes || !h_a || nplanes < 1 || nplanes > GLF_MAX_SIGNALS || opt->struct_size != sizeof(glf_robust_options)) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
-    const unsigned m = g->m, ld = g->ld;
+    const unsigned m = g->m;
     const int64_t N = (int64_t)g->width * g->height;
     const bool estimate = opt->estimate_sigma == 1;
     bool ok = (opt->estimate_sigma == 0 || estimate) && loss_shape_ok(&opt->loss, nplanes, !estimate) && std::isfinite(opt->tol) && opt->tol >= 0.0 &&
@@ -243,7 +252,7 @@ int glf_graph_fit_robust(glf_graph *g, const glf_robust_options *opt, const floa
     // a_0: the plain weighted fit
     const size_t na = (size_t)nplanes * m;
     std::vector<double> G((size_t)m * m), b(na), a(na), a_new(na);
-    GLF_TRY(graph_normal_equations(ctx, g->phi, N, m, ld, d_w, nplanes, d_planes, G.data(), b.data()));
+    GLF_TRY(graph_normal_equations(g, d_w, nplanes, d_planes, G.data(), b.data()));
     if (glf_fit_coeffs(m, G.data(), opt->penalty, nplanes, b.data(), a.data()) != GLF_OK)
         return set_error(ctx, GLF_ERR_INVALID, "glf_graph_fit_robust: the plain weighted system is not positive definite (pass a penalty)");
     double sigma[GLF_MAX_SIGNALS] = {0.0, 0.0, 0.0, 0.0};
@@ -253,9 +262,7 @@ int glf_graph_fit_robust(glf_graph *g, const glf_robust_options *opt, const floa
         const size_t cnt = (size_t)ns * cols;
         DevBuf<float> d_rows;
         GLF_TRY(d_rows.alloc(ctx, cnt));
-        hipLaunchKernelGGL(k_sample_rows, dim3((unsigned)ceil_div((int64_t)cnt, 256)), dim3(256), 0, ctx->stream, g->phi, N, (int)ld, (int)m, nplanes,
-                           d_planes, d_w, 1, ns, d_rows.p);
-        GLF_LAUNCH_CHECK(ctx);
+        GLF_TRY(graph_sample_rows(g, (int)m, nplanes, d_planes, d_w, 1, ns, d_rows.p));
         std::vector<float> h_rows(cnt);
         GLF_HIP(ctx, hipMemcpyAsync(h_rows.data(), d_rows.p, sizeof(float) * cnt, hipMemcpyDeviceToHost, ctx->stream));
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));

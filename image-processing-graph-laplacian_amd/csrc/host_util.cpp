@@ -1,7 +1,8 @@
 // host_util.cpp -- host-side stages of the C-ABI: sampling grid, X0 random block,
 // synthetic benchmark images, the geometry and schedule of the band form, the centroid updates and
 // the seedings (plain and weighted) of the spectral segmentation, the orthonormal change of basis of a
-// graph handle from its Gram matrix, the loss table and the scale estimate of the robust fit. No device code.
+// graph handle from its Gram matrix, the loss table and the scale estimate of the robust fit, the exponent rule and the
+// scale folding of the compact graph handle. No device code.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -10,6 +11,7 @@
 
 #include "../../include/glf.h"
 #include "band_plan.hpp"
+#include "phi_compact.hpp"
 #include "robust_loss.hpp"
 
 namespace {
@@ -580,6 +582,30 @@ unsigned BandGeom::window(int cmin, int cmax, int dr, int shift) const
     band_cols_range(cols.data(), (int)cols.size(), cmin - dcmax[dr], cmax + dcmax[dr], &lo, &n);
     if (n <= 0) return BAND_EMPTY;
     return (unsigned)(lo >> shift) | ((unsigned)((lo + n - 1) >> shift) << 16);
+}
+
+// ---- compact graph handle: the exponent rule and the folding of the column scales -------------------------------
+bool compact_exponent(float max_c, int32_t *e)
+{
+    if (!e || !(max_c >= 0.f) || !std::isfinite(max_c) || max_c >= std::ldexp(1.f, 100)) return false;
+    *e = max_c == 0.f ? 0 : std::max(std::ilogb(max_c), COMPACT_E_FLOOR) - COMPACT_E_SHIFT;
+    return true;
+}
+
+float compact_multiplier(int32_t e) { return std::ldexp(1.f, -e); }
+
+void compact_fold_cols(double *x, size_t rows, unsigned cols, const int32_t *e, int sign)
+{
+    if (!e) return;
+    for (size_t r = 0; r < rows; ++r)
+        for (unsigned c = 0; c < cols; ++c) x[r * cols + c] = std::ldexp(x[r * cols + c], sign * e[c]);
+}
+
+void compact_fold_gram(double *G, unsigned m, const int32_t *e)
+{
+    if (!e) return;
+    for (unsigned i = 0; i < m; ++i)
+        for (unsigned j = 0; j < m; ++j) G[(size_t)i * m + j] = std::ldexp(G[(size_t)i * m + j], e[i] + e[j]);
 }
 
 } // namespace glf

@@ -22,6 +22,8 @@
 #pragma once
 #include "glf_internal.hpp"
 
+#include <hip/hip_fp16.h>
+
 #include <type_traits>
 
 namespace glf {
@@ -66,10 +68,61 @@ __device__ __forceinline__ void tile_put(float *img, const float4 (&v)[CW / 8], 
     }
 }
 
+// The compact storage (a handle after glf_graph_compact: Phi as __half [N][ld], the column scales on the host). The same tile, the
+// same image: a lane loads CW / 16 uint4s of 8 halves each, whole 16-byte pieces in address order (piece e = q 64 + lane is row
+// e / (CW / 8), halves [8 (e % (CW / 8)), + 8): each row's CW * 2 bytes contiguous), rows past N as zeros, never read; tile_put
+// converts a piece with v_cvt_f32_f16 (exact, f16 subnormals kept; no scale is applied on the device) and writes its two float4s
+// where the f32 pieces of those columns go (neighbouring lanes' float4s then lie 32 bytes apart, a two-way conflict of the
+// ds_write_b128 that the f32 put, 16 bytes apart, does not have: profiles/graph_compact_pmc_cluster.txt). Everything after the
+// image is the f32 kernel's own.
+template <class T>
+struct phi_piece;
+template <>
+struct phi_piece<float> {
+    typedef float4 type;
+    static constexpr int elems = 4;
+};
+template <>
+struct phi_piece<__half> {
+    typedef uint4 type;
+    static constexpr int elems = 8;
+};
+// the registers that hold a lane's pieces of CW columns of a tile
+template <class T, int CW>
+using tile_regs = typename phi_piece<T>::type[CW / (2 * phi_piece<T>::elems)];
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <int CW>
+__device__ __forceinline__ void tile_load(uint4 (&v)[CW / 16], const __half *phi, int ld, int col0, int64_t N, int64_t tile, int lane)
+{
+    constexpr int PPR = CW / 8; // 16-byte pieces per staged row
+    const int64_t base = tile * 32;
+#pragma unroll
+    for (int q = 0; q < CW / 16; ++q) {
+        const int e = q * 64 + lane, row = e / PPR, c8 = e % PPR;
+        v[q] = base + row < N ? *reinterpret_cast<const uint4 *>(phi + (size_t)(base + row) * ld + col0 + c8 * 8) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+template <int CW, int PITCH>
+__device__ __forceinline__ void tile_put(float *img, const uint4 (&v)[CW / 16], int lane)
+{
+    constexpr int PPR = CW / 8;
+#pragma unroll
+    for (int q = 0; q < CW / 16; ++q) {
+        const int e = q * 64 + lane, row = e / PPR, c8 = e % PPR;
+        const f16x8 x = __builtin_bit_cast(f16x8, v[q]);
+        float *dst = img + row * PITCH + c8 * 8;
+        *reinterpret_cast<float4 *>(dst) = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
+        *reinterpret_cast<float4 *>(dst + 4) = make_float4((float)x[4], (float)x[5], (float)x[6], (float)x[7]);
+    }
+}
+
 // the wave's image <- the pieces, between the two wave barriers. A kernel that stages more with the tile (a second image, weights,
 // planes) writes all of it between two barriers of its own, the pieces with tile_put.
-template <int CW, int PITCH>
-__device__ __forceinline__ void tile_store(float *img, const float4 (&v)[CW / 8], int lane)
+template <int CW, int PITCH, class V>
+__device__ __forceinline__ void tile_store(float *img, const V &v, int lane)
 {
     __builtin_amdgcn_wave_barrier();
     tile_put<CW, PITCH>(img, v, lane);
@@ -149,8 +202,20 @@ __device__ __forceinline__ void wave_tiles_reduce(float (&region)[4][RW], const 
 
 // out[i] = [Phi[px_i][0 .. dim) | s_k[px_i], k < nplanes | w[px_i] if wcol (1 where w is NULL)], px_i = floor(i N / ns): the sample of
 // rows a host-side seeding or scale estimate reads. A pure gather (graph.hip).
-__global__ void k_sample_rows(const float *__restrict__ phi, int64_t N, int ld, int dim, int nplanes, const float *__restrict__ planes,
-                              const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out);
+// expo: NULL on an f32 handle; on a compact one the column exponents (device int [ld]), and the gather writes Q = 2^e_c half.
+template <class T>
+__global__ void k_sample_rows(const T *__restrict__ phi, const int *__restrict__ expo, int64_t N, int ld, int dim, int nplanes,
+                              const float *__restrict__ planes, const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out);
+// the gather on a handle of either storage (queued)
+int graph_sample_rows(glf_graph *g, int dim, int nplanes, const float *d_planes, const float *d_w, int wcol, int64_t ns, float *d_out);
+
+// f(phi) with the handle's Phi as const float * or const __half *, by its storage
+template <class F>
+inline void dispatch_phi(const glf_graph *g, F &&f)
+{
+    if (g->storage == GLF_PHI_F16) f(static_cast<const __half *>(g->phi16));
+    else f(static_cast<const float *>(g->phi));
+}
 
 // f(std::integral_constant<int, LD>) for the ld of a graph handle; false: no such instance
 template <class F>

@@ -67,6 +67,7 @@ EXPORTS = [
     "glf_graph_cluster_step", "glf_cluster_update", "glf_cluster_seed", "glf_graph_segment",
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize", "glf_graph_project_wide",
+    "glf_graph_compact", "glf_graph_storage", "glf_graph_dequantize",
     "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex",
 ]
@@ -76,6 +77,7 @@ GRAPH_MAX_OUTPUTS = 32
 GRAPH_MAX_PLANES = 32      # GLF_GRAPH_MAX_PLANES: the most planes of one glf_graph_project_wide call
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
+PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
 ROBUST_HUBER, ROBUST_CAUCHY, ROBUST_TUKEY = 0, 1, 2
 ROBUST_LOSSES = {"huber": ROBUST_HUBER, "cauchy": ROBUST_CAUCHY, "tukey": ROBUST_TUKEY}
@@ -224,6 +226,9 @@ _lib.glf_graph_transform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_
 _lib.glf_basis_orthonormal.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_orthonormalize.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
 _lib.glf_graph_project_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+_lib.glf_graph_compact.argtypes = [C.c_void_p, C.c_int]
+_lib.glf_graph_storage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_dequantize.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
@@ -1512,7 +1517,8 @@ class Graph:
         gi = self._refresh()
         self.stats = _info(st, self.eigenvalues)   # the build call's: a later transform does not rewrite them
         n = gi.width * gi.height
-        self.phi = device_tensor_from_ptr(gi.d_phi, n * gi.ld, torch.float32, ctx.device).view(n, gi.ld)   # a view: dies with the handle
+        # a view: dies with the handle, and becomes None when the handle is compacted
+        self.phi = device_tensor_from_ptr(gi.d_phi, n * gi.ld, torch.float32, ctx.device).view(n, gi.ld)
 
     def _refresh(self):
         """info and eigenvalues from the handle: what the object caches of it (at build time and after every transform)."""
@@ -1549,6 +1555,41 @@ class Graph:
         self.ctx._check(_lib.glf_graph_gram(self._g, _ptr(G)), "graph gram")
         return G
 
+    @property
+    def storage(self):
+        """PHI_F32, or PHI_F16 once compact() ran (glf_graph_storage)."""
+        st = C.c_int(0)
+        self.ctx._check(_lib.glf_graph_storage(self._g, C.byref(st), None), "graph storage")
+        return int(st.value)
+
+    def column_exponents(self):
+        """e_c as numpy int32 [ld] (glf_graph_storage): a compact handle stands for Q[px, c] = 2^e_c * half[px, c]; all 0 on an f32 one."""
+        e = np.zeros(self.info["ld"], dtype=np.int32)
+        self.ctx._check(_lib.glf_graph_storage(self._g, None, _ptr(e)), "graph storage")
+        return e
+
+    def compact(self, storage=PHI_F16):
+        """glf_graph_compact: rewrite Phi as f16 with one power-of-two scale per column and release the f32 array (half the bytes of
+        every pass and of the handle). The last step of preparing a handle: transform, orthonormalize and project refuse a compact
+        handle, every other call returns bit for bit what it returns on an f32 handle whose Phi is dequantize(). phi becomes None
+        (the view's memory is released: drop every reference taken from it before), info is refreshed. There is no way back."""
+        t = self.ctx.torch
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the caller's own work on phi precedes the rewrite
+        try:
+            self.ctx._check(_lib.glf_graph_compact(self._g, C.c_int(storage)), "graph compact")   # (drained)
+        finally:
+            if self._refresh().d_phi is None:
+                self.phi = None
+
+    def dequantize(self):
+        """Q as a new device float32 [N, ld] tensor (glf_graph_dequantize); on an f32 handle a copy of Phi."""
+        t = self.ctx.torch
+        n = self.info["height"] * self.info["width"]
+        with t.cuda.stream(self.ctx.stream):
+            out = t.empty((n, self.info["ld"]), dtype=t.float32, device=self.ctx.device)
+        self.ctx._check(_lib.glf_graph_dequantize(self._g, C.c_void_p(out.data_ptr())), "graph dequantize")   # (drained)
+        return out
+
     def _planes(self, planes):
         t = self.ctx.torch
         h, w = self.info["height"], self.info["width"]
@@ -1559,7 +1600,8 @@ class Graph:
         return planes
 
     def project(self, planes):
-        """c_k = Phi^T s_k in f64 (glf_graph_project): planes device float32 [nplanes, H, W], 1 <= nplanes <= 4 -> numpy [nplanes, m]."""
+        """c_k = Phi^T s_k in f64 (glf_graph_project): planes device float32 [nplanes, H, W], 1 <= nplanes <= 4 -> numpy [nplanes, m].
+        A compact handle raises (GLF_ERR_UNSUPPORTED): project_wide is its projection."""
         planes = self._planes(planes)
         c = np.zeros((planes.shape[0], self.info["m"]), dtype=np.float64)
         self.ctx._check(_lib.glf_graph_project(self._g, C.c_int(planes.shape[0]), C.c_void_p(planes.data_ptr()), _ptr(c)), "graph project")
@@ -1876,6 +1918,7 @@ class Graph:
         nresp, nplanes = wts.shape[0], planes.shape[0]
         if wide is None:
             wide = nplanes > MAX_SIGNALS or nresp * nplanes > GRAPH_MAX_OUTPUTS
+        wide = wide or self.phi is None   # a compact handle has no project: always the wide route
         c = self.project_wide(planes) if wide else self.project(planes)
         a = (wts[:, None, :] * c[None, :, :]).reshape(nresp * nplanes, -1)
         idn = np.repeat(np.broadcast_to(np.asarray(ident, dtype=np.float32), (nresp,)), nplanes)

@@ -920,6 +920,44 @@ int glf_graph_orthonormalize(glf_graph *g, int mode, int passes /* 1 | 2 */, int
  * plane's. Returns with the stream drained. */
 int glf_graph_project_wide(glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_c);
 
+/* ---- graph handle: compact storage, Phi as f16 with one power-of-two scale per column ---------------------------------------------------
+ * The calls on a handle are one or two passes over the resident Phi and run at the memory stream: the only lever left is the number
+ * of bytes. glf_graph_compact(g, GLF_PHI_F16) rewrites the handle's Phi as __half [N][ld] (raster rows, the same ld: a row pitch of
+ * 2 ld bytes; from glf_malloc, not from the pool) and releases the f32 array; the peak during the call is 1.5 times the f32 size.
+ * The quantisation, operation by operation: max_c is the exact maximum of |Phi[px][c]| over the pixels (a maximum: it does not depend
+ * on the order); e_c = max(ilogb(max_c), -100) - 14, and e_c = 0 for a column of zeros and for every column >= m; the stored half
+ * is f16_rn(Phi[px][c] 2^-e_c): the multiplication is exact, the conversion rounds to nearest even and keeps f16 subnormals. A
+ * column's largest stored magnitude therefore lies in [2^14, 2^15] (2^15 when the rounding carries a maximum up to it). The handle then stands for Q[px][c] = 2^e_c half[px][c], with
+ * |Q - Phi| <= 2^-11 |Phi| wherever |Phi| >= 2^(e_c - 14) and <= 2^(e_c - 25) below that.
+ * The scales never reach the device: the kernels of a compact handle stage the halves through v_cvt_f32_f16 into the LDS image
+ * their f32 instances read (csrc/phi_tile.hpp) and keep the MFMA shapes, contraction orders, chain rule and epilogues, and the
+ * power-of-two scales, which commute with every rounding the kernels perform, are folded in f64 into the host-side operand before
+ * its fl32 (the coefficients a_j[c] 2^e_c of glf_graph_synthesize and of the residuals of glf_graph_robust_step, the scale operand
+ * scale_c 2^e_c of the cluster calls) and into the host-side result after its read-back (c_k[c] 2^e_c of glf_graph_project_wide,
+ * G[i][j] 2^(e_i + e_j) and b_k[c] 2^e_c of glf_graph_normal_equations and glf_graph_robust_step, sums[j][c] 2^e_c of the cluster
+ * steps); the row gathers of the drivers write Q. The contract: on a compact handle every call returns, bit for bit, what it
+ * returns on an f32 handle whose Phi is Q, short of under- or overflow of a folded operand in f32. The calls' refusals of operands
+ * that are not finite apply to the folded values.
+ * A compact handle is taken by glf_graph_synthesize, _project_wide, _normal_equations, _robust_step, _fit_robust, _cluster_step[_ex],
+ * _segment[_ex], _eigenvalues, _get_info (d_phi = NULL, phi_bytes = 2 N ld) and _gram (served by the normal-equations pass with
+ * w = NULL and cached: a compact handle has no earlier bits to keep). GLF_ERR_UNSUPPORTED, the reason in glf_ctx_last_error and the
+ * handle untouched: glf_graph_transform and glf_graph_orthonormalize (compaction is the last step of preparing a handle) and
+ * glf_graph_project (its f64-chain kernel reads f32; glf_graph_project_wide is the projection of a compact handle).
+ * Out of scope: bf16 or 8-bit storage, compacting during glf_graph_build, a compact handle as input to glf_graph_transform,
+ * rerouting glf_graph_project, contexts with a communicator and glf_multi_* (handles refuse them), m > 256, a flag of the
+ * image_processing host program, anything inside k_band. */
+enum { GLF_PHI_F32 = 0, GLF_PHI_F16 = 1 };
+/* storage GLF_PHI_F16: compact the handle as above (on a compact handle: GLF_OK, nothing done). GLF_PHI_F32: GLF_OK and nothing
+ * done on an f32 handle, GLF_ERR_UNSUPPORTED on a compact one (there is no way back). GLF_ERR_INVALID, the handle untouched and
+ * still f32: a NULL handle (before any device work), another storage value, a max_c (c < m) that is not finite or is >= 2^100.
+ * On success the cached Gram matrix is dropped. Returns with the stream drained. */
+int glf_graph_compact(glf_graph *g, int storage);
+/* *storage (or NULL) <- the format; h_exponent HOST int32 [ld] (or NULL) <- e_c, all 0 on an f32 handle. NULL handle: GLF_ERR_INVALID. */
+int glf_graph_storage(const glf_graph *g, int *storage, int32_t *h_exponent /* HOST [ld] or NULL */);
+/* d_out device float [N][ld] <- Q (2^e_c half, exact; f32 subnormals kept); on an f32 handle a copy of Phi. GLF_ERR_INVALID for
+ * a NULL handle or d_out, before any device work. Returns with the stream drained. */
+int glf_graph_dequantize(glf_graph *g, float *d_out /* device [N][ld] */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
