@@ -49,13 +49,9 @@ int build_sample_tables(glf_ctx *ctx, const uint8_t *d_img, int width, int heigh
     GLF_HIP(ctx, hipMemcpyAsync(out.idx.p, h_idx, sizeof(uint32_t) * p, hipMemcpyHostToDevice, ctx->stream));
     GLF_HIP(ctx, hipMemsetAsync(out.mask.p, 0, (size_t)N, ctx->stream));
     const dim3 grid((p + 255) / 256);
-    switch (pixgen_of(kernel)) {
-    case PixGen::Grey: hipLaunchKernelGGL(k_sample_tables<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
-    case PixGen::Rgb: hipLaunchKernelGGL(k_sample_tables<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
-    case PixGen::U16: hipLaunchKernelGGL(k_sample_tables<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
-    case PixGen::F32: hipLaunchKernelGGL(k_sample_tables<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
-    case PixGen::RgbF32: hipLaunchKernelGGL(k_sample_tables<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p); break;
-    }
+    pix_dispatch(pixgen_of(kernel), [&](auto t) {
+        hipLaunchKernelGGL(k_sample_tables<t.G>, grid, dim3(256), 0, ctx->stream, d_img, width, N, p, out.idx.p, out.samples.p, out.mask.p);
+    });
     GLF_LAUNCH_CHECK(ctx);
     // h_idx is pageable host memory: make sure the async copy has consumed it
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -562,15 +558,10 @@ int build_sample_matrix(glf_ctx *ctx, const float4 *d_samples, unsigned p, Kerne
     }
     if (col0 + ncols > p) return set_error(ctx, GLF_ERR_INVALID, "build_sample_matrix: column range");
     dim3 grid((unsigned)((ld + 63) / 64), (p + 63) / 64); // covers the padding columns too
-    if (pixgen_of(coef.kernel) == PixGen::Rgb)
-        hipLaunchKernelGGL(k_sample_matrix<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
+    pix_dispatch(pixgen_of(coef.kernel), [&](auto t) { // (the 16-bit and float records are grey records: Pix<G>::MATRIX_AS)
+        hipLaunchKernelGGL(k_sample_matrix<Pix<t.G>::MATRIX_AS>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
                            ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
-    else if (pixgen_of(coef.kernel) == PixGen::RgbF32)
-        hipLaunchKernelGGL(k_sample_matrix<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
-                           ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
-    else
-        hipLaunchKernelGGL(k_sample_matrix<PixGen::Grey>, grid, dim3(256), 0, ctx->stream, d_samples, p, coef.s_loc, coef.s_val, d_out,
-                           ld, laplacian ? 1 : 0, alpha, d_degree, col0, ncols);
+    });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

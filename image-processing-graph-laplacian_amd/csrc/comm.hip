@@ -395,9 +395,9 @@ const char *glf_multi_last_error(const glf_multi *w) { return w ? w->last_error 
 // path, copy this rank's pixel rows of the result back (hpc/utils.c:502-527 gathers to rank 0).
 // nsig > 0: signal planes h_sig [nsig][N] replicated on every rank, each rank's pixel rows of the results into h_sig_out
 // gen: the guide's pixel format (glf_image_processing / _signals, _rgb, _u16, _f32, _rgbf32): h_img and h_out are [N] pixels of it, h_zf the
-// format's [NCH][N] floats
-static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
-                     float *h_zf, double *eigvals_out, glf_stats *stats, int nsig = 0, const float *h_sig = nullptr, float *h_sig_out = nullptr);
+// format's [NCH][N] floats (null for the float formats, whose h_out is z itself). sig: the _signals entry points' host planes
+static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const void *h_img, int width, int height, void *h_out, float *h_zf,
+                     double *eigvals_out, glf_stats *stats, const SignalPlanes *sig = nullptr);
 
 int glf_multi_image_processing(glf_multi *w, const glf_options *opt, const uint8_t *h_img, int width, int height, uint8_t *h_out,
                                float *h_zf, double *eigvals_out, glf_stats *stats)
@@ -409,8 +409,8 @@ int glf_multi_image_processing_signals(glf_multi *w, const glf_options *opt, con
                                        const float *h_sig, float *h_sig_out, uint8_t *h_out, float *h_zf, double *eigvals_out,
                                        glf_stats *stats)
 {
-    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run(w, opt, PixGen::Grey, h_img, width, height, h_out, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
+    const SignalPlanes sig{nsig, h_sig, h_sig_out};
+    return multi_run(w, opt, PixGen::Grey, h_img, width, height, h_out, h_zf, eigvals_out, stats, &sig);
 }
 
 int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height, uint8_t *h_out_rgb,
@@ -422,78 +422,76 @@ int glf_multi_image_processing_rgb(glf_multi *w, const glf_options *opt, const u
 int glf_multi_image_processing_u16(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height, uint16_t *h_out,
                                    float *h_zf, double *eigvals_out, glf_stats *stats)
 {
-    return multi_run(w, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), h_zf,
-                     eigvals_out, stats);
+    return multi_run(w, opt, PixGen::U16, h_img, width, height, h_out, h_zf, eigvals_out, stats);
 }
 
 int glf_multi_image_processing_rgb_signals(glf_multi *w, const glf_options *opt, const uint8_t *h_rgb, int width, int height, int nsig,
                                            const float *h_sig, float *h_sig_out, uint8_t *h_out_rgb, float *h_zf, double *eigvals_out,
                                            glf_stats *stats)
 {
-    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run(w, opt, PixGen::Rgb, h_rgb, width, height, h_out_rgb, h_zf, eigvals_out, stats, nsig, h_sig, h_sig_out);
+    const SignalPlanes sig{nsig, h_sig, h_sig_out};
+    return multi_run(w, opt, PixGen::Rgb, h_rgb, width, height, h_out_rgb, h_zf, eigvals_out, stats, &sig);
 }
 
 int glf_multi_image_processing_u16_signals(glf_multi *w, const glf_options *opt, const uint16_t *h_img, int width, int height, int nsig,
                                            const float *h_sig, float *h_sig_out, uint16_t *h_out, float *h_zf, double *eigvals_out,
                                            glf_stats *stats)
 {
-    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run(w, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), h_zf,
-                     eigvals_out, stats, nsig, h_sig, h_sig_out);
-}
-
-// float grey: the finite check runs here on the host image, once for all ranks and before any of them starts (a rank that failed
-// alone would cost the world its communicators)
-static int multi_run_f32(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, float *h_out, double *eigvals_out,
-                         glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out, PixGen gen = PixGen::F32)
-{
-    if (!w || !h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    const size_t nch = (size_t)pix_channels(gen), N = (size_t)width * height * nch;
-    for (size_t i = 0; i < N; ++i) {
-        uint32_t bits;
-        std::memcpy(&bits, h_img + i, sizeof(bits));
-        if ((bits & 0x7f800000u) == 0x7f800000u) {
-            std::snprintf(w->last_error, sizeof(w->last_error), "the %s image holds a NaN or an Inf (pixel %zu): finite values only", pix_name(gen), i / nch);
-            return GLF_ERR_INVALID;
-        }
-    }
-    return multi_run(w, opt, gen, reinterpret_cast<const uint8_t *>(h_img), width, height, reinterpret_cast<uint8_t *>(h_out), nullptr,
-                     eigvals_out, stats, nsig, h_sig, h_sig_out);
+    const SignalPlanes sig{nsig, h_sig, h_sig_out};
+    return multi_run(w, opt, PixGen::U16, h_img, width, height, h_out, h_zf, eigvals_out, stats, &sig);
 }
 
 int glf_multi_image_processing_f32(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, float *h_out,
                                    double *eigvals_out, glf_stats *stats)
 {
-    return multi_run_f32(w, opt, h_img, width, height, h_out, eigvals_out, stats, 0, nullptr, nullptr);
+    return multi_run(w, opt, PixGen::F32, h_img, width, height, h_out, nullptr, eigvals_out, stats);
 }
 
 int glf_multi_image_processing_f32_signals(glf_multi *w, const glf_options *opt, const float *h_img, int width, int height, int nsig,
                                            const float *h_sig, float *h_sig_out, float *h_out, double *eigvals_out, glf_stats *stats)
 {
-    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run_f32(w, opt, h_img, width, height, h_out, eigvals_out, stats, nsig, h_sig, h_sig_out);
+    const SignalPlanes sig{nsig, h_sig, h_sig_out};
+    return multi_run(w, opt, PixGen::F32, h_img, width, height, h_out, nullptr, eigvals_out, stats, &sig);
 }
 
 int glf_multi_image_processing_rgbf32(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, float *h_out_rgb,
                                       double *eigvals_out, glf_stats *stats)
 {
-    return multi_run_f32(w, opt, h_rgb, width, height, h_out_rgb, eigvals_out, stats, 0, nullptr, nullptr, PixGen::RgbF32);
+    return multi_run(w, opt, PixGen::RgbF32, h_rgb, width, height, h_out_rgb, nullptr, eigvals_out, stats);
 }
 
 int glf_multi_image_processing_rgbf32_signals(glf_multi *w, const glf_options *opt, const float *h_rgb, int width, int height, int nsig,
                                               const float *h_sig, float *h_sig_out, float *h_out_rgb, double *eigvals_out, glf_stats *stats)
 {
-    if (!w || nsig < 1 || nsig > GLF_MAX_SIGNALS || !h_sig || !h_sig_out) return GLF_ERR_INVALID;
-    return multi_run_f32(w, opt, h_rgb, width, height, h_out_rgb, eigvals_out, stats, nsig, h_sig, h_sig_out, PixGen::RgbF32);
+    const SignalPlanes sig{nsig, h_sig, h_sig_out};
+    return multi_run(w, opt, PixGen::RgbF32, h_rgb, width, height, h_out_rgb, nullptr, eigvals_out, stats, &sig);
 }
 
-static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uint8_t *h_img, int width, int height, uint8_t *h_out,
-                     float *h_zf, double *eigvals_out, glf_stats *stats, int nsig, const float *h_sig, float *h_sig_out)
+static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const void *h_img_any, int width, int height, void *h_out_any,
+                     float *h_zf, double *eigvals_out, glf_stats *stats, const SignalPlanes *sig)
 {
-    const size_t pxb = pix_bytes(gen); // bytes per pixel in and out
-    const int nzf = pix_channels(gen); // float z planes
-    if (!w || !h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    const uint8_t *h_img = static_cast<const uint8_t *>(h_img_any);
+    uint8_t *h_out = static_cast<uint8_t *>(h_out_any);
+    const size_t pxb = pix_desc(gen).bytes;   // bytes per pixel in and out
+    const int nzf = pix_desc(gen).channels;   // float z planes
+    const int nsig = sig ? sig->nsig : 0;
+    // (both answer GLF_ERR_INVALID and leave last_error alone)
+    if (!w || (sig && (nsig < 1 || nsig > GLF_MAX_SIGNALS || !sig->d_sig || !sig->d_out))) return GLF_ERR_INVALID;
+    if (!h_img || !h_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    // a float guide: the finite check runs here on the host image, once for all ranks and before any of them starts (a rank that
+    // failed alone would cost the world its communicators)
+    if (pix_desc(gen).is_float) {
+        const size_t nch = (size_t)nzf, n = (size_t)width * height * nch;
+        for (size_t i = 0; i < n; ++i) {
+            uint32_t bits;
+            std::memcpy(&bits, h_img + sizeof(bits) * i, sizeof(bits));
+            if ((bits & 0x7f800000u) == 0x7f800000u) {
+                std::snprintf(w->last_error, sizeof(w->last_error), "the %s image holds a NaN or an Inf (pixel %zu): finite values only",
+                              pix_desc(gen).name, i / nch);
+                return GLF_ERR_INVALID;
+            }
+        }
+    }
     if (w->broken) {
         std::snprintf(w->last_error, sizeof(w->last_error), "the communicators of this world were aborted after a rank failed; create a new one");
         return GLF_ERR_COMM;
@@ -534,35 +532,14 @@ static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uin
             if (rc == GLF_OK) rc = sig_out.alloc(ctx, (size_t)nsig * N);
             d_sig = sig_in.p;
             d_sig_out = sig_out.p;
-            if (rc == GLF_OK) step(hipMemcpyAsync(d_sig, h_sig, (size_t)nsig * N * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+            if (rc == GLF_OK) step(hipMemcpyAsync(d_sig, sig->d_sig, (size_t)nsig * N * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
             step(hipStreamSynchronize(ctx->stream));
         }
         if (rc == GLF_OK) {
             float *zf = h_zf ? b.d_zf : nullptr;
             double *ev = r == 0 ? eigvals_out : nullptr;
-            if (gen == PixGen::Rgb && nsig > 0)
-                rc = glf_image_processing_rgb_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out, zf, ev, &st);
-            else if (gen == PixGen::U16 && nsig > 0)
-                rc = glf_image_processing_u16_signals(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height, nsig, d_sig,
-                                                      d_sig_out, reinterpret_cast<uint16_t *>(b.d_out), zf, ev, &st);
-            else if (gen == PixGen::F32 && nsig > 0)
-                rc = glf_image_processing_f32_signals(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height, nsig, d_sig, d_sig_out,
-                                                      reinterpret_cast<float *>(b.d_out), ev, &st);
-            else if (gen == PixGen::F32)
-                rc = glf_image_processing_f32(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height,
-                                              reinterpret_cast<float *>(b.d_out), ev, &st);
-            else if (gen == PixGen::RgbF32 && nsig > 0)
-                rc = glf_image_processing_rgbf32_signals(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height, nsig, d_sig, d_sig_out,
-                                                         reinterpret_cast<float *>(b.d_out), ev, &st);
-            else if (gen == PixGen::RgbF32)
-                rc = glf_image_processing_rgbf32(ctx, opt, reinterpret_cast<const float *>(b.d_img), width, height,
-                                                 reinterpret_cast<float *>(b.d_out), ev, &st);
-            else if (gen == PixGen::Rgb) rc = glf_image_processing_rgb(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
-            else if (gen == PixGen::U16)
-                rc = glf_image_processing_u16(ctx, opt, reinterpret_cast<const uint16_t *>(b.d_img), width, height,
-                                              reinterpret_cast<uint16_t *>(b.d_out), zf, ev, &st);
-            else if (nsig > 0) rc = glf_image_processing_signals(ctx, opt, b.d_img, width, height, nsig, d_sig, d_sig_out, b.d_out, zf, ev, &st);
-            else rc = glf_image_processing(ctx, opt, b.d_img, width, height, b.d_out, zf, ev, &st);
+            const SignalPlanes d_planes{nsig, d_sig, d_sig_out};
+            rc = image_processing_run(ctx, opt, gen, b.d_img, width, height, b.d_out, zf, ev, &st, nullptr, sig ? &d_planes : nullptr);
         }
         if (rc == GLF_OK) {
             const size_t o = (size_t)st.row0 * width, len = (size_t)(st.row1 - st.row0) * width;
@@ -570,7 +547,7 @@ static int multi_run(glf_multi *w, const glf_options *opt, PixGen gen, const uin
             for (int k = 0; k < nzf && len && h_zf; ++k)
                 step(hipMemcpyAsync(h_zf + k * N + o, b.d_zf + k * N + o, len * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
             for (int k = 0; k < nsig && len; ++k)
-                step(hipMemcpyAsync(h_sig_out + (size_t)k * N + o, d_sig_out + (size_t)k * N + o, len * sizeof(float), hipMemcpyDeviceToHost,
+                step(hipMemcpyAsync(sig->d_out + (size_t)k * N + o, d_sig_out + (size_t)k * N + o, len * sizeof(float), hipMemcpyDeviceToHost,
                                     ctx->stream));
             step(hipStreamSynchronize(ctx->stream));
             if (stats) stats[r] = st;

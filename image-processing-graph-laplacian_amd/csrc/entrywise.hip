@@ -122,20 +122,17 @@ int degree_rows_entrywise(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int wi
     const int radius = coef.s_loc > 0.f ? (int)std::floor(std::sqrt(151.0 / (double)coef.s_loc)) + 1 : (width + height) * 2;
     const int nchunks = (int)ceil_div(row1 - row0, EW_ROWS);
     if (nchunks > 65535)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too tall for one %s degree launch", pix_name(gen));
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too tall for one %s degree launch", pix_desc(gen).name);
     DevBuf<double> partial;
     DevBuf<unsigned long long> count;
     GLF_TRY(partial.alloc(ctx, (size_t)nchunks * p));
     GLF_TRY(count.alloc(ctx, 1));
     GLF_HIP(ctx, hipMemsetAsync(count.p, 0, sizeof(unsigned long long), ctx->stream));
     const dim3 grid((unsigned)ceil_div(p, 256), nchunks);
-#define GLF_DEGREE_EW(G_) hipLaunchKernelGGL(k_degree_entrywise<G_>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p, \
-                                             coef.s_loc, coef.s_val, radius, partial.p, count.p)
-    if (gen == PixGen::Rgb) GLF_DEGREE_EW(PixGen::Rgb);
-    else if (gen == PixGen::U16) GLF_DEGREE_EW(PixGen::U16);
-    else if (gen == PixGen::F32) GLF_DEGREE_EW(PixGen::F32);
-    else GLF_DEGREE_EW(PixGen::RgbF32);
-#undef GLF_DEGREE_EW
+    pix_dispatch_raw(gen, [&](auto t) {
+        hipLaunchKernelGGL(k_degree_entrywise<t.G>, grid, dim3(256), 0, ctx->stream, d_img, width, row0, row1, d_samples, p, coef.s_loc,
+                           coef.s_val, radius, partial.p, count.p);
+    });
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
     GLF_LAUNCH_CHECK(ctx);
@@ -162,10 +159,7 @@ int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float 
 {
     if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "pix_planes: the 8-bit grey format has kernels of its own");
     const dim3 grid((unsigned)ceil_div(N, 256));
-    if (gen == PixGen::Rgb) hipLaunchKernelGGL(k_planes<PixGen::Rgb>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
-    else if (gen == PixGen::U16) hipLaunchKernelGGL(k_planes<PixGen::U16>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
-    else if (gen == PixGen::F32) hipLaunchKernelGGL(k_planes<PixGen::F32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
-    else hipLaunchKernelGGL(k_planes<PixGen::RgbF32>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes);
+    pix_dispatch_raw(gen, [&](auto t) { hipLaunchKernelGGL(k_planes<t.G>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes); });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -227,10 +221,7 @@ int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0,
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     const dim3 grid((unsigned)nblk);
-    if (gen == PixGen::Rgb) launch_apply_filter_pix<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
-    else if (gen == PixGen::U16) launch_apply_filter_pix<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
-    else if (gen == PixGen::F32) launch_apply_filter_pix<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
-    else launch_apply_filter_pix<PixGen::RgbF32>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N);
+    pix_dispatch_raw(gen, [&](auto t) { launch_apply_filter_pix<t.G>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -289,7 +280,7 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
     if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "phi_t_pix_signals: the 8-bit grey format has kernels of its own");
     if (!valid_ld(ld) || pix0 > pix1 || nsig < 1 || nsig > GLF_MAX_SIGNALS)
         return set_error(ctx, GLF_ERR_INVALID, "phi_t_pix_signals: ld=%u nsig=%d", ld, nsig);
-    const int nch = pix_channels(gen);
+    const int nch = pix_desc(gen).channels;
     if (pix0 == pix1) {
         GLF_HIP(ctx, hipMemsetAsync(d_c, 0, sizeof(double) * ld * nch, ctx->stream));
         GLF_HIP(ctx, hipMemsetAsync(d_cs, 0, sizeof(double) * ld * nsig, ctx->stream));
@@ -299,18 +290,10 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
     DevBuf<double> part_g, part_s;
     GLF_TRY(part_g.alloc(ctx, (size_t)nblk * nch * ld));
     GLF_TRY(part_s.alloc(ctx, (size_t)nblk * nsig * ld));
-    if (gen == PixGen::Rgb)
-        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::Rgb>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
-                           part_g.p, part_s.p);
-    else if (gen == PixGen::U16)
-        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::U16>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
-                           part_g.p, part_s.p);
-    else if (gen == PixGen::F32)
-        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::F32>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
-                           part_g.p, part_s.p);
-    else
-        hipLaunchKernelGGL(k_phi_t_pix_signals<PixGen::RgbF32>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld,
-                           part_g.p, part_s.p);
+    pix_dispatch_raw(gen, [&](auto t) {
+        hipLaunchKernelGGL(k_phi_t_pix_signals<t.G>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld, part_g.p,
+                           part_s.p);
+    });
     GLF_LAUNCH_CHECK(ctx);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * nch), dim3(256), 0, ctx->stream, part_g.p, nblk, ld * nch, d_c);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * nsig), dim3(256), 0, ctx->stream, part_s.p, nblk, ld * nsig, d_cs);
@@ -393,18 +376,9 @@ int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     const dim3 grid((unsigned)nblk);
-    if (gen == PixGen::Rgb)
-        launch_apply_filter_pix_signals<PixGen::Rgb>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
-                                                     d_sig_out, N);
-    else if (gen == PixGen::U16)
-        launch_apply_filter_pix_signals<PixGen::U16>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
-                                                     d_sig_out, N);
-    else if (gen == PixGen::F32)
-        launch_apply_filter_pix_signals<PixGen::F32>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
-                                                     d_sig_out, N);
-    else
-        launch_apply_filter_pix_signals<PixGen::RgbF32>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig,
-                                                        d_sig_out, N);
+    pix_dispatch_raw(gen, [&](auto t) {
+        launch_apply_filter_pix_signals<t.G>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N);
+    });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }

@@ -309,6 +309,7 @@ __device__ __forceinline__ uint16_t filter_output_u16(int x, double c)
 //                  carries a value block of float4 {R, G, B, 0}, one per sample, behind its padded records (samples + p_pad, p_pad =
 //                  round_up(p, NYS_PAD): one pointer, one allocation). value(record, entry) takes both; the formats without a
 //                  block ignore the entry, and sample_value<G> does not load it for them
+//   MATRIX_AS      (host side) the format whose k_sample_matrix reads the format's records: U16 and F32 records are Grey's {row, col, v, 0}
 //   dist2          the squared photometric distance |a - b|^2 in a fixed operation order; the kernels take
 //                  K = exp2(-fmaf(dist2, s_val, (dr^2 + dc^2) s_loc))
 //   Tile, tile     the degree sweep's LDS element {value, col}; outside() lies in a column no sample reaches (K = 0)
@@ -326,6 +327,7 @@ template <typename T> struct PixGreyValue {
     using Val = float;
     static constexpr int NCH = 1;
     static constexpr bool HAS_VALUE_BLOCK = false;
+    static constexpr PixGen MATRIX_AS = PixGen::Grey;
     __device__ __forceinline__ static Val read(const In *img, int64_t px) { return (float)img[px]; }
     __device__ __forceinline__ static float4 record(const In *img, uint32_t px, uint32_t width)
     {
@@ -361,6 +363,7 @@ template <> struct Pix<PixGen::Rgb> {
     using Out = uint8_t;
     static constexpr int NCH = 3;
     static constexpr bool HAS_VALUE_BLOCK = false;
+    static constexpr PixGen MATRIX_AS = PixGen::Rgb;
     __device__ __forceinline__ static Val read(const In *img, int64_t px)
     {
         return make_float3((float)img[3 * px], (float)img[3 * px + 1], (float)img[3 * px + 2]);
@@ -400,6 +403,7 @@ template <> struct Pix<PixGen::RgbF32> {
     using Out = float;
     static constexpr int NCH = 3;
     static constexpr bool HAS_VALUE_BLOCK = true;
+    static constexpr PixGen MATRIX_AS = PixGen::RgbF32;
     __device__ __forceinline__ static Val read(const In *img, int64_t px) { return make_float3(img[3 * px], img[3 * px + 1], img[3 * px + 2]); }
     __device__ __forceinline__ static float4 record(const In *, uint32_t px, uint32_t width)
     {
@@ -433,57 +437,80 @@ template <PixGen G> __device__ __forceinline__ typename Pix<G>::Val sample_value
     if constexpr (Pix<G>::HAS_VALUE_BLOCK) return Pix<G>::value(s, samples[(size_t)p_pad + i]);
     else return Pix<G>::value(s, s);
 }
-// records the sample table allocates for p samples in the format: the padded records, and the value block behind them
-inline size_t sample_table_records(PixGen g, unsigned p)
+
+// ---- host side: the format table and the dispatchers ---------------------------------------------------------------------------
+// What the host code knows of a format, one row per PixGen, built from Pix<G>: everything outside the kernels that differs between
+// the formats is read from here (pix_desc) or instantiated through pix_dispatch / pix_dispatch_raw below.
+struct PixDesc {
+    int pix;              // the public GLF_PIX_*
+    int kernel;           // the format's bilateral GLF_KERNEL_* (GLF_KERNEL_BILATERAL stands for it at the format's entry points)
+    size_t bytes;         // per pixel, in and out
+    int channels;         // per pixel; the float z planes of a call
+    bool is_float;        // float elements: admitted after the finite check only, which runs over `channels` floats per pixel
+    bool value_block;     // Pix<G>::HAS_VALUE_BLOCK: the sample table carries as many value-block entries behind its padded records
+    int svals32_what;     // k_gridop_svals32's code for the sample values as u32: 0 the record's z as an integer, 1 the packed colour
+                          // (its w), 2 the bit pattern of the float z, 3 three planes of bit patterns from the value block
+    int svals32_planes;   // u32 values per sample in that image
+    const char *name;     // the format in messages
+    const char *image;    // "the <name> kernel takes <image>: <entry>": what the 8-bit entry points answer to another format's kernel
+    const char *entry;    // the public entry point that message cites
+};
+template <PixGen G> constexpr PixDesc make_pix_desc(int pix, int kernel, const char *name, const char *image, const char *entry)
 {
-    const size_t p_pad = (size_t)round_up(p, NYS_PAD);
-    return g == PixGen::RgbF32 ? 2 * p_pad : p_pad;
+    using P = Pix<G>;
+    constexpr bool flt = std::is_floating_point<typename P::In>::value;
+    return {pix, kernel, sizeof(typename P::In) * P::NCH, P::NCH, flt, P::HAS_VALUE_BLOCK,
+            P::HAS_VALUE_BLOCK ? 3 : flt ? 2 : P::NCH == 3 ? 1 : 0, P::HAS_VALUE_BLOCK ? P::NCH : 1, name, image, entry};
 }
-// host side: the format a kernel reads (and the bilateral kernel on a format), whether the factored forms over the 256 grey
-// levels apply to a kernel, bytes and channels per pixel
+constexpr PixDesc PIX_TABLE[] = { // indexed by PixGen
+    make_pix_desc<PixGen::Grey>(GLF_PIX_U8, GLF_KERNEL_BILATERAL, "8-bit", "an 8-bit image", "glf_image_processing"),
+    make_pix_desc<PixGen::Rgb>(GLF_PIX_RGB8, GLF_KERNEL_BILATERAL_RGB, "colour", "an RGB image", "glf_image_processing_rgb"),
+    make_pix_desc<PixGen::U16>(GLF_PIX_U16, GLF_KERNEL_BILATERAL_U16, "16-bit", "a 16-bit image", "glf_image_processing_u16"),
+    make_pix_desc<PixGen::F32>(GLF_PIX_F32, GLF_KERNEL_BILATERAL_F32, "float", "a float image", "glf_image_processing_f32"),
+    make_pix_desc<PixGen::RgbF32>(GLF_PIX_RGBF32, GLF_KERNEL_BILATERAL_RGBF32, "float colour", "a float RGB image", "glf_image_processing_rgbf32"),
+};
+constexpr int PIX_FORMATS = (int)(sizeof(PIX_TABLE) / sizeof(PIX_TABLE[0]));
+inline const PixDesc &pix_desc(PixGen g) { return PIX_TABLE[(int)g]; }
+// the format a kernel reads (every kernel that is not another format's bilateral kernel reads 8-bit grey), and the format of a
+// GLF_PIX_* value (the caller has checked its range)
 inline PixGen pixgen_of(int kernel)
 {
-    return kernel == GLF_KERNEL_BILATERAL_RGB   ? PixGen::Rgb
-           : kernel == GLF_KERNEL_BILATERAL_U16 ? PixGen::U16
-           : kernel == GLF_KERNEL_BILATERAL_F32 ? PixGen::F32
-           : kernel == GLF_KERNEL_BILATERAL_RGBF32 ? PixGen::RgbF32
-                                                : PixGen::Grey;
+    for (int g = 1; g < PIX_FORMATS; ++g)
+        if (PIX_TABLE[g].kernel == kernel) return (PixGen)g;
+    return PixGen::Grey;
 }
-inline int bilateral_kernel_of(PixGen g)
+inline PixGen pixgen_of_pix(int pix)
 {
-    return g == PixGen::Rgb   ? GLF_KERNEL_BILATERAL_RGB
-           : g == PixGen::U16 ? GLF_KERNEL_BILATERAL_U16
-           : g == PixGen::F32 ? GLF_KERNEL_BILATERAL_F32
-           : g == PixGen::RgbF32 ? GLF_KERNEL_BILATERAL_RGBF32
-                              : GLF_KERNEL_BILATERAL;
+    for (int g = 1; g < PIX_FORMATS; ++g)
+        if (PIX_TABLE[g].pix == pix) return (PixGen)g;
+    return PixGen::Grey;
 }
+// f(PixTag<G>{}) for the runtime format g: inside a generic lambda `t.G` is the format as a constant (k_planes<t.G>, Pix<t.G>)
+template <PixGen V> struct PixTag { static constexpr PixGen G = V; };
+template <class F> inline void pix_dispatch(PixGen g, F &&f)
+{
+    switch (g) {
+    case PixGen::Grey: f(PixTag<PixGen::Grey>{}); break;
+    case PixGen::Rgb: f(PixTag<PixGen::Rgb>{}); break;
+    case PixGen::U16: f(PixTag<PixGen::U16>{}); break;
+    case PixGen::F32: f(PixTag<PixGen::F32>{}); break;
+    case PixGen::RgbF32: f(PixTag<PixGen::RgbF32>{}); break;
+    }
+}
+// the same over the formats without a factored form: Pix<Grey> has no Tile and no Out, so their kernels are never instantiated for
+// it (Grey does nothing here: every caller has refused it before)
+template <class F> inline void pix_dispatch_raw(PixGen g, F &&f)
+{
+    if (g != PixGen::Grey) pix_dispatch(g, [&](auto t) {
+        if constexpr (decltype(t)::G != PixGen::Grey) f(t);
+    });
+}
+// records the sample table allocates for p samples in the format: the padded records, and the value block behind them
+inline size_t sample_table_records(PixGen g, unsigned p) { return (size_t)round_up(p, NYS_PAD) * (pix_desc(g).value_block ? 2 : 1); }
+// whether the factored forms over the 256 grey levels apply to a kernel
 inline bool grey_levels_factor(int kernel) { return kernel != GLF_KERNEL_NLM && pixgen_of(kernel) == PixGen::Grey; }
 // the band form applies to a kernel: it factors over grey levels, or it is a colour / 16-bit / float bilateral kernel and PIX_BAND is set
 inline bool band_form_applies(const glf_ctx *ctx, int kernel) { return grey_levels_factor(kernel) || (ctx->tune.pix_band && pixgen_of(kernel) != PixGen::Grey); }
-template <PixGen G> constexpr size_t pix_bytes_of = sizeof(typename Pix<G>::In) * Pix<G>::NCH;
-inline size_t pix_bytes(PixGen g)
-{
-    return g == PixGen::Rgb   ? pix_bytes_of<PixGen::Rgb>
-           : g == PixGen::U16 ? pix_bytes_of<PixGen::U16>
-           : g == PixGen::F32 ? pix_bytes_of<PixGen::F32>
-           : g == PixGen::RgbF32 ? pix_bytes_of<PixGen::RgbF32>
-                              : pix_bytes_of<PixGen::Grey>;
-}
-inline int pix_channels(PixGen g)
-{
-    return g == PixGen::Rgb      ? Pix<PixGen::Rgb>::NCH
-           : g == PixGen::U16    ? Pix<PixGen::U16>::NCH
-           : g == PixGen::F32    ? Pix<PixGen::F32>::NCH
-           : g == PixGen::RgbF32 ? Pix<PixGen::RgbF32>::NCH
-                                 : Pix<PixGen::Grey>::NCH;
-}
-// the name of a format in messages
-inline const char *pix_name(PixGen g)
-{
-    return g == PixGen::Rgb ? "colour" : g == PixGen::U16 ? "16-bit" : g == PixGen::F32 ? "float" : g == PixGen::RgbF32 ? "float colour" : "8-bit";
-}
-// the float formats (admitted after the finite check only) and the floats per pixel the check runs over
-inline bool pix_is_float(PixGen g) { return g == PixGen::F32 || g == PixGen::RgbF32; }
 
 // ---- LDS-DMA staging ---------------------------------------------------------------------------
 // global_load_lds_dwordx4: 64 lanes x 16 B land at LDS byte offset (wave-uniform base) + lane * 16, no
@@ -533,6 +560,23 @@ __device__ __forceinline__ void lds_dma_copy(const void *gsrc, void *ldst, int p
 }
 
 // ---- stage implementations (device pointers, all on ctx->stream) -----------------
+
+// extra signal planes of the _signals entry points (nullptr: the guide alone): float [nsig][N] in and out, device pointers
+// (comm.hip's multi_run takes the host planes of the glf_multi_ entry points in one)
+struct SignalPlanes {
+    int nsig;
+    const float *d_sig;
+    float *d_out;
+};
+// The whole approximate path behind every glf_image_processing_* and glf_multi_image_processing_* entry point and glf_graph_build
+// (pipeline.hip). gen: the guide's pixel format; d_img and d_out are [N] pixels of it, d_zf (optional; null for the float formats,
+// whose d_out is z itself) its [NCH][N] floats. It alone checks the pointers, the sizes, sig's plane count, the struct sizes and
+// that a float guide is finite. A colour, 16-bit or float guide has no 8-bit y: its channels are filtered as planes (formed inside
+// from the image) and written to d_out; sig there: float planes that ride along in the same two passes over Phi. (Hidden: an
+// internal entry shared by three translation units, not one of the library's dynamic symbols.)
+__attribute__((visibility("hidden"))) int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img,
+                                                               int width, int height, uint8_t *d_out, float *d_zf, double *eigvals_out,
+                                                               glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
 
 // Sample table: float4 {row, col, value, 0} per sample (float colour: and the value block behind the padded records) + mask + device idx.
 struct SampleTables {

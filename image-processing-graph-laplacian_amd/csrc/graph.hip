@@ -182,8 +182,7 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
     if (m > PANEL_COLS)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: a graph handle takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
     const unsigned ld = ld_for(m);
-    const PixGen gen = pix == GLF_PIX_RGB8 ? PixGen::Rgb : pix == GLF_PIX_U16 ? PixGen::U16 : pix == GLF_PIX_F32 ? PixGen::F32
-                       : pix == GLF_PIX_RGBF32 ? PixGen::RgbF32 : PixGen::Grey;
+    const PixGen gen = pixgen_of_pix(pix);
     glf_graph *g = new (std::nothrow) glf_graph;
     if (!g) return set_error(ctx, GLF_ERR_NOMEM, "glf_graph_build: host allocation");
     g->ctx = ctx;
@@ -200,31 +199,13 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
     }
     if (rc == GLF_OK) {
         DevBuf<uint8_t> img_out; // the call's filtered image: not kept
-        rc = img_out.alloc(ctx, (size_t)N * pix_bytes(gen));
+        rc = img_out.alloc(ctx, (size_t)N * pix_desc(gen).bytes);
         glf_capture cap{};
         cap.struct_size = sizeof(glf_capture);
         cap.d_phi = g->phi;
         cap.phi_floats = (size_t)N * ld;
-        if (rc == GLF_OK) switch (gen) {
-            case PixGen::Grey:
-                rc = glf_image_processing_capture(ctx, &opt, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap);
-                break;
-            case PixGen::Rgb:
-                rc = glf_image_processing_rgb_capture(ctx, &opt, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap);
-                break;
-            case PixGen::U16:
-                rc = glf_image_processing_u16_capture(ctx, &opt, static_cast<const uint16_t *>(d_img), width, height,
-                                                      reinterpret_cast<uint16_t *>(img_out.p), nullptr, g->lam.data(), &S, &cap);
-                break;
-            case PixGen::F32:
-                rc = glf_image_processing_f32_capture(ctx, &opt, static_cast<const float *>(d_img), width, height, reinterpret_cast<float *>(img_out.p),
-                                                      g->lam.data(), &S, &cap);
-                break;
-            case PixGen::RgbF32:
-                rc = glf_image_processing_rgbf32_capture(ctx, &opt, static_cast<const float *>(d_img), width, height,
-                                                         reinterpret_cast<float *>(img_out.p), g->lam.data(), &S, &cap);
-                break;
-            }
+        if (rc == GLF_OK) // (no float z: the handle keeps Phi and the eigenvalues only)
+            rc = image_processing_run(ctx, &opt, gen, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap, nullptr);
         if (rc == GLF_OK && (S.m != m || cap.ld != ld))
             rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised m=%u ld=%u, %u / %u expected", S.m, cap.ld, m, ld);
         if (rc == GLF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GLF_ERR_HIP, "glf_graph_build: synchronize");

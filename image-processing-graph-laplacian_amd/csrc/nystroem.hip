@@ -871,12 +871,10 @@ int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height,
         }
         if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour, 16-bit, float and float colour kernels have no 8-bit y for Phi^T y");
         window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
-#define GLF_NYS_EW(G_) nystroem_entrywise<G_>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window, entries_evaluated)
-        rc = gen == PixGen::Rgb   ? GLF_NYS_EW(PixGen::Rgb)
-             : gen == PixGen::U16 ? GLF_NYS_EW(PixGen::U16)
-             : gen == PixGen::F32 ? GLF_NYS_EW(PixGen::F32)
-                                  : GLF_NYS_EW(PixGen::RgbF32);
-#undef GLF_NYS_EW
+        pix_dispatch_raw(gen, [&](auto t) {
+            rc = nystroem_entrywise<t.G>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window,
+                                         entries_evaluated);
+        });
         if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
         return rc;
     }

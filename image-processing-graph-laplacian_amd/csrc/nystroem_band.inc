@@ -1058,7 +1058,7 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(colscale.alloc(ctx, ld_total));
     GLF_TRY(inv.alloc(ctx, ld_total));
     GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    if (raw) GLF_TRY(svals32.alloc(ctx, svals32_planes(gen) * p));
+    if (raw) GLF_TRY(svals32.alloc(ctx, (size_t)pix_desc(gen).svals32_planes * p));
     GLF_TRY(chunks.alloc(ctx, (size_t)bt.nr * bt.ksc * band_chunk_bytes(mb)));
     const size_t wgs = band_px_wgs(bt, nrows);
     if (flt) d_c = nullptr; // (c was needed before this launch: c_from_ysum)
@@ -1066,14 +1066,14 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(band_eval_zero(ctx, dev_eval));
     band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);
     if (raw) {
-        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals32_what(gen), svals32.p);
+        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, pix_desc(gen).svals32_what, svals32.p);
         GLF_LAUNCH_CHECK(ctx);
     } else GLF_TRY(band_svals(ctx, d_samples, p, svals));
     if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     float band_ms = 0.f;
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
-        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p, (int)svals32_planes(gen)));
+        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p, pix_desc(gen).svals32_planes));
         const bool timed = stats && (int)cb < glf_ctx::CP_RING;
         if (timed)
             for (int q = 0; q < 2; ++q)
@@ -1083,12 +1083,14 @@ static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, i
         if (raw) {
             float *po = d_phi + c0;
             const float nsval = -coef.s_val;
-#define GLF_BAND_PX(MB_, G_) launch_band_px<MB_, 0, G_>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster, nullptr, dev_eval.p, nullptr, pix0, nsval)
-            if (gen == PixGen::Rgb) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::Rgb) : GLF_BAND_PX(1, PixGen::Rgb));
-            else if (gen == PixGen::U16) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::U16) : GLF_BAND_PX(1, PixGen::U16));
-            else if (gen == PixGen::F32) GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::F32) : GLF_BAND_PX(1, PixGen::F32));
-            else GLF_TRY(mb == 2 ? GLF_BAND_PX(2, PixGen::RgbF32) : GLF_BAND_PX(1, PixGen::RgbF32));
-#undef GLF_BAND_PX
+            int rc = GLF_OK;
+            pix_dispatch_raw(gen, [&](auto t) { // (these formats' k_band exists for one and two column blocks only)
+                rc = mb == 2 ? launch_band_px<2, 0, t.G>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster,
+                                                         nullptr, dev_eval.p, nullptr, pix0, nsval)
+                             : launch_band_px<1, 0, t.G>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster,
+                                                         nullptr, dev_eval.p, nullptr, pix0, nsval);
+            });
+            GLF_TRY(rc);
         } else if (mb == 2)
             GLF_TRY(launch_band_px<2>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,
                                       raster, d_c ? cpart.p : nullptr, dev_eval.p, flt, pix0));

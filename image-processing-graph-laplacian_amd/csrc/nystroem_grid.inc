@@ -1346,7 +1346,7 @@ __global__ __launch_bounds__(256) void k_gridop_svals(const float4 *__restrict__
 
 // the colour, 16-bit and float formats' sample values as u32 [nr][nc]. what = 0: the 16-bit value (record's z); 1: the packed colour
 // (its w); 2: the bit pattern of the float value (its z); 3 (float colour): three planes [3][nr][nc], the bit patterns of R, G and B
-// from the value block behind the padded records
+// from the value block behind the padded records. The host takes `what` and the planes from the format table (PixDesc::svals32_*)
 __global__ __launch_bounds__(256) void k_gridop_svals32(const float4 *__restrict__ samples, unsigned p, int what, unsigned *__restrict__ svals)
 {
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
@@ -1359,9 +1359,6 @@ __global__ __launch_bounds__(256) void k_gridop_svals32(const float4 *__restrict
     } else
         svals[s] = what == 2 ? __float_as_uint(samples[s].z) : (unsigned)(what == 1 ? samples[s].w : samples[s].z);
 }
-inline int svals32_what(glf::PixGen g) { return g == glf::PixGen::Rgb ? 1 : g == glf::PixGen::F32 ? 2 : g == glf::PixGen::RgbF32 ? 3 : 0; }
-// u32 values per sample in that image
-inline size_t svals32_planes(glf::PixGen g) { return g == glf::PixGen::RgbF32 ? 3 : 1; }
 
 #include "nystroem_rank.inc"
 #include "nystroem_band.inc"
@@ -1448,8 +1445,8 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
     op->gen = pixgen_of(coef.kernel);
     op->nsval = -coef.s_val;
     if (band_only) {
-        GLF_TRY(op->svals32.alloc(ctx, svals32_planes(op->gen) * p));
-        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, svals32_what(op->gen), op->svals32.p);
+        GLF_TRY(op->svals32.alloc(ctx, (size_t)pix_desc(op->gen).svals32_planes * p));
+        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, pix_desc(op->gen).svals32_what, op->svals32.p);
     } else {
         GLF_TRY(op->svals.alloc(ctx, p));
         hipLaunchKernelGGL(k_gridop_svals, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, op->svals.p);
@@ -1538,15 +1535,13 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         for (unsigned c0 = 0; c0 < ld_total; c0 += LD) {
             const bool raw = op->gen != PixGen::Grey;
             const uint8_t *sv = raw ? reinterpret_cast<const uint8_t *>(op->svals32.p) : op->svals.p;
-            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->colscale.p + c0, sv, raw, nr, nc, ksc, NT, op->band_chunks.p, (int)svals32_planes(op->gen)));
-#define GLF_BAND_SAMPLES(G_) launch_band_samples<NT, G_>(ctx, *op->band, sv, a0, nrows, op->band_chunks.p, op->band_inv.p + c0, Y + c0, (int)ld_total, \
-                                                         X + c0, (int)ld_total, d_degree, (float)alpha, nullptr, op->nsval)
-            GLF_TRY(op->gen == PixGen::Rgb   ? GLF_BAND_SAMPLES(PixGen::Rgb)
-                    : op->gen == PixGen::U16 ? GLF_BAND_SAMPLES(PixGen::U16)
-                    : op->gen == PixGen::F32 ? GLF_BAND_SAMPLES(PixGen::F32)
-                    : op->gen == PixGen::RgbF32 ? GLF_BAND_SAMPLES(PixGen::RgbF32)
-                                             : GLF_BAND_SAMPLES(PixGen::Grey));
-#undef GLF_BAND_SAMPLES
+            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->colscale.p + c0, sv, raw, nr, nc, ksc, NT, op->band_chunks.p, pix_desc(op->gen).svals32_planes));
+            int rc = GLF_OK;
+            pix_dispatch(op->gen, [&](auto t) {
+                rc = launch_band_samples<NT, t.G>(ctx, *op->band, sv, a0, nrows, op->band_chunks.p, op->band_inv.p + c0, Y + c0, (int)ld_total, X + c0,
+                                                  (int)ld_total, d_degree, (float)alpha, nullptr, op->nsval);
+            });
+            GLF_TRY(rc);
         }
         return GLF_OK;
     }

@@ -172,13 +172,11 @@ int glf_image_processing_batch(glf_ctx *const *ctxs, int nctx, const glf_options
 // ------------------------------------------------------------------------------------------
 
 // the float formats admit finite values only: one pass over the image's floats (nch per pixel) before anything else
-static int f32_admit(glf_ctx *ctx, const float *d_img, int width, int height, int nch = 1)
+static int f32_admit(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height)
 {
     bool finite = true;
-    GLF_TRY(f32_all_finite(ctx, d_img, (int64_t)width * height * nch, &finite));
-    if (!finite)
-        return set_error(ctx, GLF_ERR_INVALID, nch == 1 ? "the float image holds a NaN or an Inf: finite values only"
-                                                        : "the float colour image holds a NaN or an Inf: finite values only");
+    GLF_TRY(f32_all_finite(ctx, reinterpret_cast<const float *>(d_img), (int64_t)width * height * pix_desc(gen).channels, &finite));
+    if (!finite) return set_error(ctx, GLF_ERR_INVALID, "the %s image holds a NaN or an Inf: finite values only", pix_desc(gen).name);
     return GLF_OK;
 }
 
@@ -191,8 +189,7 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
     if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3)) // (nlm.hip reflects an out-of-image patch index once: valid from 3 pixels on)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     GLF_ENTER(ctx);
-    if (pix_is_float(pixgen_of(kernel)))
-        GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height, pix_channels(pixgen_of(kernel))));
+    if (pix_desc(pixgen_of(kernel)).is_float) GLF_TRY(f32_admit(ctx, pixgen_of(kernel), d_img, width, height));
     const unsigned p = sample_size;
     SampleTables tb;
     GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3]; U16: uint16_t; F32: float; RGBF32: float [height][width][3])
@@ -527,36 +524,29 @@ int glf_EntireComputation(glf_ctx *ctx, const uint8_t *d_img, int width, int hei
 // Whole approximate path
 // ------------------------------------------------------------------------------------------
 
-int glf_image_processing(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height,
-                         uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats)
+// (an image of any format travels as a byte pointer)
+static inline const uint8_t *bytes_of(const void *q) { return static_cast<const uint8_t *>(q); }
+static inline uint8_t *bytes_of(void *q) { return static_cast<uint8_t *>(q); }
+
+// Every typed entry point forwards to glf::image_processing_run with its format: the checks are there. (The float formats' output is
+// z itself, interleaved as the image: no d_zf.)
+
+int glf_image_processing(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, uint8_t *d_out, float *d_zf,
+                         double *eigvals_out, glf_stats *stats)
 {
-    return glf_image_processing_capture(ctx, opt_in, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
+    return image_processing_run(ctx, opt, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, nullptr);
 }
 
-// extra signal planes of glf_image_processing_signals (nullptr: the guide alone)
-struct SignalPlanes {
-    int nsig;
-    const float *d_sig;
-    float *d_out;
-};
-
-// gen: the guide's pixel format; d_img and d_out are [N] pixels of it. A colour or 16-bit guide has no 8-bit y: its channels are
-// filtered as planes (formed inside from the image) and written to d_out; sig there: float planes that ride along in the same two
-// passes over Phi (glf_image_processing_rgb_signals / _u16_signals).
-static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
-                                uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
-
-int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt_in, const uint8_t *d_img, int width, int height,
-                                 uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
+int glf_image_processing_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, uint8_t *d_out,
+                                 float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    return image_processing_run(ctx, opt_in, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, nullptr);
+    return image_processing_run(ctx, opt, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_img, int width, int height, int nsig,
                                  const float *d_sig, float *d_sig_out, uint8_t *d_out, float *d_zf, double *eigvals_out,
                                  glf_stats *stats)
 {
-    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
     return image_processing_run(ctx, opt, PixGen::Grey, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr, &sig);
 }
@@ -564,35 +554,31 @@ int glf_image_processing_signals(glf_ctx *ctx, const glf_options *opt, const uin
 int glf_image_processing_rgb(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                              float *d_zf, double *eigvals_out, glf_stats *stats)
 {
-    return glf_image_processing_rgb_capture(ctx, opt, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr);
+    return image_processing_run(ctx, opt, PixGen::Rgb, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr, nullptr);
 }
 
 int glf_image_processing_rgb_capture(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, uint8_t *d_out_rgb,
                                      float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     return image_processing_run(ctx, opt, PixGen::Rgb, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_u16(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
                              float *d_zf, double *eigvals_out, glf_stats *stats)
 {
-    return glf_image_processing_u16_capture(ctx, opt, d_img, width, height, d_out, d_zf, eigvals_out, stats, nullptr);
+    return image_processing_run(ctx, opt, PixGen::U16, bytes_of(d_img), width, height, bytes_of(d_out), d_zf, eigvals_out, stats, nullptr, nullptr);
 }
 
 int glf_image_processing_u16_capture(glf_ctx *ctx, const glf_options *opt, const uint16_t *d_img, int width, int height, uint16_t *d_out,
                                      float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    return image_processing_run(ctx, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(d_img), width, height,
-                                reinterpret_cast<uint8_t *>(d_out), d_zf, eigvals_out, stats, cap, nullptr);
+    return image_processing_run(ctx, opt, PixGen::U16, bytes_of(d_img), width, height, bytes_of(d_out), d_zf, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_rgb_signals(glf_ctx *ctx, const glf_options *opt, const uint8_t *d_rgb, int width, int height, int nsig,
                                      const float *d_sig, float *d_sig_out, uint8_t *d_out_rgb, float *d_zf, double *eigvals_out,
                                      glf_stats *stats)
 {
-    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
     return image_processing_run(ctx, opt, PixGen::Rgb, d_rgb, width, height, d_out_rgb, d_zf, eigvals_out, stats, nullptr, &sig);
 }
@@ -601,58 +587,46 @@ int glf_image_processing_u16_signals(glf_ctx *ctx, const glf_options *opt, const
                                      const float *d_sig, float *d_sig_out, uint16_t *d_out, float *d_zf, double *eigvals_out,
                                      glf_stats *stats)
 {
-    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
-    return image_processing_run(ctx, opt, PixGen::U16, reinterpret_cast<const uint8_t *>(d_img), width, height,
-                                reinterpret_cast<uint8_t *>(d_out), d_zf, eigvals_out, stats, nullptr, &sig);
+    return image_processing_run(ctx, opt, PixGen::U16, bytes_of(d_img), width, height, bytes_of(d_out), d_zf, eigvals_out, stats, nullptr, &sig);
 }
 
 int glf_image_processing_f32(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, float *d_out,
                              double *eigvals_out, glf_stats *stats)
 {
-    return glf_image_processing_f32_capture(ctx, opt, d_img, width, height, d_out, eigvals_out, stats, nullptr);
+    return image_processing_run(ctx, opt, PixGen::F32, bytes_of(d_img), width, height, bytes_of(d_out), nullptr, eigvals_out, stats, nullptr, nullptr);
 }
 
-// (the float output is z itself: no d_zf)
 int glf_image_processing_f32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, float *d_out,
                                      double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    return image_processing_run(ctx, opt, PixGen::F32, reinterpret_cast<const uint8_t *>(d_img), width, height,
-                                reinterpret_cast<uint8_t *>(d_out), nullptr, eigvals_out, stats, cap, nullptr);
+    return image_processing_run(ctx, opt, PixGen::F32, bytes_of(d_img), width, height, bytes_of(d_out), nullptr, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_f32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_img, int width, int height, int nsig,
                                      const float *d_sig, float *d_sig_out, float *d_out, double *eigvals_out, glf_stats *stats)
 {
-    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
-    return image_processing_run(ctx, opt, PixGen::F32, reinterpret_cast<const uint8_t *>(d_img), width, height,
-                                reinterpret_cast<uint8_t *>(d_out), nullptr, eigvals_out, stats, nullptr, &sig);
+    return image_processing_run(ctx, opt, PixGen::F32, bytes_of(d_img), width, height, bytes_of(d_out), nullptr, eigvals_out, stats, nullptr, &sig);
 }
 
 int glf_image_processing_rgbf32(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, float *d_out_rgb,
                                 double *eigvals_out, glf_stats *stats)
 {
-    return glf_image_processing_rgbf32_capture(ctx, opt, d_rgb, width, height, d_out_rgb, eigvals_out, stats, nullptr);
+    return image_processing_run(ctx, opt, PixGen::RgbF32, bytes_of(d_rgb), width, height, bytes_of(d_out_rgb), nullptr, eigvals_out, stats, nullptr, nullptr);
 }
 
-// (the float output is z itself, interleaved as the image: no d_zf)
 int glf_image_processing_rgbf32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height,
                                         float *d_out_rgb, double *eigvals_out, glf_stats *stats, glf_capture *cap)
 {
-    if (!ctx || !d_rgb || !d_out_rgb || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    return image_processing_run(ctx, opt, PixGen::RgbF32, reinterpret_cast<const uint8_t *>(d_rgb), width, height,
-                                reinterpret_cast<uint8_t *>(d_out_rgb), nullptr, eigvals_out, stats, cap, nullptr);
+    return image_processing_run(ctx, opt, PixGen::RgbF32, bytes_of(d_rgb), width, height, bytes_of(d_out_rgb), nullptr, eigvals_out, stats, cap, nullptr);
 }
 
 int glf_image_processing_rgbf32_signals(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height, int nsig,
                                         const float *d_sig, float *d_sig_out, float *d_out_rgb, double *eigvals_out, glf_stats *stats)
 {
-    if (!ctx || nsig < 1 || nsig > GLF_MAX_SIGNALS || !d_sig || !d_sig_out) return GLF_ERR_INVALID;
     const SignalPlanes sig{nsig, d_sig, d_sig_out};
-    return image_processing_run(ctx, opt, PixGen::RgbF32, reinterpret_cast<const uint8_t *>(d_rgb), width, height,
-                                reinterpret_cast<uint8_t *>(d_out_rgb), nullptr, eigvals_out, stats, nullptr, &sig);
+    return image_processing_run(ctx, opt, PixGen::RgbF32, bytes_of(d_rgb), width, height, bytes_of(d_out_rgb), nullptr, eigvals_out, stats, nullptr, &sig);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -807,7 +781,7 @@ int glf_operator_apply(glf_operator *op, const glf_mat *X, glf_mat *Y, glf_opera
     const unsigned ld = (unsigned)X->ld;
     if (!op->gop && !valid_ld(ld)) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the stored L_A takes ld 32, 64, 128 or 256 (ld = %u)", ld);
     if (op->gop && op->gen != PixGen::Grey && ld != 32 && ld != 64)
-        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the %s band form takes ld 32 or 64 (ld = %u)", pix_name(op->gen), ld);
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: the %s band form takes ld 32 or 64 (ld = %u)", pix_desc(op->gen).name, ld);
     if (op->gop && ld != 32 && ld % 64) // (grid_op_apply walks the block 64 columns at a time from ld 64 on)
         return set_error(ctx, GLF_ERR_INVALID, "glf_operator_apply: a factored form takes ld 32, 64, 128, 192 or 256 (ld = %u)", ld);
     GLF_TRY(block_matvec(ctx, op->store.LA.p, op->store.lda, p, X->data, Y->data, ld, shard_arg(op->shard)));
@@ -845,14 +819,18 @@ int glf_operator_destroy(glf_operator *op)
     return GLF_OK;
 }
 
-static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height,
-                                uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
+} // extern "C"
+
+int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height, uint8_t *d_out,
+                              float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
 {
+    // (all of these answer GLF_ERR_INVALID and leave last_error alone)
     if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    if (sig && (sig->nsig < 1 || sig->nsig > GLF_MAX_SIGNALS || !sig->d_sig || !sig->d_out)) return GLF_ERR_INVALID;
     if (cap && cap->struct_size != sizeof(glf_capture))
         return set_error(ctx, GLF_ERR_INVALID, "glf_capture.struct_size %u != %zu", cap->struct_size, sizeof(glf_capture));
     GLF_ENTER(ctx);
-    if (pix_is_float(gen)) GLF_TRY(f32_admit(ctx, reinterpret_cast<const float *>(d_img), width, height, pix_channels(gen))); // (before anything else)
+    if (pix_desc(gen).is_float) GLF_TRY(f32_admit(ctx, gen, d_img, width, height)); // (before anything else)
     pool_age(ctx);
     glf_options opt;
     glf_options_default(&opt);
@@ -865,17 +843,14 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     // GLF_KERNEL_BILATERAL stands there), the 8-bit entry points no kernel of another format. The colour and 16-bit guides have no
     // 8-bit y: their values are filtered as planes (u8_guide false)
     const bool u8_guide = gen == PixGen::Grey;
-    if (!u8_guide && opt.kernel == GLF_KERNEL_BILATERAL) opt.kernel = bilateral_kernel_of(gen);
+    if (!u8_guide && opt.kernel == GLF_KERNEL_BILATERAL) opt.kernel = pix_desc(gen).kernel;
     if (pixgen_of(opt.kernel) != gen) {
         if (!u8_guide) {
-            const char *what = pix_name(gen);
+            const char *what = pix_desc(gen).name;
             return set_error(ctx, GLF_ERR_UNSUPPORTED, "%s filtering: kernel %d (the %s bilateral kernel only)", what, opt.kernel, what);
         }
-        return set_error(ctx, GLF_ERR_UNSUPPORTED,
-                         pixgen_of(opt.kernel) == PixGen::Rgb      ? "the colour kernel takes an RGB image: glf_image_processing_rgb"
-                         : pixgen_of(opt.kernel) == PixGen::F32    ? "the float kernel takes a float image: glf_image_processing_f32"
-                         : pixgen_of(opt.kernel) == PixGen::RgbF32 ? "the float colour kernel takes a float RGB image: glf_image_processing_rgbf32"
-                                                                   : "the 16-bit kernel takes a 16-bit image: glf_image_processing_u16");
+        const PixDesc &k = pix_desc(pixgen_of(opt.kernel));
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the %s kernel takes %s: %s", k.name, k.image, k.entry);
     }
     if (opt.kernel < GLF_KERNEL_BILATERAL || opt.kernel > GLF_KERNEL_BILATERAL_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "kernel %d", opt.kernel);
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
@@ -906,7 +881,7 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     SignalPlanes guide_sig{};
     const SignalPlanes *planes = nullptr; // a colour or 16-bit guide's extra planes (its own kernels read the channels from the image)
     if (!u8_guide) {
-        const int nch = pix_channels(gen);
+        const int nch = pix_desc(gen).channels;
         planes = sig;
         if (!planes) {
             GLF_TRY(guide_planes.alloc(ctx, (size_t)nch * N));
@@ -1424,5 +1399,3 @@ static int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen 
     }
     return GLF_OK;
 }
-
-} // extern "C"

@@ -10,6 +10,7 @@ C-ABI does: ComputeAffinityMatrices, ComputeLaplacianMatrix,
 InversePowerIteration, OrthonormaliseVecs, Nystroem, Permutation,
 ComputeResultFromLaplacian, plus image_processing for the whole path.
 """
+import collections
 import ctypes as C
 import functools
 import os
@@ -73,6 +74,20 @@ EXPORTS = [
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
+# The guide formats, one row per PIX_*: everything the image_processing* methods of Context and Multi and Context.graph know of a
+# format. torch_dtype / zeros_dtype are names (torch is looked up per context): torch fills no uint16, so the 16-bit outputs are
+# allocated as int16 and viewed as uint16. float_out: the output is the float z itself, so the call takes and returns no zf.
+# suffix: the entry points are glf_[multi_]image_processing<suffix>[_capture | _signals].
+# wait_stream: the plain call orders the context's stream behind the caller's before the library reads the image; the 8-bit
+# call never did (its callers hand it images that are complete), and it is the call the benchmark times.
+_PixFormat = collections.namedtuple("_PixFormat", "np_dtype torch_dtype zeros_dtype channels float_out suffix wait_stream")
+_PIX_FORMATS = {
+    PIX_U8: _PixFormat(np.uint8, "uint8", "uint8", 1, False, "", False),
+    PIX_RGB8: _PixFormat(np.uint8, "uint8", "uint8", 3, False, "_rgb", True),
+    PIX_U16: _PixFormat(np.uint16, "uint16", "int16", 1, False, "_u16", True),
+    PIX_F32: _PixFormat(np.float32, "float32", "float32", 1, True, "_f32", True),
+    PIX_RGBF32: _PixFormat(np.float32, "float32", "float32", 3, True, "_rgbf32", True),
+}
 GRAPH_MAX_OUTPUTS = 32
 GRAPH_MAX_PLANES = 32      # GLF_GRAPH_MAX_PLANES: the most planes of one glf_graph_project_wide call
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
@@ -709,12 +724,67 @@ class Multi:
 
     def image_processing(self, img, opt=None, want_float=False):
         """Host image in, host image out (glf_multi_image_processing): (out u8 [H, W], zf f32 [H, W] or None, per-rank infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        h, w = img.shape
+        return self._image_processing(PIX_U8, img, None, opt, want_float)
+
+    def image_processing_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_signals: the host image plus float planes [nsig, H, W] (numpy, replicated on every
+        rank) filtered through the image's graph. Returns (out u8 [H, W], zf f32 [H, W], sig_out f32 [nsig, H, W], infos)."""
+        return self._image_processing(PIX_U8, img, signals, opt, True)
+
+    def image_processing_rgb(self, img, opt=None, want_float=False):
+        """glf_multi_image_processing_rgb: host uint8 [H, W, 3] in, (out u8 [H, W, 3], zf f32 [3, H, W] or None, per-rank infos)."""
+        return self._image_processing(PIX_RGB8, img, None, opt, want_float)
+
+    def image_processing_u16(self, img, opt=None, want_float=False):
+        """glf_multi_image_processing_u16: host uint16 [H, W] in, (out uint16 [H, W], zf f32 [H, W] or None, per-rank infos)."""
+        return self._image_processing(PIX_U16, img, None, opt, want_float)
+
+    def image_processing_rgb_signals(self, img, signals, opt=None, want_float=False):
+        """glf_multi_image_processing_rgb_signals: host uint8 [H, W, 3] plus float planes [nsig, H, W] filtered through the colour
+        graph. Returns (out u8 [H, W, 3], zf f32 [3, H, W] or None, sig_out f32 [nsig, H, W], infos)."""
+        return self._image_processing(PIX_RGB8, img, signals, opt, want_float)
+
+    def image_processing_u16_signals(self, img, signals, opt=None, want_float=False):
+        """glf_multi_image_processing_u16_signals: host uint16 [H, W] plus float planes [nsig, H, W] filtered through the 16-bit
+        graph. Returns (out uint16 [H, W], zf f32 [H, W] or None, sig_out f32 [nsig, H, W], infos)."""
+        return self._image_processing(PIX_U16, img, signals, opt, want_float)
+
+    def image_processing_f32(self, img, opt=None):
+        """glf_multi_image_processing_f32: host float32 [H, W] in (finite values), (z float32 [H, W], per-rank infos)."""
+        return self._image_processing(PIX_F32, img, None, opt, False)
+
+    def image_processing_f32_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_f32_signals: host float32 [H, W] plus float planes [nsig, H, W] filtered through the float
+        image's graph. Returns (z float32 [H, W], sig_out f32 [nsig, H, W], infos)."""
+        return self._image_processing(PIX_F32, img, signals, opt, False)
+
+    def image_processing_rgbf32(self, img, opt=None):
+        """glf_multi_image_processing_rgbf32: host float32 [H, W, 3] in (finite values), (z float32 [H, W, 3], per-rank infos)."""
+        return self._image_processing(PIX_RGBF32, img, None, opt, False)
+
+    def image_processing_rgbf32_signals(self, img, signals, opt=None):
+        """glf_multi_image_processing_rgbf32_signals: host float32 [H, W, 3] plus float planes [nsig, H, W] filtered through the
+        float colour graph. Returns (z float32 [H, W, 3], sig_out f32 [nsig, H, W], infos)."""
+        return self._image_processing(PIX_RGBF32, img, signals, opt, False)
+
+    def _image_processing(self, fmt, img, signals, opt, want_float):
+        """Every image_processing* method: the host image of format fmt (a PIX_*) and, with signals, float planes [nsig, H, W]
+        through glf_multi_image_processing<suffix>[_signals]. Returns (out, [zf or None,] [sig_out,] per-rank infos): zf is left
+        out for the float formats, whose out is the float z."""
+        f = _PIX_FORMATS[fmt]
+        img = np.ascontiguousarray(img, dtype=f.np_dtype)
+        if fmt != PIX_U8 and not _pix_shape_ok(f, img):   # (the 8-bit calls never checked: a wrong shape fails in the unpacking below)
+            raise ValueError("image must be %s, got %s" % ("[H, W, 3]" if f.channels == 3 else "[H, W]", img.shape))
+        h, w = img.shape[:2] if f.channels == 3 else img.shape
+        fn, sig, sig_out = "glf_multi_image_processing" + f.suffix, (), ()
+        if signals is not None:
+            planes, planes_out = self._planes(signals, h, w)
+            fn, sig, sig_out = fn + "_signals", (C.c_int(planes.shape[0]), _ptr(planes), _ptr(planes_out)), (planes_out,)
         opt = opt or default_options()
-        out = np.zeros((h, w), dtype=np.uint8)
-        zf = np.zeros((h, w), dtype=np.float32) if want_float else None
-        return out, zf, self._run("glf_multi_image_processing", opt, img, out, zf)
+        out = np.zeros(img.shape, dtype=f.np_dtype)
+        zf = np.zeros((3, h, w) if f.channels == 3 else (h, w), dtype=np.float32) if want_float and not f.float_out else None
+        infos = self._run(fn, opt, img, out, zf, sig=sig, no_zf=f.float_out)
+        return (out,) + (() if f.float_out else (zf,)) + sig_out + (infos,)
 
     def _run(self, fn, opt, img, out, zf, sig=(), no_zf=False):
         """glf_multi_<...>(world, opt, img, width, height, [nsig, planes, planes out,] out, zf, eigvals, stats): per-rank infos.
@@ -727,117 +797,6 @@ class Multi:
         if rc != OK:
             raise GlfError(rc, fn + ": " + _lib.glf_multi_last_error(self._w).decode())
         return [_info(s, lam) for s in stats]
-
-    def image_processing_signals(self, img, signals, opt=None):
-        """glf_multi_image_processing_signals: the host image plus float planes [nsig, H, W] (numpy, replicated on every
-        rank) filtered through the image's graph. Returns (out u8 [H, W], zf f32 [H, W], sig_out f32 [nsig, H, W], infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        h, w = img.shape
-        sig = np.ascontiguousarray(signals, dtype=np.float32)
-        if sig.ndim != 3 or sig.shape[1:] != (h, w):
-            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, sig.shape))
-        opt = opt or default_options()
-        out = np.zeros((h, w), dtype=np.uint8)
-        zf = np.zeros((h, w), dtype=np.float32)
-        sig_out = np.zeros(sig.shape, dtype=np.float32)
-        infos = self._run("glf_multi_image_processing_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
-        return out, zf, sig_out, infos
-
-    def image_processing_rgb(self, img, opt=None, want_float=False):
-        """glf_multi_image_processing_rgb: host uint8 [H, W, 3] in, (out u8 [H, W, 3], zf f32 [3, H, W] or None, per-rank infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
-        h, w = img.shape[:2]
-        opt = opt or default_options()
-        out = np.zeros((h, w, 3), dtype=np.uint8)
-        zf = np.zeros((3, h, w), dtype=np.float32) if want_float else None
-        return out, zf, self._run("glf_multi_image_processing_rgb", opt, img, out, zf)
-
-    def image_processing_u16(self, img, opt=None, want_float=False):
-        """glf_multi_image_processing_u16: host uint16 [H, W] in, (out uint16 [H, W], zf f32 [H, W] or None, per-rank infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint16)
-        if img.ndim != 2:
-            raise ValueError("image must be [H, W], got %s" % (img.shape,))
-        h, w = img.shape
-        opt = opt or default_options()
-        out = np.zeros((h, w), dtype=np.uint16)
-        zf = np.zeros((h, w), dtype=np.float32) if want_float else None
-        return out, zf, self._run("glf_multi_image_processing_u16", opt, img, out, zf)
-
-    def image_processing_rgb_signals(self, img, signals, opt=None, want_float=False):
-        """glf_multi_image_processing_rgb_signals: host uint8 [H, W, 3] plus float planes [nsig, H, W] filtered through the colour
-        graph. Returns (out u8 [H, W, 3], zf f32 [3, H, W] or None, sig_out f32 [nsig, H, W], infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint8)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
-        h, w = img.shape[:2]
-        sig, sig_out = self._planes(signals, h, w)
-        opt = opt or default_options()
-        out = np.zeros((h, w, 3), dtype=np.uint8)
-        zf = np.zeros((3, h, w), dtype=np.float32) if want_float else None
-        infos = self._run("glf_multi_image_processing_rgb_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
-        return out, zf, sig_out, infos
-
-    def image_processing_u16_signals(self, img, signals, opt=None, want_float=False):
-        """glf_multi_image_processing_u16_signals: host uint16 [H, W] plus float planes [nsig, H, W] filtered through the 16-bit
-        graph. Returns (out uint16 [H, W], zf f32 [H, W] or None, sig_out f32 [nsig, H, W], infos)."""
-        img = np.ascontiguousarray(img, dtype=np.uint16)
-        if img.ndim != 2:
-            raise ValueError("image must be [H, W], got %s" % (img.shape,))
-        h, w = img.shape
-        sig, sig_out = self._planes(signals, h, w)
-        opt = opt or default_options()
-        out = np.zeros((h, w), dtype=np.uint16)
-        zf = np.zeros((h, w), dtype=np.float32) if want_float else None
-        infos = self._run("glf_multi_image_processing_u16_signals", opt, img, out, zf, sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)))
-        return out, zf, sig_out, infos
-
-    def image_processing_f32(self, img, opt=None):
-        """glf_multi_image_processing_f32: host float32 [H, W] in (finite values), (z float32 [H, W], per-rank infos)."""
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        if img.ndim != 2:
-            raise ValueError("image must be [H, W], got %s" % (img.shape,))
-        opt = opt or default_options()
-        out = np.zeros(img.shape, dtype=np.float32)
-        return out, self._run("glf_multi_image_processing_f32", opt, img, out, None, no_zf=True)
-
-    def image_processing_f32_signals(self, img, signals, opt=None):
-        """glf_multi_image_processing_f32_signals: host float32 [H, W] plus float planes [nsig, H, W] filtered through the float
-        image's graph. Returns (z float32 [H, W], sig_out f32 [nsig, H, W], infos)."""
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        if img.ndim != 2:
-            raise ValueError("image must be [H, W], got %s" % (img.shape,))
-        h, w = img.shape
-        sig, sig_out = self._planes(signals, h, w)
-        opt = opt or default_options()
-        out = np.zeros((h, w), dtype=np.float32)
-        infos = self._run("glf_multi_image_processing_f32_signals", opt, img, out, None,
-                          sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)), no_zf=True)
-        return out, sig_out, infos
-
-    def image_processing_rgbf32(self, img, opt=None):
-        """glf_multi_image_processing_rgbf32: host float32 [H, W, 3] in (finite values), (z float32 [H, W, 3], per-rank infos)."""
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
-        opt = opt or default_options()
-        out = np.zeros(img.shape, dtype=np.float32)
-        return out, self._run("glf_multi_image_processing_rgbf32", opt, img, out, None, no_zf=True)
-
-    def image_processing_rgbf32_signals(self, img, signals, opt=None):
-        """glf_multi_image_processing_rgbf32_signals: host float32 [H, W, 3] plus float planes [nsig, H, W] filtered through the
-        float colour graph. Returns (z float32 [H, W, 3], sig_out f32 [nsig, H, W], infos)."""
-        img = np.ascontiguousarray(img, dtype=np.float32)
-        if img.ndim != 3 or img.shape[2] != 3:
-            raise ValueError("image must be [H, W, 3], got %s" % (img.shape,))
-        h, w = img.shape[:2]
-        sig, sig_out = self._planes(signals, h, w)
-        opt = opt or default_options()
-        out = np.zeros((h, w, 3), dtype=np.float32)
-        infos = self._run("glf_multi_image_processing_rgbf32_signals", opt, img, out, None,
-                          sig=(C.c_int(sig.shape[0]), _ptr(sig), _ptr(sig_out)), no_zf=True)
-        return out, sig_out, infos
 
     @staticmethod
     def _planes(signals, h, w):
@@ -1217,15 +1176,91 @@ class Context:
         """Whole approximate path (hpc/image_processing.c:183-277) on a device image tensor.
         capture=True additionally returns the run's by-products in info["capture"] (glf_capture): phi_A [p, ld] and
         phi [rows of this rank * width, ld] as device tensors, c = Phi^T y and the degree vector as numpy arrays."""
+        return self._image_processing(PIX_U8, d_img, None, opt, want_float, capture, out)
+
+    def image_processing_signals(self, d_img, signals, opt=None, want_float=False):
+        """Joint filtering (glf_image_processing_signals): the guide d_img (device uint8 [H, W]) defines the graph, the
+        eigenpairs and the filter; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same operator.
+        Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing."""
+        return self._image_processing(PIX_U8, d_img, signals, opt, want_float, False, None)
+
+    def image_processing_rgb(self, d_rgb, opt=None, want_float=False, capture=False):
+        """Colour-guided filtering (glf_image_processing_rgb): d_rgb (device uint8 [H, W, 3]) defines the graph through its RGB
+        differences, and each channel goes through the graph's filter. Returns (out uint8 [H, W, 3], zf float32 [3, H, W] or None,
+        info). capture=True (glf_image_processing_rgb_capture) adds info["capture"]: phi_A [p, ld] and phi [rows of this rank *
+        width, ld] as device tensors, the degree vector as a numpy array."""
+        return self._image_processing(PIX_RGB8, d_rgb, None, opt, want_float, capture, None)
+
+    def image_processing_u16(self, d_img, opt=None, want_float=False, capture=False):
+        """16-bit greyscale filtering (glf_image_processing_u16): d_img (device uint16 [H, W]) defines the graph through its 16-bit
+        values (opt.h_val in 16-bit units) and goes through the graph's filter. Returns (out uint16 [H, W], zf float32 [H, W] or None,
+        info). capture=True (glf_image_processing_u16_capture) adds info["capture"] as image_processing_rgb does."""
+        return self._image_processing(PIX_U16, d_img, None, opt, want_float, capture, None)
+
+    def image_processing_f32(self, d_img, opt=None, capture=False, out=None):
+        """32-bit float greyscale filtering (glf_image_processing_f32): d_img (device float32 [H, W], finite values) defines the graph
+        through its values (opt.h_val in the image's units) and goes through the graph's filter. Returns (z float32 [H, W], info):
+        the output is the float z itself, not clamped. A NaN or an Inf in d_img raises GlfError(ERR_INVALID) and `out` (optional: a
+        device float32 [H, W] to write into) is left as it was. capture=True adds info["capture"] as image_processing_u16 does."""
+        return self._image_processing(PIX_F32, d_img, None, opt, False, capture, out)
+
+    def image_processing_f32_signals(self, d_img, signals, opt=None):
+        """Joint filtering under a float guide (glf_image_processing_f32_signals): as image_processing_u16_signals with the graph
+        and the output of image_processing_f32. Returns (z float32 [H, W], sig_out float32 [nsig, H, W], info)."""
+        return self._image_processing(PIX_F32, d_img, signals, opt, False, False, None)
+
+    def image_processing_rgbf32(self, d_rgb, opt=None, capture=False, out=None):
+        """Float colour filtering (glf_image_processing_rgbf32): d_rgb (device float32 [H, W, 3], finite values: HDR, [0, 1] RGB,
+        Lab / YUV, a network's output) defines the graph through the differences of its three channels (opt.h_val in the image's units)
+        and each channel goes through the graph's filter. Returns (z float32 [H, W, 3], info): the output is the float z itself,
+        interleaved as the image, not clamped. A NaN or an Inf in d_rgb raises GlfError(ERR_INVALID) and `out` (optional: a device
+        float32 [H, W, 3] to write into) is left as it was. capture=True adds info["capture"] as image_processing_rgb does."""
+        return self._image_processing(PIX_RGBF32, d_rgb, None, opt, False, capture, out)
+
+    def image_processing_rgbf32_signals(self, d_rgb, signals, opt=None):
+        """Joint filtering under a float colour guide (glf_image_processing_rgbf32_signals): as image_processing_rgb_signals with the
+        graph and the output of image_processing_rgbf32. Returns (z float32 [H, W, 3], sig_out float32 [nsig, H, W], info)."""
+        return self._image_processing(PIX_RGBF32, d_rgb, signals, opt, False, False, None)
+
+    def image_processing_rgb_signals(self, d_rgb, signals, opt=None, want_float=False):
+        """Joint filtering under a colour guide (glf_image_processing_rgb_signals): d_rgb (device uint8 [H, W, 3]) defines the graph
+        and is filtered as by image_processing_rgb; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same
+        operator. Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing_rgb."""
+        return self._image_processing(PIX_RGB8, d_rgb, signals, opt, want_float, False, None)
+
+    def image_processing_u16_signals(self, d_img, signals, opt=None, want_float=False):
+        """Joint filtering under a 16-bit guide (glf_image_processing_u16_signals): as image_processing_rgb_signals with the graph
+        and the outputs of image_processing_u16 (d_img device uint16 [H, W])."""
+        return self._image_processing(PIX_U16, d_img, signals, opt, want_float, False, None)
+
+    def _image_processing(self, fmt, d_img, signals, opt, want_float, capture, out):
+        """Every image_processing* method: the device image of format fmt (a PIX_*) and, with signals, device float planes
+        [nsig, H, W] through glf_image_processing<suffix>_capture or <suffix>_signals on the context's stream. Returns (out,
+        [zf or None,] [sig_out,] info): zf is left out for the float formats, whose out is the float z."""
         torch = self.torch
-        assert d_img.dtype == torch.uint8 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
+        f = _PIX_FORMATS[fmt]
+        dtype = getattr(torch, f.torch_dtype)
+        assert d_img.dtype == dtype and d_img.is_cuda and _pix_shape_ok(f, d_img) and d_img.is_contiguous()
+        h, w = d_img.shape[:2]
         opt = opt or default_options()
+        what, sig, sig_out = "image_processing" + f.suffix, (), ()
+        if signals is not None:
+            planes_out, sig = self._signal_planes(signals, h, w)   # (waits for the caller's stream)
+            what, sig_out = what + "_signals", (planes_out,)
+        elif f.wait_stream:
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
         with torch.cuda.stream(self.stream):   # the zero fills must be ordered before the library's writes
             if out is None:
-                out = torch.zeros((h, w), dtype=torch.uint8, device=self.device)
-            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-        return out, zf, self._run("glf_image_processing_capture", "image_processing", opt, d_img, out, zf, capture, grey=True)
+                out = torch.zeros(tuple(d_img.shape), dtype=getattr(torch, f.zeros_dtype), device=self.device)
+                if f.zeros_dtype != f.torch_dtype:
+                    out = out.view(dtype)
+            zf = torch.zeros((3, h, w) if f.channels == 3 else (h, w), dtype=torch.float32,
+                             device=self.device) if want_float and not f.float_out else None
+        if f.float_out:   # (out= of the float calls; the 8-bit call takes its out as it comes)
+            assert out.dtype == dtype and out.is_cuda and tuple(out.shape) == tuple(d_img.shape) and out.is_contiguous()
+        info = self._run("glf_" + what + ("" if sig else "_capture"), what, opt, d_img, out, zf, capture, grey=fmt == PIX_U8, sig=sig,
+                         no_zf=f.float_out)
+        return (out,) + (() if f.float_out else (zf,)) + sig_out + (info,)
 
     def _run(self, fn, what, opt, d_img, out, zf, capture=False, grey=False, sig=(), no_zf=False):
         """fn(ctx, opt, img, width, height, [*sig,] out, zf, eigvals, stats[, capture]) on the context's stream (sig: nsig, the
@@ -1252,144 +1287,6 @@ class Context:
                 info["capture"].update(c=c_host[:st.m].copy(), corr=corr)
         return info
 
-
-    def image_processing_signals(self, d_img, signals, opt=None, want_float=False):
-        """Joint filtering (glf_image_processing_signals): the guide d_img (device uint8 [H, W]) defines the graph, the
-        eigenpairs and the filter; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same operator.
-        Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing."""
-        torch = self.torch
-        assert d_img.dtype == torch.uint8 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        assert signals.dtype == torch.float32 and signals.is_cuda and signals.dim() == 3 and signals.is_contiguous()
-        h, w = d_img.shape
-        if tuple(signals.shape[1:]) != (h, w):
-            raise ValueError("signals must be [nsig, %d, %d], got %s" % (h, w, tuple(signals.shape)))
-        opt = opt or default_options()
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the planes are complete before the library reads them
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w), dtype=torch.uint8, device=self.device)
-            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-            sig_out = torch.zeros(tuple(signals.shape), dtype=torch.float32, device=self.device)
-        info = self._run("glf_image_processing_signals", "image_processing_signals", opt, d_img, out, zf,
-                         sig=(C.c_int(signals.shape[0]), C.c_void_p(signals.data_ptr()), C.c_void_p(sig_out.data_ptr())))
-        return out, zf, sig_out, info
-
-    def image_processing_rgb(self, d_rgb, opt=None, want_float=False, capture=False):
-        """Colour-guided filtering (glf_image_processing_rgb): d_rgb (device uint8 [H, W, 3]) defines the graph through its RGB
-        differences, and each channel goes through the graph's filter. Returns (out uint8 [H, W, 3], zf float32 [3, H, W] or None,
-        info). capture=True (glf_image_processing_rgb_capture) adds info["capture"]: phi_A [p, ld] and phi [rows of this rank *
-        width, ld] as device tensors, the degree vector as a numpy array."""
-        torch = self.torch
-        assert d_rgb.dtype == torch.uint8 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
-        h, w = d_rgb.shape[:2]
-        opt = opt or default_options()
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w, 3), dtype=torch.uint8, device=self.device)
-            zf = torch.zeros((3, h, w), dtype=torch.float32, device=self.device) if want_float else None
-        return out, zf, self._run("glf_image_processing_rgb_capture", "image_processing_rgb", opt, d_rgb, out, zf, capture)
-
-    def image_processing_u16(self, d_img, opt=None, want_float=False, capture=False):
-        """16-bit greyscale filtering (glf_image_processing_u16): d_img (device uint16 [H, W]) defines the graph through its 16-bit
-        values (opt.h_val in 16-bit units) and goes through the graph's filter. Returns (out uint16 [H, W], zf float32 [H, W] or None,
-        info). capture=True (glf_image_processing_u16_capture) adds info["capture"] as image_processing_rgb does."""
-        torch = self.torch
-        assert d_img.dtype == torch.uint16 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
-        opt = opt or default_options()
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
-            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-        return out, zf, self._run("glf_image_processing_u16_capture", "image_processing_u16", opt, d_img, out, zf, capture)
-
-    def image_processing_f32(self, d_img, opt=None, capture=False, out=None):
-        """32-bit float greyscale filtering (glf_image_processing_f32): d_img (device float32 [H, W], finite values) defines the graph
-        through its values (opt.h_val in the image's units) and goes through the graph's filter. Returns (z float32 [H, W], info):
-        the output is the float z itself, not clamped. A NaN or an Inf in d_img raises GlfError(ERR_INVALID) and `out` (optional: a
-        device float32 [H, W] to write into) is left as it was. capture=True adds info["capture"] as image_processing_u16 does."""
-        torch = self.torch
-        assert d_img.dtype == torch.float32 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
-        opt = opt or default_options()
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
-        with torch.cuda.stream(self.stream):
-            if out is None:
-                out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.is_cuda and tuple(out.shape) == (h, w) and out.is_contiguous()
-        return out, self._run("glf_image_processing_f32_capture", "image_processing_f32", opt, d_img, out, None, capture, no_zf=True)
-
-    def image_processing_f32_signals(self, d_img, signals, opt=None):
-        """Joint filtering under a float guide (glf_image_processing_f32_signals): as image_processing_u16_signals with the graph
-        and the output of image_processing_f32. Returns (z float32 [H, W], sig_out float32 [nsig, H, W], info)."""
-        torch = self.torch
-        assert d_img.dtype == torch.float32 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
-        opt = opt or default_options()
-        sig_out, sig = self._signal_planes(signals, h, w)
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w), dtype=torch.float32, device=self.device)
-        info = self._run("glf_image_processing_f32_signals", "image_processing_f32_signals", opt, d_img, out, None, sig=sig, no_zf=True)
-        return out, sig_out, info
-
-    def image_processing_rgbf32(self, d_rgb, opt=None, capture=False, out=None):
-        """Float colour filtering (glf_image_processing_rgbf32): d_rgb (device float32 [H, W, 3], finite values: HDR, [0, 1] RGB,
-        Lab / YUV, a network's output) defines the graph through the differences of its three channels (opt.h_val in the image's units)
-        and each channel goes through the graph's filter. Returns (z float32 [H, W, 3], info): the output is the float z itself,
-        interleaved as the image, not clamped. A NaN or an Inf in d_rgb raises GlfError(ERR_INVALID) and `out` (optional: a device
-        float32 [H, W, 3] to write into) is left as it was. capture=True adds info["capture"] as image_processing_rgb does."""
-        torch = self.torch
-        assert d_rgb.dtype == torch.float32 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
-        h, w = d_rgb.shape[:2]
-        opt = opt or default_options()
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))   # the image is complete before the library reads it
-        with torch.cuda.stream(self.stream):
-            if out is None:
-                out = torch.zeros((h, w, 3), dtype=torch.float32, device=self.device)
-        assert out.dtype == torch.float32 and out.is_cuda and tuple(out.shape) == (h, w, 3) and out.is_contiguous()
-        return out, self._run("glf_image_processing_rgbf32_capture", "image_processing_rgbf32", opt, d_rgb, out, None, capture, no_zf=True)
-
-    def image_processing_rgbf32_signals(self, d_rgb, signals, opt=None):
-        """Joint filtering under a float colour guide (glf_image_processing_rgbf32_signals): as image_processing_rgb_signals with the
-        graph and the output of image_processing_rgbf32. Returns (z float32 [H, W, 3], sig_out float32 [nsig, H, W], info)."""
-        torch = self.torch
-        assert d_rgb.dtype == torch.float32 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
-        h, w = d_rgb.shape[:2]
-        opt = opt or default_options()
-        sig_out, sig = self._signal_planes(signals, h, w)
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w, 3), dtype=torch.float32, device=self.device)
-        info = self._run("glf_image_processing_rgbf32_signals", "image_processing_rgbf32_signals", opt, d_rgb, out, None, sig=sig, no_zf=True)
-        return out, sig_out, info
-
-    def image_processing_rgb_signals(self, d_rgb, signals, opt=None, want_float=False):
-        """Joint filtering under a colour guide (glf_image_processing_rgb_signals): d_rgb (device uint8 [H, W, 3]) defines the graph
-        and is filtered as by image_processing_rgb; `signals` (device float32 [nsig, H, W], 1 <= nsig <= 4) go through the same
-        operator. Returns (out, zf or None, sig_out float32 [nsig, H, W], info); out / zf / info are those of image_processing_rgb."""
-        torch = self.torch
-        assert d_rgb.dtype == torch.uint8 and d_rgb.is_cuda and d_rgb.dim() == 3 and d_rgb.shape[2] == 3 and d_rgb.is_contiguous()
-        h, w = d_rgb.shape[:2]
-        opt = opt or default_options()
-        sig_out, sig = self._signal_planes(signals, h, w)
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w, 3), dtype=torch.uint8, device=self.device)
-            zf = torch.zeros((3, h, w), dtype=torch.float32, device=self.device) if want_float else None
-        info = self._run("glf_image_processing_rgb_signals", "image_processing_rgb_signals", opt, d_rgb, out, zf, sig=sig)
-        return out, zf, sig_out, info
-
-    def image_processing_u16_signals(self, d_img, signals, opt=None, want_float=False):
-        """Joint filtering under a 16-bit guide (glf_image_processing_u16_signals): as image_processing_rgb_signals with the graph
-        and the outputs of image_processing_u16 (d_img device uint16 [H, W])."""
-        torch = self.torch
-        assert d_img.dtype == torch.uint16 and d_img.is_cuda and d_img.dim() == 2 and d_img.is_contiguous()
-        h, w = d_img.shape
-        opt = opt or default_options()
-        sig_out, sig = self._signal_planes(signals, h, w)
-        with torch.cuda.stream(self.stream):
-            out = torch.zeros((h, w), dtype=torch.int16, device=self.device).view(torch.uint16)
-            zf = torch.zeros((h, w), dtype=torch.float32, device=self.device) if want_float else None
-        info = self._run("glf_image_processing_u16_signals", "image_processing_u16_signals", opt, d_img, out, zf, sig=sig)
-        return out, zf, sig_out, info
-
     def _signal_planes(self, signals, h, w):
         """The zero-filled result planes and the (nsig, planes, planes out) arguments of a signals entry point."""
         torch = self.torch
@@ -1407,9 +1304,7 @@ class Context:
         Graph.synthesize / Graph.apply run any number of spectral responses on any planes in two passes over Phi each."""
         torch = self.torch
         assert d_img.is_cuda and d_img.is_contiguous()
-        key = (d_img.dtype, d_img.dim(), d_img.shape[2] if d_img.dim() == 3 else 1)
-        pix = {(torch.uint8, 2, 1): PIX_U8, (torch.uint8, 3, 3): PIX_RGB8, (torch.uint16, 2, 1): PIX_U16,
-               (torch.float32, 2, 1): PIX_F32, (torch.float32, 3, 3): PIX_RGBF32}.get(key)
+        pix = next((k for k, f in _PIX_FORMATS.items() if d_img.dtype == getattr(torch, f.torch_dtype) and _pix_shape_ok(f, d_img)), None)
         if pix is None:
             raise ValueError("graph: no pixel format for dtype %s, shape %s" % (d_img.dtype, tuple(d_img.shape)))
         h, w = d_img.shape[:2]
@@ -1936,6 +1831,11 @@ def _realised_samples(w, h, opt):
     uniform sampler (which rewrites the request), the request with margin for the random one; cached per image size and request."""
     req = int(opt.num_samples) if opt.num_samples else int(h * w * opt.sample_frac)
     return _realised(w, h, req, bool(getattr(opt, "sampling", 0)))
+
+
+def _pix_shape_ok(f, a):
+    """a (numpy array or tensor) is [H, W] of a one-channel format f, [H, W, 3] of a three-channel one."""
+    return len(a.shape) == 3 and a.shape[2] == 3 if f.channels == 3 else len(a.shape) == 2
 
 
 def _info(st, lam):

@@ -1,0 +1,160 @@
+"""SHA-256 of everything the whole-path calls return for the five guide formats (8-bit grey, RGB8, 16-bit grey, float grey, float RGB),
+with matvec_path, nystroem_path, outer iterations and sweep count: whether a change to the format plumbing -- the format table and the
+dispatchers of csrc/glf_internal.hpp, image_processing_run, the typed entry points, glf.py's format table -- left every bit alone.
+Per format: a 61 x 47 image (40 uniform samples, m = 5) and a 96 x 80 image (120 uniform samples, m = 8, epsilon 1e-3); the plain call, the
+signals call with 2 planes, the plain call with capture=True (phi_A, phi, degree), Context.graph followed by gram(); the non-grey
+formats on 96 x 80 also under PIX_BAND=1, NYS_PATH=band, MV_PATH=band; the plain and signals calls through Multi(2) on the loopback
+backend. Then the refusals as status and message: a kernel of another format at each entry point (both directions; KERNEL_BILATERAL at
+a non-grey entry point stands for the format's own kernel and is recorded as "no error"), a NaN and an Inf in a float guide (Context,
+Context.graph and Multi), nsig 0 and MAX_SIGNALS + 1 (Context and Multi). Run it once per build and compare the two files:
+    python tools/pix_hashes.py new                 # this tree's glf.py and libglf.so -> pix_hashes_new.json in the current directory
+    python tools/pix_hashes.py parent DIR          # DIR holds another commit's glf.py and libglf.so -> pix_hashes_parent.json"""
+import hashlib, json, os, sys
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))  # (tools/ sits under the repository root)
+tag = sys.argv[1]
+if len(sys.argv) > 2:
+    os.environ["GLF_LIBRARY"] = os.path.join(sys.argv[2], "libglf.so")
+    sys.path.insert(0, sys.argv[2])
+else:
+    sys.path.insert(0, os.path.join(ROOT, "image-processing-graph-laplacian_amd"))
+import numpy as np
+import torch
+import glf
+print("library:", glf.LIB_PATH)
+
+FORMATS = ("u8", "rgb", "u16", "f32", "rgbf32")
+SUFFIX = {"u8": "", "rgb": "_rgb", "u16": "_u16", "f32": "_f32", "rgbf32": "_rgbf32"}
+KERNEL = {"u8": glf.KERNEL_BILATERAL, "rgb": glf.KERNEL_BILATERAL_RGB, "u16": glf.KERNEL_BILATERAL_U16, "f32": glf.KERNEL_BILATERAL_F32,
+          "rgbf32": glf.KERNEL_BILATERAL_RGBF32}
+SHAPES = {"61x47": (61, 47, dict(num_samples=40, num_eigvals=5)), "96x80": (96, 80, dict(num_samples=120, num_eigvals=8, epsilon=1e-3))}
+
+
+def image(fmt, w, h):
+    """The format's image of one scene: three 8-bit planes; grey formats take the first, 16 bits scale it by 257, floats to [0, 1]."""
+    planes = np.stack([glf.synth_image(w, h, seed=s) for s in (3, 4, 5)], axis=-1)
+    x = planes if fmt in ("rgb", "rgbf32") else planes[..., 0]
+    if fmt == "u16":
+        return np.ascontiguousarray(x.astype(np.uint16) * np.uint16(257))
+    if fmt in ("f32", "rgbf32"):
+        return np.ascontiguousarray(x.astype(np.float32) / np.float32(255.0))
+    return np.ascontiguousarray(x)
+
+
+def options(fmt, **kw):
+    """h_val in the image's units (30 grey levels of 255)."""
+    h_val = {"u16": 30.0 * 257.0, "f32": 30.0 / 255.0, "rgbf32": 30.0 / 255.0}.get(fmt, 30.0)
+    return glf.default_options(h_val=h_val, **kw)
+
+
+def planes(w, h, n=2):
+    rng = np.random.default_rng(11)
+    return rng.normal(0.0, 1.0, (n, h, w)).astype(np.float32)
+
+
+def sha(a):
+    if a is None:
+        return None
+    if isinstance(a, torch.Tensor):
+        a = a.cpu()
+        a = a.view(torch.int16).numpy() if a.dtype == torch.uint16 else a.numpy()
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def record(arrays, info):
+    infos = info if isinstance(info, list) else [info]
+    d = {"arrays": [sha(a) for a in arrays], "eigvals": sha(infos[0]["eigvals"])}
+    for k in ("matvec_path", "nystroem_path", "outer_its", "matvecs"):
+        d[k] = [i[k] for i in infos]
+    if "capture" in infos[0]:
+        cap = infos[0]["capture"]
+        d["capture"] = {k: sha(cap[k]) for k in ("phi_A", "phi", "degree")}
+    return d
+
+
+def refusal(call):
+    try:
+        r = call()
+        if hasattr(r, "close"):
+            r.close()
+    except glf.GlfError as e:
+        return dict(status=e.status, message=str(e))
+    except (ValueError, AssertionError) as e:
+        return dict(status=type(e).__name__, message=str(e))
+    return dict(status="no error", message="")
+
+
+out = {}
+for fmt in FORMATS:
+    for shape, (w, h, okw) in SHAPES.items():
+        img, sig = image(fmt, w, h), planes(w, h)
+        tunings = [("default", {})]
+        if fmt != "u8" and shape == "96x80":
+            tunings.append(("band", dict(PIX_BAND="1", NYS_PATH="band", MV_PATH="band")))
+        for tname, tune in tunings:
+            with glf.Context(0) as ctx:
+                ctx.set_tuning(**tune)
+                d_img, d_sig = torch.from_numpy(img).to(ctx.device), torch.from_numpy(sig).to(ctx.device)
+                plain, signals = getattr(ctx, "image_processing" + SUFFIX[fmt]), getattr(ctx, "image_processing" + SUFFIX[fmt] + "_signals")
+                kw = {} if fmt in ("f32", "rgbf32") else dict(want_float=True)
+                key = "%s/%s/%s/" % (fmt, shape, tname)
+                r = plain(d_img, options(fmt, **okw), **kw)
+                out[key + "plain"] = record(r[:-1], r[-1])
+                r = signals(d_img, d_sig, options(fmt, **okw), **kw)
+                out[key + "signals"] = record(r[:-1], r[-1])
+                r = plain(d_img, options(fmt, **okw), capture=True, **kw)
+                out[key + "capture"] = record(r[:-1], r[-1])
+                with ctx.graph(d_img, options(fmt, **okw)) as g:
+                    out[key + "graph"] = dict(gram=sha(g.gram()), eigvals=sha(g.eigenvalues), info=g.info,
+                                              **{k: g.stats[k] for k in ("matvec_path", "nystroem_path", "outer_its", "matvecs")})
+        with glf.Multi(2, devices=[0, 0], backend=glf.MULTI_LOOPBACK) as world:
+            kw = {} if fmt in ("f32", "rgbf32") else dict(want_float=True)
+            skw = {} if fmt in ("u8", "f32", "rgbf32") else dict(want_float=True)   # (the 8-bit signals call always returns zf)
+            r = getattr(world, "image_processing" + SUFFIX[fmt])(img, options(fmt, **okw), **kw)
+            out["%s/%s/multi/plain" % (fmt, shape)] = record(r[:-1], r[-1])
+            r = getattr(world, "image_processing" + SUFFIX[fmt] + "_signals")(img, sig, options(fmt, **okw), **skw)
+            out["%s/%s/multi/signals" % (fmt, shape)] = record(r[:-1], r[-1])
+
+# the refusals (a fresh context or world each: a refusal that leaves last_error alone then reports an empty message)
+w, h, okw = SHAPES["61x47"]
+for fmt in FORMATS:
+    img = image(fmt, w, h)
+    for kfmt in FORMATS + ("photometric",):
+        if kfmt == fmt:
+            continue
+        kernel = glf.KERNEL_PHOTOMETRIC if kfmt == "photometric" else KERNEL[kfmt]
+        if fmt == "u8" and kfmt == "photometric":
+            continue   # (the 8-bit entry points take it)
+        with glf.Context(0) as ctx:
+            d_img = torch.from_numpy(img).to(ctx.device)
+            out["refuse/kernel/%s<-%s" % (fmt, kfmt)] = refusal(
+                lambda: getattr(ctx, "image_processing" + SUFFIX[fmt])(d_img, options(fmt, kernel=kernel, **okw)))
+            out["refuse/kernel/%s<-%s/signals" % (fmt, kfmt)] = refusal(
+                lambda: getattr(ctx, "image_processing" + SUFFIX[fmt] + "_signals")(d_img, torch.from_numpy(planes(w, h)).to(ctx.device),
+                                                                                      options(fmt, kernel=kernel, **okw)))
+            out["refuse/kernel/%s<-%s/graph" % (fmt, kfmt)] = refusal(lambda: ctx.graph(d_img, options(fmt, kernel=kernel, **okw)))
+    for nsig in (0, glf.MAX_SIGNALS + 1):
+        with glf.Context(0) as ctx:
+            d_img = torch.from_numpy(img).to(ctx.device)
+            out["refuse/nsig%d/%s" % (nsig, fmt)] = refusal(
+                lambda: getattr(ctx, "image_processing" + SUFFIX[fmt] + "_signals")(d_img, torch.from_numpy(planes(w, h, nsig)).to(ctx.device),
+                                                                                      options(fmt, **okw)))
+        with glf.Multi(2, devices=[0, 0], backend=glf.MULTI_LOOPBACK) as world:
+            out["refuse/nsig%d/%s/multi" % (nsig, fmt)] = refusal(
+                lambda: getattr(world, "image_processing" + SUFFIX[fmt] + "_signals")(img, planes(w, h, nsig), options(fmt, **okw)))
+    if fmt in ("f32", "rgbf32"):
+        for name, bad in (("nan", np.float32("nan")), ("inf", np.float32("inf"))):
+            x = img.copy()
+            x.reshape(-1)[x.size // 3] = bad
+            with glf.Context(0) as ctx:
+                d_img = torch.from_numpy(x).to(ctx.device)
+                out["refuse/%s/%s" % (name, fmt)] = refusal(lambda: getattr(ctx, "image_processing" + SUFFIX[fmt])(d_img, options(fmt, **okw)))
+                out["refuse/%s/%s/signals" % (name, fmt)] = refusal(
+                    lambda: getattr(ctx, "image_processing" + SUFFIX[fmt] + "_signals")(d_img, torch.from_numpy(planes(w, h)).to(ctx.device),
+                                                                                          options(fmt, **okw)))
+                out["refuse/%s/%s/graph" % (name, fmt)] = refusal(lambda: ctx.graph(d_img, options(fmt, **okw)))
+            with glf.Multi(2, devices=[0, 0], backend=glf.MULTI_LOOPBACK) as world:
+                out["refuse/%s/%s/multi" % (name, fmt)] = refusal(lambda: getattr(world, "image_processing" + SUFFIX[fmt])(x, options(fmt, **okw)))
+                out["refuse/%s/%s/multi/signals" % (name, fmt)] = refusal(
+                    lambda: getattr(world, "image_processing" + SUFFIX[fmt] + "_signals")(x, planes(w, h), options(fmt, **okw)))
+json.dump(out, open("pix_hashes_%s.json" % tag, "w"), indent=1, sort_keys=True)
+print(tag, len(out), "cases")
