@@ -12,7 +12,8 @@ CFLAGS   ?= -O2 -std=gnu11 -Wall -Wextra -fPIC
 HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystroem.hip \
             $(CSRC)/filter.hip $(CSRC)/pipeline.hip $(CSRC)/comm.hip $(CSRC)/nlm.hip $(CSRC)/balance.hip \
             $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip \
-            $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip $(CSRC)/graph_robust.hip $(CSRC)/graph_project.hip $(CSRC)/graph_compact.hip
+            $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip $(CSRC)/graph_robust.hip $(CSRC)/graph_project.hip $(CSRC)/graph_compact.hip \
+            $(CSRC)/graph_quad.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
 C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
@@ -68,8 +69,13 @@ compact_check: tools/compact_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_pl
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/compact_host_check $(filter %.cpp,$^)
 	tools/compact_host_check
 
+# the host-only half of the per-pixel quadratic forms (glf_fit_factor: the factor's identity, its determinism, every refusal) under the address and undefined-behaviour sanitizers (CPU only)
+quad_check: tools/quad_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp $(CSRC)/phi_compact.hpp $(CSRC)/robust_loss.hpp include/glf.h
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/quad_host_check $(filter %.cpp,$^)
+	tools/quad_host_check
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean pfm_check cluster_check basis_check band_plan_check robust_check compact_check
+.PHONY: all oracle clean pfm_check cluster_check basis_check band_plan_check robust_check compact_check quad_check

@@ -121,6 +121,7 @@ struct glf_graph {
     int cluster_blocks_per_cu[3] = {0, 0, 0}; // k_graph_cluster<CW, MODE>'s at [MODE], asked at the first cluster step in that mode
     int transform_blocks_per_cu = 0; // k_graph_transform<ld>'s, asked at the first transform
     int robust_blocks_per_cu = 0;    // k_graph_residual_weight<ld>'s, asked at the first robust step
+    int quad_blocks_per_cu[2] = {0, 0}; // k_graph_quadform<ld, T, NB>'s at [NB - 1], asked at the first quadratic form of that width
 };
 
 namespace glf {
@@ -867,5 +868,8 @@ int graph_normal_equations(glf_ctx *ctx, const float *d_phi, int64_t N, unsigned
 // ... of a handle of either storage: on a compact one the f16 instance forms them on the stored halves, and the column scales are
 // folded into the read-back in f64 (G[i][j] 2^(e_i + e_j), b_k[c] 2^e_c: the bits of the f32 pass over Q)
 int graph_normal_equations(const glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_G, double *h_b);
+// graph.hip: d_out[i] = Phi[h_px[i]][0 .. dim) (Q on a compact handle) for the pixels 0 <= h_px[i] < N the caller names, by the row
+// gather of graph_sample_rows (queued)
+int graph_gather_rows(glf_graph *g, int dim, unsigned nrows, const int64_t *h_px, float *d_out);
 
 } // namespace glf

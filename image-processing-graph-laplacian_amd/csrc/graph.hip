@@ -126,6 +126,21 @@ int graph_sample_rows(glf_graph *g, int dim, int nplanes, const float *d_planes,
     return GLF_OK;
 }
 
+int graph_gather_rows(glf_graph *g, int dim, unsigned nrows, const int64_t *h_px, float *d_out)
+{
+    glf_ctx *ctx = g->ctx;
+    // the sample of one row of a one-row Phi that starts at the pixel: k_sample_rows' own reads, nothing new on the device
+    dispatch_phi(g, [&](auto *phi) {
+        using T = std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>;
+        for (unsigned i = 0; i < nrows; ++i)
+            hipLaunchKernelGGL(k_sample_rows<T>, dim3((unsigned)ceil_div(dim, 256)), dim3(256), 0, ctx->stream, phi + (size_t)h_px[i] * g->ld,
+                               (const int *)g->d_expo, (int64_t)1, (int)g->ld, dim, 0, (const float *)nullptr, (const float *)nullptr, 0, (int64_t)1,
+                               d_out + (size_t)i * dim);
+    });
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
 } // namespace glf
 
 using namespace glf;

@@ -431,6 +431,25 @@ int glf_basis_orthonormal(unsigned m, const double *G, const double *lam, double
     return GLF_OK;
 }
 
+// R = L^-T of G + diag(penalty) = L L^T: glf_basis_orthonormal's Cholesky mode on the penalised matrix (its factorisation reads the
+// lower triangle, as glf_fit_coeffs' does, so the two refuse the same systems)
+int glf_fit_factor(unsigned m, const double *G, const double *penalty, double *R)
+{
+    if (!G || !R || m == 0) return GLF_ERR_INVALID;
+    const size_t n = m;
+    std::vector<double> M(G, G + n * n), out(n * n);
+    for (size_t i = 0; penalty && i < n; ++i) {
+        if (!std::isfinite(penalty[i])) return GLF_ERR_INVALID;
+        M[i * n + i] += penalty[i];
+    }
+    const int rc = glf_basis_orthonormal(m, M.data(), nullptr, out.data(), nullptr);
+    if (rc != GLF_OK) return rc;
+    for (size_t e = 0; e < n * n; ++e)
+        if (!std::isfinite(out[e])) return GLF_ERR_INVALID;
+    std::copy(out.begin(), out.end(), R);
+    return GLF_OK;
+}
+
 } // extern "C"
 
 // ---- low-rank factor of the photometric table -----------------------------------------------------------------

@@ -69,6 +69,7 @@ EXPORTS = [
     "glf_graph_cluster_step_ex", "glf_cluster_update_w", "glf_cluster_seed_w", "glf_graph_segment_ex",
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize", "glf_graph_project_wide",
     "glf_graph_compact", "glf_graph_storage", "glf_graph_dequantize",
+    "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
     "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex",
 ]
@@ -91,6 +92,8 @@ _PIX_FORMATS = {
 GRAPH_MAX_OUTPUTS = 32
 GRAPH_MAX_PLANES = 32      # GLF_GRAPH_MAX_PLANES: the most planes of one glf_graph_project_wide call
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
+QUAD_MAX_COLS = 64         # GLF_QUAD_MAX_COLS: the most columns of R of one glf_graph_quadform call
+QUAD_MAX_CENTRES = 32      # GLF_QUAD_MAX_CENTRES: the most centres of one glf_graph_quadform call
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -244,6 +247,9 @@ _lib.glf_graph_project_wide.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_voi
 _lib.glf_graph_compact.argtypes = [C.c_void_p, C.c_int]
 _lib.glf_graph_storage.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_dequantize.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_quadform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int, C.c_void_p]
+_lib.glf_fit_factor.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_rows.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
@@ -473,6 +479,25 @@ def fit_coeffs(G, b, penalty=None):
     if rc != OK:
         raise GlfError(rc, "glf_fit_coeffs(m=%d): not positive definite, or an empty system" % m)
     return a.reshape(np.shape(b))
+
+
+def fit_factor(G, penalty=None):
+    """glf_fit_factor (host only): R [m, m] = L^-T of G + diag(penalty) = L L^T, upper triangular, so that
+    phi^T (G + diag(penalty))^-1 phi = |R^T phi|^2: the R whose Graph.quadform is the leverage of the fit. G [m, m] symmetric (its
+    lower triangle is read), penalty [m] or None. Raises GlfError where fit_coeffs does (not positive definite, NaN, Inf)."""
+    G = np.ascontiguousarray(G, dtype=np.float64)
+    m = G.shape[0]
+    if G.shape != (m, m):
+        raise ValueError("G must be square, got %s" % (G.shape,))
+    if penalty is not None:
+        penalty = np.ascontiguousarray(penalty, dtype=np.float64)
+        if penalty.shape != (m,):
+            raise ValueError("penalty must be [%d], got %s" % (m, penalty.shape))
+    R = np.zeros((m, m), dtype=np.float64)
+    rc = _lib.glf_fit_factor(C.c_uint(m), _ptr(G), _ptr(penalty), _ptr(R))
+    if rc != OK:
+        raise GlfError(rc, "glf_fit_factor(m=%d): not positive definite, or an empty system" % m)
+    return R
 
 
 def _robust_kind(loss):
@@ -1578,6 +1603,111 @@ class Graph:
         if penalty is None:
             penalty = (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / self.info["m"])
         return self._synthesize_groups(fit_coeffs(G, b, penalty))
+
+    def quadform(self, R, centres=None, out=None, accumulate=False):
+        """q_k(px) = |R^T phi_px - t_k|^2 for every pixel and centre in one pass over Phi per launch (glf_graph_quadform): R [m, r],
+        centres [ncent, r] or None (one centre at the origin) -> device float32 [ncent, H, W] (out: a contiguous tensor of that shape
+        to write into, or with accumulate to add to). Any r: launches of at most QUAD_MAX_COLS columns, every one after the first
+        accumulating; any ncent: launches of at most QUAD_MAX_CENTRES centres. A centre's plane depends neither on the centres beside
+        it nor on zero columns appended to R and the centres; up to 64 columns it is one launch and accumulate adds the plain result
+        with one f32 addition, beyond that each group of columns is added in turn. Soft memberships are a softmax over -q in torch."""
+        t = self.ctx.torch
+        R = np.asarray(R, dtype=np.float64)
+        m, (h, w) = self.info["m"], (self.info["height"], self.info["width"])
+        if R.ndim != 2 or R.shape[0] != m or R.shape[1] < 1:
+            raise ValueError("R must be [%d, r] with r >= 1, got %s" % (m, R.shape))
+        r = R.shape[1]
+        cen = np.zeros((1, r)) if centres is None else np.atleast_2d(np.asarray(centres, dtype=np.float64))
+        if cen.shape[1] != r or cen.shape[0] < 1:
+            raise ValueError("centres must be [ncent, %d], got %s" % (r, cen.shape))
+        ncent, n = cen.shape[0], h * w
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate needs out")
+            with t.cuda.stream(self.ctx.stream):
+                out = t.empty((ncent, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        else:
+            assert out.dtype == t.float32 and out.is_cuda and out.is_contiguous()
+            if tuple(out.shape) != (ncent, h, w):
+                raise ValueError("out must be [%d, %d, %d], got %s" % (ncent, h, w, tuple(out.shape)))
+            self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # out is complete before the library touches it
+        for c0 in range(0, r, QUAD_MAX_COLS):
+            cols = slice(c0, min(c0 + QUAD_MAX_COLS, r))
+            Rg = np.ascontiguousarray(R[:, cols])
+            for k0 in range(0, ncent, QUAD_MAX_CENTRES):
+                k1 = min(k0 + QUAD_MAX_CENTRES, ncent)
+                tg = None if centres is None else np.ascontiguousarray(cen[k0:k1, cols])
+                self.ctx._check(_lib.glf_graph_quadform(self._g, C.c_uint(Rg.shape[1]), _ptr(Rg), C.c_uint(k1 - k0), _ptr(tg),
+                                                        C.c_int(1 if accumulate or c0 > 0 else 0), C.c_void_p(out.data_ptr() + 4 * n * k0)),
+                                "graph quadform")   # (returns with the stream drained)
+        return out
+
+    def rows(self, pixels):
+        """Phi[px][:m] of the given flat pixel indices as numpy float32 [len(pixels), m] (glf_graph_rows); on a compact handle the
+        rows of Q = dequantize(), exact."""
+        px = np.ascontiguousarray(np.atleast_1d(np.asarray(pixels)), dtype=np.int64)
+        rows = np.zeros((px.size, self.info["m"]), dtype=np.float32)
+        for k0 in range(0, px.size, QUAD_MAX_CENTRES):
+            k1 = min(k0 + QUAD_MAX_CENTRES, px.size)
+            self.ctx._check(_lib.glf_graph_rows(self._g, C.c_uint(k1 - k0), _ptr(px[k0:k1]), _ptr(rows[k0:k1])), "graph rows")
+        return rows
+
+    def _penalty(self, G, smooth, ridge, penalty):
+        """fit's penalty rule: penalty_j = (ridge + smooth * lam_j) * trace(G) / m unless given in absolute units."""
+        if penalty is None:
+            return (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / self.info["m"])
+        return np.ascontiguousarray(penalty, dtype=np.float64)
+
+    def leverage(self, weight=None, smooth=0.0, ridge=0.0, penalty=None):
+        """v(px) = phi_px^T (G_w + diag(penalty))^-1 phi_px of the fit(planes, weight, smooth, ridge, penalty) of any planes: one
+        normal_equations(weight), fit_factor on the host, one quadform (m > 64: in groups of 64 columns of R) -> device float32
+        [H, W]. Up to the noise variance v is the posterior variance of the fitted value, where it can be trusted; with h = w v the
+        fit's leave-one-out residual is e / (1 - h). The penalty rule is fit's own."""
+        G = self.normal_equations(weight)[0]
+        return self.quadform(fit_factor(G, self._penalty(G, smooth, ridge, penalty)))[0]
+
+    def fit_loo(self, planes, weight, smooths, ridge=0.0):
+        """Choose fit's `smooth` by exact leave-one-out cross-validation. One normal_equations in total; per candidate smooth
+        fit_coeffs and fit_factor on the host, one synthesize (the fit z), one quadform (the leverage v), and in torch the score
+        sum_px w (e / (1 - w v))^2 / sum_px w per plane with e = s - z. planes: device float32 [nplanes, H, W], nplanes <= 4; weight:
+        device float32 [H, W] or None (= 1). -> (scores numpy [len(smooths), nplanes], the fit of the candidate with the lowest
+        score summed over the planes, device float32 [nplanes, H, W], its index)."""
+        t = self.ctx.torch
+        G, b = self.normal_equations(weight, planes)
+        smooths = [float(s) for s in smooths]
+        if not smooths:
+            raise ValueError("fit_loo: no candidates")
+        scores = np.zeros((len(smooths), planes.shape[0]), dtype=np.float64)
+        best, best_fit = -1, None
+        for i, smooth in enumerate(smooths):
+            pen = self._penalty(G, smooth, ridge, None)
+            z = self.synthesize(fit_coeffs(G, b, pen))
+            v = self.quadform(fit_factor(G, pen))[0]
+            with t.cuda.stream(self.ctx.stream):
+                wd = t.ones_like(v, dtype=t.float64) if weight is None else weight.double()
+                loo = (planes.double() - z.double()) / (1.0 - wd * v.double())
+                sc = (wd * loo * loo).sum(dim=(1, 2)) / wd.sum()
+            scores[i] = sc.cpu().numpy()
+            if best < 0 or scores[i].sum() < scores[best].sum():
+                best, best_fit = i, z
+        return scores, best_fit, best
+
+    def distance(self, seeds, response=None, dim=None):
+        """Squared diffusion distance from seed pixels, D_s(px)^2 = sum_{j < dim} g_j^2 (Phi[px][j] - Phi[seed_s][j])^2: the "magic
+        wand" on a resident graph. seeds: flat pixel indices; response: g [m], default 1 - lam; dim: default m. One quadform with
+        R = diag(g)[:, :dim] and the centres t_s = fl32(g) o Q[seed_s][:dim] (rows(): a compact handle uses Q), formed as the
+        difference before the square, so that nothing cancels near the seed and D_s(seed_s) is 0 exactly. -> device float32
+        [len(seeds), H, W]."""
+        m = self.info["m"]
+        dim = m if dim is None else int(dim)
+        if not 1 <= dim <= m:
+            raise ValueError("dim must be in 1 .. %d, got %d" % (m, dim))
+        g = np.asarray(1.0 - self.eigenvalues if response is None else response, dtype=np.float64)
+        if g.shape != (m,):
+            raise ValueError("response must be [%d], got %s" % (m, g.shape))
+        g32 = g.astype(np.float32).astype(np.float64)          # what the kernel multiplies by: the centre is then the pixel's own y
+        R = np.diag(g32)[:, :dim]
+        return self.quadform(R, g32[None, :dim] * self.rows(seeds)[:, :dim].astype(np.float64))
 
     def _robust_loss(self, loss, c, sigma, nplanes):
         rl = RobustLoss(struct_size=C.sizeof(RobustLoss), kind=_robust_kind(loss), c=0.0 if c is None else float(c))

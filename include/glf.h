@@ -920,6 +920,49 @@ int glf_graph_orthonormalize(glf_graph *g, int mode, int passes /* 1 | 2 */, int
  * plane's. Returns with the stream drained. */
 int glf_graph_project_wide(glf_graph *g, const float *d_w, int nplanes, const float *d_planes, double *h_c);
 
+/* ---- graph handle: per-pixel quadratic forms (leverage, leave-one-out, distances) ------------------------------------------------------
+ * Every other call on a handle returns a linear map of Phi's rows or a reduction over the pixels. glf_graph_quadform returns a
+ * quadratic function of one pixel's row, q_k(px) = | R^T phi_px - t_k |^2 with phi_px = Phi[px][0 .. m), for up to
+ * GLF_QUAD_MAX_CENTRES centres t_k under one R of up to GLF_QUAD_MAX_COLS columns, in one pass over Phi (k_graph_quadform). With
+ * R = L^-T of G_w + diag(penalty) = L L^T (glf_fit_factor) and no centre it is the leverage v = phi^T (G_w + diag(penalty))^-1 phi
+ * of the weighted fit: its posterior variance up to the noise variance and, with h = w v, its exact leave-one-out residual
+ * e / (1 - h). With R = diag(g) and t_s = g o Phi[seed_s] it is the squared diffusion distance from seed pixels; with a metric R
+ * and centroids t_k the squared distances whose softmax (in torch) gives soft memberships.
+ * Operation by operation: y_c = sum_j Phi[px][j] fl32(R[j][c]) on v_mfma_f32_32x32x2_f32 in glf_graph_synthesize's contraction
+ * order (y_c has the bits of glf_graph_synthesize's output for the coefficient column R[:, c] with no identity term); then in f32,
+ * nothing contracted that is not written here: a lane holds 16 columns of each block of 32, the columns c = 32 b + (g & 3) +
+ * 8 (g >> 2) + 4 h for g < 16 in half-wave h; per centre q_h = 0, x = y_c - fl32(t_k[c]), q_h = fmaf(x, x, q_h) over b ascending
+ * and g ascending; q = q_0 + q_1 (one f32 addition); out_k[px] = q, or out_k[px] + q (one f32 addition) under accumulate.
+ * r <= 32 runs one block, r > 32 two: the order depends on that padded column count alone. A column that is zero in R and in every
+ * t adds exactly nothing (x = 0), so a plane's bits depend neither on ncent, nor on the centres beside it, nor on appended zero
+ * columns; two calls give the same bits; no atomics. Rows past N are neither read nor stored. Against exact arithmetic on the
+ * handle's Phi, with x*_c = y*_c - fl32(t_k[c]), delta_c = (ld + 4) 2^-24 sum_j |Phi[px][j] R[j][c]| (glf_graph_synthesize's bound)
+ * and eps_c = delta_c + 2^-24 (|x*_c| + delta_c): |q - q*| <= sum_c (2 |x*_c| eps_c + eps_c^2) + (r + 1) 2^-24 sum_c (|x*_c| + eps_c)^2
+ * (DESIGN.md). Phi is read once at every ld; the call writes (and under accumulate reads) ncent planes.
+ * On a compact handle the column exponents are folded into the rows of R in f64 before the fl32 (R[j][c] 2^e_j, glf_graph_synthesize's
+ * rule; t lives in the space of R^T phi and takes no scale): the call returns, bit for bit, what it returns on an f32 handle whose
+ * Phi is Q.
+ * Out of scope: r > GLF_QUAD_MAX_COLS per launch (the Python wrapper groups, accumulating), per-centre metrics in one call,
+ * unit-length rows, soft memberships (a softmax over the output), contexts with a communicator and glf_multi_* (handles refuse
+ * them), m > 256, a flag of the image_processing host program. */
+#define GLF_QUAD_MAX_COLS 64
+#define GLF_QUAD_MAX_CENTRES 32
+/* out_k[px] (+)= sum_{c<r} (sum_j Phi[px][j] fl32(R[j][c]) - fl32(t_k[c]))^2, k < ncent.
+ * GLF_ERR_INVALID before any device work, d_out untouched: a NULL handle, h_R or d_out, r = 0 or r > GLF_QUAD_MAX_COLS, ncent = 0 or
+ * ncent > GLF_QUAD_MAX_CENTRES, an entry of R (after folding) or of t whose fl32 is not finite. accumulate: 0 writes, anything else
+ * adds to what d_out holds. Returns with the stream drained. */
+int glf_graph_quadform(glf_graph *g, unsigned r, const double *h_R /* HOST [m][r] */, unsigned ncent,
+                       const double *h_t /* HOST [ncent][r]; NULL: zeros */, int accumulate, float *d_out /* device [ncent][N] */);
+/* Host only: R [m][m] = L^-T of G + diag(penalty) = L L^T (upper triangular), so that phi^T (G + diag(penalty))^-1 phi = |R^T phi|^2.
+ * penalty [m] or NULL (zeros). The factorisation and the triangular inverse are glf_basis_orthonormal's. Refusals as glf_fit_coeffs
+ * (m = 0, a NULL G or R, not positive definite, NaN, Inf): GLF_ERR_INVALID, R untouched. */
+int glf_fit_factor(unsigned m, const double *G, const double *penalty, double *R);
+/* h_rows HOST float [nrows][m] <- Phi[h_px[i]][0 .. m) (on a compact handle Q, exact) for 1 <= nrows <= GLF_QUAD_MAX_CENTRES pixel
+ * indices 0 <= h_px[i] < N: the rows that become the centres of a distance from seed pixels. The gather is the one behind the seeding
+ * of glf_graph_segment. GLF_ERR_INVALID before any device work, h_rows untouched: a NULL argument, nrows outside the range, an index
+ * outside the image. Returns with the stream drained. */
+int glf_graph_rows(glf_graph *g, unsigned nrows, const int64_t *h_px /* HOST [nrows] */, float *h_rows /* HOST [nrows][m] */);
+
 /* ---- graph handle: compact storage, Phi as f16 with one power-of-two scale per column ---------------------------------------------------
  * The calls on a handle are one or two passes over the resident Phi and run at the memory stream: the only lever left is the number
  * of bytes. glf_graph_compact(g, GLF_PHI_F16) rewrites the handle's Phi as __half [N][ld] (raster rows, the same ld: a row pitch of
