@@ -76,6 +76,41 @@ GLF_BAND_HD inline void band_cols_range(const int *gcol, int nc, int cmin, int c
     *count = l - first;
 }
 
+// Column pass of the separable form on the matrix pipe (k_band_sep_cols_mfma, nystroem_band_sep.inc). A wave's tile is `tile_px`
+// pixels of one image row = tile_px / 32 pixel tiles of the MFMA's N; the sample columns within d of the tile (band_cols_range,
+// clipped at the image width) are walked in k-steps of BSEP_KSTEP: entry i of the range is column clo + i, k-step i / 16, and
+// entries from the count on are dead (their Ec operand is zero, their index clamped inside the grid).
+constexpr int BSEP_KSTEP = 16;
+GLF_BAND_HD inline void band_sep_tile_cols(const int *gcol, int nc, int width, int tc0, int tile_px, int d, int *clo, int *count)
+{
+    *clo = 0;
+    *count = 0;
+    const int tc1 = (tc0 + tile_px < width ? tc0 + tile_px : width) - 1;
+    if (d >= 0 && tc1 >= tc0) band_cols_range(gcol, nc, tc0 - d, tc1 + d, clo, count);
+}
+GLF_BAND_HD inline int band_sep_ksteps(int count) { return (count + BSEP_KSTEP - 1) / BSEP_KSTEP; }
+// index (into gcol, and of S's sample column) of entry i >= 0 of a range from clo: inside [0, nc) whatever i
+GLF_BAND_HD inline int band_sep_col(int clo, int i, int nc) { return clo + i < nc - 1 ? clo + i : nc - 1; }
+// do the live entries of k-step ks (16 ks < count) all lie rad or more from every pixel of [p0, p1]? Then the block of Ec is zero
+// throughout (the table is an exact zero from rad on) and the k-step adds exact zeros to that pixel tile.
+GLF_BAND_HD inline bool band_sep_block_dead(const int *gcol, int nc, int clo, int count, int ks, int p0, int p1, int rad)
+{
+    const int i1 = BSEP_KSTEP * ks + BSEP_KSTEP - 1 < count - 1 ? BSEP_KSTEP * ks + BSEP_KSTEP - 1 : count - 1;
+    const int first = gcol[band_sep_col(clo, BSEP_KSTEP * ks, nc)], last = gcol[band_sep_col(clo, i1, nc)];
+    return first - p1 >= rad || p0 - last >= rad;
+}
+// 16 x 32 entries per (k-step, pixel tile) the column pass executes for the tile from tc0 (all: none is passed over)
+GLF_BAND_HD inline uint64_t band_sep_tile_entries(const int *gcol, int nc, int width, int tc0, int tile_px, int d, int rad, bool all)
+{
+    int clo, count;
+    band_sep_tile_cols(gcol, nc, width, tc0, tile_px, d, &clo, &count);
+    uint64_t n = 0;
+    for (int ks = 0; ks < band_sep_ksteps(count); ++ks)
+        for (int pt = 0; pt < tile_px / 32; ++pt)
+            if (all || !band_sep_block_dead(gcol, nc, clo, count, ks, tc0 + 32 * pt, tc0 + 32 * pt + 31, rad)) n += (uint64_t)BSEP_KSTEP * 32u;
+    return n;
+}
+
 // radius and windows of one (sample grid, spatial coefficient)
 struct BandGeom {
     int rad = 0;

@@ -139,7 +139,7 @@ static void band_scales(hipStream_t st, const float *X, unsigned p, unsigned ld,
 
 // The filter of one pixel px that is no sample, from sdot[k] = Phi[px] . w_k (k = 0: the guide, then the planes of joint filtering):
 // hpc/display.c:64-78 as k_apply_filter has it, Phi never written. The one store of every form of the fused filter -- k_band's
-// epilogue, k_band_vec, k_band_sep_cols; y: the guide's value at px.
+// epilogue, k_band_vec, k_band_sep_cols_mfma; y: the guide's value at px.
 template <int NC>
 __device__ __forceinline__ void band_filter_store(const BandFilter &f, int64_t pix0, int64_t px, int y, const float (&sdot)[NC])
 {
@@ -153,7 +153,7 @@ __device__ __forceinline__ void band_filter_store(const BandFilter &f, int64_t p
         f.sig.out[(size_t)(k - 1) * f.sig.N + px] = v + (f.gain * sdot[k] - f.ysub * v);
     }
 }
-// k_band_vec and k_band_sep_cols sum with the Er15 table, which carries k_band's 2^15 (k_band's inv[] takes it out); their f64
+// k_band_vec and k_band_sep_cols_mfma sum with the Er15 table, which carries k_band's 2^15 (k_band's inv[] takes it out); their f64
 // totals lose it here
 constexpr double BAND_UNSCALE = 1.0 / 32768.0;
 static_assert(NYS_F16_KSCALE_LOG2 == 15.0f, "BAND_UNSCALE takes the scale of the Er15 table out again");
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(NW * 64) void k_band(const uint8_t *__restrict__ tv
     while (blk <= Bhi) {
         int issued = 0;
         if (qblk[BAND_NBUF - 1] <= Bhi) issued = issue(qblk[BAND_NBUF - 1], qg0[BAND_NBUF - 1], (buf + BAND_NBUF - 1) % BAND_NBUF);
-        if (wvalid || noskip) { // (noskip: a wave without a target row walks too, as in k_band_vec and k_band_sep_cols -- its Er15 is 0 and it writes nothing)
+        if (wvalid || noskip) { // (noskip: a wave without a target row walks too, as in k_band_vec and k_band_sep_cols_mfma -- its Er15 is 0 and it writes nothing)
             if (blk != cur_blk) {
                 cur_blk = blk;
 #pragma unroll
@@ -752,8 +752,9 @@ struct BandTables {
     const unsigned *win_s() const { return blob.p + o_win_s; }
     const int *dcmax() const { return reinterpret_cast<const int *>(blob.p + o_dcmax); } // geom.dcmax (k_band_vec's support)
     std::vector<unsigned> h_rowband_px; // host copy of rowband_px (the launchers' window plans)
+    double er15_rowsum = 0.0;           // max over the image rows r of sum_a Er15(|r - R_a|): |S| <= max |q| times this (the separable form's operand scale)
     int dc0() const { return geom.dcmax.empty() ? -1 : geom.dcmax[0]; } // the circle's half-width in a sample's own row (-1: none)
-    int cols_near_tile(int t) const // sample columns within dc0 of pixel tile t: what k_band_vec and k_band_sep_cols walk at most
+    int cols_near_tile(int t) const // sample columns within dc0 of pixel tile t: what k_band_vec walks at most
     {
         int lo = 0, n = 0;
         if (dc0() >= 0) band_cols_range(geom.cols.data(), nc, t * tile_px - dc0(), std::min(width, (t + 1) * tile_px) - 1 + dc0(), &lo, &n);
@@ -833,6 +834,13 @@ struct BandTables {
                 maxband = std::max(maxband, (int)(rb >> 16) - (int)(rb & 0xFFFF) + 1);
             }
             h_rowband_px.assign(h.begin() + o_rb_px, h.begin() + o_win_px);
+            er15_rowsum = 0.0;
+            for (int r = 0; r < height; ++r) {
+                const unsigned rb = h[o_rb_px + r];
+                double s = 0.0;
+                for (int a = (int)(rb & 0xFFFFu); a <= (int)(rb >> 16); ++a) s += (double)htab[256 + rad + 1 + std::min(std::abs(r - g.rows[a]), rad)];
+                er15_rowsum = std::max(er15_rowsum, s);
+            }
             for (int dr = 0; dr < rad; ++dr)
                 for (int t = 0; t < ntiles_px; ++t) h[o_win_px + (size_t)dr * ntiles_px + t] = geom.window(t * tile_px, std::min(width, (t + 1) * tile_px) - 1, dr, BAND_HALF_SHIFT);
             pairs_dr.assign(rad, 0.0);

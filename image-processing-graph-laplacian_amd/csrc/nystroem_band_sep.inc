@@ -6,13 +6,16 @@
 // term depends on the pixel's row, its column or its value alone, and the sum factors:
 //   G[a][b][k] = f_k(v_ab) q_ab                         k_band_sep_g     p R values per plane
 //   S[r][b][k] = sum_a Er15(|r - R_a|) G[a][b][k]       k_band_sep_rows  one fmaf chain per element, a ascending
-//   U_k[px]    = sum_b Ec(|c - C_b|) S[r][b][k]         k_band_sep_cols  one gather of Ec + R FMAs per (pixel, sample column)
+//   U_k[px]    = sum_b S[r][b][k] Ec(|c - C_b|)         k_band_sep_cols_mfma  a banded GEMM on the matrix pipe (split f16, f32 accumulate)
 //   s[px]      = sum_k f_k(v_px) U_k[px]                                 folded in f64, then band_filter_store
-// In the column pass a wave is 64 pixels of one image row, so S[r][b][.] is wave-uniform: it is fetched by scalar loads and enters the
-// FMAs as their scalar operand. No gather of P, no support test, no select: the support is the square |dr|, |dc| < rad (Er15 and
-// Ec are exact zeros from rad on) instead of k_band_vec's circle -- the corners add terms below 2^-40 of the largest one.
-// Layouts: G [plane][a][b][k], S [row][plane][b][k] (k fastest: a (row, b)'s terms are R consecutive floats = one or two scalar
-// loads; a thread of the row pass owns one (plane, b, k) and walks a, so its loads and stores are contiguous over the wave).
+// The column pass is M = term k, N = pixel, K = sample column b: S arrives as the MFMA's A operand through coalesced vector loads,
+// scaled by one power of two per plane (k_band_sep_scales, from the block maxima of |q| that k_band_sep_g leaves) and split into
+// f16 (hi, lo) in registers; 2^12 Ec is the B operand, formed once per workgroup in LDS. No gather of P, no support test, no select:
+// the support is the square |dr|, |dc| < rad (Er15 and Ec are exact zeros from rad on) instead of k_band_vec's circle -- the
+// corners add terms below 2^-40 of the largest one.
+// Layouts: G [plane][a][b][k], S [row][plane][b][k] (k fastest: the 32 terms of a term tile at one (row, b) are 128 contiguous
+// bytes, one half-wave's load; a thread of the row pass owns one (plane, b, k) and walks a, so its loads and stores are contiguous
+// over the wave).
 
 constexpr int BSEP_RB = 8;                 // image rows a thread of the row pass holds (G is read once per block of rows)
 constexpr int BSEP_ATILE = 128;            // band rows whose Er15 sit in LDS at a time (BAND_MAXROWS covers a block of rows at once)
@@ -21,15 +24,28 @@ static_assert(BSEP_RB == BAND_NW, "a block of the row pass is the rows of one wo
 static_assert(BSEP_ATILE >= BAND_MAXROWS, "without BAND_NOSKIP one tile holds the band of a block of rows");
 
 // q_k[s] = (float)(Psi[s] . w_k) as k_band_q has it (band_q_row), then G[k][s][t] = ftab[t][v_s] q_k[s]. One thread per sample.
+// qpart [blocks][NC]: max |q_k| over the block's samples.
 template <int NC>
 __global__ __launch_bounds__(256) void k_band_sep_g(const float *__restrict__ psi, unsigned p, unsigned ld, const float *__restrict__ w,
                                                     const float *__restrict__ sig_w, const uint8_t *__restrict__ svals,
-                                                    const float *__restrict__ ftab, int R, float *__restrict__ G)
+                                                    const float *__restrict__ ftab, int R, float *__restrict__ G, float *__restrict__ qpart)
 {
+    __shared__ float qm[4][NC];
     const unsigned s = blockIdx.x * 256 + threadIdx.x;
-    if (s >= p) return;
+    const bool live = s < p;
     double acc[NC];
-    band_q_row<NC>(psi + (size_t)s * ld, ld, w, sig_w, acc);
+    if (live) band_q_row<NC>(psi + (size_t)s * ld, ld, w, sig_w, acc);
+    // the block's max |q| per plane (q as it enters G), for the column pass' operand scale: k_band_sep_scales
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
+        float m = live ? fabsf((float)acc[k]) : 0.f;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if ((threadIdx.x & 63) == 0) qm[threadIdx.x >> 6][k] = m;
+    }
+    __syncthreads();
+    if (threadIdx.x < NC) qpart[(size_t)blockIdx.x * NC + threadIdx.x] = fmaxf(fmaxf(qm[0][threadIdx.x], qm[1][threadIdx.x]), fmaxf(qm[2][threadIdx.x], qm[3][threadIdx.x]));
+    if (!live) return;
     const int v = (int)svals[s];
     for (int t = 0; t < R; t += 4) {
         const float f0 = ftab[(t + 0) * 256 + v], f1 = ftab[(t + 1) * 256 + v], f2 = ftab[(t + 2) * 256 + v], f3 = ftab[(t + 3) * 256 + v];
@@ -87,76 +103,213 @@ __global__ __launch_bounds__(256) void k_band_sep_rows(const float *__restrict__
             if (j < nrb) S[(size_t)(r0 + j - srow0) * E + e] = acc[j];
 }
 
+// The operand scale of S, one power of two per plane: |S| <= max |q| er15_rowsum (|f_k| <= 1, BandTables::er15_rowsum), so with
+// 2^e max |q| er15_rowsum in [2^13, 2^14) the f16 (hi, lo) halves of 2^e S neither overflow nor lose their low bits. One workgroup:
+// the block maxima of |q| that k_band_sep_g left, then scl[k] = 2^e and scl[BANDV_MAXNC + k] = 2^(-e - BSEP_EC_LOG2) (a plane
+// whose q is all zero: e = 0), as k_band_absmax_scales does for the sweeps' operands.
+constexpr int BSEP_EC_LOG2 = 12; // the Ec operand is split as 2^12 Ec: its f16 halves reach down to 2^-36 Ec(0)
+__global__ __launch_bounds__(256) void k_band_sep_scales(const float *__restrict__ qpart, int nblk, int ncol, float er15_rowsum, float *__restrict__ scl)
+{
+    __shared__ float sh[256];
+    for (int k = 0; k < ncol; ++k) {
+        float m = 0.f;
+        for (int i = threadIdx.x; i < nblk; i += 256) m = fmaxf(m, qpart[(size_t)i * ncol + k]);
+        __syncthreads();
+        sh[threadIdx.x] = m;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) sh[threadIdx.x] = fmaxf(sh[threadIdx.x], sh[threadIdx.x + o]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            const float mx = sh[0] * er15_rowsum;
+            int e = 0;
+            if (mx > 0.f && isfinite(mx)) {
+                int ex;
+                (void)frexpf(mx, &ex);
+                e = 14 - ex;
+            }
+            e = max(-90, min(90, e));
+            scl[k] = ldexpf(1.0f, e);
+            scl[BANDV_MAXNC + k] = ldexpf(1.0f, -e - BSEP_EC_LOG2);
+        }
+    }
+}
+
+#ifndef BSEP_PT_X
+#define BSEP_PT_X 4
+#endif
+constexpr int BSEP_PT = BSEP_PT_X; // pixel tiles of 32 per wave of the column pass: one fragment of S feeds all of them
+constexpr int BSEP_KCH = 4;        // k-steps whose Ec fragments sit in LDS at a time (the headline's tiles have 2 or 3)
+static_assert(BSEP_PT % 2 == 0 && BSEP_PT >= 2 && BSEP_PT <= 8, "a lane ends with BSEP_PT / 2 pixels");
+
 // F transposed in LDS: [256][R + 1] (the odd pitch keeps lanes with different values off one bank) | Ec[rad + 1]
 __host__ __device__ inline unsigned band_sep_lds_bytes(int R, int rad) { return 4u * (256u * (unsigned)(R + 1) + (unsigned)(rad + 1)); }
+// ... | (16-byte aligned) the B fragments of BSEP_KCH k-steps: [k-step][pixel tile][hi | lo][lane][8] f16
+__host__ __device__ inline unsigned band_sep_frag_offset(int R, int rad) { return (band_sep_lds_bytes(R, rad) + 15u) & ~15u; }
+__host__ __device__ inline unsigned band_sep_mfma_lds_bytes(int R, int rad) { return band_sep_frag_offset(R, rad) + (unsigned)(BSEP_KCH * BSEP_PT) * 2048u; }
 
-// 8 waves = 8 consecutive image rows x one tile of 64 columns, one lane per pixel, as k_band_vec. Every wave walks the sample
-// columns within dc0 = dcmax[0] of the tile, ascending; per column one gather of Ec (exactly 0 from |dc| = rad on) and KB FMAs
-// whose other operand is S[row][plane][b][k0 .. k0 + KB): wave-uniform, scalar loads. The KB accumulators of a (plane, block of
-// terms) are folded with f_k(v_px) in f64. noskip: a wave without an image row walks too (with the last row's S) and writes nothing.
-template <int NC, int KB>
-__global__ __launch_bounds__(BAND_NW * 64) void k_band_sep_cols(const uint8_t *__restrict__ img, int width, int row_begin, int row_end, int srow0,
-                                                                const int *__restrict__ gcol, int nc, const float *__restrict__ btab, int rad,
-                                                                int dc0, const float *__restrict__ S, int R, const float *__restrict__ ftab,
-                                                                const uint8_t *__restrict__ mask, BandFilter flt, int64_t fpix0, int noskip)
+// The column pass as a banded GEMM on the matrix pipe: U[k][px] = sum_b S[r][b][k] Ec(|c_px - C_b|) with M = term k, N = pixel,
+// K = sample column b, split-f16 (hi hi + hi lo + lo hi, f32 accumulate) on v_mfma_f32_32x32x16_f16.
+// 8 waves = 8 consecutive image rows x one tile of 32 PT columns. The tile's sample columns (band_sep_tile_cols: within dc0 of it)
+// go in k-steps of 16, ascending.
+// B = 2^12 Ec is the same for the 8 rows, every plane and every term tile: its (hi, lo) fragments are formed once per workgroup
+// into LDS (lane l of pixel tile t: pixel 32 t + (l & 31), entries 8 (l >> 5) + j of the k-step; an entry past the range, or rad or
+// more away, is an exact zero in both halves). A tile with more than BSEP_KCH k-steps re-forms them per (plane, term tile).
+// A = scl[plane] S[row][plane][b][k]: lane l holds term k0 + (l & 31) of columns b0 + 8 (l >> 5) + j, eight coalesced loads, scaled
+// and split in registers; a term from R on (R = 16, 48: the last term tile is half full) is a zero that is never loaded, a column
+// past the range is loaded from a clamped index and meets a zero of B.
+// A (k-step, pixel tile) whose block of Ec is zero throughout (band_sep_block_dead) is passed over unless noskip: it adds exact
+// zeros. The accumulator has the pixel on the lane and 16 of the tile's 32 terms in its registers, so the fold sum_k f_k(v_px) U_k
+// is per-lane f64 FMAs against F in LDS -- registers ascending, term tiles ascending -- and one exchange between the half-waves,
+// half 0 + half 1; lane l then owns pixel l of each 64 of the tile. Every wave stays to the end (the barriers); one without an
+// image row loads nothing and stores nothing unless noskip, where it walks with the last row's S.
+template <int NC, int PT>
+__global__ __launch_bounds__(BAND_NW * 64) void k_band_sep_cols_mfma(const uint8_t *__restrict__ img, int width, int row_begin, int row_end, int srow0,
+                                                                     const int *__restrict__ gcol, int nc, const float *__restrict__ btab, int rad,
+                                                                     int dc0, const float *__restrict__ S, int R, const float *__restrict__ ftab,
+                                                                     const float *__restrict__ scl, const uint8_t *__restrict__ mask, BandFilter flt,
+                                                                     int64_t fpix0, int noskip)
 {
-    constexpr int NW = BAND_NW;
+    constexpr int NW = BAND_NW, NI = PT / 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char bsdyn[];
     float *ft = reinterpret_cast<float *>(bsdyn);  // [256][R + 1]
     float *elut = ft + 256 * (R + 1);              // [rad + 1]: Ec(d), 0 at d = rad
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    f16x8 *bfrag = reinterpret_cast<f16x8 *>(bsdyn + band_sep_frag_offset(R, rad)); // [BSEP_KCH][PT][2][64]
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), half = lane >> 5, l31 = lane & 31;
     const int trow0 = row_begin + blockIdx.y * NW, ntw = min(NW, row_end - trow0);
-    const int tc0 = blockIdx.x * 64, tc1 = min(width, tc0 + 64) - 1;
+    const int tc0 = blockIdx.x * (32 * PT);
     for (int i = tid; i < 256 * R; i += NW * 64) ft[(i & 255) * (R + 1) + (i >> 8)] = ftab[i];
     for (int i = tid; i <= rad; i += NW * 64) elut[i] = btab[256 + i];
-    // the tile's range of sample columns: within dc0 of it
-    int Clo = 0, W = 0;
-    if (dc0 >= 0) band_cols_range(gcol, nc, tc0 - dc0, tc1 + dc0, &Clo, &W);
+    int Clo, W;
+    band_sep_tile_cols(gcol, nc, width, tc0, 32 * PT, dc0, &Clo, &W);
+    const int nks = band_sep_ksteps(W);
+    const bool walk = wave < ntw || noskip;
+    const int trow = min(trow0 + wave, row_end - 1);
+    int pv[PT];
+#pragma unroll
+    for (int t = 0; t < PT; ++t) pv[t] = (int)img[(size_t)trow * width + min(tc0 + 32 * t + l31, width - 1)];
     __syncthreads();
-    if (wave >= ntw && !noskip) return;
-    const int trow = min(trow0 + wave, row_end - 1), tcol = min(tc0 + lane, width - 1);
-    const int pv = (int)img[(size_t)trow * width + tcol];
-    const float *fpx = ft + pv * (R + 1);
-    const size_t ncR = (size_t)nc * R;
-    double tot[NC];
+    // the (hi, lo) fragments of 2^12 Ec of the k-steps [ks0, ks0 + BSEP_KCH)
+    auto form = [&](int ks0) {
+        for (int i = tid; i < BSEP_KCH * PT * 64; i += NW * 64) {
+            const int ln = i & 63, t = (i >> 6) % PT, ks = ks0 + (i >> 6) / PT;
+            if (ks >= nks) break;
+            const int cpx = tc0 + 32 * t + (ln & 31);
+            f16x8 hi, lo;
 #pragma unroll
-    for (int k = 0; k < NC; ++k) {
-        tot[k] = 0.0;
-        const float *Srow = S + ((size_t)(trow - srow0) * NC + k) * ncR + (size_t)Clo * R;
-        for (int k0 = 0; k0 < R; k0 += KB) {
-            float U[KB];
-#pragma unroll
-            for (int t = 0; t < KB; ++t) U[t] = 0.f;
-            for (int bb = 0; bb < W; ++bb) {
-                const float ecv = elut[min(abs(tcol - gcol[Clo + bb]), rad)];
-                const float *sp = Srow + (size_t)bb * R + k0;
-#pragma unroll
-                for (int t = 0; t < KB; ++t) U[t] = fmaf(ecv, sp[t], U[t]);
+            for (int j = 0; j < 8; ++j) {
+                const int e = BSEP_KSTEP * ks + 8 * (ln >> 5) + j;
+                const float ec = elut[min(abs(cpx - gcol[band_sep_col(Clo, e, nc)]), rad)];
+                const float v = e < W ? ec * (float)(1 << BSEP_EC_LOG2) : 0.f;
+                hi[j] = (_Float16)v;
+                lo[j] = (_Float16)(v - (float)hi[j]);
             }
+            bfrag[((i >> 6) * 2 + 0) * 64 + ln] = hi;
+            bfrag[((i >> 6) * 2 + 1) * 64 + ln] = lo;
+        }
+    };
+    const bool once = nks <= BSEP_KCH;
+    if (once) {
+        form(0);
+        __syncthreads();
+    }
+    const size_t ncR = (size_t)nc * R;
+    float sdot[NI][NC];
+#pragma unroll 1 // (one plane at a time: unrolled, the planes' loads are hoisted over each other and the registers grow by 12 per plane)
+    for (int k = 0; k < NC; ++k) {
+        const float sc = scl[k];
+        const float *Srow = S + ((size_t)(trow - srow0) * NC + k) * ncR;
+        double tot[PT];
 #pragma unroll
-            for (int t = 0; t < KB; ++t) tot[k] = fma((double)fpx[k0 + t], (double)U[t], tot[k]);
+        for (int t = 0; t < PT; ++t) tot[t] = 0.0;
+        for (int k0 = 0; k0 < R; k0 += 32) {
+            f32x16 acc[PT];
+#pragma unroll
+            for (int t = 0; t < PT; ++t)
+#pragma unroll
+                for (int q = 0; q < 16; ++q) acc[t][q] = 0.f;
+            const bool kin = k0 + l31 < R;
+            const float *Sk = Srow + min(k0 + l31, R - 1);
+            for (int ks0 = 0; ks0 < nks; ks0 += BSEP_KCH) {
+                if (!once) {
+                    __syncthreads();
+                    form(ks0);
+                    __syncthreads();
+                }
+                if (!walk) continue;
+                // (the next k-step's eight loads are in flight under this one's MFMAs)
+                const int ks1 = min(ks0 + BSEP_KCH, nks);
+                float sv[8], sn[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sn[j] = Sk[(size_t)band_sep_col(Clo, BSEP_KSTEP * ks0 + 8 * half + j, nc) * R];
+                for (int ks = ks0; ks < ks1; ++ks) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) sv[j] = sn[j];
+                    if (ks + 1 < ks1)
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) sn[j] = Sk[(size_t)band_sep_col(Clo, BSEP_KSTEP * (ks + 1) + 8 * half + j, nc) * R];
+                    f16x8 ah, al;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const float v = kin ? sv[j] * sc : 0.f;
+                        ah[j] = (_Float16)v;
+                        al[j] = (_Float16)(v - (float)ah[j]);
+                    }
+                    const f16x8 *bf = bfrag + (size_t)(ks - ks0) * PT * 128 + lane;
+#pragma unroll
+                    for (int t = 0; t < PT; ++t) {
+                        if (!noskip && band_sep_block_dead(gcol, nc, Clo, W, ks, tc0 + 32 * t, tc0 + 32 * t + 31, rad)) continue; // (wave-uniform)
+                        const f16x8 bh = bf[t * 128], bl = bf[t * 128 + 64];
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);
+                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);
+                    }
+                }
+            }
+            // register q of a lane: term k0 + (q & 3) + 8 (q >> 2) + 4 half of pixel l31 of each pixel tile
+#pragma unroll
+            for (int q = 0; q < 16; ++q) {
+                if (k0 + 8 * (q >> 2) >= R) continue; // (the empty half of a last term tile: R is a multiple of 16)
+                const int kk = k0 + (q & 3) + 8 * (q >> 2) + 4 * half;
+#pragma unroll
+                for (int t = 0; t < PT; ++t) tot[t] = fma((double)ft[pv[t] * (R + 1) + kk], (double)acc[t][q], tot[t]);
+            }
+        }
+        // half 0 + half 1: lane l ends with pixel tile 2 i + half, i.e. pixel tc0 + 64 i + l
+        const double unscale = BAND_UNSCALE * (double)scl[BANDV_MAXNC + k];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const double s0 = tot[2 * i] + __shfl_xor(tot[2 * i], 32, 64), s1 = tot[2 * i + 1] + __shfl_xor(tot[2 * i + 1], 32, 64);
+            const float r = (float)((half ? s1 : s0) * unscale);
+#pragma unroll
+            for (int kk = 0; kk < NC; ++kk) // (k is not a constant: the planes' loop is not unrolled)
+                if (kk == k) sdot[i][kk] = r;
         }
     }
 
     // the filter, one lane per pixel (the sample pixels are filter_sample_rows' from Phi_A)
-    if (wave >= ntw || tc0 + lane >= width) return;
-    const int64_t px = (int64_t)trow * width + tcol;
-    if (mask[px]) return;
-    float sdot[NC];
+    if (wave >= ntw) return;
 #pragma unroll
-    for (int k = 0; k < NC; ++k) sdot[k] = (float)(tot[k] * BAND_UNSCALE);
-    band_filter_store<NC>(flt, fpix0, px, pv, sdot);
+    for (int i = 0; i < NI; ++i) {
+        const int col = tc0 + 64 * i + lane;
+        if (col >= width) continue;
+        const int64_t px = (int64_t)trow * width + col;
+        if (mask[px]) continue;
+        band_filter_store<NC>(flt, fpix0, px, (int)img[px], sdot[i]);
+    }
 }
 
-template <int NC, int KB>
+template <int NC>
 static int band_sep_cols_launch(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int row0, int nrows, int srow0, const float *S, int R,
-                                const float *ftab, unsigned lds, const uint8_t *d_mask, const BandFilter &flt, int64_t pix0)
+                                const float *ftab, const float *scl, const uint8_t *d_mask, const BandFilter &flt, int64_t pix0)
 {
-    auto kern = k_band_sep_cols<NC, KB>;
+    auto kern = k_band_sep_cols_mfma<NC, BSEP_PT>;
+    const unsigned lds = band_sep_mfma_lds_bytes(R, bt.rad);
     if (lds > 48u * 1024u) GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
+    const dim3 grid((unsigned)ceil_div(bt.width, 32 * BSEP_PT), (unsigned)ceil_div(nrows, BAND_NW));
     hipLaunchKernelGGL(kern, grid, dim3(BAND_NW * 64), lds, ctx->stream, d_img, bt.width, row0, row0 + nrows, srow0, bt.gcol(), bt.nc, bt.tab(), bt.rad,
-                       bt.dc0(), S, R, ftab, d_mask, flt, pix0, ctx->tune.band_noskip ? 1 : 0);
+                       bt.dc0(), S, R, ftab, scl, d_mask, flt, pix0, ctx->tune.band_noskip ? 1 : 0);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
 }
@@ -176,13 +329,15 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     const _Float16 *Ff = nullptr;
     GLF_TRY(rank_tables(ctx, coef, &R, &ftab, &Ff));
     if (R <= 0) return GLF_ERR_UNSUPPORTED;
-    const unsigned lds = band_sep_lds_bytes(R, bt.rad);
-    if (lds > BANDV_LDS_MAX) return GLF_ERR_UNSUPPORTED; // (R = 64: the F table alone is 66 KB)
+    if (band_sep_lds_bytes(R, bt.rad) > BANDV_LDS_MAX) return GLF_ERR_UNSUPPORTED; // (R = 64: the F table alone is 66 KB)
     // S in chunks of whole workgroups' rows: everything at once where BSEP_S_BYTES and the pool allow, else halved
     const size_t row_bytes = sizeof(float) * (size_t)bt.nc * R * ncol;
     int chunk = (int)std::min<size_t>((size_t)round_up(nrows, BAND_NW), std::max<size_t>(BAND_NW, BSEP_S_BYTES / row_bytes / BAND_NW * BAND_NW));
     DevBuf<uint8_t> svals;
-    DevBuf<float> G, S;
+    DevBuf<float> G, S, qpart, scl;
+    const unsigned gblocks = (p + 255) / 256;
+    GLF_TRY(qpart.alloc(ctx, (size_t)gblocks * ncol));
+    GLF_TRY(scl.alloc(ctx, 2 * BANDV_MAXNC));
     GLF_TRY(G.alloc(ctx, (size_t)ncol * p * R));
     while (S.alloc(ctx, (size_t)chunk * bt.nc * R * ncol) != GLF_OK) {
         if (chunk <= BAND_NW) return GLF_ERR_NOMEM;
@@ -194,7 +349,9 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     const bool noskip = ctx->tune.band_noskip;
     GLF_TRY(band_dispatch_planes(ncol, [&](auto nc_) -> int {
         constexpr int NC = decltype(nc_)::value;
-        hipLaunchKernelGGL(k_band_sep_g<NC>, dim3((p + 255) / 256), dim3(256), 0, st, d_psi, p, ld, flt.w, flt.sig.w, svals.p, ftab, R, G.p);
+        hipLaunchKernelGGL(k_band_sep_g<NC>, dim3(gblocks), dim3(256), 0, st, d_psi, p, ld, flt.w, flt.sig.w, svals.p, ftab, R, G.p, qpart.p);
+        GLF_LAUNCH_CHECK(ctx);
+        hipLaunchKernelGGL(k_band_sep_scales, dim3(1), dim3(256), 0, st, qpart.p, (int)gblocks, NC, (float)bt.er15_rowsum, scl.p);
         GLF_LAUNCH_CHECK(ctx);
         const unsigned ncR = (unsigned)bt.nc * (unsigned)R, E = ncR * NC;
         GLF_HIP(ctx, hipEventRecord(e0, st));
@@ -203,8 +360,7 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
             hipLaunchKernelGGL(k_band_sep_rows, dim3((E + 255) / 256, (unsigned)ceil_div(n, BSEP_RB)), dim3(256), 0, st, G.p, E, ncR, bt.nr, r0, r0 + n, r0,
                                bt.grow(), bt.tab(), bt.rad, bt.rowband_px(), noskip ? 1 : 0, S.p);
             GLF_LAUNCH_CHECK(ctx);
-            if (R % 32 == 0) GLF_TRY((band_sep_cols_launch<NC, 32>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, lds, d_mask, flt, pix0)));
-            else GLF_TRY((band_sep_cols_launch<NC, 16>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, lds, d_mask, flt, pix0)));
+            GLF_TRY(band_sep_cols_launch<NC>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, scl.p, d_mask, flt, pix0));
         }
         GLF_HIP(ctx, hipEventRecord(e1, st));
         return GLF_OK;
@@ -214,9 +370,11 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
     if (kernel_ms) *kernel_ms = ms;
     if (entries_evaluated) {
-        // lane-entries covered by the windows, from the plan: 64 x sum over the walking waves of (columns walked x band rows feeding them)
+        // entries covered by the windows, from the plan: sum over the walking waves of (the 16 x 32 blocks of Ec the column pass
+        // executes x band rows feeding them)
         uint64_t cols = 0, rows = 0;
-        for (int t = 0; t < bt.ntiles_px; ++t) cols += (uint64_t)bt.cols_near_tile(t);
+        for (int tc0 = 0; tc0 < width; tc0 += 32 * BSEP_PT)
+            cols += band_sep_tile_entries(bt.geom.cols.data(), bt.nc, width, tc0, 32 * BSEP_PT, bt.dc0(), bt.rad, noskip);
         if (noskip) rows = (uint64_t)ceil_div(nrows, BAND_NW) * BAND_NW * (uint64_t)bt.nr; // every wave, every band row
         else
             for (int r = row0; r < row1; ++r) {
@@ -224,7 +382,7 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
                 band_rows_hull(bt.h_rowband_px.data(), r, 1, &alo, &ahi);
                 rows += (uint64_t)std::max(0, ahi - alo + 1);
             }
-        *entries_evaluated = 64ull * cols * rows;
+        *entries_evaluated = cols * rows;
     }
     if (mfma_flops) *mfma_flops = 0.0;
     band_stats(stats, bt, row0, row1, 1, ms, (unsigned)ncol, R);
