@@ -990,6 +990,43 @@ static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, 
                               : GLF_OK;
 }
 
+// The PCG's set-up, one code for the solver (inverse_power_iteration) and for a solve on its own (operator_solve): the work
+// buffers, the operand maxima carried from their writers, and the Jacobi preconditioner -- the caller's (a factored or sharded
+// A holds no whole diagonal) or the stored matrix's own diagonal.
+static int cg_setup(glf_ctx *ctx, CgWork &cg, const float *A, int64_t lda, unsigned p, unsigned ld, const MatShard *shard, const float *d_dinv)
+{
+    GLF_TRY(cg.init(ctx, p, ld, shard));
+    cg.carry_maxima = true;
+    if (d_dinv) // Jacobi preconditioner supplied by the caller (a sharded A does not hold the whole diagonal)
+        GLF_HIP(ctx, hipMemcpyAsync(cg.dinv.p, d_dinv, sizeof(float) * p, hipMemcpyDeviceToDevice, ctx->stream));
+    else if (shard && shard->rows_per_rank)
+        return set_error(ctx, GLF_ERR_INVALID, "sharded inverse iteration needs the diagonal (d_dinv)");
+    else
+        hipLaunchKernelGGL(k_diag_inv, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, A, lda, p, cg.dinv.p);
+    GLF_LAUNCH_CHECK(ctx);
+    return GLF_OK;
+}
+
+// One block solve L_A X = B on its own (glf_operator_solve): the set-up and the PCG of the solver, then the PCG's state copied
+// out -- X = CgWork::Xs, R = CgWork::R (the recurrence residual, not a recomputation), `rows` rows of ld each (rows from p on:
+// the zeros the work buffers hold there). B is only read. A cut at max_it answers GLF_ERR_NOCONV after the copies.
+int operator_solve(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, unsigned m, unsigned ld, const MatShard *shard, const float *d_dinv,
+                   const float *d_B, float *d_X, float *d_R, unsigned rows, double rtol, int max_it, int *iters, int *unconverged)
+{
+    if (m == 0 || m > ld || !valid_ld(ld) || (shard && shard->rows_per_rank) || !d_dinv)
+        return set_error(ctx, GLF_ERR_INVALID, "operator_solve: m=%u ld=%u p=%u (one rank, m <= ld, ld 32, 64, 128 or 256)", m, ld, p);
+    CgWork cg;
+    GLF_TRY(cg_setup(ctx, cg, A, lda, p, ld, shard, d_dinv));
+    const int rc = block_pcg_work(ctx, cg, A, lda, p, const_cast<float *>(d_B), m, ld, rtol, max_it, iters, false);
+    if (rc != GLF_OK && rc != GLF_ERR_NOCONV) return rc;
+    const size_t n = (size_t)std::min<unsigned>(rows, vec_rows(p, shard, ctx->comm.size)) * ld;
+    GLF_HIP(ctx, hipMemcpyAsync(d_X, cg.Xs.p, sizeof(float) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    if (d_R) GLF_HIP(ctx, hipMemcpyAsync(d_R, cg.R.p, sizeof(float) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (unconverged) *unconverged = *cg.h_nactive;
+    return rc;
+}
+
 // =====================================================================================
 // Classical Gram-Schmidt (hpc/gram_schmidt.c:29-64), column k at a time
 // =====================================================================================
@@ -2050,22 +2087,13 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
     GsWork gs;
     GLF_TRY(gs.init(ctx, p, ld));
     CgWork cg;
-    GLF_TRY(cg.init(ctx, p, ld, shard));
-    cg.carry_maxima = true;
+    GLF_TRY(cg_setup(ctx, cg, A, lda, p, ld, shard, d_dinv));
     ResWork rs;
     GLF_TRY(rs.init(ctx, p, ld, shard));
     // Sharded solve (see Rows above): every vector kernel below touches this rank's rows [rows.r0, rows.r1) only.
     const Rows rows = rows_of(p, shard);
     const unsigned nloc = rows.n();
     const size_t off = (size_t)rows.r0 * ld, nloc_ld = (size_t)nloc * ld;
-    if (d_dinv) // Jacobi preconditioner supplied by the caller (a sharded A does not hold the whole diagonal)
-        GLF_HIP(ctx, hipMemcpyAsync(cg.dinv.p, d_dinv, sizeof(float) * p, hipMemcpyDeviceToDevice, st));
-    else if (shard && shard->rows_per_rank)
-        return set_error(ctx, GLF_ERR_INVALID, "sharded inverse iteration needs the diagonal (d_dinv)");
-    else
-        hipLaunchKernelGGL(k_diag_inv, dim3((p + 255) / 256), dim3(256), 0, st, A, lda, p, cg.dinv.p);
-    GLF_LAUNCH_CHECK(ctx);
-
     GLF_TRY(mv_collect(ctx));
     const int mv_count0 = ctx->mv_count, narrow0 = ctx->narrow_sweeps;
     const double mv_ms0 = ctx->mv_ms, mv_bytes0 = ctx->mv_bytes;

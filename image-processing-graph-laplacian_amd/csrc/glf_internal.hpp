@@ -813,6 +813,10 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
                             const MatShard *shard = nullptr, const float *d_dinv = nullptr,
                             const float *d_X0_block = nullptr);
 
+// one block solve L_A X = B by the solver's PCG, its state copied out (glf_operator_solve): see eigen.hip
+int operator_solve(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, unsigned m, unsigned ld, const MatShard *shard, const float *d_dinv,
+                   const float *d_B, float *d_X, float *d_R, unsigned rows, double rtol, int max_it, int *iters, int *unconverged);
+
 // m > 256 (the reference default m = p - 1): panel-major blocks, see eigen.hip
 int inverse_power_iteration_panels(glf_ctx *ctx, const float *A, int64_t lda, unsigned p, unsigned m, const double *h_X0,
                                    unsigned long long seed, int opti_gs, double epsilon, double inner_rtol, int max_outer,

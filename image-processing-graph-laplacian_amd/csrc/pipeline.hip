@@ -699,6 +699,8 @@ struct glf_operator {
     unsigned row0 = 0, row1 = 0;
     int contraction = 0, mv_path = 0; // what the form was chosen (and a factored operator's tables built) under
     bool sweep_samples = false;
+    double alpha = 0.0;               // of L_A = alpha (D - K_A), and the descriptor's degree: the Jacobi preconditioner of glf_operator_solve
+    const double *degree = nullptr;
     ~glf_operator() { grid_op_destroy(gop); }
 };
 
@@ -738,6 +740,8 @@ int glf_operator_create(glf_ctx *ctx, const glf_mat *L_B, int skip_exact_zeros, 
     op->contraction = ctx->contraction;
     op->mv_path = ctx->tune.mv_path;
     op->sweep_samples = ctx->tune.sweep_samples;
+    op->alpha = alpha;
+    op->degree = L_B->degree;
     GLF_TRY(operator_factored(ctx, samples, h_idx.data(), p, width, height, coef, kernel, ld_hint, &op->gop));
     if (forced && !op->gop)
         return set_error(ctx, GLF_ERR_UNSUPPORTED,
@@ -796,6 +800,55 @@ int glf_operator_apply(glf_operator *op, const glf_mat *X, glf_mat *Y, glf_opera
         info->row1 = (int32_t)op->row1;
     }
     return GLF_OK;
+}
+
+int glf_operator_solve(glf_operator *op, const glf_mat *B, glf_mat *X, glf_mat *R, unsigned m, double rtol, int max_it, glf_solve_info *info)
+{
+    if (!op || !op->ctx) return GLF_ERR_INVALID;
+    glf_ctx *ctx = op->ctx;
+    auto dense = [](const glf_mat *M) { return M && M->kind == GLF_MAT_DENSE && M->data; };
+    if (!dense(B) || !dense(X) || (R && !dense(R)) || B->data == X->data || (R && (R->data == B->data || R->data == X->data)))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: B, X and R (or NULL) must be distinct dense matrices");
+    GLF_ENTER(ctx);
+    const unsigned p = op->p;
+    if (ctx->contraction != op->contraction || ctx->tune.mv_path != op->mv_path || ctx->tune.sweep_samples != op->sweep_samples)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: the contraction mode, MV_PATH or SWEEP_COLPASS changed since glf_operator_create");
+    if (op->shard.rows_per_rank)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_operator_solve: the operator was created for the rows [%u, %u) (the sharded solve needs a communicator)",
+                         op->row0, op->row1);
+    if (B->rows < (int64_t)p || X->rows < (int64_t)p || (R && R->rows < (int64_t)p))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: B has %lld rows, X %lld, R %lld, fewer than p = %u", (long long)B->rows,
+                         (long long)X->rows, (long long)(R ? R->rows : p), p);
+    if (B->ld != X->ld || (R && R->ld != B->ld) || B->ld <= 0 || B->ld > 256)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: B has ld %lld, X ld %lld, R ld %lld (equal, at most 256)", (long long)B->ld,
+                         (long long)X->ld, (long long)(R ? R->ld : B->ld));
+    const unsigned ld = (unsigned)B->ld;
+    if (!valid_ld(ld)) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: the block PCG takes ld 32, 64, 128 or 256 (ld = %u)", ld);
+    if (op->gop && op->gen != PixGen::Grey && ld != 32 && ld != 64)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: the %s band form takes ld 32 or 64 (ld = %u)", pix_desc(op->gen).name, ld);
+    if (m == 0 || m > ld) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: m = %u columns of ld = %u (0 < m <= ld)", m, ld);
+    if (!(rtol > 0.0) || max_it < 0) return set_error(ctx, GLF_ERR_INVALID, "glf_operator_solve: rtol = %g, max_it = %d", rtol, max_it);
+    // the whole path's Jacobi preconditioner, whatever the form: 1 / (alpha (D_i - 1)) from the degree
+    DevBuf<float> dinv;
+    GLF_TRY(dinv.alloc(ctx, p));
+    hipLaunchKernelGGL(k_dinv_from_degree, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, op->degree, p, op->alpha, dinv.p);
+    GLF_LAUNCH_CHECK(ctx);
+    GLF_TRY(mv_collect(ctx));
+    const int mv_count0 = ctx->mv_count, narrow0 = ctx->narrow_sweeps;
+    int iters = 0, unconverged = 0;
+    const int rc = operator_solve(ctx, op->store.LA.p, op->store.lda, p, m, ld, shard_arg(op->shard), dinv.p, B->data, X->data, R ? R->data : nullptr,
+                                  (unsigned)round_up(p, VEC_PAD), rtol, max_it, &iters, &unconverged);
+    if (rc != GLF_OK && rc != GLF_ERR_NOCONV) return rc;
+    GLF_TRY(mv_collect(ctx));
+    if (info) {
+        info->iters = iters;
+        info->unconverged = unconverged;
+        info->matvecs = ctx->mv_count - mv_count0;
+        info->narrow_sweeps = ctx->narrow_sweeps - narrow0;
+        info->path = op->gop ? grid_op_path(op->gop) : 0;
+        info->reserved = 0;
+    }
+    return rc; // (GLF_ERR_NOCONV: block_pcg_work's message stands)
 }
 
 int glf_operator_stored(const glf_operator *op, glf_mat *view)

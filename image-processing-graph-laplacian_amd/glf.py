@@ -70,7 +70,7 @@ EXPORTS = [
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize", "glf_graph_project_wide",
     "glf_graph_compact", "glf_graph_storage", "glf_graph_dequantize",
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
-    "glf_operator_create", "glf_operator_apply", "glf_operator_stored", "glf_operator_destroy",
+    "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex",
 ]
 MAX_SIGNALS = 4
@@ -188,6 +188,11 @@ class OperatorInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("ksplit", C.c_int32), ("skipping", C.c_int32), ("row0", C.c_int32), ("row1", C.c_int32)]
 
 
+class SolveInfo(C.Structure):
+    _fields_ = [("iters", C.c_int32), ("unconverged", C.c_int32), ("matvecs", C.c_int32), ("narrow_sweeps", C.c_int32),
+                ("path", C.c_int32), ("reserved", C.c_int32)]
+
+
 class NystroemInfo(C.Structure):
     _fields_ = [("path", C.c_int32), ("contraction", C.c_int32), ("skipping", C.c_int32), ("lut", C.c_int32), ("row0", C.c_uint32),
                 ("row1", C.c_uint32), ("entries_evaluated", C.c_double)]
@@ -252,6 +257,7 @@ _lib.glf_fit_factor.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_rows.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_operator_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_double, C.c_int, C.c_void_p]
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_operator_destroy.argtypes = [C.c_void_p]
 _lib.glf_Nystroem_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
@@ -1417,6 +1423,49 @@ class Operator:
         finally:
             ctx.destroy(dX, dY)
         return out
+
+    def solve(self, B, X, R, m, rtol=1e-5, max_it=1000, allow_noconv=False):
+        """glf_operator_solve on dense Mats of one ld (R: a Mat or None) -> the info dict (iters, unconverged, matvecs, narrow_sweeps,
+        path, reserved, and status: OK, or ERR_NOCONV where allow_noconv let a cut solve pass); also kept in self.solve_info."""
+        info = SolveInfo()
+        rc = _lib.glf_operator_solve(self._h, C.byref(B), C.byref(X), C.byref(R) if R is not None else None, C.c_uint(m), C.c_double(rtol),
+                                     C.c_int(max_it), C.byref(info))
+        if not (allow_noconv and rc == ERR_NOCONV):
+            self.ctx._check(rc, "operator.solve")
+        self.solve_info = {k: int(getattr(info, k)) for k, _ in SolveInfo._fields_}
+        self.solve_info["status"] = rc
+        return self.solve_info
+
+    def solve_numpy(self, B, m, rtol=1e-5, max_it=1000, allow_noconv=False, fill=None, want_R=True):
+        """B: float32 [rows <= round_up(p, 64), ld] (the whole block, padding columns included) -> (X, R, info), float32
+        [round_up(p, 64), ld] each. X and R start as zeros, or as the float32 array `fill` (a sentinel: a refusal leaves it; kept
+        in self.last_X, self.last_R even when the call raises)."""
+        B = np.ascontiguousarray(B, dtype=np.float32)
+        rows, ld = (self.p + 63) // 64 * 64, B.shape[1]
+        if B.shape[0] > rows:
+            raise ValueError("B has %d rows, more than round_up(p, 64) = %d" % (B.shape[0], rows))
+        ctx = self.ctx
+        full = np.zeros((rows, ld), dtype=np.float32)
+        full[:B.shape[0]] = B
+        x0 = np.zeros((rows, ld), dtype=np.float32) if fill is None else np.ascontiguousarray(fill, dtype=np.float32)
+        assert x0.shape == (rows, ld)
+        dB, dX = ctx.dense_from_numpy(full, ld=ld), ctx.dense_from_numpy(x0, ld=ld)
+        dR = ctx.dense_from_numpy(x0, ld=ld) if want_R else None
+        mats = [dB, dX] + ([dR] if want_R else [])
+        for M in mats:
+            M.rows = max(B.shape[0], 1) if B.shape[0] < self.p else self.p
+        X, R = np.empty((rows, ld), dtype=np.float32), (np.empty((rows, ld), dtype=np.float32) if want_R else None)
+        try:
+            try:
+                info = self.solve(dB, dX, dR, m, rtol, max_it, allow_noconv)
+            finally:
+                ctx._check(_lib.glf_memcpy_d2h(ctx._ctx, _ptr(X), C.c_void_p(dX.data), C.c_size_t(X.nbytes)))
+                if want_R:
+                    ctx._check(_lib.glf_memcpy_d2h(ctx._ctx, _ptr(R), C.c_void_p(dR.data), C.c_size_t(R.nbytes)))
+                self.last_X, self.last_R = X, R
+        finally:
+            ctx.destroy(*mats)
+        return X, R, info
 
     def stored(self):
         """The stored form's matrix as downloaded, float32 [p, row1 - row0] (element (k, row - row0) of the symmetric L_A);

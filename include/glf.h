@@ -330,6 +330,24 @@ typedef struct glf_operator_info {
 int glf_operator_create(glf_ctx *ctx, const glf_mat *L_B, int skip_exact_zeros, unsigned row0, unsigned row1, unsigned ld_hint,
                         glf_operator **op);
 int glf_operator_apply(glf_operator *op, const glf_mat *X, glf_mat *Y, glf_operator_info *info);
+/* glf_operator_solve: L_A X = B for the first m columns by the eigen-solve's Jacobi-preconditioned block PCG -- the solver's own
+ * set-up and loop (one code), with the whole path's preconditioner 1 / (alpha (D_i - 1)) for every form and its per-column rule
+ * ||r|| <= rtol ||b||. B, X and R: distinct dense matrices of one ld (32, 64, 128 or 256; the colour, 16-bit and float band forms 32
+ * or 64), at least p logical rows and round_up(p, 64) rows of storage; 0 < m <= ld. B is only read. X: the solution; R (or NULL): the
+ * PCG's own recurrence residual at exit, not a recomputation of B - L_A X. The padding columns m .. ld - 1 never iterate: X is zero
+ * there and R holds B's values; a column of B that is all zero returns X = 0 and costs no step. A solve cut at max_it answers
+ * GLF_ERR_NOCONV, and X, R and info then hold the state at the cut. An operator created for a row range is refused
+ * (GLF_ERR_UNSUPPORTED: the sharded solve needs a communicator); every refusal names its reason and leaves X and R untouched. The
+ * NO_NARROW and OPERAND_MAXIMA tunings act as in the whole path. */
+typedef struct glf_solve_info {
+    int32_t iters;          /* block PCG steps taken */
+    int32_t unconverged;    /* columns still active at exit */
+    int32_t matvecs, narrow_sweeps; /* as in glf_eig_stats: timed sweeps (the stored form with f32 operands times none), and the packed ones */
+    int32_t path;           /* as glf_operator_info.path */
+    int32_t reserved;
+} glf_solve_info;
+int glf_operator_solve(glf_operator *op, const glf_mat *B, glf_mat *X, glf_mat *R /* or NULL */, unsigned m, double rtol, int max_it,
+                       glf_solve_info *info);
 /* the stored form's matrix as a dense view (not owned: p rows, row1 - row0 columns, element (k, row) of the symmetric L_A at
  * data[k * ld + row - row0]); GLF_ERR_UNSUPPORTED for a factored form, which stores none */
 int glf_operator_stored(const glf_operator *op, glf_mat *view);
