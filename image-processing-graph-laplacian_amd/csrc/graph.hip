@@ -185,10 +185,17 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
     // (pipeline.hip, "p = width*height*0.01 ..." and "GetNumberEigenvalues": keep the two in step); the call's own answer is checked
     // against it below (S.m, cap.ld), and capture's phi_floats guard refuses a Phi that would not fit
     unsigned p = opt.num_samples ? opt.num_samples : (unsigned)((double)N * opt.sample_frac);
+    // The list itself stays in the handle (glf_graph_samples). It is this sizing call's list, not a copy of the capture call's:
+    // image_processing_run below repeats the sampler call with the same (width, height, request, seed), and both samplers are pure
+    // functions of those (glf_Sampling is a grid rule, glf_RandomSampling draws from its own seeded generator, tests/test_abi.py),
+    // so the two lists are equal entry by entry. Only the count is cross-checked below (S.p): a sampler that read anything else --
+    // the image, a clock, a global generator -- would break this, and would have to hand its list out through glf_capture instead.
+    std::vector<unsigned> samples;
     {
         unsigned *h_idx = nullptr;
         const int rc = opt.sampling == GLF_SAMPLING_RANDOM ? glf_RandomSampling(width, height, &p, &h_idx, opt.sampling_seed)
                                                            : glf_Sampling(width, height, &p, &h_idx);
+        if (rc == GLF_OK && h_idx) samples.assign(h_idx, h_idx + p);
         std::free(h_idx);
         if (rc != GLF_OK || p < 2) return set_error(ctx, GLF_ERR_INVALID, "sampling failed (requested %u samples on %dx%d)", p, width, height);
     }
@@ -223,6 +230,8 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
             rc = image_processing_run(ctx, &opt, gen, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap, nullptr);
         if (rc == GLF_OK && (S.m != m || cap.ld != ld))
             rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised m=%u ld=%u, %u / %u expected", S.m, cap.ld, m, ld);
+        if (rc == GLF_OK && S.p != samples.size())
+            rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised p=%u, %zu expected", S.p, samples.size());
         if (rc == GLF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GLF_ERR_HIP, "glf_graph_build: synchronize");
     }
     if (rc != GLF_OK) {
@@ -233,6 +242,7 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
     g->p = S.p;
     g->m = m;
     g->ld = ld;
+    g->samples = std::move(samples);
     if (stats) *stats = S;
     *graph = g;
     return GLF_OK;

@@ -70,6 +70,7 @@ EXPORTS = [
     "glf_graph_transform", "glf_basis_orthonormal", "glf_graph_orthonormalize", "glf_graph_project_wide",
     "glf_graph_compact", "glf_graph_storage", "glf_graph_dequantize",
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
+    "glf_graph_edges", "glf_graph_samples",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex",
 ]
@@ -94,6 +95,7 @@ GRAPH_MAX_PLANES = 32      # GLF_GRAPH_MAX_PLANES: the most planes of one glf_gr
 GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixel terms) of glf_graph_normal_equations' G
 QUAD_MAX_COLS = 64         # GLF_QUAD_MAX_COLS: the most columns of R of one glf_graph_quadform call
 QUAD_MAX_CENTRES = 32      # GLF_QUAD_MAX_CENTRES: the most centres of one glf_graph_quadform call
+EDGE_DIRS = {"E": 1, "S": 2, "SE": 4, "SW": 8}   # GLF_EDGE_*: the neighbour (row, col+1), (row+1, col), (row+1, col+1), (row+1, col-1)
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -255,6 +257,8 @@ _lib.glf_graph_dequantize.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_graph_quadform.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_int, C.c_void_p]
 _lib.glf_fit_factor.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_rows.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
+_lib.glf_graph_edges.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_graph_samples.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_double, C.c_int, C.c_void_p]
@@ -1757,6 +1761,101 @@ class Graph:
         g32 = g.astype(np.float32).astype(np.float64)          # what the kernel multiplies by: the centre is then the pixel's own y
         R = np.diag(g32)[:, :dim]
         return self.quadform(R, g32[None, :dim] * self.rows(seeds)[:, :dim].astype(np.float64))
+
+    def samples(self):
+        """The sample pixels of the build call as numpy uint32 [p], ascending flat pixel indices (glf_graph_samples). Their rows of
+        Phi are phi_A's own, every other row is extended, and the two differ in scale: edges() leaves them out by default."""
+        idx = np.zeros(self.info["p"], dtype=np.uint32)
+        self.ctx._check(_lib.glf_graph_samples(self._g, _ptr(idx)), "graph samples")
+        return idx
+
+    def _edge_args(self, dirs, response, dim, valid, exclude_samples):
+        """(the bit mask of dirs, scale [dim] f64, dim, the validity mask as device uint8 [H, W] or None)."""
+        t = self.ctx.torch
+        m, (h, w) = self.info["m"], (self.info["height"], self.info["width"])
+        dirs = (dirs,) if isinstance(dirs, str) else tuple(dirs)
+        if not dirs or any(d not in EDGE_DIRS for d in dirs) or len(set(dirs)) != len(dirs):
+            raise ValueError("dirs must be distinct names out of %s, got %r" % (sorted(EDGE_DIRS), dirs))
+        dim = m if dim is None else int(dim)
+        if not 1 <= dim <= m:
+            raise ValueError("dim must be in 1 .. %d, got %d" % (m, dim))
+        g = np.asarray(1.0 - self.eigenvalues if response is None else response, dtype=np.float64)
+        if g.shape != (m,):
+            raise ValueError("response must be [%d], got %s" % (m, g.shape))
+        if valid is not None:
+            if tuple(valid.shape) != (h, w) or not valid.is_cuda:
+                raise ValueError("valid must be a device tensor [%d, %d], got %s" % (h, w, tuple(valid.shape)))
+            self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the mask is complete before the library reads it
+        with t.cuda.stream(self.ctx.stream):
+            mask = None if valid is None else (valid != 0).to(t.uint8).contiguous()
+            if exclude_samples:
+                mask = t.ones((h, w), dtype=t.uint8, device=self.ctx.device) if mask is None else mask   # (a fresh tensor either way)
+                mask.view(-1)[t.from_numpy(self.samples().astype(np.int64)).to(self.ctx.device)] = 0
+        return sum(EDGE_DIRS[d] for d in dirs), np.ascontiguousarray(g[:dim]), dim, mask
+
+    def edges(self, dirs=("E", "S", "SE", "SW"), response=None, dim=None, valid=None, exclude_samples=True):
+        """The spectral edge map (glf_graph_edges): per direction the squared distance in the embedding between a pixel and its
+        neighbour, sum_{c < dim} (g_c (Phi[nb][c] - Phi[px][c]))^2 with nb = E (row, col + 1), S (row + 1, col), SE (row + 1, col + 1),
+        SW (row + 1, col - 1) -> device float32 [len(dirs), H, W], plane i for dirs[i], in one pass over Phi (m > 64: one per 64
+        columns). response: g [m], default 1 - lam (distance's default); dim: default m; valid: device tensor [H, W], an edge
+        with an endpoint where it is 0 is +0, as is an edge that leaves the image; exclude_samples: also drop the handle's sample
+        pixels (samples()), whose rows of Phi have another scale than the extended rows and would dominate the map. The values are
+        the edge weights of the 4- / 8-connected pixel graph in the spectral metric."""
+        t = self.ctx.torch
+        dirs = (dirs,) if isinstance(dirs, str) else tuple(dirs)
+        out, order, _ = self._edges_run(dirs, response, dim, valid, exclude_samples)
+        if list(dirs) == order:
+            return out
+        with t.cuda.stream(self.ctx.stream):
+            out = out[[order.index(d) for d in dirs]]
+        self.ctx.stream.synchronize()                                            # as every call here: the result is complete on return
+        return out
+
+    def _edges_run(self, dirs, response, dim, valid, exclude_samples):
+        """(the planes of glf_graph_edges in the library's order, that order as a list of names, the mask the call ran with as device
+        uint8 [H, W] or None). Returns with the stream drained."""
+        t = self.ctx.torch
+        bits, scale, dim, mask = self._edge_args(dirs, response, dim, valid, exclude_samples)
+        order = sorted(dirs, key=lambda d: EDGE_DIRS[d])                         # the library's plane order: ascending bits
+        h, w = self.info["height"], self.info["width"]
+        with t.cuda.stream(self.ctx.stream):
+            out = t.empty((len(order), h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        self.ctx._check(_lib.glf_graph_edges(self._g, C.c_uint(bits), C.c_uint(dim), _ptr(scale), C.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                             C.c_void_p(out.data_ptr())), "graph edges")   # (returns with the stream drained)
+        return out, order, mask
+
+    def boundary(self, response=None, dim=None, valid=None, exclude_samples=True):
+        """The boundary strength of every pixel -> device float32 [H, W]: the sum over the pixel's up to eight incident edges (its own
+        E, S, SE, SW edges and those of its W, N, NW, NE predecessors that point at it) of edges(...), divided by the number of them
+        that are live (inside the image, both endpoints valid), 0 where none is. Formed in torch on the library's stream from the
+        four planes of one glf_graph_edges call and the mask it ran with, in f32, the eight terms added in that order; returns with
+        that stream drained."""
+        t = self.ctx.torch
+        e, _, mask = self._edges_run(("E", "S", "SE", "SW"), response, dim, valid, exclude_samples)
+        h, w = self.info["height"], self.info["width"]
+        with t.cuda.stream(self.ctx.stream):
+            v = t.ones((h, w), dtype=t.bool, device=self.ctx.device) if mask is None else mask != 0
+            live = t.zeros((4, h, w), dtype=t.bool, device=self.ctx.device)
+            live[0, :, :-1] = v[:, :-1] & v[:, 1:]
+            live[1, :-1, :] = v[:-1, :] & v[1:, :]
+            live[2, :-1, :-1] = v[:-1, :-1] & v[1:, 1:]
+            live[3, :-1, 1:] = v[:-1, 1:] & v[1:, :-1]
+            total, count = t.zeros((h, w), dtype=t.float32, device=self.ctx.device), t.zeros((h, w), dtype=t.float32, device=self.ctx.device)
+            for k in range(4):                                                   # the pixel's own forward edges
+                total += e[k]
+                count += live[k]
+            # the forward edges of the predecessors, seen from the pixel they point at
+            total[:, 1:] += e[0, :, :-1]
+            count[:, 1:] += live[0, :, :-1]
+            total[1:, :] += e[1, :-1, :]
+            count[1:, :] += live[1, :-1, :]
+            total[1:, 1:] += e[2, :-1, :-1]
+            count[1:, 1:] += live[2, :-1, :-1]
+            total[1:, :-1] += e[3, :-1, 1:]
+            count[1:, :-1] += live[3, :-1, 1:]
+            out = t.where(count > 0, total / count.clamp_min(1.0), t.zeros_like(total))
+        self.ctx.stream.synchronize()                                            # as every call here: the result is complete on return
+        return out
 
     def _robust_loss(self, loss, c, sigma, nplanes):
         rl = RobustLoss(struct_size=C.sizeof(RobustLoss), kind=_robust_kind(loss), c=0.0 if c is None else float(c))

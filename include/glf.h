@@ -1019,6 +1019,45 @@ int glf_graph_storage(const glf_graph *g, int *storage, int32_t *h_exponent /* H
  * a NULL handle or d_out, before any device work. Returns with the stream drained. */
 int glf_graph_dequantize(glf_graph *g, float *d_out /* device [N][ld] */);
 
+/* ---- graph handle: the spectral edge map, neighbour differences of Phi ------------------------------------------------------------------
+ * Every other call on a handle treats the rows of Phi as an unordered set. glf_graph_edges uses that they lie on the image raster:
+ * for the neighbours nb of a pixel px = (row, col) -- E (row, col + 1), S (row + 1, col), SE (row + 1, col + 1), SW (row + 1, col - 1)
+ * -- it returns out(px) = sum_{c < dim} (scale_c (Phi[nb][c] - Phi[px][c]))^2, the squared distance in the embedding between the two
+ * pixels (k_graph_edges, the handle's stencil kernel). With scale = g(lam) it is the boundary signal sum_c g_c^2 (v_c(px) - v_c(nb))^2
+ * of normalised-cuts contour detection, and the edge weights of the 4- / 8-connected pixel graph in the spectral metric that a
+ * watershed, a random walker or an edge-stopping function consume; glf_graph_quadform with seed centres is its global counterpart.
+ * The sample pixels' rows of Phi are phi_A's own bits, every other row is extended, and the two differ in scale (README, "Spectral
+ * edge map"): an edge that touches a sample pixel is an outlier. Hence the validity mask, and glf_graph_samples, which says where
+ * the samples are.
+ * Planes: plane k belongs to the k-th set bit of dirs in ascending order, [popcount(dirs)][N] floats. A plane's value is +0 (the bit
+ * pattern) where nb lies outside the image, or d_valid is given and valid[px] or valid[nb] is 0: E and SE at col = W - 1, SW at
+ * col = 0, S / SE / SW on the last row. The raster neighbour px + 1 of the next image row is never taken for E. Every pixel of every
+ * requested plane is written, nothing else is.
+ * Operation by operation, in f32, nothing contracted that is not written here: s_c = fl32(scale_c); q = +0; for c = 0 .. dim - 1
+ * ascending, one chain per (pixel, direction): d = Phi[nb][c] - Phi[px][c] (one subtraction), x = s_c d (one multiplication),
+ * q = fmaf(x, x, q). The chain continues across the staged column chunks (CW = min(ld, 64); a partial sum that is stored and
+ * reloaded between chunks keeps its bits). A plane's bits therefore depend neither on dirs, nor on ld, nor on the launch geometry,
+ * nor on d_valid where the edge is live; a column with scale 0 changes nothing (x = +-0, fmaf(x, x, q) = q); two calls give the same
+ * bits; no atomics. Columns at or beyond dim rounded up to CW are not read (the cluster step's rule); the columns between dim and
+ * that bound are read and multiplied by 0, so they must be finite (columns >= m are zeros).
+ * Against exact arithmetic on the handle's Phi with the scale fl32(scale), q* = sum_c (s_c (Phi[nb][c] - Phi[px][c]))^2:
+ * |q - q*| <= gamma(dim + 4) q* + dim 2^-149, gamma(n) = n 2^-24 / (1 - n 2^-24) ("Spectral edge map").
+ * On a compact handle 2^e_c is folded into scale_c in f64 before its fl32 (the cluster calls' rule): the call returns, bit for bit,
+ * what it returns on an f32 handle whose Phi is Q (glf_graph_dequantize), short of under- or overflow of a folded scale in f32.
+ * Out of scope: a full (non-diagonal) metric, unit-length rows, Gaussian-derivative or oriented filters wider than one pixel,
+ * non-maximum suppression, watershed, connected components, repairing the scale of Phi's sample rows, contexts with a communicator
+ * and glf_multi_* (handles refuse them), m > 256, a flag of the image_processing host program. */
+enum { GLF_EDGE_E = 1, GLF_EDGE_S = 2, GLF_EDGE_SE = 4, GLF_EDGE_SW = 8 };   /* neighbour (row, col+1), (row+1, col), (row+1, col+1), (row+1, col-1) */
+/* GLF_ERR_INVALID before any device work, d_out untouched, the reason in glf_ctx_last_error: dirs 0 or above 15, dim 0 or above m, a
+ * scale (after folding) whose fl32 is not finite, a NULL d_out; a NULL handle likewise (there is no context to take the reason).
+ * d_valid is not checked. Returns with the stream drained. */
+int glf_graph_edges(glf_graph *g, unsigned dirs, unsigned dim, const double *h_scale /* HOST [dim] or NULL = ones */,
+                    const uint8_t *d_valid /* device [N] or NULL */, float *d_out /* device [popcount(dirs)][N] */);
+/* h_idx HOST [p] <- the sample pixels of the build call, ascending pixel indices: the list of glf_graph_build's own sampler call
+ * (glf_Sampling or glf_RandomSampling under the build's options), kept in the handle; p is glf_graph_info.p. GLF_ERR_INVALID for a NULL handle, and for a NULL h_idx with the reason
+ * in glf_ctx_last_error. */
+int glf_graph_samples(const glf_graph *g, unsigned *h_idx /* HOST [p], ascending pixel indices */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
