@@ -20,7 +20,7 @@ C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
 
 all: $(PKG)/libglf.so $(PKG)/image_processing oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/glf_internal.hpp $(CSRC)/phi_tile.hpp $(CSRC)/phi_compact.hpp $(CSRC)/nystroem_grid.inc $(CSRC)/nystroem_rank.inc $(CSRC)/nystroem_band.inc $(CSRC)/nystroem_band_vec.inc $(CSRC)/nystroem_band_sep.inc $(CSRC)/grid_common.inc $(CSRC)/affinity_grid.inc $(CSRC)/band_plan.hpp $(CSRC)/robust_loss.hpp include/glf.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/glf_internal.hpp $(CSRC)/phi_tile.hpp $(CSRC)/phi_compact.hpp $(CSRC)/nystroem_grid.inc $(CSRC)/nystroem_rank.inc $(CSRC)/nystroem_band.inc $(CSRC)/nystroem_band_vec.inc $(CSRC)/nystroem_band_sep.inc $(CSRC)/grid_common.inc $(CSRC)/affinity_grid.inc $(CSRC)/band_plan.hpp $(CSRC)/robust_loss.hpp $(CSRC)/filter_rule.hpp include/glf.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/host_util.o: $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp $(CSRC)/phi_compact.hpp $(CSRC)/robust_loss.hpp include/glf.h

@@ -580,6 +580,30 @@ struct SignalPlanes {
 __attribute__((visibility("hidden"))) int image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img,
                                                                int width, int height, uint8_t *d_out, float *d_zf, double *eigvals_out,
                                                                glf_stats *stats, glf_capture *cap, const SignalPlanes *sig);
+// What follows from the options and the image size before any device work; const once plan_run has built it. image_processing_run
+// is its checks, f32_admit, pool_age, plan_run and run_planned; glf_graph_build plans once itself, sizes Phi from the plan and keeps
+// the sample list.
+struct RunPlan {
+    glf_options opt; // defaulted; GLF_KERNEL_BILATERAL at a non-grey entry point replaced by the format's kernel
+    PixGen gen;
+    bool u8_guide;   // an 8-bit grey guide: the only one with an 8-bit y (the others' values are filtered as planes)
+    int64_t N;
+    unsigned p;
+    std::vector<unsigned> samples; // [p] pixel indices, ascending
+    unsigned m;
+    bool wide;       // more than 256 eigenpairs (the reference default m = p - 1): 256-column panels
+    unsigned ld, p32;
+    KernelCoef coef;
+    float gain, ysub; // of the filter z = (1 - ysub) y + gain Phi f(Pi) Phi^T y (filter_rule.hpp)
+};
+// the validation of the options and the sizing, with the whole path's statuses and messages
+__attribute__((visibility("hidden"))) int plan_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, int width, int height, bool has_capture,
+                                                   bool has_signals, RunPlan *plan);
+__attribute__((visibility("hidden"))) int run_planned(glf_ctx *ctx, const RunPlan &plan, const uint8_t *d_img, int width, int height,
+                                                      uint8_t *d_out, float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap,
+                                                      const SignalPlanes *sig);
+// the float formats admit finite values only: one pass over the image's floats before anything else (a no-op for the others)
+__attribute__((visibility("hidden"))) int f32_admit(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height);
 
 // Sample table: float4 {row, col, value, 0} per sample (float colour: and the value block behind the padded records) + mask + device idx.
 struct SampleTables {

@@ -3,6 +3,7 @@
 // capture target; Phi^T s and Phi^T Phi are filter.hip's phi_t_signals / phi_gram; the synthesis is the one new kernel.
 #include "phi_tile.hpp"
 #include "phi_compact.hpp"
+#include "filter_rule.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -170,41 +171,20 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
     if (graph) *graph = nullptr;
     if (!ctx || !graph || !d_img || width <= 0 || height <= 0) return GLF_ERR_INVALID;
     if (pix < GLF_PIX_U8 || pix > GLF_PIX_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: pixel format %d", pix);
-    glf_options opt;
-    glf_options_default(&opt);
-    if (opt_in) {
-        if (opt_in->struct_size != sizeof(glf_options))
-            return set_error(ctx, GLF_ERR_INVALID, "glf_options.struct_size %u != %zu", opt_in->struct_size, sizeof(glf_options));
-        opt = *opt_in;
-    }
     if (ctx->has_comm || ctx->native)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: the context carries a communicator (row-sharded graph handles are not supported)");
-    const int64_t N = (int64_t)width * height;
-    if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
-    // the sample count and the eigenpairs the capture call will realise: they size Phi. This restates image_processing_run's rules
-    // (pipeline.hip, "p = width*height*0.01 ..." and "GetNumberEigenvalues": keep the two in step); the call's own answer is checked
-    // against it below (S.m, cap.ld), and capture's phi_floats guard refuses a Phi that would not fit
-    unsigned p = opt.num_samples ? opt.num_samples : (unsigned)((double)N * opt.sample_frac);
-    // The list itself stays in the handle (glf_graph_samples). It is this sizing call's list, not a copy of the capture call's:
-    // image_processing_run below repeats the sampler call with the same (width, height, request, seed), and both samplers are pure
-    // functions of those (glf_Sampling is a grid rule, glf_RandomSampling draws from its own seeded generator, tests/test_abi.py),
-    // so the two lists are equal entry by entry. Only the count is cross-checked below (S.p): a sampler that read anything else --
-    // the image, a clock, a global generator -- would break this, and would have to hand its list out through glf_capture instead.
-    std::vector<unsigned> samples;
-    {
-        unsigned *h_idx = nullptr;
-        const int rc = opt.sampling == GLF_SAMPLING_RANDOM ? glf_RandomSampling(width, height, &p, &h_idx, opt.sampling_seed)
-                                                           : glf_Sampling(width, height, &p, &h_idx);
-        if (rc == GLF_OK && h_idx) samples.assign(h_idx, h_idx + p);
-        std::free(h_idx);
-        if (rc != GLF_OK || p < 2) return set_error(ctx, GLF_ERR_INVALID, "sampling failed (requested %u samples on %dx%d)", p, width, height);
-    }
-    unsigned m = opt.num_eigvals;
-    if (m == 0 || m >= p) m = p - 1;
-    if (m > PANEL_COLS)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: a graph handle takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
-    const unsigned ld = ld_for(m);
     const PixGen gen = pixgen_of_pix(pix);
+    GLF_ENTER(ctx);
+    GLF_TRY(f32_admit(ctx, gen, static_cast<const uint8_t *>(d_img), width, height)); // (before the options can refuse, as in every whole-path call)
+    pool_age(ctx);
+    // the plan of the run below sizes Phi; its sample list stays in the handle (glf_graph_samples). Planned as the plain call, so that
+    // more than 256 eigenpairs meet the handle's own refusal and not glf_capture's
+    RunPlan plan;
+    GLF_TRY(plan_run(ctx, opt_in, gen, width, height, false, false, &plan));
+    const int64_t N = plan.N;
+    const unsigned m = plan.m, ld = plan.ld;
+    if (plan.wide)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_graph_build: a graph handle takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
     glf_graph *g = new (std::nothrow) glf_graph;
     if (!g) return set_error(ctx, GLF_ERR_NOMEM, "glf_graph_build: host allocation");
     g->ctx = ctx;
@@ -227,11 +207,7 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
         cap.d_phi = g->phi;
         cap.phi_floats = (size_t)N * ld;
         if (rc == GLF_OK) // (no float z: the handle keeps Phi and the eigenvalues only)
-            rc = image_processing_run(ctx, &opt, gen, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap, nullptr);
-        if (rc == GLF_OK && (S.m != m || cap.ld != ld))
-            rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised m=%u ld=%u, %u / %u expected", S.m, cap.ld, m, ld);
-        if (rc == GLF_OK && S.p != samples.size())
-            rc = set_error(ctx, GLF_ERR_INVALID, "glf_graph_build: the call realised p=%u, %zu expected", S.p, samples.size());
+            rc = run_planned(ctx, plan, static_cast<const uint8_t *>(d_img), width, height, img_out.p, nullptr, g->lam.data(), &S, &cap, nullptr);
         if (rc == GLF_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = set_error(ctx, GLF_ERR_HIP, "glf_graph_build: synchronize");
     }
     if (rc != GLF_OK) {
@@ -239,10 +215,10 @@ int glf_graph_build(glf_ctx *ctx, const glf_options *opt_in, int pix, const void
         delete g;
         return rc;
     }
-    g->p = S.p;
+    g->p = plan.p;
     g->m = m;
     g->ld = ld;
-    g->samples = std::move(samples);
+    g->samples = std::move(plan.samples);
     if (stats) *stats = S;
     *graph = g;
     return GLF_OK;
@@ -371,42 +347,17 @@ int glf_filter_coeffs(const glf_options *opt_in, unsigned m, const double *lam, 
         if (opt_in->struct_size != sizeof(glf_options)) return GLF_ERR_INVALID;
         opt = *opt_in;
     }
-    switch (opt.filter_mode) {
-    case GLF_FILTER_REFERENCE: {
-        const double gain = (double)opt.gain, k = (double)(opt.filter_pow > 0 ? opt.filter_pow : 1);
-        for (unsigned j = 0; j < m; ++j) a[j] = gain * std::pow(lam[j], k) * c[j];
-        *ident = 1.f;
-        return GLF_OK;
-    }
-    case GLF_FILTER_POC:
-        for (unsigned j = 0; j < m; ++j) a[j] = -(lam[j] + 5.0) * c[j];
-        *ident = 1.f;
-        return GLF_OK;
-    case GLF_FILTER_SMOOTH:
-        for (unsigned j = 0; j < m; ++j) a[j] = (1.0 - lam[j]) * c[j];
-        *ident = 0.f;
-        return GLF_OK;
-    case GLF_FILTER_SHARPEN: {
+    if (opt.filter_mode < GLF_FILTER_REFERENCE || opt.filter_mode > GLF_FILTER_SHARPEN) return GLF_ERR_INVALID;
+    // the whole path's rule (filter_rule.hpp), the gain folded into the coefficients
+    if (opt.filter_mode == GLF_FILTER_SHARPEN) {
         if (!gram) return GLF_ERR_INVALID;
-        // (1 + beta) L G L c - beta L G L G L c, factor by factor as the whole path forms it
-        const double beta = (double)opt.filter_beta;
-        std::vector<double> t(m), u(m), v(m);
-        auto LG = [&](const std::vector<double> &x, std::vector<double> &y) {
-            for (unsigned i = 0; i < m; ++i) {
-                double s = 0.0;
-                for (unsigned j = 0; j < m; ++j) s += gram[(size_t)i * m + j] * x[j];
-                y[i] = (1.0 - lam[i]) * s;
-            }
-        };
-        for (unsigned j = 0; j < m; ++j) t[j] = (1.0 - lam[j]) * c[j];
-        LG(t, u);
-        LG(u, v);
-        for (unsigned j = 0; j < m; ++j) a[j] = (1.0 + beta) * u[j] - beta * v[j];
-        *ident = 0.f;
-        return GLF_OK;
+        sharpen_weights(m, lam, gram, m, (double)opt.filter_beta, c, a);
+    } else {
+        const double gain = (double)filter_gain(opt);
+        for (unsigned j = 0; j < m; ++j) a[j] = gain * filter_response(opt, lam[j]) * c[j];
     }
-    }
-    return GLF_ERR_INVALID;
+    *ident = filter_ident(opt);
+    return GLF_OK;
 }
 
 } // extern "C"

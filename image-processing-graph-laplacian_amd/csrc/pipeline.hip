@@ -1,6 +1,7 @@
 // pipeline.hip -- the C-ABI stage entry points (mirror of hpc/*.h) and the whole
 // approximate path glf_image_processing (hpc/image_processing.c:183-277).
 #include "glf_internal.hpp"
+#include "filter_rule.hpp"
 
 #include <cmath>
 #include <cstring>
@@ -96,6 +97,28 @@ static int sum_host(glf_ctx *ctx, const double *d_v, unsigned n, double *out)
     return GLF_OK;
 }
 
+int f32_admit(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height)
+{
+    if (!pix_desc(gen).is_float) return GLF_OK;
+    bool finite = true;
+    GLF_TRY(f32_all_finite(ctx, reinterpret_cast<const float *>(d_img), (int64_t)width * height * pix_desc(gen).channels, &finite));
+    if (!finite) return set_error(ctx, GLF_ERR_INVALID, "the %s image holds a NaN or an Inf: finite values only", pix_desc(gen).name);
+    return GLF_OK;
+}
+
+// The filter's weights from c = Phi^T y: fetches d_c ([k][ld] f64), forms k rows of ld f32 weights -- row(c_r, w_r) writes a row's
+// live entries, the rest stay zero -- and uploads them to d_w; h_c0 (optional) takes a copy of the first row of c. Both copies synchronise.
+template <class Row>
+static int weights_from_c(glf_ctx *ctx, const double *d_c, int k, unsigned ld, Row row, float *d_w, double *h_c0 = nullptr)
+{
+    std::vector<double> hc((size_t)k * ld);
+    GLF_TRY(glf_memcpy_d2h(ctx, hc.data(), d_c, sizeof(double) * hc.size()));
+    if (h_c0) std::memcpy(h_c0, hc.data(), sizeof(double) * ld);
+    std::vector<float> hw((size_t)k * ld, 0.f);
+    for (int r = 0; r < k; ++r) row(hc.data() + (size_t)r * ld, hw.data() + (size_t)r * ld);
+    return glf_memcpy_h2d(ctx, d_w, hw.data(), sizeof(float) * hw.size());
+}
+
 // OrthonormaliseVecs / NormaliseVecs for more than 256 vectors: row-major in, panels inside, row-major out
 static int orthonormalise_wide(glf_ctx *ctx, glf_mat *X, double *norms, bool normalise_only)
 {
@@ -171,15 +194,6 @@ int glf_image_processing_batch(glf_ctx *const *ctxs, int nctx, const glf_options
 
 // ------------------------------------------------------------------------------------------
 
-// the float formats admit finite values only: one pass over the image's floats (nch per pixel) before anything else
-static int f32_admit(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int width, int height)
-{
-    bool finite = true;
-    GLF_TRY(f32_all_finite(ctx, reinterpret_cast<const float *>(d_img), (int64_t)width * height * pix_desc(gen).channels, &finite));
-    if (!finite) return set_error(ctx, GLF_ERR_INVALID, "the %s image holds a NaN or an Inf: finite values only", pix_desc(gen).name);
-    return GLF_OK;
-}
-
 int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const uint8_t *d_img, int width, int height,
                                 unsigned sample_size, const unsigned *sample_indices, int kernel, float h_loc,
                                 float h_val)
@@ -189,7 +203,7 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
     if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3)) // (nlm.hip reflects an out-of-image patch index once: valid from 3 pixels on)
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     GLF_ENTER(ctx);
-    if (pix_desc(pixgen_of(kernel)).is_float) GLF_TRY(f32_admit(ctx, pixgen_of(kernel), d_img, width, height));
+    GLF_TRY(f32_admit(ctx, pixgen_of(kernel), d_img, width, height));
     const unsigned p = sample_size;
     SampleTables tb;
     GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel)); // (RGB: d_img is [height][width][3]; U16: uint16_t; F32: float; RGBF32: float [height][width][3])
@@ -484,11 +498,10 @@ int glf_ComputeResultFromLaplacian(glf_ctx *ctx, const uint8_t *d_img, const glf
             const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
             GLF_TRY(pack_panel(ctx, phi->data, ld, N, q, pan.p));
             GLF_TRY(phi_t_y(ctx, pan.p, d_img, 0, N, mq, PANEL_COLS, cq.p));
-            std::vector<double> hc(PANEL_COLS);
-            std::vector<float> hw(PANEL_COLS, 0.f);
-            GLF_TRY(glf_memcpy_d2h(ctx, hc.data(), cq.p, sizeof(double) * PANEL_COLS));
-            for (unsigned j = 0; j < mq; ++j) hw[j] = (float)((double)hp[q * PANEL_COLS + j] * hc[j]);
-            GLF_TRY(glf_memcpy_h2d(ctx, wq.p, hw.data(), sizeof(float) * PANEL_COLS));
+            const float *pq = hp.data() + q * PANEL_COLS;
+            GLF_TRY(weights_from_c(ctx, cq.p, 1, PANEL_COLS, [&](const double *hc, float *hw) {
+                for (unsigned j = 0; j < mq; ++j) hw[j] = (float)((double)pq[j] * hc[j]);
+            }, wq.p));
             GLF_TRY(filter_accumulate(ctx, pan.p, 0, N, PANEL_COLS, wq.p, acc.p, q == 0));
         }
         GLF_TRY(filter_finish(ctx, d_img, acc.p, 0, N, gain, 0.f, d_out, d_zf));
@@ -498,14 +511,13 @@ int glf_ComputeResultFromLaplacian(glf_ctx *ctx, const uint8_t *d_img, const glf
     DevBuf<double> c;
     GLF_TRY(c.alloc(ctx, ld));
     GLF_TRY(phi_t_y(ctx, phi->data, d_img, 0, N, m, ld, c.p)); // right = phi^T z, hpc/display.c:66
-    std::vector<double> hc(ld);
-    std::vector<float> hp(m), hw(ld, 0.f);
-    GLF_TRY(glf_memcpy_d2h(ctx, hc.data(), c.p, sizeof(double) * ld));
+    std::vector<float> hp(m);
     GLF_TRY(glf_memcpy_d2h(ctx, hp.data(), Pi->data, sizeof(float) * m));
-    for (unsigned j = 0; j < m; ++j) hw[j] = (float)((double)hp[j] * hc[j]); // left = phi Pi, :64
     DevBuf<float> w;
     GLF_TRY(w.alloc(ctx, ld));
-    GLF_TRY(glf_memcpy_h2d(ctx, w.p, hw.data(), sizeof(float) * ld));
+    GLF_TRY(weights_from_c(ctx, c.p, 1, ld, [&](const double *hc, float *hw) {
+        for (unsigned j = 0; j < m; ++j) hw[j] = (float)((double)hp[j] * hc[j]); // left = phi Pi, :64
+    }, w.p));
     GLF_TRY(apply_filter(ctx, d_img, phi->data, 0, N, m, ld, w.p, gain, 0.f, d_out, d_zf));
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return GLF_OK;
@@ -874,18 +886,14 @@ int glf_operator_destroy(glf_operator *op)
 
 } // extern "C"
 
-int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height, uint8_t *d_out,
-                              float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
+// ------------------------------------------------------------------------------------------
+// The whole-path driver: plan, affinity, Laplacian, eigenpairs, wide or narrow, fused or unfused, planes tail
+// ------------------------------------------------------------------------------------------
+
+int glf::plan_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, int width, int height, bool has_capture, bool has_signals, RunPlan *plan)
 {
-    // (all of these answer GLF_ERR_INVALID and leave last_error alone)
-    if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
-    if (sig && (sig->nsig < 1 || sig->nsig > GLF_MAX_SIGNALS || !sig->d_sig || !sig->d_out)) return GLF_ERR_INVALID;
-    if (cap && cap->struct_size != sizeof(glf_capture))
-        return set_error(ctx, GLF_ERR_INVALID, "glf_capture.struct_size %u != %zu", cap->struct_size, sizeof(glf_capture));
-    GLF_ENTER(ctx);
-    if (pix_desc(gen).is_float) GLF_TRY(f32_admit(ctx, gen, d_img, width, height)); // (before anything else)
-    pool_age(ctx);
-    glf_options opt;
+    RunPlan &P = *plan;
+    glf_options &opt = P.opt;
     glf_options_default(&opt);
     if (opt_in) {
         if (opt_in->struct_size != sizeof(glf_options))
@@ -895,10 +903,11 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
     // a kernel reads one pixel format: the colour and 16-bit entry points take their format's bilateral kernel only (for which
     // GLF_KERNEL_BILATERAL stands there), the 8-bit entry points no kernel of another format. The colour and 16-bit guides have no
     // 8-bit y: their values are filtered as planes (u8_guide false)
-    const bool u8_guide = gen == PixGen::Grey;
-    if (!u8_guide && opt.kernel == GLF_KERNEL_BILATERAL) opt.kernel = pix_desc(gen).kernel;
+    P.gen = gen;
+    P.u8_guide = gen == PixGen::Grey;
+    if (!P.u8_guide && opt.kernel == GLF_KERNEL_BILATERAL) opt.kernel = pix_desc(gen).kernel;
     if (pixgen_of(opt.kernel) != gen) {
-        if (!u8_guide) {
+        if (!P.u8_guide) {
             const char *what = pix_desc(gen).name;
             return set_error(ctx, GLF_ERR_UNSUPPORTED, "%s filtering: kernel %d (the %s bilateral kernel only)", what, opt.kernel, what);
         }
@@ -909,25 +918,214 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
     if (opt.kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
         return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
     if (opt.filter_mode < GLF_FILTER_REFERENCE || opt.filter_mode > GLF_FILTER_SHARPEN) return set_error(ctx, GLF_ERR_INVALID, "filter_mode %d", opt.filter_mode);
-    // f(Pi), the gain and the y term of the filter z = ysub' y + gain Phi f(Pi) Phi^T y:
-    //   reference: z = y + gain Phi Pi^k Phi^T y (MatPow is a no-op there, hpc/utils.c:721 => k = 1);
-    //   PoC: z = y - Phi diag(mu + 5) Phi^T y (python/image_processing.py:304-305);
-    //   smoothing / sharpening (:197-241): z = Phi f(s) Phi^T y with s = 1 - mu the eigenvalues of W = I - L, f(s) = s or
-    //   (1 + beta) s^2 - beta s^3 -- no y term: the kernels subtract it from the correction (filter_ysub).
-    const bool ref_filter = opt.filter_mode == GLF_FILTER_REFERENCE;
-    const float filter_gain = ref_filter ? opt.gain : 1.0f;
-    const float filter_ysub = opt.filter_mode >= GLF_FILTER_SMOOTH ? 1.0f : 0.0f;
-    auto filter_weight = [&](double lambda) {
-        const double s1 = 1.0 - lambda, beta = (double)opt.filter_beta;
-        switch (opt.filter_mode) {
-        case GLF_FILTER_POC: return -(lambda + 5.0);
-        case GLF_FILTER_SMOOTH: return s1;
-        case GLF_FILTER_SHARPEN: return (1.0 + beta) * s1 * s1 - beta * s1 * s1 * s1;
-        default: return std::pow(lambda, (double)(opt.filter_pow > 0 ? opt.filter_pow : 1));
-        }
-    };
-    const int64_t N = (int64_t)width * height;
-    if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
+    P.gain = filter_gain(opt);
+    P.ysub = 1.0f - filter_ident(opt);
+    P.N = (int64_t)width * height;
+    if (P.N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
+    // p = width*height*0.01 (truncating), hpc/image_processing.c:187; Sampling rewrites it, :191-193
+    P.p = opt.num_samples ? opt.num_samples : (unsigned)((double)P.N * opt.sample_frac);
+    {
+        unsigned *h_idx = nullptr;
+        const int rc = opt.sampling == GLF_SAMPLING_RANDOM ? glf_RandomSampling(width, height, &P.p, &h_idx, opt.sampling_seed)
+                                                           : glf_Sampling(width, height, &P.p, &h_idx);
+        if (rc == GLF_OK && h_idx) P.samples.assign(h_idx, h_idx + P.p);
+        std::free(h_idx);
+        if (rc != GLF_OK || P.p < 2) return set_error(ctx, GLF_ERR_INVALID, "sampling failed (requested %u samples on %dx%d)", P.p, width, height);
+    }
+    // GetNumberEigenvalues, hpc/image_processing.c:96-108
+    P.m = opt.num_eigvals;
+    if (P.m == 0 || P.m >= P.p) P.m = P.p - 1;
+    P.wide = P.m > PANEL_COLS;
+    if (P.wide && opt.filter_mode == GLF_FILTER_SHARPEN) // (its Gram matrix Phi^T Phi would couple the panels)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the sharpening filter takes at most %u eigenpairs (%u asked for)", PANEL_COLS, P.m);
+    if (P.wide && has_capture) return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_capture with more than 256 eigenpairs");
+    if (P.wide && (has_signals || !P.u8_guide)) // (a colour, 16-bit or float guide's own values are planes)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "signal planes with more than 256 eigenpairs (%u asked for)", P.m);
+    P.ld = P.wide ? PANEL_COLS : ld_for(P.m);
+    P.p32 = (unsigned)round_up(P.p, VEC_PAD);
+    P.coef = make_coef(opt.kernel, opt.h_loc, opt.h_val);
+    return GLF_OK;
+}
+
+// [*i0, *i1): the samples (ascending pixel indices) among the pixels [pix0, pix1) of this shard
+static void samples_among(const std::vector<unsigned> &idx, int64_t pix0, int64_t pix1, unsigned *i0, unsigned *i1)
+{
+    const unsigned p = (unsigned)idx.size();
+    unsigned i = 0;
+    while (i < p && (int64_t)idx[i] < pix0) ++i;
+    *i0 = i;
+    while (i < p && (int64_t)idx[i] < pix1) ++i;
+    *i1 = i;
+}
+
+// Closes the last stage (ev[5]) and re-times the stages from `first` on (ev[i] opens stage i) and the total; then *stats = S
+static int finish_stats(glf_ctx *ctx, glf_stats &S, int first, glf_stats *stats)
+{
+    float glf_stats::*const stage_ms[5] = {&glf_stats::ms_affinity, &glf_stats::ms_laplacian, &glf_stats::ms_eigen, &glf_stats::ms_nystroem,
+                                           &glf_stats::ms_filter};
+    GLF_HIP(ctx, hipEventRecord(ctx->ev[5], ctx->stream));
+    GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
+    for (int i = first; i < 5; ++i) GLF_HIP(ctx, hipEventElapsedTime(&(S.*stage_ms[i]), ctx->ev[i], ctx->ev[i + 1]));
+    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
+    if (stats) *stats = S;
+    return GLF_OK;
+}
+
+// More than 256 eigenpairs, from the eigenpairs on. Panels of 256 vectors: the eigen-solve once (eigen.hip "panels"), then Nystroem,
+// Phi^T y and the filter's correction one panel at a time -- only one [pixels][256] block of Phi exists at any moment.
+static int run_wide_panels(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
+                           const SampleTables &tb, OperatorStore &store, const MatShard &shard, const float *d_dinv, double alpha, uint8_t *d_out,
+                           float *d_zf, double *eigvals_out, glf_stats &S, glf_stats *stats)
+{
+    const glf_options &opt = P.opt;
+    const unsigned p = P.p, m = P.m;
+    hipStream_t st = ctx->stream;
+    const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS);
+    const size_t pstride = (size_t)P.p32 * PANEL_COLS;
+    DevBuf<float> vecs;
+    GLF_TRY(vecs.alloc(ctx, pstride * npan));
+    std::vector<double> lam(m);
+    GLF_TRY(inverse_power_iteration_panels(ctx, store.LA.p, store.lda, p, m, nullptr, opt.seed, opt.opti_gs, opt.epsilon, opt.inner_rtol,
+                                           opt.max_outer > 0 ? opt.max_outer : 100000, vecs.p, lam.data(), &S.eig, shard.grid ? &shard : nullptr,
+                                           d_dinv));
+    store.LA.release();
+    if (eigvals_out)
+        for (unsigned j = 0; j < m; ++j) eigvals_out[j] = lam[j];
+    GLF_HIP(ctx, hipEventRecord(ctx->ev[3], st));
+    const int64_t npix = pix1 - pix0;
+    DevBuf<float> psi, pinv, phi, w, acc;
+    DevBuf<double> c;
+    const size_t psi_n = (size_t)round_up(p, NYS_PAD) * PANEL_COLS;
+    GLF_TRY(psi.alloc(ctx, psi_n));
+    GLF_TRY(pinv.alloc(ctx, PANEL_COLS));
+    GLF_TRY(w.alloc(ctx, PANEL_COLS));
+    GLF_TRY(c.alloc(ctx, PANEL_COLS));
+    GLF_TRY(phi.alloc(ctx, (size_t)npix * PANEL_COLS));
+    GLF_TRY(acc.alloc(ctx, (size_t)npix));
+    float *phi_base = phi.p - (size_t)pix0 * PANEL_COLS;
+    unsigned si0, si1;
+    samples_among(P.samples, pix0, pix1, &si0, &si1);
+    float kms_total = 0.f;
+    for (unsigned q = 0; q < npan; ++q) {
+        const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
+        const float *vq = vecs.p + q * pstride;
+        const double *lamq = lam.data() + q * PANEL_COLS;
+        std::vector<float> hp(PANEL_COLS, 0.f);
+        for (unsigned j = 0; j < mq; ++j) hp[j] = (float)(1.0 / lamq[j]); // InverseDiagMat, hpc/utils.c:559-586
+        GLF_HIP(ctx, hipMemcpyAsync(pinv.p, hp.data(), sizeof(float) * PANEL_COLS, hipMemcpyHostToDevice, st));
+        GLF_HIP(ctx, hipStreamSynchronize(st));
+        GLF_HIP(ctx, hipMemsetAsync(psi.p, 0, sizeof(float) * psi_n, st));
+        hipLaunchKernelGGL(k_make_psi, dim3((unsigned)ceil_div((int64_t)p * PANEL_COLS, 256)), dim3(256), 0, st, vq, pinv.p, p, PANEL_COLS, mq,
+                           (float)(-alpha), psi.p);
+        GLF_LAUNCH_CHECK(ctx);
+        GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * PANEL_COLS, st));
+        float kms = 0.f;
+        uint64_t evaluated = 0;
+        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, P.coef, (float)(-alpha), psi.p, mq,
+                                  PANEL_COLS, phi_base, 1, c.p, &kms, opt.skip_exact_zeros, &evaluated, nullptr, &S.nystroem_path, nullptr));
+        kms_total += kms;
+        S.nystroem_evaluated += (double)evaluated;
+        if (si1 > si0)
+            GLF_TRY(scatter_sample_rows(ctx, vq + (size_t)si0 * PANEL_COLS, si1 - si0, PANEL_COLS, tb.idx.p + si0, phi_base, 1, d_img, c.p, mq));
+        GLF_TRY(allreduce_f64(ctx, c.p, PANEL_COLS)); // right = phi^T y over all ranks' pixels (this panel's columns)
+        GLF_TRY(weights_from_c(ctx, c.p, 1, PANEL_COLS, [&](const double *hc, float *hw) {
+            filter_weights_row(opt, mq, lamq, nullptr, 0, hc, hw);
+        }, w.p));
+        GLF_TRY(filter_accumulate(ctx, phi.p, pix0, pix1, PANEL_COLS, w.p, acc.p, q == 0));
+    }
+    GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
+    GLF_TRY(filter_finish(ctx, d_img, acc.p, pix0, pix1, P.gain, P.ysub, d_out, d_zf));
+    S.nystroem_launches = (int)npan;
+    S.nystroem_kernel_ms = kms_total;
+    S.contraction = ctx->contraction;
+    S.skip_exact_zeros = opt.skip_exact_zeros;
+    return finish_stats(ctx, S, 0, stats);
+}
+
+// The signal planes through the guide's operator, after the guide is complete: its outputs, stats and collectives are those of the
+// plain call. Phi is written for them on every path: the fused guide filter never writes it, so it is extended here with the guide's
+// own Psi and contraction (unfused: phi_base, the rows the guide's filter read, addressed by absolute pixel index). Every rank comes
+// here, so the collectives match. sig_w: the planes' weights where the band launch fell back after c_s was formed, null otherwise.
+static int filter_planes(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
+                         const SampleTables &tb, double alpha, const float *d_psi, const float *d_phiA, unsigned si0, unsigned si1,
+                         const std::vector<double> &lam, const std::vector<double> &hG, bool fused, float *phi_base, const SignalPlanes *sig,
+                         const SignalPlanes *planes, const float *sig_w, uint8_t *d_out, float *d_zf, glf_stats &S, glf_stats *stats)
+{
+    const unsigned p = P.p, m = P.m, ld = P.ld;
+    const int64_t N = P.N;
+    DevBuf<float> phis;
+    float *phi_rows = phi_base; // rows addressed by absolute pixel index
+    if (fused) {
+        GLF_TRY(phis.alloc(ctx, (size_t)(pix1 - pix0) * ld));
+        phi_rows = phis.p - (size_t)pix0 * ld;
+        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, P.coef, (float)(-alpha), d_psi, m, ld,
+                                  phi_rows, 1, nullptr, nullptr, P.opt.skip_exact_zeros));
+        if (si1 > si0) GLF_TRY(scatter_sample_rows(ctx, d_phiA + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
+    }
+    auto rule = [&](const double *hc, float *hw) { filter_weights_row(P.opt, m, lam.data(), hG.data(), ld, hc, hw); };
+    const int ns = sig->nsig;
+    if (planes) { // colour or 16-bit guide with planes: c for the channels and the planes in one pass over Phi, the outputs in one more
+        const int np = planes->nsig;
+        DevBuf<double> ca; // [ns + np][ld]: the guide's channels, then the planes
+        DevBuf<float> wa;
+        GLF_TRY(ca.alloc(ctx, (size_t)(ns + np) * ld));
+        GLF_TRY(wa.alloc(ctx, (size_t)(ns + np) * ld));
+        double *cg = ca.p, *cp = ca.p + (size_t)ns * ld;
+        GLF_TRY(phi_t_pix_signals(ctx, P.gen, phi_rows, d_img, planes->d_sig, N, np, pix0, pix1, ld, cg, cp));
+        GLF_TRY(allreduce_f64(ctx, cg, (size_t)ns * ld)); // the guide's collective, with the shape it has in the plain call
+        GLF_TRY(allreduce_f64(ctx, cp, (size_t)np * ld)); // the planes' in one of their own (a ring's summation order may follow the layout)
+        GLF_TRY(weights_from_c(ctx, ca.p, ns + np, ld, rule, wa.p));
+        GLF_TRY(apply_filter_pix_signals(ctx, P.gen, phi_rows, pix0, pix1, ld, np, wa.p, P.gain, P.ysub, d_img, d_out, d_zf, planes->d_sig,
+                                         planes->d_out, N));
+        return finish_stats(ctx, S, 4, stats);
+    }
+    if (sig_w) { // (its weights stand, c_s's collective is not repeated)
+        GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w, P.gain, P.ysub, sig->d_sig, sig->d_out, N));
+        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return GLF_OK;
+    }
+    DevBuf<double> cs;
+    DevBuf<float> ws;
+    GLF_TRY(cs.alloc(ctx, (size_t)ns * ld));
+    GLF_TRY(ws.alloc(ctx, (size_t)ns * ld));
+    GLF_TRY(phi_t_signals(ctx, phi_rows, sig->d_sig, N, ns, pix0, pix1, ld, cs.p));
+    GLF_TRY(allreduce_f64(ctx, cs.p, (size_t)ns * ld)); // c_k = Phi^T s_k over all ranks' pixels (a collective of its own)
+    GLF_TRY(weights_from_c(ctx, cs.p, ns, ld, rule, ws.p));
+    if (!P.u8_guide) { // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
+        GLF_TRY(apply_filter_pix(ctx, P.gen, phi_rows, pix0, pix1, ld, ws.p, P.gain, P.ysub, d_img, d_out, d_zf, N));
+        return finish_stats(ctx, S, 4, stats);
+    }
+    GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, P.gain, P.ysub, sig->d_sig, sig->d_out, N));
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return GLF_OK;
+}
+
+int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen gen, const uint8_t *d_img, int width, int height, uint8_t *d_out,
+                              float *d_zf, double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
+{
+    // (all of these answer GLF_ERR_INVALID and leave last_error alone)
+    if (!ctx || !d_img || !d_out || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    if (sig && (sig->nsig < 1 || sig->nsig > GLF_MAX_SIGNALS || !sig->d_sig || !sig->d_out)) return GLF_ERR_INVALID;
+    if (cap && cap->struct_size != sizeof(glf_capture))
+        return set_error(ctx, GLF_ERR_INVALID, "glf_capture.struct_size %u != %zu", cap->struct_size, sizeof(glf_capture));
+    GLF_ENTER(ctx);
+    GLF_TRY(f32_admit(ctx, gen, d_img, width, height)); // (before anything else)
+    pool_age(ctx);
+    RunPlan plan;
+    GLF_TRY(plan_run(ctx, opt_in, gen, width, height, cap != nullptr, sig != nullptr, &plan));
+    return run_planned(ctx, plan, d_img, width, height, d_out, d_zf, eigvals_out, stats, cap, sig);
+}
+
+int glf::run_planned(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int width, int height, uint8_t *d_out, float *d_zf,
+                     double *eigvals_out, glf_stats *stats, glf_capture *cap, const SignalPlanes *sig)
+{
+    const glf_options &opt = P.opt;
+    const PixGen gen = P.gen;
+    const bool u8_guide = P.u8_guide;
+    const int64_t N = P.N;
+    const unsigned p = P.p, m = P.m, ld = P.ld, p32 = P.p32;
+    const unsigned *h_idx = P.samples.data();
+    const KernelCoef coef = P.coef;
     hipStream_t st = ctx->stream;
     glf_stats S{};
     DevBuf<float> guide_planes; // colour: the channels as float planes [3][N] (Phi^T x_c); 16-bit: the image as one plane
@@ -943,33 +1141,6 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
         guide_sig = SignalPlanes{nch, guide_planes.p, nullptr};
         sig = &guide_sig;
     }
-
-    // p = width*height*0.01 (truncating), hpc/image_processing.c:187; Sampling rewrites it, :191-193
-    unsigned p = opt.num_samples ? opt.num_samples : (unsigned)((double)N * opt.sample_frac);
-    unsigned *h_idx = nullptr;
-    {
-        int rc = opt.sampling == GLF_SAMPLING_RANDOM ? glf_RandomSampling(width, height, &p, &h_idx, opt.sampling_seed)
-                                                       : glf_Sampling(width, height, &p, &h_idx);
-        if (rc != GLF_OK || p < 2) {
-            std::free(h_idx);
-            return set_error(ctx, GLF_ERR_INVALID, "sampling failed (requested %u samples on %dx%d)", p, width, height);
-        }
-    }
-    struct FreeIdx {
-        unsigned *q;
-        ~FreeIdx() { std::free(q); }
-    } free_idx{h_idx};
-    // GetNumberEigenvalues, hpc/image_processing.c:96-108
-    unsigned m = opt.num_eigvals;
-    if (m == 0 || m >= p) m = p - 1;
-    const bool wide = m > PANEL_COLS; // more than 256 eigenpairs (the reference default m = p - 1): 256-column panels, see below
-    if (wide && opt.filter_mode == GLF_FILTER_SHARPEN) // (its Gram matrix Phi^T Phi would couple the panels)
-        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the sharpening filter takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
-    if (wide && cap) return set_error(ctx, GLF_ERR_UNSUPPORTED, "glf_capture with more than 256 eigenpairs");
-    if (wide && sig) return set_error(ctx, GLF_ERR_UNSUPPORTED, "signal planes with more than 256 eigenpairs (%u asked for)", m);
-    const unsigned ld = wide ? PANEL_COLS : ld_for(m);
-    const unsigned p32 = (unsigned)round_up(p, VEC_PAD);
-    const KernelCoef coef = make_coef(opt.kernel, opt.h_loc, opt.h_val);
     int row0, row1;
     shard_rows(ctx, height, &row0, &row1);
     const int64_t pix0 = (int64_t)row0 * width, pix1 = (int64_t)row1 * width;
@@ -1008,7 +1179,7 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
     // L_A[:, r0:r1) (= its row block transposed; L_A is symmetric) and computes rows [r0,r1) of every
     // mat-vec. Otherwise (single GPU, f32 contraction, or no allgather callback) L_A is whole.
     MatShard shard;
-    bool shard_eig = ctx->has_comm && ctx->comm.allgather_f32 && ctx->contraction == GLF_CONTRACT_F16_SPLIT && !wide;
+    bool shard_eig = ctx->has_comm && ctx->comm.allgather_f32 && ctx->contraction == GLF_CONTRACT_F16_SPLIT && !P.wide;
     // For a tensor-grid sample set L_A is applied in grid-factored form and never stored (GLF_MV_PATH = grid | dense | auto;
     // auto: from 16 384 samples on -- below, streaming a small stored L_A is cheaper than the factored sweep's fixed cost)
     struct GridOpGuard {
@@ -1040,98 +1211,15 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipEventRecord(ctx->ev[2], st));
     // ---- eigenpairs --------------------------------------------------------------------------
-    if (wide) {
-        // Panels of 256 vectors: the eigen-solve once (eigen.hip "panels"), then Nystroem, Phi^T y and the filter's correction
-        // one panel at a time -- only one [pixels][256] block of Phi exists at any moment.
-        const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS);
-        const size_t pstride = (size_t)p32 * PANEL_COLS;
-        DevBuf<float> vecs;
-        GLF_TRY(vecs.alloc(ctx, pstride * npan));
-        std::vector<double> lamw(m);
-        int rcw = inverse_power_iteration_panels(ctx, LA.p, lda, p, m, nullptr, opt.seed, opt.opti_gs, opt.epsilon, opt.inner_rtol,
-                                                 opt.max_outer > 0 ? opt.max_outer : 100000, vecs.p, lamw.data(), &S.eig,
-                                                 shard.grid ? &shard : nullptr, dinv.p);
-        if (rcw != GLF_OK) return rcw;
-        LA.release();
-        if (eigvals_out)
-            for (unsigned j = 0; j < m; ++j) eigvals_out[j] = lamw[j];
-        GLF_HIP(ctx, hipEventRecord(ctx->ev[3], st));
-        const int64_t npixw = pix1 - pix0;
-        DevBuf<float> psiw, pinvw, phiw, ww, acc;
-        DevBuf<double> cw;
-        const size_t psi_n = (size_t)round_up(p, NYS_PAD) * PANEL_COLS;
-        GLF_TRY(psiw.alloc(ctx, psi_n));
-        GLF_TRY(pinvw.alloc(ctx, PANEL_COLS));
-        GLF_TRY(ww.alloc(ctx, PANEL_COLS));
-        GLF_TRY(cw.alloc(ctx, PANEL_COLS));
-        GLF_TRY(phiw.alloc(ctx, (size_t)npixw * PANEL_COLS));
-        GLF_TRY(acc.alloc(ctx, (size_t)npixw));
-        float *phi_basew = phiw.p - (size_t)pix0 * PANEL_COLS;
-        float kms_total = 0.f;
-        for (unsigned q = 0; q < npan; ++q) {
-            const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
-            const float *vq = vecs.p + q * pstride;
-            std::vector<float> hp(PANEL_COLS, 0.f);
-            for (unsigned j = 0; j < mq; ++j) hp[j] = (float)(1.0 / lamw[q * PANEL_COLS + j]); // InverseDiagMat, hpc/utils.c:559-586
-            GLF_HIP(ctx, hipMemcpyAsync(pinvw.p, hp.data(), sizeof(float) * PANEL_COLS, hipMemcpyHostToDevice, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-            GLF_HIP(ctx, hipMemsetAsync(psiw.p, 0, sizeof(float) * psi_n, st));
-            hipLaunchKernelGGL(k_make_psi, dim3((unsigned)ceil_div((int64_t)p * PANEL_COLS, 256)), dim3(256), 0, st, vq, pinvw.p, p, PANEL_COLS, mq,
-                               (float)(-alpha), psiw.p);
-            GLF_LAUNCH_CHECK(ctx);
-            GLF_HIP(ctx, hipMemsetAsync(cw.p, 0, sizeof(double) * PANEL_COLS, st));
-            float kms = 0.f;
-            uint64_t evaluated = 0;
-            GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha), psiw.p,
-                                      mq, PANEL_COLS, phi_basew, 1, cw.p, &kms, opt.skip_exact_zeros, &evaluated, nullptr, &S.nystroem_path, nullptr));
-            kms_total += kms;
-            S.nystroem_evaluated += (double)evaluated;
-            {
-                unsigned i0 = 0, i1 = 0;
-                while (i0 < p && (int64_t)h_idx[i0] < pix0) ++i0;
-                i1 = i0;
-                while (i1 < p && (int64_t)h_idx[i1] < pix1) ++i1;
-                if (i1 > i0)
-                    GLF_TRY(scatter_sample_rows(ctx, vq + (size_t)i0 * PANEL_COLS, i1 - i0, PANEL_COLS, tb.idx.p + i0, phi_basew, 1, d_img, cw.p, mq));
-            }
-            GLF_TRY(allreduce_f64(ctx, cw.p, PANEL_COLS)); // right = phi^T y over all ranks' pixels (this panel's columns)
-            std::vector<double> hc(PANEL_COLS);
-            GLF_HIP(ctx, hipMemcpyAsync(hc.data(), cw.p, sizeof(double) * PANEL_COLS, hipMemcpyDeviceToHost, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-            std::vector<float> hw(PANEL_COLS, 0.f);
-            for (unsigned j = 0; j < mq; ++j)
-                hw[j] = (float)(filter_weight(lamw[q * PANEL_COLS + j]) * hc[j]);
-            GLF_HIP(ctx, hipMemcpyAsync(ww.p, hw.data(), sizeof(float) * PANEL_COLS, hipMemcpyHostToDevice, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-            GLF_TRY(filter_accumulate(ctx, phiw.p, pix0, pix1, PANEL_COLS, ww.p, acc.p, q == 0));
-        }
-        GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
-        GLF_TRY(filter_finish(ctx, d_img, acc.p, pix0, pix1, filter_gain, filter_ysub, d_out, d_zf));
-        GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
-        GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
-        S.nystroem_launches = (int)npan;
-        S.nystroem_kernel_ms = kms_total;
-        S.contraction = ctx->contraction;
-        S.skip_exact_zeros = opt.skip_exact_zeros;
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_affinity, ctx->ev[0], ctx->ev[1]));
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_laplacian, ctx->ev[1], ctx->ev[2]));
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_eigen, ctx->ev[2], ctx->ev[3]));
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_nystroem, ctx->ev[3], ctx->ev[4]));
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
-        GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-        if (stats) *stats = S;
-        return GLF_OK;
-    }
+    if (P.wide) return run_wide_panels(ctx, P, d_img, width, height, pix0, pix1, tb, store, shard, dinv.p, alpha, d_out, d_zf, eigvals_out, S, stats);
     DevBuf<float> phiA;
     GLF_TRY(phiA.alloc(ctx, (size_t)p32 * ld));
     std::vector<double> lam(m);
     {
         const float *d_x0 = nullptr; // seeded start block (hpc/inverse_power_it.c:12-47), cached per (p, m, ld, seed)
         GLF_TRY(start_block_cached(ctx, p, m, ld, opt.seed, &d_x0));
-        int rc = inverse_power_iteration(ctx, LA.p, lda, p, m, ld, nullptr, opt.opti_gs, opt.epsilon, opt.inner_rtol,
-                                         opt.max_outer > 0 ? opt.max_outer : 100000, phiA.p, lam.data(), &S.eig,
-                                         shard_arg(shard), dinv.p, d_x0);
-        if (rc != GLF_OK) return rc;
+        GLF_TRY(inverse_power_iteration(ctx, LA.p, lda, p, m, ld, nullptr, opt.opti_gs, opt.epsilon, opt.inner_rtol,
+                                        opt.max_outer > 0 ? opt.max_outer : 100000, phiA.p, lam.data(), &S.eig, shard_arg(shard), dinv.p, d_x0));
     }
     if (shard_eig || gop.op) LA.release(); // (a whole stored L_A is used once more below: K_A y_A for the fused filter)
     if (cap && cap->d_phi_A) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi_A, phiA.p, sizeof(float) * (size_t)p32 * ld, hipMemcpyDeviceToDevice, st));
@@ -1173,10 +1261,11 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
         S.skip_exact_zeros = opt.skip_exact_zeros;
         S.nystroem_evaluated = (double)evaluated; // kernel entries generated (listed chunks x 64 x workgroup pixels)
     };
-    unsigned si0 = 0, si1 = 0; // the samples among this shard's pixels
-    while (si0 < p && (int64_t)h_idx[si0] < pix0) ++si0;
-    si1 = si0;
-    while (si1 < p && (int64_t)h_idx[si1] < pix1) ++si1;
+    unsigned si0, si1;
+    samples_among(P.samples, pix0, pix1, &si0, &si1);
+    // the filter's weights from c = Phi^T y (sharpening: with hG = Phi^T Phi, f64 [ld][ld] over all ranks' pixels, filled on the unfused path)
+    std::vector<double> hG;
+    auto rule = [&](const double *hc, float *hw) { filter_weights_row(opt, m, lam.data(), hG.data(), ld, hc, hw); };
     // ---- band form with the filter in the kernel's epilogue: Phi is never written -----------------------------------------
     // c = Phi^T y is needed before the extension then: it follows from the degree stage's value-weighted sums (c_from_ysum).
     // ---- joint filtering on the band form: the planes ride in k_band's epilogue, Phi is never written for them either --------
@@ -1218,6 +1307,7 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
         GLF_TRY(ts.alloc(ctx, (size_t)p32 * 32));
         GLF_TRY(zdeg.alloc(ctx, p));
         GLF_TRY(cs.alloc(ctx, (size_t)nsig * ld));
+        GLF_TRY(sig_w.alloc(ctx, (size_t)nsig * ld));
         GLF_HIP(ctx, hipMemsetAsync(xs.p, 0, sizeof(float) * (size_t)p32 * 32, st));
         GLF_HIP(ctx, hipMemsetAsync(ts.p, 0, sizeof(float) * (size_t)p32 * 32, st));
         GLF_HIP(ctx, hipMemsetAsync(zdeg.p, 0, sizeof(double) * p, st));
@@ -1226,15 +1316,7 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
         GLF_TRY(grid_op_apply(ctx, gop.op, xs.p, ts.p, 32, -1.0, zdeg.p, 0, p, 0)); // K_A s_A for every plane's column
         for (int k = 0; k < nsig; ++k)
             GLF_TRY(c_from_ysum(ctx, psi.p, phiA.p, us.p + (size_t)k * p, ts.p + k, 32, tb.samples.p, p, ld, cs.p + (size_t)k * ld, xs.p + k));
-        std::vector<double> hcs((size_t)nsig * ld);
-        GLF_HIP(ctx, hipMemcpyAsync(hcs.data(), cs.p, sizeof(double) * nsig * ld, hipMemcpyDeviceToHost, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-        std::vector<float> hws((size_t)nsig * ld, 0.f);
-        for (int k = 0; k < nsig; ++k)
-            for (unsigned j = 0; j < m; ++j) hws[(size_t)k * ld + j] = (float)(filter_weight(lam[j]) * hcs[(size_t)k * ld + j]);
-        GLF_TRY(sig_w.alloc(ctx, (size_t)nsig * ld));
-        GLF_HIP(ctx, hipMemcpyAsync(sig_w.p, hws.data(), sizeof(float) * nsig * ld, hipMemcpyHostToDevice, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
+        GLF_TRY(weights_from_c(ctx, cs.p, nsig, ld, rule, sig_w.p));
     }
     bool fused = false;
     if (have_ysum && (gop.op || LA.p) && ld <= 64 && opt.filter_mode != GLF_FILTER_SHARPEN && !(cap && cap->d_phi) &&
@@ -1257,29 +1339,22 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
             GLF_LAUNCH_CHECK(ctx);
         }
         GLF_TRY(c_from_ysum(ctx, psi.p, phiA.p, deg.p + p, t.p, 32, tb.samples.p, p, ld, c.p));
-        std::vector<double> hc(ld);
-        GLF_HIP(ctx, hipMemcpyAsync(hc.data(), c.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-        if (cap && cap->h_c) std::memcpy(cap->h_c, hc.data(), sizeof(double) * ld);
-        std::vector<float> hw(ld, 0.f);
-        for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
-        GLF_HIP(ctx, hipMemcpyAsync(w.p, hw.data(), sizeof(float) * ld, hipMemcpyHostToDevice, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
+        GLF_TRY(weights_from_c(ctx, c.p, 1, ld, rule, w.p, cap ? cap->h_c : nullptr));
         BandFilter flt;
         flt.w = w.p;
-        flt.gain = filter_gain;
-        flt.ysub = filter_ysub;
+        flt.gain = P.gain;
+        flt.ysub = P.ysub;
         flt.out = d_out;
         flt.zf = d_zf;
         flt.corr = cap ? cap->d_corr : nullptr;
         if (sig_fused) {
             flt.sig = BandSignals{nsig, sig_w.p, sig->d_sig, sig->d_out, (int64_t)N};
-            GLF_TRY(filter_sample_rows_signals(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, nsig, sig_w.p, filter_gain, filter_ysub,
+            GLF_TRY(filter_sample_rows_signals(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, nsig, sig_w.p, P.gain, P.ysub,
                                                sig->d_sig, sig->d_out, N));
         }
         // the sample pixels from their rows of Phi_A first (k_band leaves them alone: the host work between the two launches --
         // grid detection, cached tables -- then overlaps a kernel instead of following the long one)
-        GLF_TRY(filter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, d_img, w.p, filter_gain, filter_ysub, d_out, d_zf,
+        GLF_TRY(filter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, d_img, w.p, P.gain, P.ysub, d_out, d_zf,
                                    cap ? cap->d_corr : nullptr, pix0));
         const int rc = nystroem_band_filter(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, psi.p, ld, flt, &kms,
                                             &evaluated, &S.nystroem_mfma_flops, &S.nystroem_path, &rps, h_idx);
@@ -1292,163 +1367,41 @@ int glf::image_processing_run(glf_ctx *ctx, const glf_options *opt_in, PixGen ge
         } else if (rc != GLF_ERR_UNSUPPORTED) return rc;
     }
     LA.release();
-    // sharpening: (1 + beta) W^2 y - beta W^3 y with W = Phi L Phi^T applied factor by factor as the PoC does
-    // (python/image_processing.py:231-235): the extended eigenvectors are not orthonormal, so G = Phi^T Phi sits
-    // between the factors -- z = Phi w, w = (1 + beta) L G L c - beta L G L G L c, L = 1 - mu, c = Phi^T y
-    std::vector<double> hG; // G (f64 [ld][ld], all ranks' pixels): filled on the unfused path for the sharpening filter
-    auto sharpen_weights = [&](const double *hc, float *hw) {
-        std::vector<double> t(m), u(m), v(m);
-        const double beta = (double)opt.filter_beta;
-        auto LG = [&](const std::vector<double> &x, std::vector<double> &y) { // y = L (G x)
-            for (unsigned i = 0; i < m; ++i) {
-                double a = 0.0;
-                for (unsigned j = 0; j < m; ++j) a += hG[(size_t)i * ld + j] * x[j];
-                y[i] = (1.0 - lam[i]) * a;
-            }
-        };
-        for (unsigned j = 0; j < m; ++j) t[j] = (1.0 - lam[j]) * hc[j];
-        LG(t, u);
-        LG(u, v);
-        for (unsigned j = 0; j < m; ++j) hw[j] = (float)((1.0 + beta) * u[j] - beta * v[j]);
-    };
+    float *phi_base = nullptr; // unfused: Phi's rows addressed by absolute pixel index
     if (!fused) {
-    GLF_TRY(phi.alloc(ctx, (size_t)npix * ld));
-    float *phi_base = phi.p - (size_t)pix0 * ld; // rows addressed by absolute pixel index
-    GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * ld, st));
-    GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha),
-                              psi.p, m, ld, phi_base, 1, u8_guide ? c.p : nullptr, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
-                              &S.nystroem_path, &rps));
-    nystroem_stats();
-    // sample rows of this shard <- Phi_A, and their share of c
-    if (si1 > si0)
-        GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, u8_guide ? c.p : nullptr, m));
-    if (u8_guide) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
-    GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
-    // ---- filter ------------------------------------------------------------------------------
-    auto gram_to_host = [&]() -> int { // hG = Phi^T Phi over all ranks' pixels (the sharpening weights)
-        DevBuf<double> G;
-        GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
-        GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
-        GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
-        hG.resize((size_t)ld * ld);
-        GLF_HIP(ctx, hipMemcpyAsync(hG.data(), G.p, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-        return GLF_OK;
-    };
-    if (!u8_guide) { // (no 8-bit y: the channels / the 16-bit image are filtered below, as planes; the sharpening weights need G)
-        if (S.nystroem_path != 4) S.contraction = GLF_CONTRACT_F32_MFMA; // (those formats' entry-by-entry kernel; their band form (PIX_BAND) is split f16)
+        GLF_TRY(phi.alloc(ctx, (size_t)npix * ld));
+        phi_base = phi.p - (size_t)pix0 * ld;
+        GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * ld, st));
+        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha), psi.p, m, ld,
+                                  phi_base, 1, u8_guide ? c.p : nullptr, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
+                                  &S.nystroem_path, &rps));
+        nystroem_stats();
+        // sample rows of this shard <- Phi_A, and their share of c
+        if (si1 > si0)
+            GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_base, 1, d_img, u8_guide ? c.p : nullptr, m));
+        if (u8_guide) GLF_TRY(allreduce_f64(ctx, c.p, ld)); // right = phi^T y over all ranks' pixels
+        GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
+        // ---- filter ------------------------------------------------------------------------------
+        // (no 8-bit y: the channels / the 16-bit image are filtered in the planes tail; those formats' entry-by-entry kernel is f32, their
+        // band form (PIX_BAND) split f16)
+        if (!u8_guide && S.nystroem_path != 4) S.contraction = GLF_CONTRACT_F32_MFMA;
+        if (opt.filter_mode == GLF_FILTER_SHARPEN) { // hG = Phi^T Phi over all ranks' pixels (the sharpening weights, here and in the tail)
+            DevBuf<double> G;
+            GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
+            GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
+            GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
+            hG.resize((size_t)ld * ld);
+            GLF_TRY(glf_memcpy_d2h(ctx, hG.data(), G.p, sizeof(double) * ld * ld));
+        }
+        if (u8_guide) GLF_TRY(weights_from_c(ctx, c.p, 1, ld, rule, w.p, cap ? cap->h_c : nullptr));
         if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
-        if (opt.filter_mode == GLF_FILTER_SHARPEN) GLF_TRY(gram_to_host());
-    } else {
-    {
-        std::vector<double> hc(ld);
-        GLF_HIP(ctx, hipMemcpyAsync(hc.data(), c.p, sizeof(double) * ld, hipMemcpyDeviceToHost, st));
-        if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-        if (cap && cap->h_c) std::memcpy(cap->h_c, hc.data(), sizeof(double) * ld);
-        std::vector<float> hw(ld, 0.f);
-        for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
-        if (opt.filter_mode == GLF_FILTER_SHARPEN) {
-            GLF_TRY(gram_to_host());
-            sharpen_weights(hc.data(), hw.data());
-        }
-        GLF_HIP(ctx, hipMemcpyAsync(w.p, hw.data(), sizeof(float) * ld, hipMemcpyHostToDevice, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
+        if (u8_guide)
+            GLF_TRY(apply_filter(ctx, d_img, phi_base, pix0, pix1, m, ld, w.p, P.gain, P.ysub, d_out, d_zf, cap ? cap->d_corr : nullptr));
     }
-    GLF_TRY(apply_filter(ctx, d_img, phi_base, pix0, pix1, m, ld, w.p, filter_gain, filter_ysub, d_out, d_zf, cap ? cap->d_corr : nullptr));
-    } // (u8_guide)
-    } // (!fused)
-    GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
-    GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_affinity, ctx->ev[0], ctx->ev[1]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_laplacian, ctx->ev[1], ctx->ev[2]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_eigen, ctx->ev[2], ctx->ev[3]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_nystroem, ctx->ev[3], ctx->ev[4]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
-    GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-    if (stats && u8_guide) *stats = S;
-    // ---- signal planes through the guide's operator (after the guide is complete: its outputs, stats and collectives are
-    // those of the plain call). Phi is written for them on every path: the fused guide filter never writes it, so it is
-    // extended here with the guide's own Psi and contraction. Every rank takes this branch, so the collectives match.
-    if (sig && !sig_done) {
-        DevBuf<float> phis;
-        float *phi_rows = nullptr; // rows addressed by absolute pixel index
-        if (!fused) phi_rows = phi.p - (size_t)pix0 * ld;
-        else {
-            GLF_TRY(phis.alloc(ctx, (size_t)npix * ld));
-            phi_rows = phis.p - (size_t)pix0 * ld;
-            GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha),
-                                      psi.p, m, ld, phi_rows, 1, nullptr, nullptr, opt.skip_exact_zeros));
-            if (si1 > si0)
-                GLF_TRY(scatter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
-        }
-        const int ns = sig->nsig;
-        if (planes) { // colour or 16-bit guide with planes: c for the channels and the planes in one pass over Phi, the outputs in one more
-            const int np = planes->nsig;
-            DevBuf<double> cg, cp;
-            DevBuf<float> wa;
-            GLF_TRY(cg.alloc(ctx, (size_t)ns * ld));
-            GLF_TRY(cp.alloc(ctx, (size_t)np * ld));
-            GLF_TRY(wa.alloc(ctx, (size_t)(ns + np) * ld));
-            GLF_TRY(phi_t_pix_signals(ctx, gen, phi_rows, d_img, planes->d_sig, N, np, pix0, pix1, ld, cg.p, cp.p));
-            GLF_TRY(allreduce_f64(ctx, cg.p, (size_t)ns * ld)); // the guide's collective, with the shape it has in the plain call
-            GLF_TRY(allreduce_f64(ctx, cp.p, (size_t)np * ld)); // the planes' in one of their own (a ring's summation order may follow the layout)
-            std::vector<double> hca((size_t)(ns + np) * ld);
-            GLF_HIP(ctx, hipMemcpyAsync(hca.data(), cg.p, sizeof(double) * ns * ld, hipMemcpyDeviceToHost, st));
-            GLF_HIP(ctx, hipMemcpyAsync(hca.data() + (size_t)ns * ld, cp.p, sizeof(double) * np * ld, hipMemcpyDeviceToHost, st));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-            std::vector<float> hwa((size_t)(ns + np) * ld, 0.f);
-            for (int k = 0; k < ns + np; ++k) {
-                const double *hc = hca.data() + (size_t)k * ld;
-                float *hw = hwa.data() + (size_t)k * ld;
-                if (opt.filter_mode == GLF_FILTER_SHARPEN) sharpen_weights(hc, hw);
-                else
-                    for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
-            }
-            GLF_HIP(ctx, hipMemcpyAsync(wa.p, hwa.data(), sizeof(float) * (ns + np) * ld, hipMemcpyHostToDevice, st));
-            GLF_TRY(apply_filter_pix_signals(ctx, gen, phi_rows, pix0, pix1, ld, np, wa.p, filter_gain, filter_ysub, d_img, d_out, d_zf,
-                                             planes->d_sig, planes->d_out, N));
-            GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
-            GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
-            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
-            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-            if (stats) *stats = S;
-            return GLF_OK;
-        }
-        if (sig_fused) { // (the band launch fell back after c_s was formed: its weights stand, c_s's collective is not repeated)
-            GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
-            GLF_HIP(ctx, hipStreamSynchronize(st));
-            return GLF_OK;
-        }
-        DevBuf<double> cs;
-        DevBuf<float> ws;
-        GLF_TRY(cs.alloc(ctx, (size_t)ns * ld));
-        GLF_TRY(ws.alloc(ctx, (size_t)ns * ld));
-        GLF_TRY(phi_t_signals(ctx, phi_rows, sig->d_sig, N, ns, pix0, pix1, ld, cs.p));
-        GLF_TRY(allreduce_f64(ctx, cs.p, (size_t)ns * ld)); // c_k = Phi^T s_k over all ranks' pixels (a collective of its own)
-        std::vector<double> hcs((size_t)ns * ld);
-        GLF_HIP(ctx, hipMemcpyAsync(hcs.data(), cs.p, sizeof(double) * ns * ld, hipMemcpyDeviceToHost, st));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-        std::vector<float> hws((size_t)ns * ld, 0.f);
-        for (int k = 0; k < ns; ++k) {
-            const double *hc = hcs.data() + (size_t)k * ld;
-            float *hw = hws.data() + (size_t)k * ld;
-            if (opt.filter_mode == GLF_FILTER_SHARPEN) sharpen_weights(hc, hw);
-            else
-                for (unsigned j = 0; j < m; ++j) hw[j] = (float)(filter_weight(lam[j]) * hc[j]);
-        }
-        GLF_HIP(ctx, hipMemcpyAsync(ws.p, hws.data(), sizeof(float) * ns * ld, hipMemcpyHostToDevice, st));
-        if (!u8_guide) { // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
-            GLF_TRY(apply_filter_pix(ctx, gen, phi_rows, pix0, pix1, ld, ws.p, filter_gain, filter_ysub, d_img, d_out, d_zf, N));
-            GLF_HIP(ctx, hipEventRecord(ctx->ev[5], st));
-            GLF_HIP(ctx, hipEventSynchronize(ctx->ev[5]));
-            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_filter, ctx->ev[4], ctx->ev[5]));
-            GLF_HIP(ctx, hipEventElapsedTime(&S.ms_total, ctx->ev[0], ctx->ev[5]));
-            if (stats) *stats = S;
-            return GLF_OK;
-        }
-        GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, filter_gain, filter_ysub, sig->d_sig, sig->d_out, N));
-        GLF_HIP(ctx, hipStreamSynchronize(st));
-    }
+    GLF_TRY(finish_stats(ctx, S, 0, u8_guide ? stats : nullptr));
+    // ---- planes tail ----------------------------------------------------------------------------
+    if (sig && !sig_done)
+        return filter_planes(ctx, P, d_img, width, height, pix0, pix1, tb, alpha, psi.p, phiA.p, si0, si1, lam, hG, fused, phi_base, sig, planes,
+                             sig_fused ? sig_w.p : nullptr, d_out, d_zf, S, stats);
     return GLF_OK;
 }

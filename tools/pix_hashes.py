@@ -6,7 +6,12 @@ signals call with 2 planes, the plain call with capture=True (phi_A, phi, degree
 formats on 96 x 80 also under PIX_BAND=1, NYS_PATH=band, MV_PATH=band; the plain and signals calls through Multi(2) on the loopback
 backend. Then the refusals as status and message: a kernel of another format at each entry point (both directions; KERNEL_BILATERAL at
 a non-grey entry point stands for the format's own kernel and is recorded as "no error"), a NaN and an Inf in a float guide (Context,
-Context.graph and Multi), nsig 0 and MAX_SIGNALS + 1 (Context and Multi). Run it once per build and compare the two files:
+Context.graph and Multi), nsig 0 and MAX_SIGNALS + 1 (Context and Multi). Then the driver's other branches ("driver/..."): an 8-bit grey
+96 x 80 image (60 samples, m = 8) on the band form, where the filter is fused into the extension, in every filter mode and once more with
+NO_FUSED_FILTER (plain, capture, signals with 3 planes); the grey cases above in the smoothing, PoC and sharpening modes; colour and 16-bit
+signals calls with sharpening; more than 256 eigenpairs (and their refusal of sharpening); glf_ComputeResultFromLaplacian on a narrow and a
+wide Phi; the fused grey case and the colour signals case on two loopback ranks with each rank's collectives. Every record keeps
+filter_fused, p and m. Run it once per build and compare the two files:
     python tools/pix_hashes.py new                 # this tree's glf.py and libglf.so -> pix_hashes_new.json in the current directory
     python tools/pix_hashes.py parent DIR          # DIR holds another commit's glf.py and libglf.so -> pix_hashes_parent.json"""
 import hashlib, json, os, sys
@@ -63,7 +68,7 @@ def sha(a):
 def record(arrays, info):
     infos = info if isinstance(info, list) else [info]
     d = {"arrays": [sha(a) for a in arrays], "eigvals": sha(infos[0]["eigvals"])}
-    for k in ("matvec_path", "nystroem_path", "outer_its", "matvecs"):
+    for k in ("matvec_path", "nystroem_path", "outer_its", "matvecs", "filter_fused", "p", "m"):
         d[k] = [i[k] for i in infos]
     if "capture" in infos[0]:
         cap = infos[0]["capture"]
@@ -156,5 +161,78 @@ for fmt in FORMATS:
                 out["refuse/%s/%s/multi" % (name, fmt)] = refusal(lambda: getattr(world, "image_processing" + SUFFIX[fmt])(x, options(fmt, **okw)))
                 out["refuse/%s/%s/multi/signals" % (name, fmt)] = refusal(
                     lambda: getattr(world, "image_processing" + SUFFIX[fmt] + "_signals")(x, planes(w, h), options(fmt, **okw)))
+
+# ---- the branches of the whole-path driver (image_processing_run) that the cases above do not reach ------------------------------------
+MODES = {"reference": dict(filter_mode=glf.FILTER_REFERENCE), "poc": dict(filter_mode=glf.FILTER_POC),
+         "smooth": dict(filter_mode=glf.FILTER_SMOOTH), "sharpen": dict(filter_mode=glf.FILTER_SHARPEN),
+         "reference_pow3": dict(filter_mode=glf.FILTER_REFERENCE, filter_pow=3)}
+FUSED_TUNE = dict(MV_PATH="band", NYS_PATH="band", DEG_PATH="grid")   # (where a 96 x 80 grey image takes the fused band filter)
+
+
+def grey_calls(ctx, key, img, sig, opt_kw):
+    """The plain, capture and signals calls of one 8-bit grey image."""
+    d_img, d_sig = torch.from_numpy(img).to(ctx.device), torch.from_numpy(sig).to(ctx.device)
+    r = ctx.image_processing(d_img, glf.default_options(**opt_kw), want_float=True)
+    out[key + "plain"] = record(r[:-1], r[-1])
+    r = ctx.image_processing(d_img, glf.default_options(**opt_kw), want_float=True, capture=True)
+    out[key + "capture"] = record(r[:-1], r[-1])
+    r = ctx.image_processing_signals(d_img, d_sig, glf.default_options(**opt_kw), want_float=True)
+    out[key + "signals"] = record(r[:-1], r[-1])
+
+
+# 8-bit grey, 96 x 80, 60 samples, m = 8 on the band form: the fused filter in the diagonal modes (sharpening: unfused), then NO_FUSED_FILTER
+img, sig = np.ascontiguousarray(glf.synth_image(96, 80, seed=4)), planes(96, 80, 3)
+for tname, tune in (("fused", FUSED_TUNE), ("no_fused", dict(FUSED_TUNE, NO_FUSED_FILTER="1"))):
+    for mname, mode in MODES.items():
+        with glf.Context(0) as ctx:
+            ctx.set_tuning(**tune)
+            grey_calls(ctx, "driver/u8/96x80/%s/%s/" % (tname, mname), img, sig, dict(num_samples=60, num_eigvals=8, **mode))
+# the default tuning (a stored L_A, the unfused branch) of the grey cases above in the other filter modes
+for shape, (w, h, okw) in SHAPES.items():
+    for mname in ("smooth", "poc", "sharpen"):
+        with glf.Context(0) as ctx:
+            grey_calls(ctx, "driver/u8/%s/default/%s/" % (shape, mname), image("u8", w, h), planes(w, h), dict(okw, **MODES[mname]))
+# a colour and a 16-bit guide with planes, sharpening
+w, h, okw = SHAPES["96x80"]
+for fmt in ("rgb", "u16"):
+    with glf.Context(0) as ctx:
+        d_img, d_sig = torch.from_numpy(image(fmt, w, h)).to(ctx.device), torch.from_numpy(planes(w, h)).to(ctx.device)
+        r = getattr(ctx, "image_processing" + SUFFIX[fmt] + "_signals")(d_img, d_sig, options(fmt, **okw, **MODES["sharpen"]), want_float=True)
+        out["driver/%s/96x80/signals/sharpen" % fmt] = record(r[:-1], r[-1])
+# more than 256 eigenpairs: the panels in the reference and the smoothing mode; sharpening is refused
+img = np.ascontiguousarray(glf.synth_image(256, 192, seed=17))
+for mname in ("reference", "smooth", "sharpen"):
+    with glf.Context(0) as ctx:
+        d_img = torch.from_numpy(img).to(ctx.device)
+        opt = glf.default_options(num_samples=300, num_eigvals=257, epsilon=0.2, **MODES[mname])
+        if mname == "sharpen":
+            out["refuse/wide/sharpen"] = refusal(lambda: ctx.image_processing(d_img, opt))
+        else:
+            r = ctx.image_processing(d_img, opt, want_float=True)
+            out["driver/u8/256x192/wide/%s" % mname] = record(r[:-1], r[-1])
+# glf_ComputeResultFromLaplacian on a narrow and on a wide Phi (raster rows of seeded noise, a seeded Pi)
+w, h = 61, 47
+for name, m in (("narrow", 8), ("wide", 300)):
+    rng = np.random.default_rng(23)
+    phi_np, pi_np = rng.normal(0.0, 0.05, (w * h, m)).astype(np.float32), rng.uniform(0.1, 1.0, m).astype(np.float32)
+    with glf.Context(0) as ctx:
+        phi, Pi = ctx.dense_from_numpy(phi_np, row_order=glf.ROWS_RASTER), ctx.diag_from_numpy(pi_np)
+        r = ctx.ComputeResultFromLaplacian(torch.from_numpy(image("u8", w, h)).to(ctx.device), phi, Pi, gain=3.0)
+        out["driver/result_from_laplacian/%s" % name] = dict(arrays=[sha(a) for a in r])
+        ctx.destroy(phi, Pi)
+# two ranks on the loopback backend: the fused grey case and the colour signals case, with every rank's collectives
+for name, fmt, tune, okw in (("u8/96x80/fused", "u8", FUSED_TUNE, dict(num_samples=60, num_eigvals=8)), ("rgb/96x80/default", "rgb", {}, SHAPES["96x80"][2])):
+    with glf.Multi(2, devices=[0, 0], backend=glf.MULTI_LOOPBACK) as world:
+        world.set_tuning(**tune)
+        img = np.ascontiguousarray(glf.synth_image(96, 80, seed=4)) if fmt == "u8" else image(fmt, 96, 80)
+        for r in (0, 1):
+            world.comm_counters(r)   # (reset)
+        if fmt == "u8":
+            res = world.image_processing(img, glf.default_options(**okw), want_float=True)
+            out["driver/multi/%s/plain" % name] = dict(record(res[:-1], res[-1]), comm=[world.comm_counters(r) for r in (0, 1)])
+            res = world.image_processing_signals(img, planes(96, 80, 3), glf.default_options(**okw))
+        else:
+            res = world.image_processing_rgb_signals(img, planes(96, 80), options(fmt, **okw), want_float=True)
+        out["driver/multi/%s/signals" % name] = dict(record(res[:-1], res[-1]), comm=[world.comm_counters(r) for r in (0, 1)])
 json.dump(out, open("pix_hashes_%s.json" % tag, "w"), indent=1, sort_keys=True)
 print(tag, len(out), "cases")
