@@ -289,6 +289,7 @@ int degree_rows(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int r
                        d_degree);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // partial is freed at scope exit
+    ctx->deg_note = {0, 0, 0, nchunks, 0, (double)p * (double)(row1 - row0) * (double)width};
     return GLF_OK;
 }
 
@@ -346,10 +347,11 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
     int max_rows = 1;
     double evals = 0.0;
     for (int b = 0; b < nsb; ++b) {
-        int rmin = 1 << 30, rmax = -1, cmin = 1 << 30, cmax = -1;
+        int rmin = 1 << 30, rmax = -1, cmin = 1 << 30, cmax = -1, live = 0;
         for (int t = 0; t < DEG_THREADS; ++t) {
             const uint32_t i = perm[(size_t)b * DEG_THREADS + t];
             if (i >= p) continue;
+            ++live;
             const int r = (int)(h_idx[i] / (unsigned)width), c = (int)(h_idx[i] % (unsigned)width);
             rmin = std::min(rmin, r); rmax = std::max(rmax, r); cmin = std::min(cmin, c); cmax = std::max(cmax, c);
         }
@@ -359,7 +361,7 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
         const int rows = std::max(0, std::min(row1, rw0 + (int)ceil_div(std::max(0, rw1 - rw0), DEG_ROWS) * DEG_ROWS) - rw0);
         const int cols = std::min(width, cmax + radius + 1) - (std::max(0, cmin - radius) & ~3);
         max_rows = std::max(max_rows, rows);
-        evals += (double)DEG_THREADS * rows * cols;
+        evals += (double)live * rows * cols; // (the entries of the block's samples: the padding lanes of the last block are not entries)
     }
     if (evaluated) *evaluated = evals;
     const int nchunks = (int)ceil_div(max_rows, DEG_ROWS);
@@ -380,6 +382,7 @@ int degree_rows_windowed(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
     hipLaunchKernelGGL(k_reduce_partials, dim3((p + 255) / 256), dim3(256), 0, ctx->stream, partial.p, p, nchunks, d_degree);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // host vectors and DevBufs are released at scope exit
+    ctx->deg_note = {2, 0, 1, nchunks, 0, evals};
     return GLF_OK;
 }
 
@@ -405,11 +408,17 @@ int degree_rows_auto(glf_ctx *ctx, const uint8_t *d_img, int width, int height, 
     if (coef.kernel == GLF_KERNEL_NLM) { // patch distances: no factored form, its own sweep (nlm.hip)
         if (!d_idx) return set_error(ctx, GLF_ERR_INVALID, "NLM degree needs the device sample indices");
         if (evaluated) *evaluated = (double)p * (double)(row1 - row0) * (double)width;
+        ctx->deg_note = {6, 0, 0, 0, 0, (double)p * (double)(row1 - row0) * (double)width};
         return nlm_degree_rows(ctx, d_img, width, height, row0, row1, d_idx, p, coef, d_degree);
     }
     const PixGen gen = pixgen_of(coef.kernel);
-    if (gen != PixGen::Grey) // no factored form over 2^24 colours or 65 536 levels, no 256-entry table: the windowed sweep (entrywise.hip)
-        return degree_rows_entrywise(ctx, gen, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, evaluated);
+    if (gen != PixGen::Grey) { // no factored form over 2^24 colours or 65 536 levels, no 256-entry table: the windowed sweep (entrywise.hip)
+        double ev = 0.0;
+        const int rc = degree_rows_entrywise(ctx, gen, d_img, width, height, row0, row1, d_samples, p, coef, d_degree, &ev);
+        if (evaluated) *evaluated = ev;
+        ctx->deg_note = {5, 0, 1, (int)ceil_div(std::max(0, row1 - row0), 16), 0, ev}; // (chunks of EW_ROWS = 16 rows; always windowed)
+        return rc;
+    }
     const int rc = degree_rows_grid(ctx, d_img, width, height, row0, row1, d_samples, p, h_idx, coef, d_degree, window, evaluated, d_ysum);
     if (rc != GLF_ERR_UNSUPPORTED) {
         if (have_ysum) *have_ysum = rc == GLF_OK && d_ysum != nullptr; // (only the grid-factored degree has the value-weighted sums)

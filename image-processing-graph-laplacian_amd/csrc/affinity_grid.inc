@@ -31,7 +31,7 @@ template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void k_dgrid_hist(const float *__restrict__ etab, int ne, const int *__restrict__ gcol, int nc,
                                                      int ncp, const unsigned short *__restrict__ scol,
                                                      const unsigned *__restrict__ goff, int width, float *__restrict__ Wt,
-                                                     const float *__restrict__ wplane)
+                                                     const float *__restrict__ wplane, int pexp)
 {
     extern __shared__ float etab_s[]; // [ne], then the row's value-sorted columns u16 [width] (WEIGHTED: then the row's weights)
     unsigned short *sc_s = reinterpret_cast<unsigned short *>(etab_s + ne);
@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void k_dgrid_hist(const float *__restrict__ et
     // every step; from LDS, and with eight pixels' gathers in flight at a time, 1.25 -> 0.94 ms at cfg4)
     for (int i = threadIdx.x; i < width; i += 256) sc_s[i] = sc[i];
     if (WEIGHTED)
-        for (int i = threadIdx.x; i < width; i += 256) w_s[i] = wplane[(size_t)rl * width + i];
+        for (int i = threadIdx.x; i < width; i += 256) w_s[i] = ldexpf(wplane[(size_t)rl * width + i], -pexp); // (pexp = 0: the plane's bits)
     __syncthreads();
     constexpr int NB = 10; // ncp <= 640
     int gc[NB];
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(NW * 64) void k_dgrid_zmfma(const _Float16 *__restr
 __global__ __launch_bounds__(256) void k_dgrid_final_parts(const float *__restrict__ Zpart, int nchunks, const float *__restrict__ ptab,
                                                             const float4 *__restrict__ samples, int nr, int nc, int ncp,
                                                             double *__restrict__ degree, double *__restrict__ ysum,
-                                                            const int *__restrict__ grow, int row0, int radius)
+                                                            const int *__restrict__ grow, int row0, int radius, double dscale)
 {
     // ysum (optional): U[s] = sum over the same pixels of K(s, px) y[px] -- the pixel's value rides along with its
     // histogram bin (y = v), so it is the same sum with v P in place of P: the whole of c = Phi^T y for the extended
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(256) void k_dgrid_final_parts(const float *__restri
             t += sh[k][sl];
             tu += shu[k][sl];
         }
-        degree[s] = t;
+        degree[s] = t * dscale; // (1, or the power of two a far-scaled weight plane was divided by: exact)
         if (ysum) ysum[s] = tu;
     }
 }
@@ -337,12 +337,22 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
     // entries of the factor table the histogram needs: up to the first exact zero (kept as the clamp target)
     const int ne = std::min(gt.maxdim, gt.radius + 1);
     if (ne > DGRID_NE_MAX) return GLF_ERR_UNSUPPORTED; // (a kernel this wide on an image this large: the direct sweep runs)
+    // A weight plane far from 1 (max |s| below 2^-40 or above 2^100) is divided by the power of two 2^pexp of its maximum as the
+    // histogram reads it, and the sums are multiplied by it in f64 at the end: with the plane as it is, the f32 histogram sums and
+    // the f32 chunk sums Zpart underflow below about 2^-60 (and 2^wsh overflows below 2^-113), and Zpart overflows above about
+    // 2^118. Both scalings are exact, so U_s(2^k s) = 2^k U_s(s) bit for bit; a plane within the range keeps pexp = 0 and its bits.
+    int pexp = 0;
+    if (d_wplane && wabs > 0.0 && std::isfinite(wabs)) {
+        int aexp = 0;
+        (void)std::frexp(wabs, &aexp);
+        if (aexp < -40 || aexp > 100) pexp = aexp;
+    }
     if (d_wplane)
         hipLaunchKernelGGL(k_dgrid_hist<true>, dim3(nrows), dim3(256), (size_t)ne * sizeof(float) + (size_t)((width + 1) / 2) * 4 + (size_t)width * 4,
-                           st, gt.etab(), ne, gt.gcol(), gt.nc, gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, d_wplane + (size_t)row0 * width);
+                           st, gt.etab(), ne, gt.gcol(), gt.nc, gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, d_wplane + (size_t)row0 * width, pexp);
     else
         hipLaunchKernelGGL(k_dgrid_hist<false>, dim3(nrows), dim3(256), (size_t)ne * sizeof(float) + (size_t)width * 2, st, gt.etab(), ne, gt.gcol(), gt.nc,
-                           gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, (const float *)nullptr);
+                           gt.ncp, gt.scol.p, gt.goff.p, width, Wt.p, (const float *)nullptr, 0);
     const bool skip = window && gt.can_skip(coef);
     // row contraction on the matrix pipe (k_dgrid_zmfma): Wt entries are sums of Ec over a row's pixels of one value, bounded by
     // the whole factor table's mass -> one power-of-two scale keeps 2^wsh Wt below the f16 range
@@ -351,7 +361,7 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
         const double s_loc = (double)coef.s_loc;
         for (int d = 1; d < width; ++d) wmax += std::exp2(-s_loc * (double)d * (double)d);
         wmax = 1.0 + 2.0 * wmax;
-        if (d_wplane) wmax *= wabs > 0.0 ? wabs : 1.0; // signed weights: |Wt_s| <= max |s| x the table's mass
+        if (d_wplane) wmax *= wabs > 0.0 ? std::ldexp(wabs, -pexp) : 1.0; // signed weights: |Wt_s| <= max |s| x the table's mass
     }
     int wexp = 0;
     (void)std::frexp(wmax, &wexp);       // wmax < 2^wexp
@@ -408,10 +418,10 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
     }
 #undef GLF_ZMFMA
     hipLaunchKernelGGL(k_dgrid_final_parts, dim3((p + 31) / 32), dim3(256), 0, st, Zpart.p, nchunks, gt.ptab(), d_samples, gt.nr, gt.nc,
-                       gt.ncp, d_degree, d_ysum, gt.grow(), row0, gt.radius < gt.maxdim ? gt.radius : (1 << 28));
+                       gt.ncp, d_degree, d_ysum, gt.grow(), row0, gt.radius < gt.maxdim ? gt.radius : (1 << 28), std::ldexp(1.0, pexp));
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (evaluated) { // kernel entries represented by the factored sums
+    { // kernel entries represented by the factored sums
         double rows_in = (double)g.nr * nrows, cols_in = (double)g.nc * width;
         if (skip) { // (row, grid row) and (column, grid column) pairs closer than the exact-zero radius
             rows_in = cols_in = 0.0;
@@ -420,7 +430,9 @@ static int degree_rows_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int h
             for (int b = 0; b < g.nc; ++b)
                 cols_in += std::max(0, std::min(width, g.cols[b] + gt.radius) - std::max(0, g.cols[b] - gt.radius + 1));
         }
-        *evaluated = rows_in * cols_in;
+        if (evaluated) *evaluated = rows_in * cols_in;
+        // (what glf_Degree_ex reports: the shape of k_dgrid_zmfma that ran, its chunks of DGZ_CHUNK image rows and its m-groups)
+        ctx->deg_note = {1, window_ok ? 2 : one_group ? 1 : 0, skip ? 1 : 0, nchunks, mgroups, rows_in * cols_in};
     }
     return GLF_OK;
 }

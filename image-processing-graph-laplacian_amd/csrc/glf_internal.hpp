@@ -87,6 +87,8 @@ struct glf_ctx {
     // what the last nystroem_contract launch ran with (glf_Nystroem_ex reports it): an exact-zero window (a SKIP instantiation, the
     // grid and rank forms' skipping passes, the band form's schedule), the table-driven generation of k_nystroem_f16s
     struct { int skipping = 0, lut = 0; } nys_note;
+    // what the last degree sweep ran (glf_Degree_ex reports it): glf_degree_info's path, shape, skipping, chunks, mgroups, entries
+    struct { int path = 0, shape = 0, skipping = 0, chunks = 0, mgroups = 0; double entries = 0.0; } deg_note;
     // one page of pinned, device-visible host memory the eigensolver's kernels write their flags and norms into (read
     // after a stream synchronise; no D2H copy launches, and no hipHostMalloc per image): see glf::ctx_pinned()
     void *pinned = nullptr;

@@ -240,6 +240,69 @@ int glf_ComputeAffinityMatrices(glf_ctx *ctx, glf_mat *K_A, glf_mat *K_B, const 
     return GLF_OK;
 }
 
+// The degree stage by itself: the tables, coefficients and dispatch of glf_ComputeAffinityMatrices over one rank's rows, with the whole
+// path's window and sums (run_planned's degree_rows_auto and weighted_sums_grid calls), no all-reduce, and a report of what ran.
+int glf_Degree_ex(glf_ctx *ctx, const void *d_img_v, int width, int height, unsigned sample_size, const unsigned *sample_indices,
+                  int kernel, float h_loc, float h_val, int skip_exact_zeros, unsigned row0u, unsigned row1u, const float *d_plane,
+                  double *h_degree, double *h_ysum, glf_degree_info *info)
+{
+    const uint8_t *d_img = static_cast<const uint8_t *>(d_img_v);
+    if (!ctx || !d_img || !h_degree || width <= 0 || height <= 0) return GLF_ERR_INVALID;
+    if (info && info->struct_size != sizeof(glf_degree_info))
+        return set_error(ctx, GLF_ERR_INVALID, "degree: glf_degree_info.struct_size %u, expected %zu", info->struct_size, sizeof(glf_degree_info));
+    if (kernel < GLF_KERNEL_BILATERAL || kernel > GLF_KERNEL_BILATERAL_RGBF32)
+        return set_error(ctx, GLF_ERR_INVALID, "degree: kernel %d is not one of GLF_KERNEL_*", kernel);
+    if (kernel == GLF_KERNEL_NLM && (width < 3 || height < 3))
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "non-local-means kernel: the image must be at least 3 x 3 pixels (%d x %d)", width, height);
+    const bool all_rows = row0u == 0 && row1u == 0;
+    if (!all_rows && (row0u >= row1u || row1u > (unsigned)height))
+        return set_error(ctx, GLF_ERR_INVALID, "degree: image rows [%u, %u) are not a range of the %d rows", row0u, row1u, height);
+    if (d_plane && h_ysum) return set_error(ctx, GLF_ERR_INVALID, "degree: a weight plane has no value-weighted sums (d_plane with h_ysum)");
+    if (d_plane && !grey_levels_factor(kernel))
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "degree: the weighted sums take an 8-bit grey kernel (kernel %d)", kernel);
+    if (h_ysum && !grey_levels_factor(kernel))
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "degree: only the grid-factored form has the value-weighted sums (kernel %d)", kernel);
+    GLF_ENTER(ctx);
+    GLF_TRY(f32_admit(ctx, pixgen_of(kernel), d_img, width, height));
+    const unsigned p = sample_size;
+    const int row0 = all_rows ? 0 : (int)row0u, row1 = all_rows ? height : (int)row1u;
+    SampleTables tb;
+    GLF_TRY(build_sample_tables(ctx, d_img, width, height, p, sample_indices, tb, kernel));
+    const KernelCoef coef = make_coef(kernel, h_loc, h_val);
+    const int window = skip_exact_zeros ? 1 : 0;
+    DevBuf<double> deg;
+    GLF_TRY(deg.alloc(ctx, (size_t)2 * p));
+    bool have_ysum = false;
+    if (d_plane) {
+        float smax = 0.f;
+        GLF_TRY(plane_absmax(ctx, d_plane + (size_t)row0 * width, (int64_t)(row1 - row0) * width, &smax));
+        const int rc = weighted_sums_grid(ctx, d_img, width, height, row0, row1, tb.samples.p, p, sample_indices, coef, window, d_plane,
+                                          (double)smax, deg.p);
+        if (rc != GLF_OK) return rc == GLF_ERR_UNSUPPORTED ? set_error(ctx, GLF_ERR_UNSUPPORTED, "degree: weighted sums: no grid-factored degree for this sample set") : rc;
+    } else {
+        GLF_TRY(degree_rows_auto(ctx, d_img, width, height, row0, row1, tb.samples.p, p, sample_indices, coef, deg.p, window, nullptr,
+                                 tb.idx.p, h_ysum ? deg.p + p : nullptr, &have_ysum));
+        if (h_ysum && !have_ysum)
+            return set_error(ctx, GLF_ERR_UNSUPPORTED, "degree: the form that ran (path %d) has no value-weighted sums", ctx->deg_note.path);
+    }
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<double> h((size_t)2 * p); // (staged: a failing copy leaves the caller's buffers as they were)
+    GLF_TRY(glf_memcpy_d2h(ctx, h.data(), deg.p, sizeof(double) * (have_ysum ? 2 : 1) * p));
+    std::memcpy(h_degree, h.data(), sizeof(double) * p);
+    if (h_ysum) std::memcpy(h_ysum, h.data() + p, sizeof(double) * p);
+    if (info) {
+        info->path = ctx->deg_note.path;
+        info->shape = ctx->deg_note.shape;
+        info->skipping = ctx->deg_note.skipping;
+        info->chunks = ctx->deg_note.chunks;
+        info->mgroups = ctx->deg_note.mgroups;
+        info->row0 = (uint32_t)row0;
+        info->row1 = (uint32_t)row1;
+        info->entries_evaluated = ctx->deg_note.entries;
+    }
+    return GLF_OK;
+}
+
 int glf_ComputeLaplacianMatrix(glf_ctx *ctx, glf_mat *L_A, glf_mat *L_B, const glf_mat *K_A, const glf_mat *K_B,
                                double *alpha_out)
 {

@@ -72,7 +72,7 @@ EXPORTS = [
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
     "glf_graph_edges", "glf_graph_samples",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
-    "glf_Nystroem_ex",
+    "glf_Nystroem_ex", "glf_Degree_ex",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
@@ -200,6 +200,15 @@ class NystroemInfo(C.Structure):
                 ("row1", C.c_uint32), ("entries_evaluated", C.c_double)]
 
 
+class DegreeInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("path", C.c_int32), ("shape", C.c_int32), ("skipping", C.c_int32), ("chunks", C.c_int32),
+                ("mgroups", C.c_int32), ("row0", C.c_uint32), ("row1", C.c_uint32), ("entries_evaluated", C.c_double)]
+
+
+DEG_DENSE, DEG_GRID, DEG_WINDOWED, DEG_ENTRYWISE, DEG_NLM = 0, 1, 2, 5, 6   # glf_degree_info.path
+DEG_FIVES, DEG_TEN, DEG_WINDOW = 0, 1, 2                                    # glf_degree_info.shape (grid form)
+
+
 class BasisStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("defect_in", C.c_double), ("defect_out", C.c_double)]
 
@@ -265,6 +274,8 @@ _lib.glf_operator_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void
 _lib.glf_operator_stored.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_operator_destroy.argtypes = [C.c_void_p]
 _lib.glf_Nystroem_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
+_lib.glf_Degree_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint,
+                               C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -1171,6 +1182,27 @@ class Context:
         self._check(_lib.glf_Nystroem_ex(self._ctx, C.byref(B), C.byref(phi_A), C.byref(Pi_A_Inv), C.c_int(skip_exact_zeros), C.c_uint(row0),
                                          C.c_uint(row1), C.byref(out), C.byref(info)), "Nystroem_ex")
         return out, {k: getattr(info, k) for k, _ in NystroemInfo._fields_}
+
+    def Degree_ex(self, d_img, sample_indices, kernel=KERNEL_BILATERAL, h_loc=40.0, h_val=30.0, skip_exact_zeros=0, rows=None,
+                  plane=None, want_ysum=False, out=None):
+        """glf_Degree_ex: the degree stage over the image rows `rows` = (row0, row1) (None: all) with the whole path's knobs. d_img: the
+        guide as a device tensor in the kernel's format; plane: a device float32 [H, W] tensor -- the result is then the weighted sums
+        U_s. out = (degree, ysum or None): host float64 [p] arrays to write into (default: new ones). Returns (degree, ysum or None,
+        info dict of glf_degree_info); a refusal raises GlfError and leaves `out` untouched."""
+        h, w = d_img.shape[:2]
+        idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)
+        row0, row1 = (0, 0) if rows is None else rows
+        deg, ysum = out if out is not None else (np.empty(idx.size, dtype=np.float64), np.empty(idx.size, dtype=np.float64) if want_ysum else None)
+        assert deg.dtype == np.float64 and deg.size == idx.size and deg.flags.c_contiguous
+        assert ysum is None or (ysum.dtype == np.float64 and ysum.size == idx.size and ysum.flags.c_contiguous)
+        assert plane is None or (plane.dtype == self.torch.float32 and plane.is_cuda and plane.is_contiguous() and tuple(plane.shape) == (h, w))
+        info = DegreeInfo(struct_size=C.sizeof(DegreeInfo))
+        self._check(_lib.glf_Degree_ex(self._ctx, C.c_void_p(d_img.data_ptr()), C.c_int(w), C.c_int(h), C.c_uint(idx.size),
+                                       idx.ctypes.data_as(C.c_void_p), C.c_int(kernel), C.c_float(h_loc), C.c_float(h_val),
+                                       C.c_int(skip_exact_zeros), C.c_uint(row0), C.c_uint(row1),
+                                       C.c_void_p(plane.data_ptr()) if plane is not None else None, deg.ctypes.data_as(C.c_void_p),
+                                       ysum.ctypes.data_as(C.c_void_p) if ysum is not None else None, C.byref(info)), "Degree_ex")
+        return deg, ysum, {k: getattr(info, k) for k, _ in DegreeInfo._fields_}
 
     def Permutation(self, mat, sample_indices):
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)

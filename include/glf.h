@@ -398,6 +398,33 @@ int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const 
                     int skip_exact_zeros, unsigned row0, unsigned row1,
                     glf_mat *phi, glf_nystroem_info *info);
 
+/* The degree stage on its own, with the whole path's knobs: D[i] = sum over the image rows [row0, row1) of K(sample i, pixel), this
+ * rank's share only (no all-reduce), by the sample tables, coefficients and the degree dispatch glf_ComputeAffinityMatrices and
+ * glf_image_processing run. d_img: the guide in the kernel's pixel format; sample_indices: HOST, ascending.
+ * skip_exact_zeros: as glf_options.skip_exact_zeros (the grid form's SKIP kernels, the windowed direct sweep); same bits, less work.
+ * row0 == row1 == 0: all image rows; otherwise row0 < row1 <= height.
+ * h_ysum (optional, HOST [p]): the value-weighted sums U[i] = sum K(sample i, pixel) y[pixel]. Only the grid-factored form has them:
+ *   where another form runs the call answers GLF_ERR_UNSUPPORTED and writes nothing.
+ * d_plane (optional, device float [height][width]): h_degree receives the joint-filtering sums U_s[i] = sum K(sample i, pixel)
+ *   s[pixel] of the grid-factored form instead (operand scale: max |s| over the rows summed); h_ysum must be NULL. Where the grid form
+ *   does not apply (not a tensor grid, not an 8-bit grey kernel, DEG_PATH) the call answers GLF_ERR_UNSUPPORTED.
+ * info (optional): the caller sets struct_size = sizeof(glf_degree_info); the call fills the rest.
+ * A refusal names its reason in glf_ctx_last_error and leaves h_degree, h_ysum and info untouched. */
+typedef struct glf_degree_info {
+    uint32_t struct_size;
+    int32_t  path;        /* 0 dense direct sweep (k_degree), 1 grid-factored, 2 windowed direct (k_degree_win), 5 entry by entry (pixel formats), 6 NLM */
+    int32_t  shape;       /* grid only: 0 groups of five m-tiles, 1 one group of ten, 2 window */
+    int32_t  skipping;    /* 1: a SKIP / windowed instantiation ran */
+    int32_t  chunks;      /* grid: chunks of 512 image rows; direct and entry by entry: chunks of 16 rows */
+    int32_t  mgroups;     /* grid only */
+    uint32_t row0, row1;  /* image rows summed */
+    double   entries_evaluated;
+} glf_degree_info;
+
+int glf_Degree_ex(glf_ctx *ctx, const void *d_img, int width, int height, unsigned sample_size, const unsigned *sample_indices,
+                  int kernel, float h_loc, float h_val, int skip_exact_zeros, unsigned row0, unsigned row1,
+                  const float *d_plane, double *h_degree, double *h_ysum, glf_degree_info *info);
+
 /* Mat Permutation(Mat m, const unsigned* idx, unsigned p)  hpc/utils.h:18, hpc/utils.c:134-173
  * sample-first rows -> raster rows. sample_indices: HOST. */
 int glf_Permutation(glf_ctx *ctx, const glf_mat *in, const unsigned *sample_indices,
