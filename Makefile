@@ -20,7 +20,7 @@ C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o
 
 all: $(PKG)/libglf.so $(PKG)/image_processing oracle
 
-$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/glf_internal.hpp $(CSRC)/phi_tile.hpp $(CSRC)/phi_compact.hpp $(CSRC)/nystroem_grid.inc $(CSRC)/nystroem_rank.inc $(CSRC)/nystroem_band.inc $(CSRC)/nystroem_band_vec.inc $(CSRC)/nystroem_band_sep.inc $(CSRC)/grid_common.inc $(CSRC)/affinity_grid.inc $(CSRC)/band_plan.hpp $(CSRC)/robust_loss.hpp $(CSRC)/filter_rule.hpp include/glf.h
+$(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/glf_internal.hpp $(CSRC)/phi_tile.hpp $(CSRC)/phi_compact.hpp $(CSRC)/nystroem_grid.inc $(CSRC)/nystroem_rank.inc $(CSRC)/nystroem_band.inc $(CSRC)/nystroem_band_vec.inc $(CSRC)/nystroem_band_sep.inc $(CSRC)/grid_common.inc $(CSRC)/affinity_grid.inc $(CSRC)/band_plan.hpp $(CSRC)/robust_loss.hpp $(CSRC)/filter_rule.hpp $(CSRC)/scale_rule.hpp include/glf.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/host_util.o: $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp $(CSRC)/phi_compact.hpp $(CSRC)/robust_loss.hpp include/glf.h
@@ -74,8 +74,14 @@ quad_check: tools/quad_host_main.cpp $(CSRC)/host_util.cpp $(CSRC)/band_plan.hpp
 	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o tools/quad_host_check $(filter %.cpp,$^)
 	tools/quad_host_check
 
+# the power-of-two operand scale rule (scale_rule.hpp) against its statement in double precision, at every f32 exponent and at the edges, under the address and undefined-behaviour sanitizers (CPU only)
+SCALE_RULE_CHECK_BIN ?= tools/scale_rule_host_check
+scale_rule_check: tools/scale_rule_host_main.cpp $(CSRC)/scale_rule.hpp
+	g++ -O1 -g -std=c++17 -Wall -Wextra -fsanitize=address,undefined -fno-sanitize-recover=all -o $(SCALE_RULE_CHECK_BIN) $(filter %.cpp,$^)
+	$(SCALE_RULE_CHECK_BIN)
+
 clean:
 	rm -f $(CSRC)/*.o $(HOST)/*.o $(PKG)/libglf.so $(PKG)/image_processing
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean pfm_check cluster_check basis_check band_plan_check robust_check compact_check quad_check
+.PHONY: all oracle clean pfm_check cluster_check basis_check band_plan_check robust_check compact_check quad_check scale_rule_check

@@ -651,9 +651,8 @@ int nlm_degree_rows(glf_ctx *ctx, const uint8_t *d_img, int width, int height, i
                     KernelCoef coef, double *d_degree);
 int nlm_sample_matrix(glf_ctx *ctx, const uint8_t *d_img, int width, int height, const uint32_t *d_idx, unsigned p, KernelCoef coef,
                       float *d_out, int64_t ld, bool laplacian, double alpha, const double *d_degree, unsigned col0, unsigned ncols);
-int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const uint8_t *d_mask,
-                 const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld, float *d_phi, int raster,
-                 double *d_c, float *kernel_ms);
+struct NysRequest;
+int nlm_nystroem(glf_ctx *ctx, const NysRequest &rq);
 // out[i] = sum over the chunks k of partial[k][i], k ascending (affinity.hip)
 __global__ void k_reduce_partials(const double *__restrict__ partial, unsigned p, int nchunks, double *__restrict__ out);
 // the formats without a factored form (entrywise.hip, gen Rgb, U16, F32 or RgbF32; d_img in the format): the contract of degree_rows, the
@@ -719,11 +718,6 @@ struct BandFilter {
     BandSignals sig;
     const float *w = nullptr; // [ld] filter weights x c (device)
 };
-// GLF_ERR_UNSUPPORTED: the band form does not apply (not a tensor grid, radius too large, or auto mode prefers a factored form)
-int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                         const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
-                         const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, int *path,
-                         RowpassStats *stats, const unsigned *h_idx = nullptr); // h_idx: the host copy of d_idx when the caller has it
 // c = Psi^T (ysum - t) + Phi_A^T y_A  (ysum: the degree stage's value-weighted sums over all pixels; t = K_A y_A takes the
 // sample pixels out again): Phi^T y without Phi. d_c [ld] f64.
 int c_from_ysum(glf_ctx *ctx, const float *d_psi, const float *d_phiA, const double *d_ysum, const float *d_t, unsigned t_ld,
@@ -852,15 +846,41 @@ int inverse_power_iteration_panels(glf_ctx *ctx, const float *A, int64_t lda, un
                                    const float *d_dinv);
 int orthonormalise_panels(glf_ctx *ctx, float *X, unsigned n, unsigned m, double *h_norms, bool normalise_only);
 
-// Nystroem contraction (nystroem.hip): Phi[pix][j] = sum_i scale*K(sample i, pix) * Psi[i][j]
-// for pixels [pix0, pix1). raster != 0: row = pix; else sample-first (rows of sample pixels skipped).
-// cpart (optional): m doubles, += sum over NON-sample pixels of Phi[pix][j] * y[pix].
-int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
-                      const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
-                      KernelCoef coef, float scale, const float *d_psi, unsigned m, unsigned ld,
-                      float *d_phi, int raster, double *d_c, float *kernel_ms, int window = 0,
-                      uint64_t *entries_evaluated = nullptr, double *mfma_flops = nullptr, int *path = nullptr,
-                      RowpassStats *rowpass = nullptr);
+// One Nystroem extension, as every form of it takes it (nystroem.hip): Phi[pix][j] = sum_i K(sample i, pix) * Psi[i][j] for the pixels
+// [pix0, pix1). The caller names the fields it sets; the rest keep their defaults.
+struct NysRequest {
+    // the targets: [N] pixels in the format of coef.kernel; mask [N] != 0 and idx [p] (ascending) name the sample pixels
+    const uint8_t *d_img = nullptr;
+    int width = 0, height = 0;
+    int64_t pix0 = 0, pix1 = 0;
+    const uint8_t *d_mask = nullptr;
+    const uint32_t *d_idx = nullptr;
+    int raster = 0; // != 0: Phi's row = the pixel; else sample-first (the rows of the sample pixels are skipped)
+    // the samples: records {row, col, value, 0}; h_idx: the host copy of d_idx when the caller has it
+    const float4 *d_samples = nullptr;
+    unsigned p = 0;
+    KernelCoef coef{};
+    const unsigned *h_idx = nullptr;
+    // the operand: Psi [round_up(p, NYS_PAD)][ld] (the scale -alpha folded in), m <= ld columns in use
+    const float *d_psi = nullptr;
+    unsigned m = 0, ld = 0;
+    // the outputs: Phi (row stride ld); d_c (optional): ld doubles, += the sum over the NON-sample pixels of Phi[pix][j] * y[pix];
+    // flt (nystroem_band_filter only): the filter applied in the kernel's epilogue, Phi never written
+    float *d_phi = nullptr;
+    double *d_c = nullptr;
+    const BandFilter *flt = nullptr;
+    int window = 0; // != 0: pass over what is exactly zero (skip_exact_zeros)
+    // the report, each field optional. path: 0 entry by entry, 1 exact grid form, 3 rank form, 4 band form
+    float *kernel_ms = nullptr;
+    uint64_t *entries_evaluated = nullptr;
+    double *mfma_flops = nullptr;
+    int *path = nullptr;
+    RowpassStats *rowpass = nullptr;
+};
+int nystroem_contract(glf_ctx *ctx, const NysRequest &rq);
+// The same extension with the filter fused into the band form (rq.flt set; d_phi, d_c, m, raster and window are not read).
+// GLF_ERR_UNSUPPORTED: the band form does not apply (not a tensor grid, radius too large, or auto mode prefers a factored form)
+int nystroem_band_filter(glf_ctx *ctx, const NysRequest &rq);
 // box[c] = {rmin, rmax, cmin, cmax} of samples [64 c, 64 c + 64) (nystroem.hip)
 int chunk_boxes(glf_ctx *ctx, const float4 *d_samples, unsigned p, int4 *d_box);
 // Phi rows of the sample pixels <- Phi_A rows (hpc/nystroem.c:25-34 + hpc/utils.c:149-152)

@@ -160,10 +160,19 @@ __global__ __launch_bounds__(256) void k_grid_rowsort(const uint8_t *__restrict_
 }
 
 
-// Device-side tables of one (sample grid, kernel, row shard): P and E factor tables (correctly rounded from f64),
-// grid coordinates, Er per (image row, grid row) with the non-zero k-step mask, and the value-sorted columns of every image row of the shard.
+// The target rows of the tables: nrows rows of a byte image with `stride` columns, from its row `first` on. They stand at the image
+// rows first + rl -- or, at_grid_rows, at the sample grid's own rows: the L_A operator, whose image is the nr x nc image of the
+// sample values.
+struct GridTargets {
+    const uint8_t *img;
+    int stride, first, nrows;
+    bool at_grid_rows;
+};
+// Device-side tables of one (sample grid, kernel, target rows): P and E factor tables (correctly rounded from f64), grid
+// coordinates, Er per (target row, grid row) with the non-zero k-step mask, and the value-sorted columns of every target row.
 struct GridTables {
     int nr = 0, nc = 0, ks = 0, kp = 0, ncp = 0, radius = 0, radius16 = 0, row0 = 0, nrows = 0, maxdim = 0;
+    std::vector<float> htab; // (pageable: kept while its upload may be in flight)
     DevBuf<float> tab, ermat;
     DevBuf<int> grid;
     DevBuf<unsigned long long> active;
@@ -173,7 +182,9 @@ struct GridTables {
     const float *etab() const { return tab.p + 256; }
     const int *grow() const { return grid.p; }
     const int *gcol() const { return grid.p + nr; }
-    int build(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, const uint8_t *d_img, int width, int height, int r0, int r1)
+    // maxdim: the distances the E table covers (the larger side of the image). g outlives the call's stream work; sync = false
+    // leaves the stream to the caller, who synchronises before the tables are used from another stream or g goes away.
+    int build(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, int maxdim_, const GridTargets &t, bool sync = true)
     {
         hipStream_t st = ctx->stream;
         nr = g.nr;
@@ -181,10 +192,10 @@ struct GridTables {
         ks = (int)ceil_div(nr, 16);
         kp = ks * 16;
         ncp = (int)round_up(nc, 4);
-        row0 = r0;
-        nrows = r1 - r0;
-        maxdim = std::max(width, height);
-        std::vector<float> htab(256 + (size_t)maxdim);
+        row0 = t.first;
+        nrows = t.nrows;
+        maxdim = maxdim_;
+        htab.resize(256 + (size_t)maxdim);
         for (int e = 0; e < 256; ++e) htab[e] = (float)std::exp2(-(double)coef.s_val * e * e);
         for (int d = 0; d < maxdim; ++d) htab[256 + d] = (float)std::exp2(-(double)coef.s_loc * (double)d * (double)d);
         radius = maxdim; // first distance at which the spatial factor is exactly +0 in f32
@@ -201,14 +212,20 @@ struct GridTables {
         GLF_HIP(ctx, hipMemcpyAsync(grid.p + nr, g.cols.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st));
         GLF_TRY(ermat.alloc(ctx, (size_t)nrows * kp));
         GLF_TRY(active.alloc(ctx, (size_t)nrows));
-        GLF_TRY(scol.alloc(ctx, (size_t)nrows * width));
+        GLF_TRY(scol.alloc(ctx, (size_t)nrows * t.stride));
         GLF_TRY(goff.alloc(ctx, (size_t)nrows * 257));
         GLF_TRY(pmask.alloc(ctx, (size_t)nrows * 8));
-        hipLaunchKernelGGL(k_grid_rowsort, dim3(nrows), dim3(256), 0, st, d_img, width, row0, scol.p, goff.p, pmask.p);
-        hipLaunchKernelGGL(k_grid_ermat, dim3(nrows), dim3(64), 0, st, etab(), grow(), nr, kp, row0, nullptr, ermat.p, active.p);
+        hipLaunchKernelGGL(k_grid_rowsort, dim3(nrows), dim3(256), 0, st, t.img, t.stride, row0, scol.p, goff.p, pmask.p);
+        hipLaunchKernelGGL(k_grid_ermat, dim3(nrows), dim3(64), 0, st, etab(), grow(), nr, kp, row0, t.at_grid_rows ? grow() : nullptr, ermat.p,
+                           active.p);
         GLF_LAUNCH_CHECK(ctx);
-        GLF_HIP(ctx, hipStreamSynchronize(st)); // htab is pageable host memory
+        if (sync) GLF_HIP(ctx, hipStreamSynchronize(st));
         return GLF_OK;
+    }
+    // the image rows [r0, r1) of d_img as targets (the Nystroem passes, the degree)
+    int build(glf_ctx *ctx, const GridInfo &g, KernelCoef coef, const uint8_t *d_img, int width, int height, int r0, int r1)
+    {
+        return build(ctx, g, coef, std::max(width, height), GridTargets{d_img, width, r0, r1 - r0, false});
     }
     bool can_skip(KernelCoef coef) const { return coef.s_loc > 0.f && radius < maxdim; }
 };

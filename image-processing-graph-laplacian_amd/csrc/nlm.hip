@@ -326,35 +326,33 @@ __global__ __launch_bounds__(256) void k_nlm_rows_sum(const double *__restrict__
     }
 }
 
-int nlm_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const uint8_t *d_mask,
-                 const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld, float *d_phi, int raster,
-                 double *d_c, float *kernel_ms)
+int nlm_nystroem(glf_ctx *ctx, const NysRequest &rq)
 {
-    const int64_t nwg = ceil_div(pix1 - pix0, 128);
+    const int64_t nwg = ceil_div(rq.pix1 - rq.pix0, 128);
     DevBuf<double> cpart;
-    if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * ld));
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * rq.ld));
     hipStream_t st = ctx->stream;
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     const NlmMask G = nlm_mask();
 #define GLF_NLM_GO(MB_)                                                                                                            \
-    hipLaunchKernelGGL((k_nlm_nystroem<MB_>), dim3((unsigned)nwg), dim3(256), 0, st, d_img, width, height, pix0, pix1, d_idx, p,   \
-                       coef.s_val, G, d_psi, d_phi, raster, d_mask, d_c ? cpart.p : nullptr)
-    switch (ld) {
+    hipLaunchKernelGGL((k_nlm_nystroem<MB_>), dim3((unsigned)nwg), dim3(256), 0, st, rq.d_img, rq.width, rq.height, rq.pix0, rq.pix1, rq.d_idx, rq.p,   \
+                       rq.coef.s_val, G, rq.d_psi, rq.d_phi, rq.raster, rq.d_mask, rq.d_c ? cpart.p : nullptr)
+    switch (rq.ld) {
     case 32: GLF_NLM_GO(1); break;
     case 64: GLF_NLM_GO(2); break;
     case 128: GLF_NLM_GO(4); break;
     case 256: GLF_NLM_GO(8); break;
-    default: return set_error(ctx, GLF_ERR_INVALID, "nlm_nystroem: ld=%u", ld);
+    default: return set_error(ctx, GLF_ERR_INVALID, "nlm_nystroem: ld=%u", rq.ld);
     }
 #undef GLF_NLM_GO
     GLF_LAUNCH_CHECK(ctx);
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
-    if (d_c) {
-        hipLaunchKernelGGL(k_nlm_rows_sum, dim3(1), dim3(256), 0, st, cpart.p, nwg, ld, d_c);
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    if (rq.d_c) {
+        hipLaunchKernelGGL(k_nlm_rows_sum, dim3(1), dim3(256), 0, st, cpart.p, nwg, rq.ld, rq.d_c);
         GLF_LAUNCH_CHECK(ctx);
     }
     GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
     return GLF_OK;
 }
 

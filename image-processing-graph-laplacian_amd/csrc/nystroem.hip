@@ -13,6 +13,7 @@
 // the Phi write (4 N m bytes) -- the kernel is MFMA-bound for m >= 64 and
 // VALU/transcendental-bound (kernel generation) below.
 #include "glf_internal.hpp"
+#include "scale_rule.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -332,39 +333,36 @@ struct NysWindow {
 };
 
 template <int MB, int PB, PixGen GEN = PixGen::Grey>
-static int launch_nystroem(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                           const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
-                           KernelCoef coef, const float *d_psi, float *d_phi, int raster, double *d_c, float *kernel_ms,
-                           int window, uint64_t *entries_evaluated)
+static int launch_nystroem(glf_ctx *ctx, const NysRequest &rq)
 {
     constexpr int LD = MB * 32;
-    const int64_t npix = pix1 - pix0;
+    const int64_t npix = rq.pix1 - rq.pix0;
     const int64_t nwg = ceil_div(npix, 4 * 32 * PB);
     DevBuf<double> cpart;
-    if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * LD));
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * LD));
     // f32 operands: K underflows to exactly 0 below 2^-149 (t > 150)
     NysWindow win;
-    GLF_TRY(win.init(ctx, d_samples, p, coef, window, 151.0, nwg));
+    GLF_TRY(win.init(ctx, rq.d_samples, rq.p, rq.coef, rq.window, 151.0, nwg));
     ctx->nys_note.skipping = win.radius >= 0;
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], ctx->stream));
     if (win.radius >= 0)
-        hipLaunchKernelGGL((k_nystroem<MB, PB, true, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
-                           d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, true, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, rq.d_img, rq.width, rq.pix0, rq.pix1,
+                           rq.d_samples, rq.p, rq.coef.s_loc, rq.coef.s_val, rq.d_psi, rq.d_phi, rq.raster, rq.d_mask, rq.d_idx, rq.d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     else
-        hipLaunchKernelGGL((k_nystroem<MB, PB, false, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, d_img, width, pix0, pix1,
-                           d_samples, p, coef.s_loc, coef.s_val, d_psi, d_phi, raster, d_mask, d_idx, d_c ? cpart.p : nullptr,
+        hipLaunchKernelGGL((k_nystroem<MB, PB, false, GEN>), dim3((unsigned)nwg), dim3(256), 0, ctx->stream, rq.d_img, rq.width, rq.pix0, rq.pix1,
+                           rq.d_samples, rq.p, rq.coef.s_loc, rq.coef.s_val, rq.d_psi, rq.d_phi, rq.raster, rq.d_mask, rq.d_idx, rq.d_c ? cpart.p : nullptr,
                            win.box.p, win.radius, win.visited.p);
     GLF_LAUNCH_CHECK(ctx);
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
-    if (entries_evaluated) { // listed chunks x 64 samples x the workgroup's pixels
-        GLF_TRY(win.total(ctx, nwg, entries_evaluated));
-        *entries_evaluated *= 64ull * (4 * 32 * PB);
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], ctx->stream));
+    if (rq.entries_evaluated) { // listed chunks x 64 samples x the workgroup's pixels
+        GLF_TRY(win.total(ctx, nwg, rq.entries_evaluated));
+        *rq.entries_evaluated *= 64ull * (4 * 32 * PB);
     }
-    if (d_c) GLF_TRY(sum_rows(ctx, cpart.p, nwg, LD, d_c, true));
-    if (kernel_ms) {
+    if (rq.d_c) GLF_TRY(sum_rows(ctx, cpart.p, nwg, LD, rq.d_c, true));
+    if (rq.kernel_ms) {
         GLF_HIP(ctx, hipEventSynchronize(ctx->ev[7]));
-        GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
+        GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
     }
     return GLF_OK;
 }
@@ -473,6 +471,38 @@ static void col_absmax(hipStream_t st, const float *psi, unsigned p, unsigned ld
     hipLaunchKernelGGL(k_col_absmax_part, dim3(nblk), dim3(256), 0, st, psi, p, ld, scratch);
     hipLaunchKernelGGL(k_col_absmax_fin, dim3(1), dim3(256), 0, st, scratch, nblk, ld, out);
 }
+
+// The power-of-two operand scales of one block X [p][ld] (scale_rule.hpp), on the device: no host round trip between the column
+// maxima and the kernels that read the scales. nr: the terms of the factored forms' intermediate sum (the sample grid's rows).
+static_assert(NYS_F16_KSCALE_LOG2 == (float)SCALE_KSCALE_LOG2, "scale_rule.hpp takes the kernels' 2^15 out again");
+__global__ void k_gridop_scales(const float *__restrict__ colmax, unsigned ld, int nr, float *__restrict__ colscale,
+                                float *__restrict__ tscale, float *__restrict__ tinv)
+{
+    const unsigned j = threadIdx.x;
+    if (j >= ld) return;
+    const OperandScales s = operand_scales(colmax[j], nr);
+    colscale[j] = s.colscale;
+    tscale[j] = s.tscale; // T arrives with the row pass' scales on it
+    tinv[j] = s.tinv;
+}
+// the buffers around the rule, sized for (p, ld), and its two steps: col_absmax, then the scales
+struct OperandScaleBufs {
+    DevBuf<float> colmax, camx, colscale, tscale, tinv;
+    int reserve(glf_ctx *ctx, unsigned p, unsigned ld)
+    {
+        GLF_TRY(colmax.alloc(ctx, ld));
+        GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld));
+        GLF_TRY(colscale.alloc(ctx, ld));
+        GLF_TRY(tscale.alloc(ctx, ld));
+        return tinv.alloc(ctx, ld);
+    }
+    // (queued on the stream; maxima: the block maxima the writer of X carried along, see ColMaxima)
+    void run(hipStream_t st, const float *X, unsigned p, unsigned ld, int nr, const ColMaxima *maxima = nullptr)
+    {
+        col_absmax(st, X, p, ld, camx.p, colmax.p, maxima);
+        hipLaunchKernelGGL(k_gridop_scales, dim3(1), dim3(256), 0, st, colmax.p, ld, nr, colscale.p, tscale.p, tinv.p);
+    }
+};
 
 // |a - b| + c in one instruction (hipcc expands __usad into max/min/sub/add)
 __device__ __forceinline__ unsigned sad_u32(unsigned a, unsigned b, unsigned c)
@@ -716,13 +746,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 8
 }
 
 template <int MB, int PB>
-static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
-                                KernelCoef coef, const float *d_psi, float *d_phi, int raster, double *d_c, float *kernel_ms,
-                                int window, uint64_t *entries_evaluated)
+static int launch_nystroem_f16s(glf_ctx *ctx, const NysRequest &rq)
 {
     constexpr unsigned LD = MB * 32;
-    const unsigned p_pad = (unsigned)round_up(p, NYS_PAD);
+    const unsigned p_pad = (unsigned)round_up(rq.p, NYS_PAD);
     hipStream_t st = ctx->stream;
     // per-column power-of-two scale T_j with |Psi| T_j < 2^14
     DevBuf<float> colmax, colscale, invscale, soa;
@@ -733,53 +760,47 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
     GLF_TRY(soa.alloc(ctx, (size_t)p_pad * 4));
     GLF_TRY(psi16.alloc(ctx, (size_t)p_pad * LD * 2));
     DevBuf<float> camx;
-    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * LD));
-    col_absmax(st, d_psi, p, LD, camx.p, colmax.p);
+    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(rq.p, CAM_ROWS) * LD));
+    col_absmax(st, rq.d_psi, rq.p, LD, camx.p, colmax.p);
     GLF_LAUNCH_CHECK(ctx);
     std::vector<float> hmax(LD), hscale(LD), hinv(LD);
     GLF_HIP(ctx, hipMemcpyAsync(hmax.data(), colmax.p, sizeof(float) * LD, hipMemcpyDeviceToHost, st));
     GLF_HIP(ctx, hipStreamSynchronize(st));
-    for (unsigned j = 0; j < LD; ++j) {
-        int e = 0;
-        if (hmax[j] > 0.f && std::isfinite(hmax[j])) {
-            (void)std::frexp(hmax[j], &e);   // hmax = f * 2^e, f in [0.5, 1)
-            e = 14 - e;                       // hmax * 2^e in [2^13, 2^14)
-        }
-        if (e > 100) e = 100;
-        if (e < -100) e = -100;
-        hscale[j] = std::ldexp(1.0f, e);
-        hinv[j] = std::ldexp(1.0f, -e - (int)NYS_F16_KSCALE_LOG2);
+    for (unsigned j = 0; j < LD; ++j) { // (on the host: see DESIGN.md beside the rule)
+        const OperandScales s = operand_scales(hmax[j], 1);
+        hscale[j] = s.colscale;
+        hinv[j] = s.inv;
     }
     GLF_HIP(ctx, hipMemcpyAsync(colscale.p, hscale.data(), sizeof(float) * LD, hipMemcpyHostToDevice, st));
     GLF_HIP(ctx, hipMemcpyAsync(invscale.p, hinv.data(), sizeof(float) * LD, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_psi_split_f16, dim3((unsigned)ceil_div((int64_t)p_pad * LD, 256)), dim3(256), 0, st, d_psi, p_pad, LD,
+    hipLaunchKernelGGL(k_psi_split_f16, dim3((unsigned)ceil_div((int64_t)p_pad * LD, 256)), dim3(256), 0, st, rq.d_psi, p_pad, LD,
                        colscale.p, psi16.p);
-    hipLaunchKernelGGL(k_samples_soa, dim3((p_pad + 255) / 256), dim3(256), 0, st, d_samples, p_pad, soa.p);
+    hipLaunchKernelGGL(k_samples_soa, dim3((p_pad + 255) / 256), dim3(256), 0, st, rq.d_samples, p_pad, soa.p);
     GLF_LAUNCH_CHECK(ctx);
 
     // Table-driven generation (k_nystroem_f16s<.., LUT = true>): needs each wave's 32 PB pixels inside one image
     // row, a spatial factor that reaches exact zero within NYS_LUT_RMAX, and LDS for two workgroups per CU.
     constexpr int NW_LUT = 8;
     int lut_r = 0;
-    if (MB <= 2 && coef.s_loc > 0.f && width % (32 * PB) == 0 && pix0 % (32 * PB) == 0 && !ctx->tune.nys_no_lut) {
+    if (MB <= 2 && rq.coef.s_loc > 0.f && rq.width % (32 * PB) == 0 && rq.pix0 % (32 * PB) == 0 && !ctx->tune.nys_no_lut) {
         // exp2(-s d^2) < 2^-150 rounds to +0 in f32
-        lut_r = (int)std::floor(std::sqrt(150.5 / (double)coef.s_loc)) + 1;
+        lut_r = (int)std::floor(std::sqrt(150.5 / (double)rq.coef.s_loc)) + 1;
         if (lut_r > NYS_LUT_RMAX) lut_r = 0;
     }
     const bool use_lut = lut_r > 0;
     const int nw = use_lut ? NW_LUT : 4;
-    const int64_t npix = pix1 - pix0;
+    const int64_t npix = rq.pix1 - rq.pix0;
     const int64_t nwg = ceil_div(npix, nw * 32 * PB);
     DevBuf<double> cpart;
-    if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * LD));
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nwg * LD));
     std::vector<float> hlut;
     DevBuf<float> dlut;
     if (use_lut) {
         const int lut_w = lut_r + 32 * PB, ne = 2 * lut_w + 1; // 32 PB zero entries of margin on both sides
         hlut.resize(256 + 2 * (size_t)ne);
-        for (int e = 0; e < 256; ++e) hlut[e] = (float)std::exp2(-(double)coef.s_val * e * e);
+        for (int e = 0; e < 256; ++e) hlut[e] = (float)std::exp2(-(double)rq.coef.s_val * e * e);
         for (int i = 0; i < ne; ++i) {
-            const double t = (double)coef.s_loc * (double)(i - lut_w) * (double)(i - lut_w);
+            const double t = (double)rq.coef.s_loc * (double)(i - lut_w) * (double)(i - lut_w);
             hlut[256 + i] = (float)std::exp2(-t);
             hlut[256 + ne + i] = (float)std::exp2((double)NYS_F16_KSCALE_LOG2 - t);
         }
@@ -788,14 +809,14 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
     }
     // K' = 2^15 K rounds to zero in f16 (hi and lo) below 2^-25: t > 40; 40.5 covers the f32 rounding of t
     NysWindow win;
-    GLF_TRY(win.init(ctx, d_samples, p, coef, window, 40.5, nwg, use_lut ? NYS_MAXCH_LUT : NYS_MAXCH));
+    GLF_TRY(win.init(ctx, rq.d_samples, rq.p, rq.coef, rq.window, 40.5, nwg, use_lut ? NYS_MAXCH_LUT : NYS_MAXCH));
     ctx->nys_note.skipping = win.radius >= 0;
     ctx->nys_note.lut = use_lut;
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
 #define GLF_NYS_LAUNCH(SKIP_, LUT_, NW_)                                                                                     \
-    hipLaunchKernelGGL((k_nystroem_f16s<MB, PB, SKIP_, LUT_, NW_>), dim3((unsigned)nwg), dim3(NW_ * 64), 0, st, d_img, width, \
-                       pix0, pix1, soa.p, p, coef.s_loc, coef.s_val, psi16.p, invscale.p, d_phi, raster, d_mask, d_idx,      \
-                       d_c ? cpart.p : nullptr, win.box.p, win.radius, win.visited.p, dlut.p, lut_r)
+    hipLaunchKernelGGL((k_nystroem_f16s<MB, PB, SKIP_, LUT_, NW_>), dim3((unsigned)nwg), dim3(NW_ * 64), 0, st, rq.d_img, rq.width, \
+                       rq.pix0, rq.pix1, soa.p, rq.p, rq.coef.s_loc, rq.coef.s_val, psi16.p, invscale.p, rq.d_phi, rq.raster, rq.d_mask, rq.d_idx,      \
+                       rq.d_c ? cpart.p : nullptr, win.box.p, win.radius, win.visited.p, dlut.p, lut_r)
     if constexpr (MB <= 2) {
         if (use_lut) {
             if (win.radius >= 0) GLF_NYS_LAUNCH(true, true, NW_LUT);
@@ -808,105 +829,79 @@ static int launch_nystroem_f16s(glf_ctx *ctx, const uint8_t *d_img, int width, i
     }
 #undef GLF_NYS_LAUNCH
     GLF_LAUNCH_CHECK(ctx);
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
-    if (entries_evaluated) { // listed chunks x 64 samples x the workgroup's pixels
-        GLF_TRY(win.total(ctx, nwg, entries_evaluated));
-        *entries_evaluated *= 64ull * (uint64_t)(nw * 32 * PB);
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    if (rq.entries_evaluated) { // listed chunks x 64 samples x the workgroup's pixels
+        GLF_TRY(win.total(ctx, nwg, rq.entries_evaluated));
+        *rq.entries_evaluated *= 64ull * (uint64_t)(nw * 32 * PB);
     }
-    if (d_c) GLF_TRY(sum_rows(ctx, cpart.p, nwg, LD, d_c, true));
+    if (rq.d_c) GLF_TRY(sum_rows(ctx, cpart.p, nwg, LD, rq.d_c, true));
     GLF_HIP(ctx, hipStreamSynchronize(st)); // hscale/hinv and the DevBufs go out of scope
-    if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
     return GLF_OK;
 }
 
 #include "grid_common.inc"
 #include "nystroem_grid.inc"
 
-// the f32-MFMA k_nystroem with a non-grey pixel format (no c = Phi^T y in its epilogue)
-template <PixGen GEN>
-static int nystroem_entrywise(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                              const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
-                              float *d_phi, int raster, float *kernel_ms, int window, uint64_t *entries_evaluated)
+// ld -> the (MB, PB) instantiation of the direct kernels: MB n-tiles of 32 columns, PB tiles of 32 pixels per wave. The split-f16
+// kernel (F16S) holds one pixel tile at 128 columns where the f32 kernel holds two. f(MB, PB) as integral constants.
+template <bool F16S, class F> static int nys_dispatch_ld(unsigned ld, F &&f)
 {
+    using std::integral_constant;
     switch (ld) {
-    case 32: return launch_nystroem<1, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
-    case 64: return launch_nystroem<2, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
-    case 128: return launch_nystroem<4, 2, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
-    case 256: return launch_nystroem<8, 1, GEN>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, nullptr, kernel_ms, window, entries_evaluated);
+    case 32: return f(integral_constant<int, 1>{}, integral_constant<int, 2>{});
+    case 64: return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+    case 128: return f(integral_constant<int, 4>{}, integral_constant<int, F16S ? 1 : 2>{});
+    case 256: return f(integral_constant<int, 8>{}, integral_constant<int, 1>{});
     }
     return GLF_ERR_UNSUPPORTED;
 }
 
-int nystroem_contract(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
-                      const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p,
-                      KernelCoef coef, float /*scale folded into psi*/, const float *d_psi, unsigned m, unsigned ld,
-                      float *d_phi, int raster, double *d_c, float *kernel_ms, int window, uint64_t *entries_evaluated,
-                      double *mfma_flops, int *path, RowpassStats *rowpass)
+int nystroem_contract(glf_ctx *ctx, const NysRequest &rq_in)
 {
+    NysRequest rq = rq_in;
+    rq.flt = nullptr;
     uint64_t entries_local = 0;
-    if (!entries_evaluated) entries_evaluated = &entries_local;
-    if (path) *path = 0;
-    if (mfma_flops) *mfma_flops = 0.0;
+    if (!rq.entries_evaluated) rq.entries_evaluated = &entries_local;
+    if (rq.path) *rq.path = 0;
+    if (rq.mfma_flops) *rq.mfma_flops = 0.0;
     ctx->nys_note.skipping = ctx->nys_note.lut = 0;
-    const int64_t N = (int64_t)width * height;
-    if (pix0 < 0 || pix1 > N || pix0 > pix1 || !valid_ld(ld) || m > ld)
-        return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: bad range or ld=%u", ld);
-    if (kernel_ms) *kernel_ms = 0.f;
-    if (pix0 == pix1) return GLF_OK;
-    if (coef.kernel == GLF_KERNEL_NLM) { // patch distances generated on the vector pipe, f32 MFMA contraction (nlm.hip)
-        *entries_evaluated = (uint64_t)p * (uint64_t)(pix1 - pix0);
-        if (mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
-        return nlm_nystroem(ctx, d_img, width, height, pix0, pix1, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c, kernel_ms);
-    }
-    int rc = GLF_ERR_UNSUPPORTED;
-    const PixGen gen = pixgen_of(coef.kernel);
-    if (gen != PixGen::Grey) {
-        // the colour and 16-bit formats: the band form where PIX_BAND asks for it and it applies (split f16, *path = 4), otherwise
-        // entry by entry, f32 MFMA (no grid or rank form)
-        if (ctx->tune.pix_band && !d_c) {
-            rc = nystroem_contract_grid(ctx, d_img, width, height, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, nullptr,
-                                        kernel_ms, window, entries_evaluated, mfma_flops, rowpass, path);
-            if (rc != GLF_ERR_UNSUPPORTED) return rc;
-            if (path) *path = 0;
-        }
-        if (d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour, 16-bit, float and float colour kernels have no 8-bit y for Phi^T y");
-        window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
-        pix_dispatch_raw(gen, [&](auto t) {
-            rc = nystroem_entrywise<t.G>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, kernel_ms, window,
-                                         entries_evaluated);
-        });
-        if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
+    const int64_t N = (int64_t)rq.width * rq.height;
+    if (rq.pix0 < 0 || rq.pix1 > N || rq.pix0 > rq.pix1 || !valid_ld(rq.ld) || rq.m > rq.ld)
+        return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: bad range or ld=%u", rq.ld);
+    if (rq.kernel_ms) *rq.kernel_ms = 0.f;
+    if (rq.pix0 == rq.pix1) return GLF_OK;
+    // the entry-by-entry forms' work: flops_per_entry_col MFMA flops per evaluated entry and column
+    auto direct_flops = [&](int rc, double flops_per_entry_col) {
+        if (rc == GLF_OK && rq.mfma_flops) *rq.mfma_flops = flops_per_entry_col * (double)*rq.entries_evaluated * rq.ld;
         return rc;
+    };
+    if (rq.coef.kernel == GLF_KERNEL_NLM) { // patch distances generated on the vector pipe, f32 MFMA contraction (nlm.hip)
+        *rq.entries_evaluated = (uint64_t)rq.p * (uint64_t)(rq.pix1 - rq.pix0);
+        (void)direct_flops(GLF_OK, 2.0);
+        return nlm_nystroem(ctx, rq);
     }
-    {
-        // a tensor-grid sample set (hpc/sampling.c always yields one) takes the factored contraction
-        const int rc = nystroem_contract_grid(ctx, d_img, width, height, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld,
-                                              d_phi, raster, d_c, kernel_ms, window, entries_evaluated, mfma_flops, rowpass, path);
+    const PixGen gen = pixgen_of(rq.coef.kernel);
+    // a tensor-grid sample set (hpc/sampling.c always yields one) takes the factored contraction. The colour, 16-bit and float
+    // formats: the band form where PIX_BAND asks for it and it applies (split f16, *path = 4), otherwise entry by entry, f32 MFMA
+    // (no grid or rank form)
+    if (gen == PixGen::Grey || (ctx->tune.pix_band && !rq.d_c)) {
+        const int rc = nystroem_contract_grid(ctx, rq);
         if (rc != GLF_ERR_UNSUPPORTED) return rc;
-        if (path) *path = 0;
+        if (rq.path) *rq.path = 0;
     }
-    if (ctx->contraction == GLF_CONTRACT_F16_SPLIT) {
-        switch (ld) {
-        case 32: rc = launch_nystroem_f16s<1, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-        case 64: rc = launch_nystroem_f16s<2, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-        case 128: rc = launch_nystroem_f16s<4, 1>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-        case 256: rc = launch_nystroem_f16s<8, 1>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-        }
-        if (rc == GLF_OK && mfma_flops) *mfma_flops = 6.0 * (double)*entries_evaluated * ld;
-        return rc;
+    if (gen != PixGen::Grey) {
+        if (rq.d_c) return set_error(ctx, GLF_ERR_INVALID, "nystroem_contract: the colour, 16-bit, float and float colour kernels have no 8-bit y for Phi^T y");
+        rq.window = 1; // chunks beyond the f32 underflow radius add exactly +0: always passed over (bit-identical)
+        int rc = GLF_ERR_UNSUPPORTED;
+        pix_dispatch_raw(gen, [&](auto t) {
+            rc = nys_dispatch_ld<false>(rq.ld, [&](auto mb, auto pb) { return launch_nystroem<mb(), pb(), t.G>(ctx, rq); });
+        });
+        return direct_flops(rc, 2.0);
     }
-    switch (ld) {
-    case 32:
-        rc = launch_nystroem<1, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-    case 64:
-        rc = launch_nystroem<2, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-    case 128:
-        rc = launch_nystroem<4, 2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-    case 256:
-        rc = launch_nystroem<8, 1>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, d_phi, raster, d_c, kernel_ms, window, entries_evaluated); break;
-    }
-    if (rc == GLF_OK && mfma_flops) *mfma_flops = 2.0 * (double)*entries_evaluated * ld;
-    return rc;
+    if (ctx->contraction == GLF_CONTRACT_F16_SPLIT)
+        return direct_flops(nys_dispatch_ld<true>(rq.ld, [&](auto mb, auto pb) { return launch_nystroem_f16s<mb(), pb()>(ctx, rq); }), 6.0);
+    return direct_flops(nys_dispatch_ld<false>(rq.ld, [&](auto mb, auto pb) { return launch_nystroem<mb(), pb()>(ctx, rq); }), 2.0);
 }
 
 // ---- sample rows: Phi[row(i)] = Phi_A[i]; c += Phi_A^T y_A -------------------------------------

@@ -110,16 +110,9 @@ __global__ __launch_bounds__(RED2_THREADS) void k_band_absmax_scales(const float
     wg_reduce_partials<float, 1, true>(part, nblk, ld, mx, sh);
     if (threadIdx.x < RED2_COLS) {
         const unsigned col = blockIdx.x * RED2_COLS + threadIdx.x;
-        const float m = mx[0];
-        int e = 0;
-        if (m > 0.f && isfinite(m)) {
-            int ex;
-            (void)frexpf(m, &ex);
-            e = 14 - ex;
-        }
-        e = max(-100, min(100, e));
-        colscale[col] = ldexpf(1.0f, e);
-        inv[col] = ldexpf(1.0f, -e - (int)NYS_F16_KSCALE_LOG2);
+        const OperandScales s = operand_scales(mx[0], 1); // (scale_rule.hpp)
+        colscale[col] = s.colscale;
+        inv[col] = s.inv;
     }
 }
 // the column maxima of X, then colscale / inv (two launches; one where the writer of X carried the block maxima along)
@@ -1018,109 +1011,91 @@ static void band_stats(RowpassStats *stats, const BandTables &bt, int row0, int 
 }
 
 // (nystroem_band_vec.inc: the fused filter contracted with q = Psi w, one column per plane)
-static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, const float *d_psi, unsigned ld, const BandFilter &flt,
-                                    float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats);
+static int launch_nystroem_band_vec(glf_ctx *ctx, const NysRequest &rq, const BandTables &bt);
 // (nystroem_band_sep.inc: the same sum in separable form, the photometric table as its rank-R expansion)
-static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
-                                    const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats);
+static int launch_nystroem_band_sep(glf_ctx *ctx, const NysRequest &rq, const BandTables &bt);
 
-// Nystroem extension of the image rows [pix0 / width, pix1 / width) in band form (see the head of this file)
-static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                                const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi,
-                                unsigned ld_total, float *d_phi, int raster, double *d_c, float *kernel_ms, uint64_t *entries_evaluated,
-                                double *mfma_flops, const GridInfo &g, int height, RowpassStats *stats, bool forced, const BandFilter *flt)
+// Nystroem extension of the image rows [pix0 / width, pix1 / width) in band form (see the head of this file). With rq.flt the
+// request names no Phi and no c (nystroem_band_filter sees to it).
+static int launch_nystroem_band(glf_ctx *ctx, const NysRequest &rq, const GridInfo &g, bool forced)
 {
     const BandTables *btp = nullptr;
-    GLF_TRY(band_tables_cached(ctx, g, coef, width, height, 32 * BAND_PB, true, &btp));
+    GLF_TRY(band_tables_cached(ctx, g, rq.coef, rq.width, rq.height, 32 * BAND_PB, true, &btp));
     const BandTables &bt = *btp;
-    if (!forced && !bt.narrow(height)) return GLF_ERR_UNSUPPORTED;
+    if (!forced && !bt.narrow(rq.height)) return GLF_ERR_UNSUPPORTED;
     hipStream_t st = ctx->stream;
-    const int row0 = (int)(pix0 / width), row1 = (int)(pix1 / width), nrows = row1 - row0;
-    const unsigned LD = ld_total >= 64 ? 64u : 32u, nblocks = ld_total / LD;
+    const int row0 = (int)(rq.pix0 / rq.width), row1 = (int)(rq.pix1 / rq.width), nrows = row1 - row0;
+    const unsigned LD = rq.ld >= 64 ? 64u : 32u, nblocks = rq.ld / LD;
     const int mb = (int)LD / 32;
     DevBuf<float> colscale, inv, camx;
     DevBuf<uint8_t> svals;
     DevBuf<unsigned> svals32; // (Rgb, U16, F32: the sample values as u32; float colour: three planes)
     DevBuf<unsigned char> chunks;
     DevBuf<double> cpart;
-    const PixGen gen = pixgen_of(coef.kernel);
+    const PixGen gen = pixgen_of(rq.coef.kernel);
     const bool raw = gen != PixGen::Grey;
-    if (raw && (flt || d_c)) return GLF_ERR_UNSUPPORTED; // (no 8-bit y: the filter stays a stage of its own)
-    if (flt && ld_total > 64) return GLF_ERR_UNSUPPORTED; // (the filter's dot product with w runs over one block of at most 64 columns)
+    if (raw && (rq.flt || rq.d_c)) return GLF_ERR_UNSUPPORTED; // (no 8-bit y: the filter stays a stage of its own)
+    if (rq.flt && rq.ld > 64) return GLF_ERR_UNSUPPORTED; // (the filter's dot product with w runs over one block of at most 64 columns)
     // FILTER_FORM: sep (separable rank-R form) where the photometric table has an expansion, else vec (pair by pair, one column per
     // plane instead of Phi's), else -- its LDS window too large -- k_band's epilogue
-    if (flt && ctx->tune.filter_form <= 1) {
-        const int rc = launch_nystroem_band_sep(ctx, bt, d_img, width, pix0, pix1, d_samples, d_mask, p, coef, d_psi, ld_total, *flt, kernel_ms,
-                                                entries_evaluated, mfma_flops, stats);
+    if (rq.flt && ctx->tune.filter_form <= 1) {
+        const int rc = launch_nystroem_band_sep(ctx, rq, bt);
         if (rc != GLF_ERR_UNSUPPORTED) return rc;
     }
-    if (flt && ctx->tune.filter_form <= 2) {
-        const int rc = launch_nystroem_band_vec(ctx, bt, d_img, width, pix0, pix1, d_samples, d_mask, p, d_psi, ld_total, *flt, kernel_ms,
-                                                entries_evaluated, mfma_flops, stats);
+    if (rq.flt && ctx->tune.filter_form <= 2) {
+        const int rc = launch_nystroem_band_vec(ctx, rq, bt);
         if (rc != GLF_ERR_UNSUPPORTED) return rc;
     }
     DevBuf<unsigned long long> dev_eval;
     ctx->nys_note.skipping = ctx->tune.band_noskip ? 0 : 1; // (the band is a window by construction; BAND_NOSKIP executes all of it)
-    GLF_TRY(colscale.alloc(ctx, ld_total));
-    GLF_TRY(inv.alloc(ctx, ld_total));
-    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    if (raw) GLF_TRY(svals32.alloc(ctx, (size_t)pix_desc(gen).svals32_planes * p));
+    GLF_TRY(colscale.alloc(ctx, rq.ld));
+    GLF_TRY(inv.alloc(ctx, rq.ld));
+    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(rq.p, CAM_ROWS) * rq.ld));
+    if (raw) GLF_TRY(svals32.alloc(ctx, (size_t)pix_desc(gen).svals32_planes * rq.p));
     GLF_TRY(chunks.alloc(ctx, (size_t)bt.nr * bt.ksc * band_chunk_bytes(mb)));
     const size_t wgs = band_px_wgs(bt, nrows);
-    if (flt) d_c = nullptr; // (c was needed before this launch: c_from_ysum)
-    if (d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, wgs * LD));
     GLF_TRY(band_eval_zero(ctx, dev_eval));
-    band_scales(st, d_psi, p, ld_total, camx.p, colscale.p, inv.p);
+    band_scales(st, rq.d_psi, rq.p, rq.ld, camx.p, colscale.p, inv.p);
     if (raw) {
-        hipLaunchKernelGGL(k_gridop_svals32, dim3((p + 255) / 256), dim3(256), 0, st, d_samples, p, pix_desc(gen).svals32_what, svals32.p);
+        hipLaunchKernelGGL(k_gridop_svals32, dim3((rq.p + 255) / 256), dim3(256), 0, st, rq.d_samples, rq.p, pix_desc(gen).svals32_what, svals32.p);
         GLF_LAUNCH_CHECK(ctx);
-    } else GLF_TRY(band_svals(ctx, d_samples, p, svals));
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
+    } else GLF_TRY(band_svals(ctx, rq.d_samples, rq.p, svals));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     float band_ms = 0.f;
+    CpTimer timer{ctx, rq.rowpass != nullptr};
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
-        GLF_TRY(band_prep(ctx, d_psi + c0, ld_total, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p, pix_desc(gen).svals32_planes));
-        const bool timed = stats && (int)cb < glf_ctx::CP_RING;
-        if (timed)
-            for (int q = 0; q < 2; ++q)
-                if (!ctx->cp_ev[q][cb]) GLF_HIP(ctx, hipEventCreate(&ctx->cp_ev[q][cb]));
-        hipEvent_t e0 = timed ? ctx->cp_ev[0][cb] : nullptr, e1 = timed ? ctx->cp_ev[1][cb] : nullptr;
-        if (timed) GLF_HIP(ctx, hipEventRecord(e0, st));
+        GLF_TRY(band_prep(ctx, rq.d_psi + c0, rq.ld, colscale.p + c0, raw ? (const void *)svals32.p : (const void *)svals.p, raw, bt.nr, bt.nc, bt.ksc, mb, chunks.p, pix_desc(gen).svals32_planes));
+        GLF_TRY(timer.start());
         if (raw) {
-            float *po = d_phi + c0;
-            const float nsval = -coef.s_val;
+            float *po = rq.d_phi + c0;
+            const float nsval = -rq.coef.s_val;
             int rc = GLF_OK;
             pix_dispatch_raw(gen, [&](auto t) { // (these formats' k_band exists for one and two column blocks only)
-                rc = mb == 2 ? launch_band_px<2, 0, t.G>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster,
-                                                         nullptr, dev_eval.p, nullptr, pix0, nsval)
-                             : launch_band_px<1, 0, t.G>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)ld_total, d_mask, d_idx, p, raster,
-                                                         nullptr, dev_eval.p, nullptr, pix0, nsval);
+                rc = mb == 2 ? launch_band_px<2, 0, t.G>(ctx, bt, rq.d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)rq.ld, rq.d_mask, rq.d_idx, rq.p, rq.raster,
+                                                         nullptr, dev_eval.p, nullptr, rq.pix0, nsval)
+                             : launch_band_px<1, 0, t.G>(ctx, bt, rq.d_img, row0, nrows, chunks.p, inv.p + c0, po, (int)rq.ld, rq.d_mask, rq.d_idx, rq.p, rq.raster,
+                                                         nullptr, dev_eval.p, nullptr, rq.pix0, nsval);
             });
             GLF_TRY(rc);
         } else if (mb == 2)
-            GLF_TRY(launch_band_px<2>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,
-                                      raster, d_c ? cpart.p : nullptr, dev_eval.p, flt, pix0));
+            GLF_TRY(launch_band_px<2>(ctx, bt, rq.d_img, row0, nrows, chunks.p, inv.p + c0, rq.flt ? nullptr : rq.d_phi + c0, (int)rq.ld, rq.d_mask, rq.d_idx, rq.p,
+                                      rq.raster, rq.d_c ? cpart.p : nullptr, dev_eval.p, rq.flt, rq.pix0));
         else
-            GLF_TRY(launch_band_px<1>(ctx, bt, d_img, row0, nrows, chunks.p, inv.p + c0, flt ? nullptr : d_phi + c0, (int)ld_total, d_mask, d_idx, p,
-                                      raster, d_c ? cpart.p : nullptr, dev_eval.p, flt, pix0));
-        if (timed) GLF_HIP(ctx, hipEventRecord(e1, st));
-        if (d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)wgs, LD, d_c + c0, true)); // synchronises
-        if (timed) {
-            GLF_HIP(ctx, hipEventSynchronize(e1));
-            float ms = 0.f;
-            GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-            band_ms += ms;
-        }
+            GLF_TRY(launch_band_px<1>(ctx, bt, rq.d_img, row0, nrows, chunks.p, inv.p + c0, rq.flt ? nullptr : rq.d_phi + c0, (int)rq.ld, rq.d_mask, rq.d_idx, rq.p,
+                                      rq.raster, rq.d_c ? cpart.p : nullptr, dev_eval.p, rq.flt, rq.pix0));
+        GLF_TRY(timer.stop());
+        if (rq.d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)wgs, LD, rq.d_c + c0, true)); // synchronises
     }
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     unsigned long long h_eval = 0;
-    GLF_TRY(band_eval_read(ctx, dev_eval, &h_eval));
-    if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
+    GLF_TRY(band_eval_read(ctx, dev_eval, &h_eval)); // (synchronises)
+    GLF_TRY(timer.total(&band_ms));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
     // (every column block evaluates the same entries: per block, h_eval / nblocks)
-    if (entries_evaluated) *entries_evaluated = (uint64_t)(h_eval / std::max(1u, nblocks));
-    if (mfma_flops) *mfma_flops = 6.0 * (double)h_eval * LD; // three split products per entry and column
-    band_stats(stats, bt, row0, row1, (int)nblocks, band_ms, ld_total, 0);
+    if (rq.entries_evaluated) *rq.entries_evaluated = (uint64_t)(h_eval / std::max(1u, nblocks));
+    if (rq.mfma_flops) *rq.mfma_flops = 6.0 * (double)h_eval * LD; // three split products per entry and column
+    band_stats(rq.rowpass, bt, row0, row1, (int)nblocks, band_ms, rq.ld, 0);
     return GLF_OK;
 }

@@ -317,17 +317,16 @@ static int band_sep_cols_launch(glf_ctx *ctx, const BandTables &bt, const uint8_
 // The fused filter of the image rows [pix0 / width, pix1 / width) in separable rank-R form: G, then per chunk of image rows the row
 // pass and the column pass. GLF_ERR_UNSUPPORTED: the photometric table has no expansion of at most RANK_MAX_R terms (R = 0: sharp
 // kernels), or more planes than instantiated -- k_band_vec runs then.
-static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
-                                    const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats)
+static int launch_nystroem_band_sep(glf_ctx *ctx, const NysRequest &rq, const BandTables &bt)
 {
-    const int row0 = (int)(pix0 / width), row1 = (int)(pix1 / width), nrows = row1 - row0;
+    const int row0 = (int)(rq.pix0 / rq.width), row1 = (int)(rq.pix1 / rq.width), nrows = row1 - row0;
+    const BandFilter &flt = *rq.flt;
     const int ncol = 1 + flt.sig.nsig;
-    if (ncol < 1 || ncol > BANDV_MAXNC || bt.width != width || p != (unsigned)bt.nr * (unsigned)bt.nc) return GLF_ERR_UNSUPPORTED;
+    if (ncol < 1 || ncol > BANDV_MAXNC || bt.width != rq.width || rq.p != (unsigned)bt.nr * (unsigned)bt.nc) return GLF_ERR_UNSUPPORTED;
     int R = 0;
     const float *ftab = nullptr;
     const _Float16 *Ff = nullptr;
-    GLF_TRY(rank_tables(ctx, coef, &R, &ftab, &Ff));
+    GLF_TRY(rank_tables(ctx, rq.coef, &R, &ftab, &Ff));
     if (R <= 0) return GLF_ERR_UNSUPPORTED;
     if (band_sep_lds_bytes(R, bt.rad) > BANDV_LDS_MAX) return GLF_ERR_UNSUPPORTED; // (R = 64: the F table alone is 66 KB)
     // S in chunks of whole workgroups' rows: everything at once where BSEP_S_BYTES and the pool allow, else halved
@@ -335,21 +334,21 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     int chunk = (int)std::min<size_t>((size_t)round_up(nrows, BAND_NW), std::max<size_t>(BAND_NW, BSEP_S_BYTES / row_bytes / BAND_NW * BAND_NW));
     DevBuf<uint8_t> svals;
     DevBuf<float> G, S, qpart, scl;
-    const unsigned gblocks = (p + 255) / 256;
+    const unsigned gblocks = (rq.p + 255) / 256;
     GLF_TRY(qpart.alloc(ctx, (size_t)gblocks * ncol));
     GLF_TRY(scl.alloc(ctx, 2 * BANDV_MAXNC));
-    GLF_TRY(G.alloc(ctx, (size_t)ncol * p * R));
+    GLF_TRY(G.alloc(ctx, (size_t)ncol * rq.p * R));
     while (S.alloc(ctx, (size_t)chunk * bt.nc * R * ncol) != GLF_OK) {
         if (chunk <= BAND_NW) return GLF_ERR_NOMEM;
         chunk = (int)round_up(chunk / 2, BAND_NW);
     }
-    GLF_TRY(band_svals(ctx, d_samples, p, svals));
+    GLF_TRY(band_svals(ctx, rq.d_samples, rq.p, svals));
     hipStream_t st = ctx->stream;
     hipEvent_t e0 = ctx->ev[6], e1 = ctx->ev[7];
     const bool noskip = ctx->tune.band_noskip;
     GLF_TRY(band_dispatch_planes(ncol, [&](auto nc_) -> int {
         constexpr int NC = decltype(nc_)::value;
-        hipLaunchKernelGGL(k_band_sep_g<NC>, dim3(gblocks), dim3(256), 0, st, d_psi, p, ld, flt.w, flt.sig.w, svals.p, ftab, R, G.p, qpart.p);
+        hipLaunchKernelGGL(k_band_sep_g<NC>, dim3(gblocks), dim3(256), 0, st, rq.d_psi, rq.p, rq.ld, flt.w, flt.sig.w, svals.p, ftab, R, G.p, qpart.p);
         GLF_LAUNCH_CHECK(ctx);
         hipLaunchKernelGGL(k_band_sep_scales, dim3(1), dim3(256), 0, st, qpart.p, (int)gblocks, NC, (float)bt.er15_rowsum, scl.p);
         GLF_LAUNCH_CHECK(ctx);
@@ -360,7 +359,7 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
             hipLaunchKernelGGL(k_band_sep_rows, dim3((E + 255) / 256, (unsigned)ceil_div(n, BSEP_RB)), dim3(256), 0, st, G.p, E, ncR, bt.nr, r0, r0 + n, r0,
                                bt.grow(), bt.tab(), bt.rad, bt.rowband_px(), noskip ? 1 : 0, S.p);
             GLF_LAUNCH_CHECK(ctx);
-            GLF_TRY(band_sep_cols_launch<NC>(ctx, bt, d_img, r0, n, r0, S.p, R, ftab, scl.p, d_mask, flt, pix0));
+            GLF_TRY(band_sep_cols_launch<NC>(ctx, bt, rq.d_img, r0, n, r0, S.p, R, ftab, scl.p, rq.d_mask, flt, rq.pix0));
         }
         GLF_HIP(ctx, hipEventRecord(e1, st));
         return GLF_OK;
@@ -368,13 +367,13 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
     GLF_HIP(ctx, hipStreamSynchronize(st));
     float ms = 0.f;
     GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-    if (kernel_ms) *kernel_ms = ms;
-    if (entries_evaluated) {
+    if (rq.kernel_ms) *rq.kernel_ms = ms;
+    if (rq.entries_evaluated) {
         // entries covered by the windows, from the plan: sum over the walking waves of (the 16 x 32 blocks of Ec the column pass
         // executes x band rows feeding them)
         uint64_t cols = 0, rows = 0;
-        for (int tc0 = 0; tc0 < width; tc0 += 32 * BSEP_PT)
-            cols += band_sep_tile_entries(bt.geom.cols.data(), bt.nc, width, tc0, 32 * BSEP_PT, bt.dc0(), bt.rad, noskip);
+        for (int tc0 = 0; tc0 < rq.width; tc0 += 32 * BSEP_PT)
+            cols += band_sep_tile_entries(bt.geom.cols.data(), bt.nc, rq.width, tc0, 32 * BSEP_PT, bt.dc0(), bt.rad, noskip);
         if (noskip) rows = (uint64_t)ceil_div(nrows, BAND_NW) * BAND_NW * (uint64_t)bt.nr; // every wave, every band row
         else
             for (int r = row0; r < row1; ++r) {
@@ -382,9 +381,9 @@ static int launch_nystroem_band_sep(glf_ctx *ctx, const BandTables &bt, const ui
                 band_rows_hull(bt.h_rowband_px.data(), r, 1, &alo, &ahi);
                 rows += (uint64_t)std::max(0, ahi - alo + 1);
             }
-        *entries_evaluated = cols * rows;
+        *rq.entries_evaluated = cols * rows;
     }
-    if (mfma_flops) *mfma_flops = 0.0;
-    band_stats(stats, bt, row0, row1, 1, ms, (unsigned)ncol, R);
+    if (rq.mfma_flops) *rq.mfma_flops = 0.0;
+    band_stats(rq.rowpass, bt, row0, row1, 1, ms, (unsigned)ncol, R);
     return GLF_OK;
 }

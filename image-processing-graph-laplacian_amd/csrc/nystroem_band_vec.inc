@@ -244,33 +244,32 @@ static void band_vec_caps(const BandTables &bt, int row0, int row1, int *wcap, i
 
 // The fused filter of the image rows [pix0 / width, pix1 / width) through k_band_vec: the sample values, q = Psi w (and the planes'),
 // one launch. GLF_ERR_UNSUPPORTED: the window of samples does not fit the LDS (the caller takes k_band's epilogue then).
-static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                    const float4 *d_samples, const uint8_t *d_mask, unsigned p, const float *d_psi, unsigned ld, const BandFilter &flt,
-                                    float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *stats)
+static int launch_nystroem_band_vec(glf_ctx *ctx, const NysRequest &rq, const BandTables &bt)
 {
-    const int row0 = (int)(pix0 / width), row1 = (int)(pix1 / width), nrows = row1 - row0;
+    const int row0 = (int)(rq.pix0 / rq.width), row1 = (int)(rq.pix1 / rq.width), nrows = row1 - row0;
+    const BandFilter &flt = *rq.flt;
     const int ncol = 1 + flt.sig.nsig;
-    if (ncol < 1 || ncol > BANDV_MAXNC || bt.width != width) return GLF_ERR_UNSUPPORTED;
+    if (ncol < 1 || ncol > BANDV_MAXNC || bt.width != rq.width) return GLF_ERR_UNSUPPORTED;
     int wcap = 0, nbcap = 0;
     band_vec_caps(bt, row0, row1, &wcap, &nbcap);
     const unsigned lds = band_vec_lds_bytes(ncol, bt.rad, wcap, nbcap);
     if (lds > BANDV_LDS_MAX) return GLF_ERR_UNSUPPORTED;
     hipStream_t st = ctx->stream;
-    const unsigned p32 = (unsigned)round_up(p, VEC_PAD);
+    const unsigned p32 = (unsigned)round_up(rq.p, VEC_PAD);
     DevBuf<uint8_t> svals;
     DevBuf<float> q;
     DevBuf<unsigned long long> dev_eval;
     GLF_TRY(q.alloc(ctx, (size_t)ncol * p32));
     GLF_TRY(band_eval_zero(ctx, dev_eval));
-    GLF_TRY(band_svals(ctx, d_samples, p, svals));
+    GLF_TRY(band_svals(ctx, rq.d_samples, rq.p, svals));
     hipEvent_t e0 = ctx->ev[6], e1 = ctx->ev[7];
     GLF_TRY(band_dispatch_planes(ncol, [&](auto nc_) -> int {
         constexpr int NC = decltype(nc_)::value;
-        hipLaunchKernelGGL(k_band_q<NC>, dim3((p32 + 255) / 256), dim3(256), 0, st, d_psi, p, p32, ld, flt.w, flt.sig.w, q.p);
+        hipLaunchKernelGGL(k_band_q<NC>, dim3((p32 + 255) / 256), dim3(256), 0, st, rq.d_psi, rq.p, p32, rq.ld, flt.w, flt.sig.w, q.p);
         const dim3 grid((unsigned)bt.ntiles_px, (unsigned)ceil_div(nrows, BAND_NW));
         (void)hipEventRecord(e0, st);
-        hipLaunchKernelGGL(k_band_vec<NC>, grid, dim3(BAND_NW * 64), lds, st, d_img, bt.width, row0, row1, bt.grow(), bt.gcol(), bt.nc, bt.tab(), bt.pexp(),
-                           bt.rad, bt.rowband_px(), bt.dcmax(), svals.p, q.p, p32, wcap, nbcap, d_mask, flt, pix0, ctx->tune.band_noskip ? 1 : 0, dev_eval.p);
+        hipLaunchKernelGGL(k_band_vec<NC>, grid, dim3(BAND_NW * 64), lds, st, rq.d_img, bt.width, row0, row1, bt.grow(), bt.gcol(), bt.nc, bt.tab(), bt.pexp(),
+                           bt.rad, bt.rowband_px(), bt.dcmax(), svals.p, q.p, p32, wcap, nbcap, rq.d_mask, flt, rq.pix0, ctx->tune.band_noskip ? 1 : 0, dev_eval.p);
         (void)hipEventRecord(e1, st);
         return GLF_OK;
     }));
@@ -279,9 +278,9 @@ static int launch_nystroem_band_vec(glf_ctx *ctx, const BandTables &bt, const ui
     GLF_TRY(band_eval_read(ctx, dev_eval, &h_eval));
     float ms = 0.f;
     GLF_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-    if (kernel_ms) *kernel_ms = ms;
-    if (entries_evaluated) *entries_evaluated = (uint64_t)h_eval; // wave-level entry steps x 64 lanes
-    if (mfma_flops) *mfma_flops = 0.0;
-    band_stats(stats, bt, row0, row1, 1, ms, (unsigned)ncol, 0);
+    if (rq.kernel_ms) *rq.kernel_ms = ms;
+    if (rq.entries_evaluated) *rq.entries_evaluated = (uint64_t)h_eval; // wave-level entry steps x 64 lanes
+    if (rq.mfma_flops) *rq.mfma_flops = 0.0;
+    band_stats(rq.rowpass, bt, row0, row1, 1, ms, (unsigned)ncol, 0);
     return GLF_OK;
 }

@@ -1030,87 +1030,166 @@ static int launch_rowpass_rt(glf_ctx *ctx, bool skip, const RowTiles &rt, const 
 #undef GLF_RT_GO
 }
 
+// The first row pass (k_grid_rowpass) of the target rows [rb, rb + nrp): its LDS, the instantiation, the split of the rows
+// over workgroups. OP: the L_A operator's sweep (the targets are grid rows).
+template <int NT, bool OP>
+static int launch_rowpass_v1(glf_ctx *ctx, bool skip, const _Float16 *Af, const float *Bp, const float *ermat, const unsigned long long *active,
+                             int nc, int ks, int rb, int nrp, const unsigned *pmask, float *T)
+{
+    constexpr int MT = GRID_MT;
+    const bool blds = ks <= GRID_KS_BLDS && GRID_MT <= 2;
+    const size_t lds = (size_t)ks * 2048 * MT + (blds ? (size_t)ks * NT * 2048 + GRID_NW * 2 * ER_PIECE * sizeof(float) : 0);
+    auto kern = blds ? (skip ? k_grid_rowpass<NT, true, MT, true, OP> : k_grid_rowpass<NT, false, MT, true, OP>)
+                     : (skip ? k_grid_rowpass<NT, true, MT, false, OP> : k_grid_rowpass<NT, false, MT, false, OP>);
+    GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // splits: enough workgroups to fill the chip several times over, at least one row per wave each
+    const int nwg_base = nc * (8 / MT);
+    int splits = std::max(1, std::min((int)ceil_div(nrp, GRID_NW), (int)ceil_div(256 * 8, nwg_base)));
+    const int rows_per_wg = (int)round_up((int)ceil_div(nrp, splits), GRID_NW); // whole rounds of the waves
+    splits = (int)ceil_div(nrp, rows_per_wg);
+    hipLaunchKernelGGL(kern, dim3(nc, 8 / MT, splits), dim3(GRID_NW * 64), lds, ctx->stream, Af, Bp, ermat, active, nc, ks, rb, nrp, rows_per_wg,
+                       pmask, T);
+    return GLF_OK;
+}
+
+// The Ec fragments of a column pass: per target column (the image's columns, or the listed ones: the grid's own for the L_A
+// operator), or -- a uniform grid of at most 32 pixels' pitch, unless NO_ECR -- the compact table, one fragment set per residue of
+// the pitch (hpc/sampling.c always yields a uniform grid; any tensor grid is accepted). zfrag: what a lane without a pixel reads.
+struct EcTable {
+    int dist = 0, off = 0, len = 0; // compact: the pitch (0: per column), the table's centre and length
+    DevBuf<_Float16> frag, zfrag;
+    int build(glf_ctx *ctx, const GridInfo &g, const float *etab, int maxdim, const int *d_gcol, int ntargets, const int *d_targets, bool compact)
+    {
+        const int nc = g.nc, ksc = (int)ceil_div(nc, 16);
+        dist = compact && nc >= 2 ? g.cols[1] - g.cols[0] : 0;
+        for (int b = 1; b < nc && dist > 0; ++b)
+            if (g.cols[b] != g.cols[0] + dist * b) dist = 0;
+        if (dist > 32 || ctx->tune.no_ecr) dist = 0;
+        off = (int)round_up(ntargets / std::max(1, dist) + 16, 8);
+        len = off + 16 * ksc + 16;
+        if (dist > 0) {
+            GLF_TRY(frag.alloc(ctx, (size_t)dist * 8 * 2 * len));
+            hipLaunchKernelGGL(k_grid_ecr, dim3((unsigned)ceil_div((int64_t)dist * 8 * len, 256)), dim3(256), 0, ctx->stream, etab, maxdim, dist, len,
+                               off, frag.p);
+        } else {
+            GLF_TRY(frag.alloc(ctx, (size_t)ntargets * ksc * 2 * 2 * 8));
+            hipLaunchKernelGGL(k_grid_ecfrag, dim3((unsigned)ceil_div((int64_t)ntargets * ksc * 2, 256)), dim3(256), 0, ctx->stream, etab, d_gcol,
+                               ntargets, d_targets, nc, ksc, frag.p);
+        }
+        return GLF_OK;
+    }
+    int build_zfrag(glf_ctx *ctx, int ksc)
+    {
+        GLF_TRY(zfrag.alloc(ctx, (size_t)(ksc * 4 + 4) * 8));
+        GLF_HIP(ctx, hipMemsetAsync(zfrag.p, 0, (size_t)(ksc * 4 + 4) * 16, ctx->stream));
+        return GLF_OK;
+    }
+};
+
+// The row passes of one Nystroem call timed launch by launch through the context's event ring (idle here: the eigensolver is
+// done). The ring's totals belong to the eigensolver's sweeps: end() (a timer that is on) takes this call's share back out.
+struct MvRingTimer {
+    glf_ctx *ctx;
+    bool on;
+    double ms0 = 0.0;
+    int count0 = 0;
+    int begin()
+    {
+        if (on) GLF_TRY(mv_collect(ctx));
+        ms0 = ctx->mv_ms;
+        count0 = ctx->mv_count;
+        return GLF_OK;
+    }
+    int start()
+    {
+        if (on && ctx->mv_pending == glf_ctx::MV_RING) GLF_TRY(mv_collect(ctx));
+        if (on) GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[0][ctx->mv_pending], ctx->stream));
+        return GLF_OK;
+    }
+    int stop()
+    {
+        if (on) GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[1][ctx->mv_pending++], ctx->stream));
+        return GLF_OK;
+    }
+    int end(float *ms)
+    {
+        GLF_TRY(mv_collect(ctx));
+        *ms = (float)(ctx->mv_ms - ms0);
+        ctx->mv_ms = ms0;
+        ctx->mv_count = count0;
+        return GLF_OK;
+    }
+};
+// The column-pass (band form: k_band) launches of one call, the first CP_RING of them timed by event pairs of their own, created on
+// first use. total(): with the stream synchronised.
+struct CpTimer {
+    glf_ctx *ctx;
+    bool on;
+    int n = 0;
+    bool timing = false;
+    int start()
+    {
+        timing = on && n < glf_ctx::CP_RING;
+        for (int q = 0; timing && q < 2; ++q)
+            if (!ctx->cp_ev[q][n]) GLF_HIP(ctx, hipEventCreate(&ctx->cp_ev[q][n]));
+        if (timing) GLF_HIP(ctx, hipEventRecord(ctx->cp_ev[0][n], ctx->stream));
+        return GLF_OK;
+    }
+    int stop()
+    {
+        if (timing) GLF_HIP(ctx, hipEventRecord(ctx->cp_ev[1][n++], ctx->stream));
+        return GLF_OK;
+    }
+    int total(float *sum)
+    {
+        for (int q = 0; q < n; ++q) {
+            float ms = 0.f;
+            GLF_HIP(ctx, hipEventElapsedTime(&ms, ctx->cp_ev[0][q], ctx->cp_ev[1][q]));
+            *sum += ms;
+        }
+        return GLF_OK;
+    }
+};
+
 // GLF_ERR_UNSUPPORTED = the caller runs the direct kernel instead (no error is recorded).
-// ld_total = row stride of Psi and Phi; the contraction runs per block of LD = 32 NT columns (ld_total / LD blocks share
+// rq.ld = row stride of Psi and Phi; the contraction runs per block of LD = 32 NT columns (rq.ld / LD blocks share
 // the grid tables, the A fragments and the T buffer).
 template <int NT>
-static int launch_nystroem_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1,
-                                const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef,
-                                const float *d_psi, unsigned ld_total, float *d_phi, int raster, double *d_c, float *kernel_ms,
-                                int window, uint64_t *entries_evaluated, double *mfma_flops, const GridInfo &g, int height,
-                                RowpassStats *rowpass_stats)
+static int launch_nystroem_grid(glf_ctx *ctx, const NysRequest &rq, const GridInfo &g)
 {
     constexpr unsigned LD = 32 * NT;
-    const unsigned nblocks = ld_total / LD;
+    const unsigned nblocks = rq.ld / LD;
     hipStream_t st = ctx->stream;
     const int nr = g.nr, nc = g.nc, ks = (int)ceil_div(nr, 16);
-    const int row0 = (int)(pix0 / width), row1 = (int)(pix1 / width), nrows = row1 - row0;
+    const int row0 = (int)(rq.pix0 / rq.width), row1 = (int)(rq.pix1 / rq.width), nrows = row1 - row0;
 
-    // column scales of Psi (as launch_nystroem_f16s): |Psi| T_j < 2^14; and of T: |T[..][n]| <= nr max|Psi[:, n]|
-    DevBuf<float> colmax, colscale, tscale, tinv;
-    GLF_TRY(colmax.alloc(ctx, ld_total));
-    GLF_TRY(colscale.alloc(ctx, ld_total));
-    GLF_TRY(tscale.alloc(ctx, ld_total));
-    GLF_TRY(tinv.alloc(ctx, ld_total));
-    DevBuf<float> camx;
-    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    col_absmax(st, d_psi, p, ld_total, camx.p, colmax.p);
+    // column scales of Psi (as launch_nystroem_f16s): |Psi| T_j < 2^14; and of T: |T[..][n]| <= nr max|Psi[:, n]|. T is stored as
+    // the row pass accumulated it (Psi scaled by 2^e, Er by 2^15): the column pass takes both out together with its own scale 2^et
+    // -- one power of two (the row pass' 128 multiplies per epilogue were a seventh of its stores' cost)
+    OperandScaleBufs sc;
+    GLF_TRY(sc.reserve(ctx, rq.p, rq.ld));
+    sc.run(st, rq.d_psi, rq.p, rq.ld, nr);
     GLF_LAUNCH_CHECK(ctx);
-    std::vector<float> hmax(ld_total), hscale(ld_total), hts(ld_total), hti(ld_total);
-    GLF_HIP(ctx, hipMemcpyAsync(hmax.data(), colmax.p, sizeof(float) * ld_total, hipMemcpyDeviceToHost, st));
-    GLF_HIP(ctx, hipStreamSynchronize(st));
-    auto pow2_below = [](float bound, int target) { // e with bound * 2^e in [2^(target-1), 2^target)
-        int e = 0;
-        if (bound > 0.f && std::isfinite(bound)) {
-            (void)std::frexp(bound, &e);
-            e = target - e;
-        }
-        return std::max(-100, std::min(100, e));
-    };
-    for (unsigned j = 0; j < ld_total; ++j) {
-        const int e = pow2_below(hmax[j], 14), et = pow2_below(hmax[j] * (float)nr, 14);
-        hscale[j] = std::ldexp(1.0f, e);
-        // T is stored as the row pass accumulated it (Psi scaled by 2^e, Er by 2^15): the column pass takes both out together
-        // with its own scale 2^et -- one power of two (the row pass' 128 multiplies per epilogue were a seventh of its stores' cost)
-        hts[j] = std::ldexp(1.0f, std::max(-126, std::min(126, et - e - (int)NYS_F16_KSCALE_LOG2)));
-        hti[j] = std::ldexp(1.0f, -et - (int)NYS_F16_KSCALE_LOG2);
-    }
-    GLF_HIP(ctx, hipMemcpyAsync(colscale.p, hscale.data(), sizeof(float) * ld_total, hipMemcpyHostToDevice, st));
-    GLF_HIP(ctx, hipMemcpyAsync(tscale.p, hts.data(), sizeof(float) * ld_total, hipMemcpyHostToDevice, st));
-    GLF_HIP(ctx, hipMemcpyAsync(tinv.p, hti.data(), sizeof(float) * ld_total, hipMemcpyHostToDevice, st));
 
     GridTables gt;
-    GLF_TRY(gt.build(ctx, g, coef, d_img, width, height, row0, row1));
+    GLF_TRY(gt.build(ctx, g, rq.coef, rq.d_img, rq.width, rq.height, row0, row1));
     const int radius = gt.radius;
     const int *d_gcol = gt.gcol();
     // operands that do not depend on the column block: Pm_b A fragments, Ec fragment table
     const int ksc = (int)ceil_div(nc, 16);
-    DevBuf<_Float16> Af, ecf;
+    DevBuf<_Float16> Af;
     DevBuf<float> Bp;
     GLF_TRY(Af.alloc(ctx, (size_t)nc * 8 * ks * 2 * 64 * 8));
     GLF_TRY(Bp.alloc(ctx, (size_t)nc * ks * NT * 512));
-    hipLaunchKernelGGL(k_grid_afrag, dim3((unsigned)ceil_div((int64_t)nc * 8 * ks * 64, 256)), dim3(256), 0, st, gt.ptab(), d_samples,
+    hipLaunchKernelGGL(k_grid_afrag, dim3((unsigned)ceil_div((int64_t)nc * 8 * ks * 64, 256)), dim3(256), 0, st, gt.ptab(), rq.d_samples,
                        nr, nc, ks, Af.p);
-    // uniform grid (hpc/sampling.c always; any tensor grid is accepted above): the compact fragment table
-    int ecr_dist = nc >= 2 ? g.cols[1] - g.cols[0] : 0;
-    for (int b = 1; b < nc && ecr_dist > 0; ++b)
-        if (g.cols[b] != g.cols[0] + ecr_dist * b) ecr_dist = 0;
-    if (ecr_dist > 32 || ctx->tune.no_ecr) ecr_dist = 0;
-    const int ecr_off = (int)round_up(width / std::max(1, ecr_dist) + 16, 8), ecr_len = ecr_off + 16 * ksc + 16;
-    if (ecr_dist > 0) {
-        GLF_TRY(ecf.alloc(ctx, (size_t)ecr_dist * 8 * 2 * ecr_len));
-        hipLaunchKernelGGL(k_grid_ecr, dim3((unsigned)ceil_div((int64_t)ecr_dist * 8 * ecr_len, 256)), dim3(256), 0, st, gt.etab(),
-                           gt.maxdim, ecr_dist, ecr_len, ecr_off, ecf.p);
-    } else {
-        GLF_TRY(ecf.alloc(ctx, (size_t)width * ksc * 2 * 2 * 8));
-        hipLaunchKernelGGL(k_grid_ecfrag, dim3((unsigned)ceil_div((int64_t)width * ksc * 2, 256)), dim3(256), 0, st, gt.etab(), d_gcol,
-                           width, nullptr, nc, ksc, ecf.p);
-    }
+    EcTable ec;
+    GLF_TRY(ec.build(ctx, g, gt.etab(), gt.maxdim, d_gcol, rq.width, nullptr, true));
     GLF_LAUNCH_CHECK(ctx);
 
     const bool use_rt = rowpass_rt_wanted(ctx);
     RowTiles rtl;
-    if (use_rt) GLF_TRY(rtl.build(ctx, gt.etab(), gt.grow(), nr, ks, row0, nrows, nullptr, gt.pmask.p, d_samples, nc));
+    if (use_rt) GLF_TRY(rtl.build(ctx, gt.etab(), gt.grow(), nr, ks, row0, nrows, nullptr, gt.pmask.p, rq.d_samples, nc));
 
     // passes over blocks of image rows
     const size_t t_row_bytes = (size_t)256 * nc * LD * sizeof(float);
@@ -1123,70 +1202,49 @@ static int launch_nystroem_grid(glf_ctx *ctx, const uint8_t *d_img, int width, i
         rows_pass = use_rt ? std::max(64, rows_pass / 128 * 64) : std::max(4, rows_pass / 2);
     }
     constexpr int CSPLIT = GRID_COLPASS_SPLIT; // workgroups per image row in the column pass
-    if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nrows * CSPLIT * LD));
-    constexpr int MT = GRID_MT;
-    const bool blds = ks <= GRID_KS_BLDS && GRID_MT <= 2;
-    const size_t lds_row = (size_t)ks * 2048 * MT + (blds ? (size_t)ks * NT * 2048 + GRID_NW * 2 * ER_PIECE * sizeof(float) : 0);
-    const bool skip = window && gt.can_skip(coef);
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nrows * CSPLIT * LD));
+    const bool skip = rq.window && gt.can_skip(rq.coef);
     ctx->nys_note.skipping = skip;
-    auto rowpass = blds ? (skip ? k_grid_rowpass<NT, true, MT, true, false> : k_grid_rowpass<NT, false, MT, true, false>)
-                        : (skip ? k_grid_rowpass<NT, true, MT, false, false> : k_grid_rowpass<NT, false, MT, false, false>);
-    auto colpass = ecr_dist > 0 ? (skip ? k_grid_colpass<NT, true, false, true> : k_grid_colpass<NT, false, false, true>)
-                                : (skip ? k_grid_colpass<NT, true, false, false> : k_grid_colpass<NT, false, false, false>);
-    GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rowpass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row));
-    if (rowpass_stats) GLF_TRY(mv_collect(ctx));
-    const double ring_ms0 = ctx->mv_ms;
-    const int ring_count0 = ctx->mv_count;
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
+    auto colpass = ec.dist > 0 ? (skip ? k_grid_colpass<NT, true, false, true> : k_grid_colpass<NT, false, false, true>)
+                               : (skip ? k_grid_colpass<NT, true, false, false> : k_grid_colpass<NT, false, false, false>);
+    MvRingTimer row_timer{ctx, rq.rowpass != nullptr};
+    GLF_TRY(row_timer.begin());
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
-        hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * NT * 128, 256)), dim3(256), 0, st, d_psi + c0,
-                           ld_total, colscale.p + c0, nr, nc, ks, NT, Bp.p);
+        hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * NT * 128, 256)), dim3(256), 0, st, rq.d_psi + c0,
+                           rq.ld, sc.colscale.p + c0, nr, nc, ks, NT, Bp.p);
         for (int rb = 0; rb < nrows; rb += rows_pass) {
             const int nrp = std::min(rows_pass, nrows - rb);
-            // splits: enough workgroups to fill the chip several times over, at least one row per wave each
-            const int nwg_base = nc * (8 / MT);
-            int splits = std::max(1, std::min((int)ceil_div(nrp, GRID_NW), (int)ceil_div(256 * 8, nwg_base)));
-            const int rows_per_wg = (int)round_up((int)ceil_div(nrp, splits), GRID_NW); // whole rounds of the waves
-            splits = (int)ceil_div(nrp, rows_per_wg);
-            // the row pass is timed launch by launch through the context's event ring (idle here: the eigensolver is done)
-            if (rowpass_stats && ctx->mv_pending == glf_ctx::MV_RING) GLF_TRY(mv_collect(ctx));
-            if (rowpass_stats) GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[0][ctx->mv_pending], st));
+            GLF_TRY(row_timer.start());
             if (use_rt)
                 GLF_TRY((launch_rowpass_rt<NT, false>(ctx, skip, rtl, Bp.p, gt.ptab(), nr, nc, ks, rb, nrp, T.p)));
             else
-                hipLaunchKernelGGL(rowpass, dim3(nc, 8 / MT, splits), dim3(GRID_NW * 64), lds_row, st, Af.p, Bp.p, gt.ermat.p, gt.active.p,
-                                   nc, ks, rb, nrp, rows_per_wg, gt.pmask.p, T.p);
-            if (rowpass_stats) {
-                GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[1][ctx->mv_pending], st));
-                ++ctx->mv_pending;
-                ++rowpass_stats->launches;
-                rowpass_stats->flops += 2.0 * nrp * 256.0 * nc * nr * LD;
+                GLF_TRY((launch_rowpass_v1<NT, false>(ctx, skip, Af.p, Bp.p, gt.ermat.p, gt.active.p, nc, ks, rb, nrp, gt.pmask.p, T.p)));
+            GLF_TRY(row_timer.stop());
+            if (rq.rowpass) {
+                ++rq.rowpass->launches;
+                rq.rowpass->flops += 2.0 * nrp * 256.0 * nc * nr * LD;
             }
-            hipLaunchKernelGGL(colpass, dim3(nrp, CSPLIT), dim3(256), colpass_lds_bytes(width), st, T.p, ecf.p, nc, ksc, d_gcol, radius, gt.scol.p, gt.goff.p, d_img,
-                               d_mask, d_idx, p, width, row0 + rb, row0, tscale.p + c0, tinv.p + c0, d_phi + c0, (int)ld_total,
-                               raster, d_c ? cpart.p + (size_t)rb * CSPLIT * LD : nullptr, nullptr, nullptr, 0.f, ecr_dist, g.cols[0],
-                               ecr_len, ecr_off);
+            hipLaunchKernelGGL(colpass, dim3(nrp, CSPLIT), dim3(256), colpass_lds_bytes(rq.width), st, T.p, ec.frag.p, nc, ksc, d_gcol, radius, gt.scol.p, gt.goff.p, rq.d_img,
+                               rq.d_mask, rq.d_idx, rq.p, rq.width, row0 + rb, row0, sc.tscale.p + c0, sc.tinv.p + c0, rq.d_phi + c0, (int)rq.ld,
+                               rq.raster, rq.d_c ? cpart.p + (size_t)rb * CSPLIT * LD : nullptr, nullptr, nullptr, 0.f, ec.dist, g.cols[0],
+                               ec.len, ec.off);
             GLF_LAUNCH_CHECK(ctx);
         }
-        if (d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)nrows * CSPLIT, LD, d_c + c0, true)); // synchronises: cpart is reused by the next block
+        if (rq.d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)nrows * CSPLIT, LD, rq.d_c + c0, true)); // synchronises: cpart is reused by the next block
     }
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
-    if (rowpass_stats) { // the ring's totals belong to the eigensolver's sweeps: take the row-pass share back out
-        GLF_TRY(mv_collect(ctx));
-        rowpass_stats->ms = (float)(ctx->mv_ms - ring_ms0);
-        ctx->mv_ms = ring_ms0;
-        ctx->mv_count = ring_count0;
-    }
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
+    if (rq.rowpass) GLF_TRY(row_timer.end(&rq.rowpass->ms));
 
     // work accounting (host side, from the grid geometry; closed forms, the loops are over grid rows / columns only)
-    double ksteps = (double)ks * nrows, entries = (double)nr * nrows * (double)nc * width;
+    double ksteps = (double)ks * nrows, entries = (double)nr * nrows * (double)nc * rq.width;
     if (skip) {
         double sum_cols = 0.0;
         for (int b = 0; b < nc; ++b)
-            sum_cols += std::max(0, std::min(width, g.cols[b] + radius) - std::max(0, g.cols[b] - radius + 1));
+            sum_cols += std::max(0, std::min(rq.width, g.cols[b] + radius) - std::max(0, g.cols[b] - radius + 1));
         double rows_in = 0.0;
         ksteps = 0.0;
         for (int kk = 0; kk < ks; ++kk) { // image rows for which k-step kk holds a non-zero Er: within radius of one of its grid rows
@@ -1203,89 +1261,80 @@ static int launch_nystroem_grid(glf_ctx *ctx, const uint8_t *d_img, int width, i
         for (int a = 0; a < nr; ++a) rows_in += std::max(0, std::min(row1, g.rows[a] + radius) - std::max(row0, g.rows[a] - radius + 1));
         entries = rows_in * sum_cols;
     }
-    if (entries_evaluated) *entries_evaluated = (uint64_t)entries; // kernel entries represented by the factored sums
-    if (mfma_flops) // row pass + column pass (every pixel takes part in one 32-row m-tile of its chunk), 3 split products
-        *mfma_flops = nblocks * 3.0 * 2.0 * LD * 16.0 * (ksteps * nc * 256.0 + (double)nrows * width * (double)ksc);
+    if (rq.entries_evaluated) *rq.entries_evaluated = (uint64_t)entries; // kernel entries represented by the factored sums
+    if (rq.mfma_flops) // row pass + column pass (every pixel takes part in one 32-row m-tile of its chunk), 3 split products
+        *rq.mfma_flops = nblocks * 3.0 * 2.0 * LD * 16.0 * (ksteps * nc * 256.0 + (double)nrows * rq.width * (double)ksc);
     return GLF_OK;
 }
 
 // rank form (nystroem_rank.inc): the photometric table as a rank-R expansion, T' formed in LDS
-static int launch_nystroem_rank(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                                const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi,
-                                unsigned ld_total, float *d_phi, int raster, double *d_c, float *kernel_ms, int window,
-                                uint64_t *entries_evaluated, double *mfma_flops, const GridInfo &g, int height,
-                                RowpassStats *rowpass_stats);
+static int launch_nystroem_rank(glf_ctx *ctx, const NysRequest &rq, const GridInfo &g);
 
-// band form (nystroem_band.inc): entry by entry, only the samples within the kernel's radius of each pixel
-static int launch_nystroem_band(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                                const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi,
-                                unsigned ld_total, float *d_phi, int raster, double *d_c, float *kernel_ms, uint64_t *entries_evaluated,
-                                double *mfma_flops, const GridInfo &g, int height, RowpassStats *stats, bool forced,
-                                const BandFilter *flt = nullptr);
+// band form (nystroem_band.inc): entry by entry, only the samples within the kernel's radius of each pixel. forced: NYS_PATH = band
+// (auto takes it only where the band is narrow); rq.flt: the filter fused into it
+static int launch_nystroem_band(glf_ctx *ctx, const NysRequest &rq, const GridInfo &g, bool forced);
 
-// *path: 1 = exact grid form, 3 = rank form, 4 = band form
-static int nystroem_contract_grid(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
-                                  const float4 *d_samples, const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef,
-                                  const float *d_psi, unsigned ld, float *d_phi, int raster, double *d_c, float *kernel_ms,
-                                  int window, uint64_t *entries_evaluated, double *mfma_flops, RowpassStats *rowpass_stats,
-                                  int *path)
+// the sample indices on the host (the caller's copy, or read back) as a tensor grid; false: they are none
+static int nys_detect_grid(glf_ctx *ctx, const NysRequest &rq, GridInfo &g, bool *is_grid)
 {
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(ctx->tune.nys_path, width) || !band_form_applies(ctx, coef.kernel))
-        return GLF_ERR_UNSUPPORTED;
-    // the colour and 16-bit kernels (PIX_BAND): the band form or nothing, one block of at most 64 columns, no c = Phi^T y
-    const bool band_only = !grey_levels_factor(coef.kernel);
-    if (band_only && (!(ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) || ld > 64 || d_c)) return GLF_ERR_UNSUPPORTED;
-    if (pix0 % width || pix1 % width || width > GRID_MAX_W || p < 4) return GLF_ERR_UNSUPPORTED;
-    std::vector<uint32_t> hidx(p);
-    GLF_HIP(ctx, hipMemcpyAsync(hidx.data(), d_idx, sizeof(uint32_t) * p, hipMemcpyDeviceToHost, ctx->stream));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    GridInfo g;
-    if (!detect_grid(hidx, width, g) || ceil_div(g.nr, 16) > GRID_MAX_KS) return GLF_ERR_UNSUPPORTED;
-    if (path) *path = 1;
-    if (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) { // auto | band: only the samples within the radius of each pixel
-        const int rc = launch_nystroem_band(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c,
-                                            kernel_ms, entries_evaluated, mfma_flops, g, height, rowpass_stats, ctx->tune.nys_path == 4);
-        if (rc != GLF_ERR_UNSUPPORTED) {
-            if (path) *path = 4;
-            return rc;
-        }
-    }
-    if (band_only) return GLF_ERR_UNSUPPORTED;
-    if (ctx->tune.nys_path == 0 || ctx->tune.nys_path == 3) { // auto | rank: the rank form when the photometric table allows it
-        const int rc = launch_nystroem_rank(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster,
-                                            d_c, kernel_ms, window, entries_evaluated, mfma_flops, g, height, rowpass_stats);
-        if (rc != GLF_ERR_UNSUPPORTED) {
-            if (path) *path = 3;
-            return rc;
-        }
-    }
-    if (ld >= 64) // 64 columns at a time (ld = 128, 256: two or four column blocks)
-        return launch_nystroem_grid<2>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c,
-                                       kernel_ms, window, entries_evaluated, mfma_flops, g, height, rowpass_stats);
-    return launch_nystroem_grid<1>(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, d_phi, raster, d_c,
-                                   kernel_ms, window, entries_evaluated, mfma_flops, g, height, rowpass_stats);
-}
-
-int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                         const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi, unsigned ld,
-                         const BandFilter &flt, float *kernel_ms, uint64_t *entries_evaluated, double *mfma_flops, int *path,
-                         RowpassStats *stats, const unsigned *h_idx)
-{
-    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !(ctx->tune.nys_path == 0 || ctx->tune.nys_path == 4) || !grey_levels_factor(coef.kernel) ||
-        !grid_path_wanted(ctx->tune.nys_path, width) || ld > 64)
-        return GLF_ERR_UNSUPPORTED;
-    if (pix0 % width || pix1 % width || width > GRID_MAX_W || p < 4 || pix0 >= pix1) return GLF_ERR_UNSUPPORTED;
-    std::vector<uint32_t> hidx(p);
-    if (h_idx) std::copy(h_idx, h_idx + p, hidx.begin());
+    std::vector<uint32_t> hidx(rq.p);
+    if (rq.h_idx) std::copy(rq.h_idx, rq.h_idx + rq.p, hidx.begin());
     else {
-        GLF_HIP(ctx, hipMemcpyAsync(hidx.data(), d_idx, sizeof(uint32_t) * p, hipMemcpyDeviceToHost, ctx->stream));
+        GLF_HIP(ctx, hipMemcpyAsync(hidx.data(), rq.d_idx, sizeof(uint32_t) * rq.p, hipMemcpyDeviceToHost, ctx->stream));
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
+    *is_grid = detect_grid(hidx, rq.width, g);
+    return GLF_OK;
+}
+
+// *path: 1 = exact grid form, 3 = rank form, 4 = band form
+static int nystroem_contract_grid(glf_ctx *ctx, const NysRequest &rq)
+{
+    const int nys_path = ctx->tune.nys_path;
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !grid_path_wanted(nys_path, rq.width) || !band_form_applies(ctx, rq.coef.kernel))
+        return GLF_ERR_UNSUPPORTED;
+    // the colour and 16-bit kernels (PIX_BAND): the band form or nothing, one block of at most 64 columns, no c = Phi^T y
+    const bool band_only = !grey_levels_factor(rq.coef.kernel);
+    if (band_only && (!(nys_path == 0 || nys_path == 4) || rq.ld > 64 || rq.d_c)) return GLF_ERR_UNSUPPORTED;
+    if (rq.pix0 % rq.width || rq.pix1 % rq.width || rq.width > GRID_MAX_W || rq.p < 4) return GLF_ERR_UNSUPPORTED;
     GridInfo g;
-    if (!detect_grid(hidx, width, g)) return GLF_ERR_UNSUPPORTED;
-    const int rc = launch_nystroem_band(ctx, d_img, width, pix0, pix1, d_samples, d_mask, d_idx, p, coef, d_psi, ld, nullptr, 1, nullptr, kernel_ms,
-                                        entries_evaluated, mfma_flops, g, height, stats, ctx->tune.nys_path == 4, &flt);
-    if (rc == GLF_OK && path) *path = 4;
+    bool is_grid = false;
+    GLF_TRY(nys_detect_grid(ctx, rq, g, &is_grid));
+    if (!is_grid || ceil_div(g.nr, 16) > GRID_MAX_KS) return GLF_ERR_UNSUPPORTED;
+    // a form that answers GLF_ERR_UNSUPPORTED leaves the request to the next one
+    auto ran = [&](int rc, int path) {
+        if (rc != GLF_ERR_UNSUPPORTED && rq.path) *rq.path = path;
+        return rc != GLF_ERR_UNSUPPORTED;
+    };
+    if (rq.path) *rq.path = 1;
+    int rc = GLF_ERR_UNSUPPORTED;
+    if (nys_path == 0 || nys_path == 4) // auto | band: only the samples within the radius of each pixel
+        if (ran(rc = launch_nystroem_band(ctx, rq, g, nys_path == 4), 4)) return rc;
+    if (band_only) return GLF_ERR_UNSUPPORTED;
+    if (nys_path == 0 || nys_path == 3) // auto | rank: the rank form when the photometric table allows it
+        if (ran(rc = launch_nystroem_rank(ctx, rq, g), 3)) return rc;
+    // 64 columns at a time (ld = 128, 256: two or four column blocks)
+    return rq.ld >= 64 ? launch_nystroem_grid<2>(ctx, rq, g) : launch_nystroem_grid<1>(ctx, rq, g);
+}
+
+int nystroem_band_filter(glf_ctx *ctx, const NysRequest &rq_in)
+{
+    const int nys_path = ctx->tune.nys_path;
+    if (!rq_in.flt) return set_error(ctx, GLF_ERR_INVALID, "nystroem_band_filter: no filter");
+    NysRequest rq = rq_in; // (Phi is not written and c was needed before this launch: c_from_ysum)
+    rq.d_phi = nullptr;
+    rq.d_c = nullptr;
+    rq.raster = 1;
+    if (ctx->contraction != GLF_CONTRACT_F16_SPLIT || !(nys_path == 0 || nys_path == 4) || !grey_levels_factor(rq.coef.kernel) ||
+        !grid_path_wanted(nys_path, rq.width) || rq.ld > 64)
+        return GLF_ERR_UNSUPPORTED;
+    if (rq.pix0 % rq.width || rq.pix1 % rq.width || rq.width > GRID_MAX_W || rq.p < 4 || rq.pix0 >= rq.pix1) return GLF_ERR_UNSUPPORTED;
+    GridInfo g;
+    bool is_grid = false;
+    GLF_TRY(nys_detect_grid(ctx, rq, g, &is_grid));
+    if (!is_grid) return GLF_ERR_UNSUPPORTED;
+    const int rc = launch_nystroem_band(ctx, rq, g, nys_path == 4);
+    if (rc == GLF_OK && rq.path) *rq.path = 4;
     return rc;
 }
 
@@ -1294,8 +1343,6 @@ int nystroem_band_filter(glf_ctx *ctx, const uint8_t *d_img, int width, int heig
 // the samples themselves as targets -- nr target rows instead of H image rows, so a sweep costs nr / H of a Nystroem row
 // pass (T: 5.6 GB at cfg4) instead of streaming the 29 GB of a stored L_A, and L_A is not stored at all.
 
-// power-of-two operand scales of one sweep from the column maxima of X (the device twin of the host code in
-// launch_nystroem_grid: |X| T < 2^14, |T| <= nr max|X| scaled below 2^14, results brought back exactly)
 // Y[s][n] = alpha (D_s X[s][n] - Y[s][n]) for the samples s in [s0, s1): Y holds (K_A X) from the column pass
 __global__ __launch_bounds__(256) void k_gridop_finish(float *__restrict__ Y, const float *__restrict__ X,
                                                         const double *__restrict__ degree, unsigned s0, unsigned s1, unsigned ld,
@@ -1314,27 +1361,6 @@ __global__ __launch_bounds__(256) void k_gridop_finish(float *__restrict__ Y, co
     y.z = alpha * fmaf(dg, x.z, -y.z);
     y.w = alpha * fmaf(dg, x.w, -y.w);
     reinterpret_cast<float4 *>(Y)[o] = y;
-}
-
-__global__ void k_gridop_scales(const float *__restrict__ colmax, unsigned ld, int nr, float *__restrict__ colscale,
-                                float *__restrict__ tscale, float *__restrict__ tinv)
-{
-    const unsigned j = threadIdx.x;
-    if (j >= ld) return;
-    const float m = colmax[j];
-    int e = 0, et = 0;
-    if (m > 0.f && isfinite(m)) {
-        int ex;
-        (void)frexpf(m, &ex);
-        e = 14 - ex;
-        (void)frexpf(m * (float)nr, &ex);
-        et = 14 - ex;
-    }
-    e = max(-100, min(100, e));
-    et = max(-100, min(100, et));
-    colscale[j] = ldexpf(1.0f, e);
-    tscale[j] = ldexpf(1.0f, max(-126, min(126, et - e - (int)NYS_F16_KSCALE_LOG2))); // T arrives with the row pass' scales on it
-    tinv[j] = ldexpf(1.0f, -et - (int)NYS_F16_KSCALE_LOG2);
 }
 
 // sample values as an nr x nc byte image (what k_grid_rowsort sorts per target row)
@@ -1370,14 +1396,15 @@ __global__ __launch_bounds__(256) void k_gridop_svals32(const float4 *__restrict
 struct glf::GridOp {
     glf::GridInfo g;
     unsigned p = 0;
-    int ks = 0, kp = 0, ksc = 0, radius = 0, radius16 = 0, maxdim = 0;
+    int ksc = 0;
     bool can_skip = false;
-    glf::DevBuf<float> tab, ermat, T, Bp, colmax, camx, colscale, tscale, tinv;
-    glf::DevBuf<int> grid;
-    glf::DevBuf<_Float16> Af, ecf;
-    glf::DevBuf<unsigned long long> active;
-    glf::DevBuf<unsigned short> scol;
-    glf::DevBuf<unsigned> goff, pmask;
+    // the factored forms' tables (none in band form): the Nystroem passes' own, over the nr x nc byte image of the sample values
+    // with the grid rows as target rows; the Ec fragments per grid column
+    glf::GridTables gt;
+    glf::EcTable ec;
+    glf::OperandScaleBufs sc;
+    glf::DevBuf<float> T, Bp;
+    glf::DevBuf<_Float16> Af;
     glf::DevBuf<uint8_t> svals;
     glf::DevBuf<unsigned> svals32; // the colour, 16-bit and float formats (band form only): the sample values as u32, in place of svals (float colour: three planes)
     glf::PixGen gen = glf::PixGen::Grey;
@@ -1391,7 +1418,6 @@ struct glf::GridOp {
     const _Float16 *rank_Ff = nullptr;
     glf::RankSegments rank_sg;
     glf::DevBuf<float> rank_S;
-    glf::DevBuf<_Float16> rank_zfrag;
     unsigned rank_ld = 0;
     int rank_nt = 0; // n-tiles per row of S the padding columns were last zeroed for
     // band form (nystroem_band.inc): only the samples within the kernel's radius of each target
@@ -1420,28 +1446,7 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
     op->g = g;
     op->p = p;
     const int nr = g.nr, nc = g.nc;
-    op->ks = (int)ceil_div(nr, 16);
-    op->kp = op->ks * 16;
     op->ksc = (int)ceil_div(nc, 16);
-    op->maxdim = std::max(width, height);
-    std::vector<float> htab(256 + (size_t)op->maxdim);
-    for (int e = 0; e < 256; ++e) htab[e] = (float)std::exp2(-(double)coef.s_val * e * e);
-    for (int d = 0; d < op->maxdim; ++d) htab[256 + d] = (float)std::exp2(-(double)coef.s_loc * (double)d * (double)d);
-    op->radius = op->maxdim;
-    for (int d = 0; d < op->maxdim; ++d)
-        if (htab[256 + d] == 0.f) {
-            op->radius = d;
-            break;
-        }
-    op->can_skip = coef.s_loc > 0.f && op->radius < op->maxdim;
-    op->radius16 = f16_zero_radius(htab.data() + 256, op->maxdim);
-    GLF_TRY(op->tab.alloc(ctx, htab.size()));
-    GLF_TRY(op->grid.alloc(ctx, (size_t)nr + nc));
-    GLF_HIP(ctx, hipMemcpyAsync(op->tab.p, htab.data(), sizeof(float) * htab.size(), hipMemcpyHostToDevice, st));
-    GLF_HIP(ctx, hipMemcpyAsync(op->grid.p, g.rows.data(), sizeof(int) * nr, hipMemcpyHostToDevice, st));
-    GLF_HIP(ctx, hipMemcpyAsync(op->grid.p + nr, g.cols.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st));
-    const float *ptab = op->tab.p, *etab = op->tab.p + 256;
-    const int *grow = op->grid.p, *gcol = op->grid.p + nr;
     op->gen = pixgen_of(coef.kernel);
     op->nsval = -coef.s_val;
     if (band_only) {
@@ -1459,39 +1464,32 @@ int grid_op_create(glf_ctx *ctx, const float4 *d_samples, const unsigned *h_idx,
         if (ctx->tune.mv_path == 4 && !op->use_band) return GLF_ERR_UNSUPPORTED;
     }
     if (band_only && !op->use_band) {
-        GLF_HIP(ctx, hipStreamSynchronize(st)); // htab is pageable host memory
+        GLF_HIP(ctx, hipStreamSynchronize(st));
         return GLF_ERR_UNSUPPORTED;
     }
     if (op->use_band) {
         op->d_samples = d_samples;
-        GLF_HIP(ctx, hipStreamSynchronize(st)); // htab is pageable host memory
+        GLF_HIP(ctx, hipStreamSynchronize(st));
         *out = op.release();
         return GLF_OK;
     }
-    GLF_TRY(op->Af.alloc(ctx, (size_t)nc * 8 * op->ks * 2 * 64 * 8));
-    GLF_TRY(op->ecf.alloc(ctx, (size_t)nc * op->ksc * 2 * 2 * 8));
-    GLF_TRY(op->ermat.alloc(ctx, (size_t)nr * op->kp));
-    GLF_TRY(op->active.alloc(ctx, (size_t)nr));
-    GLF_TRY(op->scol.alloc(ctx, (size_t)nr * nc));
-    GLF_TRY(op->goff.alloc(ctx, (size_t)nr * 257));
-    GLF_TRY(op->pmask.alloc(ctx, (size_t)nr * 8));
-    hipLaunchKernelGGL(k_grid_afrag, dim3((unsigned)ceil_div((int64_t)nc * 8 * op->ks * 64, 256)), dim3(256), 0, st, ptab, d_samples, nr,
-                       nc, op->ks, op->Af.p);
-    hipLaunchKernelGGL(k_grid_ecfrag, dim3((unsigned)ceil_div((int64_t)nc * op->ksc * 2, 256)), dim3(256), 0, st, etab, gcol, nc, gcol,
-                       nc, op->ksc, op->ecf.p);
-    hipLaunchKernelGGL(k_grid_ermat, dim3(nr), dim3(64), 0, st, etab, grow, nr, op->kp, 0, grow, op->ermat.p, op->active.p);
-    hipLaunchKernelGGL(k_grid_rowsort, dim3(nr), dim3(256), 0, st, op->svals.p, nc, 0, op->scol.p, op->goff.p, op->pmask.p);
+    GridTables &gt = op->gt;
+    GLF_TRY(gt.build(ctx, op->g, coef, std::max(width, height), GridTargets{op->svals.p, nc, 0, nr, true}, false));
+    op->can_skip = gt.can_skip(coef);
+    GLF_TRY(op->Af.alloc(ctx, (size_t)nc * 8 * gt.ks * 2 * 64 * 8));
+    hipLaunchKernelGGL(k_grid_afrag, dim3((unsigned)ceil_div((int64_t)nc * 8 * gt.ks * 64, 256)), dim3(256), 0, st, gt.ptab(), d_samples, nr, nc,
+                       gt.ks, op->Af.p);
+    GLF_TRY(op->ec.build(ctx, op->g, gt.etab(), gt.maxdim, gt.gcol(), nc, gt.gcol(), false));
     GLF_LAUNCH_CHECK(ctx);
-    if ((ctx->tune.mv_path == 0 || ctx->tune.mv_path == 3) && op->ks <= GRID_KS_BLDS) { // auto | rank
+    if ((ctx->tune.mv_path == 0 || ctx->tune.mv_path == 3) && gt.ks <= GRID_KS_BLDS) { // auto | rank
         GLF_TRY(rank_tables(ctx, coef, &op->rank_R, &op->rank_ftab, &op->rank_Ff));
         if (op->rank_R && !ctx->tune.sweep_samples) { // (only the value-grouped column pass needs the segments of the grid rows)
-            GLF_TRY(op->rank_sg.build(ctx, op->scol.p, op->goff.p, nr, nc, gcol, nc, op->ksc, true, op->radius16, nullptr, 0, 0, 0, 0));
-            GLF_TRY(op->rank_zfrag.alloc(ctx, (size_t)(op->ksc * 4 + 4) * 8));
-            GLF_HIP(ctx, hipMemsetAsync(op->rank_zfrag.p, 0, (size_t)(op->ksc * 4 + 4) * 16, st));
+            GLF_TRY(op->rank_sg.build(ctx, gt.scol.p, gt.goff.p, nr, nc, gt.gcol(), nc, op->ksc, true, gt.radius16, nullptr, 0, 0, 0, 0));
+            GLF_TRY(op->ec.build_zfrag(ctx, op->ksc));
         }
     }
     op->d_samples = d_samples; // the sample table outlives the operator (both belong to one image_processing call)
-    GLF_HIP(ctx, hipStreamSynchronize(st)); // htab is pageable host memory
+    GLF_HIP(ctx, hipStreamSynchronize(st)); // (the one of the call: the tables' uploads from op->g and gt.htab included)
     *out = op.release();
     return GLF_OK;
 }
@@ -1519,23 +1517,22 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
     if (ctx->tune.operand_maxima_sweep) maxima = nullptr;
     constexpr unsigned LD = 32 * NT;
     hipStream_t st = ctx->stream;
-    const int nr = op->g.nr, nc = op->g.nc, ks = op->ks, ksc = op->ksc;
+    const GridTables &gt = op->gt;
+    const int nr = op->g.nr, nc = op->g.nc, ks = gt.ks, ksc = op->ksc;
     const int a0 = (int)(row0 / nc), a1 = (int)(row1 / nc), nrows = a1 - a0;
     if (nrows <= 0) return GLF_OK;
     if (op->use_band) { // scales, operand chunks, one launch per 32 NT columns: Y = alpha (D X - K_A X) in the kernel's epilogue
         if (op->work_ld < ld_total) {
-            GLF_TRY(op->colmax.alloc(ctx, ld_total));
-            GLF_TRY(op->camx.alloc(ctx, (size_t)ceil_div(op->p, CAM_ROWS) * ld_total));
-            GLF_TRY(op->colscale.alloc(ctx, ld_total));
+            GLF_TRY(op->sc.reserve(ctx, op->p, ld_total));
             GLF_TRY(op->band_inv.alloc(ctx, ld_total));
             GLF_TRY(op->band_chunks.alloc(ctx, (size_t)nr * ksc * band_chunk_bytes(2)));
             op->work_ld = ld_total;
         }
-        band_scales(st, X, op->p, ld_total, op->camx.p, op->colscale.p, op->band_inv.p, maxima);
+        band_scales(st, X, op->p, ld_total, op->sc.camx.p, op->sc.colscale.p, op->band_inv.p, maxima);
         for (unsigned c0 = 0; c0 < ld_total; c0 += LD) {
             const bool raw = op->gen != PixGen::Grey;
             const uint8_t *sv = raw ? reinterpret_cast<const uint8_t *>(op->svals32.p) : op->svals.p;
-            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->colscale.p + c0, sv, raw, nr, nc, ksc, NT, op->band_chunks.p, pix_desc(op->gen).svals32_planes));
+            GLF_TRY(band_prep(ctx, X + c0, ld_total, op->sc.colscale.p + c0, sv, raw, nr, nc, ksc, NT, op->band_chunks.p, pix_desc(op->gen).svals32_planes));
             int rc = GLF_OK;
             pix_dispatch(op->gen, [&](auto t) {
                 rc = launch_band_samples<NT, t.G>(ctx, *op->band, sv, a0, nrows, op->band_chunks.p, op->band_inv.p + c0, Y + c0, (int)ld_total, X + c0,
@@ -1546,28 +1543,16 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         return GLF_OK;
     }
     if (op->work_ld < ld_total) { // (a narrower block -- the packed sweeps of block PCG -- reuses the wider block's buffers)
-        GLF_TRY(op->colmax.alloc(ctx, ld_total));
-        GLF_TRY(op->camx.alloc(ctx, (size_t)ceil_div(op->p, CAM_ROWS) * ld_total));
-        GLF_TRY(op->colscale.alloc(ctx, ld_total));
-        GLF_TRY(op->tscale.alloc(ctx, ld_total));
-        GLF_TRY(op->tinv.alloc(ctx, ld_total));
+        GLF_TRY(op->sc.reserve(ctx, op->p, ld_total));
         GLF_TRY(op->Bp.alloc(ctx, (size_t)nc * ks * NT * 512));
         if (!op->rank_R) GLF_TRY(op->T.alloc(ctx, (size_t)nr * 256 * nc * LD + GRID_T_PAD * LD));
         op->work_ld = ld_total;
     }
     // per-column power-of-two scales from max |X[:, n]| (device side: no host round trip inside the PCG loop)
-    col_absmax(st, X, op->p, ld_total, op->camx.p, op->colmax.p, maxima);
-    hipLaunchKernelGGL(k_gridop_scales, dim3(1), dim3(256), 0, st, op->colmax.p, ld_total, nr, op->colscale.p, op->tscale.p,
-                       op->tinv.p);
-    constexpr int MT = GRID_MT;
-    const bool blds = ks <= GRID_KS_BLDS && GRID_MT <= 2;
-    const size_t lds_row = (size_t)ks * 2048 * MT + (blds ? (size_t)ks * NT * 2048 + GRID_NW * 2 * ER_PIECE * sizeof(float) : 0);
+    op->sc.run(st, X, op->p, ld_total, nr, maxima);
     const bool skip = window && op->can_skip;
-    auto rowpass = blds ? (skip ? k_grid_rowpass<NT, true, MT, true, true> : k_grid_rowpass<NT, false, MT, true, true>)
-                        : (skip ? k_grid_rowpass<NT, true, MT, false, true> : k_grid_rowpass<NT, false, MT, false, true>);
     auto colpass = skip ? k_grid_colpass<NT, true, true> : k_grid_colpass<NT, false, true>;
-    GLF_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(rowpass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_row));
-    const int *gcol = op->grid.p + nr;
+    const int *gcol = gt.gcol();
     const bool use_rank = op->rank_R > 0;
     const bool use_rt = use_rank || ctx->tune.rowpass_op == 1; // rt | v1 (default: the sweeps have few target rows per B operand)
     const int ncs = ksc * 16;
@@ -1581,7 +1566,7 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         op->rank_nt = NT;
     }
     if (use_rt && (op->rtl_a0 != a0 || op->rtl_rows != nrows)) { // a rank applies the operator to the same grid rows every time
-        GLF_TRY(op->rtl.build(ctx, op->tab.p + 256, op->grid.p, nr, ks, 0, nrows, op->grid.p + a0, op->pmask.p + (size_t)a0 * 8, op->d_samples, nc));
+        GLF_TRY(op->rtl.build(ctx, gt.etab(), gt.grow(), nr, ks, 0, nrows, gt.grow() + a0, gt.pmask.p + (size_t)a0 * 8, op->d_samples, nc));
         op->rtl_a0 = a0;
         op->rtl_rows = nrows;
     }
@@ -1589,35 +1574,29 @@ static int grid_op_apply_nt(glf_ctx *ctx, GridOp *op, const float *X, float *Y, 
         if (use_rank) // one operand image per n-tile of 32 columns (the rank row pass takes one n-tile per workgroup)
             for (int t = 0; t < NT; ++t)
                 hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * 128, 256)), dim3(256), 0, st, X + c0 + 32 * t, ld_total,
-                                   op->colscale.p + c0 + 32 * t, nr, nc, ks, 1, op->Bp.p + (size_t)t * nc * ks * 512);
+                                   op->sc.colscale.p + c0 + 32 * t, nr, nc, ks, 1, op->Bp.p + (size_t)t * nc * ks * 512);
         else
             hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * NT * 128, 256)), dim3(256), 0, st, X + c0, ld_total,
-                               op->colscale.p + c0, nr, nc, ks, NT, op->Bp.p);
-        const int nwg_base = nc * (8 / MT);
-        int splits = std::max(1, std::min((int)ceil_div(nrows, GRID_NW), (int)ceil_div(256 * 8, nwg_base)));
-        const int rows_per_wg = (int)round_up((int)ceil_div(nrows, splits), GRID_NW); // whole rounds of the waves
-        splits = (int)ceil_div(nrows, rows_per_wg);
+                               op->sc.colscale.p + c0, nr, nc, ks, NT, op->Bp.p);
         if (use_rank) {
             // S[a'][n-tile][b][k][32] for the grid rows of this rank, then T' and the Ec contraction per (grid row, segment)
             GLF_TRY((launch_rowpass_rank<true>(ctx, skip, op->rtl, op->Bp.p, op->rank_ftab, op->rank_R, NT, nr, nc, ks, ncs, 0, nrows,
-                                                   op->rank_S.p, op->tscale.p + c0)));
+                                                   op->rank_S.p, op->sc.tscale.p + c0)));
             if (!ctx->tune.sweep_samples) // (default) the value-grouped column pass of the Nystroem stage on the samples
-                GLF_TRY((launch_rank_colpass<true>(ctx, op->rank_R, false, op->rank_S.p, ncs, NT, op->rank_Ff, op->ecf.p, op->rank_zfrag.p, nc, ksc,
-                                                   op->rank_sg, a0, nrows, nullptr, op->p, nc, a0, op->tinv.p + c0, Y + c0, (int)ld_total, 1,
+                GLF_TRY((launch_rank_colpass<true>(ctx, op->rank_R, false, op->rank_S.p, ncs, NT, op->rank_Ff, op->ec.frag.p, op->ec.zfrag.p, nc, ksc,
+                                                   op->rank_sg, a0, nrows, nullptr, op->p, nc, a0, op->sc.tinv.p + c0, Y + c0, (int)ld_total, 1,
                                                    nullptr)));
             else
-                GLF_TRY(launch_rank_samples(ctx, op->rank_R, op->rank_S.p, ncs, NT, op->rank_ftab, op->svals.p, op->tab.p + 256, gcol, nc, a0,
-                                            nrows, op->tinv.p + c0, Y + c0, (int)ld_total));
+                GLF_TRY(launch_rank_samples(ctx, op->rank_R, op->rank_S.p, ncs, NT, op->rank_ftab, op->svals.p, gt.etab(), gcol, nc, a0,
+                                            nrows, op->sc.tinv.p + c0, Y + c0, (int)ld_total));
             continue;
         }
         if (use_rt)
-            GLF_TRY((launch_rowpass_rt<NT, true>(ctx, skip, op->rtl, op->Bp.p, op->tab.p, nr, nc, ks, 0, nrows,
-                                                 op->T.p)));
+            GLF_TRY((launch_rowpass_rt<NT, true>(ctx, skip, op->rtl, op->Bp.p, gt.ptab(), nr, nc, ks, 0, nrows, op->T.p)));
         else
-            hipLaunchKernelGGL(rowpass, dim3(nc, 8 / MT, splits), dim3(GRID_NW * 64), lds_row, st, op->Af.p, op->Bp.p, op->ermat.p,
-                               op->active.p, nc, ks, a0, nrows, rows_per_wg, op->pmask.p, op->T.p);
-        hipLaunchKernelGGL(colpass, dim3(nrows, GRID_COLPASS_SPLIT_OP), dim3(256), colpass_lds_bytes(nc), st, op->T.p, op->ecf.p, nc, ksc, gcol, op->radius, op->scol.p, op->goff.p,
-                           nullptr, nullptr, nullptr, op->p, nc, a0, 0, op->tscale.p + c0, op->tinv.p + c0, Y + c0, (int)ld_total, 1,
+            GLF_TRY((launch_rowpass_v1<NT, true>(ctx, skip, op->Af.p, op->Bp.p, gt.ermat.p, gt.active.p, nc, ks, a0, nrows, gt.pmask.p, op->T.p)));
+        hipLaunchKernelGGL(colpass, dim3(nrows, GRID_COLPASS_SPLIT_OP), dim3(256), colpass_lds_bytes(nc), st, op->T.p, op->ec.frag.p, nc, ksc, gcol, gt.radius, gt.scol.p, gt.goff.p,
+                           nullptr, nullptr, nullptr, op->p, nc, a0, 0, op->sc.tscale.p + c0, op->sc.tinv.p + c0, Y + c0, (int)ld_total, 1,
                            nullptr, X + c0, d_degree, (float)alpha, 0, 0, 0, 0);
     }
     hipLaunchKernelGGL(k_gridop_finish, dim3((unsigned)ceil_div((int64_t)nrows * nc * (ld_total / 4), 256)), dim3(256), 0, st, Y, X,

@@ -1303,62 +1303,38 @@ static int launch_rank_colpass(glf_ctx *ctx, int R, bool ecr, const float *S, in
 constexpr size_t RANK_S_BYTES = 24ull << 30; // HBM for S per pass (cfg4: 10.2 GB for the whole image)
 
 // The Nystroem contraction in rank form; GLF_ERR_UNSUPPORTED = the caller runs the exact grid form instead.
-static int launch_nystroem_rank(glf_ctx *ctx, const uint8_t *d_img, int width, int64_t pix0, int64_t pix1, const float4 *d_samples,
-                                const uint8_t *d_mask, const uint32_t *d_idx, unsigned p, KernelCoef coef, const float *d_psi,
-                                unsigned ld_total, float *d_phi, int raster, double *d_c, float *kernel_ms, int window,
-                                uint64_t *entries_evaluated, double *mfma_flops, const GridInfo &g, int height,
-                                RowpassStats *rowpass_stats)
+static int launch_nystroem_rank(glf_ctx *ctx, const NysRequest &rq, const GridInfo &g)
 {
     int R = 0;
     const float *ftab = nullptr;
     const _Float16 *Ff = nullptr;
-    GLF_TRY(rank_tables(ctx, coef, &R, &ftab, &Ff));
+    GLF_TRY(rank_tables(ctx, rq.coef, &R, &ftab, &Ff));
     const int nr = g.nr, nc = g.nc, ks = (int)ceil_div(nr, 16), ksc = (int)ceil_div(nc, 16), ncs = ksc * 16;
     if (!R || ks > GRID_KS_BLDS) return GLF_ERR_UNSUPPORTED;
     constexpr int NT = 2; // the row pass produces 64 columns at a time (32: its second n-tile is padding of Psi)
-    const unsigned LD = ld_total >= 64 ? 64u : 32u, ntt = LD / 32, nblocks = ld_total / LD;
+    const unsigned LD = rq.ld >= 64 ? 64u : 32u, ntt = LD / 32, nblocks = rq.ld / LD;
     hipStream_t st = ctx->stream;
-    const int row0 = (int)(pix0 / width), row1 = (int)(pix1 / width), nrows = row1 - row0;
+    const int row0 = (int)(rq.pix0 / rq.width), row1 = (int)(rq.pix1 / rq.width), nrows = row1 - row0;
 
     // column scales of Psi and of the intermediates, as launch_nystroem_grid (|S|, |T'| <= nr max|Psi| since sum_k |f_k f_k| <= 1)
-    DevBuf<float> colmax, colscale, tscale, tinv, camx;
-    GLF_TRY(colmax.alloc(ctx, ld_total));
-    GLF_TRY(colscale.alloc(ctx, ld_total));
-    GLF_TRY(tscale.alloc(ctx, ld_total));
-    GLF_TRY(tinv.alloc(ctx, ld_total));
-    GLF_TRY(camx.alloc(ctx, (size_t)ceil_div(p, CAM_ROWS) * ld_total));
-    col_absmax(st, d_psi, p, ld_total, camx.p, colmax.p);
-    hipLaunchKernelGGL(k_gridop_scales, dim3(1), dim3(256), 0, st, colmax.p, ld_total, nr, colscale.p, tscale.p, tinv.p);
+    OperandScaleBufs sc;
+    GLF_TRY(sc.reserve(ctx, rq.p, rq.ld));
+    sc.run(st, rq.d_psi, rq.p, rq.ld, nr);
     GLF_LAUNCH_CHECK(ctx);
 
     GridTables gt;
-    GLF_TRY(gt.build(ctx, g, coef, d_img, width, height, row0, row1));
+    GLF_TRY(gt.build(ctx, g, rq.coef, rq.d_img, rq.width, rq.height, row0, row1));
     const int *d_gcol = gt.gcol();
-    DevBuf<_Float16> ecf;
     DevBuf<float> Bp;
     GLF_TRY(Bp.alloc(ctx, (size_t)nc * ks * NT * 512));
-    int ecr_dist = nc >= 2 ? g.cols[1] - g.cols[0] : 0;
-    for (int b = 1; b < nc && ecr_dist > 0; ++b)
-        if (g.cols[b] != g.cols[0] + ecr_dist * b) ecr_dist = 0;
-    if (ecr_dist > 32 || ctx->tune.no_ecr) ecr_dist = 0;
-    const int ecr_off = (int)round_up(width / std::max(1, ecr_dist) + 16, 8), ecr_len = ecr_off + 16 * ksc + 16;
-    if (ecr_dist > 0) {
-        GLF_TRY(ecf.alloc(ctx, (size_t)ecr_dist * 8 * 2 * ecr_len));
-        hipLaunchKernelGGL(k_grid_ecr, dim3((unsigned)ceil_div((int64_t)ecr_dist * 8 * ecr_len, 256)), dim3(256), 0, st, gt.etab(),
-                           gt.maxdim, ecr_dist, ecr_len, ecr_off, ecf.p);
-    } else {
-        GLF_TRY(ecf.alloc(ctx, (size_t)width * ksc * 2 * 2 * 8));
-        hipLaunchKernelGGL(k_grid_ecfrag, dim3((unsigned)ceil_div((int64_t)width * ksc * 2, 256)), dim3(256), 0, st, gt.etab(), d_gcol,
-                           width, nullptr, nc, ksc, ecf.p);
-    }
-    DevBuf<_Float16> zfrag; // what a lane without a pixel reads as its Ec fragments
-    GLF_TRY(zfrag.alloc(ctx, (size_t)(ksc * 4 + 4) * 8));
-    GLF_HIP(ctx, hipMemsetAsync(zfrag.p, 0, (size_t)(ksc * 4 + 4) * 16, st));
+    EcTable ec;
+    GLF_TRY(ec.build(ctx, g, gt.etab(), gt.maxdim, d_gcol, rq.width, nullptr, true));
+    GLF_TRY(ec.build_zfrag(ctx, ksc));
     RowTiles rtl;
-    GLF_TRY(rtl.build(ctx, gt.etab(), gt.grow(), nr, ks, row0, nrows, nullptr, gt.pmask.p, d_samples, nc));
+    GLF_TRY(rtl.build(ctx, gt.etab(), gt.grow(), nr, ks, row0, nrows, nullptr, gt.pmask.p, rq.d_samples, nc));
     RankSegments sg;
-    GLF_TRY(sg.build(ctx, gt.scol.p, gt.goff.p, nrows, width, d_gcol, nc, ksc, false, gt.radius16, d_mask + (size_t)row0 * width, ecr_dist,
-                     g.cols[0], ecr_len, ecr_off));
+    GLF_TRY(sg.build(ctx, gt.scol.p, gt.goff.p, nrows, rq.width, d_gcol, nc, ksc, false, gt.radius16, rq.d_mask + (size_t)row0 * rq.width, ec.dist,
+                     g.cols[0], ec.len, ec.off));
     GLF_LAUNCH_CHECK(ctx);
 
     const size_t s_row_floats = (size_t)ntt * ncs * R * 32;
@@ -1370,77 +1346,59 @@ static int launch_nystroem_rank(glf_ctx *ctx, const uint8_t *d_img, int width, i
         rows_pass = std::max(64, rows_pass / 128 * 64);
     }
     GLF_TRY(rank_zero_pad(ctx, S.p, (int)round_up(rows_pass, 64), (int)ntt, nc, ncs, R));
-    if (d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nrows * sg.nseg_max * LD));
-    const bool skip = window && gt.can_skip(coef);
+    if (rq.d_c) GLF_TRY(cpart.alloc(ctx, (size_t)nrows * sg.nseg_max * LD));
+    const bool skip = rq.window && gt.can_skip(rq.coef);
     ctx->nys_note.skipping = skip;
-    if (rowpass_stats) GLF_TRY(mv_collect(ctx));
-    const double ring_ms0 = ctx->mv_ms;
-    const int ring_count0 = ctx->mv_count;
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
-    int ncp = 0; // timed column-pass launches
+    MvRingTimer row_timer{ctx, rq.rowpass != nullptr};
+    CpTimer col_timer{ctx, rq.rowpass != nullptr};
+    GLF_TRY(row_timer.begin());
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[6], st));
     for (unsigned cb = 0; cb < nblocks; ++cb) {
         const unsigned c0 = cb * LD;
         for (unsigned t = 0; t < ntt; ++t) // one operand image per n-tile of 32 columns
-            hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * 128, 256)), dim3(256), 0, st, d_psi + c0 + 32 * t,
-                               ld_total, colscale.p + c0 + 32 * t, nr, nc, ks, 1, Bp.p + (size_t)t * nc * ks * 512);
+            hipLaunchKernelGGL(k_grid_bprep, dim3((unsigned)ceil_div((int64_t)nc * ks * 128, 256)), dim3(256), 0, st, rq.d_psi + c0 + 32 * t,
+                               rq.ld, sc.colscale.p + c0 + 32 * t, nr, nc, ks, 1, Bp.p + (size_t)t * nc * ks * 512);
         for (int rb = 0; rb < nrows; rb += rows_pass) {
             const int nrp = std::min(rows_pass, nrows - rb);
-            if (rowpass_stats && ctx->mv_pending == glf_ctx::MV_RING) GLF_TRY(mv_collect(ctx));
-            if (rowpass_stats) GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[0][ctx->mv_pending], st));
-            GLF_TRY((launch_rowpass_rank<false>(ctx, skip, rtl, Bp.p, ftab, R, (int)ntt, nr, nc, ks, ncs, rb, nrp, S.p, tscale.p + c0)));
-            if (rowpass_stats) {
-                GLF_HIP(ctx, hipEventRecord(ctx->mv_ev[1][ctx->mv_pending], st));
-                ++ctx->mv_pending;
-                ++rowpass_stats->launches;
-                rowpass_stats->flops += 2.0 * nrp * (double)R * nc * nr * LD;
+            GLF_TRY(row_timer.start());
+            GLF_TRY((launch_rowpass_rank<false>(ctx, skip, rtl, Bp.p, ftab, R, (int)ntt, nr, nc, ks, ncs, rb, nrp, S.p, sc.tscale.p + c0)));
+            GLF_TRY(row_timer.stop());
+            if (rq.rowpass) {
+                ++rq.rowpass->launches;
+                rq.rowpass->flops += 2.0 * nrp * (double)R * nc * nr * LD;
             }
-            const bool tcp = rowpass_stats && ncp < glf_ctx::CP_RING;
-            if (tcp) {
-                for (int q = 0; q < 2; ++q)
-                    if (!ctx->cp_ev[q][ncp]) GLF_HIP(ctx, hipEventCreate(&ctx->cp_ev[q][ncp]));
-                GLF_HIP(ctx, hipEventRecord(ctx->cp_ev[0][ncp], st));
-            }
-            GLF_TRY((launch_rank_colpass<false>(ctx, R, ecr_dist > 0, S.p, ncs, (int)ntt, Ff, ecf.p, zfrag.p, nc, ksc, sg, rb, nrp, d_idx, p,
-                                                width, row0 + rb, tinv.p + c0, d_phi + c0, (int)ld_total, raster,
-                                                d_c ? cpart.p + (size_t)rb * sg.nseg_max * LD : nullptr)));
-            if (tcp) {
-                GLF_HIP(ctx, hipEventRecord(ctx->cp_ev[1][ncp], st));
-                ++ncp;
-            }
+            GLF_TRY(col_timer.start());
+            GLF_TRY((launch_rank_colpass<false>(ctx, R, ec.dist > 0, S.p, ncs, (int)ntt, Ff, ec.frag.p, ec.zfrag.p, nc, ksc, sg, rb, nrp, rq.d_idx, rq.p,
+                                                rq.width, row0 + rb, sc.tinv.p + c0, rq.d_phi + c0, (int)rq.ld, rq.raster,
+                                                rq.d_c ? cpart.p + (size_t)rb * sg.nseg_max * LD : nullptr)));
+            GLF_TRY(col_timer.stop());
             GLF_LAUNCH_CHECK(ctx);
         }
-        if (d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)nrows * sg.nseg_max, LD, d_c + c0, true)); // synchronises
+        if (rq.d_c) GLF_TRY(sum_rows(ctx, cpart.p, (int64_t)nrows * sg.nseg_max, LD, rq.d_c + c0, true)); // synchronises
     }
-    if (kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventRecord(ctx->ev[7], st));
     GLF_HIP(ctx, hipStreamSynchronize(st));
-    if (kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(kernel_ms, ctx->ev[6], ctx->ev[7]));
-    if (rowpass_stats) {
-        GLF_TRY(mv_collect(ctx));
-        rowpass_stats->ms = (float)(ctx->mv_ms - ring_ms0);
-        ctx->mv_ms = ring_ms0;
-        ctx->mv_count = ring_count0;
-        for (int q = 0; q < ncp; ++q) {
-            float ms = 0.f;
-            GLF_HIP(ctx, hipEventElapsedTime(&ms, ctx->cp_ev[0][q], ctx->cp_ev[1][q]));
-            rowpass_stats->col_ms += ms;
-        }
-        rowpass_stats->col_launches = ncp;
-        rowpass_stats->rank_R = R;
+    if (rq.kernel_ms) GLF_HIP(ctx, hipEventElapsedTime(rq.kernel_ms, ctx->ev[6], ctx->ev[7]));
+    if (rq.rowpass) {
+        GLF_TRY(row_timer.end(&rq.rowpass->ms));
+        GLF_TRY(col_timer.total(&rq.rowpass->col_ms));
+        rq.rowpass->col_launches = col_timer.n; // the timed ones
+        rq.rowpass->rank_R = R;
         // T' for the (row, value) pairs that occur, then the Ec contraction per pixel; one product per multiply-add
         int pairs = 0;
         GLF_HIP(ctx, hipMemcpy(&pairs, sg.dpairs.p, sizeof(int), hipMemcpyDeviceToHost));
-        rowpass_stats->col_flops = (double)nblocks * 2.0 * LD * ncs * ((double)pairs * R + (double)nrows * width);
+        rq.rowpass->col_flops = (double)nblocks * 2.0 * LD * ncs * ((double)pairs * R + (double)nrows * rq.width);
     }
-    if (entries_evaluated) { // kernel entries the factored sums stand for (skipping: the row pass leaves out the grid rows beyond the f32 radius)
+    if (rq.entries_evaluated) { // kernel entries the factored sums stand for (skipping: the row pass leaves out the grid rows beyond the f32 radius)
         double rows_in = (double)nr * nrows;
         if (skip) {
             rows_in = 0.0;
             for (int a = 0; a < nr; ++a) rows_in += std::max(0, std::min(row1, g.rows[a] + gt.radius) - std::max(row0, g.rows[a] - gt.radius + 1));
         }
-        *entries_evaluated = (uint64_t)(rows_in * (double)nc * width);
+        *rq.entries_evaluated = (uint64_t)(rows_in * (double)nc * rq.width);
     }
-    if (mfma_flops) // row pass + T' (all 256 values of a row at most, whole m-tiles) + column pass, 3 split products each
-        *mfma_flops = (double)nblocks * 3.0 * 2.0 * LD * ((double)nrows * ks * 16.0 * nc * R + (double)nrows * 256.0 * R * ncs +
-                                                           (double)nrows * width * (double)ncs);
+    if (rq.mfma_flops) // row pass + T' (all 256 values of a row at most, whole m-tiles) + column pass, 3 split products each
+        *rq.mfma_flops = (double)nblocks * 3.0 * 2.0 * LD * ((double)nrows * ks * 16.0 * nc * R + (double)nrows * 256.0 * R * ncs +
+                                                           (double)nrows * rq.width * (double)ncs);
     return GLF_OK;
 }

@@ -453,6 +453,12 @@ int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const 
         info->row1 = all_rows ? (unsigned)B->height : row1;
         info->entries_evaluated = (double)evaluated;
     };
+    NysRequest rq; // (sample-first rows; the operand and Phi differ between the two branches below)
+    rq.d_img = B->img; rq.width = B->width; rq.height = B->height;
+    rq.d_mask = B->mask; rq.d_idx = B->idx;
+    rq.d_samples = reinterpret_cast<const float4 *>(B->samples); rq.p = p; rq.coef = make_coef(B->kernel, B->h_loc, B->h_val);
+    rq.window = window;
+    rq.path = &path;
     if (wide_ld(ld)) { // more than 256 eigenvectors: one 256-column panel of Phi at a time (columns are independent)
         const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS), p64 = (unsigned)round_up(p, NYS_PAD);
         DevBuf<float> pa, psiw, phip;
@@ -461,7 +467,9 @@ int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const 
         GLF_TRY(phip.alloc(ctx, (size_t)N * PANEL_COLS));
         GLF_TRY(glf_mat_create_dense(ctx, phi, N, m, ld));
         phi->row_order = GLF_ROWS_SAMPLE_FIRST;
-        const KernelCoef coefw = make_coef(B->kernel, B->h_loc, B->h_val);
+        rq.pix1 = N;
+        rq.d_psi = psiw.p; rq.ld = PANEL_COLS;
+        rq.d_phi = phip.p;
         for (unsigned q = 0; q < npan; ++q) {
             const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
             GLF_HIP(ctx, hipMemsetAsync(pa.p, 0, sizeof(float) * (size_t)p64 * PANEL_COLS, ctx->stream));
@@ -471,8 +479,8 @@ int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const 
                                Pi_A_Inv->data + (size_t)q * PANEL_COLS, p, PANEL_COLS, mq, B->scale, psiw.p);
             GLF_LAUNCH_CHECK(ctx);
             uint64_t ev = 0;
-            GLF_TRY(nystroem_contract(ctx, B->img, B->width, B->height, 0, N, reinterpret_cast<const float4 *>(B->samples), B->mask, B->idx, p,
-                                      coefw, B->scale, psiw.p, mq, PANEL_COLS, phip.p, 0, nullptr, nullptr, window, &ev, nullptr, &path));
+            rq.m = mq; rq.entries_evaluated = &ev;
+            GLF_TRY(nystroem_contract(ctx, rq));
             evaluated += ev; // (every panel evaluates K_B again)
             GLF_TRY(scatter_sample_rows(ctx, pa.p, p, PANEL_COLS, B->idx, phip.p, 0, B->img, nullptr, mq));
             GLF_TRY(unpack_panel(ctx, phip.p, ld, N, q, phi->data));
@@ -491,9 +499,11 @@ int glf_Nystroem_ex(glf_ctx *ctx, const glf_mat *B, const glf_mat *phi_A, const 
         GLF_TRY(glf_mat_create_dense(ctx, phi, N, m, ld));
         phi->row_order = GLF_ROWS_SAMPLE_FIRST;
     }
-    const KernelCoef coef = make_coef(B->kernel, B->h_loc, B->h_val);
-    GLF_TRY(nystroem_contract(ctx, B->img, B->width, B->height, pix0, pix1, reinterpret_cast<const float4 *>(B->samples), B->mask,
-                              B->idx, p, coef, B->scale, psi.p, m, ld, phi->data, 0, nullptr, nullptr, window, &evaluated, nullptr, &path));
+    rq.pix0 = pix0; rq.pix1 = pix1;
+    rq.d_psi = psi.p; rq.m = m; rq.ld = ld;
+    rq.d_phi = phi->data;
+    rq.entries_evaluated = &evaluated;
+    GLF_TRY(nystroem_contract(ctx, rq));
     GLF_TRY(scatter_sample_rows(ctx, phi_A->data, p, ld, B->idx, phi->data, 0, B->img, nullptr, m));
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     report();
@@ -1034,6 +1044,19 @@ static int finish_stats(glf_ctx *ctx, glf_stats &S, int first, glf_stats *stats)
     return GLF_OK;
 }
 
+// This rank's Nystroem request as far as the image, its pixel range and the sample tables settle it, Phi's rows at their pixels
+// (raster); the operand, the outputs and the report are the caller's to name
+static NysRequest nys_request(const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1, const SampleTables &tb, unsigned p,
+                              KernelCoef coef)
+{
+    NysRequest rq;
+    rq.d_img = d_img; rq.width = width; rq.height = height;
+    rq.pix0 = pix0; rq.pix1 = pix1;
+    rq.d_mask = tb.mask.p; rq.d_idx = tb.idx.p; rq.raster = 1;
+    rq.d_samples = tb.samples.p; rq.p = p; rq.coef = coef;
+    return rq;
+}
+
 // More than 256 eigenpairs, from the eigenpairs on. Panels of 256 vectors: the eigen-solve once (eigen.hip "panels"), then Nystroem,
 // Phi^T y and the filter's correction one panel at a time -- only one [pixels][256] block of Phi exists at any moment.
 static int run_wide_panels(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int width, int height, int64_t pix0, int64_t pix1,
@@ -1084,8 +1107,11 @@ static int run_wide_panels(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img,
         GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * PANEL_COLS, st));
         float kms = 0.f;
         uint64_t evaluated = 0;
-        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, P.coef, (float)(-alpha), psi.p, mq,
-                                  PANEL_COLS, phi_base, 1, c.p, &kms, opt.skip_exact_zeros, &evaluated, nullptr, &S.nystroem_path, nullptr));
+        NysRequest rq = nys_request(d_img, width, height, pix0, pix1, tb, p, P.coef);
+        rq.d_psi = psi.p; rq.m = mq; rq.ld = PANEL_COLS;
+        rq.d_phi = phi_base; rq.d_c = c.p; rq.window = opt.skip_exact_zeros;
+        rq.kernel_ms = &kms; rq.entries_evaluated = &evaluated; rq.path = &S.nystroem_path;
+        GLF_TRY(nystroem_contract(ctx, rq));
         kms_total += kms;
         S.nystroem_evaluated += (double)evaluated;
         if (si1 > si0)
@@ -1121,8 +1147,10 @@ static int filter_planes(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, i
     if (fused) {
         GLF_TRY(phis.alloc(ctx, (size_t)(pix1 - pix0) * ld));
         phi_rows = phis.p - (size_t)pix0 * ld;
-        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, P.coef, (float)(-alpha), d_psi, m, ld,
-                                  phi_rows, 1, nullptr, nullptr, P.opt.skip_exact_zeros));
+        NysRequest rq = nys_request(d_img, width, height, pix0, pix1, tb, p, P.coef);
+        rq.d_psi = d_psi; rq.m = m; rq.ld = ld;
+        rq.d_phi = phi_rows; rq.window = P.opt.skip_exact_zeros;
+        GLF_TRY(nystroem_contract(ctx, rq));
         if (si1 > si0) GLF_TRY(scatter_sample_rows(ctx, d_phiA + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
     }
     auto rule = [&](const double *hc, float *hw) { filter_weights_row(P.opt, m, lam.data(), hG.data(), ld, hc, hw); };
@@ -1419,8 +1447,13 @@ int glf::run_planned(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int w
         // grid detection, cached tables -- then overlaps a kernel instead of following the long one)
         GLF_TRY(filter_sample_rows(ctx, phiA.p + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, d_img, w.p, P.gain, P.ysub, d_out, d_zf,
                                    cap ? cap->d_corr : nullptr, pix0));
-        const int rc = nystroem_band_filter(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, psi.p, ld, flt, &kms,
-                                            &evaluated, &S.nystroem_mfma_flops, &S.nystroem_path, &rps, h_idx);
+        NysRequest rq = nys_request(d_img, width, height, pix0, pix1, tb, p, coef);
+        rq.h_idx = h_idx;
+        rq.d_psi = psi.p; rq.m = m; rq.ld = ld;
+        rq.flt = &flt;
+        rq.kernel_ms = &kms; rq.entries_evaluated = &evaluated; rq.mfma_flops = &S.nystroem_mfma_flops;
+        rq.path = &S.nystroem_path; rq.rowpass = &rps;
+        const int rc = nystroem_band_filter(ctx, rq);
         if (rc == GLF_OK) {
             nystroem_stats();
             S.filter_fused = 1;
@@ -1435,9 +1468,12 @@ int glf::run_planned(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int w
         GLF_TRY(phi.alloc(ctx, (size_t)npix * ld));
         phi_base = phi.p - (size_t)pix0 * ld;
         GLF_HIP(ctx, hipMemsetAsync(c.p, 0, sizeof(double) * ld, st));
-        GLF_TRY(nystroem_contract(ctx, d_img, width, height, pix0, pix1, tb.samples.p, tb.mask.p, tb.idx.p, p, coef, (float)(-alpha), psi.p, m, ld,
-                                  phi_base, 1, u8_guide ? c.p : nullptr, &kms, opt.skip_exact_zeros, &evaluated, &S.nystroem_mfma_flops,
-                                  &S.nystroem_path, &rps));
+        NysRequest rq = nys_request(d_img, width, height, pix0, pix1, tb, p, coef);
+        rq.d_psi = psi.p; rq.m = m; rq.ld = ld;
+        rq.d_phi = phi_base; rq.d_c = u8_guide ? c.p : nullptr; rq.window = opt.skip_exact_zeros;
+        rq.kernel_ms = &kms; rq.entries_evaluated = &evaluated; rq.mfma_flops = &S.nystroem_mfma_flops;
+        rq.path = &S.nystroem_path; rq.rowpass = &rps;
+        GLF_TRY(nystroem_contract(ctx, rq));
         nystroem_stats();
         // sample rows of this shard <- Phi_A, and their share of c
         if (si1 > si0)

@@ -13,10 +13,10 @@ scale * (phiA * pinv)), plus the form's entry generation (below). p64 = round_up
 
 form        K (links)                  s   c    where (csrc/, line numbers as of this commit)
 f32         p64 / 2 + 1                0   316  k_nystroem<MB, PB> (any MB, PB: a pixel block and a column block have their own
-                                                accumulator): nystroem.hip:203, one mfma_f32_32x32x2f32 per two samples (one of each half
-                                                of the 64-sample chunk, :182-186) over p64 / 64 chunks (:179); +1: the products are
+                                                accumulator): nystroem.hip:204, one mfma_f32_32x32x2f32 per two samples (one of each half
+                                                of the 64-sample chunk, :183-187) over p64 / 64 chunks (:180); +1: the products are
                                                 rounded f32. c = 2 + 2 (v_exp_f32, 1 ulp = 2 u) + 3 x 104: the exponent t = fmaf(dv^2,
-                                                s_val, q s_loc) (:195-196) carries the rounding of s_loc / s_val to f32 (make_coef), of
+                                                s_val, q s_loc) (:196-197) carries the rounding of s_loc / s_val to f32 (make_coef), of
                                                 q s_loc and of the fmaf (q = dr^2 + dc^2 and dv^2 are exact integers), each amplified by
                                                 t ln 2 <= 150 ln 2 < 104: beyond t = 150 the entry is below 2^-150 (the floor below).
                                                 gamma is above 2^-16 for this chain: the amplification of the exponent's roundings.
@@ -24,11 +24,11 @@ pix f32     p64 / 2 + 1                0   316 + 104 n   the same kernel, GEN !=
                                                 adds n roundings to the exponent: rgb8 0 (integers below 2^18), u16 1 (the square of a
                                                 16-bit difference), f32 3 (difference, twice in its square, the square), rgbf32 5 (as the
                                                 comment at :389-391 counts)
-f16s        12 p64 / 64                3   120  k_nystroem_f16s<.., LUT = false>: nystroem.hip:658-660, 4 steps (:594) x 3 MFMAs per chunk
-                                                (:577); s: K' = 2^15 K split (:637-646), Psi split (k_psi_split_f16, :398-400), lo x lo;
-                                                c = 2 + 2 (v_exp_f32) + 4 x 29: s, q s_loc, the fmaf and 15 - t (:633-634), amplified by
+f16s        12 p64 / 64                3   120  k_nystroem_f16s<.., LUT = false>: nystroem.hip:688-690, 4 steps (:624) x 3 MFMAs per chunk
+                                                (:607); s: K' = 2^15 K split (:667-676), Psi split (k_psi_split_f16, :396-398), lo x lo;
+                                                c = 2 + 2 (v_exp_f32) + 4 x 29: s, q s_loc, the fmaf and 15 - t (:663-664), amplified by
                                                 |15 - t| ln 2 <= 40.5 ln 2 < 29 (t > 40.5: 2^15 K < 2^-25, a zero pair, the floor below)
-f16s lut    12 p64 / 64                3   36   LUT = true: K' = (Er Ec) P (:630), tables rounded once from f64 (:780-784): 3 + 2
+f16s lut    12 p64 / 64                3   36   LUT = true: K' = (Er Ec) P (:660), tables rounded once from f64 (:801-805): 3 + 2
                                                 multiplies, + 29 for s_loc and s_val rounded to f32 (t ln 2 u on an entry 2^-t), + 2
 grid        3 ks + 3 ksc               6   23   operator_ref's grid row with the Nystroem passes' kernels: row pass k_grid_rowpass
                                                 (ROWPASS=v1, nystroem_grid.inc:247-249) or the row-tile form (rt, :522), column pass
@@ -37,7 +37,7 @@ grid        3 ks + 3 ksc               6   23   operator_ref's grid row with the
 rank        3 ks + 3 R / 16 + 3 ksc    9   24   operator_ref's rank row (k_rank_colpass, COLPASS ws nystroem_rank.inc:450-495 / v1
                                                 :825-888): + 1 for the factor table. The order in which the column pass accumulates T'
                                                 over its segments was not traced instruction by instruction: K counts its MFMAs per output.
-band        3 nr ksc                   3   24   k_band (nystroem_band.inc:492-494): 17 + 3 + 2 (y = (era ec) pp, :464-465) + 2; the chain of
+band        3 nr ksc                   3   24   k_band (nystroem_band.inc:485-487): 17 + 3 + 2 (y = (era ec) pp, :457-458) + 2; the chain of
                                                 one pixel runs over the grid rows of its band and the 16-column blocks of its window, at
                                                 most all nr ksc of them. Its schedule (row pairs per half-block) was not traced
                                                 instruction by instruction: K counts the MFMAs per output.
@@ -76,7 +76,7 @@ ALL_LDS = (32, 64, 128, 256)
 
 
 def lut_runs(shape, ld, no_lut=False):
-    """launch_nystroem_f16s' rule (nystroem.hip:764-767): MB <= 2, every wave's 64 pixels in one image row, the table short enough."""
+    """launch_nystroem_f16s' rule (nystroem.hip:785-788): MB <= 2, every wave's 64 pixels in one image row, the table short enough."""
     w, h_loc = SHAPES[shape][0], SHAPES[shape][4]
     lut_r = int(np.floor(np.sqrt(150.5 / (np.log2(np.e) / h_loc ** 2)))) + 1
     return ld <= 64 and w % 64 == 0 and lut_r <= 511 and not no_lut
