@@ -159,6 +159,7 @@ int pix_planes(glf_ctx *ctx, PixGen gen, const uint8_t *d_img, int64_t N, float 
 {
     if (gen == PixGen::Grey) return set_error(ctx, GLF_ERR_INVALID, "pix_planes: the 8-bit grey format has kernels of its own");
     const dim3 grid((unsigned)ceil_div(N, 256));
+    ctx->flt_note.kernels |= GLF_FK_PLANES;
     pix_dispatch_raw(gen, [&](auto t) { hipLaunchKernelGGL(k_planes<t.G>, grid, dim3(256), 0, ctx->stream, d_img, N, d_planes); });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
@@ -221,6 +222,7 @@ int apply_filter_pix(glf_ctx *ctx, PixGen gen, const float *d_phi, int64_t pix0,
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     const dim3 grid((unsigned)nblk);
+    note_apply(ctx, GLF_FK_APPLY_PIX, ld, pix1 - pix0, ppb, nblk);
     pix_dispatch_raw(gen, [&](auto t) { launch_apply_filter_pix<t.G>(ld, grid, ctx->stream, d_phi, pix0, pix1, d_w, gain, ysub, d_img, d_out, d_zf, N); });
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
@@ -290,6 +292,8 @@ int phi_t_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, const uint8_
     DevBuf<double> part_g, part_s;
     GLF_TRY(part_g.alloc(ctx, (size_t)nblk * nch * ld));
     GLF_TRY(part_s.alloc(ctx, (size_t)nblk * nsig * ld));
+    ctx->flt_note.kernels |= GLF_FK_PHI_T_PIX_SIGNALS;
+    ctx->flt_note.proj_blocks = (unsigned)nblk;
     pix_dispatch_raw(gen, [&](auto t) {
         hipLaunchKernelGGL(k_phi_t_pix_signals<t.G>, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, d_sig, N, nsig, pix0, pix1, ld, part_g.p,
                            part_s.p);
@@ -376,6 +380,7 @@ int apply_filter_pix_signals(glf_ctx *ctx, PixGen gen, const float *d_phi, int64
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     const dim3 grid((unsigned)nblk);
+    note_apply(ctx, GLF_FK_APPLY_PIX_SIGNALS, ld, pix1 - pix0, ppb, nblk);
     pix_dispatch_raw(gen, [&](auto t) {
         launch_apply_filter_pix_signals<t.G>(ld, grid, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_img, d_out, d_zf, d_sig, d_sig_out, N);
     });

@@ -10,6 +10,15 @@
 
 namespace glf {
 
+// glf_filter_info's report of an apply launch: its kernel, LD instantiation and grid, and whether the grid strides the range
+void note_apply(glf_ctx *ctx, unsigned kernel, unsigned ld, int64_t npix, int ppb, int64_t nblk)
+{
+    ctx->flt_note.kernels |= kernel;
+    ctx->flt_note.ld = ld;
+    ctx->flt_note.apply_blocks = (unsigned)nblk;
+    ctx->flt_note.strided = nblk * ppb < npix ? 1u : 0u;
+}
+
 // partial[blk][j] = sum_{pix in blk} Phi[pix][j] * y[pix]
 __global__ __launch_bounds__(256) void k_phi_t_y(const float *__restrict__ phi, const uint8_t *__restrict__ img, int64_t pix0,
                                                   int64_t pix1, unsigned ld, double *__restrict__ partial)
@@ -68,6 +77,8 @@ int phi_t_y(glf_ctx *ctx, const float *d_phi, const uint8_t *d_img, int64_t pix0
     DevBuf<double> part;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ld));
     hipLaunchKernelGGL(k_phi_t_y, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_img, pix0, pix1, ld, part.p);
+    ctx->flt_note.kernels |= GLF_FK_PHI_T_Y;
+    ctx->flt_note.proj_blocks = (unsigned)nblk;
     hipLaunchKernelGGL(k_cols_sum, dim3(ld), dim3(256), 0, ctx->stream, part.p, nblk, ld, d_c);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -158,6 +169,7 @@ int phi_gram(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsig
     const int nblk = (int)std::max<int64_t>(1, std::min<int64_t>(512, ceil_div(pix1 - pix0, 64)));
     DevBuf<double> part;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * ld * ld));
+    ctx->flt_note.kernels |= GLF_FK_PHI_GRAM;
     hipLaunchKernelGGL(k_phi_gram, dim3(nblk, (unsigned)ceil_div((int64_t)ld * ld, 4096)), dim3(256), 64 * ld * sizeof(float), ctx->stream, d_phi,
                        pix0, pix1, ld, part.p);
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * ld), dim3(256), 0, ctx->stream, part.p, nblk, ld * ld, d_G);
@@ -241,6 +253,7 @@ int apply_filter(glf_ctx *ctx, const uint8_t *d_img, const float *d_phi, int64_t
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     dim3 grid((unsigned)nblk), block(256);
+    note_apply(ctx, GLF_FK_APPLY, ld, pix1 - pix0, ppb, nblk);
     switch (ld) {
     case 32: hipLaunchKernelGGL(k_apply_filter<32>, grid, block, 0, ctx->stream, d_img, d_phi, pix0, pix1, d_w, gain, ysub, d_out, d_zf, d_corr); break;
     case 64: hipLaunchKernelGGL(k_apply_filter<64>, grid, block, 0, ctx->stream, d_img, d_phi, pix0, pix1, d_w, gain, ysub, d_out, d_zf, d_corr); break;
@@ -299,6 +312,8 @@ int phi_t_signals(glf_ctx *ctx, const float *d_phi, const float *d_sig, int64_t 
     DevBuf<double> part;
     GLF_TRY(part.alloc(ctx, (size_t)nblk * nsig * ld));
     hipLaunchKernelGGL(k_phi_t_signals, dim3(nblk), dim3(256), 0, ctx->stream, d_phi, d_sig, N, nsig, pix0, pix1, ld, part.p);
+    ctx->flt_note.kernels |= GLF_FK_PHI_T_SIGNALS;
+    ctx->flt_note.proj_blocks = (unsigned)nblk;
     hipLaunchKernelGGL(k_cols_sum, dim3(ld * nsig), dim3(256), 0, ctx->stream, part.p, nblk, ld * nsig, d_c);
     GLF_LAUNCH_CHECK(ctx);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -408,6 +423,7 @@ int apply_filter_signals(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t
     int64_t nblk = ceil_div(pix1 - pix0, ppb);
     if (nblk > 8192) nblk = 8192; // grid-stride the rest
     dim3 grid((unsigned)nblk), block(256);
+    note_apply(ctx, GLF_FK_APPLY_SIGNALS, ld, pix1 - pix0, ppb, nblk);
     switch (ld) {
     case 32: hipLaunchKernelGGL(k_apply_filter_signals<32>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
     case 64: hipLaunchKernelGGL(k_apply_filter_signals<64>, grid, block, 0, ctx->stream, d_phi, pix0, pix1, nsig, d_w, gain, ysub, d_sig, d_out, N); break;
@@ -453,6 +469,7 @@ int filter_accumulate(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pi
     if (pix0 == pix1) return GLF_OK;
     int64_t nblk = ceil_div(pix1 - pix0, 4);
     if (nblk > 8192) nblk = 8192;
+    note_apply(ctx, GLF_FK_ACCUM, ld, pix1 - pix0, 4, nblk);
     hipLaunchKernelGGL(k_filter_accum, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, pix0, pix1, d_w, d_acc, first ? 1 : 0);
     GLF_LAUNCH_CHECK(ctx);
     return GLF_OK;
@@ -462,6 +479,7 @@ int filter_finish(glf_ctx *ctx, const uint8_t *d_img, const float *d_acc, int64_
                   float *d_zf)
 {
     if (pix0 >= pix1) return GLF_OK;
+    ctx->flt_note.kernels |= GLF_FK_FINISH;
     hipLaunchKernelGGL(k_filter_finish, dim3((unsigned)ceil_div(pix1 - pix0, 256)), dim3(256), 0, ctx->stream, d_img, d_acc, pix0, pix1, gain,
                        ysub, d_out, d_zf);
     GLF_LAUNCH_CHECK(ctx);

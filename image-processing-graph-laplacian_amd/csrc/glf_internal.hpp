@@ -89,6 +89,9 @@ struct glf_ctx {
     struct { int skipping = 0, lut = 0; } nys_note;
     // what the last degree sweep ran (glf_Degree_ex reports it): glf_degree_info's path, shape, skipping, chunks, mgroups, entries
     struct { int path = 0, shape = 0, skipping = 0, chunks = 0, mgroups = 0; double entries = 0.0; } deg_note;
+    // what the filter stage's launchers ran since glf_Filter_ex cleared it (glf_filter_info): each launcher ORs its GLF_FK_* bit in
+    // and notes its grid
+    struct { unsigned kernels = 0, ld = 0, panels = 0, proj_blocks = 0, apply_blocks = 0, strided = 0; } flt_note;
     // one page of pinned, device-visible host memory the eigensolver's kernels write their flags and norms into (read
     // after a stream synchronise; no D2H copy launches, and no hipHostMalloc per image): see glf::ctx_pinned()
     void *pinned = nullptr;
@@ -894,6 +897,7 @@ int permute_rows(glf_ctx *ctx, const float *d_in, float *d_out, int64_t N, unsig
 __global__ void k_cols_sum(const double *__restrict__ in, int nrows, unsigned ld, double *__restrict__ out);
 int phi_t_y(glf_ctx *ctx, const float *d_phi, const uint8_t *d_img, int64_t pix0, int64_t pix1, unsigned m,
             unsigned ld, double *d_c);
+void note_apply(glf_ctx *ctx, unsigned kernel, unsigned ld, int64_t npix, int ppb, int64_t nblk); // (filter.hip; glf_filter_info)
 int phi_gram(glf_ctx *ctx, const float *d_phi, int64_t pix0, int64_t pix1, unsigned ld, double *d_G); // Phi^T Phi (f64 [ld][ld])
 int apply_filter(glf_ctx *ctx, const uint8_t *d_img, const float *d_phi, int64_t pix0, int64_t pix1,
                  unsigned m, unsigned ld, const float *d_w, float gain, float ysub, uint8_t *d_out, float *d_zf,

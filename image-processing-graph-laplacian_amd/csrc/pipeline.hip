@@ -546,6 +546,253 @@ int glf_Permutation(glf_ctx *ctx, const glf_mat *in, const unsigned *sample_indi
     return GLF_OK;
 }
 
+// ---- the filter stage: what the whole path's unfused filter and glf_Filter_ex both run ----------------------------------------------
+// What the stage needs to know of a run: run_planned fills it from its RunPlan, glf_Filter_ex from its request.
+struct FilterSpec {
+    glf_options opt;   // filter_mode, filter_pow, filter_beta (filter_rule.hpp)
+    PixGen gen;
+    int64_t N;
+    unsigned m, ld;
+    float gain, ysub;
+    const double *lam; // HOST [m]
+    bool reduce;       // sum c and G over the ranks (the whole path; glf_Filter_ex is one rank's share)
+};
+
+// hG = Phi^T Phi over the pixels [pix0, pix1) (all ranks' when F.reduce): the sharpening weights' Gram matrix, f64 [ld][ld] on the host
+static int filter_gram(glf_ctx *ctx, const FilterSpec &F, const float *phi_rows, int64_t pix0, int64_t pix1, std::vector<double> &hG)
+{
+    DevBuf<double> G;
+    GLF_TRY(G.alloc(ctx, (size_t)F.ld * F.ld));
+    GLF_TRY(phi_gram(ctx, phi_rows, pix0, pix1, F.ld, G.p));
+    if (F.reduce) GLF_TRY(allreduce_f64(ctx, G.p, (size_t)F.ld * F.ld));
+    hG.resize((size_t)F.ld * F.ld);
+    return glf_memcpy_d2h(ctx, hG.data(), G.p, sizeof(double) * F.ld * F.ld);
+}
+
+// the 8-bit grey guide from its complete c = Phi^T y (device [ld]): the weights, then k_apply_filter over [pix0, pix1)
+static int filter_grey(glf_ctx *ctx, const FilterSpec &F, const std::vector<double> &hG, const double *d_c, float *d_w, const float *phi_rows,
+                       int64_t pix0, int64_t pix1, const uint8_t *d_img, uint8_t *d_out, float *d_zf, float *d_corr, double *h_c0)
+{
+    GLF_TRY(weights_from_c(ctx, d_c, 1, F.ld, [&](const double *hc, float *hw) {
+        filter_weights_row(F.opt, F.m, F.lam, hG.data(), F.ld, hc, hw);
+    }, d_w, h_c0));
+    return apply_filter(ctx, d_img, phi_rows, pix0, pix1, F.m, F.ld, d_w, F.gain, F.ysub, d_out, d_zf, d_corr);
+}
+
+// one 256-column panel of more than 256 eigenpairs: its weights from its complete c (device [256]; mq live columns, lamq their
+// eigenvalues), then its share of the correction into d_acc. d_pan: the panel's rows of the pixels [pix0, pix1)
+static int filter_panel(glf_ctx *ctx, const glf_options &opt, unsigned mq, const double *lamq, const double *d_c, float *d_w, const float *d_pan,
+                        int64_t pix0, int64_t pix1, float *d_acc, bool first)
+{
+    GLF_TRY(weights_from_c(ctx, d_c, 1, PANEL_COLS, [&](const double *hc, float *hw) {
+        filter_weights_row(opt, mq, lamq, nullptr, 0, hc, hw);
+    }, d_w));
+    return filter_accumulate(ctx, d_pan, pix0, pix1, PANEL_COLS, d_w, d_acc, first);
+}
+
+// The planes of the filter stage over [pix0, pix1): the signal planes of an 8-bit grey guide (sig; sig_w: their weights where they
+// are known already), or a colour / 16-bit / float guide's own channels (sig: the channels as float planes) with its extra planes
+// (planes, optional: the guide's kernels then read the channels from the image). phi_rows: Phi's rows addressed by absolute pixel
+// index. h_c_in (optional, HOST [rows][m]): stands in for the projection pass and its collective; h_c_out (optional): the
+// projection as this call formed it. Rows: the guide's channels first, then the planes.
+static int filter_planes_tail(glf_ctx *ctx, const FilterSpec &F, const std::vector<double> &hG, const float *phi_rows, int64_t pix0, int64_t pix1,
+                              const uint8_t *d_img, const SignalPlanes *sig, const SignalPlanes *planes, const float *sig_w, uint8_t *d_out,
+                              float *d_zf, const double *h_c_in = nullptr, double *h_c_out = nullptr)
+{
+    const unsigned m = F.m, ld = F.ld;
+    const int64_t N = F.N;
+    auto rule = [&](const double *hc, float *hw) { filter_weights_row(F.opt, m, F.lam, hG.data(), ld, hc, hw); };
+    // c [rows][ld] on the device from the host's [rows][m], and back
+    auto c_put = [&](double *d_c, int rows) -> int {
+        std::vector<double> h((size_t)rows * ld, 0.0);
+        for (int r = 0; r < rows; ++r) std::memcpy(h.data() + (size_t)r * ld, h_c_in + (size_t)r * m, sizeof(double) * m);
+        return glf_memcpy_h2d(ctx, d_c, h.data(), sizeof(double) * h.size());
+    };
+    auto c_get = [&](const double *d_c, int rows) -> int {
+        std::vector<double> h((size_t)rows * ld);
+        GLF_TRY(glf_memcpy_d2h(ctx, h.data(), d_c, sizeof(double) * h.size()));
+        for (int r = 0; r < rows; ++r) std::memcpy(h_c_out + (size_t)r * m, h.data() + (size_t)r * ld, sizeof(double) * m);
+        return GLF_OK;
+    };
+    const int ns = sig->nsig;
+    if (planes) { // colour or 16-bit guide with planes: c for the channels and the planes in one pass over Phi, the outputs in one more
+        const int np = planes->nsig;
+        DevBuf<double> ca; // [ns + np][ld]: the guide's channels, then the planes
+        DevBuf<float> wa;
+        GLF_TRY(ca.alloc(ctx, (size_t)(ns + np) * ld));
+        GLF_TRY(wa.alloc(ctx, (size_t)(ns + np) * ld));
+        double *cg = ca.p, *cp = ca.p + (size_t)ns * ld;
+        if (h_c_in) GLF_TRY(c_put(ca.p, ns + np));
+        else {
+            GLF_TRY(phi_t_pix_signals(ctx, F.gen, phi_rows, d_img, planes->d_sig, N, np, pix0, pix1, ld, cg, cp));
+            if (F.reduce) {
+                GLF_TRY(allreduce_f64(ctx, cg, (size_t)ns * ld)); // the guide's collective, with the shape it has in the plain call
+                GLF_TRY(allreduce_f64(ctx, cp, (size_t)np * ld)); // the planes' in one of their own (a ring's summation order may follow the layout)
+            }
+        }
+        if (h_c_out) GLF_TRY(c_get(ca.p, ns + np));
+        GLF_TRY(weights_from_c(ctx, ca.p, ns + np, ld, rule, wa.p));
+        return apply_filter_pix_signals(ctx, F.gen, phi_rows, pix0, pix1, ld, np, wa.p, F.gain, F.ysub, d_img, d_out, d_zf, planes->d_sig,
+                                        planes->d_out, N);
+    }
+    if (sig_w) // (its weights stand, c_s's collective is not repeated)
+        return apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w, F.gain, F.ysub, sig->d_sig, sig->d_out, N);
+    DevBuf<double> cs;
+    DevBuf<float> ws;
+    GLF_TRY(cs.alloc(ctx, (size_t)ns * ld));
+    GLF_TRY(ws.alloc(ctx, (size_t)ns * ld));
+    if (h_c_in) GLF_TRY(c_put(cs.p, ns));
+    else {
+        GLF_TRY(phi_t_signals(ctx, phi_rows, sig->d_sig, N, ns, pix0, pix1, ld, cs.p));
+        if (F.reduce) GLF_TRY(allreduce_f64(ctx, cs.p, (size_t)ns * ld)); // c_k = Phi^T s_k over all ranks' pixels (a collective of its own)
+    }
+    if (h_c_out) GLF_TRY(c_get(cs.p, ns));
+    GLF_TRY(weights_from_c(ctx, cs.p, ns, ld, rule, ws.p));
+    if (F.gen != PixGen::Grey) // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
+        return apply_filter_pix(ctx, F.gen, phi_rows, pix0, pix1, ld, ws.p, F.gain, F.ysub, d_img, d_out, d_zf, N);
+    return apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, F.gain, F.ysub, sig->d_sig, sig->d_out, N);
+}
+
+int glf_Filter_ex(glf_ctx *ctx, const glf_filter_request *rq, glf_filter_info *info)
+{
+    if (!ctx || !rq) return GLF_ERR_INVALID;
+    if (rq->struct_size != sizeof(glf_filter_request))
+        return set_error(ctx, GLF_ERR_INVALID, "filter: glf_filter_request.struct_size %u, expected %zu", rq->struct_size, sizeof(glf_filter_request));
+    if (info && info->struct_size != sizeof(glf_filter_info))
+        return set_error(ctx, GLF_ERR_INVALID, "filter: glf_filter_info.struct_size %u, expected %zu", info->struct_size, sizeof(glf_filter_info));
+    const glf_mat *phi = rq->phi;
+    if (!rq->d_img || !phi || !rq->lam || !rq->d_out || rq->width <= 0 || rq->height <= 0)
+        return set_error(ctx, GLF_ERR_INVALID, "filter: a guide, phi, lam and d_out are required");
+    if (rq->pix < GLF_PIX_U8 || rq->pix > GLF_PIX_RGBF32) return set_error(ctx, GLF_ERR_INVALID, "filter: pix %d is not one of GLF_PIX_*", rq->pix);
+    if (rq->filter_mode < GLF_FILTER_REFERENCE || rq->filter_mode > GLF_FILTER_SHARPEN)
+        return set_error(ctx, GLF_ERR_INVALID, "filter: filter_mode %d", rq->filter_mode);
+    const PixGen gen = rq->pix == GLF_PIX_U8 ? PixGen::Grey : pixgen_of_pix(rq->pix);
+    const bool grey = gen == PixGen::Grey;
+    const int64_t N = (int64_t)rq->width * rq->height;
+    if (N >= (int64_t)1 << 31) return set_error(ctx, GLF_ERR_UNSUPPORTED, "image too large");
+    if (phi->kind != GLF_MAT_DENSE || !phi->data || phi->rows != N || phi->cols < 1)
+        return set_error(ctx, GLF_ERR_INVALID, "filter: phi must be a dense N x m matrix (N = %lld)", (long long)N);
+    if (phi->row_order == GLF_ROWS_SAMPLE_FIRST)
+        return set_error(ctx, GLF_ERR_INVALID, "phi is in sample-first order: call glf_Permutation first (hpc/image_processing.c:250)");
+    const unsigned m = (unsigned)phi->cols, ld = (unsigned)phi->ld;
+    const bool wide = wide_ld(ld);
+    if (!(valid_ld(ld) || wide)) return set_error(ctx, GLF_ERR_INVALID, "filter: ld = %u is not 32, 64, 128, 256 or a multiple of 256", ld);
+    if (m > ld) return set_error(ctx, GLF_ERR_INVALID, "filter: m = %u columns in ld = %u", m, ld);
+    const bool all_rows = rq->row0 == 0 && rq->row1 == 0;
+    if (!all_rows && (rq->row0 >= rq->row1 || rq->row1 > (unsigned)rq->height))
+        return set_error(ctx, GLF_ERR_INVALID, "filter: image rows [%u, %u) are not a range of the %d rows", rq->row0, rq->row1, rq->height);
+    const int nsig = rq->nsig;
+    if (nsig < 0 || nsig > GLF_MAX_SIGNALS || (nsig > 0 && (!rq->d_sig || !rq->d_sig_out)))
+        return set_error(ctx, GLF_ERR_INVALID, "filter: nsig = %d planes (1 .. %d, with d_sig and d_sig_out)", nsig, GLF_MAX_SIGNALS);
+    if (rq->d_corr && (!grey || wide)) return set_error(ctx, GLF_ERR_INVALID, "filter: d_corr is the 8-bit grey guide's correction (narrow ld)");
+    if (wide && rq->filter_mode == GLF_FILTER_SHARPEN)
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "the sharpening filter takes at most %u eigenpairs (%u asked for)", PANEL_COLS, m);
+    if (wide && (nsig > 0 || !grey)) return set_error(ctx, GLF_ERR_UNSUPPORTED, "signal planes with more than 256 eigenpairs (%u asked for)", m);
+    const bool sharpen = rq->filter_mode == GLF_FILTER_SHARPEN;
+    if (sharpen && !all_rows && !(rq->row0 == 0 && rq->row1 == (unsigned)rq->height))
+        return set_error(ctx, GLF_ERR_UNSUPPORTED, "filter: the sharpening weights need Phi^T Phi over all image rows (rows [%u, %u))", rq->row0, rq->row1);
+    GLF_ENTER(ctx);
+    const uint8_t *d_img = static_cast<const uint8_t *>(rq->d_img);
+    GLF_TRY(f32_admit(ctx, gen, d_img, rq->width, rq->height));
+    FilterSpec F;
+    glf_options_default(&F.opt);
+    F.opt.filter_mode = rq->filter_mode;
+    F.opt.filter_pow = rq->filter_pow;
+    F.opt.filter_beta = rq->filter_beta;
+    F.opt.gain = rq->gain;
+    F.gen = gen;
+    F.N = N;
+    F.m = m;
+    F.ld = ld;
+    F.gain = filter_gain(F.opt);
+    F.ysub = 1.0f - filter_ident(F.opt);
+    F.lam = rq->lam;
+    F.reduce = false;
+    const int64_t pix0 = all_rows ? 0 : (int64_t)rq->row0 * rq->width, pix1 = all_rows ? N : (int64_t)rq->row1 * rq->width;
+    ctx->flt_note = {};
+    uint8_t *d_out = static_cast<uint8_t *>(rq->d_out);
+    const int nch = pix_desc(gen).channels;
+    std::vector<double> hc_out((size_t)(nch + nsig) * m), hG; // (staged: the host outputs are written once everything has run)
+    if (wide) { // 256-column panels: right = phi^T y panel by panel, then the correction accumulated over the panels
+        const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS);
+        const int64_t npix = pix1 - pix0;
+        DevBuf<float> pan, wq, acc;
+        DevBuf<double> cq;
+        GLF_TRY(pan.alloc(ctx, (size_t)npix * PANEL_COLS));
+        GLF_TRY(wq.alloc(ctx, PANEL_COLS));
+        GLF_TRY(acc.alloc(ctx, (size_t)npix));
+        GLF_TRY(cq.alloc(ctx, PANEL_COLS));
+        std::vector<double> hq(PANEL_COLS);
+        for (unsigned q = 0; q < npan; ++q) {
+            const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
+            GLF_TRY(pack_panel(ctx, phi->data + (size_t)pix0 * ld, ld, npix, q, pan.p));
+            if (rq->h_c_in) {
+                std::fill(hq.begin(), hq.end(), 0.0);
+                std::memcpy(hq.data(), rq->h_c_in + (size_t)q * PANEL_COLS, sizeof(double) * mq);
+                GLF_TRY(glf_memcpy_h2d(ctx, cq.p, hq.data(), sizeof(double) * PANEL_COLS));
+            } else {
+                GLF_TRY(phi_t_y(ctx, pan.p - (size_t)pix0 * PANEL_COLS, d_img, pix0, pix1, mq, PANEL_COLS, cq.p));
+            }
+            if (rq->h_c_out) {
+                GLF_TRY(glf_memcpy_d2h(ctx, hq.data(), cq.p, sizeof(double) * PANEL_COLS));
+                std::memcpy(hc_out.data() + (size_t)q * PANEL_COLS, hq.data(), sizeof(double) * mq);
+            }
+            GLF_TRY(filter_panel(ctx, F.opt, mq, rq->lam + (size_t)q * PANEL_COLS, cq.p, wq.p, pan.p, pix0, pix1, acc.p, q == 0));
+        }
+        GLF_TRY(filter_finish(ctx, d_img, acc.p, pix0, pix1, F.gain, F.ysub, d_out, rq->d_zf));
+        ctx->flt_note.panels = npan;
+    } else {
+        const float *phi_rows = phi->data;
+        if (sharpen) GLF_TRY(filter_gram(ctx, F, phi_rows, pix0, pix1, hG));
+        SignalPlanes sig{nsig, rq->d_sig, rq->d_sig_out};
+        if (grey) {
+            DevBuf<double> c;
+            DevBuf<float> w;
+            GLF_TRY(c.alloc(ctx, ld));
+            GLF_TRY(w.alloc(ctx, ld));
+            if (rq->h_c_in) {
+                std::vector<double> h(ld, 0.0);
+                std::memcpy(h.data(), rq->h_c_in, sizeof(double) * m);
+                GLF_TRY(glf_memcpy_h2d(ctx, c.p, h.data(), sizeof(double) * ld));
+            } else {
+                GLF_TRY(phi_t_y(ctx, phi_rows, d_img, pix0, pix1, m, ld, c.p)); // right = phi^T y, hpc/display.c:66
+            }
+            std::vector<double> h0(ld);
+            GLF_TRY(filter_grey(ctx, F, hG, c.p, w.p, phi_rows, pix0, pix1, d_img, d_out, rq->d_zf, rq->d_corr, h0.data()));
+            std::memcpy(hc_out.data(), h0.data(), sizeof(double) * m);
+            if (nsig > 0)
+                GLF_TRY(filter_planes_tail(ctx, F, hG, phi_rows, pix0, pix1, d_img, &sig, nullptr, nullptr, d_out, rq->d_zf,
+                                           rq->h_c_in ? rq->h_c_in + m : nullptr, hc_out.data() + m));
+        } else if (nsig > 0) {
+            SignalPlanes guide{nch, nullptr, nullptr};
+            GLF_TRY(filter_planes_tail(ctx, F, hG, phi_rows, pix0, pix1, d_img, &guide, &sig, nullptr, d_out, rq->d_zf, rq->h_c_in, hc_out.data()));
+        } else { // the channels as float planes, as the whole path forms them
+            DevBuf<float> gp;
+            GLF_TRY(gp.alloc(ctx, (size_t)nch * N));
+            GLF_TRY(pix_planes(ctx, gen, d_img, N, gp.p));
+            SignalPlanes guide{nch, gp.p, nullptr};
+            GLF_TRY(filter_planes_tail(ctx, F, hG, phi_rows, pix0, pix1, d_img, &guide, nullptr, nullptr, d_out, rq->d_zf, rq->h_c_in, hc_out.data()));
+        }
+    }
+    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (rq->h_c_out) std::memcpy(rq->h_c_out, hc_out.data(), sizeof(double) * hc_out.size());
+    if (rq->h_gram_out && sharpen)
+        for (unsigned i = 0; i < m; ++i) std::memcpy(rq->h_gram_out + (size_t)i * m, hG.data() + (size_t)i * ld, sizeof(double) * m);
+    if (info) {
+        info->kernels = ctx->flt_note.kernels;
+        info->ld = ctx->flt_note.ld;
+        info->panels = ctx->flt_note.panels;
+        info->proj_blocks = ctx->flt_note.proj_blocks;
+        info->apply_blocks = ctx->flt_note.apply_blocks;
+        info->grid_strided = ctx->flt_note.strided;
+        info->reserved_ = 0;
+        info->pix0 = (uint64_t)pix0;
+        info->pix1 = (uint64_t)pix1;
+    }
+    return GLF_OK;
+}
+
+// glf_Filter_ex with its defaults: the reference filter z = y + gain Phi Pi Phi^T y on all rows (Pi: the DIAG matrix of f(eigenvalues))
 int glf_ComputeResultFromLaplacian(glf_ctx *ctx, const uint8_t *d_img, const glf_mat *phi, const glf_mat *Pi, unsigned width,
                                    unsigned height, float gain, uint8_t *d_out, float *d_zf)
 {
@@ -555,45 +802,23 @@ int glf_ComputeResultFromLaplacian(glf_ctx *ctx, const uint8_t *d_img, const glf
     const unsigned m = (unsigned)phi->cols, ld = (unsigned)phi->ld;
     if (phi->kind != GLF_MAT_DENSE || phi->rows != N || Pi->kind != GLF_MAT_DIAG || Pi->rows != m || !(valid_ld(ld) || wide_ld(ld)))
         return set_error(ctx, GLF_ERR_INVALID, "ComputeResultFromLaplacian: shape mismatch");
-    if (phi->row_order == GLF_ROWS_SAMPLE_FIRST)
-        return set_error(ctx, GLF_ERR_INVALID, "phi is in sample-first order: call glf_Permutation first (hpc/image_processing.c:250)");
-    if (wide_ld(ld)) { // 256-column panels: right = phi^T z panel by panel, then the correction accumulated over the panels
-        const unsigned npan = (unsigned)ceil_div(m, PANEL_COLS);
-        DevBuf<float> pan, wq, acc;
-        DevBuf<double> cq;
-        GLF_TRY(pan.alloc(ctx, (size_t)N * PANEL_COLS));
-        GLF_TRY(wq.alloc(ctx, PANEL_COLS));
-        GLF_TRY(acc.alloc(ctx, (size_t)N));
-        GLF_TRY(cq.alloc(ctx, PANEL_COLS));
-        std::vector<float> hp(m);
-        GLF_TRY(glf_memcpy_d2h(ctx, hp.data(), Pi->data, sizeof(float) * m));
-        for (unsigned q = 0; q < npan; ++q) {
-            const unsigned mq = std::min(PANEL_COLS, m - q * PANEL_COLS);
-            GLF_TRY(pack_panel(ctx, phi->data, ld, N, q, pan.p));
-            GLF_TRY(phi_t_y(ctx, pan.p, d_img, 0, N, mq, PANEL_COLS, cq.p));
-            const float *pq = hp.data() + q * PANEL_COLS;
-            GLF_TRY(weights_from_c(ctx, cq.p, 1, PANEL_COLS, [&](const double *hc, float *hw) {
-                for (unsigned j = 0; j < mq; ++j) hw[j] = (float)((double)pq[j] * hc[j]);
-            }, wq.p));
-            GLF_TRY(filter_accumulate(ctx, pan.p, 0, N, PANEL_COLS, wq.p, acc.p, q == 0));
-        }
-        GLF_TRY(filter_finish(ctx, d_img, acc.p, 0, N, gain, 0.f, d_out, d_zf));
-        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return GLF_OK;
-    }
-    DevBuf<double> c;
-    GLF_TRY(c.alloc(ctx, ld));
-    GLF_TRY(phi_t_y(ctx, phi->data, d_img, 0, N, m, ld, c.p)); // right = phi^T z, hpc/display.c:66
     std::vector<float> hp(m);
     GLF_TRY(glf_memcpy_d2h(ctx, hp.data(), Pi->data, sizeof(float) * m));
-    DevBuf<float> w;
-    GLF_TRY(w.alloc(ctx, ld));
-    GLF_TRY(weights_from_c(ctx, c.p, 1, ld, [&](const double *hc, float *hw) {
-        for (unsigned j = 0; j < m; ++j) hw[j] = (float)((double)hp[j] * hc[j]); // left = phi Pi, :64
-    }, w.p));
-    GLF_TRY(apply_filter(ctx, d_img, phi->data, 0, N, m, ld, w.p, gain, 0.f, d_out, d_zf));
-    GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return GLF_OK;
+    const std::vector<double> lam(hp.begin(), hp.end()); // w = fl32(Pi c), left = phi Pi, hpc/display.c:64
+    glf_filter_request rq{};
+    rq.struct_size = sizeof(rq);
+    rq.pix = GLF_PIX_U8;
+    rq.d_img = d_img;
+    rq.width = (int)width;
+    rq.height = (int)height;
+    rq.phi = phi;
+    rq.lam = lam.data();
+    rq.filter_mode = GLF_FILTER_REFERENCE;
+    rq.filter_pow = 1;
+    rq.gain = gain;
+    rq.d_out = d_out;
+    rq.d_zf = d_zf;
+    return glf_Filter_ex(ctx, &rq, nullptr);
 }
 
 int glf_EntireComputation(glf_ctx *ctx, const uint8_t *d_img, int width, int height, int kernel, float h_loc, float h_val,
@@ -1117,10 +1342,7 @@ static int run_wide_panels(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img,
         if (si1 > si0)
             GLF_TRY(scatter_sample_rows(ctx, vq + (size_t)si0 * PANEL_COLS, si1 - si0, PANEL_COLS, tb.idx.p + si0, phi_base, 1, d_img, c.p, mq));
         GLF_TRY(allreduce_f64(ctx, c.p, PANEL_COLS)); // right = phi^T y over all ranks' pixels (this panel's columns)
-        GLF_TRY(weights_from_c(ctx, c.p, 1, PANEL_COLS, [&](const double *hc, float *hw) {
-            filter_weights_row(opt, mq, lamq, nullptr, 0, hc, hw);
-        }, w.p));
-        GLF_TRY(filter_accumulate(ctx, phi.p, pix0, pix1, PANEL_COLS, w.p, acc.p, q == 0));
+        GLF_TRY(filter_panel(ctx, opt, mq, lamq, c.p, w.p, phi.p, pix0, pix1, acc.p, q == 0));
     }
     GLF_HIP(ctx, hipEventRecord(ctx->ev[4], st));
     GLF_TRY(filter_finish(ctx, d_img, acc.p, pix0, pix1, P.gain, P.ysub, d_out, d_zf));
@@ -1141,7 +1363,6 @@ static int filter_planes(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, i
                          const SignalPlanes *planes, const float *sig_w, uint8_t *d_out, float *d_zf, glf_stats &S, glf_stats *stats)
 {
     const unsigned p = P.p, m = P.m, ld = P.ld;
-    const int64_t N = P.N;
     DevBuf<float> phis;
     float *phi_rows = phi_base; // rows addressed by absolute pixel index
     if (fused) {
@@ -1153,40 +1374,9 @@ static int filter_planes(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, i
         GLF_TRY(nystroem_contract(ctx, rq));
         if (si1 > si0) GLF_TRY(scatter_sample_rows(ctx, d_phiA + (size_t)si0 * ld, si1 - si0, ld, tb.idx.p + si0, phi_rows, 1, d_img, nullptr, m));
     }
-    auto rule = [&](const double *hc, float *hw) { filter_weights_row(P.opt, m, lam.data(), hG.data(), ld, hc, hw); };
-    const int ns = sig->nsig;
-    if (planes) { // colour or 16-bit guide with planes: c for the channels and the planes in one pass over Phi, the outputs in one more
-        const int np = planes->nsig;
-        DevBuf<double> ca; // [ns + np][ld]: the guide's channels, then the planes
-        DevBuf<float> wa;
-        GLF_TRY(ca.alloc(ctx, (size_t)(ns + np) * ld));
-        GLF_TRY(wa.alloc(ctx, (size_t)(ns + np) * ld));
-        double *cg = ca.p, *cp = ca.p + (size_t)ns * ld;
-        GLF_TRY(phi_t_pix_signals(ctx, P.gen, phi_rows, d_img, planes->d_sig, N, np, pix0, pix1, ld, cg, cp));
-        GLF_TRY(allreduce_f64(ctx, cg, (size_t)ns * ld)); // the guide's collective, with the shape it has in the plain call
-        GLF_TRY(allreduce_f64(ctx, cp, (size_t)np * ld)); // the planes' in one of their own (a ring's summation order may follow the layout)
-        GLF_TRY(weights_from_c(ctx, ca.p, ns + np, ld, rule, wa.p));
-        GLF_TRY(apply_filter_pix_signals(ctx, P.gen, phi_rows, pix0, pix1, ld, np, wa.p, P.gain, P.ysub, d_img, d_out, d_zf, planes->d_sig,
-                                         planes->d_out, N));
-        return finish_stats(ctx, S, 4, stats);
-    }
-    if (sig_w) { // (its weights stand, c_s's collective is not repeated)
-        GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, sig_w, P.gain, P.ysub, sig->d_sig, sig->d_out, N));
-        GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return GLF_OK;
-    }
-    DevBuf<double> cs;
-    DevBuf<float> ws;
-    GLF_TRY(cs.alloc(ctx, (size_t)ns * ld));
-    GLF_TRY(ws.alloc(ctx, (size_t)ns * ld));
-    GLF_TRY(phi_t_signals(ctx, phi_rows, sig->d_sig, N, ns, pix0, pix1, ld, cs.p));
-    GLF_TRY(allreduce_f64(ctx, cs.p, (size_t)ns * ld)); // c_k = Phi^T s_k over all ranks' pixels (a collective of its own)
-    GLF_TRY(weights_from_c(ctx, cs.p, ns, ld, rule, ws.p));
-    if (!P.u8_guide) { // the outputs, clamped and cast as the grey d_out (16-bit: at 16 bits); the filter stage ends here
-        GLF_TRY(apply_filter_pix(ctx, P.gen, phi_rows, pix0, pix1, ld, ws.p, P.gain, P.ysub, d_img, d_out, d_zf, N));
-        return finish_stats(ctx, S, 4, stats);
-    }
-    GLF_TRY(apply_filter_signals(ctx, phi_rows, pix0, pix1, ld, ns, ws.p, P.gain, P.ysub, sig->d_sig, sig->d_out, N));
+    const FilterSpec F{P.opt, P.gen, P.N, m, ld, P.gain, P.ysub, lam.data(), true};
+    GLF_TRY(filter_planes_tail(ctx, F, hG, phi_rows, pix0, pix1, d_img, sig, planes, sig_w, d_out, d_zf));
+    if (!P.u8_guide) return finish_stats(ctx, S, 4, stats); // (the guide's own values were planes: the filter stage ends here)
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return GLF_OK;
 }
@@ -1484,18 +1674,13 @@ int glf::run_planned(glf_ctx *ctx, const RunPlan &P, const uint8_t *d_img, int w
         // (no 8-bit y: the channels / the 16-bit image are filtered in the planes tail; those formats' entry-by-entry kernel is f32, their
         // band form (PIX_BAND) split f16)
         if (!u8_guide && S.nystroem_path != 4) S.contraction = GLF_CONTRACT_F32_MFMA;
-        if (opt.filter_mode == GLF_FILTER_SHARPEN) { // hG = Phi^T Phi over all ranks' pixels (the sharpening weights, here and in the tail)
-            DevBuf<double> G;
-            GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
-            GLF_TRY(phi_gram(ctx, phi_base, pix0, pix1, ld, G.p));
-            GLF_TRY(allreduce_f64(ctx, G.p, (size_t)ld * ld));
-            hG.resize((size_t)ld * ld);
-            GLF_TRY(glf_memcpy_d2h(ctx, hG.data(), G.p, sizeof(double) * ld * ld));
-        }
-        if (u8_guide) GLF_TRY(weights_from_c(ctx, c.p, 1, ld, rule, w.p, cap ? cap->h_c : nullptr));
+        const FilterSpec F{opt, gen, N, m, ld, P.gain, P.ysub, lam.data(), true};
+        if (opt.filter_mode == GLF_FILTER_SHARPEN) // hG = Phi^T Phi over all ranks' pixels (the sharpening weights, here and in the tail)
+            GLF_TRY(filter_gram(ctx, F, phi_base, pix0, pix1, hG));
         if (cap && cap->d_phi) GLF_HIP(ctx, hipMemcpyAsync(cap->d_phi, phi.p, sizeof(float) * (size_t)npix * ld, hipMemcpyDeviceToDevice, st));
         if (u8_guide)
-            GLF_TRY(apply_filter(ctx, d_img, phi_base, pix0, pix1, m, ld, w.p, P.gain, P.ysub, d_out, d_zf, cap ? cap->d_corr : nullptr));
+            GLF_TRY(filter_grey(ctx, F, hG, c.p, w.p, phi_base, pix0, pix1, d_img, d_out, d_zf, cap ? cap->d_corr : nullptr,
+                                cap ? cap->h_c : nullptr));
     }
     GLF_TRY(finish_stats(ctx, S, 0, u8_guide ? stats : nullptr));
     // ---- planes tail ----------------------------------------------------------------------------

@@ -72,7 +72,7 @@ EXPORTS = [
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
     "glf_graph_edges", "glf_graph_samples",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
-    "glf_Nystroem_ex", "glf_Degree_ex",
+    "glf_Nystroem_ex", "glf_Degree_ex", "glf_Filter_ex",
 ]
 MAX_SIGNALS = 4
 PIX_U8, PIX_RGB8, PIX_U16, PIX_F32, PIX_RGBF32 = 0, 1, 2, 3, 4
@@ -209,6 +209,24 @@ DEG_DENSE, DEG_GRID, DEG_WINDOWED, DEG_ENTRYWISE, DEG_NLM = 0, 1, 2, 5, 6   # gl
 DEG_FIVES, DEG_TEN, DEG_WINDOW = 0, 1, 2                                    # glf_degree_info.shape (grid form)
 
 
+class FilterRequest(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("pix", C.c_int32), ("d_img", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("phi", C.c_void_p), ("lam", C.c_void_p), ("filter_mode", C.c_int32), ("filter_pow", C.c_int32), ("filter_beta", C.c_float),
+                ("gain", C.c_float), ("row0", C.c_uint32), ("row1", C.c_uint32), ("nsig", C.c_int32), ("reserved_", C.c_uint32),
+                ("d_sig", C.c_void_p), ("d_sig_out", C.c_void_p), ("h_c_in", C.c_void_p), ("h_c_out", C.c_void_p), ("h_gram_out", C.c_void_p),
+                ("d_out", C.c_void_p), ("d_zf", C.c_void_p), ("d_corr", C.c_void_p)]
+
+
+class FilterInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kernels", C.c_uint32), ("ld", C.c_uint32), ("panels", C.c_uint32), ("proj_blocks", C.c_uint32),
+                ("apply_blocks", C.c_uint32), ("grid_strided", C.c_uint32), ("reserved_", C.c_uint32), ("pix0", C.c_uint64), ("pix1", C.c_uint64)]
+
+
+# glf_filter_info.kernels
+(FK_PHI_T_Y, FK_PHI_T_SIGNALS, FK_PHI_T_PIX_SIGNALS, FK_PHI_GRAM, FK_APPLY, FK_APPLY_SIGNALS, FK_APPLY_PIX, FK_APPLY_PIX_SIGNALS, FK_PLANES,
+ FK_ACCUM, FK_FINISH) = (1 << i for i in range(11))
+
+
 class BasisStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("passes", C.c_uint32), ("defect_in", C.c_double), ("defect_out", C.c_double)]
 
@@ -276,6 +294,7 @@ _lib.glf_operator_destroy.argtypes = [C.c_void_p]
 _lib.glf_Nystroem_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_Degree_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint, C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_uint,
                                C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+_lib.glf_Filter_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class GlfError(RuntimeError):
@@ -1203,6 +1222,32 @@ class Context:
                                        C.c_void_p(plane.data_ptr()) if plane is not None else None, deg.ctypes.data_as(C.c_void_p),
                                        ysum.ctypes.data_as(C.c_void_p) if ysum is not None else None, C.byref(info)), "Degree_ex")
         return deg, ysum, {k: getattr(info, k) for k, _ in DegreeInfo._fields_}
+
+    def Filter_ex(self, pix, d_img, phi, lam, filter_mode=FILTER_REFERENCE, filter_pow=1, filter_beta=1.5, gain=3.0, rows=None, sig=None,
+                  sig_out=None, c_in=None, c_out=None, gram_out=None, out=None, zf=None, corr=None):
+        """glf_Filter_ex: the filter stage on the dense raster-order glf_mat phi. d_img: the guide as a device tensor in the format
+        pix ([H, W] or [H, W, 3]); lam: host float64 [m]; rows = (row0, row1) (None: all); sig / sig_out: device float32 [nsig, H, W]
+        planes in and out; c_in / c_out: host float64 [channels + nsig, m]; gram_out: host float64 [m, m]; out (required), zf, corr:
+        device tensors the call writes into. Returns the info dict of glf_filter_info; a refusal raises GlfError and leaves every
+        output untouched."""
+        h, w = d_img.shape[:2]
+        lam = np.ascontiguousarray(lam, dtype=np.float64)
+        row0, row1 = (0, 0) if rows is None else rows
+        for a in (c_in, c_out, gram_out):
+            assert a is None or (a.dtype == np.float64 and a.flags.c_contiguous)
+        for t in (sig, sig_out, zf, corr):
+            assert t is None or (t.dtype == self.torch.float32 and t.is_cuda and t.is_contiguous())
+        assert out.is_cuda and out.is_contiguous() and d_img.is_cuda and d_img.is_contiguous()
+        host = lambda a: a.ctypes.data if a is not None else None
+        dev = lambda t: t.data_ptr() if t is not None else None
+        rq = FilterRequest(struct_size=C.sizeof(FilterRequest), pix=pix, d_img=d_img.data_ptr(), width=w, height=h, phi=C.addressof(phi),
+                           lam=lam.ctypes.data, filter_mode=filter_mode, filter_pow=filter_pow, filter_beta=filter_beta, gain=gain, row0=row0,
+                           row1=row1, nsig=0 if sig is None else sig.shape[0], d_sig=dev(sig), d_sig_out=dev(sig_out), h_c_in=host(c_in),
+                           h_c_out=host(c_out), h_gram_out=host(gram_out), d_out=out.data_ptr(), d_zf=dev(zf), d_corr=dev(corr))
+        info = FilterInfo(struct_size=C.sizeof(FilterInfo))
+        self._check(_lib.glf_Filter_ex(self._ctx, C.byref(rq), C.byref(info)), "Filter_ex")
+        self.stream.synchronize()
+        return {k: int(getattr(info, k)) for k, _ in FilterInfo._fields_}
 
     def Permutation(self, mat, sample_indices):
         idx = np.ascontiguousarray(sample_indices, dtype=np.uint32)

@@ -653,6 +653,65 @@ int glf_image_processing_f32_capture(glf_ctx *ctx, const glf_options *opt, const
 int glf_image_processing_rgbf32_capture(glf_ctx *ctx, const glf_options *opt, const float *d_rgb, int width, int height,
                                         float *d_out_rgb, double *eigvals_out, glf_stats *stats, glf_capture *cap);
 
+/* ---- the filter stage on its own ---------------------------------------------------------------------------------------------------
+ * What turns Phi into pixels, on a Phi the caller gives: c = Phi^T x (the projection), w = f(lam) c (filter_mode, filter_pow,
+ * filter_beta and gain as in glf_options, formed as the whole path forms them) and out = rule(x + gain Phi w - ysub x), by the
+ * functions the whole path's unfused filter runs. One rank's share: no all-reduce.
+ *   pix, d_img, width, height: the guide in the pixel format pix (a GLF_PIX_*), device.
+ *   phi: dense N x m, raster rows; ld 32, 64, 128 or 256, or a multiple of 256 above 256 (256-column panels; 8-bit grey guide, no
+ *     planes, no sharpening: GLF_ERR_UNSUPPORTED otherwise, as the whole path answers).
+ *   lam: HOST [m], the eigenvalues.
+ *   row0 == row1 == 0: all image rows; otherwise row0 < row1 <= height, and only the pixels [row0 width, row1 width) are projected
+ *     and written (sharpening needs Phi^T Phi over all rows: a proper row range is GLF_ERR_UNSUPPORTED there).
+ *   nsig, d_sig, d_sig_out: optional device float planes [nsig][N] in and out, 1 <= nsig <= GLF_MAX_SIGNALS (nsig 0: none).
+ *   h_c_in (optional, HOST [channels + nsig][m]): the projection pass is skipped and the weights are formed from it (what a rank
+ *     holds after the all-reduce). h_c_out (optional, same shape): the call's own projection over the row range (h_c_in's values
+ *     when that is given). h_gram_out (optional, HOST [m][m]): Phi^T Phi, written in sharpening mode only.
+ *   d_out: device, the format's output type [N][channels]; d_zf (optional) device float [channels][N]; d_corr (optional, 8-bit grey
+ *     guide only, narrow ld) device float [pixels of the range], as glf_capture.d_corr.
+ *   info (optional): the caller sets struct_size; the call fills the rest with what ran.
+ * A refusal (sample-first phi, bad row range, nsig out of range, m > ld, d_corr with another guide than 8-bit grey, a float guide
+ * holding NaN or Inf, ...) names its reason in glf_ctx_last_error and leaves every output untouched.
+ * glf_ComputeResultFromLaplacian is this call with lam = Pi, the reference filter, all rows and no planes. */
+enum {
+    GLF_FK_PHI_T_Y = 1, GLF_FK_PHI_T_SIGNALS = 2, GLF_FK_PHI_T_PIX_SIGNALS = 4, GLF_FK_PHI_GRAM = 8,
+    GLF_FK_APPLY = 16, GLF_FK_APPLY_SIGNALS = 32, GLF_FK_APPLY_PIX = 64, GLF_FK_APPLY_PIX_SIGNALS = 128,
+    GLF_FK_PLANES = 256, GLF_FK_ACCUM = 512, GLF_FK_FINISH = 1024
+};
+typedef struct glf_filter_request {
+    uint32_t struct_size;   /* sizeof(glf_filter_request) */
+    int32_t  pix;
+    const void *d_img;
+    int32_t  width, height;
+    const glf_mat *phi;
+    const double *lam;
+    int32_t  filter_mode, filter_pow;
+    float    filter_beta, gain;
+    uint32_t row0, row1;
+    int32_t  nsig;
+    uint32_t reserved_;
+    const float *d_sig;
+    float *d_sig_out;
+    const double *h_c_in;
+    double *h_c_out;
+    double *h_gram_out;
+    void  *d_out;
+    float *d_zf;
+    float *d_corr;
+} glf_filter_request;
+typedef struct glf_filter_info {
+    uint32_t struct_size;
+    uint32_t kernels;       /* GLF_FK_* bits of the kernels launched */
+    uint32_t ld;            /* the LD instantiation of the apply kernel (256 for the panels) */
+    uint32_t panels;        /* 256-column panels (0: narrow ld) */
+    uint32_t proj_blocks;   /* workgroups of the (last) projection launch, 0 when h_c_in stood in for it */
+    uint32_t apply_blocks;  /* workgroups of the (last) apply / accumulate launch */
+    uint32_t grid_strided;  /* 1: that launch was capped at 8192 workgroups and strides the rest */
+    uint32_t reserved_;
+    uint64_t pix0, pix1;    /* the pixels projected and written */
+} glf_filter_info;
+int glf_Filter_ex(glf_ctx *ctx, const glf_filter_request *rq, glf_filter_info *info);
+
 /* ---- graph handle: build the eigenbasis once, project and synthesize many ------------------------------------------------------
  * Every entry point above builds the graph, solves for the eigenpairs, extends them to every pixel, applies one spectral response
  * and discards everything. The operator is z = ident s + Phi diag(g(mu)) Phi^T s: once Phi exists, any response on any plane is
