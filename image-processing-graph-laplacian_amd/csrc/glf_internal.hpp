@@ -128,6 +128,7 @@ struct glf_graph {
     int robust_blocks_per_cu = 0;    // k_graph_residual_weight<ld>'s, asked at the first robust step
     int quad_blocks_per_cu[2] = {0, 0}; // k_graph_quadform<ld, T, NB>'s at [NB - 1], asked at the first quadratic form of that width
     int edges_blocks_per_cu[2] = {0, 0}; // k_graph_edges<ld, T>'s at [storage], asked at the first edge map in that storage
+    int classify_blocks_per_cu[2] = {0, 0}; // k_graph_classify<ld, T>'s at [storage], asked at the first read-out in that storage
     std::vector<unsigned> samples;       // [p] the sample pixels of the build call, ascending: its own sampler call's list (glf_graph_samples)
 };
 

@@ -71,6 +71,7 @@ EXPORTS = [
     "glf_graph_compact", "glf_graph_storage", "glf_graph_dequantize",
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
     "glf_graph_edges", "glf_graph_samples",
+    "glf_graph_classify",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex", "glf_Degree_ex", "glf_Filter_ex",
 ]
@@ -96,6 +97,7 @@ GRAPH_NORMAL_CHAIN = 128   # GLF_GRAPH_NORMAL_CHAIN: the longest f32 chain (pixe
 QUAD_MAX_COLS = 64         # GLF_QUAD_MAX_COLS: the most columns of R of one glf_graph_quadform call
 QUAD_MAX_CENTRES = 32      # GLF_QUAD_MAX_CENTRES: the most centres of one glf_graph_quadform call
 EDGE_DIRS = {"E": 1, "S": 2, "SE": 4, "SW": 8}   # GLF_EDGE_*: the neighbour (row, col+1), (row+1, col), (row+1, col+1), (row+1, col-1)
+CLASSIFY_MAX = 32          # GLF_CLASSIFY_MAX: the most classes of one glf_graph_classify call
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -286,6 +288,8 @@ _lib.glf_fit_factor.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_rows.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_graph_edges.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_samples.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_classify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
 _lib.glf_operator_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_operator_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_double, C.c_int, C.c_void_p]
@@ -2040,6 +2044,93 @@ class Graph:
         self.ctx._check(_lib.glf_graph_synthesize(self._g, C.c_int(nout), _ptr(a), _ptr(idn), _ptr(pl), C.c_int(nplanes),
                                                   C.c_void_p(planes.data_ptr()) if planes is not None else None,
                                                   C.c_void_p(out.data_ptr())), "graph synthesize")   # (returns with the stream drained)
+        return out
+
+    def classify(self, coeffs, ident=None, plane=None, planes=None, bias=None, want=("label",)):
+        """The label read-out of the k scores z_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (+ bias[j]) in one pass over Phi
+        (glf_graph_classify): the score planes synthesize would write are formed in registers and reduced per pixel. coeffs [k, m]
+        (k <= CLASSIFY_MAX), ident / plane / planes as in synthesize, bias [k] or None; want: any of "label", "best", "margin".
+        -> dict of device tensors [H, W]: label int32 (the lowest index among equal best scores; a NaN score never wins), best
+        float32 (without a bias: synthesize's winning output, bit for bit), margin float32 = best - runner-up (+0 on a tie, +inf
+        for k = 1)."""
+        t = self.ctx.torch
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        k, h, w = a.shape[0], self.info["height"], self.info["width"]
+        if a.shape[1] != self.info["m"]:
+            raise ValueError("coeffs must be [k, %d], got %s" % (self.info["m"], a.shape))
+        if k > CLASSIFY_MAX:
+            raise ValueError("classify takes at most %d classes (CLASSIFY_MAX), got %d" % (CLASSIFY_MAX, k))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(key not in ("label", "best", "margin") for key in want):
+            raise ValueError('want must name at least one of "label", "best", "margin", got %r' % (want,))
+        pl = np.full(k, -1, dtype=np.int32) if plane is None else np.ascontiguousarray(plane, dtype=np.int32)
+        idn = np.zeros(k, dtype=np.float32) if ident is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ident, dtype=np.float32), (k,)))
+        if pl.shape != (k,):
+            raise ValueError("plane must be [%d]" % k)
+        bs = None
+        if bias is not None:
+            bs = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (k,)))
+        nplanes = 0
+        if planes is not None:
+            planes = self._planes(planes)
+            nplanes = planes.shape[0]
+        with t.cuda.stream(self.ctx.stream):
+            out = {key: t.empty((h, w), dtype=t.int32 if key == "label" else t.float32, device=self.ctx.device) for key in want}   # (every element is written)
+        ptr = {key: C.c_void_p(out[key].data_ptr()) if key in out else None for key in ("label", "best", "margin")}
+        self.ctx._check(_lib.glf_graph_classify(self._g, C.c_int(k), _ptr(a), _ptr(idn), _ptr(pl), C.c_int(nplanes),
+                                                C.c_void_p(planes.data_ptr()) if planes is not None else None, _ptr(bs),
+                                                ptr["label"], ptr["best"], ptr["margin"]), "graph classify")   # (returns with the stream drained)
+        return out
+
+    def refine_logits(self, logits, response=None, ident=1.0, bias=None, want=("label", "margin")):
+        """argmax_j (ident * logit_j + Phi diag(response) Phi^T logit_j) without writing the filtered logits: one project_wide, the
+        scaling on the host, one classify with the logits as identity planes. logits: device float32 [k, H, W], k <= CLASSIFY_MAX;
+        response: g [m], default 1 - lam (distance's default); ident a float or [k]. -> classify's dict."""
+        k = logits.shape[0]
+        if k > CLASSIFY_MAX:
+            raise ValueError("refine_logits takes at most %d classes (CLASSIFY_MAX), got %d" % (CLASSIFY_MAX, k))
+        m = self.info["m"]
+        g = np.asarray(1.0 - self.eigenvalues if response is None else response, dtype=np.float64)
+        if g.shape != (m,):
+            raise ValueError("response must be [%d], got %s" % (m, g.shape))
+        c = self.project_wide(logits)
+        return self.classify(g[None, :] * c, ident, np.arange(k, dtype=np.int32), logits, bias, want)
+
+    def propagate_labels(self, seeds, k, weight=None, smooth=0.0, ridge=0.0, bias=None, want=("label", "margin")):
+        """Scribbles to a label map: the weighted least-squares fit of the k one-hot seed planes in the span of Phi (fit's system,
+        fit's penalty rule), read out by one classify with no identity term; the fitted planes are never written. seeds: device
+        integer [H, W], -1 where unlabelled, else the class in 0 .. k - 1 (k <= CLASSIFY_MAX; every class needs a seed); weight:
+        device float32 [H, W] or None (= 1), it counts on the seed pixels only. One normal_equations for G_w, one project_wide of
+        the one-hot planes for b, fit_coeffs on the host. -> classify's dict plus coeffs [k, m]."""
+        t = self.ctx.torch
+        k = int(k)
+        h, w = self.info["height"], self.info["width"]
+        if not 1 <= k <= CLASSIFY_MAX:
+            raise ValueError("propagate_labels takes 1 .. %d classes (CLASSIFY_MAX), got %d" % (CLASSIFY_MAX, k))
+        assert seeds.is_cuda and not seeds.is_floating_point()
+        if tuple(seeds.shape) != (h, w):
+            raise ValueError("seeds must be [%d, %d], got %s" % (h, w, tuple(seeds.shape)))
+        if weight is not None:
+            weight = self._weight(weight)
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the seeds are complete before they are read here
+        with t.cuda.stream(self.ctx.stream):
+            sd = seeds.to(t.int64)
+            lo, hi = int(sd.min()), int(sd.max())
+            if lo < -1 or hi > k - 1:
+                raise ValueError("seeds must lie in -1 .. %d, got %d .. %d" % (k - 1, lo, hi))
+            onehot = (sd[None, :, :] == t.arange(k, device=sd.device)[:, None, None]).to(t.float32).contiguous()
+            counts = onehot.sum(dim=(1, 2)).cpu().numpy()
+            if (counts == 0).any():
+                raise ValueError("propagate_labels: class %d has no seed" % int(np.flatnonzero(counts == 0)[0]))
+            wm = (sd >= 0).to(t.float32)
+            if weight is not None:
+                wm = wm * weight
+            wm = wm.contiguous()
+        G = self.normal_equations(wm)[0]
+        b = self.project_wide(onehot, wm)
+        a = fit_coeffs(G, b, self._penalty(G, smooth, ridge, None))
+        out = self.classify(a, bias=bias, want=want)
+        out["coeffs"] = a
         return out
 
     def _labels(self, labels, what):

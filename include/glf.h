@@ -1144,6 +1144,49 @@ int glf_graph_edges(glf_graph *g, unsigned dirs, unsigned dim, const double *h_s
  * in glf_ctx_last_error. */
 int glf_graph_samples(const glf_graph *g, unsigned *h_idx /* HOST [p], ascending pixel indices */);
 
+/* ---- graph handle: label read-out, the per-pixel winner of up to 32 score planes and its margin -----------------------------------------
+ * Supervised labelling on a handle -- scribbles propagated to every pixel, a network's class logits smoothed through the graph, a
+ * stack of depth hypotheses resolved per pixel -- ends in one step: form the k score planes ident_j s_j + Phi a_j and take, per
+ * pixel, the winner and how clearly it won. glf_graph_classify forms the scores in registers in one pass over Phi
+ * (k_graph_classify: glf_graph_synthesize's kernel up to its store) and writes up to three planes, the label, the best score and
+ * the margin, instead of the k score planes a caller would write with glf_graph_synthesize and read back for an argmax.
+ * Scores, operation by operation. h_a, ident, plane, nplanes and d_planes mean what they mean in glf_graph_synthesize: acc_j =
+ * sum_c Phi[px][c] fl32(a_j[c]) on v_mfma_f32_32x32x2_f32 in its contraction order; z_j = fmaf(ident[j], planes[plane[j]][px], acc_j)
+ * where plane[j] >= 0 and z_j = acc_j otherwise. With h_bias = NULL score_j = z_j has the bits of glf_graph_synthesize's output j;
+ * with a bias score_j = z_j + fl32(bias_j), one f32 addition (a bias of zeros therefore turns a score of -0 into +0 and changes
+ * nothing else).
+ * Read-out, in f32, nothing contracted that is not written here. Comparisons are IEEE: a NaN compares false, +0 and -0 are equal.
+ *   best  = max_j score_j under a strict >, from -inf with label 0: b = -inf, l = 0; for j = 0 .. k - 1 ascending: if score_j > b
+ *           then b = score_j, l = j. A NaN score never wins; of equal scores the lowest j wins (+0 and -0 tie, and best keeps the
+ *           sign of the winner's); a pixel with no score above -inf gets label 0 and best -inf.
+ *   label = l, the lowest j < k with score_j == best where there is one.
+ *   second = the same maximum over j != label, from -inf.
+ *   margin = +0 where second == best (a tie, two infinities of one sign, and best = -inf: never a NaN and never -0), else
+ *           best - second, one f32 subtraction: +inf for k = 1 and wherever second is -inf and best is not.
+ * How the kernel gets there: a lane holds the 16 scores j = (g & 3) + 8 (g >> 2) + 4 h, g < 16, of its pixel in half-wave h and
+ * runs the top two over g ascending (s > b: second = b, b = s, l = j; else s > second: second = s); one exchange with the other
+ * half-wave; the other half wins if b' > b or (b' == b and l' < l); second = max(min(b, b'), max(second, second')). The slots
+ * j >= k are masked by index: whatever they hold, they change nothing. The result is the sequential rule above for every input,
+ * NaN and infinities included (tests/test_classify_ref.py restates both and compares them).
+ * A class takes part in the same way in every slot; only the tie rule sees the order. Two calls give the same bits; no atomics;
+ * rows past N are neither read nor stored; an output whose pointer is NULL is not written, every pixel of the others is. Phi is
+ * read once at every ld, the identity planes once per class that names them (where any class has an identity term, a class
+ * without one reads plane 0's pixel and drops it: the loads are unconditional so that they are all in flight together).
+ * On a compact handle 2^e_c is folded into a_j[c] in f64 before its fl32 (glf_graph_synthesize's rule), so the scores are that
+ * handle's own synthesize outputs bit for bit, and the call returns what it returns on an f32 handle whose Phi is Q.
+ * Out of scope: softmax or temperature confidences, per-class counts, k > GLF_CLASSIFY_MAX and merging across groups, a label
+ * input to the projection, mean-field or CRF iterations, contexts with a communicator and glf_multi_* (handles refuse them),
+ * m > 256, a flag of the image_processing host program. */
+#define GLF_CLASSIFY_MAX 32   /* = GLF_GRAPH_MAX_OUTPUTS */
+/* GLF_ERR_INVALID before any device work, every output untouched, the reason in glf_ctx_last_error: k outside 1 ..
+ * GLF_CLASSIFY_MAX, a NULL h_a or plane, nplanes < 0, a plane[j] outside -1 .. nplanes - 1, an identity term with a NULL ident or
+ * d_planes, all three output pointers NULL, a coefficient (after folding) or a bias whose fl32 is not finite; a NULL handle
+ * likewise (there is no context to take the reason). The planes are not checked. Returns with the stream drained. */
+int glf_graph_classify(glf_graph *g, int k, const double *h_a /* HOST [k][m] */, const float *ident /* HOST [k] */,
+                       const int *plane /* HOST [k] */, int nplanes, const float *d_planes /* device [nplanes][N] */,
+                       const double *h_bias /* HOST [k] or NULL */, int32_t *d_label /* device [N] or NULL */,
+                       float *d_best /* device [N] or NULL */, float *d_margin /* device [N] or NULL */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
