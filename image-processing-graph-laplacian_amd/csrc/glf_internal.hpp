@@ -9,7 +9,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/glf.h"
@@ -122,13 +124,9 @@ struct glf_graph {
     int32_t *d_expo = nullptr; // device [ld], the same (glf_malloc): the row gathers of the drivers read it
     std::vector<double> lam;   // [m]
     std::vector<double> gram;  // [m][m] Phi^T Phi, filled by the first glf_graph_gram
-    int synth_blocks_per_cu = 0;   // k_graph_synthesize<ld>'s resident workgroups per CU, asked of the runtime at the first synthesize
-    int cluster_blocks_per_cu[3] = {0, 0, 0}; // k_graph_cluster<CW, MODE>'s at [MODE], asked at the first cluster step in that mode
-    int transform_blocks_per_cu = 0; // k_graph_transform<ld>'s, asked at the first transform
-    int robust_blocks_per_cu = 0;    // k_graph_residual_weight<ld>'s, asked at the first robust step
-    int quad_blocks_per_cu[2] = {0, 0}; // k_graph_quadform<ld, T, NB>'s at [NB - 1], asked at the first quadratic form of that width
-    int edges_blocks_per_cu[2] = {0, 0}; // k_graph_edges<ld, T>'s at [storage], asked at the first edge map in that storage
-    int classify_blocks_per_cu[2] = {0, 0}; // k_graph_classify<ld, T>'s at [storage], asked at the first read-out in that storage
+    // resident workgroups per CU of the handle's tile kernels, by kernel (the host stub's address: one entry per instance, whatever its
+    // storage, width or mode), asked of the runtime at a kernel's first launch (resident_tile_grid)
+    std::vector<std::pair<const void *, int>> grid_cache;
     std::vector<unsigned> samples;       // [p] the sample pixels of the build call, ascending: its own sampler call's list (glf_graph_samples)
 };
 
@@ -184,23 +182,36 @@ inline int set_error(glf_ctx *ctx, int status, const char *fmt, ...)
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
 inline int64_t ceil_div(int64_t x, int64_t q) { return (x + q - 1) / q; }
 // The grid of the graph-handle kernels that take one tile of 32 pixels per wave, four waves per workgroup, the tiles strided over
-// a resident grid: min(ceil(ceil(N / 32) / 4), what fits the device at once), the rest of the tiles by the grid stride. *per_cu
-// caches the kernel's resident workgroups per CU, asked of the runtime at the first launch.
+// a resident grid: min(ceil(ceil(N / 32) / 4), what fits the device at once), the rest of the tiles by the grid stride. The kernel's
+// resident workgroups per CU come from the handle's grid_cache, asked of the runtime at the kernel's first launch.
 template <class Kernel>
-inline int resident_tile_grid(glf_ctx *ctx, int *per_cu, Kernel kernel, int64_t N, int64_t *nblk)
+inline int resident_tile_grid(glf_graph *g, Kernel kernel, int64_t N, int64_t *nblk)
 {
-    if (*per_cu <= 0) {
-        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(per_cu, kernel, 256, 0));
-        *per_cu = *per_cu > 1 ? *per_cu : 1;
+    glf_ctx *ctx = g->ctx;
+    const void *key = reinterpret_cast<const void *>(kernel);
+    int per_cu = 0;
+    for (const auto &e : g->grid_cache)
+        if (e.first == key) per_cu = e.second;
+    if (per_cu <= 0) {
+        GLF_HIP(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0));
+        per_cu = per_cu > 1 ? per_cu : 1;
+        g->grid_cache.emplace_back(key, per_cu);
     }
     const int64_t cus = ctx->prop.multiProcessorCount > 1 ? ctx->prop.multiProcessorCount : 1, tiles4 = ceil_div(ceil_div(N, 32), 4);
-    *nblk = tiles4 < *per_cu * cus ? tiles4 : *per_cu * cus;
+    *nblk = tiles4 < per_cu * cus ? tiles4 : per_cu * cus;
     return GLF_OK;
 }
 inline bool all_finite(const double *x, size_t n)
 {
     for (size_t e = 0; e < n; ++e)
         if (!std::isfinite(x[e])) return false;
+    return true;
+}
+// |x| fits an f32 (its fl32 is finite)
+inline bool all_fl32_finite(const double *x, size_t n)
+{
+    for (size_t e = 0; e < n; ++e)
+        if (!(std::fabs(x[e]) <= (double)std::numeric_limits<float>::max())) return false;
     return true;
 }
 // Leading dimension of vector blocks: m rounded up to a power of two in {32,64,128,256}

@@ -75,27 +75,6 @@ __global__ __launch_bounds__(256) void k_graph_synthesize(const T *__restrict__ 
     }
 }
 
-template <int LD, class T>
-static int launch_synthesize(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, int nout, const float *d_operand, const float *d_planes,
-                             float *d_out)
-{
-    int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_synthesize<LD, T>, N, &nblk));
-    hipLaunchKernelGGL((k_graph_synthesize<LD, T>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, nout, d_operand, d_planes, d_out);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
-template <class T>
-static int graph_synthesize(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, unsigned ld, int nout, const float *d_operand,
-                            const float *d_planes, float *d_out)
-{
-    int rc = GLF_OK;
-    if (!dispatch_ld(ld, [&](auto LD) { rc = launch_synthesize<LD.value>(ctx, per_cu, d_phi, N, nout, d_operand, d_planes, d_out); }))
-        return set_error(ctx, GLF_ERR_INVALID, "graph_synthesize: ld=%u", ld);
-    return rc;
-}
-
 template <class T>
 __global__ void k_sample_rows(const T *__restrict__ phi, const int *__restrict__ expo, int64_t N, int ld, int dim, int nplanes,
                               const float *__restrict__ planes, const float *__restrict__ w, int wcol, int64_t ns, float *__restrict__ out)
@@ -119,7 +98,7 @@ int graph_sample_rows(glf_graph *g, int dim, int nplanes, const float *d_planes,
     glf_ctx *ctx = g->ctx;
     const int64_t N = (int64_t)g->width * g->height, cnt = ns * (dim + nplanes + wcol);
     dispatch_phi(g, [&](auto *phi) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>;
+        using T = phi_elem_t<decltype(phi)>;
         hipLaunchKernelGGL(k_sample_rows<T>, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, ctx->stream, phi, (const int *)g->d_expo, N, (int)g->ld, dim,
                            nplanes, d_planes, d_w, wcol, ns, d_out);
     });
@@ -132,7 +111,7 @@ int graph_gather_rows(glf_graph *g, int dim, unsigned nrows, const int64_t *h_px
     glf_ctx *ctx = g->ctx;
     // the sample of one row of a one-row Phi that starts at the pixel: k_sample_rows' own reads, nothing new on the device
     dispatch_phi(g, [&](auto *phi) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>;
+        using T = phi_elem_t<decltype(phi)>;
         for (unsigned i = 0; i < nrows; ++i)
             hipLaunchKernelGGL(k_sample_rows<T>, dim3((unsigned)ceil_div(dim, 256)), dim3(256), 0, ctx->stream, phi + (size_t)h_px[i] * g->ld,
                                (const int *)g->d_expo, (int64_t)1, (int)g->ld, dim, 0, (const float *)nullptr, (const float *)nullptr, 0, (int64_t)1,
@@ -298,33 +277,21 @@ int glf_graph_synthesize(glf_graph *g, int nout, const double *h_a, const float 
 {
     if (!g || nout < 1 || nout > GLF_GRAPH_MAX_OUTPUTS || !h_a || !plane || !d_out || nplanes < 0) return GLF_ERR_INVALID;
     bool any_plane = false;
-    for (int j = 0; j < nout; ++j) {
-        if (plane[j] < -1 || plane[j] >= nplanes) return GLF_ERR_INVALID;
-        any_plane = any_plane || plane[j] >= 0;
-    }
-    if (any_plane && (!ident || !d_planes)) return GLF_ERR_INVALID;
+    if (ident_terms_check(nout, plane, nplanes, ident, d_planes, &any_plane) >= 0) return GLF_ERR_INVALID;
     glf_ctx *ctx = g->ctx;
-    const unsigned m = g->m, ld = g->ld;
+    const unsigned ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
     GLF_ENTER(ctx);
-    // (a compact handle: the column scales folded into the coefficients in f64, before their fl32)
-    std::vector<double> a(h_a, h_a + (size_t)nout * m);
-    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)nout, m, g->expo.data());
     std::vector<float> h_op(gs_operand_floats(ld), 0.f);
-    int h_plane[GS_OUT];
-    for (int j = 0; j < GS_OUT; ++j) h_plane[j] = -1;
-    for (int j = 0; j < nout; ++j) {
-        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GS_OUT + j] = (float)a[(size_t)j * m + k];
-        if (plane[j] >= 0) {
-            h_op[(size_t)ld * GS_OUT + j] = ident[j];
-            h_plane[j] = plane[j];
-        }
-    }
-    std::memcpy(h_op.data() + (size_t)ld * GS_OUT + GS_OUT, h_plane, sizeof(h_plane));
+    coeff_operand(g, (size_t)nout, h_a, GS_OUT, h_op.data());
+    ident_terms_pack(nout, ident, plane, h_op.data() + (size_t)ld * GS_OUT);
     DevBuf<float> op;
     GLF_TRY(upload_operand(ctx, op, h_op));
     int rc = GLF_OK;
-    dispatch_phi(g, [&](auto *phi) { rc = graph_synthesize(ctx, &g->synth_blocks_per_cu, phi, N, ld, nout, op.p, d_planes, d_out); });
+    if (!dispatch_phi_ld(g, [&](auto LD, auto *phi, auto t) {
+            rc = launch_tiles(g, k_graph_synthesize<LD.value, decltype(t)>, N, phi, N, nout, (const float *)op.p, d_planes, d_out);
+        }))
+        return set_error(ctx, GLF_ERR_INVALID, "graph_synthesize: ld=%u", ld);
     GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)
     return GLF_OK;

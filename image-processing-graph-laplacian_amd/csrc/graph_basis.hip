@@ -155,16 +155,6 @@ __global__ __launch_bounds__(256) void k_graph_transform(float *phi, int64_t N, 
 #undef GT_LOAD_HALF
 #undef GT_STORE_HALF
 
-template <int LD>
-static int launch_transform(glf_ctx *ctx, int *per_cu, float *d_phi, int64_t N, unsigned m_new, const float *d_operand)
-{
-    int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_transform<LD>, N, &nblk));
-    hipLaunchKernelGGL(k_graph_transform<LD>, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)m_new, d_operand);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
 // max |G - I| of an [m][m] matrix
 static double gram_defect(const std::vector<double> &G, unsigned m)
 {
@@ -205,7 +195,7 @@ int glf_graph_transform(glf_graph *g, unsigned m_new, const double *h_T, const d
     // from here on a failure leaves Phi unspecified: the handle's cached Gram matrix goes first
     g->gram.clear();
     int rc = GLF_OK;
-    if (!dispatch_ld(ld, [&](auto LD) { rc = launch_transform<LD.value>(ctx, &g->transform_blocks_per_cu, g->phi, N, m_new, op.p); }))
+    if (!dispatch_ld(ld, [&](auto LD) { rc = launch_tiles(g, k_graph_transform<LD.value>, N, g->phi, N, (int)m_new, (const float *)op.p); }))
         return set_error(ctx, GLF_ERR_INVALID, "glf_graph_transform: ld=%u", ld);
     GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)

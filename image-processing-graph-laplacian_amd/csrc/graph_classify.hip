@@ -9,7 +9,6 @@
 #include "phi_tile.hpp"
 #include "phi_compact.hpp"
 
-#include <cfloat>
 #include <cmath>
 
 // the arithmetic of the epilogue is pinned operation by operation (include/glf.h): nothing here is contracted into an fma that the
@@ -151,26 +150,6 @@ __global__ __launch_bounds__(256) void k_graph_classify(const T *__restrict__ ph
     }
 }
 
-template <int LD, class T>
-static int launch_classify(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, int k, const float *d_operand, const float *d_planes,
-                           int32_t *d_label, float *d_best, float *d_margin)
-{
-    int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_classify<LD, T>, N, &nblk));
-    hipLaunchKernelGGL((k_graph_classify<LD, T>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, k, d_operand, d_planes, d_label,
-                       d_best, d_margin);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
-// |x| fits an f32 (its fl32 is finite)
-static bool all_fl32_finite(const double *x, size_t n)
-{
-    for (size_t e = 0; e < n; ++e)
-        if (!(std::fabs(x[e]) <= (double)FLT_MAX)) return false;
-    return true;
-}
-
 } // namespace glf
 
 using namespace glf;
@@ -186,43 +165,28 @@ int glf_graph_classify(glf_graph *g, int k, const double *h_a, const float *iden
     if (!h_a || !plane || nplanes < 0) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: h_a or plane is NULL, or nplanes < 0");
     if (!d_label && !d_best && !d_margin) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: no output was asked for");
     bool any_plane = false;
-    for (int j = 0; j < k; ++j) {
-        if (plane[j] < -1 || plane[j] >= nplanes)
-            return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: plane[%d] = %d outside -1 .. %d", j, plane[j], nplanes - 1);
-        any_plane = any_plane || plane[j] >= 0;
-    }
-    if (any_plane && (!ident || !d_planes)) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: identity planes without ident or d_planes");
-    const unsigned m = g->m, ld = g->ld;
+    const int bad = ident_terms_check(k, plane, nplanes, ident, d_planes, &any_plane);
+    if (bad >= 0 && bad < k)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: plane[%d] = %d outside -1 .. %d", bad, plane[bad], nplanes - 1);
+    if (bad == k) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: identity planes without ident or d_planes");
+    const unsigned ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
-    // (a compact handle: the column scales folded into the coefficients in f64, before their fl32: glf_graph_synthesize's rule)
-    std::vector<double> a(h_a, h_a + (size_t)k * m);
-    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)k, m, g->expo.data());
+    std::vector<float> h_op(gy_operand_floats(ld), 0.f);
+    const std::vector<double> a = coeff_operand(g, (size_t)k, h_a, GY_K, h_op.data());
     if (!all_fl32_finite(a.data(), a.size()))
         return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: a coefficient (folded with its column's 2^e_c) is not finite in f32");
     if (h_bias && !all_fl32_finite(h_bias, (size_t)k)) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: a bias is not finite in f32");
     GLF_ENTER(ctx);
-    std::vector<float> h_op(gy_operand_floats(ld), 0.f);
-    int h_tail[GY_K + 4];
-    for (int j = 0; j < GY_K; ++j) h_tail[j] = -1;
     float *op_ident = h_op.data() + (size_t)ld * GY_K, *op_bias = op_ident + 2 * GY_K;
-    for (int j = 0; j < k; ++j) {
-        for (unsigned c = 0; c < m; ++c) h_op[(size_t)c * GY_K + j] = (float)a[(size_t)j * m + c];
-        if (plane[j] >= 0) {
-            op_ident[j] = ident[j];
-            h_tail[j] = plane[j];
-        }
-        if (h_bias) op_bias[j] = (float)h_bias[j];
-    }
-    std::memcpy(op_ident + GY_K, h_tail, sizeof(int) * GY_K);
+    ident_terms_pack(k, ident, plane, op_ident);
+    for (int j = 0; h_bias && j < k; ++j) op_bias[j] = (float)h_bias[j];
     const int flags[4] = {(h_bias ? GY_BIAS : 0) | (any_plane ? GY_PLANES : 0), 0, 0, 0};
     std::memcpy(op_bias + GY_K, flags, sizeof(flags));
     DevBuf<float> op;
     GLF_TRY(upload_operand(ctx, op, h_op));
     int rc = GLF_ERR_INVALID;
-    dispatch_phi(g, [&](auto *phi) {
-        using T = std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>;
-        int *per_cu = &g->classify_blocks_per_cu[std::is_same<T, __half>::value ? 1 : 0];
-        dispatch_ld(ld, [&](auto LD) { rc = launch_classify<LD.value, T>(ctx, per_cu, phi, N, k, op.p, d_planes, d_label, d_best, d_margin); });
+    dispatch_phi_ld(g, [&](auto LD, auto *phi, auto t) {
+        rc = launch_tiles(g, k_graph_classify<LD.value, decltype(t)>, N, phi, N, k, (const float *)op.p, d_planes, d_label, d_best, d_margin);
     });
     if (rc == GLF_ERR_INVALID) return set_error(ctx, GLF_ERR_INVALID, "glf_graph_classify: ld=%u", ld);
     GLF_TRY(rc);

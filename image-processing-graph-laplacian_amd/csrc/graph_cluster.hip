@@ -22,7 +22,6 @@ static_assert(GC_K == 32, "the centroids fill exactly one MFMA tile");
 //   GC_WEIGHT  rinv = 1, w = the weight plane
 //   GC_NORM    rinv = 1 / |scale o Phi[px]| (unit-length rows), w = the weight plane, or 1 where there is none (a run-time NULL check)
 enum { GC_PLAIN = 0, GC_WEIGHT = 1, GC_NORM = 2, GC_MODES = 3 };
-static_assert(GC_MODES == sizeof(glf_graph::cluster_blocks_per_cu) / sizeof(int), "one cached occupancy per mode");
 
 // the per-call operand block of k_graph_cluster (device):
 //   [CW][32] float  fl32(scale_c cent_j[c]) at [c][j], zero for j >= k and c >= dim
@@ -245,20 +244,6 @@ static cluster_kernel<T> gc_kernel(int cw, int mode)
     return kernels[cw == 64][mode];
 }
 
-// the launch of one Lloyd iteration on Phi as stored (queued)
-template <class T>
-static int launch_cluster(glf_graph *g, const T *d_phi, int cw, int mode, int64_t N, unsigned k, const float *d_op, const float *d_weight,
-                          const int32_t *d_prev, int32_t *d_labels, DevBuf<double> &part, int64_t *nblk)
-{
-    glf_ctx *ctx = g->ctx;
-    const cluster_kernel<T> kernel = gc_kernel<T>(cw, mode);
-    GLF_TRY(resident_tile_grid(ctx, &g->cluster_blocks_per_cu[mode], kernel, N, nblk));
-    GLF_TRY(part.alloc(ctx, (size_t)*nblk * gc_part_cols(cw, mode)));
-    hipLaunchKernelGGL(kernel, dim3((unsigned)*nblk), dim3(256), 0, ctx->stream, d_phi, N, (int)g->ld, (int)k, d_op, d_weight, d_prev, d_labels, part.p);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
 // what the steps and the drivers refuse alike, before any device work
 static bool cluster_shape_ok(const glf_graph *g, unsigned k, unsigned dim, const double *scale)
 {
@@ -304,7 +289,10 @@ static int cluster_step(glf_graph *g, int mode, const float *d_weight, unsigned 
     const size_t ncols = gc_part_cols(cw, mode);
     int64_t nblk = 0;
     int rc = GLF_OK;
-    dispatch_phi(g, [&](auto *phi) { rc = launch_cluster(g, phi, cw, mode, N, k, op.p, d_weight, d_prev, d_labels, part, &nblk); });
+    dispatch_phi(g, [&](auto *phi) {
+        rc = launch_tiles_partials(g, gc_kernel<phi_elem_t<decltype(phi)>>(cw, mode), N, part, ncols, &nblk, phi, N, (int)ld, (int)k, (const float *)op.p,
+                                   d_weight, d_prev, d_labels);
+    });
     GLF_TRY(rc);
     std::vector<double> h_tot;
     GLF_TRY(sum_partials_to_host(ctx, part, (int)nblk, ncols, tot, h_tot)); // (the one read-back of an iteration; h_op and the buffers go out of scope)

@@ -139,9 +139,6 @@ static int graph_compact_f16(glf_graph *g)
     g->expo.swap(expo);
     g->storage = GLF_PHI_F16;
     g->gram.clear();
-    // the cached occupancies are those of the f32 instances
-    g->synth_blocks_per_cu = g->transform_blocks_per_cu = g->robust_blocks_per_cu = 0;
-    for (int &x : g->cluster_blocks_per_cu) x = 0;
     return GLF_OK;
 }
 

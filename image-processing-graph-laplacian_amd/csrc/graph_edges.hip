@@ -208,19 +208,6 @@ __global__ __launch_bounds__(256) void k_graph_edges(const T *__restrict__ phi, 
     }
 }
 
-template <int LD, class T>
-static int launch_edges(glf_ctx *ctx, int *per_cu, const T *d_phi, int W, int H, unsigned dirs, int dim, const float *d_scale, const uint8_t *d_valid,
-                        float *d_out)
-{
-    // one wave per (strip, row block) unit where resident_tile_grid counts one wave per 32-pixel tile
-    const int64_t units = ceil_div(W, GE_STRIP) * ceil_div(H, GE_ROWS);
-    int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_edges<LD, T>, units * 32, &nblk));
-    hipLaunchKernelGGL((k_graph_edges<LD, T>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, W, H, dirs, dim, d_scale, d_valid, d_out);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
 } // namespace glf
 
 using namespace glf;
@@ -246,12 +233,11 @@ int glf_graph_edges(glf_graph *g, unsigned dirs, unsigned dim, const double *h_s
     for (unsigned c = 0; c < dim; ++c) h_op[c] = (float)sc[c];
     DevBuf<float> op;
     GLF_TRY(upload_operand(ctx, op, h_op));
+    // one wave per (strip, row block) unit where resident_tile_grid counts one wave per 32-pixel tile
+    const int64_t units = ceil_div(g->width, GE_STRIP) * ceil_div(g->height, GE_ROWS);
     int rc = GLF_ERR_INVALID;
-    dispatch_phi(g, [&](auto *phi) {
-        dispatch_ld(ld, [&](auto LD) {
-            rc = launch_edges<LD.value, std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>>(ctx, &g->edges_blocks_per_cu[g->storage == GLF_PHI_F16], phi, g->width, g->height, dirs,
-                                                                                                (int)dim, op.p, d_valid, d_out);
-        });
+    dispatch_phi_ld(g, [&](auto LD, auto *phi, auto t) {
+        rc = launch_tiles(g, k_graph_edges<LD.value, decltype(t)>, units * 32, phi, g->width, g->height, dirs, (int)dim, (const float *)op.p, d_valid, d_out);
     });
     GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)

@@ -9,7 +9,7 @@
 #include "phi_tile.hpp"
 #include "phi_compact.hpp"
 
-#include <cfloat>
+#include <algorithm>
 #include <cmath>
 
 // the arithmetic of the epilogue is pinned operation by operation (include/glf.h): nothing here is contracted into an fma that the
@@ -21,9 +21,6 @@ namespace glf {
 constexpr int GQ_COLS = GLF_QUAD_MAX_COLS;     // columns of R in one launch: two accumulator tiles
 constexpr int GQ_CENT = GLF_QUAD_MAX_CENTRES;  // centres of one launch
 static_assert(GQ_COLS == 64 && GQ_CENT == 32, "two 32-row tiles of the M index; the centre image is [32][2][32] floats at most");
-
-// the row of the accumulator tile that register g of half-wave h holds (phi_tile.hpp's acc_row, restated for the host)
-inline int gq_acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
 
 // the per-call operand block of k_graph_quadform<LD, T, NB> (device):
 //   [NB][LD][32] float  fl32(R[j][32 b + cc]) at [b][j][cc], zero for columns >= r and rows >= m
@@ -102,24 +99,6 @@ __global__ __launch_bounds__(256) void k_graph_quadform(const T *__restrict__ ph
     }
 }
 
-template <int LD, class T, int NB>
-static int launch_quadform(glf_ctx *ctx, int *per_cu, const T *d_phi, int64_t N, int ncent, int accumulate, const float *d_operand, float *d_out)
-{
-    int64_t nblk = 0;
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_quadform<LD, T, NB>, N, &nblk));
-    hipLaunchKernelGGL((k_graph_quadform<LD, T, NB>), dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_phi, N, ncent, accumulate, d_operand, d_out);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
-// |x| fits an f32 (its fl32 is finite)
-static bool all_fl32_finite(const double *x, size_t n)
-{
-    for (size_t e = 0; e < n; ++e)
-        if (!(std::fabs(x[e]) <= (double)FLT_MAX)) return false;
-    return true;
-}
-
 } // namespace glf
 
 using namespace glf;
@@ -132,37 +111,37 @@ int glf_graph_quadform(glf_graph *g, unsigned r, const double *h_R, unsigned nce
     glf_ctx *ctx = g->ctx;
     const unsigned m = g->m, ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
-    // a[c][j] = R[j][c] (a compact handle: the column scales of Phi folded into the rows of R in f64, before their fl32:
-    // glf_graph_synthesize's rule; the centres live in the space of R^T phi and take no scale)
-    std::vector<double> a((size_t)r * m);
+    // the coefficient vectors are the columns of R: rt[c][j] = R[j][c], 32 of them per operand block (a compact handle: the column
+    // scales of Phi folded into the rows of R in f64, before their fl32: coeff_operand's rule; the centres live in the space of
+    // R^T phi and take no scale)
+    std::vector<double> rt((size_t)r * m);
     for (unsigned j = 0; j < m; ++j)
-        for (unsigned c = 0; c < r; ++c) a[(size_t)c * m + j] = h_R[(size_t)j * r + c];
-    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)r, m, g->expo.data());
-    if (!all_fl32_finite(a.data(), a.size()) || (h_t && !all_fl32_finite(h_t, (size_t)ncent * r)))
-        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_quadform: an entry of R (folded with its column's 2^e_c) or of t is not finite in f32");
-    GLF_ENTER(ctx);
+        for (unsigned c = 0; c < r; ++c) rt[(size_t)c * m + j] = h_R[(size_t)j * r + c];
     const int nb = r > 32 ? 2 : 1;
     std::vector<float> h_op(gq_operand_floats(ld, nb, ncent), 0.f);
-    for (unsigned c = 0; c < r; ++c)
-        for (unsigned j = 0; j < m; ++j) h_op[((size_t)(c / 32) * ld + j) * 32 + c % 32] = (float)a[(size_t)c * m + j];
+    bool fits = !h_t || all_fl32_finite(h_t, (size_t)ncent * r);
+    for (int b = 0; b < nb; ++b) {
+        const size_t cols = std::min(r - 32u * b, 32u);
+        const std::vector<double> a = coeff_operand(g, cols, rt.data() + (size_t)32 * b * m, 32, h_op.data() + (size_t)b * ld * 32);
+        fits = fits && all_fl32_finite(a.data(), a.size());
+    }
+    if (!fits)
+        return set_error(ctx, GLF_ERR_INVALID, "glf_graph_quadform: an entry of R (folded with its column's 2^e_c) or of t is not finite in f32");
+    GLF_ENTER(ctx);
     float *t_op = h_op.data() + (size_t)nb * ld * 32;
     for (unsigned k = 0; h_t && k < ncent; ++k)
         for (int h = 0; h < 2; ++h)
             for (int b = 0; b < nb; ++b)
                 for (int q = 0; q < 16; ++q) {
-                    const unsigned c = 32u * b + (unsigned)gq_acc_row(q, h);
+                    const unsigned c = 32u * b + (unsigned)acc_row(q, h);
                     if (c < r) t_op[((size_t)k * 2 + h) * 16 * nb + 16 * b + q] = (float)h_t[(size_t)k * r + c];
                 }
     DevBuf<float> op;
     GLF_TRY(upload_operand(ctx, op, h_op));
     int rc = GLF_ERR_INVALID;
-    dispatch_phi(g, [&](auto *phi) {
-        dispatch_ld(ld, [&](auto LD) {
-            rc = nb == 2 ? launch_quadform<LD.value, std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>, 2>(ctx, &g->quad_blocks_per_cu[1], phi, N, (int)ncent,
-                                                                                                                accumulate != 0, op.p, d_out)
-                         : launch_quadform<LD.value, std::remove_cv_t<std::remove_pointer_t<decltype(phi)>>, 1>(ctx, &g->quad_blocks_per_cu[0], phi, N, (int)ncent,
-                                                                                                                accumulate != 0, op.p, d_out);
-        });
+    dispatch_phi_ld(g, [&](auto LD, auto *phi, auto t) {
+        rc = nb == 2 ? launch_tiles(g, k_graph_quadform<LD.value, decltype(t), 2>, N, phi, N, (int)ncent, (int)(accumulate != 0), (const float *)op.p, d_out)
+                     : launch_tiles(g, k_graph_quadform<LD.value, decltype(t), 1>, N, phi, N, (int)ncent, (int)(accumulate != 0), (const float *)op.p, d_out);
     });
     GLF_TRY(rc);
     GLF_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (h_op and op go out of scope)

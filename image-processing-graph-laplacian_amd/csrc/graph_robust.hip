@@ -120,19 +120,6 @@ __global__ __launch_bounds__(256) void k_graph_residual_weight(const T *__restri
     }
 }
 
-template <int LD, class T>
-static int launch_residual_weight(glf_ctx *ctx, int *per_cu, int64_t *nblk, DevBuf<double> &part, const T *d_phi, int64_t N, int nplanes,
-                                  const float *d_operand, const RobustConst &rc, const float *d_w, const float *d_planes, float *d_weight_out,
-                                  float *d_res_out)
-{
-    GLF_TRY(resident_tile_grid(ctx, per_cu, k_graph_residual_weight<LD, T>, N, nblk));
-    GLF_TRY(part.alloc(ctx, (size_t)*nblk * 2));
-    hipLaunchKernelGGL((k_graph_residual_weight<LD, T>), dim3((unsigned)*nblk), dim3(256), 0, ctx->stream, d_phi, N, nplanes, d_operand, rc, d_w, d_planes,
-                       d_weight_out, d_res_out, part.p);
-    GLF_LAUNCH_CHECK(ctx);
-    return GLF_OK;
-}
-
 // what the step and the driver refuse alike, before any device work
 static bool loss_shape_ok(const glf_robust_loss *loss, int nplanes, bool with_sigma)
 {
@@ -160,16 +147,12 @@ static int robust_step(glf_graph *g, const RobustConst &rc, const float *d_w, in
                        double *h_b, double *h_loss, double *h_mass, float *d_weight_out, float *d_res_out)
 {
     glf_ctx *ctx = g->ctx;
-    const unsigned m = g->m, ld = g->ld;
+    const unsigned ld = g->ld;
     const int64_t N = (int64_t)g->width * g->height;
-    // (a compact handle: the column scales folded into the coefficients in f64 before their fl32, glf_graph_synthesize's rule; the
-    // refusal of a coefficient that is not finite then applies to the folded values)
-    std::vector<double> a(h_a, h_a + (size_t)nplanes * m);
-    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), (size_t)nplanes, m, g->expo.data());
-    if (!all_finite(a.data(), a.size())) return set_error(ctx, GLF_ERR_INVALID, "robust step: a coefficient folded with its column's 2^e_c is not finite");
+    // (a compact handle: the refusal of a coefficient that is not finite applies to the folded values)
     std::vector<float> h_op((size_t)ld * GR_OUT, 0.f);
-    for (int j = 0; j < nplanes; ++j)
-        for (unsigned k = 0; k < m; ++k) h_op[(size_t)k * GR_OUT + j] = (float)a[(size_t)j * m + k];
+    const std::vector<double> a = coeff_operand(g, (size_t)nplanes, h_a, GR_OUT, h_op.data());
+    if (!all_finite(a.data(), a.size())) return set_error(ctx, GLF_ERR_INVALID, "robust step: a coefficient folded with its column's 2^e_c is not finite");
     DevBuf<float> op, weff;
     DevBuf<double> part, tot;
     GLF_TRY(upload_operand(ctx, op, h_op));
@@ -179,11 +162,9 @@ static int robust_step(glf_graph *g, const RobustConst &rc, const float *d_w, in
     }
     int64_t nblk = 0;
     int rc_launch = GLF_ERR_INVALID;
-    dispatch_phi(g, [&](auto *phi) {
-        dispatch_ld(ld, [&](auto LD) {
-            rc_launch = launch_residual_weight<LD.value>(ctx, &g->robust_blocks_per_cu, &nblk, part, phi, N, nplanes, op.p, rc, d_w, d_planes,
-                                                         d_weight_out, d_res_out);
-        });
+    dispatch_phi_ld(g, [&](auto LD, auto *phi, auto t) {
+        rc_launch = launch_tiles_partials(g, k_graph_residual_weight<LD.value, decltype(t)>, N, part, 2, &nblk, phi, N, nplanes, (const float *)op.p, rc, d_w,
+                                          d_planes, d_weight_out, d_res_out);
     });
     GLF_TRY(rc_launch);
     std::vector<double> h_tot;

@@ -1,7 +1,9 @@
 // phi_tile.hpp -- what the graph-handle kernels share (graph.hip, graph_fit.hip, graph_cluster.hip, graph_basis.hip, graph_robust.hip,
-// graph_project.hip): staging a tile of Phi, the "outputs are M, pixels are N" contraction, the f32 chain rule, the four-wave f64
-// epilogue, and the host steps around a launch. Only pieces that at least two kernels use, as forceinlined templates and host inlines;
-// each kernel keeps its index roles, its epilogue and its arithmetic contract in its own file.
+// graph_project.hip, graph_quad.hip, graph_classify.hip, graph_edges.hip): staging a tile of Phi, the "outputs are M, pixels are N"
+// contraction, the f32 chain rule, the four-wave f64 epilogue, and the host steps around a launch (the dispatch on storage and ld, the
+// launch on a resident grid, the coefficient operand, the identity terms). Only pieces that at least two kernels use, as forceinlined
+// templates and host inlines; each kernel keeps its index roles, its tile loop, its epilogue and its arithmetic contract in its own file
+// (a shared tile loop was tried and cost time: DESIGN.md, profiles/graph_sweep_kernel_resources.txt).
 //
 // The tile. Every kernel gives one wave a tile of 32 pixels (32 rows of Phi), the tiles strided over the grid, and stages CW columns
 // of it at a time: a lane loads CW / 8 float4s, whole 16-byte pieces in address order (piece e = q 64 + lane is row e / (CW / 4),
@@ -21,6 +23,7 @@
 // (wave_tiles_reduce), the workgroups by filter.hip's k_cols_sum in an order that depends on their number alone (sum_partials).
 #pragma once
 #include "glf_internal.hpp"
+#include "phi_compact.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -35,7 +38,7 @@ static_assert(GLF_GRAPH_NORMAL_CHAIN % 32 == 0 && GLF_GRAPH_NORMAL_CHAIN >= 32 &
 constexpr int CHAIN_TILES = GLF_GRAPH_NORMAL_CHAIN / 32; // 32-pixel tiles in one f32 chain
 
 // the row of the 32 x 32 accumulator tile that register g holds in half-wave h
-__device__ __forceinline__ constexpr int acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
+__host__ __device__ __forceinline__ constexpr int acc_row(int g, int h) { return (g & 3) + 8 * (g >> 2) + 4 * h; }
 
 __device__ __forceinline__ void acc_clear(f32x16 &acc)
 {
@@ -217,6 +220,10 @@ inline void dispatch_phi(const glf_graph *g, F &&f)
     else f(static_cast<const float *>(g->phi));
 }
 
+// the element type behind the pointer dispatch_phi hands over
+template <class P>
+using phi_elem_t = std::remove_cv_t<std::remove_pointer_t<P>>;
+
 // f(std::integral_constant<int, LD>) for the ld of a graph handle; false: no such instance
 template <class F>
 inline bool dispatch_ld(unsigned ld, F &&f)
@@ -228,6 +235,76 @@ inline bool dispatch_ld(unsigned ld, F &&f)
     case 256: f(std::integral_constant<int, 256>{}); return true;
     }
     return false;
+}
+
+// both: f(LD, phi, T{}) with the handle's Phi as const T *phi, so that a kernel instance is k<LD.value, decltype(t)>; false: no
+// instance for the handle's ld
+template <class F>
+inline bool dispatch_phi_ld(const glf_graph *g, F &&f)
+{
+    bool found = false;
+    dispatch_phi(g, [&](auto *phi) { found = dispatch_ld(g->ld, [&](auto LD) { f(LD, phi, phi_elem_t<decltype(phi)>{}); }); });
+    return found;
+}
+
+// The launch of a kernel of the shape "one 32-pixel tile per wave, four waves, resident grid" over N pixels on the handle's stream
+// (queued): resident_tile_grid, the launch, the check.
+template <class Kernel, class... Args>
+inline int launch_tiles(glf_graph *g, Kernel kernel, int64_t N, Args... args)
+{
+    int64_t nblk = 0;
+    GLF_TRY(resident_tile_grid(g, kernel, N, &nblk));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, g->ctx->stream, args...);
+    GLF_LAUNCH_CHECK(g->ctx);
+    return GLF_OK;
+}
+// the same for a kernel with a reduction: its last argument is part, [workgroups][cols] f64 partials, sized here; *nblk: the
+// workgroups (the rows sum_partials adds)
+template <class Kernel, class... Args>
+inline int launch_tiles_partials(glf_graph *g, Kernel kernel, int64_t N, DevBuf<double> &part, size_t cols, int64_t *nblk, Args... args)
+{
+    GLF_TRY(resident_tile_grid(g, kernel, N, nblk));
+    GLF_TRY(part.alloc(g->ctx, (size_t)*nblk * cols));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)*nblk), dim3(256), 0, g->ctx->stream, args..., part.p);
+    GLF_LAUNCH_CHECK(g->ctx);
+    return GLF_OK;
+}
+
+// The coefficient operand of a pass that contracts Phi with `rows` coefficient vectors h_a ([rows][m], f64): the copy the handle's
+// kernels take -- on a compact handle folded with the column scales in f64 (compact_fold_cols), before any fl32 -- is returned, and
+// its fl32 written as the MFMA's A operand: a[j][c] at [c][j] of the [ld][OUT] block op, whose other entries stay as they are
+// (zeros). Whether a value that is not finite is refused, as f64 or as f32, is the caller's rule.
+inline std::vector<double> coeff_operand(const glf_graph *g, size_t rows, const double *h_a, int OUT, float *op)
+{
+    const unsigned m = g->m;
+    std::vector<double> a(h_a, h_a + rows * m);
+    if (g->storage == GLF_PHI_F16) compact_fold_cols(a.data(), rows, m, g->expo.data());
+    for (size_t j = 0; j < rows; ++j)
+        for (unsigned c = 0; c < m; ++c) op[(size_t)c * OUT + j] = (float)a[j * m + c];
+    return a;
+}
+
+// The identity terms ident[j] s_plane[j] of synthesize's outputs and classify's scores, j < n <= 32. ident_terms_check: -1 if every
+// plane[j] lies in -1 .. nplanes - 1 and ident and d_planes are there where one is >= 0 (*any_plane), else the first j out of range, or
+// n for the missing pointers. ident_terms_pack: op <- [32] float ident[j] (0 without a term), [32] int plane[j] (-1 without one).
+inline int ident_terms_check(int n, const int *plane, int nplanes, const float *ident, const float *d_planes, bool *any_plane)
+{
+    *any_plane = false;
+    for (int j = 0; j < n; ++j) {
+        if (plane[j] < -1 || plane[j] >= nplanes) return j;
+        *any_plane = *any_plane || plane[j] >= 0;
+    }
+    return *any_plane && (!ident || !d_planes) ? n : -1;
+}
+inline void ident_terms_pack(int n, const float *ident, const int *plane, float *op)
+{
+    int h_plane[32];
+    for (int j = 0; j < 32; ++j) {
+        const bool term = j < n && plane[j] >= 0;
+        op[j] = term ? ident[j] : 0.f;
+        h_plane[j] = term ? plane[j] : -1;
+    }
+    std::memcpy(op + 32, h_plane, sizeof(h_plane));
 }
 
 // tot[c] = sum over r < nrows of part[r][c], c < ncols (queued)

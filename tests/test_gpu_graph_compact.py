@@ -25,7 +25,8 @@ Shapes: those of tests/test_gpu_graph.py -- 61 x 47 = 2867 pixels (the last 32-p
    max |z16 - z32| / max |z32| per shape is printed (the README records it), and the bound of test 3 applied to the chain
    project_wide -> scale -> synthesize is asserted.
 5. Refusals, idempotence, determinism across builds, a Phi that is not finite, the debug pool.
-6. The tile loop: 509 x 515 at ld 64, every wave runs its loop more than once."""
+6. The tile loop: 509 x 515 at ld 64, every wave runs its loop more than once.
+7. The same shape: a handle that made every call as f32 before it was compacted against one compacted before its first call."""
 import numpy as np
 import pytest
 import torch
@@ -414,3 +415,54 @@ def test_many_tiles_per_wave():
         _same(gc.project_wide(d32), gt.project_wide(d32), "project_wide, 32 planes")
         gc.close()
         gt.close()
+
+
+# ---- 7. calls as f32, then compaction, then the same calls ------------------------------------------------------------------------------
+
+def _every_pass(g, a, ident, plane, d_sig, d32, d_w, rng_seed):
+    """Every pass over Phi that sizes its grid from a cached occupancy, and the two that do not, once each: name -> output."""
+    rng = np.random.default_rng(rng_seed)
+    m = g.info["m"]
+    out = {"synthesize": g.synthesize(a, ident, plane, d_sig)}
+    for r in (5, 40):                                                                 # one and two accumulator tiles
+        R, cen = rng.normal(0.0, 1.0, (m, r)) / np.sqrt(m), rng.normal(0.0, 1e-3, (3, r))
+        out["quadform r=%d" % r] = g.quadform(R, cen)
+    for key, x in g.classify(a[:8], ident[:8], plane[:8], d_sig, rng.normal(0.0, 1.0, 8), want=("label", "best", "margin")).items():
+        out["classify " + key] = x
+    out["edges"] = g.edges()
+    step = g.robust_step(d_sig[:2].contiguous(), a[:2], "huber", sigma=[30.0, 45.0], weight=d_w, want_weights=True, want_residuals=True)
+    for key, x in zip(("G", "b", "loss", "mass", "w_eff", "residuals"), step):
+        out["robust_step " + key] = np.float64(x) if isinstance(x, float) else x
+    for key, x in zip(("labels", "sums", "counts", "changed"), g.cluster_step(rng.normal(size=(5, m)) * 1e-2)):
+        out["cluster_step " + key] = np.int64(x) if isinstance(x, int) else x
+    out["normal_equations G"], out["normal_equations b"] = g.normal_equations(d_w, d_sig)
+    out["project_wide"] = g.project_wide(d32, d_w)
+    return out
+
+
+def test_calls_before_compaction_leave_no_trace():
+    """Handle A makes every call once as f32, is compacted and makes them again; handle B is compacted before its first call. 509 x 515
+    has more tiles than resident waves (asserted), so the occupancy a handle caches per kernel decides the grid, and with it the
+    partial sums of the passes that reduce: what A cached for the f32 instances must not reach its f16 instances."""
+    w, h, m, ld = 509, 515, 40, 64
+    n = w * h
+    opt = glf.default_options(num_samples=300, num_eigvals=m, epsilon=0.1)
+    with glf.Context(0) as ctx:
+        assert (n + 31) // 32 > 4 * 7 * ctx.device_info()["num_cus"]
+        d_img = ctx.to_device(glf.synth_image(w, h, seed=3))
+        ga, gb = ctx.graph(d_img, opt), ctx.graph(d_img, opt)
+        assert (ga.info["m"], ga.info["ld"]) == (m, ld)
+        _same(ga.phi, gb.phi, "the two builds")
+        d32 = _dev(ctx, _planes32(h, w))
+        d_sig, d_w = d32[:3].contiguous(), _weight_plane(ctx, h, w)
+        a, ident, plane = _outputs(32, ga.eigenvalues, ga.project_wide(d_sig), np.random.default_rng(ld))
+        first = _every_pass(ga, a, ident, plane, d_sig, d32, d_w, 41)
+        assert set(first) >= {"synthesize", "quadform r=40", "classify margin", "edges", "robust_step mass", "cluster_step sums", "project_wide"}
+        ga.compact()
+        gb.compact()
+        got, want = _every_pass(ga, a, ident, plane, d_sig, d32, d_w, 41), _every_pass(gb, a, ident, plane, d_sig, d32, d_w, 41)
+        assert list(got) == list(want) == list(first)
+        for key in want:
+            _same(got[key], want[key], "%s after f32 calls and compaction, against compaction first" % key)
+        ga.close()
+        gb.close()
