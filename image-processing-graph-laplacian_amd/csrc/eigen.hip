@@ -434,6 +434,7 @@ int start_block_cached(glf_ctx *ctx, unsigned p, unsigned m, unsigned ld, unsign
             for (unsigned i = 0; i < p; ++i) h[(size_t)i * ld + j] = (float)x0[(size_t)j * p + i];
         if (ctx->x0_block) (void)hipFree(ctx->x0_block);
         ctx->x0_block = nullptr;
+        ctx->x0_orth_form = 0; // the orthonormalised copy belongs to the old key
         GLF_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->x0_block), n * sizeof(float)));
         GLF_HIP(ctx, hipMemcpyAsync(ctx->x0_block, h.data(), n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         GLF_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -484,6 +485,12 @@ static inline Rows rows_of(unsigned p, const MatShard *sh)
         r.r1 = p;
     }
     return r;
+}
+// rows [from, rows) of a [rows][ld] block <- 0: the pad rows of a work buffer (a pooled buffer comes back with old contents)
+static int zero_pad_rows(glf_ctx *ctx, float *q, size_t from, size_t rows, unsigned ld)
+{
+    if (from < rows) GLF_HIP(ctx, hipMemsetAsync(q + from * ld, 0, (rows - from) * ld * sizeof(float), ctx->stream));
+    return GLF_OK;
 }
 static int allreduce_d(glf_ctx *ctx, double *d, size_t n)
 {
@@ -888,7 +895,11 @@ struct CgWork {
         GLF_TRY(sums.alloc(ctx, (size_t)2 * ld));
         GLF_TRY(scal.alloc(ctx, (size_t)4 * ld));
         GLF_TRY(flags.alloc(ctx, ld + 1));
-        for (float *q : {R.p, P.p, AP.p, Xs.p}) GLF_HIP(ctx, hipMemsetAsync(q, 0, n * sizeof(float), ctx->stream));
+        // The rows from p on are zero in every block and stay so. On one rank the kernels write every row below p before they
+        // read it (k_cg_init: R, P, Xs; the sweep: AP), so only the pad rows are filled. AP keeps its whole fill where a packed
+        // sweep may come first (k_cg_unpack writes the active columns only), the sharded blocks theirs (other ranks' rows).
+        const bool may_narrow = sh && sh->grid && ld >= 64 && !ctx->tune.no_narrow;
+        for (float *q : {R.p, P.p, AP.p, Xs.p}) GLF_TRY(zero_pad_rows(ctx, q, (rows.dist || (q == AP.p && may_narrow)) ? 0 : p, n / ld, ld));
         s.rz = scal.p;
         s.bn2 = scal.p + ld;
         s.alpha = scal.p + 2 * ld;
@@ -904,8 +915,11 @@ struct CgWork {
 };
 
 static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, unsigned p, float *XB, unsigned m,
-                          unsigned ld, double rtol, int max_it, int *iters, bool solution_to_XB = true)
+                          unsigned ld, double rtol, int max_it, int *iters, bool solution_to_XB = true, bool rhs_active = false)
 {
+    // rhs_active: the caller knows that every column of B is non-zero (the solver's B is an orthonormalised block), so all m
+    // columns are active after k_cg_init and the first step is enqueued behind it without the round trip that would say so.
+    // One rank only, and not under tune.verbose (which reports after every synchronise).
     // XB: the right-hand side B in, the solution out -- unless solution_to_XB is off: then XB is only read and the solution
     // stays in w.Xs (the caller swaps buffers instead of copying a block)
     const int nblk = w.nblk;
@@ -939,13 +953,14 @@ static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, 
     hipLaunchKernelGGL(k_cg_count, dim3(1), dim3(256), 0, st, w.s, ld);
     GLF_LAUNCH_CHECK(ctx);
     int it = 0;
-    GLF_HIP(ctx, hipStreamSynchronize(st));
-    while (*(volatile int *)w.h_nactive > 0 && it < max_it) {
+    bool unsynced = rhs_active && !rows.dist && !ctx->tune.verbose && max_it > 0; // the counter of k_cg_count has not been read
+    if (!unsynced) GLF_HIP(ctx, hipStreamSynchronize(st));
+    while ((unsynced || *(volatile int *)w.h_nactive > 0) && it < max_it) {
         ++it;
         if (rows.dist) GLF_TRY(allgather_rows(ctx, w.P.p, w.shard, ld)); // the operator needs every row of its operand
         unsigned wn = ld; // block width of this sweep
         if (w.shard && w.shard->grid && ld >= 64 && !ctx->tune.no_narrow) {
-            const int na = *w.h_nactive; // (as of the synchronise that ended the step before)
+            const int na = unsynced ? (int)m : *w.h_nactive; // (as of the synchronise that ended the step before)
             const unsigned cand = na <= 32 ? 32u : (unsigned)round_up(na, 64);
             if (cand < ld) wn = cand;
         }
@@ -980,6 +995,7 @@ static int block_pcg_work(glf_ctx *ctx, CgWork &w, const float *A, int64_t lda, 
                            w.s, carry ? w.pmax.p : nullptr);
         GLF_LAUNCH_CHECK(ctx);
         GLF_HIP(ctx, hipStreamSynchronize(st));
+        unsynced = false;
         if (ctx->tune.verbose) fprintf(stderr, "[glf] block PCG step %d: %d of %u columns active\n", it, *w.h_nactive, m);
     }
     if (nloc > 0 && solution_to_XB)
@@ -1233,21 +1249,27 @@ __global__ __launch_bounds__(256) void k_gsf_gram(const float *__restrict__ X, u
 }
 
 // The same chunk sums on the f64 matrix pipe (v_mfma_f64_16x16x4_f64: exact products of the f32 entries, f64 accumulation):
-// one wave per (chunk, tile pair); M = 16 columns a of X, N = 16 columns b of Y, K = 4 rows per step -- lane l holds
+// one workgroup per (chunk, tile pair); M = 16 columns a of X, N = 16 columns b of Y, K = 4 rows per step -- lane l holds
 // X[row 4 s + (l >> 4)][a0 + (l & 15)] as the A operand and the like from Y as B; the result registers of a lane are
 // G[a0 + (l >> 4) + 4 reg][b0 + (l & 15)]. The loads of 8 steps (32 rows) are issued together. The vector form reached
 // ~15 TFLOP/s of f64 (49 us for 0.7 GFLOP at cfg4).
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-template <int TILE>
-__global__ __launch_bounds__(64) void k_gsf_gram_mfma(const float *__restrict__ X, unsigned n, unsigned ld,
-                                                       double *__restrict__ Gpart, const float *__restrict__ Y = nullptr)
+// The sub-tile pairs (u, v) of a tile are dealt to the GSF_GRAM_WAVES waves of the workgroup, pair k of the enumeration below to
+// wave k % GSF_GRAM_WAVES (one wave per chunk left a third of the SIMDs without a wave at 667 chunks): every pair keeps its own
+// accumulator and its own row-ascending sequence of MFMAs, so the sums are those of one wave doing all pairs. SYM: a diagonal tile
+// of X^T X -- the sub-tiles below its diagonal are mirror images, and a row is loaded once for both operands.
+constexpr int GSF_GRAM_WAVES = 4;
+template <int S, bool SYM>
+__host__ __device__ constexpr int gsf_pair_index(int u, int v) // position of (u, v) among the pairs a tile computes
+{
+    return SYM ? u * S - u * (u - 1) / 2 + (v - u) : u * S + v;
+}
+template <int TILE, bool SYM, int W>
+__device__ __forceinline__ void gsf_gram_wave(const float *__restrict__ xa, const float *__restrict__ yb, unsigned ld, unsigned r0,
+                                              unsigned r1, int lq, int l15, int ca, int cb, double *__restrict__ out)
 {
     constexpr int S = TILE / 16; // 16 x 16 sub-tiles per side
-    const int mb = ld / TILE;
-    const int ta = blockIdx.y / mb, tb = blockIdx.y % mb;
-    if (!Y && tb < ta) return;
-    const float *Yp = Y ? Y : X;
-    const int lane = threadIdx.x, l15 = lane & 15, lq = lane >> 4;
+    auto mine = [](int u, int v) { return (!SYM || v >= u) && gsf_pair_index<S, SYM>(u, v) % GSF_GRAM_WAVES == W; };
     f64x4 acc[S][S];
 #pragma unroll
     for (int u = 0; u < S; ++u)
@@ -1255,18 +1277,15 @@ __global__ __launch_bounds__(64) void k_gsf_gram_mfma(const float *__restrict__ 
         for (int v = 0; v < S; ++v)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[u][v][r] = 0.0;
-    const unsigned r0 = blockIdx.x * GSF_ROWS, r1 = min(r0 + GSF_ROWS, n);
-    const float *xa = X + ta * TILE + l15, *yb = Yp + tb * TILE + l15;
-    const bool sym = !Y && ta == tb; // a diagonal tile of X^T X: the sub-tiles below its diagonal are mirror images
     for (unsigned ib = r0; ib < r1; ib += 32) {
-        float a[8][S], b[8][S];
+        float a[8][S], b[8][S]; // (the blocks this wave's pairs do not touch are never loaded: their values are unused)
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
             const unsigned i = min(ib + 4 * q + lq, r1 - 1);
 #pragma unroll
             for (int u = 0; u < S; ++u) {
                 a[q][u] = xa[(size_t)i * ld + 16 * u];
-                b[q][u] = yb[(size_t)i * ld + 16 * u];
+                b[q][u] = SYM ? a[q][u] : yb[(size_t)i * ld + 16 * u];
             }
         }
 #pragma unroll
@@ -1282,22 +1301,48 @@ __global__ __launch_bounds__(64) void k_gsf_gram_mfma(const float *__restrict__ 
             for (int u = 0; u < S; ++u)
 #pragma unroll
                 for (int v = 0; v < S; ++v)
-                    if (!sym || v >= u) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[u], db[v], acc[u][v], 0, 0, 0);
+                    if (mine(u, v)) acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(da[u], db[v], acc[u][v], 0, 0, 0);
         }
     }
-    double *out = Gpart + (size_t)blockIdx.x * ld * ld;
 #pragma unroll
     for (int u = 0; u < S; ++u)
 #pragma unroll
         for (int v = 0; v < S; ++v) {
-            if (sym && v < u) continue;
+            if (!mine(u, v)) continue;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const size_t ga = (size_t)(ta * TILE + 16 * u + lq + 4 * r), gb = (size_t)(tb * TILE + 16 * v + l15);
+                const size_t ga = (size_t)(ca + 16 * u + lq + 4 * r), gb = (size_t)(cb + 16 * v + l15);
                 out[ga * ld + gb] = acc[u][v][r];
-                if (sym && v > u) out[gb * ld + ga] = acc[u][v][r]; // the mirror image inside a diagonal tile
+                if (SYM && v > u) out[gb * ld + ga] = acc[u][v][r]; // the mirror image inside a diagonal tile
             }
         }
+}
+template <int TILE>
+__global__ __launch_bounds__(64 * GSF_GRAM_WAVES) void k_gsf_gram_mfma(const float *__restrict__ X, unsigned n, unsigned ld,
+                                                                        double *__restrict__ Gpart, const float *__restrict__ Y = nullptr)
+{
+    const int mb = ld / TILE;
+    const int ta = blockIdx.y / mb, tb = blockIdx.y % mb;
+    if (!Y && tb < ta) return;
+    const float *Yp = Y ? Y : X;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lq = lane >> 4;
+    const unsigned r0 = blockIdx.x * GSF_ROWS, r1 = min(r0 + GSF_ROWS, n);
+    const float *xa = X + ta * TILE + l15, *yb = Yp + tb * TILE + l15;
+    double *out = Gpart + (size_t)blockIdx.x * ld * ld;
+    const bool sym = !Y && ta == tb;
+#define GLF_GSF_GRAM_WAVE(W)                                                                                          \
+    case W:                                                                                                           \
+        if (sym) gsf_gram_wave<TILE, true, W>(xa, yb, ld, r0, r1, lq, l15, ta * TILE, tb * TILE, out);                \
+        else gsf_gram_wave<TILE, false, W>(xa, yb, ld, r0, r1, lq, l15, ta * TILE, tb * TILE, out);                   \
+        break;
+    static_assert(GSF_GRAM_WAVES == 4, "one case per wave below");
+    switch (wave) { // (wave-uniform)
+        GLF_GSF_GRAM_WAVE(0)
+        GLF_GSF_GRAM_WAVE(1)
+        GLF_GSF_GRAM_WAVE(2)
+        GLF_GSF_GRAM_WAVE(3)
+    }
+#undef GLF_GSF_GRAM_WAVE
 }
 
 // G = sum over chunks (fixed order: four interleaved partial sums per entry, combined through LDS), mirrored into the
@@ -1533,9 +1578,40 @@ __global__ __launch_bounds__(256) void k_gsf_apply(const float *X, const float *
 // block). Tn is upper triangular: column tile t needs the blocks jb <= t only (40 of the 64 MFMAs of a row tile). Tn sits in
 // LDS with rows of LD + 4 doubles (the two j rows a half-wave reads are 4 apart: 32 banks apart with that stride).
 // `tiles` row tiles per wave (1 .. 4: enough workgroups for every CU before a workgroup's copy of Tn is shared by more rows).
+// X2, Out2 (optional): a second product Out2 <- X2 Tn of the same rows behind the first, on one copy of Tn -- the solver's outer
+// step, A X_new = (B - R) Tn and then X_new = Y Tn, where Out2 is X: a wave has read its rows of X (and of X2) before it stores any.
 template <int LD>
-__global__ __launch_bounds__(256) void k_gsf_apply_mfma(const float *X, const float *__restrict__ S, float *Out, unsigned n, unsigned m,
-                                                         const double *__restrict__ Tn, const int *__restrict__ flag, int tiles)
+__device__ __forceinline__ void gsf_apply_tile(const float4 (&xa)[LD / 16], const double *ts, float *Out, unsigned row0, unsigned n,
+                                               unsigned m, int lq, int l15)
+{
+    constexpr int NTL = LD / 16, TS = LD + 4;
+    f64x4 acc[NTL];
+#pragma unroll
+    for (int t = 0; t < NTL; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
+#pragma unroll
+    for (int jb = 0; jb < NTL; ++jb) {
+        const double a4[4] = {(double)xa[jb].x, (double)xa[jb].y, (double)xa[jb].z, (double)xa[jb].w};
+#pragma unroll
+        for (int sk = 0; sk < 4; ++sk)
+#pragma unroll
+            for (int t = jb; t < NTL; ++t) // T[j][k] = 0 for j > k: the column tiles left of the block's diagonal get nothing
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[sk], ts[(16 * jb + 4 * lq + sk) * TS + 16 * t + l15], acc[t], 0, 0, 0);
+    }
+    // result register r of a lane: row lq + 4 r of the tile, column 16 t + l15
+#pragma unroll
+    for (int t = 0; t < NTL; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned i = row0 + lq + 4 * r;
+            if (i < n && 16 * t + l15 < (int)m) Out[(size_t)i * LD + 16 * t + l15] = (float)acc[t][r];
+        }
+}
+template <int LD>
+__global__ __launch_bounds__(256) void k_gsf_apply_mfma(const float *X, const float *__restrict__ S, float *Out, const float *X2, float *Out2,
+                                                         unsigned n, unsigned m, const double *__restrict__ Tn,
+                                                         const int *__restrict__ flag, int tiles)
 {
     if (*flag) return; // ill-conditioned: the caller runs the sequential sweep on the untouched block
     constexpr int NTL = LD / 16, TS = LD + 4;
@@ -1548,37 +1624,20 @@ __global__ __launch_bounds__(256) void k_gsf_apply_mfma(const float *X, const fl
         const unsigned row0 = (blockIdx.x * 4 * tiles + wave * tiles + tile) * 16;
         if (row0 >= n) break; // (wave-uniform; no barrier below)
         const unsigned ra = min(row0 + l15, n - 1); // this lane's row as the A operand (a row past the end repeats the last: not stored)
-        float4 xa[NTL];
+        float4 xa[NTL], xb[NTL];
 #pragma unroll
         for (int jb = 0; jb < NTL; ++jb) xa[jb] = *reinterpret_cast<const float4 *>(X + (size_t)ra * LD + 16 * jb + 4 * lq);
+        if (X2)
+#pragma unroll
+            for (int jb = 0; jb < NTL; ++jb) xb[jb] = *reinterpret_cast<const float4 *>(X2 + (size_t)ra * LD + 16 * jb + 4 * lq);
         if (S)
 #pragma unroll
             for (int jb = 0; jb < NTL; ++jb) {
                 const float4 s4 = *reinterpret_cast<const float4 *>(S + (size_t)ra * LD + 16 * jb + 4 * lq);
                 xa[jb] = make_float4(xa[jb].x - s4.x, xa[jb].y - s4.y, xa[jb].z - s4.z, xa[jb].w - s4.w);
             }
-        f64x4 acc[NTL];
-#pragma unroll
-        for (int t = 0; t < NTL; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[t][r] = 0.0;
-#pragma unroll
-        for (int jb = 0; jb < NTL; ++jb) {
-            const double a4[4] = {(double)xa[jb].x, (double)xa[jb].y, (double)xa[jb].z, (double)xa[jb].w};
-#pragma unroll
-            for (int sk = 0; sk < 4; ++sk)
-#pragma unroll
-                for (int t = jb; t < NTL; ++t) // T[j][k] = 0 for j > k: the column tiles left of the block's diagonal get nothing
-                    acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a4[sk], ts[(16 * jb + 4 * lq + sk) * TS + 16 * t + l15], acc[t], 0, 0, 0);
-        }
-        // result register r of a lane: row lq + 4 r of the tile, column 16 t + l15
-#pragma unroll
-        for (int t = 0; t < NTL; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const unsigned i = row0 + lq + 4 * r;
-                if (i < n && 16 * t + l15 < (int)m) Out[(size_t)i * LD + 16 * t + l15] = (float)acc[t][r];
-            }
+        gsf_apply_tile<LD>(xa, ts, Out, row0, n, m, lq, l15);
+        if (X2) gsf_apply_tile<LD>(xb, ts, Out2, row0, n, m, lq, l15);
     }
 }
 
@@ -1618,18 +1677,21 @@ __global__ __launch_bounds__(256) void k_gsf_sub(float *__restrict__ Y, const fl
     }
 }
 
-// out = (X - S) Tn (S optional); out == X: in place
+// out = (X - S) Tn (S optional); out == X: in place. X2, out2 (optional): then out2 = X2 Tn, out2 may be X -- one launch and one
+// copy of Tn for both at ld <= 64, a second launch of k_gsf_apply beyond
 static void launch_gsf_apply(hipStream_t st, const float *X, const float *S, float *out, unsigned n, unsigned ld, unsigned m, const double *Tn,
-                             const int *flag)
+                             const int *flag, const float *X2 = nullptr, float *out2 = nullptr)
 {
     const int tiles = (int)std::max<int64_t>(1, std::min<int64_t>(4, ceil_div(n, 16 * 4 * 256)));
     const unsigned rows_wg = 16 * 4 * (unsigned)tiles;
     if (ld == 64)
-        hipLaunchKernelGGL(k_gsf_apply_mfma<64>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, n, m, Tn, flag, tiles);
+        hipLaunchKernelGGL(k_gsf_apply_mfma<64>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, X2, out2, n, m, Tn, flag, tiles);
     else if (ld == 32)
-        hipLaunchKernelGGL(k_gsf_apply_mfma<32>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, n, m, Tn, flag, tiles);
-    else
+        hipLaunchKernelGGL(k_gsf_apply_mfma<32>, dim3((unsigned)ceil_div(n, rows_wg)), dim3(256), 0, st, X, S, out, X2, out2, n, m, Tn, flag, tiles);
+    else {
         hipLaunchKernelGGL(k_gsf_apply, dim3((unsigned)ceil_div(n, GSF_APPLY_TILE / ld)), dim3(256), 0, st, X, S, out, n, ld, m, Tn, flag);
+        if (X2) hipLaunchKernelGGL(k_gsf_apply, dim3((unsigned)ceil_div(n, GSF_APPLY_TILE / ld)), dim3(256), 0, st, X2, nullptr, out2, n, ld, m, Tn, flag);
+    }
 }
 
 struct GsFusedWork {
@@ -1686,7 +1748,8 @@ struct GsDerive {
     float *AX;      // out: (B - R) Tn, B read from X
 };
 
-// returns GLF_OK with *fell_back = 1 when the device found V too ill-conditioned (X untouched; der: AX too)
+// returns GLF_OK with *fell_back = 1 when the device found V too ill-conditioned (X untouched; der: AX too); with
+// fell_back == nullptr the kernels are only enqueued: no synchronise, the flag is the caller's to read later
 // rows: this rank's rows of X (X points at row 0 of the whole block); dist: the Gram block is all-reduced
 static int orthonormalise_fused_dev(glf_ctx *ctx, GsFusedWork &f, float *X, Rows rows, unsigned m, unsigned ld,
                                     double *d_norms, int *fell_back, const GsDerive *der = nullptr)
@@ -1699,9 +1762,9 @@ static int orthonormalise_fused_dev(glf_ctx *ctx, GsFusedWork &f, float *X, Rows
     const int tile = ld >= 64 ? 64 : 32, mb = (int)ld / tile;
     if (f.nchunks > 0) {
         if (tile == 64)
-            hipLaunchKernelGGL((k_gsf_gram_mfma<64>), dim3(f.nchunks, mb * mb), dim3(64), 0, st, Xl, n, ld, f.Gpart.p);
+            hipLaunchKernelGGL((k_gsf_gram_mfma<64>), dim3(f.nchunks, mb * mb), dim3(64 * GSF_GRAM_WAVES), 0, st, Xl, n, ld, f.Gpart.p);
         else
-            hipLaunchKernelGGL((k_gsf_gram_mfma<32>), dim3(f.nchunks, mb * mb), dim3(64), 0, st, Xl, n, ld, f.Gpart.p);
+            hipLaunchKernelGGL((k_gsf_gram_mfma<32>), dim3(f.nchunks, mb * mb), dim3(64 * GSF_GRAM_WAVES), 0, st, Xl, n, ld, f.Gpart.p);
     }
     hipLaunchKernelGGL(k_gsf_sum, dim3((ld * ld + 63) / 64), dim3(256), 0, st, f.Gpart.p, f.nchunks, ld, tile, f.G.p);
     GLF_LAUNCH_CHECK(ctx);
@@ -1710,15 +1773,18 @@ static int orthonormalise_fused_dev(glf_ctx *ctx, GsFusedWork &f, float *X, Rows
         hipLaunchKernelGGL(k_gsf_recur_lds, dim3(1), dim3(256), 0, st, ld, m, f.G.p, f.Tn.p, d_norms, f.flag.p, f.h_flag);
     else
         hipLaunchKernelGGL(k_gsf_recur_global, dim3(1), dim3(256), 0, st, ld, m, f.G.p, f.S.p, f.Tn.p, d_norms, f.flag.p, f.h_flag);
-    if (n > 0 && der) // (B - R) rounded to f32, then the f64 product with Tn
-        launch_gsf_apply(st, Xout, der->R + (size_t)rows.r0 * ld, der->AX + (size_t)rows.r0 * ld, n, ld, m, f.Tn.p, f.flag.p);
-    if (n > 0)
+    if (n > 0 && der) // (B - R) rounded to f32, then the f64 product with Tn; X_new = Y Tn behind it
+        launch_gsf_apply(st, Xout, der->R + (size_t)rows.r0 * ld, der->AX + (size_t)rows.r0 * ld, n, ld, m, f.Tn.p, f.flag.p, Xl, Xout);
+    else if (n > 0)
         launch_gsf_apply(st, Xl, nullptr, Xout, n, ld, m, f.Tn.p, f.flag.p);
     GLF_LAUNCH_CHECK(ctx);
+    if (!fell_back) return GLF_OK; // the caller reads f.h_flag after a synchronise of its own (gsf_fell_back)
     GLF_HIP(ctx, hipStreamSynchronize(st));
     *fell_back = *(volatile int *)f.h_flag;
     return GLF_OK;
 }
+// the flag of the last orthonormalise_fused_dev, once the stream has been synchronised
+static inline int gsf_fell_back(const GsFusedWork &f) { return *(volatile int *)f.h_flag; }
 
 static int orthonormalise_seq_dev(glf_ctx *ctx, GsWork &w, float *X, unsigned n, unsigned m, unsigned ld)
 {
@@ -1818,6 +1884,7 @@ int normalise(glf_ctx *ctx, float *X, unsigned n, unsigned m, unsigned ld, doubl
 constexpr int GRAM_ROWS = 256; // rows per Gram workgroup chunk
 
 // Gpart[chunk][a][b] = sum_{i in chunk} X[i][a] * Y[i][b]; one wave per 32x32 (a,b) tile.
+// (The four tiles of a chunk as the four waves of one workgroup, so that the rows come from memory once: 18.0 us against 18.3.)
 __global__ __launch_bounds__(64) void k_gram(const float *__restrict__ X, const float *__restrict__ Y, unsigned n,
                                               unsigned ld, float *__restrict__ Gpart)
 {
@@ -1926,6 +1993,7 @@ __global__ __launch_bounds__(256) void k_resid_mfma(const float *__restrict__ X,
     for (unsigned e = threadIdx.x; e < LD * LD; e += 256) Gs[e] = G[e];
     __syncthreads();
     const unsigned row0 = blockIdx.x * RED_ROWS + 32 * wave, rowa = row0 + l31; // this lane's row as the A operand
+    // (A wave's 32 rows read whole, 1 KB per instruction, and handed to the lanes through LDS instead: 23.1 us against 23.3.)
     float xa[KH];
     {
         const float *xr = X + (size_t)min(rowa, p - 1) * LD + KH * half;
@@ -1983,7 +2051,7 @@ struct ResWork {
         const size_t vr = vec_rows(p, sh, ctx->comm.size);
         nchunks = (int)ceil_div(rows.n(), GRAM_ROWS);
         GLF_TRY(AX.alloc(ctx, vr * ld));
-        GLF_HIP(ctx, hipMemsetAsync(AX.p, 0, sizeof(float) * vr * ld, ctx->stream));
+        GLF_TRY(zero_pad_rows(ctx, AX.p, rows.dist ? 0 : p, vr, ld)); // (one rank: the first residual's sweep writes every row below p)
         GLF_TRY(Gpart.alloc(ctx, (size_t)std::max(1, nchunks) * ld * ld));
         GLF_TRY(G.alloc(ctx, (size_t)ld * ld));
         GLF_TRY(partial.alloc(ctx, (size_t)std::max<int64_t>(1, ceil_div(rows.n(), RED_ROWS)) * ld));
@@ -2068,9 +2136,15 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
     GLF_TRY(X.alloc(ctx, n));
     GLF_TRY(Xb.alloc(ctx, n));
     // X0: a ready device block [p32][ld], or host double [m][p] (vector after vector) -> device float [p32][ld]
+    // The context's own seeded block (start_block_cached) on one rank: its orthonormalised form depends on the cache key and the
+    // Gram-Schmidt form only, not on A, so it is kept beside the raw block and copied instead of computed again.
+    const Rows rows = rows_of(p, shard);
+    const bool start_cached = d_X0_block && d_X0_block == ctx->x0_block && ctx->x0_p == p && ctx->x0_m == m && ctx->x0_ld == ld && !rows.dist;
+    const int start_form = 1 + (ctx->tune.gs_seq ? 1 : 0);
+    const bool start_hit = start_cached && ctx->x0_orth_form == start_form;
     if (d_X0_block) {
-        GLF_HIP(ctx, hipMemsetAsync(X.p, 0, sizeof(float) * n, st));
-        GLF_HIP(ctx, hipMemcpyAsync(X.p, d_X0_block, sizeof(float) * n_out, hipMemcpyDeviceToDevice, st));
+        GLF_TRY(zero_pad_rows(ctx, X.p, p32, n / ld, ld)); // (the block itself holds zeros from p to p32)
+        GLF_HIP(ctx, hipMemcpyAsync(X.p, start_hit ? ctx->x0_orth : d_X0_block, sizeof(float) * n_out, hipMemcpyDeviceToDevice, st));
     } else {
         std::vector<double> own;
         if (!h_X0) {
@@ -2091,16 +2165,38 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
     ResWork rs;
     GLF_TRY(rs.init(ctx, p, ld, shard));
     // Sharded solve (see Rows above): every vector kernel below touches this rank's rows [rows.r0, rows.r1) only.
-    const Rows rows = rows_of(p, shard);
     const unsigned nloc = rows.n();
     const size_t off = (size_t)rows.r0 * ld, nloc_ld = (size_t)nloc * ld;
     GLF_TRY(mv_collect(ctx));
     const int mv_count0 = ctx->mv_count, narrow0 = ctx->narrow_sweeps;
     const double mv_ms0 = ctx->mv_ms, mv_bytes0 = ctx->mv_bytes;
     bool replicated = false;
-    GLF_TRY(orthonormalise_dev(ctx, gs, X.p, p, m, ld, rows, shard, &replicated)); // :95
-    // The reference leaves X_k_before_orth unset when the loop never runs (:97-101); define it.
-    GLF_HIP(ctx, hipMemcpyAsync(Xb.p, X.p, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
+    if (start_hit) { // :95, done when the block was first used
+        GLF_HIP(ctx, hipMemcpyAsync(gs.norms.p, ctx->x0_orth_norms, sizeof(double) * ld, hipMemcpyDeviceToDevice, st));
+        gs.last_fused = ctx->x0_orth_fused;
+    } else {
+        GLF_TRY(orthonormalise_dev(ctx, gs, X.p, p, m, ld, rows, shard, &replicated)); // :95
+        if (start_cached) {
+            if (!ctx->x0_orth_form) { // first use of this key: blocks of its size
+                if (ctx->x0_orth) (void)hipFree(ctx->x0_orth);
+                if (ctx->x0_orth_norms) (void)hipFree(ctx->x0_orth_norms);
+                ctx->x0_orth = nullptr;
+                ctx->x0_orth_norms = nullptr;
+                GLF_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->x0_orth), n_out * sizeof(float)));
+                GLF_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->x0_orth_norms), ld * sizeof(double)));
+            }
+            ctx->x0_orth_form = 0; // (until both copies are enqueued)
+            GLF_HIP(ctx, hipMemcpyAsync(ctx->x0_orth, X.p, sizeof(float) * n_out, hipMemcpyDeviceToDevice, st));
+            GLF_HIP(ctx, hipMemcpyAsync(ctx->x0_orth_norms, gs.norms.p, sizeof(double) * ld, hipMemcpyDeviceToDevice, st));
+            ctx->x0_orth_fused = gs.last_fused;
+            ctx->x0_orth_form = start_form;
+        }
+    }
+    // The reference leaves X_k_before_orth unset when the loop never runs (:97-101); define it. One rank: only when it
+    // never runs (after the loop), and until then Xb needs zero pad rows, because the default route swaps it with cg.Xs.
+    const bool xb_late = !rows.dist;
+    if (xb_late) GLF_TRY(zero_pad_rows(ctx, Xb.p, p, n / ld, ld));
+    else GLF_HIP(ctx, hipMemcpyAsync(Xb.p, X.p, sizeof(float) * n, hipMemcpyDeviceToDevice, st));
     double r_norm = 0.0;
     GLF_TRY(residual_dev(ctx, rs, A, lda, p, X.p, m, ld, &r_norm)); // :159
     const bool verbose = ctx->tune.verbose; // the reference logs every outer iteration (:164-181)
@@ -2122,19 +2218,29 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
         if (swap_blocks) {
             // X holds B and is only read by the PCG, which leaves Y in cg.Xs; A X_new = (B - R) Tn and X_new = Y Tn are
             // written out of place, and cg.Xs becomes X_k_before_orth (CopyVecs :171) by a swap of pointers
-            GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner, false)); // :165-168
+            // (X is an orthonormalised block: every column of B is active, the first PCG step needs no round trip to learn it)
+            GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner, false, true)); // :165-168
             inner_total += inner;
             const GsDerive der{cg.Xs.p, cg.R.p, rs.AX.p};
-            int fell_back = 0;
-            GLF_TRY(orthonormalise_fused_dev(ctx, gs.fused, X.p, rows, m, ld, gs.norms.p, &fell_back, &der)); // :174-177
-            gs.last_fused = !fell_back;
-            if (fell_back) { // ill-conditioned block: X = Y, the column-by-column sweep in place, the residual from an explicit sweep
-                if (verbose) fprintf(stderr, "[glf] Gram-Schmidt: ill-conditioned block, column-by-column sweep\n");
-                GLF_HIP(ctx, hipMemcpyAsync(X.p, cg.Xs.p, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st));
-                GLF_TRY(orthonormalise_seq_dev(ctx, gs, X.p, p, m, ld));
-                ax_ready = false;
-            }
+            // The Gram-Schmidt's flag is read after the residual's synchronise, not after one of its own: the residual's
+            // kernels are enqueued behind it, and on the rare fallback they have read untouched buffers and are discarded.
+            GLF_TRY(orthonormalise_fused_dev(ctx, gs.fused, X.p, rows, m, ld, gs.norms.p, nullptr, &der)); // :174-177
             std::swap(cg.Xs.p, Xb.p);
+            rc = residual_dev(ctx, rs, A, lda, p, X.p, m, ld, &r_norm, true); // :180
+            if (rc != GLF_OK) {
+                (void)hipStreamSynchronize(st); // kernels may still be in flight: not before the work buffers go back to the pool
+                return rc;
+            }
+            gs.last_fused = !gsf_fell_back(gs.fused);
+            if (!gs.last_fused) { // ill-conditioned block: X = Y, the column-by-column sweep in place, the residual from an explicit sweep
+                if (verbose) fprintf(stderr, "[glf] Gram-Schmidt: ill-conditioned block, column-by-column sweep\n");
+                GLF_HIP(ctx, hipMemcpyAsync(X.p, Xb.p, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st));
+                GLF_TRY(orthonormalise_seq_dev(ctx, gs, X.p, p, m, ld));
+                GLF_TRY(residual_dev(ctx, rs, A, lda, p, X.p, m, ld, &r_norm, false));
+            }
+            if (verbose)
+                fprintf(stderr, "[glf rank %d] outer iteration %d: %d block-CG steps, residual %.9g\n", ctx->comm.rank, it, inner, r_norm);
+            continue;
         } else {
             if (derive_ax && nloc) GLF_HIP(ctx, hipMemcpyAsync(rs.AX.p + off, X.p + off, sizeof(float) * nloc_ld, hipMemcpyDeviceToDevice, st)); // B
             GLF_TRY(block_pcg_work(ctx, cg, A, lda, p, X.p, m, ld, inner_rtol, 10 * (int)p + 100, &inner)); // :165-168
@@ -2156,6 +2262,7 @@ int inverse_power_iteration(glf_ctx *ctx, const float *A, int64_t lda, unsigned 
         if (verbose)
             fprintf(stderr, "[glf rank %d] outer iteration %d: %d block-CG steps, residual %.9g\n", ctx->comm.rank, it, inner, r_norm);
     }
+    if (xb_late && it == 0) GLF_HIP(ctx, hipMemcpyAsync(Xb.p, X.p, sizeof(float) * n, hipMemcpyDeviceToDevice, st)); // (the loop never ran)
     if (opti_gs != 1 && (it % opti_gs) != 0)
         GLF_TRY(orthonormalise_dev(ctx, gs, X.p, p, m, ld, rows, shard, &replicated)); // :183-186
 

@@ -85,6 +85,13 @@ struct glf_ctx {
     float *x0_block = nullptr;
     unsigned x0_p = 0, x0_m = 0, x0_ld = 0;
     unsigned long long x0_seed = 0;
+    // the same block after the solver's first Gram-Schmidt (inverse_power_iteration :95), with the norms |u_k| it found: the
+    // result depends on the key above and on the Gram-Schmidt form in force, not on the image. x0_orth_form: 0 = none held,
+    // else 1 + tune.gs_seq; x0_orth_fused: the Gram-matrix form ran (no fallback to the column sweep)
+    float *x0_orth = nullptr;
+    double *x0_orth_norms = nullptr; // device, x0_ld entries
+    int x0_orth_form = 0;
+    bool x0_orth_fused = false;
     int contraction = GLF_CONTRACT_F16_SPLIT; // how glf_Nystroem / glf_image_processing contract K_B^T Psi
     // what the last nystroem_contract launch ran with (glf_Nystroem_ex reports it): an exact-zero window (a SKIP instantiation, the
     // grid and rank forms' skipping passes, the band form's schedule), the table-driven generation of k_nystroem_f16s
