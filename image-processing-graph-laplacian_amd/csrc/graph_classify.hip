@@ -3,9 +3,9 @@
 // its score and its margin over the runner-up; the planes themselves are never written. Scribble propagation, the label map of
 // graph-smoothed logits and the per-pixel choice among depth hypotheses all end in this step. The contraction is
 // k_graph_synthesize's; the new part is the epilogue.
-// Out of scope: softmax or temperature confidences, per-class counts, k > 32 and merging across groups, a label input to the
-// projection, mean-field or CRF iterations, contexts with a communicator and glf_multi_* (handles refuse them), m > 256, a flag of
-// the host program, and anything inside k_graph_synthesize, k_graph_cluster and k_graph_quadform.
+// Out of scope: per-class counts, k > 32 and merging across groups, a label input to the projection, contexts with a communicator
+// and glf_multi_* (handles refuse them), m > 256, a flag of the host program, and anything inside k_graph_synthesize,
+// k_graph_cluster and k_graph_quadform. (Softmax confidences and mean-field iterations: graph_softmax.hip.)
 #include "phi_tile.hpp"
 #include "phi_compact.hpp"
 

@@ -72,6 +72,7 @@ EXPORTS = [
     "glf_graph_quadform", "glf_fit_factor", "glf_graph_rows",
     "glf_graph_edges", "glf_graph_samples",
     "glf_graph_classify",
+    "glf_graph_softmax",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex", "glf_Degree_ex", "glf_Filter_ex",
 ]
@@ -98,6 +99,7 @@ QUAD_MAX_COLS = 64         # GLF_QUAD_MAX_COLS: the most columns of R of one glf
 QUAD_MAX_CENTRES = 32      # GLF_QUAD_MAX_CENTRES: the most centres of one glf_graph_quadform call
 EDGE_DIRS = {"E": 1, "S": 2, "SE": 4, "SW": 8}   # GLF_EDGE_*: the neighbour (row, col+1), (row+1, col), (row+1, col+1), (row+1, col-1)
 CLASSIFY_MAX = 32          # GLF_CLASSIFY_MAX: the most classes of one glf_graph_classify call
+SOFTMAX_MAX = 32           # GLF_SOFTMAX_MAX: the most classes of one glf_graph_softmax call
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -288,6 +290,8 @@ _lib.glf_fit_factor.argtypes = [C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_rows.argtypes = [C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p]
 _lib.glf_graph_edges.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_samples.argtypes = [C.c_void_p, C.c_void_p]
+_lib.glf_graph_softmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]
 _lib.glf_graph_classify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
@@ -1744,7 +1748,8 @@ class Graph:
         to write into, or with accumulate to add to). Any r: launches of at most QUAD_MAX_COLS columns, every one after the first
         accumulating; any ncent: launches of at most QUAD_MAX_CENTRES centres. A centre's plane depends neither on the centres beside
         it nor on zero columns appended to R and the centres; up to 64 columns it is one launch and accumulate adds the plain result
-        with one f32 addition, beyond that each group of columns is added in turn. Soft memberships are a softmax over -q in torch."""
+        with one f32 addition, beyond that each group of columns is added in turn. Soft memberships are a softmax over -q in torch, or
+        soft_assign without the distance planes."""
         t = self.ctx.torch
         R = np.asarray(R, dtype=np.float64)
         m, (h, w) = self.info["m"], (self.info["height"], self.info["width"])
@@ -2095,6 +2100,120 @@ class Graph:
             raise ValueError("response must be [%d], got %s" % (m, g.shape))
         c = self.project_wide(logits)
         return self.classify(g[None, :] * c, ident, np.arange(k, dtype=np.int32), logits, bias, want)
+
+    def softmax(self, coeffs, ident=None, plane=None, planes=None, bias=None, beta=1.0, want=("prob",)):
+        """The softmax read-out of the k scores z_j = ident[j] * planes[plane[j]] + Phi coeffs[j] (+ bias[j]) in one pass over Phi
+        (glf_graph_softmax): classify's scores, formed in registers and never written. coeffs [k, m] (k <= SOFTMAX_MAX), ident /
+        plane / planes / bias as in classify, beta > 0 the inverse temperature; want: any of "prob", "lse", "entropy".
+        -> dict of device float32 tensors: prob [k, H, W] = exp(beta z_j) / sum_i exp(beta z_i), lse [H, W] = log sum_j exp(beta z_j),
+        entropy [H, W] = -sum_j prob_j ln prob_j. A pixel with a NaN or +inf score, or with none above -inf, is NaN in every output.
+        planes must not overlap the returned prob (it cannot: prob is a fresh tensor)."""
+        t = self.ctx.torch
+        a = np.ascontiguousarray(np.atleast_2d(np.asarray(coeffs, dtype=np.float64)))
+        k, h, w = a.shape[0], self.info["height"], self.info["width"]
+        if a.shape[1] != self.info["m"]:
+            raise ValueError("coeffs must be [k, %d], got %s" % (self.info["m"], a.shape))
+        if k > SOFTMAX_MAX:
+            raise ValueError("softmax takes at most %d classes (SOFTMAX_MAX), got %d" % (SOFTMAX_MAX, k))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(key not in ("prob", "lse", "entropy") for key in want):
+            raise ValueError('want must name at least one of "prob", "lse", "entropy", got %r' % (want,))
+        pl = np.full(k, -1, dtype=np.int32) if plane is None else np.ascontiguousarray(plane, dtype=np.int32)
+        idn = np.zeros(k, dtype=np.float32) if ident is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ident, dtype=np.float32), (k,)))
+        if pl.shape != (k,):
+            raise ValueError("plane must be [%d]" % k)
+        bs = None
+        if bias is not None:
+            bs = np.ascontiguousarray(np.broadcast_to(np.asarray(bias, dtype=np.float64), (k,)))
+        nplanes = 0
+        if planes is not None:
+            planes = self._planes(planes)
+            nplanes = planes.shape[0]
+        with t.cuda.stream(self.ctx.stream):
+            out = {key: t.empty((k, h, w) if key == "prob" else (h, w), dtype=t.float32, device=self.ctx.device) for key in want}   # (every element is written)
+        ptr = {key: C.c_void_p(out[key].data_ptr()) if key in out else None for key in ("prob", "lse", "entropy")}
+        self.ctx._check(_lib.glf_graph_softmax(self._g, C.c_int(k), _ptr(a), _ptr(idn), _ptr(pl), C.c_int(nplanes),
+                                               C.c_void_p(planes.data_ptr()) if planes is not None else None, _ptr(bs), C.c_double(float(beta)),
+                                               ptr["prob"], ptr["lse"], ptr["entropy"]), "graph softmax")   # (returns with the stream drained)
+        return out
+
+    def soft_assign(self, centres, scale=None, temperature=1.0, want=("prob",)):
+        """Soft memberships of the centres t_j [k, dim] (embedding space, as in cluster_step; k <= SOFTMAX_MAX, dim <= m):
+        p_j(px) proportional to exp(-|scale o Phi[px][:dim] - t_j|^2 / temperature), without forming a distance plane. The row's own
+        squared length is common to the k classes and cancels, so this is one softmax with a_j = 2 scale o t_j / temperature
+        (zero-padded to m) and bias_j = -|t_j|^2 / temperature. scale [dim] or None (= 1). Unit-length rows are out of scope.
+        -> softmax's dict."""
+        cent = np.ascontiguousarray(np.atleast_2d(np.asarray(centres, dtype=np.float64)))
+        k, dim = cent.shape
+        m = self.info["m"]
+        if not 1 <= dim <= m:
+            raise ValueError("centres must be [k, dim] with dim in 1 .. %d, got %s" % (m, cent.shape))
+        if k > SOFTMAX_MAX:
+            raise ValueError("soft_assign takes at most %d centres (SOFTMAX_MAX), got %d" % (SOFTMAX_MAX, k))
+        temperature = float(temperature)
+        if not (temperature > 0.0 and np.isfinite(temperature)):
+            raise ValueError("temperature must be finite and positive, got %r" % temperature)
+        scale = _scale(scale, dim)
+        a = np.zeros((k, m), dtype=np.float64)
+        a[:, :dim] = 2.0 * (cent if scale is None else cent * scale[None, :]) / temperature
+        return self.softmax(a, bias=-(cent * cent).sum(axis=1) / temperature, want=want)
+
+    def mean_field(self, logits, coupling=1.0, compat=None, response=None, weight=None, exclude_samples=True, beta=1.0, ident=1.0,
+                   max_iter=10, tol=1e-4, init=None, want=("prob",)):
+        """Mean-field iterations of a dense CRF whose pairwise kernel is Phi diag(response) Phi^T:
+        Q <- softmax_j(beta (ident logit_j + sum_l' M[j][l'] (Phi diag(response) Phi_w^T Q_l'))), M = coupling I (Potts) or compat
+        [k, k]. Per iteration one project_wide of Q (c = Phi^T diag(weight) Q), the mixing a = M (response o c) on the host, one
+        softmax with the logits as identity planes. logits: device float32 [k, H, W], k <= SOFTMAX_MAX; response: g [m], default
+        1 - lam; weight: device float32 [H, W] or None, multiplied by the mask that is 0 on samples() when exclude_samples (their rows
+        of Phi differ in scale: edges()); init: Q^0 device float32 [k, H, W], default the softmax of the logits alone. Stops when
+        max |a - a_prev| <= tol max |a| or after max_iter iterations. The self-message is not subtracted.
+        -> softmax's dict of the last iteration (of Q^0 for max_iter = 0), plus coeffs [k, m] (the last a), changes (max |a - a_prev|
+        per iteration), iterations and converged."""
+        t = self.ctx.torch
+        logits = self._planes(logits)
+        k, (h, w), m = logits.shape[0], (self.info["height"], self.info["width"]), self.info["m"]
+        if not 1 <= k <= SOFTMAX_MAX:
+            raise ValueError("mean_field takes 1 .. %d classes (SOFTMAX_MAX), got %d" % (SOFTMAX_MAX, k))
+        g = np.asarray(1.0 - self.eigenvalues if response is None else response, dtype=np.float64)
+        if g.shape != (m,):
+            raise ValueError("response must be [%d], got %s" % (m, g.shape))
+        M = float(coupling) * np.eye(k) if compat is None else np.asarray(compat, dtype=np.float64)
+        if M.shape != (k, k):
+            raise ValueError("compat must be [%d, %d], got %s" % (k, k, M.shape))
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(key not in ("prob", "lse", "entropy") for key in want):
+            raise ValueError('want must name at least one of "prob", "lse", "entropy", got %r' % (want,))
+        if weight is not None:
+            weight = self._weight(weight)
+        if exclude_samples:
+            with t.cuda.stream(self.ctx.stream):
+                mask = t.ones((h, w), dtype=t.float32, device=self.ctx.device)
+                mask.view(-1)[t.from_numpy(self.samples().astype(np.int64)).to(self.ctx.device)] = 0
+                weight = mask if weight is None else (weight * mask).contiguous()
+        slots = np.arange(k, dtype=np.int32)
+        with_prob = tuple(dict.fromkeys(("prob",) + want))
+        a = np.zeros((k, m), dtype=np.float64)
+        if init is None:
+            out = self.softmax(a, ident, slots, logits, beta=beta, want=with_prob)
+        else:
+            init = self._planes(init)
+            if tuple(init.shape) != (k, h, w):
+                raise ValueError("init must be [%d, %d, %d], got %s" % (k, h, w, tuple(init.shape)))
+            out = {"prob": init}
+        changes, converged = [], False
+        for _ in range(int(max_iter)):
+            prev = a
+            a = M @ (g[None, :] * self.project_wide(out["prob"], weight))
+            out = self.softmax(a, ident, slots, logits, beta=beta, want=with_prob)
+            changes.append(float(np.abs(a - prev).max()))
+            if changes[-1] <= float(tol) * float(np.abs(a).max()):
+                converged = True
+                break
+        if init is not None and not changes and want != ("prob",):
+            raise ValueError("mean_field: max_iter = 0 with init leaves nothing but init to return")
+        res = {key: out[key] for key in want}
+        res.update(coeffs=a, changes=np.array(changes), iterations=len(changes), converged=converged)
+        return res
 
     def propagate_labels(self, seeds, k, weight=None, smooth=0.0, ridge=0.0, bias=None, want=("label", "margin")):
         """Scribbles to a label map: the weighted least-squares fit of the k one-hot seed planes in the span of Phi (fit's system,

@@ -1174,9 +1174,9 @@ int glf_graph_samples(const glf_graph *g, unsigned *h_idx /* HOST [p], ascending
  * without one reads plane 0's pixel and drops it: the loads are unconditional so that they are all in flight together).
  * On a compact handle 2^e_c is folded into a_j[c] in f64 before its fl32 (glf_graph_synthesize's rule), so the scores are that
  * handle's own synthesize outputs bit for bit, and the call returns what it returns on an f32 handle whose Phi is Q.
- * Out of scope: softmax or temperature confidences, per-class counts, k > GLF_CLASSIFY_MAX and merging across groups, a label
- * input to the projection, mean-field or CRF iterations, contexts with a communicator and glf_multi_* (handles refuse them),
- * m > 256, a flag of the image_processing host program. */
+ * Out of scope: per-class counts, k > GLF_CLASSIFY_MAX and merging across groups, a label input to the projection, contexts with
+ * a communicator and glf_multi_* (handles refuse them), m > 256, a flag of the image_processing host program. (Softmax
+ * confidences and mean-field iterations: glf_graph_softmax below.) */
 #define GLF_CLASSIFY_MAX 32   /* = GLF_GRAPH_MAX_OUTPUTS */
 /* GLF_ERR_INVALID before any device work, every output untouched, the reason in glf_ctx_last_error: k outside 1 ..
  * GLF_CLASSIFY_MAX, a NULL h_a or plane, nplanes < 0, a plane[j] outside -1 .. nplanes - 1, an identity term with a NULL ident or
@@ -1186,6 +1186,57 @@ int glf_graph_classify(glf_graph *g, int k, const double *h_a /* HOST [k][m] */,
                        const int *plane /* HOST [k] */, int nplanes, const float *d_planes /* device [nplanes][N] */,
                        const double *h_bias /* HOST [k] or NULL */, int32_t *d_label /* device [N] or NULL */,
                        float *d_best /* device [N] or NULL */, float *d_margin /* device [N] or NULL */);
+
+/* ---- graph handle: softmax read-out, class probabilities, log-sum-exp and entropy of up to 32 score planes ---------------------------
+ * Where glf_graph_classify returns the winner, glf_graph_softmax returns how the k classes share a pixel: p_j = exp(beta score_j) /
+ * sum_i exp(beta score_i), the log-sum-exp lse = log sum_j exp(beta score_j) and the entropy -sum_j p_j ln p_j. Per-pixel class
+ * probabilities of graph-smoothed logits, an uncertainty map, the soft memberships of a set of centres and one mean-field step of a
+ * dense CRF end in this call. The scores are formed in registers in one pass over Phi (k_graph_softmax: k_graph_classify up to its
+ * scores) instead of being written by glf_graph_synthesize, read and rewritten by a softmax and read again for the entropy.
+ * Scores. h_a, ident, plane, nplanes, d_planes and h_bias mean what they mean in glf_graph_classify, and score_j is
+ * glf_graph_classify's score_j bit for bit: acc_j on v_mfma_f32_32x32x2_f32 in glf_graph_synthesize's contraction order, z_j =
+ * fmaf(ident[j], planes[plane[j]][px], acc_j) where plane[j] >= 0 and acc_j otherwise, then one f32 addition of fl32(bias_j) when
+ * h_bias is given. The scores are those of j < k: the slots j >= k are masked by index and never enter.
+ * Read-out, in f32, nothing contracted that is not written here. A lane holds the 16 scores j = (g & 3) + 8 (g >> 2) + 4 h, g < 16,
+ * of its pixel in half-wave h; "per lane" below runs over the lane's classes < k with g ascending, and "exchange" is one
+ * __shfl_xor(.., 32) with the lane that holds the pixel's other 16 classes.
+ *   best   b = -inf; per lane: if score_j > b then b = score_j; exchange: if b' > b then b = b'. (glf_graph_classify's best: a NaN
+ *          never enters.)
+ *   t_j    d_j = score_j - best (one subtraction); t_j = beta2 * d_j (one multiplication), beta2 = fl32(beta log2 e), the product
+ *          formed in f64 on the host.
+ *   e_j    v_exp_f32(t_j) (2^t at 1 ulp; a result below 2^-126 is flushed to +0).
+ *   S      per lane from +0: S = S + e_j; exchange: S = S + S'. (Both halves hold the same bits.)
+ *   A      per lane from +0: A = fmaf(e_j, e_j > 0 ? t_j : 0, A); exchange: A = A + A'. (sum_j e_j t_j with 0 * -inf read as 0: a
+ *          class at -inf, or flushed to e_j = +0, adds +0 or -0 and changes no bit. Formed only where d_entropy is given.)
+ *   p_j    r = 1 / S, one correctly rounded f32 division; p_j = e_j * r. Plane j of d_prob gets p_j.
+ *   lse    fmaf(fl32(ln 2), L, fl32(beta) * best), L = v_log_f32(S).
+ *   entropy  fl32(ln 2) * (L - A * r): one multiplication, one subtraction, one multiplication.
+ * Special values follow from these operations: a score of -inf beside a finite one gives e_j = p_j = +0 exactly; a pixel with a
+ * NaN score, a +inf score or nothing but -inf scores has S = NaN and every requested output NaN (all k probabilities, lse and
+ * entropy); no other pixel is affected. k = 1 gives p = 1, entropy +0 and lse = fl32(beta) * score (+ (+0)).
+ * Scaling the scores by a power of two and beta by its inverse changes no bit of p and entropy, short of under- and overflow.
+ * Error against the exact softmax of the same f32 scores, u = 2^-24, t*_j = beta log2 e (score_j - best) ("Softmax
+ * read-out"): eps_j = 2 u + 3 ln 2 |t*_j| u, eps_S = max over the classes with t*_i >= -126 of eps_i + 16 u;
+ * |p_j - p*_j| <= p*_j (eps_j + eps_S + 3 u) (1 + 2^-10) + 2^-126; lse and entropy: DESIGN.md.
+ * Two calls give the same bits; no atomics; rows past N are neither read nor stored; an output whose pointer is NULL is neither
+ * computed nor written, every pixel of the others is, and asking for fewer outputs changes no bit of the ones asked for. d_prob
+ * must not overlap d_planes (stated, not detected). Phi is read once at every ld, the identity planes as in glf_graph_classify.
+ * On a compact handle 2^e_c is folded into a_j[c] in f64 before its fl32 (glf_graph_synthesize's rule): the call returns what it
+ * returns on an f32 handle whose Phi is Q. There is no new host-only function, hence no make ..._check target.
+ * Out of scope: k > GLF_SOFTMAX_MAX and merging across groups, unit-length rows in soft memberships, subtracting the self-message
+ * of a mean-field step, a C driver for mean field (Graph.mean_field in glf.py drives glf_graph_project_wide and this call), fusing
+ * the re-projection of p into this pass, repairing the scale of Phi's sample rows, contexts with a communicator and glf_multi_*
+ * (handles refuse them), m > 256, a flag of the image_processing host program. */
+#define GLF_SOFTMAX_MAX 32   /* = GLF_GRAPH_MAX_OUTPUTS */
+/* GLF_ERR_INVALID before any device work, every output untouched, the reason in glf_ctx_last_error: everything
+ * glf_graph_classify refuses (k outside 1 .. GLF_SOFTMAX_MAX, a NULL h_a or plane, nplanes < 0, a plane[j] outside -1 ..
+ * nplanes - 1, an identity term with a NULL ident or d_planes, a coefficient (after folding) or a bias whose fl32 is not finite),
+ * all three output pointers NULL, a beta whose fl32 is not finite and positive or whose beta log2 e is not finite in f32; a NULL
+ * handle likewise (there is no context to take the reason). The planes are not checked. Returns with the stream drained. */
+int glf_graph_softmax(glf_graph *g, int k, const double *h_a /* HOST [k][m] */, const float *ident /* HOST [k] */,
+                      const int *plane /* HOST [k], -1: none */, int nplanes, const float *d_planes /* device [nplanes][N] */,
+                      const double *h_bias /* HOST [k] or NULL */, double beta, float *d_prob /* device [k][N] or NULL */,
+                      float *d_lse /* device [N] or NULL */, float *d_entropy /* device [N] or NULL */);
 
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
