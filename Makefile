@@ -13,7 +13,8 @@ HIP_SRCS := $(CSRC)/ctx.hip $(CSRC)/affinity.hip $(CSRC)/eigen.hip $(CSRC)/nystr
             $(CSRC)/filter.hip $(CSRC)/pipeline.hip $(CSRC)/comm.hip $(CSRC)/nlm.hip $(CSRC)/balance.hip \
             $(CSRC)/entrywise.hip $(CSRC)/graph.hip $(CSRC)/graph_fit.hip \
             $(CSRC)/graph_cluster.hip $(CSRC)/graph_basis.hip $(CSRC)/graph_robust.hip $(CSRC)/graph_project.hip $(CSRC)/graph_compact.hip \
-            $(CSRC)/graph_quad.hip $(CSRC)/graph_edges.hip $(CSRC)/graph_classify.hip $(CSRC)/graph_softmax.hip
+            $(CSRC)/graph_quad.hip $(CSRC)/graph_edges.hip $(CSRC)/graph_classify.hip $(CSRC)/graph_softmax.hip \
+            $(CSRC)/graph_blend.hip
 HIP_OBJS := $(HIP_SRCS:.hip=.o)
 CPP_OBJS := $(CSRC)/host_util.o
 C_OBJS   := $(HOST)/png_codec.o $(HOST)/pfm_codec.o

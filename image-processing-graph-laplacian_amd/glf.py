@@ -73,6 +73,7 @@ EXPORTS = [
     "glf_graph_edges", "glf_graph_samples",
     "glf_graph_classify",
     "glf_graph_softmax",
+    "glf_graph_blend",
     "glf_operator_create", "glf_operator_apply", "glf_operator_solve", "glf_operator_stored", "glf_operator_destroy",
     "glf_Nystroem_ex", "glf_Degree_ex", "glf_Filter_ex",
 ]
@@ -100,6 +101,7 @@ QUAD_MAX_CENTRES = 32      # GLF_QUAD_MAX_CENTRES: the most centres of one glf_g
 EDGE_DIRS = {"E": 1, "S": 2, "SE": 4, "SW": 8}   # GLF_EDGE_*: the neighbour (row, col+1), (row+1, col), (row+1, col+1), (row+1, col-1)
 CLASSIFY_MAX = 32          # GLF_CLASSIFY_MAX: the most classes of one glf_graph_classify call
 SOFTMAX_MAX = 32           # GLF_SOFTMAX_MAX: the most classes of one glf_graph_softmax call
+BLEND_MAX_SLOTS = 32       # GLF_BLEND_MAX_SLOTS: the most slots (outputs x levels) of one glf_graph_blend call
 CLUSTER_MAX = 32           # GLF_CLUSTER_MAX: the most centroids of glf_graph_cluster_step / glf_graph_segment
 PHI_F32, PHI_F16 = 0, 1    # GLF_PHI_*: how a graph handle stores Phi (glf_graph_compact)
 BASIS_CHOLESKY, BASIS_RITZ = 0, 1
@@ -292,6 +294,7 @@ _lib.glf_graph_edges.argtypes = [C.c_void_p, C.c_uint, C.c_uint, C.c_void_p, C.c
 _lib.glf_graph_samples.argtypes = [C.c_void_p, C.c_void_p]
 _lib.glf_graph_softmax.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
+_lib.glf_graph_blend.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 _lib.glf_graph_classify.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p]
 _lib.glf_operator_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_void_p]
@@ -2384,6 +2387,131 @@ class Graph:
         idn = np.repeat(np.broadcast_to(np.asarray(ident, dtype=np.float32), (nresp,)), nplanes)
         out = self._synthesize_groups(a, idn, np.tile(np.arange(nplanes, dtype=np.int32), nresp), planes)
         return out.view(nresp, nplanes, self.info["height"], self.info["width"])
+
+    def _level(self, level):
+        t = self.ctx.torch
+        h, w = self.info["height"], self.info["width"]
+        assert level.dtype == t.float32 and level.is_cuda and level.is_contiguous()
+        if tuple(level.shape) != (h, w):
+            raise ValueError("level must be [%d, %d], got %s" % (h, w, tuple(level.shape)))
+        self.ctx.stream.wait_stream(t.cuda.current_stream(self.ctx.device))   # the map is complete before the library reads it
+        return level
+
+    def blend(self, coeffs, level, ident=None, plane=None, planes=None, out=None):
+        """The per-pixel read-out of a bank of score planes z[o, b] = ident[o, b] * planes[plane[o, b]] + Phi coeffs[o, b] in one pass
+        over Phi (glf_graph_blend): the planes synthesize would write are formed in registers and never written. Output o gets
+        z[o, level(px)] where the level is an integer and (1 - f) z[o, i] + f z[o, i + 1] between two levels (i its integer part, f
+        the rest); a level below 0 or NaN reads level 0, one above nlevels - 1 the last. coeffs [nout, nlevels, m], or [nlevels, m]
+        for one output (nlevels in 2 .. BLEND_MAX_SLOTS); level device float32 [H, W], shared by the outputs; ident floats and plane
+        ints in [-1, nplanes) that broadcast to [nout, nlevels] (-1 / None: no identity term); planes device float32 [nplanes, H, W]
+        or None -> device float32 [nout, H, W] (out: a contiguous tensor of that shape to write into, overlapping neither planes nor
+        level). More outputs than BLEND_MAX_SLOTS // nlevels are taken in groups, each group one pass over Phi; an output's plane
+        does not depend on its group."""
+        t = self.ctx.torch
+        a = np.asarray(coeffs, dtype=np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        m, h, w = self.info["m"], self.info["height"], self.info["width"]
+        if a.ndim != 3 or a.shape[2] != m or a.shape[0] < 1:
+            raise ValueError("coeffs must be [nout, nlevels, %d] or [nlevels, %d], got %s" % (m, m, a.shape))
+        nout, nlevels = a.shape[:2]
+        if not 2 <= nlevels <= BLEND_MAX_SLOTS:
+            raise ValueError("blend takes 2 .. %d levels (BLEND_MAX_SLOTS), got %d" % (BLEND_MAX_SLOTS, nlevels))
+        a = np.ascontiguousarray(a)
+        try:
+            pl = np.full((nout, nlevels), -1, dtype=np.int32) if plane is None else np.ascontiguousarray(
+                np.broadcast_to(np.asarray(plane, dtype=np.int32), (nout, nlevels)))
+            idn = np.zeros((nout, nlevels), dtype=np.float32) if ident is None else np.ascontiguousarray(
+                np.broadcast_to(np.asarray(ident, dtype=np.float32), (nout, nlevels)))
+        except ValueError:
+            raise ValueError("ident and plane must broadcast to [%d, %d]" % (nout, nlevels))
+        level = self._level(level)
+        nplanes = 0
+        if planes is not None:
+            planes = self._planes(planes)
+            nplanes = planes.shape[0]
+        if out is None:
+            with t.cuda.stream(self.ctx.stream):
+                out = t.empty((nout, h, w), dtype=t.float32, device=self.ctx.device)   # (every element is written: no fill)
+        else:
+            assert out.dtype == t.float32 and out.is_cuda and out.is_contiguous()
+            if tuple(out.shape) != (nout, h, w):
+                raise ValueError("out must be [%d, %d, %d], got %s" % (nout, h, w, tuple(out.shape)))
+        per = BLEND_MAX_SLOTS // nlevels
+        for o0 in range(0, nout, per):
+            o1 = min(o0 + per, nout)
+            self.ctx._check(_lib.glf_graph_blend(self._g, C.c_int(o1 - o0), C.c_int(nlevels), _ptr(a[o0:o1]), _ptr(idn[o0:o1]), _ptr(pl[o0:o1]),
+                                                 C.c_int(nplanes), C.c_void_p(planes.data_ptr()) if planes is not None else None,
+                                                 C.c_void_p(level.data_ptr()), C.c_void_p(out.data_ptr() + 4 * h * w * o0)),
+                            "graph blend")   # (returns with the stream drained)
+        return out
+
+    def apply_local(self, planes, level, weights, ident=1.0):
+        """apply with a strength that varies over the image: out_k(px) = the level(px) read-out of the bank ident[b] * s_k + Phi
+        diag(weights[b]) Phi^T s_k, b < B -- a sensor's noise map, a brush mask, depth-dependent blur. weights [B, m], a bank of
+        responses ordered by strength (exp(-t_b lam), 1 / (1 + t_b lam), a gain ladder; B in 2 .. BLEND_MAX_SLOTS), ident a float or
+        [B]; level device float32 [H, W] in units of the bank index (a strength in [0, 1] is level = strength * (B - 1)): an
+        integer level b gives apply's output for response b, bit for bit, and a level between two integers their linear blend.
+        One project_wide, the scaling on the host, one blend with the planes as identity planes (a pass over Phi per
+        BLEND_MAX_SLOTS // B planes) -> device float32 [nplanes, H, W]."""
+        wts = np.asarray(weights, dtype=np.float64)
+        m = self.info["m"]
+        if wts.ndim != 2 or wts.shape[1] != m or not 2 <= wts.shape[0] <= BLEND_MAX_SLOTS:
+            raise ValueError("weights must be [B, %d] with B in 2 .. %d (BLEND_MAX_SLOTS), got %s" % (m, BLEND_MAX_SLOTS, wts.shape))
+        nplanes = planes.shape[0]
+        c = self.project_wide(planes)
+        a = wts[None, :, :] * c[:, None, :]
+        idn = np.broadcast_to(np.asarray(ident, dtype=np.float32), (wts.shape[0],))
+        return self.blend(a, level, idn[None, :], np.arange(nplanes, dtype=np.int32)[:, None], planes)
+
+    def gather(self, coeffs, labels, out=None):
+        """The piecewise render out(px) = Phi[px] . coeffs[labels(px)] in one pass over Phi: blend with the labels as the level map.
+        coeffs [k, m], 2 <= k <= BLEND_MAX_SLOTS; labels device int32 [H, W] (segment's, classify's), converted to float32; a label
+        below 0 reads row 0, one above k - 1 the last -> device float32 [H, W] (out: a contiguous tensor of that shape to write into)."""
+        a = np.asarray(coeffs, dtype=np.float64)
+        if a.ndim != 2 or not 2 <= a.shape[0] <= BLEND_MAX_SLOTS:
+            raise ValueError("coeffs must be [k, %d] with k in 2 .. %d (BLEND_MAX_SLOTS), got %s" % (self.info["m"], BLEND_MAX_SLOTS, a.shape))
+        t = self.ctx.torch
+        labels = self._labels(labels, "labels")
+        with t.cuda.stream(self.ctx.stream):
+            level = labels.to(t.float32)
+        return self.blend(a, level, out=None if out is None else out[None])[0]
+
+    def fit_piecewise(self, planes, labels, k, weight=None, smooth=0.0, ridge=0.0):
+        """One fit per segment, rendered piecewise: for every label j < k, fit's system under the weight w * (labels == j) (one
+        normal_equations -- beyond 4 planes normal_equations and project_wide, as in fit -- and fit_coeffs under fit's penalty rule),
+        then one gather per plane. planes device float32 [nplanes, H, W], labels device int32 [H, W], 2 <= k <= BLEND_MAX_SLOTS,
+        weight device float32 [H, W] or None. A label whose system is refused (an empty segment) keeps zero coefficients.
+        -> (device float32 [nplanes, H, W], coefficients numpy [nplanes, k, m])."""
+        t = self.ctx.torch
+        k = int(k)
+        if not 2 <= k <= BLEND_MAX_SLOTS:
+            raise ValueError("fit_piecewise takes 2 .. %d segments (BLEND_MAX_SLOTS), got %d" % (BLEND_MAX_SLOTS, k))
+        planes = self._planes(planes)
+        labels = self._labels(labels, "labels")
+        if weight is not None:
+            weight = self._weight(weight)
+        nplanes, m = planes.shape[0], self.info["m"]
+        a = np.zeros((nplanes, k, m), dtype=np.float64)
+        for j in range(k):
+            with t.cuda.stream(self.ctx.stream):
+                wj = (labels == j).to(t.float32)
+                if weight is not None:
+                    wj = wj * weight
+            if nplanes > MAX_SIGNALS:
+                G = self.normal_equations(wj)[0]
+                b = self.project_wide(planes, wj)
+            else:
+                G, b = self.normal_equations(wj, planes)
+            try:
+                a[:, j, :] = fit_coeffs(G, b, (float(ridge) + float(smooth) * self.eigenvalues) * (np.trace(G) / m))
+            except GlfError:
+                pass
+        with t.cuda.stream(self.ctx.stream):
+            out = t.empty((nplanes, self.info["height"], self.info["width"]), dtype=t.float32, device=self.ctx.device)
+        for p in range(nplanes):
+            self.gather(a[p], labels, out=out[p])
+        return out, a
 
 
 @functools.lru_cache(maxsize=256)

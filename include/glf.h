@@ -1238,6 +1238,56 @@ int glf_graph_softmax(glf_graph *g, int k, const double *h_a /* HOST [k][m] */, 
                       const double *h_bias /* HOST [k] or NULL */, double beta, float *d_prob /* device [k][N] or NULL */,
                       float *d_lse /* device [N] or NULL */, float *d_entropy /* device [N] or NULL */);
 
+/* ---- graph handle: blend read-out, a bank of up to 32 score planes read out per pixel by a level map -----------------------------------
+ * Every filtering call on a handle applies one response to the whole image. "Denoise more here than there" -- a sensor's noise-level
+ * map, a brush mask, depth-dependent blur, foveation, a confidence map -- needs a strength per pixel, and rendering per-segment models
+ * a_j needs out(px) = Phi[px] . a_label(px). Both are one operation: form a small bank of score planes z_b = ident_b s + Phi a_b and
+ * read out, per pixel, the plane that a map selects, or the linear blend of its two neighbours. glf_graph_blend forms the bank in
+ * registers in one pass over Phi (k_graph_blend: k_graph_classify up to its scores) and writes the nout read-outs, instead of the
+ * nout * nlevels planes a caller would write with glf_graph_synthesize and read back for a gather and a lerp.
+ * Slots. The bank holds nout outputs of nlevels levels each, slot s = o * nlevels + b, nout * nlevels <= GLF_BLEND_MAX_SLOTS; one level
+ * map d_level serves all outputs of a call. h_a, ident, plane, nplanes and d_planes mean per slot what they mean per output in
+ * glf_graph_synthesize: acc_s = sum_c Phi[px][c] fl32(a_s[c]) on v_mfma_f32_32x32x2_f32 in its contraction order, with
+ * glf_graph_synthesize's bits for coefficient row s.
+ * Read-out per pixel px, in f32, nothing contracted that is not written here:
+ *   t   = d_level[px]
+ *   tc  = fminf(fmaxf(t, 0), (float)(nlevels - 1))      a NaN level reads as level 0; -inf and +inf clamp to the two ends
+ *   i   = min((int)tc, nlevels - 2)                     (truncation)
+ *   f   = tc - (float)i                                 exact (Sterbenz); 0 <= f <= 1, and f = 1 only at tc = nlevels - 1
+ *   for output o: lo = o * nlevels + i, hi = lo + 1
+ *   z_s = plane[s] >= 0 ? fmaf(ident[s], planes[plane[s]][px], acc_s) : acc_s    for s in {lo, hi} only: glf_graph_synthesize's
+ *         output for slot s, bit for bit
+ *   out_o[px] = f == 0 ? z_lo : f == 1 ? z_hi : fmaf(f, z_hi, fmaf(-f, z_lo, z_lo))
+ * The two scores are chosen by their index (selects), never by arithmetic over the bank: a slot that a pixel does not take with a
+ * weight other than zero cannot reach that pixel's output, whatever it holds (NaN, Inf) -- at an integer level the output is the
+ * level's plane bit for bit, and levels appended above the map's maximum change no bit. An output depends neither on nout nor on the
+ * outputs beside it. How the kernel gets there: a lane holds the 16 slots (g & 3) + 8 (g >> 2) + 4 h, g < 16, of its pixel in
+ * half-wave h (slot s lives in half (s >> 2) & 1); the wave writes its accumulators to its own LDS image as [pixel][slot] and every
+ * read-out is two indexed reads of the pixel's row (tests/blend_ref.py restates the ownership, the index rule and the lerp).
+ * Error against exact arithmetic on the handle's own Phi with the same f32 level (hence the same i and f), u = 2^-24 (DESIGN.md,
+ * "Blend read-out"): |out - out*| <= (1 - f) e_lo + f e_hi + 2 u (1 + u) ((1 - f) (|z*_lo| + e_lo) + f (|z*_hi| + e_hi)), e_s =
+ * (ld + 4) u (|ident_s s| + |Phi| |a_s|) being glf_graph_synthesize's bound, short of underflow.
+ * Two calls give the same bits; no atomics; rows past N are neither read nor stored, d_level[px] is read for px < N only; every
+ * pixel of the nout planes of d_out is written. d_out must not overlap d_planes or d_level (stated, not detected). Phi is read once
+ * at every ld, the level map once, and where any slot has an identity term two plane values per output and pixel (a slot without a
+ * term reads plane 0's pixel and drops it).
+ * On a compact handle 2^e_c is folded into a_s[c] in f64 before its fl32 (glf_graph_synthesize's rule): the call returns what it
+ * returns on an f32 handle whose Phi is Q. There is no new host-only function, hence no make ..._check target.
+ * Out of scope: per-output level maps, more than GLF_BLEND_MAX_SLOTS slots per launch (Graph.blend in glf.py groups by outputs),
+ * non-linear interpolation between levels, a derivative with respect to the level, evaluating a response per pixel and column
+ * instead of a bank, general per-pixel mixture weights over all levels, an int32 label input (Graph.gather converts), a C driver for
+ * a piecewise fit (Graph.fit_piecewise drives glf_graph_normal_equations and this call), contexts with a communicator and
+ * glf_multi_* (handles refuse them), m > 256, a flag of the image_processing host program. */
+#define GLF_BLEND_MAX_SLOTS 32   /* = GLF_GRAPH_MAX_OUTPUTS */
+/* GLF_ERR_INVALID before any device work, d_out untouched, the reason in glf_ctx_last_error: nout < 1, nlevels < 2 or nout * nlevels >
+ * GLF_BLEND_MAX_SLOTS, a NULL h_a or plane, nplanes < 0, a NULL d_level or d_out, a plane[s] outside -1 .. nplanes - 1, an identity
+ * term with a NULL ident or d_planes, a coefficient (after folding) whose fl32 is not finite; a NULL handle likewise (there is no
+ * context to take the reason). The planes and the level map are not checked. Returns with the stream drained. */
+int glf_graph_blend(glf_graph *g, int nout, int nlevels, const double *h_a /* HOST [nout * nlevels][m], slot = o * nlevels + b */,
+                    const float *ident /* HOST [nout * nlevels] or NULL */, const int *plane /* HOST [nout * nlevels], -1: none */,
+                    int nplanes, const float *d_planes /* device [nplanes][N] or NULL */, const float *d_level /* device [N] */,
+                    float *d_out /* device [nout][N] */);
+
 /* Throughput mode for a batch of equally sized tiles (BASELINE.json configs[4]: "batch of 64 x 1024x1024 noisy tiles
  * sharing one sample set"; hpc/sampling.c:6-23 gives tiles of one size the same sample grid). The reference would run its
  * main once per tile (hpc/image_processing.c:279-335); here tile t = d_imgs + t*width*height goes through
